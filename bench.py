@@ -10,6 +10,16 @@ each rank scores 2^20 candidates of every active hyperparameter, total
 C = N * 2^20, per-level winner combined by one all-gather (dist.py).
 
 value  = sum over steps of (active hyperparameters x total candidates) / time
+
+A plain run (``bench.py --gpus 1 --steps N --warmup W``) sets up, warms up,
+times the N steps and prints the result line of those steps.  ``--full`` adds
+every other measurement below to the line, each in passes of its own after
+the timed steps.  ``--dump-outputs DIR`` writes what the last timed step
+returned as DIR/values.npy (float64 [n_ids x n_labels], the space's labels in
+table order, 0 where inactive), DIR/active.npy (float32 mask) and, for
+document results, DIR/tids.npy; histories and seeds are fixed, so two builds
+run with the same arguments can be compared array for array.
+
 roofline: the dominant stage by device time (k_sample_tab on config 3),
           timed per launch with HIP events the level runner records on its own
           stream (tpe_level_profile), priced by the ALGORITHMIC VALU work of its
@@ -471,8 +481,10 @@ def mixed10_history(n, seed):
 
 
 def config_workload(config, rank, world, args):
-    """(description, setup info, step(i) -> candidate-scores, cpu_baseline_fn or None)"""
+    """(description, step(i) -> candidate-scores, outputs() -> the last step's
+    result as {name: array}, for --dump-outputs)"""
     from hyperopt_amd import base, hp, rand, tpe
+    last = {}                      # the last step's result, as the step's caller receives it
     if config == 1:
         from hyperopt_amd import Trials, fmin
 
@@ -480,8 +492,16 @@ def config_workload(config, rank, world, args):
             t = Trials()
             fmin(lambda x: (x - 3) ** 2, hp.uniform('x', -10, 10), algo=tpe.suggest, max_evals=100, trials=t,
                  rstate=np.random.RandomState(i))
+            last['out'] = t
             return 80 * 24        # 80 TPE suggests (after 20 start-up) x 24 candidates
-        return 'config1: fmin(tpe.suggest), hp.uniform 1-D quadratic, 100 trials, n_EI_candidates=24', step, None
+
+        def outputs():
+            # the trials fmin filled: every trial's x and loss, in tid order
+            t = last['out']
+            return dict(values=np.array([[d['misc']['vals']['x'][0]] for d in t.trials], dtype=np.float64),
+                        losses=np.array(t.losses(), dtype=np.float64))
+        return ('config1: fmin(tpe.suggest), hp.uniform 1-D quadratic, 100 trials, n_EI_candidates=24', step,
+                outputs)
     if config == 2:
         domain, trials = mixed10_history(1000, SEED)
         C = 10000
@@ -489,8 +509,10 @@ def config_workload(config, rank, world, args):
         def step(i):
             docs = tpe.suggest([1000], domain, trials, SEED + i, n_EI_candidates=C * world,
                                shard=(rank, world) if world > 1 else None)
+            last['out'] = docs
             return sum(1 for v in docs[0]['misc']['vals'].values() if v) * C * world
-        return 'config2: 10-dim mixed space, 1000-trial history, n_EI_candidates=10000', step, None
+        return ('config2: 10-dim mixed space, 1000-trial history, n_EI_candidates=10000', step,
+                lambda: doc_arrays(domain.table, last['out']))
     if config == 4:
         labels = ['x%02d' % i for i in range(20)]
         hist = soa_history(labels, 10000, SEED, lambda v: sum((x - 0.3) ** 2 for x in v.values()))
@@ -509,12 +531,12 @@ def config_workload(config, rank, world, args):
 
         def step(i, columns=True):
             # SoA in, SoA out (tpe.ChoiceColumns); columns=False: per-id dicts
-            tpe.suggest_choices(table, hist, ids, SEED + i, n_EI_candidates=C, columns=columns, **kw)
+            last['out'] = tpe.suggest_choices(table, hist, ids, SEED + i, n_EI_candidates=C, columns=columns, **kw)
             return len(labels) * n_ids * C          # whole job
         what = dict(grid='(label group x id block) grid', labels='hyperparameters', ids='new_ids')[axis]
         return ('config4: batched suggest, 4096 new_ids x 4096 candidates, 20-dim U(-5,5), 10k-trial '
                 'history, %s sharded over ranks + one all-gather of the chosen values, columnar results'
-                % what), step, None
+                % what), step, lambda: choice_arrays(table, last['out'])
     if config == 5 and args.appending:
         # FMinIter's flow on the columnar history (fmin.py:88-92): every suggest
         # follows the evaluation of the previous one, appended as one observation
@@ -550,9 +572,11 @@ def config_workload(config, rank, world, args):
             vals2d[state['ri'], n] = cc.values[0]    # the suggestion, evaluated (synthetic loss)
             losses[n] = rl.uniform() + 1e-9 * n
             state['n'] = n + 1
+            last['out'] = cc
             return D * C
         return ('config5 appending: %d-dim U(-5,5), %d-trial history growing by one evaluated suggestion per '
-                'step (FMinIter flow), n_EI_candidates=4096' % (D, N)), step, None
+                'step (FMinIter flow), n_EI_candidates=4096' % (D, N)), step, \
+            lambda: choice_arrays(table, last['out'])
     if config == 5:
         D, N, C = args.dims, args.history5, 4096
         labels = ['x%04d' % i for i in range(D)]
@@ -565,10 +589,11 @@ def config_workload(config, rank, world, args):
         def step(i):
             # N > 1: each rank fits and scores its labels (dist.label_owners), one
             # all-gather of the chosen values — every rank holds the whole suggestion
-            tpe.suggest_choices(table, hist, [N], SEED + i, n_EI_candidates=C, shard_labels=sid)
+            last['out'] = tpe.suggest_choices(table, hist, [N], SEED + i, n_EI_candidates=C, shard_labels=sid)
             return D * C
         return ('config5: %d-dim U(-5,5), %d-trial history, n_EI_candidates=4096, hyperparameters sharded '
-                'over ranks + one all-gather of the chosen values' % (D, N)), step, None
+                'over ranks + one all-gather of the chosen values' % (D, N)), step, \
+            lambda: choice_arrays(table, last['out'])
     raise ValueError(config)
 
 
@@ -578,6 +603,13 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=50)
     ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also measure everything beside the headline figure: the CPU '
+                         'baseline, the roofline and per-stage times, the tail record, the quantized branch, the '
+                         'appending loop, config 4, strong scaling and the per-rank report (the --no-* options '
+                         'drop single parts of it)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned to DIR/<name>.npy (see dump_outputs)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-quantized', action='store_true', help='skip the rf-branch (quantized) report')
     ap.add_argument('--no-appending', action='store_true', help='skip the FMinIter-style appending loop')
@@ -605,7 +637,7 @@ def main():
         pre = make_history(args.history, SEED)
         # the CPU baseline's process, forked before anything initialises the GPU
         # (its process pools fork), run after the GPU measurements; rank 0 at N = 1 only
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu_child = CpuBaselineChild(pre)
     try:
         main_gpu(args, world, rank, local, pre, cpu_child)
@@ -677,6 +709,15 @@ def main_gpu(args, world, rank, local, pre, cpu_child):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     value = n_active * C_total / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, doc_arrays(domain.table, docs))
+    if not args.full:
+        # a plain run: the headline figure alone
+        if rank == 0:
+            print(json.dumps(headline_line(args, world, value, elapsed, lat, n_active, C_total)))
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # strong scaling: the BASELINE 2^20 candidates in total, split over the ranks
     strong = None
@@ -801,23 +842,12 @@ def main_gpu(args, world, rank, local, pre, cpu_child):
     if cpu_child is not None:
         cpu = cpu_child.result()          # (after every GPU measurement of the line)
     if rank == 0:
-        out = {
-            'metric': 'EI candidates scored/sec (node) + tpe.suggest p50 latency, 1M cands x 10k trials',
-            'value': value, 'unit': 'candidate-scores/s', 'n_gpus': world, 'steps': args.steps,
-            'warmup': args.warmup, 'ms_per_step': 1e3 * elapsed / args.steps, 'higher_is_better': True,
-            'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
-            'config': {'workload': 'config3: conditional hp.choice tree, %d-trial history, '
-                                   'n_EI_candidates=%d per GPU (%d total), one tpe.suggest per step'
-                                   % (args.history, args.cands, C_total),
-                       'history': args.history, 'n_EI_candidates': C_total,
-                       'parallelism': 'candidate-shard x%d' % world},
-            'p50_suggest_ms': 1e3 * float(np.median(lat)), 'p99_suggest_ms': 1e3 * float(np.percentile(lat, 99)),
-            'mean_suggest_ms': 1e3 * float(np.mean(lat)),
+        out = headline_line(args, world, value, elapsed, lat, n_active, C_total)
+        out.update({
             'tail': tail,
             'ranks': ranks,
             'p50_suggest_ms_appending': appending['p50_suggest_ms'] if appending else None,
             'appending': appending,
-            'active_hyperparameters_per_suggest': n_active / args.steps,
             'stage_ms': stages, 'roofline': roof, 'kernels': kernels, 'cpu_baseline': cpu,
             'quantized_branch': quant,
             'config4_strong': cfg4,
@@ -826,12 +856,78 @@ def main_gpu(args, world, rank, local, pre, cpu_child):
                 n_EI_candidates_total=C_total, per_rank=C_total, value=value, unit='candidate-scores/s',
                 ms_per_step=1e3 * elapsed / args.steps, p50_suggest_ms=1e3 * float(np.median(lat)),
                 p99_suggest_ms=1e3 * float(np.percentile(lat, 99))),
-        }
+        })
         if cpu:
             out['speedup_vs_cpu_baseline'] = value / cpu['value']
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()
+
+
+def headline_line(args, world, value, elapsed, lat, n_active, C_total):
+    """The result line of the config-3 timed steps (a plain run prints it as it
+    is; --full adds its other measurements to it)."""
+    return {
+        'metric': 'EI candidates scored/sec (node) + tpe.suggest p50 latency, 1M cands x 10k trials',
+        'value': value, 'unit': 'candidate-scores/s', 'n_gpus': world, 'steps': args.steps,
+        'warmup': args.warmup, 'ms_per_step': 1e3 * elapsed / args.steps, 'higher_is_better': True,
+        'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic', 'full': bool(args.full),
+        'config': {'workload': 'config3: conditional hp.choice tree, %d-trial history, '
+                               'n_EI_candidates=%d per GPU (%d total), one tpe.suggest per step'
+                               % (args.history, args.cands, C_total),
+                   'history': args.history, 'n_EI_candidates': C_total,
+                   'parallelism': 'candidate-shard x%d' % world},
+        'p50_suggest_ms': 1e3 * float(np.median(lat)), 'p99_suggest_ms': 1e3 * float(np.percentile(lat, 99)),
+        'mean_suggest_ms': 1e3 * float(np.mean(lat)),
+        'active_hyperparameters_per_suggest': n_active / args.steps,
+    }
+
+
+# ------------------------------------------------------------- --dump-outputs
+DUMP_MAX_BYTES = 64 << 20
+
+
+def doc_arrays(table, docs):
+    """A suggest's documents as arrays: ``values`` float64 [n_docs x n_labels]
+    (columns in ``table.labels`` order; a categorical label's index as a float,
+    0 where the label is inactive), ``active`` float32 of the same shape (1
+    where the document holds a value) and ``tids`` float64 [n_docs]."""
+    labels = list(table.labels)
+    values = np.zeros((len(docs), len(labels)))
+    active = np.zeros((len(docs), len(labels)), dtype=np.float32)
+    for j, d in enumerate(docs):
+        for i, k in enumerate(labels):
+            v = d['misc']['vals'].get(k)
+            if v is not None and len(v):
+                values[j, i], active[j, i] = float(v[0]), 1.0
+    return dict(values=values, active=active, tids=np.array([d['tid'] for d in docs], dtype=np.float64))
+
+
+def choice_arrays(table, choices):
+    """suggest_choices' result (a ChoiceColumns or per-id {label: value or
+    None} dicts) as the ``values`` / ``active`` arrays of doc_arrays."""
+    from hyperopt_amd import tpe
+    cc = choices if isinstance(choices, tpe.ChoiceColumns) else tpe.ChoiceColumns.from_dicts(table, choices)
+    col = [cc.labels.index(k) for k in table.labels]
+    active = np.asarray(cc.active)[:, col] != 0
+    values = np.where(active, np.asarray(cc.values, dtype=np.float64)[:, col], 0.0)
+    return dict(values=values, active=active.astype(np.float32))
+
+
+def dump_outputs(path, arrays):
+    """Write {name: array} as path/<name>.npy, float32 and float64 as they are
+    and anything else as float64.  Above DUMP_MAX_BYTES in all, every array
+    keeps a fixed sample of its leading axis (RandomState(SEED), sorted rows)
+    that fits its share of the limit."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(a if a.dtype in (np.float32, np.float64) else a.astype(np.float64))
+              for k, a in ((k, np.asarray(a)) for k, a in arrays.items())}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in sorted(arrays.items()):
+        if total > DUMP_MAX_BYTES and a.ndim and len(a) > 1:
+            keep = max(1, int(len(a) * DUMP_MAX_BYTES / total))
+            a = a[np.sort(np.random.RandomState(SEED).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(path, name + '.npy'), a)
 
 
 _GC_COUNT = {}
@@ -956,7 +1052,7 @@ def run_other(args, rank, world, device):
     """Configs 1, 2, 4, 5: same timing discipline, own metric line."""
     import torch
     import torch.distributed as dist
-    desc, step, _ = config_workload(args.config, rank, world, args)
+    desc, step, outputs = config_workload(args.config, rank, world, args)
 
     def barrier():
         if world > 1:
@@ -982,6 +1078,22 @@ def run_other(args, rank, world, device):
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs())
+    line = {'metric': 'EI candidates scored/sec (node)', 'value': units * args.steps / elapsed,
+            'unit': 'candidate-scores/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
+            'ms_per_step': 1e3 * elapsed / args.steps, 'higher_is_better': True,
+            'scaling': 'strong' if args.config in (4, 5) else 'weak', 'vs_baseline': None, 'dtype': 'f32',
+            'data': 'synthetic', 'full': bool(args.full),
+            'config': {'workload': desc, 'config': args.config, 'appending': bool(args.appending)},
+            'p50_step_ms': 1e3 * float(np.median(lat))}
+    if not args.full:
+        # a plain run: the timed steps' figure alone
+        if rank == 0:
+            print(json.dumps(line))
+        if world > 1:
+            dist.destroy_process_group()
+        return
     # per-stage device time of one more step (HIP events on the launch stream)
     from hyperopt_amd import engine as engine_mod
     eng = engine_mod._ENGINES[str(device)]
@@ -1009,13 +1121,7 @@ def run_other(args, rank, world, device):
             lat_d.append(time.perf_counter() - s0)
         extra['p50_step_ms_dict_results'] = 1e3 * float(np.median(lat_d))
     if rank == 0:
-        out = {'metric': 'EI candidates scored/sec (node)', 'value': units * args.steps / elapsed,
-               'unit': 'candidate-scores/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
-               'ms_per_step': 1e3 * elapsed / args.steps, 'higher_is_better': True,
-               'scaling': 'strong' if args.config in (4, 5) else 'weak', 'vs_baseline': None, 'dtype': 'f32',
-               'data': 'synthetic', 'config': {'workload': desc, 'config': args.config,
-                                               'appending': bool(args.appending)},
-               'p50_step_ms': 1e3 * float(np.median(lat)), 'stage_ms_per_step': stages}
+        out = dict(line, stage_ms_per_step=stages)
         out.update(extra)
         print(json.dumps(out))
     if world > 1:

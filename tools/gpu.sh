@@ -6,12 +6,12 @@
 #
 #   tests      -m gpu parity suite                       (PYTEST_ARGS; PYTEST_K = one -k expression)
 #   smoke      __graft_entry__.smoke()
-#   bench      headline bench.py                         (BENCH_ARGS)
+#   bench      headline bench.py --full                  (BENCH_ARGS)
 #   trace      rocprofv3 --kernel-trace --stats of a short headline bench run (BENCH_ARGS)
 #   pmc        PMC counter passes on the headline bench, one rocprofv3 run per group
 #   stage      steady-state per-stage device times        (REP)
-#   configs    bench.py --config 1, 2, 4, 5 (CONFIGS)
-#   rehearse   bench.py --gpus 2 over gloo, two ranks on the one GPU (REH_CONFIGS)
+#   configs    bench.py --full --config 1, 2, 4, 5 (CONFIGS)
+#   rehearse   bench.py --full --gpus 2 over gloo, two ranks on the one GPU (REH_CONFIGS)
 #   hostsplit  host-side time split of the headline suggest
 #   phases     tools/phase_prof.py per workload (PHASE_WL) under the kernel trace
 #   nativesplit native fits / tpe_suggest_tree / device stages of the headline suggest
@@ -58,7 +58,7 @@ for task in "$@"; do
       step 300 $O/smoke_${TAG}.log python -c "import __graft_entry__ as g; g.smoke()"
       tail -3 $O/smoke_${TAG}.log ;;
     bench)
-      step 600 $O/bench_${TAG}.err python bench.py ${BENCH_ARGS:-}
+      step 600 $O/bench_${TAG}.err python bench.py --full ${BENCH_ARGS:-}
       grep '^{' $O/bench_${TAG}.err > $O/bench_${TAG}.json; cat $O/bench_${TAG}.json ;;
     trace)
       rm -rf $O/trace_${TAG}
@@ -80,7 +80,7 @@ for task in "$@"; do
       cat $O/stage_${TAG}.txt ;;
     configs)
       for c in ${CONFIGS:-1 2 4 5}; do
-        step 600 $O/cfg${c}_${TAG}.err python bench.py --config $c --steps ${CFG_STEPS:-5} --warmup 1
+        step 600 $O/cfg${c}_${TAG}.err python bench.py --full --config $c --steps ${CFG_STEPS:-5} --warmup 1
         grep '^{' $O/cfg${c}_${TAG}.err > $O/cfg${c}_${TAG}.json; cat $O/cfg${c}_${TAG}.json
       done ;;
     envab)
@@ -89,7 +89,7 @@ for task in "$@"; do
       for v in ${ENVAB:-default}; do
         if [ "$v" = default ]; then e=""; else e="$v"; fi
         step 300 $O/stage_${TAG}_$v.txt env $e python tools/stage_bench.py ${REP:-20}
-        step 300 $O/bench_${TAG}_$v.err env $e python bench.py --no-cpu-baseline --no-quantized --no-config4 --steps 100
+        step 300 $O/bench_${TAG}_$v.err env $e python bench.py --full --no-cpu-baseline --no-quantized --no-config4 --steps 100
         echo "$v: $(grep -o '"p50_suggest_ms": [0-9.]*\|"stage_ms": {[^}]*}' $O/bench_${TAG}_$v.err | tr '\n' ' ')"
         grep -i "k_sample\|k_tables" $O/stage_${TAG}_$v.txt | head -4
       done ;;
@@ -97,7 +97,7 @@ for task in "$@"; do
       # the N > 1 flow with 2 ranks on the box's one GPU (gloo: RCCL takes one rank per device)
       for c in ${REH_CONFIGS:-3 4 5}; do
         step 600 $O/rehearse${c}_${TAG}.err env TPE_BENCH_BACKEND=gloo python -m torch.distributed.run --nnodes=1 \
-            --nproc-per-node 2 --master-addr 127.0.0.1 --master-port $((29500 + c)) bench.py --gpus 2 --config $c \
+            --nproc-per-node 2 --master-addr 127.0.0.1 --master-port $((29500 + c)) bench.py --full --gpus 2 --config $c \
             --steps ${CFG_STEPS:-5} --warmup 2 --no-cpu-baseline --no-quantized --no-appending
         grep '^{' $O/rehearse${c}_${TAG}.err > $O/rehearse${c}_${TAG}.json; cat $O/rehearse${c}_${TAG}.json
       done ;;
@@ -105,7 +105,7 @@ for task in "$@"; do
       # config 5 appending: cProfile of its steps, then the bench line
       step 300 $O/cfg5_app_prof_${TAG}.txt python tools/cfg5_app_prof.py ${STEPS:-8}
       head -30 $O/cfg5_app_prof_${TAG}.txt
-      step 600 $O/cfg5app_${TAG}.err python bench.py --config 5 --appending --steps ${CFG_STEPS:-20} --warmup 2
+      step 600 $O/cfg5app_${TAG}.err python bench.py --full --config 5 --appending --steps ${CFG_STEPS:-20} --warmup 2
       grep '^{' $O/cfg5app_${TAG}.err > $O/cfg5app_${TAG}.json; cat $O/cfg5app_${TAG}.json ;;
     trace5)
       # kernel trace of config 5 (APP5=--appending: the FMinIter flow)
@@ -148,7 +148,7 @@ for task in "$@"; do
       for v in ${LIBS:-default}; do
         if [ "$v" = default ]; then lib=$PWD/hyperopt_amd/libtpe_hip.so; else lib=$PWD/hyperopt_amd/libtpe_hip_$v.so; fi
         step 300 $O/stage_${TAG}_$v.txt env TPE_HIP_LIB=$lib python tools/stage_bench.py ${REP:-20}
-        step 300 $O/bench_${TAG}_$v.err env TPE_HIP_LIB=$lib python bench.py --no-cpu-baseline --no-quantized --no-config4 --steps ${AB_STEPS:-200}
+        step 300 $O/bench_${TAG}_$v.err env TPE_HIP_LIB=$lib python bench.py --full --no-cpu-baseline --no-quantized --no-config4 --steps ${AB_STEPS:-200}
         echo "$v: $(grep -o '"p50_suggest_ms": [0-9.]*\|"stage_ms": {[^}]*}' $O/bench_${TAG}_$v.err | tr '\n' ' ')"
         step 120 $O/phab_${TAG}_$v.txt env TPE_HIP_LIB=$lib python tools/phase_prof.py svm 300
         grep "p50\|phases" $O/phab_${TAG}_$v.txt
