@@ -419,7 +419,75 @@ inline int64_t fill_chunk_min_level() {
 }
 struct ChunkTask { int32_t li, side; int64_t i0, i1; int64_t scr; };
 
+// one label of the level being packed: what the plan decides about it
+struct LabelPlan {
+  char dev_fit = 0;                     // above mixture fitted on the device
+  char logpoly = 0;                     // TPE_F_LOGPOLY rows
+  char pruned = 0, pooled = 0;          // candidates sorted; ... as one population over its ids
+  int32_t tmode = TPE_TAB_NONE;         // table mode and geometry (decide_table)
+  int64_t n0 = 0, n1 = 0, lat_lo = 0, boxes = 0;
+  double klo = 0, khi = 0;
+  // section offsets (rows of samp / comp64 / comp32, entries of grid; -1: none)
+  int64_t samp = 0, c64[2] = {-1, -1}, c32[2] = {-1, -1}, wide = -1, grid = -1;
+};
+
+constexpr int kPackTile = 2048;        // candidates per tile
+
+// the blob's leading sections (PackLevel.off_lead / len_lead)
+enum { L_FIT, L_BIDX, L_FSEG, L_GRID, L_C32, L_PATCH, L_PROB, L_TILES, L_C64, L_SAMP, NL };
+
+// the level being packed: the arguments, the level's scalars and the fill's
+// targets — what the packer's steps and their per-label tasks share.  The plan
+// (tpe_internal_pack_plan) sets everything down to the targets; the fill reads it.
+struct PackLevel {
+  // ---- arguments ----
+  const tpe_label_in* labels;
+  int32_t n_labels, n_cand;
+  uint64_t seed;
+  int64_t cand_base, C_ref;             // C_ref: the global candidate count
+  bool f64;
+  unsigned char* bb;                    // the blob
+  int64_t blob_cap;
+  // ---- level scalars ----
+  int64_t P, n_tiles_p;                 // problems, tiles per problem
+  int key_bits, sort_end_bit;
+  int64_t S, n_sorted_prob, n_pooled;   // sort slots, sorted problems, pooled problems
+  bool expand;
+  bool lp_on, fgt_on;                   // the table switches (read once a call)
+  double dv_ratio;
+  int64_t n_samp, n_c64, n_c32, n_grid, work_k;
+  int64_t host_rows, host_grid, host_grid_pad, dev_rows, dev_grid;
+  int64_t fit_max_new, fit_max_obs, fit_max_merge, fit_n_delta;
+  int64_t off_lead[NL], len_lead[NL], lead_end;
+  // ---- fill targets: the blob itself when it holds the leading sections
+  // (direct), else the scratch (the call then only sizes the level) ----
+  bool direct;
+  float* comp32;                        // float4 rows
+  double *comp64, *samp;                // double4 rows; 8 doubles per row
+  int32_t* grid;
+  LabelPlan* plan;                      // [label]
+  tpe_problem* lab;                     // [label]: the fields its problems share
+  const char* chunked;                  // [2 * label + side]: rows filled by chunk tasks (ChunkTask)
+  const int64_t* pa_off;                // [2 * label + side]: the side's acceptance terms in pa_terms, -1: none
+  double* pa_terms;                     // (the large bounded sides': the packer's parallel pass)
+  const PaTask* pa_tasks;
+  const ChunkTask* ch_tasks;
+  double *ch_a, *ch_c, *ch_max;         // chunked sides' a and unshifted c at ChunkTask.scr; per task: its largest finite c
+  double* side_shift;                   // [2 * label + side]: a chunked side's shift
+  int64_t Ph;                           // problems (and their tiles) the host writes: none when expanded
+  tpe_problem* prob;                    // [Ph]
+};
+
 struct PackScratch {
+  PackLevel lv;
+  std::vector<LabelPlan> plan;
+  std::vector<tpe_problem> lab;
+  std::vector<tpe_fit_job> fit;         // device-fitted labels: jobs, below positions, scratch segments
+  std::vector<int32_t> below_idx, fit_li;   // (fit_li: each fit job's label)
+  std::vector<int64_t> fit_seg;
+#ifdef TPE_PACK_TRACE
+  std::vector<std::pair<const char*, std::chrono::steady_clock::time_point>> marks;
+#endif
   std::vector<float> comp32;
   std::vector<double> comp64, samp;
   std::vector<int32_t> grid, fin_tiles, samp_tiles, tab_tiles;
@@ -455,41 +523,19 @@ void coord_range(const tpe_label_in& L, double& klo, double& khi) {
 // the table decision of one label (tpe_host_pack_level): which scoring its
 // candidates get — cells (moment rows or TPE_F_LOGPOLY rows), box-moment
 // cells, a lattice or none — and the geometry; labels are independent
-struct TabCtx {
-  const tpe_label_in* labels;
-  const char* dev_fit;
-  int32_t n_cand;
-  bool f64, lp_on, fgt_on;
-  double dv_ratio;
-  int32_t* tmode;
-  int64_t *tn0, *tn1, *tlat;
-  double *tklo, *tkhi;
-  int64_t* fgt_boxes;
-  char* logpoly;
-};
-
 constexpr int32_t kTabChunk = 16;
 
-void decide_table(const TabCtx& cx, int32_t li) {
-  const tpe_label_in* labels = cx.labels;
-  const char* dev_fit = cx.dev_fit;
-  const int32_t n_cand = cx.n_cand;
-  const bool f64 = cx.f64;
-  int32_t* tmode = cx.tmode;
-  int64_t *tn0 = cx.tn0, *tn1 = cx.tn1, *tlat = cx.tlat, *fgt_boxes = cx.fgt_boxes;
-  double *tklo = cx.tklo, *tkhi = cx.tkhi;
-  char* logpoly = cx.logpoly;
-  const tpe_label_in& L = labels[li];
-  const double ct = (double)L.n_ids * (double)n_cand;     // candidates of the label in this level
+void decide_table(const PackLevel& lv, const tpe_label_in& L, LabelPlan& lp) {
+  const double ct = (double)L.n_ids * (double)lv.n_cand;     // candidates of the label in this level
   if (L.n_ids <= 0 || L.family == TPE_FAM_CATEGORICAL || L.below_k <= 0) return;
   double klo, khi;
   coord_range(L, klo, khi);
   if (!(std::isfinite(klo) && std::isfinite(khi) && khi > klo)) return;
-  tklo[li] = klo; tkhi[li] = khi;
-  if ((L.family == TPE_FAM_GAUSS || L.family == TPE_FAM_LOGGAUSS) && !f64) {
+  lp.klo = klo; lp.khi = khi;
+  if ((L.family == TPE_FAM_GAUSS || L.family == TPE_FAM_LOGGAUSS) && !lv.f64) {
     double s0 = INFINITY, s1 = INFINITY;
     s0 = min_of(L.below_sigma, L.below_k);
-    if (dev_fit[li])           // the device fit clips every bandwidth to >= prior_sigma / min(100, 1 + K)
+    if (lp.dev_fit)            // the device fit clips every bandwidth to >= prior_sigma / min(100, 1 + K)
       s1 = L.prior_sigma / std::min(100.0, 1.0 + (double)L.above_k);
     else
       s1 = min_of(L.above_sigma, L.above_k);
@@ -501,24 +547,24 @@ void decide_table(const TabCtx& cx, int32_t li) {
     // moments": ~16 boxes per cell instead of every component within reach)
     // pay from about one candidate a cell
     int64_t nbox = 0;
-    if (dev_fit[li] && cx.fgt_on && n1 > 0) {
+    if (lp.dev_fit && lv.fgt_on && n1 > 0) {
       const double d = fgt_width(L.prior_sigma, L.above_k);
       const double nb = std::ceil((khi - klo) / d) + 1.0;
       if (d > 0 && nb >= 1.0 && nb <= (double)kFgtMaxBoxes) nbox = (int64_t)nb;
     }
-    const double ratio = nbox > 0 ? kTabMinRatioFgt : dev_fit[li] ? cx.dv_ratio : kTabMinRatio;
+    const double ratio = nbox > 0 ? kTabMinRatioFgt : lp.dev_fit ? lv.dv_ratio : kTabMinRatio;
     const int64_t nl = std::max(n0, n1);
-    const double lp_ratio = dev_fit[li] ? cx.dv_ratio : kTabMinRatio;   // (moment cells, no boxes)
+    const double lp_ratio = lp.dev_fit ? lv.dv_ratio : kTabMinRatio;   // (moment cells, no boxes)
     // (box-moment labels keep moment cells: their above cells come from the boxes)
-    if (cx.lp_on && nbox == 0 && n0 > 0 && n1 > 0 && nl <= kLogpolyMaxCells &&
+    if (lv.lp_on && nbox == 0 && n0 > 0 && n1 > 0 && nl <= kLogpolyMaxCells &&
         ct >= lp_ratio * kLpRowCost * (double)nl) {
       // both sides' log-polynomials on one grid (the finer side's cells): one
       // row per candidate look-up (include/tpe_hip.h, TPE_F_LOGPOLY)
-      tmode[li] = TPE_TAB_CELLS; tn0[li] = tn1[li] = nl;
-      logpoly[li] = 1;
+      lp.tmode = TPE_TAB_CELLS; lp.n0 = lp.n1 = nl;
+      lp.logpoly = 1;
     } else if (n0 > 0 && n1 > 0 && n0 <= kTabMaxCells && n1 <= kTabMaxCells && ct >= ratio * (double)(n0 + n1)) {
-      tmode[li] = TPE_TAB_CELLS; tn0[li] = n0; tn1[li] = n1;
-      fgt_boxes[li] = nbox;
+      lp.tmode = TPE_TAB_CELLS; lp.n0 = n0; lp.n1 = n1;
+      lp.boxes = nbox;
     }
   } else if ((L.family == TPE_FAM_QGAUSS || L.family == TPE_FAM_QLOGGAUSS) && L.q > 0 && L.above_k > 0 &&
              !(L.flags & TPE_F_NO_TABLE)) {
@@ -538,7 +584,7 @@ void decide_table(const TabCtx& cx, int32_t li) {
     const double nl = mhi - mlo + 1.0;
     if (std::isfinite(nl) && nl >= 1.0 && nl <= (double)kTabMaxLattice && std::fabs(mlo) < 9e15 &&
         ct >= 2.0 * nl) {
-      tmode[li] = TPE_TAB_LATTICE; tn0[li] = (int64_t)nl; tlat[li] = (int64_t)mlo;
+      lp.tmode = TPE_TAB_LATTICE; lp.n0 = (int64_t)nl; lp.lat_lo = (int64_t)mlo;
     }
   }
 }
@@ -619,43 +665,25 @@ inline __attribute__((always_inline)) void comp_rows_f32(const double* __restric
 // wide rows, pruning grid) at the offsets the packer assigned; labels are
 // independent, so the packer runs this on its worker threads.  (A function of
 // its own so that it carries the AVX-512 / AVX2 clones: a lambda would not.)
-struct LabelSec { int64_t samp, c64[2], c32[2], wide, grid; };
-struct FillCtx {
-  const tpe_label_in* labels;
-  const LabelSec* sec;
-  tpe_problem* lab;
-  double* samp;
-  double* comp64;
-  float* comp32;
-  int32_t* grid;
-  const char* dev_fit;
-  const int32_t* tmode;
-  int key_bits;
-  bool f64;
-  const double* pa_terms;      // a large bounded side's acceptance terms (the packer's parallel pass)
-  const int64_t* pa_off;       // [2 * label + side]: their offset in pa_terms, -1: none
-  const char* chunked;         // [2 * label + side]: rows filled by chunk tasks (ChunkTask)
-};
 
 // the acceptance mass of label li's side: the terms the parallel pass made, or p_accept
-inline double side_accept(const FillCtx& cx, int32_t li, int side, const double* w, const double* mu,
+inline double side_accept(const PackLevel& lv, int32_t li, int side, const double* w, const double* mu,
                           const double* sg, int64_t k, bool bounded, double lo, double hi, bool fast) {
-  const int64_t o = cx.pa_off[2 * (size_t)li + side];
-  return o >= 0 ? np_sum(cx.pa_terms + o, k) : p_accept(w, mu, sg, k, bounded, lo, hi, fast);
+  const int64_t o = lv.pa_off[2 * (size_t)li + side];
+  return o >= 0 ? np_sum(lv.pa_terms + o, k) : p_accept(w, mu, sg, k, bounded, lo, hi, fast);
 }
 
-struct PaCtx { const tpe_label_in* labels; const PaTask* tasks; double* terms; };
-void pa_chunk(const PaCtx& cx, int t) {
-  const PaTask& q = cx.tasks[t];
-  const tpe_label_in& L = cx.labels[q.li];
+void pa_chunk(const PackLevel& lv, int t) {
+  const PaTask& q = lv.pa_tasks[t];
+  const tpe_label_in& L = lv.labels[q.li];
   const double* w = q.side ? L.above_w : L.below_w;
   const double* mu = q.side ? L.above_mu : L.below_mu;
   const double* sg = q.side ? L.above_sigma : L.below_sigma;
-  p_accept_terms(w + q.i0, mu + q.i0, sg + q.i0, q.i1 - q.i0, L.low, L.high, cx.terms + q.off + q.i0, q.fast);
+  p_accept_terms(w + q.i0, mu + q.i0, sg + q.i0, q.i1 - q.i0, L.low, L.high, lv.pa_terms + q.off + q.i0, q.fast);
 }
 
 __attribute__((target_clones("avx512f", "avx2", "default")))
-void fill_label(const FillCtx& cx, int32_t li) {
+void fill_label(const PackLevel& lv, int32_t li) {
 #ifdef TPE_PACK_TRACE
   const auto t_fill0 = std::chrono::steady_clock::now();
   struct Done {
@@ -668,21 +696,17 @@ void fill_label(const FillCtx& cx, int32_t li) {
     }
   } done_{t_fill0, li};
 #endif
-  const tpe_label_in* labels = cx.labels;
-  const bool f64 = cx.f64;
-  const int key_bits = cx.key_bits;
-  const char* dev_fit = cx.dev_fit;
-  const int32_t* tmode = cx.tmode;
-  const tpe_label_in& L = labels[li];
-  const LabelSec& sc = cx.sec[li];
-  tpe_problem& p = cx.lab[li];
+  const bool f64 = lv.f64;
+  const tpe_label_in& L = lv.labels[li];
+  const LabelPlan& sc = lv.plan[li];
+  tpe_problem& p = lv.lab[li];
   memset(&p, 0, sizeof(p));
   p.family = L.family; p.flags = L.flags; p.n_upper = L.upper;
   p.low = L.low; p.high = L.high; p.q = L.q;
   const bool bounded = (L.flags & (TPE_F_HAS_LOW | TPE_F_HAS_HIGH)) != 0;
   // ---- sampler rows (below mixture) ----
   p.samp_off = (int32_t)sc.samp;
-  double* srow = cx.samp + 8 * (size_t)sc.samp;
+  double* srow = lv.samp + 8 * (size_t)sc.samp;
   if (L.family == TPE_FAM_CATEGORICAL) {
     const int64_t k = L.below_k;
     double acc = 0;
@@ -738,9 +762,9 @@ void fill_label(const FillCtx& cx, int32_t li) {
   double klo, khi;
   coord_range(L, klo, khi);
   p.key_lo = (float)klo;
-  p.key_inv = khi > klo ? (float)((double)(1 << key_bits) / (khi - klo)) : 0.f;
+  p.key_inv = khi > klo ? (float)((double)(1 << lv.key_bits) / (khi - klo)) : 0.f;
   // ---- component rows ----
-  for (int side = 0; side < 2 - dev_fit[li]; ++side) {
+  for (int side = 0; side < 2 - sc.dev_fit; ++side) {
     const double* w = side ? L.above_w : L.below_w;
     const double* mu = side ? L.above_mu : L.below_mu;
     const double* sg = side ? L.above_sigma : L.below_sigma;
@@ -750,27 +774,27 @@ void fill_label(const FillCtx& cx, int32_t li) {
     double& base = side ? p.above_base : p.below_base;
     if (L.family == TPE_FAM_CATEGORICAL) {
       off = (int32_t)sc.c64[side]; len = (int32_t)k; base = 0;
-      double* r = cx.comp64 + 4 * (size_t)off;
+      double* r = lv.comp64 + 4 * (size_t)off;
       for (int64_t i = 0; i < k; ++i) {
         const double row[4] = {log(w[i]), w[i], 0, 0};
         memcpy(r + 4 * i, row, sizeof(row));
       }
     } else if (L.family == TPE_FAM_QGAUSS || L.family == TPE_FAM_QLOGGAUSS) {
       off = (int32_t)sc.c64[side]; len = (int32_t)k;
-      base = -log(side_accept(cx, li, side, w, mu, sg, k, bounded, L.low, L.high, false));
-      double* r = cx.comp64 + 4 * (size_t)off;
+      base = -log(side_accept(lv, li, side, w, mu, sg, k, bounded, L.low, L.high, false));
+      double* r = lv.comp64 + 4 * (size_t)off;
       for (int64_t i = 0; i < k; ++i) {
         const double row[4] = {mu[i], np_max(sqrt(2.0) * sg[i], kEPS), w[i], 0};
         memcpy(r + 4 * i, row, sizeof(row));
       }
     } else {
       const bool logf = L.family == TPE_FAM_LOGGAUSS;
-      if (cx.chunked[2 * (size_t)li + side]) {      // (its terms and rows: the chunk tasks; its base: the packer)
+      if (lv.chunked[2 * (size_t)li + side]) {      // (its terms and rows: the chunk tasks; its base: the packer)
         off = (int32_t)sc.c32[side]; len = (int32_t)k;
         continue;
       }
       std::vector<double> a((size_t)k), c((size_t)k);
-      const double pa = logf ? 1.0 : side_accept(cx, li, side, w, mu, sg, k, bounded, L.low, L.high, !f64);
+      const double pa = logf ? 1.0 : side_accept(lv, li, side, w, mu, sg, k, bounded, L.low, L.high, !f64);
       double shift = -INFINITY;
       if (f64) {
         for (int64_t i = 0; i < k; ++i) {
@@ -788,7 +812,7 @@ void fill_label(const FillCtx& cx, int32_t li) {
       base = shift * kLn2;
       if (f64) {
         off = (int32_t)sc.c64[side]; len = (int32_t)k;
-        double* r = cx.comp64 + 4 * (size_t)off;
+        double* r = lv.comp64 + 4 * (size_t)off;
         for (int64_t i = 0; i < k; ++i) {
           const double row[4] = {mu[i], a[i], c[i], 0};
           memcpy(r + 4 * i, row, sizeof(row));
@@ -799,7 +823,7 @@ void fill_label(const FillCtx& cx, int32_t li) {
       // listed apart, grid over mu.  A tabulated label's cells sum every
       // component (k_tables), so it has neither.
       std::vector<int64_t> wide;
-      if (side == 1 && k > kPruneMinK && tmode[li] == TPE_TAB_NONE) {
+      if (side == 1 && k > kPruneMinK && sc.tmode == TPE_TAB_NONE) {
         // the kPruneWide smallest a (widest sigma), ascending by (a, index): one
         // pass with a small insertion-sorted buffer (= a stable argsort prefix)
         int64_t best[kPruneWide];
@@ -815,19 +839,19 @@ void fill_label(const FillCtx& cx, int32_t li) {
       off = (int32_t)sc.c32[side]; len = (int32_t)k;
       {
         const size_t b0 = 4 * (size_t)sc.c32[side];
-        float* r = cx.comp32 + b0;
+        float* r = lv.comp32 + b0;
         for (int64_t i = 0; i < k; ++i, r += 4) {
           const float hi = (float)mu[i];
           r[0] = hi; r[1] = (float)(mu[i] - (double)hi); r[2] = (float)a[i]; r[3] = (float)c[i];
         }
-        for (int64_t i : wide) cx.comp32[b0 + 4 * (size_t)i + 3] = -INFINITY;
+        for (int64_t i : wide) lv.comp32[b0 + 4 * (size_t)i + 3] = -INFINITY;
       }
       std::vector<char> is_wide((size_t)k, 0);
       for (int64_t i : wide) is_wide[i] = 1;
       if (!wide.empty()) {
         p.wide_off = (int32_t)sc.wide;
         p.wide_len = (int32_t)wide.size();
-        float* wr = cx.comp32 + 4 * (size_t)sc.wide;
+        float* wr = lv.comp32 + 4 * (size_t)sc.wide;
         for (int64_t i : wide) {
           const float hi = (float)mu[i];
           const float row[4] = {hi, (float)(mu[i] - (double)hi), (float)a[i], (float)c[i]};
@@ -851,7 +875,7 @@ void fill_label(const FillCtx& cx, int32_t li) {
         // no data-dependent branches in the merge
         const double step = inv > 0 ? 1.0 / (double)inv : 0.0;
         const size_t g0 = (size_t)sc.grid;
-        int32_t* __restrict__ gp = cx.grid + g0;
+        int32_t* __restrict__ gp = lv.grid + g0;
         if (!(inv > 0)) memset(gp, 0, (size_t)G * sizeof(int32_t));
         if (inv > 0) {
           // four interleaved histograms: sorted mu puts neighbours in the same
@@ -880,22 +904,9 @@ void fill_label(const FillCtx& cx, int32_t li) {
 }
 
 // the chunk tasks' two passes (ChunkTask; tpe_host_pack_level)
-struct ChunkCtx {
-  const tpe_label_in* labels;
-  const ChunkTask* tasks;
-  double* a;                   // scratch: each chunked side's a and unshifted c at ChunkTask.scr
-  double* c;
-  double* cmax;                // per task: the chunk's largest finite c
-  double* pa_terms;            // the bounded sides' acceptance terms (terms pass) ...
-  const int64_t* pa_off;       // ... at [2 * label + side] (-1: unbounded or the log family)
-  const double* shift;         // [2 * label + side]: the side's shift (rows pass)
-  const LabelSec* sec;
-  float* comp32;
-};
-
 __attribute__((target_clones("avx512f", "avx2", "default")))
-void chunk_terms(const ChunkCtx& x, int t) {
-  const ChunkTask& q = x.tasks[t];
+void chunk_terms(const PackLevel& x, int t) {
+  const ChunkTask& q = x.ch_tasks[t];
   const tpe_label_in& L = x.labels[q.li];
   const double* w = q.side ? L.above_w : L.below_w;
   const double* sg = q.side ? L.above_sigma : L.below_sigma;
@@ -906,18 +917,860 @@ void chunk_terms(const ChunkCtx& x, int t) {
     const double* mu = q.side ? L.above_mu : L.below_mu;
     p_accept_terms(w + q.i0, mu + q.i0, sg + q.i0, q.i1 - q.i0, L.low, L.high, x.pa_terms + x.pa_off[s] + q.i0, true);
   }
-  x.cmax[t] = comp_terms_f32(w + q.i0, sg + q.i0, q.i1 - q.i0, L.family == TPE_FAM_LOGGAUSS, 1.0,
-                             x.a + q.scr + q.i0, x.c + q.scr + q.i0);
+  x.ch_max[t] = comp_terms_f32(w + q.i0, sg + q.i0, q.i1 - q.i0, L.family == TPE_FAM_LOGGAUSS, 1.0,
+                               x.ch_a + q.scr + q.i0, x.ch_c + q.scr + q.i0);
 }
 
 __attribute__((target_clones("avx512f", "avx2", "default")))
-void chunk_rows(const ChunkCtx& x, int t) {
-  const ChunkTask& q = x.tasks[t];
+void chunk_rows(const PackLevel& x, int t) {
+  const ChunkTask& q = x.ch_tasks[t];
   const tpe_label_in& L = x.labels[q.li];
   const double* mu = q.side ? L.above_mu : L.below_mu;
   const size_t s = 2 * (size_t)q.li + q.side;
-  comp_rows_f32(mu + q.i0, x.a + q.scr + q.i0, x.c + q.scr + q.i0, q.i1 - q.i0, x.shift[s],
-                x.comp32 + 4 * (size_t)(x.sec[q.li].c32[q.side] + q.i0));
+  comp_rows_f32(mu + q.i0, x.ch_a + q.scr + q.i0, x.ch_c + q.scr + q.i0, q.i1 - q.i0, x.side_shift[s],
+                x.comp32 + 4 * (size_t)(x.plan[q.li].c32[q.side] + q.i0));
+}
+
+// ---------------------------------------------------------------- the level packer
+// tpe_host_pack_level as a sequence of steps over the thread's PackScratch, one
+// per PACK_MARK section: the plan's (step_devfit .. step_lead), then the fill's.
+// Their straight-line table loops vectorise: every step is inlined into
+// pack_plan / pack_fill, which carry the AVX-512 / AVX2 clones picked at
+// load time (-ffp-contract=off holds in all, so the tables are bit-identical).
+#define PACK_STEP inline __attribute__((always_inline))
+
+// (TPE_PACK_TRACE builds, tools/pack_time.py: the packer's sections timed)
+#ifdef TPE_PACK_TRACE
+#define PACK_MARK(name) ps.marks.emplace_back(name, std::chrono::steady_clock::now())
+#define PACK_DONE()                                                                            \
+  do {                                                                                         \
+    for (size_t i_ = 1; i_ < ps.marks.size(); ++i_)                                            \
+      fprintf(stderr, "pack %-16s %8.1f us\n", ps.marks[i_].first,                             \
+              std::chrono::duration<double, std::micro>(ps.marks[i_].second - ps.marks[i_ - 1].second).count()); \
+  } while (0)
+#else
+#define PACK_MARK(name) (void)0
+#define PACK_DONE() (void)0
+#endif
+
+// per-thread staging, reused across calls (no first-touch page faults on the
+// large tables — a batched level has ~10^5 problems, tiles and work items).
+// Looked up once a call: references to its members stay in registers, while a
+// thread_local named inside a loop costs a TLS call per use in a shared object.
+PackScratch& pack_scratch() {
+  static thread_local PackScratch tls_scratch;
+  return tls_scratch;
+}
+
+// the level's problems; which labels' above mixtures the device fits
+PACK_STEP int step_devfit(PackScratch& ps) {
+  PackLevel& lv = ps.lv;
+  ps.plan.assign((size_t)lv.n_labels, LabelPlan());
+  ps.lab.resize((size_t)lv.n_labels);
+  lv.plan = ps.plan.data();
+  lv.lab = ps.lab.data();
+  lv.P = 0;
+  for (int32_t li = 0; li < lv.n_labels; ++li) {
+    const tpe_label_in& L = lv.labels[li];
+    lv.P += L.n_ids;
+    if (L.dev_obs && !L.above_mu) {
+      if ((L.family != TPE_FAM_GAUSS && L.family != TPE_FAM_LOGGAUSS) || lv.f64 || L.n_below < 0 || L.n_below > 64 ||
+          (L.n_below > 0 && !L.below_idx) || L.n_obs - L.n_below + 1 != L.above_k || L.above_k <= kPruneMinK ||
+          L.n_obs >= ((int64_t)1 << 31) || L.n_ord_in < 0 || L.n_ord_in > L.n_obs ||
+          (L.n_ord_in > 0 && (!L.ord_key_in || !L.ord_idx_in)) ||
+          (L.n_ord_in < L.n_obs && (!L.ord_key_out || !L.ord_idx_out) &&
+           !(L.n_ord_in > 0 && L.n_obs - L.n_ord_in <= TPE_FIT_DELTA_MAX && !L.ord_key_out && !L.ord_idx_out)))
+        return TPE_E_ARG;
+      lv.plan[li].dev_fit = 1;
+    }
+  }
+  return TPE_OK;
+}
+
+// ---- tabulated scoring: which labels score from tables, and their geometry ----
+PACK_STEP void step_tmode(PackScratch& ps) {
+  PackLevel& lv = ps.lv;
+  if (!(tables_enabled() && lv.n_cand > 0)) return;
+  lv.lp_on = logpoly_enabled(); lv.fgt_on = fgt_enabled(); lv.dv_ratio = devfit_ratio();
+  // (a label's decision reads its whole above mixture: thousands of
+  // components per label make a worker's hand-off worth it; a device-fitted
+  // label's reads only its below side — config 5's 125 labels a rank decide in
+  // 5 us on one thread, 11-14 us handed out)
+  int64_t comps = 0;
+  for (int32_t li = 0; li < lv.n_labels; ++li)
+    comps += lv.plan[li].dev_fit ? lv.labels[li].below_k : lv.labels[li].above_k;
+  // (in chunks of up to kTabChunk labels: a thousand-label level's decisions
+  // are sub-microsecond each, too small to hand out one by one; a few large
+  // labels — config 4's twenty of 10^4 components — one a task)
+  struct Chunked { const PackLevel* lv; int32_t per; };
+  const int32_t per = std::max<int32_t>(1, std::min<int32_t>(kTabChunk, lv.n_labels / (4 * (1 + tpe_pool::workers()))));
+  const Chunked ch{&lv, per};
+  if (lv.n_labels >= 2 && comps >= 16384)
+    tpe_pool::parallel_for((lv.n_labels + per - 1) / per, [](void* c, int k) {
+      const Chunked& q = *(const Chunked*)c;
+      const PackLevel& l = *q.lv;
+      for (int32_t li = k * q.per; li < std::min(l.n_labels, (k + 1) * q.per); ++li)
+        decide_table(l, l.labels[li], l.plan[li]);
+    }, (void*)&ch);
+  else
+    for (int32_t li = 0; li < lv.n_labels; ++li) decide_table(lv, lv.labels[li], lv.plan[li]);
+}
+
+// Pruned problems (continuous f32 above mixtures of more than kPruneMinK
+// components, not tabulated) are the only ones whose candidates are sorted; they own the
+// candidate range [0, sort_count).  Sort key = sort_slot << key_bits | value
+// bucket: one 8-bit radix pass up to 8 sorted problems, never below 32
+// buckets per problem.  Large candidate sets get 4096 buckets (two passes):
+// a wave of 512 sorted candidates then spans ~1/8 of a bucket's density,
+// narrow enough for the above kernel's local expansion.
+// A pruned label active for several ids is POOLED: its problems share one
+// sort slot and are sorted as one population (include/tpe_hip.h).
+PACK_STEP void step_prune(PackScratch& ps) {
+  PackLevel& lv = ps.lv;
+  int64_t S = 0, n_sorted_prob = 0, n_pooled = 0, max_slot_cand = 0;
+  for (int32_t li = 0; li < lv.n_labels; ++li) {
+    const tpe_label_in& L = lv.labels[li];
+    LabelPlan& lp = lv.plan[li];
+    lp.pruned = !lv.f64 && (L.family == TPE_FAM_GAUSS || L.family == TPE_FAM_LOGGAUSS) &&
+                (lp.dev_fit || L.above_k > kPruneMinK) && lp.tmode == TPE_TAB_NONE;
+    lp.pooled = lp.pruned && L.n_ids >= 2;
+    if (!lp.pruned) continue;
+    S += lp.pooled ? 1 : L.n_ids;
+    n_sorted_prob += L.n_ids;
+    if (lp.pooled) n_pooled += L.n_ids;
+    max_slot_cand = std::max(max_slot_cand, (lp.pooled ? L.n_ids : 1) * (int64_t)lv.n_cand);
+  }
+  int pbits = 0;
+  while (((int64_t)1 << pbits) < S) ++pbits;
+  int key_bits = std::max(5, 8 - pbits);
+  if (max_slot_cand >= kFineKeyMinCand) key_bits = std::max(key_bits, std::min(fine_key_bits(), 16 - pbits));
+  lv.S = S; lv.n_sorted_prob = n_sorted_prob; lv.n_pooled = n_pooled;
+  lv.key_bits = key_bits;
+  lv.sort_end_bit = S > 0 && key_bits + pbits <= 32 ? key_bits + pbits : 0;
+}
+
+// ---- per-label sections: every label's sampler rows, component rows, wide
+// rows and pruning grid get their offsets first (label order, as appended
+// one after another), then each label fills its own sections — on the host
+// worker threads when the level has enough components (labels independent) ----
+PACK_STEP void step_sizing(PackScratch& ps) {
+  PackLevel& lv = ps.lv;
+  lv.n_samp = lv.n_c64 = lv.n_c32 = lv.n_grid = lv.work_k = 0;
+  for (int32_t li = 0; li < lv.n_labels; ++li) {
+    const tpe_label_in& L = lv.labels[li];
+    LabelPlan& q = lv.plan[li];
+    q.samp = lv.n_samp; lv.n_samp += L.below_k;
+    // (a label's fill beyond its rows: the sampler rows' four erfc a below
+    // component and a fixed part — a thousand device-fitted labels of 26 host
+    // components each are 3.7 us of fill a label, worth the workers)
+    lv.work_k += 4 * L.below_k + 64;
+    const bool rows64 = L.family == TPE_FAM_CATEGORICAL || L.family == TPE_FAM_QGAUSS ||
+                        L.family == TPE_FAM_QLOGGAUSS || lv.f64;
+    for (int side = 0; side < 2 - q.dev_fit; ++side) {
+      const int64_t k = side ? L.above_k : L.below_k;
+      lv.work_k += k;
+      if (rows64) { q.c64[side] = lv.n_c64; lv.n_c64 += k; continue; }
+      q.c32[side] = lv.n_c32; lv.n_c32 += k;
+      if (side == 1 && k > kPruneMinK && q.tmode == TPE_TAB_NONE) {   // wide rows + grid (pruned)
+        q.wide = lv.n_c32; lv.n_c32 += std::min<int64_t>(kPruneWide, k);
+        q.grid = lv.n_grid; lv.n_grid += std::min<int64_t>(4096, 4 * k) + 1;
+      }
+    }
+  }
+}
+
+// ---- device-fitted above mixtures: rows and grids after the host ones, fit
+// jobs (before the fill: the level runner may launch the fit right away) ----
+// (the device grid starts 256-B aligned: the host part's upload never
+// touches a word the fit wrote)
+PACK_STEP int step_devrows(PackScratch& ps) {
+  PackLevel& lv = ps.lv;
+  lv.host_rows = lv.n_c32;
+  lv.host_grid = std::max<int64_t>(lv.n_grid, 1);
+  lv.host_grid_pad = (lv.host_grid + 63) & ~(int64_t)63;
+  // (sized first and written through pointers: the sections' lengths are known,
+  // and an append to a vector of the scratch goes through memory every time)
+  int64_t nf = 0, nb = 0;
+  for (int32_t li = 0; li < lv.n_labels; ++li)
+    if (lv.plan[li].dev_fit) { ++nf; nb += lv.labels[li].n_below; }
+  ps.fit.resize((size_t)nf); ps.fit_li.resize((size_t)nf); ps.fit_seg.resize((size_t)nf + 1);
+  ps.below_idx.resize((size_t)std::max<int64_t>(nb, 1));
+  tpe_fit_job* const fit = ps.fit.data();
+  int32_t* const fit_li = ps.fit_li.data();
+  int32_t* const below_idx = ps.below_idx.data();
+  int64_t* const fit_seg = ps.fit_seg.data();
+  fit_seg[0] = 0;
+  below_idx[0] = 0;
+  const int64_t host_rows = lv.host_rows, host_grid_pad = lv.host_grid_pad;
+  int64_t dev_rows = 0, dev_grid = 0, fit_max_new = 0, fit_max_obs = 0, fit_max_merge = 0, fit_n_delta = 0;
+  int64_t r = 0, k = 0, n_bidx = 0;
+  for (int32_t li = 0; li < lv.n_labels; ++li) {
+    const tpe_label_in& L = lv.labels[li];
+    if (lv.plan[li].dev_fit) {
+      const int64_t K = L.above_k, G = std::min<int64_t>(4096, 4 * K);
+      tpe_fit_job& j = fit[k];
+      memset(&j, 0, sizeof(j));
+      j.obs = L.dev_obs; j.n_obs = L.n_obs; j.seg_off = fit_seg[k];
+      j.below_off = (int32_t)n_bidx; j.n_below = L.n_below;
+      j.family = L.family; j.flags = L.flags; j.lf = L.lf;
+      j.problem_first = (int32_t)r; j.n_problems = (int32_t)L.n_ids;
+      j.above_off = (int32_t)(host_rows + dev_rows); j.wide_off = (int32_t)(host_rows + dev_rows + K);
+      j.grid_off = (int32_t)(host_grid_pad + dev_grid); j.grid_n = (int32_t)G;
+      j.prior_mu = L.prior_mu; j.prior_sigma = L.prior_sigma; j.prior_weight = L.prior_weight;
+      j.low = L.low; j.high = L.high;
+      j.ord_key_in = L.ord_key_in; j.ord_idx_in = L.ord_idx_in; j.n_ord_in = L.n_ord_in;
+      j.ord_key_out = L.ord_key_out; j.ord_idx_out = L.ord_idx_out;
+      for (int32_t b = 0; b < L.n_below; ++b) {
+        if (L.below_idx[b] < 0 || L.below_idx[b] >= L.n_obs || (b && L.below_idx[b] <= L.below_idx[b - 1]))
+          return TPE_E_ARG;
+        below_idx[n_bidx++] = L.below_idx[b];
+      }
+      fit_li[k] = li;
+      // scratch segment: the compacted above order, the new observations' merge
+      // passes and the below positions all fit in it
+      const int64_t n_new = L.n_obs - L.n_ord_in;
+      // (delta mode: the delta arrays, then a slot of kFitStageStretch entries per
+      // 2048-component chunk for the chunks whose stretch holds a delta entry)
+      const int64_t slots = !L.ord_key_out && n_new > 0 ? ((K + 2047) / 2048) * kFitStageStretch : 0;
+      fit_seg[k + 1] = fit_seg[k] + std::max<int64_t>(std::max<int64_t>(K - 1, n_new),
+                                                      std::max<int64_t>(L.n_below, 64 + 2 * TPE_FIT_DELTA_MAX + slots));
+      ++k;
+      fit_max_new = std::max(fit_max_new, n_new);
+      if (L.ord_key_out) fit_max_merge = std::max(fit_max_merge, n_new);
+      else fit_n_delta += n_new > 0;          // (delta mode)
+      fit_max_obs = std::max<int64_t>(fit_max_obs, L.n_obs);
+      dev_rows += K + kPruneWide;
+      dev_grid += G + 1;
+    }
+    r += L.n_ids;
+  }
+  lv.dev_rows = dev_rows; lv.dev_grid = dev_grid;
+  lv.fit_max_new = fit_max_new; lv.fit_max_obs = fit_max_obs; lv.fit_max_merge = fit_max_merge;
+  lv.fit_n_delta = fit_n_delta;
+  if (host_rows + dev_rows >= ((int64_t)1 << 31) || host_grid_pad + dev_grid >= ((int64_t)1 << 31)) return TPE_E_ARG;
+  return TPE_OK;
+}
+
+// ---- expanded levels (include/tpe_hip.h "Expanded levels"): when every label
+// of a large level scores from tables, its problems differ from their label's
+// only in (cand_off, ctr3, tile_off) and its tiles are {problem, j * T, 0, 0}
+// in order: the host writes one template per label and the new ids, the
+// device (k_expand) writes the problems and tiles — ~240 B + 32 B per (label,
+// id) neither packed nor uploaded ----
+// ---- the blob's leading sections, placed before the fill (the fill writes
+// its sections in place; the device fit may run while it does):
+//   fit jobs | below positions | fit segments | grid (host | device, 256-B
+//   aligned) | comp32 (host | device) | fit patches (device only: the problem
+//   fields the fit writes, applied after the upload) | problems | tiles
+//   (device only when expanded) | comp64 | sampler rows
+// then the later sections (work, finalize tiles, table jobs, tile lists, the
+// expanded level's templates) after them ----
+PACK_STEP void step_lead(PackScratch& ps) {
+  PackLevel& lv = ps.lv;
+  lv.n_tiles_p = lv.n_cand > 0 ? (lv.n_cand + kPackTile - 1) / kPackTile : 0;
+  lv.expand = expand_enabled() && !lv.f64 && lv.P >= kExpandMinProblems && lv.n_tiles_p > 0;
+  for (int32_t li = 0; li < lv.n_labels && lv.expand; ++li)
+    if (lv.labels[li].n_ids > 0 && lv.plan[li].tmode == TPE_TAB_NONE) lv.expand = false;
+  const int64_t P = lv.P;
+  const int64_t len_lead[NL] = {(int64_t)(ps.fit.size() * sizeof(tpe_fit_job)), (int64_t)(ps.below_idx.size() * sizeof(int32_t)),
+                                (int64_t)(ps.fit_seg.size() * sizeof(int64_t)), (lv.host_grid_pad + lv.dev_grid) * 4,
+                                (lv.host_rows + lv.dev_rows) * 16, ps.fit.empty() ? 0 : P * (int64_t)sizeof(tpe_problem),
+                                P * (int64_t)sizeof(tpe_problem), P * lv.n_tiles_p * (int64_t)sizeof(tpe_tile),
+                                lv.n_c64 * 32, lv.n_samp * 64};
+  lv.lead_end = 0;
+  for (int i = 0; i < NL; ++i) {
+    lv.len_lead[i] = len_lead[i];
+    lv.off_lead[i] = (lv.lead_end + 255) & ~(int64_t)255;
+    lv.lead_end = lv.off_lead[i] + len_lead[i];
+  }
+  lv.direct = lv.bb != nullptr && lv.blob_cap >= lv.lead_end;
+  if (lv.direct) {
+    lv.comp32 = (float*)(lv.bb + lv.off_lead[L_C32]);
+    lv.comp64 = (double*)(lv.bb + lv.off_lead[L_C64]);
+    lv.samp = (double*)(lv.bb + lv.off_lead[L_SAMP]);
+    lv.grid = (int32_t*)(lv.bb + lv.off_lead[L_GRID]);
+  } else {
+    // (trivially typed: a resize to the same size as the last call touches nothing)
+    ps.comp32.resize((size_t)(4 * lv.n_c32));
+    ps.comp64.resize((size_t)(4 * lv.n_c64));
+    ps.samp.resize((size_t)(8 * lv.n_samp));
+    ps.grid.resize((size_t)lv.host_grid);
+    lv.comp32 = ps.comp32.data(); lv.comp64 = ps.comp64.data(); lv.samp = ps.samp.data(); lv.grid = ps.grid.data();
+  }
+  lv.grid[0] = 0;
+  if (lv.direct && !ps.fit.empty()) {
+    memcpy(lv.bb + lv.off_lead[L_FIT], ps.fit.data(), (size_t)len_lead[L_FIT]);
+    memcpy(lv.bb + lv.off_lead[L_BIDX], ps.below_idx.data(), (size_t)len_lead[L_BIDX]);
+    memcpy(lv.bb + lv.off_lead[L_FSEG], ps.fit_seg.data(), (size_t)len_lead[L_FSEG]);
+  }
+}
+
+// large tabulated continuous f32 sides: in chunks (ChunkTask), their
+// acceptance terms in the same tasks as their component terms; the other large
+// bounded sides' acceptance terms in chunks on the workers
+PACK_STEP void step_accept(PackScratch& ps) {
+  PackLevel& lv = ps.lv;
+  const tpe_label_in* labels = lv.labels;
+  const int32_t n_labels = lv.n_labels;
+  auto& chunked = ps.chunked;
+  auto& ch_tasks = ps.ch_tasks;
+  chunked.assign(2 * (size_t)n_labels, 0);
+  ch_tasks.clear();
+  int64_t ch_total = 0;
+  // (only a level with many such components: a chunked side costs a second
+  // hand-off to the workers, more than it saves on the headline's few thousand)
+  int64_t chunkable = 0;
+  for (int32_t li = 0; li < n_labels && !lv.f64; ++li) {
+    const tpe_label_in& L = labels[li];
+    if ((L.family != TPE_FAM_GAUSS && L.family != TPE_FAM_LOGGAUSS) || lv.plan[li].tmode == TPE_TAB_NONE) continue;
+    for (int side = 0; side < 2 - lv.plan[li].dev_fit; ++side) {
+      const int64_t k = side ? L.above_k : L.below_k;
+      if (k > kFillChunk) chunkable += k;
+    }
+  }
+  if (chunkable >= fill_chunk_min_level())
+    for (int32_t li = 0; li < n_labels; ++li) {
+      const tpe_label_in& L = labels[li];
+      if ((L.family != TPE_FAM_GAUSS && L.family != TPE_FAM_LOGGAUSS) || lv.plan[li].tmode == TPE_TAB_NONE) continue;
+      for (int side = 0; side < 2 - lv.plan[li].dev_fit; ++side) {
+        const int64_t k = side ? L.above_k : L.below_k;
+        if (k <= kFillChunk) continue;
+        chunked[2 * (size_t)li + side] = 1;
+        const int64_t nch = (k + kFillChunk - 1) / kFillChunk;
+        for (int64_t j = 0; j < nch; ++j)
+          ch_tasks.push_back(ChunkTask{li, side, k * j / nch, k * (j + 1) / nch, ch_total});
+        ch_total += k;
+      }
+    }
+  // the acceptance terms of the large bounded sides in chunks on the workers
+  // (libm erf for every component near a bound: the largest label's would
+  // otherwise be its fill's critical path); the fill sums them in order
+  auto& pa_off = ps.pa_off;
+  auto& pa_tasks = ps.pa_tasks;
+  pa_off.assign(2 * (size_t)n_labels, -1);
+  pa_tasks.clear();
+  int64_t pa_total = 0;
+  for (int32_t li = 0; li < n_labels; ++li) {
+    const tpe_label_in& L = labels[li];
+    if (!(L.flags & (TPE_F_HAS_LOW | TPE_F_HAS_HIGH)) || L.family == TPE_FAM_CATEGORICAL ||
+        L.family == TPE_FAM_LOGGAUSS)
+      continue;
+    const bool fast = L.family == TPE_FAM_GAUSS && !lv.f64;   // (an f32 side's mass: erf_tab)
+    for (int side = 0; side < 2 - lv.plan[li].dev_fit; ++side) {
+      const int64_t k = side ? L.above_k : L.below_k;
+      const bool ch = chunked[2 * (size_t)li + side] != 0;     // (its terms: the chunk tasks)
+      if (k < kPaParallelMin && !ch) continue;
+      pa_off[2 * (size_t)li + side] = pa_total;
+      for (int64_t i0 = 0; i0 < k && !ch; i0 += kPaChunk)
+        pa_tasks.push_back(PaTask{li, side, i0, std::min(k, i0 + kPaChunk), pa_total, fast});
+      pa_total += k;
+    }
+  }
+  ps.pa_terms.resize((size_t)pa_total);
+  const int n_ch = (int)ch_tasks.size();
+  if (n_ch) {
+    ps.ch_a.resize((size_t)ch_total);
+    ps.ch_c.resize((size_t)ch_total);
+    ps.ch_max.resize((size_t)n_ch);
+    ps.side_shift.assign(2 * (size_t)n_labels, 0.0);
+  }
+  lv.chunked = chunked.data(); lv.pa_off = pa_off.data(); lv.pa_terms = ps.pa_terms.data();
+  lv.pa_tasks = pa_tasks.data(); lv.ch_tasks = ch_tasks.data();
+  lv.ch_a = ps.ch_a.data(); lv.ch_c = ps.ch_c.data(); lv.ch_max = ps.ch_max.data();
+  lv.side_shift = ps.side_shift.data();
+  if (!pa_tasks.empty())
+    tpe_pool::parallel_for((int)pa_tasks.size(), [](void* c, int i) { pa_chunk(*(const PackLevel*)c, i); }, (void*)&lv);
+}
+
+// the labels' fills and the chunks' terms, one task each (a few hundred
+// components per label make a worker's hand-off worth it)
+PACK_STEP void step_fill_terms(PackScratch& ps) {
+  PackLevel& lv = ps.lv;
+  auto task = [](void* v, int i) {
+    const PackLevel& l = *(const PackLevel*)v;
+    if (i < l.n_labels) fill_label(l, (int32_t)i);
+    else chunk_terms(l, i - l.n_labels);
+  };
+  const int n_tasks = lv.n_labels + (int)ps.ch_tasks.size();
+  if (n_tasks >= 2 && lv.work_k >= 4096) tpe_pool::parallel_for(n_tasks, task, (void*)&lv);
+  else
+    for (int i = 0; i < n_tasks; ++i) task((void*)&lv, i);
+}
+
+// each chunked side's shift (the largest finite c of its chunks) and base,
+// then its rows
+PACK_STEP void step_fill(PackScratch& ps) {
+  PackLevel& lv = ps.lv;
+  const auto& ch_tasks = ps.ch_tasks;
+  const int n_ch = (int)ch_tasks.size();
+  if (!n_ch) return;
+  double* side_shift = lv.side_shift;
+  tpe_problem* lab = lv.lab;
+  for (int t = 0; t < n_ch; ++t) {
+    const size_t q = 2 * (size_t)ch_tasks[t].li + ch_tasks[t].side;
+    side_shift[q] = ch_tasks[t].i0 == 0 ? ps.ch_max[t] : std::max(side_shift[q], ps.ch_max[t]);
+  }
+  for (int32_t li = 0; li < lv.n_labels; ++li)
+    for (int side = 0; side < 2; ++side) {
+      const size_t q = 2 * (size_t)li + side;
+      if (!lv.chunked[q]) continue;
+      if (!std::isfinite(side_shift[q])) side_shift[q] = 0;
+      (side ? lab[li].above_base : lab[li].below_base) = side_shift[q] * kLn2;
+    }
+  // the rows, and each bounded side's mass (its terms summed in numpy's
+  // order) into its base: log2(w / (sigma sqrt(2 pi)) / p) - shift =
+  // c' - shift' with shift = shift' + log2(1 / p), one task a side (named by
+  // its first chunk)
+  auto& mass = ps.mass_tasks;
+  mass.clear();
+  for (int t = 0; t < n_ch; ++t)
+    if (ch_tasks[t].i0 == 0 && lv.pa_off[2 * (size_t)ch_tasks[t].li + ch_tasks[t].side] >= 0) mass.push_back(t);
+  struct Rows { const PackLevel* lv; const int* mass; int n_ch; };
+  const Rows rw{&lv, mass.data(), n_ch};
+  auto rows = [](void* v, int t) {
+    const Rows& r = *(const Rows*)v;
+    const PackLevel& l = *r.lv;
+    if (t < r.n_ch) { chunk_rows(l, t); return; }
+    const ChunkTask& q = l.ch_tasks[r.mass[t - r.n_ch]];
+    const size_t sd = 2 * (size_t)q.li + q.side;
+    const tpe_label_in& L = l.labels[q.li];
+    const double pa = np_sum(l.pa_terms + l.pa_off[sd], q.side ? L.above_k : L.below_k);
+    double& base = q.side ? l.lab[q.li].above_base : l.lab[q.li].below_base;
+    base = pa > 0 && pa < INFINITY ? base - log(pa) : NAN;      // (NaN: refilled below)
+  };
+  const int n_rows = n_ch + (int)mass.size();
+  if (n_rows >= 2) tpe_pool::parallel_for(n_rows, rows, (void*)&rw);
+  else rows((void*)&rw, 0);
+  // a side whose mass is 0, inf or NaN: its rows with 1 / p inside c, as
+  // fill_label makes them (the rows carry the non-finite values, base 0)
+  for (int m : mass) {
+    const ChunkTask& q0 = ch_tasks[m];
+    tpe_problem& p = lab[q0.li];
+    double& base = q0.side ? p.above_base : p.below_base;
+    if (base == base) continue;
+    const tpe_label_in& L = lv.labels[q0.li];
+    const size_t sd = 2 * (size_t)q0.li + q0.side;
+    const double ipa = 1.0 / np_sum(lv.pa_terms + lv.pa_off[sd], q0.side ? L.above_k : L.below_k);
+    const double* w = q0.side ? L.above_w : L.below_w;
+    const double* sg = q0.side ? L.above_sigma : L.below_sigma;
+    double sh = -INFINITY;
+    for (int t = m; t < n_ch && ch_tasks[t].li == q0.li && ch_tasks[t].side == q0.side; ++t) {
+      const ChunkTask& q = ch_tasks[t];
+      sh = std::max(sh, comp_terms_f32(w + q.i0, sg + q.i0, q.i1 - q.i0, false, ipa, lv.ch_a + q.scr + q.i0,
+                                       lv.ch_c + q.scr + q.i0));
+    }
+    side_shift[sd] = std::isfinite(sh) ? sh : 0.0;
+    base = side_shift[sd] * kLn2;
+    for (int t = m; t < n_ch && ch_tasks[t].li == q0.li && ch_tasks[t].side == q0.side; ++t) chunk_rows(lv, t);
+  }
+}
+
+// the device-fitted labels' problem fields (the fill cleared their rows), then
+// ---- score tables: 16-B units (a cell row is 3 units, a lattice row 1) ----
+PACK_STEP int step_tabunits(PackScratch& ps, tpe_pack_info& info) {
+  PackLevel& lv = ps.lv;
+  for (size_t k = 0; k < ps.fit.size(); ++k) {
+    const tpe_fit_job& j = ps.fit[k];
+    tpe_problem& p = lv.lab[ps.fit_li[k]];
+    p.above_off = j.above_off; p.above_len = (int32_t)(j.n_obs - j.n_below + 1);
+    p.wide_off = j.wide_off;
+    p.grid_off = j.grid_off; p.grid_n = j.grid_n;
+    p.narrow_amin = 1.f;       // pruned; the fit stage writes the real value
+  }
+  int64_t tab_units = 0, fgt_max_boxes = 0;
+  for (int32_t li = 0; li < lv.n_labels; ++li) {
+    tpe_problem& p = lv.lab[li];
+    const LabelPlan& lp = lv.plan[li];
+    p.tab_mode = lp.tmode;
+    if (lp.tmode == TPE_TAB_CELLS && lp.logpoly) {
+      // one table, both sides' polynomials in each row
+      const int64_t n = lp.n0;
+      p.flags |= TPE_F_LOGPOLY;
+      for (int sd = 0; sd < 2; ++sd) {
+        p.tab_off[sd] = (int32_t)tab_units;
+        p.tab_n[sd] = (int32_t)n;
+        p.tab_lo[sd] = (float)lp.klo;
+        p.tab_inv[sd] = (float)((double)n / (lp.khi - lp.klo));
+      }
+      tab_units += kTabRowUnits * n;
+    } else if (lp.tmode == TPE_TAB_CELLS) {
+      for (int sd = 0; sd < 2; ++sd) {
+        const int64_t n = sd ? lp.n1 : lp.n0;
+        p.tab_off[sd] = (int32_t)tab_units;
+        p.tab_n[sd] = (int32_t)n;
+        p.tab_lo[sd] = (float)lp.klo;
+        p.tab_inv[sd] = (float)((double)n / (lp.khi - lp.klo));
+        tab_units += kTabRowUnits * n;
+      }
+      if (lp.boxes > 0) {                   // box records after the label's cells ("Box moments")
+        const tpe_label_in& L = lv.labels[li];
+        p.flags |= TPE_F_FGT;
+        p.fgt_a = fgt_a(L.prior_sigma, L.above_k);
+        p.fgt_off = (int32_t)tab_units;
+        p.fgt_n = (int32_t)lp.boxes;
+        p.fgt_lo = lp.klo;
+        tab_units += 1 + TPE_FGT_BOX_UNITS * lp.boxes;
+        fgt_max_boxes = std::max(fgt_max_boxes, lp.boxes);
+      }
+    } else if (lp.tmode == TPE_TAB_LATTICE) {
+      p.tab_off[0] = (int32_t)tab_units;
+      p.tab_n[0] = (int32_t)lp.n0;
+      p.lat_lo = lp.lat_lo;
+      tab_units += lp.n0 + (lp.n0 + 1 + 3) / 4;      // {l, g} rows, then n + 1 f32 entry thresholds
+    }
+  }
+  if (tab_units >= ((int64_t)1 << 31)) return TPE_E_ARG;
+  info.tab_units = tab_units;
+  info.fgt_max_boxes = (int32_t)fgt_max_boxes;
+  return TPE_OK;
+}
+
+// a problem row of label li: the label's fields and what every problem of the
+// level shares (the expanded level's templates and the host-written rows)
+PACK_STEP void stamp_problem(const PackLevel& lv, int32_t li, tpe_problem& q) {
+  q = lv.lab[li];
+  q.n_cand = lv.n_cand;
+  q.cand_base = lv.cand_base;
+  q.n_cand_global = lv.C_ref;
+  q.key0 = (uint32_t)lv.seed; q.key1 = (uint32_t)(lv.seed >> 32);
+  q.ctr2 = (uint32_t)lv.labels[li].label_ix;
+  q.n_tiles = (int32_t)lv.n_tiles_p;
+}
+
+// an expanded level's templates (one per label), first problems and new ids
+PACK_STEP void step_expand(PackScratch& ps) {
+  PackLevel& lv = ps.lv;
+  auto& xtmpl = ps.xtmpl;
+  auto& xfirst = ps.xfirst;
+  auto& xctr = ps.xctr;
+  xtmpl.clear(); xfirst.clear(); xctr.clear();
+  if (!lv.expand) return;
+  xtmpl.resize((size_t)lv.n_labels);
+  xfirst.resize((size_t)lv.n_labels + 1);
+  xctr.resize((size_t)lv.P);
+  int64_t r = 0;
+  for (int32_t li = 0; li < lv.n_labels; ++li) {
+    tpe_problem& q = xtmpl[(size_t)li];
+    stamp_problem(lv, li, q);
+    q.cand_off = 0;                     // k_expand: problem r's candidates at r * n_cand
+    q.sort_slot = -1;
+    q.pool_first = -1;
+    q.ctr3 = 0;                         // k_expand: the problem's new id
+    q.tile_off = 0;                     // k_expand: r * n_tiles
+    q.n_splits = 0;                     // tabulated: no above stage
+    xfirst[(size_t)li] = (int32_t)r;
+    const tpe_label_in& L = lv.labels[li];
+    for (int64_t j = 0; j < L.n_ids; ++j) xctr[(size_t)r++] = (uint32_t)L.ids[j];
+  }
+  xfirst[(size_t)lv.n_labels] = (int32_t)r;
+}
+
+// ---- problems (the rows straight into the blob); returns the scored ones ----
+PACK_STEP int64_t step_prob(PackScratch& ps) {
+  PackLevel& lv = ps.lv;
+  lv.Ph = lv.expand ? 0 : lv.P;
+  if (lv.direct) {
+    lv.prob = (tpe_problem*)(lv.bb + lv.off_lead[L_PROB]);
+  } else {
+    ps.prob.resize((size_t)lv.Ph);
+    lv.prob = ps.prob.data();
+  }
+  int64_t scored = 0;
+  if (lv.expand) return scored;
+  const int64_t n_cand = lv.n_cand, n_tiles_p = lv.n_tiles_p;
+  int64_t r = 0, s_next = 0, u_next = lv.n_sorted_prob * n_cand;
+  int32_t slot = 0;
+  for (int32_t li = 0; li < lv.n_labels; ++li) {
+    const tpe_label_in& L = lv.labels[li];
+    const bool pruned = lv.plan[li].pruned, pooled = lv.plan[li].pooled;
+    const int32_t pool_slot = pooled ? slot++ : -1, pool_first = (int32_t)r;
+    for (int64_t j = 0; j < L.n_ids; ++j, ++r) {
+      tpe_problem& q = lv.prob[r];
+      stamp_problem(lv, li, q);
+      int64_t& next = pruned ? s_next : u_next;
+      q.cand_off = next;
+      next += n_cand;
+      q.sort_slot = pooled ? pool_slot : pruned ? slot++ : -1;
+      q.pool_first = pooled ? pool_first : -1;
+      if (pooled) q.flags |= TPE_F_POOLED;
+      q.ctr3 = (uint32_t)L.ids[j];
+      q.tile_off = (int32_t)(r * n_tiles_p);
+      if (q.family != TPE_FAM_CATEGORICAL && q.tab_mode == TPE_TAB_NONE) ++scored;
+    }
+  }
+  return scored;
+}
+
+// ---- tiles, work, finalize tiles (the tiles straight into the blob) ----
+// splits of the above mixture per tile.  Bulk tiles: enough work items to fill
+// the chip (a function of the GLOBAL candidate count).  Pruned problems with
+// many tiles: the bulk is cheap (local expansion), so one split, and the
+// outermost tiles of the (local) sorted range — the sparse tails, whose waves
+// span wide windows evaluated exactly — get geometrically more.  A shard sorts
+// and windows only its own candidates and counts its tails in its own tiles,
+// so under candidate sharding the fp32 sums (and near-tie winners) can differ
+// from a single-device run in the last bits: sharded winners agree within the
+// eps-tie set, not bit for bit (the draws themselves are identical).
+PACK_STEP int step_tiles_work_fin(PackScratch& ps, int64_t scored, tpe_pack_info& info) {
+  PackLevel& lv = ps.lv;
+  const int T = kPackTile;
+  const int64_t Ph = lv.Ph, n_tiles_p = lv.n_tiles_p;
+  tpe_problem* prob = lv.prob;
+  const int64_t tiles_ref = (lv.C_ref + T - 1) / T;
+  const int64_t scored_tiles = scored * tiles_ref;
+  const int64_t target = std::max<int64_t>(1, (target_work() + std::max<int64_t>(scored_tiles, 1) - 1) /
+                                                  std::max<int64_t>(scored_tiles, 1));
+  bool any_pruned = false;
+  for (int64_t r = 0; r < Ph; ++r) {
+    tpe_problem& q = prob[r];
+    if (q.family == TPE_FAM_CATEGORICAL || q.tab_mode != TPE_TAB_NONE) { q.n_splits = 0; continue; }
+    const int64_t ks = (q.above_len + kMinComponentsPerSplit - 1) / kMinComponentsPerSplit;
+    const bool tails = q.sort_slot >= 0 && tiles_ref >= kTailMinTiles;
+    q.n_splits = tails ? 1 : (int32_t)std::max<int64_t>(1, std::min(target, ks));
+    any_pruned = any_pruned || q.sort_slot >= 0;
+  }
+  auto tile_splits = [&](const tpe_problem& q, int64_t j) -> int32_t {
+    if (q.family == TPE_FAM_CATEGORICAL || q.tab_mode != TPE_TAB_NONE) return 0;
+    if (!(q.sort_slot >= 0 && tiles_ref >= kTailMinTiles)) return q.n_splits;
+    const int64_t e = std::min<int64_t>(j, n_tiles_p - 1 - j);
+    const int64_t ns = tail_splits(e);
+    const int64_t cap = std::max<int64_t>(1, (q.above_len + 63) / 64);
+    return (int32_t)std::max<int64_t>(1, std::min(ns, cap));
+  };
+  tpe_tile* tiles;
+  if (lv.direct) {
+    tiles = (tpe_tile*)(lv.bb + lv.off_lead[L_TILES]);
+  } else {
+    ps.tiles.resize((size_t)(Ph * n_tiles_p));
+    tiles = ps.tiles.data();
+  }
+  {
+    tpe_tile* __restrict__ tp = tiles;
+    for (int64_t r = 0; r < Ph; ++r) {
+      tpe_tile* __restrict__ row = tp + r * n_tiles_p;
+      const bool none = prob[r].family == TPE_FAM_CATEGORICAL || prob[r].tab_mode != TPE_TAB_NONE;
+      for (int64_t j = 0; j < n_tiles_p; ++j) {
+        row[j].problem = (int32_t)r;
+        row[j].cand_start = (int32_t)(j * T);
+        row[j].work_first = 0;
+        row[j].n_splits = none ? 0 : tile_splits(prob[r], j);
+      }
+    }
+  }
+  // work items grouped [continuous | quantized Gauss | quantized log]; a tile's
+  // items are consecutive, and an item's index is its row of `part`
+  auto& work = ps.work;
+  work.clear();
+  {
+    int64_t nw = 0;
+    for (int64_t t = 0; t < Ph * n_tiles_p; ++t) nw += tiles[t].n_splits;
+    work.reserve((size_t)nw);
+  }
+  int32_t counts[3] = {0, 0, 0};
+  const int fams[3][2] = {{TPE_FAM_GAUSS, TPE_FAM_LOGGAUSS}, {TPE_FAM_QGAUSS, -1}, {TPE_FAM_QLOGGAUSS, -1}};
+  for (int gi = 0; gi < 3; ++gi) {
+    const size_t before = work.size();
+    for (int64_t r = 0; r < Ph; ++r) {
+      const tpe_problem& q = prob[r];
+      if ((q.family != fams[gi][0] && q.family != fams[gi][1]) || q.tab_mode != TPE_TAB_NONE) continue;
+      for (int64_t j = 0; j < n_tiles_p; ++j) {
+        tpe_tile& tl = tiles[(size_t)(r * n_tiles_p + j)];
+        tl.work_first = (int32_t)work.size();
+        for (int32_t sp = 0; sp < tl.n_splits; ++sp) {
+          tpe_work w;
+          w.problem = (int32_t)r; w.split = sp; w.cand_start = (int32_t)(j * T);
+          w.k_start = (int32_t)(((int64_t)q.above_len * sp) / tl.n_splits);
+          w.k_end = (int32_t)(((int64_t)q.above_len * (sp + 1)) / tl.n_splits);
+          w.n_splits = tl.n_splits;
+          work.push_back(w);
+        }
+      }
+    }
+    counts[gi] = (int32_t)(work.size() - before);
+  }
+  if ((int64_t)work.size() >= ((int64_t)1 << 31)) return TPE_E_ARG;
+  // tiles the finalize stage scores (device-drawn candidates): not categorical
+  // (the sample stage scores those), not one-split continuous f32 (the above
+  // stage does)
+  auto& fin_tiles = ps.fin_tiles;
+  fin_tiles.clear();
+  for (int64_t r = 0; r < Ph; ++r) {                 // (per problem: a problem's tiles are consecutive)
+    const tpe_problem& q = prob[r];
+    if ((q.family == TPE_FAM_CATEGORICAL && q.samp_len <= TPE_SAMPLE_LDS_ROWS) || q.tab_mode != TPE_TAB_NONE) continue;
+    const bool cont = !lv.f64 && (q.family == TPE_FAM_GAUSS || q.family == TPE_FAM_LOGGAUSS);
+    for (int64_t t = r * n_tiles_p; t < (r + 1) * n_tiles_p; ++t)
+      if (!(cont && tiles[t].n_splits == 1)) fin_tiles.push_back((int32_t)t);
+  }
+  info.n_work_cont = counts[0]; info.n_work_qgauss = counts[1]; info.n_work_qlog = counts[2];
+  info.part_total = (int64_t)work.size() * T;
+  info.any_pruned = any_pruned ? 1 : 0;
+  info.n_fin_tiles = (int64_t)fin_tiles.size();
+  if (fin_tiles.empty()) fin_tiles.push_back(0);
+  return TPE_OK;
+}
+
+// table jobs: per tabulated label, one per cell side or one lattice job
+// (TPE_TAB_PER_BLOCK rows per block); `problem` = the label's first row.  Then
+// the sample-stage tile lists: untabulated tiles (lazy categorical last) and
+// tabulated tiles
+PACK_STEP int step_jobs_lists(PackScratch& ps, tpe_pack_info& info) {
+  PackLevel& lv = ps.lv;
+  const int64_t Ph = lv.Ph, n_tiles_p = lv.n_tiles_p;
+  const tpe_problem* prob = lv.prob;
+  auto& tab_jobs = ps.tab_jobs;
+  tab_jobs.clear();
+  int64_t tab_blocks = 0, fgt_max_cells = 0;
+  for (int32_t li = 0, r = 0; li < lv.n_labels; r += (int32_t)lv.labels[li].n_ids, ++li) {
+    const tpe_problem& p = lv.lab[li];
+    if (p.tab_mode == TPE_TAB_NONE || lv.labels[li].n_ids <= 0) continue;
+    const int sides = p.tab_mode == TPE_TAB_CELLS ? 2 : 1;
+    for (int sd = 0; sd < sides; ++sd) {
+      tpe_tab_job j;
+      memset(&j, 0, sizeof(j));
+      j.problem = r; j.side = sd; j.kind = p.tab_mode; j.n = p.tab_n[sd]; j.off = p.tab_off[sd];
+      j.block0 = (int32_t)tab_blocks;
+      if (j.kind == TPE_TAB_CELLS) {
+        if (p.flags & TPE_F_LOGPOLY) j.kind = TPE_TAB_LOGPOLY;
+        // the rows the side's cells sum (a device-fitted above side: its fit writes them)
+        j.rows_off = sd ? p.above_off : p.below_off;
+        j.rows_n = sd && lv.plan[li].dev_fit ? -1 : sd ? p.above_len : p.below_len;
+        j.wide_off = sd ? p.wide_off : 0;
+        j.wide_n = sd ? p.wide_len : 0;
+        j.lo = p.tab_lo[sd];
+        j.inv = p.tab_inv[sd];
+      }
+      // cells: TPE_TAB_PER_BLOCK rows per block; lattice: one block per value
+      // (a box-moment label's above cells are built by their own stage: no blocks here)
+      if (sd == 1 && (p.flags & TPE_F_FGT)) fgt_max_cells = std::max<int64_t>(fgt_max_cells, j.n);
+      else if (j.kind == TPE_TAB_LOGPOLY && j.rows_n >= 0 && j.rows_n + j.wide_n <= kLpDirectRows)
+        tab_blocks += (j.n + kLpRowsPerWave * TPE_TAB_PER_BLOCK - 1) / (kLpRowsPerWave * TPE_TAB_PER_BLOCK);
+      else if (j.kind == TPE_TAB_CELLS && j.rows_n >= 0 && j.rows_n + j.wide_n <= kMomDirectRows)
+        tab_blocks += (j.n + kMomCellsPerWave * TPE_TAB_PER_BLOCK - 1) / (kMomCellsPerWave * TPE_TAB_PER_BLOCK);
+      else tab_blocks += j.kind != TPE_TAB_LATTICE ? (j.n + TPE_TAB_PER_BLOCK - 1) / TPE_TAB_PER_BLOCK : j.n;
+      tab_jobs.push_back(j);
+    }
+  }
+  if (tab_blocks >= ((int64_t)1 << 31)) return TPE_E_ARG;
+  auto& samp_tiles = ps.samp_tiles;
+  auto& tab_tiles = ps.tab_tiles;
+  samp_tiles.clear(); tab_tiles.clear();
+  auto append_range = [&](std::vector<int32_t>& v, int64_t r) {
+    const size_t b = v.size();
+    v.resize(b + (size_t)n_tiles_p);
+    int32_t* __restrict__ d = v.data() + b;
+    for (int64_t j = 0; j < n_tiles_p; ++j) d[j] = (int32_t)(r * n_tiles_p + j);
+  };
+  int64_t n_samp_eager = 0;
+  for (int pass = 0; pass < 2; ++pass)
+    for (int64_t r = 0; r < Ph; ++r) {
+      const tpe_problem& q = prob[r];
+      if (q.tab_mode != TPE_TAB_NONE) {
+        if (pass == 0) append_range(tab_tiles, r);
+        continue;
+      }
+      const bool lazy = q.family == TPE_FAM_CATEGORICAL && (q.flags & TPE_F_CAT_LAZY) && q.samp_len <= 64;
+      if (lazy == (pass == 1)) append_range(samp_tiles, r);
+      if (pass == 0 && !lazy) n_samp_eager += n_tiles_p;
+    }
+  info.n_tab_jobs = (int64_t)tab_jobs.size(); info.tab_blocks = tab_blocks;
+  info.fgt_max_cells = fgt_max_cells;
+  info.n_samp_tiles = (int64_t)samp_tiles.size(); info.n_samp_eager = n_samp_eager;
+  // (expanded: every tile is tabulated, in order — the identity list, not stored)
+  info.n_tab_tiles = lv.expand ? lv.P * n_tiles_p : (int64_t)tab_tiles.size();
+  if (samp_tiles.empty()) samp_tiles.push_back(0);
+  if (tab_tiles.empty()) tab_tiles.push_back(0);
+  if (tab_jobs.empty()) tab_jobs.push_back(tpe_tab_job{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0.f, 0.f});
+  return TPE_OK;
+}
+
+// ---- the later sections after the leading ones (256-B aligned) ----
+enum { S_WORK, S_FIN, S_JOBS, S_SAMP_TILES, S_TAB_TILES, S_EXPAND, NS };
+struct LateSections {
+  const void* src[NS];
+  int64_t len[NS], off[NS];
+  // expanded levels: templates, first problems, new ids (one section, 256-B aligned parts)
+  int64_t x_tmpl, x_first_off, x_ctr_off;
+};
+
+// places the later sections and fills the rest of info
+PACK_STEP void step_offsets(PackScratch& ps, tpe_pack_info* info, LateSections& ls) {
+  PackLevel& lv = ps.lv;
+  ls.x_tmpl = (int64_t)(ps.xtmpl.size() * sizeof(tpe_problem));
+  ls.x_first_off = (ls.x_tmpl + 255) & ~(int64_t)255;
+  ls.x_ctr_off = (ls.x_first_off + (int64_t)(ps.xfirst.size() * sizeof(int32_t)) + 255) & ~(int64_t)255;
+  const int64_t x_len = lv.expand ? ls.x_ctr_off + (int64_t)(ps.xctr.size() * sizeof(uint32_t)) : 0;
+  const void* src[NS] = {ps.work.data(), ps.fin_tiles.data(), ps.tab_jobs.data(), ps.samp_tiles.data(),
+                         ps.tab_tiles.data(), nullptr};
+  const int64_t len[NS] = {(int64_t)(ps.work.size() * sizeof(tpe_work)), (int64_t)(ps.fin_tiles.size() * sizeof(int32_t)),
+                           (int64_t)(ps.tab_jobs.size() * sizeof(tpe_tab_job)),
+                           (int64_t)(ps.samp_tiles.size() * sizeof(int32_t)),
+                           lv.expand ? 0 : (int64_t)(ps.tab_tiles.size() * sizeof(int32_t)), x_len};
+  int64_t end = lv.lead_end;
+  for (int i = 0; i < NS; ++i) {
+    ls.src[i] = src[i]; ls.len[i] = len[i];
+    ls.off[i] = (end + 255) & ~(int64_t)255;
+    end = ls.off[i] + len[i];
+  }
+  const int64_t* off_lead = lv.off_lead;
+  info->off_problems = off_lead[L_PROB]; info->off_tiles = off_lead[L_TILES];
+  info->off_comp64 = off_lead[L_C64]; info->off_samp = off_lead[L_SAMP];
+  info->off_work = ls.off[S_WORK];
+  info->off_fin_tiles = ls.off[S_FIN];
+  info->off_tab_jobs = ls.off[S_JOBS];
+  info->off_samp_tiles = ls.off[S_SAMP_TILES];
+  info->off_tab_tiles = ls.off[S_TAB_TILES];
+  info->off_expand = lv.expand ? ls.off[S_EXPAND] : 0;
+  info->n_expand = lv.expand ? lv.n_labels : 0;
+  // host-written ranges (the upload): fit sections + host grid, host comp32
+  // rows, then problems (unless expanded: device-only) through the end
+  info->n_up = 0;
+  auto up = [&](int64_t o, int64_t n) {
+    if (n > 0) { info->up_off[info->n_up] = o; info->up_len[info->n_up] = n; ++info->n_up; }
+  };
+  up(0, off_lead[L_GRID] + lv.host_grid * 4);
+  up(off_lead[L_C32], lv.host_rows * 16);
+  const int64_t r3 = lv.expand ? off_lead[L_C64] : off_lead[L_PROB];
+  up(r3, end - r3);
+  info->n_tiles = lv.P * lv.n_tiles_p;
+  info->key_bits = lv.key_bits;
+  info->sort_end_bit = info->any_pruned ? lv.sort_end_bit : 0;
+  info->sort_count = lv.n_sorted_prob * (int64_t)lv.n_cand;
+  info->n_sorted = lv.S;
+  info->n_pooled = lv.n_pooled;
+  info->draw_blocks = (lv.C_ref + 1 + 63) / 64;
+  info->blob_bytes = end;
+}
+
+// the later sections into the blob; a large level's in 64-KiB pieces on the
+// worker pool (a batched level's work items)
+PACK_STEP void step_copy(PackScratch& ps, const LateSections& ls) {
+  struct Piece { unsigned char* dst; const unsigned char* src; size_t n; };
+  static thread_local std::vector<Piece> pieces_tl;
+  std::vector<Piece>& pieces = pieces_tl;
+  pieces.clear();
+  constexpr size_t kPiece = 64 << 10;
+  size_t total = 0;
+  for (int i = 0; i < NS; ++i) {
+    if (!ls.len[i] || !ls.src[i]) continue;
+    for (size_t o = 0; o < (size_t)ls.len[i]; o += kPiece)
+      pieces.push_back(Piece{ps.lv.bb + ls.off[i] + o, (const unsigned char*)ls.src[i] + o,
+                             std::min(kPiece, (size_t)ls.len[i] - o)});
+    total += (size_t)ls.len[i];
+  }
+  auto copy = [](void* c, int k) {
+    const Piece& q = (*(const std::vector<Piece>*)c)[(size_t)k];
+    memcpy(q.dst, q.src, q.n);
+  };
+  if (total >= (128u << 10) && pieces.size() > 1) tpe_pool::parallel_for((int)pieces.size(), copy, &pieces);
+  else for (size_t k = 0; k < pieces.size(); ++k) copy(&pieces, (int)k);
+}
+
+PACK_STEP void step_xcopy(PackScratch& ps, const LateSections& ls) {
+  if (!ps.lv.expand) return;
+  unsigned char* x = ps.lv.bb + ls.off[S_EXPAND];
+  memcpy(x, ps.xtmpl.data(), (size_t)ls.x_tmpl);
+  memcpy(x + ls.x_first_off, ps.xfirst.data(), ps.xfirst.size() * sizeof(int32_t));
+  memcpy(x + ls.x_ctr_off, ps.xctr.data(), ps.xctr.size() * sizeof(uint32_t));
 }
 
 }  // namespace
@@ -1081,824 +1934,101 @@ int tpe_host_cat_split(const int64_t* obs, const int64_t* tids, int64_t n, const
   return tpe_host_cat_probs(ap, n - nb, upper, p_prior, prior_weight, lf, out_above);
 }
 
-// the level runner's early-fit hook (tpe_level_run): called on the packing
-// thread once the blob's leading sections are placed and the fit jobs written,
-// before the fill — so the device fit runs while the host fills the rest
-static thread_local TpePackHook g_pack_hook = {nullptr, nullptr};
-
-__attribute__((visibility("hidden"))) void tpe_internal_pack_hook(TpePackHook h) { g_pack_hook = h; }
-
-// the pack's straight-line table loops vectorise: an AVX2 clone is picked at
-// load time on hosts that have it (-ffp-contract=off holds in both clones, so
-// the tables are bit-identical)
+// tpe_host_pack_level's two steps (tpe_pool.h): the plan, up to the point where
+// the device fit of the level can be launched, and the fill.  (The clones on
+// functions of internal linkage: a cloned function's dispatcher symbol ignores
+// hidden visibility and would be exported.)
 __attribute__((target_clones("avx512f", "avx2", "default")))
-// (TPE_PACK_TRACE builds, tools/pack_time*.py: the packer's sections timed)
+static int pack_plan(const tpe_label_in* labels, int32_t n_labels, int32_t n_cand, uint64_t seed, int64_t cand_base,
+                     int64_t n_cand_global, int32_t precision, void* blob, int64_t blob_cap, tpe_pack_info* info,
+                     TpePackLead* lead) {
+  if (!info || !lead || n_labels < 0 || n_cand < 0 || (n_labels && !labels)) return TPE_E_ARG;
+  PackScratch& ps = pack_scratch();
 #ifdef TPE_PACK_TRACE
-#define PACK_MARK(name) pack_marks.emplace_back(name, std::chrono::steady_clock::now())
-#define PACK_DONE()                                                                              \
-  do {                                                                                           \
-    for (size_t i_ = 1; i_ < pack_marks.size(); ++i_)                                            \
-      fprintf(stderr, "pack %-16s %8.1f us\n", pack_marks[i_].first,                             \
-              std::chrono::duration<double, std::micro>(pack_marks[i_].second - pack_marks[i_ - 1].second).count()); \
-  } while (0)
-#else
-#define PACK_MARK(name) (void)0
-#define PACK_DONE() (void)0
+  ps.marks.clear();
 #endif
-
-int tpe_host_pack_level(const tpe_label_in* labels, int32_t n_labels, int32_t n_cand, uint64_t seed,
-                        int64_t cand_base, int64_t n_cand_global, int32_t precision, void* blob, int64_t blob_cap,
-                        tpe_pack_info* info) {
-#ifdef TPE_PACK_TRACE
-  std::vector<std::pair<const char*, std::chrono::steady_clock::time_point>> pack_marks;
   PACK_MARK("entry");
-#endif
-  if (!info || n_labels < 0 || n_cand < 0 || (n_labels && !labels)) return TPE_E_ARG;
-  const bool f64 = precision == TPE_PREC_F64;
-  const int T = 2048;
-  // staging tables: per-thread, reused across calls (no first-touch page faults
-  // on the large ones — a batched level has ~10^5 problems, tiles and work items)
-  // (one thread-local lookup: references to its members stay in registers —
-  // a thread_local named inside a loop costs a TLS call per use in a shared object)
-  static thread_local PackScratch tls_scratch;
-  PackScratch& ps = tls_scratch;
-  auto& comp32 = ps.comp32;     // float4 rows
-  auto& comp64 = ps.comp64;     // double4 rows
-  auto& samp = ps.samp;         // 8 doubles per row
-  auto& grid = ps.grid;
-  std::vector<tpe_problem> lab((size_t)n_labels);
-  int64_t P = 0;
-  std::vector<char> dev_fit((size_t)n_labels, 0);   // above mixture fitted on the device
-  for (int32_t li = 0; li < n_labels; ++li) {
-    const tpe_label_in& L = labels[li];
-    P += L.n_ids;
-    if (L.dev_obs && !L.above_mu) {
-      if ((L.family != TPE_FAM_GAUSS && L.family != TPE_FAM_LOGGAUSS) || f64 || L.n_below < 0 || L.n_below > 64 ||
-          (L.n_below > 0 && !L.below_idx) || L.n_obs - L.n_below + 1 != L.above_k || L.above_k <= kPruneMinK ||
-          L.n_obs >= ((int64_t)1 << 31) || L.n_ord_in < 0 || L.n_ord_in > L.n_obs ||
-          (L.n_ord_in > 0 && (!L.ord_key_in || !L.ord_idx_in)) ||
-          (L.n_ord_in < L.n_obs && (!L.ord_key_out || !L.ord_idx_out) &&
-           !(L.n_ord_in > 0 && L.n_obs - L.n_ord_in <= TPE_FIT_DELTA_MAX && !L.ord_key_out && !L.ord_idx_out)))
-        return TPE_E_ARG;
-      dev_fit[li] = 1;
-    }
-  }
+  PackLevel& lv = ps.lv;
+  lv.labels = labels; lv.n_labels = n_labels; lv.n_cand = n_cand; lv.seed = seed;
+  lv.cand_base = cand_base; lv.C_ref = n_cand_global > 0 ? n_cand_global : n_cand;
+  lv.f64 = precision == TPE_PREC_F64;
+  lv.bb = (unsigned char*)blob; lv.blob_cap = blob_cap;
+  int rc;
+  if ((rc = step_devfit(ps))) return rc;
   PACK_MARK("devfit");
-  // ---- tabulated scoring: which labels score from tables, and their geometry ----
-  const bool tab_on = tables_enabled();
-  std::vector<int32_t> tmode((size_t)n_labels, TPE_TAB_NONE);
-  std::vector<int64_t> tn0((size_t)n_labels, 0), tn1((size_t)n_labels, 0), tlat((size_t)n_labels, 0);
-  std::vector<double> tklo((size_t)n_labels, 0), tkhi((size_t)n_labels, 0);
-  std::vector<int64_t> fgt_boxes((size_t)n_labels, 0);   // box-moment labels: their boxes
-  std::vector<char> logpoly((size_t)n_labels, 0);         // TPE_F_LOGPOLY labels
-  if (tab_on && n_cand > 0) {
-    const TabCtx tcx{labels, dev_fit.data(), n_cand, f64, logpoly_enabled(), fgt_enabled(), devfit_ratio(),
-                     tmode.data(), tn0.data(), tn1.data(), tlat.data(), tklo.data(), tkhi.data(), fgt_boxes.data(),
-                     logpoly.data()};
-    // (a label's decision reads its whole above mixture: thousands of
-    // components per label make a worker's hand-off worth it; a device-fitted
-    // label's reads only its below side — config 5's 125 labels a rank decide in
-    // 5 us on one thread, 11-14 us handed out)
-    int64_t comps = 0;
-    for (int32_t li = 0; li < n_labels; ++li) comps += dev_fit[li] ? labels[li].below_k : labels[li].above_k;
-    // (in chunks of up to kTabChunk labels: a thousand-label level's decisions
-    // are sub-microsecond each, too small to hand out one by one; a few large
-    // labels — config 4's twenty of 10^4 components — one a task)
-    struct Chunked { const TabCtx* cx; int32_t n, per; };
-    const int32_t per = std::max<int32_t>(1, std::min<int32_t>(kTabChunk, n_labels / (4 * (1 + tpe_pool::workers()))));
-    const Chunked ch{&tcx, n_labels, per};
-    if (n_labels >= 2 && comps >= 16384)
-      tpe_pool::parallel_for((n_labels + per - 1) / per, [](void* c, int k) {
-        const Chunked& q = *(const Chunked*)c;
-        for (int32_t li = k * q.per; li < std::min(q.n, (k + 1) * q.per); ++li) decide_table(*q.cx, li);
-      }, (void*)&ch);
-    else
-      for (int32_t li = 0; li < n_labels; ++li) decide_table(tcx, li);
-  }
+  step_tmode(ps);
   PACK_MARK("tmode");
-  // Pruned problems (continuous f32 above mixtures of more than kPruneMinK
-  // components, not tabulated) are the only ones whose candidates are sorted; they own the
-  // candidate range [0, sort_count).  Sort key = sort_slot << key_bits | value
-  // bucket: one 8-bit radix pass up to 8 sorted problems, never below 32
-  // buckets per problem.  Large candidate sets get 4096 buckets (two passes):
-  // a wave of 512 sorted candidates then spans ~1/8 of a bucket's density,
-  // narrow enough for the above kernel's local expansion.
-  // A pruned label active for several ids is POOLED: its problems share one
-  // sort slot and are sorted as one population (include/tpe_hip.h).
-  std::vector<char> pruned((size_t)n_labels, 0), pooled((size_t)n_labels, 0);
-  int64_t S = 0, n_sorted_prob = 0, n_pooled = 0, max_slot_cand = 0;   // S: sort slots
-  for (int32_t li = 0; li < n_labels; ++li) {
-    const tpe_label_in& L = labels[li];
-    pruned[li] = !f64 && (L.family == TPE_FAM_GAUSS || L.family == TPE_FAM_LOGGAUSS) &&
-                 (dev_fit[li] || L.above_k > kPruneMinK) && tmode[li] == TPE_TAB_NONE;
-    pooled[li] = pruned[li] && L.n_ids >= 2;
-    if (!pruned[li]) continue;
-    S += pooled[li] ? 1 : L.n_ids;
-    n_sorted_prob += L.n_ids;
-    if (pooled[li]) n_pooled += L.n_ids;
-    max_slot_cand = std::max(max_slot_cand, (pooled[li] ? L.n_ids : 1) * (int64_t)n_cand);
-  }
-  int pbits = 0;
-  while (((int64_t)1 << pbits) < S) ++pbits;
-  int key_bits = std::max(5, 8 - pbits);
-  if (max_slot_cand >= kFineKeyMinCand) key_bits = std::max(key_bits, std::min(fine_key_bits(), 16 - pbits));
-  const int sort_end_bit = S > 0 && key_bits + pbits <= 32 ? key_bits + pbits : 0;
+  step_prune(ps);
   PACK_MARK("prune");
-  // ---- per-label sections: every label's sampler rows, component rows, wide
-  // rows and pruning grid get their offsets first (label order, as appended
-  // one after another), then each label fills its own sections — on the host
-  // worker threads when the level has enough components (labels independent) ----
-  std::vector<LabelSec> sec((size_t)n_labels);
-  int64_t n_samp = 0, n_c64 = 0, n_c32 = 0, n_grid = 0, work_k = 0;
-  for (int32_t li = 0; li < n_labels; ++li) {
-    const tpe_label_in& L = labels[li];
-    LabelSec& q = sec[(size_t)li];
-    q.samp = n_samp; n_samp += L.below_k;
-    // (a label's fill beyond its rows: the sampler rows' four erfc a below
-    // component and a fixed part — a thousand device-fitted labels of 26 host
-    // components each are 3.7 us of fill a label, worth the workers)
-    work_k += 4 * L.below_k + 64;
-    q.c64[0] = q.c64[1] = q.c32[0] = q.c32[1] = q.wide = q.grid = -1;
-    const bool rows64 = L.family == TPE_FAM_CATEGORICAL || L.family == TPE_FAM_QGAUSS ||
-                        L.family == TPE_FAM_QLOGGAUSS || f64;
-    for (int side = 0; side < 2 - dev_fit[li]; ++side) {
-      const int64_t k = side ? L.above_k : L.below_k;
-      work_k += k;
-      if (rows64) { q.c64[side] = n_c64; n_c64 += k; continue; }
-      q.c32[side] = n_c32; n_c32 += k;
-      if (side == 1 && k > kPruneMinK && tmode[li] == TPE_TAB_NONE) {   // wide rows + grid (pruned)
-        q.wide = n_c32; n_c32 += std::min<int64_t>(kPruneWide, k);
-        q.grid = n_grid; n_grid += std::min<int64_t>(4096, 4 * k) + 1;
-      }
-    }
-  }
+  step_sizing(ps);
   PACK_MARK("sizing");
-  // ---- device-fitted above mixtures: rows and grids after the host ones, fit
-  // jobs (before the fill: the level runner may launch the fit right away) ----
-  // (the device grid starts 256-B aligned: the host part's upload never
-  // touches a word the fit wrote)
-  const int64_t host_rows = n_c32, host_grid = std::max<int64_t>(n_grid, 1);
-  const int64_t host_grid_pad = (host_grid + 63) & ~(int64_t)63;
-  std::vector<tpe_fit_job> fit;
-  std::vector<int32_t> below_idx;
-  std::vector<int64_t> fit_seg(1, 0);
-  std::vector<int32_t> fit_li;          // each fit job's label
-  {
-    int64_t nf = 0, nb = 0;
-    for (int32_t li = 0; li < n_labels; ++li)
-      if (dev_fit[li]) { ++nf; nb += std::max<int32_t>(labels[li].n_below, 0); }
-    fit.reserve((size_t)nf); below_idx.reserve((size_t)nb + 1); fit_seg.reserve((size_t)nf + 1);
-  }
-  int64_t dev_rows = 0, dev_grid = 0, fit_max_new = 0, fit_max_obs = 0, fit_max_merge = 0, fit_n_delta = 0;
-  {
-    int64_t r = 0;
-    for (int32_t li = 0; li < n_labels; ++li) {
-      const tpe_label_in& L = labels[li];
-      if (dev_fit[li]) {
-        const int64_t K = L.above_k, G = std::min<int64_t>(4096, 4 * K);
-        tpe_fit_job j;
-        memset(&j, 0, sizeof(j));
-        j.obs = L.dev_obs; j.n_obs = L.n_obs; j.seg_off = fit_seg.back();
-        j.below_off = (int32_t)below_idx.size(); j.n_below = L.n_below;
-        j.family = L.family; j.flags = L.flags; j.lf = L.lf;
-        j.problem_first = (int32_t)r; j.n_problems = (int32_t)L.n_ids;
-        j.above_off = (int32_t)(host_rows + dev_rows); j.wide_off = (int32_t)(host_rows + dev_rows + K);
-        j.grid_off = (int32_t)(host_grid_pad + dev_grid); j.grid_n = (int32_t)G;
-        j.prior_mu = L.prior_mu; j.prior_sigma = L.prior_sigma; j.prior_weight = L.prior_weight;
-        j.low = L.low; j.high = L.high;
-        j.ord_key_in = L.ord_key_in; j.ord_idx_in = L.ord_idx_in; j.n_ord_in = L.n_ord_in;
-        j.ord_key_out = L.ord_key_out; j.ord_idx_out = L.ord_idx_out;
-        for (int32_t b = 0; b < L.n_below; ++b) {
-          if (L.below_idx[b] < 0 || L.below_idx[b] >= L.n_obs || (b && L.below_idx[b] <= L.below_idx[b - 1]))
-            return TPE_E_ARG;
-          below_idx.push_back(L.below_idx[b]);
-        }
-        fit.push_back(j);
-        fit_li.push_back(li);
-        // scratch segment: the compacted above order, the new observations' merge
-        // passes and the below positions all fit in it
-        const int64_t n_new = L.n_obs - L.n_ord_in;
-        // (delta mode: the delta arrays, then a slot of kFitStageStretch entries per
-        // 2048-component chunk for the chunks whose stretch holds a delta entry)
-        const int64_t slots = !L.ord_key_out && n_new > 0 ? ((K + 2047) / 2048) * kFitStageStretch : 0;
-        fit_seg.push_back(fit_seg.back() + std::max<int64_t>(std::max<int64_t>(K - 1, n_new),
-                                                             std::max<int64_t>(L.n_below, 64 + 2 * TPE_FIT_DELTA_MAX + slots)));
-        fit_max_new = std::max(fit_max_new, n_new);
-        if (L.ord_key_out) fit_max_merge = std::max(fit_max_merge, n_new);
-        else fit_n_delta += n_new > 0;          // (delta mode)
-        fit_max_obs = std::max<int64_t>(fit_max_obs, L.n_obs);
-        dev_rows += K + kPruneWide;
-        dev_grid += G + 1;
-      }
-      r += L.n_ids;
-    }
-  }
-  if (host_rows + dev_rows >= ((int64_t)1 << 31) || host_grid_pad + dev_grid >= ((int64_t)1 << 31)) return TPE_E_ARG;
-  if (below_idx.empty()) below_idx.push_back(0);
+  if ((rc = step_devrows(ps))) return rc;
   PACK_MARK("devrows");
-  // ---- expanded levels (include/tpe_hip.h "Expanded levels"): when every label
-  // of a large level scores from tables, its problems differ from their label's
-  // only in (cand_off, ctr3, tile_off) and its tiles are {problem, j * T, 0, 0}
-  // in order: the host writes one template per label and the new ids, the
-  // device (k_expand) writes the problems and tiles — ~240 B + 32 B per (label,
-  // id) neither packed nor uploaded ----
-  const int64_t n_tiles_p = n_cand > 0 ? (n_cand + T - 1) / T : 0;
-  bool expand = expand_enabled() && !f64 && P >= kExpandMinProblems && n_tiles_p > 0;
-  for (int32_t li = 0; li < n_labels && expand; ++li)
-    if (labels[li].n_ids > 0 && tmode[li] == TPE_TAB_NONE) expand = false;
-  // ---- the blob's leading sections, placed before the fill (the fill writes
-  // its sections in place; the device fit may run while it does):
-  //   fit jobs | below positions | fit segments | grid (host | device, 256-B
-  //   aligned) | comp32 (host | device) | fit patches (device only: the problem
-  //   fields the fit writes, applied after the upload) | problems | tiles
-  //   (device only when expanded) | comp64 | sampler rows
-  // then the later sections (work, finalize tiles, table jobs, tile lists, the
-  // expanded level's templates) after them ----
-  const int NL = 10;
-  const int64_t len_lead[NL] = {(int64_t)(fit.size() * sizeof(tpe_fit_job)), (int64_t)(below_idx.size() * sizeof(int32_t)),
-                                (int64_t)(fit_seg.size() * sizeof(int64_t)), (host_grid_pad + dev_grid) * 4,
-                                (host_rows + dev_rows) * 16, fit.empty() ? 0 : P * (int64_t)sizeof(tpe_problem),
-                                P * (int64_t)sizeof(tpe_problem), P * n_tiles_p * (int64_t)sizeof(tpe_tile),
-                                n_c64 * 32, n_samp * 64};
-  int64_t off_lead[NL], lead_end = 0;
-  for (int i = 0; i < NL; ++i) {
-    off_lead[i] = (lead_end + 255) & ~(int64_t)255;
-    lead_end = off_lead[i] + len_lead[i];
-  }
-  enum { L_FIT, L_BIDX, L_FSEG, L_GRID, L_C32, L_PATCH, L_PROB, L_TILES, L_C64, L_SAMP };
-  // the fill's targets: the blob itself when it holds the leading sections,
-  // else the scratch (the call then only sizes the level: TPE_E_SPACE)
-  const bool direct = blob != nullptr && blob_cap >= lead_end;
-  unsigned char* const bb = (unsigned char*)blob;
-  float* f_comp32;
-  double *f_comp64, *f_samp;
-  int32_t* f_grid;
-  if (direct) {
-    f_comp32 = (float*)(bb + off_lead[L_C32]);
-    f_comp64 = (double*)(bb + off_lead[L_C64]);
-    f_samp = (double*)(bb + off_lead[L_SAMP]);
-    f_grid = (int32_t*)(bb + off_lead[L_GRID]);
-  } else {
-    // (trivially typed: a resize to the same size as the last call touches nothing)
-    comp32.resize((size_t)(4 * n_c32));
-    comp64.resize((size_t)(4 * n_c64));
-    samp.resize((size_t)(8 * n_samp));
-    grid.resize((size_t)host_grid);
-    f_comp32 = comp32.data(); f_comp64 = comp64.data(); f_samp = samp.data(); f_grid = grid.data();
-  }
-  f_grid[0] = 0;
-  if (direct && !fit.empty()) {
-    memcpy(bb + off_lead[L_FIT], fit.data(), (size_t)len_lead[L_FIT]);
-    memcpy(bb + off_lead[L_BIDX], below_idx.data(), (size_t)len_lead[L_BIDX]);
-    memcpy(bb + off_lead[L_FSEG], fit_seg.data(), (size_t)len_lead[L_FSEG]);
-    if (g_pack_hook.fn) {
-      // the level runner uploads the fit sections and launches the device fit
-      tpe_pack_info e;
-      memset(&e, 0, sizeof(e));
-      e.off_fit = off_lead[L_FIT]; e.off_below_idx = off_lead[L_BIDX]; e.off_fit_seg = off_lead[L_FSEG];
-      e.off_grid = off_lead[L_GRID]; e.off_comp32 = off_lead[L_C32]; e.off_patch = off_lead[L_PATCH];
-      e.n_fit = (int32_t)fit.size(); e.fit_total = fit_seg.back();
-      e.fit_max_new = fit_max_new; e.fit_max_obs = fit_max_obs; e.fit_max_merge = fit_max_merge;
-      e.fit_n_delta = fit_n_delta; e.n_problems = P;
-      e.up_off[0] = 0; e.up_len[0] = off_lead[L_FSEG] + len_lead[L_FSEG]; e.n_up = 1;
-      e.blob_bytes = off_lead[L_PATCH] + len_lead[L_PATCH];     // (the device bytes the fit touches)
-      g_pack_hook.fn(g_pack_hook.ctx, &e);
-    }
-  }
-  PACK_MARK("lead");
-  // large tabulated continuous f32 sides: in chunks (ChunkTask), their
-  // acceptance terms in the same tasks as their component terms
-  auto& chunked = ps.chunked;
-  auto& ch_tasks = ps.ch_tasks;
-  auto& side_shift = ps.side_shift;
-  chunked.assign(2 * (size_t)n_labels, 0);
-  ch_tasks.clear();
-  int64_t ch_total = 0;
-  // (only a level with many such components: a chunked side costs a second
-  // hand-off to the workers, more than it saves on the headline's few thousand)
-  int64_t chunkable = 0;
-  for (int32_t li = 0; li < n_labels && !f64; ++li) {
-    const tpe_label_in& L = labels[li];
-    if ((L.family != TPE_FAM_GAUSS && L.family != TPE_FAM_LOGGAUSS) || tmode[li] == TPE_TAB_NONE) continue;
-    for (int side = 0; side < 2 - dev_fit[li]; ++side) {
-      const int64_t k = side ? L.above_k : L.below_k;
-      if (k > kFillChunk) chunkable += k;
-    }
-  }
-  if (chunkable >= fill_chunk_min_level())
-    for (int32_t li = 0; li < n_labels; ++li) {
-      const tpe_label_in& L = labels[li];
-      if ((L.family != TPE_FAM_GAUSS && L.family != TPE_FAM_LOGGAUSS) || tmode[li] == TPE_TAB_NONE) continue;
-      for (int side = 0; side < 2 - dev_fit[li]; ++side) {
-        const int64_t k = side ? L.above_k : L.below_k;
-        if (k <= kFillChunk) continue;
-        chunked[2 * (size_t)li + side] = 1;
-        const int64_t nch = (k + kFillChunk - 1) / kFillChunk;
-        for (int64_t j = 0; j < nch; ++j)
-          ch_tasks.push_back(ChunkTask{li, side, k * j / nch, k * (j + 1) / nch, ch_total});
-        ch_total += k;
-      }
-    }
-  // the acceptance terms of the large bounded sides in chunks on the workers
-  // (libm erf for every component near a bound: the largest label's would
-  // otherwise be its fill's critical path); the fill sums them in order
-  auto& pa_off = ps.pa_off;
-  auto& pa_terms = ps.pa_terms;
-  auto& pa_tasks = ps.pa_tasks;
-  pa_off.assign(2 * (size_t)n_labels, -1);
-  pa_tasks.clear();
-  int64_t pa_total = 0;
-  for (int32_t li = 0; li < n_labels; ++li) {
-    const tpe_label_in& L = labels[li];
-    if (!(L.flags & (TPE_F_HAS_LOW | TPE_F_HAS_HIGH)) || L.family == TPE_FAM_CATEGORICAL ||
-        L.family == TPE_FAM_LOGGAUSS)
-      continue;
-    const bool fast = L.family == TPE_FAM_GAUSS && !f64;   // (an f32 side's mass: erf_tab)
-    for (int side = 0; side < 2 - dev_fit[li]; ++side) {
-      const int64_t k = side ? L.above_k : L.below_k;
-      const bool ch = chunked[2 * (size_t)li + side] != 0;     // (its terms: the chunk tasks)
-      if (k < kPaParallelMin && !ch) continue;
-      pa_off[2 * (size_t)li + side] = pa_total;
-      for (int64_t i0 = 0; i0 < k && !ch; i0 += kPaChunk)
-        pa_tasks.push_back(PaTask{li, side, i0, std::min(k, i0 + kPaChunk), pa_total, fast});
-      pa_total += k;
-    }
-  }
-  pa_terms.resize((size_t)pa_total);
-  if (!pa_tasks.empty()) {
-    const PaCtx pcx{labels, pa_tasks.data(), pa_terms.data()};
-    tpe_pool::parallel_for((int)pa_tasks.size(), [](void* c, int i) { pa_chunk(*(const PaCtx*)c, i); }, (void*)&pcx);
-  }
-  PACK_MARK("accept");
-  const FillCtx fcx{labels, sec.data(), lab.data(), f_samp, f_comp64, f_comp32, f_grid,
-                    dev_fit.data(), tmode.data(), key_bits, f64, pa_terms.data(), pa_off.data(), chunked.data()};
-  const int n_ch = (int)ch_tasks.size();
-  ChunkCtx ccx{labels, ch_tasks.data(), nullptr, nullptr, nullptr, pa_terms.data(), pa_off.data(), nullptr,
-               sec.data(), f_comp32};
-  if (n_ch) {
-    ps.ch_a.resize((size_t)ch_total);
-    ps.ch_c.resize((size_t)ch_total);
-    ps.ch_max.resize((size_t)n_ch);
-    side_shift.assign(2 * (size_t)n_labels, 0.0);
-    ccx.a = ps.ch_a.data(); ccx.c = ps.ch_c.data(); ccx.cmax = ps.ch_max.data();
-    ccx.shift = side_shift.data();
-  }
-  {
-    // the labels' fills and the chunks' terms, one task each (a few hundred
-    // components per label make a worker's hand-off worth it)
-    struct Both { const FillCtx* f; const ChunkCtx* c; int32_t n_labels; };
-    const Both both{&fcx, &ccx, n_labels};
-    auto task = [](void* v, int i) {
-      const Both& b = *(const Both*)v;
-      if (i < b.n_labels) fill_label(*b.f, (int32_t)i);
-      else chunk_terms(*b.c, i - b.n_labels);
-    };
-    const int n_tasks = n_labels + n_ch;
-    if (n_tasks >= 2 && work_k >= 4096) tpe_pool::parallel_for(n_tasks, task, (void*)&both);
-    else
-      for (int i = 0; i < n_tasks; ++i) task((void*)&both, i);
-  }
-  PACK_MARK("fill_terms");
-  if (n_ch) {
-    // each chunked side's shift (the largest finite c of its chunks) and base,
-    // then its rows
-    for (int t = 0; t < n_ch; ++t) {
-      const size_t q = 2 * (size_t)ch_tasks[t].li + ch_tasks[t].side;
-      side_shift[q] = ch_tasks[t].i0 == 0 ? ps.ch_max[t] : std::max(side_shift[q], ps.ch_max[t]);
-    }
-    for (int32_t li = 0; li < n_labels; ++li)
-      for (int side = 0; side < 2; ++side) {
-        const size_t q = 2 * (size_t)li + side;
-        if (!chunked[q]) continue;
-        if (!std::isfinite(side_shift[q])) side_shift[q] = 0;
-        (side ? lab[li].above_base : lab[li].below_base) = side_shift[q] * kLn2;
-      }
-    // the rows, and each bounded side's mass (its terms summed in numpy's
-    // order) into its base: log2(w / (sigma sqrt(2 pi)) / p) - shift =
-    // c' - shift' with shift = shift' + log2(1 / p), one task a side (named by
-    // its first chunk)
-    auto& mass = ps.mass_tasks;
-    mass.clear();
-    for (int t = 0; t < n_ch; ++t)
-      if (ch_tasks[t].i0 == 0 && pa_off[2 * (size_t)ch_tasks[t].li + ch_tasks[t].side] >= 0) mass.push_back(t);
-    struct Rows { const ChunkCtx* c; tpe_problem* lab; const int* mass; int n_ch; };
-    const Rows rw{&ccx, lab.data(), mass.data(), n_ch};
-    auto rows = [](void* v, int t) {
-      const Rows& r = *(const Rows*)v;
-      if (t < r.n_ch) { chunk_rows(*r.c, t); return; }
-      const ChunkTask& q = r.c->tasks[r.mass[t - r.n_ch]];
-      const size_t sd = 2 * (size_t)q.li + q.side;
-      const tpe_label_in& L = r.c->labels[q.li];
-      const double pa = np_sum(r.c->pa_terms + r.c->pa_off[sd], q.side ? L.above_k : L.below_k);
-      double& base = q.side ? r.lab[q.li].above_base : r.lab[q.li].below_base;
-      base = pa > 0 && pa < INFINITY ? base - log(pa) : NAN;      // (NaN: refilled below)
-    };
-    const int n_rows = n_ch + (int)mass.size();
-    if (n_rows >= 2) tpe_pool::parallel_for(n_rows, rows, (void*)&rw);
-    else rows((void*)&rw, 0);
-    // a side whose mass is 0, inf or NaN: its rows with 1 / p inside c, as
-    // fill_label makes them (the rows carry the non-finite values, base 0)
-    for (int m : mass) {
-      const ChunkTask& q0 = ch_tasks[m];
-      tpe_problem& p = lab[q0.li];
-      double& base = q0.side ? p.above_base : p.below_base;
-      if (base == base) continue;
-      const tpe_label_in& L = labels[q0.li];
-      const size_t sd = 2 * (size_t)q0.li + q0.side;
-      const double ipa = 1.0 / np_sum(pa_terms.data() + pa_off[sd], q0.side ? L.above_k : L.below_k);
-      const double* w = q0.side ? L.above_w : L.below_w;
-      const double* sg = q0.side ? L.above_sigma : L.below_sigma;
-      double sh = -INFINITY;
-      for (int t = m; t < n_ch && ch_tasks[t].li == q0.li && ch_tasks[t].side == q0.side; ++t) {
-        const ChunkTask& q = ch_tasks[t];
-        sh = std::max(sh, comp_terms_f32(w + q.i0, sg + q.i0, q.i1 - q.i0, false, ipa, ccx.a + q.scr + q.i0,
-                                         ccx.c + q.scr + q.i0));
-      }
-      side_shift[sd] = std::isfinite(sh) ? sh : 0.0;
-      base = side_shift[sd] * kLn2;
-      for (int t = m; t < n_ch && ch_tasks[t].li == q0.li && ch_tasks[t].side == q0.side; ++t) chunk_rows(ccx, t);
-    }
-  }
-  PACK_MARK("fill");
-  // the device-fitted labels' problem fields (the fill cleared their rows)
-  for (size_t k = 0; k < fit.size(); ++k) {
-    const tpe_fit_job& j = fit[k];
-    tpe_problem& p = lab[fit_li[k]];
-    p.above_off = j.above_off; p.above_len = (int32_t)(j.n_obs - j.n_below + 1);
-    p.wide_off = j.wide_off;
-    p.grid_off = j.grid_off; p.grid_n = j.grid_n;
-    p.narrow_amin = 1.f;       // pruned; the fit stage writes the real value
-  }
-  // ---- score tables: 16-B units (a cell row is 3 units, a lattice row 1) ----
-  int64_t tab_units = 0, fgt_max_boxes = 0;
-  for (int32_t li = 0; li < n_labels; ++li) {
-    tpe_problem& p = lab[li];
-    p.tab_mode = tmode[li];
-    if (tmode[li] == TPE_TAB_CELLS && logpoly[li]) {
-      // one table, both sides' polynomials in each row
-      const int64_t n = tn0[li];
-      p.flags |= TPE_F_LOGPOLY;
-      for (int sd = 0; sd < 2; ++sd) {
-        p.tab_off[sd] = (int32_t)tab_units;
-        p.tab_n[sd] = (int32_t)n;
-        p.tab_lo[sd] = (float)tklo[li];
-        p.tab_inv[sd] = (float)((double)n / (tkhi[li] - tklo[li]));
-      }
-      tab_units += kTabRowUnits * n;
-    } else if (tmode[li] == TPE_TAB_CELLS) {
-      for (int sd = 0; sd < 2; ++sd) {
-        const int64_t n = sd ? tn1[li] : tn0[li];
-        p.tab_off[sd] = (int32_t)tab_units;
-        p.tab_n[sd] = (int32_t)n;
-        p.tab_lo[sd] = (float)tklo[li];
-        p.tab_inv[sd] = (float)((double)n / (tkhi[li] - tklo[li]));
-        tab_units += kTabRowUnits * n;
-      }
-      if (fgt_boxes[li] > 0) {              // box records after the label's cells ("Box moments")
-        const tpe_label_in& L = labels[li];
-        p.flags |= TPE_F_FGT;
-        p.fgt_a = fgt_a(L.prior_sigma, L.above_k);
-        p.fgt_off = (int32_t)tab_units;
-        p.fgt_n = (int32_t)fgt_boxes[li];
-        p.fgt_lo = tklo[li];
-        tab_units += 1 + TPE_FGT_BOX_UNITS * fgt_boxes[li];
-        fgt_max_boxes = std::max(fgt_max_boxes, fgt_boxes[li]);
-      }
-    } else if (tmode[li] == TPE_TAB_LATTICE) {
-      p.tab_off[0] = (int32_t)tab_units;
-      p.tab_n[0] = (int32_t)tn0[li];
-      p.lat_lo = tlat[li];
-      tab_units += tn0[li] + (tn0[li] + 1 + 3) / 4;      // {l, g} rows, then n + 1 f32 entry thresholds
-    }
-  }
-  if (tab_units >= ((int64_t)1 << 31)) return TPE_E_ARG;
-  PACK_MARK("tabunits");
-  // ---- problems, tiles, work (problem rows and tiles straight into the blob) ----
-  int64_t scored = 0;
-  const int64_t C_ref = n_cand_global > 0 ? n_cand_global : n_cand;
-  auto& xtmpl = ps.xtmpl;
-  auto& xfirst = ps.xfirst;
-  auto& xctr = ps.xctr;
-  xtmpl.clear(); xfirst.clear(); xctr.clear();
-  if (expand) {
-    xtmpl.resize((size_t)n_labels);
-    xfirst.resize((size_t)n_labels + 1);
-    xctr.resize((size_t)P);
-    int64_t r = 0;
-    for (int32_t li = 0; li < n_labels; ++li) {
-      tpe_problem q = lab[li];
-      q.n_cand = n_cand;
-      q.cand_off = 0;                     // k_expand: problem r's candidates at r * n_cand
-      q.sort_slot = -1;
-      q.pool_first = -1;
-      q.cand_base = cand_base;
-      q.n_cand_global = C_ref;
-      q.key0 = (uint32_t)seed; q.key1 = (uint32_t)(seed >> 32);
-      q.ctr2 = (uint32_t)labels[li].label_ix;
-      q.ctr3 = 0;                         // k_expand: the problem's new id
-      q.n_tiles = (int32_t)n_tiles_p;
-      q.tile_off = 0;                     // k_expand: r * n_tiles
-      q.n_splits = 0;                     // tabulated: no above stage
-      xtmpl[(size_t)li] = q;
-      xfirst[(size_t)li] = (int32_t)r;
-      for (int64_t j = 0; j < labels[li].n_ids; ++j) xctr[(size_t)r++] = (uint32_t)labels[li].ids[j];
-    }
-    xfirst[(size_t)n_labels] = (int32_t)r;
-  }
-  PACK_MARK("expand");
-  const int64_t Ph = expand ? 0 : P;      // problems (and their tiles) the host writes
-  tpe_problem* prob;
-  if (direct) {
-    prob = (tpe_problem*)(bb + off_lead[L_PROB]);
-  } else {
-    ps.prob.resize((size_t)Ph);
-    prob = ps.prob.data();
-  }
-  if (!expand) {
-    int64_t r = 0, s_next = 0, u_next = n_sorted_prob * (int64_t)n_cand;
-    int32_t slot = 0;
-    for (int32_t li = 0; li < n_labels; ++li) {
-      const int32_t pool_slot = pooled[li] ? slot++ : -1, pool_first = (int32_t)r;
-      for (int64_t j = 0; j < labels[li].n_ids; ++j, ++r) {
-        tpe_problem& q = prob[r];
-        q = lab[li];
-        q.n_cand = n_cand;
-        int64_t& next = pruned[li] ? s_next : u_next;
-        q.cand_off = next;
-        next += n_cand;
-        q.sort_slot = pooled[li] ? pool_slot : pruned[li] ? slot++ : -1;
-        q.pool_first = pooled[li] ? pool_first : -1;
-        if (pooled[li]) q.flags |= TPE_F_POOLED;
-        q.cand_base = cand_base;
-        q.n_cand_global = C_ref;
-        q.key0 = (uint32_t)seed; q.key1 = (uint32_t)(seed >> 32);
-        q.ctr2 = (uint32_t)labels[li].label_ix;
-        q.ctr3 = (uint32_t)labels[li].ids[j];
-        q.n_tiles = (int32_t)n_tiles_p;
-        q.tile_off = (int32_t)(r * n_tiles_p);
-        if (q.family != TPE_FAM_CATEGORICAL && q.tab_mode == TPE_TAB_NONE) ++scored;
-      }
-    }
-  }
-  PACK_MARK("prob");
-  // splits of the above mixture per tile.  Bulk tiles: enough work items to fill
-  // the chip (a function of the GLOBAL candidate count).  Pruned problems with
-  // many tiles: the bulk is cheap (local expansion), so one split, and the
-  // outermost tiles of the (local) sorted range — the sparse tails, whose waves
-  // span wide windows evaluated exactly — get geometrically more.  A shard sorts
-  // and windows only its own candidates and counts its tails in its own tiles,
-  // so under candidate sharding the fp32 sums (and near-tie winners) can differ
-  // from a single-device run in the last bits: sharded winners agree within the
-  // eps-tie set, not bit for bit (the draws themselves are identical).
-  const int64_t tiles_ref = (C_ref + T - 1) / T;
-  const int64_t scored_tiles = scored * tiles_ref;
-  const int64_t target = std::max<int64_t>(1, (target_work() + std::max<int64_t>(scored_tiles, 1) - 1) /
-                                                  std::max<int64_t>(scored_tiles, 1));
-  bool any_pruned = false;
-  for (int64_t r = 0; r < Ph; ++r) {
-    tpe_problem& q = prob[r];
-    if (q.family == TPE_FAM_CATEGORICAL || q.tab_mode != TPE_TAB_NONE) { q.n_splits = 0; continue; }
-    const int64_t ks = (q.above_len + kMinComponentsPerSplit - 1) / kMinComponentsPerSplit;
-    const bool tails = q.sort_slot >= 0 && tiles_ref >= kTailMinTiles;
-    q.n_splits = tails ? 1 : (int32_t)std::max<int64_t>(1, std::min(target, ks));
-    any_pruned = any_pruned || q.sort_slot >= 0;
-  }
-  auto tile_splits = [&](const tpe_problem& q, int64_t j) -> int32_t {
-    if (q.family == TPE_FAM_CATEGORICAL || q.tab_mode != TPE_TAB_NONE) return 0;
-    if (!(q.sort_slot >= 0 && tiles_ref >= kTailMinTiles)) return q.n_splits;
-    const int64_t e = std::min<int64_t>(j, n_tiles_p - 1 - j);
-    const int64_t ns = tail_splits(e);
-    const int64_t cap = std::max<int64_t>(1, (q.above_len + 63) / 64);
-    return (int32_t)std::max<int64_t>(1, std::min(ns, cap));
-  };
-  tpe_tile* tiles;
-  if (direct) {
-    tiles = (tpe_tile*)(bb + off_lead[L_TILES]);
-  } else {
-    ps.tiles.resize((size_t)(Ph * n_tiles_p));
-    tiles = ps.tiles.data();
-  }
-  {
-    tpe_tile* __restrict__ tp = tiles;
-    for (int64_t r = 0; r < Ph; ++r) {
-      tpe_tile* __restrict__ row = tp + r * n_tiles_p;
-      const bool none = prob[r].family == TPE_FAM_CATEGORICAL || prob[r].tab_mode != TPE_TAB_NONE;
-      for (int64_t j = 0; j < n_tiles_p; ++j) {
-        row[j].problem = (int32_t)r;
-        row[j].cand_start = (int32_t)(j * T);
-        row[j].work_first = 0;
-        row[j].n_splits = none ? 0 : tile_splits(prob[r], j);
-      }
-    }
-  }
-  // work items grouped [continuous | quantized Gauss | quantized log]; a tile's
-  // items are consecutive, and an item's index is its row of `part`
-  auto& work = ps.work;
-  work.clear();
-  {
-    int64_t nw = 0;
-    for (int64_t t = 0; t < Ph * n_tiles_p; ++t) nw += tiles[t].n_splits;
-    work.reserve((size_t)nw);
-  }
-  int32_t counts[3] = {0, 0, 0};
-  const int fams[3][2] = {{TPE_FAM_GAUSS, TPE_FAM_LOGGAUSS}, {TPE_FAM_QGAUSS, -1}, {TPE_FAM_QLOGGAUSS, -1}};
-  for (int gi = 0; gi < 3; ++gi) {
-    const size_t before = work.size();
-    for (int64_t r = 0; r < Ph; ++r) {
-      const tpe_problem& q = prob[r];
-      if ((q.family != fams[gi][0] && q.family != fams[gi][1]) || q.tab_mode != TPE_TAB_NONE) continue;
-      for (int64_t j = 0; j < n_tiles_p; ++j) {
-        tpe_tile& tl = tiles[(size_t)(r * n_tiles_p + j)];
-        tl.work_first = (int32_t)work.size();
-        for (int32_t sp = 0; sp < tl.n_splits; ++sp) {
-          tpe_work w;
-          w.problem = (int32_t)r; w.split = sp; w.cand_start = (int32_t)(j * T);
-          w.k_start = (int32_t)(((int64_t)q.above_len * sp) / tl.n_splits);
-          w.k_end = (int32_t)(((int64_t)q.above_len * (sp + 1)) / tl.n_splits);
-          w.n_splits = tl.n_splits;
-          work.push_back(w);
-        }
-      }
-    }
-    counts[gi] = (int32_t)(work.size() - before);
-  }
-  if ((int64_t)work.size() >= ((int64_t)1 << 31)) return TPE_E_ARG;
-  const int64_t part_total = (int64_t)work.size() * T;
-  // tiles the finalize stage scores (device-drawn candidates): not categorical
-  // (the sample stage scores those), not one-split continuous f32 (the above
-  // stage does)
-  auto& fin_tiles = ps.fin_tiles;
-  fin_tiles.clear();
-  for (int64_t r = 0; r < Ph; ++r) {                 // (per problem: a problem's tiles are consecutive)
-    const tpe_problem& q = prob[r];
-    if ((q.family == TPE_FAM_CATEGORICAL && q.samp_len <= TPE_SAMPLE_LDS_ROWS) || q.tab_mode != TPE_TAB_NONE) continue;
-    const bool cont = !f64 && (q.family == TPE_FAM_GAUSS || q.family == TPE_FAM_LOGGAUSS);
-    for (int64_t t = r * n_tiles_p; t < (r + 1) * n_tiles_p; ++t)
-      if (!(cont && tiles[t].n_splits == 1)) fin_tiles.push_back((int32_t)t);
-  }
-  PACK_MARK("tiles_work_fin");
-  // table jobs: per tabulated label, one per cell side or one lattice job
-  // (TPE_TAB_PER_BLOCK rows per block); `problem` = the label's first row
-  auto& tab_jobs = ps.tab_jobs;
-  tab_jobs.clear();
-  int64_t tab_blocks = 0, fgt_max_cells = 0;
-  for (int32_t li = 0, r = 0; li < n_labels; r += (int32_t)labels[li].n_ids, ++li) {
-    const tpe_problem& p = lab[li];
-    if (p.tab_mode == TPE_TAB_NONE || labels[li].n_ids <= 0) continue;
-    const int sides = p.tab_mode == TPE_TAB_CELLS ? 2 : 1;
-    for (int sd = 0; sd < sides; ++sd) {
-      tpe_tab_job j;
-      memset(&j, 0, sizeof(j));
-      j.problem = r; j.side = sd; j.kind = p.tab_mode; j.n = p.tab_n[sd]; j.off = p.tab_off[sd];
-      j.block0 = (int32_t)tab_blocks;
-      if (j.kind == TPE_TAB_CELLS) {
-        if (p.flags & TPE_F_LOGPOLY) j.kind = TPE_TAB_LOGPOLY;
-        // the rows the side's cells sum (a device-fitted above side: its fit writes them)
-        j.rows_off = sd ? p.above_off : p.below_off;
-        j.rows_n = sd && dev_fit[li] ? -1 : sd ? p.above_len : p.below_len;
-        j.wide_off = sd ? p.wide_off : 0;
-        j.wide_n = sd ? p.wide_len : 0;
-        j.lo = p.tab_lo[sd];
-        j.inv = p.tab_inv[sd];
-      }
-      // cells: TPE_TAB_PER_BLOCK rows per block; lattice: one block per value
-      // (a box-moment label's above cells are built by their own stage: no blocks here)
-      if (sd == 1 && (p.flags & TPE_F_FGT)) fgt_max_cells = std::max<int64_t>(fgt_max_cells, j.n);
-      else if (j.kind == TPE_TAB_LOGPOLY && j.rows_n >= 0 && j.rows_n + j.wide_n <= kLpDirectRows)
-        tab_blocks += (j.n + kLpRowsPerWave * TPE_TAB_PER_BLOCK - 1) / (kLpRowsPerWave * TPE_TAB_PER_BLOCK);
-      else if (j.kind == TPE_TAB_CELLS && j.rows_n >= 0 && j.rows_n + j.wide_n <= kMomDirectRows)
-        tab_blocks += (j.n + kMomCellsPerWave * TPE_TAB_PER_BLOCK - 1) / (kMomCellsPerWave * TPE_TAB_PER_BLOCK);
-      else tab_blocks += j.kind != TPE_TAB_LATTICE ? (j.n + TPE_TAB_PER_BLOCK - 1) / TPE_TAB_PER_BLOCK : j.n;
-      tab_jobs.push_back(j);
-    }
-  }
-  if (tab_blocks >= ((int64_t)1 << 31)) return TPE_E_ARG;
-  const int64_t n_tab_jobs = (int64_t)tab_jobs.size();
-  // sample-stage tile lists: untabulated tiles (lazy categorical last) and tabulated tiles
-  auto& samp_tiles = ps.samp_tiles;
-  auto& tab_tiles = ps.tab_tiles;
-  samp_tiles.clear(); tab_tiles.clear();
-  auto append_range = [&](std::vector<int32_t>& v, int64_t r) {
-    const size_t b = v.size();
-    v.resize(b + (size_t)n_tiles_p);
-    int32_t* __restrict__ d = v.data() + b;
-    for (int64_t j = 0; j < n_tiles_p; ++j) d[j] = (int32_t)(r * n_tiles_p + j);
-  };
-  int64_t n_samp_eager = 0;
-  for (int pass = 0; pass < 2; ++pass)
-    for (int64_t r = 0; r < Ph; ++r) {
-      const tpe_problem& q = prob[r];
-      if (q.tab_mode != TPE_TAB_NONE) {
-        if (pass == 0) append_range(tab_tiles, r);
-        continue;
-      }
-      const bool lazy = q.family == TPE_FAM_CATEGORICAL && (q.flags & TPE_F_CAT_LAZY) && q.samp_len <= 64;
-      if (lazy == (pass == 1)) append_range(samp_tiles, r);
-      if (pass == 0 && !lazy) n_samp_eager += n_tiles_p;
-    }
-  // (expanded: every tile is tabulated, in order — the identity list, not stored)
-  const int64_t n_samp_tiles = (int64_t)samp_tiles.size(),
-                n_tab_tiles = expand ? P * n_tiles_p : (int64_t)tab_tiles.size();
-  if (samp_tiles.empty()) samp_tiles.push_back(0);
-  if (tab_tiles.empty()) tab_tiles.push_back(0);
-  if (tab_jobs.empty()) tab_jobs.push_back(tpe_tab_job{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0.f, 0.f});
-  const int64_t n_fin = (int64_t)fin_tiles.size();
-  if (fin_tiles.empty()) fin_tiles.push_back(0);
-  PACK_MARK("jobs_lists");
-  // ---- the later sections after the leading ones (256-B aligned) ----
-  const int NS = 6;
-  // expanded levels: templates, first problems, new ids (one section, 256-B aligned parts)
-  const int64_t x_tmpl = (int64_t)(xtmpl.size() * sizeof(tpe_problem));
-  const int64_t x_first_off = (x_tmpl + 255) & ~(int64_t)255;
-  const int64_t x_ctr_off = (x_first_off + (int64_t)(xfirst.size() * sizeof(int32_t)) + 255) & ~(int64_t)255;
-  const int64_t x_len = expand ? x_ctr_off + (int64_t)(xctr.size() * sizeof(uint32_t)) : 0;
-  const void* src[NS] = {work.data(), fin_tiles.data(), tab_jobs.data(), samp_tiles.data(), tab_tiles.data(), nullptr};
-  const int64_t len[NS] = {(int64_t)(work.size() * sizeof(tpe_work)), (int64_t)(fin_tiles.size() * sizeof(int32_t)),
-                           (int64_t)(tab_jobs.size() * sizeof(tpe_tab_job)),
-                           (int64_t)(samp_tiles.size() * sizeof(int32_t)),
-                           expand ? 0 : (int64_t)(tab_tiles.size() * sizeof(int32_t)), x_len};
-  int64_t off[NS], end = lead_end;
-  for (int i = 0; i < NS; ++i) {
-    off[i] = (end + 255) & ~(int64_t)255;
-    end = off[i] + len[i];
-  }
+  step_lead(ps);
+  const int64_t* off_lead = lv.off_lead;
   info->off_fit = off_lead[L_FIT]; info->off_below_idx = off_lead[L_BIDX]; info->off_fit_seg = off_lead[L_FSEG];
   info->off_grid = off_lead[L_GRID]; info->off_comp32 = off_lead[L_C32];
-  info->off_patch = fit.empty() ? 0 : off_lead[L_PATCH];
-  info->off_problems = off_lead[L_PROB]; info->off_tiles = off_lead[L_TILES];
-  info->off_comp64 = off_lead[L_C64]; info->off_samp = off_lead[L_SAMP];
-  info->off_work = off[0];
-  info->off_fin_tiles = off[1]; info->n_fin_tiles = n_fin;
-  info->fit_max_new = fit_max_new;
-  info->fit_max_merge = fit_max_merge;
-  info->fit_n_delta = fit_n_delta;
-  info->fit_max_obs = fit_max_obs;
-  info->off_tab_jobs = off[2]; info->n_tab_jobs = n_tab_jobs; info->tab_blocks = tab_blocks;
-  info->tab_units = tab_units;
-  info->off_samp_tiles = off[3]; info->n_samp_tiles = n_samp_tiles; info->n_samp_eager = n_samp_eager;
-  info->off_tab_tiles = off[4]; info->n_tab_tiles = n_tab_tiles;
-  info->off_expand = expand ? off[5] : 0;
-  info->n_expand = expand ? n_labels : 0;
-  // host-written ranges (the upload): fit sections + host grid, host comp32
-  // rows, then problems (unless expanded: device-only) through the end
-  info->n_up = 0;
-  auto up = [&](int64_t o, int64_t n) {
-    if (n > 0) { info->up_off[info->n_up] = o; info->up_len[info->n_up] = n; ++info->n_up; }
-  };
-  up(0, off_lead[L_GRID] + host_grid * 4);
-  up(off_lead[L_C32], host_rows * 16);
-  const int64_t r3 = expand ? off_lead[L_C64] : off_lead[L_PROB];
-  up(r3, end - r3);
-  info->n_problems = P;
-  info->n_tiles = P * n_tiles_p;
-  info->n_work_cont = counts[0]; info->n_work_qgauss = counts[1]; info->n_work_qlog = counts[2];
-  info->any_pruned = any_pruned ? 1 : 0;
-  info->key_bits = key_bits;
-  info->sort_end_bit = any_pruned ? sort_end_bit : 0;
-  info->part_total = part_total;
-  info->n_fit = (int32_t)fit.size();
-  info->fgt_max_boxes = (int32_t)fgt_max_boxes;
-  info->fgt_max_cells = fgt_max_cells;
-  info->fit_total = fit_seg.back();
-  info->sort_count = n_sorted_prob * (int64_t)n_cand;
-  info->n_sorted = S;
-  info->n_pooled = n_pooled;
-  info->draw_blocks = (C_ref + 1 + 63) / 64;
-  info->blob_bytes = end;
+  info->off_patch = ps.fit.empty() ? 0 : off_lead[L_PATCH];
+  info->n_fit = (int32_t)ps.fit.size(); info->fit_total = ps.fit_seg.back();
+  info->fit_max_new = lv.fit_max_new; info->fit_max_obs = lv.fit_max_obs; info->fit_max_merge = lv.fit_max_merge;
+  info->fit_n_delta = lv.fit_n_delta;
+  info->n_problems = lv.P;
+  lead->direct = lv.direct;
+  lead->up_len = off_lead[L_FSEG] + lv.len_lead[L_FSEG];
+  lead->dev_bytes = off_lead[L_PATCH] + lv.len_lead[L_PATCH];
+  PACK_MARK("lead");
+  return TPE_OK;
+}
+
+__attribute__((target_clones("avx512f", "avx2", "default")))
+static int pack_fill(tpe_pack_info* info) {
+  PackScratch& ps = pack_scratch();
+  int rc;
+  step_accept(ps);
+  PACK_MARK("accept");
+  step_fill_terms(ps);
+  PACK_MARK("fill_terms");
+  step_fill(ps);
+  PACK_MARK("fill");
+  if ((rc = step_tabunits(ps, *info))) return rc;
+  PACK_MARK("tabunits");
+  step_expand(ps);
+  PACK_MARK("expand");
+  const int64_t scored = step_prob(ps);
+  PACK_MARK("prob");
+  if ((rc = step_tiles_work_fin(ps, scored, *info))) return rc;
+  PACK_MARK("tiles_work_fin");
+  if ((rc = step_jobs_lists(ps, *info))) return rc;
+  PACK_MARK("jobs_lists");
+  LateSections ls;
+  step_offsets(ps, info, ls);
   PACK_MARK("offsets");
-  if (!direct || blob_cap < end) return TPE_E_SPACE;
-  {
-    // the later sections into the blob; a large level's in 64-KiB pieces on the
-    // worker pool (a batched level's work items)
-    struct Piece { unsigned char* dst; const unsigned char* src; size_t n; };
-    static thread_local std::vector<Piece> pieces_tl;
-    std::vector<Piece>& pieces = pieces_tl;
-    pieces.clear();
-    constexpr size_t kPiece = 64 << 10;
-    size_t total = 0;
-    for (int i = 0; i < NS; ++i) {
-      if (!len[i] || !src[i]) continue;
-      for (size_t o = 0; o < (size_t)len[i]; o += kPiece)
-        pieces.push_back(Piece{bb + off[i] + o, (const unsigned char*)src[i] + o, std::min(kPiece, (size_t)len[i] - o)});
-      total += (size_t)len[i];
-    }
-    auto copy = [](void* c, int k) {
-      const Piece& q = (*(const std::vector<Piece>*)c)[(size_t)k];
-      memcpy(q.dst, q.src, q.n);
-    };
-    if (total >= (128u << 10) && pieces.size() > 1) tpe_pool::parallel_for((int)pieces.size(), copy, &pieces);
-    else for (size_t k = 0; k < pieces.size(); ++k) copy(&pieces, (int)k);
-  }
+  if (!ps.lv.direct || ps.lv.blob_cap < info->blob_bytes) return TPE_E_SPACE;
+  step_copy(ps, ls);
   PACK_MARK("copy");
-  if (expand) {
-    unsigned char* x = bb + off[5];
-    memcpy(x, xtmpl.data(), (size_t)x_tmpl);
-    memcpy(x + x_first_off, xfirst.data(), xfirst.size() * sizeof(int32_t));
-    memcpy(x + x_ctr_off, xctr.data(), xctr.size() * sizeof(uint32_t));
-  }
+  step_xcopy(ps, ls);
   PACK_MARK("xcopy");
   PACK_DONE();
   return TPE_OK;
+}
+
+__attribute__((visibility("hidden")))
+int tpe_internal_pack_plan(const tpe_label_in* labels, int32_t n_labels, int32_t n_cand, uint64_t seed,
+                           int64_t cand_base, int64_t n_cand_global, int32_t precision, void* blob, int64_t blob_cap,
+                           tpe_pack_info* info, TpePackLead* lead) {
+  return pack_plan(labels, n_labels, n_cand, seed, cand_base, n_cand_global, precision, blob, blob_cap, info, lead);
+}
+
+__attribute__((visibility("hidden"))) int tpe_internal_pack_fill(tpe_pack_info* info) { return pack_fill(info); }
+
+__attribute__((target_clones("avx512f", "avx2", "default")))
+int tpe_host_pack_level(const tpe_label_in* labels, int32_t n_labels, int32_t n_cand, uint64_t seed,
+                        int64_t cand_base, int64_t n_cand_global, int32_t precision, void* blob, int64_t blob_cap,
+                        tpe_pack_info* info) {
+  TpePackLead lead;
+  const int rc = pack_plan(labels, n_labels, n_cand, seed, cand_base, n_cand_global, precision, blob, blob_cap, info,
+                           &lead);
+  return rc ? rc : pack_fill(info);
 }
 
 }  // extern "C"

@@ -2,7 +2,7 @@
 //
 // Replaces, per (new_id, hyperparameter) problem, the numpy operators of
 // gsmafra/hyperopt's tpe.suggest (see include/tpe_hip.h for the reference
-// file:line of each stage).  Five stages, each a batched launch over a flat
+// file:line of each stage).  Seven stages, each a batched launch over a flat
 // work list so that problems of very different size share one grid:
 //
 //   tpe_fit_above    (optional) Parzen fit of large continuous above mixtures
@@ -4981,7 +4981,7 @@ int check_batch(const tpe_batch* b) {
 }
 
 // TPE_EARLY_FIT=0: a level's device fit runs after its upload (else it starts
-// while the host packs the rest of the level: early_fit_hook; A/B, tests)
+// while the host packs the rest of the level: early_fit; A/B, tests)
 bool early_fit_enabled() {           // (read per level: the tests switch it)
   const char* v = getenv("TPE_EARLY_FIT");
   return !(v && v[0] == '0');
@@ -5526,11 +5526,12 @@ static bool force_combine() {
 
 // host-written byte ranges of the packed level as k_upload's 8-byte words; false
 // when a rounded range would pass the device blob (the caller copies instead)
-static bool upload_ranges(const tpe_pack_info& info, int64_t blob_cap, UploadRanges& r, int64_t& words) {
+static bool upload_ranges(const int64_t* up_off, const int64_t* up_len, int n_up, int64_t blob_cap, UploadRanges& r,
+                          int64_t& words) {
   memset(&r, 0, sizeof(r));
   words = 0;
-  for (int k = 0; k < info.n_up && k < 4; ++k) {
-    const int64_t o = info.up_off[k], n = (info.up_len[k] + 7) & ~(int64_t)7;
+  for (int k = 0; k < n_up && k < 4; ++k) {
+    const int64_t o = up_off[k], n = (up_len[k] + 7) & ~(int64_t)7;
     if ((o & 7) || o + n > blob_cap) return false;
     r.w0[r.n] = o / 8;
     r.n8[r.n] = n / 8;
@@ -5540,84 +5541,94 @@ static bool upload_ranges(const tpe_pack_info& info, int64_t blob_cap, UploadRan
   return true;
 }
 
-// the early device fit (tpe_host_pack_level's hook): the fit sections uploaded
-// and tpe_fit_above launched — its problem fields into the patch rows — while
-// the host packs the rest of the level; k_fit_patch applies them after the
-// level's upload.  Nothing happens (the fit stage runs after the upload, as
-// without the hook) unless the workspace holds what it touches.
-struct EarlyFit {
-  const tpe_level_ws* ws;
-  hipStream_t s;
-  const char* dbase;            // the pinned staging buffer's device address
-  int launched;
-  int rc;
-};
-
-static void early_fit_hook(void* c, const tpe_pack_info* e) {
-  EarlyFit& x = *(EarlyFit*)c;
-  const tpe_level_ws* ws = x.ws;
-  if (x.launched || e->n_fit <= 0 || !x.dbase || !kernel_upload() || e->fit_total > ws->fit_cap ||
-      e->blob_bytes > ws->blob_bytes || e->n_problems <= 0)
-    return;
-  UploadRanges r;
-  int64_t words;
-  if (!upload_ranges(*e, ws->blob_bytes, r, words) || words * 8 > ws->pinned_bytes) return;
-  unsigned char* dev = (unsigned char*)ws->blob;
+static int launch_upload(const UploadRanges& r, int64_t words, const char* dbase, unsigned char* dev, hipStream_t s,
+                         const char* what) {
   const int grid = (int)std::min<int64_t>(std::max<int64_t>((words + kUploadThreads - 1) / kUploadThreads, 1), 2048);
-  TPE_LAUNCH(k_upload, dim3(grid), dim3(kUploadThreads), 0, x.s, (const unsigned long long*)x.dbase,
+  TPE_LAUNCH(k_upload, dim3(grid), dim3(kUploadThreads), 0, s, (const unsigned long long*)dbase,
              (unsigned long long*)dev, r);
-  if ((x.rc = hip_check("k_upload (early fit)"))) return;
-  tpe_batch b;
-  memset(&b, 0, sizeof(b));
-  b.problems = (const tpe_problem*)(dev + e->off_patch);      // (the fit's problem fields: patch rows)
-  b.n_problems = (int32_t)e->n_problems;
-  b.result = (tpe_result*)dev;                                // (unused by the fit)
-  b.precision = TPE_PREC_F32;
-  b.comp32 = (const float*)(dev + e->off_comp32);
-  b.grid = (const int32_t*)(dev + e->off_grid);
-  b.keys_sorted = b.keys; b.vals_sorted = b.vals;
-  b.fit = (const tpe_fit_job*)(dev + e->off_fit);
-  b.n_fit = e->n_fit;
-  b.below_idx = (const int32_t*)(dev + e->off_below_idx);
-  b.fit_seg = (const int64_t*)(dev + e->off_fit_seg);
-  b.fit_total = e->fit_total;
-  b.fit_keys = ws->fit_keys; b.fit_keys_sorted = ws->fit_keys_sorted;
-  b.fit_vals = ws->fit_vals; b.fit_vals_sorted = ws->fit_vals_sorted;
-  b.fit_max_new = e->fit_max_new; b.fit_max_obs = e->fit_max_obs; b.fit_max_merge = e->fit_max_merge;
-  b.fit_n_delta = e->fit_n_delta;
-  x.rc = tpe_fit_above(&b, x.s);
-  x.launched = x.rc == TPE_OK;
+  return hip_check(what);
 }
 
-static int level_run_impl(const tpe_label_in* labels, int32_t n_labels, int32_t n_cand, uint64_t seed,
-                          int64_t cand_base, int64_t n_cand_global, int32_t precision, int32_t flags,
-                          const tpe_level_ws* ws, tpe_level_need* need, void* stream, tpe_result* out,
-                          const LevelEx* lx) {
-  if (!ws || !need || (n_labels > 0 && !out)) return fail(TPE_E_ARG, "null workspace/need/out");
-  memset(need, 0, sizeof(*need));
+// the pinned staging buffer's device address
+static char* pinned_alias(const tpe_level_ws* ws) {
+  return ws->pinned_dev ? (char*)ws->pinned_dev : device_alias(ws->pinned);
+}
+
+// the fit stage's fields of a level's batch
+static void batch_fit_fields(tpe_batch& b, const tpe_pack_info& info, const tpe_level_ws* ws, const unsigned char* dev) {
+  b.fit = (const tpe_fit_job*)(dev + info.off_fit);
+  b.n_fit = info.n_fit;
+  b.below_idx = (const int32_t*)(dev + info.off_below_idx);
+  b.fit_seg = (const int64_t*)(dev + info.off_fit_seg);
+  b.fit_total = info.fit_total;
+  b.fit_keys = ws->fit_keys; b.fit_keys_sorted = ws->fit_keys_sorted;
+  b.fit_vals = ws->fit_vals; b.fit_vals_sorted = ws->fit_vals_sorted;
+  b.fit_max_new = info.fit_max_new; b.fit_max_obs = info.fit_max_obs; b.fit_max_merge = info.fit_max_merge;
+  b.fit_n_delta = info.fit_n_delta;
+}
+
+// the early device fit, between the pack's plan and its fill: the fit sections
+// uploaded and tpe_fit_above launched — its problem fields into the patch rows
+// — while the host packs the rest of the level; k_fit_patch applies them after
+// the level's upload.  Nothing happens (*launched stays 0: the fit stage runs
+// after the upload) unless the level has fit jobs in the pinned buffer and the
+// workspace holds what the fit touches.
+static int early_fit(const tpe_pack_info& info, const TpePackLead& lead, const tpe_level_ws* ws, hipStream_t s,
+                     int* launched) {
+  if (!lead.direct || info.n_fit <= 0 || !kernel_upload() || info.fit_total > ws->fit_cap ||
+      lead.dev_bytes > ws->blob_bytes || info.n_problems <= 0)
+    return TPE_OK;
+  const char* dbase = pinned_alias(ws);
+  UploadRanges r;
+  int64_t words;
+  const int64_t up_off = 0;
+  if (!dbase || !upload_ranges(&up_off, &lead.up_len, 1, ws->blob_bytes, r, words) || words * 8 > ws->pinned_bytes)
+    return TPE_OK;
+  unsigned char* dev = (unsigned char*)ws->blob;
+  int rc;
+  if ((rc = launch_upload(r, words, dbase, dev, s, "k_upload (early fit)"))) return rc;
+  tpe_batch b;
+  memset(&b, 0, sizeof(b));
+  b.problems = (const tpe_problem*)(dev + info.off_patch);      // (the fit's problem fields: patch rows)
+  b.n_problems = (int32_t)info.n_problems;
+  b.result = (tpe_result*)dev;                                   // (unused by the fit)
+  b.precision = TPE_PREC_F32;
+  b.comp32 = (const float*)(dev + info.off_comp32);
+  b.grid = (const int32_t*)(dev + info.off_grid);
+  batch_fit_fields(b, info, ws, dev);
+  if ((rc = tpe_fit_above(&b, s))) return rc;
+  *launched = 1;
+  return TPE_OK;
+}
+
+// one tpe_level_run: what level_run_impl's steps share
+struct LevelRun {
+  const tpe_level_ws* ws;
+  hipStream_t s;
+  int32_t n_cand, precision, flags;
   tpe_pack_info info;
-  memset(&info, 0, sizeof(info));
-  // pack straight into the pinned staging buffer; the result readback area
-  // follows the blob.  A level with device fits launches them from inside the
-  // pack, as soon as their jobs are placed (early_fit_hook), unless profiling
-  EarlyFit ef{ws, (hipStream_t)stream, nullptr, 0, TPE_OK};
-  const bool hook = !g_prof.on && precision == TPE_PREC_F32 && direct_results() && early_fit_enabled();
-  if (hook) {
-    ef.dbase = ws->pinned_dev ? (const char*)ws->pinned_dev : device_alias(ws->pinned);
-    tpe_internal_pack_hook(TpePackHook{early_fit_hook, &ef});
-  }
-  int rc = tpe_host_pack_level(labels, n_labels, n_cand, seed, cand_base, n_cand_global, precision, ws->pinned,
-                               ws->pinned_bytes, &info);
-  if (hook) tpe_internal_pack_hook(TpePackHook{nullptr, nullptr});
-  if (ef.rc != TPE_OK) return ef.rc;
-  if (rc != TPE_OK && rc != TPE_E_SPACE) return fail(rc, "tpe_host_pack_level: bad level description");
-  tpe_internal_phase(TPE_PHASE_PACK);
-  const int64_t P = info.n_problems, C = P * (int64_t)n_cand;
-  const int64_t res_off = (info.blob_bytes + 255) & ~(int64_t)255;
+  int fit_launched;               // the early fit ran: its fields reach the problems by k_fit_patch
+  int64_t P, n_tiles_p;
+  int64_t res_off, rb_off;        // the pinned buffer's results; early selection's per-run bests after them
+  bool od;                        // ordered draws replace the sort of the pruned problems' candidates
+  unsigned char *host, *dev;      // the pinned staging buffer, the device blob
+  char* dbase;                    // the pinned buffer's device address (nullptr: results by readback)
+  const tpe_problem* xtmpl;       // expanded level: the templates and first problems (host copies)
+  const int32_t* xfirst;
+  const tpe_problem* hp;          // else the host-written problem rows
+};
+
+// what the level needs of the workspace (tpe_level_need); TPE_E_SPACE when the
+// pack or any buffer fell short
+static int level_need(LevelRun& x, int pack_rc, tpe_level_need* need) {
+  const tpe_pack_info& info = x.info;
+  const tpe_level_ws* ws = x.ws;
+  const int64_t P = x.P = info.n_problems, C = P * (int64_t)x.n_cand;
+  x.res_off = (info.blob_bytes + 255) & ~(int64_t)255;
   // early selection's per-run bests follow the results (host-visible)
   // (+ 64: the device exchange's status word between them)
-  const int64_t rb_off = (res_off + P * (int64_t)sizeof(tpe_result) + 64 + 255) & ~(int64_t)255;
-  need->pinned_bytes = rb_off + (info.n_tab_jobs > 0 ? info.n_tiles * (int64_t)sizeof(tpe_result) : 0);
+  x.rb_off = (x.res_off + P * (int64_t)sizeof(tpe_result) + 64 + 255) & ~(int64_t)255;
+  need->pinned_bytes = x.rb_off + (info.n_tab_jobs > 0 ? info.n_tiles * (int64_t)sizeof(tpe_result) : 0);
   need->blob_bytes = info.blob_bytes;
   need->cand = C;
   need->part = info.part_total;
@@ -5626,80 +5637,81 @@ static int level_run_impl(const tpe_label_in* labels, int32_t n_labels, int32_t 
   need->fit = info.fit_total;
   if (C >= ((int64_t)1 << 32)) return fail(TPE_E_ARG, "more than 2^32 candidates in one level: shard the batch");
   uint64_t sz = 0;
-  // ordered draws replace the sort of the pruned problems' candidates
-  const bool od = precision == TPE_PREC_F32 && (flags & TPE_BATCH_ORDERED_DRAWS) && info.n_sorted > 0 &&
-                  info.sort_count > 0 && info.n_pooled == 0;
+  x.od = x.precision == TPE_PREC_F32 && (x.flags & TPE_BATCH_ORDERED_DRAWS) && info.n_sorted > 0 &&
+         info.sort_count > 0 && info.n_pooled == 0;
   if (info.n_pooled > 0) need->pool_best = P;
   need->tab = info.tab_units;
-  if (od) need->draw_pref = info.n_sorted * (info.draw_blocks + 1);
-  if (!od && info.sort_end_bit > 0 && info.sort_count > 0) {
+  if (x.od) need->draw_pref = info.n_sorted * (info.draw_blocks + 1);
+  if (!x.od && info.sort_end_bit > 0 && info.sort_count > 0) {
+    int rc;
     if ((rc = tpe_sort_workspace_bytes(info.sort_count, &sz))) return rc;
     need->sort_tmp_bytes = (int64_t)sz;
   }
-  if (rc == TPE_E_SPACE || need->pinned_bytes > ws->pinned_bytes || need->blob_bytes > ws->blob_bytes ||
+  if (pack_rc == TPE_E_SPACE || need->pinned_bytes > ws->pinned_bytes || need->blob_bytes > ws->blob_bytes ||
       need->cand > ws->cand_cap || need->part > ws->part_cap || need->best > ws->best_cap ||
       need->result > ws->result_cap || need->fit > ws->fit_cap || need->sort_tmp_bytes > ws->sort_tmp_bytes ||
       need->draw_pref > ws->draw_pref_cap ||
       need->pool_best > ws->pool_best_cap || need->tab > ws->tab_cap)
     return fail(TPE_E_SPACE, "level workspace too small (see tpe_level_need)");
-  if (P == 0) return TPE_OK;
-  hipStream_t s = (hipStream_t)stream;
-  unsigned char* host = (unsigned char*)ws->pinned;
-  unsigned char* dev = (unsigned char*)ws->blob;
-  // the host-written ranges (tpe_pack_info.up_*): by k_upload, a copy kernel on
-  // the compute queue, or by the copy engine (TPE_UPLOAD_COPY=1)
+  return TPE_OK;
+}
+
+// the host-written ranges (tpe_pack_info.up_*): by k_upload, a copy kernel on
+// the compute queue, or by the copy engine (TPE_UPLOAD_COPY=1)
+static int level_upload(LevelRun& x) {
+  const tpe_pack_info& info = x.info;
+  x.dbase = !direct_results() ? nullptr : pinned_alias(x.ws);
+  UploadRanges r;
+  int64_t words = 0;
+  if (x.dbase && kernel_upload() && upload_ranges(info.up_off, info.up_len, info.n_up, x.ws->blob_bytes, r, words) &&
+      words <= ((int64_t)8 << 20))
+    return launch_upload(r, words, x.dbase, x.dev, x.s, "k_upload");
   hipError_t e = hipSuccess;
-  char* dbase = !direct_results() ? nullptr : (ws->pinned_dev ? (char*)ws->pinned_dev : device_alias(ws->pinned));
-  {
-    UploadRanges r;
-    int64_t words = 0;
-    if (dbase && kernel_upload() && upload_ranges(info, ws->blob_bytes, r, words) && words <= ((int64_t)8 << 20)) {
-      const int grid = (int)std::min<int64_t>(std::max<int64_t>((words + kUploadThreads - 1) / kUploadThreads, 1),
-                                              2048);
-      TPE_LAUNCH(k_upload, dim3(grid), dim3(kUploadThreads), 0, s, (const unsigned long long*)dbase,
-                 (unsigned long long*)dev, r);
-      if ((rc = hip_check("k_upload"))) return rc;
-    } else {
-      for (int k = 0; k < info.n_up && e == hipSuccess; ++k)
-        e = hipMemcpyAsync(dev + info.up_off[k], host + info.up_off[k], (size_t)info.up_len[k], hipMemcpyHostToDevice,
-                           s);
-    }
-  }
-  if (e != hipSuccess) return fail(TPE_E_HIP, hipGetErrorString(e));
-  // expanded level: the templates, first problems and new ids (uploaded above)
-  const tpe_problem* xtmpl = nullptr;
-  const int32_t* xfirst = nullptr;
-  const int64_t n_tiles_p = P > 0 ? info.n_tiles / P : 0;
-  if (info.n_expand > 0) {
-    const int64_t nl = info.n_expand;
-    const int64_t first_off = ((int64_t)(nl * sizeof(tpe_problem)) + 255) & ~(int64_t)255;
-    const int64_t ctr_off = (first_off + (nl + 1) * (int64_t)sizeof(int32_t) + 255) & ~(int64_t)255;
-    xtmpl = (const tpe_problem*)(host + info.off_expand);
-    xfirst = (const int32_t*)(host + info.off_expand + first_off);
-    if (nl >= ((int64_t)1 << 31) || xfirst[0] != 0 || xfirst[nl] != P || n_tiles_p * P != info.n_tiles ||
-        n_tiles_p < 1 || n_cand > n_tiles_p * kTile || info.n_tab_tiles != info.n_tiles)
+  for (int k = 0; k < info.n_up && e == hipSuccess; ++k)
+    e = hipMemcpyAsync(x.dev + info.up_off[k], x.host + info.up_off[k], (size_t)info.up_len[k], hipMemcpyHostToDevice,
+                       x.s);
+  return e != hipSuccess ? fail(TPE_E_HIP, hipGetErrorString(e)) : TPE_OK;
+}
+
+// expanded level: the device writes the problems and tiles from the templates,
+// first problems and new ids (uploaded with the rest)
+static int level_expand(LevelRun& x) {
+  const tpe_pack_info& info = x.info;
+  const int64_t P = x.P, n_tiles_p = x.n_tiles_p;
+  x.xtmpl = nullptr;
+  x.xfirst = nullptr;
+  if (info.n_expand <= 0) return TPE_OK;
+  const int64_t nl = info.n_expand;
+  const int64_t first_off = ((int64_t)(nl * sizeof(tpe_problem)) + 255) & ~(int64_t)255;
+  const int64_t ctr_off = (first_off + (nl + 1) * (int64_t)sizeof(int32_t) + 255) & ~(int64_t)255;
+  const tpe_problem* xtmpl = x.xtmpl = (const tpe_problem*)(x.host + info.off_expand);
+  const int32_t* xfirst = x.xfirst = (const int32_t*)(x.host + info.off_expand + first_off);
+  if (nl >= ((int64_t)1 << 31) || xfirst[0] != 0 || xfirst[nl] != P || n_tiles_p * P != info.n_tiles ||
+      n_tiles_p < 1 || x.n_cand > n_tiles_p * kTile || info.n_tab_tiles != info.n_tiles)
+    return fail(TPE_E_ARG, "tpe_level_run: bad expanded level");
+  for (int64_t l = 0; l < nl; ++l)
+    if (xfirst[l + 1] < xfirst[l] || xtmpl[l].tab_mode == TPE_TAB_NONE)
       return fail(TPE_E_ARG, "tpe_level_run: bad expanded level");
-    for (int64_t l = 0; l < nl; ++l)
-      if (xfirst[l + 1] < xfirst[l] || xtmpl[l].tab_mode == TPE_TAB_NONE)
-        return fail(TPE_E_ARG, "tpe_level_run: bad expanded level");
-    const int64_t n_thr = std::max<int64_t>(P * kProbWords, info.n_tiles);
-    TPE_LAUNCH(k_expand, dim3((unsigned)((n_thr + kExpandThreads - 1) / kExpandThreads)), dim3(kExpandThreads), 0, s,
-               (const tpe_problem*)(dev + info.off_expand), (const int32_t*)(dev + info.off_expand + first_off),
-               (int)nl, (const uint32_t*)(dev + info.off_expand + ctr_off), (tpe_problem*)(dev + info.off_problems),
-               (tpe_tile*)(dev + info.off_tiles), P, (int32_t)n_tiles_p, n_cand);
-    if ((rc = hip_check("k_expand"))) return rc;
-  }
-  if (ef.launched) {                           // the early fit's problem fields into the rows
-    TPE_LAUNCH(k_fit_patch, dim3(info.n_fit), dim3(64), 0, s, (const tpe_fit_job*)(dev + info.off_fit),
-               (const tpe_problem*)(dev + info.off_patch), (tpe_problem*)(dev + info.off_problems));
-    if ((rc = hip_check("k_fit_patch"))) return rc;
-  }
-  tpe_batch b;
+  const int64_t n_thr = std::max<int64_t>(P * kProbWords, info.n_tiles);
+  unsigned char* dev = x.dev;
+  TPE_LAUNCH(k_expand, dim3((unsigned)((n_thr + kExpandThreads - 1) / kExpandThreads)), dim3(kExpandThreads), 0, x.s,
+             (const tpe_problem*)(dev + info.off_expand), (const int32_t*)(dev + info.off_expand + first_off),
+             (int)nl, (const uint32_t*)(dev + info.off_expand + ctr_off), (tpe_problem*)(dev + info.off_problems),
+             (tpe_tile*)(dev + info.off_tiles), P, (int32_t)n_tiles_p, x.n_cand);
+  return hip_check("k_expand");
+}
+
+// the level's tpe_batch from the packed level, the workspace and the device blob
+static void level_batch(const LevelRun& x, tpe_batch& b) {
+  const tpe_pack_info& info = x.info;
+  const tpe_level_ws* ws = x.ws;
+  const unsigned char* dev = x.dev;
+  const int64_t P = x.P;
   memset(&b, 0, sizeof(b));
   b.problems = (const tpe_problem*)(dev + info.off_problems);
   b.n_problems = (int32_t)P;
-  b.precision = precision;
-  b.flags = flags;
+  b.precision = x.precision;
+  b.flags = x.flags;
   b.sample = 1;
   b.sort_end_bit = info.sort_end_bit;
   b.key_bits = info.key_bits;
@@ -5708,7 +5720,7 @@ static int level_run_impl(const tpe_label_in* labels, int32_t n_labels, int32_t 
   b.samp = (const double*)(dev + info.off_samp);
   b.grid = (const int32_t*)(dev + info.off_grid);
   b.cand = ws->cand; b.coord = ws->coord; b.keys = ws->keys; b.vals = ws->vals;
-  if (od) {
+  if (x.od) {
     b.keys_sorted = ws->keys; b.vals_sorted = ws->vals;
     b.draw_pref = ws->draw_pref; b.draw_blocks = info.draw_blocks; b.n_sorted = (int32_t)info.n_sorted;
   } else if (info.sort_end_bit > 0) {
@@ -5717,12 +5729,12 @@ static int level_run_impl(const tpe_label_in* labels, int32_t n_labels, int32_t 
   } else {
     b.keys_sorted = ws->keys; b.vals_sorted = ws->vals;
   }
-  b.total_cand = C;
+  b.total_cand = P * (int64_t)x.n_cand;
   b.sort_count = info.sort_count;
   b.tiles = (const tpe_tile*)(dev + info.off_tiles);
   b.n_tiles = (int32_t)info.n_tiles;
   // (the packer gives every problem n_tiles_p tiles {r, j * kTile}, in order)
-  b.tiles_per_problem = n_tiles_p * P == info.n_tiles ? (int32_t)n_tiles_p : 0;
+  b.tiles_per_problem = x.n_tiles_p * P == info.n_tiles ? (int32_t)x.n_tiles_p : 0;
   b.fin_tiles = (const int32_t*)(dev + info.off_fin_tiles);
   b.n_fin_tiles = (int32_t)info.n_fin_tiles;
   b.work = (const tpe_work*)(dev + info.off_work);
@@ -5733,7 +5745,7 @@ static int level_run_impl(const tpe_label_in* labels, int32_t n_labels, int32_t 
   b.samp_tiles = (const int32_t*)(dev + info.off_samp_tiles);
   b.n_samp_tiles = (int32_t)info.n_samp_tiles;
   b.n_samp_eager = (int32_t)info.n_samp_eager;
-  b.tab_tiles = xtmpl ? nullptr : (const int32_t*)(dev + info.off_tab_tiles);   // (expanded: every tile, in order)
+  b.tab_tiles = x.xtmpl ? nullptr : (const int32_t*)(dev + info.off_tab_tiles);   // (expanded: every tile, in order)
   b.n_tab_tiles = (int32_t)info.n_tab_tiles;
   if (info.n_tab_jobs > 0) {
     b.tab_jobs = (const tpe_tab_job*)(dev + info.off_tab_jobs);
@@ -5746,81 +5758,249 @@ static int level_run_impl(const tpe_label_in* labels, int32_t n_labels, int32_t 
   }
   // the select stage writes the results straight into the pinned staging
   // buffer when the device can address it (no readback copy)
-  tpe_result* rh = (tpe_result*)(host + res_off);
-  tpe_result* rd = dbase ? (tpe_result*)(dbase + res_off) : nullptr;
-  // early selection (include/tpe_hip.h): the sample stage reports each run of
-  // tabulated tiles to host-visible memory, the table stage selects the lazy
-  // categoricals, and only the rest go through the select stage
+  b.result = x.dbase ? (tpe_result*)(x.dbase + x.res_off) : ws->result;
+  if (info.n_fit > 0 && !x.fit_launched) batch_fit_fields(b, info, ws, dev);
+}
+
+// early selection (include/tpe_hip.h): the sample stage reports each run of
+// tabulated tiles to host-visible memory, the table stage selects the lazy
+// categoricals, and only the rest go through the select stage — with the
+// sample stage's specialised kernel where the level's tables allow it
+static void level_early_select(const LevelRun& x, tpe_batch& b) {
+  const tpe_pack_info& info = x.info;
+  if (!(info.n_tab_jobs > 0 && x.dbase)) return;
+  const tpe_problem* hp = x.hp;
+  const int32_t flags = x.flags;
+  b.early_select = 1;
+  b.run_best = (tpe_result*)(x.dbase + x.rb_off);
+  const bool lz = !(flags & TPE_BATCH_WRITE_CAND);
+  int32_t late = 0;
+  for (int64_t r = 0; hp && r < x.P; ++r) {
+    const tpe_problem& q = hp[r];
+    const bool lazy = lz && (q.flags & TPE_F_CAT_LAZY) && q.family == TPE_FAM_CATEGORICAL && q.samp_len <= 64;
+    late += !(lazy || q.tab_mode != TPE_TAB_NONE);
+  }
+  b.n_late = late;
+  // the sample stage's specialised kernel: every tabulated problem cells with
+  // both tables within its LDS and a staged sampler (the problem rows: the
+  // host's, or an expanded level's label templates)
+  const bool fast_ok = x.precision == TPE_PREC_F32 && !(flags & (TPE_BATCH_WRITE_CAND | TPE_BATCH_NO_TAB_FAST)) &&
+                       !tab_fast_disabled();
+  // k_sample_fast: every tabulated problem a log-polynomial cells table or a
+  // lattice within its LDS; k_sample_tab's FAST pass: log-polynomial cells only
+  bool fast = fast_ok, fast_lp = fast_ok;
+  const tpe_problem* rows = hp ? hp : x.xtmpl;
+  const int64_t n_rows = hp ? x.P : (x.xtmpl ? info.n_expand : 0);
+  int max_cells = 0, max_units = 0, max_samp = 0;
+  for (int64_t r = 0; (fast || fast_lp) && r < n_rows; ++r) {
+    const tpe_problem& q = rows[r];
+    if (q.tab_mode == TPE_TAB_NONE) continue;
+    const bool samp_ok = q.samp_len > 0 && q.samp_len <= kCumLds;
+    const bool lp = q.tab_mode == TPE_TAB_CELLS && (q.flags & TPE_F_LOGPOLY) && q.tab_n[0] <= kTabLdsCells && samp_ok;
+    const bool lat = q.tab_mode == TPE_TAB_LATTICE && q.tab_n[0] <= kFastLatMax && samp_ok;
+    fast_lp = fast_lp && lp;
+    fast = fast && (lp || lat);
+    max_cells = std::max(max_cells, lp ? q.tab_n[0] : 0);
+    max_units = std::max(max_units, lp ? TPE_TAB_ROW_UNITS * q.tab_n[0] : fast_lat_units(q.tab_n[0]));
+    max_samp = std::max(max_samp, q.samp_len);
+  }
+  // (the small-workgroup kernel when the level's tables and sampler rows fit its LDS)
+  const bool fast2 = fast && !fast2_disabled() && !(flags & TPE_BATCH_NO_FAST2) && max_cells <= kFastMaxCells &&
+                     max_units <= kFastMaxUnits &&
+                     max_samp <= kFastSamp;
+  b.tab_fast = n_rows > 0 ? (fast2 ? 1 + max_units : fast_lp ? 1 : 0) : 0;
+}
+
+// device exchange (sharded level over RCCL): whether this level takes it — run
+// records and results then go to device scratch after the exchange slots,
+// combined on the device (level_exchange)
+static bool level_exchange_setup(const LevelRun& x, const LevelEx* lx, tpe_batch& b) {
+  const tpe_pack_info& info = x.info;
+  const int64_t P = x.P, xper = TPE_EXCHANGE_HEADER + P * (int64_t)sizeof(tpe_result);
+  if (!(lx && lx->ex && lx->ex->comm && x.dbase && b.early_select && lx->P == P)) return false;
+  const int64_t base = ((int64_t)lx->ex->world * xper + 255) & ~(int64_t)255;
+  const int64_t need_x = base + (info.n_tiles + P) * (int64_t)sizeof(tpe_result);
+  const int64_t runs_bytes = 2 * P * (int64_t)sizeof(int32_t);
+  if (!(lx->ex->dev && lx->ex->dev_bytes >= need_x && runs_bytes <= info.n_tiles * (int64_t)sizeof(tpe_result)))
+    return false;
+  unsigned char* xrun = (unsigned char*)lx->ex->dev + base;
+  b.run_best = (tpe_result*)xrun;
+  b.result = (tpe_result*)(xrun + info.n_tiles * (int64_t)sizeof(tpe_result));
+  return true;
+}
+
+// the device exchange after the level's launches: each rank's runs reduced
+// into its slot, the in-place all-gather, the combine; the global winners into
+// `out` and the ranks' worst status into *lx->all_status
+static int level_exchange(const LevelRun& x, const LevelEx* lx, const tpe_batch& b, tpe_result* out) {
+  const tpe_pack_info& info = x.info;
+  const int64_t P = x.P, n_tiles_p = x.n_tiles_p, xper = TPE_EXCHANGE_HEADER + P * (int64_t)sizeof(tpe_result);
+  unsigned char* host = x.host;
+  hipStream_t s = x.s;
+  tpe_result* rd = (tpe_result*)(x.dbase + x.res_off);
+  int rc;
+  // each problem's span of the tabulated tile list: from the packer's layout
+  // on the device (a level of at most kRunsDevMax problems with tpp tiles
+  // each), else written by the host (host-visible: the run-record area is
+  // free in this mode) — its runs are enumerated on the device as the host
+  // reduction (level_reduce_runs) enumerates them
+  const int n_tab = (int)info.n_tab_tiles, per = tab_tiles_per_wg(n_tab, tab_wgs_per_cu(&b));
+  const int tpp = b.tiles_per_problem;
+  const int32_t* d_span = nullptr;
+  if (P > kRunsDevMax || tpp <= 0) {
+    int32_t* span = (int32_t*)(host + x.rb_off);
+    if (x.xtmpl) {                                   // expanded: every problem's tiles, in order
+      for (int64_t r = 0; r < P; ++r) { span[2 * r] = (int32_t)(r * n_tiles_p); span[2 * r + 1] = (int32_t)n_tiles_p; }
+    } else {
+      for (int64_t r = 0; r < P; ++r) span[2 * r] = span[2 * r + 1] = 0;
+      const int32_t* list = (const int32_t*)(host + info.off_tab_tiles);
+      const tpe_tile* tl = (const tpe_tile*)(host + info.off_tiles);
+      for (int i = 0; i < n_tab; ++i) {
+        const int pr = tl[list[i]].problem;
+        if (span[2 * pr + 1]++ == 0) span[2 * pr] = i;
+      }
+    }
+    d_span = (const int32_t*)(x.dbase + x.rb_off);
+  }
+  const unsigned int blocks = (unsigned int)((P + kCombThreads / 64 - 1) / (kCombThreads / 64));
+  unsigned char* slot = (unsigned char*)lx->ex->dev + (int64_t)lx->ex->rank * xper;
+  int32_t* st_host = (int32_t*)(host + x.res_off + P * (int64_t)sizeof(tpe_result));   // (the pad before rb_off)
+  int32_t* st_dev = (int32_t*)(x.dbase + x.res_off + P * (int64_t)sizeof(tpe_result));
+  // (forced exchange on one rank: no gather, no combine — unless
+  // TPE_FORCE_COMBINE=1, the tests' way to run the N > 1 device combine,
+  // slot → in-place all-gather → k_combine, on the box's one GPU)
+  const bool one = lx->ex->world == 1 && !force_combine();
+  TPE_LAUNCH(k_runs_reduce, dim3(blocks), dim3(kCombThreads), 0, s, d_span, x.xtmpl ? nullptr : b.tab_tiles, per,
+             b.problems, tpp, (const tpe_result*)b.run_best, (const tpe_result*)b.result, P, slot, (int32_t)TPE_OK,
+             one ? rd : (tpe_result*)nullptr, one ? st_dev : (int32_t*)nullptr);
+  if ((rc = hip_check("k_runs_reduce"))) return rc;
+  if ((rc = rccl_allgather_inplace(lx->ex, xper, s))) return rc;
+  // the level's collective is issued: from here every failure is this level's
+  // status (done = 1), so the caller never issues a second collective for it
+  // that the other ranks would not join
+  auto gathered_fail = [&](int code) {
+    *lx->all_status = code;
+    *lx->done = 1;
+    return code;
+  };
+  if (!one) {
+    const unsigned int cblocks = (unsigned int)((P + kCombThreads - 1) / kCombThreads);   // (a thread a problem)
+    TPE_LAUNCH(k_combine, dim3(cblocks), dim3(kCombThreads), 0, s, (const unsigned char*)lx->ex->dev,
+               lx->ex->world, xper, P, rd, st_dev);
+    if ((rc = hip_check("k_combine"))) return gathered_fail(rc);
+  }
+  tpe_internal_phase(TPE_PHASE_LAUNCHED);
+  const hipError_t e = hipStreamSynchronize(s);
+  if (e != hipSuccess) return gathered_fail(fail(TPE_E_HIP, hipGetErrorString(e)));
+  tpe_internal_phase(TPE_PHASE_SYNCED);
+  memcpy(out, host + x.res_off, (size_t)P * sizeof(tpe_result));
+  *lx->all_status = *(volatile int32_t*)st_host;
+  *lx->done = 1;
+  return TPE_OK;
+}
+
+// early selection's host reduction: each tabulated problem's best of its runs
+// (np.argmax order), runs enumerated exactly as the sample stage partitions
+// the tile list (expanded level: the identity list, tile t of problem t /
+// n_tiles_p).  The winners into the pinned results `rh` — or, true returned,
+// straight into `out`.
+static bool level_reduce_runs(const LevelRun& x, const tpe_batch& b, tpe_result* rh, tpe_result* out) {
+  const tpe_pack_info& info = x.info;
+  const int64_t P = x.P, n_tiles_p = x.n_tiles_p;
+  const tpe_problem *xtmpl = x.xtmpl, *hp = x.hp;
+  const unsigned char* host = x.host;
+  const tpe_result* rb = (const tpe_result*)(host + x.rb_off);
+  const int32_t* list = xtmpl ? nullptr : (const int32_t*)(host + info.off_tab_tiles);
+  const tpe_tile* tl = xtmpl ? nullptr : (const tpe_tile*)(host + info.off_tiles);
+  auto tile_of = [&](int i) { return list ? list[i] : i; };
+  auto prob_of = [&](int t) { return tl ? tl[t].problem : (int)(t / n_tiles_p); };
+  const int n_tab = (int)info.n_tab_tiles, per = tab_tiles_per_wg(n_tab, tab_wgs_per_cu(&b));
+  if (xtmpl && n_tiles_p > 0 && per % n_tiles_p == 0) {
+    // expanded level (every problem tabulated, tiles in order) whose workgroups
+    // hold whole problems: each problem is one run, recorded at its first
+    // tile — gathered straight into `out`, in slices on the worker pool (a
+    // batched level has ~10^5 of them)
+    struct Gather { const tpe_result* rb; tpe_result* out; int64_t P, ntp, slice; } g{rb, out, P, n_tiles_p, 4096};
+    tpe_pool::parallel_for((int)((P + g.slice - 1) / g.slice), [](void* c, int k) {
+      const Gather& q = *(const Gather*)c;
+      const int64_t r1 = std::min(q.P, (k + 1) * q.slice);
+      for (int64_t r = k * q.slice; r < r1; ++r) q.out[r] = q.rb[r * q.ntp];
+    }, &g);
+    return true;
+  }
+  const int tpp = b.tiles_per_problem;
+  if (tpp > 0) {
+    // the packer's layout (every problem tpp tiles, the list the tabulated
+    // problems' tiles in problem order): a problem's runs start at its first
+    // list position and at every multiple of per after it — visited directly,
+    // not found by a scan of the whole list (the headline's 5 problems have
+    // ~5000 tabulated tiles and a few hundred runs)
+    int rank = 0;
+    for (int64_t r = 0; r < P; ++r) {
+      if (hp && hp[r].tab_mode == TPE_TAB_NONE) continue;
+      tpe_result w{0, 0, 0, 0, -1, -1};
+      const int a = rank * tpp, e = a + tpp;
+      for (int pos = a; pos < e; pos = (pos / per + 1) * per) {
+        const tpe_result& c = rb[r * tpp + (pos - a)];
+        if (host_better(c.score, c.idx, w.score, w.idx)) w = c;
+      }
+      rh[r] = w;
+      ++rank;
+    }
+  } else {
+    for (int64_t r = 0; r < P; ++r)
+      if (!hp || hp[r].tab_mode != TPE_TAB_NONE) { rh[r] = tpe_result{0, 0, 0, 0, -1, -1}; }
+    for (int i = 0; i < n_tab; ++i) {
+      const int t = tile_of(i), pr = prob_of(t);
+      if (i % per != 0 && prob_of(tile_of(i - 1)) == pr) continue;      // not a run's first tile
+      const tpe_result& c = rb[t];
+      tpe_result& w = rh[pr];
+      if (host_better(c.score, c.idx, w.score, w.idx)) w = c;
+    }
+  }
+  return false;
+}
+
+static int level_run_impl(const tpe_label_in* labels, int32_t n_labels, int32_t n_cand, uint64_t seed,
+                          int64_t cand_base, int64_t n_cand_global, int32_t precision, int32_t flags,
+                          const tpe_level_ws* ws, tpe_level_need* need, void* stream, tpe_result* out,
+                          const LevelEx* lx) {
+  if (!ws || !need || (n_labels > 0 && !out)) return fail(TPE_E_ARG, "null workspace/need/out");
+  memset(need, 0, sizeof(*need));
+  LevelRun x;
+  memset(&x, 0, sizeof(x));
+  x.ws = ws; x.s = (hipStream_t)stream;
+  x.n_cand = n_cand; x.precision = precision; x.flags = flags;
+  x.host = (unsigned char*)ws->pinned; x.dev = (unsigned char*)ws->blob;
+  const tpe_pack_info& info = x.info;
+  // pack straight into the pinned staging buffer; the result readback area
+  // follows the blob.  A level with device fits launches them between the
+  // pack's plan and its fill, as soon as their jobs are placed, unless profiling
+  TpePackLead lead;
+  int rc = tpe_internal_pack_plan(labels, n_labels, n_cand, seed, cand_base, n_cand_global, precision, ws->pinned,
+                                  ws->pinned_bytes, &x.info, &lead);
+  if (rc == TPE_OK && !g_prof.on && precision == TPE_PREC_F32 && direct_results() && early_fit_enabled() &&
+      (rc = early_fit(info, lead, ws, x.s, &x.fit_launched)))
+    return rc;
+  if (rc == TPE_OK) rc = tpe_internal_pack_fill(&x.info);
+  if (rc != TPE_OK && rc != TPE_E_SPACE) return fail(rc, "tpe_host_pack_level: bad level description");
+  tpe_internal_phase(TPE_PHASE_PACK);
+  if ((rc = level_need(x, rc, need))) return rc;
+  const int64_t P = x.P;
+  if (P == 0) return TPE_OK;
+  x.n_tiles_p = info.n_tiles / P;
+  if ((rc = level_upload(x)) || (rc = level_expand(x))) return rc;
+  if (x.fit_launched) {                        // the early fit's problem fields into the rows
+    TPE_LAUNCH(k_fit_patch, dim3(info.n_fit), dim3(64), 0, x.s, (const tpe_fit_job*)(x.dev + info.off_fit),
+               (const tpe_problem*)(x.dev + info.off_patch), (tpe_problem*)(x.dev + info.off_problems));
+    if ((rc = hip_check("k_fit_patch"))) return rc;
+  }
   // (expanded level: no host-written problems; every problem is tabulated)
-  const tpe_problem* hp = xtmpl ? nullptr : (const tpe_problem*)(host + info.off_problems);
-  if (info.n_tab_jobs > 0 && dbase) {
-    b.early_select = 1;
-    b.run_best = (tpe_result*)(dbase + rb_off);
-    const bool lz = !(flags & TPE_BATCH_WRITE_CAND);
-    int32_t late = 0;
-    for (int64_t r = 0; hp && r < P; ++r) {
-      const tpe_problem& q = hp[r];
-      const bool lazy = lz && (q.flags & TPE_F_CAT_LAZY) && q.family == TPE_FAM_CATEGORICAL && q.samp_len <= 64;
-      late += !(lazy || q.tab_mode != TPE_TAB_NONE);
-    }
-    b.n_late = late;
-    // the sample stage's specialised kernel: every tabulated problem cells with
-    // both tables within its LDS and a staged sampler (the problem rows: the
-    // host's, or an expanded level's label templates)
-    const bool fast_ok = precision == TPE_PREC_F32 && !(flags & (TPE_BATCH_WRITE_CAND | TPE_BATCH_NO_TAB_FAST)) &&
-                         !tab_fast_disabled();
-    // k_sample_fast: every tabulated problem a log-polynomial cells table or a
-    // lattice within its LDS; k_sample_tab's FAST pass: log-polynomial cells only
-    bool fast = fast_ok, fast_lp = fast_ok;
-    const tpe_problem* rows = hp ? hp : xtmpl;
-    const int64_t n_rows = hp ? P : (xtmpl ? info.n_expand : 0);
-    int max_cells = 0, max_units = 0, max_samp = 0;
-    for (int64_t r = 0; (fast || fast_lp) && r < n_rows; ++r) {
-      const tpe_problem& q = rows[r];
-      if (q.tab_mode == TPE_TAB_NONE) continue;
-      const bool samp_ok = q.samp_len > 0 && q.samp_len <= kCumLds;
-      const bool lp = q.tab_mode == TPE_TAB_CELLS && (q.flags & TPE_F_LOGPOLY) && q.tab_n[0] <= kTabLdsCells && samp_ok;
-      const bool lat = q.tab_mode == TPE_TAB_LATTICE && q.tab_n[0] <= kFastLatMax && samp_ok;
-      fast_lp = fast_lp && lp;
-      fast = fast && (lp || lat);
-      max_cells = std::max(max_cells, lp ? q.tab_n[0] : 0);
-      max_units = std::max(max_units, lp ? TPE_TAB_ROW_UNITS * q.tab_n[0] : fast_lat_units(q.tab_n[0]));
-      max_samp = std::max(max_samp, q.samp_len);
-    }
-    // (the small-workgroup kernel when the level's tables and sampler rows fit its LDS)
-    const bool fast2 = fast && !fast2_disabled() && !(flags & TPE_BATCH_NO_FAST2) && max_cells <= kFastMaxCells &&
-                       max_units <= kFastMaxUnits &&
-                       max_samp <= kFastSamp;
-    b.tab_fast = n_rows > 0 ? (fast2 ? 1 + max_units : fast_lp ? 1 : 0) : 0;
-  }
-  b.result = rd ? rd : ws->result;
-  // device exchange (sharded level over RCCL): run records and results in
-  // device scratch after the exchange slots, combined on the device
-  const int64_t xper = TPE_EXCHANGE_HEADER + P * (int64_t)sizeof(tpe_result);
-  unsigned char* xrun = nullptr;
-  bool dex = false;
-  if (lx && lx->ex && lx->ex->comm && dbase && b.early_select && lx->P == P) {
-    const int64_t base = ((int64_t)lx->ex->world * xper + 255) & ~(int64_t)255;
-    const int64_t need_x = base + (info.n_tiles + P) * (int64_t)sizeof(tpe_result);
-    const int64_t runs_bytes = 2 * P * (int64_t)sizeof(int32_t);
-    if (lx->ex->dev && lx->ex->dev_bytes >= need_x && runs_bytes <= info.n_tiles * (int64_t)sizeof(tpe_result)) {
-      dex = true;
-      xrun = (unsigned char*)lx->ex->dev + base;
-      b.run_best = (tpe_result*)xrun;
-      b.result = (tpe_result*)(xrun + info.n_tiles * (int64_t)sizeof(tpe_result));
-    }
-  }
-  if (info.n_fit > 0 && !ef.launched) {
-    b.fit = (const tpe_fit_job*)(dev + info.off_fit);
-    b.n_fit = info.n_fit;
-    b.below_idx = (const int32_t*)(dev + info.off_below_idx);
-    b.fit_seg = (const int64_t*)(dev + info.off_fit_seg);
-    b.fit_total = info.fit_total;
-    b.fit_keys = ws->fit_keys; b.fit_keys_sorted = ws->fit_keys_sorted;
-    b.fit_vals = ws->fit_vals; b.fit_vals_sorted = ws->fit_vals_sorted;
-    b.fit_max_new = info.fit_max_new; b.fit_max_obs = info.fit_max_obs; b.fit_max_merge = info.fit_max_merge;
-    b.fit_n_delta = info.fit_n_delta;
-  }
+  x.hp = x.xtmpl ? nullptr : (const tpe_problem*)(x.host + info.off_problems);
+  tpe_batch b;
+  level_batch(x, b);
+  level_early_select(x, b);
+  const bool dex = level_exchange_setup(x, lx, b);
   if (g_prof.on) {
     g_prof.valid = 0;
     if ((rc = check_batch(&b)) || (rc = run_batch_profiled(&b, stream))) return rc;
@@ -5828,129 +6008,19 @@ static int level_run_impl(const tpe_label_in* labels, int32_t n_labels, int32_t 
     return rc;
   }
   if (dex) {
-    // each problem's span of the tabulated tile list: from the packer's layout
-    // on the device (a level of at most kRunsDevMax problems with tpp tiles
-    // each), else written by the host (host-visible: the run-record area is
-    // free in this mode) — its runs are enumerated on the device as the host
-    // reduction below enumerates them
-    const int n_tab = (int)info.n_tab_tiles, per = tab_tiles_per_wg(n_tab, tab_wgs_per_cu(&b));
-    const int tpp = b.tiles_per_problem;
-    const int32_t* d_span = nullptr;
-    if (P > kRunsDevMax || tpp <= 0) {
-      int32_t* span = (int32_t*)(host + rb_off);
-      if (xtmpl) {                                   // expanded: every problem's tiles, in order
-        for (int64_t r = 0; r < P; ++r) { span[2 * r] = (int32_t)(r * n_tiles_p); span[2 * r + 1] = (int32_t)n_tiles_p; }
-      } else {
-        for (int64_t r = 0; r < P; ++r) span[2 * r] = span[2 * r + 1] = 0;
-        const int32_t* list = (const int32_t*)(host + info.off_tab_tiles);
-        const tpe_tile* tl = (const tpe_tile*)(host + info.off_tiles);
-        for (int i = 0; i < n_tab; ++i) {
-          const int pr = tl[list[i]].problem;
-          if (span[2 * pr + 1]++ == 0) span[2 * pr] = i;
-        }
-      }
-      d_span = (const int32_t*)(dbase + rb_off);
-    }
-    const unsigned int blocks = (unsigned int)((P + kCombThreads / 64 - 1) / (kCombThreads / 64));
-    unsigned char* slot = (unsigned char*)lx->ex->dev + (int64_t)lx->ex->rank * xper;
-    int32_t* st_host = (int32_t*)(host + res_off + P * (int64_t)sizeof(tpe_result));   // (the pad before rb_off)
-    int32_t* st_dev = (int32_t*)(dbase + res_off + P * (int64_t)sizeof(tpe_result));
-    // (forced exchange on one rank: no gather, no combine — unless
-    // TPE_FORCE_COMBINE=1, the tests' way to run the N > 1 device combine,
-    // slot → in-place all-gather → k_combine, on the box's one GPU)
-    const bool one = lx->ex->world == 1 && !force_combine();
-    TPE_LAUNCH(k_runs_reduce, dim3(blocks), dim3(kCombThreads), 0, s, d_span, xtmpl ? nullptr : b.tab_tiles, per,
-               b.problems, tpp, (const tpe_result*)b.run_best, (const tpe_result*)b.result, P, slot, (int32_t)TPE_OK,
-               one ? rd : (tpe_result*)nullptr, one ? st_dev : (int32_t*)nullptr);
-    if ((rc = hip_check("k_runs_reduce"))) return rc;
-    if ((rc = rccl_allgather_inplace(lx->ex, xper, s))) return rc;
-    // the level's collective is issued: from here every failure is this level's
-    // status (done = 1), so the caller never issues a second collective for it
-    // that the other ranks would not join
-    auto gathered_fail = [&](int code) {
-      *lx->all_status = code;
-      *lx->done = 1;
-      return code;
-    };
-    if (!one) {
-      const unsigned int cblocks = (unsigned int)((P + kCombThreads - 1) / kCombThreads);   // (a thread a problem)
-      TPE_LAUNCH(k_combine, dim3(cblocks), dim3(kCombThreads), 0, s, (const unsigned char*)lx->ex->dev,
-                 lx->ex->world, xper, P, rd, st_dev);
-      if ((rc = hip_check("k_combine"))) return gathered_fail(rc);
-    }
+    if ((rc = level_exchange(x, lx, b, out))) return rc;
+  } else {
+    tpe_result* rh = (tpe_result*)(x.host + x.res_off);
+    hipError_t e = x.dbase ? hipSuccess
+                           : hipMemcpyAsync(rh, ws->result, (size_t)P * sizeof(tpe_result), hipMemcpyDeviceToHost, x.s);
     tpe_internal_phase(TPE_PHASE_LAUNCHED);
-    e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return gathered_fail(fail(TPE_E_HIP, hipGetErrorString(e)));
+    if (e == hipSuccess) e = hipStreamSynchronize(x.s);
+    if (e != hipSuccess) return fail(TPE_E_HIP, hipGetErrorString(e));
     tpe_internal_phase(TPE_PHASE_SYNCED);
-    memcpy(out, rh, (size_t)P * sizeof(tpe_result));
-    *lx->all_status = *(volatile int32_t*)st_host;
-    *lx->done = 1;
-    tpe_internal_phase(TPE_PHASE_LEVEL);
-    return g_prof.on ? profile_collect(b, info, xtmpl ? xtmpl : hp, xfirst, n_cand) : TPE_OK;
+    if (!(b.early_select && level_reduce_runs(x, b, rh, out))) memcpy(out, rh, (size_t)P * sizeof(tpe_result));
   }
-  e = rd ? hipSuccess : hipMemcpyAsync(rh, ws->result, (size_t)P * sizeof(tpe_result), hipMemcpyDeviceToHost, s);
-  tpe_internal_phase(TPE_PHASE_LAUNCHED);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return fail(TPE_E_HIP, hipGetErrorString(e));
-  tpe_internal_phase(TPE_PHASE_SYNCED);
-  if (b.early_select) {
-    // each tabulated problem: the best of its runs (np.argmax order), runs
-    // enumerated exactly as the sample stage partitions the tile list
-    // (expanded level: the identity list, tile t of problem t / n_tiles_p)
-    const tpe_result* rb = (const tpe_result*)(host + rb_off);
-    const int32_t* list = xtmpl ? nullptr : (const int32_t*)(host + info.off_tab_tiles);
-    const tpe_tile* tl = xtmpl ? nullptr : (const tpe_tile*)(host + info.off_tiles);
-    auto tile_of = [&](int i) { return list ? list[i] : i; };
-    auto prob_of = [&](int t) { return tl ? tl[t].problem : (int)(t / n_tiles_p); };
-    const int n_tab = (int)info.n_tab_tiles, per = tab_tiles_per_wg(n_tab, tab_wgs_per_cu(&b));
-    if (xtmpl && n_tiles_p > 0 && per % n_tiles_p == 0) {
-      // expanded level (every problem tabulated, tiles in order) whose workgroups
-      // hold whole problems: each problem is one run, recorded at its first
-      // tile — gathered straight into `out`, in slices on the worker pool (a
-      // batched level has ~10^5 of them)
-      struct Gather { const tpe_result* rb; tpe_result* out; int64_t P, ntp, slice; } g{rb, out, P, n_tiles_p, 4096};
-      tpe_pool::parallel_for((int)((P + g.slice - 1) / g.slice), [](void* c, int k) {
-        const Gather& q = *(const Gather*)c;
-        const int64_t r1 = std::min(q.P, (k + 1) * q.slice);
-        for (int64_t r = k * q.slice; r < r1; ++r) q.out[r] = q.rb[r * q.ntp];
-      }, &g);
-      tpe_internal_phase(TPE_PHASE_LEVEL);
-      return g_prof.on ? profile_collect(b, info, xtmpl, xfirst, n_cand) : TPE_OK;
-    }
-    const int tpp = b.tiles_per_problem;
-    if (tpp > 0) {
-      // the packer's layout (every problem tpp tiles, the list the tabulated
-      // problems' tiles in problem order): a problem's runs start at its first
-      // list position and at every multiple of per after it — visited directly,
-      // not found by a scan of the whole list (the headline's 5 problems have
-      // ~5000 tabulated tiles and a few hundred runs)
-      int rank = 0;
-      for (int64_t r = 0; r < P; ++r) {
-        if (hp && hp[r].tab_mode == TPE_TAB_NONE) continue;
-        tpe_result w{0, 0, 0, 0, -1, -1};
-        const int a = rank * tpp, e = a + tpp;
-        for (int pos = a; pos < e; pos = (pos / per + 1) * per) {
-          const tpe_result& c = rb[r * tpp + (pos - a)];
-          if (host_better(c.score, c.idx, w.score, w.idx)) w = c;
-        }
-        rh[r] = w;
-        ++rank;
-      }
-    } else {
-      for (int64_t r = 0; r < P; ++r)
-        if (!hp || hp[r].tab_mode != TPE_TAB_NONE) { rh[r] = tpe_result{0, 0, 0, 0, -1, -1}; }
-      for (int i = 0; i < n_tab; ++i) {
-        const int t = tile_of(i), pr = prob_of(t);
-        if (i % per != 0 && prob_of(tile_of(i - 1)) == pr) continue;      // not a run's first tile
-        const tpe_result& c = rb[t];
-        tpe_result& w = rh[pr];
-        if (host_better(c.score, c.idx, w.score, w.idx)) w = c;
-      }
-    }
-  }
-  memcpy(out, rh, (size_t)P * sizeof(tpe_result));
   tpe_internal_phase(TPE_PHASE_LEVEL);
-  return g_prof.on ? profile_collect(b, info, xtmpl ? xtmpl : hp, xfirst, n_cand) : TPE_OK;
+  return g_prof.on ? profile_collect(b, info, x.xtmpl ? x.xtmpl : x.hp, x.xfirst, n_cand) : TPE_OK;
 }
 
 }  // extern "C"

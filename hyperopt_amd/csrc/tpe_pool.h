@@ -1,4 +1,5 @@
-// tpe_pool.h — the host runtime's worker pool (tpe_pool.cpp), internal.
+// tpe_pool.h — the host runtime's worker pool (tpe_pool.cpp) and the level
+// packer's two steps (tpe_host.cpp), internal.
 //
 // The per-label host work of a suggest (the Parzen fits of every label a tree
 // level needs, tpe.py:398-475 / 573-607 per label) is independent across
@@ -22,15 +23,24 @@ int workers();
 
 }  // namespace tpe_pool
 
-// tpe_host_pack_level's early hook (internal, per thread): tpe_level_run sets it
-// around its pack; the packer calls fn once the blob's leading sections are
-// placed and its device-fit jobs written, before the fill — `early` holds the
-// leading offsets, the fit counts, the bytes to upload (up_off / up_len[0]) and
-// the device bytes the fit touches (blob_bytes) — so the device fit can run
-// while the host fills the rest.  {nullptr, nullptr}: no hook.
+// tpe_host_pack_level in its two steps (tpe_host.cpp; internal).  The plan
+// validates the level, decides its tables and sort keys, sizes and places the
+// blob's leading sections and — when the blob holds them (lead->direct) —
+// writes the device-fit sections; it fills info's leading fields (the leading
+// offsets, n_fit, fit_*, n_problems).  The fill writes everything else and the
+// rest of info, with tpe_host_pack_level's return codes.  Between the two the
+// caller may upload [0, lead->up_len) and launch the device fit, which touches
+// the device blob's first lead->dev_bytes, so that it runs while the host fills
+// the rest.  The level's state stays in per-thread scratch: the thread that
+// planned calls the fill, with the same labels, blob and info.
+struct tpe_label_in;
 struct tpe_pack_info;
-struct TpePackHook {
-  void (*fn)(void* ctx, const struct tpe_pack_info* early);
-  void* ctx;
+struct TpePackLead {
+  int32_t direct;       // the leading sections landed in the blob
+  int64_t up_len;       // the fit sections: blob bytes [0, up_len)
+  int64_t dev_bytes;    // the device bytes the fit touches (through the patch rows)
 };
-extern "C" void tpe_internal_pack_hook(TpePackHook h);
+extern "C" int tpe_internal_pack_plan(const struct tpe_label_in* labels, int32_t n_labels, int32_t n_cand,
+                                      uint64_t seed, int64_t cand_base, int64_t n_cand_global, int32_t precision,
+                                      void* blob, int64_t blob_cap, struct tpe_pack_info* info, TpePackLead* lead);
+extern "C" int tpe_internal_pack_fill(struct tpe_pack_info* info);

@@ -479,42 +479,33 @@ static int suggest_tree(const tpe_tree_label* labels, int32_t n_labels, const in
     for (int32_t r = 0; r < n_recs; ++r) P += recs[(size_t)r].n_ids;
     res.resize((size_t)std::max<int64_t>(P, 1));
     ++path[1];
+    // this rank's status rc, then the worst status the ranks gathered
+    auto gathered = [](int rc, int32_t all_rc) -> int {
+      if (rc != TPE_OK) return rc;
+      if (all_rc == TPE_E_SPACE) return tpe_internal_fail(TPE_E_SPACE, "another rank needs a larger workspace");
+      if (all_rc != TPE_OK) return tpe_internal_fail(all_rc, "a level run failed on another rank");
+      return TPE_OK;
+    };
+    // the host exchange: every rank takes part, whatever its own status
+    auto exchange_host = [&](int rc) -> int {
+      if (rc != TPE_OK)
+        for (int64_t q = 0; q < P; ++q) res[(size_t)q] = tpe_result{0, 0, 0, 0, -1, -1};
+      int32_t all_rc = TPE_OK;
+      const int xrc = tpe_internal_exchange(ex, stream, rc, res.data(), P, &all_rc);
+      return xrc != TPE_OK ? xrc : gathered(rc, all_rc);
+    };
     if (exchange && ex->comm && device_combine()) {
       // RCCL: the level's runs reduced, gathered and combined on the device, one
-      // stream synchronise (falls back to the host exchange below when the level
+      // stream synchronise (falls back to the host exchange when the level
       // cannot take that path: then nothing was launched or exchanged)
       int32_t all_rc = TPE_OK, done = 0;
       const int rc = tpe_internal_level_run_ex(recs.data(), n_recs, n_cand, seed, cand_base, n_cand_global, TPE_PREC_F32,
                                                run_flags, ws, need, stream, res.data(), ex, P, &all_rc, &done);
-      if (done) {
-        if (rc != TPE_OK) return rc;
-        if (all_rc == TPE_E_SPACE) return tpe_internal_fail(TPE_E_SPACE, "another rank needs a larger workspace");
-        if (all_rc != TPE_OK) return tpe_internal_fail(all_rc, "a level run failed on another rank");
-        return TPE_OK;
-      }
-      if (rc != TPE_OK)
-        for (int64_t q = 0; q < P; ++q) res[(size_t)q] = tpe_result{0, 0, 0, 0, -1, -1};
-      int32_t all2 = TPE_OK;
-      const int xrc = tpe_internal_exchange(ex, stream, rc, res.data(), P, &all2);
-      if (xrc != TPE_OK) return xrc;
-      if (rc != TPE_OK) return rc;
-      if (all2 == TPE_E_SPACE) return tpe_internal_fail(TPE_E_SPACE, "another rank needs a larger workspace");
-      if (all2 != TPE_OK) return tpe_internal_fail(all2, "a level run failed on another rank");
-      return TPE_OK;
+      return done ? gathered(rc, all_rc) : exchange_host(rc);
     }
-    int rc = tpe_level_run(recs.data(), n_recs, n_cand, seed, cand_base, n_cand_global, TPE_PREC_F32, run_flags, ws,
-                           need, stream, res.data());
-    if (!exchange) return rc;
-    // every rank takes part in the exchange, whatever its own status
-    if (rc != TPE_OK)
-      for (int64_t q = 0; q < P; ++q) res[(size_t)q] = tpe_result{0, 0, 0, 0, -1, -1};
-    int32_t all_rc = TPE_OK;
-    const int xrc = tpe_internal_exchange(ex, stream, rc, res.data(), P, &all_rc);
-    if (xrc != TPE_OK) return xrc;
-    if (rc != TPE_OK) return rc;
-    if (all_rc == TPE_E_SPACE) return tpe_internal_fail(TPE_E_SPACE, "another rank needs a larger workspace");
-    if (all_rc != TPE_OK) return tpe_internal_fail(all_rc, "a level run failed on another rank");
-    return TPE_OK;
+    const int rc = tpe_level_run(recs.data(), n_recs, n_cand, seed, cand_base, n_cand_global, TPE_PREC_F32, run_flags,
+                                 ws, need, stream, res.data());
+    return exchange ? exchange_host(rc) : rc;
   };
 
   // speculative fusion (hyperopt_amd.tpe._choices_fused): every level in one
