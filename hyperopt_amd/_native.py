@@ -11,7 +11,7 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('TPE_HIP_LIB') or os.path.join(HERE, 'libtpe_hip.so')   # override: A/B builds
-ABI_VERSION = 22
+ABI_VERSION = 23
 FIT_DELTA_MAX = 16             # TPE_FIT_DELTA_MAX: new observations read as a delta (no merge)
 BEST_PER_TILE = 8         # TPE_BEST_PER_TILE: tile_best slots per candidate tile
 
@@ -64,6 +64,14 @@ assert FIT_JOB_DTYPE.itemsize == 152
 RESULT_DTYPE = np.dtype([('score', '<f8'), ('l', '<f8'), ('g', '<f8'), ('value', '<f8'),
                          ('idx', '<i8'), ('global_idx', '<i8')])
 assert RESULT_DTYPE.itemsize == 48
+# candidate report (include/tpe_hip.h "Candidate report")
+REPORT_CHUNK = 4096            # TPE_REPORT_CHUNK: candidates per pass-1 workgroup
+REPORT_MAX_K = 64              # TPE_REPORT_MAX_K
+TOP_ENTRY_DTYPE = np.dtype([('value', '<f8'), ('l', '<f8'), ('g', '<f8'), ('global_idx', '<i8')])
+assert TOP_ENTRY_DTYPE.itemsize == 32
+SCORE_STATS_DTYPE = np.dtype([('n_finite', '<i8'), ('n_nan', '<i8'), ('n_posinf', '<i8'), ('n_neginf', '<i8'),
+                              ('mean', '<f8'), ('m2', '<f8'), ('min', '<f8'), ('max', '<f8')])
+assert SCORE_STATS_DTYPE.itemsize == 64
 
 
 class Batch(ctypes.Structure):
@@ -243,7 +251,8 @@ EXPORTS = ('tpe_abi_version', 'tpe_last_error', 'tpe_device_count', 'tpe_tile_si
            'tpe_replay_mixture', 'tpe_replay_categorical', 'tpe_level_profile', 'tpe_level_profile_read',
            'tpe_suggest_tree', 'tpe_comm_unique_id', 'tpe_comm_init', 'tpe_comm_destroy', 'tpe_combine_results',
            'tpe_host_threads', 'tpe_host_phases', 'tpe_exchange_allgather', 'tpe_debug_fast_lg',
-           'tpe_collectives_issued', 'tpe_scatter_f64', 'tpe_move_ranges')
+           'tpe_collectives_issued', 'tpe_scatter_f64', 'tpe_move_ranges', 'tpe_report_scratch_bytes', 'tpe_report',
+           'tpe_report_profile')
 
 # host phases of tpe_suggest_tree (tpe_host_phases order)
 PHASES = ('prefit', 'pack', 'launched', 'synced', 'level', 'return', 'recs')
@@ -348,6 +357,12 @@ def load(path=LIB_PATH):
     lib.tpe_scatter_f64.restype = ctypes.c_int
     lib.tpe_move_ranges.argtypes = [P, ctypes.c_int32, ctypes.c_int32, P, P, P]
     lib.tpe_move_ranges.restype = ctypes.c_int
+    lib.tpe_report_scratch_bytes.argtypes = [I64, I32, ctypes.POINTER(ctypes.c_uint64)]
+    lib.tpe_report_scratch_bytes.restype = ctypes.c_int
+    lib.tpe_report.argtypes = [ctypes.POINTER(Batch), I32, P, P, P, P, ctypes.c_uint64, P]
+    lib.tpe_report.restype = ctypes.c_int
+    lib.tpe_report_profile.argtypes = [I32, P]
+    lib.tpe_report_profile.restype = ctypes.c_int
     lib.tpe_level_profile.argtypes = [ctypes.c_int32]
     lib.tpe_level_profile.restype = ctypes.c_int
     lib.tpe_level_profile_read.argtypes = [ctypes.POINTER(StageProf), ctypes.c_int32]
@@ -362,6 +377,15 @@ def check(rc, lib, what):
     if rc != 0:
         msg = lib.tpe_last_error().decode(errors='replace')
         raise RuntimeError('%s failed (%d): %s' % (what, rc, msg))
+
+
+def report_chunks(n_problems, total_cand):
+    """Chunk slots of a batch's candidate report (include/tpe_hip.h "Chunk
+    slots"): n_problems * ceil(ceil(total_cand / n_problems) / TPE_REPORT_CHUNK)."""
+    if n_problems <= 0 or total_cand <= 0:
+        return 0
+    per = -(-int(total_cand) // int(n_problems))
+    return int(n_problems) * (-(-per // REPORT_CHUNK))
 
 
 def tile_size():

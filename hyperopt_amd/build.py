@@ -8,6 +8,7 @@ SRC = os.path.join(HERE, 'csrc', 'tpe_kernels.hip')
 HOST_SRC = os.path.join(HERE, 'csrc', 'tpe_host.cpp')
 SUGGEST_SRC = os.path.join(HERE, 'csrc', 'tpe_suggest.cpp')
 POOL_SRC = os.path.join(HERE, 'csrc', 'tpe_pool.cpp')
+REPORT_SRC = os.path.join(HERE, 'csrc', 'tpe_report.hip')
 OUT = os.path.join(HERE, 'libtpe_hip.so')
 ARCH = os.environ.get('TPE_OFFLOAD_ARCH', 'gfx950')
 # host ISA baseline of the runtime (any x86-64 host); the vectorised pack loops
@@ -20,7 +21,7 @@ def build(force=False, verbose=False, out=OUT, defines=()):
     semantics), link both into hyperopt_amd/libtpe_hip.so (or `out`, with extra
     -D `defines` on the kernels: A/B variants for tools/)."""
     OUT = out
-    deps = [SRC, HOST_SRC, SUGGEST_SRC, POOL_SRC, os.path.join(HERE, 'csrc', 'tpe_pool.h'), os.path.join(HERE, 'csrc', 'sort_net.h'),
+    deps = [SRC, HOST_SRC, SUGGEST_SRC, POOL_SRC, REPORT_SRC, os.path.join(HERE, 'csrc', 'tpe_pool.h'), os.path.join(HERE, 'csrc', 'sort_net.h'),
             os.path.join(HERE, '..', 'include', 'tpe_hip.h'), os.path.abspath(__file__)]
     if out == os.path.join(HERE, 'libtpe_hip.so'):
         build_hostaddr(force, verbose)
@@ -34,6 +35,7 @@ def build(force=False, verbose=False, out=OUT, defines=()):
     suggest_o = os.path.join(HERE, 'csrc', 'tpe_suggest.o')
     pool_o = os.path.join(HERE, 'csrc', 'tpe_pool.o')
     dev_o = os.path.join(HERE, 'csrc', 'tpe_kernels.o' if not defines else tag + '.o')
+    report_o = os.path.join(HERE, 'csrc', 'tpe_report.o')
     hdr = [os.path.join(HERE, '..', 'include', 'tpe_hip.h'), os.path.join(HERE, 'csrc', 'tpe_pool.h'),
            os.path.join(HERE, 'csrc', 'sort_net.h')]
     host_flags = [gxx, '-O3', '-march=' + HOST_MARCH, '-std=c++17', '-fPIC', '-Wall']
@@ -47,11 +49,13 @@ def build(force=False, verbose=False, out=OUT, defines=()):
         (dev_o, [SRC] + hdr, [hipcc, '-O3', '--offload-arch=' + ARCH, '-std=c++17', '-fPIC', '-Wall',
                               '-Wno-unused-command-line-argument'] + ['-D' + d for d in defines] +
          ['-c', SRC, '-o', dev_o]),
+        (report_o, [REPORT_SRC] + hdr, [hipcc, '-O3', '--offload-arch=' + ARCH, '-std=c++17', '-fPIC', '-Wall',
+                                        '-Wno-unused-command-line-argument', '-c', REPORT_SRC, '-o', report_o]),
     ]
     cmds = [c for o, srcs, c in objs
             if force or not os.path.exists(o) or any(os.path.getmtime(s) > os.path.getmtime(o) for s in srcs)]
     cmds.append([hipcc, '-shared', '-fPIC', '--offload-arch=' + ARCH, '-Wno-unused-command-line-argument', '-o', tmp,
-                 dev_o, host_o, suggest_o, pool_o, '-pthread'])
+                 dev_o, report_o, host_o, suggest_o, pool_o, '-pthread'])
     for cmd in cmds:
         if verbose:
             print(' '.join(cmd))

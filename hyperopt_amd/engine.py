@@ -781,19 +781,41 @@ class Engine(object):
                                                           1e-6 * float(r.kernel_ns)))
 
     # ---------------------------------------------------------------- run
-    def run(self, problems, n_cand, seed, cand_base=0, want_lg=False, return_cand=False, n_cand_global=None):
+    def run(self, problems, n_cand, seed, cand_base=0, want_lg=False, return_cand=False, n_cand_global=None,
+            report_k=0):
         """Sample, score and select every problem of one level.
 
         Returns a RESULT_DTYPE array with one row per (LevelProblem, id) in
-        order, plus (cand, l, g) float64 [P, n_cand] arrays when requested."""
+        order, plus (cand, l, g) float64 [P, n_cand] arrays when requested.
+
+        ``report_k`` > 0 (at most N.REPORT_MAX_K): the candidate report of the
+        level (tpe_report, include/tpe_hip.h "Candidate report") runs on the
+        same stream after the stages and (top, n_top, stats) is appended to
+        the return value, in problem order: top TOP_ENTRY_DTYPE [P, report_k]
+        — the report_k best distinct candidate values of each problem with
+        their l, g and global index, n_top [P] of them valid — and stats
+        SCORE_STATS_DTYPE [P].  The per-candidate arrays stay on the device
+        unless want_lg / return_cand ask for them.  A level with a pooled
+        label (a pruned label active for several ids) is refused."""
         n_cand = int(n_cand)
         if n_cand < 0 or n_cand >= 2 ** 31:
             raise ValueError('n_EI_candidates out of range: %r' % n_cand)
+        report_k = int(report_k)
+        if report_k < 0 or report_k > N.REPORT_MAX_K:
+            raise ValueError('report_k must be in [0, %d]: %r' % (N.REPORT_MAX_K, report_k))
         info = self._pack(problems, n_cand, seed, cand_base, n_cand_global)
         self._last_info = info
         P = int(info.n_problems)
+        if report_k and info.n_pooled:
+            # (tpe_report cannot see the problem flags: the check is here)
+            raise ValueError('candidate report of a level with a pooled label (one label, several ids, pruned '
+                             'above mixture): report its ids one per run')
         if P == 0:
-            return np.zeros(0, dtype=N.RESULT_DTYPE)
+            res = np.zeros(0, dtype=N.RESULT_DTYPE)
+            if not report_k:
+                return res
+            return (res, np.zeros((0, report_k), dtype=N.TOP_ENTRY_DTYPE), np.zeros(0, dtype=np.int32),
+                    np.zeros(0, dtype=N.SCORE_STATS_DTYPE))
         C_total = P * n_cand
         if C_total >= 2 ** 32:
             raise ValueError('more than 2^32 candidates in one level: shard the batch')
@@ -847,13 +869,13 @@ class Engine(object):
             d_cand[:C_total].copy_(torch.from_numpy(placed))
             d_coord[:C_total].copy_(torch.from_numpy(placed_t))
         d_l = d_g = None
-        if want_lg:
+        if want_lg or report_k:
             d_l = self._buf('l_out', C_total, torch.float64)
             d_g = self._buf('g_out', C_total, torch.float64)
         b = N.Batch()
         b.problems, b.n_problems = base + info.off_problems, P
         b.precision = N.PREC_F64 if self.precision == 'fp64' else N.PREC_F32
-        b.flags = self._flags() | (N.BATCH_WRITE_CAND if (return_cand or want_lg) else 0)
+        b.flags = self._flags() | (N.BATCH_WRITE_CAND if (return_cand or want_lg or report_k) else 0)
         b.sample = 0 if inject else 1
         b.sort_end_bit, b.key_bits = info.sort_end_bit, info.key_bits
         b.comp32, b.comp64 = base + info.off_comp32, base + info.off_comp64
@@ -905,9 +927,11 @@ class Engine(object):
         else:
             tb = dict(prob=prob.copy(), counts_w=[info.n_work_cont, info.n_work_qgauss, info.n_work_qlog], P=P)
             self._run_profiled(b, stream, tb, n_cand)
+        if report_k:
+            rep = self._report(b, P, C_total, report_k, stream)
         self._commit_orders(problems)
         res = d_res[:P * 6].cpu().numpy().view(N.RESULT_DTYPE).copy()
-        if not (want_lg or return_cand):
+        if not (want_lg or return_cand or report_k):
             return res
         out = [res]
         rows = (prob['cand_off'] // max(n_cand, 1)).astype(np.int64)    # sorted problems come first
@@ -919,7 +943,28 @@ class Engine(object):
         if want_lg:
             out.append(per_problem(d_l))
             out.append(per_problem(d_g))
+        if report_k:
+            # (the report's records are per problem row: the caller's order already)
+            d_top, d_ntop, d_stats = rep
+            out.append(d_top[:P * report_k * 4].cpu().numpy().view(N.TOP_ENTRY_DTYPE).reshape(P, report_k).copy())
+            out.append(d_ntop[:P].cpu().numpy().copy())
+            out.append(d_stats[:P * 8].cpu().numpy().view(N.SCORE_STATS_DTYPE).copy())
         return tuple(out)
+
+    def _report(self, b, P, C_total, k, stream):
+        """Enqueue tpe_report for the batch ``b`` just run; returns the device
+        tensors (top, n_top, stats)."""
+        nb = ctypes.c_uint64(0)
+        N.check(self.lib.tpe_report_scratch_bytes(N.report_chunks(P, C_total), k, ctypes.byref(nb)), self.lib,
+                'tpe_report_scratch_bytes')
+        d_scr = self._buf('report_scratch', (nb.value + 7) // 8, torch.float64)
+        d_top = self._buf('report_top', P * k * 4, torch.float64)
+        d_ntop = self._buf('report_n_top', P, torch.int32)
+        d_stats = self._buf('report_stats', P * 8, torch.float64)
+        N.check(self.lib.tpe_report(ctypes.byref(b), k, d_top.data_ptr(), d_ntop.data_ptr(), d_stats.data_ptr(),
+                                    d_scr.data_ptr(), d_scr.numel() * 8, ctypes.c_void_p(stream)), self.lib,
+                'tpe_report')
+        return d_top, d_ntop, d_stats
 
     def device_tables(self):
         """(problems, comp32) of the last ``run`` as the device holds them after

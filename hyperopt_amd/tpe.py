@@ -1011,6 +1011,140 @@ def _suggest_sharded(table, hist, new_ids, seed, prior_weight, n_EI_candidates, 
     return cc if columns else cc.dicts(table)
 
 
+# candidates of one engine run of a candidate report: 2^24 x (cand, l, g, coord,
+# sort key and value) is about 1 GB of per-candidate buffers — a bound on
+# memory, not a tuning knob
+REPORT_MAX_RUN_CANDIDATES = 1 << 24
+
+REPORT_TOP_DTYPE = np.dtype([('value', '<f8'), ('l', '<f8'), ('g', '<f8'), ('score', '<f8'), ('index', '<i8')])
+
+
+class CandidateReport(object):
+    """What the device scored for one new id, per hyperparameter label
+    (``candidate_report``):
+
+    labels  the reported labels, in table order
+    top     REPORT_TOP_DTYPE [n_labels, k]: the k best DISTINCT candidate
+            values of each label in np.argmax order of score = l - g (NaN
+            first, then descending, ties to the lower index), each with its
+            l = log-density under the below mixture, g = under the above
+            mixture and global candidate index; row j holds n_top[j] entries
+            (fewer than k when the pool has fewer distinct values), the rest
+            are value NaN / index -1.  A categorical label's value is its
+            category index (``values`` gives reference-typed values)
+    n_top   int [n_labels]
+    stats   _native.SCORE_STATS_DTYPE [n_labels]: counts of finite, NaN, +inf
+            and -inf scores; mean, m2 = sum (s - mean)^2, min and max of the
+            finite ones.  ``mean`` is the Monte-Carlo estimate of
+            E_l[log l(x) - log g(x)] over the pool (the candidates are draws
+            from l): a summary of how far apart the two fitted densities are,
+            nothing more — with the handful of observations the below set
+            holds it is as large for a label that does not matter as for one
+            that does
+    """
+    __slots__ = ('labels', 'top', 'n_top', 'stats', '_cat')
+
+    def __init__(self, labels, top, n_top, stats, categorical):
+        self.labels, self.top, self.n_top, self.stats = list(labels), top, n_top, stats
+        self._cat = list(categorical)
+
+    def __len__(self):
+        return len(self.labels)
+
+    def values(self, label):
+        """The label's ranked distinct values with the reference's value types
+        (np.int64 for categorical labels, np.float64 else)."""
+        j = self.labels.index(label)
+        v = self.top['value'][j, :int(self.n_top[j])]
+        return list(v.astype(np.int64)) if self._cat[j] else list(np.asarray(v, dtype=np.float64))
+
+    def dicts(self):
+        """{label: dict(top=[dict(value, l, g, score, index), ...], stats=dict(...))}."""
+        out = {}
+        for j, lab in enumerate(self.labels):
+            vals = self.values(lab)
+            rows = [dict(value=vals[i], l=float(e['l']), g=float(e['g']), score=float(e['score']),
+                         index=int(e['index'])) for i, e in enumerate(self.top[j, :len(vals)])]
+            st = self.stats[j]
+            out[lab] = dict(top=rows, stats={f: st[f].item() for f in self.stats.dtype.names})
+        return out
+
+
+def _report_check_k(k):
+    k = int(k)
+    if k < 1 or k > N.REPORT_MAX_K:
+        raise ValueError('k must be in [1, %d]: %r' % (N.REPORT_MAX_K, k))
+    return k
+
+
+def candidate_report_columns(table, hist, new_id, seed, k=8, labels=None, prior_weight=_default_prior_weight,
+                             n_EI_candidates=_default_n_EI_candidates, gamma=_default_gamma, precision='fp32',
+                             device=None):
+    """``candidate_report`` on a structure-of-arrays history (as
+    ``suggest_choices`` is to ``suggest``)."""
+    k = _report_check_k(k)
+    if len(hist) == 0:
+        raise ValueError('candidate_report needs a history: no completed trial to fit the posteriors from')
+    C = int(n_EI_candidates)
+    if C < 1 or C >= 2 ** 31:
+        raise ValueError('n_EI_candidates out of range: %r' % C)
+    if labels is None:
+        rows = list(table.rows)
+    else:
+        want = set(labels)
+        unknown = want - set(table.labels)
+        if unknown:
+            raise ValueError('not labels of the space: %r' % sorted(unknown))
+        rows = [r for r in table.rows if r.label in want]
+    engine = get_engine(device, precision)
+    fits = _Fits(table, hist, _history.split_below(hist, gamma), prior_weight, engine)
+    ids = np.array([int(new_id)], dtype=np.int64)
+    n = len(rows)
+    top = np.zeros((n, k), dtype=REPORT_TOP_DTYPE)
+    n_top = np.zeros(n, dtype=np.int64)
+    stats = np.zeros(n, dtype=N.SCORE_STATS_DTYPE)
+    per_run = max(1, REPORT_MAX_RUN_CANDIDATES // C)
+    for lo in range(0, n, per_run):
+        group = rows[lo:lo + per_run]
+        # one problem per label, scored as if active: its own Philox stream
+        # (seed, label, new id, global index) — the pool a suggest of this id
+        # with this seed and candidate count scores where the label is active
+        problems = [LevelProblem(fits.get(r), r.index, ids) for r in group]
+        _, t, nt, st = engine.run(problems, C, seed, report_k=k)
+        if (nt < 0).any():
+            raise RuntimeError('candidate report: a problem did not fit its chunk slots')
+        sl = slice(lo, lo + len(group))
+        for f in ('value', 'l', 'g'):
+            top[f][sl] = t[f]
+        top['index'][sl] = t['global_idx']
+        with np.errstate(invalid='ignore'):
+            top['score'][sl] = t['l'] - t['g']
+        n_top[sl], stats[sl] = nt, st
+    empty = np.arange(k)[None, :] >= n_top[:, None]
+    for f in ('value', 'l', 'g', 'score'):
+        top[f][empty] = np.nan
+    return CandidateReport([r.label for r in rows], top, n_top, stats, [r.categorical for r in rows])
+
+
+def candidate_report(new_id, domain, trials, seed, k=8, labels=None, prior_weight=_default_prior_weight,
+                     n_EI_candidates=_default_n_EI_candidates, gamma=_default_gamma, precision='fp32', device=None):
+    """The candidate pool behind a ``suggest([new_id], domain, trials, seed,
+    n_EI_candidates=...)``: for every label of the space (or the ``labels``
+    subset) the ``k`` best distinct candidate values with their l, g and score,
+    and statistics of the label's scores — a CandidateReport.
+
+    Every label is scored as if it were active, its posterior fitted from its
+    own observations; labels on a conditional branch the suggest does not take
+    are reported too.  The per-candidate arrays never leave the device: the
+    ranking and the statistics are device stages (tpe_report).  One new id per
+    call; ``k`` in [1, 64]."""
+    k = _report_check_k(k)
+    hist = _history.extract(domain, trials)
+    return candidate_report_columns(domain.table, hist, new_id, seed, k=k, labels=labels, prior_weight=prior_weight,
+                                    n_EI_candidates=n_EI_candidates, gamma=gamma, precision=precision,
+                                    device=device)
+
+
 def suggest_replay(new_ids, domain, trials, seed, **kw):
     """``suggest`` in exact-parity mode: the reference's RandomState candidate
     draws and float64 scoring (trajectories identical to the reference)."""

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define TPE_ABI_VERSION 22
+#define TPE_ABI_VERSION 23
 
 /* finalize slots per candidate tile: tile_best holds n_tiles * TPE_BEST_PER_TILE entries */
 #define TPE_BEST_PER_TILE 8
@@ -935,6 +935,72 @@ int tpe_debug_fast_lg(void* dev, int64_t n_records);
 /* the last profiled tpe_level_run: min(n, TPE_N_STAGES) records in stage
  * order; TPE_E_ARG if no run completed since the profiler was enabled */
 int tpe_level_profile_read(tpe_stage_prof* out, int32_t n);
+
+/* ------------------------------------------------------------------------
+ * Candidate report (tpe_report.hip; ABI 23): the k best DISTINCT candidate
+ * values of every problem of a batch and statistics of its scores, computed
+ * from the per-candidate buffers a tpe_run_batch with TPE_BATCH_WRITE_CAND,
+ * l_out and g_out leaves on the device (cand, l_out, g_out: all indexed
+ * cand_off + i by original candidate index).  Of a problem the stage reads
+ * n_cand, cand_off and cand_base only.
+ *
+ * Score s = l - g (float64).  Ranked order = np.argmax order (tpe_select): NaN
+ * scores first (equal to each other), then descending (+-inf ordinary values),
+ * ties to the lower candidate index.  Walking that order, a candidate is kept
+ * when no kept candidate has an equal (float64 ==) value; the first k kept are
+ * the problem's entries top[p * k ..], n_top[p] = min(k, distinct values) their
+ * count; the entries after them are {0, 0, 0, -1}.
+ * Statistics: the counts of finite, NaN, +inf and -inf scores; mean, m2 =
+ * sum (s - mean)^2, min and max over the finite ones (none: mean, min, max =
+ * NaN, m2 = 0).  mean is the Monte-Carlo estimate of E_l[log l - log g] over
+ * the candidate pool (the candidates are draws from l).
+ *
+ * Two passes.  A problem's candidates are cut into chunks of TPE_REPORT_CHUNK
+ * consecutive indices; pass 1 (one workgroup per problem and chunk) writes the
+ * chunk's distinct top-k and its (n, mean, m2, min, max) record to `scratch`,
+ * pass 2 (one workgroup per problem) merges the lists by the same rule — a
+ * chunk's distinct top-k holds every entry of the problem's that lies in the
+ * chunk — and the records by Chan's update in a fixed order.  No float atomics:
+ * two calls on the same buffers give the same bytes.
+ *
+ * Chunk slots: every problem gets S = ceil(ceil(total_cand / n_problems) /
+ * TPE_REPORT_CHUNK) of them — a packed level gives every problem the same
+ * n_cand and total_cand = n_problems * n_cand — so n_chunks_total =
+ * n_problems * S, and tpe_report_scratch_bytes(n_chunks_total, k) =
+ * n_chunks_total * (80 + 32 k).  A problem that does not fit (n_cand > S *
+ * TPE_REPORT_CHUNK, or [cand_off, cand_off + n_cand) outside [0, total_cand))
+ * is not read: n_top[p] = -1, empty statistics.
+ *
+ * tpe_report returns TPE_E_ARG before any launch (no device needed) for a null
+ * batch, k outside [1, TPE_REPORT_MAX_K], null cand / l_out / g_out,
+ * TPE_BATCH_WRITE_CAND not set, null outputs, or scratch smaller than
+ * tpe_report_scratch_bytes.  Pooled problems (TPE_F_POOLED) are not supported;
+ * the problem flags live in device memory, so the CALLER checks its host copy
+ * of them before the call (hyperopt_amd.engine.Engine.run does, and raises).
+ * ---------------------------------------------------------------------- */
+#define TPE_REPORT_CHUNK 4096
+#define TPE_REPORT_MAX_K 64
+typedef struct tpe_top_entry {
+  double value, l, g;
+  int64_t global_idx;    /* cand_base + candidate index */
+} tpe_top_entry;
+typedef struct tpe_score_stats {
+  int64_t n_finite, n_nan, n_posinf, n_neginf;
+  double mean, m2, min, max;
+} tpe_score_stats;
+
+int tpe_report_scratch_bytes(int64_t n_chunks_total, int32_t k, uint64_t* bytes);
+
+/* top: device [n_problems * k]; n_top: device [n_problems]; stats: device
+ * [n_problems]; enqueued on `stream` after the batch's stages */
+int tpe_report(const tpe_batch* batch, int32_t k, tpe_top_entry* top, int32_t* n_top, tpe_score_stats* stats,
+               void* scratch, uint64_t scratch_bytes, void* stream);
+
+/* Profiling only (tools/report_time.py).  While enabled, tpe_report launches its
+ * two kernels with start / stop events of their own; last_ms (if not NULL)
+ * first gets the device times {pass 1, pass 2} in ms of the last such call —
+ * it WAITS for that call's kernels — then the setting changes.  Process-wide. */
+int tpe_report_profile(int32_t enable, double* last_ms);
 
 /* ------------------------------------------------------------------------
  * Host phase clock of tpe_suggest_tree (tools/native_split.py).  While
