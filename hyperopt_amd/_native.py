@@ -11,7 +11,7 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('TPE_HIP_LIB') or os.path.join(HERE, 'libtpe_hip.so')   # override: A/B builds
-ABI_VERSION = 23
+ABI_VERSION = 24
 FIT_DELTA_MAX = 16             # TPE_FIT_DELTA_MAX: new observations read as a delta (no merge)
 BEST_PER_TILE = 8         # TPE_BEST_PER_TILE: tile_best slots per candidate tile
 
@@ -72,6 +72,13 @@ assert TOP_ENTRY_DTYPE.itemsize == 32
 SCORE_STATS_DTYPE = np.dtype([('n_finite', '<i8'), ('n_nan', '<i8'), ('n_posinf', '<i8'), ('n_neginf', '<i8'),
                               ('mean', '<f8'), ('m2', '<f8'), ('min', '<f8'), ('max', '<f8')])
 assert SCORE_STATS_DTYPE.itemsize == 64
+# joint TPE stage (include/tpe_hip.h "Joint (multivariate) TPE stage")
+JOINT_MAX_DIMS = 16            # TPE_JOINT_MAX_DIMS
+JOINT_CHUNK = 1024             # TPE_JOINT_CHUNK: candidates per workgroup
+JOINT_STREAM = 0xFFFFFFFF      # TPE_JOINT_STREAM: the Philox counter word no label index equals
+JOINT_INJECT = 1               # TPE_JOINT_INJECT
+JOINT_RECORD_DTYPE = np.dtype([('global_idx', '<i8'), ('l', '<f8'), ('g', '<f8'), ('z', '<f8', (JOINT_MAX_DIMS,))])
+assert JOINT_RECORD_DTYPE.itemsize == 152
 
 
 class Batch(ctypes.Structure):
@@ -107,6 +114,21 @@ class Batch(ctypes.Structure):
         ('samp_tiles', ctypes.c_void_p), ('n_samp_tiles', ctypes.c_int32), ('n_samp_eager', ctypes.c_int32),
         ('tab_tiles', ctypes.c_void_p), ('n_tab_tiles', ctypes.c_int32), ('early_select', ctypes.c_int32),
         ('run_best', ctypes.c_void_p), ('n_late', ctypes.c_int32), ('tiles_per_problem', ctypes.c_int32),
+    ]
+
+
+class JointArgs(ctypes.Structure):
+    """tpe_joint_args: one tpe_joint_run."""
+    _fields_ = [
+        ('n_dims', ctypes.c_int32), ('n_cand', ctypes.c_int32), ('n_ids', ctypes.c_int32), ('flags', ctypes.c_int32),
+        ('k_below', ctypes.c_int32), ('k_above', ctypes.c_int32), ('stream_word', ctypes.c_uint32),
+        ('reserved', ctypes.c_int32), ('seed', ctypes.c_uint64),
+        ('below_mu', ctypes.c_void_p), ('below_a', ctypes.c_void_p), ('below_c', ctypes.c_void_p),
+        ('above_mu', ctypes.c_void_p), ('above_a', ctypes.c_void_p), ('above_c', ctypes.c_void_p),
+        ('below_base', ctypes.c_double), ('above_base', ctypes.c_double),
+        ('samp_cum', ctypes.c_void_p), ('samp', ctypes.c_void_p), ('ids', ctypes.c_void_p),
+        ('inject', ctypes.c_void_p),
+        ('low', ctypes.c_double * JOINT_MAX_DIMS), ('high', ctypes.c_double * JOINT_MAX_DIMS),
     ]
 
 
@@ -252,7 +274,7 @@ EXPORTS = ('tpe_abi_version', 'tpe_last_error', 'tpe_device_count', 'tpe_tile_si
            'tpe_suggest_tree', 'tpe_comm_unique_id', 'tpe_comm_init', 'tpe_comm_destroy', 'tpe_combine_results',
            'tpe_host_threads', 'tpe_host_phases', 'tpe_exchange_allgather', 'tpe_debug_fast_lg',
            'tpe_collectives_issued', 'tpe_scatter_f64', 'tpe_move_ranges', 'tpe_report_scratch_bytes', 'tpe_report',
-           'tpe_report_profile')
+           'tpe_report_profile', 'tpe_joint_scratch_bytes', 'tpe_joint_run', 'tpe_joint_profile')
 
 # host phases of tpe_suggest_tree (tpe_host_phases order)
 PHASES = ('prefit', 'pack', 'launched', 'synced', 'level', 'return', 'recs')
@@ -363,6 +385,12 @@ def load(path=LIB_PATH):
     lib.tpe_report.restype = ctypes.c_int
     lib.tpe_report_profile.argtypes = [I32, P]
     lib.tpe_report_profile.restype = ctypes.c_int
+    lib.tpe_joint_scratch_bytes.argtypes = [I32, I32, ctypes.POINTER(ctypes.c_uint64)]
+    lib.tpe_joint_scratch_bytes.restype = ctypes.c_int
+    lib.tpe_joint_run.argtypes = [ctypes.POINTER(JointArgs), P, P, P, P, P, ctypes.c_uint64, P]
+    lib.tpe_joint_run.restype = ctypes.c_int
+    lib.tpe_joint_profile.argtypes = [I32, P]
+    lib.tpe_joint_profile.restype = ctypes.c_int
     lib.tpe_level_profile.argtypes = [ctypes.c_int32]
     lib.tpe_level_profile.restype = ctypes.c_int
     lib.tpe_level_profile_read.argtypes = [ctypes.POINTER(StageProf), ctypes.c_int32]

@@ -9,6 +9,8 @@ HOST_SRC = os.path.join(HERE, 'csrc', 'tpe_host.cpp')
 SUGGEST_SRC = os.path.join(HERE, 'csrc', 'tpe_suggest.cpp')
 POOL_SRC = os.path.join(HERE, 'csrc', 'tpe_pool.cpp')
 REPORT_SRC = os.path.join(HERE, 'csrc', 'tpe_report.hip')
+JOINT_SRC = os.path.join(HERE, 'csrc', 'tpe_joint.hip')
+RNG_HDR = os.path.join(HERE, 'csrc', 'tpe_device_rng.h')
 OUT = os.path.join(HERE, 'libtpe_hip.so')
 ARCH = os.environ.get('TPE_OFFLOAD_ARCH', 'gfx950')
 # host ISA baseline of the runtime (any x86-64 host); the vectorised pack loops
@@ -21,7 +23,7 @@ def build(force=False, verbose=False, out=OUT, defines=()):
     semantics), link both into hyperopt_amd/libtpe_hip.so (or `out`, with extra
     -D `defines` on the kernels: A/B variants for tools/)."""
     OUT = out
-    deps = [SRC, HOST_SRC, SUGGEST_SRC, POOL_SRC, REPORT_SRC, os.path.join(HERE, 'csrc', 'tpe_pool.h'), os.path.join(HERE, 'csrc', 'sort_net.h'),
+    deps = [SRC, HOST_SRC, SUGGEST_SRC, POOL_SRC, REPORT_SRC, JOINT_SRC, RNG_HDR, os.path.join(HERE, 'csrc', 'tpe_pool.h'), os.path.join(HERE, 'csrc', 'sort_net.h'),
             os.path.join(HERE, '..', 'include', 'tpe_hip.h'), os.path.abspath(__file__)]
     if out == os.path.join(HERE, 'libtpe_hip.so'):
         build_hostaddr(force, verbose)
@@ -36,6 +38,7 @@ def build(force=False, verbose=False, out=OUT, defines=()):
     pool_o = os.path.join(HERE, 'csrc', 'tpe_pool.o')
     dev_o = os.path.join(HERE, 'csrc', 'tpe_kernels.o' if not defines else tag + '.o')
     report_o = os.path.join(HERE, 'csrc', 'tpe_report.o')
+    joint_o = os.path.join(HERE, 'csrc', 'tpe_joint.o')
     hdr = [os.path.join(HERE, '..', 'include', 'tpe_hip.h'), os.path.join(HERE, 'csrc', 'tpe_pool.h'),
            os.path.join(HERE, 'csrc', 'sort_net.h')]
     host_flags = [gxx, '-O3', '-march=' + HOST_MARCH, '-std=c++17', '-fPIC', '-Wall']
@@ -46,16 +49,18 @@ def build(force=False, verbose=False, out=OUT, defines=()):
         (host_o, [HOST_SRC] + hdr, host_flags + numpy_fp + ['-c', HOST_SRC, '-o', host_o]),
         (suggest_o, [SUGGEST_SRC] + hdr, host_flags + numpy_fp + ['-c', SUGGEST_SRC, '-o', suggest_o]),
         (pool_o, [POOL_SRC] + hdr, host_flags + ['-pthread', '-c', POOL_SRC, '-o', pool_o]),
-        (dev_o, [SRC] + hdr, [hipcc, '-O3', '--offload-arch=' + ARCH, '-std=c++17', '-fPIC', '-Wall',
+        (dev_o, [SRC, RNG_HDR] + hdr, [hipcc, '-O3', '--offload-arch=' + ARCH, '-std=c++17', '-fPIC', '-Wall',
                               '-Wno-unused-command-line-argument'] + ['-D' + d for d in defines] +
          ['-c', SRC, '-o', dev_o]),
         (report_o, [REPORT_SRC] + hdr, [hipcc, '-O3', '--offload-arch=' + ARCH, '-std=c++17', '-fPIC', '-Wall',
                                         '-Wno-unused-command-line-argument', '-c', REPORT_SRC, '-o', report_o]),
+        (joint_o, [JOINT_SRC, RNG_HDR] + hdr, [hipcc, '-O3', '--offload-arch=' + ARCH, '-std=c++17', '-fPIC', '-Wall',
+                                               '-Wno-unused-command-line-argument', '-c', JOINT_SRC, '-o', joint_o]),
     ]
     cmds = [c for o, srcs, c in objs
             if force or not os.path.exists(o) or any(os.path.getmtime(s) > os.path.getmtime(o) for s in srcs)]
     cmds.append([hipcc, '-shared', '-fPIC', '--offload-arch=' + ARCH, '-Wno-unused-command-line-argument', '-o', tmp,
-                 dev_o, report_o, host_o, suggest_o, pool_o, '-pthread'])
+                 dev_o, report_o, joint_o, host_o, suggest_o, pool_o, '-pthread'])
     for cmd in cmds:
         if verbose:
             print(' '.join(cmd))

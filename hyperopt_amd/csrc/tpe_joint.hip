@@ -1,0 +1,354 @@
+// MI355X (gfx950) joint TPE stage: whole-vector candidates scored under two
+// product-kernel mixtures (include/tpe_hip.h, "Joint (multivariate) TPE
+// stage").  Nothing on the univariate suggest path runs through this file.
+//
+// k_joint_chunk  one 256-thread workgroup per (new id, chunk of 1024
+//                candidates).  A lane holds kR = 4 candidates' z[D] in
+//                registers (candidate first + r * 256 + t: coalesced stores),
+//                drawn from the below mixture (one component per candidate,
+//                then D truncated-normal inversions) or loaded (inject).  Both
+//                sides' rows stream through LDS in tiles of kTileK components;
+//                every lane reads the same row, so an LDS read is a broadcast
+//                that serves 64 * kR evaluations.  Per (candidate, component):
+//                3 D VALU operations (subtract, scale, fma) and 7 for the
+//                running-maximum sum of 2^term (one v_exp_f32).
+// k_joint_merge  one wave per new id: the chunk winners in index order.
+// Every reduction has a fixed shape and there are no atomics: the output bytes
+// are a function of the input bytes.
+#include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "../../include/tpe_hip.h"
+#include "tpe_device_rng.h"
+
+extern "C" int tpe_internal_fail(int code, const char* what);   // tpe_kernels.hip (hidden)
+
+namespace {
+
+constexpr int kThreads = 256;                       // 4 waves of 64
+constexpr int kR = TPE_JOINT_CHUNK / kThreads;      // candidates per lane
+constexpr int kTileK = 128;                         // components per LDS tile
+constexpr double kLn2 = 0.69314718055994530942;
+static_assert(kR * kThreads == TPE_JOINT_CHUNK, "chunk = threads x candidates per lane");
+static_assert(sizeof(tpe_joint_record) == 24 + 8 * TPE_JOINT_MAX_DIMS, "layout");
+
+// the kernels' view of tpe_joint_args (f32 bounds made on the host)
+struct JointK {
+  int D, C, n_chunks, inject;
+  int kb, ka;
+  uint32_t key0, key1, stream_word;
+  const float *bmu, *ba, *bc, *amu, *aa, *ac;
+  double bbase, abase;
+  const double* cum;
+  const float* samp;
+  const int64_t* ids;
+  const float* inj;
+  float lo[TPE_JOINT_MAX_DIMS], hi[TPE_JOINT_MAX_DIMS];
+  float* cand;
+  double *l_out, *g_out;
+  tpe_joint_record* chunk_rec;      // scratch [n_ids * n_chunks]
+};
+
+// np.argmax order of a score as one unsigned key, larger = better, 0 = no
+// candidate: every NaN the largest key, then the f64 bits made monotone (-0 as
+// +0); -inf maps above 0  (as tpe_report.hip)
+__device__ __forceinline__ uint64_t score_key(double s) {
+  if (s != s) return ~0ull;
+  const uint64_t b = (uint64_t)__double_as_longlong(s + 0.0);
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+struct Pick {
+  uint64_t key;
+  int64_t idx;
+};
+__device__ __forceinline__ bool beats(const Pick& a, const Pick& b) {
+  return a.key > b.key || (a.key == b.key && a.key != 0 && a.idx < b.idx);
+}
+__device__ __forceinline__ Pick wave_best(Pick p) {
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) {
+    Pick o;
+    o.key = (uint64_t)__shfl_xor((unsigned long long)p.key, m, 64);
+    o.idx = (int64_t)__shfl_xor((long long)p.idx, m, 64);
+    if (beats(o, p)) p = o;
+  }
+  return p;
+}
+
+// log2 of one side's mixture at the lane's kR candidates, rows through LDS.
+// s accumulates 2^(term - m) with m the running maximum of the terms.
+template <int DP>
+__device__ __forceinline__ void score_side(const float* __restrict__ mu, const float* __restrict__ a,
+                                           const float* __restrict__ c, int K, int D, const float (&z)[kR][DP],
+                                           float* __restrict__ rows, float* __restrict__ cl, double (&out)[kR]) {
+  float m[kR], s[kR];
+#pragma unroll
+  for (int r = 0; r < kR; ++r) { m[r] = -3.0e38f; s[r] = 0.f; }
+  for (int k0 = 0; k0 < K; k0 += kTileK) {
+    const int nk = min(kTileK, K - k0);
+    __syncthreads();                       // the previous tile (or side) is read
+    for (int e = threadIdx.x; e < nk * DP; e += kThreads) {
+      const int kk = e / DP, d = e % DP;
+      const bool in = d < D;               // padded dimensions: a = 0 adds nothing
+      const int64_t src = (int64_t)(k0 + kk) * D + d;
+      rows[kk * 2 * DP + d] = in ? mu[src] : 0.f;
+      rows[kk * 2 * DP + DP + d] = in ? a[src] : 0.f;
+    }
+    for (int e = threadIdx.x; e < nk; e += kThreads) cl[e] = c[k0 + e];
+    __syncthreads();
+    for (int kk = 0; kk < nk; ++kk) {
+      const float* row = rows + kk * 2 * DP;
+      float rm[DP], ra[DP];
+#pragma unroll
+      for (int d = 0; d < DP; ++d) { rm[d] = row[d]; ra[d] = row[DP + d]; }
+      const float ck = cl[kk];
+#pragma unroll
+      for (int r = 0; r < kR; ++r) {
+        float acc = 0.f;
+#pragma unroll
+        for (int d = 0; d < DP; ++d) {
+          const float u = (z[r][d] - rm[d]) * ra[d];
+          acc = __builtin_fmaf(u, u, acc);
+        }
+        const float t = ck - acc;
+        const float dl = t - m[r];
+        const float e2 = __builtin_amdgcn_exp2f(-__builtin_fabsf(dl));
+        s[r] = dl > 0.f ? __builtin_fmaf(s[r], e2, 1.f) : s[r] + e2;
+        m[r] = fmaxf(m[r], t);
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < kR; ++r) out[r] = (double)m[r] + log2((double)s[r]);
+}
+
+template <int DP>
+__global__ __launch_bounds__(kThreads) void k_joint_chunk(const JointK p) {
+  __shared__ __attribute__((aligned(16))) float rows[kTileK * 2 * DP];
+  __shared__ float cl[kTileK];
+  __shared__ Pick slot[kThreads / 64];
+  const int t = threadIdx.x, D = p.D;
+  const int id = blockIdx.x / p.n_chunks, chunk = blockIdx.x % p.n_chunks;
+  const int first = chunk * TPE_JOINT_CHUNK;
+
+  float z[kR][DP];
+#pragma unroll
+  for (int r = 0; r < kR; ++r) {
+#pragma unroll
+    for (int d = 0; d < DP; ++d) z[r][d] = 0.f;
+    const int i = first + r * kThreads + t;
+    if (i >= p.C) continue;
+    if (p.inject) {
+#pragma unroll
+      for (int d = 0; d < DP; ++d)
+        if (d < D) z[r][d] = p.inj[(int64_t)i * D + d];
+      continue;
+    }
+    const uint32_t c3 = (uint32_t)p.ids[id];
+    U4 w = philox4x32_10((uint32_t)i, 0u, p.stream_word, c3, p.key0, p.key1);
+    const double us = u01w(w.x);
+    int lo = 0, hi = p.kb - 1;             // first k with us < cum[k]
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (us < p.cum[mid]) hi = mid; else lo = mid + 1; }
+    const float* srow = p.samp + (int64_t)lo * D * 5;
+#pragma unroll
+    for (int d = 0; d < DP; ++d) {
+      if (d >= D) continue;
+      const int wi = d + 1;
+      if ((wi & 3) == 0) w = philox4x32_10((uint32_t)i, (uint32_t)(wi >> 2), p.stream_word, c3, p.key0, p.key1);
+      const uint32_t word = (wi & 3) == 0 ? w.x : (wi & 3) == 1 ? w.y : (wi & 3) == 2 ? w.z : w.w;
+      const float* sr = srow + d * 5;
+      const float pr = sr[2] + u01f(word) * (sr[3] - sr[2]);
+      float zz = ndtri_f32(pr);
+      if (sr[4] != 0.f) zz = -zz;
+      float x = sr[0] + sr[1] * zz;
+      if (!(x == x)) x = sr[0];
+      z[r][d] = fminf(fmaxf(x, p.lo[d]), p.hi[d]);      // low <= z < high
+    }
+  }
+
+  double l2[kR], g2[kR];
+  score_side<DP>(p.bmu, p.ba, p.bc, p.kb, D, z, rows, cl, l2);
+  score_side<DP>(p.amu, p.aa, p.ac, p.ka, D, z, rows, cl, g2);
+
+  Pick best{0, 0};
+  double lv[kR], gv[kR];
+#pragma unroll
+  for (int r = 0; r < kR; ++r) {
+    const int i = first + r * kThreads + t;
+    lv[r] = l2[r] * kLn2 + p.bbase;
+    gv[r] = g2[r] * kLn2 + p.abase;
+    if (i >= p.C) continue;
+    const int64_t o = (int64_t)id * p.C + i;
+    if (p.l_out) p.l_out[o] = lv[r];
+    if (p.g_out) p.g_out[o] = gv[r];
+    if (p.cand)
+#pragma unroll
+      for (int d = 0; d < DP; ++d)
+        if (d < D) p.cand[o * D + d] = z[r][d];
+    const uint64_t key = score_key(lv[r] - gv[r]);
+    if (key > best.key) best = Pick{key, (int64_t)i};   // ascending index: strict > keeps the first of a tie
+  }
+  Pick w = wave_best(best);
+  if ((t & 63) == 0) slot[t >> 6] = w;
+  __syncthreads();
+  w = slot[0];
+#pragma unroll
+  for (int q = 1; q < kThreads / 64; ++q)
+    if (beats(slot[q], w)) w = slot[q];
+
+  tpe_joint_record* rec = p.chunk_rec + blockIdx.x;
+  if (w.key == 0) {
+    if (t == 0) rec->global_idx = -1;
+    return;
+  }
+  const int off = (int)(w.idx - first);
+  if (t != off % kThreads) return;
+  const int wr = off / kThreads;
+#pragma unroll
+  for (int r = 0; r < kR; ++r) {
+    if (r != wr) continue;
+    rec->global_idx = w.idx;
+    rec->l = lv[r];
+    rec->g = gv[r];
+#pragma unroll
+    for (int d = 0; d < TPE_JOINT_MAX_DIMS; ++d) rec->z[d] = d < DP ? (double)z[r][d < DP ? d : 0] : 0.0;
+  }
+}
+
+__global__ __launch_bounds__(64) void k_joint_merge(const tpe_joint_record* __restrict__ chunk_rec, int n_chunks,
+                                                    tpe_joint_record* __restrict__ records) {
+  const tpe_joint_record* rec = chunk_rec + (int64_t)blockIdx.x * n_chunks;
+  Pick best{0, 0};
+  for (int c = threadIdx.x; c < n_chunks; c += 64) {
+    if (rec[c].global_idx < 0) continue;
+    const Pick x{score_key(rec[c].l - rec[c].g), (int64_t)c};
+    if (beats(x, best)) best = x;            // (chunk order = candidate index order)
+  }
+  const Pick w = wave_best(best);
+  if (threadIdx.x != 0) return;
+  tpe_joint_record* out = records + blockIdx.x;
+  if (w.key == 0) {
+    out->global_idx = -1;
+    out->l = out->g = 0.0;
+    for (int d = 0; d < TPE_JOINT_MAX_DIMS; ++d) out->z[d] = 0.0;
+  } else {
+    *out = rec[w.idx];
+  }
+}
+
+int64_t n_chunks_of(int32_t n_cand) { return ((int64_t)n_cand + TPE_JOINT_CHUNK - 1) / TPE_JOINT_CHUNK; }
+
+// tpe_joint_profile: start / stop events of the two launches (profiling only)
+struct {
+  int on, valid;
+  hipEvent_t ev[4];
+} g_prof = {0, 0, {nullptr, nullptr, nullptr, nullptr}};
+
+template <int DP>
+void launch_chunk(const JointK& k, unsigned blocks, hipStream_t stream, bool timed) {
+  if (timed)
+    hipExtLaunchKernelGGL(k_joint_chunk<DP>, dim3(blocks), dim3(kThreads), 0u, stream, g_prof.ev[0], g_prof.ev[1], 0u,
+                          k);
+  else
+    hipLaunchKernelGGL(k_joint_chunk<DP>, dim3(blocks), dim3(kThreads), 0, stream, k);
+}
+
+}  // namespace
+
+extern "C" {
+
+int tpe_joint_profile(int32_t enable, double* last_ms) {
+  if (last_ms) {
+    if (!g_prof.valid) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_profile: no profiled tpe_joint_run to read");
+    for (int i = 0; i < 2; ++i) {
+      float ms = 0.f;
+      hipError_t e = hipEventSynchronize(g_prof.ev[2 * i + 1]);
+      if (e == hipSuccess) e = hipEventElapsedTime(&ms, g_prof.ev[2 * i], g_prof.ev[2 * i + 1]);
+      if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
+      last_ms[i] = (double)ms;
+    }
+  }
+  if (enable && !g_prof.ev[0])
+    for (int i = 0; i < 4; ++i) {
+      const hipError_t e = hipEventCreate(&g_prof.ev[i]);
+      if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
+    }
+  g_prof.on = enable ? 1 : 0;
+  g_prof.valid = 0;
+  return TPE_OK;
+}
+
+int tpe_joint_scratch_bytes(int32_t n_ids, int32_t n_cand, uint64_t* bytes) {
+  if (!bytes || n_ids < 1 || n_cand < 1) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_scratch_bytes: bad arguments");
+  *bytes = (uint64_t)n_ids * (uint64_t)n_chunks_of(n_cand) * sizeof(tpe_joint_record);
+  return TPE_OK;
+}
+
+int tpe_joint_run(const tpe_joint_args* a, tpe_joint_record* records, float* cand, double* l_out, double* g_out,
+                  void* scratch, uint64_t scratch_bytes, void* stream) {
+  if (!a) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run: null args");
+  if (a->n_dims < 1 || a->n_dims > TPE_JOINT_MAX_DIMS)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run: n_dims outside [1, TPE_JOINT_MAX_DIMS]");
+  if (a->n_cand < 1) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run: n_cand < 1");
+  if (a->n_ids < 1) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run: n_ids < 1");
+  if (a->k_below < 1 || a->k_above < 1) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run: k_below < 1 or k_above < 1");
+  if (!a->below_mu || !a->below_a || !a->below_c || !a->above_mu || !a->above_a || !a->above_c)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run: null density rows");
+  const bool inject = (a->flags & TPE_JOINT_INJECT) != 0;
+  if (inject && !a->inject) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run: TPE_JOINT_INJECT without candidates");
+  if (!inject && (!a->samp_cum || !a->samp)) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run: null sampler rows");
+  if (!a->ids || !records) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run: null ids / records");
+  const int64_t n_chunks = n_chunks_of(a->n_cand), blocks = n_chunks * a->n_ids;
+  if (blocks > INT32_MAX) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run: too many candidates");
+  const uint64_t need = (uint64_t)blocks * sizeof(tpe_joint_record);
+  if (!scratch || scratch_bytes < need) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run: scratch too small");
+
+  JointK k;
+  k.D = a->n_dims; k.C = a->n_cand; k.n_chunks = (int)n_chunks; k.inject = inject ? 1 : 0;
+  k.kb = a->k_below; k.ka = a->k_above;
+  k.key0 = (uint32_t)a->seed; k.key1 = (uint32_t)(a->seed >> 32); k.stream_word = a->stream_word;
+  k.bmu = a->below_mu; k.ba = a->below_a; k.bc = a->below_c;
+  k.amu = a->above_mu; k.aa = a->above_a; k.ac = a->above_c;
+  k.bbase = a->below_base; k.abase = a->above_base;
+  k.cum = a->samp_cum; k.samp = a->samp; k.ids = a->ids; k.inj = a->inject;
+  for (int d = 0; d < TPE_JOINT_MAX_DIMS; ++d) {
+    // f32 bounds: smallest float >= low, largest float < high
+    float lo = -INFINITY, hi = INFINITY;
+    if (d < a->n_dims) {
+      const double L = a->low[d], H = a->high[d];
+      if (L > -INFINITY) { lo = (float)L; if ((double)lo < L) lo = nextafterf(lo, INFINITY); }
+      if (H < INFINITY) { hi = (float)H; while ((double)hi >= H) hi = nextafterf(hi, -INFINITY); }
+    }
+    k.lo[d] = lo; k.hi[d] = hi;
+  }
+  k.cand = cand; k.l_out = l_out; k.g_out = g_out;
+  k.chunk_rec = (tpe_joint_record*)scratch;
+
+  const bool timed = g_prof.on != 0;
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned nb = (unsigned)blocks;
+  const int D = a->n_dims;
+  if (D == 1) launch_chunk<1>(k, nb, s, timed);
+  else if (D == 2) launch_chunk<2>(k, nb, s, timed);
+  else if (D == 3) launch_chunk<3>(k, nb, s, timed);
+  else if (D == 4) launch_chunk<4>(k, nb, s, timed);
+  else if (D <= 6) launch_chunk<6>(k, nb, s, timed);
+  else if (D <= 8) launch_chunk<8>(k, nb, s, timed);
+  else if (D <= 12) launch_chunk<12>(k, nb, s, timed);
+  else launch_chunk<16>(k, nb, s, timed);
+  if (timed) {
+    hipExtLaunchKernelGGL(k_joint_merge, dim3((unsigned)a->n_ids), dim3(64), 0u, s, g_prof.ev[2], g_prof.ev[3], 0u,
+                          (const tpe_joint_record*)scratch, (int)n_chunks, records);
+    g_prof.valid = 1;
+  } else {
+    hipLaunchKernelGGL(k_joint_merge, dim3((unsigned)a->n_ids), dim3(64), 0, s, (const tpe_joint_record*)scratch,
+                       (int)n_chunks, records);
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
+  return TPE_OK;
+}
+
+}  // extern "C"

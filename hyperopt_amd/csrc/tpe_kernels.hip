@@ -44,6 +44,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "../../include/tpe_hip.h"
+#include "tpe_device_rng.h"
 
 extern "C" void tpe_internal_phase(int i);   // tpe_suggest.cpp: host phase clock (hidden)
 
@@ -88,35 +89,7 @@ int hip_check(const char* stage) {
   return TPE_OK;
 }
 
-// ---------------------------------------------------------------- Philox
-struct U4 { uint32_t x, y, z, w; };
-
-__device__ __forceinline__ U4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                            uint32_t k0, uint32_t k1) {
-  const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    // one 32x32 -> 64-bit product per multiplier (v_mad_u64_u32) instead of a
-    // mul_hi / mul_lo pair
-    const uint64_t p0 = (uint64_t)M0 * (uint64_t)c0, p1 = (uint64_t)M1 * (uint64_t)c2;
-    const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
-    const uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-    const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-    c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-    k0 += W0; k1 += W1;
-  }
-  return U4{c0, c1, c2, c3};
-}
-
-// open-interval uniforms
-// 23-bit float uniform in [2^-24, 1 - 2^-24]: (k + 0.5) is exact, so never 0 or 1
-__device__ __forceinline__ float u01f(uint32_t r) { return ((float)(r >> 9) + 0.5f) * 1.1920928955078125e-07f; }
-__device__ __forceinline__ double u01d(uint32_t a, uint32_t b) {
-  const uint64_t m = ((uint64_t)a << 21) ^ (uint64_t)(b >> 11);   // 53 bits
-  return ((double)m + 0.5) * 1.1102230246251565e-16;
-}
-// 32-bit uniform as a double in (0, 1) (exact)
-__device__ __forceinline__ double u01w(uint32_t a) { return ((double)a + 0.5) * 2.3283064365386963e-10; }
+// (Philox-4x32-10, the open-interval uniforms and ndtri_f32: tpe_device_rng.h)
 
 // ---------------------------------------------------------- argmax order
 // better() on an f32 key with a 32-bit index (the cells candidates of k_sample_tab)
@@ -346,33 +319,7 @@ __device__ __forceinline__ int tile_pos(int cand_start, int j) {
 }
 
 // ================================================================= sample
-// Phi^-1(pr) in f32 = -sqrt2 erfinv(1 - 2 pr), erfinv by Giles' single-precision
-// approximation ("Approximating the erfinv function", GPU Computing Gems 2010)
-// with its log argument (1 - x)(1 + x) = 4 pr (1 - pr) formed from pr itself (no
-// cancellation in the tails).  Relative error <= 3e-7 over the f32 uniforms
-// (checked against scipy.special.ndtri); one v_log_f32, the tail branch adds a
-// sqrt.  Every f32 draw inverts through this one function.
-__device__ __forceinline__ float ndtri_f32(float pr) {
-  const float x = 1.f - 2.f * pr;
-  float w = -__logf(4.f * pr * (1.f - pr));
-  float q;
-  if (w < 5.f) {
-    w -= 2.5f;
-    q = 2.81022636e-08f;
-    q = __builtin_fmaf(q, w, 3.43273939e-07f); q = __builtin_fmaf(q, w, -3.5233877e-06f);
-    q = __builtin_fmaf(q, w, -4.39150654e-06f); q = __builtin_fmaf(q, w, 0.00021858087f);
-    q = __builtin_fmaf(q, w, -0.00125372503f); q = __builtin_fmaf(q, w, -0.00417768164f);
-    q = __builtin_fmaf(q, w, 0.246640727f); q = __builtin_fmaf(q, w, 1.50140941f);
-  } else {
-    w = __builtin_sqrtf(w) - 3.f;
-    q = -0.000200214257f;
-    q = __builtin_fmaf(q, w, 0.000100950558f); q = __builtin_fmaf(q, w, 0.00134934322f);
-    q = __builtin_fmaf(q, w, -0.00367342844f); q = __builtin_fmaf(q, w, 0.00573950773f);
-    q = __builtin_fmaf(q, w, -0.0076224613f); q = __builtin_fmaf(q, w, 0.00943887047f);
-    q = __builtin_fmaf(q, w, 1.00167406f); q = __builtin_fmaf(q, w, 2.83297682f);
-  }
-  return -1.41421356237309505f * (q * x);
-}
+// (Phi^-1 in f32, ndtri_f32: tpe_device_rng.h)
 
 // The uniforms of candidate i (Philox-4x32-10, counter = its GLOBAL index g, so
 // draws do not depend on sharding or on which kernel re-draws them): `us`

@@ -966,6 +966,77 @@ class Engine(object):
                 'tpe_report')
         return d_top, d_ntop, d_stats
 
+    def run_joint(self, below, above, low, high, ids, n_cand, seed, inject=None, return_cand=False, want_lg=False):
+        """One joint TPE stage (tpe_joint_run, include/tpe_hip.h "Joint
+        (multivariate) TPE stage"): ``below`` / ``above`` = (w [K], mu [K, D],
+        sigma [K, D]) float64 mixtures (joint.side_mixture), ``low`` / ``high``
+        [D] the bounds (+-inf: unbounded).  The rows are packed in float64 on
+        the host, uploaded and scored; per new id the winner record
+        (N.JOINT_RECORD_DTYPE) comes back.  ``inject`` [C, D]: score these
+        candidates (every id) instead of sampling.  ``return_cand``: also the
+        candidates f32 [n_ids, C, D]; ``want_lg``: also l, g float64 [n_ids, C]."""
+        from . import joint as J
+        low, high = np.asarray(low, dtype=np.float64), np.asarray(high, dtype=np.float64)
+        D = len(low)
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        n_ids, C = len(ids), int(n_cand)
+        if not 1 <= D <= N.JOINT_MAX_DIMS:
+            raise ValueError('joint stage: %d dimensions, at most %d' % (D, N.JOINT_MAX_DIMS))
+        if C < 1 or C >= 2 ** 31 or n_ids < 1:
+            raise ValueError('joint stage: n_cand / ids out of range')
+        if n_ids * C * max(D, 2) >= 2 ** 31:
+            raise ValueError('joint stage: %d ids x %d candidates do not fit one run' % (n_ids, C))
+        for side in (below, above):
+            if side[1].shape != (len(side[0]), D) or side[2].shape != side[1].shape:
+                raise ValueError('joint stage: mixture shapes do not match %d dimensions' % D)
+
+        def up(name, arr, dtype):
+            t = self._buf('joint_' + name, arr.size, dtype)
+            t[:arr.size].copy_(torch.from_numpy(np.ascontiguousarray(arr).reshape(-1)))
+            return t.data_ptr()
+        a = N.JointArgs()
+        a.n_dims, a.n_cand, a.n_ids, a.flags = D, C, n_ids, 0
+        a.k_below, a.k_above = len(below[0]), len(above[0])
+        a.stream_word, a.seed = N.JOINT_STREAM, int(seed) & 0xFFFFFFFFFFFFFFFF
+        for name, side in (('below', below), ('above', above)):
+            mu, aa, c, base = J.density_rows(side[0], side[1], side[2], low, high)
+            setattr(a, name + '_mu', up(name + '_mu', mu, torch.float32))
+            setattr(a, name + '_a', up(name + '_a', aa, torch.float32))
+            setattr(a, name + '_c', up(name + '_c', c, torch.float32))
+            setattr(a, name + '_base', base)
+        cum, rows = J.sampler_rows(below[0], below[1], below[2], low, high)
+        a.samp_cum, a.samp = up('cum', cum, torch.float64), up('samp', rows, torch.float32)
+        a.ids = up('ids', ids, torch.int64)
+        if inject is not None:
+            inj = np.ascontiguousarray(inject, dtype=np.float32)
+            if inj.shape != (C, D):
+                raise ValueError('joint stage: inject must be [n_cand, n_dims]')
+            a.flags |= N.JOINT_INJECT
+            a.inject = up('inject', inj, torch.float32)
+        for d in range(D):
+            a.low[d], a.high[d] = low[d], high[d]
+        nb = ctypes.c_uint64(0)
+        N.check(self.lib.tpe_joint_scratch_bytes(n_ids, C, ctypes.byref(nb)), self.lib, 'tpe_joint_scratch_bytes')
+        d_scr = self._buf('joint_scratch', (nb.value + 7) // 8, torch.float64)
+        d_rec = self._buf('joint_records', n_ids * N.JOINT_RECORD_DTYPE.itemsize // 8, torch.float64)
+        d_cand = self._buf('joint_cand', n_ids * C * D, torch.float32) if return_cand else None
+        d_l = self._buf('joint_l', n_ids * C, torch.float64) if want_lg else None
+        d_g = self._buf('joint_g', n_ids * C, torch.float64) if want_lg else None
+        N.check(self.lib.tpe_joint_run(ctypes.byref(a), d_rec.data_ptr(), d_cand.data_ptr() if return_cand else None,
+                                       d_l.data_ptr() if want_lg else None, d_g.data_ptr() if want_lg else None,
+                                       d_scr.data_ptr(), d_scr.numel() * 8, ctypes.c_void_p(self._stream())),
+                self.lib, 'tpe_joint_run')
+        rec = d_rec[:n_ids * 19].cpu().numpy().view(N.JOINT_RECORD_DTYPE).copy()
+        if not (return_cand or want_lg):
+            return rec
+        out = [rec]
+        if return_cand:
+            out.append(d_cand[:n_ids * C * D].cpu().numpy().reshape(n_ids, C, D).copy())
+        if want_lg:
+            out.append(d_l[:n_ids * C].cpu().numpy().reshape(n_ids, C).copy())
+            out.append(d_g[:n_ids * C].cpu().numpy().reshape(n_ids, C).copy())
+        return tuple(out)
+
     def device_tables(self):
         """(problems, comp32) of the last ``run`` as the device holds them after
         its stages ran — device-fitted above rows and the problem fields the fit

@@ -31,6 +31,10 @@ Extensions over the reference (keyword-only, defaults keep its behaviour):
     batched suggest's new ids / its hyperparameters over the ranks; one
     all-gather of the chosen values after the suggest, every rank returns the
     whole result (include/tpe_hip.h "Shard axes").
+  * ``joint=True`` / ``joint=[labels]``: the unconditional continuous labels
+    (or the listed ones) are suggested as one vector — product-kernel
+    mixtures over the group, whole-vector candidates, one argmax
+    (joint.py, DESIGN.md "Joint TPE"); every other label as without it.
 
 ``linear_forgetting`` is accepted and, as in the reference, not used: the
 forgetting window is fixed at DEFAULT_LF=25 (tpe.py:27-29).
@@ -46,6 +50,7 @@ from . import _native as N
 from . import devhist
 from . import dist as _dist
 from . import history as _history
+from . import joint as _joint
 from . import rand
 from . import replay
 from .engine import LevelProblem, get_engine
@@ -827,10 +832,12 @@ def suggest(new_ids, domain, trials, seed,
             gamma=_default_gamma,
             linear_forgetting=_default_linear_forgetting,
             sampler='philox', precision='fp32', device=None, shard=None, shard_ids=None, shard_labels=None,
-            shard_grid=None):
+            shard_grid=None, joint=False):
     new_ids = list(new_ids)
     if not new_ids:
         return []
+    if joint is not False and joint is not None:     # (argument errors first: no device use, no startup draw)
+        _joint_group(domain.table, joint, sampler, precision, (shard, shard_ids, shard_labels, shard_grid))
     t0 = time.time()
     hist = _history.extract(domain, trials)
     if logger.isEnabledFor(logging.INFO):
@@ -844,7 +851,7 @@ def suggest(new_ids, domain, trials, seed,
     choices = suggest_choices(domain.table, hist, new_ids, seed, prior_weight=prior_weight,
                               n_EI_candidates=n_EI_candidates, gamma=gamma, sampler=sampler,
                               precision=precision, device=device, shard=shard, shard_ids=shard_ids,
-                              shard_labels=shard_labels, shard_grid=shard_grid)
+                              shard_labels=shard_labels, shard_grid=shard_grid, joint=joint)
     logger.info('tpe.suggest took %f seconds', time.time() - t0)
     return rand.docs_from_choices(new_ids, domain, trials, choices)
 
@@ -884,7 +891,7 @@ class ChoiceColumns(object):
 def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weight,
                     n_EI_candidates=_default_n_EI_candidates, gamma=_default_gamma,
                     sampler='philox', precision='fp32', device=None, shard=None, columns=False,
-                    shard_ids=None, shard_labels=None, shard_grid=None):
+                    shard_ids=None, shard_labels=None, shard_grid=None, joint=False):
     """The suggest core on a structure-of-arrays history (``history.History``):
     per new id a {label: value or None} dict.  ``suggest`` wraps it with the
     Trials document layout; columnar callers (and bench.py's large configs)
@@ -900,9 +907,18 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
     divides) — those three exchange the chosen values once, after the
     suggest; every rank returns the whole result, equal to the unsharded
     suggest's (the candidates are keyed on seed, label, new id and global
-    index)."""
+    index).
+
+    ``joint``: True joins every eligible label (unconditional ``uniform``,
+    ``loguniform``, ``normal``, ``lognormal``), a list joins exactly those
+    labels: their candidates are whole vectors scored under product-kernel
+    mixtures, one argmax picks the vector (DESIGN.md "Joint TPE").  Every other
+    label is suggested exactly as without ``joint``."""
     if sampler not in ('philox', 'replay'):
         raise ValueError("sampler must be 'philox' or 'replay'")
+    group = None
+    if joint is not False and joint is not None:
+        group = _joint_group(table, joint, sampler, precision, (shard, shard_ids, shard_labels, shard_grid))
     if sum(a is not None for a in (shard, shard_ids, shard_labels, shard_grid)) > 1:
         raise ValueError('shard, shard_ids, shard_labels and shard_grid are exclusive: one shard axis per suggest')
     if (shard_ids is not None or shard_labels is not None or shard_grid is not None) and sampler == 'replay':
@@ -912,8 +928,70 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
     if shard_ids is not None or shard_labels is not None or shard_grid is not None:
         return _suggest_sharded(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, precision, device,
                                 columns, shard_ids, shard_labels, shard_grid)
+    if group is not None:
+        return _suggest_joint(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, device, columns, group)
     return _suggest_local(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, sampler, precision,
                           device, shard, columns)
+
+
+TPE_JOINT_MAX_DIMS = N.JOINT_MAX_DIMS
+
+
+def _joint_group(table, joint, sampler, precision, shards):
+    """The ParamRows a ``joint`` argument joins, in table order; ValueError for
+    every combination the joint stage does not take.  Touches no device."""
+    if sampler == 'replay':
+        raise ValueError("joint does not combine with sampler='replay': the joint candidates are Philox draws")
+    if precision == 'fp64':
+        raise ValueError("joint does not combine with precision='fp64': the joint stage scores in fp32")
+    if any(a is not None for a in shards):
+        raise ValueError('joint does not combine with a shard argument')
+    if joint is True:
+        rows = [r for r in table.rows if _joint.eligible(r)]
+    else:
+        if isinstance(joint, str):
+            raise ValueError('joint must be True or a list of labels, not the string %r' % joint)
+        want = list(joint)
+        for label in want:
+            r = table.by_label.get(label)
+            if r is None:
+                raise ValueError('joint: %r is not a label of the space' % (label,))
+            if not _joint.eligible(r):
+                raise ValueError('joint: label %r is not eligible (%s%s): only unconditional uniform, loguniform, '
+                                 'normal and lognormal labels are joined'
+                                 % (label, r.dist, '' if all(p is None for p in r.parents) else ', conditional'))
+        rows = [r for r in table.rows if r.label in set(want)]
+    if len(rows) < 2:
+        raise ValueError('joint needs at least 2 labels to join, got %d' % len(rows))
+    if len(rows) > TPE_JOINT_MAX_DIMS:
+        raise ValueError('joint joins at most TPE_JOINT_MAX_DIMS = %d labels, not %d: pass the labels to join as '
+                         'joint=[...]' % (TPE_JOINT_MAX_DIMS, len(rows)))
+    return rows
+
+
+def _suggest_joint(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, device, columns, group):
+    """The univariate suggest of every label (the joined labels' univariate
+    winners are discarded: each costs one problem of the level's batch, and the
+    other labels' values are then the same bytes as without ``joint``), then
+    one joint stage over the group, whose winner fills the group's columns."""
+    cc = _suggest_local(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, 'philox', 'fp32', device,
+                        None, True)
+    if len(cc) == 0:
+        return cc if columns else []
+    engine = get_engine(device, 'fp32')
+    model = _joint.fit_model(group, hist, _history.split_below(hist, gamma), prior_weight, DEFAULT_LF)
+    ids = np.asarray(new_ids, dtype=np.int64).reshape(-1)
+    rec = engine.run_joint(model.below, model.above, model.low, model.high, ids, int(n_EI_candidates), seed)
+    if (rec['global_idx'] < 0).any():
+        raise RuntimeError('no joint candidate selected')
+    vals = model.values(rec['z'][:, :len(group)])
+    values = np.array(cc.values, dtype=np.float64)
+    active = np.array(cc.active, dtype=bool)
+    for d, r in enumerate(group):
+        values[:, r.index] = vals[:, d]
+        active[:, r.index] = True
+    cc = ChoiceColumns(table.labels, values, active)
+    return cc if columns else cc.dicts(table)
 
 
 def _suggest_local(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, sampler, precision, device,

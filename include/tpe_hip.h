@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define TPE_ABI_VERSION 23
+#define TPE_ABI_VERSION 24
 
 /* finalize slots per candidate tile: tile_best holds n_tiles * TPE_BEST_PER_TILE entries */
 #define TPE_BEST_PER_TILE 8
@@ -1001,6 +1001,88 @@ int tpe_report(const tpe_batch* batch, int32_t k, tpe_top_entry* top, int32_t* n
  * first gets the device times {pass 1, pass 2} in ms of the last such call —
  * it WAITS for that call's kernels — then the setting changes.  Process-wide. */
 int tpe_report_profile(int32_t enable, double* last_ms);
+
+/* ------------------------------------------------------------------------
+ * Joint (multivariate) TPE stage (tpe_joint.hip; ABI 24): candidates are whole
+ * vectors z[D] (D <= TPE_JOINT_MAX_DIMS kernel coordinates: the value, or its
+ * log for the log families), a mixture component is a product of D normals
+ * truncated to the labels' bounds, one argmax per new id picks the vector.
+ * Nothing on the univariate suggest path runs through this stage.
+ *
+ * Density rows of a side (below: l, above: g), K components, all f32, device:
+ *   mu[K * D]   component k, dimension d at [k * D + d]
+ *   a [K * D]   sqrt(log2(e) / 2) / sigma_kd
+ *   c [K]       log2 of  w_k / prod_d (sigma_kd sqrt(2 pi) mass_kd),
+ *               mass_kd = Phi((high_d - mu_kd) / sigma_kd) - Phi((low_d - mu_kd) / sigma_kd)
+ *               (1 where unbounded), shifted so that max_k c_k = 0
+ *   base        (double) the shift in natural-log units (parzen.gauss_table's scheme)
+ *   log p(z) = ln2 * log2( sum_k 2^(c_k - sum_d (a_kd (z_d - mu_kd))^2) ) + base
+ * The sum over d is accumulated in this subtract-then-scale form in f32; the
+ * sum over k carries a running maximum per candidate, so a candidate more than
+ * 126 binades below max c still gets a finite density.  score = l - g in f64.
+ *
+ * Sampler rows of the below side, device:
+ *   samp_cum[K_below]           (double) cumsum of the normalised weights, last = 1
+ *   samp[(k * D + d) * 5 + ..]  (float) {mu, sigma, fa, fb, flip}: fa, fb = Phi of
+ *                               the standardised bounds, mirrored (flip != 0) when
+ *                               the interval lies right of 0 (parzen.sampler_table)
+ * Candidate i of new id j (i < n_cand < 2^31): Philox-4x32-10 with key =
+ * (seed lo, seed hi) and counter = (i, b, stream_word, id_j lo), b = 0, 1, ...
+ * the block number.  The candidate's words in block order: word 0 -> u01w -> the
+ * component k (first k with u < samp_cum[k]); word 1 + d -> the 23-bit uniform
+ * u of dimension d, z_d = mu_kd + sigma_kd * ndtri_f32(fa + u (fb - fa)) (negated
+ * under flip), clipped to [smallest float >= low_d, largest float < high_d].
+ * stream_word must differ from every univariate label index (tpe_problem.ctr2):
+ * TPE_JOINT_STREAM.
+ *
+ * One 256-thread workgroup per (id, chunk of TPE_JOINT_CHUNK consecutive
+ * candidates) samples (or loads, TPE_JOINT_INJECT) its candidates into
+ * registers, streams both sides' rows through LDS, and writes its chunk winner
+ * to `scratch`; a second launch merges an id's chunks in index order.  Winner =
+ * np.argmax order of score (NaN first, ties to the lower index).  No atomics:
+ * the same call twice gives the same bytes.
+ *
+ * tpe_joint_run returns TPE_E_ARG before any launch (no device needed) for null
+ * args / rows / ids / records, n_dims outside [1, TPE_JOINT_MAX_DIMS],
+ * n_cand < 1, n_ids < 1, k_below < 1, k_above < 1, TPE_JOINT_INJECT without
+ * `inject`, or scratch smaller than tpe_joint_scratch_bytes(n_ids, n_cand).
+ * ---------------------------------------------------------------------- */
+#define TPE_JOINT_MAX_DIMS 16
+#define TPE_JOINT_CHUNK 1024
+#define TPE_JOINT_STREAM 0xFFFFFFFFu
+#define TPE_JOINT_INJECT 1     /* tpe_joint_args.flags: score `inject` instead of sampling */
+typedef struct tpe_joint_record {
+  int64_t global_idx;          /* the winner's candidate index */
+  double l, g;
+  double z[TPE_JOINT_MAX_DIMS];   /* its coordinates (entries from n_dims on: 0) */
+} tpe_joint_record;
+typedef struct tpe_joint_args {
+  int32_t n_dims, n_cand, n_ids, flags;
+  int32_t k_below, k_above;
+  uint32_t stream_word;
+  int32_t reserved;
+  uint64_t seed;
+  const float *below_mu, *below_a, *below_c;
+  const float *above_mu, *above_a, *above_c;
+  double below_base, above_base;
+  const double* samp_cum;
+  const float* samp;
+  const int64_t* ids;          /* device [n_ids] */
+  const float* inject;         /* device [n_cand * n_dims], every id scores it */
+  double low[TPE_JOINT_MAX_DIMS], high[TPE_JOINT_MAX_DIMS];   /* -inf / +inf: unbounded */
+} tpe_joint_args;
+
+int tpe_joint_scratch_bytes(int32_t n_ids, int32_t n_cand, uint64_t* bytes);
+
+/* records: device [n_ids]; optional (NULL: not written) cand: device f32
+ * [n_ids * n_cand * n_dims], l_out / g_out: device f64 [n_ids * n_cand];
+ * enqueued on `stream` */
+int tpe_joint_run(const tpe_joint_args* args, tpe_joint_record* records, float* cand, double* l_out, double* g_out,
+                  void* scratch, uint64_t scratch_bytes, void* stream);
+
+/* Profiling only (tools/joint_time.py), as tpe_report_profile: last_ms gets the
+ * device times {chunk kernel, merge kernel} of the last profiled tpe_joint_run. */
+int tpe_joint_profile(int32_t enable, double* last_ms);
 
 /* ------------------------------------------------------------------------
  * Host phase clock of tpe_suggest_tree (tools/native_split.py).  While

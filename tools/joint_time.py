@@ -1,0 +1,143 @@
+"""Time the joint TPE stage against the host route.
+Usage: python tools/joint_time.py [--pairs 3] [--warmup 1] [--cand 1048576] [--history 10000]
+                                  [--host-cand N] [--out FILE]
+
+Workload: a flat space of 4 continuous labels (uniform, loguniform, normal,
+uniform), a seeded 10,000-trial history whose loss has an x0 * x1 term, one
+new id, C = 2^20 candidate vectors: K_below = 26 and K_above = 9976 components
+of 4 dimensions.  Two routes to the winner, alternating, each timed from a
+synchronised device to its result on the host (wall clock):
+
+  (a) host    Engine.run_joint(return_cand=True) — the candidates copied to the
+              host — then the float64 numpy model (joint.lpdf_numpy) on both
+              sides and np.argmax.  --host-cand N scores only the first N
+              candidates on the host (the numpy model takes minutes for 2^20 x
+              10^4 x 4); the line then carries the measured time for N and its
+              linear extrapolation to C, labelled as such
+  (b) device  Engine.run_joint() — tpe_joint_run, one 152-byte record copied
+
+then (untimed) the device's l and g of the host-scored candidates against the
+host's, plus the two joint kernels' own device times (tpe_joint_profile), the achieved
+(candidate x component x dimension) evaluations per second and the fraction of
+the VALU issue peak (256 CU x 4 SIMD x 2.4 GHz / 2 = 1228.8 G
+wave-instructions/s) at the kernel's instruction count per
+(candidate, component): 3 D + 7 lane-operations, D = 4.  One JSON line goes to
+stdout and is appended to --out (default profiles/joint_time.jsonl)."""
+import argparse
+import ctypes
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..')
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+
+VALU_PEAK = 1228.8e9          # wave-instructions per second
+SEED = 20240607
+
+
+def make_history(n):
+    from hyperopt_amd import base, history as H, hp
+    space = {'x0': hp.uniform('x0', -5, 5), 'x1': hp.loguniform('x1', -3, 2), 'x2': hp.normal('x2', 0, 2),
+             'x3': hp.uniform('x3', 0, 1)}
+    domain = base.Domain(lambda d: 0.0, space)
+    rs = np.random.RandomState(SEED)
+    cols = {'x0': rs.uniform(-5, 5, n), 'x1': np.exp(rs.uniform(-3, 2, n)), 'x2': rs.normal(0, 2, n),
+            'x3': rs.uniform(0, 1, n)}
+    loss = (cols['x0'] * cols['x1'] - 2.0) ** 2 + 0.1 * cols['x2'] ** 2 + (cols['x3'] - 0.3) ** 2 \
+        + 0.01 * rs.standard_normal(n)
+    tids = np.arange(n, dtype=np.int64)
+    return domain, H.History(tids, loss, {k: (tids, v) for k, v in cols.items()})
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--pairs', type=int, default=3)
+    ap.add_argument('--warmup', type=int, default=1)
+    ap.add_argument('--cand', type=int, default=1 << 20)
+    ap.add_argument('--history', type=int, default=10000)
+    ap.add_argument('--host-cand', type=int, default=None)
+    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'joint_time.jsonl'))
+    args = ap.parse_args()
+
+    import torch
+    from hyperopt_amd import _native as N, history as H, joint as J
+    from hyperopt_amd.engine import get_engine
+
+    domain, hist = make_history(args.history)
+    rows = [r for r in domain.table.rows if J.eligible(r)]
+    model = J.fit_model(rows, hist, H.split_below(hist, 0.25), 1.0)
+    eng = get_engine(None, 'fp32')
+    lib = eng.lib
+    C, D = args.cand, len(rows)
+    Kb, Ka = len(model.below[0]), len(model.above[0])
+    n_host = C if args.host_cand is None else min(C, args.host_cand)
+    ids = np.array([args.history], dtype=np.int64)
+
+    def route_device():
+        return eng.run_joint(model.below, model.above, model.low, model.high, ids, C, SEED)
+
+    def route_host():
+        rec, cand = eng.run_joint(model.below, model.above, model.low, model.high, ids, C, SEED, return_cand=True)
+        z = cand[0, :n_host].astype(np.float64)
+        l = J.lpdf_numpy(z, model.below[0], model.below[1], model.below[2], model.low, model.high)
+        g = J.lpdf_numpy(z, model.above[0], model.above[1], model.above[2], model.low, model.high)
+        return rec, l, g
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, out
+
+    for _ in range(args.warmup):
+        rec = route_device()
+    wall = {'host': [], 'device': []}
+    kern = []
+    ms2 = (ctypes.c_double * 2)()
+    for i in range(args.pairs):
+        w, (rec_h, l, g) = timed(route_host)
+        wall['host'].append(w)
+        print('pair %d: host route %.0f ms' % (i, w), file=sys.stderr, flush=True)
+        N.check(lib.tpe_joint_profile(1, None), lib, 'tpe_joint_profile')
+        w, rec = timed(route_device)
+        N.check(lib.tpe_joint_profile(0, ms2), lib, 'tpe_joint_profile')
+        wall['device'].append(w)
+        kern.append((ms2[0], ms2[1]))
+    # (untimed) the device's l and g of the host-scored candidates against the float64 model, in
+    # units of the project's lpdf tolerance 1e-5 * max(1, |ref|)
+    _, dl, dg = eng.run_joint(model.below, model.above, model.low, model.high, ids, C, SEED, want_lg=True)
+    err = max(float(np.max(np.abs(dl[0, :n_host] - l) / np.maximum(1.0, np.abs(l)))),
+              float(np.max(np.abs(dg[0, :n_host] - g) / np.maximum(1.0, np.abs(g))))) / 1e-5
+    med = lambda x: float(np.median(x))   # noqa: E731
+    k1, k2 = med([a for a, _ in kern]), med([b for _, b in kern])
+    evals = float(C) * (Kb + Ka) * D
+    ops = 3 * D + 7                        # lane-operations per (candidate, component)
+    wave_instr = float(C) * (Kb + Ka) * ops / 64.0
+    line = dict(tool='joint_time', labels=[r.label for r in rows], history=args.history, n_cand=C, n_dims=D,
+                k_below=Kb, k_above=Ka, pairs=args.pairs, host_cand=n_host,
+                host_route_ms=dict(wall_median=med(wall['host']), wall_min=min(wall['host']),
+                                   wall_max=max(wall['host']),
+                                   extrapolated_to_all_candidates_median=med(wall['host']) * C / n_host),
+                device_route_ms=dict(wall_median=med(wall['device']), wall_min=min(wall['device']),
+                                     wall_max=max(wall['device'])),
+                k_joint_chunk_ms=k1, k_joint_merge_ms=k2,
+                evals_per_s=evals / (k1 * 1e-3) if k1 > 0 else None,
+                ops_per_cand_comp=ops,
+                valu_wave_instr_per_s=wave_instr / (k1 * 1e-3) if k1 > 0 else None,
+                fraction_of_valu_peak=wave_instr / (k1 * 1e-3) / VALU_PEAK if k1 > 0 else None,
+                lpdf_err_over_tol=err, gpu=torch.cuda.get_device_name(0))
+    text = json.dumps(line)
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, 'a') as f:
+        f.write(text + '\n')
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())
