@@ -79,6 +79,8 @@ JOINT_STREAM = 0xFFFFFFFF      # TPE_JOINT_STREAM: the Philox counter word no la
 JOINT_INJECT = 1               # TPE_JOINT_INJECT
 JOINT_RECORD_DTYPE = np.dtype([('global_idx', '<i8'), ('l', '<f8'), ('g', '<f8'), ('z', '<f8', (JOINT_MAX_DIMS,))])
 assert JOINT_RECORD_DTYPE.itemsize == 152
+JOINT_MAX_CATS = 256           # TPE_JOINT_MAX_CATS: categories of one joined discrete label
+JOINT_MAX_CAT_TOTAL = 1024     # TPE_JOINT_MAX_CAT_TOTAL: categories of a joint group
 
 
 class Batch(ctypes.Structure):
@@ -129,6 +131,26 @@ class JointArgs(ctypes.Structure):
         ('samp_cum', ctypes.c_void_p), ('samp', ctypes.c_void_p), ('ids', ctypes.c_void_p),
         ('inject', ctypes.c_void_p),
         ('low', ctypes.c_double * JOINT_MAX_DIMS), ('high', ctypes.c_double * JOINT_MAX_DIMS),
+    ]
+
+
+class JointMixedArgs(ctypes.Structure):
+    """tpe_joint_mixed_args: one tpe_joint_mixed_run (n_dims continuous, n_cat discrete labels)."""
+    _fields_ = [
+        ('n_dims', ctypes.c_int32), ('n_cand', ctypes.c_int32), ('n_ids', ctypes.c_int32), ('flags', ctypes.c_int32),
+        ('k_below', ctypes.c_int32), ('k_above', ctypes.c_int32), ('stream_word', ctypes.c_uint32),
+        ('n_cat', ctypes.c_int32), ('seed', ctypes.c_uint64),
+        ('below_mu', ctypes.c_void_p), ('below_a', ctypes.c_void_p), ('below_c', ctypes.c_void_p),
+        ('above_mu', ctypes.c_void_p), ('above_a', ctypes.c_void_p), ('above_c', ctypes.c_void_p),
+        ('below_base', ctypes.c_double), ('above_base', ctypes.c_double),
+        ('samp_cum', ctypes.c_void_p), ('samp', ctypes.c_void_p), ('ids', ctypes.c_void_p),
+        ('inject', ctypes.c_void_p),
+        ('low', ctypes.c_double * JOINT_MAX_DIMS), ('high', ctypes.c_double * JOINT_MAX_DIMS),
+        ('cat_upper', ctypes.c_int32 * JOINT_MAX_DIMS), ('cat_off', ctypes.c_int32 * JOINT_MAX_DIMS),
+        ('below_cat', ctypes.c_void_p), ('above_cat', ctypes.c_void_p),
+        ('below_miss', ctypes.c_void_p), ('below_bonus', ctypes.c_void_p),
+        ('above_miss', ctypes.c_void_p), ('above_bonus', ctypes.c_void_p),
+        ('below_h', ctypes.c_void_p), ('cat_cum', ctypes.c_void_p),
     ]
 
 
@@ -274,7 +296,8 @@ EXPORTS = ('tpe_abi_version', 'tpe_last_error', 'tpe_device_count', 'tpe_tile_si
            'tpe_suggest_tree', 'tpe_comm_unique_id', 'tpe_comm_init', 'tpe_comm_destroy', 'tpe_combine_results',
            'tpe_host_threads', 'tpe_host_phases', 'tpe_exchange_allgather', 'tpe_debug_fast_lg',
            'tpe_collectives_issued', 'tpe_scatter_f64', 'tpe_move_ranges', 'tpe_report_scratch_bytes', 'tpe_report',
-           'tpe_report_profile', 'tpe_joint_scratch_bytes', 'tpe_joint_run', 'tpe_joint_profile')
+           'tpe_report_profile', 'tpe_joint_scratch_bytes', 'tpe_joint_run', 'tpe_joint_profile',
+           'tpe_joint_mixed_run')
 
 # host phases of tpe_suggest_tree (tpe_host_phases order)
 PHASES = ('prefit', 'pack', 'launched', 'synced', 'level', 'return', 'recs')
@@ -389,6 +412,8 @@ def load(path=LIB_PATH):
     lib.tpe_joint_scratch_bytes.restype = ctypes.c_int
     lib.tpe_joint_run.argtypes = [ctypes.POINTER(JointArgs), P, P, P, P, P, ctypes.c_uint64, P]
     lib.tpe_joint_run.restype = ctypes.c_int
+    lib.tpe_joint_mixed_run.argtypes = [ctypes.POINTER(JointMixedArgs), P, P, P, P, P, ctypes.c_uint64, P]
+    lib.tpe_joint_mixed_run.restype = ctypes.c_int
     lib.tpe_joint_profile.argtypes = [I32, P]
     lib.tpe_joint_profile.restype = ctypes.c_int
     lib.tpe_level_profile.argtypes = [ctypes.c_int32]

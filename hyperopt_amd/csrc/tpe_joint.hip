@@ -12,6 +12,9 @@
 //                that serves 64 * kR evaluations.  Per (candidate, component):
 //                3 D VALU operations (subtract, scale, fma) and 7 for the
 //                running-maximum sum of 2^term (one v_exp_f32).
+// k_joint_mixed_chunk  the same for a group that also holds discrete labels: a
+//                category costs one compare, one select and one add per
+//                (candidate, component).
 // k_joint_merge  one wave per new id: the chunk winners in index order.
 // Every reduction has a fixed shape and there are no atomics: the output bytes
 // are a function of the input bytes.
@@ -238,6 +241,241 @@ __global__ __launch_bounds__(64) void k_joint_merge(const tpe_joint_record* __re
   }
 }
 
+// ------------------------------------------------------------ mixed groups
+// Dc continuous coordinates (as above) followed by Dk discrete ones; a category
+// is its index as an f32 (include/tpe_hip.h "Mixed joint stage").
+struct MixedK {
+  JointK j;                         // j.D = Dc; cand / inject rows are [Dc + Dk]
+  int Dk;
+  int U[TPE_JOINT_MAX_DIMS], off[TPE_JOINT_MAX_DIMS];
+  const float *bcat, *acat;
+  const float *bmiss, *bbonus, *amiss, *abonus;
+  const double* bh;
+  const double* ccum;
+};
+
+// the candidate's category of dimension d as a table index (a category outside
+// [0, U) is the caller's error: the index is kept inside the table, no more)
+__device__ __forceinline__ int cat_index(float v, int U) { return min(max((int)v, 0), U - 1); }
+
+// score_side with KP discrete dimensions: a component's term gains the
+// candidate's bonus where the categories are equal.  nb = -bonus_d(v_d) is read
+// once per candidate here; per (candidate, component) and dimension then one
+// compare, one select and one add.  out gets + sum_d miss_d(v_d) in f64.
+template <int CP, int KP>
+__device__ __forceinline__ void score_side_mixed(const float* __restrict__ mu, const float* __restrict__ a,
+                                                 const float* __restrict__ c, const float* __restrict__ cat,
+                                                 const float* __restrict__ miss, const float* __restrict__ bonus,
+                                                 int K, const MixedK& p, const float (&z)[kR][CP + KP],
+                                                 float* __restrict__ rows, float* __restrict__ cl, double (&out)[kR]) {
+  constexpr int S = 2 * CP + KP;
+  const int Dc = p.j.D, Dk = p.Dk;
+  float m[kR], s[kR], nb[kR][KP];
+#pragma unroll
+  for (int r = 0; r < kR; ++r) {
+    m[r] = -3.0e38f;
+    s[r] = 0.f;
+#pragma unroll
+    for (int d = 0; d < KP; ++d) nb[r][d] = d < Dk ? -bonus[p.off[d] + cat_index(z[r][CP + d], p.U[d])] : 0.f;
+  }
+  for (int k0 = 0; k0 < K; k0 += kTileK) {
+    const int nk = min(kTileK, K - k0);
+    __syncthreads();                       // the previous tile (or side) is read
+    if constexpr (CP > 0)
+      for (int e = threadIdx.x; e < nk * CP; e += kThreads) {
+        const int kk = e / CP, d = e % CP;
+        const bool in = d < Dc;              // padded dimensions: a = 0 adds nothing
+        const int64_t src = (int64_t)(k0 + kk) * Dc + d;
+        rows[kk * S + d] = in ? mu[src] : 0.f;
+        rows[kk * S + CP + d] = in ? a[src] : 0.f;
+      }
+    for (int e = threadIdx.x; e < nk * KP; e += kThreads) {
+      const int kk = e / KP, d = e % KP;     // padded dimensions: category -1 never matches
+      rows[kk * S + 2 * CP + d] = d < Dk ? cat[(int64_t)(k0 + kk) * Dk + d] : -1.f;
+    }
+    for (int e = threadIdx.x; e < nk; e += kThreads) cl[e] = c[k0 + e];
+    __syncthreads();
+    for (int kk = 0; kk < nk; ++kk) {
+      const float* row = rows + kk * S;
+      float rm[CP + 1], ra[CP + 1], rc[KP];
+#pragma unroll
+      for (int d = 0; d < CP; ++d) { rm[d] = row[d]; ra[d] = row[CP + d]; }
+#pragma unroll
+      for (int d = 0; d < KP; ++d) rc[d] = row[2 * CP + d];
+      const float ck = cl[kk];
+#pragma unroll
+      for (int r = 0; r < kR; ++r) {
+        float acc = 0.f;
+#pragma unroll
+        for (int d = 0; d < CP; ++d) {
+          const float u = (z[r][d] - rm[d]) * ra[d];
+          acc = __builtin_fmaf(u, u, acc);
+        }
+#pragma unroll
+        for (int d = 0; d < KP; ++d) acc += z[r][CP + d] == rc[d] ? nb[r][d] : 0.f;
+        const float t = ck - acc;
+        const float dl = t - m[r];
+        const float e2 = __builtin_amdgcn_exp2f(-__builtin_fabsf(dl));
+        s[r] = dl > 0.f ? __builtin_fmaf(s[r], e2, 1.f) : s[r] + e2;
+        m[r] = fmaxf(m[r], t);
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < kR; ++r) {
+    double M = 0.0;
+#pragma unroll
+    for (int d = 0; d < KP; ++d)
+      if (d < Dk) M += (double)miss[p.off[d] + cat_index(z[r][CP + d], p.U[d])];
+    out[r] = (double)m[r] + log2((double)s[r]) + M;
+  }
+}
+
+// k_joint_chunk for a mixed group: CP / KP the padded continuous / discrete
+// counts (CP = 0: an all-discrete group).  z[r] holds the continuous
+// coordinates at [0, CP) and the categories at [CP, CP + KP).
+// (From 12 padded coordinates on the register allocator is told not to aim above
+// 2 waves a SIMD: left alone it spills a few dwords to hold 3.)
+template <int CP, int KP>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, (CP + KP >= 12 ? 2 : 8))))
+void k_joint_mixed_chunk(const MixedK p) {
+  constexpr int ZP = CP + KP;
+  __shared__ __attribute__((aligned(16))) float rows[kTileK * (2 * CP + KP)];
+  __shared__ float cl[kTileK];
+  __shared__ Pick slot[kThreads / 64];
+  const JointK& q = p.j;
+  const int t = threadIdx.x, Dc = q.D, Dk = p.Dk, D = Dc + Dk;
+  const int id = blockIdx.x / q.n_chunks, chunk = blockIdx.x % q.n_chunks;
+  const int first = chunk * TPE_JOINT_CHUNK;
+
+  float z[kR][ZP];
+#pragma unroll
+  for (int r = 0; r < kR; ++r) {
+#pragma unroll
+    for (int d = 0; d < ZP; ++d) z[r][d] = 0.f;
+    const int i = first + r * kThreads + t;
+    if (i >= q.C) continue;
+    if (q.inject) {
+#pragma unroll
+      for (int d = 0; d < CP; ++d)
+        if (d < Dc) z[r][d] = q.inj[(int64_t)i * D + d];
+#pragma unroll
+      for (int d = 0; d < KP; ++d)
+        if (d < Dk) z[r][CP + d] = q.inj[(int64_t)i * D + Dc + d];
+      continue;
+    }
+    const uint32_t c3 = (uint32_t)q.ids[id];
+    U4 w = philox4x32_10((uint32_t)i, 0u, q.stream_word, c3, q.key0, q.key1);
+    const double us = u01w(w.x);
+    int lo = 0, hi = q.kb - 1;             // first k with us < cum[k]
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (us < q.cum[mid]) hi = mid; else lo = mid + 1; }
+    const int comp = lo;
+    const float* srow = q.samp + (int64_t)comp * Dc * 5;
+    // One loop over the kernel coordinates, not unrolled (4 (CP + KP) copies of
+    // the samplers would keep z out of registers); word 1 + j serves coordinate
+    // j, and a continuous one is k_joint_chunk's draw, operation for operation.
+    for (int j = 0; j < D; ++j) {
+      const int wi = j + 1;
+      if ((wi & 3) == 0) w = philox4x32_10((uint32_t)i, (uint32_t)(wi >> 2), q.stream_word, c3, q.key0, q.key1);
+      const uint32_t word = (wi & 3) == 0 ? w.x : (wi & 3) == 1 ? w.y : (wi & 3) == 2 ? w.z : w.w;
+      float x;
+      if (j < Dc) {
+        const float* sr = srow + j * 5;
+        const float pr = sr[2] + u01f(word) * (sr[3] - sr[2]);
+        float zz = ndtri_f32(pr);
+        if (sr[4] != 0.f) zz = -zz;
+        x = sr[0] + sr[1] * zz;
+        if (!(x == x)) x = sr[0];
+        float blo = 0.f, bhi = 0.f;                       // (kernel-argument arrays: constant indices only)
+#pragma unroll
+        for (int f = 0; f < CP; ++f)
+          if (f == j) { blo = q.lo[f]; bhi = q.hi[f]; }
+        x = fminf(fmaxf(x, blo), bhi);                    // low <= z < high
+      } else {
+        const int d = j - Dc;
+        const double u = u01w(word);
+        x = p.bcat[(int64_t)comp * Dk + d];               // the component's category, -1: the prior row
+        const double h = x >= 0.f ? p.bh[d] : 0.0;
+        if (!(u < h)) {
+          const double u2 = (u - h) / (1.0 - h);
+          int off = 0, U = 1;
+#pragma unroll
+          for (int f = 0; f < KP; ++f)
+            if (f == d) { off = p.off[f]; U = p.U[f]; }
+          const double* cum = p.ccum + off;
+          int a = 0, b = U - 1;                           // first category with u2 < cum[v]
+          while (a < b) { const int mid = (a + b) >> 1; if (u2 < cum[mid]) b = mid; else a = mid + 1; }
+          x = (float)a;
+        }
+      }
+      const int e = j < Dc ? j : CP + (j - Dc);
+#pragma unroll
+      for (int f = 0; f < ZP; ++f)
+        if (f == e) z[r][f] = x;
+    }
+  }
+
+  double l2[kR], g2[kR];
+  score_side_mixed<CP, KP>(q.bmu, q.ba, q.bc, p.bcat, p.bmiss, p.bbonus, q.kb, p, z, rows, cl, l2);
+  score_side_mixed<CP, KP>(q.amu, q.aa, q.ac, p.acat, p.amiss, p.abonus, q.ka, p, z, rows, cl, g2);
+
+  Pick best{0, 0};
+  double lv[kR], gv[kR];
+#pragma unroll
+  for (int r = 0; r < kR; ++r) {
+    const int i = first + r * kThreads + t;
+    lv[r] = l2[r] * kLn2 + q.bbase;
+    gv[r] = g2[r] * kLn2 + q.abase;
+    if (i >= q.C) continue;
+    const int64_t o = (int64_t)id * q.C + i;
+    if (q.l_out) q.l_out[o] = lv[r];
+    if (q.g_out) q.g_out[o] = gv[r];
+    if (q.cand) {
+#pragma unroll
+      for (int d = 0; d < CP; ++d)
+        if (d < Dc) q.cand[o * D + d] = z[r][d];
+#pragma unroll
+      for (int d = 0; d < KP; ++d)
+        if (d < Dk) q.cand[o * D + Dc + d] = z[r][CP + d];
+    }
+    const uint64_t key = score_key(lv[r] - gv[r]);
+    if (key > best.key) best = Pick{key, (int64_t)i};   // ascending index: strict > keeps the first of a tie
+  }
+  Pick w = wave_best(best);
+  if ((t & 63) == 0) slot[t >> 6] = w;
+  __syncthreads();
+  w = slot[0];
+#pragma unroll
+  for (int s = 1; s < kThreads / 64; ++s)
+    if (beats(slot[s], w)) w = slot[s];
+
+  tpe_joint_record* rec = q.chunk_rec + blockIdx.x;
+  if (w.key == 0) {
+    if (t == 0) rec->global_idx = -1;
+    return;
+  }
+  const int off = (int)(w.idx - first);
+  if (t != off % kThreads) return;
+  const int wr = off / kThreads;
+#pragma unroll
+  for (int r = 0; r < kR; ++r) {
+    if (r != wr) continue;
+    rec->global_idx = w.idx;
+    rec->l = lv[r];
+    rec->g = gv[r];
+    // kernel coordinate order: the Dc continuous entries, the categories, then zeros
+#pragma unroll
+    for (int d = 0; d < TPE_JOINT_MAX_DIMS; ++d)
+      if (d >= D) rec->z[d] = 0.0;
+#pragma unroll
+    for (int d = 0; d < CP; ++d)
+      if (d < Dc) rec->z[d] = (double)z[r][d];
+#pragma unroll
+    for (int d = 0; d < KP; ++d)
+      if (d < Dk) rec->z[Dc + d] = (double)z[r][CP + d];
+  }
+}
+
 int64_t n_chunks_of(int32_t n_cand) { return ((int64_t)n_cand + TPE_JOINT_CHUNK - 1) / TPE_JOINT_CHUNK; }
 
 // tpe_joint_profile: start / stop events of the two launches (profiling only)
@@ -253,6 +491,28 @@ void launch_chunk(const JointK& k, unsigned blocks, hipStream_t stream, bool tim
                           k);
   else
     hipLaunchKernelGGL(k_joint_chunk<DP>, dim3(blocks), dim3(kThreads), 0, stream, k);
+}
+
+template <int CP, int KP>
+void launch_mixed(const MixedK& k, unsigned blocks, hipStream_t stream, bool timed) {
+  if (timed)
+    hipExtLaunchKernelGGL((k_joint_mixed_chunk<CP, KP>), dim3(blocks), dim3(kThreads), 0u, stream, g_prof.ev[0],
+                          g_prof.ev[1], 0u, k);
+  else
+    hipLaunchKernelGGL((k_joint_mixed_chunk<CP, KP>), dim3(blocks), dim3(kThreads), 0, stream, k);
+}
+
+// padded counts: CP in {0, 2, 4, 8, 16}, KP in {1, 2, 4, 8, 16}; 16 continuous
+// slots mean at least 9 continuous labels, so at most 7 discrete ones: 24
+// instantiations in all
+template <int CP>
+void launch_mixed_k(const MixedK& k, unsigned blocks, hipStream_t stream, bool timed) {
+  const int Dk = k.Dk;
+  if (Dk == 1) launch_mixed<CP, 1>(k, blocks, stream, timed);
+  else if (Dk == 2) launch_mixed<CP, 2>(k, blocks, stream, timed);
+  else if (Dk <= 4) launch_mixed<CP, 4>(k, blocks, stream, timed);
+  else if (Dk <= 8) launch_mixed<CP, 8>(k, blocks, stream, timed);
+  else if constexpr (CP < 16) launch_mixed<CP, 16>(k, blocks, stream, timed);
 }
 
 }  // namespace
@@ -338,6 +598,106 @@ int tpe_joint_run(const tpe_joint_args* a, tpe_joint_record* records, float* can
   else if (D <= 8) launch_chunk<8>(k, nb, s, timed);
   else if (D <= 12) launch_chunk<12>(k, nb, s, timed);
   else launch_chunk<16>(k, nb, s, timed);
+  if (timed) {
+    hipExtLaunchKernelGGL(k_joint_merge, dim3((unsigned)a->n_ids), dim3(64), 0u, s, g_prof.ev[2], g_prof.ev[3], 0u,
+                          (const tpe_joint_record*)scratch, (int)n_chunks, records);
+    g_prof.valid = 1;
+  } else {
+    hipLaunchKernelGGL(k_joint_merge, dim3((unsigned)a->n_ids), dim3(64), 0, s, (const tpe_joint_record*)scratch,
+                       (int)n_chunks, records);
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
+  return TPE_OK;
+}
+
+int tpe_joint_mixed_run(const tpe_joint_mixed_args* a, tpe_joint_record* records, float* cand, double* l_out,
+                        double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
+  if (!a) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: null args");
+  if (a->n_cat < 0) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: n_cat < 0");
+  if (a->n_dims < 0 || a->n_dims > TPE_JOINT_MAX_DIMS || a->n_dims + a->n_cat < 1 ||
+      a->n_dims + a->n_cat > TPE_JOINT_MAX_DIMS)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: n_dims + n_cat outside [1, TPE_JOINT_MAX_DIMS]");
+  if (a->n_cat == 0) {                      // no discrete label: the continuous stage, the same bytes
+    tpe_joint_args c;
+    c.n_dims = a->n_dims; c.n_cand = a->n_cand; c.n_ids = a->n_ids; c.flags = a->flags;
+    c.k_below = a->k_below; c.k_above = a->k_above; c.stream_word = a->stream_word; c.reserved = 0;
+    c.seed = a->seed;
+    c.below_mu = a->below_mu; c.below_a = a->below_a; c.below_c = a->below_c;
+    c.above_mu = a->above_mu; c.above_a = a->above_a; c.above_c = a->above_c;
+    c.below_base = a->below_base; c.above_base = a->above_base;
+    c.samp_cum = a->samp_cum; c.samp = a->samp; c.ids = a->ids; c.inject = a->inject;
+    for (int d = 0; d < TPE_JOINT_MAX_DIMS; ++d) { c.low[d] = a->low[d]; c.high[d] = a->high[d]; }
+    return tpe_joint_run(&c, records, cand, l_out, g_out, scratch, scratch_bytes, stream);
+  }
+  const int Dc = a->n_dims, Dk = a->n_cat;
+  if (a->n_cand < 1) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: n_cand < 1");
+  if (a->n_ids < 1) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: n_ids < 1");
+  if (a->k_below < 1 || a->k_above < 1)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: k_below < 1 or k_above < 1");
+  if (!a->below_c || !a->above_c || (Dc > 0 && (!a->below_mu || !a->below_a || !a->above_mu || !a->above_a)))
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: null density rows");
+  const bool inject = (a->flags & TPE_JOINT_INJECT) != 0;
+  if (inject && !a->inject)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: TPE_JOINT_INJECT without candidates");
+  if (!inject && (!a->samp_cum || (Dc > 0 && !a->samp)))
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: null sampler rows");
+  if (!a->ids || !records) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: null ids / records");
+  if (!a->below_cat || !a->above_cat || !a->below_miss || !a->below_bonus || !a->above_miss || !a->above_bonus ||
+      !a->below_h || !a->cat_cum)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: null category tables");
+  int total = 0;
+  for (int d = 0; d < Dk; ++d) {
+    if (a->cat_upper[d] < 2 || a->cat_upper[d] > TPE_JOINT_MAX_CATS)
+      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: categories of a label outside [2, TPE_JOINT_MAX_CATS]");
+    total += a->cat_upper[d];
+  }
+  if (total > TPE_JOINT_MAX_CAT_TOTAL)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: more than TPE_JOINT_MAX_CAT_TOTAL categories");
+  for (int d = 0; d < Dk; ++d)
+    if (a->cat_off[d] < 0 || a->cat_off[d] > total - a->cat_upper[d])
+      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: cat_off outside the tables");
+  const int64_t n_chunks = n_chunks_of(a->n_cand), blocks = n_chunks * a->n_ids;
+  if (blocks > INT32_MAX) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: too many candidates");
+  const uint64_t need = (uint64_t)blocks * sizeof(tpe_joint_record);
+  if (!scratch || scratch_bytes < need) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: scratch too small");
+
+  MixedK m;
+  JointK& k = m.j;
+  k.D = Dc; k.C = a->n_cand; k.n_chunks = (int)n_chunks; k.inject = inject ? 1 : 0;
+  k.kb = a->k_below; k.ka = a->k_above;
+  k.key0 = (uint32_t)a->seed; k.key1 = (uint32_t)(a->seed >> 32); k.stream_word = a->stream_word;
+  k.bmu = a->below_mu; k.ba = a->below_a; k.bc = a->below_c;
+  k.amu = a->above_mu; k.aa = a->above_a; k.ac = a->above_c;
+  k.bbase = a->below_base; k.abase = a->above_base;
+  k.cum = a->samp_cum; k.samp = a->samp; k.ids = a->ids; k.inj = a->inject;
+  for (int d = 0; d < TPE_JOINT_MAX_DIMS; ++d) {
+    // f32 bounds: smallest float >= low, largest float < high (as tpe_joint_run)
+    float lo = -INFINITY, hi = INFINITY;
+    if (d < Dc) {
+      const double L = a->low[d], H = a->high[d];
+      if (L > -INFINITY) { lo = (float)L; if ((double)lo < L) lo = nextafterf(lo, INFINITY); }
+      if (H < INFINITY) { hi = (float)H; while ((double)hi >= H) hi = nextafterf(hi, -INFINITY); }
+    }
+    k.lo[d] = lo; k.hi[d] = hi;
+    m.U[d] = d < Dk ? a->cat_upper[d] : 1;
+    m.off[d] = d < Dk ? a->cat_off[d] : 0;
+  }
+  k.cand = cand; k.l_out = l_out; k.g_out = g_out;
+  k.chunk_rec = (tpe_joint_record*)scratch;
+  m.Dk = Dk;
+  m.bcat = a->below_cat; m.acat = a->above_cat;
+  m.bmiss = a->below_miss; m.bbonus = a->below_bonus; m.amiss = a->above_miss; m.abonus = a->above_bonus;
+  m.bh = a->below_h; m.ccum = a->cat_cum;
+
+  const bool timed = g_prof.on != 0;
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned nb = (unsigned)blocks;
+  if (Dc == 0) launch_mixed_k<0>(m, nb, s, timed);
+  else if (Dc <= 2) launch_mixed_k<2>(m, nb, s, timed);
+  else if (Dc <= 4) launch_mixed_k<4>(m, nb, s, timed);
+  else if (Dc <= 8) launch_mixed_k<8>(m, nb, s, timed);
+  else launch_mixed_k<16>(m, nb, s, timed);
   if (timed) {
     hipExtLaunchKernelGGL(k_joint_merge, dim3((unsigned)a->n_ids), dim3(64), 0u, s, g_prof.ev[2], g_prof.ev[3], 0u,
                           (const tpe_joint_record*)scratch, (int)n_chunks, records);

@@ -978,22 +978,11 @@ class Engine(object):
         from . import joint as J
         low, high = np.asarray(low, dtype=np.float64), np.asarray(high, dtype=np.float64)
         D = len(low)
-        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
-        n_ids, C = len(ids), int(n_cand)
-        if not 1 <= D <= N.JOINT_MAX_DIMS:
-            raise ValueError('joint stage: %d dimensions, at most %d' % (D, N.JOINT_MAX_DIMS))
-        if C < 1 or C >= 2 ** 31 or n_ids < 1:
-            raise ValueError('joint stage: n_cand / ids out of range')
-        if n_ids * C * max(D, 2) >= 2 ** 31:
-            raise ValueError('joint stage: %d ids x %d candidates do not fit one run' % (n_ids, C))
+        ids, n_ids, C = self._joint_sizes(D, ids, n_cand)
         for side in (below, above):
             if side[1].shape != (len(side[0]), D) or side[2].shape != side[1].shape:
                 raise ValueError('joint stage: mixture shapes do not match %d dimensions' % D)
-
-        def up(name, arr, dtype):
-            t = self._buf('joint_' + name, arr.size, dtype)
-            t[:arr.size].copy_(torch.from_numpy(np.ascontiguousarray(arr).reshape(-1)))
-            return t.data_ptr()
+        up = self._joint_up
         a = N.JointArgs()
         a.n_dims, a.n_cand, a.n_ids, a.flags = D, C, n_ids, 0
         a.k_below, a.k_above = len(below[0]), len(above[0])
@@ -1007,14 +996,40 @@ class Engine(object):
         cum, rows = J.sampler_rows(below[0], below[1], below[2], low, high)
         a.samp_cum, a.samp = up('cum', cum, torch.float64), up('samp', rows, torch.float32)
         a.ids = up('ids', ids, torch.int64)
-        if inject is not None:
-            inj = np.ascontiguousarray(inject, dtype=np.float32)
-            if inj.shape != (C, D):
-                raise ValueError('joint stage: inject must be [n_cand, n_dims]')
-            a.flags |= N.JOINT_INJECT
-            a.inject = up('inject', inj, torch.float32)
+        self._joint_inject(a, inject, C, D)
         for d in range(D):
             a.low[d], a.high[d] = low[d], high[d]
+        return self._joint_call('tpe_joint_run', a, n_ids, C, D, return_cand, want_lg)
+
+    # what run_joint and run_joint_mixed share: the size checks, the uploads, the call and its results
+    def _joint_sizes(self, D, ids, n_cand):
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        n_ids, C = len(ids), int(n_cand)
+        if not 1 <= D <= N.JOINT_MAX_DIMS:
+            raise ValueError('joint stage: %d dimensions, at most %d' % (D, N.JOINT_MAX_DIMS))
+        if C < 1 or C >= 2 ** 31 or n_ids < 1:
+            raise ValueError('joint stage: n_cand / ids out of range')
+        if n_ids * C * max(D, 2) >= 2 ** 31:
+            raise ValueError('joint stage: %d ids x %d candidates do not fit one run' % (n_ids, C))
+        return ids, n_ids, C
+
+    def _joint_up(self, name, arr, dtype):
+        t = self._buf('joint_' + name, arr.size, dtype)
+        t[:arr.size].copy_(torch.from_numpy(np.ascontiguousarray(arr).reshape(-1)))
+        return t.data_ptr()
+
+    def _joint_inject(self, a, inject, C, D):
+        if inject is None:
+            return
+        inj = np.ascontiguousarray(inject, dtype=np.float32)
+        if inj.shape != (C, D):
+            raise ValueError('joint stage: inject must be [n_cand, %d]' % D)
+        a.flags |= N.JOINT_INJECT
+        a.inject = self._joint_up('inject', inj, torch.float32)
+
+    def _joint_call(self, fn, a, n_ids, C, D, return_cand, want_lg):
+        """Scratch and result buffers, the native call ``fn`` and the records
+        (and candidates [n_ids, C, D], l, g [n_ids, C]) on the host."""
         nb = ctypes.c_uint64(0)
         N.check(self.lib.tpe_joint_scratch_bytes(n_ids, C, ctypes.byref(nb)), self.lib, 'tpe_joint_scratch_bytes')
         d_scr = self._buf('joint_scratch', (nb.value + 7) // 8, torch.float64)
@@ -1022,10 +1037,10 @@ class Engine(object):
         d_cand = self._buf('joint_cand', n_ids * C * D, torch.float32) if return_cand else None
         d_l = self._buf('joint_l', n_ids * C, torch.float64) if want_lg else None
         d_g = self._buf('joint_g', n_ids * C, torch.float64) if want_lg else None
-        N.check(self.lib.tpe_joint_run(ctypes.byref(a), d_rec.data_ptr(), d_cand.data_ptr() if return_cand else None,
-                                       d_l.data_ptr() if want_lg else None, d_g.data_ptr() if want_lg else None,
-                                       d_scr.data_ptr(), d_scr.numel() * 8, ctypes.c_void_p(self._stream())),
-                self.lib, 'tpe_joint_run')
+        N.check(getattr(self.lib, fn)(ctypes.byref(a), d_rec.data_ptr(), d_cand.data_ptr() if return_cand else None,
+                                      d_l.data_ptr() if want_lg else None, d_g.data_ptr() if want_lg else None,
+                                      d_scr.data_ptr(), d_scr.numel() * 8, ctypes.c_void_p(self._stream())),
+                self.lib, fn)
         rec = d_rec[:n_ids * 19].cpu().numpy().view(N.JOINT_RECORD_DTYPE).copy()
         if not (return_cand or want_lg):
             return rec
@@ -1036,6 +1051,79 @@ class Engine(object):
             out.append(d_l[:n_ids * C].cpu().numpy().reshape(n_ids, C).copy())
             out.append(d_g[:n_ids * C].cpu().numpy().reshape(n_ids, C).copy())
         return tuple(out)
+
+    def run_joint_mixed(self, below, above, low, high, cats, ids, n_cand, seed, inject=None, return_cand=False,
+                        want_lg=False):
+        """One joint stage over a mixed group (tpe_joint_mixed_run,
+        include/tpe_hip.h "Mixed joint stage"): ``below`` / ``above`` = (w [K],
+        mu [K, Dc], sigma [K, Dc]) the continuous part as in ``run_joint`` (Dc
+        may be 0), ``cats`` one (x_below [K_below], x_above [K_above], p [U],
+        s_below, s_above) per discrete dimension: the components' categories
+        (-1: the prior row), the prior and the two smoothing masses.  Kernel
+        coordinates: the Dc continuous ones, then the categories as indices;
+        ``inject`` [C, Dc + Dk], candidates f32 [n_ids, C, Dc + Dk]."""
+        from . import joint as J
+        low, high = np.asarray(low, dtype=np.float64).reshape(-1), np.asarray(high, dtype=np.float64).reshape(-1)
+        Dc, Dk = len(low), len(cats)
+        D = Dc + Dk
+        if Dk == 0:
+            raise ValueError('joint stage: no discrete dimension, use run_joint')
+        ids, n_ids, C = self._joint_sizes(D, ids, n_cand)
+        sides = []
+        for i, side in enumerate((below, above)):
+            w = np.asarray(side[0], dtype=np.float64)
+            mu = np.asarray(side[1], dtype=np.float64).reshape(len(w), -1)
+            sigma = np.asarray(side[2], dtype=np.float64).reshape(len(w), -1)
+            if mu.shape != (len(w), Dc) or sigma.shape != mu.shape:
+                raise ValueError('joint stage: mixture shapes do not match %d dimensions' % Dc)
+            cols = [np.asarray(c[i], dtype=np.int64).reshape(-1) for c in cats]
+            if any(len(col) != len(w) for col in cols):
+                raise ValueError('joint stage: one category per component and discrete dimension')
+            sides.append((w, mu, sigma, np.stack(cols, axis=1)))
+        ps = [np.asarray(c[2], dtype=np.float64).reshape(-1) for c in cats]
+        total = 0
+        for d, p in enumerate(ps):
+            U = len(p)
+            if not 2 <= U <= N.JOINT_MAX_CATS:
+                raise ValueError('joint stage: %d categories, outside [2, %d]' % (U, N.JOINT_MAX_CATS))
+            if not (p > 0).all():
+                raise ValueError('joint stage: a prior probability of 0')
+            for w, mu, sigma, xc in sides:
+                if xc[:, d].min() < -1 or xc[:, d].max() >= U:
+                    raise ValueError('joint stage: a component category outside [-1, %d)' % U)
+            total += U
+        if total > N.JOINT_MAX_CAT_TOTAL:
+            raise ValueError('joint stage: %d categories in the group, at most %d' % (total, N.JOINT_MAX_CAT_TOTAL))
+        s_side = [np.array([float(c[3 + i]) for c in cats]) for i in (0, 1)]
+        if not all((s > 0).all() and np.isfinite(s).all() for s in s_side):
+            raise ValueError('joint stage: the smoothing masses must be positive')
+        up = self._joint_up
+        a = N.JointMixedArgs()
+        a.n_dims, a.n_cat, a.n_cand, a.n_ids, a.flags = Dc, Dk, C, n_ids, 0
+        a.k_below, a.k_above = len(sides[0][0]), len(sides[1][0])
+        a.stream_word, a.seed = N.JOINT_STREAM, int(seed) & 0xFFFFFFFFFFFFFFFF
+        for i, name in enumerate(('below', 'above')):
+            w, mu, sigma, xc = sides[i]
+            mu32, aa, c, base, cat32, miss, bonus = J.mixed_density_rows(w, mu, sigma, low, high, xc, ps, s_side[i])
+            setattr(a, name + '_mu', up(name + '_mu', mu32, torch.float32))
+            setattr(a, name + '_a', up(name + '_a', aa, torch.float32))
+            setattr(a, name + '_c', up(name + '_c', c, torch.float32))
+            setattr(a, name + '_base', base)
+            setattr(a, name + '_cat', up(name + '_cat', cat32, torch.float32))
+            setattr(a, name + '_miss', up(name + '_miss', miss, torch.float32))
+            setattr(a, name + '_bonus', up(name + '_bonus', bonus, torch.float32))
+        cum, rows, h, cat_cum = J.mixed_sampler_rows(sides[0][0], sides[0][1], sides[0][2], low, high, ps, s_side[0])
+        a.samp_cum, a.samp = up('cum', cum, torch.float64), up('samp', rows, torch.float32)
+        a.below_h, a.cat_cum = up('cat_h', h, torch.float64), up('cat_cum', cat_cum, torch.float64)
+        a.ids = up('ids', ids, torch.int64)
+        self._joint_inject(a, inject, C, D)
+        off = 0
+        for d in range(Dc):
+            a.low[d], a.high[d] = low[d], high[d]
+        for d, p in enumerate(ps):
+            a.cat_upper[d], a.cat_off[d] = len(p), off
+            off += len(p)
+        return self._joint_call('tpe_joint_mixed_run', a, n_ids, C, D, return_cand, want_lg)
 
     def device_tables(self):
         """(problems, comp32) of the last ``run`` as the device holds them after

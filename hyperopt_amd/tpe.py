@@ -35,6 +35,8 @@ Extensions over the reference (keyword-only, defaults keep its behaviour):
     (or the listed ones) are suggested as one vector — product-kernel
     mixtures over the group, whole-vector candidates, one argmax
     (joint.py, DESIGN.md "Joint TPE"); every other label as without it.
+    ``joint_discrete=True`` lets the group also hold unconditional randint /
+    categorical labels that gate no other label.
 
 ``linear_forgetting`` is accepted and, as in the reference, not used: the
 forgetting window is fixed at DEFAULT_LF=25 (tpe.py:27-29).
@@ -832,12 +834,14 @@ def suggest(new_ids, domain, trials, seed,
             gamma=_default_gamma,
             linear_forgetting=_default_linear_forgetting,
             sampler='philox', precision='fp32', device=None, shard=None, shard_ids=None, shard_labels=None,
-            shard_grid=None, joint=False):
+            shard_grid=None, joint=False, joint_discrete=False):
     new_ids = list(new_ids)
     if not new_ids:
         return []
-    if joint is not False and joint is not None:     # (argument errors first: no device use, no startup draw)
-        _joint_group(domain.table, joint, sampler, precision, (shard, shard_ids, shard_labels, shard_grid))
+    if (joint is not False and joint is not None) or joint_discrete:
+        # (argument errors first: no device use, no startup draw)
+        _joint_group(domain.table, joint, sampler, precision, (shard, shard_ids, shard_labels, shard_grid),
+                     joint_discrete)
     t0 = time.time()
     hist = _history.extract(domain, trials)
     if logger.isEnabledFor(logging.INFO):
@@ -851,7 +855,8 @@ def suggest(new_ids, domain, trials, seed,
     choices = suggest_choices(domain.table, hist, new_ids, seed, prior_weight=prior_weight,
                               n_EI_candidates=n_EI_candidates, gamma=gamma, sampler=sampler,
                               precision=precision, device=device, shard=shard, shard_ids=shard_ids,
-                              shard_labels=shard_labels, shard_grid=shard_grid, joint=joint)
+                              shard_labels=shard_labels, shard_grid=shard_grid, joint=joint,
+                              joint_discrete=joint_discrete)
     logger.info('tpe.suggest took %f seconds', time.time() - t0)
     return rand.docs_from_choices(new_ids, domain, trials, choices)
 
@@ -891,7 +896,7 @@ class ChoiceColumns(object):
 def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weight,
                     n_EI_candidates=_default_n_EI_candidates, gamma=_default_gamma,
                     sampler='philox', precision='fp32', device=None, shard=None, columns=False,
-                    shard_ids=None, shard_labels=None, shard_grid=None, joint=False):
+                    shard_ids=None, shard_labels=None, shard_grid=None, joint=False, joint_discrete=False):
     """The suggest core on a structure-of-arrays history (``history.History``):
     per new id a {label: value or None} dict.  ``suggest`` wraps it with the
     Trials document layout; columnar callers (and bench.py's large configs)
@@ -913,12 +918,21 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
     ``loguniform``, ``normal``, ``lognormal``), a list joins exactly those
     labels: their candidates are whole vectors scored under product-kernel
     mixtures, one argmax picks the vector (DESIGN.md "Joint TPE").  Every other
-    label is suggested exactly as without ``joint``."""
+    label is suggested exactly as without ``joint``.
+
+    ``joint_discrete=True`` (with ``joint``): the group may also hold discrete
+    labels — unconditional ``randint`` / ``categorical`` labels (``hp.choice``,
+    ``hp.pchoice``) that gate no other label, have 2 to 256 categories and
+    no prior probability 0.  ``joint=True`` then joins every such label too and
+    a list may name them; a named gate, conditional or quantised label raises
+    ValueError.  A group that ends up with no discrete label is the continuous
+    stage, byte for byte."""
     if sampler not in ('philox', 'replay'):
         raise ValueError("sampler must be 'philox' or 'replay'")
     group = None
-    if joint is not False and joint is not None:
-        group = _joint_group(table, joint, sampler, precision, (shard, shard_ids, shard_labels, shard_grid))
+    if (joint is not False and joint is not None) or joint_discrete:
+        group = _joint_group(table, joint, sampler, precision, (shard, shard_ids, shard_labels, shard_grid),
+                             joint_discrete)
     if sum(a is not None for a in (shard, shard_ids, shard_labels, shard_grid)) > 1:
         raise ValueError('shard, shard_ids, shard_labels and shard_grid are exclusive: one shard axis per suggest')
     if (shard_ids is not None or shard_labels is not None or shard_grid is not None) and sampler == 'replay':
@@ -937,9 +951,12 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
 TPE_JOINT_MAX_DIMS = N.JOINT_MAX_DIMS
 
 
-def _joint_group(table, joint, sampler, precision, shards):
-    """The ParamRows a ``joint`` argument joins, in table order; ValueError for
-    every combination the joint stage does not take.  Touches no device."""
+def _joint_group(table, joint, sampler, precision, shards, discrete=False):
+    """The ParamRows a ``joint`` argument joins, in table order (``discrete``:
+    the eligible discrete labels among them); ValueError for every combination
+    the joint stage does not take.  Touches no device."""
+    if discrete and (joint is False or joint is None):
+        raise ValueError('joint_discrete=True needs joint=True or joint=[labels]: it only widens what joint joins')
     if sampler == 'replay':
         raise ValueError("joint does not combine with sampler='replay': the joint candidates are Philox draws")
     if precision == 'fp64':
@@ -947,7 +964,7 @@ def _joint_group(table, joint, sampler, precision, shards):
     if any(a is not None for a in shards):
         raise ValueError('joint does not combine with a shard argument')
     if joint is True:
-        rows = [r for r in table.rows if _joint.eligible(r)]
+        rows = [r for r in table.rows if _joint.eligible(r) or (discrete and _joint.eligible_discrete(r, table))]
     else:
         if isinstance(joint, str):
             raise ValueError('joint must be True or a list of labels, not the string %r' % joint)
@@ -956,7 +973,11 @@ def _joint_group(table, joint, sampler, precision, shards):
             r = table.by_label.get(label)
             if r is None:
                 raise ValueError('joint: %r is not a label of the space' % (label,))
-            if not _joint.eligible(r):
+            if discrete and not _joint.eligible(r):
+                why = _joint.discrete_reason(r, table)
+                if why is not None:
+                    raise ValueError('joint: label %r is not eligible with joint_discrete=True: %s' % (label, why))
+            elif not _joint.eligible(r):
                 raise ValueError('joint: label %r is not eligible (%s%s): only unconditional uniform, loguniform, '
                                  'normal and lognormal labels are joined'
                                  % (label, r.dist, '' if all(p is None for p in r.parents) else ', conditional'))
@@ -966,6 +987,10 @@ def _joint_group(table, joint, sampler, precision, shards):
     if len(rows) > TPE_JOINT_MAX_DIMS:
         raise ValueError('joint joins at most TPE_JOINT_MAX_DIMS = %d labels, not %d: pass the labels to join as '
                          'joint=[...]' % (TPE_JOINT_MAX_DIMS, len(rows)))
+    n_cats = sum(int(r.args['upper']) for r in rows if r.categorical)
+    if n_cats > N.JOINT_MAX_CAT_TOTAL:
+        raise ValueError('joint joins discrete labels of at most TPE_JOINT_MAX_CAT_TOTAL = %d categories in all, not '
+                         '%d: pass the labels to join as joint=[...]' % (N.JOINT_MAX_CAT_TOTAL, n_cats))
     return rows
 
 
@@ -979,9 +1004,17 @@ def _suggest_joint(table, hist, new_ids, seed, prior_weight, n_EI_candidates, ga
     if len(cc) == 0:
         return cc if columns else []
     engine = get_engine(device, 'fp32')
-    model = _joint.fit_model(group, hist, _history.split_below(hist, gamma), prior_weight, DEFAULT_LF)
     ids = np.asarray(new_ids, dtype=np.int64).reshape(-1)
-    rec = engine.run_joint(model.below, model.above, model.low, model.high, ids, int(n_EI_candidates), seed)
+    drows = [r for r in group if r.categorical]
+    if drows:                                    # kernel coordinates: the continuous labels, then the discrete ones
+        group = [r for r in group if not r.categorical] + drows
+        model = _joint.fit_mixed_model(group[:len(group) - len(drows)], drows, hist,
+                                       _history.split_below(hist, gamma), prior_weight, DEFAULT_LF)
+        rec = engine.run_joint_mixed(model.below[:3], model.above[:3], model.low, model.high, model.cats(), ids,
+                                     int(n_EI_candidates), seed)
+    else:
+        model = _joint.fit_model(group, hist, _history.split_below(hist, gamma), prior_weight, DEFAULT_LF)
+        rec = engine.run_joint(model.below, model.above, model.low, model.high, ids, int(n_EI_candidates), seed)
     if (rec['global_idx'] < 0).any():
         raise RuntimeError('no joint candidate selected')
     vals = model.values(rec['z'][:, :len(group)])

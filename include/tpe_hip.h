@@ -1081,8 +1081,79 @@ int tpe_joint_run(const tpe_joint_args* args, tpe_joint_record* records, float* 
                   void* scratch, uint64_t scratch_bytes, void* stream);
 
 /* Profiling only (tools/joint_time.py), as tpe_report_profile: last_ms gets the
- * device times {chunk kernel, merge kernel} of the last profiled tpe_joint_run. */
+ * device times {chunk kernel, merge kernel} of the last profiled tpe_joint_run
+ * or tpe_joint_mixed_run. */
 int tpe_joint_profile(int32_t enable, double* last_ms);
+
+/* ------------------------------------------------------------------------
+ * Mixed joint stage (tpe_joint.hip; additive to ABI 24): a group of n_dims
+ * continuous labels (0 allowed) and n_cat discrete ones (randint /
+ * categorical), 1 <= n_dims + n_cat <= TPE_JOINT_MAX_DIMS.  Kernel coordinate
+ * order: the continuous labels, then the discrete ones; a category travels as
+ * its index (f32 in `cand` / `inject` / the component rows, double in
+ * tpe_joint_record.z).  Everything tpe_joint_args says holds for the fields of
+ * the same name (the rows of the continuous part: [K * n_dims]).
+ *
+ * Discrete dimension d has U_d = cat_upper[d] categories with prior p_d; its
+ * tables start at cat_off[d] in the flat [sum_d U_d] tables (packed in
+ * dimension order).  On a side with smoothing mass s_d a component k whose
+ * category is x_kd >= 0 has  P_kd(v) = (1[v = x_kd] + s_d p_d(v)) / (1 + s_d);
+ * a component whose category is -1 (the prior row) has P_kd(v) = p_d(v).
+ *   cat  [K * n_cat]  (f32) x_kd at [k * n_cat + d], -1: never matches
+ *   miss [total]      (f32) log2(s_d p_d(v) / (1 + s_d))
+ *   bonus[total]      (f32) log2(1 + 1 / (s_d p_d(v)))
+ *   c[K]              as tpe_joint_args, plus sum_d log2((1 + s_d) / s_d) over the
+ *                     dimensions where x_kd = -1, before the shift to max 0
+ *   log2 of a component's term at (z, v) = c_k - sum_cont(..) + sum_d [v_d = x_kd]
+ *   bonus_d(v_d); the candidate's sum_d miss_d(v_d) is added in f64 after the
+ *   sum over k.  A candidate's bonus_d(v_d) is read once per side, so a discrete
+ *   dimension costs one compare, one select and one add per (candidate, component).
+ *
+ * Sampling: word 0 picks the component k and word 1 + j serves kernel
+ * coordinate j, as in tpe_joint_run (so the continuous coordinates are those
+ * of a tpe_joint_run over the continuous part).  A discrete coordinate takes
+ * u = u01w(word): with h = below_h[d] = 1 / (1 + s_d) (h = 0 where x_kd = -1),
+ * u < h gives v = x_kd, else v = the first category with (u - h) / (1 - h) <
+ * cat_cum[cat_off[d] + v] (cat_cum: the cumsum of p_d, its last entry 1).
+ *
+ * tpe_joint_mixed_run returns TPE_E_ARG before any launch for everything
+ * tpe_joint_run checks (mu / a / samp rows may be NULL when n_dims = 0),
+ * n_cat < 0, n_dims < 0, n_dims + n_cat outside [1, TPE_JOINT_MAX_DIMS], a null
+ * table while n_cat > 0, a U_d outside [2, TPE_JOINT_MAX_CATS], a category
+ * total above TPE_JOINT_MAX_CAT_TOTAL, or a cat_off that leaves [0, total - U_d].
+ * n_cat = 0 is tpe_joint_run on the same fields.  With TPE_JOINT_INJECT a
+ * non-integral or out-of-range category in `inject` is the caller's error: the
+ * device does not check it and the scores of such a candidate are unspecified.
+ * tpe_joint_record, tpe_joint_scratch_bytes and tpe_joint_profile serve both.
+ * ---------------------------------------------------------------------- */
+#define TPE_JOINT_MAX_CATS 256          /* categories per discrete label */
+#define TPE_JOINT_MAX_CAT_TOTAL 1024    /* categories per group */
+typedef struct tpe_joint_mixed_args {
+  int32_t n_dims, n_cand, n_ids, flags;   /* n_dims: the continuous labels */
+  int32_t k_below, k_above;
+  uint32_t stream_word;
+  int32_t n_cat;                          /* the discrete labels */
+  uint64_t seed;
+  const float *below_mu, *below_a, *below_c;
+  const float *above_mu, *above_a, *above_c;
+  double below_base, above_base;
+  const double* samp_cum;
+  const float* samp;
+  const int64_t* ids;
+  const float* inject;                    /* device [n_cand * (n_dims + n_cat)] */
+  double low[TPE_JOINT_MAX_DIMS], high[TPE_JOINT_MAX_DIMS];
+  int32_t cat_upper[TPE_JOINT_MAX_DIMS];  /* U_d */
+  int32_t cat_off[TPE_JOINT_MAX_DIMS];    /* start of dimension d in the flat tables */
+  const float *below_cat, *above_cat;     /* device [K * n_cat] */
+  const float *below_miss, *below_bonus;  /* device [total] */
+  const float *above_miss, *above_bonus;
+  const double* below_h;                  /* device [n_cat] */
+  const double* cat_cum;                  /* device [total] */
+} tpe_joint_mixed_args;
+
+/* as tpe_joint_run; cand: device f32 [n_ids * n_cand * (n_dims + n_cat)] */
+int tpe_joint_mixed_run(const tpe_joint_mixed_args* args, tpe_joint_record* records, float* cand, double* l_out,
+                        double* g_out, void* scratch, uint64_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
  * Host phase clock of tpe_suggest_tree (tools/native_split.py).  While

@@ -1,6 +1,6 @@
 """Time the joint TPE stage against the host route.
 Usage: python tools/joint_time.py [--pairs 3] [--warmup 1] [--cand 1048576] [--history 10000]
-                                  [--host-cand N] [--out FILE]
+                                  [--host-cand N] [--out FILE] [--mixed]
 
 Workload: a flat space of 4 continuous labels (uniform, loguniform, normal,
 uniform), a seeded 10,000-trial history whose loss has an x0 * x1 term, one
@@ -22,7 +22,17 @@ host's, plus the two joint kernels' own device times (tpe_joint_profile), the ac
 the VALU issue peak (256 CU x 4 SIMD x 2.4 GHz / 2 = 1228.8 G
 wave-instructions/s) at the kernel's instruction count per
 (candidate, component): 3 D + 7 lane-operations, D = 4.  One JSON line goes to
-stdout and is appended to --out (default profiles/joint_time.jsonl)."""
+stdout and is appended to --out (default profiles/joint_time.jsonl).
+
+--mixed: the mixed stage instead of the host route.  A second flat space of 3
+continuous labels and one hp.choice of 4 (the same history size, the loss
+couples x0 with the choice) runs through Engine.run_joint_mixed; each round is
+one 4-continuous-label run, one 3 + 1 mixed run and one run over the mixed
+space's 3 continuous labels alone (k_joint_chunk<3>: what the mixed kernel's
+padded fourth continuous slot costs is read off against it), alternating in
+one process, each timed by the chunk kernel's own events (tpe_joint_profile).
+The line carries the three medians and the ratios mixed / continuous; --out defaults to
+profiles/joint_mixed_time.jsonl."""
 import argparse
 import ctypes
 import json
@@ -53,6 +63,102 @@ def make_history(n):
     return domain, H.History(tids, loss, {k: (tids, v) for k, v in cols.items()})
 
 
+def make_mixed_history(n):
+    from hyperopt_amd import base, history as H, hp
+    space = {'x0': hp.uniform('x0', -5, 5), 'x1': hp.loguniform('x1', -3, 2), 'x2': hp.normal('x2', 0, 2),
+             'c3': hp.choice('c3', [0, 1, 2, 3])}
+    domain = base.Domain(lambda d: 0.0, space)
+    rs = np.random.RandomState(SEED)
+    cols = {'x0': rs.uniform(-5, 5, n), 'x1': np.exp(rs.uniform(-3, 2, n)), 'x2': rs.normal(0, 2, n)}
+    c3 = rs.randint(4, size=n).astype(np.int64)
+    loss = (cols['x0'] - (2.0 * c3 - 3.0)) ** 2 + 0.1 * (np.log(cols['x1']) - 1.0) ** 2 + 0.1 * cols['x2'] ** 2 \
+        + 0.01 * rs.standard_normal(n)
+    tids = np.arange(n, dtype=np.int64)
+    obs = {k: (tids, v) for k, v in cols.items()}
+    obs['c3'] = (tids, c3)
+    return domain, H.History(tids, loss, obs)
+
+
+def main_mixed(args):
+    import torch
+    from hyperopt_amd import _native as N, history as H, joint as J
+    from hyperopt_amd.engine import get_engine
+
+    domain, hist = make_history(args.history)
+    rows = [r for r in domain.table.rows if J.eligible(r)]
+    cont = J.fit_model(rows, hist, H.split_below(hist, 0.25), 1.0)
+    mdomain, mhist = make_mixed_history(args.history)
+    mrows = [r for r in mdomain.table.rows if J.eligible(r)]
+    drows = [r for r in mdomain.table.rows if J.eligible_discrete(r, mdomain.table)]
+    mixed = J.fit_mixed_model(mrows, drows, mhist, H.split_below(mhist, 0.25), 1.0)
+    cont3 = J.fit_model(mrows, mhist, H.split_below(mhist, 0.25), 1.0)
+    eng = get_engine(None, 'fp32')
+    lib = eng.lib
+    C = args.cand
+    ids = np.array([args.history], dtype=np.int64)
+
+    def run_cont(**kw):
+        return eng.run_joint(cont.below, cont.above, cont.low, cont.high, ids, C, SEED, **kw)
+
+    def run_cont3(**kw):
+        return eng.run_joint(cont3.below, cont3.above, cont3.low, cont3.high, ids, C, SEED, **kw)
+
+    def run_mixed(**kw):
+        return eng.run_joint_mixed(mixed.below[:3], mixed.above[:3], mixed.low, mixed.high, mixed.cats(), ids, C,
+                                   SEED, **kw)
+
+    def kernel_ms(fn):
+        ms2 = (ctypes.c_double * 2)()
+        torch.cuda.synchronize()
+        N.check(lib.tpe_joint_profile(1, None), lib, 'tpe_joint_profile')
+        fn()
+        N.check(lib.tpe_joint_profile(0, ms2), lib, 'tpe_joint_profile')
+        return ms2[0], ms2[1]
+
+    for _ in range(args.warmup):
+        run_cont()
+        run_mixed()
+        run_cont3()
+    kc, km, k3 = [], [], []
+    for i in range(args.pairs):
+        kc.append(kernel_ms(run_cont))
+        km.append(kernel_ms(run_mixed))
+        k3.append(kernel_ms(run_cont3))
+        print('round %d: continuous %.3f ms, mixed %.3f ms, 3 continuous %.3f ms' % (i, kc[-1][0], km[-1][0],
+                                                                                   k3[-1][0]),
+              file=sys.stderr, flush=True)
+    # (untimed) the mixed stage's l and g of the first --host-cand candidates against the float64 model
+    n_host = min(C, args.host_cand or 4096)
+    _, cand, dl, dg = run_mixed(return_cand=True, want_lg=True)
+    z, v = cand[0, :n_host, :len(mrows)].astype(np.float64), cand[0, :n_host, len(mrows):].astype(np.int64)
+    err = 0.0
+    for side, s, dev in ((mixed.below, mixed.s_below, dl), (mixed.above, mixed.s_above, dg)):
+        ref = J.mixed_lpdf_numpy(z, v, side[0], side[1], side[2], mixed.low, mixed.high, side[3], mixed.ps, s)
+        err = max(err, float(np.max(np.abs(dev[0, :n_host] - ref) / np.maximum(1.0, np.abs(ref)))) / 1e-5)
+    med = lambda x: float(np.median(x))   # noqa: E731
+    c1, m1, t1 = med([a for a, _ in kc]), med([a for a, _ in km]), med([a for a, _ in k3])
+    line = dict(tool='joint_time --mixed', history=args.history, n_cand=C, pairs=args.pairs,
+                continuous=dict(labels=[r.label for r in rows], n_dims=len(rows), k_below=len(cont.below[0]),
+                                k_above=len(cont.above[0]), k_joint_chunk_ms=c1,
+                                k_joint_chunk_ms_all=[a for a, _ in kc], k_joint_merge_ms=med([b for _, b in kc])),
+                mixed=dict(labels=[r.label for r in mrows] + [r.label for r in drows], n_dims=len(mrows),
+                           n_cat=len(drows), categories=[len(p) for p in mixed.ps], k_below=len(mixed.below[0]),
+                           k_above=len(mixed.above[0]), k_joint_mixed_chunk_ms=m1,
+                           k_joint_mixed_chunk_ms_all=[a for a, _ in km], k_joint_merge_ms=med([b for _, b in km]),
+                           lpdf_err_over_tol=err, host_cand=n_host),
+                continuous3=dict(labels=[r.label for r in mrows], n_dims=len(mrows), k_joint_chunk_ms=t1,
+                                 k_joint_chunk_ms_all=[a for a, _ in k3]),
+                ratio_mixed_over_continuous=m1 / c1 if c1 > 0 else None,
+                ratio_mixed_over_continuous3=m1 / t1 if t1 > 0 else None, gpu=torch.cuda.get_device_name(0))
+    text = json.dumps(line)
+    print(text)
+    out = args.out or os.path.join(ROOT, 'profiles', 'joint_mixed_time.jsonl')
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, 'a') as f:
+        f.write(text + '\n')
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--pairs', type=int, default=3)
@@ -60,8 +166,12 @@ def main():
     ap.add_argument('--cand', type=int, default=1 << 20)
     ap.add_argument('--history', type=int, default=10000)
     ap.add_argument('--host-cand', type=int, default=None)
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'joint_time.jsonl'))
+    ap.add_argument('--mixed', action='store_true')
+    ap.add_argument('--out', default=None)
     args = ap.parse_args()
+    if args.mixed:
+        return main_mixed(args)
+    args.out = args.out or os.path.join(ROOT, 'profiles', 'joint_time.jsonl')
 
     import torch
     from hyperopt_amd import _native as N, history as H, joint as J
