@@ -81,6 +81,12 @@ JOINT_RECORD_DTYPE = np.dtype([('global_idx', '<i8'), ('l', '<f8'), ('g', '<f8')
 assert JOINT_RECORD_DTYPE.itemsize == 152
 JOINT_MAX_CATS = 256           # TPE_JOINT_MAX_CATS: categories of one joined discrete label
 JOINT_MAX_CAT_TOTAL = 1024     # TPE_JOINT_MAX_CAT_TOTAL: categories of a joint group
+JOINT_MAX_QUANT = 4            # TPE_JOINT_MAX_QUANT: quantised labels of a joint group
+JOINT_MAX_LATTICE = 256        # TPE_JOINT_MAX_LATTICE: lattice values of one joined quantised label
+JOINT_MAX_LATTICE_TOTAL = 512  # TPE_JOINT_MAX_LATTICE_TOTAL: lattice values of a joint group
+JOINT_QFLOOR = -4096.0         # TPE_JOINT_QFLOOR: the smallest stored log2 P_kd(i)
+JOINT_QUANT_MAX_CONT = 8       # continuous / discrete labels beside a quantised one
+JOINT_QUANT_MAX_DISC = 4
 
 
 class Batch(ctypes.Structure):
@@ -151,6 +157,18 @@ class JointMixedArgs(ctypes.Structure):
         ('below_miss', ctypes.c_void_p), ('below_bonus', ctypes.c_void_p),
         ('above_miss', ctypes.c_void_p), ('above_bonus', ctypes.c_void_p),
         ('below_h', ctypes.c_void_p), ('cat_cum', ctypes.c_void_p),
+    ]
+
+
+class JointQuantArgs(ctypes.Structure):
+    """tpe_joint_quant_args: one tpe_joint_quant_run (tpe_joint_mixed_args' fields, then the quantised labels')."""
+    _fields_ = JointMixedArgs._fields_ + [
+        ('n_quant', ctypes.c_int32), ('n_edges', ctypes.c_int32),
+        ('quant_v', ctypes.c_int32 * JOINT_MAX_QUANT), ('quant_edge_off', ctypes.c_int32 * JOINT_MAX_QUANT),
+        ('quant_edges', ctypes.c_void_p),
+        ('below_qmu', ctypes.c_void_p), ('below_qsigma', ctypes.c_void_p),
+        ('above_qmu', ctypes.c_void_p), ('above_qsigma', ctypes.c_void_p),
+        ('quant_samp', ctypes.c_void_p), ('quant_table', ctypes.c_void_p), ('quant_table_bytes', ctypes.c_uint64),
     ]
 
 
@@ -297,7 +315,7 @@ EXPORTS = ('tpe_abi_version', 'tpe_last_error', 'tpe_device_count', 'tpe_tile_si
            'tpe_host_threads', 'tpe_host_phases', 'tpe_exchange_allgather', 'tpe_debug_fast_lg',
            'tpe_collectives_issued', 'tpe_scatter_f64', 'tpe_move_ranges', 'tpe_report_scratch_bytes', 'tpe_report',
            'tpe_report_profile', 'tpe_joint_scratch_bytes', 'tpe_joint_run', 'tpe_joint_profile',
-           'tpe_joint_mixed_run')
+           'tpe_joint_mixed_run', 'tpe_joint_quant_table_bytes', 'tpe_joint_quant_run', 'tpe_joint_quant_profile')
 
 # host phases of tpe_suggest_tree (tpe_host_phases order)
 PHASES = ('prefit', 'pack', 'launched', 'synced', 'level', 'return', 'recs')
@@ -414,6 +432,12 @@ def load(path=LIB_PATH):
     lib.tpe_joint_run.restype = ctypes.c_int
     lib.tpe_joint_mixed_run.argtypes = [ctypes.POINTER(JointMixedArgs), P, P, P, P, P, ctypes.c_uint64, P]
     lib.tpe_joint_mixed_run.restype = ctypes.c_int
+    lib.tpe_joint_quant_table_bytes.argtypes = [I32, I32, I32, ctypes.POINTER(ctypes.c_uint64)]
+    lib.tpe_joint_quant_table_bytes.restype = ctypes.c_int
+    lib.tpe_joint_quant_run.argtypes = [ctypes.POINTER(JointQuantArgs), P, P, P, P, P, ctypes.c_uint64, P]
+    lib.tpe_joint_quant_run.restype = ctypes.c_int
+    lib.tpe_joint_quant_profile.argtypes = [P]
+    lib.tpe_joint_quant_profile.restype = ctypes.c_int
     lib.tpe_joint_profile.argtypes = [I32, P]
     lib.tpe_joint_profile.restype = ctypes.c_int
     lib.tpe_level_profile.argtypes = [ctypes.c_int32]

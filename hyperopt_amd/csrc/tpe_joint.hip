@@ -15,13 +15,21 @@
 // k_joint_mixed_chunk  the same for a group that also holds discrete labels: a
 //                category costs one compare, one select and one add per
 //                (candidate, component).
+// k_joint_qtable  per side of a group with quantised labels: log2 of every
+//                (component, lattice value) bin mass in f64, stored as f32.
+// k_joint_quant_chunk  k_joint_mixed_chunk for such a group: the table streams
+//                through LDS as [lattice value][component], and a quantised
+//                dimension costs one read at the candidate's own lattice index
+//                (four components a 16-byte read) and one add.
 // k_joint_merge  one wave per new id: the chunk winners in index order.
 // Every reduction has a fixed shape and there are no atomics: the output bytes
 // are a function of the input bytes.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <math.h>
+#include <stddef.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "../../include/tpe_hip.h"
 #include "tpe_device_rng.h"
@@ -515,6 +523,389 @@ void launch_mixed_k(const MixedK& k, unsigned blocks, hipStream_t stream, bool t
   else if constexpr (CP < 16) launch_mixed<CP, 16>(k, blocks, stream, timed);
 }
 
+// -------------------------------------------------------- quantised groups
+// Dc continuous and Dk discrete coordinates (as above) followed by Dq
+// quantised ones; a quantised coordinate is its lattice index as an f32
+// (include/tpe_hip.h "Quantised joint stage").
+constexpr int kQTileBytes = 41 * 1024;      // the table tile's share of the LDS (dynamic)
+constexpr double kQFloor = (double)TPE_JOINT_QFLOOR;
+
+struct QuantK {
+  MixedK m;                         // m.j.D = Dc, m.Dk = Dk; cand / inject rows are [Dc + Dk + Dq]
+  int Dq, tile, stride, total;      // components per tile, floats per lattice value in the tile, sum V_d
+  int V[TPE_JOINT_MAX_QUANT], voff[TPE_JOINT_MAX_QUANT], eoff[TPE_JOINT_MAX_QUANT];
+  float qlo[TPE_JOINT_MAX_QUANT], qhi[TPE_JOINT_MAX_QUANT];
+  const double* edges;
+  const float* qsamp;
+  const float *bT, *aT;             // [total][K] of a side
+};
+
+// One side's table: thread k of block row d walks the V_d + 1 edges of its
+// (component, dimension) once, one erfc per edge (the smaller tail), shared by
+// the two bins that meet there.
+struct QTabK {
+  int K, Dq;
+  int V[TPE_JOINT_MAX_QUANT], voff[TPE_JOINT_MAX_QUANT], eoff[TPE_JOINT_MAX_QUANT];
+  const double *mu, *sigma, *edges;
+  float* T;
+};
+
+// The smaller tail of a standardised edge, u = |e - mu| / (sigma sqrt 2).  Beyond
+// kQTailMax the tail (below 2^-1018) counts as exactly 0: float64 would go
+// subnormal there, and the result must not depend on how a libm rounds them.
+constexpr double kQTailMax = 26.5;
+__device__ __forceinline__ double small_tail(double u) { return u > kQTailMax ? 0.0 : 0.5 * erfc(u); }
+
+// Phi(tb) - Phi(ta) of ta < tb from the smaller tails sa, sb
+__device__ __forceinline__ double bin_mass(double ta, double sa, double tb, double sb) {
+  return tb <= 0.0 ? sb - sa : ta >= 0.0 ? sa - sb : 1.0 - sa - sb;
+}
+
+__global__ __launch_bounds__(kThreads) void k_joint_qtable(const QTabK p) {
+  const int k = blockIdx.x * kThreads + threadIdx.x, d = blockIdx.y;
+  if (k >= p.K) return;
+  int V = 2, voff = 0, eoff = 0;            // (kernel-argument arrays: constant indices only)
+#pragma unroll
+  for (int f = 0; f < TPE_JOINT_MAX_QUANT; ++f)
+    if (f == d) { V = p.V[f]; voff = p.voff[f]; eoff = p.eoff[f]; }
+  const double m = p.mu[(int64_t)k * p.Dq + d], s = p.sigma[(int64_t)k * p.Dq + d];
+  const double* e = p.edges + eoff;
+  const double r = 0.70710678118654752440 / s;
+  const double t0 = (e[0] - m) * r, tv = (e[V] - m) * r;
+  const double s0 = small_tail(fabs(t0)), sv = small_tail(fabs(tv));
+  const double lmass = log2(bin_mass(t0, s0, tv, sv));
+  float* out = p.T + (int64_t)voff * p.K + k;
+  double ta = t0, sa = s0;
+  for (int i = 0; i < V; ++i) {
+    const double tb = i + 1 < V ? (e[i + 1] - m) * r : tv;
+    const double sb = i + 1 < V ? small_tail(fabs(tb)) : sv;
+    double v = log2(bin_mass(ta, sa, tb, sb)) - lmass;
+    if (!(v >= kQFloor)) v = kQFloor;       // -inf (a far bin's mass is 0) and NaN included
+    out[(int64_t)i * p.K] = (float)v;
+    ta = tb; sa = sb;
+  }
+}
+
+// score_side_mixed with QP quantised dimensions.  The side's table streams
+// through the dynamic LDS tile qt, laid out [lattice value][component] with
+// p.stride floats a value (p.tile + 4: consecutive values start 4 banks apart,
+// and stride / 4 is odd, so 16 lanes with 16 consecutive values hit 16 different
+// bank quads); row p.total is all zeros (padded slots).  A lane fetches four
+// consecutive components of its own lattice value with one 16-byte read; qo is
+// that value's row offset in floats.  Components are taken four at a time: the
+// tile's tail is padded with c = -3e38 (such a term adds 2^-inf = 0).
+template <int CP, int KP, int QP>
+__device__ __forceinline__ void score_side_quant(const float* __restrict__ mu, const float* __restrict__ a,
+                                                 const float* __restrict__ c, const float* __restrict__ cat,
+                                                 const float* __restrict__ miss, const float* __restrict__ bonus,
+                                                 const float* __restrict__ T, int K, const QuantK& p,
+                                                 const float (&z)[kR][CP + KP + QP], const int (&qo)[kR][QP],
+                                                 float* __restrict__ rows, float* __restrict__ cl,
+                                                 float* __restrict__ qt, double (&out)[kR]) {
+  constexpr int S = 2 * CP + KP, KPa = KP > 0 ? KP : 1;
+  const int Dc = p.m.j.D, Dk = p.m.Dk, tile = p.tile, stride = p.stride;
+  float m[kR], s[kR], nb[kR][KPa];
+#pragma unroll
+  for (int r = 0; r < kR; ++r) {
+    m[r] = -3.0e38f;
+    s[r] = 0.f;
+#pragma unroll
+    for (int d = 0; d < KP; ++d)
+      nb[r][d] = d < Dk ? -bonus[p.m.off[d] + cat_index(z[r][CP + d], p.m.U[d])] : 0.f;
+  }
+  for (int k0 = 0; k0 < K; k0 += tile) {
+    const int nk = min(tile, K - k0), nk4 = (nk + 3) & ~3;
+    __syncthreads();                       // the previous tile (or side) is read
+    if constexpr (CP > 0)
+      for (int e = threadIdx.x; e < nk4 * CP; e += kThreads) {
+        const int kk = e / CP, d = e % CP;
+        const bool in = d < Dc && kk < nk;   // padded dimensions and components: a = 0 adds nothing
+        const int64_t src = (int64_t)(k0 + kk) * Dc + d;
+        rows[kk * S + d] = in ? mu[src] : 0.f;
+        rows[kk * S + CP + d] = in ? a[src] : 0.f;
+      }
+    if constexpr (KP > 0)
+      for (int e = threadIdx.x; e < nk4 * KP; e += kThreads) {
+        const int kk = e / KP, d = e % KP;   // padded: category -1 never matches
+        rows[kk * S + 2 * CP + d] = (d < Dk && kk < nk) ? cat[(int64_t)(k0 + kk) * Dk + d] : -1.f;
+      }
+    for (int e = threadIdx.x; e < nk4; e += kThreads) cl[e] = e < nk ? c[k0 + e] : -3.0e38f;
+    for (int e = threadIdx.x; e < p.total * tile; e += kThreads) {
+      const int b = e / tile, kk = e - b * tile;         // a run over k of one lattice value: coalesced
+      if (kk < nk4) qt[b * stride + kk] = kk < nk ? T[(int64_t)b * K + k0 + kk] : 0.f;
+    }
+    __syncthreads();
+    for (int k4 = 0; k4 < nk4; k4 += 4) {
+      float tq[kR][QP][4];
+#pragma unroll
+      for (int r = 0; r < kR; ++r)
+#pragma unroll
+        for (int d = 0; d < QP; ++d) {
+          const float4 v = *reinterpret_cast<const float4*>(qt + qo[r][d] + k4);
+          tq[r][d][0] = v.x; tq[r][d][1] = v.y; tq[r][d][2] = v.z; tq[r][d][3] = v.w;
+        }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int kk = k4 + j;
+        float rm[CP + 1], ra[CP + 1], rc[KPa];
+        if constexpr (S > 0) {
+          const float* row = rows + kk * S;
+#pragma unroll
+          for (int d = 0; d < CP; ++d) { rm[d] = row[d]; ra[d] = row[CP + d]; }
+#pragma unroll
+          for (int d = 0; d < KP; ++d) rc[d] = row[2 * CP + d];
+        }
+        const float ck = cl[kk];
+#pragma unroll
+        for (int r = 0; r < kR; ++r) {
+          float acc = 0.f;
+#pragma unroll
+          for (int d = 0; d < CP; ++d) {
+            const float u = (z[r][d] - rm[d]) * ra[d];
+            acc = __builtin_fmaf(u, u, acc);
+          }
+#pragma unroll
+          for (int d = 0; d < KP; ++d) acc += z[r][CP + d] == rc[d] ? nb[r][d] : 0.f;
+#pragma unroll
+          for (int d = 0; d < QP; ++d) acc -= tq[r][d][j];
+          const float t = ck - acc;
+          const float dl = t - m[r];
+          const float e2 = __builtin_amdgcn_exp2f(-__builtin_fabsf(dl));
+          s[r] = dl > 0.f ? __builtin_fmaf(s[r], e2, 1.f) : s[r] + e2;
+          m[r] = fmaxf(m[r], t);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < kR; ++r) {
+    double M = 0.0;
+#pragma unroll
+    for (int d = 0; d < KP; ++d)
+      if (d < Dk) M += (double)miss[p.m.off[d] + cat_index(z[r][CP + d], p.m.U[d])];
+    out[r] = (double)m[r] + log2((double)s[r]) + M;
+  }
+}
+
+// k_joint_mixed_chunk for a group with quantised labels: CP / KP / QP the padded
+// continuous / discrete / quantised counts (CP = 0, KP = 0 allowed).  z[r] holds
+// the continuous coordinates at [0, CP), the categories at [CP, CP + KP) and the
+// lattice indices at [CP + KP, CP + KP + QP).
+template <int CP, int KP, int QP>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, (CP + KP + QP >= 12 ? 2 : 8))))
+void k_joint_quant_chunk(const QuantK p) {
+  constexpr int ZP = CP + KP + QP, S = 2 * CP + KP;
+  __shared__ __attribute__((aligned(16))) float rows[kTileK * (S > 0 ? S : 1)];
+  __shared__ float cl[kTileK];
+  __shared__ Pick slot[kThreads / 64];
+  extern __shared__ __attribute__((aligned(16))) float qt[];     // [(total + 1) * stride]
+  const JointK& q = p.m.j;
+  const int t = threadIdx.x, Dc = q.D, Dk = p.m.Dk, Dq = p.Dq, D = Dc + Dk + Dq;
+  const int id = blockIdx.x / q.n_chunks, chunk = blockIdx.x % q.n_chunks;
+  const int first = chunk * TPE_JOINT_CHUNK;
+
+  for (int e = t; e < p.stride; e += kThreads) qt[p.total * p.stride + e] = 0.f;   // the padded slots' row
+
+  float z[kR][ZP];
+#pragma unroll
+  for (int r = 0; r < kR; ++r) {
+#pragma unroll
+    for (int d = 0; d < ZP; ++d) z[r][d] = 0.f;
+    const int i = first + r * kThreads + t;
+    if (i >= q.C) continue;
+    if (q.inject) {
+#pragma unroll
+      for (int d = 0; d < CP; ++d)
+        if (d < Dc) z[r][d] = q.inj[(int64_t)i * D + d];
+#pragma unroll
+      for (int d = 0; d < KP; ++d)
+        if (d < Dk) z[r][CP + d] = q.inj[(int64_t)i * D + Dc + d];
+#pragma unroll
+      for (int d = 0; d < QP; ++d)
+        if (d < Dq) z[r][CP + KP + d] = q.inj[(int64_t)i * D + Dc + Dk + d];
+      continue;
+    }
+    const uint32_t c3 = (uint32_t)q.ids[id];
+    U4 w = philox4x32_10((uint32_t)i, 0u, q.stream_word, c3, q.key0, q.key1);
+    const double us = u01w(w.x);
+    int lo = 0, hi = q.kb - 1;             // first k with us < cum[k]
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (us < q.cum[mid]) hi = mid; else lo = mid + 1; }
+    const int comp = lo;
+    // One loop over the kernel coordinates, not unrolled, word 1 + j for
+    // coordinate j; a continuous or discrete one is k_joint_mixed_chunk's draw,
+    // operation for operation, and a quantised one the continuous draw binned.
+    for (int j = 0; j < D; ++j) {
+      const int wi = j + 1;
+      if ((wi & 3) == 0) w = philox4x32_10((uint32_t)i, (uint32_t)(wi >> 2), q.stream_word, c3, q.key0, q.key1);
+      const uint32_t word = (wi & 3) == 0 ? w.x : (wi & 3) == 1 ? w.y : (wi & 3) == 2 ? w.z : w.w;
+      float x;
+      if (j < Dc || j >= Dc + Dk) {
+        const bool quant = j >= Dc;
+        const int d = quant ? j - Dc - Dk : j;
+        const float* sr = quant ? p.qsamp + ((int64_t)comp * Dq + d) * 5 : q.samp + ((int64_t)comp * Dc + d) * 5;
+        const float pr = sr[2] + u01f(word) * (sr[3] - sr[2]);
+        float zz = ndtri_f32(pr);
+        if (sr[4] != 0.f) zz = -zz;
+        x = sr[0] + sr[1] * zz;
+        if (!(x == x)) x = sr[0];
+        float blo = 0.f, bhi = 0.f;                       // (kernel-argument arrays: constant indices only)
+        if (!quant) {
+#pragma unroll
+          for (int f = 0; f < CP; ++f)
+            if (f == d) { blo = q.lo[f]; bhi = q.hi[f]; }
+        } else {
+#pragma unroll
+          for (int f = 0; f < QP; ++f)
+            if (f == d) { blo = p.qlo[f]; bhi = p.qhi[f]; }
+        }
+        x = fminf(fmaxf(x, blo), bhi);                    // low <= z < high
+        if (quant) {
+          int V = 2, eoff = 0;
+#pragma unroll
+          for (int f = 0; f < QP; ++f)
+            if (f == d) { V = p.V[f]; eoff = p.eoff[f]; }
+          const double* e = p.edges + eoff + 1;           // the interior edges e_1 .. e_{V-1}
+          const double zd = (double)x;
+          int a = 0, b = V - 1;                           // how many of them are <= z
+          while (a < b) { const int mid = (a + b) >> 1; if (e[mid] <= zd) a = mid + 1; else b = mid; }
+          x = (float)a;
+        }
+      } else {
+        if constexpr (KP > 0) {
+          const int d = j - Dc;
+          const double u = u01w(word);
+          x = p.m.bcat[(int64_t)comp * Dk + d];             // the component's category, -1: the prior row
+          const double h = x >= 0.f ? p.m.bh[d] : 0.0;
+          if (!(u < h)) {
+            const double u2 = (u - h) / (1.0 - h);
+            int off = 0, U = 1;
+#pragma unroll
+            for (int f = 0; f < KP; ++f)
+              if (f == d) { off = p.m.off[f]; U = p.m.U[f]; }
+            const double* cum = p.m.ccum + off;
+            int a = 0, b = U - 1;                           // first category with u2 < cum[v]
+            while (a < b) { const int mid = (a + b) >> 1; if (u2 < cum[mid]) b = mid; else a = mid + 1; }
+            x = (float)a;
+          }
+        } else {
+          x = 0.f;
+        }
+      }
+      const int e = j < Dc ? j : j < Dc + Dk ? CP + (j - Dc) : CP + KP + (j - Dc - Dk);
+#pragma unroll
+      for (int f = 0; f < ZP; ++f)
+        if (f == e) z[r][f] = x;
+    }
+  }
+
+  // the lattice value's row in the tile (kept inside the table); a padded slot reads the zero row
+  int qo[kR][QP];
+#pragma unroll
+  for (int r = 0; r < kR; ++r)
+#pragma unroll
+    for (int d = 0; d < QP; ++d)
+      qo[r][d] = (d < Dq ? p.voff[d] + cat_index(z[r][CP + KP + d], p.V[d]) : p.total) * p.stride;
+
+  double l2[kR], g2[kR];
+  score_side_quant<CP, KP, QP>(q.bmu, q.ba, q.bc, p.m.bcat, p.m.bmiss, p.m.bbonus, p.bT, q.kb, p, z, qo, rows, cl, qt,
+                               l2);
+  score_side_quant<CP, KP, QP>(q.amu, q.aa, q.ac, p.m.acat, p.m.amiss, p.m.abonus, p.aT, q.ka, p, z, qo, rows, cl, qt,
+                               g2);
+
+  Pick best{0, 0};
+  double lv[kR], gv[kR];
+#pragma unroll
+  for (int r = 0; r < kR; ++r) {
+    const int i = first + r * kThreads + t;
+    lv[r] = l2[r] * kLn2 + q.bbase;
+    gv[r] = g2[r] * kLn2 + q.abase;
+    if (i >= q.C) continue;
+    const int64_t o = (int64_t)id * q.C + i;
+    if (q.l_out) q.l_out[o] = lv[r];
+    if (q.g_out) q.g_out[o] = gv[r];
+    if (q.cand) {
+#pragma unroll
+      for (int d = 0; d < CP; ++d)
+        if (d < Dc) q.cand[o * D + d] = z[r][d];
+#pragma unroll
+      for (int d = 0; d < KP; ++d)
+        if (d < Dk) q.cand[o * D + Dc + d] = z[r][CP + d];
+#pragma unroll
+      for (int d = 0; d < QP; ++d)
+        if (d < Dq) q.cand[o * D + Dc + Dk + d] = z[r][CP + KP + d];
+    }
+    const uint64_t key = score_key(lv[r] - gv[r]);
+    if (key > best.key) best = Pick{key, (int64_t)i};   // ascending index: strict > keeps the first of a tie
+  }
+  Pick w = wave_best(best);
+  if ((t & 63) == 0) slot[t >> 6] = w;
+  __syncthreads();
+  w = slot[0];
+#pragma unroll
+  for (int s = 1; s < kThreads / 64; ++s)
+    if (beats(slot[s], w)) w = slot[s];
+
+  tpe_joint_record* rec = q.chunk_rec + blockIdx.x;
+  if (w.key == 0) {
+    if (t == 0) rec->global_idx = -1;
+    return;
+  }
+  const int off = (int)(w.idx - first);
+  if (t != off % kThreads) return;
+  const int wr = off / kThreads;
+#pragma unroll
+  for (int r = 0; r < kR; ++r) {
+    if (r != wr) continue;
+    rec->global_idx = w.idx;
+    rec->l = lv[r];
+    rec->g = gv[r];
+    // kernel coordinate order: continuous, categories, lattice indices, then zeros
+#pragma unroll
+    for (int d = 0; d < TPE_JOINT_MAX_DIMS; ++d)
+      if (d >= D) rec->z[d] = 0.0;
+#pragma unroll
+    for (int d = 0; d < CP; ++d)
+      if (d < Dc) rec->z[d] = (double)z[r][d];
+#pragma unroll
+    for (int d = 0; d < KP; ++d)
+      if (d < Dk) rec->z[Dc + d] = (double)z[r][CP + d];
+#pragma unroll
+    for (int d = 0; d < QP; ++d)
+      if (d < Dq) rec->z[Dc + Dk + d] = (double)z[r][CP + KP + d];
+  }
+}
+
+// start / stop events around the two table launches (profiling only)
+struct {
+  int valid;
+  hipEvent_t ev[2];
+} g_qprof = {0, {nullptr, nullptr}};
+
+template <int CP, int KP, int QP>
+void launch_quant(const QuantK& k, unsigned blocks, unsigned lds, hipStream_t stream, bool timed) {
+  if (timed)
+    hipExtLaunchKernelGGL((k_joint_quant_chunk<CP, KP, QP>), dim3(blocks), dim3(kThreads), lds, stream, g_prof.ev[0],
+                          g_prof.ev[1], 0u, k);
+  else
+    hipLaunchKernelGGL((k_joint_quant_chunk<CP, KP, QP>), dim3(blocks), dim3(kThreads), lds, stream, k);
+}
+
+// padded counts: CP in {0, 2, 4, 8}, KP in {0, 1, 2, 4}, QP in {1, 2, 4}: 48 instantiations
+template <int CP, int KP>
+void launch_quant_q(const QuantK& k, unsigned blocks, unsigned lds, hipStream_t stream, bool timed) {
+  if (k.Dq == 1) launch_quant<CP, KP, 1>(k, blocks, lds, stream, timed);
+  else if (k.Dq == 2) launch_quant<CP, KP, 2>(k, blocks, lds, stream, timed);
+  else launch_quant<CP, KP, 4>(k, blocks, lds, stream, timed);
+}
+template <int CP>
+void launch_quant_k(const QuantK& k, unsigned blocks, unsigned lds, hipStream_t stream, bool timed) {
+  const int Dk = k.m.Dk;
+  if (Dk == 0) launch_quant_q<CP, 0>(k, blocks, lds, stream, timed);
+  else if (Dk == 1) launch_quant_q<CP, 1>(k, blocks, lds, stream, timed);
+  else if (Dk == 2) launch_quant_q<CP, 2>(k, blocks, lds, stream, timed);
+  else launch_quant_q<CP, 4>(k, blocks, lds, stream, timed);
+}
+
 }  // namespace
 
 extern "C" {
@@ -698,6 +1089,183 @@ int tpe_joint_mixed_run(const tpe_joint_mixed_args* a, tpe_joint_record* records
   else if (Dc <= 4) launch_mixed_k<4>(m, nb, s, timed);
   else if (Dc <= 8) launch_mixed_k<8>(m, nb, s, timed);
   else launch_mixed_k<16>(m, nb, s, timed);
+  if (timed) {
+    hipExtLaunchKernelGGL(k_joint_merge, dim3((unsigned)a->n_ids), dim3(64), 0u, s, g_prof.ev[2], g_prof.ev[3], 0u,
+                          (const tpe_joint_record*)scratch, (int)n_chunks, records);
+    g_prof.valid = 1;
+  } else {
+    hipLaunchKernelGGL(k_joint_merge, dim3((unsigned)a->n_ids), dim3(64), 0, s, (const tpe_joint_record*)scratch,
+                       (int)n_chunks, records);
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
+  return TPE_OK;
+}
+
+int tpe_joint_quant_table_bytes(int32_t k_below, int32_t k_above, int32_t total_bins, uint64_t* bytes) {
+  if (!bytes || k_below < 1 || k_above < 1 || total_bins < 1)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_table_bytes: bad arguments");
+  *bytes = ((uint64_t)k_below + (uint64_t)k_above) * (uint64_t)total_bins * sizeof(float);
+  return TPE_OK;
+}
+
+int tpe_joint_quant_profile(double* table_ms) {
+  if (!table_ms || !g_qprof.valid)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_profile: no profiled tpe_joint_quant_run to read");
+  float ms = 0.f;
+  hipError_t e = hipEventSynchronize(g_qprof.ev[1]);
+  if (e == hipSuccess) e = hipEventElapsedTime(&ms, g_qprof.ev[0], g_qprof.ev[1]);
+  if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
+  *table_ms = (double)ms;
+  return TPE_OK;
+}
+
+int tpe_joint_quant_run(const tpe_joint_quant_args* a, tpe_joint_record* records, float* cand, double* l_out,
+                        double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
+  static_assert(offsetof(tpe_joint_quant_args, n_quant) == sizeof(tpe_joint_mixed_args), "the shared fields");
+  static_assert(offsetof(tpe_joint_quant_args, cat_cum) == offsetof(tpe_joint_mixed_args, cat_cum), "the shared fields");
+  if (!a) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: null args");
+  if (a->n_quant < 0 || a->n_quant > TPE_JOINT_MAX_QUANT)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: n_quant outside [0, TPE_JOINT_MAX_QUANT]");
+  if (a->n_quant == 0) {                    // no quantised label: the mixed stage, the same bytes
+    tpe_joint_mixed_args m;
+    memcpy(&m, a, sizeof m);
+    return tpe_joint_mixed_run(&m, records, cand, l_out, g_out, scratch, scratch_bytes, stream);
+  }
+  const int Dc = a->n_dims, Dk = a->n_cat, Dq = a->n_quant;
+  if (Dk < 0) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: n_cat < 0");
+  if (Dc < 0 || Dc > TPE_JOINT_MAX_DIMS || Dk > TPE_JOINT_MAX_DIMS || Dc + Dk + Dq > TPE_JOINT_MAX_DIMS)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: n_dims + n_cat + n_quant outside [1, TPE_JOINT_MAX_DIMS]");
+  if (Dc > 8 || Dk > 4)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: n_dims > 8 or n_cat > 4 beside a quantised label");
+  if (a->n_cand < 1) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: n_cand < 1");
+  if (a->n_ids < 1) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: n_ids < 1");
+  if (a->k_below < 1 || a->k_above < 1)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: k_below < 1 or k_above < 1");
+  if (!a->below_c || !a->above_c || (Dc > 0 && (!a->below_mu || !a->below_a || !a->above_mu || !a->above_a)))
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: null density rows");
+  const bool inject = (a->flags & TPE_JOINT_INJECT) != 0;
+  if (inject && !a->inject)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: TPE_JOINT_INJECT without candidates");
+  if (!inject && (!a->samp_cum || (Dc > 0 && !a->samp)))
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: null sampler rows");
+  if (!a->ids || !records) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: null ids / records");
+  int cat_total = 0;
+  if (Dk > 0) {
+    if (!a->below_cat || !a->above_cat || !a->below_miss || !a->below_bonus || !a->above_miss || !a->above_bonus ||
+        !a->below_h || !a->cat_cum)
+      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: null category tables");
+    for (int d = 0; d < Dk; ++d) {
+      if (a->cat_upper[d] < 2 || a->cat_upper[d] > TPE_JOINT_MAX_CATS)
+        return tpe_internal_fail(TPE_E_ARG,
+                                 "tpe_joint_quant_run: categories of a label outside [2, TPE_JOINT_MAX_CATS]");
+      cat_total += a->cat_upper[d];
+    }
+    for (int d = 0; d < Dk; ++d)
+      if (a->cat_off[d] < 0 || a->cat_off[d] > cat_total - a->cat_upper[d])
+        return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: cat_off outside the tables");
+  }
+  int total = 0;
+  for (int d = 0; d < Dq; ++d) {
+    if (a->quant_v[d] < 2 || a->quant_v[d] > TPE_JOINT_MAX_LATTICE)
+      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: lattice values of a label outside [2, TPE_JOINT_MAX_LATTICE]");
+    total += a->quant_v[d];
+  }
+  if (total > TPE_JOINT_MAX_LATTICE_TOTAL)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: more than TPE_JOINT_MAX_LATTICE_TOTAL lattice values");
+  for (int d = 0; d < Dq; ++d)
+    if (a->quant_edge_off[d] < 0 || (int64_t)a->quant_edge_off[d] + a->quant_v[d] + 1 > (int64_t)a->n_edges)
+      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: quant_edge_off outside the edge array");
+  if (!a->quant_edges || !a->below_qmu || !a->below_qsigma || !a->above_qmu || !a->above_qsigma || !a->quant_samp ||
+      !a->quant_table)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: null quantised rows or table");
+  const uint64_t tneed = ((uint64_t)a->k_below + (uint64_t)a->k_above) * (uint64_t)total * sizeof(float);
+  if (a->quant_table_bytes < tneed) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: table workspace too small");
+  const int64_t n_chunks = n_chunks_of(a->n_cand), blocks = n_chunks * a->n_ids;
+  if (blocks > INT32_MAX) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: too many candidates");
+  const uint64_t need = (uint64_t)blocks * sizeof(tpe_joint_record);
+  if (!scratch || scratch_bytes < need) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: scratch too small");
+
+  QuantK qk;
+  MixedK& m = qk.m;
+  JointK& k = m.j;
+  k.D = Dc; k.C = a->n_cand; k.n_chunks = (int)n_chunks; k.inject = inject ? 1 : 0;
+  k.kb = a->k_below; k.ka = a->k_above;
+  k.key0 = (uint32_t)a->seed; k.key1 = (uint32_t)(a->seed >> 32); k.stream_word = a->stream_word;
+  k.bmu = a->below_mu; k.ba = a->below_a; k.bc = a->below_c;
+  k.amu = a->above_mu; k.aa = a->above_a; k.ac = a->above_c;
+  k.bbase = a->below_base; k.abase = a->above_base;
+  k.cum = a->samp_cum; k.samp = a->samp; k.ids = a->ids; k.inj = a->inject;
+  // f32 bounds: smallest float >= low, largest float < high (as tpe_joint_run)
+  auto f32_bounds = [](double L, double H, float& lo, float& hi) {
+    lo = -INFINITY; hi = INFINITY;
+    if (L > -INFINITY) { lo = (float)L; if ((double)lo < L) lo = nextafterf(lo, INFINITY); }
+    if (H < INFINITY) { hi = (float)H; while ((double)hi >= H) hi = nextafterf(hi, -INFINITY); }
+  };
+  for (int d = 0; d < TPE_JOINT_MAX_DIMS; ++d) {
+    k.lo[d] = -INFINITY; k.hi[d] = INFINITY;
+    if (d < Dc) f32_bounds(a->low[d], a->high[d], k.lo[d], k.hi[d]);
+    m.U[d] = d < Dk ? a->cat_upper[d] : 1;
+    m.off[d] = d < Dk ? a->cat_off[d] : 0;
+  }
+  k.cand = cand; k.l_out = l_out; k.g_out = g_out;
+  k.chunk_rec = (tpe_joint_record*)scratch;
+  m.Dk = Dk;
+  m.bcat = a->below_cat; m.acat = a->above_cat;
+  m.bmiss = a->below_miss; m.bbonus = a->below_bonus; m.amiss = a->above_miss; m.abonus = a->above_bonus;
+  m.bh = a->below_h; m.ccum = a->cat_cum;
+  qk.Dq = Dq; qk.total = total;
+  qk.edges = a->quant_edges; qk.qsamp = a->quant_samp;
+  qk.bT = a->quant_table; qk.aT = a->quant_table + (int64_t)total * a->k_below;
+
+  // a quantised dimension's bounds (its outer edges): low / high [Dc + d]
+  QTabK tb, ta;
+  int voff = 0;
+  for (int d = 0; d < TPE_JOINT_MAX_QUANT; ++d) {
+    const bool in = d < Dq;
+    qk.V[d] = tb.V[d] = in ? a->quant_v[d] : 2;
+    qk.voff[d] = tb.voff[d] = in ? voff : 0;
+    qk.eoff[d] = tb.eoff[d] = in ? a->quant_edge_off[d] : 0;
+    qk.qlo[d] = -INFINITY; qk.qhi[d] = INFINITY;
+    if (in) {
+      f32_bounds(a->low[Dc + d], a->high[Dc + d], qk.qlo[d], qk.qhi[d]);
+      voff += a->quant_v[d];
+    }
+  }
+  // the longest tile (a multiple of 8 components, at most kTileK) whose table fits kQTileBytes
+  int tile = 8;
+  for (int tk = kTileK; tk >= 8; tk -= 8)
+    if ((int64_t)(total + 1) * (tk + 4) * (int64_t)sizeof(float) <= kQTileBytes) { tile = tk; break; }
+  qk.tile = tile; qk.stride = tile + 4;
+  const unsigned lds = (unsigned)((total + 1) * qk.stride * sizeof(float));
+
+  const bool timed = g_prof.on != 0;
+  hipStream_t s = (hipStream_t)stream;
+  if (timed && !g_qprof.ev[0])
+    for (int i = 0; i < 2; ++i) {
+      const hipError_t e = hipEventCreate(&g_qprof.ev[i]);
+      if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
+    }
+  tb.K = a->k_below; tb.Dq = Dq; tb.mu = a->below_qmu; tb.sigma = a->below_qsigma; tb.edges = a->quant_edges;
+  tb.T = a->quant_table;
+  ta = tb;
+  ta.K = a->k_above; ta.mu = a->above_qmu; ta.sigma = a->above_qsigma; ta.T = a->quant_table + (int64_t)total * a->k_below;
+  const dim3 gb((unsigned)((a->k_below + kThreads - 1) / kThreads), (unsigned)Dq);
+  const dim3 ga((unsigned)((a->k_above + kThreads - 1) / kThreads), (unsigned)Dq);
+  if (timed) {
+    hipExtLaunchKernelGGL(k_joint_qtable, gb, dim3(kThreads), 0u, s, g_qprof.ev[0], nullptr, 0u, tb);
+    hipExtLaunchKernelGGL(k_joint_qtable, ga, dim3(kThreads), 0u, s, nullptr, g_qprof.ev[1], 0u, ta);
+    g_qprof.valid = 1;
+  } else {
+    hipLaunchKernelGGL(k_joint_qtable, gb, dim3(kThreads), 0, s, tb);
+    hipLaunchKernelGGL(k_joint_qtable, ga, dim3(kThreads), 0, s, ta);
+  }
+
+  const unsigned nb = (unsigned)blocks;
+  if (Dc == 0) launch_quant_k<0>(qk, nb, lds, s, timed);
+  else if (Dc <= 2) launch_quant_k<2>(qk, nb, lds, s, timed);
+  else if (Dc <= 4) launch_quant_k<4>(qk, nb, lds, s, timed);
+  else launch_quant_k<8>(qk, nb, lds, s, timed);
   if (timed) {
     hipExtLaunchKernelGGL(k_joint_merge, dim3((unsigned)a->n_ids), dim3(64), 0u, s, g_prof.ev[2], g_prof.ev[3], 0u,
                           (const tpe_joint_record*)scratch, (int)n_chunks, records);

@@ -1125,6 +1125,135 @@ class Engine(object):
             off += len(p)
         return self._joint_call('tpe_joint_mixed_run', a, n_ids, C, D, return_cand, want_lg)
 
+    def run_joint_quant(self, below, above, low, high, cats, quants, ids, n_cand, seed, inject=None, return_cand=False,
+                        want_lg=False, return_table=False):
+        """One joint stage over a group with quantised labels
+        (tpe_joint_quant_run, include/tpe_hip.h "Quantised joint stage"):
+        ``below`` / ``above``, ``low`` / ``high`` and ``cats`` the continuous and
+        discrete parts as in ``run_joint_mixed`` (Dc and Dk may be 0), ``quants``
+        one (mu_below [K_below], sigma_below, mu_above [K_above], sigma_above,
+        edges [V + 1]) per quantised dimension: its components in the fit
+        coordinate and its lattice edges (joint.quant_lattice).  Kernel
+        coordinates: the Dc continuous ones, the Dk categories, then the Dq
+        lattice indices; ``inject`` [C, Dc + Dk + Dq], candidates f32 [n_ids, C,
+        Dc + Dk + Dq].  ``return_table`` (debug): also the two sides' tables
+        log2 P as the device built them, f32 [K, sum V] each."""
+        from . import joint as J
+        low, high = np.asarray(low, dtype=np.float64).reshape(-1), np.asarray(high, dtype=np.float64).reshape(-1)
+        Dc, Dk, Dq = len(low), len(cats), len(quants)
+        D = Dc + Dk + Dq
+        if Dq == 0:
+            raise ValueError('joint stage: no quantised dimension, use run_joint_mixed / run_joint')
+        if Dq > N.JOINT_MAX_QUANT:
+            raise ValueError('joint stage: %d quantised dimensions, at most %d' % (Dq, N.JOINT_MAX_QUANT))
+        if Dc > N.JOINT_QUANT_MAX_CONT or Dk > N.JOINT_QUANT_MAX_DISC:
+            raise ValueError('joint stage: beside a quantised dimension at most %d continuous and %d discrete ones, '
+                             'not %d and %d' % (N.JOINT_QUANT_MAX_CONT, N.JOINT_QUANT_MAX_DISC, Dc, Dk))
+        ids, n_ids, C = self._joint_sizes(D, ids, n_cand)
+        edges = [np.ascontiguousarray(q[4], dtype=np.float64).reshape(-1) for q in quants]
+        total = 0
+        for e in edges:
+            V = len(e) - 1
+            if not 2 <= V <= N.JOINT_MAX_LATTICE:
+                raise ValueError('joint stage: %d lattice values, outside [2, %d]' % (V, N.JOINT_MAX_LATTICE))
+            if not (np.isfinite(e).all() and (np.diff(e) > 0).all()):
+                raise ValueError('joint stage: the lattice edges must be finite and strictly increasing')
+            total += V
+        if total > N.JOINT_MAX_LATTICE_TOTAL:
+            raise ValueError('joint stage: %d lattice values in the group, at most %d'
+                             % (total, N.JOINT_MAX_LATTICE_TOTAL))
+        sides = []
+        for i, side in enumerate((below, above)):
+            w = np.asarray(side[0], dtype=np.float64)
+            mu = np.asarray(side[1], dtype=np.float64).reshape(len(w), -1)
+            sigma = np.asarray(side[2], dtype=np.float64).reshape(len(w), -1)
+            if mu.shape != (len(w), Dc) or sigma.shape != mu.shape:
+                raise ValueError('joint stage: mixture shapes do not match %d dimensions' % Dc)
+            cols = [np.asarray(c[i], dtype=np.int64).reshape(-1) for c in cats]
+            qmu = [np.asarray(q[2 * i], dtype=np.float64).reshape(-1) for q in quants]
+            qsig = [np.asarray(q[2 * i + 1], dtype=np.float64).reshape(-1) for q in quants]
+            if any(len(col) != len(w) for col in cols + qmu + qsig):
+                raise ValueError('joint stage: one category / (mu, sigma) per component and dimension')
+            qsig = np.stack(qsig, axis=1)
+            if not ((qsig > 0).all() and np.isfinite(qsig).all()):
+                raise ValueError('joint stage: the quantised bandwidths must be positive')
+            xc = np.stack(cols, axis=1) if cols else np.zeros((len(w), 0), dtype=np.int64)
+            sides.append((w, mu, sigma, xc, np.stack(qmu, axis=1), qsig))
+        ps = [np.asarray(c[2], dtype=np.float64).reshape(-1) for c in cats]
+        cat_total = 0
+        for d, p in enumerate(ps):
+            U = len(p)
+            if not 2 <= U <= N.JOINT_MAX_CATS:
+                raise ValueError('joint stage: %d categories, outside [2, %d]' % (U, N.JOINT_MAX_CATS))
+            if not (p > 0).all():
+                raise ValueError('joint stage: a prior probability of 0')
+            for side in sides:
+                if side[3][:, d].min() < -1 or side[3][:, d].max() >= U:
+                    raise ValueError('joint stage: a component category outside [-1, %d)' % U)
+            cat_total += U
+        s_side = [np.array([float(c[3 + i]) for c in cats]) for i in (0, 1)]
+        if not all((s > 0).all() and np.isfinite(s).all() for s in s_side):
+            raise ValueError('joint stage: the smoothing masses must be positive')
+        up = self._joint_up
+        a = N.JointQuantArgs()
+        a.n_dims, a.n_cat, a.n_quant, a.n_cand, a.n_ids, a.flags = Dc, Dk, Dq, C, n_ids, 0
+        a.k_below, a.k_above = len(sides[0][0]), len(sides[1][0])
+        a.stream_word, a.seed = N.JOINT_STREAM, int(seed) & 0xFFFFFFFFFFFFFFFF
+        for i, name in enumerate(('below', 'above')):
+            w, mu, sigma, xc, qmu, qsig = sides[i]
+            if Dk:
+                mu32, aa, c, base, cat32, miss, bonus = J.mixed_density_rows(w, mu, sigma, low, high, xc, ps, s_side[i])
+                setattr(a, name + '_cat', up(name + '_cat', cat32, torch.float32))
+                setattr(a, name + '_miss', up(name + '_miss', miss, torch.float32))
+                setattr(a, name + '_bonus', up(name + '_bonus', bonus, torch.float32))
+            else:
+                mu32, aa, c, base = J.density_rows(w, mu, sigma, low, high)
+            if Dc:
+                setattr(a, name + '_mu', up(name + '_mu', mu32, torch.float32))
+                setattr(a, name + '_a', up(name + '_a', aa, torch.float32))
+            setattr(a, name + '_c', up(name + '_c', c, torch.float32))
+            setattr(a, name + '_base', base)
+            setattr(a, name + '_qmu', up(name + '_qmu', qmu, torch.float64))
+            setattr(a, name + '_qsigma', up(name + '_qsigma', qsig, torch.float64))
+        w, mu, sigma, xc, qmu, qsig = sides[0]
+        if Dk:
+            cum, rows, h, cat_cum = J.mixed_sampler_rows(w, mu, sigma, low, high, ps, s_side[0])
+            a.below_h, a.cat_cum = up('cat_h', h, torch.float64), up('cat_cum', cat_cum, torch.float64)
+        else:
+            cum, rows = J.sampler_rows(w, mu, sigma, low, high)
+        a.samp_cum = up('cum', cum, torch.float64)
+        if Dc:
+            a.samp = up('samp', rows, torch.float32)
+        qlow, qhigh = np.array([e[0] for e in edges]), np.array([e[-1] for e in edges])
+        a.quant_samp = up('qsamp', J.sampler_rows(w, qmu, qsig, qlow, qhigh)[1], torch.float32)
+        all_edges = np.concatenate(edges)
+        a.quant_edges, a.n_edges = up('qedges', all_edges, torch.float64), len(all_edges)
+        a.ids = up('ids', ids, torch.int64)
+        self._joint_inject(a, inject, C, D)
+        off = 0
+        for d in range(Dc):
+            a.low[d], a.high[d] = low[d], high[d]
+        for d, p in enumerate(ps):
+            a.cat_upper[d], a.cat_off[d] = len(p), off
+            off += len(p)
+        off = 0
+        for d, e in enumerate(edges):
+            a.low[Dc + d], a.high[Dc + d] = e[0], e[-1]
+            a.quant_v[d], a.quant_edge_off[d] = len(e) - 1, off
+            off += len(e)
+        nb = ctypes.c_uint64(0)
+        N.check(self.lib.tpe_joint_quant_table_bytes(a.k_below, a.k_above, total, ctypes.byref(nb)), self.lib,
+                'tpe_joint_quant_table_bytes')
+        d_tab = self._buf('joint_qtable', (nb.value + 3) // 4, torch.float32)
+        a.quant_table, a.quant_table_bytes = d_tab.data_ptr(), d_tab.numel() * 4
+        out = self._joint_call('tpe_joint_quant_run', a, n_ids, C, D, return_cand, want_lg)
+        if not return_table:
+            return out
+        tab = d_tab[:(a.k_below + a.k_above) * total].cpu().numpy()
+        tb = tab[:total * a.k_below].reshape(total, a.k_below).T.copy()
+        ta = tab[total * a.k_below:].reshape(total, a.k_above).T.copy()
+        return (out if isinstance(out, tuple) else (out,)) + (tb, ta)
+
     def device_tables(self):
         """(problems, comp32) of the last ``run`` as the device holds them after
         its stages ran — device-fitted above rows and the problem fields the fit

@@ -370,3 +370,228 @@ def fit_mixed_model(rows, drows, hist, below_tids, prior_weight=1.0, lf=DEFAULT_
                       np.array([p[2] for p in pb], dtype=np.float64), np.array([p[3] for p in pb], dtype=np.float64),
                       ps, np.array([smoothing(prior_weight, len(p), nb) for p in ps]),
                       np.array([smoothing(prior_weight, len(p), na) for p in ps]))
+
+
+# -------------------------------------------------------- quantised groups
+# A joint group may also hold quantised labels (quniform / qloguniform): the
+# kernel coordinates are the continuous labels, the discrete ones, then the
+# quantised ones, each in table order (include/tpe_hip.h "Quantised joint
+# stage").  A quantised label is a continuous dimension of the model observed
+# through bins: lattice index i stands for the value (m_lo + i) q and takes the
+# component's mass on [e_i, e_{i+1}) over its mass on [low, high).
+QUANT_DISTS = ('quniform', 'qloguniform')
+SQRT1_2 = math.sqrt(0.5)
+QUANT_TAIL_MAX = 26.5       # |e - mu| / (sigma sqrt 2) beyond which a tail (below 2^-1018) counts as exactly 0
+
+
+def lattice_size(dist, args):
+    """(m_lo, V, q) of a quniform / qloguniform label with q > 0: m_lo the
+    smallest integer m with (m + 1/2) q > lo_v (not below 0 for qloguniform),
+    m_hi the largest with (m - 1/2) q < hi_v, V = m_hi - m_lo + 1; lo_v, hi_v the
+    bounds as values.  A value whose clipped bin would be empty is not in the
+    lattice (quniform(0, 3.5, 1): V = 4)."""
+    q = float(args['q'])
+    lo, hi = float(args['low']), float(args['high'])
+    if dist == 'qloguniform':
+        lo, hi = math.exp(lo), math.exp(hi)
+    m_lo = int(math.floor(lo / q - 0.5)) + 1
+    while (m_lo - 1 + 0.5) * q > lo:
+        m_lo -= 1
+    while not (m_lo + 0.5) * q > lo:
+        m_lo += 1
+    m_hi = int(math.ceil(hi / q + 0.5)) - 1
+    while (m_hi + 1 - 0.5) * q < hi:
+        m_hi += 1
+    while not (m_hi - 0.5) * q < hi:
+        m_hi -= 1
+    if dist == 'qloguniform':
+        m_lo = max(m_lo, 0)
+    return m_lo, m_hi - m_lo + 1, q
+
+
+def quant_lattice(dist, args):
+    """(m_lo, V, q, edges [V + 1]) of a joinable quantised label: the edges in
+    the fit coordinate, e_0 = low, e_V = high, e_i = (m_lo + i - 1/2) q between
+    (its log for qloguniform); strictly increasing."""
+    m_lo, V, q = lattice_size(dist, args)
+    inner = (m_lo + np.arange(1, V) - 0.5) * q
+    if dist == 'qloguniform':
+        inner = np.log(inner)
+    edges = np.concatenate([[float(args['low'])], inner, [float(args['high'])]])
+    assert (np.diff(edges) > 0).all(), (dist, args)
+    return m_lo, V, q, edges
+
+
+def quant_reason(row, table):
+    """Why ``row`` cannot be joined as a quantised dimension, or None if it can."""
+    if not all(p is None for p in row.parents) or row.depth != 0:
+        return 'conditional (%s)' % row.dist
+    if row.dist in ('qnormal', 'qlognormal'):
+        return ('%s: its lattice is unbounded and data-dependent, so eligibility could not be decided before the fit'
+                % row.dist)
+    if row.dist not in QUANT_DISTS:
+        return 'not a quniform or qloguniform label (%s)' % row.dist
+    if not float(row.args['q']) > 0:
+        return 'q = %r is not positive' % (row.args['q'],)
+    if not float(row.args['high']) > float(row.args['low']):
+        return 'an empty range'
+    V = lattice_size(row.dist, row.args)[1]
+    if V < 2:
+        return '%d lattice value, fewer than 2: nothing to choose' % V
+    if V > N.JOINT_MAX_LATTICE:
+        return ('%d lattice values, more than TPE_JOINT_MAX_LATTICE = %d: such a label is close to continuous, model '
+                'it as uniform / loguniform' % (V, N.JOINT_MAX_LATTICE))
+    return None
+
+
+def eligible_quant(row, table):
+    """Whether a ParamRow can be joined as a quantised dimension: unconditional
+    quniform / qloguniform, q > 0, 2 to 256 lattice values."""
+    return quant_reason(row, table) is None
+
+
+def quant_bin_masses(mu, sigma, edges):
+    """(diff [K, V], mass [K]) of one quantised dimension: the components' float64
+    normal masses on the bins [e_i, e_{i+1}) and on [e_0, e_V), every Phi
+    difference between the two smaller tails (_std_bounds' mirroring, per bin):
+    lower tails left of mu, upper tails right of it, 1 - upper - lower for the
+    bin that holds mu.  A tail beyond QUANT_TAIL_MAX is exactly 0 (float64 would
+    go subnormal there: the rule keeps the result independent of the libm), so a
+    far bin's mass is exactly 0."""
+    mu, sigma = np.asarray(mu, dtype=np.float64)[:, None], np.asarray(sigma, dtype=np.float64)[:, None]
+    t = (np.asarray(edges, dtype=np.float64)[None, :] - mu) * (SQRT1_2 / sigma)
+    s = np.where(np.abs(t) > QUANT_TAIL_MAX, 0.0, 0.5 * erfc(np.abs(t)))
+
+    def mass(ta, sa, tb, sb):
+        return np.where(tb <= 0, sb - sa, np.where(ta >= 0, sa - sb, 1.0 - sa - sb))
+    return mass(t[:, :-1], s[:, :-1], t[:, 1:], s[:, 1:]), mass(t[:, 0], s[:, 0], t[:, -1], s[:, -1])
+
+
+def quant_P(mu, sigma, edges):
+    """P_kd(i) [K, V]: every row sums to 1."""
+    diff, mass = quant_bin_masses(mu, sigma, edges)
+    return diff / mass[:, None]
+
+
+def quant_table(mu, sigma, edges):
+    """float64 T [K, V] = log2 P_kd(i) as the device stores it: entries below
+    TPE_JOINT_QFLOOR (-inf included) are TPE_JOINT_QFLOOR."""
+    diff, mass = quant_bin_masses(mu, sigma, edges)
+    with np.errstate(divide='ignore'):
+        T = np.log2(diff) - np.log2(mass)[:, None]
+    return np.where(T >= N.JOINT_QFLOOR, T, N.JOINT_QFLOOR)
+
+
+def quant_lpdf_numpy(z, v, qi, w, mu, sigma, low, high, xc, ps, s, quants, block=1 << 14):
+    """The quantised model's float64 log-density at continuous ``z`` [C, Dc],
+    categories ``v`` [C, Dk] and lattice indices ``qi`` [C, Dq]: ``quants`` one
+    (mu [K], sigma [K], edges [V + 1]) per quantised dimension of this side.
+    log p = logsumexp_k [log w_k + the continuous terms + sum_d log P_kd(v_d) +
+    sum_d log P_kd(i_d)]; a quantised dimension adds nothing to the coefficient."""
+    qi = np.asarray(qi, dtype=np.int64)
+    C = len(qi)
+    v = np.asarray(v, dtype=np.int64).reshape(C, len(ps))
+    z = np.asarray(z, dtype=np.float64).reshape(C, np.asarray(mu).shape[1])
+    mu, sigma = np.asarray(mu, dtype=np.float64), np.asarray(sigma, dtype=np.float64)
+    fa, fb, _ = _std_bounds(mu, sigma, np.asarray(low, dtype=np.float64)[None, :],
+                            np.asarray(high, dtype=np.float64)[None, :])
+    logc = np.log(w) - np.sum(np.log(sigma * np.sqrt(2 * np.pi)) + np.log(fb - fa), axis=1)
+    with np.errstate(divide='ignore'):
+        logP = [np.log(quant_P(qm, qs, e)) for qm, qs, e in quants]              # [K, V] each
+    out = np.empty(C)
+    step = max(1, block // max(1, len(w) // 64 + 1))
+    for lo in range(0, C, step):
+        zz, vv, qq = z[lo:lo + step], v[lo:lo + step], qi[lo:lo + step]
+        t = logc[None, :].repeat(len(qq), axis=0)
+        for d in range(z.shape[1]):
+            t -= 0.5 * ((zz[:, d, None] - mu[None, :, d]) / sigma[None, :, d]) ** 2
+        for d, p in enumerate(ps):
+            p = np.asarray(p, dtype=np.float64)
+            pv = p[vv[:, d]][:, None]
+            hit = vv[:, d, None] == xc[None, :, d]
+            t += np.log(np.where(xc[None, :, d] < 0, pv, (hit + s[d] * pv) / (1.0 + s[d])))
+        for d in range(len(quants)):
+            t += logP[d][:, qq[:, d]].T
+        m = t.max(axis=1)
+        out[lo:lo + step] = m + np.log(np.exp(t - m[:, None]).sum(axis=1))
+    return out
+
+
+class QuantModel(object):
+    """The two mixtures of a joint group with quantised labels: ``rows`` the
+    continuous ParamRows, ``drows`` the discrete and ``qrows`` the quantised
+    ones (kernel coordinate order: rows, drows, qrows); ``below`` / ``above`` =
+    (w, mu, sigma, xc, qmu, qsigma) with qmu / qsigma [K, Dq] the quantised
+    dimensions' components; ``lattices`` one quant_lattice per quantised label."""
+    __slots__ = ('rows', 'drows', 'qrows', 'below', 'above', 'low', 'high', 'ps', 's_below', 's_above', 'lattices')
+
+    def __init__(self, rows, drows, qrows, below, above, low, high, ps, s_below, s_above, lattices):
+        self.rows, self.drows, self.qrows, self.below, self.above = list(rows), list(drows), list(qrows), below, above
+        self.low, self.high, self.ps, self.s_below, self.s_above = low, high, ps, s_below, s_above
+        self.lattices = lattices
+
+    def cats(self):
+        """The ``cats`` argument of Engine.run_joint_quant."""
+        return [(self.below[3][:, d], self.above[3][:, d], self.ps[d], self.s_below[d], self.s_above[d])
+                for d in range(len(self.drows))]
+
+    def quants(self):
+        """The ``quants`` argument of Engine.run_joint_quant."""
+        return [(self.below[4][:, d], self.below[5][:, d], self.above[4][:, d], self.above[5][:, d], lat[3])
+                for d, lat in enumerate(self.lattices)]
+
+    def values(self, z):
+        """Label values of kernel coordinates z [.., Dc + Dk + Dq]: exp for the
+        log families, (m_lo + i) q for a lattice index i."""
+        z = np.array(z, dtype=np.float64)
+        for d, r in enumerate(self.rows):
+            if r.dist in LOG_DISTS:
+                z[..., d] = np.exp(z[..., d])
+        o = len(self.rows) + len(self.drows)
+        for d, (m_lo, V, q, _) in enumerate(self.lattices):
+            z[..., o + d] = (m_lo + np.rint(z[..., o + d])) * q
+        return z
+
+
+def fit_quant_model(rows, drows, qrows, hist, below_tids, prior_weight=1.0, lf=DEFAULT_LF):
+    """QuantModel of the eligible continuous ``rows``, discrete ``drows`` and
+    quantised ``qrows`` from a History and its below set (fit_mixed_model with
+    the quantised columns fitted as continuous ones in their fit coordinate)."""
+    crow = list(rows) + list(qrows)
+    pb = [prior_and_bounds('uniform' if r.dist in QUANT_DISTS else r.dist, r.args) for r in crow]
+    tids = None
+    cols, ccols = [], []
+    every = crow + list(drows)
+    for r in every:
+        otids, ovals = hist.obs[r.label]
+        otids = np.asarray(otids, dtype=np.int64)
+        if tids is None:
+            tids = otids
+        elif len(otids) != len(tids) or (otids != tids).any():
+            raise ValueError('joint label %r is not observed in the same trials as %r' % (r.label, every[0].label))
+        if r.dist in DISCRETE_DISTS:
+            ovals = np.asarray(ovals, dtype=np.int64)
+            if len(ovals) and (ovals.min() < 0 or ovals.max() >= int(r.args['upper'])):
+                raise IndexError('categorical observation of %r out of range [0, %d)' % (r.label, int(r.args['upper'])))
+            ccols.append(ovals)
+        else:
+            cols.append(fit_coord(r.dist, r.args, ovals))
+    n, Dc = len(tids), len(rows)
+    X = np.stack(cols, axis=1) if cols else np.zeros((n, 0))
+    XC = np.stack(ccols, axis=1) if ccols else np.zeros((n, 0), dtype=np.int64)
+    order = np.argsort(tids, kind='stable')
+    X, XC, tids = X[order], XC[order], tids[order]
+    m = np.isin(tids, np.asarray(below_tids, dtype=np.int64))
+    priors = [(p[0], p[1]) for p in pb]
+    ps = [cat_prior(r.dist, r.args) for r in drows]
+    nb, na = int(m.sum()), int((~m).sum())
+    sides = []
+    for sel in (m, ~m):
+        w, mu, sigma, xc = mixed_side_mixture(X[sel], priors, XC[sel], prior_weight, lf)
+        sides.append((w, mu[:, :Dc], sigma[:, :Dc], xc, mu[:, Dc:], sigma[:, Dc:]))
+    return QuantModel(rows, drows, qrows, sides[0], sides[1],
+                      np.array([p[2] for p in pb[:Dc]], dtype=np.float64),
+                      np.array([p[3] for p in pb[:Dc]], dtype=np.float64),
+                      ps, np.array([smoothing(prior_weight, len(p), nb) for p in ps]),
+                      np.array([smoothing(prior_weight, len(p), na) for p in ps]),
+                      [quant_lattice(r.dist, r.args) for r in qrows])

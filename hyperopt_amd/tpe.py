@@ -36,7 +36,8 @@ Extensions over the reference (keyword-only, defaults keep its behaviour):
     mixtures over the group, whole-vector candidates, one argmax
     (joint.py, DESIGN.md "Joint TPE"); every other label as without it.
     ``joint_discrete=True`` lets the group also hold unconditional randint /
-    categorical labels that gate no other label.
+    categorical labels that gate no other label, ``joint_quantized=True``
+    unconditional quniform / qloguniform labels of 2 to 256 lattice values.
 
 ``linear_forgetting`` is accepted and, as in the reference, not used: the
 forgetting window is fixed at DEFAULT_LF=25 (tpe.py:27-29).
@@ -834,14 +835,14 @@ def suggest(new_ids, domain, trials, seed,
             gamma=_default_gamma,
             linear_forgetting=_default_linear_forgetting,
             sampler='philox', precision='fp32', device=None, shard=None, shard_ids=None, shard_labels=None,
-            shard_grid=None, joint=False, joint_discrete=False):
+            shard_grid=None, joint=False, joint_discrete=False, joint_quantized=False):
     new_ids = list(new_ids)
     if not new_ids:
         return []
-    if (joint is not False and joint is not None) or joint_discrete:
+    if (joint is not False and joint is not None) or joint_discrete or joint_quantized:
         # (argument errors first: no device use, no startup draw)
         _joint_group(domain.table, joint, sampler, precision, (shard, shard_ids, shard_labels, shard_grid),
-                     joint_discrete)
+                     joint_discrete, joint_quantized)
     t0 = time.time()
     hist = _history.extract(domain, trials)
     if logger.isEnabledFor(logging.INFO):
@@ -856,7 +857,7 @@ def suggest(new_ids, domain, trials, seed,
                               n_EI_candidates=n_EI_candidates, gamma=gamma, sampler=sampler,
                               precision=precision, device=device, shard=shard, shard_ids=shard_ids,
                               shard_labels=shard_labels, shard_grid=shard_grid, joint=joint,
-                              joint_discrete=joint_discrete)
+                              joint_discrete=joint_discrete, joint_quantized=joint_quantized)
     logger.info('tpe.suggest took %f seconds', time.time() - t0)
     return rand.docs_from_choices(new_ids, domain, trials, choices)
 
@@ -896,7 +897,8 @@ class ChoiceColumns(object):
 def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weight,
                     n_EI_candidates=_default_n_EI_candidates, gamma=_default_gamma,
                     sampler='philox', precision='fp32', device=None, shard=None, columns=False,
-                    shard_ids=None, shard_labels=None, shard_grid=None, joint=False, joint_discrete=False):
+                    shard_ids=None, shard_labels=None, shard_grid=None, joint=False, joint_discrete=False,
+                    joint_quantized=False):
     """The suggest core on a structure-of-arrays history (``history.History``):
     per new id a {label: value or None} dict.  ``suggest`` wraps it with the
     Trials document layout; columnar callers (and bench.py's large configs)
@@ -926,13 +928,21 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
     no prior probability 0.  ``joint=True`` then joins every such label too and
     a list may name them; a named gate, conditional or quantised label raises
     ValueError.  A group that ends up with no discrete label is the continuous
-    stage, byte for byte."""
+    stage, byte for byte.
+
+    ``joint_quantized=True`` (with ``joint``): the group may also hold
+    unconditional ``quniform`` / ``qloguniform`` labels with q > 0 and 2 to 256
+    lattice values — at most 4 of them with 512 lattice values in all, beside at
+    most 8 continuous and 4 discrete labels (DESIGN.md "Quantised labels in the
+    joint stage").  Their joined values are ``np.float64`` multiples of q.
+    ``qnormal`` / ``qlognormal`` labels stay univariate.  A group that ends up
+    with no quantised label is the stage without the keyword, byte for byte."""
     if sampler not in ('philox', 'replay'):
         raise ValueError("sampler must be 'philox' or 'replay'")
     group = None
-    if (joint is not False and joint is not None) or joint_discrete:
+    if (joint is not False and joint is not None) or joint_discrete or joint_quantized:
         group = _joint_group(table, joint, sampler, precision, (shard, shard_ids, shard_labels, shard_grid),
-                             joint_discrete)
+                             joint_discrete, joint_quantized)
     if sum(a is not None for a in (shard, shard_ids, shard_labels, shard_grid)) > 1:
         raise ValueError('shard, shard_ids, shard_labels and shard_grid are exclusive: one shard axis per suggest')
     if (shard_ids is not None or shard_labels is not None or shard_grid is not None) and sampler == 'replay':
@@ -951,12 +961,15 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
 TPE_JOINT_MAX_DIMS = N.JOINT_MAX_DIMS
 
 
-def _joint_group(table, joint, sampler, precision, shards, discrete=False):
-    """The ParamRows a ``joint`` argument joins, in table order (``discrete``:
-    the eligible discrete labels among them); ValueError for every combination
-    the joint stage does not take.  Touches no device."""
+def _joint_group(table, joint, sampler, precision, shards, discrete=False, quantized=False):
+    """The ParamRows a ``joint`` argument joins, in table order (``discrete`` /
+    ``quantized``: the eligible discrete / quantised labels among them);
+    ValueError for every combination the joint stage does not take.  Touches no
+    device."""
     if discrete and (joint is False or joint is None):
         raise ValueError('joint_discrete=True needs joint=True or joint=[labels]: it only widens what joint joins')
+    if quantized and (joint is False or joint is None):
+        raise ValueError('joint_quantized=True needs joint=True or joint=[labels]: it only widens what joint joins')
     if sampler == 'replay':
         raise ValueError("joint does not combine with sampler='replay': the joint candidates are Philox draws")
     if precision == 'fp64':
@@ -964,7 +977,8 @@ def _joint_group(table, joint, sampler, precision, shards, discrete=False):
     if any(a is not None for a in shards):
         raise ValueError('joint does not combine with a shard argument')
     if joint is True:
-        rows = [r for r in table.rows if _joint.eligible(r) or (discrete and _joint.eligible_discrete(r, table))]
+        rows = [r for r in table.rows if _joint.eligible(r) or (discrete and _joint.eligible_discrete(r, table))
+                or (quantized and _joint.eligible_quant(r, table))]
     else:
         if isinstance(joint, str):
             raise ValueError('joint must be True or a list of labels, not the string %r' % joint)
@@ -973,7 +987,11 @@ def _joint_group(table, joint, sampler, precision, shards, discrete=False):
             r = table.by_label.get(label)
             if r is None:
                 raise ValueError('joint: %r is not a label of the space' % (label,))
-            if discrete and not _joint.eligible(r):
+            if quantized and r.dist.startswith('q'):
+                why = _joint.quant_reason(r, table)
+                if why is not None:
+                    raise ValueError('joint: label %r is not eligible with joint_quantized=True: %s' % (label, why))
+            elif discrete and not _joint.eligible(r):
                 why = _joint.discrete_reason(r, table)
                 if why is not None:
                     raise ValueError('joint: label %r is not eligible with joint_discrete=True: %s' % (label, why))
@@ -991,7 +1009,33 @@ def _joint_group(table, joint, sampler, precision, shards, discrete=False):
     if n_cats > N.JOINT_MAX_CAT_TOTAL:
         raise ValueError('joint joins discrete labels of at most TPE_JOINT_MAX_CAT_TOTAL = %d categories in all, not '
                          '%d: pass the labels to join as joint=[...]' % (N.JOINT_MAX_CAT_TOTAL, n_cats))
+    qrows = [r for r in rows if r.dist in _joint.QUANT_DISTS]
+    if qrows:
+        n_disc = sum(1 for r in rows if r.categorical)
+        n_cont = len(rows) - len(qrows) - n_disc
+        n_lat = sum(_joint.lattice_size(r.dist, r.args)[1] for r in qrows)
+        tail = ': pass the labels to join as joint=[...]'
+        if len(qrows) > N.JOINT_MAX_QUANT:
+            raise ValueError('joint joins at most TPE_JOINT_MAX_QUANT = %d quantised labels, not %d%s'
+                             % (N.JOINT_MAX_QUANT, len(qrows), tail))
+        if n_lat > N.JOINT_MAX_LATTICE_TOTAL:
+            raise ValueError('joint joins quantised labels of at most TPE_JOINT_MAX_LATTICE_TOTAL = %d lattice values '
+                             'in all, not %d%s' % (N.JOINT_MAX_LATTICE_TOTAL, n_lat, tail))
+        if n_cont > N.JOINT_QUANT_MAX_CONT:
+            raise ValueError('joint joins at most %d continuous labels beside a quantised one, not %d%s'
+                             % (N.JOINT_QUANT_MAX_CONT, n_cont, tail))
+        if n_disc > N.JOINT_QUANT_MAX_DISC:
+            raise ValueError('joint joins at most %d discrete labels beside a quantised one, not %d%s'
+                             % (N.JOINT_QUANT_MAX_DISC, n_disc, tail))
     return rows
+
+
+def _joint_kernel_order(group):
+    """(continuous, discrete, quantised) rows of a joint group, each in table
+    order: concatenated, the kernel coordinate order."""
+    drows = [r for r in group if r.categorical]
+    qrows = [r for r in group if r.dist in _joint.QUANT_DISTS]
+    return [r for r in group if not r.categorical and r.dist not in _joint.QUANT_DISTS], drows, qrows
 
 
 def _suggest_joint(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, device, columns, group):
@@ -1005,8 +1049,14 @@ def _suggest_joint(table, hist, new_ids, seed, prior_weight, n_EI_candidates, ga
         return cc if columns else []
     engine = get_engine(device, 'fp32')
     ids = np.asarray(new_ids, dtype=np.int64).reshape(-1)
-    drows = [r for r in group if r.categorical]
-    if drows:                                    # kernel coordinates: the continuous labels, then the discrete ones
+    crows, drows, qrows = _joint_kernel_order(group)
+    if qrows:                                    # kernel coordinates: continuous, discrete, then quantised labels
+        group = crows + drows + qrows
+        model = _joint.fit_quant_model(crows, drows, qrows, hist, _history.split_below(hist, gamma), prior_weight,
+                                       DEFAULT_LF)
+        rec = engine.run_joint_quant(model.below[:3], model.above[:3], model.low, model.high, model.cats(),
+                                     model.quants(), ids, int(n_EI_candidates), seed)
+    elif drows:                                  # kernel coordinates: the continuous labels, then the discrete ones
         group = [r for r in group if not r.categorical] + drows
         model = _joint.fit_mixed_model(group[:len(group) - len(drows)], drows, hist,
                                        _history.split_below(hist, gamma), prior_weight, DEFAULT_LF)

@@ -1156,6 +1156,120 @@ int tpe_joint_mixed_run(const tpe_joint_mixed_args* args, tpe_joint_record* reco
                         double* g_out, void* scratch, uint64_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Quantised joint stage (tpe_joint.hip; additive to ABI 24): a group that also
+ * holds n_quant quantised labels (quniform / qloguniform), 1 <= n_quant <=
+ * TPE_JOINT_MAX_QUANT.  Kernel coordinate order: the n_dims continuous labels,
+ * the n_cat discrete ones, then the quantised ones; a quantised coordinate
+ * travels as its lattice index (f32 in `cand` / `inject`, double in
+ * tpe_joint_record.z), like a category.  The first fields are those of
+ * tpe_joint_mixed_args at the same offsets and mean the same (n_dims = 0 and
+ * n_cat = 0 are allowed: an all-quantised group).
+ *
+ * Quantised dimension d is a continuous dimension observed through bins: its
+ * lattice has V_d = quant_v[d] values and V_d + 1 strictly increasing edges
+ * e_0 = low .. e_V = high in the fit coordinate, at quant_edge_off[d] in
+ * `quant_edges` (f64, n_edges entries in all); the host-side copies of e_0 and
+ * e_V are low[n_dims + d] and high[n_dims + d] (the sampler's f32 clip is made
+ * from them).  A component with (mu, sigma)
+ * gives lattice value i the mass
+ *   P_kd(i) = [Phi((e_{i+1} - mu) / sigma) - Phi((e_i - mu) / sigma)] / mass_kd,
+ *   mass_kd = Phi((e_V - mu) / sigma) - Phi((e_0 - mu) / sigma),
+ * every Phi difference taken between the two smaller tails (lower tails left
+ * of mu, upper tails right of it, 1 - upper - lower for the bin that holds mu);
+ * a tail with |e - mu| / (sigma sqrt 2) > 26.5 (below 2^-1018, where float64
+ * would go subnormal) counts as exactly 0.
+ * The log2 of a component's term gains sum_d log2 P_kd(i_d); a quantised
+ * dimension adds nothing to c.
+ *
+ * k_joint_qtable (one launch per side) evaluates T[d][i][k] = log2 P_kd(i) in
+ * f64 from below_qmu / below_qsigma (above_..: f64 [K * n_quant], component k,
+ * dimension d at [k * n_quant + d]) and stores it as f32 in `quant_table`, a
+ * caller-owned device workspace of tpe_joint_quant_table_bytes(k_below,
+ * k_above, sum_d V_d) bytes: the below side's [sum V][K_below] (per lattice
+ * value a contiguous run over k, dimensions in order), then the above side's.
+ * An entry below TPE_JOINT_QFLOOR (a far bin's f64 mass is exactly 0: -inf
+ * included) is stored as TPE_JOINT_QFLOOR; next to the prior row's term such a
+ * term is 0 in f32.  The chunk kernel stages the table through LDS in component
+ * tiles laid out [lattice value][component]; per (candidate, component,
+ * quantised dimension) it costs one LDS read at the candidate's own lattice
+ * index and one add.
+ *
+ * Sampling: word 0 picks the component and word 1 + j serves kernel coordinate
+ * j, as in the other two stages (so the continuous and discrete coordinates are
+ * those of a tpe_joint_mixed_run / tpe_joint_run over the group without its
+ * quantised labels).  A quantised coordinate draws z exactly as a continuous
+ * dimension with the sampler row quant_samp[(k * n_quant + d) * 5 ..] = {mu,
+ * sigma, fa, fb, flip} would (clipped to [smallest float >= e_0, largest float
+ * < e_V]); its lattice index is the number of interior edges e_1 .. e_{V-1}
+ * that are <= (double) z.
+ *
+ * Limits (conditions that bound the instantiation set and the LDS tile, not
+ * measurements): n_quant <= TPE_JOINT_MAX_QUANT, 2 <= V_d <=
+ * TPE_JOINT_MAX_LATTICE, sum_d V_d <= TPE_JOINT_MAX_LATTICE_TOTAL, and beside a
+ * quantised label n_dims <= 8 and n_cat <= 4.
+ *
+ * tpe_joint_quant_run returns TPE_E_ARG before any launch (no device needed)
+ * for everything tpe_joint_mixed_run checks (with n_quant counted among the
+ * coordinates), n_quant outside [0, TPE_JOINT_MAX_QUANT], n_dims > 8 or n_cat >
+ * 4 while n_quant > 0, a V_d outside [2, TPE_JOINT_MAX_LATTICE], a total above
+ * TPE_JOINT_MAX_LATTICE_TOTAL, a quant_edge_off that leaves [0, n_edges - V_d -
+ * 1], a null edge / mu / sigma / sampler / table pointer, or a table workspace
+ * smaller than tpe_joint_quant_table_bytes says.  n_quant = 0 is
+ * tpe_joint_mixed_run on the shared fields: the same bytes.  With
+ * TPE_JOINT_INJECT an out-of-range lattice index is the caller's error; the
+ * device only keeps the table index in range.  tpe_joint_record,
+ * tpe_joint_scratch_bytes and tpe_joint_profile serve this stage too;
+ * tpe_joint_quant_profile reads the table kernels' time of a profiled run.
+ * ---------------------------------------------------------------------- */
+#define TPE_JOINT_MAX_QUANT 4            /* quantised labels per group */
+#define TPE_JOINT_MAX_LATTICE 256        /* lattice values per quantised label */
+#define TPE_JOINT_MAX_LATTICE_TOTAL 512  /* lattice values per group */
+#define TPE_JOINT_QFLOOR (-4096.0f)      /* smallest stored log2 P_kd(i) */
+typedef struct tpe_joint_quant_args {
+  int32_t n_dims, n_cand, n_ids, flags;   /* as tpe_joint_mixed_args ... */
+  int32_t k_below, k_above;
+  uint32_t stream_word;
+  int32_t n_cat;
+  uint64_t seed;
+  const float *below_mu, *below_a, *below_c;
+  const float *above_mu, *above_a, *above_c;
+  double below_base, above_base;
+  const double* samp_cum;
+  const float* samp;
+  const int64_t* ids;
+  const float* inject;                    /* device [n_cand * (n_dims + n_cat + n_quant)] */
+  double low[TPE_JOINT_MAX_DIMS], high[TPE_JOINT_MAX_DIMS];
+  int32_t cat_upper[TPE_JOINT_MAX_DIMS];
+  int32_t cat_off[TPE_JOINT_MAX_DIMS];
+  const float *below_cat, *above_cat;
+  const float *below_miss, *below_bonus;
+  const float *above_miss, *above_bonus;
+  const double* below_h;
+  const double* cat_cum;                  /* ... up to here */
+  int32_t n_quant;                        /* the quantised labels */
+  int32_t n_edges;                        /* entries of quant_edges */
+  int32_t quant_v[TPE_JOINT_MAX_QUANT];         /* V_d */
+  int32_t quant_edge_off[TPE_JOINT_MAX_QUANT];  /* e_0 of dimension d in quant_edges */
+  const double* quant_edges;              /* device f64 [n_edges] */
+  const double *below_qmu, *below_qsigma; /* device f64 [k_below * n_quant] */
+  const double *above_qmu, *above_qsigma; /* device f64 [k_above * n_quant] */
+  const float* quant_samp;                /* device f32 [k_below * n_quant * 5] */
+  float* quant_table;                     /* device workspace */
+  uint64_t quant_table_bytes;
+} tpe_joint_quant_args;
+
+int tpe_joint_quant_table_bytes(int32_t k_below, int32_t k_above, int32_t total_bins, uint64_t* bytes);
+
+/* as tpe_joint_run; cand: device f32 [n_ids * n_cand * (n_dims + n_cat + n_quant)] */
+int tpe_joint_quant_run(const tpe_joint_quant_args* args, tpe_joint_record* records, float* cand, double* l_out,
+                        double* g_out, void* scratch, uint64_t scratch_bytes, void* stream);
+
+/* Profiling only: while tpe_joint_profile is enabled a tpe_joint_quant_run also
+ * times its two table launches together; *table_ms gets that device time of the
+ * last such run (it WAITS for them). */
+int tpe_joint_quant_profile(double* table_ms);
+
+/* ------------------------------------------------------------------------
  * Host phase clock of tpe_suggest_tree (tools/native_split.py).  While
  * enabled, a call records the steady-clock microseconds since its entry at
  * each phase below (a tree of several level runs: the last run's phases);

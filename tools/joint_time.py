@@ -1,6 +1,6 @@
 """Time the joint TPE stage against the host route.
 Usage: python tools/joint_time.py [--pairs 3] [--warmup 1] [--cand 1048576] [--history 10000]
-                                  [--host-cand N] [--out FILE] [--mixed]
+                                  [--host-cand N] [--out FILE] [--mixed | --quant]
 
 Workload: a flat space of 4 continuous labels (uniform, loguniform, normal,
 uniform), a seeded 10,000-trial history whose loss has an x0 * x1 term, one
@@ -32,7 +32,18 @@ space's 3 continuous labels alone (k_joint_chunk<3>: what the mixed kernel's
 padded fourth continuous slot costs is read off against it), alternating in
 one process, each timed by the chunk kernel's own events (tpe_joint_profile).
 The line carries the three medians and the ratios mixed / continuous; --out defaults to
-profiles/joint_mixed_time.jsonl."""
+profiles/joint_mixed_time.jsonl.
+
+--quant: the quantised stage (DESIGN.md "Quantised labels in the joint stage").
+Three continuous labels with, per round, (a) one hp.quniform of 32 values
+through Engine.run_joint_quant, (a256) the same with 256 values, (b) one
+hp.choice of 32 through Engine.run_joint_mixed (k_joint_mixed_chunk<4, 1>: the
+yardstick) and (c) the three continuous labels alone (k_joint_chunk<3>),
+alternating in one process, each chunk kernel by its own events; the two table
+launches of (a) and (a256) by theirs (tpe_joint_quant_profile).  The line
+carries the medians and ranges, (a) / (b), (a) - (c), and the worst l / g error
+of the first --host-cand (default 4096) sampled vectors of (a) as a fraction of
+the lpdf tolerance; --out defaults to profiles/joint_quant_time.jsonl."""
 import argparse
 import ctypes
 import json
@@ -159,6 +170,113 @@ def main_mixed(args):
     return 0
 
 
+def make_quant_history(n, V):
+    """make_mixed_history's continuous columns with a quniform(0, V - 1, 1) label
+    'q3' and a choice 'c3' of V options; the loss couples x0 with both."""
+    from hyperopt_amd import base, history as H, hp
+    space = {'x0': hp.uniform('x0', -5, 5), 'x1': hp.loguniform('x1', -3, 2), 'x2': hp.normal('x2', 0, 2),
+             'q3': hp.quniform('q3', 0, V - 1, 1), 'c3': hp.choice('c3', list(range(V)))}
+    domain = base.Domain(lambda d: 0.0, space)
+    rs = np.random.RandomState(SEED)
+    cols = {'x0': rs.uniform(-5, 5, n), 'x1': np.exp(rs.uniform(-3, 2, n)), 'x2': rs.normal(0, 2, n)}
+    q3 = np.rint(rs.uniform(0, V - 1, n))
+    c3 = rs.randint(V, size=n).astype(np.int64)
+    loss = (cols['x0'] - (10.0 * q3 / (V - 1) - 5.0)) ** 2 + (cols['x0'] - (10.0 * c3 / (V - 1) - 5.0)) ** 2 \
+        + 0.1 * (np.log(cols['x1']) - 1.0) ** 2 + 0.1 * cols['x2'] ** 2 + 0.01 * rs.standard_normal(n)
+    tids = np.arange(n, dtype=np.int64)
+    obs = {k: (tids, v) for k, v in cols.items()}
+    obs['q3'] = (tids, q3)
+    obs['c3'] = (tids, c3)
+    return domain, H.History(tids, loss, obs)
+
+
+def main_quant(args):
+    import torch
+    from hyperopt_amd import _native as N, history as H, joint as J
+    from hyperopt_amd.engine import get_engine
+
+    eng = get_engine(None, 'fp32')
+    lib = eng.lib
+    C = args.cand
+    ids = np.array([args.history], dtype=np.int64)
+    models = {}
+    for V in (32, 256):
+        domain, hist = make_quant_history(args.history, V)
+        t = domain.table
+        crows = [r for r in t.rows if J.eligible(r)]
+        below = H.split_below(hist, 0.25)
+        models[V] = J.fit_quant_model(crows, [], [t.by_label['q3']], hist, below, 1.0)
+        if V == 32:
+            mixed = J.fit_mixed_model(crows, [t.by_label['c3']], hist, below, 1.0)
+            cont3 = J.fit_model(crows, hist, below, 1.0)
+
+    def run_quant(V, **kw):
+        m = models[V]
+        return eng.run_joint_quant(m.below[:3], m.above[:3], m.low, m.high, [], m.quants(), ids, C, SEED, **kw)
+
+    def run_mixed(**kw):
+        return eng.run_joint_mixed(mixed.below[:3], mixed.above[:3], mixed.low, mixed.high, mixed.cats(), ids, C,
+                                   SEED, **kw)
+
+    def run_cont3(**kw):
+        return eng.run_joint(cont3.below, cont3.above, cont3.low, cont3.high, ids, C, SEED, **kw)
+
+    def kernel_ms(fn, table=False):
+        ms2, tms = (ctypes.c_double * 2)(), ctypes.c_double(0.0)
+        torch.cuda.synchronize()
+        N.check(lib.tpe_joint_profile(1, None), lib, 'tpe_joint_profile')
+        fn()
+        if table:
+            N.check(lib.tpe_joint_quant_profile(ctypes.byref(tms)), lib, 'tpe_joint_quant_profile')
+        N.check(lib.tpe_joint_profile(0, ms2), lib, 'tpe_joint_profile')
+        return ms2[0], ms2[1], tms.value
+
+    routes = [('quant32', lambda: run_quant(32), True), ('quant256', lambda: run_quant(256), True),
+              ('mixed32', run_mixed, False), ('continuous3', run_cont3, False)]
+    for _ in range(args.warmup):
+        for _, fn, _ in routes:
+            fn()
+    ms = dict((name, []) for name, _, _ in routes)
+    for i in range(args.pairs):
+        for name, fn, table in routes:
+            ms[name].append(kernel_ms(fn, table))
+        print('round %d: %s' % (i, ', '.join('%s %.3f ms' % (name, ms[name][-1][0]) for name, _, _ in routes)),
+              file=sys.stderr, flush=True)
+    # (untimed) the stage's l and g of the first --host-cand sampled vectors against the float64 model
+    n_host = min(C, args.host_cand or 4096)
+    m = models[32]
+    _, cand, dl, dg = run_quant(32, return_cand=True, want_lg=True)
+    z, qi = cand[0, :n_host, :3].astype(np.float64), cand[0, :n_host, 3:].astype(np.int64)
+    err = 0.0
+    for side, dev in ((m.below, dl), (m.above, dg)):
+        ref = J.quant_lpdf_numpy(z, np.zeros((n_host, 0)), qi, side[0], side[1], side[2], m.low, m.high, side[3], [], [],
+                                 [(side[4][:, 0], side[5][:, 0], m.lattices[0][3])])
+        err = max(err, float(np.max(np.abs(dev[0, :n_host] - ref) / np.maximum(1.0, np.abs(ref)))) / 1e-5)
+
+    def stat(name, j=0):
+        x = [r[j] for r in ms[name]]
+        return dict(median=float(np.median(x)), min=min(x), max=max(x), all=x)
+    a, b, c = stat('quant32')['median'], stat('mixed32')['median'], stat('continuous3')['median']
+    line = dict(tool='joint_time --quant', history=args.history, n_cand=C, rounds=args.pairs,
+                k_below=len(m.below[0]), k_above=len(m.above[0]),
+                a_quant32=dict(kernel='k_joint_quant_chunk<4, 0, 1>', chunk_ms=stat('quant32'),
+                               table_ms=stat('quant32', 2), merge_ms=stat('quant32', 1)['median']),
+                a_quant256=dict(kernel='k_joint_quant_chunk<4, 0, 1>', chunk_ms=stat('quant256'),
+                                table_ms=stat('quant256', 2)),
+                b_mixed32=dict(kernel='k_joint_mixed_chunk<4, 1>', chunk_ms=stat('mixed32')),
+                c_continuous3=dict(kernel='k_joint_chunk<3>', chunk_ms=stat('continuous3')),
+                ratio_a_over_b=a / b if b > 0 else None, a_minus_c_ms=a - c,
+                ratio_a256_over_b=stat('quant256')['median'] / b if b > 0 else None,
+                lpdf_err_over_tol=err, host_cand=n_host, gpu=torch.cuda.get_device_name(0))
+    text = json.dumps(line)
+    print(text)
+    out = args.out or os.path.join(ROOT, 'profiles', 'joint_quant_time.jsonl')
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, 'a') as f:
+        f.write(text + '\n')
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--pairs', type=int, default=3)
@@ -167,10 +285,13 @@ def main():
     ap.add_argument('--history', type=int, default=10000)
     ap.add_argument('--host-cand', type=int, default=None)
     ap.add_argument('--mixed', action='store_true')
+    ap.add_argument('--quant', action='store_true')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     if args.mixed:
         return main_mixed(args)
+    if args.quant:
+        return main_quant(args)
     args.out = args.out or os.path.join(ROOT, 'profiles', 'joint_time.jsonl')
 
     import torch
