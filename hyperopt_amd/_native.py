@@ -87,6 +87,10 @@ JOINT_MAX_LATTICE_TOTAL = 512  # TPE_JOINT_MAX_LATTICE_TOTAL: lattice values of 
 JOINT_QFLOOR = -4096.0         # TPE_JOINT_QFLOOR: the smallest stored log2 P_kd(i)
 JOINT_QUANT_MAX_CONT = 8       # continuous / discrete labels beside a quantised one
 JOINT_QUANT_MAX_DISC = 4
+JOINT_WIDE_MAX_DIMS = 64       # TPE_JOINT_WIDE_MAX_DIMS: labels of a wide joint group (continuous only)
+JOINT_WIDE_RECORD_DTYPE = np.dtype([('global_idx', '<i8'), ('l', '<f8'), ('g', '<f8'),
+                                    ('z', '<f8', (JOINT_WIDE_MAX_DIMS,))])
+assert JOINT_WIDE_RECORD_DTYPE.itemsize == 536
 
 
 class Batch(ctypes.Structure):
@@ -137,6 +141,13 @@ class JointArgs(ctypes.Structure):
         ('samp_cum', ctypes.c_void_p), ('samp', ctypes.c_void_p), ('ids', ctypes.c_void_p),
         ('inject', ctypes.c_void_p),
         ('low', ctypes.c_double * JOINT_MAX_DIMS), ('high', ctypes.c_double * JOINT_MAX_DIMS),
+    ]
+
+
+class JointWideArgs(ctypes.Structure):
+    """tpe_joint_wide_args: one tpe_joint_wide_run (tpe_joint_args with 64 bounds)."""
+    _fields_ = JointArgs._fields_[:-2] + [
+        ('low', ctypes.c_double * JOINT_WIDE_MAX_DIMS), ('high', ctypes.c_double * JOINT_WIDE_MAX_DIMS),
     ]
 
 
@@ -315,7 +326,8 @@ EXPORTS = ('tpe_abi_version', 'tpe_last_error', 'tpe_device_count', 'tpe_tile_si
            'tpe_host_threads', 'tpe_host_phases', 'tpe_exchange_allgather', 'tpe_debug_fast_lg',
            'tpe_collectives_issued', 'tpe_scatter_f64', 'tpe_move_ranges', 'tpe_report_scratch_bytes', 'tpe_report',
            'tpe_report_profile', 'tpe_joint_scratch_bytes', 'tpe_joint_run', 'tpe_joint_profile',
-           'tpe_joint_mixed_run', 'tpe_joint_quant_table_bytes', 'tpe_joint_quant_run', 'tpe_joint_quant_profile')
+           'tpe_joint_mixed_run', 'tpe_joint_quant_table_bytes', 'tpe_joint_quant_run', 'tpe_joint_quant_profile',
+           'tpe_joint_wide_scratch_bytes', 'tpe_joint_wide_run', 'tpe_joint_wide_profile')
 
 # host phases of tpe_suggest_tree (tpe_host_phases order)
 PHASES = ('prefit', 'pack', 'launched', 'synced', 'level', 'return', 'recs')
@@ -438,6 +450,12 @@ def load(path=LIB_PATH):
     lib.tpe_joint_quant_run.restype = ctypes.c_int
     lib.tpe_joint_quant_profile.argtypes = [P]
     lib.tpe_joint_quant_profile.restype = ctypes.c_int
+    lib.tpe_joint_wide_scratch_bytes.argtypes = [I32, I32, I32, ctypes.POINTER(ctypes.c_uint64)]
+    lib.tpe_joint_wide_scratch_bytes.restype = ctypes.c_int
+    lib.tpe_joint_wide_run.argtypes = [ctypes.POINTER(JointWideArgs), P, P, P, P, P, ctypes.c_uint64, P]
+    lib.tpe_joint_wide_run.restype = ctypes.c_int
+    lib.tpe_joint_wide_profile.argtypes = [P]
+    lib.tpe_joint_wide_profile.restype = ctypes.c_int
     lib.tpe_joint_profile.argtypes = [I32, P]
     lib.tpe_joint_profile.restype = ctypes.c_int
     lib.tpe_level_profile.argtypes = [ctypes.c_int32]

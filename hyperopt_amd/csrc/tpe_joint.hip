@@ -22,6 +22,9 @@
 //                dimension costs one read at the candidate's own lattice index
 //                (four components a 16-byte read) and one add.
 // k_joint_merge  one wave per new id: the chunk winners in index order.
+// k_joint_wide_sample / k_joint_wide_chunk / k_joint_wide_merge  the continuous
+//                stage for 17 to 64 coordinates ("wide groups" below): the
+//                candidates are drawn by a kernel of their own into scratch.
 // Every reduction has a fixed shape and there are no atomics: the output bytes
 // are a function of the input bytes.
 #include <hip/hip_runtime.h>
@@ -906,6 +909,268 @@ void launch_quant_k(const QuantK& k, unsigned blocks, unsigned lds, hipStream_t 
   else launch_quant_q<CP, 4>(k, blocks, lds, stream, timed);
 }
 
+// -------------------------------------------------------------- wide groups
+// 17 to TPE_JOINT_WIDE_MAX_DIMS continuous coordinates (include/tpe_hip.h "Wide
+// joint stage").  A lane cannot hold 4 x 64 coordinates, and 64 inlined copies
+// of the sampler cannot be unrolled, so the work is split:
+// k_joint_wide_sample  one thread per (id, candidate): k_joint_chunk's draw, word
+//                for word, in a loop over d that is not unrolled.  Block b of an
+//                id (256 consecutive candidates) writes zbuf[(id * nblk + b)]
+//                [d][256]: thread t stores at d * 256 + t, a coalesced store.
+// k_joint_wide_chunk<DP, R>  one workgroup per (id, chunk of 256 R candidates):
+//                loads R candidates' z[DP] per lane from zbuf (coalesced) or
+//                from `inject`, every index a compile-time constant, and scores
+//                them as k_joint_chunk does.  A tile row is read four dimensions
+//                at a time (16-byte broadcast reads of mu and a).
+// k_joint_wide_merge  k_joint_merge on the wide record.
+constexpr int kWD = TPE_JOINT_WIDE_MAX_DIMS;
+static_assert(sizeof(tpe_joint_wide_record) == 24 + 8 * kWD, "layout");
+
+// components per LDS tile: at most 32 KiB of rows, so four workgroups fit a CU's 160 KiB
+constexpr int wide_tile(int DP) { return DP <= 32 ? 128 : ((4096 / DP) & ~7); }
+constexpr int wide_r(int DP) { return DP <= 32 ? 2 : 1; }
+
+struct WideK {
+  int D, C, n_chunks, nblk, inject;
+  int kb, ka;
+  const float *bmu, *ba, *bc, *amu, *aa, *ac;
+  double bbase, abase;
+  const float* zsrc;                // inject: [C][D]; else zbuf [n_ids * nblk][D][256]
+  float* cand;
+  double *l_out, *g_out;
+  tpe_joint_wide_record* chunk_rec; // scratch [n_ids * n_chunks]
+};
+
+struct WideSampK {
+  int D, C, nblk, kb;
+  uint32_t key0, key1, stream_word;
+  const double* cum;
+  const float* samp;
+  const int64_t* ids;
+  float* zbuf;
+  float lo[kWD], hi[kWD];
+};
+
+__global__ __launch_bounds__(kThreads) void k_joint_wide_sample(const WideSampK p) {
+  __shared__ float blo[kWD], bhi[kWD];          // (kernel-argument arrays: constant indices only)
+  const int t = threadIdx.x, D = p.D;
+  if (t == 0) {
+#pragma unroll
+    for (int f = 0; f < kWD; ++f) { blo[f] = p.lo[f]; bhi[f] = p.hi[f]; }
+  }
+  __syncthreads();
+  const int id = blockIdx.x / p.nblk, blk = blockIdx.x % p.nblk;
+  const int i = blk * kThreads + t;
+  if (i >= p.C) return;
+  float* out = p.zbuf + (int64_t)blockIdx.x * kThreads * D + t;
+  const uint32_t c3 = (uint32_t)p.ids[id];
+  U4 w = philox4x32_10((uint32_t)i, 0u, p.stream_word, c3, p.key0, p.key1);
+  const double us = u01w(w.x);
+  int lo = 0, hi = p.kb - 1;               // first k with us < cum[k]
+  while (lo < hi) { const int mid = (lo + hi) >> 1; if (us < p.cum[mid]) hi = mid; else lo = mid + 1; }
+  const float* srow = p.samp + (int64_t)lo * D * 5;
+  // word 1 + d serves dimension d: k_joint_chunk's draw, operation for operation
+#pragma unroll 1
+  for (int d = 0; d < D; ++d) {
+    const int wi = d + 1;
+    if ((wi & 3) == 0) w = philox4x32_10((uint32_t)i, (uint32_t)(wi >> 2), p.stream_word, c3, p.key0, p.key1);
+    const uint32_t word = (wi & 3) == 0 ? w.x : (wi & 3) == 1 ? w.y : (wi & 3) == 2 ? w.z : w.w;
+    const float* sr = srow + d * 5;
+    const float pr = sr[2] + u01f(word) * (sr[3] - sr[2]);
+    float zz = ndtri_f32(pr);
+    if (sr[4] != 0.f) zz = -zz;
+    float x = sr[0] + sr[1] * zz;
+    if (!(x == x)) x = sr[0];
+    out[(int64_t)d * kThreads] = fminf(fmaxf(x, blo[d]), bhi[d]);      // low <= z < high
+  }
+}
+
+// score_side for R candidates a lane; a row is read four dimensions at a time
+template <int DP, int R>
+__device__ __forceinline__ void score_side_wide(const float* __restrict__ mu, const float* __restrict__ a,
+                                                const float* __restrict__ c, int K, int D, const float (&z)[R][DP],
+                                                float* __restrict__ rows, float* __restrict__ cl, double (&out)[R]) {
+  constexpr int TK = wide_tile(DP);
+  float m[R], s[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) { m[r] = -3.0e38f; s[r] = 0.f; }
+  for (int k0 = 0; k0 < K; k0 += TK) {
+    const int nk = min(TK, K - k0);
+    __syncthreads();                       // the previous tile (or side) is read
+    for (int e = threadIdx.x; e < nk * DP; e += kThreads) {
+      const int kk = e / DP, d = e % DP;
+      const bool in = d < D;               // padded dimensions: a = 0 adds nothing
+      const int64_t src = (int64_t)(k0 + kk) * D + d;
+      rows[kk * 2 * DP + d] = in ? mu[src] : 0.f;
+      rows[kk * 2 * DP + DP + d] = in ? a[src] : 0.f;
+    }
+    for (int e = threadIdx.x; e < nk; e += kThreads) cl[e] = c[k0 + e];
+    __syncthreads();
+    for (int kk = 0; kk < nk; ++kk) {
+      const float4* row = reinterpret_cast<const float4*>(rows + kk * 2 * DP);
+      float acc[R];
+#pragma unroll
+      for (int r = 0; r < R; ++r) acc[r] = 0.f;
+#pragma unroll
+      for (int q = 0; q < DP / 4; ++q) {
+        const float4 rm = row[q], ra = row[DP / 4 + q];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          float u = (z[r][4 * q] - rm.x) * ra.x;
+          acc[r] = __builtin_fmaf(u, u, acc[r]);
+          u = (z[r][4 * q + 1] - rm.y) * ra.y;
+          acc[r] = __builtin_fmaf(u, u, acc[r]);
+          u = (z[r][4 * q + 2] - rm.z) * ra.z;
+          acc[r] = __builtin_fmaf(u, u, acc[r]);
+          u = (z[r][4 * q + 3] - rm.w) * ra.w;
+          acc[r] = __builtin_fmaf(u, u, acc[r]);
+        }
+      }
+      const float ck = cl[kk];
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const float t = ck - acc[r];
+        const float dl = t - m[r];
+        const float e2 = __builtin_amdgcn_exp2f(-__builtin_fabsf(dl));
+        s[r] = dl > 0.f ? __builtin_fmaf(s[r], e2, 1.f) : s[r] + e2;
+        m[r] = fmaxf(m[r], t);
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < R; ++r) out[r] = (double)m[r] + log2((double)s[r]);
+}
+
+template <int DP, int R>
+__global__ __launch_bounds__(kThreads) void k_joint_wide_chunk(const WideK p) {
+  static_assert(DP % 4 == 0 && DP <= kWD, "rows are read as float4");
+  constexpr int TK = wide_tile(DP);
+  __shared__ __attribute__((aligned(16))) float rows[TK * 2 * DP];
+  __shared__ float cl[TK];
+  __shared__ Pick slot[kThreads / 64];
+  const int t = threadIdx.x, D = p.D;
+  const int id = blockIdx.x / p.n_chunks, chunk = blockIdx.x % p.n_chunks;
+  const int first = chunk * (R * kThreads);
+
+  float z[R][DP];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+#pragma unroll
+    for (int d = 0; d < DP; ++d) z[r][d] = 0.f;
+    const int i = first + r * kThreads + t;
+    if (i >= p.C) continue;
+    if (p.inject) {
+#pragma unroll
+      for (int d = 0; d < DP; ++d)
+        if (d < D) z[r][d] = p.zsrc[(int64_t)i * D + d];
+    } else {
+      // block chunk * R + r of this id (i < C: the block exists)
+      const float* src = p.zsrc + ((int64_t)id * p.nblk + chunk * R + r) * kThreads * D + t;
+#pragma unroll
+      for (int d = 0; d < DP; ++d)
+        if (d < D) z[r][d] = src[(int64_t)d * kThreads];
+    }
+  }
+
+  double l2[R], g2[R];
+  score_side_wide<DP, R>(p.bmu, p.ba, p.bc, p.kb, D, z, rows, cl, l2);
+  score_side_wide<DP, R>(p.amu, p.aa, p.ac, p.ka, D, z, rows, cl, g2);
+
+  Pick best{0, 0};
+  double lv[R], gv[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int i = first + r * kThreads + t;
+    lv[r] = l2[r] * kLn2 + p.bbase;
+    gv[r] = g2[r] * kLn2 + p.abase;
+    if (i >= p.C) continue;
+    const int64_t o = (int64_t)id * p.C + i;
+    if (p.l_out) p.l_out[o] = lv[r];
+    if (p.g_out) p.g_out[o] = gv[r];
+    if (p.cand)
+#pragma unroll
+      for (int d = 0; d < DP; ++d)
+        if (d < D) p.cand[o * D + d] = z[r][d];
+    const uint64_t key = score_key(lv[r] - gv[r]);
+    if (key > best.key) best = Pick{key, (int64_t)i};   // ascending index: strict > keeps the first of a tie
+  }
+  Pick w = wave_best(best);
+  if ((t & 63) == 0) slot[t >> 6] = w;
+  __syncthreads();
+  w = slot[0];
+#pragma unroll
+  for (int q = 1; q < kThreads / 64; ++q)
+    if (beats(slot[q], w)) w = slot[q];
+
+  tpe_joint_wide_record* rec = p.chunk_rec + blockIdx.x;
+  if (w.key == 0) {
+    if (t == 0) rec->global_idx = -1;
+    return;
+  }
+  const int off = (int)(w.idx - first);
+  if (t != off % kThreads) return;
+  const int wr = off / kThreads;
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    if (r != wr) continue;
+    rec->global_idx = w.idx;
+    rec->l = lv[r];
+    rec->g = gv[r];
+#pragma unroll
+    for (int d = 0; d < kWD; ++d) rec->z[d] = d < DP ? (double)z[r][d < DP ? d : 0] : 0.0;
+  }
+}
+
+__global__ __launch_bounds__(64) void k_joint_wide_merge(const tpe_joint_wide_record* __restrict__ chunk_rec,
+                                                         int n_chunks, tpe_joint_wide_record* __restrict__ records) {
+  const tpe_joint_wide_record* rec = chunk_rec + (int64_t)blockIdx.x * n_chunks;
+  Pick best{0, 0};
+  for (int c = threadIdx.x; c < n_chunks; c += 64) {
+    if (rec[c].global_idx < 0) continue;
+    const Pick x{score_key(rec[c].l - rec[c].g), (int64_t)c};
+    if (beats(x, best)) best = x;            // (chunk order = candidate index order)
+  }
+  const Pick w = wave_best(best);
+  if (threadIdx.x != 0) return;
+  tpe_joint_wide_record* out = records + blockIdx.x;
+  if (w.key == 0) {
+    out->global_idx = -1;
+    out->l = out->g = 0.0;
+    for (int d = 0; d < kWD; ++d) out->z[d] = 0.0;
+  } else {
+    *out = rec[w.idx];
+  }
+}
+
+// start / stop events of the sampling kernel (profiling only)
+struct {
+  int valid;
+  hipEvent_t ev[2];
+} g_wprof = {0, {nullptr, nullptr}};
+
+template <int DP>
+void launch_wide(const WideK& k, unsigned blocks, hipStream_t stream, bool timed) {
+  if (timed)
+    hipExtLaunchKernelGGL((k_joint_wide_chunk<DP, wide_r(DP)>), dim3(blocks), dim3(kThreads), 0u, stream, g_prof.ev[0],
+                          g_prof.ev[1], 0u, k);
+  else
+    hipLaunchKernelGGL((k_joint_wide_chunk<DP, wide_r(DP)>), dim3(blocks), dim3(kThreads), 0, stream, k);
+}
+
+// padded width of a wide group: DP in {20, 24, 32, 48, 64}
+int wide_dp(int D) { return D <= 20 ? 20 : D <= 24 ? 24 : D <= 32 ? 32 : D <= 48 ? 48 : 64; }
+int64_t wide_blocks_of(int32_t n_cand) { return ((int64_t)n_cand + kThreads - 1) / kThreads; }
+int64_t wide_chunks_of(int32_t n_cand, int D) {
+  const int64_t per = (int64_t)kThreads * wide_r(wide_dp(D));
+  return ((int64_t)n_cand + per - 1) / per;
+}
+uint64_t wide_record_bytes(int32_t n_ids, int32_t n_cand, int D) {
+  return (uint64_t)n_ids * (uint64_t)wide_chunks_of(n_cand, D) * sizeof(tpe_joint_wide_record);
+}
+uint64_t wide_zbuf_bytes(int32_t n_ids, int32_t n_cand, int D) {
+  return (uint64_t)n_ids * (uint64_t)wide_blocks_of(n_cand) * kThreads * (uint64_t)D * sizeof(float);
+}
+
 }  // namespace
 
 extern "C" {
@@ -996,6 +1261,112 @@ int tpe_joint_run(const tpe_joint_args* a, tpe_joint_record* records, float* can
   } else {
     hipLaunchKernelGGL(k_joint_merge, dim3((unsigned)a->n_ids), dim3(64), 0, s, (const tpe_joint_record*)scratch,
                        (int)n_chunks, records);
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
+  return TPE_OK;
+}
+
+int tpe_joint_wide_scratch_bytes(int32_t n_ids, int32_t n_cand, int32_t n_dims, uint64_t* bytes) {
+  if (!bytes || n_ids < 1 || n_cand < 1 || n_dims < 1 || n_dims > TPE_JOINT_WIDE_MAX_DIMS)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_wide_scratch_bytes: bad arguments");
+  *bytes = wide_record_bytes(n_ids, n_cand, n_dims) + wide_zbuf_bytes(n_ids, n_cand, n_dims);
+  return TPE_OK;
+}
+
+int tpe_joint_wide_profile(double* sample_ms) {
+  if (!sample_ms || !g_wprof.valid)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_wide_profile: no profiled sampling tpe_joint_wide_run to read");
+  float ms = 0.f;
+  hipError_t e = hipEventSynchronize(g_wprof.ev[1]);
+  if (e == hipSuccess) e = hipEventElapsedTime(&ms, g_wprof.ev[0], g_wprof.ev[1]);
+  if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
+  *sample_ms = (double)ms;
+  return TPE_OK;
+}
+
+int tpe_joint_wide_run(const tpe_joint_wide_args* a, tpe_joint_wide_record* records, float* cand, double* l_out,
+                       double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
+  if (!a) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_wide_run: null args");
+  if (a->n_dims < 1 || a->n_dims > TPE_JOINT_WIDE_MAX_DIMS)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_wide_run: n_dims outside [1, TPE_JOINT_WIDE_MAX_DIMS]");
+  if (a->n_cand < 1) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_wide_run: n_cand < 1");
+  if (a->n_ids < 1) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_wide_run: n_ids < 1");
+  if (a->k_below < 1 || a->k_above < 1)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_wide_run: k_below < 1 or k_above < 1");
+  if (!a->below_mu || !a->below_a || !a->below_c || !a->above_mu || !a->above_a || !a->above_c)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_wide_run: null density rows");
+  const bool inject = (a->flags & TPE_JOINT_INJECT) != 0;
+  if (inject && !a->inject)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_wide_run: TPE_JOINT_INJECT without candidates");
+  if (!inject && (!a->samp_cum || !a->samp)) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_wide_run: null sampler rows");
+  if (!a->ids || !records) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_wide_run: null ids / records");
+  const int D = a->n_dims;
+  const int64_t n_chunks = wide_chunks_of(a->n_cand, D), blocks = n_chunks * a->n_ids;
+  const int64_t nblk = wide_blocks_of(a->n_cand), sblocks = nblk * a->n_ids;
+  if (sblocks > INT32_MAX) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_wide_run: too many candidates");
+  const uint64_t rec_bytes = wide_record_bytes(a->n_ids, a->n_cand, D);
+  const uint64_t need = rec_bytes + wide_zbuf_bytes(a->n_ids, a->n_cand, D);
+  if (!scratch || scratch_bytes < need) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_wide_run: scratch too small");
+
+  const bool timed = g_prof.on != 0;
+  hipStream_t s = (hipStream_t)stream;
+  float* zbuf = (float*)((char*)scratch + rec_bytes);
+  g_wprof.valid = 0;
+  if (!inject) {
+    WideSampK sk;
+    sk.D = D; sk.C = a->n_cand; sk.nblk = (int)nblk; sk.kb = a->k_below;
+    sk.key0 = (uint32_t)a->seed; sk.key1 = (uint32_t)(a->seed >> 32); sk.stream_word = a->stream_word;
+    sk.cum = a->samp_cum; sk.samp = a->samp; sk.ids = a->ids; sk.zbuf = zbuf;
+    for (int d = 0; d < TPE_JOINT_WIDE_MAX_DIMS; ++d) {
+      // f32 bounds: smallest float >= low, largest float < high (as tpe_joint_run)
+      float lo = -INFINITY, hi = INFINITY;
+      if (d < D) {
+        const double L = a->low[d], H = a->high[d];
+        if (L > -INFINITY) { lo = (float)L; if ((double)lo < L) lo = nextafterf(lo, INFINITY); }
+        if (H < INFINITY) { hi = (float)H; while ((double)hi >= H) hi = nextafterf(hi, -INFINITY); }
+      }
+      sk.lo[d] = lo; sk.hi[d] = hi;
+    }
+    if (timed) {
+      if (!g_wprof.ev[0])
+        for (int i = 0; i < 2; ++i) {
+          const hipError_t e = hipEventCreate(&g_wprof.ev[i]);
+          if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
+        }
+      hipExtLaunchKernelGGL(k_joint_wide_sample, dim3((unsigned)sblocks), dim3(kThreads), 0u, s, g_wprof.ev[0],
+                            g_wprof.ev[1], 0u, sk);
+      g_wprof.valid = 1;
+    } else {
+      hipLaunchKernelGGL(k_joint_wide_sample, dim3((unsigned)sblocks), dim3(kThreads), 0, s, sk);
+    }
+  }
+
+  WideK k;
+  k.D = D; k.C = a->n_cand; k.n_chunks = (int)n_chunks; k.nblk = (int)nblk; k.inject = inject ? 1 : 0;
+  k.kb = a->k_below; k.ka = a->k_above;
+  k.bmu = a->below_mu; k.ba = a->below_a; k.bc = a->below_c;
+  k.amu = a->above_mu; k.aa = a->above_a; k.ac = a->above_c;
+  k.bbase = a->below_base; k.abase = a->above_base;
+  k.zsrc = inject ? a->inject : zbuf;
+  k.cand = cand; k.l_out = l_out; k.g_out = g_out;
+  k.chunk_rec = (tpe_joint_wide_record*)scratch;
+
+  const unsigned nb = (unsigned)blocks;
+  switch (wide_dp(D)) {
+    case 20: launch_wide<20>(k, nb, s, timed); break;
+    case 24: launch_wide<24>(k, nb, s, timed); break;
+    case 32: launch_wide<32>(k, nb, s, timed); break;
+    case 48: launch_wide<48>(k, nb, s, timed); break;
+    default: launch_wide<64>(k, nb, s, timed); break;
+  }
+  if (timed) {
+    hipExtLaunchKernelGGL(k_joint_wide_merge, dim3((unsigned)a->n_ids), dim3(64), 0u, s, g_prof.ev[2], g_prof.ev[3],
+                          0u, (const tpe_joint_wide_record*)scratch, (int)n_chunks, records);
+    g_prof.valid = 1;
+  } else {
+    hipLaunchKernelGGL(k_joint_wide_merge, dim3((unsigned)a->n_ids), dim3(64), 0, s,
+                       (const tpe_joint_wide_record*)scratch, (int)n_chunks, records);
   }
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));

@@ -975,15 +975,26 @@ class Engine(object):
         (N.JOINT_RECORD_DTYPE) comes back.  ``inject`` [C, D]: score these
         candidates (every id) instead of sampling.  ``return_cand``: also the
         candidates f32 [n_ids, C, D]; ``want_lg``: also l, g float64 [n_ids, C]."""
+        return self._joint_continuous(False, below, above, low, high, ids, n_cand, seed, inject, return_cand, want_lg)
+
+    def run_joint_wide(self, below, above, low, high, ids, n_cand, seed, inject=None, return_cand=False,
+                       want_lg=False):
+        """``run_joint`` for up to N.JOINT_WIDE_MAX_DIMS dimensions
+        (tpe_joint_wide_run, include/tpe_hip.h "Wide joint stage"): the same
+        arguments, model, Philox streams and return shapes; the records are
+        N.JOINT_WIDE_RECORD_DTYPE."""
+        return self._joint_continuous(True, below, above, low, high, ids, n_cand, seed, inject, return_cand, want_lg)
+
+    def _joint_continuous(self, wide, below, above, low, high, ids, n_cand, seed, inject, return_cand, want_lg):
         from . import joint as J
         low, high = np.asarray(low, dtype=np.float64), np.asarray(high, dtype=np.float64)
         D = len(low)
-        ids, n_ids, C = self._joint_sizes(D, ids, n_cand)
+        ids, n_ids, C = self._joint_sizes(D, ids, n_cand, N.JOINT_WIDE_MAX_DIMS if wide else N.JOINT_MAX_DIMS)
         for side in (below, above):
             if side[1].shape != (len(side[0]), D) or side[2].shape != side[1].shape:
                 raise ValueError('joint stage: mixture shapes do not match %d dimensions' % D)
         up = self._joint_up
-        a = N.JointArgs()
+        a = N.JointWideArgs() if wide else N.JointArgs()
         a.n_dims, a.n_cand, a.n_ids, a.flags = D, C, n_ids, 0
         a.k_below, a.k_above = len(below[0]), len(above[0])
         a.stream_word, a.seed = N.JOINT_STREAM, int(seed) & 0xFFFFFFFFFFFFFFFF
@@ -999,14 +1010,15 @@ class Engine(object):
         self._joint_inject(a, inject, C, D)
         for d in range(D):
             a.low[d], a.high[d] = low[d], high[d]
-        return self._joint_call('tpe_joint_run', a, n_ids, C, D, return_cand, want_lg)
+        return self._joint_call('tpe_joint_wide_run' if wide else 'tpe_joint_run', a, n_ids, C, D, return_cand,
+                                want_lg, wide=wide)
 
     # what run_joint and run_joint_mixed share: the size checks, the uploads, the call and its results
-    def _joint_sizes(self, D, ids, n_cand):
+    def _joint_sizes(self, D, ids, n_cand, max_dims=N.JOINT_MAX_DIMS):
         ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
         n_ids, C = len(ids), int(n_cand)
-        if not 1 <= D <= N.JOINT_MAX_DIMS:
-            raise ValueError('joint stage: %d dimensions, at most %d' % (D, N.JOINT_MAX_DIMS))
+        if not 1 <= D <= max_dims:
+            raise ValueError('joint stage: %d dimensions, at most %d' % (D, max_dims))
         if C < 1 or C >= 2 ** 31 or n_ids < 1:
             raise ValueError('joint stage: n_cand / ids out of range')
         if n_ids * C * max(D, 2) >= 2 ** 31:
@@ -1027,13 +1039,19 @@ class Engine(object):
         a.flags |= N.JOINT_INJECT
         a.inject = self._joint_up('inject', inj, torch.float32)
 
-    def _joint_call(self, fn, a, n_ids, C, D, return_cand, want_lg):
+    def _joint_call(self, fn, a, n_ids, C, D, return_cand, want_lg, wide=False):
         """Scratch and result buffers, the native call ``fn`` and the records
-        (and candidates [n_ids, C, D], l, g [n_ids, C]) on the host."""
+        (and candidates [n_ids, C, D], l, g [n_ids, C]) on the host.  ``wide``:
+        the wide stage's scratch size and record."""
         nb = ctypes.c_uint64(0)
-        N.check(self.lib.tpe_joint_scratch_bytes(n_ids, C, ctypes.byref(nb)), self.lib, 'tpe_joint_scratch_bytes')
+        rec_dtype = N.JOINT_WIDE_RECORD_DTYPE if wide else N.JOINT_RECORD_DTYPE
+        if wide:
+            N.check(self.lib.tpe_joint_wide_scratch_bytes(n_ids, C, D, ctypes.byref(nb)), self.lib,
+                    'tpe_joint_wide_scratch_bytes')
+        else:
+            N.check(self.lib.tpe_joint_scratch_bytes(n_ids, C, ctypes.byref(nb)), self.lib, 'tpe_joint_scratch_bytes')
         d_scr = self._buf('joint_scratch', (nb.value + 7) // 8, torch.float64)
-        d_rec = self._buf('joint_records', n_ids * N.JOINT_RECORD_DTYPE.itemsize // 8, torch.float64)
+        d_rec = self._buf('joint_records', n_ids * rec_dtype.itemsize // 8, torch.float64)
         d_cand = self._buf('joint_cand', n_ids * C * D, torch.float32) if return_cand else None
         d_l = self._buf('joint_l', n_ids * C, torch.float64) if want_lg else None
         d_g = self._buf('joint_g', n_ids * C, torch.float64) if want_lg else None
@@ -1041,7 +1059,7 @@ class Engine(object):
                                       d_l.data_ptr() if want_lg else None, d_g.data_ptr() if want_lg else None,
                                       d_scr.data_ptr(), d_scr.numel() * 8, ctypes.c_void_p(self._stream())),
                 self.lib, fn)
-        rec = d_rec[:n_ids * 19].cpu().numpy().view(N.JOINT_RECORD_DTYPE).copy()
+        rec = d_rec[:n_ids * rec_dtype.itemsize // 8].cpu().numpy().view(rec_dtype).copy()
         if not (return_cand or want_lg):
             return rec
         out = [rec]

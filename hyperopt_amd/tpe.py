@@ -37,7 +37,8 @@ Extensions over the reference (keyword-only, defaults keep its behaviour):
     (joint.py, DESIGN.md "Joint TPE"); every other label as without it.
     ``joint_discrete=True`` lets the group also hold unconditional randint /
     categorical labels that gate no other label, ``joint_quantized=True``
-    unconditional quniform / qloguniform labels of 2 to 256 lattice values.
+    unconditional quniform / qloguniform labels of 2 to 256 lattice values,
+    ``joint_wide=True`` 17 to 64 continuous labels instead of at most 16.
 
 ``linear_forgetting`` is accepted and, as in the reference, not used: the
 forgetting window is fixed at DEFAULT_LF=25 (tpe.py:27-29).
@@ -835,14 +836,14 @@ def suggest(new_ids, domain, trials, seed,
             gamma=_default_gamma,
             linear_forgetting=_default_linear_forgetting,
             sampler='philox', precision='fp32', device=None, shard=None, shard_ids=None, shard_labels=None,
-            shard_grid=None, joint=False, joint_discrete=False, joint_quantized=False):
+            shard_grid=None, joint=False, joint_discrete=False, joint_quantized=False, joint_wide=False):
     new_ids = list(new_ids)
     if not new_ids:
         return []
-    if (joint is not False and joint is not None) or joint_discrete or joint_quantized:
+    if (joint is not False and joint is not None) or joint_discrete or joint_quantized or joint_wide:
         # (argument errors first: no device use, no startup draw)
         _joint_group(domain.table, joint, sampler, precision, (shard, shard_ids, shard_labels, shard_grid),
-                     joint_discrete, joint_quantized)
+                     joint_discrete, joint_quantized, joint_wide)
     t0 = time.time()
     hist = _history.extract(domain, trials)
     if logger.isEnabledFor(logging.INFO):
@@ -857,7 +858,7 @@ def suggest(new_ids, domain, trials, seed,
                               n_EI_candidates=n_EI_candidates, gamma=gamma, sampler=sampler,
                               precision=precision, device=device, shard=shard, shard_ids=shard_ids,
                               shard_labels=shard_labels, shard_grid=shard_grid, joint=joint,
-                              joint_discrete=joint_discrete, joint_quantized=joint_quantized)
+                              joint_discrete=joint_discrete, joint_quantized=joint_quantized, joint_wide=joint_wide)
     logger.info('tpe.suggest took %f seconds', time.time() - t0)
     return rand.docs_from_choices(new_ids, domain, trials, choices)
 
@@ -898,7 +899,7 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
                     n_EI_candidates=_default_n_EI_candidates, gamma=_default_gamma,
                     sampler='philox', precision='fp32', device=None, shard=None, columns=False,
                     shard_ids=None, shard_labels=None, shard_grid=None, joint=False, joint_discrete=False,
-                    joint_quantized=False):
+                    joint_quantized=False, joint_wide=False):
     """The suggest core on a structure-of-arrays history (``history.History``):
     per new id a {label: value or None} dict.  ``suggest`` wraps it with the
     Trials document layout; columnar callers (and bench.py's large configs)
@@ -936,13 +937,20 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
     most 8 continuous and 4 discrete labels (DESIGN.md "Quantised labels in the
     joint stage").  Their joined values are ``np.float64`` multiples of q.
     ``qnormal`` / ``qlognormal`` labels stay univariate.  A group that ends up
-    with no quantised label is the stage without the keyword, byte for byte."""
+    with no quantised label is the stage without the keyword, byte for byte.
+
+    ``joint_wide=True`` (with ``joint``): a group may hold 17 to
+    TPE_JOINT_WIDE_MAX_DIMS = 64 labels, all of them continuous (the labels
+    ``joint`` alone joins); it is scored by the wide stage (DESIGN.md "Wide
+    groups"), whose candidates continue the same Philox streams.  A group of at
+    most 16 labels takes exactly the path without the keyword, byte for byte.
+    64 bounds the set of kernel instantiations; it is not a measured limit."""
     if sampler not in ('philox', 'replay'):
         raise ValueError("sampler must be 'philox' or 'replay'")
     group = None
-    if (joint is not False and joint is not None) or joint_discrete or joint_quantized:
+    if (joint is not False and joint is not None) or joint_discrete or joint_quantized or joint_wide:
         group = _joint_group(table, joint, sampler, precision, (shard, shard_ids, shard_labels, shard_grid),
-                             joint_discrete, joint_quantized)
+                             joint_discrete, joint_quantized, joint_wide)
     if sum(a is not None for a in (shard, shard_ids, shard_labels, shard_grid)) > 1:
         raise ValueError('shard, shard_ids, shard_labels and shard_grid are exclusive: one shard axis per suggest')
     if (shard_ids is not None or shard_labels is not None or shard_grid is not None) and sampler == 'replay':
@@ -959,13 +967,17 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
 
 
 TPE_JOINT_MAX_DIMS = N.JOINT_MAX_DIMS
+TPE_JOINT_WIDE_MAX_DIMS = N.JOINT_WIDE_MAX_DIMS
 
 
-def _joint_group(table, joint, sampler, precision, shards, discrete=False, quantized=False):
+def _joint_group(table, joint, sampler, precision, shards, discrete=False, quantized=False, wide=False):
     """The ParamRows a ``joint`` argument joins, in table order (``discrete`` /
-    ``quantized``: the eligible discrete / quantised labels among them);
+    ``quantized``: the eligible discrete / quantised labels among them;
+    ``wide``: more than TPE_JOINT_MAX_DIMS continuous labels allowed);
     ValueError for every combination the joint stage does not take.  Touches no
     device."""
+    if wide and (joint is False or joint is None):
+        raise ValueError('joint_wide=True needs joint=True or joint=[labels]: it only widens what joint joins')
     if discrete and (joint is False or joint is None):
         raise ValueError('joint_discrete=True needs joint=True or joint=[labels]: it only widens what joint joins')
     if quantized and (joint is False or joint is None):
@@ -1003,8 +1015,19 @@ def _joint_group(table, joint, sampler, precision, shards, discrete=False, quant
     if len(rows) < 2:
         raise ValueError('joint needs at least 2 labels to join, got %d' % len(rows))
     if len(rows) > TPE_JOINT_MAX_DIMS:
-        raise ValueError('joint joins at most TPE_JOINT_MAX_DIMS = %d labels, not %d: pass the labels to join as '
-                         'joint=[...]' % (TPE_JOINT_MAX_DIMS, len(rows)))
+        if not wide:
+            raise ValueError('joint joins at most TPE_JOINT_MAX_DIMS = %d labels, not %d: pass the labels to join as '
+                             'joint=[...]' % (TPE_JOINT_MAX_DIMS, len(rows)))
+        if len(rows) > TPE_JOINT_WIDE_MAX_DIMS:
+            raise ValueError('joint with joint_wide=True joins at most TPE_JOINT_WIDE_MAX_DIMS = %d labels, not %d: '
+                             'pass the labels to join as joint=[...]' % (TPE_JOINT_WIDE_MAX_DIMS, len(rows)))
+        n_disc = sum(1 for r in rows if r.categorical)
+        n_quant = sum(1 for r in rows if r.dist in _joint.QUANT_DISTS)
+        if n_disc or n_quant:
+            raise ValueError('joint with joint_wide=True: a group of more than TPE_JOINT_MAX_DIMS = %d labels joins '
+                             'continuous labels only, not %d discrete and %d quantised ones among its %d: pass the '
+                             'labels to join as joint=[...]' % (TPE_JOINT_MAX_DIMS, n_disc, n_quant, len(rows)))
+        return rows
     n_cats = sum(int(r.args['upper']) for r in rows if r.categorical)
     if n_cats > N.JOINT_MAX_CAT_TOTAL:
         raise ValueError('joint joins discrete labels of at most TPE_JOINT_MAX_CAT_TOTAL = %d categories in all, not '
@@ -1064,7 +1087,9 @@ def _suggest_joint(table, hist, new_ids, seed, prior_weight, n_EI_candidates, ga
                                      int(n_EI_candidates), seed)
     else:
         model = _joint.fit_model(group, hist, _history.split_below(hist, gamma), prior_weight, DEFAULT_LF)
-        rec = engine.run_joint(model.below, model.above, model.low, model.high, ids, int(n_EI_candidates), seed)
+        # more than TPE_JOINT_MAX_DIMS labels (joint_wide=True let them through): the wide stage
+        run = engine.run_joint_wide if len(group) > TPE_JOINT_MAX_DIMS else engine.run_joint
+        rec = run(model.below, model.above, model.low, model.high, ids, int(n_EI_candidates), seed)
     if (rec['global_idx'] < 0).any():
         raise RuntimeError('no joint candidate selected')
     vals = model.values(rec['z'][:, :len(group)])

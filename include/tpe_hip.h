@@ -1081,9 +1081,74 @@ int tpe_joint_run(const tpe_joint_args* args, tpe_joint_record* records, float* 
                   void* scratch, uint64_t scratch_bytes, void* stream);
 
 /* Profiling only (tools/joint_time.py), as tpe_report_profile: last_ms gets the
- * device times {chunk kernel, merge kernel} of the last profiled tpe_joint_run
- * or tpe_joint_mixed_run. */
+ * device times {chunk kernel, merge kernel} of the last profiled tpe_joint_run,
+ * tpe_joint_mixed_run, tpe_joint_quant_run or tpe_joint_wide_run. */
 int tpe_joint_profile(int32_t enable, double* last_ms);
+
+/* ------------------------------------------------------------------------
+ * Wide joint stage (tpe_joint.hip; additive to ABI 24): the stage above for a
+ * group of up to TPE_JOINT_WIDE_MAX_DIMS continuous labels.  The model, the
+ * density and sampler rows, the score and the winner's order are those of
+ * tpe_joint_run; only where the data lives differs, and the record and the
+ * bounds are 64 wide.  64 bounds the set of kernel instantiations (padded
+ * widths 20, 24, 32, 48, 64); it is a condition, not a measurement.
+ *
+ * The Philox streams are tpe_joint_run's, continued: word 1 + d of candidate i
+ * serves dimension d, that is word (1 + d) & 3 of block (1 + d) >> 2 (D = 64:
+ * blocks 0 to 16).  A wide run and a tpe_joint_run over the same model cut to
+ * its first D' <= TPE_JOINT_MAX_DIMS dimensions (same seed, stream_word and
+ * ids) draw the same f32 coordinates in those dimensions, bit for bit.
+ *
+ * Three launches: k_joint_wide_sample (skipped under TPE_JOINT_INJECT) draws
+ * one candidate a thread in a loop over d and writes it to `scratch`, laid out
+ * [256-candidate block][d][256] so that its stores and the scoring kernel's
+ * loads are coalesced; k_joint_wide_chunk<DP, R> (one workgroup per id and
+ * chunk of 256 R candidates, R = 2 for DP <= 32 and 1 above) loads them into
+ * registers and scores them as k_joint_chunk does, both sides' rows streaming
+ * through LDS in tiles of at most 32 KiB; k_joint_wide_merge picks an id's
+ * winner from its chunks in index order.  No atomics: the same call twice
+ * gives the same bytes.
+ *
+ * tpe_joint_wide_run accepts n_dims in [1, TPE_JOINT_WIDE_MAX_DIMS] (so it can
+ * be compared with tpe_joint_run at n_dims <= TPE_JOINT_MAX_DIMS) and returns
+ * TPE_E_ARG before any launch (no device needed) for everything tpe_joint_run
+ * rejects, n_dims outside that range, or scratch smaller than
+ * tpe_joint_wide_scratch_bytes(n_ids, n_cand, n_dims).
+ * ---------------------------------------------------------------------- */
+#define TPE_JOINT_WIDE_MAX_DIMS 64
+typedef struct tpe_joint_wide_record {
+  int64_t global_idx;          /* the winner's candidate index */
+  double l, g;
+  double z[TPE_JOINT_WIDE_MAX_DIMS];   /* its coordinates (entries from n_dims on: 0) */
+} tpe_joint_wide_record;
+typedef struct tpe_joint_wide_args {
+  int32_t n_dims, n_cand, n_ids, flags;   /* as tpe_joint_args ... */
+  int32_t k_below, k_above;
+  uint32_t stream_word;
+  int32_t reserved;
+  uint64_t seed;
+  const float *below_mu, *below_a, *below_c;
+  const float *above_mu, *above_a, *above_c;
+  double below_base, above_base;
+  const double* samp_cum;
+  const float* samp;
+  const int64_t* ids;
+  const float* inject;
+  double low[TPE_JOINT_WIDE_MAX_DIMS], high[TPE_JOINT_WIDE_MAX_DIMS];   /* ... with 64 bounds */
+} tpe_joint_wide_args;
+
+/* the chunk records and the candidate block of one tpe_joint_wide_run */
+int tpe_joint_wide_scratch_bytes(int32_t n_ids, int32_t n_cand, int32_t n_dims, uint64_t* bytes);
+
+/* as tpe_joint_run: records device [n_ids]; optional cand device f32
+ * [n_ids * n_cand * n_dims], l_out / g_out device f64 [n_ids * n_cand] */
+int tpe_joint_wide_run(const tpe_joint_wide_args* args, tpe_joint_wide_record* records, float* cand, double* l_out,
+                       double* g_out, void* scratch, uint64_t scratch_bytes, void* stream);
+
+/* Profiling only: while tpe_joint_profile is enabled a sampling
+ * tpe_joint_wide_run also times k_joint_wide_sample; this reads that time (ms)
+ * of the last such run (it WAITS for it). */
+int tpe_joint_wide_profile(double* sample_ms);
 
 /* ------------------------------------------------------------------------
  * Mixed joint stage (tpe_joint.hip; additive to ABI 24): a group of n_dims

@@ -1,6 +1,6 @@
 """Time the joint TPE stage against the host route.
 Usage: python tools/joint_time.py [--pairs 3] [--warmup 1] [--cand 1048576] [--history 10000]
-                                  [--host-cand N] [--out FILE] [--mixed | --quant]
+                                  [--host-cand N] [--out FILE] [--mixed | --quant | --wide]
 
 Workload: a flat space of 4 continuous labels (uniform, loguniform, normal,
 uniform), a seeded 10,000-trial history whose loss has an x0 * x1 term, one
@@ -43,7 +43,20 @@ alternating in one process, each chunk kernel by its own events; the two table
 launches of (a) and (a256) by theirs (tpe_joint_quant_profile).  The line
 carries the medians and ranges, (a) / (b), (a) - (c), and the worst l / g error
 of the first --host-cand (default 4096) sampled vectors of (a) as a fraction of
-the lpdf tolerance; --out defaults to profiles/joint_quant_time.jsonl."""
+the lpdf tolerance; --out defaults to profiles/joint_quant_time.jsonl.
+
+--wide: the wide stage (DESIGN.md "Wide groups").  Flat spaces of D labels of
+hp.uniform(-5, 5) with the same history size; per round one run of
+Engine.run_joint at D = 16 (k_joint_chunk<16>: the yardstick) and one of
+Engine.run_joint_wide at each of D = 20, 32 and 64, alternating in one
+process, the chunk kernels by their own events (tpe_joint_profile) and the
+sampling kernel by its own (tpe_joint_wide_profile).  The line carries per run
+the medians and ranges, the (candidate x component x dimension) evaluations per
+second of the chunk kernel and their ratio to the yardstick's; the worst l / g
+error of the first --host-cand (default 1024) sampled vectors at D = 64 as a
+fraction of the lpdf tolerance; and the host route at D = 20: joint.lpdf_numpy on
+both sides of those --host-cand vectors, measured and scaled linearly to C.
+--out defaults to profiles/joint_wide_time.jsonl."""
 import argparse
 import ctypes
 import json
@@ -277,6 +290,106 @@ def main_quant(args):
     return 0
 
 
+def make_flat_history(n, D):
+    """D labels of hp.uniform(-5, 5) (bench.py config 4's space at D = 20), a
+    seeded history whose loss is a shifted bowl with one product term."""
+    from hyperopt_amd import base, history as H, hp
+    labels = ['x%02d' % i for i in range(D)]
+    domain = base.Domain(lambda d: 0.0, {k: hp.uniform(k, -5, 5) for k in labels})
+    rs = np.random.RandomState(SEED + D)
+    X = rs.uniform(-5, 5, (n, D))
+    loss = ((X - np.linspace(-2, 2, D)[None, :]) ** 2).sum(axis=1) + X[:, 0] * X[:, 1] + 0.01 * rs.standard_normal(n)
+    tids = np.arange(n, dtype=np.int64)
+    return domain, H.History(tids, loss, {k: (tids, X[:, i]) for i, k in enumerate(labels)})
+
+
+def main_wide(args):
+    import torch
+    from hyperopt_amd import _native as N, history as H, joint as J
+    from hyperopt_amd.engine import get_engine
+
+    eng = get_engine(None, 'fp32')
+    lib = eng.lib
+    C = args.cand
+    ids = np.array([args.history], dtype=np.int64)
+    dims = (16, 20, 32, 64)
+    models = {}
+    for D in dims:
+        domain, hist = make_flat_history(args.history, D)
+        models[D] = J.fit_model(list(domain.table.rows), hist, H.split_below(hist, 0.25), 1.0)
+
+    def run(D, **kw):
+        m = models[D]
+        fn = eng.run_joint if D <= N.JOINT_MAX_DIMS else eng.run_joint_wide
+        return fn(m.below, m.above, m.low, m.high, ids, C, SEED, **kw)
+
+    def kernel_ms(D):
+        ms2, sms = (ctypes.c_double * 2)(), ctypes.c_double(0.0)
+        torch.cuda.synchronize()
+        N.check(lib.tpe_joint_profile(1, None), lib, 'tpe_joint_profile')
+        run(D)
+        if D > N.JOINT_MAX_DIMS:
+            N.check(lib.tpe_joint_wide_profile(ctypes.byref(sms)), lib, 'tpe_joint_wide_profile')
+        N.check(lib.tpe_joint_profile(0, ms2), lib, 'tpe_joint_profile')
+        return ms2[0], ms2[1], sms.value
+
+    for _ in range(args.warmup):
+        for D in dims:
+            run(D)
+    ms = dict((D, []) for D in dims)
+    for i in range(args.pairs):
+        for D in dims:
+            ms[D].append(kernel_ms(D))
+        print('round %d: %s' % (i, ', '.join('D=%d %.3f ms' % (D, ms[D][-1][0]) for D in dims)), file=sys.stderr,
+              flush=True)
+
+    # (untimed) l and g of the first --host-cand sampled vectors against the float64 model, at D = 64
+    # and D = 20; the D = 20 evaluation is also the host route's measured time
+    n_host = min(C, args.host_cand or 1024)
+    err, host_ms = {}, None
+    for D in (64, 20):
+        m = models[D]
+        _, cand, dl, dg = run(D, return_cand=True, want_lg=True)
+        z = cand[0, :n_host].astype(np.float64)
+        t0 = time.perf_counter()
+        refs = [J.lpdf_numpy(z, side[0], side[1], side[2], m.low, m.high) for side in (m.below, m.above)]
+        if D == 20:
+            host_ms = (time.perf_counter() - t0) * 1e3
+        err[D] = max(float(np.max(np.abs(dev[0, :n_host] - ref) / np.maximum(1.0, np.abs(ref))))
+                     for dev, ref in zip((dl, dg), refs)) / 1e-5
+
+    def stat(D, j=0):
+        x = [r[j] for r in ms[D]]
+        return dict(median=float(np.median(x)), min=min(x), max=max(x), all=x)
+
+    def rate(D):
+        m = models[D]
+        k = stat(D)['median']
+        return float(C) * (len(m.below[0]) + len(m.above[0])) * D / (k * 1e-3) if k > 0 else None
+    yard = rate(16)
+    runs = {}
+    for D in dims:
+        m = models[D]
+        wide = D > N.JOINT_MAX_DIMS
+        dp = D if not wide else (20 if D <= 20 else 24 if D <= 24 else 32 if D <= 32 else 48 if D <= 48 else 64)
+        runs['D%d' % D] = dict(
+            kernel='k_joint_wide_chunk<%d, %d>' % (dp, 2 if dp <= 32 else 1) if wide else 'k_joint_chunk<16>',
+            n_dims=D, k_below=len(m.below[0]), k_above=len(m.above[0]), chunk_ms=stat(D),
+            merge_ms=stat(D, 1)['median'], sample_ms=stat(D, 2) if wide else None,
+            evals_per_s=rate(D), ratio_to_yardstick=rate(D) / yard if yard else None)
+    line = dict(tool='joint_time --wide', history=args.history, n_cand=C, rounds=args.pairs, runs=runs,
+                lpdf_err_over_tol_D64=err[64], lpdf_err_over_tol_D20=err[20], host_cand=n_host,
+                host_route_D20_ms=dict(measured_for_host_cand=host_ms, scaled_to_all_candidates=host_ms * C / n_host),
+                gpu=torch.cuda.get_device_name(0))
+    text = json.dumps(line)
+    print(text)
+    out = args.out or os.path.join(ROOT, 'profiles', 'joint_wide_time.jsonl')
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, 'a') as f:
+        f.write(text + '\n')
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--pairs', type=int, default=3)
@@ -286,12 +399,15 @@ def main():
     ap.add_argument('--host-cand', type=int, default=None)
     ap.add_argument('--mixed', action='store_true')
     ap.add_argument('--quant', action='store_true')
+    ap.add_argument('--wide', action='store_true')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     if args.mixed:
         return main_mixed(args)
     if args.quant:
         return main_quant(args)
+    if args.wide:
+        return main_wide(args)
     args.out = args.out or os.path.join(ROOT, 'profiles', 'joint_time.jsonl')
 
     import torch
