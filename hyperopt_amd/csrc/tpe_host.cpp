@@ -876,7 +876,12 @@ void fill_label(const PackLevel& lv, int32_t li) {
         const double step = inv > 0 ? 1.0 / (double)inv : 0.0;
         const size_t g0 = (size_t)sc.grid;
         int32_t* __restrict__ gp = lv.grid + g0;
-        if (!(inv > 0)) memset(gp, 0, (size_t)G * sizeof(int32_t));
+        // (every f32 mean equal: bucket 0 starts at component 0, no mean lies past
+        // it — the later buckets say k, so a reader's window holds every component)
+        if (!(inv > 0)) {
+          gp[0] = 0;
+          for (int64_t g = 1; g < G; ++g) gp[g] = (int32_t)k;
+        }
         if (inv > 0) {
           // four interleaved histograms: sorted mu puts neighbours in the same
           // bucket, and one array would chain every increment through memory

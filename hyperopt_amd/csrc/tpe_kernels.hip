@@ -4288,10 +4288,10 @@ struct FitCtx {
     if (i == pos) return pw;
     if (!ramp) return 1.0;
     const int64_t r = src.rank(i < pos ? i : i - 1);
-    if (r >= num) return 1.0;
-    if (r == num - 1) return 1.0;
-    if (num == 1) return start;
-    return __dadd_rn(__dmul_rn((double)r, step), start);        // linspace: i * step + start
+    // np.linspace(1 / n, 1, num): i * step + start with the exact endpoint 1 —
+    // except num == 1, whose only entry is start (step = 0)
+    if (r >= (num > 1 ? num - 1 : num)) return 1.0;
+    return __dadd_rn(__dmul_rn((double)r, step), start);
   }
 };
 
@@ -4547,6 +4547,15 @@ __device__ __forceinline__ double* wide_sigmas(const tpe_fit_job& j, double* scr
   const int64_t nc = (K + kFitChunk - 1) / kFitChunk;
   return scratch + j.seg_off + kFitHdrParts + 12 * nc;
 }
+// the candidates a job of K components lists: at most kWideCap, and no more
+// than its scratch segment — at least K - 1 entries (include/tpe_hip.h,
+// fit_seg) — holds after the header and the chunk statistics (a small job
+// whose sigmas are nearly all above 2 smin; past it k_fit_wide examines every
+// component, as past kWideCap)
+__device__ __forceinline__ uint32_t wide_cap(int64_t K) {
+  const int64_t nc = (K + kFitChunk - 1) / kFitChunk;
+  return (uint32_t)max<int64_t>(0, min<int64_t>(kWideCap, K - 1 - (kFitHdrParts + 12 * nc)));
+}
 
 // Delta mode: the stretches of the chunks that hold delta entries gathered
 // into their slots, before k_fit_main.  Workgroup (k, job): delta entry k's
@@ -4632,6 +4641,9 @@ __global__ __launch_bounds__(kFitThreads) __attribute__((amdgpu_waves_per_eu(6))
   const bool ramp = j.lf > 0 && j.lf < n;
   const int64_t num = n - j.lf;
   const double start = 1.0 / (double)n, step = num > 1 ? (1.0 - start) / (double)(num - 1) : 0.0;
+  // ranks on the ramp proper: linspace's endpoint (rank num - 1) is exactly 1,
+  // except num == 1, whose only entry is start (FitCtx::weight)
+  const int64_t n_ramp = num > 1 ? num - 1 : num;
   const bool bounded = j.family != TPE_FAM_LOGGAUSS && (j.flags & (TPE_F_HAS_LOW | TPE_F_HAS_HIGH));
   const double cm = fit_cm_bound(j, K), thr0 = 2.0 * smin;
   // most components sit at the clip: their a and log2(se) once (fit_row's values)
@@ -4640,6 +4652,7 @@ __global__ __launch_bounds__(kFitThreads) __attribute__((amdgpu_waves_per_eu(6))
   float4* __restrict__ C = comp + j.above_off;
   uint32_t* __restrict__ wl = wide_scratch + j.seg_off;
   double* __restrict__ wsg = wide_sigmas(j, scratch, K);
+  const uint32_t wcap = wide_cap(K);
   double W = 0, M = 0, sm_all = 0, s_lo = 0;
   double sm[kThr];
   int cnt[kThr];
@@ -4664,7 +4677,7 @@ __global__ __launch_bounds__(kFitThreads) __attribute__((amdgpu_waves_per_eu(6))
       w = 1.0;
       if (ramp) {
         const int64_t r = lrk[li];
-        if (r < num - 1) w = __dadd_rn(__dmul_rn((double)r, step), start);    // linspace: i * step + start
+        if (r < n_ramp) w = __dadd_rn(__dmul_rn((double)r, step), start);    // linspace: i * step + start
       }
     }
     const double se = fmax(sg, kEPS);
@@ -4682,7 +4695,7 @@ __global__ __launch_bounds__(kFitThreads) __attribute__((amdgpu_waves_per_eu(6))
     if (bounded) M += w * (ncdf_fit(j.high, mu, sg) - ncdf_fit(j.low, mu, sg));
     if (i == pos || sg > thr0) {
       const uint32_t slot = atomicAdd(&wl[0], 1u);
-      if (slot < (uint32_t)kWideCap) { wl[1 + slot] = (uint32_t)i; wsg[slot] = i == pos ? INFINITY : sg; }
+      if (slot < wcap) { wl[1 + slot] = (uint32_t)i; wsg[slot] = i == pos ? INFINITY : sg; }
     }
     if (i != pos) {
       sm_all = fmax(sm_all, sg);
@@ -4722,7 +4735,11 @@ __global__ __launch_bounds__(kFitThreads) __attribute__((amdgpu_waves_per_eu(6))
     const float ginv = ghi > glo ? (float)((double)G / (ghi - glo)) : 0.f;
     int ga, gb;
     if (!(ginv > 0.f)) {
-      ga = 0; gb = c0 == 0 ? G : 0;                  // every bucket 0, written by the first chunk
+      // every f32 mean equal: bucket 0 starts at component 0 and no mean lies
+      // past it (every later bucket K, as past the last mean of a proper grid:
+      // a reader's window [grid[bl], grid[bh]) then holds every component);
+      // written by the first chunk
+      ga = 0; gb = c0 == 0 ? G : 0;
     } else {
       auto first_above = [&](double m) {             // first g in [0, G] with edge_g > m (G: none)
         int lo = 0, hi = G;
@@ -4753,7 +4770,7 @@ __global__ __launch_bounds__(kFitThreads) __attribute__((amdgpu_waves_per_eu(6))
   const double glo = s_glo;
   const float ginv = s_ginv;
   for (int g = ga + (int)threadIdx.x; g < gb; g += kFitThreads) {
-    if (!(ginv > 0.f)) { Gp[g] = 0; continue; }
+    if (!(ginv > 0.f)) { Gp[g] = g == 0 ? 0 : (int32_t)K; continue; }
     const double edge = glo + (double)g / (double)ginv;
     int64_t lo = c0, hi = c1;                      // first i with !(mu32[i] < edge) (c1: none in the chunk)
     while (lo < hi) {
@@ -4826,10 +4843,11 @@ __global__ __launch_bounds__(64) void k_fit_wide(const tpe_fit_job* __restrict__
   __syncthreads();
   // the candidates above thr (at most 15 and the prior: thr's definition); past
   // the candidate list's capacity every component is examined
-  const int64_t m = n_cand <= (uint32_t)kWideCap ? (int64_t)n_cand : K;
+  const bool listed = n_cand <= wide_cap(K);
+  const int64_t m = listed ? (int64_t)n_cand : K;
   for (int64_t q = threadIdx.x; q < m; q += 64) {
-    const int64_t i = n_cand <= (uint32_t)kWideCap ? (int64_t)wl[1 + q] : q;
-    const double sg = n_cand <= (uint32_t)kWideCap ? wsg[q] : (i == c.pos ? INFINITY : c.sigma(i));
+    const int64_t i = listed ? (int64_t)wl[1 + q] : q;
+    const double sg = listed ? wsg[q] : (i == c.pos ? INFINITY : c.sigma(i));
     if (sg > thr) {
       const int slot = atomicAdd(&s_nw, 1);
       if (slot < kPruneWide) wide_ix[slot] = i;

@@ -433,7 +433,9 @@ def prune_tables(mu, a, c):
     inv = np.float32(G / (hi - lo)) if hi > lo else np.float32(0.0)
     edges = lo + np.arange(G, dtype=np.float64) * (1.0 / float(inv) if inv > 0 else 0.0)
     grid = np.empty(G + 1, dtype=np.int32)
-    grid[:G] = np.searchsorted(mu32, edges, side='left') if inv > 0 else 0
+    # (every f32 mean equal: bucket 0 starts at component 0 and no mean lies past
+    # it, so the later buckets say K and a reader's window holds every component)
+    grid[:G] = np.searchsorted(mu32, edges, side='left') if inv > 0 else np.where(np.arange(G) == 0, 0, K)
     grid[G] = K
     meta = dict(prior_mu=float(mu[anchor]), prior_a=float(a[anchor]), prior_c=float(c[anchor]),
                 narrow_cmax=float(np.max(np.asarray(c)[narrow])), narrow_amin=float(np.min(np.asarray(a)[narrow])),

@@ -177,6 +177,29 @@ def test_native_pack_matches_numpy_packer(precision):
             assert N.TAB_CELLS not in modes
 
 
+def test_native_pack_degenerate_grid():
+    """A pruned above mixture whose f32 means are all equal (every observation
+    at prior_mu): grid_inv = 0, bucket 0 starts at component 0 and every later
+    bucket says K — no mean lies past bucket 0 — so the readers' window
+    [grid[bl], grid[bh]) (bl = 0, bh = 2 at grid_inv = 0) holds every
+    component; the native and the numpy packer agree."""
+    rs = np.random.RandomState(8)
+    post = parzen.fit_posterior('uniform', dict(low=-5.0, high=5.0), rs.uniform(-5, 5, 9), np.zeros(100), 1.0)
+    K = 101
+    assert np.all(post.above[1] == 0.0) and len(post.above[1]) == K
+    lps = [LevelProblem(post, 3, np.array([100]))]
+    e = _engine('fp32')
+    ref = e._build_numpy(lps, 24, 77, 10, None)
+    info = e._pack(lps, 24, 77, 10, None)
+    p = _blob(e, info, info.off_problems, N.PROBLEM_DTYPE, 1)[0]
+    G = int(p['grid_n'])
+    assert G == 4 * K and p['grid_inv'] == 0.0 and p['wide_len'] > 0 and p['narrow_amin'] > 0
+    g = _blob(e, info, info.off_grid, np.int32, ref['grid'].size)
+    np.testing.assert_array_equal(g, ref['grid'])
+    at = int(p['grid_off'])
+    np.testing.assert_array_equal(g[at:at + G + 1], [0] + [K] * G)
+
+
 def test_native_pack_chunked_sides_match_numpy_packer():
     """A level with >= 16384 components of large tabulated f32 sides: their
     rows and acceptance terms come from the chunk tasks (the mass folded into
