@@ -183,6 +183,43 @@ class JointQuantArgs(ctypes.Structure):
     ]
 
 
+class JointSeg(ctypes.Structure):
+    """tpe_joint_seg: the device descriptor of one group of a tpe_joint_seg_run."""
+    _fields_ = [
+        ('n_dims', ctypes.c_int32), ('k_below', ctypes.c_int32), ('k_above', ctypes.c_int32),
+        ('stream_word', ctypes.c_uint32),
+        ('below_base', ctypes.c_double), ('above_base', ctypes.c_double),
+        ('below_mu', ctypes.c_int64), ('below_a', ctypes.c_int64), ('below_c', ctypes.c_int64),
+        ('above_mu', ctypes.c_int64), ('above_a', ctypes.c_int64), ('above_c', ctypes.c_int64),
+        ('samp', ctypes.c_int64), ('inject', ctypes.c_int64), ('samp_cum', ctypes.c_int64),
+        ('lo', ctypes.c_float * JOINT_MAX_DIMS), ('hi', ctypes.c_float * JOINT_MAX_DIMS),
+    ]
+
+
+# numpy mirror of tpe_joint_seg (an array of them is uploaded in one transfer)
+JOINT_SEG_DTYPE = np.dtype([
+    ('n_dims', '<i4'), ('k_below', '<i4'), ('k_above', '<i4'), ('stream_word', '<u4'),
+    ('below_base', '<f8'), ('above_base', '<f8'),
+    ('below_mu', '<i8'), ('below_a', '<i8'), ('below_c', '<i8'),
+    ('above_mu', '<i8'), ('above_a', '<i8'), ('above_c', '<i8'),
+    ('samp', '<i8'), ('inject', '<i8'), ('samp_cum', '<i8'),
+    ('lo', '<f4', (JOINT_MAX_DIMS,)), ('hi', '<f4', (JOINT_MAX_DIMS,))])
+assert JOINT_SEG_DTYPE.itemsize == ctypes.sizeof(JointSeg) == 232
+
+
+class JointSegArgs(ctypes.Structure):
+    """tpe_joint_seg_args: one tpe_joint_seg_run."""
+    _fields_ = [
+        ('n_segs', ctypes.c_int32), ('n_probs', ctypes.c_int32), ('n_cand', ctypes.c_int32), ('flags', ctypes.c_int32),
+        ('seed', ctypes.c_uint64),
+        ('segs', ctypes.c_void_p), ('host_segs', ctypes.c_void_p),
+        ('pool_f32', ctypes.c_void_p), ('pool_f64', ctypes.c_void_p),
+        ('pool_f32_len', ctypes.c_int64), ('pool_f64_len', ctypes.c_int64),
+        ('prob_seg', ctypes.c_void_p), ('host_prob_seg', ctypes.c_void_p),
+        ('prob_id', ctypes.c_void_p), ('cand_off', ctypes.c_void_p),
+    ]
+
+
 class LabelIn(ctypes.Structure):
     _fields_ = [
         ('family', ctypes.c_int32), ('flags', ctypes.c_int32), ('upper', ctypes.c_int32),
@@ -327,7 +364,8 @@ EXPORTS = ('tpe_abi_version', 'tpe_last_error', 'tpe_device_count', 'tpe_tile_si
            'tpe_collectives_issued', 'tpe_scatter_f64', 'tpe_move_ranges', 'tpe_report_scratch_bytes', 'tpe_report',
            'tpe_report_profile', 'tpe_joint_scratch_bytes', 'tpe_joint_run', 'tpe_joint_profile',
            'tpe_joint_mixed_run', 'tpe_joint_quant_table_bytes', 'tpe_joint_quant_run', 'tpe_joint_quant_profile',
-           'tpe_joint_wide_scratch_bytes', 'tpe_joint_wide_run', 'tpe_joint_wide_profile')
+           'tpe_joint_wide_scratch_bytes', 'tpe_joint_wide_run', 'tpe_joint_wide_profile',
+           'tpe_joint_seg_scratch_bytes', 'tpe_joint_seg_run')
 
 # host phases of tpe_suggest_tree (tpe_host_phases order)
 PHASES = ('prefit', 'pack', 'launched', 'synced', 'level', 'return', 'recs')
@@ -456,6 +494,10 @@ def load(path=LIB_PATH):
     lib.tpe_joint_wide_run.restype = ctypes.c_int
     lib.tpe_joint_wide_profile.argtypes = [P]
     lib.tpe_joint_wide_profile.restype = ctypes.c_int
+    lib.tpe_joint_seg_scratch_bytes.argtypes = [I32, I32, ctypes.POINTER(ctypes.c_uint64)]
+    lib.tpe_joint_seg_scratch_bytes.restype = ctypes.c_int
+    lib.tpe_joint_seg_run.argtypes = [ctypes.POINTER(JointSegArgs), P, P, P, P, P, ctypes.c_uint64, P]
+    lib.tpe_joint_seg_run.restype = ctypes.c_int
     lib.tpe_joint_profile.argtypes = [I32, P]
     lib.tpe_joint_profile.restype = ctypes.c_int
     lib.tpe_level_profile.argtypes = [ctypes.c_int32]

@@ -22,6 +22,10 @@
 //                dimension costs one read at the candidate's own lattice index
 //                (four components a 16-byte read) and one add.
 // k_joint_merge  one wave per new id: the chunk winners in index order.
+// k_joint_seg_order / k_joint_seg_chunk  k_joint_chunk over the (id, group)
+//                problems of many groups at once ("segmented stage" below): a
+//                workgroup reads its problem's group descriptor, then runs the
+//                same device code; k_joint_merge serves it unchanged.
 // k_joint_wide_sample / k_joint_wide_chunk / k_joint_wide_merge  the continuous
 //                stage for 17 to 64 coordinates ("wide groups" below): the
 //                candidates are drawn by a kernel of their own into scratch.
@@ -138,14 +142,31 @@ __device__ __forceinline__ void score_side(const float* __restrict__ mu, const f
   for (int r = 0; r < kR; ++r) out[r] = (double)m[r] + log2((double)s[r]);
 }
 
+// What one workgroup of k_joint_chunk / k_joint_seg_chunk works on: the model
+// rows, the Philox words and the outputs of ONE (id, group) problem.  Every
+// field is wave-uniform.
+struct ChunkIO {
+  int D, C, inject;
+  int kb, ka;
+  uint32_t key0, key1, stream_word, c3;   // c3: the new id's low word
+  const float *bmu, *ba, *bc, *amu, *aa, *ac;
+  double bbase, abase;
+  const double* cum;
+  const float* samp;
+  const float* inj;
+  float* cand;                      // the problem's [C][D] rows, or null
+  double *l_out, *g_out;            // the problem's [C], or null
+  tpe_joint_record* rec;            // this workgroup's chunk record
+};
+
+// The chunk of candidates [first, first + TPE_JOINT_CHUNK) of one problem: draw
+// (or load) kR candidates a lane, score both sides, write the optional outputs
+// and the chunk winner.  blo / bhi: the f32 bounds of the DP padded dimensions.
 template <int DP>
-__global__ __launch_bounds__(kThreads) void k_joint_chunk(const JointK p) {
-  __shared__ __attribute__((aligned(16))) float rows[kTileK * 2 * DP];
-  __shared__ float cl[kTileK];
-  __shared__ Pick slot[kThreads / 64];
+__device__ __forceinline__ void joint_chunk_body(const ChunkIO& p, const float (&blo)[DP], const float (&bhi)[DP],
+                                                 int first, float* __restrict__ rows, float* __restrict__ cl,
+                                                 Pick* __restrict__ slot) {
   const int t = threadIdx.x, D = p.D;
-  const int id = blockIdx.x / p.n_chunks, chunk = blockIdx.x % p.n_chunks;
-  const int first = chunk * TPE_JOINT_CHUNK;
 
   float z[kR][DP];
 #pragma unroll
@@ -160,7 +181,7 @@ __global__ __launch_bounds__(kThreads) void k_joint_chunk(const JointK p) {
         if (d < D) z[r][d] = p.inj[(int64_t)i * D + d];
       continue;
     }
-    const uint32_t c3 = (uint32_t)p.ids[id];
+    const uint32_t c3 = p.c3;
     U4 w = philox4x32_10((uint32_t)i, 0u, p.stream_word, c3, p.key0, p.key1);
     const double us = u01w(w.x);
     int lo = 0, hi = p.kb - 1;             // first k with us < cum[k]
@@ -178,7 +199,7 @@ __global__ __launch_bounds__(kThreads) void k_joint_chunk(const JointK p) {
       if (sr[4] != 0.f) zz = -zz;
       float x = sr[0] + sr[1] * zz;
       if (!(x == x)) x = sr[0];
-      z[r][d] = fminf(fmaxf(x, p.lo[d]), p.hi[d]);      // low <= z < high
+      z[r][d] = fminf(fmaxf(x, blo[d]), bhi[d]);        // low <= z < high
     }
   }
 
@@ -194,13 +215,12 @@ __global__ __launch_bounds__(kThreads) void k_joint_chunk(const JointK p) {
     lv[r] = l2[r] * kLn2 + p.bbase;
     gv[r] = g2[r] * kLn2 + p.abase;
     if (i >= p.C) continue;
-    const int64_t o = (int64_t)id * p.C + i;
-    if (p.l_out) p.l_out[o] = lv[r];
-    if (p.g_out) p.g_out[o] = gv[r];
+    if (p.l_out) p.l_out[i] = lv[r];
+    if (p.g_out) p.g_out[i] = gv[r];
     if (p.cand)
 #pragma unroll
       for (int d = 0; d < DP; ++d)
-        if (d < D) p.cand[o * D + d] = z[r][d];
+        if (d < D) p.cand[(int64_t)i * D + d] = z[r][d];
     const uint64_t key = score_key(lv[r] - gv[r]);
     if (key > best.key) best = Pick{key, (int64_t)i};   // ascending index: strict > keeps the first of a tie
   }
@@ -212,7 +232,7 @@ __global__ __launch_bounds__(kThreads) void k_joint_chunk(const JointK p) {
   for (int q = 1; q < kThreads / 64; ++q)
     if (beats(slot[q], w)) w = slot[q];
 
-  tpe_joint_record* rec = p.chunk_rec + blockIdx.x;
+  tpe_joint_record* rec = p.rec;
   if (w.key == 0) {
     if (t == 0) rec->global_idx = -1;
     return;
@@ -229,6 +249,113 @@ __global__ __launch_bounds__(kThreads) void k_joint_chunk(const JointK p) {
 #pragma unroll
     for (int d = 0; d < TPE_JOINT_MAX_DIMS; ++d) rec->z[d] = d < DP ? (double)z[r][d < DP ? d : 0] : 0.0;
   }
+}
+
+template <int DP>
+__global__ __launch_bounds__(kThreads) void k_joint_chunk(const JointK p) {
+  __shared__ __attribute__((aligned(16))) float rows[kTileK * 2 * DP];
+  __shared__ float cl[kTileK];
+  __shared__ Pick slot[kThreads / 64];
+  const int id = blockIdx.x / p.n_chunks, chunk = blockIdx.x % p.n_chunks;
+
+  ChunkIO q;
+  q.D = p.D; q.C = p.C; q.inject = p.inject;
+  q.kb = p.kb; q.ka = p.ka;
+  q.key0 = p.key0; q.key1 = p.key1; q.stream_word = p.stream_word;
+  q.c3 = p.inject ? 0u : (uint32_t)p.ids[id];
+  q.bmu = p.bmu; q.ba = p.ba; q.bc = p.bc; q.amu = p.amu; q.aa = p.aa; q.ac = p.ac;
+  q.bbase = p.bbase; q.abase = p.abase;
+  q.cum = p.cum; q.samp = p.samp; q.inj = p.inj;
+  const int64_t o = (int64_t)id * p.C;
+  q.cand = p.cand ? p.cand + o * p.D : nullptr;
+  q.l_out = p.l_out ? p.l_out + o : nullptr;
+  q.g_out = p.g_out ? p.g_out + o : nullptr;
+  q.rec = p.chunk_rec + blockIdx.x;
+  float blo[DP], bhi[DP];                  // (kernel-argument arrays: constant indices only)
+#pragma unroll
+  for (int d = 0; d < DP; ++d) { blo[d] = p.lo[d]; bhi[d] = p.hi[d]; }
+  joint_chunk_body<DP>(q, blo, bhi, chunk * TPE_JOINT_CHUNK, rows, cl, slot);
+}
+
+// --------------------------------------------------------- segmented stage
+// One launch scores problems of MANY groups (include/tpe_hip.h "Segmented joint
+// stage"): a workgroup reads its problem's group descriptor and then runs
+// joint_chunk_body, so a problem's bytes are those of a k_joint_chunk launch
+// over that group alone.
+struct SegK {
+  int C, n_chunks, inject, first;   // first: this launch's first entry of `order`
+  int n_probs, n_segs;
+  uint32_t key0, key1;
+  const tpe_joint_seg* segs;
+  const float* pool;
+  const double* pool64;
+  const int32_t* prob_seg;
+  const int64_t* prob_id;
+  const int64_t* cand_off;
+  int32_t* order;                   // scratch [n_probs]: the problems by (DP class, group, index)
+  float* cand;
+  double *l_out, *g_out;
+  tpe_joint_record* chunk_rec;      // scratch [n_probs * n_chunks], problem-major
+};
+
+// the kernel instantiation of a group of D dimensions, as an index 0 .. 7
+__host__ __device__ __forceinline__ int dp_class(int D) {
+  return D <= 4 ? D - 1 : D <= 6 ? 4 : D <= 8 ? 5 : D <= 12 ? 6 : 7;
+}
+
+// order[rank of p] = p, the rank by (DP class, group, problem index): one thread
+// a problem counts the problems before it.  No atomics; P^2 / 256 reads a
+// workgroup from arrays that sit in L2.
+__global__ __launch_bounds__(kThreads) void k_joint_seg_order(const SegK p) {
+  const int me = blockIdx.x * kThreads + threadIdx.x;
+  if (me >= p.n_probs) return;
+  const int sme = p.prob_seg[me];
+  const int kme = dp_class(p.segs[sme].n_dims) * p.n_segs + sme;
+  int rank = 0;
+  for (int q = 0; q < p.n_probs; ++q) {
+    const int sq = p.prob_seg[q];
+    const int kq = dp_class(p.segs[sq].n_dims) * p.n_segs + sq;
+    rank += (kq < kme || (kq == kme && q < me)) ? 1 : 0;
+  }
+  p.order[rank] = me;
+}
+
+__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ int64_t uni(int64_t v) {
+  return (int64_t)(((uint64_t)(uint32_t)uni((int)((uint64_t)v >> 32)) << 32) | (uint32_t)uni((int)(uint32_t)v));
+}
+__device__ __forceinline__ float unif(float v) { return __int_as_float(uni(__float_as_int(v))); }
+__device__ __forceinline__ double unid(double v) { return __longlong_as_double(uni((int64_t)__double_as_longlong(v))); }
+
+template <int DP>
+__global__ __launch_bounds__(kThreads) void k_joint_seg_chunk(const SegK p) {
+  __shared__ __attribute__((aligned(16))) float rows[kTileK * 2 * DP];
+  __shared__ float cl[kTileK];
+  __shared__ Pick slot[kThreads / 64];
+  const int chunk = blockIdx.x % p.n_chunks;
+  // the problem and its group: the same for every lane, kept in scalar registers
+  const int prob = uni(p.order[p.first + blockIdx.x / p.n_chunks]);
+  const tpe_joint_seg* __restrict__ sg = p.segs + uni(p.prob_seg[prob]);
+
+  ChunkIO q;
+  q.D = uni(sg->n_dims); q.C = p.C; q.inject = p.inject;
+  q.kb = uni(sg->k_below); q.ka = uni(sg->k_above);
+  q.key0 = p.key0; q.key1 = p.key1; q.stream_word = (uint32_t)uni((int)sg->stream_word);
+  q.c3 = (uint32_t)uni((int)(uint32_t)p.prob_id[prob]);
+  q.bmu = p.pool + uni(sg->below_mu); q.ba = p.pool + uni(sg->below_a); q.bc = p.pool + uni(sg->below_c);
+  q.amu = p.pool + uni(sg->above_mu); q.aa = p.pool + uni(sg->above_a); q.ac = p.pool + uni(sg->above_c);
+  q.bbase = unid(sg->below_base); q.abase = unid(sg->above_base);
+  q.cum = p.inject ? nullptr : p.pool64 + uni(sg->samp_cum);
+  q.samp = p.inject ? nullptr : p.pool + uni(sg->samp);
+  q.inj = p.inject ? p.pool + uni(sg->inject) : nullptr;
+  q.cand = p.cand ? p.cand + uni(p.cand_off[prob]) : nullptr;
+  q.l_out = p.l_out ? p.l_out + (int64_t)prob * p.C : nullptr;
+  q.g_out = p.g_out ? p.g_out + (int64_t)prob * p.C : nullptr;
+  q.rec = p.chunk_rec + (int64_t)prob * p.n_chunks + chunk;
+  float blo[DP], bhi[DP];
+#pragma unroll
+  for (int d = 0; d < DP; ++d) { blo[d] = unif(sg->lo[d]); bhi[d] = unif(sg->hi[d]); }
+  joint_chunk_body<DP>(q, blo, bhi, chunk * TPE_JOINT_CHUNK, rows, cl, slot);
 }
 
 __global__ __launch_bounds__(64) void k_joint_merge(const tpe_joint_record* __restrict__ chunk_rec, int n_chunks,
@@ -494,6 +621,23 @@ struct {
   int on, valid;
   hipEvent_t ev[4];
 } g_prof = {0, 0, {nullptr, nullptr, nullptr, nullptr}};
+
+// tpe_joint_seg_run's launches before the merge: the order kernel and one chunk
+// launch per DP class present (g_prof.valid == 2: sum these for last_ms[0])
+uint64_t seg_order_bytes(int32_t n_probs) { return ((uint64_t)n_probs * sizeof(int32_t) + 7) & ~(uint64_t)7; }
+constexpr int kSegLaunches = 9;
+struct {
+  int n;
+  hipEvent_t ev[2 * kSegLaunches];
+} g_sprof = {0, {}};
+
+template <int DP>
+void launch_seg(const SegK& k, unsigned blocks, hipStream_t stream, hipEvent_t* ev) {
+  if (ev)
+    hipExtLaunchKernelGGL(k_joint_seg_chunk<DP>, dim3(blocks), dim3(kThreads), 0u, stream, ev[0], ev[1], 0u, k);
+  else
+    hipLaunchKernelGGL(k_joint_seg_chunk<DP>, dim3(blocks), dim3(kThreads), 0, stream, k);
+}
 
 template <int DP>
 void launch_chunk(const JointK& k, unsigned blocks, hipStream_t stream, bool timed) {
@@ -1178,12 +1322,22 @@ extern "C" {
 int tpe_joint_profile(int32_t enable, double* last_ms) {
   if (last_ms) {
     if (!g_prof.valid) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_profile: no profiled tpe_joint_run to read");
-    for (int i = 0; i < 2; ++i) {
+    for (int i = g_prof.valid == 2 ? 1 : 0; i < 2; ++i) {
       float ms = 0.f;
       hipError_t e = hipEventSynchronize(g_prof.ev[2 * i + 1]);
       if (e == hipSuccess) e = hipEventElapsedTime(&ms, g_prof.ev[2 * i], g_prof.ev[2 * i + 1]);
       if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
       last_ms[i] = (double)ms;
+    }
+    if (g_prof.valid == 2) {               // tpe_joint_seg_run: its launches before the merge, summed
+      last_ms[0] = 0.0;
+      for (int i = 0; i < g_sprof.n; ++i) {
+        float ms = 0.f;
+        hipError_t e = hipEventSynchronize(g_sprof.ev[2 * i + 1]);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, g_sprof.ev[2 * i], g_sprof.ev[2 * i + 1]);
+        if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
+        last_ms[0] += (double)ms;
+      }
     }
   }
   if (enable && !g_prof.ev[0])
@@ -1261,6 +1415,112 @@ int tpe_joint_run(const tpe_joint_args* a, tpe_joint_record* records, float* can
   } else {
     hipLaunchKernelGGL(k_joint_merge, dim3((unsigned)a->n_ids), dim3(64), 0, s, (const tpe_joint_record*)scratch,
                        (int)n_chunks, records);
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
+  return TPE_OK;
+}
+
+int tpe_joint_seg_scratch_bytes(int32_t n_probs, int32_t n_cand, uint64_t* bytes) {
+  if (!bytes || n_probs < 1 || n_cand < 1)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_scratch_bytes: bad arguments");
+  *bytes = seg_order_bytes(n_probs) + (uint64_t)n_probs * (uint64_t)n_chunks_of(n_cand) * sizeof(tpe_joint_record);
+  return TPE_OK;
+}
+
+int tpe_joint_seg_run(const tpe_joint_seg_args* a, tpe_joint_record* records, float* cand, double* l_out,
+                      double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
+  if (!a) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: null args");
+  if (a->n_segs < 1) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: n_segs < 1");
+  if (a->n_probs < 1) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: n_probs < 1");
+  if (a->n_cand < 1) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: n_cand < 1");
+  if (!a->segs || !a->host_segs) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: null segs / host_segs");
+  const bool inject = (a->flags & TPE_JOINT_INJECT) != 0;
+  if (!a->pool_f32 || (!inject && !a->pool_f64)) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: null pool");
+  if (!a->prob_seg || !a->host_prob_seg || !a->prob_id)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: null prob_seg / host_prob_seg / prob_id");
+  if (!records) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: null records");
+  if (cand && !a->cand_off) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: cand without cand_off");
+  // rows [off, off + n) inside a pool of len elements
+  auto inside = [](int64_t off, int64_t n, int64_t len) { return off >= 0 && n <= len && off <= len - n; };
+  for (int s = 0; s < a->n_segs; ++s) {
+    const tpe_joint_seg& g = a->host_segs[s];
+    if (g.n_dims < 1 || g.n_dims > TPE_JOINT_MAX_DIMS)
+      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: a segment's n_dims outside [1, TPE_JOINT_MAX_DIMS]");
+    if (g.k_below < 1 || g.k_above < 1)
+      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: a segment's k_below < 1 or k_above < 1");
+    const int64_t D = g.n_dims, kb = g.k_below, ka = g.k_above, L = a->pool_f32_len;
+    bool ok = inside(g.below_mu, kb * D, L) && inside(g.below_a, kb * D, L) && inside(g.below_c, kb, L) &&
+              inside(g.above_mu, ka * D, L) && inside(g.above_a, ka * D, L) && inside(g.above_c, ka, L);
+    if (!inject) ok = ok && inside(g.samp, kb * D * 5, L) && inside(g.samp_cum, kb, a->pool_f64_len);
+    if (inject && g.inject >= 0) ok = ok && inside(g.inject, (int64_t)a->n_cand * D, L);
+    if (!ok) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: a segment's rows leave its pool");
+  }
+  int64_t per_class[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int p = 0; p < a->n_probs; ++p) {
+    const int s = a->host_prob_seg[p];
+    if (s < 0 || s >= a->n_segs) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: prob_seg outside [0, n_segs)");
+    if (inject && a->host_segs[s].inject < 0)
+      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: TPE_JOINT_INJECT without candidates");
+    ++per_class[dp_class(a->host_segs[s].n_dims)];
+  }
+  const int64_t n_chunks = n_chunks_of(a->n_cand), blocks = n_chunks * a->n_probs;
+  if (blocks > INT32_MAX || (int64_t)a->n_segs * 8 > INT32_MAX)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: too many candidates");
+  const uint64_t need = seg_order_bytes(a->n_probs) + (uint64_t)blocks * sizeof(tpe_joint_record);
+  if (!scratch || scratch_bytes < need) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: scratch too small");
+
+  SegK k;
+  k.C = a->n_cand; k.n_chunks = (int)n_chunks; k.inject = inject ? 1 : 0; k.first = 0;
+  k.n_probs = a->n_probs; k.n_segs = a->n_segs;
+  k.key0 = (uint32_t)a->seed; k.key1 = (uint32_t)(a->seed >> 32);
+  k.segs = a->segs; k.pool = a->pool_f32; k.pool64 = a->pool_f64;
+  k.prob_seg = a->prob_seg; k.prob_id = a->prob_id; k.cand_off = a->cand_off;
+  k.order = (int32_t*)scratch;
+  k.cand = cand; k.l_out = l_out; k.g_out = g_out;
+  k.chunk_rec = (tpe_joint_record*)((char*)scratch + seg_order_bytes(a->n_probs));
+
+  const bool timed = g_prof.on != 0;
+  hipStream_t s = (hipStream_t)stream;
+  if (timed && !g_sprof.ev[0])
+    for (int i = 0; i < 2 * kSegLaunches; ++i) {
+      const hipError_t e = hipEventCreate(&g_sprof.ev[i]);
+      if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
+    }
+  int n_timed = 0;
+  const unsigned ob = (unsigned)((a->n_probs + kThreads - 1) / kThreads);
+  if (timed) {
+    hipExtLaunchKernelGGL(k_joint_seg_order, dim3(ob), dim3(kThreads), 0u, s, g_sprof.ev[0], g_sprof.ev[1], 0u, k);
+    n_timed = 1;
+  } else {
+    hipLaunchKernelGGL(k_joint_seg_order, dim3(ob), dim3(kThreads), 0, s, k);
+  }
+  int64_t first = 0;
+  for (int c = 0; c < 8; ++c) {
+    if (!per_class[c]) continue;
+    k.first = (int)first;
+    const unsigned nb = (unsigned)(per_class[c] * n_chunks);
+    hipEvent_t* ev = timed ? g_sprof.ev + 2 * n_timed++ : nullptr;
+    switch (c) {
+      case 0: launch_seg<1>(k, nb, s, ev); break;
+      case 1: launch_seg<2>(k, nb, s, ev); break;
+      case 2: launch_seg<3>(k, nb, s, ev); break;
+      case 3: launch_seg<4>(k, nb, s, ev); break;
+      case 4: launch_seg<6>(k, nb, s, ev); break;
+      case 5: launch_seg<8>(k, nb, s, ev); break;
+      case 6: launch_seg<12>(k, nb, s, ev); break;
+      default: launch_seg<16>(k, nb, s, ev); break;
+    }
+    first += per_class[c];
+  }
+  if (timed) {
+    hipExtLaunchKernelGGL(k_joint_merge, dim3((unsigned)a->n_probs), dim3(64), 0u, s, g_prof.ev[2], g_prof.ev[3], 0u,
+                          (const tpe_joint_record*)k.chunk_rec, (int)n_chunks, records);
+    g_sprof.n = n_timed;
+    g_prof.valid = 2;
+  } else {
+    hipLaunchKernelGGL(k_joint_merge, dim3((unsigned)a->n_probs), dim3(64), 0, s,
+                       (const tpe_joint_record*)k.chunk_rec, (int)n_chunks, records);
   }
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));

@@ -985,7 +985,10 @@ class Engine(object):
         N.JOINT_WIDE_RECORD_DTYPE."""
         return self._joint_continuous(True, below, above, low, high, ids, n_cand, seed, inject, return_cand, want_lg)
 
-    def _joint_continuous(self, wide, below, above, low, high, ids, n_cand, seed, inject, return_cand, want_lg):
+    def _joint_continuous(self, wide, below, above, low, high, ids, n_cand, seed, inject, return_cand, want_lg,
+                          stream_word=None):
+        """``stream_word``: the Philox stream word (None: N.JOINT_STREAM; a branch
+        group's joint.branch_stream_word, to compare with run_joint_segments)."""
         from . import joint as J
         low, high = np.asarray(low, dtype=np.float64), np.asarray(high, dtype=np.float64)
         D = len(low)
@@ -997,7 +1000,8 @@ class Engine(object):
         a = N.JointWideArgs() if wide else N.JointArgs()
         a.n_dims, a.n_cand, a.n_ids, a.flags = D, C, n_ids, 0
         a.k_below, a.k_above = len(below[0]), len(above[0])
-        a.stream_word, a.seed = N.JOINT_STREAM, int(seed) & 0xFFFFFFFFFFFFFFFF
+        a.stream_word = N.JOINT_STREAM if stream_word is None else int(stream_word)
+        a.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         for name, side in (('below', below), ('above', above)):
             mu, aa, c, base = J.density_rows(side[0], side[1], side[2], low, high)
             setattr(a, name + '_mu', up(name + '_mu', mu, torch.float32))
@@ -1069,6 +1073,124 @@ class Engine(object):
             out.append(d_l[:n_ids * C].cpu().numpy().reshape(n_ids, C).copy())
             out.append(d_g[:n_ids * C].cpu().numpy().reshape(n_ids, C).copy())
         return tuple(out)
+
+    def run_joint_segments(self, models, stream_words, prob_seg, prob_id, n_cand, seed, inject=None,
+                           return_cand=False, want_lg=False):
+        """One segmented joint stage (tpe_joint_seg_run, include/tpe_hip.h
+        "Segmented joint stage"): problem p scores new id ``prob_id[p]`` under
+        group ``prob_seg[p]``.  ``models``: per group a joint.JointModel or a
+        (below, above, low, high) tuple as ``run_joint`` takes them (1 to
+        N.JOINT_MAX_DIMS continuous dimensions); ``stream_words``: per group its
+        Philox stream word.  Every group's rows go into two pools, uploaded with
+        the descriptors and the problem list in ONE transfer; one transfer
+        brings the results back.  Problem p's results are byte for byte those
+        of ``run_joint`` over its group with that stream word and ids =
+        [prob_id[p]].  ``inject``: per group an array [C, D_group] (or None for
+        a group without a problem): its problems score these candidates.
+        Returns the records [P] (N.JOINT_RECORD_DTYPE); with ``return_cand``
+        also a list of P arrays f32 [C, D_group]; with ``want_lg`` also l, g
+        float64 [P, C]."""
+        from . import joint as J
+        S, C = len(models), int(n_cand)
+        prob_seg = np.ascontiguousarray(prob_seg, dtype=np.int32).reshape(-1)
+        prob_id = np.ascontiguousarray(prob_id, dtype=np.int64).reshape(-1)
+        P = len(prob_seg)
+        if S < 1 or len(stream_words) != S:
+            raise ValueError('joint stage: one stream word per group, at least one group')
+        if P < 1 or len(prob_id) != P or C < 1 or C >= 2 ** 31:
+            raise ValueError('joint stage: n_cand / problems out of range')
+        if prob_seg.min() < 0 or prob_seg.max() >= S:
+            raise ValueError('joint stage: a problem names a group outside [0, %d)' % S)
+        if inject is not None and len(inject) != S:
+            raise ValueError('joint stage: inject must hold one entry per group')
+        segs = np.zeros(S, dtype=N.JOINT_SEG_DTYPE)
+        f32, f64 = [], []
+        n32 = n64 = 0
+
+        def put32(arr):
+            nonlocal n32
+            arr = np.ascontiguousarray(arr, dtype=np.float32).reshape(-1)
+            f32.append(arr)
+            n32 += arr.size
+            return n32 - arr.size
+        dims = np.empty(S, dtype=np.int64)
+        for s, m in enumerate(models):
+            below, above, low, high = (m.below, m.above, m.low, m.high) if hasattr(m, 'below') else m
+            low, high = np.asarray(low, dtype=np.float64), np.asarray(high, dtype=np.float64)
+            D = dims[s] = len(low)
+            if not 1 <= D <= N.JOINT_MAX_DIMS:
+                raise ValueError('joint stage: %d dimensions, at most %d' % (D, N.JOINT_MAX_DIMS))
+            g = segs[s]
+            g['n_dims'], g['k_below'], g['k_above'] = D, len(below[0]), len(above[0])
+            g['stream_word'] = int(stream_words[s])
+            for name, side in (('below', below), ('above', above)):
+                if side[1].shape != (len(side[0]), D) or side[2].shape != side[1].shape:
+                    raise ValueError('joint stage: mixture shapes do not match %d dimensions' % D)
+                mu, aa, c, base = J.density_rows(side[0], side[1], side[2], low, high)
+                g[name + '_mu'], g[name + '_a'], g[name + '_c'] = put32(mu), put32(aa), put32(c)
+                g[name + '_base'] = base
+            cum, rows = J.sampler_rows(below[0], below[1], below[2], low, high)
+            g['samp'] = put32(rows)
+            g['samp_cum'] = n64
+            f64.append(cum)
+            n64 += cum.size
+            g['inject'] = -1
+            if inject is not None and inject[s] is not None:
+                inj = np.ascontiguousarray(inject[s], dtype=np.float32)
+                if inj.shape != (C, D):
+                    raise ValueError('joint stage: inject must be [n_cand, %d]' % D)
+                g['inject'] = put32(inj)
+            g['lo'], g['hi'] = np.float32(-np.inf), np.float32(np.inf)
+            g['lo'][:D], g['hi'][:D] = J.f32_bounds(low, high)
+        if inject is not None and any(inject[s] is None for s in np.unique(prob_seg)):
+            raise ValueError('joint stage: inject lacks the candidates of a group that has a problem')
+        pd = dims[prob_seg]
+        cand_off = np.concatenate([[0], np.cumsum(C * pd)]).astype(np.int64)
+        if P * C >= 2 ** 31 or cand_off[-1] >= 2 ** 31:
+            raise ValueError('joint stage: %d problems x %d candidates do not fit one run' % (P, C))
+
+        # one blob: 8-byte items first (descriptors, the f64 pool, ids, offsets), then the 4-byte ones
+        parts = [segs.view(np.uint8), np.concatenate(f64).view(np.uint8), prob_id.view(np.uint8),
+                 cand_off[:P].view(np.uint8), np.concatenate(f32).view(np.uint8), prob_seg.view(np.uint8)]
+        offs = np.concatenate([[0], np.cumsum([len(x) for x in parts])])
+        blob = np.concatenate(parts)
+        d_blob = self._buf('joint_seg_blob', len(blob), torch.uint8)
+        d_blob[:len(blob)].copy_(torch.from_numpy(blob))
+        base = d_blob.data_ptr()
+        a = N.JointSegArgs()
+        a.n_segs, a.n_probs, a.n_cand, a.flags = S, P, C, N.JOINT_INJECT if inject is not None else 0
+        a.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        a.segs, a.host_segs = base + int(offs[0]), segs.ctypes.data
+        a.pool_f64, a.prob_id, a.cand_off = base + int(offs[1]), base + int(offs[2]), base + int(offs[3])
+        a.pool_f32, a.prob_seg, a.host_prob_seg = base + int(offs[4]), base + int(offs[5]), prob_seg.ctypes.data
+        a.pool_f32_len, a.pool_f64_len = n32, n64
+
+        nb = ctypes.c_uint64(0)
+        N.check(self.lib.tpe_joint_seg_scratch_bytes(P, C, ctypes.byref(nb)), self.lib, 'tpe_joint_seg_scratch_bytes')
+        d_scr = self._buf('joint_scratch', (nb.value + 7) // 8, torch.float64)
+        # one result block of 8-byte words: records, l, g, then the candidates (f32 pairs)
+        rec_w = P * N.JOINT_RECORD_DTYPE.itemsize // 8
+        lg_w = P * C if want_lg else 0
+        cand_w = (int(cand_off[-1]) + 1) // 2 if return_cand else 0
+        d_out = self._buf('joint_seg_out', rec_w + 2 * lg_w + cand_w, torch.float64)
+        out = d_out.data_ptr()
+        N.check(self.lib.tpe_joint_seg_run(ctypes.byref(a), out, out + 8 * (rec_w + 2 * lg_w) if return_cand else None,
+                                           out + 8 * rec_w if want_lg else None,
+                                           out + 8 * (rec_w + lg_w) if want_lg else None,
+                                           d_scr.data_ptr(), d_scr.numel() * 8, ctypes.c_void_p(self._stream())),
+                self.lib, 'tpe_joint_seg_run')
+        host = d_out[:rec_w + 2 * lg_w + cand_w].cpu().numpy()
+        rec = host[:rec_w].view(N.JOINT_RECORD_DTYPE).copy()
+        if not (return_cand or want_lg):
+            return rec
+        res = [rec]
+        if return_cand:
+            flat = host[rec_w + 2 * lg_w:].view(np.float32)
+            res.append([flat[cand_off[p]:cand_off[p + 1]].reshape(C, int(pd[p])).copy() for p in range(P)])
+        if want_lg:
+            res.append(host[rec_w:rec_w + lg_w].reshape(P, C).copy())
+            res.append(host[rec_w + lg_w:rec_w + 2 * lg_w].reshape(P, C).copy())
+        return tuple(res)
 
     def run_joint_mixed(self, below, above, low, high, cats, ids, n_cand, seed, inject=None, return_cand=False,
                         want_lg=False):

@@ -104,6 +104,28 @@ def sampler_rows(w, mu, sigma, low, high):
     return np.ascontiguousarray(cum, dtype=np.float64), np.ascontiguousarray(rows, dtype=np.float32)
 
 
+def f32_bounds(low, high):
+    """f32 (lo [D], hi [D]) the kernels clip a drawn coordinate to, as
+    tpe_joint_run derives them: the smallest float >= low_d and the largest
+    float < high_d (-inf / +inf where unbounded)."""
+    low, high = np.asarray(low, dtype=np.float64), np.asarray(high, dtype=np.float64)
+    lo, hi = low.astype(np.float32), high.astype(np.float32)
+    up = np.isfinite(low) & (lo.astype(np.float64) < low)
+    lo[up] = np.nextafter(lo[up], np.float32(np.inf))
+    for d in np.flatnonzero(np.isfinite(high)):
+        while float(hi[d]) >= high[d]:
+            hi[d] = np.nextafter(hi[d], np.float32(-np.inf))
+    return lo, hi
+
+
+def branch_stream_word(rows):
+    """The Philox stream word of a branch group (DESIGN.md "Branch groups"):
+    0xFFFFFFFE - the lowest table index among its labels.  It depends on the
+    space alone, differs between groups (a label is in one group), and is at
+    least 2^31, so it equals no univariate label index and not N.JOINT_STREAM."""
+    return 0xFFFFFFFE - min(r.index for r in rows)
+
+
 def lpdf_numpy(z, w, mu, sigma, low, high, block=1 << 14):
     """The model's float64 log-density at ``z`` [C, D] (the specification the
     device stage is tested against; tools/joint_time.py's host route)."""

@@ -39,6 +39,9 @@ Extensions over the reference (keyword-only, defaults keep its behaviour):
     categorical labels that gate no other label, ``joint_quantized=True``
     unconditional quniform / qloguniform labels of 2 to 256 lattice values,
     ``joint_wide=True`` 17 to 64 continuous labels instead of at most 16.
+    ``joint_branches=True`` also joins the continuous labels of every
+    conditional branch, one group per (gate, option), each id under the model
+    of the branch it takes (DESIGN.md "Branch groups").
 
 ``linear_forgetting`` is accepted and, as in the reference, not used: the
 forgetting window is fixed at DEFAULT_LF=25 (tpe.py:27-29).
@@ -836,14 +839,15 @@ def suggest(new_ids, domain, trials, seed,
             gamma=_default_gamma,
             linear_forgetting=_default_linear_forgetting,
             sampler='philox', precision='fp32', device=None, shard=None, shard_ids=None, shard_labels=None,
-            shard_grid=None, joint=False, joint_discrete=False, joint_quantized=False, joint_wide=False):
+            shard_grid=None, joint=False, joint_discrete=False, joint_quantized=False, joint_wide=False,
+            joint_branches=False):
     new_ids = list(new_ids)
     if not new_ids:
         return []
-    if (joint is not False and joint is not None) or joint_discrete or joint_quantized or joint_wide:
+    if (joint is not False and joint is not None) or joint_discrete or joint_quantized or joint_wide or joint_branches:
         # (argument errors first: no device use, no startup draw)
-        _joint_group(domain.table, joint, sampler, precision, (shard, shard_ids, shard_labels, shard_grid),
-                     joint_discrete, joint_quantized, joint_wide)
+        _joint_plan(domain.table, joint, sampler, precision, (shard, shard_ids, shard_labels, shard_grid),
+                    joint_discrete, joint_quantized, joint_wide, joint_branches)
     t0 = time.time()
     hist = _history.extract(domain, trials)
     if logger.isEnabledFor(logging.INFO):
@@ -858,7 +862,8 @@ def suggest(new_ids, domain, trials, seed,
                               n_EI_candidates=n_EI_candidates, gamma=gamma, sampler=sampler,
                               precision=precision, device=device, shard=shard, shard_ids=shard_ids,
                               shard_labels=shard_labels, shard_grid=shard_grid, joint=joint,
-                              joint_discrete=joint_discrete, joint_quantized=joint_quantized, joint_wide=joint_wide)
+                              joint_discrete=joint_discrete, joint_quantized=joint_quantized, joint_wide=joint_wide,
+                              joint_branches=joint_branches)
     logger.info('tpe.suggest took %f seconds', time.time() - t0)
     return rand.docs_from_choices(new_ids, domain, trials, choices)
 
@@ -899,7 +904,7 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
                     n_EI_candidates=_default_n_EI_candidates, gamma=_default_gamma,
                     sampler='philox', precision='fp32', device=None, shard=None, columns=False,
                     shard_ids=None, shard_labels=None, shard_grid=None, joint=False, joint_discrete=False,
-                    joint_quantized=False, joint_wide=False):
+                    joint_quantized=False, joint_wide=False, joint_branches=False):
     """The suggest core on a structure-of-arrays history (``history.History``):
     per new id a {label: value or None} dict.  ``suggest`` wraps it with the
     Trials document layout; columnar callers (and bench.py's large configs)
@@ -944,13 +949,32 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
     ``joint`` alone joins); it is scored by the wide stage (DESIGN.md "Wide
     groups"), whose candidates continue the same Philox streams.  A group of at
     most 16 labels takes exactly the path without the keyword, byte for byte.
-    64 bounds the set of kernel instantiations; it is not a measured limit."""
+    64 bounds the set of kernel instantiations; it is not a measured limit.
+
+    ``joint_branches=True`` (with ``joint``): conditional labels are joined
+    too, one group per branch (DESIGN.md "Branch groups").  A branch group is
+    the ``uniform`` / ``loguniform`` / ``normal`` / ``lognormal`` labels that
+    share one condition (gate label, option) and have no other parent; a label
+    nested below a conditional gate belongs to its own direct parent's group.
+    ``joint=True`` joins every branch group of 2 to 16 labels (one label stays
+    univariate, more than 16 raise ValueError) beside the unconditional group,
+    which is formed and run exactly as without the keyword and which the other
+    three keywords alone widen; it is skipped when fewer than 2 unconditional
+    labels are eligible, and at least one group of 2 labels must exist.  A list
+    may name conditional continuous labels: the named labels are partitioned by
+    condition, and a part of one label raises ValueError.  Gates, labels with
+    several parents and conditional discrete or quantised labels stay
+    univariate.  Per new id a branch group's winner replaces its labels' values
+    only where the branch is taken; every other value, the gates' included, is
+    the same bytes as without ``joint``.  All branch groups of a suggest are
+    scored by one segmented device stage (Engine.run_joint_segments)."""
     if sampler not in ('philox', 'replay'):
         raise ValueError("sampler must be 'philox' or 'replay'")
-    group = None
-    if (joint is not False and joint is not None) or joint_discrete or joint_quantized or joint_wide:
-        group = _joint_group(table, joint, sampler, precision, (shard, shard_ids, shard_labels, shard_grid),
-                             joint_discrete, joint_quantized, joint_wide)
+    group, branch_groups = None, []
+    if (joint is not False and joint is not None) or joint_discrete or joint_quantized or joint_wide or joint_branches:
+        group, branch_groups = _joint_plan(table, joint, sampler, precision,
+                                           (shard, shard_ids, shard_labels, shard_grid), joint_discrete,
+                                           joint_quantized, joint_wide, joint_branches)
     if sum(a is not None for a in (shard, shard_ids, shard_labels, shard_grid)) > 1:
         raise ValueError('shard, shard_ids, shard_labels and shard_grid are exclusive: one shard axis per suggest')
     if (shard_ids is not None or shard_labels is not None or shard_grid is not None) and sampler == 'replay':
@@ -960,8 +984,9 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
     if shard_ids is not None or shard_labels is not None or shard_grid is not None:
         return _suggest_sharded(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, precision, device,
                                 columns, shard_ids, shard_labels, shard_grid)
-    if group is not None:
-        return _suggest_joint(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, device, columns, group)
+    if group is not None or branch_groups:
+        return _suggest_joint(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, device, columns, group,
+                              branch_groups)
     return _suggest_local(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, sampler, precision,
                           device, shard, columns)
 
@@ -976,6 +1001,19 @@ def _joint_group(table, joint, sampler, precision, shards, discrete=False, quant
     ``wide``: more than TPE_JOINT_MAX_DIMS continuous labels allowed);
     ValueError for every combination the joint stage does not take.  Touches no
     device."""
+    _joint_restrictions(joint, sampler, precision, shards, discrete, quantized, wide)
+    rows = _joint_rows(table, joint, discrete, quantized)
+    if len(rows) < 2:
+        raise ValueError('joint needs at least 2 labels to join, got %d' % len(rows))
+    return _joint_limits(rows, wide)
+
+
+def _joint_restrictions(joint, sampler, precision, shards, discrete=False, quantized=False, wide=False,
+                        branches=False):
+    """ValueError for a keyword without ``joint`` and for the sampler, precision
+    and shard arguments the joint stage does not combine with."""
+    if branches and (joint is False or joint is None):
+        raise ValueError('joint_branches=True needs joint=True or joint=[labels]: it only widens what joint joins')
     if wide and (joint is False or joint is None):
         raise ValueError('joint_wide=True needs joint=True or joint=[labels]: it only widens what joint joins')
     if discrete and (joint is False or joint is None):
@@ -988,6 +1026,11 @@ def _joint_group(table, joint, sampler, precision, shards, discrete=False, quant
         raise ValueError("joint does not combine with precision='fp64': the joint stage scores in fp32")
     if any(a is not None for a in shards):
         raise ValueError('joint does not combine with a shard argument')
+
+
+def _joint_rows(table, joint, discrete=False, quantized=False):
+    """The unconditional rows ``joint`` (True or a list of labels) selects, in
+    table order; ValueError for a listed label that cannot be joined."""
     if joint is True:
         rows = [r for r in table.rows if _joint.eligible(r) or (discrete and _joint.eligible_discrete(r, table))
                 or (quantized and _joint.eligible_quant(r, table))]
@@ -1012,8 +1055,12 @@ def _joint_group(table, joint, sampler, precision, shards, discrete=False, quant
                                  'normal and lognormal labels are joined'
                                  % (label, r.dist, '' if all(p is None for p in r.parents) else ', conditional'))
         rows = [r for r in table.rows if r.label in set(want)]
-    if len(rows) < 2:
-        raise ValueError('joint needs at least 2 labels to join, got %d' % len(rows))
+    return rows
+
+
+def _joint_limits(rows, wide=False):
+    """``rows`` (at least 2), or ValueError where the group exceeds what one
+    joint stage takes."""
     if len(rows) > TPE_JOINT_MAX_DIMS:
         if not wide:
             raise ValueError('joint joins at most TPE_JOINT_MAX_DIMS = %d labels, not %d: pass the labels to join as '
@@ -1061,45 +1108,146 @@ def _joint_kernel_order(group):
     return [r for r in group if not r.categorical and r.dist not in _joint.QUANT_DISTS], drows, qrows
 
 
-def _suggest_joint(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, device, columns, group):
+def _branch_key(row):
+    """(gate label, option) of a continuous label under exactly one condition
+    (a label a branch group may hold), else None."""
+    if row.dist in _joint.JOINT_DISTS and len(row.parents) == 1 and row.parents[0] is not None:
+        return tuple(row.parents[0])
+    return None
+
+
+def _branch_limit(key, rows):
+    if len(rows) > TPE_JOINT_MAX_DIMS:
+        raise ValueError('joint with joint_branches=True: the branch group under option %d of gate %r has %d labels, '
+                         'more than TPE_JOINT_MAX_DIMS = %d: pass the labels to join as joint=[...]'
+                         % (key[1], key[0], len(rows), TPE_JOINT_MAX_DIMS))
+    return rows
+
+
+def _joint_plan(table, joint, sampler, precision, shards, discrete=False, quantized=False, wide=False,
+                branches=False):
+    """(root group or None, branch groups) of a ``joint`` argument.  Without
+    ``branches``: (_joint_group(...), []).  With it (DESIGN.md "Branch
+    groups"): the root group as _joint_group forms it, or None where fewer than
+    2 unconditional labels are joined, and one list of ParamRows (table order)
+    per condition with 2 to TPE_JOINT_MAX_DIMS joined labels, ordered by their
+    first label.  ValueError as _joint_group; touches no device."""
+    if not branches:
+        return _joint_group(table, joint, sampler, precision, shards, discrete, quantized, wide), []
+    _joint_restrictions(joint, sampler, precision, shards, discrete, quantized, wide, True)
+    parts = {}
+    if joint is True:
+        root = _joint_rows(table, True, discrete, quantized)
+        for r in table.rows:
+            key = _branch_key(r)
+            if key is not None:
+                parts.setdefault(key, []).append(r)
+        groups = [_branch_limit(key, rows) for key, rows in parts.items() if len(rows) >= 2]
+        root = root if len(root) >= 2 else None
+    else:
+        if isinstance(joint, str):
+            raise ValueError('joint must be True or a list of labels, not the string %r' % joint)
+        want = list(joint)
+        named = set(label for label in want if label in table.by_label and _branch_key(table.by_label[label]))
+        root = _joint_rows(table, [label for label in want if label not in named], discrete, quantized)
+        if len(root) == 1:
+            raise ValueError('joint with joint_branches=True: %r is the only unconditional label named: a group needs '
+                             'at least 2 labels' % root[0].label)
+        for r in table.rows:
+            if r.label in named:
+                parts.setdefault(_branch_key(r), []).append(r)
+        for key, rows in parts.items():
+            if len(rows) == 1:
+                raise ValueError('joint with joint_branches=True: %r is the only label named under option %d of gate '
+                                 '%r: a group needs at least 2 labels' % (rows[0].label, key[1], key[0]))
+        groups = [_branch_limit(key, rows) for key, rows in parts.items()]
+        root = root or None
+    if root is None and not groups:
+        raise ValueError('joint needs at least 2 labels to join in one group (the unconditional labels, or the labels '
+                         'of one branch), and there is none')
+    return (None if root is None else _joint_limits(root, wide)), groups
+
+
+def _suggest_joint(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, device, columns, group,
+                   branch_groups=()):
     """The univariate suggest of every label (the joined labels' univariate
     winners are discarded: each costs one problem of the level's batch, and the
     other labels' values are then the same bytes as without ``joint``), then
-    one joint stage over the group, whose winner fills the group's columns."""
+    one joint stage over the root group (if any), whose winner fills the
+    group's columns, then one segmented stage over the branch groups: group g
+    applies to the ids for which its labels are active, and its winners fill
+    its columns for those ids only (a joined label gates nothing, so the
+    routing is the univariate pass's)."""
     cc = _suggest_local(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, 'philox', 'fp32', device,
                         None, True)
     if len(cc) == 0:
         return cc if columns else []
     engine = get_engine(device, 'fp32')
     ids = np.asarray(new_ids, dtype=np.int64).reshape(-1)
-    crows, drows, qrows = _joint_kernel_order(group)
-    if qrows:                                    # kernel coordinates: continuous, discrete, then quantised labels
-        group = crows + drows + qrows
-        model = _joint.fit_quant_model(crows, drows, qrows, hist, _history.split_below(hist, gamma), prior_weight,
-                                       DEFAULT_LF)
-        rec = engine.run_joint_quant(model.below[:3], model.above[:3], model.low, model.high, model.cats(),
-                                     model.quants(), ids, int(n_EI_candidates), seed)
-    elif drows:                                  # kernel coordinates: the continuous labels, then the discrete ones
-        group = [r for r in group if not r.categorical] + drows
-        model = _joint.fit_mixed_model(group[:len(group) - len(drows)], drows, hist,
-                                       _history.split_below(hist, gamma), prior_weight, DEFAULT_LF)
-        rec = engine.run_joint_mixed(model.below[:3], model.above[:3], model.low, model.high, model.cats(), ids,
-                                     int(n_EI_candidates), seed)
-    else:
-        model = _joint.fit_model(group, hist, _history.split_below(hist, gamma), prior_weight, DEFAULT_LF)
-        # more than TPE_JOINT_MAX_DIMS labels (joint_wide=True let them through): the wide stage
-        run = engine.run_joint_wide if len(group) > TPE_JOINT_MAX_DIMS else engine.run_joint
-        rec = run(model.below, model.above, model.low, model.high, ids, int(n_EI_candidates), seed)
-    if (rec['global_idx'] < 0).any():
-        raise RuntimeError('no joint candidate selected')
-    vals = model.values(rec['z'][:, :len(group)])
     values = np.array(cc.values, dtype=np.float64)
     active = np.array(cc.active, dtype=bool)
-    for d, r in enumerate(group):
-        values[:, r.index] = vals[:, d]
-        active[:, r.index] = True
+    if group is not None:
+        crows, drows, qrows = _joint_kernel_order(group)
+        if qrows:                                    # kernel coordinates: continuous, discrete, then quantised labels
+            group = crows + drows + qrows
+            model = _joint.fit_quant_model(crows, drows, qrows, hist, _history.split_below(hist, gamma), prior_weight,
+                                           DEFAULT_LF)
+            rec = engine.run_joint_quant(model.below[:3], model.above[:3], model.low, model.high, model.cats(),
+                                         model.quants(), ids, int(n_EI_candidates), seed)
+        elif drows:                                  # kernel coordinates: the continuous labels, then the discrete ones
+            group = [r for r in group if not r.categorical] + drows
+            model = _joint.fit_mixed_model(group[:len(group) - len(drows)], drows, hist,
+                                           _history.split_below(hist, gamma), prior_weight, DEFAULT_LF)
+            rec = engine.run_joint_mixed(model.below[:3], model.above[:3], model.low, model.high, model.cats(), ids,
+                                         int(n_EI_candidates), seed)
+        else:
+            model = _joint.fit_model(group, hist, _history.split_below(hist, gamma), prior_weight, DEFAULT_LF)
+            # more than TPE_JOINT_MAX_DIMS labels (joint_wide=True let them through): the wide stage
+            run = engine.run_joint_wide if len(group) > TPE_JOINT_MAX_DIMS else engine.run_joint
+            rec = run(model.below, model.above, model.low, model.high, ids, int(n_EI_candidates), seed)
+        if (rec['global_idx'] < 0).any():
+            raise RuntimeError('no joint candidate selected')
+        vals = model.values(rec['z'][:, :len(group)])
+        for d, r in enumerate(group):
+            values[:, r.index] = vals[:, d]
+            active[:, r.index] = True
+    if branch_groups:
+        _suggest_branches(engine, hist, ids, seed, prior_weight, n_EI_candidates, gamma, branch_groups,
+                          np.asarray(cc.active, dtype=bool), values)
     cc = ChoiceColumns(table.labels, values, active)
     return cc if columns else cc.dicts(table)
+
+
+def _suggest_branches(engine, hist, ids, seed, prior_weight, n_EI_candidates, gamma, branch_groups, taken, values):
+    """The segmented joint stage of a suggest: one problem per (new id, branch
+    group whose labels are active for it in ``taken`` [n_ids x n_labels]), all
+    in one Engine.run_joint_segments call; the winners overwrite ``values``."""
+    below_tids = _history.split_below(hist, gamma)
+    models, words, prob_seg, prob_id, where = [], [], [], [], []
+    for rows in branch_groups:
+        on = taken[:, rows[0].index]
+        for r in rows[1:]:
+            assert (taken[:, r.index] == on).all(), ('labels of one branch group differ in activity', rows[0].label,
+                                                     r.label)
+        js = np.flatnonzero(on)
+        if len(js) == 0:                             # no new id takes this branch
+            continue
+        prob_seg.extend([len(models)] * len(js))
+        prob_id.extend(ids[js])
+        where.append((rows, js))
+        models.append(_joint.fit_model(rows, hist, below_tids, prior_weight, DEFAULT_LF))
+        words.append(_joint.branch_stream_word(rows))
+    if not models:
+        return
+    rec = engine.run_joint_segments(models, words, prob_seg, prob_id, int(n_EI_candidates), seed)
+    if (rec['global_idx'] < 0).any():
+        raise RuntimeError('no joint candidate selected')
+    p = 0
+    for (rows, js), model in zip(where, models):
+        vals = model.values(rec['z'][p:p + len(js), :len(rows)])
+        for d, r in enumerate(rows):
+            values[js, r.index] = vals[:, d]
+        p += len(js)
 
 
 def _suggest_local(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, sampler, precision, device,

@@ -1084,7 +1084,8 @@ int tpe_joint_run(const tpe_joint_args* args, tpe_joint_record* records, float* 
 
 /* Profiling only (tools/joint_time.py), as tpe_report_profile: last_ms gets the
  * device times {chunk kernel, merge kernel} of the last profiled tpe_joint_run,
- * tpe_joint_mixed_run, tpe_joint_quant_run or tpe_joint_wide_run. */
+ * tpe_joint_mixed_run, tpe_joint_quant_run, tpe_joint_wide_run or
+ * tpe_joint_seg_run (whose first entry sums its launches before the merge). */
 int tpe_joint_profile(int32_t enable, double* last_ms);
 
 /* ------------------------------------------------------------------------
@@ -1335,6 +1336,85 @@ int tpe_joint_quant_run(const tpe_joint_quant_args* args, tpe_joint_record* reco
  * times its two table launches together; *table_ms gets that device time of the
  * last such run (it WAITS for them). */
 int tpe_joint_quant_profile(double* table_ms);
+
+/* ------------------------------------------------------------------------
+ * Segmented joint stage (tpe_joint.hip; additive to ABI 24): one call scores the
+ * (new id, group) problems of MANY continuous groups, each group ("segment")
+ * with its own model, dimension count and Philox stream word.  It serves joint
+ * TPE on conditional branches (DESIGN.md "Branch groups"): in a batched suggest
+ * over a tree every id takes its own branch, so every id needs its branch's
+ * model.  A group's rows are those of tpe_joint_args, laid side by side in two
+ * pools; tpe_joint_seg says where:
+ *   pool_f32   every group's mu / a / c rows of both sides, its sampler rows
+ *              samp[k_below * n_dims * 5] and, under TPE_JOINT_INJECT, its
+ *              candidates [n_cand * n_dims]; the descriptor fields are ELEMENT
+ *              offsets of their first float
+ *   pool_f64   every group's samp_cum[k_below]
+ *   lo / hi    the f32 bounds tpe_joint_run derives from low / high, made by the
+ *              caller: the smallest float >= low_d, the largest float < high_d,
+ *              -inf / +inf where unbounded and for d >= n_dims
+ * Problem p = (prob_id[p], segment prob_seg[p]).
+ *
+ * Defining property: the record, the cand rows, l_out and g_out of problem p
+ * are byte for byte those of a tpe_joint_run over that segment's rows with its
+ * stream_word, ids = [prob_id[p]] and the same seed, n_cand and flags; the order
+ * of the problems does not matter.  The device code is tpe_joint_run's:
+ * k_joint_seg_chunk<DP> (one 256-thread workgroup per problem and chunk of
+ * TPE_JOINT_CHUNK candidates) reads its problem's descriptor into scalar
+ * registers and runs k_joint_chunk's body; k_joint_merge then picks every
+ * problem's winner.  Launches, all on `stream` with no sync between them:
+ * k_joint_seg_order (ranks the problems by DP class, then segment, then index,
+ * into `scratch`: consecutive workgroups share a model), one k_joint_seg_chunk
+ * launch per DP class present (1, 2, 3, 4, 6, 8, 12, 16), one k_joint_merge over
+ * all problems.  Plain vector stores, no atomics: the same call twice gives the
+ * same bytes.
+ *
+ * tpe_joint_seg_run returns TPE_E_ARG before any launch (no device needed) for
+ * null args / segs / pools / problem arrays / records, n_segs < 1, n_probs < 1,
+ * n_cand < 1, a host_prob_seg entry outside [0, n_segs), a host_segs entry with
+ * n_dims outside [1, TPE_JOINT_MAX_DIMS], k_below < 1, k_above < 1 or rows that
+ * leave its pool (pool_f32_len / pool_f64_len elements), TPE_JOINT_INJECT with a
+ * problem whose segment has no candidates (inject < 0), cand without cand_off,
+ * or scratch smaller than tpe_joint_seg_scratch_bytes(n_probs, n_cand).
+ * host_segs / host_prob_seg are the caller's host copies of segs / prob_seg
+ * (the checks and the launch sizes read them; the kernels read the device
+ * arrays).  A segment with no problem is legal.  tpe_joint_profile covers this
+ * stage: {the launches before the merge, summed; the merge}.
+ * ---------------------------------------------------------------------- */
+typedef struct tpe_joint_seg {
+  int32_t n_dims, k_below, k_above;
+  uint32_t stream_word;
+  double below_base, above_base;
+  int64_t below_mu, below_a, below_c;     /* element offsets in pool_f32 */
+  int64_t above_mu, above_a, above_c;
+  int64_t samp;
+  int64_t inject;                         /* TPE_JOINT_INJECT: [n_cand * n_dims]; < 0: none */
+  int64_t samp_cum;                       /* element offset in pool_f64 */
+  float lo[TPE_JOINT_MAX_DIMS], hi[TPE_JOINT_MAX_DIMS];
+} tpe_joint_seg;
+typedef struct tpe_joint_seg_args {
+  int32_t n_segs, n_probs, n_cand, flags;   /* flags: TPE_JOINT_INJECT */
+  uint64_t seed;
+  const tpe_joint_seg* segs;        /* device [n_segs] */
+  const tpe_joint_seg* host_segs;   /* host   [n_segs], the same bytes */
+  const float* pool_f32;            /* device */
+  const double* pool_f64;           /* device (may be NULL under TPE_JOINT_INJECT) */
+  int64_t pool_f32_len, pool_f64_len;   /* elements */
+  const int32_t* prob_seg;          /* device [n_probs] */
+  const int32_t* host_prob_seg;     /* host   [n_probs], the same bytes */
+  const int64_t* prob_id;           /* device [n_probs] */
+  const int64_t* cand_off;          /* device [n_probs]: element offset of problem p's rows in `cand` (NULL without cand) */
+} tpe_joint_seg_args;
+
+/* the problem order and the chunk records of one tpe_joint_seg_run */
+int tpe_joint_seg_scratch_bytes(int32_t n_probs, int32_t n_cand, uint64_t* bytes);
+
+/* records: device [n_probs], in the caller's problem order; optional (NULL: not
+ * written) cand: device f32, problem p's [n_cand * n_dims(p)] rows from
+ * cand_off[p] on; l_out / g_out: device f64 [n_probs * n_cand]; enqueued on
+ * `stream` */
+int tpe_joint_seg_run(const tpe_joint_seg_args* args, tpe_joint_record* records, float* cand, double* l_out,
+                      double* g_out, void* scratch, uint64_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
  * Host phase clock of tpe_suggest_tree (tools/native_split.py).  While
