@@ -91,6 +91,10 @@ JOINT_WIDE_MAX_DIMS = 64       # TPE_JOINT_WIDE_MAX_DIMS: labels of a wide joint
 JOINT_WIDE_RECORD_DTYPE = np.dtype([('global_idx', '<i8'), ('l', '<f8'), ('g', '<f8'),
                                     ('z', '<f8', (JOINT_WIDE_MAX_DIMS,))])
 assert JOINT_WIDE_RECORD_DTYPE.itemsize == 536
+# joint candidate report (include/tpe_hip.h "Joint candidate report")
+JOINT_REPORT_CHUNK = 4096      # TPE_JOINT_REPORT_CHUNK: candidates per pass-1 workgroup
+JOINT_TOP_ENTRY_DTYPE = np.dtype([('idx', '<i8'), ('l', '<f8'), ('g', '<f8'), ('reserved', '<i8')])
+assert JOINT_TOP_ENTRY_DTYPE.itemsize == 32
 
 
 class Batch(ctypes.Structure):
@@ -217,6 +221,16 @@ class JointSegArgs(ctypes.Structure):
         ('pool_f32_len', ctypes.c_int64), ('pool_f64_len', ctypes.c_int64),
         ('prob_seg', ctypes.c_void_p), ('host_prob_seg', ctypes.c_void_p),
         ('prob_id', ctypes.c_void_p), ('cand_off', ctypes.c_void_p),
+    ]
+
+
+class JointReportArgs(ctypes.Structure):
+    """tpe_joint_report_args: one tpe_joint_report."""
+    _fields_ = [
+        ('n_probs', ctypes.c_int32), ('n_cand', ctypes.c_int32), ('width', ctypes.c_int32),
+        ('z_stride', ctypes.c_int32),
+        ('cand', ctypes.c_void_p), ('l_out', ctypes.c_void_p), ('g_out', ctypes.c_void_p),
+        ('cand_off', ctypes.c_void_p), ('widths', ctypes.c_void_p), ('host_widths', ctypes.c_void_p),
     ]
 
 
@@ -365,7 +379,8 @@ EXPORTS = ('tpe_abi_version', 'tpe_last_error', 'tpe_device_count', 'tpe_tile_si
            'tpe_report_profile', 'tpe_joint_scratch_bytes', 'tpe_joint_run', 'tpe_joint_profile',
            'tpe_joint_mixed_run', 'tpe_joint_quant_table_bytes', 'tpe_joint_quant_run', 'tpe_joint_quant_profile',
            'tpe_joint_wide_scratch_bytes', 'tpe_joint_wide_run', 'tpe_joint_wide_profile',
-           'tpe_joint_seg_scratch_bytes', 'tpe_joint_seg_run')
+           'tpe_joint_seg_scratch_bytes', 'tpe_joint_seg_run', 'tpe_joint_report_scratch_bytes',
+           'tpe_joint_report', 'tpe_joint_report_profile')
 
 # host phases of tpe_suggest_tree (tpe_host_phases order)
 PHASES = ('prefit', 'pack', 'launched', 'synced', 'level', 'return', 'recs')
@@ -498,6 +513,12 @@ def load(path=LIB_PATH):
     lib.tpe_joint_seg_scratch_bytes.restype = ctypes.c_int
     lib.tpe_joint_seg_run.argtypes = [ctypes.POINTER(JointSegArgs), P, P, P, P, P, ctypes.c_uint64, P]
     lib.tpe_joint_seg_run.restype = ctypes.c_int
+    lib.tpe_joint_report_scratch_bytes.argtypes = [I32, I32, I32, ctypes.POINTER(ctypes.c_uint64)]
+    lib.tpe_joint_report_scratch_bytes.restype = ctypes.c_int
+    lib.tpe_joint_report.argtypes = [ctypes.POINTER(JointReportArgs), I32, P, P, P, P, P, ctypes.c_uint64, P]
+    lib.tpe_joint_report.restype = ctypes.c_int
+    lib.tpe_joint_report_profile.argtypes = [I32, P]
+    lib.tpe_joint_report_profile.restype = ctypes.c_int
     lib.tpe_joint_profile.argtypes = [I32, P]
     lib.tpe_joint_profile.restype = ctypes.c_int
     lib.tpe_level_profile.argtypes = [ctypes.c_int32]

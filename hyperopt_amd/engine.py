@@ -966,7 +966,8 @@ class Engine(object):
                 'tpe_report')
         return d_top, d_ntop, d_stats
 
-    def run_joint(self, below, above, low, high, ids, n_cand, seed, inject=None, return_cand=False, want_lg=False):
+    def run_joint(self, below, above, low, high, ids, n_cand, seed, inject=None, return_cand=False, want_lg=False,
+                  report_k=0):
         """One joint TPE stage (tpe_joint_run, include/tpe_hip.h "Joint
         (multivariate) TPE stage"): ``below`` / ``above`` = (w [K], mu [K, D],
         sigma [K, D]) float64 mixtures (joint.side_mixture), ``low`` / ``high``
@@ -974,19 +975,29 @@ class Engine(object):
         the host, uploaded and scored; per new id the winner record
         (N.JOINT_RECORD_DTYPE) comes back.  ``inject`` [C, D]: score these
         candidates (every id) instead of sampling.  ``return_cand``: also the
-        candidates f32 [n_ids, C, D]; ``want_lg``: also l, g float64 [n_ids, C]."""
-        return self._joint_continuous(False, below, above, low, high, ids, n_cand, seed, inject, return_cand, want_lg)
+        candidates f32 [n_ids, C, D]; ``want_lg``: also l, g float64 [n_ids, C].
+        ``report_k`` > 0 (every run_joint* method): the stage leaves its
+        candidates, l and g on the device, tpe_joint_report (include/tpe_hip.h
+        "Joint candidate report") runs on the same stream, and the call also
+        returns, after everything else, top [P, k] (N.JOINT_TOP_ENTRY_DTYPE),
+        top_z f32 [P, k, D] (run_joint_segments: a list of P arrays [k, D_p]),
+        n_top int32 [P] and stats [P] (N.SCORE_STATS_DTYPE), P the ids or
+        problems; the per-candidate arrays come to the host only with
+        ``return_cand`` / ``want_lg``."""
+        return self._joint_continuous(False, below, above, low, high, ids, n_cand, seed, inject, return_cand, want_lg,
+                                      report_k=report_k)
 
     def run_joint_wide(self, below, above, low, high, ids, n_cand, seed, inject=None, return_cand=False,
-                       want_lg=False):
+                       want_lg=False, report_k=0):
         """``run_joint`` for up to N.JOINT_WIDE_MAX_DIMS dimensions
         (tpe_joint_wide_run, include/tpe_hip.h "Wide joint stage"): the same
         arguments, model, Philox streams and return shapes; the records are
         N.JOINT_WIDE_RECORD_DTYPE."""
-        return self._joint_continuous(True, below, above, low, high, ids, n_cand, seed, inject, return_cand, want_lg)
+        return self._joint_continuous(True, below, above, low, high, ids, n_cand, seed, inject, return_cand, want_lg,
+                                      report_k=report_k)
 
     def _joint_continuous(self, wide, below, above, low, high, ids, n_cand, seed, inject, return_cand, want_lg,
-                          stream_word=None):
+                          stream_word=None, report_k=0):
         """``stream_word``: the Philox stream word (None: N.JOINT_STREAM; a branch
         group's joint.branch_stream_word, to compare with run_joint_segments)."""
         from . import joint as J
@@ -1015,7 +1026,7 @@ class Engine(object):
         for d in range(D):
             a.low[d], a.high[d] = low[d], high[d]
         return self._joint_call('tpe_joint_wide_run' if wide else 'tpe_joint_run', a, n_ids, C, D, return_cand,
-                                want_lg, wide=wide)
+                                want_lg, wide=wide, report_k=report_k)
 
     # what run_joint and run_joint_mixed share: the size checks, the uploads, the call and its results
     def _joint_sizes(self, D, ids, n_cand, max_dims=N.JOINT_MAX_DIMS):
@@ -1043,10 +1054,13 @@ class Engine(object):
         a.flags |= N.JOINT_INJECT
         a.inject = self._joint_up('inject', inj, torch.float32)
 
-    def _joint_call(self, fn, a, n_ids, C, D, return_cand, want_lg, wide=False):
+    def _joint_call(self, fn, a, n_ids, C, D, return_cand, want_lg, wide=False, report_k=0):
         """Scratch and result buffers, the native call ``fn`` and the records
         (and candidates [n_ids, C, D], l, g [n_ids, C]) on the host.  ``wide``:
-        the wide stage's scratch size and record."""
+        the wide stage's scratch size and record.  ``report_k``: the stage
+        writes all three device buffers and the joint report follows."""
+        report_k = self._report_k(report_k)
+        dev_cand, dev_lg = return_cand or report_k > 0, want_lg or report_k > 0
         nb = ctypes.c_uint64(0)
         rec_dtype = N.JOINT_WIDE_RECORD_DTYPE if wide else N.JOINT_RECORD_DTYPE
         if wide:
@@ -1056,15 +1070,19 @@ class Engine(object):
             N.check(self.lib.tpe_joint_scratch_bytes(n_ids, C, ctypes.byref(nb)), self.lib, 'tpe_joint_scratch_bytes')
         d_scr = self._buf('joint_scratch', (nb.value + 7) // 8, torch.float64)
         d_rec = self._buf('joint_records', n_ids * rec_dtype.itemsize // 8, torch.float64)
-        d_cand = self._buf('joint_cand', n_ids * C * D, torch.float32) if return_cand else None
-        d_l = self._buf('joint_l', n_ids * C, torch.float64) if want_lg else None
-        d_g = self._buf('joint_g', n_ids * C, torch.float64) if want_lg else None
-        N.check(getattr(self.lib, fn)(ctypes.byref(a), d_rec.data_ptr(), d_cand.data_ptr() if return_cand else None,
-                                      d_l.data_ptr() if want_lg else None, d_g.data_ptr() if want_lg else None,
-                                      d_scr.data_ptr(), d_scr.numel() * 8, ctypes.c_void_p(self._stream())),
+        d_cand = self._buf('joint_cand', n_ids * C * D, torch.float32) if dev_cand else None
+        d_l = self._buf('joint_l', n_ids * C, torch.float64) if dev_lg else None
+        d_g = self._buf('joint_g', n_ids * C, torch.float64) if dev_lg else None
+        stream = self._stream()
+        N.check(getattr(self.lib, fn)(ctypes.byref(a), d_rec.data_ptr(), d_cand.data_ptr() if dev_cand else None,
+                                      d_l.data_ptr() if dev_lg else None, d_g.data_ptr() if dev_lg else None,
+                                      d_scr.data_ptr(), d_scr.numel() * 8, ctypes.c_void_p(stream)),
                 self.lib, fn)
+        if report_k:
+            rep = self._joint_report(d_cand.data_ptr(), d_l.data_ptr(), d_g.data_ptr(), n_ids, C, report_k, stream,
+                                     width=D)
         rec = d_rec[:n_ids * rec_dtype.itemsize // 8].cpu().numpy().view(rec_dtype).copy()
-        if not (return_cand or want_lg):
+        if not (return_cand or want_lg or report_k):
             return rec
         out = [rec]
         if return_cand:
@@ -1072,10 +1090,56 @@ class Engine(object):
         if want_lg:
             out.append(d_l[:n_ids * C].cpu().numpy().reshape(n_ids, C).copy())
             out.append(d_g[:n_ids * C].cpu().numpy().reshape(n_ids, C).copy())
+        if report_k:
+            out.extend(self._joint_report_host(rep, n_ids, report_k, D))
         return tuple(out)
 
+    @staticmethod
+    def _report_k(report_k):
+        report_k = int(report_k)
+        if report_k < 0 or report_k > N.REPORT_MAX_K:
+            raise ValueError('joint stage: report_k must be in [0, %d]: %r' % (N.REPORT_MAX_K, report_k))
+        return report_k
+
+    def _joint_report(self, cand, l, g, P, C, k, stream, width=0, cand_off=None, widths=None):
+        """Enqueue tpe_joint_report over the device buffers a joint stage just
+        wrote (``widths``: the host int32 [P] row widths of a segmented stage,
+        with ``cand_off`` its device offsets); returns the device tensors (top,
+        top_z, n_top, stats) and the row stride of top_z."""
+        a = N.JointReportArgs()
+        zs = int(width if widths is None else widths.max())
+        a.n_probs, a.n_cand, a.width, a.z_stride = P, C, int(width), zs
+        a.cand, a.l_out, a.g_out = cand, l, g
+        if widths is not None:
+            widths = np.ascontiguousarray(widths, dtype=np.int32)
+            a.cand_off, a.widths, a.host_widths = cand_off, self._joint_up('report_widths', widths, torch.int32), \
+                widths.ctypes.data
+        nb = ctypes.c_uint64(0)
+        N.check(self.lib.tpe_joint_report_scratch_bytes(P, C, k, ctypes.byref(nb)), self.lib,
+                'tpe_joint_report_scratch_bytes')
+        d_scr = self._buf('joint_report_scratch', (nb.value + 7) // 8, torch.float64)
+        d_top = self._buf('joint_report_top', P * k * 4, torch.float64)
+        d_z = self._buf('joint_report_z', P * k * zs, torch.float32)
+        d_ntop = self._buf('joint_report_n_top', P, torch.int32)
+        d_stats = self._buf('joint_report_stats', P * 8, torch.float64)
+        N.check(self.lib.tpe_joint_report(ctypes.byref(a), k, d_top.data_ptr(), d_z.data_ptr(), d_ntop.data_ptr(),
+                                          d_stats.data_ptr(), d_scr.data_ptr(), d_scr.numel() * 8,
+                                          ctypes.c_void_p(stream)), self.lib, 'tpe_joint_report')
+        return d_top, d_z, d_ntop, d_stats, zs
+
+    @staticmethod
+    def _joint_report_host(rep, P, k, width):
+        """(top [P, k], top_z, n_top [P], stats [P]) on the host; ``width`` an
+        int (top_z [P, k, width]) or the per-problem widths (a list of [k, w])."""
+        d_top, d_z, d_ntop, d_stats, zs = rep
+        top = d_top[:P * k * 4].cpu().numpy().view(N.JOINT_TOP_ENTRY_DTYPE).reshape(P, k).copy()
+        z = d_z[:P * k * zs].cpu().numpy().reshape(P, k, zs)
+        z = z.copy() if np.isscalar(width) else [z[p, :, :int(w)].copy() for p, w in enumerate(width)]
+        return (top, z, d_ntop[:P].cpu().numpy().copy(),
+                d_stats[:P * 8].cpu().numpy().view(N.SCORE_STATS_DTYPE).copy())
+
     def run_joint_segments(self, models, stream_words, prob_seg, prob_id, n_cand, seed, inject=None,
-                           return_cand=False, want_lg=False):
+                           return_cand=False, want_lg=False, report_k=0):
         """One segmented joint stage (tpe_joint_seg_run, include/tpe_hip.h
         "Segmented joint stage"): problem p scores new id ``prob_id[p]`` under
         group ``prob_seg[p]``.  ``models``: per group a joint.JointModel or a
@@ -1092,6 +1156,8 @@ class Engine(object):
         float64 [P, C]."""
         from . import joint as J
         S, C = len(models), int(n_cand)
+        report_k = self._report_k(report_k)
+        dev_cand, dev_lg = return_cand or report_k > 0, want_lg or report_k > 0
         prob_seg = np.ascontiguousarray(prob_seg, dtype=np.int32).reshape(-1)
         prob_id = np.ascontiguousarray(prob_id, dtype=np.int64).reshape(-1)
         P = len(prob_seg)
@@ -1170,18 +1236,30 @@ class Engine(object):
         d_scr = self._buf('joint_scratch', (nb.value + 7) // 8, torch.float64)
         # one result block of 8-byte words: records, l, g, then the candidates (f32 pairs)
         rec_w = P * N.JOINT_RECORD_DTYPE.itemsize // 8
-        lg_w = P * C if want_lg else 0
-        cand_w = (int(cand_off[-1]) + 1) // 2 if return_cand else 0
+        lg_w = P * C if dev_lg else 0
+        cand_w = (int(cand_off[-1]) + 1) // 2 if dev_cand else 0
         d_out = self._buf('joint_seg_out', rec_w + 2 * lg_w + cand_w, torch.float64)
         out = d_out.data_ptr()
-        N.check(self.lib.tpe_joint_seg_run(ctypes.byref(a), out, out + 8 * (rec_w + 2 * lg_w) if return_cand else None,
-                                           out + 8 * rec_w if want_lg else None,
-                                           out + 8 * (rec_w + lg_w) if want_lg else None,
-                                           d_scr.data_ptr(), d_scr.numel() * 8, ctypes.c_void_p(self._stream())),
+        stream = self._stream()
+        N.check(self.lib.tpe_joint_seg_run(ctypes.byref(a), out, out + 8 * (rec_w + 2 * lg_w) if dev_cand else None,
+                                           out + 8 * rec_w if dev_lg else None,
+                                           out + 8 * (rec_w + lg_w) if dev_lg else None,
+                                           d_scr.data_ptr(), d_scr.numel() * 8, ctypes.c_void_p(stream)),
                 self.lib, 'tpe_joint_seg_run')
-        host = d_out[:rec_w + 2 * lg_w + cand_w].cpu().numpy()
+        if report_k:
+            rep = self._joint_report(out + 8 * (rec_w + 2 * lg_w), out + 8 * rec_w, out + 8 * (rec_w + lg_w), P, C,
+                                     report_k, stream, cand_off=a.cand_off, widths=pd)
+        # one transfer of what the caller asked for (the report's buffers stay on the device)
+        if not report_k or (want_lg and return_cand):
+            host = d_out[:rec_w + 2 * lg_w + cand_w].cpu().numpy()
+        else:
+            hi = rec_w + (2 * lg_w if want_lg else 0)
+            host = np.empty(rec_w + 2 * lg_w + cand_w)
+            host[:hi] = d_out[:hi].cpu().numpy()
+            if return_cand:
+                host[rec_w + 2 * lg_w:] = d_out[rec_w + 2 * lg_w:rec_w + 2 * lg_w + cand_w].cpu().numpy()
         rec = host[:rec_w].view(N.JOINT_RECORD_DTYPE).copy()
-        if not (return_cand or want_lg):
+        if not (return_cand or want_lg or report_k):
             return rec
         res = [rec]
         if return_cand:
@@ -1190,10 +1268,12 @@ class Engine(object):
         if want_lg:
             res.append(host[rec_w:rec_w + lg_w].reshape(P, C).copy())
             res.append(host[rec_w + lg_w:rec_w + 2 * lg_w].reshape(P, C).copy())
+        if report_k:
+            res.extend(self._joint_report_host(rep, P, report_k, pd))
         return tuple(res)
 
     def run_joint_mixed(self, below, above, low, high, cats, ids, n_cand, seed, inject=None, return_cand=False,
-                        want_lg=False):
+                        want_lg=False, report_k=0):
         """One joint stage over a mixed group (tpe_joint_mixed_run,
         include/tpe_hip.h "Mixed joint stage"): ``below`` / ``above`` = (w [K],
         mu [K, Dc], sigma [K, Dc]) the continuous part as in ``run_joint`` (Dc
@@ -1263,10 +1343,10 @@ class Engine(object):
         for d, p in enumerate(ps):
             a.cat_upper[d], a.cat_off[d] = len(p), off
             off += len(p)
-        return self._joint_call('tpe_joint_mixed_run', a, n_ids, C, D, return_cand, want_lg)
+        return self._joint_call('tpe_joint_mixed_run', a, n_ids, C, D, return_cand, want_lg, report_k=report_k)
 
     def run_joint_quant(self, below, above, low, high, cats, quants, ids, n_cand, seed, inject=None, return_cand=False,
-                        want_lg=False, return_table=False):
+                        want_lg=False, return_table=False, report_k=0):
         """One joint stage over a group with quantised labels
         (tpe_joint_quant_run, include/tpe_hip.h "Quantised joint stage"):
         ``below`` / ``above``, ``low`` / ``high`` and ``cats`` the continuous and
@@ -1386,7 +1466,7 @@ class Engine(object):
                 'tpe_joint_quant_table_bytes')
         d_tab = self._buf('joint_qtable', (nb.value + 3) // 4, torch.float32)
         a.quant_table, a.quant_table_bytes = d_tab.data_ptr(), d_tab.numel() * 4
-        out = self._joint_call('tpe_joint_quant_run', a, n_ids, C, D, return_cand, want_lg)
+        out = self._joint_call('tpe_joint_quant_run', a, n_ids, C, D, return_cand, want_lg, report_k=report_k)
         if not return_table:
             return out
         tab = d_tab[:(a.k_below + a.k_above) * total].cpu().numpy()

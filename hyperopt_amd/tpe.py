@@ -1168,6 +1168,31 @@ def _joint_plan(table, joint, sampler, precision, shards, discrete=False, quanti
     return (None if root is None else _joint_limits(root, wide)), groups
 
 
+def _run_root_group(engine, group, hist, ids, seed, prior_weight, n_EI_candidates, gamma, **kw):
+    """Fit the root group's model and run its joint stage: (the group in kernel
+    coordinate order, the model, what the engine call returned).  ``kw``: more
+    keywords of the Engine.run_joint* call (report_k, return_cand, want_lg)."""
+    crows, drows, qrows = _joint_kernel_order(group)
+    if qrows:                                    # kernel coordinates: continuous, discrete, then quantised labels
+        group = crows + drows + qrows
+        model = _joint.fit_quant_model(crows, drows, qrows, hist, _history.split_below(hist, gamma), prior_weight,
+                                       DEFAULT_LF)
+        out = engine.run_joint_quant(model.below[:3], model.above[:3], model.low, model.high, model.cats(),
+                                     model.quants(), ids, int(n_EI_candidates), seed, **kw)
+    elif drows:                                  # kernel coordinates: the continuous labels, then the discrete ones
+        group = [r for r in group if not r.categorical] + drows
+        model = _joint.fit_mixed_model(group[:len(group) - len(drows)], drows, hist,
+                                       _history.split_below(hist, gamma), prior_weight, DEFAULT_LF)
+        out = engine.run_joint_mixed(model.below[:3], model.above[:3], model.low, model.high, model.cats(), ids,
+                                     int(n_EI_candidates), seed, **kw)
+    else:
+        model = _joint.fit_model(group, hist, _history.split_below(hist, gamma), prior_weight, DEFAULT_LF)
+        # more than TPE_JOINT_MAX_DIMS labels (joint_wide=True let them through): the wide stage
+        run = engine.run_joint_wide if len(group) > TPE_JOINT_MAX_DIMS else engine.run_joint
+        out = run(model.below, model.above, model.low, model.high, ids, int(n_EI_candidates), seed, **kw)
+    return group, model, out
+
+
 def _suggest_joint(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, device, columns, group,
                    branch_groups=()):
     """The univariate suggest of every label (the joined labels' univariate
@@ -1187,24 +1212,7 @@ def _suggest_joint(table, hist, new_ids, seed, prior_weight, n_EI_candidates, ga
     values = np.array(cc.values, dtype=np.float64)
     active = np.array(cc.active, dtype=bool)
     if group is not None:
-        crows, drows, qrows = _joint_kernel_order(group)
-        if qrows:                                    # kernel coordinates: continuous, discrete, then quantised labels
-            group = crows + drows + qrows
-            model = _joint.fit_quant_model(crows, drows, qrows, hist, _history.split_below(hist, gamma), prior_weight,
-                                           DEFAULT_LF)
-            rec = engine.run_joint_quant(model.below[:3], model.above[:3], model.low, model.high, model.cats(),
-                                         model.quants(), ids, int(n_EI_candidates), seed)
-        elif drows:                                  # kernel coordinates: the continuous labels, then the discrete ones
-            group = [r for r in group if not r.categorical] + drows
-            model = _joint.fit_mixed_model(group[:len(group) - len(drows)], drows, hist,
-                                           _history.split_below(hist, gamma), prior_weight, DEFAULT_LF)
-            rec = engine.run_joint_mixed(model.below[:3], model.above[:3], model.low, model.high, model.cats(), ids,
-                                         int(n_EI_candidates), seed)
-        else:
-            model = _joint.fit_model(group, hist, _history.split_below(hist, gamma), prior_weight, DEFAULT_LF)
-            # more than TPE_JOINT_MAX_DIMS labels (joint_wide=True let them through): the wide stage
-            run = engine.run_joint_wide if len(group) > TPE_JOINT_MAX_DIMS else engine.run_joint
-            rec = run(model.below, model.above, model.low, model.high, ids, int(n_EI_candidates), seed)
+        group, model, rec = _run_root_group(engine, group, hist, ids, seed, prior_weight, n_EI_candidates, gamma)
         if (rec['global_idx'] < 0).any():
             raise RuntimeError('no joint candidate selected')
         vals = model.values(rec['z'][:, :len(group)])
@@ -1477,6 +1485,139 @@ def candidate_report(new_id, domain, trials, seed, k=8, labels=None, prior_weigh
     return candidate_report_columns(domain.table, hist, new_id, seed, k=k, labels=labels, prior_weight=prior_weight,
                                     n_EI_candidates=n_EI_candidates, gamma=gamma, precision=precision,
                                     device=device)
+
+
+JOINT_REPORT_TOP_DTYPE = np.dtype([('l', '<f8'), ('g', '<f8'), ('score', '<f8'), ('index', '<i8')])
+
+
+class JointGroupReport(object):
+    """One joint group of a JointCandidateReport:
+
+    labels     the group's labels in kernel coordinate order (continuous,
+               discrete, quantised; each in table order)
+    condition  None for the root group, (gate label, option) for a branch group
+    vectors    float64 [n_top, D]: the ranked distinct candidate vectors as label
+               values (the group model's ``values()``: exp for the log families,
+               category indices, multiples of q)
+    top        JOINT_REPORT_TOP_DTYPE [n_top]: l, g, score = l - g and the
+               candidate index of each vector, in np.argmax order of score
+    n_top      min(k, distinct kernel rows of the pool)
+    stats      _native.SCORE_STATS_DTYPE record of all the pool's scores (as
+               CandidateReport.stats)
+    """
+    __slots__ = ('labels', 'condition', 'vectors', 'top', 'n_top', 'stats')
+
+    def __init__(self, labels, condition, vectors, top, n_top, stats):
+        self.labels, self.condition, self.vectors = list(labels), condition, vectors
+        self.top, self.n_top, self.stats = top, int(n_top), stats
+
+
+class JointCandidateReport(object):
+    """What the joint stages scored for one new id (``joint_candidate_report``):
+    ``groups``, one JointGroupReport per joint group — the root group first (if
+    any), then the branch groups in plan order.  Iterable and indexable."""
+    __slots__ = ('groups',)
+
+    def __init__(self, groups):
+        self.groups = list(groups)
+
+    def __len__(self):
+        return len(self.groups)
+
+    def __iter__(self):
+        return iter(self.groups)
+
+    def __getitem__(self, i):
+        return self.groups[i]
+
+    def dicts(self):
+        """Per group dict(labels, condition, top=[dict(vector={label: value}, l,
+        g, score, index), ...], stats=dict(...))."""
+        out = []
+        for gr in self.groups:
+            rows = [dict(vector={lab: float(v) for lab, v in zip(gr.labels, gr.vectors[i])}, l=float(e['l']),
+                         g=float(e['g']), score=float(e['score']), index=int(e['index']))
+                    for i, e in enumerate(gr.top)]
+            out.append(dict(labels=list(gr.labels), condition=gr.condition, top=rows,
+                            stats={f: gr.stats[f].item() for f in gr.stats.dtype.names}))
+        return out
+
+
+def _joint_group_report(rows, condition, model, top, z, n_top, stats):
+    n = int(n_top)
+    t = np.zeros(n, dtype=JOINT_REPORT_TOP_DTYPE)
+    t['l'], t['g'], t['index'] = top['l'][:n], top['g'][:n], top['idx'][:n]
+    with np.errstate(invalid='ignore'):
+        t['score'] = t['l'] - t['g']
+    vectors = model.values(np.asarray(z[:n, :len(rows)], dtype=np.float64)).reshape(n, len(rows))
+    return JointGroupReport([r.label for r in rows], condition, vectors, t, n, stats.copy())
+
+
+def joint_candidate_report_columns(table, hist, new_id, seed, k=8, joint=True, joint_discrete=False,
+                                   joint_quantized=False, joint_wide=False, joint_branches=False,
+                                   prior_weight=_default_prior_weight, n_EI_candidates=_default_n_EI_candidates,
+                                   gamma=_default_gamma, device=None):
+    """``joint_candidate_report`` on a structure-of-arrays history (as
+    ``candidate_report_columns`` is to ``candidate_report``)."""
+    k = _report_check_k(k)
+    if joint is False or joint is None:
+        raise ValueError('joint_candidate_report needs joint=True or joint=[labels]')
+    group, branch_groups = _joint_plan(table, joint, 'philox', 'fp32', (None, None, None, None), joint_discrete,
+                                       joint_quantized, joint_wide, joint_branches)
+    if len(hist) == 0:
+        raise ValueError('joint_candidate_report needs a history: no completed trial to fit the models from')
+    C = int(n_EI_candidates)
+    if C < 1 or C >= 2 ** 31:
+        raise ValueError('n_EI_candidates out of range: %r' % C)
+    engine = get_engine(device, 'fp32')
+    ids = np.array([int(new_id)], dtype=np.int64)
+    groups = []
+    if group is not None:
+        group, model, out = _run_root_group(engine, group, hist, ids, seed, prior_weight, C, gamma, report_k=k)
+        top, z, nt, st = out[-4:]
+        groups.append(_joint_group_report(group, None, model, top[0], z[0], nt[0], st[0]))
+    if branch_groups:
+        # every branch group as if active: fitted on the trials that took the
+        # branch, scored with its own stream word and this id — the pool a
+        # suggest that takes the branch scores
+        below_tids = _history.split_below(hist, gamma)
+        per_run = max(1, REPORT_MAX_RUN_CANDIDATES // C)
+        for lo in range(0, len(branch_groups), per_run):
+            part = branch_groups[lo:lo + per_run]
+            models = [_joint.fit_model(rows, hist, below_tids, prior_weight, DEFAULT_LF) for rows in part]
+            words = [_joint.branch_stream_word(rows) for rows in part]
+            out = engine.run_joint_segments(models, words, np.arange(len(part)), np.repeat(ids, len(part)), C, seed,
+                                            report_k=k)
+            top, z, nt, st = out[-4:]
+            for p, (rows, model) in enumerate(zip(part, models)):
+                groups.append(_joint_group_report(rows, _branch_key(rows[0]), model, top[p], z[p], nt[p], st[p]))
+    return JointCandidateReport(groups)
+
+
+def joint_candidate_report(new_id, domain, trials, seed, k=8, joint=True, joint_discrete=False, joint_quantized=False,
+                           joint_wide=False, joint_branches=False, prior_weight=_default_prior_weight,
+                           n_EI_candidates=_default_n_EI_candidates, gamma=_default_gamma, device=None):
+    """The candidate pools behind the joint stages of a ``suggest([new_id],
+    domain, trials, seed, joint=..., n_EI_candidates=...)`` with the same joint
+    keywords: per joint group the ``k`` best distinct candidate vectors with
+    their l, g and score, and statistics of the group's scores — a
+    JointCandidateReport.  Entry 0 of a group is the vector that suggest joins.
+
+    The groups are the suggest's (the same ValueErrors).  Every branch group is
+    reported as if active, whether or not ``new_id`` takes the branch.  The
+    per-candidate arrays never leave the device: the ranking and the statistics
+    are device stages (tpe_joint_report).  One new id per call; ``k`` in
+    [1, 64]."""
+    k = _report_check_k(k)
+    if joint is not False and joint is not None:
+        _joint_plan(domain.table, joint, 'philox', 'fp32', (None, None, None, None), joint_discrete, joint_quantized,
+                    joint_wide, joint_branches)          # (argument errors before the history is read)
+    hist = _history.extract(domain, trials)
+    return joint_candidate_report_columns(domain.table, hist, new_id, seed, k=k, joint=joint,
+                                          joint_discrete=joint_discrete, joint_quantized=joint_quantized,
+                                          joint_wide=joint_wide, joint_branches=joint_branches,
+                                          prior_weight=prior_weight, n_EI_candidates=n_EI_candidates, gamma=gamma,
+                                          device=device)
 
 
 def suggest_replay(new_ids, domain, trials, seed, **kw):

@@ -1005,6 +1005,77 @@ int tpe_report(const tpe_batch* batch, int32_t k, tpe_top_entry* top, int32_t* n
 int tpe_report_profile(int32_t enable, double* last_ms);
 
 /* ------------------------------------------------------------------------
+ * Joint candidate report (tpe_report.hip; ABI 24, symbols added): the k best
+ * DISTINCT candidate ROWS of every problem of a joint stage and the statistics
+ * of its scores, from the buffers tpe_joint_run, tpe_joint_mixed_run,
+ * tpe_joint_quant_run, tpe_joint_wide_run or tpe_joint_seg_run leave on the
+ * device: cand (f32, problem p's n_cand rows of width_p floats, row-major, from
+ * element cand_off[p] on; cand_off == NULL: p * n_cand * width), l_out and
+ * g_out (f64 [n_probs * n_cand]).  The stage takes arbitrary l and g: it never
+ * assumes that equal rows have equal scores.
+ *
+ * Score s = l - g (float64).  Ranked order = np.argmax order, as "Candidate
+ * report": NaN scores first (equal to each other), then descending (+-inf
+ * ordinary values), ties to the lower candidate index.  Walking that order, a
+ * candidate is kept when no kept candidate has an equal row.  Two rows are
+ * equal iff all width_p f32 coordinates compare ==: -0 equals +0, a row with a
+ * NaN coordinate equals nothing (not even itself: every such candidate is
+ * kept).  The first k kept are the problem's entries top[p * k ..] = {candidate
+ * index, l, g, 0}, n_top[p] = min(k, distinct rows) their count; entry r's row
+ * is copied (bit for bit) to top_z[(p * k + r) * z_stride ..], the floats from
+ * width_p to z_stride are 0.  The entries after n_top[p] are {-1, 0, 0, 0} with
+ * zero rows.  Statistics: tpe_score_stats, exactly as "Candidate report".
+ *
+ * Two passes, as tpe_report.  Pass 1: one 256-thread workgroup per (problem,
+ * chunk of TPE_JOINT_REPORT_CHUNK consecutive candidates); a lane keeps the
+ * score keys and a 32-bit row hash of its 16 candidates in registers.  Equal
+ * rows have equal hashes (-0 hashed as +0), so the hash only filters which
+ * rows are re-read from `cand` and compared, coordinate by coordinate, with
+ * the round winner's row in LDS: the hash never decides equality.  The chunk
+ * statistics: per-lane two-pass, a butterfly with the lower lane first, the
+ * waves in order.  Pass 2: one workgroup per problem merges the chunk lists
+ * (ranked and distinct, so only list heads compete; a chunk's list holds every
+ * entry of the problem's that lies in the chunk) against the chosen rows held
+ * in LDS (k * width floats, at most 16 KB), and the chunk statistics by Chan's
+ * update in chunk order.  No float atomics, every reduction has a fixed shape:
+ * two calls on the same buffers give the same bytes.
+ *
+ * tpe_joint_report_scratch_bytes(n_probs, n_cand, k) = n_probs * S * (80 +
+ * 32 k), S = ceil(n_cand / TPE_JOINT_REPORT_CHUNK).
+ *
+ * tpe_joint_report returns TPE_E_ARG before any launch (no device needed) for
+ * null args, buffers or outputs, k outside [1, TPE_REPORT_MAX_K], n_probs < 1,
+ * n_cand < 1, a width outside [1, TPE_JOINT_WIDE_MAX_DIMS], z_stride below the
+ * largest width, `widths` without `host_widths`, n_probs * S beyond int32, or
+ * scratch smaller than tpe_joint_report_scratch_bytes.
+ * ---------------------------------------------------------------------- */
+#define TPE_JOINT_REPORT_CHUNK 4096
+typedef struct tpe_joint_top_entry {
+  int64_t idx;           /* candidate index in the problem's pool; -1: unused entry */
+  double l, g;
+  int64_t reserved;      /* 0 */
+} tpe_joint_top_entry;
+typedef struct tpe_joint_report_args {
+  int32_t n_probs, n_cand, width, z_stride;   /* width: every problem's row width when widths == NULL */
+  const float* cand;           /* device */
+  const double *l_out, *g_out; /* device [n_probs * n_cand] */
+  const int64_t* cand_off;     /* device [n_probs] element offsets into cand; NULL: p * n_cand * width */
+  const int32_t* widths;       /* device [n_probs], each in [1, 64]; NULL: `width` */
+  const int32_t* host_widths;  /* host copy of widths for the argument check (NULL with widths == NULL) */
+} tpe_joint_report_args;
+
+int tpe_joint_report_scratch_bytes(int32_t n_probs, int32_t n_cand, int32_t k, uint64_t* bytes);
+
+/* top: device [n_probs * k]; top_z: device f32 [n_probs * k * z_stride]; n_top:
+ * device [n_probs]; stats: device [n_probs]; enqueued on `stream` (after the
+ * joint stage that wrote the buffers) */
+int tpe_joint_report(const tpe_joint_report_args* args, int32_t k, tpe_joint_top_entry* top, float* top_z,
+                     int32_t* n_top, tpe_score_stats* stats, void* scratch, uint64_t scratch_bytes, void* stream);
+
+/* tpe_report_profile for tpe_joint_report (tools/joint_report_time.py) */
+int tpe_joint_report_profile(int32_t enable, double* last_ms);
+
+/* ------------------------------------------------------------------------
  * Joint (multivariate) TPE stage (tpe_joint.hip; ABI 24): candidates are whole
  * vectors z[D] (D <= TPE_JOINT_MAX_DIMS kernel coordinates: the value, or its
  * log for the log families), a mixture component is a product of D normals
