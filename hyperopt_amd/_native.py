@@ -375,7 +375,7 @@ EXPORTS = ('tpe_abi_version', 'tpe_last_error', 'tpe_device_count', 'tpe_tile_si
            'tpe_replay_mixture', 'tpe_replay_categorical', 'tpe_level_profile', 'tpe_level_profile_read',
            'tpe_suggest_tree', 'tpe_comm_unique_id', 'tpe_comm_init', 'tpe_comm_destroy', 'tpe_combine_results',
            'tpe_host_threads', 'tpe_host_phases', 'tpe_exchange_allgather', 'tpe_debug_fast_lg',
-           'tpe_collectives_issued', 'tpe_scatter_f64', 'tpe_move_ranges', 'tpe_report_scratch_bytes', 'tpe_report',
+           'tpe_collectives_issued', 'tpe_level_resident', 'tpe_scatter_f64', 'tpe_move_ranges', 'tpe_report_scratch_bytes', 'tpe_report',
            'tpe_report_profile', 'tpe_joint_scratch_bytes', 'tpe_joint_run', 'tpe_joint_profile',
            'tpe_joint_mixed_run', 'tpe_joint_quant_table_bytes', 'tpe_joint_quant_run', 'tpe_joint_quant_profile',
            'tpe_joint_wide_scratch_bytes', 'tpe_joint_wide_run', 'tpe_joint_wide_profile',
@@ -479,6 +479,8 @@ def load(path=LIB_PATH):
     lib.tpe_host_phases.restype = ctypes.c_int
     lib.tpe_debug_fast_lg.argtypes = [P, I64]
     lib.tpe_debug_fast_lg.restype = ctypes.c_int
+    lib.tpe_level_resident.argtypes = [I32, ctypes.POINTER(I64)]
+    lib.tpe_level_resident.restype = ctypes.c_int
     lib.tpe_collectives_issued.argtypes = [ctypes.POINTER(I64)]
     lib.tpe_collectives_issued.restype = ctypes.c_int
     lib.tpe_scatter_f64.argtypes = [P, I64, P, P]
@@ -557,3 +559,12 @@ def collectives_issued(lib=None):
     n = ctypes.c_int64(0)
     check(lib.tpe_collectives_issued(ctypes.byref(n)), lib, 'tpe_collectives_issued')
     return int(n.value)
+
+
+def level_resident(mode=-1, lib=None):
+    """tpe_level_resident: set the resident-level mode (0 off and drop, 1 on,
+    2 drop only, < 0 query); returns (on, {hits, misses, fit_reuses, drops})."""
+    lib = lib or load()
+    st = (ctypes.c_int64 * 4)()
+    on = lib.tpe_level_resident(int(mode), st)
+    return bool(on), dict(zip(('hits', 'misses', 'fit_reuses', 'drops'), (int(v) for v in st)))

@@ -24,6 +24,7 @@ def build(force=False, verbose=False, out=OUT, defines=()):
     -D `defines` on the kernels: A/B variants for tools/)."""
     OUT = out
     deps = [SRC, HOST_SRC, SUGGEST_SRC, POOL_SRC, REPORT_SRC, JOINT_SRC, RNG_HDR, os.path.join(HERE, 'csrc', 'tpe_pool.h'), os.path.join(HERE, 'csrc', 'sort_net.h'),
+            os.path.join(HERE, 'csrc', 'tpe_keystore.h'),
             os.path.join(HERE, '..', 'include', 'tpe_hip.h'), os.path.abspath(__file__)]
     if out == os.path.join(HERE, 'libtpe_hip.so'):
         build_hostaddr(force, verbose)
@@ -40,7 +41,7 @@ def build(force=False, verbose=False, out=OUT, defines=()):
     report_o = os.path.join(HERE, 'csrc', 'tpe_report.o')
     joint_o = os.path.join(HERE, 'csrc', 'tpe_joint.o')
     hdr = [os.path.join(HERE, '..', 'include', 'tpe_hip.h'), os.path.join(HERE, 'csrc', 'tpe_pool.h'),
-           os.path.join(HERE, 'csrc', 'sort_net.h')]
+           os.path.join(HERE, 'csrc', 'sort_net.h'), os.path.join(HERE, 'csrc', 'tpe_keystore.h')]
     host_flags = [gxx, '-O3', '-march=' + HOST_MARCH, '-std=c++17', '-fPIC', '-Wall']
     numpy_fp = ['-ffp-contract=off', '-fno-fast-math', '-fno-trapping-math']
     # (object, its sources, compile command): an object is rebuilt when a source

@@ -2026,10 +2026,21 @@ int tpe_internal_pack_plan(const tpe_label_in* labels, int32_t n_labels, int32_t
 
 __attribute__((visibility("hidden"))) int tpe_internal_pack_fill(tpe_pack_info* info) { return pack_fill(info); }
 
+// the packer's per-call switches as one word: part of a resident level's key
+// (tpe_kernels.hip), since a level packed under other switches is another level
+__attribute__((visibility("hidden"))) uint64_t tpe_internal_pack_switches(void) {
+  const double r = devfit_ratio();
+  uint64_t rb;
+  memcpy(&rb, &r, sizeof(rb));
+  return (rb << 4) ^ (rb >> 60) ^ ((uint64_t)expand_enabled() | (uint64_t)tables_enabled() << 1 |
+                                   (uint64_t)fgt_enabled() << 2 | (uint64_t)logpoly_enabled() << 3);
+}
+
 __attribute__((target_clones("avx512f", "avx2", "default")))
 int tpe_host_pack_level(const tpe_label_in* labels, int32_t n_labels, int32_t n_cand, uint64_t seed,
                         int64_t cand_base, int64_t n_cand_global, int32_t precision, void* blob, int64_t blob_cap,
                         tpe_pack_info* info) {
+  tpe_pool::epoch_bump();                 // (packs into caller memory: a resident level may live there)
   TpePackLead lead;
   const int rc = pack_plan(labels, n_labels, n_cand, seed, cand_base, n_cand_global, precision, blob, blob_cap, info,
                            &lead);

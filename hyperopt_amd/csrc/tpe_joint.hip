@@ -41,6 +41,8 @@
 #include "../../include/tpe_hip.h"
 #include "tpe_device_rng.h"
 
+extern "C" void tpe_internal_epoch_bump(void);                    // tpe_kernels.hip (hidden): the device epoch
+
 extern "C" int tpe_internal_fail(int code, const char* what);   // tpe_kernels.hip (hidden)
 
 namespace {
@@ -1358,6 +1360,7 @@ int tpe_joint_scratch_bytes(int32_t n_ids, int32_t n_cand, uint64_t* bytes) {
 
 int tpe_joint_run(const tpe_joint_args* a, tpe_joint_record* records, float* cand, double* l_out, double* g_out,
                   void* scratch, uint64_t scratch_bytes, void* stream) {
+  tpe_internal_epoch_bump();
   if (!a) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run: null args");
   if (a->n_dims < 1 || a->n_dims > TPE_JOINT_MAX_DIMS)
     return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run: n_dims outside [1, TPE_JOINT_MAX_DIMS]");
@@ -1430,6 +1433,7 @@ int tpe_joint_seg_scratch_bytes(int32_t n_probs, int32_t n_cand, uint64_t* bytes
 
 int tpe_joint_seg_run(const tpe_joint_seg_args* a, tpe_joint_record* records, float* cand, double* l_out,
                       double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
+  tpe_internal_epoch_bump();
   if (!a) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: null args");
   if (a->n_segs < 1) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: n_segs < 1");
   if (a->n_probs < 1) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: n_probs < 1");
@@ -1547,6 +1551,7 @@ int tpe_joint_wide_profile(double* sample_ms) {
 
 int tpe_joint_wide_run(const tpe_joint_wide_args* a, tpe_joint_wide_record* records, float* cand, double* l_out,
                        double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
+  tpe_internal_epoch_bump();
   if (!a) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_wide_run: null args");
   if (a->n_dims < 1 || a->n_dims > TPE_JOINT_WIDE_MAX_DIMS)
     return tpe_internal_fail(TPE_E_ARG, "tpe_joint_wide_run: n_dims outside [1, TPE_JOINT_WIDE_MAX_DIMS]");
@@ -1635,6 +1640,7 @@ int tpe_joint_wide_run(const tpe_joint_wide_args* a, tpe_joint_wide_record* reco
 
 int tpe_joint_mixed_run(const tpe_joint_mixed_args* a, tpe_joint_record* records, float* cand, double* l_out,
                         double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
+  tpe_internal_epoch_bump();
   if (!a) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: null args");
   if (a->n_cat < 0) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: n_cat < 0");
   if (a->n_dims < 0 || a->n_dims > TPE_JOINT_MAX_DIMS || a->n_dims + a->n_cat < 1 ||
@@ -1753,6 +1759,7 @@ int tpe_joint_quant_profile(double* table_ms) {
 
 int tpe_joint_quant_run(const tpe_joint_quant_args* a, tpe_joint_record* records, float* cand, double* l_out,
                         double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
+  tpe_internal_epoch_bump();
   static_assert(offsetof(tpe_joint_quant_args, n_quant) == sizeof(tpe_joint_mixed_args), "the shared fields");
   static_assert(offsetof(tpe_joint_quant_args, cat_cum) == offsetof(tpe_joint_mixed_args, cat_cum), "the shared fields");
   if (!a) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: null args");

@@ -47,6 +47,7 @@
 #include "tpe_device_rng.h"
 
 extern "C" void tpe_internal_phase(int i);   // tpe_suggest.cpp: host phase clock (hidden)
+extern "C" uint64_t tpe_internal_pack_switches(void);   // tpe_host.cpp: the packer's per-call switches (hidden)
 
 namespace {
 
@@ -87,6 +88,14 @@ int hip_check(const char* stage) {
     return TPE_E_HIP;
   }
   return TPE_OK;
+}
+
+// the device epoch (tpe_pool.h, include/tpe_hip.h "Resident levels"): every
+// exported entry that enqueues device work bumps it — except from inside a
+// level run of the library's own (g_epoch_quiet), which bumps once, as a miss
+thread_local int g_epoch_quiet = 0;
+inline void epoch_bump() {
+  if (!g_epoch_quiet) tpe_pool::epoch_bump();
 }
 
 // (Philox-4x32-10, the open-interval uniforms and ndtri_f32: tpe_device_rng.h)
@@ -3802,6 +3811,41 @@ constexpr int kExpandThreads = 256;
 constexpr int kProbWords = (int)(sizeof(tpe_problem) / 8);
 static_assert(sizeof(tpe_problem) % 8 == 0, "problem rows in 8-byte words");
 
+// A resident level's per-call step (include/tpe_hip.h "Resident levels"): the
+// device blob, its tables included, is the previous run's; only the Philox key
+// and the new id of each problem row differ.  One block per problem reads the
+// two 8-byte words that hold them — {key0, key1} and {ctr2, ctr3} — from the
+// host-written row in pinned memory (system-scope loads, as k_upload), stores
+// them into its device row, and selects a lazy categorical problem on the
+// patched row, staged in LDS (the job the table stage's extra blocks do on a
+// level that is not resident; same workgroup size, so the same scan rounds).
+constexpr int kKeyWord = (int)(offsetof(tpe_problem, key0) / 8);
+static_assert(offsetof(tpe_problem, key0) % 8 == 0 && offsetof(tpe_problem, key1) == offsetof(tpe_problem, key0) + 4 &&
+              offsetof(tpe_problem, ctr2) == offsetof(tpe_problem, key0) + 8 &&
+              offsetof(tpe_problem, ctr3) == offsetof(tpe_problem, key0) + 12, "the per-call words of a problem row");
+static_assert(kProbWords <= kTabTblThreads, "a thread a row word");
+__global__ __launch_bounds__(kTabTblThreads) void k_resident_patch(const unsigned long long* __restrict__ host_rows,
+                                                                   unsigned long long* prob_words, int lazy,
+                                                                   const double* __restrict__ samp,
+                                                                   const double4* __restrict__ comp64,
+                                                                   tpe_result* __restrict__ result) {
+  __shared__ tpe_problem sp;
+  const int64_t w0 = (int64_t)blockIdx.x * kProbWords;
+  const int t = (int)threadIdx.x;
+  if (t < kProbWords) {
+    unsigned long long v;
+    if (t == kKeyWord || t == kKeyWord + 1) {
+      v = __hip_atomic_load(host_rows + w0 + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      prob_words[w0 + t] = v;
+    } else {
+      v = prob_words[w0 + t];
+    }
+    ((unsigned long long*)&sp)[t] = v;
+  }
+  __syncthreads();
+  if (lazy && lazy_eligible(sp)) select_cat_lazy(sp, samp, comp64, result + blockIdx.x);
+}
+
 __global__ __launch_bounds__(kExpandThreads) void k_expand(const tpe_problem* __restrict__ tmpl,
                                                            const int32_t* __restrict__ first, int n_lab,
                                                            const uint32_t* __restrict__ new_id,
@@ -5073,6 +5117,7 @@ int tpe_sort_workspace_bytes(int64_t total_cand, uint64_t* bytes) {
 }
 
 int tpe_fit_above(const tpe_batch* b, void* stream) {
+  epoch_bump();
   int rc = check_batch(b);
   if (rc) return rc;
   if (b->n_fit == 0) return TPE_OK;
@@ -5139,6 +5184,7 @@ int tpe_fit_above(const tpe_batch* b, void* stream) {
 }
 
 int tpe_tables(const tpe_batch* b, void* stream) {
+  epoch_bump();
   int rc = check_batch(b);
   if (rc) return rc;
   if (b->n_tab_jobs == 0 || (b->tab_blocks == 0 && b->fgt_max_cells == 0)) return TPE_OK;
@@ -5199,6 +5245,7 @@ void launch_fast(const tpe_batch* b, int wgs, size_t lds, hipStream_t s, int n_t
 }
 
 int tpe_sample(const tpe_batch* b, void* stream) {
+  epoch_bump();
   int rc = check_batch(b);
   if (rc) return rc;
   if (b->sample && !b->samp && b->n_tiles) return fail(TPE_E_ARG, "null sampler table");
@@ -5264,6 +5311,7 @@ int tpe_sample(const tpe_batch* b, void* stream) {
 }
 
 int tpe_sort(const tpe_batch* b, void* stream) {
+  epoch_bump();
   int rc = check_batch(b);
   if (rc) return rc;
   // sort_end_bit == 0: no sort; the caller aliases keys_sorted/vals_sorted to keys/vals.
@@ -5283,6 +5331,7 @@ int tpe_sort(const tpe_batch* b, void* stream) {
 }
 
 int tpe_score_above(const tpe_batch* b, void* stream) {
+  epoch_bump();
   int rc = check_batch(b);
   if (rc) return rc;
   const int n_cont = b->n_work_cont, n_qg = b->n_work_qgauss, n_ql = b->n_work_qlog;
@@ -5307,6 +5356,7 @@ int tpe_score_above(const tpe_batch* b, void* stream) {
 }
 
 int tpe_finalize(const tpe_batch* b, void* stream) {
+  epoch_bump();
   int rc = check_batch(b);
   if (rc) return rc;
   if (b->n_tiles == 0) return TPE_OK;
@@ -5323,6 +5373,7 @@ int tpe_finalize(const tpe_batch* b, void* stream) {
 }
 
 int tpe_select(const tpe_batch* b, void* stream) {
+  epoch_bump();
   int rc = check_batch(b);
   if (rc) return rc;
   if (b->n_problems == 0 || (b->early_select && b->n_late == 0)) return TPE_OK;
@@ -5334,6 +5385,7 @@ int tpe_select(const tpe_batch* b, void* stream) {
 }
 
 int tpe_run_batch(const tpe_batch* b, void* stream) {
+  epoch_bump();
   int rc = check_batch(b);
   if (rc) return rc;
   if ((rc = tpe_fit_above(b, stream))) return rc;
@@ -5379,10 +5431,42 @@ int tpe_level_profile_read(tpe_stage_prof* out, int32_t n) {
   return TPE_OK;
 }
 
+// a resident level's hit (level_run_impl): the rows k_resident_patch reads and
+// writes, and whether it selects the lazy categoricals
+struct ResidentPatch {
+  const unsigned long long* host_rows;
+  unsigned long long* dev_rows;
+  int lazy;
+};
+static thread_local const ResidentPatch* g_patch = nullptr;
+
+// the table stage of a level run: the tables — or, on a resident level's hit,
+// the per-call patch of the problem rows (the tables are the previous run's)
+static int level_tables(const tpe_batch* b, void* stream) {
+  const ResidentPatch* h = g_patch;
+  if (!h) return tpe_tables(b, stream);
+  TPE_LAUNCH(k_resident_patch, dim3(b->n_problems), dim3(kTabTblThreads), 0, (hipStream_t)stream, h->host_rows,
+             h->dev_rows, h->lazy, b->samp, (const double4*)b->comp64, b->result);
+  return hip_check("k_resident_patch");
+}
+
+// tpe_run_batch with level_tables in the table stage's place
+static int level_stages(const tpe_batch* b, void* stream) {
+  int rc = check_batch(b);
+  if (rc) return rc;
+  if ((rc = tpe_fit_above(b, stream))) return rc;
+  if ((rc = level_tables(b, stream))) return rc;
+  if ((rc = tpe_sample(b, stream))) return rc;
+  if ((rc = tpe_sort(b, stream))) return rc;
+  if ((rc = tpe_score_above(b, stream))) return rc;
+  if ((rc = tpe_finalize(b, stream))) return rc;
+  return tpe_select(b, stream);
+}
+
 // tpe_run_batch's stages, each followed by an event
 static int run_batch_profiled(const tpe_batch* b, void* stream) {
   typedef int (*stage_fn)(const tpe_batch*, void*);
-  static const stage_fn fns[TPE_N_STAGES] = {tpe_fit_above, tpe_tables, tpe_sample, tpe_sort,
+  static const stage_fn fns[TPE_N_STAGES] = {tpe_fit_above, level_tables, tpe_sample, tpe_sort,
                                              tpe_score_above, tpe_finalize, tpe_select};
   hipStream_t s = (hipStream_t)stream;
   if (hipEventRecord(g_prof.ev[0], s) != hipSuccess) return hip_check("tpe_level_profile");
@@ -5453,10 +5537,31 @@ struct LevelEx {
   int32_t* done;         // 1: the exchange ran (out holds the global winners); 0: the caller exchanges
 };
 
+// what tpe_suggest_tree adds to its level runs (tpe_internal_level_run_gen):
+// each label's fit generation (0: never the same twice) — the evidence a
+// resident level rests on — and a call made after the level's last launch,
+// before the stream synchronise, while the host would only wait
+struct LevelGen {
+  const uint64_t* gens;
+  void (*after_launch)(void*);
+  void* ctx;
+};
+
 static int level_run_impl(const tpe_label_in* labels, int32_t n_labels, int32_t n_cand, uint64_t seed,
                           int64_t cand_base, int64_t n_cand_global, int32_t precision, int32_t flags,
                           const tpe_level_ws* ws, tpe_level_need* need, void* stream, tpe_result* out,
-                          const LevelEx* lx);
+                          const LevelEx* lx, const LevelGen* lg = nullptr);
+
+// tpe_level_run as tpe_suggest_tree issues it: with the labels' generations, so
+// that the level may stay resident (a direct tpe_level_run never is)
+__attribute__((visibility("hidden"))) int tpe_internal_level_run_gen(
+    const tpe_label_in* labels, int32_t n_labels, int32_t n_cand, uint64_t seed, int64_t cand_base,
+    int64_t n_cand_global, int32_t precision, int32_t flags, const tpe_level_ws* ws, tpe_level_need* need,
+    void* stream, tpe_result* out, const uint64_t* gens, void (*after_launch)(void*), void* ctx) {
+  const LevelGen lg{gens, after_launch, ctx};
+  return level_run_impl(labels, n_labels, n_cand, seed, cand_base, n_cand_global, precision, flags, ws, need, stream,
+                        out, nullptr, &lg);
+}
 
 int tpe_level_run(const tpe_label_in* labels, int32_t n_labels, int32_t n_cand, uint64_t seed, int64_t cand_base,
                   int64_t n_cand_global, int32_t precision, int32_t flags, const tpe_level_ws* ws,
@@ -5926,10 +6031,83 @@ static bool level_reduce_runs(const LevelRun& x, const tpe_batch& b, tpe_result*
   return false;
 }
 
+// ---------------------------------------------------------------- resident levels
+// (include/tpe_hip.h "Resident levels")
+constexpr int64_t kResidentMaxProblems = 1024;     // rows a record copies (a batched level is never resident)
+
+// TPE_RESIDENT_LEVEL=0: no fit reuse, no resident level (A/B; read once)
+static bool resident_env_on() {
+  static const bool on = [] { const char* e = getenv("TPE_RESIDENT_LEVEL"); return !(e && e[0] == '0'); }();
+  return on;
+}
+static std::atomic<int> g_resident_mode{1};
+static std::atomic<int64_t> g_resident_stats[4];    // hits, misses, fit reuses, drops
+enum { RES_HITS = 0, RES_MISSES = 1, RES_FIT_REUSES = 2, RES_DROPS = 3 };
+
+__attribute__((visibility("hidden"))) int tpe_internal_resident_on(void) {
+  return resident_env_on() && g_resident_mode.load(std::memory_order_relaxed) != 0;
+}
+__attribute__((visibility("hidden"))) void tpe_internal_resident_count(int which, int64_t n) {
+  if (which >= 0 && which < 4) g_resident_stats[which].fetch_add(n, std::memory_order_relaxed);
+}
+__attribute__((visibility("hidden"))) void tpe_internal_epoch_bump(void) { tpe_pool::epoch_bump(); }
+
+int tpe_level_resident(int32_t mode, int64_t* stats) {
+  if (mode == 0 || mode == 1) g_resident_mode.store(mode, std::memory_order_relaxed);
+  if (mode == 0 || mode == 2) {                       // (every thread's record: they die with the epoch)
+    tpe_pool::epoch_bump();
+    g_resident_stats[RES_DROPS].fetch_add(1, std::memory_order_relaxed);
+  }
+  if (stats)
+    for (int i = 0; i < 4; ++i) stats[i] = g_resident_stats[i].load(std::memory_order_relaxed);
+  return tpe_internal_resident_on();
+}
+
+// the calling thread's resident level: what its device blob, tables and pinned
+// staging buffer hold, and the exact key of the run that wrote them
+struct ResidentRec {
+  bool live = false;
+  uint64_t epoch = 0;
+  std::vector<uint64_t> key;
+  tpe_pack_info info;
+  std::vector<tpe_problem> hp;         // the host-written problem rows (the hit's early selection and reduction)
+};
+static thread_local ResidentRec g_res;
+static thread_local std::vector<uint64_t> g_res_key;
+
+// the level key: everything but the labels' content (their generations stand
+// for it) that the packed level, its tables or the launches depend on
+static void resident_key(const tpe_label_in* labels, int32_t n_labels, const uint64_t* gens, int32_t n_cand,
+                         int64_t cand_base, int64_t n_cand_global, int32_t precision, int32_t flags,
+                         const tpe_level_ws* ws, bool exchange, std::vector<uint64_t>& key) {
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = -1; }
+  constexpr size_t ws_words = (sizeof(tpe_level_ws) + 7) / 8;
+  key.assign(8 + ws_words + 3 * (size_t)n_labels, 0);
+  key[0] = (uint64_t)n_labels; key[1] = (uint64_t)(int64_t)n_cand; key[2] = (uint64_t)cand_base;
+  key[3] = (uint64_t)n_cand_global; key[4] = (uint64_t)(int64_t)precision; key[5] = (uint64_t)(int64_t)flags;
+  key[6] = (uint64_t)(int64_t)dev; key[7] = (exchange ? 1 : 0) ^ (tpe_internal_pack_switches() << 1);
+  memcpy(key.data() + 8, ws, sizeof(tpe_level_ws));   // every pointer and capacity, pinned_dev included
+  uint64_t* k = key.data() + 8 + ws_words;
+  for (int32_t i = 0; i < n_labels; ++i) {
+    k[3 * i] = (uint64_t)(int64_t)labels[i].label_ix;
+    k[3 * i + 1] = gens[i];
+    k[3 * i + 2] = (uint64_t)labels[i].n_ids;
+  }
+}
+
+struct EpochQuiet {
+  EpochQuiet() { ++g_epoch_quiet; }
+  ~EpochQuiet() { --g_epoch_quiet; }
+};
+struct PatchScope {                    // (g_patch set for the hit's launches only)
+  ~PatchScope() { g_patch = nullptr; }
+};
+
 static int level_run_impl(const tpe_label_in* labels, int32_t n_labels, int32_t n_cand, uint64_t seed,
                           int64_t cand_base, int64_t n_cand_global, int32_t precision, int32_t flags,
                           const tpe_level_ws* ws, tpe_level_need* need, void* stream, tpe_result* out,
-                          const LevelEx* lx) {
+                          const LevelEx* lx, const LevelGen* lg) {
   if (!ws || !need || (n_labels > 0 && !out)) return fail(TPE_E_ARG, "null workspace/need/out");
   memset(need, 0, sizeof(*need));
   LevelRun x;
@@ -5938,6 +6116,80 @@ static int level_run_impl(const tpe_label_in* labels, int32_t n_labels, int32_t 
   x.n_cand = n_cand; x.precision = precision; x.flags = flags;
   x.host = (unsigned char*)ws->pinned; x.dev = (unsigned char*)ws->blob;
   const tpe_pack_info& info = x.info;
+  // a level run with generations may be resident: every label's fit keyed
+  // (generation 0: never), no candidate output, no exchange (a candidate-sharded
+  // level stays on the miss path)
+  EpochQuiet quiet;
+  PatchScope patch_scope;
+  ResidentRec& rec = g_res;
+  bool want = lg && lg->gens && n_labels > 0 && labels && tpe_internal_resident_on() && !(lx && lx->ex) &&
+              !(flags & TPE_BATCH_WRITE_CAND) && ws->pinned && ws->blob && direct_results();
+  for (int32_t i = 0; want && i < n_labels; ++i)
+    want = lg->gens[i] != 0 && labels[i].n_ids >= 0 && (labels[i].n_ids == 0 || labels[i].ids);
+  if (want) resident_key(labels, n_labels, lg->gens, n_cand, cand_base, n_cand_global, precision, flags, ws, false, g_res_key);
+  const bool hit = want && rec.live && rec.epoch == tpe_pool::epoch() && rec.key == g_res_key;
+  if (hit) {
+    // the blob, the tables and the staging buffer are this level's: only the
+    // Philox key and the new ids go to the device (k_resident_patch)
+    x.info = rec.info;
+    int rc = level_need(x, TPE_OK, need);
+    x.dbase = pinned_alias(ws);
+    if (rc != TPE_OK || !x.dbase) {
+      rec.live = false;
+      g_resident_stats[RES_DROPS].fetch_add(1, std::memory_order_relaxed);
+      return rc != TPE_OK ? rc : fail(TPE_E_ARG, "tpe_level_run: the resident level's staging buffer lost its device address");
+    }
+    const int64_t P = x.P;
+    x.n_tiles_p = info.n_tiles / P;
+    tpe_problem* hrow = (tpe_problem*)(x.host + info.off_problems);
+    tpe_problem* crow = rec.hp.data();
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    int64_t r = 0;
+    for (int32_t li = 0; li < n_labels; ++li)           // (the packer's row order: step_prob)
+      for (int64_t j = 0; j < labels[li].n_ids; ++j, ++r) {
+        const uint32_t c3 = (uint32_t)labels[li].ids[j];
+        hrow[r].key0 = crow[r].key0 = k0;
+        hrow[r].key1 = crow[r].key1 = k1;
+        hrow[r].ctr3 = crow[r].ctr3 = c3;
+      }
+    tpe_internal_phase(TPE_PHASE_PACK);
+    x.hp = crow;
+    tpe_batch b;
+    level_batch(x, b);
+    level_early_select(x, b);
+    // (the lazy categoricals: selected here where the table stage's extra
+    // blocks would have, else by the select stage as on a miss)
+    const bool tab_lazy = b.early_select && !(b.n_tab_jobs == 0 || (b.tab_blocks == 0 && b.fgt_max_cells == 0));
+    const ResidentPatch pt{(const unsigned long long*)(x.dbase + info.off_problems),
+                           (unsigned long long*)(x.dev + info.off_problems), tab_lazy && lazy_ok(&b) ? 1 : 0};
+    g_patch = &pt;
+    if (g_prof.on) {
+      g_prof.valid = 0;
+      if ((rc = check_batch(&b)) || (rc = run_batch_profiled(&b, stream))) { rec.live = false; return rc; }
+    } else if ((rc = level_stages(&b, stream))) {
+      rec.live = false;
+      return rc;
+    }
+    g_patch = nullptr;
+    tpe_result* rh = (tpe_result*)(x.host + x.res_off);
+    tpe_internal_phase(TPE_PHASE_LAUNCHED);
+    if (lg->after_launch) lg->after_launch(lg->ctx);
+    const hipError_t e = hipStreamSynchronize(x.s);
+    if (e != hipSuccess) { rec.live = false; return fail(TPE_E_HIP, hipGetErrorString(e)); }
+    tpe_internal_phase(TPE_PHASE_SYNCED);
+    if (!(b.early_select && level_reduce_runs(x, b, rh, out))) memcpy(out, rh, (size_t)P * sizeof(tpe_result));
+    tpe_internal_phase(TPE_PHASE_LEVEL);
+    g_resident_stats[RES_HITS].fetch_add(1, std::memory_order_relaxed);
+    return g_prof.on ? profile_collect(b, info, x.hp, nullptr, n_cand) : TPE_OK;
+  }
+  // a miss writes the staging buffer, the blob and the tables: whatever was
+  // resident there — this thread's record or another's — is gone
+  if (rec.live) {
+    rec.live = false;
+    g_resident_stats[RES_DROPS].fetch_add(1, std::memory_order_relaxed);
+  }
+  const uint64_t my_epoch = tpe_pool::epoch_bump();
+  if (lg && lg->gens && tpe_internal_resident_on()) g_resident_stats[RES_MISSES].fetch_add(1, std::memory_order_relaxed);
   // pack straight into the pinned staging buffer; the result readback area
   // follows the blob.  A level with device fits launches them between the
   // pack's plan and its fill, as soon as their jobs are placed, unless profiling
@@ -5972,6 +6224,10 @@ static int level_run_impl(const tpe_label_in* labels, int32_t n_labels, int32_t 
   } else if ((rc = tpe_run_batch(&b, stream))) {
     return rc;
   }
+  // this level stays resident when nothing on the device rewrote what the host
+  // packed (no device fit, no expansion) and its results come back directly
+  const bool keep = want && !dex && x.dbase && x.hp && info.n_fit == 0 && info.n_expand == 0 &&
+                    P <= kResidentMaxProblems;
   if (dex) {
     if ((rc = level_exchange(x, lx, b, out))) return rc;
   } else {
@@ -5979,10 +6235,19 @@ static int level_run_impl(const tpe_label_in* labels, int32_t n_labels, int32_t 
     hipError_t e = x.dbase ? hipSuccess
                            : hipMemcpyAsync(rh, ws->result, (size_t)P * sizeof(tpe_result), hipMemcpyDeviceToHost, x.s);
     tpe_internal_phase(TPE_PHASE_LAUNCHED);
+    // (while the device works: the record's copy of the rows, the caller's key copies)
+    if (keep && e == hipSuccess) rec.hp.assign(x.hp, x.hp + P);
+    if (lg && lg->after_launch) lg->after_launch(lg->ctx);
     if (e == hipSuccess) e = hipStreamSynchronize(x.s);
     if (e != hipSuccess) return fail(TPE_E_HIP, hipGetErrorString(e));
     tpe_internal_phase(TPE_PHASE_SYNCED);
     if (!(b.early_select && level_reduce_runs(x, b, rh, out))) memcpy(out, rh, (size_t)P * sizeof(tpe_result));
+    if (keep) {
+      rec.info = info;
+      rec.key.swap(g_res_key);
+      rec.epoch = my_epoch;
+      rec.live = true;
+    }
   }
   tpe_internal_phase(TPE_PHASE_LEVEL);
   return g_prof.on ? profile_collect(b, info, x.xtmpl ? x.xtmpl : x.hp, x.xfirst, n_cand) : TPE_OK;
@@ -6045,6 +6310,7 @@ __attribute__((visibility("hidden"))) int rccl_allgather_inplace(const tpe_excha
 }
 
 int tpe_scatter_f64(const void* src, int64_t k, double* dst, void* stream) {
+  epoch_bump();
   if (k < 0 || (k > 0 && (!src || !dst))) return fail(TPE_E_ARG, "tpe_scatter_f64: bad arguments");
   if (k == 0) return TPE_OK;
   const unsigned int grid = (unsigned int)std::min<int64_t>((k + kColThreads - 1) / kColThreads, 1024);
@@ -6055,6 +6321,7 @@ int tpe_scatter_f64(const void* src, int64_t k, double* dst, void* stream) {
 
 int tpe_move_ranges(const void* ranges, int32_t n_ranges, int32_t elem_bytes, const void* src, void* dst,
                     void* stream) {
+  epoch_bump();
   if (n_ranges < 0 || (elem_bytes != 4 && elem_bytes != 8) || (n_ranges > 0 && (!ranges || !src || !dst)) ||
       src == dst)
     return fail(TPE_E_ARG, "tpe_move_ranges: bad arguments");
@@ -6124,6 +6391,7 @@ int tpe_combine_results(const tpe_result* all, int32_t world, int64_t P, tpe_res
 }
 
 int tpe_exchange_allgather(const tpe_exchange* ex, const void* mine, int64_t bytes, void* all, void* stream) {
+  epoch_bump();
   if (!ex || bytes < 0 || (bytes > 0 && (!mine || !all)) || ex->world < 1 || ex->rank < 0 || ex->rank >= ex->world)
     return fail(TPE_E_ARG, "tpe_exchange_allgather: bad arguments");
   const int W = ex->world;

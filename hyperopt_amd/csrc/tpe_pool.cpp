@@ -299,6 +299,12 @@ int workers() {
   return std::max(0, total_threads() - 1);
 }
 
+// (relaxed: a record and the bump that kills it meet on one thread, or are
+// ordered by whatever hands the workspace from one thread to another)
+static std::atomic<uint64_t> g_epoch{1};
+uint64_t epoch_bump() { return g_epoch.fetch_add(1, std::memory_order_relaxed) + 1; }
+uint64_t epoch() { return g_epoch.load(std::memory_order_relaxed); }
+
 }  // namespace tpe_pool
 
 extern "C" int tpe_host_threads(int32_t n, int32_t* previous) {

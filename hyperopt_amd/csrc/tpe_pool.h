@@ -21,6 +21,12 @@ void parallel_for(int n, void (*fn)(void* ctx, int i), void* ctx);
 // workers the next parallel_for may use (the caller not counted)
 int workers();
 
+// the process-wide device epoch (include/tpe_hip.h "Resident levels"): bumped
+// by every exported entry that enqueues device work or packs into caller
+// memory (returns the new epoch); a resident level of an older epoch is dead
+uint64_t epoch_bump();
+uint64_t epoch();
+
 }  // namespace tpe_pool
 
 // tpe_host_pack_level in its two steps (tpe_host.cpp; internal).  The plan

@@ -24,6 +24,7 @@
 #include "../../include/tpe_hip.h"
 
 extern "C" int tpe_internal_fail(int code, const char* what);   // tpe_kernels.hip (hidden)
+extern "C" void tpe_internal_epoch_bump(void);                    // tpe_kernels.hip (hidden): the device epoch
 
 namespace {
 
@@ -525,6 +526,7 @@ int tpe_report_scratch_bytes(int64_t n_chunks_total, int32_t k, uint64_t* bytes)
 
 int tpe_report(const tpe_batch* b, int32_t k, tpe_top_entry* top, int32_t* n_top, tpe_score_stats* stats,
                void* scratch, uint64_t scratch_bytes, void* stream) {
+  tpe_internal_epoch_bump();
   if (!b) return tpe_internal_fail(TPE_E_ARG, "tpe_report: null batch");
   if (k < 1 || k > TPE_REPORT_MAX_K) return tpe_internal_fail(TPE_E_ARG, "tpe_report: k outside [1, TPE_REPORT_MAX_K]");
   if (b->n_problems < 0 || b->total_cand < 0) return tpe_internal_fail(TPE_E_ARG, "tpe_report: negative count");
@@ -574,6 +576,7 @@ int tpe_joint_report_scratch_bytes(int32_t n_probs, int32_t n_cand, int32_t k, u
 
 int tpe_joint_report(const tpe_joint_report_args* a, int32_t k, tpe_joint_top_entry* top, float* top_z,
                      int32_t* n_top, tpe_score_stats* stats, void* scratch, uint64_t scratch_bytes, void* stream) {
+  tpe_internal_epoch_bump();
   if (!a) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_report: null args");
   if (k < 1 || k > TPE_REPORT_MAX_K)
     return tpe_internal_fail(TPE_E_ARG, "tpe_joint_report: k outside [1, TPE_REPORT_MAX_K]");

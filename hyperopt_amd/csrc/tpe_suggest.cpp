@@ -24,6 +24,7 @@
 
 #include "../../include/tpe_hip.h"
 #include "sort_net.h"
+#include "tpe_keystore.h"
 #include "tpe_pool.h"
 
 extern "C" int tpe_internal_fail(int code, const char* what);   // tpe_kernels.hip (hidden)
@@ -34,6 +35,13 @@ extern "C" int tpe_internal_level_run_ex(const tpe_label_in* labels, int32_t n_l
                                          const tpe_level_ws* ws, tpe_level_need* need, void* stream, tpe_result* out,
                                          const tpe_exchange* ex, int64_t P_expected, int32_t* all_status,
                                          int32_t* done);              // tpe_kernels.hip (hidden)
+extern "C" int tpe_internal_level_run_gen(const tpe_label_in* labels, int32_t n_labels, int32_t n_cand, uint64_t seed,
+                                          int64_t cand_base, int64_t n_cand_global, int32_t precision, int32_t flags,
+                                          const tpe_level_ws* ws, tpe_level_need* need, void* stream, tpe_result* out,
+                                          const uint64_t* gens, void (*after_launch)(void*),
+                                          void* ctx);                 // tpe_kernels.hip (hidden)
+extern "C" int tpe_internal_resident_on(void);                        // tpe_kernels.hip (hidden)
+extern "C" void tpe_internal_resident_count(int which, int64_t n);    // tpe_kernels.hip (hidden): 2 = fit reuses
 
 namespace {
 
@@ -85,6 +93,15 @@ struct Fit {
   const double* sg[2] = {nullptr, nullptr};
 };
 
+// fit reuse (include/tpe_hip.h "Resident levels"): per label slot a content key
+// of everything its fit and its packed sections read, and a generation that
+// changes whenever the key does.  kstate: what this call found for a label.
+// (kKeyNone: not keyed; kKeyMatched: the slot's key, its fit kept; kKeyPending:
+// fitted anew, key to copy; kKeyKept: keyed and accounted for)
+enum : uint8_t { kKeyNone = 0, kKeyMatched = 1, kKeyPending = 2, kKeyKept = 5 };
+std::atomic<int64_t> g_key_bytes{0};      // key copies of every thread (tpe_keystore::kCapBytes bounds them)
+std::atomic<uint64_t> g_next_gen{1};      // generations are unique in the process
+
 struct Tree {
   const tpe_tree_label* L;
   int32_t n;
@@ -97,7 +114,59 @@ struct Tree {
   std::vector<char> gate;       // label gates another label
   int32_t max_depth;
   int8_t* need_fit;             // labels the caller must fit (TPE_E_FALLBACK)
+  tpe_keystore::Store* keys;    // null: fit reuse off
+  uint8_t* kstate;              // per label (each label is one thread's at a time)
 };
+
+// the scalars of a label's key: its record's, and the call's fit parameters
+struct KeyHead {
+  int32_t family, flags, upper, lf;
+  double low, high, q, prior_mu, prior_sigma, prior_weight;
+  int64_t n_obs, side_n[2], host_k[2], device_fit_min, n_below;
+};
+constexpr int kKeySegs = 14;
+
+// label i's key as pieces (head: caller storage); false: the label is never
+// keyed — another rank's, device-fitted, or a record the fit will refuse
+bool label_key(const Tree& T, int i, KeyHead& h, tpe_keystore::Seg* sg, int& n_sg) {
+  const tpe_tree_label& L = T.L[i];
+  const int64_t n = L.n_obs;
+  if ((L.flags & TPE_F_REMOTE) || n < 0 || (n > 0 && (!L.tids || !L.values)) || T.n_below < 0) return false;
+  const bool cat = L.family == TPE_FAM_CATEGORICAL;
+  const bool host = L.host_k[0] > 0;
+  if (host && (L.host_k[1] <= 0 || !L.host_w[0] || !L.host_w[1] ||
+               (!cat && (!L.host_mu[0] || !L.host_mu[1] || !L.host_sigma[0] || !L.host_sigma[1]))))
+    return false;
+  const bool sided = !host && !cat && (L.side_order[0] || L.side_order[1]);
+  if (sided && (!L.side_order[0] || !L.side_order[1] || L.side_n[0] < 0 || L.side_n[1] < 0)) return false;
+  if (cat && L.upper <= 0) return false;
+  // (a continuous label large enough for the device fit: its order lives on the device)
+  if (!host && !sided && (L.family == TPE_FAM_GAUSS || L.family == TPE_FAM_LOGGAUSS) && T.device_fit_min > 0 &&
+      n >= std::max<int64_t>(T.device_fit_min, 64))
+    return false;
+  memset(&h, 0, sizeof(h));
+  // (TPE_F_PREFIT is the caller's scheduling hint: no fit and no pack reads it)
+  h.family = L.family; h.flags = L.flags & ~TPE_F_PREFIT; h.upper = L.upper; h.lf = T.lf;
+  h.low = L.low; h.high = L.high; h.q = L.q; h.prior_mu = L.prior_mu; h.prior_sigma = L.prior_sigma;
+  h.prior_weight = T.prior_weight;
+  h.n_obs = n; h.device_fit_min = T.device_fit_min; h.n_below = T.n_below;
+  for (int sd = 0; sd < 2; ++sd) { h.side_n[sd] = sided ? L.side_n[sd] : 0; h.host_k[sd] = host ? L.host_k[sd] : 0; }
+  int k = 0;
+  auto put = [&](const void* p, int64_t bytes) { sg[k++] = tpe_keystore::Seg{p, p && bytes > 0 ? (size_t)bytes : 0}; };
+  put(&h, (int64_t)sizeof(h));
+  put(T.below, T.n_below * 8);
+  put(L.tids, n * 8);
+  put(L.values, n * 8);
+  put(cat ? L.p_prior : nullptr, (int64_t)L.upper * 8);
+  for (int sd = 0; sd < 2; ++sd) {
+    put(host ? L.host_w[sd] : nullptr, L.host_k[sd] * 8);
+    put(host && !cat ? L.host_mu[sd] : nullptr, L.host_k[sd] * 8);
+    put(host && !cat ? L.host_sigma[sd] : nullptr, L.host_k[sd] * 8);
+    put(sided ? L.side_order[sd] : nullptr, L.side_n[sd] * 8);
+  }
+  n_sg = k;
+  return true;
+}
 
 // each below tid's position among a label's ascending tids (ap_filter_trials,
 // tpe.py:629-636), in the below set's (ascending) order.  Tids one apart from
@@ -124,9 +193,94 @@ inline void below_positions(const int64_t* tids, int64_t n, const int64_t* below
 // spec: a speculative fit on a pool worker (prefit): labels the caller must
 // fit are left alone (no need_fit flag), and a failure only leaves the fit
 // undone — the label's real fit, on the calling thread, reports it
+int fit_label_new(Tree& T, int i, bool spec);
 int fit_label(Tree& T, int i, bool spec = false) {
   Fit& f = (*T.fits)[(size_t)i];
   if (f.done) return TPE_OK;
+  const tpe_tree_label& L = T.L[i];
+  if (T.keys) {
+    // the same key as the slot's last fit: the fit stands, and so does its
+    // generation (a caller-made fit still takes the caller's arrays below:
+    // equal content, this call's addresses)
+    KeyHead h;
+    tpe_keystore::Seg sg[kKeySegs];
+    int n_sg = 0;
+    T.kstate[i] = kKeyNone;
+    if (label_key(T, i, h, sg, n_sg)) {
+      if (T.keys->match((size_t)i, sg, n_sg)) {
+        T.kstate[i] = kKeyMatched;
+        if (L.host_k[0] <= 0) {
+          f.done = true;
+          return TPE_OK;
+        }
+      } else {
+        T.keys->invalidate((size_t)i);          // (before the fit's buffers are rewritten)
+        T.kstate[i] = kKeyPending;
+      }
+    } else {
+      T.keys->invalidate((size_t)i);
+    }
+    if (T.kstate[i] != kKeyMatched) f.dev = false;
+  }
+  const int rc = fit_label_new(T, i, spec);
+  if (T.keys && T.kstate[i] != kKeyNone) {
+    if (rc != TPE_OK) {                                        // no fit: nothing to key
+      T.keys->invalidate((size_t)i);
+      T.kstate[i] = kKeyNone;
+    } else if (T.kstate[i] == kKeyPending) {
+      T.keys->set_gen((size_t)i, g_next_gen.fetch_add(1, std::memory_order_relaxed));
+    }
+  }
+  return rc;
+}
+
+// label i's generation for a level run: 0 unless its fit is keyed
+uint64_t label_gen(const Tree& T, int i) {
+  return T.keys && T.kstate[i] != kKeyNone && !(*T.fits)[(size_t)i].dev ? T.keys->gen((size_t)i) : 0;
+}
+
+// The keys of the labels fitted anew, copied on the pool — called after a
+// level's last launch, before its stream synchronise, when the host would only
+// wait (and once more after the run, for what a failed run left).  A copy
+// past the process-wide cap leaves this call without keys at all.
+struct KeyFlush {
+  Tree* T;
+  std::vector<int> ix;
+  std::atomic<int> over{0};
+};
+void key_flush_one(void* c, int k) {
+  KeyFlush* q = (KeyFlush*)c;
+  Tree& T = *q->T;
+  const int i = q->ix[(size_t)k];
+  KeyHead h;
+  tpe_keystore::Seg sg[kKeySegs];
+  int n_sg = 0;
+  if (!label_key(T, i, h, sg, n_sg) || !T.keys->store((size_t)i, sg, n_sg)) q->over.store(1, std::memory_order_relaxed);
+}
+void key_flush(void* c) {
+  KeyFlush* q = (KeyFlush*)c;
+  Tree& T = *q->T;
+  if (!T.keys) return;
+  q->ix.clear();
+  int reused = 0;
+  for (int i = 0; i < T.n; ++i) {
+    if (T.kstate[i] == kKeyPending && (*T.fits)[(size_t)i].done) q->ix.push_back(i);
+    else if (T.kstate[i] == kKeyMatched) ++reused, T.kstate[i] = kKeyKept;   // (counted once)
+  }
+  if (reused) tpe_internal_resident_count(2, reused);
+  if (q->ix.empty()) return;
+  tpe_pool::parallel_for((int)q->ix.size(), key_flush_one, q);
+  for (int i : q->ix) T.kstate[i] = kKeyKept;                 // (keyed now; not a reuse)
+  if (q->over.load(std::memory_order_relaxed)) {
+    T.keys->clear();
+    for (int i = 0; i < T.n; ++i) T.kstate[i] = kKeyNone;
+    q->over.store(0, std::memory_order_relaxed);
+  }
+}
+
+// the fit itself (fit_label: after the key compare)
+int fit_label_new(Tree& T, int i, bool spec) {
+  Fit& f = (*T.fits)[(size_t)i];
   const tpe_tree_label& L = T.L[i];
   const int64_t n = L.n_obs;
   if (L.host_k[0] > 0) {                      // the caller's fit
@@ -436,10 +590,26 @@ static int suggest_tree(const tpe_tree_label* labels, int32_t n_labels, const in
   static thread_local std::vector<tpe_result> res_tl;
   static thread_local std::vector<int64_t> ids_tl;
   static thread_local std::vector<int> chosen_tl, pred_tl;
+  static thread_local tpe_keystore::Store keys_tl(&g_key_bytes, tpe_keystore::kCapBytes);
+  static thread_local std::vector<uint8_t> kstate_tl;
+  static thread_local std::vector<uint64_t> gens_tl;
   std::vector<Fit>& fits = fits_tl;
   if (fits.size() < (size_t)n_labels) fits.resize((size_t)n_labels);
   for (int i = 0; i < n_labels; ++i) fits[(size_t)i].done = false;
-  Tree T{labels, n_labels, below_tids, n_below, prior_weight, lf, device_fit_min, &fits, {}, 0, need_fit};
+  // fit reuse: on unless switched off (tpe_level_resident, TPE_RESIDENT_LEVEL=0)
+  const bool keyed = tpe_internal_resident_on() != 0;
+  if (keyed) keys_tl.reserve_slots((size_t)n_labels);
+  else if (keys_tl.n_slots()) keys_tl.clear();
+  kstate_tl.assign((size_t)std::max(n_labels, 1), kKeyNone);
+  Tree T{labels, n_labels, below_tids, n_below, prior_weight, lf, device_fit_min, &fits, {}, 0, need_fit,
+         keyed ? &keys_tl : nullptr, kstate_tl.data()};
+  static thread_local KeyFlush flush_tl;
+  KeyFlush& flush = flush_tl;
+  flush.T = &T;
+  struct FlushAtExit {                 // (every return: what was fitted keeps its key)
+    KeyFlush& f;
+    ~FlushAtExit() { key_flush(&f); f.T = nullptr; }
+  } flush_at_exit{flush};
   T.gate.assign((size_t)n_labels, 0);
   for (int i = 0; i < n_labels; ++i) {
     const tpe_tree_label& L = labels[i];
@@ -503,8 +673,10 @@ static int suggest_tree(const tpe_tree_label* labels, int32_t n_labels, const in
                                                run_flags, ws, need, stream, res.data(), ex, P, &all_rc, &done);
       return done ? gathered(rc, all_rc) : exchange_host(rc);
     }
-    const int rc = tpe_level_run(recs.data(), n_recs, n_cand, seed, cand_base, n_cand_global, TPE_PREC_F32, run_flags,
-                                 ws, need, stream, res.data());
+    // (with the labels' generations, unless the ranks exchange: such a level is never resident)
+    const int rc = tpe_internal_level_run_gen(recs.data(), n_recs, n_cand, seed, cand_base, n_cand_global, TPE_PREC_F32,
+                                              run_flags, ws, need, stream, res.data(),
+                                              keyed && !exchange ? gens_tl.data() : nullptr, key_flush, &flush);
     return exchange ? exchange_host(rc) : rc;
   };
 
@@ -517,6 +689,7 @@ static int suggest_tree(const tpe_tree_label* labels, int32_t n_labels, const in
     if (rc != TPE_OK) return rc;
     if (ok) {
       recs.resize((size_t)n_labels);
+      gens_tl.resize((size_t)n_labels);
       int32_t nr = 0;
       bool pending = false;                 // labels flagged for the caller's fit: all of them at once
       for (int i = 0; i < n_labels; ++i) {
@@ -525,6 +698,7 @@ static int suggest_tree(const tpe_tree_label* labels, int32_t n_labels, const in
           if (rc == TPE_E_FALLBACK && need_fit && need_fit[i]) { pending = true; continue; }
           return rc;
         }
+        gens_tl[(size_t)nr] = label_gen(T, i);
         label_rec(T, labels[i], fits[(size_t)i], ids, n_ids, recs[(size_t)nr++]);
       }
       if (pending) return TPE_E_FALLBACK;
@@ -686,8 +860,10 @@ static int suggest_tree(const tpe_tree_label* labels, int32_t n_labels, const in
     std::vector<int64_t> lvl_new((size_t)lvl_ids.size());
     for (size_t q = 0; q < lvl_ids.size(); ++q) lvl_new[q] = ids[lvl_ids[q]];
     recs.resize(members.size());
+    gens_tl.resize(members.size());
     for (size_t k = 0; k < members.size(); ++k) {
       const Member& m = members[k];
+      gens_tl[k] = label_gen(T, m.label);
       label_rec(T, labels[m.label], fits[(size_t)m.label], m.lvl_first < 0 ? ids : lvl_new.data() + m.lvl_first,
                 m.count, recs[k]);
     }

@@ -229,7 +229,13 @@ class Engine(object):
             t = torch.empty(cap, dtype=dtype, device=self.device)
             self._bufs[name] = t
             self._ws = None
+            self._drop_resident()
         return t
+
+    def _drop_resident(self):
+        """The engine replaced or wrote a pool itself: no level is resident
+        there any more (tpe_level_resident, mode 2)."""
+        self.lib.tpe_level_resident(2, None)
 
     # ------------------------------------------------------------- tables
     def _build_numpy(self, problems, n_cand, seed, cand_base, n_cand_global):
@@ -589,6 +595,7 @@ class Engine(object):
                 self._pinned = torch.empty(max(info.blob_bytes, 2 * cap), dtype=torch.uint8,
                                            pin_memory=torch.cuda.is_available())
                 self._ws = None
+                self._drop_resident()
                 continue
             N.check(rc, self.lib, 'tpe_host_pack_level')
             break
@@ -645,6 +652,7 @@ class Engine(object):
         if need.pinned_bytes > (self._pinned.numel() if self._pinned is not None else 0):
             self._pinned = torch.empty(int(need.pinned_bytes * 1.25) + 4096, dtype=torch.uint8,
                                        pin_memory=torch.cuda.is_available())
+            self._drop_resident()
         self._buf('blob', need.blob_bytes, torch.uint8)
         for name, dt in (('cand', torch.float64), ('coord', torch.float32), ('keys', torch.int32),
                          ('vals', torch.int64), ('keys_sorted', torch.int32), ('vals_sorted', torch.int64)):
@@ -822,6 +830,7 @@ class Engine(object):
         nbytes = int(info.blob_bytes)
         dev = self._buf('blob', nbytes, torch.uint8)
         # host-written ranges only: device-fitted rows are produced by tpe_fit_above
+        self._drop_resident()             # (the blob is rewritten here, outside a library call)
         for i in range(int(info.n_up)):
             o, n = int(info.up_off[i]), int(info.up_len[i])
             dev[o:o + n].copy_(self._pinned[o:o + n], non_blocking=True)

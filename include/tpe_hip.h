@@ -1506,6 +1506,32 @@ int tpe_joint_seg_run(const tpe_joint_seg_args* args, tpe_joint_record* records,
  * phase times of the last call (before this one changes the setting) */
 int tpe_host_phases(int32_t enable, double* last, int32_t n);
 
+/* ------------------------------------------------------------------------
+ * Resident levels.  Of a tpe_suggest_tree call only the Philox key (the seed)
+ * and the new ids reach the sample stage afresh; the fits, the packed level
+ * and its score tables are a function of the labels' finished trials, the
+ * below set, the candidate count and the fit parameters.  The library keeps,
+ * per calling thread, a content key of every label's fit (private copies of
+ * the scalars and arrays the fit reads: a matching label keeps its fit and its
+ * generation) and one record of the last level run (the labels' generations,
+ * the run's arguments, every field of its tpe_level_ws, the device, and the
+ * process-wide device epoch).  A level run with the same record skips the
+ * pack, the upload and the table stage: one small kernel patches key0 / key1 /
+ * ctr3 of the device problem rows and selects the lazy categoricals, then the
+ * stages run as ever.  Every exported entry that enqueues device work or packs
+ * into caller memory advances the epoch, so nothing else can have written
+ * under a record that is still alive.  tpe_level_run itself is never resident;
+ * levels with device fits, expanded levels, TPE_BATCH_WRITE_CAND levels and
+ * candidate-sharded levels are not either.
+ *
+ * mode 0: off, and drop every record; 1: on (the default); 2: drop only (a
+ * caller that rewrites the workspace's blob, tables or staging buffer itself);
+ * < 0: query.  stats (if not NULL) gets {hits, misses, fit_reuses, drops}
+ * since load.  Returns 1 when the feature is on, else 0.  The environment
+ * variable TPE_RESIDENT_LEVEL=0 (read once) keeps it off whatever the mode.
+ * ---------------------------------------------------------------------- */
+int tpe_level_resident(int32_t mode, int64_t* stats);
+
 #ifdef __cplusplus
 }
 #endif
