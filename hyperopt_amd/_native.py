@@ -224,6 +224,48 @@ class JointSegArgs(ctypes.Structure):
     ]
 
 
+JOINT_MSEG_MAX_CONT = 8        # TPE_JOINT_MSEG_MAX_CONT: continuous coordinates beside a discrete / quantised one
+JOINT_MSEG_MAX_CAT = 4         # TPE_JOINT_MSEG_MAX_CAT: discrete coordinates of a segment
+
+
+class JointMSeg(ctypes.Structure):
+    """tpe_joint_mseg: the device descriptor of one group of a tpe_joint_mseg_run (tpe_joint_seg's fields first)."""
+    _fields_ = JointSeg._fields_ + [
+        ('n_cat', ctypes.c_int32), ('n_quant', ctypes.c_int32),
+        ('cat_upper', ctypes.c_int32 * JOINT_MSEG_MAX_CAT), ('cat_off', ctypes.c_int32 * JOINT_MSEG_MAX_CAT),
+        ('quant_v', ctypes.c_int32 * JOINT_MAX_QUANT), ('quant_edge_off', ctypes.c_int32 * JOINT_MAX_QUANT),
+        ('qlo', ctypes.c_float * JOINT_MAX_QUANT), ('qhi', ctypes.c_float * JOINT_MAX_QUANT),
+        ('n_edges', ctypes.c_int32), ('reserved', ctypes.c_int32),
+        ('below_cat', ctypes.c_int64), ('above_cat', ctypes.c_int64),
+        ('below_miss', ctypes.c_int64), ('below_bonus', ctypes.c_int64),
+        ('above_miss', ctypes.c_int64), ('above_bonus', ctypes.c_int64),
+        ('quant_samp', ctypes.c_int64), ('below_h', ctypes.c_int64), ('cat_cum', ctypes.c_int64),
+        ('quant_edges', ctypes.c_int64),
+        ('below_qmu', ctypes.c_int64), ('below_qsigma', ctypes.c_int64),
+        ('above_qmu', ctypes.c_int64), ('above_qsigma', ctypes.c_int64),
+        ('table', ctypes.c_int64),
+    ]
+
+
+# numpy mirror of tpe_joint_mseg
+JOINT_MSEG_DTYPE = np.dtype(JOINT_SEG_DTYPE.descr + [
+    ('n_cat', '<i4'), ('n_quant', '<i4'),
+    ('cat_upper', '<i4', (JOINT_MSEG_MAX_CAT,)), ('cat_off', '<i4', (JOINT_MSEG_MAX_CAT,)),
+    ('quant_v', '<i4', (JOINT_MAX_QUANT,)), ('quant_edge_off', '<i4', (JOINT_MAX_QUANT,)),
+    ('qlo', '<f4', (JOINT_MAX_QUANT,)), ('qhi', '<f4', (JOINT_MAX_QUANT,)),
+    ('n_edges', '<i4'), ('reserved', '<i4'),
+    ('below_cat', '<i8'), ('above_cat', '<i8'), ('below_miss', '<i8'), ('below_bonus', '<i8'),
+    ('above_miss', '<i8'), ('above_bonus', '<i8'), ('quant_samp', '<i8'), ('below_h', '<i8'), ('cat_cum', '<i8'),
+    ('quant_edges', '<i8'), ('below_qmu', '<i8'), ('below_qsigma', '<i8'), ('above_qmu', '<i8'),
+    ('above_qsigma', '<i8'), ('table', '<i8')])
+assert JOINT_MSEG_DTYPE.itemsize == ctypes.sizeof(JointMSeg) == 464
+
+
+class JointMSegArgs(ctypes.Structure):
+    """tpe_joint_mseg_args: one tpe_joint_mseg_run (tpe_joint_seg_args' fields, then the table workspace)."""
+    _fields_ = JointSegArgs._fields_ + [('quant_table', ctypes.c_void_p), ('quant_table_bytes', ctypes.c_uint64)]
+
+
 class JointReportArgs(ctypes.Structure):
     """tpe_joint_report_args: one tpe_joint_report."""
     _fields_ = [
@@ -379,7 +421,8 @@ EXPORTS = ('tpe_abi_version', 'tpe_last_error', 'tpe_device_count', 'tpe_tile_si
            'tpe_report_profile', 'tpe_joint_scratch_bytes', 'tpe_joint_run', 'tpe_joint_profile',
            'tpe_joint_mixed_run', 'tpe_joint_quant_table_bytes', 'tpe_joint_quant_run', 'tpe_joint_quant_profile',
            'tpe_joint_wide_scratch_bytes', 'tpe_joint_wide_run', 'tpe_joint_wide_profile',
-           'tpe_joint_seg_scratch_bytes', 'tpe_joint_seg_run', 'tpe_joint_report_scratch_bytes',
+           'tpe_joint_seg_scratch_bytes', 'tpe_joint_seg_run', 'tpe_joint_mseg_scratch_bytes',
+           'tpe_joint_mseg_table_bytes', 'tpe_joint_mseg_run', 'tpe_joint_report_scratch_bytes',
            'tpe_joint_report', 'tpe_joint_report_profile')
 
 # host phases of tpe_suggest_tree (tpe_host_phases order)
@@ -515,6 +558,12 @@ def load(path=LIB_PATH):
     lib.tpe_joint_seg_scratch_bytes.restype = ctypes.c_int
     lib.tpe_joint_seg_run.argtypes = [ctypes.POINTER(JointSegArgs), P, P, P, P, P, ctypes.c_uint64, P]
     lib.tpe_joint_seg_run.restype = ctypes.c_int
+    lib.tpe_joint_mseg_scratch_bytes.argtypes = [I32, I32, ctypes.POINTER(ctypes.c_uint64)]
+    lib.tpe_joint_mseg_scratch_bytes.restype = ctypes.c_int
+    lib.tpe_joint_mseg_table_bytes.argtypes = [P, I32, ctypes.POINTER(ctypes.c_uint64)]
+    lib.tpe_joint_mseg_table_bytes.restype = ctypes.c_int
+    lib.tpe_joint_mseg_run.argtypes = [ctypes.POINTER(JointMSegArgs), P, P, P, P, P, ctypes.c_uint64, P]
+    lib.tpe_joint_mseg_run.restype = ctypes.c_int
     lib.tpe_joint_report_scratch_bytes.argtypes = [I32, I32, I32, ctypes.POINTER(ctypes.c_uint64)]
     lib.tpe_joint_report_scratch_bytes.restype = ctypes.c_int
     lib.tpe_joint_report.argtypes = [ctypes.POINTER(JointReportArgs), I32, P, P, P, P, P, ctypes.c_uint64, P]

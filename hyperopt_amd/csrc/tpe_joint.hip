@@ -26,6 +26,12 @@
 //                problems of many groups at once ("segmented stage" below): a
 //                workgroup reads its problem's group descriptor, then runs the
 //                same device code; k_joint_merge serves it unchanged.
+// k_joint_mseg_qtable / k_joint_mseg_mixed_chunk / k_joint_mseg_quant_chunk  the
+//                segmented stage for groups that also hold discrete and
+//                quantised labels ("Mixed segmented joint stage"): one table
+//                launch for all segments, then the mixed / quantised chunk
+//                bodies (mixed_chunk_body, quant_chunk_body, shared with the
+//                solo kernels) behind a descriptor read.
 // k_joint_wide_sample / k_joint_wide_chunk / k_joint_wide_merge  the continuous
 //                stage for 17 to 64 coordinates ("wide groups" below): the
 //                candidates are drawn by a kernel of their own into scratch.
@@ -288,7 +294,7 @@ struct SegK {
   int C, n_chunks, inject, first;   // first: this launch's first entry of `order`
   int n_probs, n_segs;
   uint32_t key0, key1;
-  const tpe_joint_seg* segs;
+  const tpe_joint_seg* segs;        // (MIXED kernels: the tpe_joint_mseg array behind this pointer)
   const float* pool;
   const double* pool64;
   const int32_t* prob_seg;
@@ -305,18 +311,51 @@ __host__ __device__ __forceinline__ int dp_class(int D) {
   return D <= 4 ? D - 1 : D <= 6 ? 4 : D <= 8 ? 5 : D <= 12 ? 6 : 7;
 }
 
-// order[rank of p] = p, the rank by (DP class, group, problem index): one thread
-// a problem counts the problems before it.  No atomics; P^2 / 256 reads a
+// The kernel instantiation of a segment with Dc continuous, Dk discrete and Dq
+// quantised coordinates as an index 0 .. kMClasses - 1: the continuous DP
+// classes first (dp_class), then the 12 (CP, KP) shapes of the mixed kernel,
+// then the 48 (CP, KP, QP) shapes of the quantised one.
+constexpr int kMClasses = 8 + 12 + 48;
+__host__ __device__ __forceinline__ int cp_index(int Dc) { return Dc == 0 ? 0 : Dc <= 2 ? 1 : Dc <= 4 ? 2 : 3; }
+__host__ __device__ __forceinline__ int mseg_class(int Dc, int Dk, int Dq) {
+  if (Dq > 0) return 20 + (cp_index(Dc) * 4 + (Dk <= 2 ? Dk : 3)) * 3 + (Dq <= 2 ? Dq - 1 : 2);
+  if (Dk > 0) return 8 + cp_index(Dc) * 3 + (Dk <= 2 ? Dk - 1 : 2);
+  return dp_class(Dc);
+}
+
+// Segment s of a launch.  MIXED: the descriptors are tpe_joint_mseg (the launches
+// of tpe_joint_mseg_run), and this is the tpe_joint_seg at the head of one.
+__device__ __forceinline__ const tpe_joint_mseg* mseg_at(const SegK& p, int s) {
+  return reinterpret_cast<const tpe_joint_mseg*>(p.segs) + s;
+}
+template <bool MIXED>
+__device__ __forceinline__ const tpe_joint_seg* seg_at(const SegK& p, int s) {
+  if constexpr (MIXED) return reinterpret_cast<const tpe_joint_seg*>(mseg_at(p, s));
+  else return p.segs + s;
+}
+template <bool MIXED>
+__device__ __forceinline__ int seg_class(const SegK& p, int s) {
+  if constexpr (MIXED) {
+    const tpe_joint_mseg* m = mseg_at(p, s);
+    return mseg_class(m->n_dims, m->n_cat, m->n_quant);
+  } else {
+    return dp_class(p.segs[s].n_dims);
+  }
+}
+
+// order[rank of p] = p, the rank by (kernel class, group, problem index): one
+// thread a problem counts the problems before it.  No atomics; P^2 / 256 reads a
 // workgroup from arrays that sit in L2.
+template <bool MIXED>
 __global__ __launch_bounds__(kThreads) void k_joint_seg_order(const SegK p) {
   const int me = blockIdx.x * kThreads + threadIdx.x;
   if (me >= p.n_probs) return;
   const int sme = p.prob_seg[me];
-  const int kme = dp_class(p.segs[sme].n_dims) * p.n_segs + sme;
+  const int kme = seg_class<MIXED>(p, sme) * p.n_segs + sme;
   int rank = 0;
   for (int q = 0; q < p.n_probs; ++q) {
     const int sq = p.prob_seg[q];
-    const int kq = dp_class(p.segs[sq].n_dims) * p.n_segs + sq;
+    const int kq = seg_class<MIXED>(p, sq) * p.n_segs + sq;
     rank += (kq < kme || (kq == kme && q < me)) ? 1 : 0;
   }
   p.order[rank] = me;
@@ -329,7 +368,7 @@ __device__ __forceinline__ int64_t uni(int64_t v) {
 __device__ __forceinline__ float unif(float v) { return __int_as_float(uni(__float_as_int(v))); }
 __device__ __forceinline__ double unid(double v) { return __longlong_as_double(uni((int64_t)__double_as_longlong(v))); }
 
-template <int DP>
+template <int DP, bool MIXED>
 __global__ __launch_bounds__(kThreads) void k_joint_seg_chunk(const SegK p) {
   __shared__ __attribute__((aligned(16))) float rows[kTileK * 2 * DP];
   __shared__ float cl[kTileK];
@@ -337,7 +376,7 @@ __global__ __launch_bounds__(kThreads) void k_joint_seg_chunk(const SegK p) {
   const int chunk = blockIdx.x % p.n_chunks;
   // the problem and its group: the same for every lane, kept in scalar registers
   const int prob = uni(p.order[p.first + blockIdx.x / p.n_chunks]);
-  const tpe_joint_seg* __restrict__ sg = p.segs + uni(p.prob_seg[prob]);
+  const tpe_joint_seg* __restrict__ sg = seg_at<MIXED>(p, uni(p.prob_seg[prob]));
 
   ChunkIO q;
   q.D = uni(sg->n_dims); q.C = p.C; q.inject = p.inject;
@@ -406,17 +445,17 @@ template <int CP, int KP>
 __device__ __forceinline__ void score_side_mixed(const float* __restrict__ mu, const float* __restrict__ a,
                                                  const float* __restrict__ c, const float* __restrict__ cat,
                                                  const float* __restrict__ miss, const float* __restrict__ bonus,
-                                                 int K, const MixedK& p, const float (&z)[kR][CP + KP],
-                                                 float* __restrict__ rows, float* __restrict__ cl, double (&out)[kR]) {
+                                                 int K, int Dc, int Dk, const int (&U)[KP], const int (&off)[KP],
+                                                 const float (&z)[kR][CP + KP], float* __restrict__ rows,
+                                                 float* __restrict__ cl, double (&out)[kR]) {
   constexpr int S = 2 * CP + KP;
-  const int Dc = p.j.D, Dk = p.Dk;
   float m[kR], s[kR], nb[kR][KP];
 #pragma unroll
   for (int r = 0; r < kR; ++r) {
     m[r] = -3.0e38f;
     s[r] = 0.f;
 #pragma unroll
-    for (int d = 0; d < KP; ++d) nb[r][d] = d < Dk ? -bonus[p.off[d] + cat_index(z[r][CP + d], p.U[d])] : 0.f;
+    for (int d = 0; d < KP; ++d) nb[r][d] = d < Dk ? -bonus[off[d] + cat_index(z[r][CP + d], U[d])] : 0.f;
   }
   for (int k0 = 0; k0 < K; k0 += kTileK) {
     const int nk = min(kTileK, K - k0);
@@ -466,27 +505,36 @@ __device__ __forceinline__ void score_side_mixed(const float* __restrict__ mu, c
     double M = 0.0;
 #pragma unroll
     for (int d = 0; d < KP; ++d)
-      if (d < Dk) M += (double)miss[p.off[d] + cat_index(z[r][CP + d], p.U[d])];
+      if (d < Dk) M += (double)miss[off[d] + cat_index(z[r][CP + d], U[d])];
     out[r] = (double)m[r] + log2((double)s[r]) + M;
   }
 }
 
-// k_joint_chunk for a mixed group: CP / KP the padded continuous / discrete
+// What one workgroup of k_joint_mixed_chunk / k_joint_mseg_mixed_chunk works on:
+// ChunkIO (q.D = Dc; cand / inject rows are [Dc + Dk]) and the discrete part of
+// ONE (id, group) problem.  Every field is wave-uniform; the arrays are only
+// ever indexed by constants (they stay in scalar registers).
+template <int CP, int KP>
+struct MixedIO {
+  ChunkIO q;
+  int Dk;
+  float lo[CP > 0 ? CP : 1], hi[CP > 0 ? CP : 1];
+  int U[KP], off[KP];
+  const float *bcat, *acat;
+  const float *bmiss, *bbonus, *amiss, *abonus;
+  const double* bh;
+  const double* ccum;
+};
+
+// joint_chunk_body for a mixed group: CP / KP the padded continuous / discrete
 // counts (CP = 0: an all-discrete group).  z[r] holds the continuous
 // coordinates at [0, CP) and the categories at [CP, CP + KP).
-// (From 12 padded coordinates on the register allocator is told not to aim above
-// 2 waves a SIMD: left alone it spills a few dwords to hold 3.)
 template <int CP, int KP>
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, (CP + KP >= 12 ? 2 : 8))))
-void k_joint_mixed_chunk(const MixedK p) {
+__device__ __forceinline__ void mixed_chunk_body(const MixedIO<CP, KP>& p, int first, float* __restrict__ rows,
+                                                 float* __restrict__ cl, Pick* __restrict__ slot) {
   constexpr int ZP = CP + KP;
-  __shared__ __attribute__((aligned(16))) float rows[kTileK * (2 * CP + KP)];
-  __shared__ float cl[kTileK];
-  __shared__ Pick slot[kThreads / 64];
-  const JointK& q = p.j;
+  const ChunkIO& q = p.q;
   const int t = threadIdx.x, Dc = q.D, Dk = p.Dk, D = Dc + Dk;
-  const int id = blockIdx.x / q.n_chunks, chunk = blockIdx.x % q.n_chunks;
-  const int first = chunk * TPE_JOINT_CHUNK;
 
   float z[kR][ZP];
 #pragma unroll
@@ -504,7 +552,7 @@ void k_joint_mixed_chunk(const MixedK p) {
         if (d < Dk) z[r][CP + d] = q.inj[(int64_t)i * D + Dc + d];
       continue;
     }
-    const uint32_t c3 = (uint32_t)q.ids[id];
+    const uint32_t c3 = q.c3;
     U4 w = philox4x32_10((uint32_t)i, 0u, q.stream_word, c3, q.key0, q.key1);
     const double us = u01w(w.x);
     int lo = 0, hi = q.kb - 1;             // first k with us < cum[k]
@@ -526,10 +574,10 @@ void k_joint_mixed_chunk(const MixedK p) {
         if (sr[4] != 0.f) zz = -zz;
         x = sr[0] + sr[1] * zz;
         if (!(x == x)) x = sr[0];
-        float blo = 0.f, bhi = 0.f;                       // (kernel-argument arrays: constant indices only)
+        float blo = 0.f, bhi = 0.f;                       // (the bound arrays: constant indices only)
 #pragma unroll
         for (int f = 0; f < CP; ++f)
-          if (f == j) { blo = q.lo[f]; bhi = q.hi[f]; }
+          if (f == j) { blo = p.lo[f]; bhi = p.hi[f]; }
         x = fminf(fmaxf(x, blo), bhi);                    // low <= z < high
       } else {
         const int d = j - Dc;
@@ -556,8 +604,8 @@ void k_joint_mixed_chunk(const MixedK p) {
   }
 
   double l2[kR], g2[kR];
-  score_side_mixed<CP, KP>(q.bmu, q.ba, q.bc, p.bcat, p.bmiss, p.bbonus, q.kb, p, z, rows, cl, l2);
-  score_side_mixed<CP, KP>(q.amu, q.aa, q.ac, p.acat, p.amiss, p.abonus, q.ka, p, z, rows, cl, g2);
+  score_side_mixed<CP, KP>(q.bmu, q.ba, q.bc, p.bcat, p.bmiss, p.bbonus, q.kb, Dc, Dk, p.U, p.off, z, rows, cl, l2);
+  score_side_mixed<CP, KP>(q.amu, q.aa, q.ac, p.acat, p.amiss, p.abonus, q.ka, Dc, Dk, p.U, p.off, z, rows, cl, g2);
 
   Pick best{0, 0};
   double lv[kR], gv[kR];
@@ -567,16 +615,15 @@ void k_joint_mixed_chunk(const MixedK p) {
     lv[r] = l2[r] * kLn2 + q.bbase;
     gv[r] = g2[r] * kLn2 + q.abase;
     if (i >= q.C) continue;
-    const int64_t o = (int64_t)id * q.C + i;
-    if (q.l_out) q.l_out[o] = lv[r];
-    if (q.g_out) q.g_out[o] = gv[r];
+    if (q.l_out) q.l_out[i] = lv[r];
+    if (q.g_out) q.g_out[i] = gv[r];
     if (q.cand) {
 #pragma unroll
       for (int d = 0; d < CP; ++d)
-        if (d < Dc) q.cand[o * D + d] = z[r][d];
+        if (d < Dc) q.cand[(int64_t)i * D + d] = z[r][d];
 #pragma unroll
       for (int d = 0; d < KP; ++d)
-        if (d < Dk) q.cand[o * D + Dc + d] = z[r][CP + d];
+        if (d < Dk) q.cand[(int64_t)i * D + Dc + d] = z[r][CP + d];
     }
     const uint64_t key = score_key(lv[r] - gv[r]);
     if (key > best.key) best = Pick{key, (int64_t)i};   // ascending index: strict > keeps the first of a tie
@@ -589,7 +636,7 @@ void k_joint_mixed_chunk(const MixedK p) {
   for (int s = 1; s < kThreads / 64; ++s)
     if (beats(slot[s], w)) w = slot[s];
 
-  tpe_joint_record* rec = q.chunk_rec + blockIdx.x;
+  tpe_joint_record* rec = q.rec;
   if (w.key == 0) {
     if (t == 0) rec->global_idx = -1;
     return;
@@ -616,6 +663,100 @@ void k_joint_mixed_chunk(const MixedK p) {
   }
 }
 
+// ChunkIO of workgroup blockIdx.x of a solo launch (JointK: k_joint_chunk's
+// arguments) over a group of D coordinates in all
+__device__ __forceinline__ void solo_chunk_io(ChunkIO& q, const JointK& p, int D) {
+  const int id = blockIdx.x / p.n_chunks;
+  q.D = p.D; q.C = p.C; q.inject = p.inject;
+  q.kb = p.kb; q.ka = p.ka;
+  q.key0 = p.key0; q.key1 = p.key1; q.stream_word = p.stream_word;
+  q.c3 = p.inject ? 0u : (uint32_t)p.ids[id];
+  q.bmu = p.bmu; q.ba = p.ba; q.bc = p.bc; q.amu = p.amu; q.aa = p.aa; q.ac = p.ac;
+  q.bbase = p.bbase; q.abase = p.abase;
+  q.cum = p.cum; q.samp = p.samp; q.inj = p.inj;
+  const int64_t o = (int64_t)id * p.C;
+  q.cand = p.cand ? p.cand + o * D : nullptr;
+  q.l_out = p.l_out ? p.l_out + o : nullptr;
+  q.g_out = p.g_out ? p.g_out + o : nullptr;
+  q.rec = p.chunk_rec + blockIdx.x;
+}
+
+// (From 12 padded coordinates on the register allocator is told not to aim above
+// 2 waves a SIMD: left alone it spills a few dwords to hold 3.)
+template <int CP, int KP>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, (CP + KP >= 12 ? 2 : 8))))
+void k_joint_mixed_chunk(const MixedK p) {
+  __shared__ __attribute__((aligned(16))) float rows[kTileK * (2 * CP + KP)];
+  __shared__ float cl[kTileK];
+  __shared__ Pick slot[kThreads / 64];
+  MixedIO<CP, KP> io;
+  solo_chunk_io(io.q, p.j, p.j.D + p.Dk);
+  io.Dk = p.Dk;
+#pragma unroll
+  for (int d = 0; d < CP; ++d) { io.lo[d] = p.j.lo[d]; io.hi[d] = p.j.hi[d]; }   // (kernel-argument arrays: constant indices only)
+#pragma unroll
+  for (int d = 0; d < KP; ++d) { io.U[d] = p.U[d]; io.off[d] = p.off[d]; }
+  io.bcat = p.bcat; io.acat = p.acat;
+  io.bmiss = p.bmiss; io.bbonus = p.bbonus; io.amiss = p.amiss; io.abonus = p.abonus;
+  io.bh = p.bh; io.ccum = p.ccum;
+  mixed_chunk_body<CP, KP>(io, (int)(blockIdx.x % p.j.n_chunks) * TPE_JOINT_CHUNK, rows, cl, slot);
+}
+
+// The segmented launch of the same body: the problem's descriptor (a
+// tpe_joint_mseg) read into scalar registers, as k_joint_seg_chunk does.
+struct MSegK {
+  SegK s;                           // s.segs: the tpe_joint_mseg array
+  float* table;                     // the table workspace
+};
+
+__device__ __forceinline__ void mseg_chunk_io(ChunkIO& q, const SegK& p, const tpe_joint_mseg* __restrict__ sg, int prob,
+                                              int chunk) {
+  q.D = uni(sg->n_dims); q.C = p.C; q.inject = p.inject;
+  q.kb = uni(sg->k_below); q.ka = uni(sg->k_above);
+  q.key0 = p.key0; q.key1 = p.key1; q.stream_word = (uint32_t)uni((int)sg->stream_word);
+  q.c3 = (uint32_t)uni((int)(uint32_t)p.prob_id[prob]);
+  q.bmu = p.pool + uni(sg->below_mu); q.ba = p.pool + uni(sg->below_a); q.bc = p.pool + uni(sg->below_c);
+  q.amu = p.pool + uni(sg->above_mu); q.aa = p.pool + uni(sg->above_a); q.ac = p.pool + uni(sg->above_c);
+  q.bbase = unid(sg->below_base); q.abase = unid(sg->above_base);
+  q.cum = p.inject ? nullptr : p.pool64 + uni(sg->samp_cum);
+  q.samp = p.inject ? nullptr : p.pool + uni(sg->samp);
+  q.inj = p.inject ? p.pool + uni(sg->inject) : nullptr;
+  q.cand = p.cand ? p.cand + uni(p.cand_off[prob]) : nullptr;
+  q.l_out = p.l_out ? p.l_out + (int64_t)prob * p.C : nullptr;
+  q.g_out = p.g_out ? p.g_out + (int64_t)prob * p.C : nullptr;
+  q.rec = p.chunk_rec + (int64_t)prob * p.n_chunks + chunk;
+}
+
+template <int CP, int KP>
+__device__ __forceinline__ void mseg_mixed_io(MixedIO<CP, KP>& io, const SegK& p, const tpe_joint_mseg* __restrict__ sg) {
+  io.Dk = uni(sg->n_cat);
+#pragma unroll
+  for (int d = 0; d < CP; ++d) { io.lo[d] = unif(sg->lo[d]); io.hi[d] = unif(sg->hi[d]); }
+#pragma unroll
+  for (int d = 0; d < KP; ++d) { io.U[d] = uni(sg->cat_upper[d]); io.off[d] = uni(sg->cat_off[d]); }
+  io.bcat = p.pool + uni(sg->below_cat); io.acat = p.pool + uni(sg->above_cat);
+  io.bmiss = p.pool + uni(sg->below_miss); io.bbonus = p.pool + uni(sg->below_bonus);
+  io.amiss = p.pool + uni(sg->above_miss); io.abonus = p.pool + uni(sg->above_bonus);
+  io.bh = p.inject ? nullptr : p.pool64 + uni(sg->below_h);
+  io.ccum = p.inject ? nullptr : p.pool64 + uni(sg->cat_cum);
+}
+
+template <int CP, int KP>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, (CP + KP >= 12 ? 2 : 8))))
+void k_joint_mseg_mixed_chunk(const MSegK p) {
+  static_assert(KP <= TPE_JOINT_MSEG_MAX_CAT && CP <= TPE_JOINT_MSEG_MAX_CONT, "the descriptor's arrays");
+  __shared__ __attribute__((aligned(16))) float rows[kTileK * (2 * CP + KP)];
+  __shared__ float cl[kTileK];
+  __shared__ Pick slot[kThreads / 64];
+  const int chunk = blockIdx.x % p.s.n_chunks;
+  const int prob = uni(p.s.order[p.s.first + blockIdx.x / p.s.n_chunks]);
+  const tpe_joint_mseg* __restrict__ sg = mseg_at(p.s, uni(p.s.prob_seg[prob]));
+  MixedIO<CP, KP> io;
+  mseg_chunk_io(io.q, p.s, sg, prob, chunk);
+  mseg_mixed_io<CP, KP>(io, p.s, sg);
+  mixed_chunk_body<CP, KP>(io, chunk * TPE_JOINT_CHUNK, rows, cl, slot);
+}
+
 int64_t n_chunks_of(int32_t n_cand) { return ((int64_t)n_cand + TPE_JOINT_CHUNK - 1) / TPE_JOINT_CHUNK; }
 
 // tpe_joint_profile: start / stop events of the two launches (profiling only)
@@ -624,21 +765,23 @@ struct {
   hipEvent_t ev[4];
 } g_prof = {0, 0, {nullptr, nullptr, nullptr, nullptr}};
 
-// tpe_joint_seg_run's launches before the merge: the order kernel and one chunk
-// launch per DP class present (g_prof.valid == 2: sum these for last_ms[0])
+// tpe_joint_seg_run's / tpe_joint_mseg_run's launches before the merge: the order
+// kernel, the table kernel and one chunk launch per kernel class present
+// (g_prof.valid == 2: sum these for last_ms[0])
 uint64_t seg_order_bytes(int32_t n_probs) { return ((uint64_t)n_probs * sizeof(int32_t) + 7) & ~(uint64_t)7; }
-constexpr int kSegLaunches = 9;
+constexpr int kSegLaunches = 2 + kMClasses;
 struct {
   int n;
   hipEvent_t ev[2 * kSegLaunches];
 } g_sprof = {0, {}};
 
-template <int DP>
+template <int DP, bool MIXED = false>
 void launch_seg(const SegK& k, unsigned blocks, hipStream_t stream, hipEvent_t* ev) {
   if (ev)
-    hipExtLaunchKernelGGL(k_joint_seg_chunk<DP>, dim3(blocks), dim3(kThreads), 0u, stream, ev[0], ev[1], 0u, k);
+    hipExtLaunchKernelGGL((k_joint_seg_chunk<DP, MIXED>), dim3(blocks), dim3(kThreads), 0u, stream, ev[0], ev[1], 0u,
+                          k);
   else
-    hipLaunchKernelGGL(k_joint_seg_chunk<DP>, dim3(blocks), dim3(kThreads), 0, stream, k);
+    hipLaunchKernelGGL((k_joint_seg_chunk<DP, MIXED>), dim3(blocks), dim3(kThreads), 0, stream, k);
 }
 
 template <int DP>
@@ -710,6 +853,27 @@ __device__ __forceinline__ double bin_mass(double ta, double sa, double tb, doub
   return tb <= 0.0 ? sb - sa : ta >= 0.0 ? sa - sb : 1.0 - sa - sb;
 }
 
+// One (component, dimension) column of a side's table: walk the V + 1 edges e of
+// the dimension once, one erfc per edge (the smaller tail), shared by the two
+// bins that meet there; out[i * K] = log2 P(i), floored at TPE_JOINT_QFLOOR.
+__device__ __forceinline__ void qtable_column(double m, double s, const double* __restrict__ e, int V,
+                                              float* __restrict__ out, int K) {
+  const double r = 0.70710678118654752440 / s;
+  const double t0 = (e[0] - m) * r, tv = (e[V] - m) * r;
+  const double s0 = small_tail(fabs(t0)), sv = small_tail(fabs(tv));
+  const double lmass = log2(bin_mass(t0, s0, tv, sv));
+  double ta = t0, sa = s0;
+  for (int i = 0; i < V; ++i) {
+    const double tb = i + 1 < V ? (e[i + 1] - m) * r : tv;
+    const double sb = i + 1 < V ? small_tail(fabs(tb)) : sv;
+    double v = log2(bin_mass(ta, sa, tb, sb)) - lmass;
+    if (!(v >= kQFloor)) v = kQFloor;       // -inf (a far bin's mass is 0) and NaN included
+    out[(int64_t)i * K] = (float)v;
+    ta = tb; sa = sb;
+  }
+}
+
+
 __global__ __launch_bounds__(kThreads) void k_joint_qtable(const QTabK p) {
   const int k = blockIdx.x * kThreads + threadIdx.x, d = blockIdx.y;
   if (k >= p.K) return;
@@ -717,22 +881,53 @@ __global__ __launch_bounds__(kThreads) void k_joint_qtable(const QTabK p) {
 #pragma unroll
   for (int f = 0; f < TPE_JOINT_MAX_QUANT; ++f)
     if (f == d) { V = p.V[f]; voff = p.voff[f]; eoff = p.eoff[f]; }
-  const double m = p.mu[(int64_t)k * p.Dq + d], s = p.sigma[(int64_t)k * p.Dq + d];
-  const double* e = p.edges + eoff;
-  const double r = 0.70710678118654752440 / s;
-  const double t0 = (e[0] - m) * r, tv = (e[V] - m) * r;
-  const double s0 = small_tail(fabs(t0)), sv = small_tail(fabs(tv));
-  const double lmass = log2(bin_mass(t0, s0, tv, sv));
-  float* out = p.T + (int64_t)voff * p.K + k;
-  double ta = t0, sa = s0;
-  for (int i = 0; i < V; ++i) {
-    const double tb = i + 1 < V ? (e[i + 1] - m) * r : tv;
-    const double sb = i + 1 < V ? small_tail(fabs(tb)) : sv;
-    double v = log2(bin_mass(ta, sa, tb, sb)) - lmass;
-    if (!(v >= kQFloor)) v = kQFloor;       // -inf (a far bin's mass is 0) and NaN included
-    out[(int64_t)i * p.K] = (float)v;
-    ta = tb; sa = sb;
+  qtable_column(p.mu[(int64_t)k * p.Dq + d], p.sigma[(int64_t)k * p.Dq + d], p.edges + eoff, V,
+                p.T + (int64_t)voff * p.K + k, p.K);
+}
+
+// k_joint_qtable for every quantised segment and side of a tpe_joint_mseg_run in
+// one launch: blockIdx.z = 2 * segment + side, blockIdx.y the quantised
+// dimension, thread k of blockIdx.x the component.  A segment's table holds the
+// bytes its solo run builds (qtable_column).
+__global__ __launch_bounds__(kThreads) void k_joint_mseg_qtable(const MSegK p) {
+  const tpe_joint_mseg* __restrict__ sg = mseg_at(p.s, (int)(blockIdx.z >> 1));
+  const int side = blockIdx.z & 1, d = blockIdx.y, Dq = sg->n_quant;
+  const int kb = sg->k_below, K = side ? sg->k_above : kb;
+  const int k = blockIdx.x * kThreads + threadIdx.x;
+  if (d >= Dq || k >= K) return;
+  int voff = 0, total = 0;
+  for (int f = 0; f < Dq; ++f) {
+    if (f < d) voff += sg->quant_v[f];
+    total += sg->quant_v[f];
   }
+  const double* mu = p.s.pool64 + (side ? sg->above_qmu : sg->below_qmu);
+  const double* sigma = p.s.pool64 + (side ? sg->above_qsigma : sg->below_qsigma);
+  float* T = p.table + sg->table + (side ? (int64_t)total * kb : 0);
+  qtable_column(mu[(int64_t)k * Dq + d], sigma[(int64_t)k * Dq + d],
+                p.s.pool64 + sg->quant_edges + sg->quant_edge_off[d], sg->quant_v[d], T + (int64_t)voff * K + k, K);
+}
+
+// What one workgroup of k_joint_quant_chunk / k_joint_mseg_quant_chunk works on:
+// MixedIO (cand / inject rows are [Dc + Dk + Dq]) and the quantised part of ONE
+// (id, group) problem.  Wave-uniform; arrays indexed by constants only.
+template <int CP, int KP, int QP>
+struct QuantIO {
+  MixedIO<CP, (KP > 0 ? KP : 1)> m;
+  int Dq, tile, stride, total;      // components per tile, floats per lattice value in the tile, sum V_d
+  int V[QP], voff[QP], eoff[QP];
+  float qlo[QP], qhi[QP];
+  const double* edges;
+  const float* qsamp;
+  const float *bT, *aT;             // [total][K] of a side
+};
+
+// the longest tile (a multiple of 8 components, at most kTileK) whose table of
+// `total` lattice values (and the zero row) fits kQTileBytes
+__host__ __device__ __forceinline__ int quant_tile(int total) {
+  int tile = 8;
+  for (int tk = kTileK; tk >= 8; tk -= 8)
+    if ((int64_t)(total + 1) * (tk + 4) * (int64_t)sizeof(float) <= kQTileBytes) { tile = tk; break; }
+  return tile;
 }
 
 // score_side_mixed with QP quantised dimensions.  The side's table streams
@@ -747,12 +942,12 @@ template <int CP, int KP, int QP>
 __device__ __forceinline__ void score_side_quant(const float* __restrict__ mu, const float* __restrict__ a,
                                                  const float* __restrict__ c, const float* __restrict__ cat,
                                                  const float* __restrict__ miss, const float* __restrict__ bonus,
-                                                 const float* __restrict__ T, int K, const QuantK& p,
+                                                 const float* __restrict__ T, int K, const QuantIO<CP, KP, QP>& p,
                                                  const float (&z)[kR][CP + KP + QP], const int (&qo)[kR][QP],
                                                  float* __restrict__ rows, float* __restrict__ cl,
                                                  float* __restrict__ qt, double (&out)[kR]) {
   constexpr int S = 2 * CP + KP, KPa = KP > 0 ? KP : 1;
-  const int Dc = p.m.j.D, Dk = p.m.Dk, tile = p.tile, stride = p.stride;
+  const int Dc = p.m.q.D, Dk = p.m.Dk, tile = p.tile, stride = p.stride;
   float m[kR], s[kR], nb[kR][KPa];
 #pragma unroll
   for (int r = 0; r < kR; ++r) {
@@ -836,22 +1031,18 @@ __device__ __forceinline__ void score_side_quant(const float* __restrict__ mu, c
   }
 }
 
-// k_joint_mixed_chunk for a group with quantised labels: CP / KP / QP the padded
+// mixed_chunk_body for a group with quantised labels: CP / KP / QP the padded
 // continuous / discrete / quantised counts (CP = 0, KP = 0 allowed).  z[r] holds
 // the continuous coordinates at [0, CP), the categories at [CP, CP + KP) and the
-// lattice indices at [CP + KP, CP + KP + QP).
+// lattice indices at [CP + KP, CP + KP + QP).  qt: the dynamic LDS tile,
+// [(total + 1) * stride].
 template <int CP, int KP, int QP>
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, (CP + KP + QP >= 12 ? 2 : 8))))
-void k_joint_quant_chunk(const QuantK p) {
-  constexpr int ZP = CP + KP + QP, S = 2 * CP + KP;
-  __shared__ __attribute__((aligned(16))) float rows[kTileK * (S > 0 ? S : 1)];
-  __shared__ float cl[kTileK];
-  __shared__ Pick slot[kThreads / 64];
-  extern __shared__ __attribute__((aligned(16))) float qt[];     // [(total + 1) * stride]
-  const JointK& q = p.m.j;
+__device__ __forceinline__ void quant_chunk_body(const QuantIO<CP, KP, QP>& p, int first, float* __restrict__ rows,
+                                                 float* __restrict__ cl, float* __restrict__ qt,
+                                                 Pick* __restrict__ slot) {
+  constexpr int ZP = CP + KP + QP;
+  const ChunkIO& q = p.m.q;
   const int t = threadIdx.x, Dc = q.D, Dk = p.m.Dk, Dq = p.Dq, D = Dc + Dk + Dq;
-  const int id = blockIdx.x / q.n_chunks, chunk = blockIdx.x % q.n_chunks;
-  const int first = chunk * TPE_JOINT_CHUNK;
 
   for (int e = t; e < p.stride; e += kThreads) qt[p.total * p.stride + e] = 0.f;   // the padded slots' row
 
@@ -874,7 +1065,7 @@ void k_joint_quant_chunk(const QuantK p) {
         if (d < Dq) z[r][CP + KP + d] = q.inj[(int64_t)i * D + Dc + Dk + d];
       continue;
     }
-    const uint32_t c3 = (uint32_t)q.ids[id];
+    const uint32_t c3 = q.c3;
     U4 w = philox4x32_10((uint32_t)i, 0u, q.stream_word, c3, q.key0, q.key1);
     const double us = u01w(w.x);
     int lo = 0, hi = q.kb - 1;             // first k with us < cum[k]
@@ -897,11 +1088,11 @@ void k_joint_quant_chunk(const QuantK p) {
         if (sr[4] != 0.f) zz = -zz;
         x = sr[0] + sr[1] * zz;
         if (!(x == x)) x = sr[0];
-        float blo = 0.f, bhi = 0.f;                       // (kernel-argument arrays: constant indices only)
+        float blo = 0.f, bhi = 0.f;                       // (the bound arrays: constant indices only)
         if (!quant) {
 #pragma unroll
           for (int f = 0; f < CP; ++f)
-            if (f == d) { blo = q.lo[f]; bhi = q.hi[f]; }
+            if (f == d) { blo = p.m.lo[f]; bhi = p.m.hi[f]; }
         } else {
 #pragma unroll
           for (int f = 0; f < QP; ++f)
@@ -969,19 +1160,19 @@ void k_joint_quant_chunk(const QuantK p) {
     lv[r] = l2[r] * kLn2 + q.bbase;
     gv[r] = g2[r] * kLn2 + q.abase;
     if (i >= q.C) continue;
-    const int64_t o = (int64_t)id * q.C + i;
-    if (q.l_out) q.l_out[o] = lv[r];
-    if (q.g_out) q.g_out[o] = gv[r];
+    if (q.l_out) q.l_out[i] = lv[r];
+    if (q.g_out) q.g_out[i] = gv[r];
     if (q.cand) {
+      float* row = q.cand + (int64_t)i * D;
 #pragma unroll
       for (int d = 0; d < CP; ++d)
-        if (d < Dc) q.cand[o * D + d] = z[r][d];
+        if (d < Dc) row[d] = z[r][d];
 #pragma unroll
       for (int d = 0; d < KP; ++d)
-        if (d < Dk) q.cand[o * D + Dc + d] = z[r][CP + d];
+        if (d < Dk) row[Dc + d] = z[r][CP + d];
 #pragma unroll
       for (int d = 0; d < QP; ++d)
-        if (d < Dq) q.cand[o * D + Dc + Dk + d] = z[r][CP + KP + d];
+        if (d < Dq) row[Dc + Dk + d] = z[r][CP + KP + d];
     }
     const uint64_t key = score_key(lv[r] - gv[r]);
     if (key > best.key) best = Pick{key, (int64_t)i};   // ascending index: strict > keeps the first of a tie
@@ -994,7 +1185,7 @@ void k_joint_quant_chunk(const QuantK p) {
   for (int s = 1; s < kThreads / 64; ++s)
     if (beats(slot[s], w)) w = slot[s];
 
-  tpe_joint_record* rec = q.chunk_rec + blockIdx.x;
+  tpe_joint_record* rec = q.rec;
   if (w.key == 0) {
     if (t == 0) rec->global_idx = -1;
     return;
@@ -1022,6 +1213,81 @@ void k_joint_quant_chunk(const QuantK p) {
     for (int d = 0; d < QP; ++d)
       if (d < Dq) rec->z[Dc + Dk + d] = (double)z[r][CP + KP + d];
   }
+}
+
+template <int CP, int KP, int QP>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, (CP + KP + QP >= 12 ? 2 : 8))))
+void k_joint_quant_chunk(const QuantK p) {
+  constexpr int S = 2 * CP + KP;
+  __shared__ __attribute__((aligned(16))) float rows[kTileK * (S > 0 ? S : 1)];
+  __shared__ float cl[kTileK];
+  __shared__ Pick slot[kThreads / 64];
+  extern __shared__ __attribute__((aligned(16))) float qt[];     // [(total + 1) * stride]
+  const JointK& j = p.m.j;
+  QuantIO<CP, KP, QP> io;
+  solo_chunk_io(io.m.q, j, j.D + p.m.Dk + p.Dq);
+  io.m.Dk = p.m.Dk;
+#pragma unroll
+  for (int d = 0; d < CP; ++d) { io.m.lo[d] = j.lo[d]; io.m.hi[d] = j.hi[d]; }   // (kernel-argument arrays: constant indices only)
+#pragma unroll
+  for (int d = 0; d < KP; ++d) { io.m.U[d] = p.m.U[d]; io.m.off[d] = p.m.off[d]; }
+  io.m.bcat = p.m.bcat; io.m.acat = p.m.acat;
+  io.m.bmiss = p.m.bmiss; io.m.bbonus = p.m.bbonus; io.m.amiss = p.m.amiss; io.m.abonus = p.m.abonus;
+  io.m.bh = p.m.bh; io.m.ccum = p.m.ccum;
+  io.Dq = p.Dq; io.tile = p.tile; io.stride = p.stride; io.total = p.total;
+#pragma unroll
+  for (int d = 0; d < QP; ++d) {
+    io.V[d] = p.V[d]; io.voff[d] = p.voff[d]; io.eoff[d] = p.eoff[d];
+    io.qlo[d] = p.qlo[d]; io.qhi[d] = p.qhi[d];
+  }
+  io.edges = p.edges; io.qsamp = p.qsamp; io.bT = p.bT; io.aT = p.aT;
+  quant_chunk_body<CP, KP, QP>(io, (int)(blockIdx.x % j.n_chunks) * TPE_JOINT_CHUNK, rows, cl, qt, slot);
+}
+
+template <int CP, int KP, int QP>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, (CP + KP + QP >= 12 ? 2 : 8))))
+void k_joint_mseg_quant_chunk(const MSegK p) {
+  static_assert(KP <= TPE_JOINT_MSEG_MAX_CAT && CP <= TPE_JOINT_MSEG_MAX_CONT && QP <= TPE_JOINT_MAX_QUANT,
+                "the descriptor's arrays");
+  constexpr int S = 2 * CP + KP;
+  __shared__ __attribute__((aligned(16))) float rows[kTileK * (S > 0 ? S : 1)];
+  __shared__ float cl[kTileK];
+  __shared__ Pick slot[kThreads / 64];
+  extern __shared__ __attribute__((aligned(16))) float qt[];     // at least [(total + 1) * stride] of this segment
+  const int chunk = blockIdx.x % p.s.n_chunks;
+  const int prob = uni(p.s.order[p.s.first + blockIdx.x / p.s.n_chunks]);
+  const tpe_joint_mseg* __restrict__ sg = mseg_at(p.s, uni(p.s.prob_seg[prob]));
+  QuantIO<CP, KP, QP> io;
+  mseg_chunk_io(io.m.q, p.s, sg, prob, chunk);
+  if constexpr (KP > 0) {
+    mseg_mixed_io<CP, KP>(io.m, p.s, sg);
+  } else {
+    io.m.Dk = 0;
+#pragma unroll
+    for (int d = 0; d < CP; ++d) { io.m.lo[d] = unif(sg->lo[d]); io.m.hi[d] = unif(sg->hi[d]); }
+    io.m.U[0] = 1; io.m.off[0] = 0;
+    io.m.bcat = io.m.acat = io.m.bmiss = io.m.bbonus = io.m.amiss = io.m.abonus = nullptr;
+    io.m.bh = io.m.ccum = nullptr;
+  }
+  io.Dq = uni(sg->n_quant);
+  int total = 0;
+#pragma unroll
+  for (int d = 0; d < QP; ++d) {
+    const bool in = d < io.Dq;                // padded slots: as tpe_joint_quant_run fills them
+    io.V[d] = in ? uni(sg->quant_v[d]) : 2;
+    io.voff[d] = in ? total : 0;
+    io.eoff[d] = in ? uni(sg->quant_edge_off[d]) : 0;
+    io.qlo[d] = in ? unif(sg->qlo[d]) : -INFINITY;
+    io.qhi[d] = in ? unif(sg->qhi[d]) : INFINITY;
+    total += in ? io.V[d] : 0;
+  }
+  io.total = total;
+  io.tile = quant_tile(total); io.stride = io.tile + 4;     // the solo run's tiling of this segment
+  io.edges = p.s.pool64 + uni(sg->quant_edges);
+  io.qsamp = p.s.inject ? nullptr : p.s.pool + uni(sg->quant_samp);
+  io.bT = p.table + uni(sg->table);
+  io.aT = io.bT + (int64_t)total * io.m.q.kb;
+  quant_chunk_body<CP, KP, QP>(io, chunk * TPE_JOINT_CHUNK, rows, cl, qt, slot);
 }
 
 // start / stop events around the two table launches (profiling only)
@@ -1053,6 +1319,71 @@ void launch_quant_k(const QuantK& k, unsigned blocks, unsigned lds, hipStream_t 
   else if (Dk == 1) launch_quant_q<CP, 1>(k, blocks, lds, stream, timed);
   else if (Dk == 2) launch_quant_q<CP, 2>(k, blocks, lds, stream, timed);
   else launch_quant_q<CP, 4>(k, blocks, lds, stream, timed);
+}
+
+// the segmented launches of the mixed and the quantised kernels, by class index
+template <int CP, int KP>
+void launch_mseg_mixed(const MSegK& k, unsigned blocks, hipStream_t stream, hipEvent_t* ev) {
+  if (ev)
+    hipExtLaunchKernelGGL((k_joint_mseg_mixed_chunk<CP, KP>), dim3(blocks), dim3(kThreads), 0u, stream, ev[0], ev[1],
+                          0u, k);
+  else
+    hipLaunchKernelGGL((k_joint_mseg_mixed_chunk<CP, KP>), dim3(blocks), dim3(kThreads), 0, stream, k);
+}
+template <int CP>
+void launch_mseg_mixed_k(int kp, const MSegK& k, unsigned blocks, hipStream_t stream, hipEvent_t* ev) {
+  if (kp == 0) launch_mseg_mixed<CP, 1>(k, blocks, stream, ev);
+  else if (kp == 1) launch_mseg_mixed<CP, 2>(k, blocks, stream, ev);
+  else launch_mseg_mixed<CP, 4>(k, blocks, stream, ev);
+}
+template <int CP, int KP, int QP>
+void launch_mseg_quant(const MSegK& k, unsigned blocks, unsigned lds, hipStream_t stream, hipEvent_t* ev) {
+  if (ev)
+    hipExtLaunchKernelGGL((k_joint_mseg_quant_chunk<CP, KP, QP>), dim3(blocks), dim3(kThreads), lds, stream, ev[0],
+                          ev[1], 0u, k);
+  else
+    hipLaunchKernelGGL((k_joint_mseg_quant_chunk<CP, KP, QP>), dim3(blocks), dim3(kThreads), lds, stream, k);
+}
+template <int CP, int KP>
+void launch_mseg_quant_q(int qp, const MSegK& k, unsigned blocks, unsigned lds, hipStream_t stream, hipEvent_t* ev) {
+  if (qp == 0) launch_mseg_quant<CP, KP, 1>(k, blocks, lds, stream, ev);
+  else if (qp == 1) launch_mseg_quant<CP, KP, 2>(k, blocks, lds, stream, ev);
+  else launch_mseg_quant<CP, KP, 4>(k, blocks, lds, stream, ev);
+}
+template <int CP>
+void launch_mseg_quant_k(int kp, int qp, const MSegK& k, unsigned blocks, unsigned lds, hipStream_t stream,
+                         hipEvent_t* ev) {
+  if (kp == 0) launch_mseg_quant_q<CP, 0>(qp, k, blocks, lds, stream, ev);
+  else if (kp == 1) launch_mseg_quant_q<CP, 1>(qp, k, blocks, lds, stream, ev);
+  else if (kp == 2) launch_mseg_quant_q<CP, 2>(qp, k, blocks, lds, stream, ev);
+  else launch_mseg_quant_q<CP, 4>(qp, k, blocks, lds, stream, ev);
+}
+// one chunk launch of kernel class c (mseg_class) over `blocks` workgroups
+void launch_mseg_class(int c, const MSegK& k, unsigned blocks, unsigned lds, hipStream_t s, hipEvent_t* ev) {
+  if (c < 8) {
+    switch (c) {
+      case 0: launch_seg<1, true>(k.s, blocks, s, ev); break;
+      case 1: launch_seg<2, true>(k.s, blocks, s, ev); break;
+      case 2: launch_seg<3, true>(k.s, blocks, s, ev); break;
+      case 3: launch_seg<4, true>(k.s, blocks, s, ev); break;
+      case 4: launch_seg<6, true>(k.s, blocks, s, ev); break;
+      case 5: launch_seg<8, true>(k.s, blocks, s, ev); break;
+      case 6: launch_seg<12, true>(k.s, blocks, s, ev); break;
+      default: launch_seg<16, true>(k.s, blocks, s, ev); break;
+    }
+  } else if (c < 20) {
+    const int cp = (c - 8) / 3, kp = (c - 8) % 3;
+    if (cp == 0) launch_mseg_mixed_k<0>(kp, k, blocks, s, ev);
+    else if (cp == 1) launch_mseg_mixed_k<2>(kp, k, blocks, s, ev);
+    else if (cp == 2) launch_mseg_mixed_k<4>(kp, k, blocks, s, ev);
+    else launch_mseg_mixed_k<8>(kp, k, blocks, s, ev);
+  } else {
+    const int cp = (c - 20) / 12, kp = (c - 20) / 3 % 4, qp = (c - 20) % 3;
+    if (cp == 0) launch_mseg_quant_k<0>(kp, qp, k, blocks, lds, s, ev);
+    else if (cp == 1) launch_mseg_quant_k<2>(kp, qp, k, blocks, lds, s, ev);
+    else if (cp == 2) launch_mseg_quant_k<4>(kp, qp, k, blocks, lds, s, ev);
+    else launch_mseg_quant_k<8>(kp, qp, k, blocks, lds, s, ev);
+  }
 }
 
 // -------------------------------------------------------------- wide groups
@@ -1486,18 +1817,19 @@ int tpe_joint_seg_run(const tpe_joint_seg_args* a, tpe_joint_record* records, fl
 
   const bool timed = g_prof.on != 0;
   hipStream_t s = (hipStream_t)stream;
-  if (timed && !g_sprof.ev[0])
+  if (timed && !g_sprof.ev[2 * kSegLaunches - 1])
     for (int i = 0; i < 2 * kSegLaunches; ++i) {
+      if (g_sprof.ev[i]) continue;
       const hipError_t e = hipEventCreate(&g_sprof.ev[i]);
       if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
     }
   int n_timed = 0;
   const unsigned ob = (unsigned)((a->n_probs + kThreads - 1) / kThreads);
   if (timed) {
-    hipExtLaunchKernelGGL(k_joint_seg_order, dim3(ob), dim3(kThreads), 0u, s, g_sprof.ev[0], g_sprof.ev[1], 0u, k);
+    hipExtLaunchKernelGGL(k_joint_seg_order<false>, dim3(ob), dim3(kThreads), 0u, s, g_sprof.ev[0], g_sprof.ev[1], 0u, k);
     n_timed = 1;
   } else {
-    hipLaunchKernelGGL(k_joint_seg_order, dim3(ob), dim3(kThreads), 0, s, k);
+    hipLaunchKernelGGL(k_joint_seg_order<false>, dim3(ob), dim3(kThreads), 0, s, k);
   }
   int64_t first = 0;
   for (int c = 0; c < 8; ++c) {
@@ -1515,6 +1847,214 @@ int tpe_joint_seg_run(const tpe_joint_seg_args* a, tpe_joint_record* records, fl
       case 6: launch_seg<12>(k, nb, s, ev); break;
       default: launch_seg<16>(k, nb, s, ev); break;
     }
+    first += per_class[c];
+  }
+  if (timed) {
+    hipExtLaunchKernelGGL(k_joint_merge, dim3((unsigned)a->n_probs), dim3(64), 0u, s, g_prof.ev[2], g_prof.ev[3], 0u,
+                          (const tpe_joint_record*)k.chunk_rec, (int)n_chunks, records);
+    g_sprof.n = n_timed;
+    g_prof.valid = 2;
+  } else {
+    hipLaunchKernelGGL(k_joint_merge, dim3((unsigned)a->n_probs), dim3(64), 0, s,
+                       (const tpe_joint_record*)k.chunk_rec, (int)n_chunks, records);
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
+  return TPE_OK;
+}
+
+int tpe_joint_mseg_scratch_bytes(int32_t n_probs, int32_t n_cand, uint64_t* bytes) {
+  if (!bytes || n_probs < 1 || n_cand < 1)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_scratch_bytes: bad arguments");
+  *bytes = seg_order_bytes(n_probs) + (uint64_t)n_probs * (uint64_t)n_chunks_of(n_cand) * sizeof(tpe_joint_record);
+  return TPE_OK;
+}
+
+int tpe_joint_mseg_table_bytes(const tpe_joint_mseg* host_segs, int32_t n_segs, uint64_t* bytes) {
+  if (!bytes || !host_segs || n_segs < 1)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_table_bytes: bad arguments");
+  uint64_t n = 0;
+  for (int s = 0; s < n_segs; ++s) {
+    const tpe_joint_mseg& g = host_segs[s];
+    if (g.n_quant < 0 || g.n_quant > TPE_JOINT_MAX_QUANT || g.k_below < 1 || g.k_above < 1)
+      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_table_bytes: a segment's n_quant, k_below or k_above out of range");
+    uint64_t total = 0;
+    for (int d = 0; d < g.n_quant; ++d) {
+      if (g.quant_v[d] < 2 || g.quant_v[d] > TPE_JOINT_MAX_LATTICE)
+        return tpe_internal_fail(TPE_E_ARG,
+                                 "tpe_joint_mseg_table_bytes: lattice values of a label outside [2, TPE_JOINT_MAX_LATTICE]");
+      total += (uint64_t)g.quant_v[d];
+    }
+    n += ((uint64_t)g.k_below + (uint64_t)g.k_above) * total;
+  }
+  *bytes = n * sizeof(float);
+  return TPE_OK;
+}
+
+int tpe_joint_mseg_run(const tpe_joint_mseg_args* a, tpe_joint_record* records, float* cand, double* l_out,
+                       double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
+  tpe_internal_epoch_bump();
+  static_assert(offsetof(tpe_joint_mseg, hi) == offsetof(tpe_joint_seg, hi) &&
+                    offsetof(tpe_joint_mseg, n_cat) == sizeof(tpe_joint_seg),
+                "tpe_joint_mseg starts with tpe_joint_seg");
+  static_assert(offsetof(tpe_joint_mseg_args, cand_off) == offsetof(tpe_joint_seg_args, cand_off), "the shared fields");
+  if (!a) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: null args");
+  if (a->n_segs < 1) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: n_segs < 1");
+  if (a->n_segs > 32767) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: more than 32767 segments");
+  if (a->n_probs < 1) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: n_probs < 1");
+  if (a->n_cand < 1) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: n_cand < 1");
+  if (!a->segs || !a->host_segs) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: null segs / host_segs");
+  const bool inject = (a->flags & TPE_JOINT_INJECT) != 0;
+  if (!a->pool_f32 || (!inject && !a->pool_f64)) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: null pool");
+  if (!a->prob_seg || !a->host_prob_seg || !a->prob_id)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: null prob_seg / host_prob_seg / prob_id");
+  if (!records) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: null records");
+  if (cand && !a->cand_off) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: cand without cand_off");
+  // rows [off, off + n) inside a pool of len elements
+  auto inside = [](int64_t off, int64_t n, int64_t len) { return off >= 0 && n <= len && off <= len - n; };
+  const int64_t L = a->pool_f32_len, L64 = a->pool_f64_len, LT = (int64_t)(a->quant_table_bytes / sizeof(float));
+  int max_kblocks = 0;
+  bool any_quant = false;
+  for (int s = 0; s < a->n_segs; ++s) {
+    const tpe_joint_mseg& g = a->host_segs[s];
+    if (g.n_cat < 0 || g.n_cat > TPE_JOINT_MAX_DIMS)
+      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: a segment's n_cat outside [0, TPE_JOINT_MAX_DIMS]");
+    if (g.n_quant < 0 || g.n_quant > TPE_JOINT_MAX_QUANT)
+      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: a segment's n_quant outside [0, TPE_JOINT_MAX_QUANT]");
+    const int64_t Dc = g.n_dims, Dk = g.n_cat, Dq = g.n_quant, D = Dc + Dk + Dq, kb = g.k_below, ka = g.k_above;
+    if (Dk + Dq == 0) {
+      if (Dc < 1 || Dc > TPE_JOINT_MAX_DIMS)
+        return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: a segment's n_dims outside [1, TPE_JOINT_MAX_DIMS]");
+    } else {
+      if (Dc < 0) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: a segment's n_dims < 0");
+      if (Dc > TPE_JOINT_MSEG_MAX_CONT || Dk > TPE_JOINT_MSEG_MAX_CAT)
+        return tpe_internal_fail(TPE_E_ARG,
+                                 "tpe_joint_mseg_run: n_dims > 8 or n_cat > 4 in a segment with a discrete or quantised label");
+    }
+    if (kb < 1 || ka < 1)
+      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: a segment's k_below < 1 or k_above < 1");
+    int64_t cat_total = 0, total = 0;
+    for (int d = 0; d < Dk; ++d) {
+      if (g.cat_upper[d] < 2 || g.cat_upper[d] > TPE_JOINT_MAX_CATS)
+        return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: categories of a label outside [2, TPE_JOINT_MAX_CATS]");
+      cat_total += g.cat_upper[d];
+    }
+    if (cat_total > TPE_JOINT_MAX_CAT_TOTAL)
+      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: more than TPE_JOINT_MAX_CAT_TOTAL categories in a segment");
+    for (int d = 0; d < Dk; ++d)
+      if (g.cat_off[d] < 0 || g.cat_off[d] > cat_total - g.cat_upper[d])
+        return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: cat_off outside the tables");
+    for (int d = 0; d < Dq; ++d) {
+      if (g.quant_v[d] < 2 || g.quant_v[d] > TPE_JOINT_MAX_LATTICE)
+        return tpe_internal_fail(TPE_E_ARG,
+                                 "tpe_joint_mseg_run: lattice values of a label outside [2, TPE_JOINT_MAX_LATTICE]");
+      total += g.quant_v[d];
+    }
+    if (total > TPE_JOINT_MAX_LATTICE_TOTAL)
+      return tpe_internal_fail(TPE_E_ARG,
+                               "tpe_joint_mseg_run: more than TPE_JOINT_MAX_LATTICE_TOTAL lattice values in a segment");
+    for (int d = 0; d < Dq; ++d)
+      if (g.quant_edge_off[d] < 0 || (int64_t)g.quant_edge_off[d] + g.quant_v[d] + 1 > (int64_t)g.n_edges)
+        return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: quant_edge_off outside the edge array");
+    if (Dq > 0 && !a->pool_f64)
+      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: null pool_f64 with a quantised segment");
+    if (Dq > 0 && !a->quant_table)
+      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: null table workspace with a quantised segment");
+    bool ok = inside(g.below_c, kb, L) && inside(g.above_c, ka, L);
+    if (Dc > 0)
+      ok = ok && inside(g.below_mu, kb * Dc, L) && inside(g.below_a, kb * Dc, L) && inside(g.above_mu, ka * Dc, L) &&
+           inside(g.above_a, ka * Dc, L);
+    if (!inject) ok = ok && inside(g.samp_cum, kb, L64) && (Dc == 0 || inside(g.samp, kb * Dc * 5, L));
+    if (inject && g.inject >= 0) ok = ok && inside(g.inject, (int64_t)a->n_cand * D, L);
+    if (Dk > 0) {
+      ok = ok && inside(g.below_cat, kb * Dk, L) && inside(g.above_cat, ka * Dk, L) &&
+           inside(g.below_miss, cat_total, L) && inside(g.below_bonus, cat_total, L) &&
+           inside(g.above_miss, cat_total, L) && inside(g.above_bonus, cat_total, L);
+      if (!inject) ok = ok && inside(g.below_h, Dk, L64) && inside(g.cat_cum, cat_total, L64);
+    }
+    if (Dq > 0) {
+      ok = ok && inside(g.quant_edges, g.n_edges, L64) && inside(g.below_qmu, kb * Dq, L64) &&
+           inside(g.below_qsigma, kb * Dq, L64) && inside(g.above_qmu, ka * Dq, L64) &&
+           inside(g.above_qsigma, ka * Dq, L64);
+      if (!inject) ok = ok && inside(g.quant_samp, kb * Dq * 5, L);
+    }
+    if (!ok) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: a segment's rows leave its pool");
+    if (Dq > 0) {
+      if (!inside(g.table, (kb + ka) * total, LT))
+        return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: a segment's table leaves the table workspace");
+      any_quant = true;
+      const int64_t km = kb > ka ? kb : ka;
+      max_kblocks = (int)((km + kThreads - 1) / kThreads) > max_kblocks ? (int)((km + kThreads - 1) / kThreads) : max_kblocks;
+    }
+  }
+  int64_t per_class[kMClasses];
+  unsigned lds_class[kMClasses];
+  for (int c = 0; c < kMClasses; ++c) { per_class[c] = 0; lds_class[c] = 0u; }
+  for (int p = 0; p < a->n_probs; ++p) {
+    const int s = a->host_prob_seg[p];
+    if (s < 0 || s >= a->n_segs) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: prob_seg outside [0, n_segs)");
+    const tpe_joint_mseg& g = a->host_segs[s];
+    if (inject && g.inject < 0)
+      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: TPE_JOINT_INJECT without candidates");
+    const int c = mseg_class(g.n_dims, g.n_cat, g.n_quant);
+    ++per_class[c];
+    if (g.n_quant > 0) {                     // the segment's own tile (the solo run's rule); the launch takes the largest
+      int total = 0;
+      for (int d = 0; d < g.n_quant; ++d) total += g.quant_v[d];
+      const unsigned lds = (unsigned)((total + 1) * (quant_tile(total) + 4) * sizeof(float));
+      if (lds > lds_class[c]) lds_class[c] = lds;
+    }
+  }
+  const int64_t n_chunks = n_chunks_of(a->n_cand), blocks = n_chunks * a->n_probs;
+  if (blocks > INT32_MAX || (int64_t)a->n_segs * kMClasses > INT32_MAX)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: too many candidates");
+  const uint64_t need = seg_order_bytes(a->n_probs) + (uint64_t)blocks * sizeof(tpe_joint_record);
+  if (!scratch || scratch_bytes < need) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: scratch too small");
+
+  MSegK mk;
+  SegK& k = mk.s;
+  k.C = a->n_cand; k.n_chunks = (int)n_chunks; k.inject = inject ? 1 : 0; k.first = 0;
+  k.n_probs = a->n_probs; k.n_segs = a->n_segs;
+  k.key0 = (uint32_t)a->seed; k.key1 = (uint32_t)(a->seed >> 32);
+  k.segs = reinterpret_cast<const tpe_joint_seg*>(a->segs); k.pool = a->pool_f32; k.pool64 = a->pool_f64;
+  k.prob_seg = a->prob_seg; k.prob_id = a->prob_id; k.cand_off = a->cand_off;
+  k.order = (int32_t*)scratch;
+  k.cand = cand; k.l_out = l_out; k.g_out = g_out;
+  k.chunk_rec = (tpe_joint_record*)((char*)scratch + seg_order_bytes(a->n_probs));
+  mk.table = a->quant_table;
+
+  const bool timed = g_prof.on != 0;
+  hipStream_t s = (hipStream_t)stream;
+  if (timed && !g_sprof.ev[2 * kSegLaunches - 1])
+    for (int i = 0; i < 2 * kSegLaunches; ++i) {
+      if (g_sprof.ev[i]) continue;
+      const hipError_t e = hipEventCreate(&g_sprof.ev[i]);
+      if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
+    }
+  int n_timed = 0;
+  const unsigned ob = (unsigned)((a->n_probs + kThreads - 1) / kThreads);
+  if (timed) {
+    hipExtLaunchKernelGGL(k_joint_seg_order<true>, dim3(ob), dim3(kThreads), 0u, s, g_sprof.ev[0], g_sprof.ev[1], 0u, k);
+    n_timed = 1;
+  } else {
+    hipLaunchKernelGGL(k_joint_seg_order<true>, dim3(ob), dim3(kThreads), 0, s, k);
+  }
+  if (any_quant) {
+    const dim3 grid((unsigned)max_kblocks, (unsigned)TPE_JOINT_MAX_QUANT, (unsigned)(2 * a->n_segs));
+    if (timed) {
+      hipExtLaunchKernelGGL(k_joint_mseg_qtable, grid, dim3(kThreads), 0u, s, g_sprof.ev[2 * n_timed],
+                            g_sprof.ev[2 * n_timed + 1], 0u, mk);
+      ++n_timed;
+    } else {
+      hipLaunchKernelGGL(k_joint_mseg_qtable, grid, dim3(kThreads), 0, s, mk);
+    }
+  }
+  int64_t first = 0;
+  for (int c = 0; c < kMClasses; ++c) {
+    if (!per_class[c]) continue;
+    k.first = (int)first;
+    hipEvent_t* ev = timed ? g_sprof.ev + 2 * n_timed++ : nullptr;
+    launch_mseg_class(c, mk, (unsigned)(per_class[c] * n_chunks), lds_class[c], s, ev);
     first += per_class[c];
   }
   if (timed) {
@@ -1870,11 +2410,7 @@ int tpe_joint_quant_run(const tpe_joint_quant_args* a, tpe_joint_record* records
       voff += a->quant_v[d];
     }
   }
-  // the longest tile (a multiple of 8 components, at most kTileK) whose table fits kQTileBytes
-  int tile = 8;
-  for (int tk = kTileK; tk >= 8; tk -= 8)
-    if ((int64_t)(total + 1) * (tk + 4) * (int64_t)sizeof(float) <= kQTileBytes) { tile = tk; break; }
-  qk.tile = tile; qk.stride = tile + 4;
+  qk.tile = quant_tile(total); qk.stride = qk.tile + 4;
   const unsigned lds = (unsigned)((total + 1) * qk.stride * sizeof(float));
 
   const bool timed = g_prof.on != 0;

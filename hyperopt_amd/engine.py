@@ -1162,8 +1162,21 @@ class Engine(object):
         a group without a problem): its problems score these candidates.
         Returns the records [P] (N.JOINT_RECORD_DTYPE); with ``return_cand``
         also a list of P arrays f32 [C, D_group]; with ``want_lg`` also l, g
-        float64 [P, C]."""
+        float64 [P, C].
+
+        A group may also be a joint.MixedModel / joint.QuantModel, or a tuple
+        (below, above, low, high, cats) / (below, above, low, high, cats,
+        quants) as ``run_joint_mixed`` / ``run_joint_quant`` take them.  With
+        such a group among them all groups, continuous ones included, go to
+        tpe_joint_mseg_run (include/tpe_hip.h "Mixed segmented joint stage"):
+        still one upload, one call and one download, and problem p's results
+        are those of the solo run of its group's kind; D_group counts the
+        continuous, discrete and quantised coordinates, in that order.  With
+        continuous groups only nothing changes: tpe_joint_seg_run, the same blob."""
         from . import joint as J
+        if any(self._seg_parts(m)[4] or self._seg_parts(m)[5] for m in models):
+            return self._run_joint_msegments(models, stream_words, prob_seg, prob_id, n_cand, seed, inject,
+                                             return_cand, want_lg, report_k)
         S, C = len(models), int(n_cand)
         report_k = self._report_k(report_k)
         dev_cand, dev_lg = return_cand or report_k > 0, want_lg or report_k > 0
@@ -1239,9 +1252,14 @@ class Engine(object):
         a.pool_f64, a.prob_id, a.cand_off = base + int(offs[1]), base + int(offs[2]), base + int(offs[3])
         a.pool_f32, a.prob_seg, a.host_prob_seg = base + int(offs[4]), base + int(offs[5]), prob_seg.ctypes.data
         a.pool_f32_len, a.pool_f64_len = n32, n64
+        return self._joint_seg_call('tpe_joint_seg', a, P, C, cand_off, pd, return_cand, want_lg, report_k)
 
+    def _joint_seg_call(self, fn, a, P, C, cand_off, pd, return_cand, want_lg, report_k):
+        """What the two segmented stages share: scratch and the result block, the
+        native call ``fn``_run, the report, and one transfer of the results."""
+        dev_cand, dev_lg = return_cand or report_k > 0, want_lg or report_k > 0
         nb = ctypes.c_uint64(0)
-        N.check(self.lib.tpe_joint_seg_scratch_bytes(P, C, ctypes.byref(nb)), self.lib, 'tpe_joint_seg_scratch_bytes')
+        N.check(getattr(self.lib, fn + '_scratch_bytes')(P, C, ctypes.byref(nb)), self.lib, fn + '_scratch_bytes')
         d_scr = self._buf('joint_scratch', (nb.value + 7) // 8, torch.float64)
         # one result block of 8-byte words: records, l, g, then the candidates (f32 pairs)
         rec_w = P * N.JOINT_RECORD_DTYPE.itemsize // 8
@@ -1250,11 +1268,11 @@ class Engine(object):
         d_out = self._buf('joint_seg_out', rec_w + 2 * lg_w + cand_w, torch.float64)
         out = d_out.data_ptr()
         stream = self._stream()
-        N.check(self.lib.tpe_joint_seg_run(ctypes.byref(a), out, out + 8 * (rec_w + 2 * lg_w) if dev_cand else None,
-                                           out + 8 * rec_w if dev_lg else None,
-                                           out + 8 * (rec_w + lg_w) if dev_lg else None,
-                                           d_scr.data_ptr(), d_scr.numel() * 8, ctypes.c_void_p(stream)),
-                self.lib, 'tpe_joint_seg_run')
+        N.check(getattr(self.lib, fn + '_run')(ctypes.byref(a), out, out + 8 * (rec_w + 2 * lg_w) if dev_cand else None,
+                                               out + 8 * rec_w if dev_lg else None,
+                                               out + 8 * (rec_w + lg_w) if dev_lg else None,
+                                               d_scr.data_ptr(), d_scr.numel() * 8, ctypes.c_void_p(stream)),
+                self.lib, fn + '_run')
         if report_k:
             rep = self._joint_report(out + 8 * (rec_w + 2 * lg_w), out + 8 * rec_w, out + 8 * (rec_w + lg_w), P, C,
                                      report_k, stream, cand_off=a.cand_off, widths=pd)
@@ -1281,8 +1299,209 @@ class Engine(object):
             res.extend(self._joint_report_host(rep, P, report_k, pd))
         return tuple(res)
 
+    @staticmethod
+    def _seg_parts(m):
+        """(below, above, low, high, cats, quants) of one group of
+        run_joint_segments: a model object or a tuple of 4, 5 or 6 entries;
+        below / above = (w, mu, sigma)."""
+        if hasattr(m, 'below'):
+            cats = m.cats() if hasattr(m, 'drows') else []
+            quants = m.quants() if hasattr(m, 'qrows') else []
+            return m.below[:3], m.above[:3], m.low, m.high, cats, quants
+        m = tuple(m)
+        return m[0][:3], m[1][:3], m[2], m[3], list(m[4]) if len(m) > 4 else [], list(m[5]) if len(m) > 5 else []
+
+    def _mseg_rows(self, below, above, low, high, cats, quants):
+        """The device rows of one group with discrete or quantised labels, as
+        run_joint_mixed / run_joint_quant make them (the same functions of
+        joint.py on the same arguments: the same bytes): a dict of arrays, the
+        per-side ones under 'below_..' / 'above_..'."""
+        from . import joint as J
+        low, high = np.asarray(low, dtype=np.float64).reshape(-1), np.asarray(high, dtype=np.float64).reshape(-1)
+        Dc, Dk, Dq = len(low), len(cats), len(quants)
+        if Dq > N.JOINT_MAX_QUANT:
+            raise ValueError('joint stage: %d quantised dimensions, at most %d' % (Dq, N.JOINT_MAX_QUANT))
+        if Dc > N.JOINT_MSEG_MAX_CONT or Dk > N.JOINT_MSEG_MAX_CAT:
+            raise ValueError('joint stage: a segment with discrete or quantised dimensions holds at most %d continuous '
+                             'and %d discrete ones, not %d and %d' % (N.JOINT_MSEG_MAX_CONT, N.JOINT_MSEG_MAX_CAT, Dc, Dk))
+        edges = [np.ascontiguousarray(q[4], dtype=np.float64).reshape(-1) for q in quants]
+        for e in edges:
+            if not 2 <= len(e) - 1 <= N.JOINT_MAX_LATTICE:
+                raise ValueError('joint stage: %d lattice values, outside [2, %d]' % (len(e) - 1, N.JOINT_MAX_LATTICE))
+            if not (np.isfinite(e).all() and (np.diff(e) > 0).all()):
+                raise ValueError('joint stage: the lattice edges must be finite and strictly increasing')
+        if sum(len(e) - 1 for e in edges) > N.JOINT_MAX_LATTICE_TOTAL:
+            raise ValueError('joint stage: %d lattice values in the group, at most %d'
+                             % (sum(len(e) - 1 for e in edges), N.JOINT_MAX_LATTICE_TOTAL))
+        ps = [np.asarray(c[2], dtype=np.float64).reshape(-1) for c in cats]
+        for p in ps:
+            if not 2 <= len(p) <= N.JOINT_MAX_CATS:
+                raise ValueError('joint stage: %d categories, outside [2, %d]' % (len(p), N.JOINT_MAX_CATS))
+            if not (p > 0).all():
+                raise ValueError('joint stage: a prior probability of 0')
+        if sum(len(p) for p in ps) > N.JOINT_MAX_CAT_TOTAL:
+            raise ValueError('joint stage: %d categories in the group, at most %d'
+                             % (sum(len(p) for p in ps), N.JOINT_MAX_CAT_TOTAL))
+        s_side = [np.array([float(c[3 + i]) for c in cats]) for i in (0, 1)]
+        if not all((s > 0).all() and np.isfinite(s).all() for s in s_side):
+            raise ValueError('joint stage: the smoothing masses must be positive')
+        r = dict(Dc=Dc, Dk=Dk, Dq=Dq, low=low, high=high, ps=ps, edges=edges)
+        sides = []
+        for i, (name, side) in enumerate((('below', below), ('above', above))):
+            w = np.asarray(side[0], dtype=np.float64)
+            mu = np.asarray(side[1], dtype=np.float64).reshape(len(w), -1)
+            sigma = np.asarray(side[2], dtype=np.float64).reshape(len(w), -1)
+            if mu.shape != (len(w), Dc) or sigma.shape != mu.shape:
+                raise ValueError('joint stage: mixture shapes do not match %d dimensions' % Dc)
+            cols = [np.asarray(c[i], dtype=np.int64).reshape(-1) for c in cats]
+            qmu = [np.asarray(q[2 * i], dtype=np.float64).reshape(-1) for q in quants]
+            qsig = [np.asarray(q[2 * i + 1], dtype=np.float64).reshape(-1) for q in quants]
+            if any(len(col) != len(w) for col in cols + qmu + qsig):
+                raise ValueError('joint stage: one category / (mu, sigma) per component and dimension')
+            for d, col in enumerate(cols):
+                if col.min() < -1 or col.max() >= len(ps[d]):
+                    raise ValueError('joint stage: a component category outside [-1, %d)' % len(ps[d]))
+            xc = np.stack(cols, axis=1) if cols else np.zeros((len(w), 0), dtype=np.int64)
+            if Dk:
+                mu32, aa, c, base, cat32, miss, bonus = J.mixed_density_rows(w, mu, sigma, low, high, xc, ps, s_side[i])
+                r[name + '_cat'], r[name + '_miss'], r[name + '_bonus'] = cat32, miss, bonus
+            else:
+                mu32, aa, c, base = J.density_rows(w, mu, sigma, low, high)
+            r[name + '_mu'], r[name + '_a'], r[name + '_c'], r[name + '_base'] = mu32, aa, c, base
+            if Dq:
+                qsig = np.stack(qsig, axis=1)
+                if not ((qsig > 0).all() and np.isfinite(qsig).all()):
+                    raise ValueError('joint stage: the quantised bandwidths must be positive')
+                r[name + '_qmu'], r[name + '_qsigma'] = np.stack(qmu, axis=1), qsig
+            sides.append((w, mu, sigma))
+        w, mu, sigma = sides[0]
+        if Dk:
+            r['cum'], r['samp'], r['below_h'], r['cat_cum'] = J.mixed_sampler_rows(w, mu, sigma, low, high, ps, s_side[0])
+        else:
+            r['cum'], r['samp'] = J.sampler_rows(w, mu, sigma, low, high)
+        if Dq:
+            qlow, qhigh = np.array([e[0] for e in edges]), np.array([e[-1] for e in edges])
+            r['quant_samp'] = J.sampler_rows(w, r['below_qmu'], r['below_qsigma'], qlow, qhigh)[1]
+            r['qlo'], r['qhi'] = J.f32_bounds(qlow, qhigh)
+        return r
+
+    def _run_joint_msegments(self, models, stream_words, prob_seg, prob_id, n_cand, seed, inject, return_cand,
+                             want_lg, report_k):
+        """run_joint_segments through tpe_joint_mseg_run: every group, whatever
+        its kind, packed into the two pools behind one array of tpe_joint_mseg."""
+        from . import joint as J
+        S, C = len(models), int(n_cand)
+        report_k = self._report_k(report_k)
+        prob_seg = np.ascontiguousarray(prob_seg, dtype=np.int32).reshape(-1)
+        prob_id = np.ascontiguousarray(prob_id, dtype=np.int64).reshape(-1)
+        P = len(prob_seg)
+        if S < 1 or len(stream_words) != S:
+            raise ValueError('joint stage: one stream word per group, at least one group')
+        if P < 1 or len(prob_id) != P or C < 1 or C >= 2 ** 31:
+            raise ValueError('joint stage: n_cand / problems out of range')
+        if prob_seg.min() < 0 or prob_seg.max() >= S:
+            raise ValueError('joint stage: a problem names a group outside [0, %d)' % S)
+        if inject is not None and len(inject) != S:
+            raise ValueError('joint stage: inject must hold one entry per group')
+        segs = np.zeros(S, dtype=N.JOINT_MSEG_DTYPE)
+        pools = {4: [], 8: []}
+        fill = {4: 0, 8: 0}
+
+        def put(arr, dtype):
+            arr = np.ascontiguousarray(arr, dtype=dtype).reshape(-1)
+            size = arr.dtype.itemsize
+            pools[size].append(arr)
+            fill[size] += arr.size
+            return fill[size] - arr.size
+        dims = np.empty(S, dtype=np.int64)
+        n_table = 0
+        for s, m in enumerate(models):
+            below, above, low, high, cats, quants = self._seg_parts(m)
+            g = segs[s]
+            g['stream_word'] = int(stream_words[s])
+            g['lo'], g['hi'] = np.float32(-np.inf), np.float32(np.inf)
+            g['qlo'], g['qhi'] = np.float32(-np.inf), np.float32(np.inf)
+            if not cats and not quants:                  # a continuous group: run_joint_segments' rows
+                low, high = np.asarray(low, dtype=np.float64), np.asarray(high, dtype=np.float64)
+                Dc, Dk, Dq = len(low), 0, 0
+                if not 1 <= Dc <= N.JOINT_MAX_DIMS:
+                    raise ValueError('joint stage: %d dimensions, at most %d' % (Dc, N.JOINT_MAX_DIMS))
+                r = dict(low=low, high=high)
+                for name, side in (('below', below), ('above', above)):
+                    if side[1].shape != (len(side[0]), Dc) or side[2].shape != side[1].shape:
+                        raise ValueError('joint stage: mixture shapes do not match %d dimensions' % Dc)
+                    r[name + '_mu'], r[name + '_a'], r[name + '_c'], r[name + '_base'] = J.density_rows(
+                        side[0], side[1], side[2], low, high)
+                r['cum'], r['samp'] = J.sampler_rows(below[0], below[1], below[2], low, high)
+            else:
+                r = self._mseg_rows(below, above, low, high, cats, quants)
+                Dc, Dk, Dq = r['Dc'], r['Dk'], r['Dq']
+            D = dims[s] = Dc + Dk + Dq
+            g['n_dims'], g['n_cat'], g['n_quant'] = Dc, Dk, Dq
+            g['k_below'], g['k_above'] = len(r['below_c']), len(r['above_c'])
+            for name in ('below', 'above'):
+                for f in ('_mu', '_a', '_c'):
+                    g[name + f] = put(r[name + f], np.float32)
+                g[name + '_base'] = r[name + '_base']
+                if Dk:
+                    for f in ('_cat', '_miss', '_bonus'):
+                        g[name + f] = put(r[name + f], np.float32)
+                if Dq:
+                    g[name + '_qmu'], g[name + '_qsigma'] = put(r[name + '_qmu'], np.float64), put(r[name + '_qsigma'],
+                                                                                                   np.float64)
+            g['samp'], g['samp_cum'] = put(r['samp'], np.float32), put(r['cum'], np.float64)
+            g['lo'][:Dc], g['hi'][:Dc] = J.f32_bounds(r['low'], r['high'])
+            if Dk:
+                g['below_h'], g['cat_cum'] = put(r['below_h'], np.float64), put(r['cat_cum'], np.float64)
+                ups = [len(p) for p in r['ps']]
+                g['cat_upper'][:Dk], g['cat_off'][:Dk] = ups, np.cumsum([0] + ups[:-1])
+            if Dq:
+                vs = [len(e) - 1 for e in r['edges']]
+                g['quant_v'][:Dq], g['quant_edge_off'][:Dq] = vs, np.cumsum([0] + [v + 1 for v in vs[:-1]])
+                g['quant_edges'], g['n_edges'] = put(np.concatenate(r['edges']), np.float64), sum(vs) + Dq
+                g['quant_samp'] = put(r['quant_samp'], np.float32)
+                g['qlo'][:Dq], g['qhi'][:Dq] = r['qlo'], r['qhi']
+                g['table'] = n_table
+                n_table += (int(g['k_below']) + int(g['k_above'])) * sum(vs)
+            g['inject'] = -1
+            if inject is not None and inject[s] is not None:
+                inj = np.ascontiguousarray(inject[s], dtype=np.float32)
+                if inj.shape != (C, D):
+                    raise ValueError('joint stage: inject must be [n_cand, %d]' % D)
+                g['inject'] = put(inj, np.float32)
+        if inject is not None and any(inject[s] is None for s in np.unique(prob_seg)):
+            raise ValueError('joint stage: inject lacks the candidates of a group that has a problem')
+        pd = dims[prob_seg]
+        cand_off = np.concatenate([[0], np.cumsum(C * pd)]).astype(np.int64)
+        if P * C >= 2 ** 31 or cand_off[-1] >= 2 ** 31:
+            raise ValueError('joint stage: %d problems x %d candidates do not fit one run' % (P, C))
+
+        # one blob: 8-byte items first (descriptors, the f64 pool, ids, offsets), then the 4-byte ones
+        parts = [segs.view(np.uint8), np.concatenate(pools[8]).view(np.uint8), prob_id.view(np.uint8),
+                 cand_off[:P].view(np.uint8), np.concatenate(pools[4]).view(np.uint8), prob_seg.view(np.uint8)]
+        offs = np.concatenate([[0], np.cumsum([len(x) for x in parts])])
+        blob = np.concatenate(parts)
+        d_blob = self._buf('joint_seg_blob', len(blob), torch.uint8)
+        d_blob[:len(blob)].copy_(torch.from_numpy(blob))
+        base = d_blob.data_ptr()
+        a = N.JointMSegArgs()
+        a.n_segs, a.n_probs, a.n_cand, a.flags = S, P, C, N.JOINT_INJECT if inject is not None else 0
+        a.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        a.segs, a.host_segs = base + int(offs[0]), segs.ctypes.data
+        a.pool_f64, a.prob_id, a.cand_off = base + int(offs[1]), base + int(offs[2]), base + int(offs[3])
+        a.pool_f32, a.prob_seg, a.host_prob_seg = base + int(offs[4]), base + int(offs[5]), prob_seg.ctypes.data
+        a.pool_f32_len, a.pool_f64_len = fill[4], fill[8]
+        nb = ctypes.c_uint64(0)
+        N.check(self.lib.tpe_joint_mseg_table_bytes(segs.ctypes.data, S, ctypes.byref(nb)), self.lib,
+                'tpe_joint_mseg_table_bytes')
+        assert nb.value == 4 * n_table, (nb.value, n_table)
+        if n_table:
+            d_tab = self._buf('joint_mseg_table', n_table, torch.float32)
+            a.quant_table, a.quant_table_bytes = d_tab.data_ptr(), d_tab.numel() * 4
+        return self._joint_seg_call('tpe_joint_mseg', a, P, C, cand_off, pd, return_cand, want_lg, report_k)
+
     def run_joint_mixed(self, below, above, low, high, cats, ids, n_cand, seed, inject=None, return_cand=False,
-                        want_lg=False, report_k=0):
+                        want_lg=False, report_k=0, stream_word=None):
         """One joint stage over a mixed group (tpe_joint_mixed_run,
         include/tpe_hip.h "Mixed joint stage"): ``below`` / ``above`` = (w [K],
         mu [K, Dc], sigma [K, Dc]) the continuous part as in ``run_joint`` (Dc
@@ -1290,7 +1509,9 @@ class Engine(object):
         s_below, s_above) per discrete dimension: the components' categories
         (-1: the prior row), the prior and the two smoothing masses.  Kernel
         coordinates: the Dc continuous ones, then the categories as indices;
-        ``inject`` [C, Dc + Dk], candidates f32 [n_ids, C, Dc + Dk]."""
+        ``inject`` [C, Dc + Dk], candidates f32 [n_ids, C, Dc + Dk].
+        ``stream_word``: the Philox stream word (None: N.JOINT_STREAM; a branch
+        group's joint.branch_stream_word, to compare with run_joint_segments)."""
         from . import joint as J
         low, high = np.asarray(low, dtype=np.float64).reshape(-1), np.asarray(high, dtype=np.float64).reshape(-1)
         Dc, Dk = len(low), len(cats)
@@ -1330,7 +1551,8 @@ class Engine(object):
         a = N.JointMixedArgs()
         a.n_dims, a.n_cat, a.n_cand, a.n_ids, a.flags = Dc, Dk, C, n_ids, 0
         a.k_below, a.k_above = len(sides[0][0]), len(sides[1][0])
-        a.stream_word, a.seed = N.JOINT_STREAM, int(seed) & 0xFFFFFFFFFFFFFFFF
+        a.stream_word = N.JOINT_STREAM if stream_word is None else int(stream_word)
+        a.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         for i, name in enumerate(('below', 'above')):
             w, mu, sigma, xc = sides[i]
             mu32, aa, c, base, cat32, miss, bonus = J.mixed_density_rows(w, mu, sigma, low, high, xc, ps, s_side[i])
@@ -1355,7 +1577,7 @@ class Engine(object):
         return self._joint_call('tpe_joint_mixed_run', a, n_ids, C, D, return_cand, want_lg, report_k=report_k)
 
     def run_joint_quant(self, below, above, low, high, cats, quants, ids, n_cand, seed, inject=None, return_cand=False,
-                        want_lg=False, return_table=False, report_k=0):
+                        want_lg=False, return_table=False, report_k=0, stream_word=None):
         """One joint stage over a group with quantised labels
         (tpe_joint_quant_run, include/tpe_hip.h "Quantised joint stage"):
         ``below`` / ``above``, ``low`` / ``high`` and ``cats`` the continuous and
@@ -1366,7 +1588,8 @@ class Engine(object):
         coordinates: the Dc continuous ones, the Dk categories, then the Dq
         lattice indices; ``inject`` [C, Dc + Dk + Dq], candidates f32 [n_ids, C,
         Dc + Dk + Dq].  ``return_table`` (debug): also the two sides' tables
-        log2 P as the device built them, f32 [K, sum V] each."""
+        log2 P as the device built them, f32 [K, sum V] each.  ``stream_word``: as
+        in ``run_joint_mixed``."""
         from . import joint as J
         low, high = np.asarray(low, dtype=np.float64).reshape(-1), np.asarray(high, dtype=np.float64).reshape(-1)
         Dc, Dk, Dq = len(low), len(cats), len(quants)
@@ -1427,7 +1650,8 @@ class Engine(object):
         a = N.JointQuantArgs()
         a.n_dims, a.n_cat, a.n_quant, a.n_cand, a.n_ids, a.flags = Dc, Dk, Dq, C, n_ids, 0
         a.k_below, a.k_above = len(sides[0][0]), len(sides[1][0])
-        a.stream_word, a.seed = N.JOINT_STREAM, int(seed) & 0xFFFFFFFFFFFFFFFF
+        a.stream_word = N.JOINT_STREAM if stream_word is None else int(stream_word)
+        a.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         for i, name in enumerate(('below', 'above')):
             w, mu, sigma, xc, qmu, qsig = sides[i]
             if Dk:

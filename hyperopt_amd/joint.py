@@ -120,7 +120,8 @@ def f32_bounds(low, high):
 
 def branch_stream_word(rows):
     """The Philox stream word of a branch group (DESIGN.md "Branch groups"):
-    0xFFFFFFFE - the lowest table index among its labels.  It depends on the
+    0xFFFFFFFE - the lowest table index among its labels (all of them: the
+    discrete and quantised ones of a widened group too).  It depends on the
     space alone, differs between groups (a label is in one group), and is at
     least 2^31, so it equals no univariate label index and not N.JOINT_STREAM."""
     return 0xFFFFFFFE - min(r.index for r in rows)
@@ -195,9 +196,11 @@ def fit_model(rows, hist, below_tids, prior_weight=1.0, lf=DEFAULT_LF):
 DISCRETE_DISTS = ('randint', 'categorical')
 
 
-def discrete_reason(row, table):
-    """Why ``row`` cannot be joined as a discrete dimension, or None if it can."""
-    if not all(p is None for p in row.parents) or row.depth != 0:
+def discrete_reason(row, table, conditional=False):
+    """Why ``row`` cannot be joined as a discrete dimension, or None if it can.
+    ``conditional``: the label may be conditional (a branch group's label,
+    tpe.suggest_choices' ``joint_branches_mixed``); every other test holds."""
+    if not conditional and (not all(p is None for p in row.parents) or row.depth != 0):
         return 'conditional (%s)' % row.dist
     if row.dist.startswith('q'):
         return 'a quantised label (%s)' % row.dist
@@ -444,9 +447,10 @@ def quant_lattice(dist, args):
     return m_lo, V, q, edges
 
 
-def quant_reason(row, table):
-    """Why ``row`` cannot be joined as a quantised dimension, or None if it can."""
-    if not all(p is None for p in row.parents) or row.depth != 0:
+def quant_reason(row, table, conditional=False):
+    """Why ``row`` cannot be joined as a quantised dimension, or None if it can
+    (``conditional``: as in discrete_reason)."""
+    if not conditional and (not all(p is None for p in row.parents) or row.depth != 0):
         return 'conditional (%s)' % row.dist
     if row.dist in ('qnormal', 'qlognormal'):
         return ('%s: its lattice is unbounded and data-dependent, so eligibility could not be decided before the fit'

@@ -41,7 +41,9 @@ Extensions over the reference (keyword-only, defaults keep its behaviour):
     ``joint_wide=True`` 17 to 64 continuous labels instead of at most 16.
     ``joint_branches=True`` also joins the continuous labels of every
     conditional branch, one group per (gate, option), each id under the model
-    of the branch it takes (DESIGN.md "Branch groups").
+    of the branch it takes (DESIGN.md "Branch groups");
+    ``joint_branches_mixed=True`` lets joint_discrete / joint_quantized widen
+    those branch groups too.
 
 ``linear_forgetting`` is accepted and, as in the reference, not used: the
 forgetting window is fixed at DEFAULT_LF=25 (tpe.py:27-29).
@@ -840,14 +842,15 @@ def suggest(new_ids, domain, trials, seed,
             linear_forgetting=_default_linear_forgetting,
             sampler='philox', precision='fp32', device=None, shard=None, shard_ids=None, shard_labels=None,
             shard_grid=None, joint=False, joint_discrete=False, joint_quantized=False, joint_wide=False,
-            joint_branches=False):
+            joint_branches=False, joint_branches_mixed=False):
     new_ids = list(new_ids)
     if not new_ids:
         return []
-    if (joint is not False and joint is not None) or joint_discrete or joint_quantized or joint_wide or joint_branches:
+    if ((joint is not False and joint is not None) or joint_discrete or joint_quantized or joint_wide or joint_branches
+            or joint_branches_mixed):
         # (argument errors first: no device use, no startup draw)
         _joint_plan(domain.table, joint, sampler, precision, (shard, shard_ids, shard_labels, shard_grid),
-                    joint_discrete, joint_quantized, joint_wide, joint_branches)
+                    joint_discrete, joint_quantized, joint_wide, joint_branches, joint_branches_mixed)
     t0 = time.time()
     hist = _history.extract(domain, trials)
     if logger.isEnabledFor(logging.INFO):
@@ -863,7 +866,7 @@ def suggest(new_ids, domain, trials, seed,
                               precision=precision, device=device, shard=shard, shard_ids=shard_ids,
                               shard_labels=shard_labels, shard_grid=shard_grid, joint=joint,
                               joint_discrete=joint_discrete, joint_quantized=joint_quantized, joint_wide=joint_wide,
-                              joint_branches=joint_branches)
+                              joint_branches=joint_branches, joint_branches_mixed=joint_branches_mixed)
     logger.info('tpe.suggest took %f seconds', time.time() - t0)
     return rand.docs_from_choices(new_ids, domain, trials, choices)
 
@@ -904,7 +907,7 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
                     n_EI_candidates=_default_n_EI_candidates, gamma=_default_gamma,
                     sampler='philox', precision='fp32', device=None, shard=None, columns=False,
                     shard_ids=None, shard_labels=None, shard_grid=None, joint=False, joint_discrete=False,
-                    joint_quantized=False, joint_wide=False, joint_branches=False):
+                    joint_quantized=False, joint_wide=False, joint_branches=False, joint_branches_mixed=False):
     """The suggest core on a structure-of-arrays history (``history.History``):
     per new id a {label: value or None} dict.  ``suggest`` wraps it with the
     Trials document layout; columnar callers (and bench.py's large configs)
@@ -967,14 +970,35 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
     univariate.  Per new id a branch group's winner replaces its labels' values
     only where the branch is taken; every other value, the gates' included, is
     the same bytes as without ``joint``.  All branch groups of a suggest are
-    scored by one segmented device stage (Engine.run_joint_segments)."""
+    scored by one segmented device stage (Engine.run_joint_segments).
+
+    ``joint_branches_mixed=True`` (with ``joint_branches``): the other keywords
+    widen the branch groups too (DESIGN.md "Discrete and quantised labels in
+    branch groups").  ``joint_discrete`` then also admits a conditional
+    ``randint`` / ``categorical`` label that has exactly one parent (gate,
+    option), gates nothing, has 2 to 256 categories and no prior probability 0;
+    ``joint_quantized`` a conditional ``quniform`` / ``qloguniform`` label with
+    exactly one parent, q > 0 and 2 to 256 lattice values; a list may name such
+    labels (each joins the part of its condition; an ineligible one raises
+    ValueError).  A branch group that holds a discrete or quantised label takes
+    at most 8 continuous, 4 discrete and 4 quantised labels, 1024 categories and
+    512 lattice values in all (these bound the set of compiled kernels; they are
+    not measurements; more raises ValueError); a group of continuous labels only
+    keeps its limit of 16 and its path.  A group's kernel coordinates are its
+    continuous, discrete, then quantised labels, and its Philox stream word
+    comes from ALL its labels: a branch whose lowest-index label is discrete or
+    quantised draws its continuous coordinates from another stream than without
+    the keyword.  A joined category is typed as the univariate path types it, a
+    quantised value is a multiple of q.  Without the keyword every plan and
+    every output byte is what ``joint_branches`` alone gives."""
     if sampler not in ('philox', 'replay'):
         raise ValueError("sampler must be 'philox' or 'replay'")
     group, branch_groups = None, []
-    if (joint is not False and joint is not None) or joint_discrete or joint_quantized or joint_wide or joint_branches:
+    if ((joint is not False and joint is not None) or joint_discrete or joint_quantized or joint_wide or joint_branches
+            or joint_branches_mixed):
         group, branch_groups = _joint_plan(table, joint, sampler, precision,
                                            (shard, shard_ids, shard_labels, shard_grid), joint_discrete,
-                                           joint_quantized, joint_wide, joint_branches)
+                                           joint_quantized, joint_wide, joint_branches, joint_branches_mixed)
     if sum(a is not None for a in (shard, shard_ids, shard_labels, shard_grid)) > 1:
         raise ValueError('shard, shard_ids, shard_labels and shard_grid are exclusive: one shard axis per suggest')
     if (shard_ids is not None or shard_labels is not None or shard_grid is not None) and sampler == 'replay':
@@ -1009,9 +1033,11 @@ def _joint_group(table, joint, sampler, precision, shards, discrete=False, quant
 
 
 def _joint_restrictions(joint, sampler, precision, shards, discrete=False, quantized=False, wide=False,
-                        branches=False):
+                        branches=False, branch_mixed=False):
     """ValueError for a keyword without ``joint`` and for the sampler, precision
     and shard arguments the joint stage does not combine with."""
+    if branch_mixed and not branches:
+        raise ValueError('joint_branches_mixed=True needs joint_branches=True: it only widens the branch groups')
     if branches and (joint is False or joint is None):
         raise ValueError('joint_branches=True needs joint=True or joint=[labels]: it only widens what joint joins')
     if wide and (joint is False or joint is None):
@@ -1116,6 +1142,59 @@ def _branch_key(row):
     return None
 
 
+def _branch_condition(row):
+    """(gate label, option) of a label under exactly one condition, else None."""
+    if len(row.parents) == 1 and row.parents[0] is not None:
+        return tuple(row.parents[0])
+    return None
+
+
+def _branch_mixed_reason(row, table, discrete, quantized):
+    """Why a conditional ``row`` joins no branch group under
+    ``joint_branches_mixed``, or None if it joins the group of its condition."""
+    if _branch_key(row) is not None:
+        return None
+    if quantized and row.dist.startswith('q'):
+        why = _joint.quant_reason(row, table, conditional=True)
+    elif discrete and row.categorical:
+        why = _joint.discrete_reason(row, table, conditional=True)
+    else:
+        return 'not a label that the joint keywords given admit to a branch group (%s)' % row.dist
+    if why is None and _branch_condition(row) is None:
+        why = ('it has %d parents: a label that several branches share belongs to no single branch group'
+               % len(row.parents))
+    return why
+
+
+def _branch_mixed_limit(key, rows):
+    """``rows`` of the branch group under ``key``, or ValueError where it
+    exceeds what the segmented stage takes: a group with a discrete or
+    quantised label is bound by the quantised stage's limits (they bound the
+    set of compiled kernels), a continuous one by _branch_limit."""
+    crows, drows, qrows = _joint_kernel_order(rows)
+    if not drows and not qrows:
+        return _branch_limit(key, rows)
+    head = 'joint with joint_branches_mixed=True: the branch group under option %d of gate %r has ' % (key[1], key[0])
+    tail = ': pass the labels to join as joint=[...]'
+    n_cats = sum(int(r.args['upper']) for r in drows)
+    n_lat = sum(_joint.lattice_size(r.dist, r.args)[1] for r in qrows)
+    if len(crows) > N.JOINT_QUANT_MAX_CONT:
+        raise ValueError('%s%d continuous labels beside a discrete or quantised one, more than %d%s'
+                         % (head, len(crows), N.JOINT_QUANT_MAX_CONT, tail))
+    if len(drows) > N.JOINT_QUANT_MAX_DISC:
+        raise ValueError('%s%d discrete labels, more than %d%s' % (head, len(drows), N.JOINT_QUANT_MAX_DISC, tail))
+    if len(qrows) > N.JOINT_MAX_QUANT:
+        raise ValueError('%s%d quantised labels, more than TPE_JOINT_MAX_QUANT = %d%s'
+                         % (head, len(qrows), N.JOINT_MAX_QUANT, tail))
+    if n_cats > N.JOINT_MAX_CAT_TOTAL:
+        raise ValueError('%s%d categories in all, more than TPE_JOINT_MAX_CAT_TOTAL = %d%s'
+                         % (head, n_cats, N.JOINT_MAX_CAT_TOTAL, tail))
+    if n_lat > N.JOINT_MAX_LATTICE_TOTAL:
+        raise ValueError('%s%d lattice values in all, more than TPE_JOINT_MAX_LATTICE_TOTAL = %d%s'
+                         % (head, n_lat, N.JOINT_MAX_LATTICE_TOTAL, tail))
+    return rows
+
+
 def _branch_limit(key, rows):
     if len(rows) > TPE_JOINT_MAX_DIMS:
         raise ValueError('joint with joint_branches=True: the branch group under option %d of gate %r has %d labels, '
@@ -1125,42 +1204,65 @@ def _branch_limit(key, rows):
 
 
 def _joint_plan(table, joint, sampler, precision, shards, discrete=False, quantized=False, wide=False,
-                branches=False):
+                branches=False, branch_mixed=False):
     """(root group or None, branch groups) of a ``joint`` argument.  Without
     ``branches``: (_joint_group(...), []).  With it (DESIGN.md "Branch
     groups"): the root group as _joint_group forms it, or None where fewer than
     2 unconditional labels are joined, and one list of ParamRows (table order)
     per condition with 2 to TPE_JOINT_MAX_DIMS joined labels, ordered by their
-    first label.  ValueError as _joint_group; touches no device."""
+    first label.  ``branch_mixed``: ``discrete`` / ``quantized`` also admit
+    conditional discrete / quantised labels with exactly one parent to the
+    group of their condition (_branch_mixed_reason, _branch_mixed_limit).
+    ValueError as _joint_group; touches no device."""
     if not branches:
+        if branch_mixed:
+            raise ValueError('joint_branches_mixed=True needs joint_branches=True: it only widens the branch groups')
         return _joint_group(table, joint, sampler, precision, shards, discrete, quantized, wide), []
-    _joint_restrictions(joint, sampler, precision, shards, discrete, quantized, wide, True)
+    _joint_restrictions(joint, sampler, precision, shards, discrete, quantized, wide, True, branch_mixed)
     parts = {}
+    limit = _branch_mixed_limit if branch_mixed else _branch_limit
+
+    def conditional(r):
+        return any(p is not None for p in r.parents)
     if joint is True:
         root = _joint_rows(table, True, discrete, quantized)
         for r in table.rows:
             key = _branch_key(r)
+            if key is None and branch_mixed and conditional(r) and \
+                    _branch_mixed_reason(r, table, discrete, quantized) is None:
+                key = _branch_condition(r)
             if key is not None:
                 parts.setdefault(key, []).append(r)
-        groups = [_branch_limit(key, rows) for key, rows in parts.items() if len(rows) >= 2]
+        groups = [limit(key, rows) for key, rows in parts.items() if len(rows) >= 2]
         root = root if len(root) >= 2 else None
     else:
         if isinstance(joint, str):
             raise ValueError('joint must be True or a list of labels, not the string %r' % joint)
         want = list(joint)
         named = set(label for label in want if label in table.by_label and _branch_key(table.by_label[label]))
+        if branch_mixed:
+            for label in want:
+                r = table.by_label.get(label)
+                if r is None or label in named or not conditional(r):
+                    continue
+                if (quantized and r.dist.startswith('q')) or (discrete and r.categorical):
+                    why = _branch_mixed_reason(r, table, discrete, quantized)
+                    if why is not None:
+                        raise ValueError('joint: label %r is not eligible with joint_branches_mixed=True: %s'
+                                         % (label, why))
+                    named.add(label)
         root = _joint_rows(table, [label for label in want if label not in named], discrete, quantized)
         if len(root) == 1:
             raise ValueError('joint with joint_branches=True: %r is the only unconditional label named: a group needs '
                              'at least 2 labels' % root[0].label)
         for r in table.rows:
             if r.label in named:
-                parts.setdefault(_branch_key(r), []).append(r)
+                parts.setdefault(_branch_condition(r), []).append(r)
         for key, rows in parts.items():
             if len(rows) == 1:
                 raise ValueError('joint with joint_branches=True: %r is the only label named under option %d of gate '
                                  '%r: a group needs at least 2 labels' % (rows[0].label, key[1], key[0]))
-        groups = [_branch_limit(key, rows) for key, rows in parts.items()]
+        groups = [limit(key, rows) for key, rows in parts.items()]
         root = root or None
     if root is None and not groups:
         raise ValueError('joint needs at least 2 labels to join in one group (the unconditional labels, or the labels '
@@ -1226,6 +1328,19 @@ def _suggest_joint(table, hist, new_ids, seed, prior_weight, n_EI_candidates, ga
     return cc if columns else cc.dicts(table)
 
 
+def _fit_branch_model(rows, hist, below_tids, prior_weight):
+    """(the branch group in kernel coordinate order, its model): a JointModel
+    for continuous labels, a MixedModel with discrete labels, a QuantModel with
+    quantised ones — each fitted on the trials that took the branch."""
+    crows, drows, qrows = _joint_kernel_order(rows)
+    if qrows:
+        return crows + drows + qrows, _joint.fit_quant_model(crows, drows, qrows, hist, below_tids, prior_weight,
+                                                              DEFAULT_LF)
+    if drows:
+        return crows + drows, _joint.fit_mixed_model(crows, drows, hist, below_tids, prior_weight, DEFAULT_LF)
+    return rows, _joint.fit_model(rows, hist, below_tids, prior_weight, DEFAULT_LF)
+
+
 def _suggest_branches(engine, hist, ids, seed, prior_weight, n_EI_candidates, gamma, branch_groups, taken, values):
     """The segmented joint stage of a suggest: one problem per (new id, branch
     group whose labels are active for it in ``taken`` [n_ids x n_labels]), all
@@ -1242,8 +1357,9 @@ def _suggest_branches(engine, hist, ids, seed, prior_weight, n_EI_candidates, ga
             continue
         prob_seg.extend([len(models)] * len(js))
         prob_id.extend(ids[js])
+        rows, model = _fit_branch_model(rows, hist, below_tids, prior_weight)
         where.append((rows, js))
-        models.append(_joint.fit_model(rows, hist, below_tids, prior_weight, DEFAULT_LF))
+        models.append(model)
         words.append(_joint.branch_stream_word(rows))
     if not models:
         return
@@ -1556,14 +1672,14 @@ def _joint_group_report(rows, condition, model, top, z, n_top, stats):
 def joint_candidate_report_columns(table, hist, new_id, seed, k=8, joint=True, joint_discrete=False,
                                    joint_quantized=False, joint_wide=False, joint_branches=False,
                                    prior_weight=_default_prior_weight, n_EI_candidates=_default_n_EI_candidates,
-                                   gamma=_default_gamma, device=None):
+                                   gamma=_default_gamma, device=None, joint_branches_mixed=False):
     """``joint_candidate_report`` on a structure-of-arrays history (as
     ``candidate_report_columns`` is to ``candidate_report``)."""
     k = _report_check_k(k)
     if joint is False or joint is None:
         raise ValueError('joint_candidate_report needs joint=True or joint=[labels]')
     group, branch_groups = _joint_plan(table, joint, 'philox', 'fp32', (None, None, None, None), joint_discrete,
-                                       joint_quantized, joint_wide, joint_branches)
+                                       joint_quantized, joint_wide, joint_branches, joint_branches_mixed)
     if len(hist) == 0:
         raise ValueError('joint_candidate_report needs a history: no completed trial to fit the models from')
     C = int(n_EI_candidates)
@@ -1583,20 +1699,22 @@ def joint_candidate_report_columns(table, hist, new_id, seed, k=8, joint=True, j
         below_tids = _history.split_below(hist, gamma)
         per_run = max(1, REPORT_MAX_RUN_CANDIDATES // C)
         for lo in range(0, len(branch_groups), per_run):
-            part = branch_groups[lo:lo + per_run]
-            models = [_joint.fit_model(rows, hist, below_tids, prior_weight, DEFAULT_LF) for rows in part]
+            fits = [_fit_branch_model(rows, hist, below_tids, prior_weight) for rows in branch_groups[lo:lo + per_run]]
+            part, models = [f[0] for f in fits], [f[1] for f in fits]
             words = [_joint.branch_stream_word(rows) for rows in part]
             out = engine.run_joint_segments(models, words, np.arange(len(part)), np.repeat(ids, len(part)), C, seed,
                                             report_k=k)
             top, z, nt, st = out[-4:]
             for p, (rows, model) in enumerate(zip(part, models)):
-                groups.append(_joint_group_report(rows, _branch_key(rows[0]), model, top[p], z[p], nt[p], st[p]))
+                groups.append(_joint_group_report(rows, _branch_condition(rows[0]), model, top[p], z[p], nt[p],
+                                                  st[p]))
     return JointCandidateReport(groups)
 
 
 def joint_candidate_report(new_id, domain, trials, seed, k=8, joint=True, joint_discrete=False, joint_quantized=False,
                            joint_wide=False, joint_branches=False, prior_weight=_default_prior_weight,
-                           n_EI_candidates=_default_n_EI_candidates, gamma=_default_gamma, device=None):
+                           n_EI_candidates=_default_n_EI_candidates, gamma=_default_gamma, device=None,
+                           joint_branches_mixed=False):
     """The candidate pools behind the joint stages of a ``suggest([new_id],
     domain, trials, seed, joint=..., n_EI_candidates=...)`` with the same joint
     keywords: per joint group the ``k`` best distinct candidate vectors with
@@ -1611,12 +1729,12 @@ def joint_candidate_report(new_id, domain, trials, seed, k=8, joint=True, joint_
     k = _report_check_k(k)
     if joint is not False and joint is not None:
         _joint_plan(domain.table, joint, 'philox', 'fp32', (None, None, None, None), joint_discrete, joint_quantized,
-                    joint_wide, joint_branches)          # (argument errors before the history is read)
+                    joint_wide, joint_branches, joint_branches_mixed)   # (argument errors before the history is read)
     hist = _history.extract(domain, trials)
     return joint_candidate_report_columns(domain.table, hist, new_id, seed, k=k, joint=joint,
                                           joint_discrete=joint_discrete, joint_quantized=joint_quantized,
                                           joint_wide=joint_wide, joint_branches=joint_branches,
-                                          prior_weight=prior_weight, n_EI_candidates=n_EI_candidates, gamma=gamma,
+                                          joint_branches_mixed=joint_branches_mixed, prior_weight=prior_weight, n_EI_candidates=n_EI_candidates, gamma=gamma,
                                           device=device)
 
 

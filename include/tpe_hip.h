@@ -1488,6 +1488,120 @@ int tpe_joint_seg_run(const tpe_joint_seg_args* args, tpe_joint_record* records,
                       double* g_out, void* scratch, uint64_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Mixed segmented joint stage (tpe_joint.hip; additive to ABI 24): the
+ * segmented stage for groups that may also hold discrete and quantised labels
+ * (DESIGN.md "Discrete and quantised labels in branch groups").  A segment is
+ * a group of tpe_joint_quant_args' kind: n_dims continuous, n_cat discrete and
+ * n_quant quantised coordinates in that kernel order.  tpe_joint_mseg starts
+ * with the fields of tpe_joint_seg at the same offsets (n_dims counts the
+ * continuous coordinates; `inject` rows are [n_cand * (n_dims + n_cat +
+ * n_quant)]) and then says, as ELEMENT offsets, where the rest of what
+ * tpe_joint_quant_args carries per group lies:
+ *   pool_f32   below_cat / above_cat [K * n_cat], below_miss / below_bonus /
+ *              above_miss / above_bonus [sum U_d], quant_samp [k_below *
+ *              n_quant * 5] (and, as in tpe_joint_seg, the mu / a / c rows, samp
+ *              and the injected rows)
+ *   pool_f64   below_h [n_cat], cat_cum [sum U_d], quant_edges [n_edges],
+ *              below_qmu / below_qsigma [k_below * n_quant], above_qmu /
+ *              above_qsigma [k_above * n_quant] (and samp_cum)
+ *   cat_upper / cat_off, quant_v / quant_edge_off   as in tpe_joint_quant_args
+ *   lo / hi, qlo / qhi   the f32 clip bounds of the continuous and the quantised
+ *              coordinates (the smallest float >= e_0, the largest float < e_V)
+ *   table      the element offset of the segment's table in `quant_table`, one
+ *              caller-owned device workspace of f32: the below side's [sum V]
+ *              [k_below], then the above side's, (k_below + k_above) sum V
+ *              elements; tpe_joint_mseg_table_bytes gives the bytes of all
+ *              segments laid end to end in descriptor order
+ *
+ * Defining property: the record, the cand rows, l_out and g_out of problem p are
+ * byte for byte those of a solo run over its segment alone with the segment's
+ * stream_word, ids = [prob_id[p]] and the same seed, n_cand and flags:
+ * tpe_joint_quant_run when n_quant > 0, tpe_joint_mixed_run when n_quant = 0 and
+ * n_cat > 0, tpe_joint_run when both are 0.  The order of the problems does not
+ * matter; the same call twice gives the same bytes (plain vector stores, no
+ * atomics).  The device code is the solo stages': their chunk bodies are
+ * __device__ functions that both kinds of kernel call.
+ *
+ * Launches, all on `stream` with no sync between them: k_joint_seg_order (ranks
+ * the problems by kernel class (CP, KP, QP), then segment, then index; the
+ * continuous DP classes are the first eight), k_joint_mseg_qtable (one launch:
+ * T[d][i][k] of every quantised segment and side, k_joint_qtable's arithmetic
+ * and TPE_JOINT_QFLOOR), one chunk launch per class present —
+ * k_joint_seg_chunk<DP>, k_joint_mseg_mixed_chunk<CP, KP> (CP in {0, 2, 4, 8},
+ * KP in {1, 2, 4}) or k_joint_mseg_quant_chunk<CP, KP, QP> (the 48 shapes of
+ * the solo stage) — and k_joint_merge over all problems.  A quantised segment's
+ * LDS tile and row stride are derived from its own lattice total by the solo
+ * run's rule; a class launch takes the largest dynamic LDS among its segments.
+ *
+ * Limits (they bound the set of compiled kernels; they are not measurements):
+ * a segment with n_cat + n_quant > 0 has n_dims <= 8, n_cat <= 4, n_quant <=
+ * TPE_JOINT_MAX_QUANT, and the category and lattice limits of the solo stages; a
+ * continuous segment has 1 <= n_dims <= TPE_JOINT_MAX_DIMS.
+ *
+ * tpe_joint_mseg_run returns TPE_E_ARG before any launch (no device needed) for
+ * everything tpe_joint_seg_run checks and, per host descriptor, everything
+ * tpe_joint_quant_run checks: counts outside their limits, n_dims > 8 or n_cat >
+ * 4 beside a discrete or quantised coordinate, a U_d or V_d outside its range, a
+ * category or lattice total above its limit, a cat_off or quant_edge_off outside
+ * its tables, a null f64 pool or table workspace where a segment needs it, rows,
+ * edges or a table that leave their pool or the workspace, more than 32767
+ * segments, or scratch smaller than tpe_joint_mseg_scratch_bytes says.
+ * tpe_joint_profile covers this stage as it covers tpe_joint_seg_run.
+ * ---------------------------------------------------------------------- */
+#define TPE_JOINT_MSEG_MAX_CONT 8   /* continuous coordinates beside a discrete / quantised one */
+#define TPE_JOINT_MSEG_MAX_CAT 4    /* discrete coordinates of a segment */
+typedef struct tpe_joint_mseg {
+  int32_t n_dims, k_below, k_above;       /* as tpe_joint_seg ... */
+  uint32_t stream_word;
+  double below_base, above_base;
+  int64_t below_mu, below_a, below_c;
+  int64_t above_mu, above_a, above_c;
+  int64_t samp;
+  int64_t inject;
+  int64_t samp_cum;
+  float lo[TPE_JOINT_MAX_DIMS], hi[TPE_JOINT_MAX_DIMS];   /* ... up to here */
+  int32_t n_cat, n_quant;
+  int32_t cat_upper[TPE_JOINT_MSEG_MAX_CAT], cat_off[TPE_JOINT_MSEG_MAX_CAT];
+  int32_t quant_v[TPE_JOINT_MAX_QUANT], quant_edge_off[TPE_JOINT_MAX_QUANT];
+  float qlo[TPE_JOINT_MAX_QUANT], qhi[TPE_JOINT_MAX_QUANT];
+  int32_t n_edges, reserved;
+  int64_t below_cat, above_cat;           /* element offsets in pool_f32 */
+  int64_t below_miss, below_bonus, above_miss, above_bonus;
+  int64_t quant_samp;
+  int64_t below_h, cat_cum;               /* element offsets in pool_f64 */
+  int64_t quant_edges;
+  int64_t below_qmu, below_qsigma, above_qmu, above_qsigma;
+  int64_t table;                          /* element offset in quant_table */
+} tpe_joint_mseg;
+typedef struct tpe_joint_mseg_args {
+  int32_t n_segs, n_probs, n_cand, flags;   /* as tpe_joint_seg_args ... */
+  uint64_t seed;
+  const tpe_joint_mseg* segs;
+  const tpe_joint_mseg* host_segs;
+  const float* pool_f32;
+  const double* pool_f64;
+  int64_t pool_f32_len, pool_f64_len;
+  const int32_t* prob_seg;
+  const int32_t* host_prob_seg;
+  const int64_t* prob_id;
+  const int64_t* cand_off;                  /* ... up to here */
+  float* quant_table;                       /* device workspace (may be NULL without a quantised segment) */
+  uint64_t quant_table_bytes;
+} tpe_joint_mseg_args;
+
+/* the problem order and the chunk records of one tpe_joint_mseg_run */
+int tpe_joint_mseg_scratch_bytes(int32_t n_probs, int32_t n_cand, uint64_t* bytes);
+
+/* the table workspace of the host descriptors: sum over the segments with
+ * n_quant > 0 of (k_below + k_above) * sum_d V_d floats */
+int tpe_joint_mseg_table_bytes(const tpe_joint_mseg* host_segs, int32_t n_segs, uint64_t* bytes);
+
+/* as tpe_joint_seg_run; problem p's cand rows are [n_cand * (n_dims + n_cat +
+ * n_quant)(p)], categories and lattice indices as f32 */
+int tpe_joint_mseg_run(const tpe_joint_mseg_args* args, tpe_joint_record* records, float* cand, double* l_out,
+                       double* g_out, void* scratch, uint64_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Host phase clock of tpe_suggest_tree (tools/native_split.py).  While
  * enabled, a call records the steady-clock microseconds since its entry at
  * each phase below (a tree of several level runs: the last run's phases);
