@@ -266,6 +266,19 @@ class JointMSegArgs(ctypes.Structure):
     _fields_ = JointSegArgs._fields_ + [('quant_table', ctypes.c_void_p), ('quant_table_bytes', ctypes.c_uint64)]
 
 
+# tpe_joint_run_shard (include/tpe_hip.h "Sharded joint stage"): the stage whose args and records a call takes
+JOINT_STAGE_RUN, JOINT_STAGE_WIDE, JOINT_STAGE_MIXED, JOINT_STAGE_QUANT, JOINT_STAGE_SEG, JOINT_STAGE_MSEG = range(6)
+# the stage of each stage entry point, by its name
+JOINT_STAGES = {'tpe_joint_run': JOINT_STAGE_RUN, 'tpe_joint_wide_run': JOINT_STAGE_WIDE,
+                'tpe_joint_mixed_run': JOINT_STAGE_MIXED, 'tpe_joint_quant_run': JOINT_STAGE_QUANT,
+                'tpe_joint_seg_run': JOINT_STAGE_SEG, 'tpe_joint_mseg_run': JOINT_STAGE_MSEG}
+
+
+class JointShard(ctypes.Structure):
+    """tpe_joint_shard: the candidates [cand_base, cand_base + args.n_cand) of n_cand_global."""
+    _fields_ = [('cand_base', ctypes.c_int64), ('n_cand_global', ctypes.c_int64)]
+
+
 class JointReportArgs(ctypes.Structure):
     """tpe_joint_report_args: one tpe_joint_report."""
     _fields_ = [
@@ -423,7 +436,7 @@ EXPORTS = ('tpe_abi_version', 'tpe_last_error', 'tpe_device_count', 'tpe_tile_si
            'tpe_joint_wide_scratch_bytes', 'tpe_joint_wide_run', 'tpe_joint_wide_profile',
            'tpe_joint_seg_scratch_bytes', 'tpe_joint_seg_run', 'tpe_joint_mseg_scratch_bytes',
            'tpe_joint_mseg_table_bytes', 'tpe_joint_mseg_run', 'tpe_joint_report_scratch_bytes',
-           'tpe_joint_report', 'tpe_joint_report_profile')
+           'tpe_joint_report', 'tpe_joint_report_profile', 'tpe_joint_run_shard')
 
 # host phases of tpe_suggest_tree (tpe_host_phases order)
 PHASES = ('prefit', 'pack', 'launched', 'synced', 'level', 'return', 'recs')
@@ -564,6 +577,8 @@ def load(path=LIB_PATH):
     lib.tpe_joint_mseg_table_bytes.restype = ctypes.c_int
     lib.tpe_joint_mseg_run.argtypes = [ctypes.POINTER(JointMSegArgs), P, P, P, P, P, ctypes.c_uint64, P]
     lib.tpe_joint_mseg_run.restype = ctypes.c_int
+    lib.tpe_joint_run_shard.argtypes = [I32, P, ctypes.POINTER(JointShard), P, P, P, P, P, ctypes.c_uint64, P]
+    lib.tpe_joint_run_shard.restype = ctypes.c_int
     lib.tpe_joint_report_scratch_bytes.argtypes = [I32, I32, I32, ctypes.POINTER(ctypes.c_uint64)]
     lib.tpe_joint_report_scratch_bytes.restype = ctypes.c_int
     lib.tpe_joint_report.argtypes = [ctypes.POINTER(JointReportArgs), I32, P, P, P, P, P, ctypes.c_uint64, P]

@@ -35,6 +35,11 @@
 // k_joint_wide_sample / k_joint_wide_chunk / k_joint_wide_merge  the continuous
 //                stage for 17 to 64 coordinates ("wide groups" below): the
 //                candidates are drawn by a kernel of their own into scratch.
+// tpe_joint_run_shard  any of the six stages over the candidates [cand_base,
+//                cand_base + n_cand) of a larger run: the views carry cand_base (a
+//                kernel argument: scalar registers), added to the local index
+//                where it becomes a Philox word or a record's global_idx, and
+//                nowhere else (bounds tests and addressing stay local).
 // Every reduction has a fixed shape and there are no atomics: the output bytes
 // are a function of the input bytes.
 #include <hip/hip_runtime.h>
@@ -65,6 +70,7 @@ struct JointK {
   int D, C, n_chunks, inject;
   int kb, ka;
   uint32_t key0, key1, stream_word;
+  uint32_t cand_base;               // the global index of local candidate 0 (tpe_joint_run_shard)
   const float *bmu, *ba, *bc, *amu, *aa, *ac;
   double bbase, abase;
   const double* cum;
@@ -157,6 +163,7 @@ struct ChunkIO {
   int D, C, inject;
   int kb, ka;
   uint32_t key0, key1, stream_word, c3;   // c3: the new id's low word
+  uint32_t base;                    // global index of local candidate 0: Philox word and record index only
   const float *bmu, *ba, *bc, *amu, *aa, *ac;
   double bbase, abase;
   const double* cum;
@@ -189,8 +196,8 @@ __device__ __forceinline__ void joint_chunk_body(const ChunkIO& p, const float (
         if (d < D) z[r][d] = p.inj[(int64_t)i * D + d];
       continue;
     }
-    const uint32_t c3 = p.c3;
-    U4 w = philox4x32_10((uint32_t)i, 0u, p.stream_word, c3, p.key0, p.key1);
+    const uint32_t c3 = p.c3, gi = p.base + (uint32_t)i;   // gi < 2^31: i < C and base + C <= n_cand_global
+    U4 w = philox4x32_10(gi, 0u, p.stream_word, c3, p.key0, p.key1);
     const double us = u01w(w.x);
     int lo = 0, hi = p.kb - 1;             // first k with us < cum[k]
     while (lo < hi) { const int mid = (lo + hi) >> 1; if (us < p.cum[mid]) hi = mid; else lo = mid + 1; }
@@ -199,7 +206,7 @@ __device__ __forceinline__ void joint_chunk_body(const ChunkIO& p, const float (
     for (int d = 0; d < DP; ++d) {
       if (d >= D) continue;
       const int wi = d + 1;
-      if ((wi & 3) == 0) w = philox4x32_10((uint32_t)i, (uint32_t)(wi >> 2), p.stream_word, c3, p.key0, p.key1);
+      if ((wi & 3) == 0) w = philox4x32_10(gi, (uint32_t)(wi >> 2), p.stream_word, c3, p.key0, p.key1);
       const uint32_t word = (wi & 3) == 0 ? w.x : (wi & 3) == 1 ? w.y : (wi & 3) == 2 ? w.z : w.w;
       const float* sr = srow + d * 5;
       const float pr = sr[2] + u01f(word) * (sr[3] - sr[2]);
@@ -251,7 +258,7 @@ __device__ __forceinline__ void joint_chunk_body(const ChunkIO& p, const float (
 #pragma unroll
   for (int r = 0; r < kR; ++r) {
     if (r != wr) continue;
-    rec->global_idx = w.idx;
+    rec->global_idx = w.idx + (int64_t)p.base;
     rec->l = lv[r];
     rec->g = gv[r];
 #pragma unroll
@@ -271,6 +278,7 @@ __global__ __launch_bounds__(kThreads) void k_joint_chunk(const JointK p) {
   q.kb = p.kb; q.ka = p.ka;
   q.key0 = p.key0; q.key1 = p.key1; q.stream_word = p.stream_word;
   q.c3 = p.inject ? 0u : (uint32_t)p.ids[id];
+  q.base = p.cand_base;
   q.bmu = p.bmu; q.ba = p.ba; q.bc = p.bc; q.amu = p.amu; q.aa = p.aa; q.ac = p.ac;
   q.bbase = p.bbase; q.abase = p.abase;
   q.cum = p.cum; q.samp = p.samp; q.inj = p.inj;
@@ -294,6 +302,7 @@ struct SegK {
   int C, n_chunks, inject, first;   // first: this launch's first entry of `order`
   int n_probs, n_segs;
   uint32_t key0, key1;
+  uint32_t cand_base;               // as JointK
   const tpe_joint_seg* segs;        // (MIXED kernels: the tpe_joint_mseg array behind this pointer)
   const float* pool;
   const double* pool64;
@@ -383,6 +392,7 @@ __global__ __launch_bounds__(kThreads) void k_joint_seg_chunk(const SegK p) {
   q.kb = uni(sg->k_below); q.ka = uni(sg->k_above);
   q.key0 = p.key0; q.key1 = p.key1; q.stream_word = (uint32_t)uni((int)sg->stream_word);
   q.c3 = (uint32_t)uni((int)(uint32_t)p.prob_id[prob]);
+  q.base = p.cand_base;
   q.bmu = p.pool + uni(sg->below_mu); q.ba = p.pool + uni(sg->below_a); q.bc = p.pool + uni(sg->below_c);
   q.amu = p.pool + uni(sg->above_mu); q.aa = p.pool + uni(sg->above_a); q.ac = p.pool + uni(sg->above_c);
   q.bbase = unid(sg->below_base); q.abase = unid(sg->above_base);
@@ -552,8 +562,8 @@ __device__ __forceinline__ void mixed_chunk_body(const MixedIO<CP, KP>& p, int f
         if (d < Dk) z[r][CP + d] = q.inj[(int64_t)i * D + Dc + d];
       continue;
     }
-    const uint32_t c3 = q.c3;
-    U4 w = philox4x32_10((uint32_t)i, 0u, q.stream_word, c3, q.key0, q.key1);
+    const uint32_t c3 = q.c3, gi = q.base + (uint32_t)i;   // gi < 2^31: i < C and base + C <= n_cand_global
+    U4 w = philox4x32_10(gi, 0u, q.stream_word, c3, q.key0, q.key1);
     const double us = u01w(w.x);
     int lo = 0, hi = q.kb - 1;             // first k with us < cum[k]
     while (lo < hi) { const int mid = (lo + hi) >> 1; if (us < q.cum[mid]) hi = mid; else lo = mid + 1; }
@@ -564,7 +574,7 @@ __device__ __forceinline__ void mixed_chunk_body(const MixedIO<CP, KP>& p, int f
     // j, and a continuous one is k_joint_chunk's draw, operation for operation.
     for (int j = 0; j < D; ++j) {
       const int wi = j + 1;
-      if ((wi & 3) == 0) w = philox4x32_10((uint32_t)i, (uint32_t)(wi >> 2), q.stream_word, c3, q.key0, q.key1);
+      if ((wi & 3) == 0) w = philox4x32_10(gi, (uint32_t)(wi >> 2), q.stream_word, c3, q.key0, q.key1);
       const uint32_t word = (wi & 3) == 0 ? w.x : (wi & 3) == 1 ? w.y : (wi & 3) == 2 ? w.z : w.w;
       float x;
       if (j < Dc) {
@@ -647,7 +657,7 @@ __device__ __forceinline__ void mixed_chunk_body(const MixedIO<CP, KP>& p, int f
 #pragma unroll
   for (int r = 0; r < kR; ++r) {
     if (r != wr) continue;
-    rec->global_idx = w.idx;
+    rec->global_idx = w.idx + (int64_t)q.base;
     rec->l = lv[r];
     rec->g = gv[r];
     // kernel coordinate order: the Dc continuous entries, the categories, then zeros
@@ -671,6 +681,7 @@ __device__ __forceinline__ void solo_chunk_io(ChunkIO& q, const JointK& p, int D
   q.kb = p.kb; q.ka = p.ka;
   q.key0 = p.key0; q.key1 = p.key1; q.stream_word = p.stream_word;
   q.c3 = p.inject ? 0u : (uint32_t)p.ids[id];
+  q.base = p.cand_base;
   q.bmu = p.bmu; q.ba = p.ba; q.bc = p.bc; q.amu = p.amu; q.aa = p.aa; q.ac = p.ac;
   q.bbase = p.bbase; q.abase = p.abase;
   q.cum = p.cum; q.samp = p.samp; q.inj = p.inj;
@@ -715,6 +726,7 @@ __device__ __forceinline__ void mseg_chunk_io(ChunkIO& q, const SegK& p, const t
   q.kb = uni(sg->k_below); q.ka = uni(sg->k_above);
   q.key0 = p.key0; q.key1 = p.key1; q.stream_word = (uint32_t)uni((int)sg->stream_word);
   q.c3 = (uint32_t)uni((int)(uint32_t)p.prob_id[prob]);
+  q.base = p.cand_base;
   q.bmu = p.pool + uni(sg->below_mu); q.ba = p.pool + uni(sg->below_a); q.bc = p.pool + uni(sg->below_c);
   q.amu = p.pool + uni(sg->above_mu); q.aa = p.pool + uni(sg->above_a); q.ac = p.pool + uni(sg->above_c);
   q.bbase = unid(sg->below_base); q.abase = unid(sg->above_base);
@@ -1065,8 +1077,8 @@ __device__ __forceinline__ void quant_chunk_body(const QuantIO<CP, KP, QP>& p, i
         if (d < Dq) z[r][CP + KP + d] = q.inj[(int64_t)i * D + Dc + Dk + d];
       continue;
     }
-    const uint32_t c3 = q.c3;
-    U4 w = philox4x32_10((uint32_t)i, 0u, q.stream_word, c3, q.key0, q.key1);
+    const uint32_t c3 = q.c3, gi = q.base + (uint32_t)i;   // gi < 2^31: i < C and base + C <= n_cand_global
+    U4 w = philox4x32_10(gi, 0u, q.stream_word, c3, q.key0, q.key1);
     const double us = u01w(w.x);
     int lo = 0, hi = q.kb - 1;             // first k with us < cum[k]
     while (lo < hi) { const int mid = (lo + hi) >> 1; if (us < q.cum[mid]) hi = mid; else lo = mid + 1; }
@@ -1076,7 +1088,7 @@ __device__ __forceinline__ void quant_chunk_body(const QuantIO<CP, KP, QP>& p, i
     // operation for operation, and a quantised one the continuous draw binned.
     for (int j = 0; j < D; ++j) {
       const int wi = j + 1;
-      if ((wi & 3) == 0) w = philox4x32_10((uint32_t)i, (uint32_t)(wi >> 2), q.stream_word, c3, q.key0, q.key1);
+      if ((wi & 3) == 0) w = philox4x32_10(gi, (uint32_t)(wi >> 2), q.stream_word, c3, q.key0, q.key1);
       const uint32_t word = (wi & 3) == 0 ? w.x : (wi & 3) == 1 ? w.y : (wi & 3) == 2 ? w.z : w.w;
       float x;
       if (j < Dc || j >= Dc + Dk) {
@@ -1196,7 +1208,7 @@ __device__ __forceinline__ void quant_chunk_body(const QuantIO<CP, KP, QP>& p, i
 #pragma unroll
   for (int r = 0; r < kR; ++r) {
     if (r != wr) continue;
-    rec->global_idx = w.idx;
+    rec->global_idx = w.idx + (int64_t)q.base;
     rec->l = lv[r];
     rec->g = gv[r];
     // kernel coordinate order: continuous, categories, lattice indices, then zeros
@@ -1410,6 +1422,7 @@ constexpr int wide_r(int DP) { return DP <= 32 ? 2 : 1; }
 struct WideK {
   int D, C, n_chunks, nblk, inject;
   int kb, ka;
+  uint32_t cand_base;               // as JointK: the record index only (the draws are k_joint_wide_sample's)
   const float *bmu, *ba, *bc, *amu, *aa, *ac;
   double bbase, abase;
   const float* zsrc;                // inject: [C][D]; else zbuf [n_ids * nblk][D][256]
@@ -1421,6 +1434,7 @@ struct WideK {
 struct WideSampK {
   int D, C, nblk, kb;
   uint32_t key0, key1, stream_word;
+  uint32_t cand_base;               // as JointK: the Philox word
   const double* cum;
   const float* samp;
   const int64_t* ids;
@@ -1440,8 +1454,8 @@ __global__ __launch_bounds__(kThreads) void k_joint_wide_sample(const WideSampK 
   const int i = blk * kThreads + t;
   if (i >= p.C) return;
   float* out = p.zbuf + (int64_t)blockIdx.x * kThreads * D + t;
-  const uint32_t c3 = (uint32_t)p.ids[id];
-  U4 w = philox4x32_10((uint32_t)i, 0u, p.stream_word, c3, p.key0, p.key1);
+  const uint32_t c3 = (uint32_t)p.ids[id], gi = p.cand_base + (uint32_t)i;   // gi < 2^31 (i < C)
+  U4 w = philox4x32_10(gi, 0u, p.stream_word, c3, p.key0, p.key1);
   const double us = u01w(w.x);
   int lo = 0, hi = p.kb - 1;               // first k with us < cum[k]
   while (lo < hi) { const int mid = (lo + hi) >> 1; if (us < p.cum[mid]) hi = mid; else lo = mid + 1; }
@@ -1450,7 +1464,7 @@ __global__ __launch_bounds__(kThreads) void k_joint_wide_sample(const WideSampK 
 #pragma unroll 1
   for (int d = 0; d < D; ++d) {
     const int wi = d + 1;
-    if ((wi & 3) == 0) w = philox4x32_10((uint32_t)i, (uint32_t)(wi >> 2), p.stream_word, c3, p.key0, p.key1);
+    if ((wi & 3) == 0) w = philox4x32_10(gi, (uint32_t)(wi >> 2), p.stream_word, c3, p.key0, p.key1);
     const uint32_t word = (wi & 3) == 0 ? w.x : (wi & 3) == 1 ? w.y : (wi & 3) == 2 ? w.z : w.w;
     const float* sr = srow + d * 5;
     const float pr = sr[2] + u01f(word) * (sr[3] - sr[2]);
@@ -1590,7 +1604,7 @@ __global__ __launch_bounds__(kThreads) void k_joint_wide_chunk(const WideK p) {
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     if (r != wr) continue;
-    rec->global_idx = w.idx;
+    rec->global_idx = w.idx + (int64_t)p.cand_base;
     rec->l = lv[r];
     rec->g = gv[r];
 #pragma unroll
@@ -1689,8 +1703,9 @@ int tpe_joint_scratch_bytes(int32_t n_ids, int32_t n_cand, uint64_t* bytes) {
   return TPE_OK;
 }
 
-int tpe_joint_run(const tpe_joint_args* a, tpe_joint_record* records, float* cand, double* l_out, double* g_out,
-                  void* scratch, uint64_t scratch_bytes, void* stream) {
+// tpe_joint_run with local candidate i as global candidate cand_base + i (tpe_joint_run_shard)
+static int joint_run_at(const tpe_joint_args* a, tpe_joint_record* records, float* cand, double* l_out,
+                        double* g_out, void* scratch, uint64_t scratch_bytes, void* stream, uint32_t cand_base) {
   tpe_internal_epoch_bump();
   if (!a) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run: null args");
   if (a->n_dims < 1 || a->n_dims > TPE_JOINT_MAX_DIMS)
@@ -1713,6 +1728,7 @@ int tpe_joint_run(const tpe_joint_args* a, tpe_joint_record* records, float* can
   k.D = a->n_dims; k.C = a->n_cand; k.n_chunks = (int)n_chunks; k.inject = inject ? 1 : 0;
   k.kb = a->k_below; k.ka = a->k_above;
   k.key0 = (uint32_t)a->seed; k.key1 = (uint32_t)(a->seed >> 32); k.stream_word = a->stream_word;
+  k.cand_base = cand_base;
   k.bmu = a->below_mu; k.ba = a->below_a; k.bc = a->below_c;
   k.amu = a->above_mu; k.aa = a->above_a; k.ac = a->above_c;
   k.bbase = a->below_base; k.abase = a->above_base;
@@ -1762,8 +1778,9 @@ int tpe_joint_seg_scratch_bytes(int32_t n_probs, int32_t n_cand, uint64_t* bytes
   return TPE_OK;
 }
 
-int tpe_joint_seg_run(const tpe_joint_seg_args* a, tpe_joint_record* records, float* cand, double* l_out,
-                      double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
+// tpe_joint_seg_run with local candidate i as global candidate cand_base + i (tpe_joint_run_shard)
+static int joint_seg_run_at(const tpe_joint_seg_args* a, tpe_joint_record* records, float* cand, double* l_out,
+                            double* g_out, void* scratch, uint64_t scratch_bytes, void* stream, uint32_t cand_base) {
   tpe_internal_epoch_bump();
   if (!a) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: null args");
   if (a->n_segs < 1) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: n_segs < 1");
@@ -1808,7 +1825,7 @@ int tpe_joint_seg_run(const tpe_joint_seg_args* a, tpe_joint_record* records, fl
   SegK k;
   k.C = a->n_cand; k.n_chunks = (int)n_chunks; k.inject = inject ? 1 : 0; k.first = 0;
   k.n_probs = a->n_probs; k.n_segs = a->n_segs;
-  k.key0 = (uint32_t)a->seed; k.key1 = (uint32_t)(a->seed >> 32);
+  k.key0 = (uint32_t)a->seed; k.key1 = (uint32_t)(a->seed >> 32); k.cand_base = cand_base;
   k.segs = a->segs; k.pool = a->pool_f32; k.pool64 = a->pool_f64;
   k.prob_seg = a->prob_seg; k.prob_id = a->prob_id; k.cand_off = a->cand_off;
   k.order = (int32_t*)scratch;
@@ -1891,8 +1908,9 @@ int tpe_joint_mseg_table_bytes(const tpe_joint_mseg* host_segs, int32_t n_segs, 
   return TPE_OK;
 }
 
-int tpe_joint_mseg_run(const tpe_joint_mseg_args* a, tpe_joint_record* records, float* cand, double* l_out,
-                       double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
+// tpe_joint_mseg_run with local candidate i as global candidate cand_base + i (tpe_joint_run_shard)
+static int joint_mseg_run_at(const tpe_joint_mseg_args* a, tpe_joint_record* records, float* cand, double* l_out,
+                             double* g_out, void* scratch, uint64_t scratch_bytes, void* stream, uint32_t cand_base) {
   tpe_internal_epoch_bump();
   static_assert(offsetof(tpe_joint_mseg, hi) == offsetof(tpe_joint_seg, hi) &&
                     offsetof(tpe_joint_mseg, n_cat) == sizeof(tpe_joint_seg),
@@ -2015,7 +2033,7 @@ int tpe_joint_mseg_run(const tpe_joint_mseg_args* a, tpe_joint_record* records, 
   SegK& k = mk.s;
   k.C = a->n_cand; k.n_chunks = (int)n_chunks; k.inject = inject ? 1 : 0; k.first = 0;
   k.n_probs = a->n_probs; k.n_segs = a->n_segs;
-  k.key0 = (uint32_t)a->seed; k.key1 = (uint32_t)(a->seed >> 32);
+  k.key0 = (uint32_t)a->seed; k.key1 = (uint32_t)(a->seed >> 32); k.cand_base = cand_base;
   k.segs = reinterpret_cast<const tpe_joint_seg*>(a->segs); k.pool = a->pool_f32; k.pool64 = a->pool_f64;
   k.prob_seg = a->prob_seg; k.prob_id = a->prob_id; k.cand_off = a->cand_off;
   k.order = (int32_t*)scratch;
@@ -2089,8 +2107,9 @@ int tpe_joint_wide_profile(double* sample_ms) {
   return TPE_OK;
 }
 
-int tpe_joint_wide_run(const tpe_joint_wide_args* a, tpe_joint_wide_record* records, float* cand, double* l_out,
-                       double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
+// tpe_joint_wide_run with local candidate i as global candidate cand_base + i (tpe_joint_run_shard)
+static int joint_wide_run_at(const tpe_joint_wide_args* a, tpe_joint_wide_record* records, float* cand, double* l_out,
+                             double* g_out, void* scratch, uint64_t scratch_bytes, void* stream, uint32_t cand_base) {
   tpe_internal_epoch_bump();
   if (!a) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_wide_run: null args");
   if (a->n_dims < 1 || a->n_dims > TPE_JOINT_WIDE_MAX_DIMS)
@@ -2122,6 +2141,7 @@ int tpe_joint_wide_run(const tpe_joint_wide_args* a, tpe_joint_wide_record* reco
     WideSampK sk;
     sk.D = D; sk.C = a->n_cand; sk.nblk = (int)nblk; sk.kb = a->k_below;
     sk.key0 = (uint32_t)a->seed; sk.key1 = (uint32_t)(a->seed >> 32); sk.stream_word = a->stream_word;
+    sk.cand_base = cand_base;
     sk.cum = a->samp_cum; sk.samp = a->samp; sk.ids = a->ids; sk.zbuf = zbuf;
     for (int d = 0; d < TPE_JOINT_WIDE_MAX_DIMS; ++d) {
       // f32 bounds: smallest float >= low, largest float < high (as tpe_joint_run)
@@ -2149,7 +2169,7 @@ int tpe_joint_wide_run(const tpe_joint_wide_args* a, tpe_joint_wide_record* reco
 
   WideK k;
   k.D = D; k.C = a->n_cand; k.n_chunks = (int)n_chunks; k.nblk = (int)nblk; k.inject = inject ? 1 : 0;
-  k.kb = a->k_below; k.ka = a->k_above;
+  k.kb = a->k_below; k.ka = a->k_above; k.cand_base = cand_base;
   k.bmu = a->below_mu; k.ba = a->below_a; k.bc = a->below_c;
   k.amu = a->above_mu; k.aa = a->above_a; k.ac = a->above_c;
   k.bbase = a->below_base; k.abase = a->above_base;
@@ -2178,8 +2198,9 @@ int tpe_joint_wide_run(const tpe_joint_wide_args* a, tpe_joint_wide_record* reco
   return TPE_OK;
 }
 
-int tpe_joint_mixed_run(const tpe_joint_mixed_args* a, tpe_joint_record* records, float* cand, double* l_out,
-                        double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
+// tpe_joint_mixed_run with local candidate i as global candidate cand_base + i (tpe_joint_run_shard)
+static int joint_mixed_run_at(const tpe_joint_mixed_args* a, tpe_joint_record* records, float* cand, double* l_out,
+                              double* g_out, void* scratch, uint64_t scratch_bytes, void* stream, uint32_t cand_base) {
   tpe_internal_epoch_bump();
   if (!a) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: null args");
   if (a->n_cat < 0) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: n_cat < 0");
@@ -2196,7 +2217,7 @@ int tpe_joint_mixed_run(const tpe_joint_mixed_args* a, tpe_joint_record* records
     c.below_base = a->below_base; c.above_base = a->above_base;
     c.samp_cum = a->samp_cum; c.samp = a->samp; c.ids = a->ids; c.inject = a->inject;
     for (int d = 0; d < TPE_JOINT_MAX_DIMS; ++d) { c.low[d] = a->low[d]; c.high[d] = a->high[d]; }
-    return tpe_joint_run(&c, records, cand, l_out, g_out, scratch, scratch_bytes, stream);
+    return joint_run_at(&c, records, cand, l_out, g_out, scratch, scratch_bytes, stream, cand_base);
   }
   const int Dc = a->n_dims, Dk = a->n_cat;
   if (a->n_cand < 1) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: n_cand < 1");
@@ -2235,6 +2256,7 @@ int tpe_joint_mixed_run(const tpe_joint_mixed_args* a, tpe_joint_record* records
   k.D = Dc; k.C = a->n_cand; k.n_chunks = (int)n_chunks; k.inject = inject ? 1 : 0;
   k.kb = a->k_below; k.ka = a->k_above;
   k.key0 = (uint32_t)a->seed; k.key1 = (uint32_t)(a->seed >> 32); k.stream_word = a->stream_word;
+  k.cand_base = cand_base;
   k.bmu = a->below_mu; k.ba = a->below_a; k.bc = a->below_c;
   k.amu = a->above_mu; k.aa = a->above_a; k.ac = a->above_c;
   k.bbase = a->below_base; k.abase = a->above_base;
@@ -2297,8 +2319,9 @@ int tpe_joint_quant_profile(double* table_ms) {
   return TPE_OK;
 }
 
-int tpe_joint_quant_run(const tpe_joint_quant_args* a, tpe_joint_record* records, float* cand, double* l_out,
-                        double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
+// tpe_joint_quant_run with local candidate i as global candidate cand_base + i (tpe_joint_run_shard)
+static int joint_quant_run_at(const tpe_joint_quant_args* a, tpe_joint_record* records, float* cand, double* l_out,
+                              double* g_out, void* scratch, uint64_t scratch_bytes, void* stream, uint32_t cand_base) {
   tpe_internal_epoch_bump();
   static_assert(offsetof(tpe_joint_quant_args, n_quant) == sizeof(tpe_joint_mixed_args), "the shared fields");
   static_assert(offsetof(tpe_joint_quant_args, cat_cum) == offsetof(tpe_joint_mixed_args, cat_cum), "the shared fields");
@@ -2308,7 +2331,7 @@ int tpe_joint_quant_run(const tpe_joint_quant_args* a, tpe_joint_record* records
   if (a->n_quant == 0) {                    // no quantised label: the mixed stage, the same bytes
     tpe_joint_mixed_args m;
     memcpy(&m, a, sizeof m);
-    return tpe_joint_mixed_run(&m, records, cand, l_out, g_out, scratch, scratch_bytes, stream);
+    return joint_mixed_run_at(&m, records, cand, l_out, g_out, scratch, scratch_bytes, stream, cand_base);
   }
   const int Dc = a->n_dims, Dk = a->n_cat, Dq = a->n_quant;
   if (Dk < 0) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: n_cat < 0");
@@ -2370,6 +2393,7 @@ int tpe_joint_quant_run(const tpe_joint_quant_args* a, tpe_joint_record* records
   k.D = Dc; k.C = a->n_cand; k.n_chunks = (int)n_chunks; k.inject = inject ? 1 : 0;
   k.kb = a->k_below; k.ka = a->k_above;
   k.key0 = (uint32_t)a->seed; k.key1 = (uint32_t)(a->seed >> 32); k.stream_word = a->stream_word;
+  k.cand_base = cand_base;
   k.bmu = a->below_mu; k.ba = a->below_a; k.bc = a->below_c;
   k.amu = a->above_mu; k.aa = a->above_a; k.ac = a->above_c;
   k.bbase = a->below_base; k.abase = a->above_base;
@@ -2451,6 +2475,86 @@ int tpe_joint_quant_run(const tpe_joint_quant_args* a, tpe_joint_record* records
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
   return TPE_OK;
+}
+
+int tpe_joint_run(const tpe_joint_args* a, tpe_joint_record* records, float* cand, double* l_out,
+                  double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
+  return joint_run_at(a, records, cand, l_out, g_out, scratch, scratch_bytes, stream, 0u);
+}
+
+int tpe_joint_seg_run(const tpe_joint_seg_args* a, tpe_joint_record* records, float* cand, double* l_out,
+                      double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
+  return joint_seg_run_at(a, records, cand, l_out, g_out, scratch, scratch_bytes, stream, 0u);
+}
+
+int tpe_joint_mseg_run(const tpe_joint_mseg_args* a, tpe_joint_record* records, float* cand, double* l_out,
+                       double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
+  return joint_mseg_run_at(a, records, cand, l_out, g_out, scratch, scratch_bytes, stream, 0u);
+}
+
+int tpe_joint_wide_run(const tpe_joint_wide_args* a, tpe_joint_wide_record* records, float* cand, double* l_out,
+                       double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
+  return joint_wide_run_at(a, records, cand, l_out, g_out, scratch, scratch_bytes, stream, 0u);
+}
+
+int tpe_joint_mixed_run(const tpe_joint_mixed_args* a, tpe_joint_record* records, float* cand, double* l_out,
+                        double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
+  return joint_mixed_run_at(a, records, cand, l_out, g_out, scratch, scratch_bytes, stream, 0u);
+}
+
+int tpe_joint_quant_run(const tpe_joint_quant_args* a, tpe_joint_record* records, float* cand, double* l_out,
+                        double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
+  return joint_quant_run_at(a, records, cand, l_out, g_out, scratch, scratch_bytes, stream, 0u);
+}
+
+int tpe_joint_run_shard(int32_t stage, const void* args, const tpe_joint_shard* shard, void* records, float* cand,
+                        double* l_out, double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
+  tpe_internal_epoch_bump();
+  if (!args) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run_shard: null args");
+  if (!shard) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run_shard: null shard");
+  // every stage's args begin with int32 fields that hold n_cand and flags; read them by the stage's own type
+  int64_t n_cand = 0;
+  uint32_t flags = 0;
+#define TPE_SHARD_HEAD(T) { n_cand = ((const T*)args)->n_cand; flags = (uint32_t)((const T*)args)->flags; } break
+  switch (stage) {
+    case TPE_JOINT_STAGE_RUN: TPE_SHARD_HEAD(tpe_joint_args);
+    case TPE_JOINT_STAGE_WIDE: TPE_SHARD_HEAD(tpe_joint_wide_args);
+    case TPE_JOINT_STAGE_MIXED: TPE_SHARD_HEAD(tpe_joint_mixed_args);
+    case TPE_JOINT_STAGE_QUANT: TPE_SHARD_HEAD(tpe_joint_quant_args);
+    case TPE_JOINT_STAGE_SEG: TPE_SHARD_HEAD(tpe_joint_seg_args);
+    case TPE_JOINT_STAGE_MSEG: TPE_SHARD_HEAD(tpe_joint_mseg_args);
+    default: return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run_shard: stage outside [0, 5]");
+  }
+#undef TPE_SHARD_HEAD
+  if (shard->cand_base < 0) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run_shard: cand_base < 0");
+  // the Philox counter word and the kernels' index arithmetic are 32-bit
+  if (shard->n_cand_global >= ((int64_t)1 << 31))
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run_shard: n_cand_global >= 2^31");
+  if (n_cand > shard->n_cand_global || shard->cand_base > shard->n_cand_global - n_cand)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run_shard: cand_base + n_cand > n_cand_global");
+  if ((flags & TPE_JOINT_INJECT) && shard->cand_base != 0)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run_shard: TPE_JOINT_INJECT with cand_base != 0");
+  const uint32_t base = (uint32_t)shard->cand_base;
+  switch (stage) {
+    case TPE_JOINT_STAGE_RUN:
+      return joint_run_at((const tpe_joint_args*)args, (tpe_joint_record*)records, cand, l_out, g_out, scratch,
+                          scratch_bytes, stream, base);
+    case TPE_JOINT_STAGE_WIDE:
+      return joint_wide_run_at((const tpe_joint_wide_args*)args, (tpe_joint_wide_record*)records, cand, l_out, g_out,
+                               scratch, scratch_bytes, stream, base);
+    case TPE_JOINT_STAGE_MIXED:
+      return joint_mixed_run_at((const tpe_joint_mixed_args*)args, (tpe_joint_record*)records, cand, l_out, g_out,
+                                scratch, scratch_bytes, stream, base);
+    case TPE_JOINT_STAGE_QUANT:
+      return joint_quant_run_at((const tpe_joint_quant_args*)args, (tpe_joint_record*)records, cand, l_out, g_out,
+                                scratch, scratch_bytes, stream, base);
+    case TPE_JOINT_STAGE_SEG:
+      return joint_seg_run_at((const tpe_joint_seg_args*)args, (tpe_joint_record*)records, cand, l_out, g_out, scratch,
+                              scratch_bytes, stream, base);
+    default:
+      return joint_mseg_run_at((const tpe_joint_mseg_args*)args, (tpe_joint_record*)records, cand, l_out, g_out,
+                               scratch, scratch_bytes, stream, base);
+  }
 }
 
 }  // extern "C"

@@ -337,3 +337,18 @@ def gather_label_columns(ex, values, owner, failed=False):
         if r != rank and cols[r]:
             out[:, cols[r]] = allb[r].view(np.float64).reshape(n, m)[:, :len(cols[r])]
     return out
+
+
+def gather_joint_records(ex, rec, P, dtype, failed=False):
+    """Candidate axis of a joint stage (tpe.suggest(..., joint_shard=)): ``rec``
+    [P] of ``dtype`` holds this rank's winner records (None on a rank whose
+    stage failed); every rank gets all of them, [world, P] in rank order, for
+    joint.combine_records.  One all-gather of P * itemsize bytes a rank."""
+    pay = np.zeros(int(P) * dtype.itemsize, dtype=np.uint8)
+    if not failed:
+        rec = np.ascontiguousarray(rec, dtype=dtype).reshape(-1)
+        if len(rec) != P:
+            raise ValueError('gather_joint_records: %d records, expected %d' % (len(rec), P))
+        pay[:] = rec.view(np.uint8)
+    allb = _exchange_status(ex, pay, failed)
+    return np.ascontiguousarray(allb).view(dtype).reshape(ex.world, int(P))

@@ -976,7 +976,7 @@ class Engine(object):
         return d_top, d_ntop, d_stats
 
     def run_joint(self, below, above, low, high, ids, n_cand, seed, inject=None, return_cand=False, want_lg=False,
-                  report_k=0):
+                  report_k=0, shard=None):
         """One joint TPE stage (tpe_joint_run, include/tpe_hip.h "Joint
         (multivariate) TPE stage"): ``below`` / ``above`` = (w [K], mu [K, D],
         sigma [K, D]) float64 mixtures (joint.side_mixture), ``low`` / ``high``
@@ -992,30 +992,42 @@ class Engine(object):
         top_z f32 [P, k, D] (run_joint_segments: a list of P arrays [k, D_p]),
         n_top int32 [P] and stats [P] (N.SCORE_STATS_DTYPE), P the ids or
         problems; the per-candidate arrays come to the host only with
-        ``return_cand`` / ``want_lg``."""
+        ``return_cand`` / ``want_lg``.
+        ``shard`` = (cand_base, n_cand_global) (every run_joint* method,
+        tpe_joint_run_shard, include/tpe_hip.h "Sharded joint stage"): the call
+        scores the ``n_cand`` candidates [cand_base, cand_base + n_cand) of a
+        stage of n_cand_global < 2^31 candidates.  The per-candidate arrays are
+        the local ones, a record's global_idx is global, and
+        joint.combine_records over the parts of a partition gives the unsharded
+        records.  ``n_cand`` may then be 0 (a rank whose range is empty): empty
+        records (joint.empty_records) and no native call.  ``report_k`` > 0 or
+        ``inject`` with a non-zero cand_base raise ValueError."""
         return self._joint_continuous(False, below, above, low, high, ids, n_cand, seed, inject, return_cand, want_lg,
-                                      report_k=report_k)
+                                      report_k=report_k, shard=shard)
 
     def run_joint_wide(self, below, above, low, high, ids, n_cand, seed, inject=None, return_cand=False,
-                       want_lg=False, report_k=0):
+                       want_lg=False, report_k=0, shard=None):
         """``run_joint`` for up to N.JOINT_WIDE_MAX_DIMS dimensions
         (tpe_joint_wide_run, include/tpe_hip.h "Wide joint stage"): the same
         arguments, model, Philox streams and return shapes; the records are
         N.JOINT_WIDE_RECORD_DTYPE."""
         return self._joint_continuous(True, below, above, low, high, ids, n_cand, seed, inject, return_cand, want_lg,
-                                      report_k=report_k)
+                                      report_k=report_k, shard=shard)
 
     def _joint_continuous(self, wide, below, above, low, high, ids, n_cand, seed, inject, return_cand, want_lg,
-                          stream_word=None, report_k=0):
+                          stream_word=None, report_k=0, shard=None):
         """``stream_word``: the Philox stream word (None: N.JOINT_STREAM; a branch
         group's joint.branch_stream_word, to compare with run_joint_segments)."""
         from . import joint as J
         low, high = np.asarray(low, dtype=np.float64), np.asarray(high, dtype=np.float64)
         D = len(low)
-        ids, n_ids, C = self._joint_sizes(D, ids, n_cand, N.JOINT_WIDE_MAX_DIMS if wide else N.JOINT_MAX_DIMS)
+        ids, n_ids, C = self._joint_sizes(D, ids, n_cand, N.JOINT_WIDE_MAX_DIMS if wide else N.JOINT_MAX_DIMS, shard)
+        shard = self._joint_shard(shard, C, report_k, inject)
         for side in (below, above):
             if side[1].shape != (len(side[0]), D) or side[2].shape != side[1].shape:
                 raise ValueError('joint stage: mixture shapes do not match %d dimensions' % D)
+        if C == 0:
+            return self._joint_empty(n_ids, D, return_cand, want_lg, wide)
         up = self._joint_up
         a = N.JointWideArgs() if wide else N.JointArgs()
         a.n_dims, a.n_cand, a.n_ids, a.flags = D, C, n_ids, 0
@@ -1035,19 +1047,69 @@ class Engine(object):
         for d in range(D):
             a.low[d], a.high[d] = low[d], high[d]
         return self._joint_call('tpe_joint_wide_run' if wide else 'tpe_joint_run', a, n_ids, C, D, return_cand,
-                                want_lg, wide=wide, report_k=report_k)
+                                want_lg, wide=wide, report_k=report_k, shard=shard)
 
     # what run_joint and run_joint_mixed share: the size checks, the uploads, the call and its results
-    def _joint_sizes(self, D, ids, n_cand, max_dims=N.JOINT_MAX_DIMS):
+    def _joint_sizes(self, D, ids, n_cand, max_dims=N.JOINT_MAX_DIMS, shard=None):
         ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
         n_ids, C = len(ids), int(n_cand)
         if not 1 <= D <= max_dims:
             raise ValueError('joint stage: %d dimensions, at most %d' % (D, max_dims))
-        if C < 1 or C >= 2 ** 31 or n_ids < 1:
+        if C < (1 if shard is None else 0) or C >= 2 ** 31 or n_ids < 1:   # (an empty part of a sharded stage: C = 0)
             raise ValueError('joint stage: n_cand / ids out of range')
         if n_ids * C * max(D, 2) >= 2 ** 31:
             raise ValueError('joint stage: %d ids x %d candidates do not fit one run' % (n_ids, C))
         return ids, n_ids, C
+
+    @staticmethod
+    def _joint_shard(shard, C, report_k=0, inject=None):
+        """The N.JointShard of a ``shard`` = (cand_base, n_cand_global) argument
+        over ``C`` local candidates (None: no shard); ValueError for a range
+        outside [0, n_cand_global), n_cand_global >= 2^31, and a report or
+        injected candidates at a non-zero base."""
+        if shard is None:
+            return None
+        try:
+            base, total = shard
+            base, total = int(base), int(total)
+        except (TypeError, ValueError):
+            raise ValueError('joint stage: shard must be (cand_base, n_cand_global): %r' % (shard,))
+        if base < 0 or total >= 2 ** 31 or base + int(C) > total:
+            raise ValueError('joint stage: shard (%d, %d) with %d candidates: need 0 <= cand_base, cand_base + n_cand '
+                             '<= n_cand_global < 2^31' % (base, total, int(C)))
+        if base != 0 and int(report_k) > 0:
+            raise ValueError('joint stage: report_k does not combine with a shard at a non-zero cand_base')
+        if base != 0 and inject is not None:
+            raise ValueError('joint stage: inject does not combine with a shard at a non-zero cand_base')
+        sh = N.JointShard()
+        sh.cand_base, sh.n_cand_global = base, total
+        return sh
+
+    @staticmethod
+    def _joint_empty(P, D, return_cand, want_lg, wide=False, widths=None):
+        """What a run_joint* call returns for an empty part of a sharded stage
+        (n_cand = 0): joint.empty_records and per-candidate arrays of length 0
+        (``widths``: the segmented stages' list of [0, D_p])."""
+        from . import joint as J
+        rec = J.empty_records(P, N.JOINT_WIDE_RECORD_DTYPE if wide else N.JOINT_RECORD_DTYPE)
+        if not (return_cand or want_lg):
+            return rec
+        out = [rec]
+        if return_cand:
+            out.append(np.zeros((P, 0, D), dtype=np.float32) if widths is None
+                       else [np.zeros((0, int(w)), dtype=np.float32) for w in widths])
+        if want_lg:
+            out.extend([np.zeros((P, 0)), np.zeros((P, 0))])
+        return tuple(out)
+
+    def _joint_native(self, fn, a, shard, *rest):
+        """The stage entry point ``fn``, or tpe_joint_run_shard over the same
+        arguments where ``shard`` (N.JointShard) is given."""
+        if shard is None:
+            N.check(getattr(self.lib, fn)(ctypes.byref(a), *rest), self.lib, fn)
+        else:
+            N.check(self.lib.tpe_joint_run_shard(N.JOINT_STAGES[fn], ctypes.byref(a), ctypes.byref(shard), *rest),
+                    self.lib, 'tpe_joint_run_shard')
 
     def _joint_up(self, name, arr, dtype):
         t = self._buf('joint_' + name, arr.size, dtype)
@@ -1063,11 +1125,12 @@ class Engine(object):
         a.flags |= N.JOINT_INJECT
         a.inject = self._joint_up('inject', inj, torch.float32)
 
-    def _joint_call(self, fn, a, n_ids, C, D, return_cand, want_lg, wide=False, report_k=0):
+    def _joint_call(self, fn, a, n_ids, C, D, return_cand, want_lg, wide=False, report_k=0, shard=None):
         """Scratch and result buffers, the native call ``fn`` and the records
         (and candidates [n_ids, C, D], l, g [n_ids, C]) on the host.  ``wide``:
         the wide stage's scratch size and record.  ``report_k``: the stage
-        writes all three device buffers and the joint report follows."""
+        writes all three device buffers and the joint report follows.
+        ``shard`` (N.JointShard): the call goes through tpe_joint_run_shard."""
         report_k = self._report_k(report_k)
         dev_cand, dev_lg = return_cand or report_k > 0, want_lg or report_k > 0
         nb = ctypes.c_uint64(0)
@@ -1083,10 +1146,9 @@ class Engine(object):
         d_l = self._buf('joint_l', n_ids * C, torch.float64) if dev_lg else None
         d_g = self._buf('joint_g', n_ids * C, torch.float64) if dev_lg else None
         stream = self._stream()
-        N.check(getattr(self.lib, fn)(ctypes.byref(a), d_rec.data_ptr(), d_cand.data_ptr() if dev_cand else None,
-                                      d_l.data_ptr() if dev_lg else None, d_g.data_ptr() if dev_lg else None,
-                                      d_scr.data_ptr(), d_scr.numel() * 8, ctypes.c_void_p(stream)),
-                self.lib, fn)
+        self._joint_native(fn, a, shard, d_rec.data_ptr(), d_cand.data_ptr() if dev_cand else None,
+                           d_l.data_ptr() if dev_lg else None, d_g.data_ptr() if dev_lg else None,
+                           d_scr.data_ptr(), d_scr.numel() * 8, ctypes.c_void_p(stream))
         if report_k:
             rep = self._joint_report(d_cand.data_ptr(), d_l.data_ptr(), d_g.data_ptr(), n_ids, C, report_k, stream,
                                      width=D)
@@ -1148,7 +1210,7 @@ class Engine(object):
                 d_stats[:P * 8].cpu().numpy().view(N.SCORE_STATS_DTYPE).copy())
 
     def run_joint_segments(self, models, stream_words, prob_seg, prob_id, n_cand, seed, inject=None,
-                           return_cand=False, want_lg=False, report_k=0):
+                           return_cand=False, want_lg=False, report_k=0, shard=None):
         """One segmented joint stage (tpe_joint_seg_run, include/tpe_hip.h
         "Segmented joint stage"): problem p scores new id ``prob_id[p]`` under
         group ``prob_seg[p]``.  ``models``: per group a joint.JointModel or a
@@ -1176,19 +1238,23 @@ class Engine(object):
         from . import joint as J
         if any(self._seg_parts(m)[4] or self._seg_parts(m)[5] for m in models):
             return self._run_joint_msegments(models, stream_words, prob_seg, prob_id, n_cand, seed, inject,
-                                             return_cand, want_lg, report_k)
+                                             return_cand, want_lg, report_k, shard)
         S, C = len(models), int(n_cand)
         report_k = self._report_k(report_k)
+        shard = self._joint_shard(shard, C, report_k, inject)
         dev_cand, dev_lg = return_cand or report_k > 0, want_lg or report_k > 0
         prob_seg = np.ascontiguousarray(prob_seg, dtype=np.int32).reshape(-1)
         prob_id = np.ascontiguousarray(prob_id, dtype=np.int64).reshape(-1)
         P = len(prob_seg)
         if S < 1 or len(stream_words) != S:
             raise ValueError('joint stage: one stream word per group, at least one group')
-        if P < 1 or len(prob_id) != P or C < 1 or C >= 2 ** 31:
+        if P < 1 or len(prob_id) != P or C < (1 if shard is None else 0) or C >= 2 ** 31:
             raise ValueError('joint stage: n_cand / problems out of range')
         if prob_seg.min() < 0 or prob_seg.max() >= S:
             raise ValueError('joint stage: a problem names a group outside [0, %d)' % S)
+        if C == 0:                                   # an empty part of a sharded stage
+            widths = [sum(len(x) for x in self._seg_parts(models[s])[3:]) for s in prob_seg]
+            return self._joint_empty(P, 0, return_cand, want_lg, widths=widths)
         if inject is not None and len(inject) != S:
             raise ValueError('joint stage: inject must hold one entry per group')
         segs = np.zeros(S, dtype=N.JOINT_SEG_DTYPE)
@@ -1252,9 +1318,9 @@ class Engine(object):
         a.pool_f64, a.prob_id, a.cand_off = base + int(offs[1]), base + int(offs[2]), base + int(offs[3])
         a.pool_f32, a.prob_seg, a.host_prob_seg = base + int(offs[4]), base + int(offs[5]), prob_seg.ctypes.data
         a.pool_f32_len, a.pool_f64_len = n32, n64
-        return self._joint_seg_call('tpe_joint_seg', a, P, C, cand_off, pd, return_cand, want_lg, report_k)
+        return self._joint_seg_call('tpe_joint_seg', a, P, C, cand_off, pd, return_cand, want_lg, report_k, shard)
 
-    def _joint_seg_call(self, fn, a, P, C, cand_off, pd, return_cand, want_lg, report_k):
+    def _joint_seg_call(self, fn, a, P, C, cand_off, pd, return_cand, want_lg, report_k, shard=None):
         """What the two segmented stages share: scratch and the result block, the
         native call ``fn``_run, the report, and one transfer of the results."""
         dev_cand, dev_lg = return_cand or report_k > 0, want_lg or report_k > 0
@@ -1268,11 +1334,9 @@ class Engine(object):
         d_out = self._buf('joint_seg_out', rec_w + 2 * lg_w + cand_w, torch.float64)
         out = d_out.data_ptr()
         stream = self._stream()
-        N.check(getattr(self.lib, fn + '_run')(ctypes.byref(a), out, out + 8 * (rec_w + 2 * lg_w) if dev_cand else None,
-                                               out + 8 * rec_w if dev_lg else None,
-                                               out + 8 * (rec_w + lg_w) if dev_lg else None,
-                                               d_scr.data_ptr(), d_scr.numel() * 8, ctypes.c_void_p(stream)),
-                self.lib, fn + '_run')
+        self._joint_native(fn + '_run', a, shard, out, out + 8 * (rec_w + 2 * lg_w) if dev_cand else None,
+                           out + 8 * rec_w if dev_lg else None, out + 8 * (rec_w + lg_w) if dev_lg else None,
+                           d_scr.data_ptr(), d_scr.numel() * 8, ctypes.c_void_p(stream))
         if report_k:
             rep = self._joint_report(out + 8 * (rec_w + 2 * lg_w), out + 8 * rec_w, out + 8 * (rec_w + lg_w), P, C,
                                      report_k, stream, cand_off=a.cand_off, widths=pd)
@@ -1386,21 +1450,25 @@ class Engine(object):
         return r
 
     def _run_joint_msegments(self, models, stream_words, prob_seg, prob_id, n_cand, seed, inject, return_cand,
-                             want_lg, report_k):
+                             want_lg, report_k, shard=None):
         """run_joint_segments through tpe_joint_mseg_run: every group, whatever
         its kind, packed into the two pools behind one array of tpe_joint_mseg."""
         from . import joint as J
         S, C = len(models), int(n_cand)
         report_k = self._report_k(report_k)
+        shard = self._joint_shard(shard, C, report_k, inject)
         prob_seg = np.ascontiguousarray(prob_seg, dtype=np.int32).reshape(-1)
         prob_id = np.ascontiguousarray(prob_id, dtype=np.int64).reshape(-1)
         P = len(prob_seg)
         if S < 1 or len(stream_words) != S:
             raise ValueError('joint stage: one stream word per group, at least one group')
-        if P < 1 or len(prob_id) != P or C < 1 or C >= 2 ** 31:
+        if P < 1 or len(prob_id) != P or C < (1 if shard is None else 0) or C >= 2 ** 31:
             raise ValueError('joint stage: n_cand / problems out of range')
         if prob_seg.min() < 0 or prob_seg.max() >= S:
             raise ValueError('joint stage: a problem names a group outside [0, %d)' % S)
+        if C == 0:                                   # an empty part of a sharded stage
+            widths = [sum(len(x) for x in self._seg_parts(models[s])[3:]) for s in prob_seg]
+            return self._joint_empty(P, 0, return_cand, want_lg, widths=widths)
         if inject is not None and len(inject) != S:
             raise ValueError('joint stage: inject must hold one entry per group')
         segs = np.zeros(S, dtype=N.JOINT_MSEG_DTYPE)
@@ -1498,10 +1566,10 @@ class Engine(object):
         if n_table:
             d_tab = self._buf('joint_mseg_table', n_table, torch.float32)
             a.quant_table, a.quant_table_bytes = d_tab.data_ptr(), d_tab.numel() * 4
-        return self._joint_seg_call('tpe_joint_mseg', a, P, C, cand_off, pd, return_cand, want_lg, report_k)
+        return self._joint_seg_call('tpe_joint_mseg', a, P, C, cand_off, pd, return_cand, want_lg, report_k, shard)
 
     def run_joint_mixed(self, below, above, low, high, cats, ids, n_cand, seed, inject=None, return_cand=False,
-                        want_lg=False, report_k=0, stream_word=None):
+                        want_lg=False, report_k=0, stream_word=None, shard=None):
         """One joint stage over a mixed group (tpe_joint_mixed_run,
         include/tpe_hip.h "Mixed joint stage"): ``below`` / ``above`` = (w [K],
         mu [K, Dc], sigma [K, Dc]) the continuous part as in ``run_joint`` (Dc
@@ -1518,7 +1586,10 @@ class Engine(object):
         D = Dc + Dk
         if Dk == 0:
             raise ValueError('joint stage: no discrete dimension, use run_joint')
-        ids, n_ids, C = self._joint_sizes(D, ids, n_cand)
+        ids, n_ids, C = self._joint_sizes(D, ids, n_cand, shard=shard)
+        shard = self._joint_shard(shard, C, report_k, inject)
+        if C == 0:
+            return self._joint_empty(n_ids, D, return_cand, want_lg)
         sides = []
         for i, side in enumerate((below, above)):
             w = np.asarray(side[0], dtype=np.float64)
@@ -1574,10 +1645,11 @@ class Engine(object):
         for d, p in enumerate(ps):
             a.cat_upper[d], a.cat_off[d] = len(p), off
             off += len(p)
-        return self._joint_call('tpe_joint_mixed_run', a, n_ids, C, D, return_cand, want_lg, report_k=report_k)
+        return self._joint_call('tpe_joint_mixed_run', a, n_ids, C, D, return_cand, want_lg, report_k=report_k,
+                                shard=shard)
 
     def run_joint_quant(self, below, above, low, high, cats, quants, ids, n_cand, seed, inject=None, return_cand=False,
-                        want_lg=False, return_table=False, report_k=0, stream_word=None):
+                        want_lg=False, return_table=False, report_k=0, stream_word=None, shard=None):
         """One joint stage over a group with quantised labels
         (tpe_joint_quant_run, include/tpe_hip.h "Quantised joint stage"):
         ``below`` / ``above``, ``low`` / ``high`` and ``cats`` the continuous and
@@ -1601,7 +1673,12 @@ class Engine(object):
         if Dc > N.JOINT_QUANT_MAX_CONT or Dk > N.JOINT_QUANT_MAX_DISC:
             raise ValueError('joint stage: beside a quantised dimension at most %d continuous and %d discrete ones, '
                              'not %d and %d' % (N.JOINT_QUANT_MAX_CONT, N.JOINT_QUANT_MAX_DISC, Dc, Dk))
-        ids, n_ids, C = self._joint_sizes(D, ids, n_cand)
+        ids, n_ids, C = self._joint_sizes(D, ids, n_cand, shard=shard)
+        shard = self._joint_shard(shard, C, report_k, inject)
+        if C == 0:
+            if return_table:
+                raise ValueError('joint stage: return_table needs at least one candidate')
+            return self._joint_empty(n_ids, D, return_cand, want_lg)
         edges = [np.ascontiguousarray(q[4], dtype=np.float64).reshape(-1) for q in quants]
         total = 0
         for e in edges:
@@ -1699,7 +1776,8 @@ class Engine(object):
                 'tpe_joint_quant_table_bytes')
         d_tab = self._buf('joint_qtable', (nb.value + 3) // 4, torch.float32)
         a.quant_table, a.quant_table_bytes = d_tab.data_ptr(), d_tab.numel() * 4
-        out = self._joint_call('tpe_joint_quant_run', a, n_ids, C, D, return_cand, want_lg, report_k=report_k)
+        out = self._joint_call('tpe_joint_quant_run', a, n_ids, C, D, return_cand, want_lg, report_k=report_k,
+                               shard=shard)
         if not return_table:
             return out
         tab = d_tab[:(a.k_below + a.k_above) * total].cpu().numpy()

@@ -621,3 +621,38 @@ def fit_quant_model(rows, drows, qrows, hist, below_tids, prior_weight=1.0, lf=D
                       ps, np.array([smoothing(prior_weight, len(p), nb) for p in ps]),
                       np.array([smoothing(prior_weight, len(p), na) for p in ps]),
                       [quant_lattice(r.dist, r.args) for r in qrows])
+
+
+# ------------------------------------------------------- sharded joint stage
+def empty_records(P, dtype=N.JOINT_RECORD_DTYPE):
+    """[P] records of a part that holds no candidate: global_idx -1, the rest 0
+    (what the merge kernels write for a problem without a winner)."""
+    rec = np.zeros(int(P), dtype=dtype)
+    rec['global_idx'] = -1
+    return rec
+
+
+def combine_records(stacked):
+    """[world, P] winner records (N.JOINT_RECORD_DTYPE or
+    N.JOINT_WIDE_RECORD_DTYPE) of the parts of a candidate-sharded joint stage
+    -> [P]: per problem the record the unsharded stage returns.  The order is
+    the device's (np.argmax over the float64 score l - g in candidate index
+    order): a NaN score beats every number, then the larger score wins, then
+    the lower global_idx; -0.0 ties with +0.0.  A record with global_idx < 0 is
+    empty and never wins against one that is not."""
+    stacked = np.asarray(stacked)
+    if stacked.ndim == 1:
+        return stacked.copy()
+    out = stacked[0].copy()
+    for r in range(1, stacked.shape[0]):
+        new = stacked[r]
+        with np.errstate(invalid='ignore'):
+            s_out, s_new = out['l'] - out['g'], new['l'] - new['g']
+            out_nan, new_nan = np.isnan(s_out), np.isnan(s_new)
+            lower = new['global_idx'] < out['global_idx']
+            better = (new_nan & (~out_nan | lower)) | \
+                     (~new_nan & ~out_nan & ((s_new > s_out) | ((s_new == s_out) & lower)))
+        out_empty, new_empty = out['global_idx'] < 0, new['global_idx'] < 0
+        better = (better | out_empty) & ~new_empty
+        out[better] = new[better]
+    return out

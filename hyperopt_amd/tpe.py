@@ -842,10 +842,12 @@ def suggest(new_ids, domain, trials, seed,
             linear_forgetting=_default_linear_forgetting,
             sampler='philox', precision='fp32', device=None, shard=None, shard_ids=None, shard_labels=None,
             shard_grid=None, joint=False, joint_discrete=False, joint_quantized=False, joint_wide=False,
-            joint_branches=False, joint_branches_mixed=False):
+            joint_branches=False, joint_branches_mixed=False, joint_shard=None):
     new_ids = list(new_ids)
     if not new_ids:
         return []
+    if joint_shard is not None:                  # (argument errors first, as below; nothing on the default path)
+        _joint_shard_pair(joint_shard, joint)
     if ((joint is not False and joint is not None) or joint_discrete or joint_quantized or joint_wide or joint_branches
             or joint_branches_mixed):
         # (argument errors first: no device use, no startup draw)
@@ -866,7 +868,8 @@ def suggest(new_ids, domain, trials, seed,
                               precision=precision, device=device, shard=shard, shard_ids=shard_ids,
                               shard_labels=shard_labels, shard_grid=shard_grid, joint=joint,
                               joint_discrete=joint_discrete, joint_quantized=joint_quantized, joint_wide=joint_wide,
-                              joint_branches=joint_branches, joint_branches_mixed=joint_branches_mixed)
+                              joint_branches=joint_branches, joint_branches_mixed=joint_branches_mixed,
+                              joint_shard=joint_shard)
     logger.info('tpe.suggest took %f seconds', time.time() - t0)
     return rand.docs_from_choices(new_ids, domain, trials, choices)
 
@@ -907,7 +910,8 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
                     n_EI_candidates=_default_n_EI_candidates, gamma=_default_gamma,
                     sampler='philox', precision='fp32', device=None, shard=None, columns=False,
                     shard_ids=None, shard_labels=None, shard_grid=None, joint=False, joint_discrete=False,
-                    joint_quantized=False, joint_wide=False, joint_branches=False, joint_branches_mixed=False):
+                    joint_quantized=False, joint_wide=False, joint_branches=False, joint_branches_mixed=False,
+                    joint_shard=None):
     """The suggest core on a structure-of-arrays history (``history.History``):
     per new id a {label: value or None} dict.  ``suggest`` wraps it with the
     Trials document layout; columnar callers (and bench.py's large configs)
@@ -990,9 +994,22 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
     quantised draws its continuous coordinates from another stream than without
     the keyword.  A joined category is typed as the univariate path types it, a
     quantised value is a multiple of q.  Without the keyword every plan and
-    every output byte is what ``joint_branches`` alone gives."""
+    every output byte is what ``joint_branches`` alone gives.
+
+    ``joint_shard=(rank, world)`` (with ``joint`` and any of the keywords
+    above): the candidates of every joint stage are split over the ranks of the
+    default process group (DESIGN.md "Sharded joint stage").  The univariate
+    pass runs whole on every rank; a rank scores the candidate indices
+    dist.shard_range(n_EI_candidates, rank, world) of the root group's stage
+    and of the branch stage, and one all-gather per stage brings every rank all
+    winner records (joint.combine_records).  Every rank returns the whole
+    result, byte for byte that of the same call without the keyword.
+    n_EI_candidates < 2^31.  It does not combine with the four ``shard*``
+    arguments, and joint_candidate_report does not take it."""
     if sampler not in ('philox', 'replay'):
         raise ValueError("sampler must be 'philox' or 'replay'")
+    if joint_shard is not None:
+        joint_shard = _joint_shard_pair(joint_shard, joint)
     group, branch_groups = None, []
     if ((joint is not False and joint is not None) or joint_discrete or joint_quantized or joint_wide or joint_branches
             or joint_branches_mixed):
@@ -1010,13 +1027,79 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
                                 columns, shard_ids, shard_labels, shard_grid)
     if group is not None or branch_groups:
         return _suggest_joint(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, device, columns, group,
-                              branch_groups)
+                              branch_groups, joint_shard)
     return _suggest_local(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, sampler, precision,
                           device, shard, columns)
 
 
 TPE_JOINT_MAX_DIMS = N.JOINT_MAX_DIMS
 TPE_JOINT_WIDE_MAX_DIMS = N.JOINT_WIDE_MAX_DIMS
+
+
+def _joint_shard_pair(joint_shard, joint):
+    """(rank, world) of a ``joint_shard`` argument as ints, or None; ValueError
+    without ``joint`` and for anything but a pair of ints with 0 <= rank <
+    world.  Touches no device."""
+    if joint_shard is None:
+        return None
+    if joint is False or joint is None:
+        raise ValueError('joint_shard needs joint=True or joint=[labels]: it only shards the joint stages')
+    ok = isinstance(joint_shard, (tuple, list)) and len(joint_shard) == 2 and \
+        all(isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) for v in joint_shard)
+    if not ok or not 0 <= joint_shard[0] < joint_shard[1]:
+        raise ValueError('joint_shard must be a pair of ints (rank, world) with 0 <= rank < world: %r' % (joint_shard,))
+    return int(joint_shard[0]), int(joint_shard[1])
+
+
+class _JointParts(object):
+    """This rank's part of every joint stage of a ``joint_shard`` suggest: its
+    candidate range [lo, hi) of ``C`` and the exchange of the winner records
+    (None in a world of one rank, unless dist.EXCHANGE_ALWAYS)."""
+
+    def __init__(self, engine, joint_shard, C):
+        import torch.distributed as td
+        rank, world = joint_shard
+        self.C = int(C)
+        if self.C >= 2 ** 31:
+            raise ValueError('joint_shard: n_EI_candidates must be below 2^31')
+        self.ex = None
+        up = td.is_available() and td.is_initialized()
+        g_rank, g_world = (td.get_rank(), td.get_world_size()) if up else (0, 1)
+        if (g_rank, g_world) != (rank, world):
+            raise ValueError('joint_shard (%d, %d) is not this process group (rank %d of %d)'
+                             % (rank, world, g_rank, g_world))
+        if up and (world > 1 or _dist.EXCHANGE_ALWAYS):
+            self.ex = _dist.exchange_for(engine)     # (collective on the first sharded call)
+        self.lo, self.hi = _dist.shard_range(self.C, rank, world)
+
+    @property
+    def n_cand(self):
+        return self.hi - self.lo
+
+    @property
+    def shard(self):
+        return self.lo, self.C
+
+    def records(self, run, P, dtype):
+        """``run()`` gives this rank's [P] records of one stage; all ranks'
+        records, combined.  A rank whose stage failed still takes part in the
+        gather (status word): every rank raises and none waits."""
+        failed, err, rec = False, None, None
+        try:
+            rec = run()
+        except Exception as e:
+            failed, err = True, e
+        if self.ex is None:
+            if err is not None:
+                raise err
+            return rec
+        try:
+            stacked = _dist.gather_joint_records(self.ex, rec, P, dtype, failed)
+        except RuntimeError:
+            if err is not None:
+                raise err
+            raise
+        return _joint.combine_records(stacked)
 
 
 def _joint_group(table, joint, sampler, precision, shards, discrete=False, quantized=False, wide=False):
@@ -1296,7 +1379,7 @@ def _run_root_group(engine, group, hist, ids, seed, prior_weight, n_EI_candidate
 
 
 def _suggest_joint(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, device, columns, group,
-                   branch_groups=()):
+                   branch_groups=(), joint_shard=None):
     """The univariate suggest of every label (the joined labels' univariate
     winners are discarded: each costs one problem of the level's batch, and the
     other labels' values are then the same bytes as without ``joint``), then
@@ -1304,7 +1387,9 @@ def _suggest_joint(table, hist, new_ids, seed, prior_weight, n_EI_candidates, ga
     group's columns, then one segmented stage over the branch groups: group g
     applies to the ids for which its labels are active, and its winners fill
     its columns for those ids only (a joined label gates nothing, so the
-    routing is the univariate pass's)."""
+    routing is the univariate pass's).  ``joint_shard``: the two joint stages
+    run over this rank's candidate range and exchange their records
+    (_JointParts); the univariate pass is replicated."""
     cc = _suggest_local(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, 'philox', 'fp32', device,
                         None, True)
     if len(cc) == 0:
@@ -1313,8 +1398,20 @@ def _suggest_joint(table, hist, new_ids, seed, prior_weight, n_EI_candidates, ga
     ids = np.asarray(new_ids, dtype=np.int64).reshape(-1)
     values = np.array(cc.values, dtype=np.float64)
     active = np.array(cc.active, dtype=bool)
-    if group is not None:
+    parts = None if joint_shard is None else _JointParts(engine, joint_shard, n_EI_candidates)
+    if group is not None and parts is not None:
+        got = []
+
+        def run():
+            got[:] = _run_root_group(engine, group, hist, ids, seed, prior_weight, parts.n_cand, gamma,
+                                     shard=parts.shard)
+            return got[2]
+        rec = parts.records(run, len(ids), N.JOINT_WIDE_RECORD_DTYPE if len(group) > TPE_JOINT_MAX_DIMS
+                            else N.JOINT_RECORD_DTYPE)
+        group, model = got[0], got[1]
+    elif group is not None:
         group, model, rec = _run_root_group(engine, group, hist, ids, seed, prior_weight, n_EI_candidates, gamma)
+    if group is not None:
         if (rec['global_idx'] < 0).any():
             raise RuntimeError('no joint candidate selected')
         vals = model.values(rec['z'][:, :len(group)])
@@ -1323,7 +1420,7 @@ def _suggest_joint(table, hist, new_ids, seed, prior_weight, n_EI_candidates, ga
             active[:, r.index] = True
     if branch_groups:
         _suggest_branches(engine, hist, ids, seed, prior_weight, n_EI_candidates, gamma, branch_groups,
-                          np.asarray(cc.active, dtype=bool), values)
+                          np.asarray(cc.active, dtype=bool), values, parts)
     cc = ChoiceColumns(table.labels, values, active)
     return cc if columns else cc.dicts(table)
 
@@ -1341,10 +1438,13 @@ def _fit_branch_model(rows, hist, below_tids, prior_weight):
     return rows, _joint.fit_model(rows, hist, below_tids, prior_weight, DEFAULT_LF)
 
 
-def _suggest_branches(engine, hist, ids, seed, prior_weight, n_EI_candidates, gamma, branch_groups, taken, values):
+def _suggest_branches(engine, hist, ids, seed, prior_weight, n_EI_candidates, gamma, branch_groups, taken, values,
+                      parts=None):
     """The segmented joint stage of a suggest: one problem per (new id, branch
     group whose labels are active for it in ``taken`` [n_ids x n_labels]), all
-    in one Engine.run_joint_segments call; the winners overwrite ``values``."""
+    in one Engine.run_joint_segments call; the winners overwrite ``values``.
+    ``parts`` (_JointParts): the call covers this rank's candidates, and the
+    records of all ranks are combined."""
     below_tids = _history.split_below(hist, gamma)
     models, words, prob_seg, prob_id, where = [], [], [], [], []
     for rows in branch_groups:
@@ -1363,7 +1463,11 @@ def _suggest_branches(engine, hist, ids, seed, prior_weight, n_EI_candidates, ga
         words.append(_joint.branch_stream_word(rows))
     if not models:
         return
-    rec = engine.run_joint_segments(models, words, prob_seg, prob_id, int(n_EI_candidates), seed)
+    if parts is None:
+        rec = engine.run_joint_segments(models, words, prob_seg, prob_id, int(n_EI_candidates), seed)
+    else:
+        rec = parts.records(lambda: engine.run_joint_segments(models, words, prob_seg, prob_id, parts.n_cand, seed,
+                                                              shard=parts.shard), len(prob_seg), N.JOINT_RECORD_DTYPE)
     if (rec['global_idx'] < 0).any():
         raise RuntimeError('no joint candidate selected')
     p = 0

@@ -1602,6 +1602,44 @@ int tpe_joint_mseg_run(const tpe_joint_mseg_args* args, tpe_joint_record* record
                        double* g_out, void* scratch, uint64_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Sharded joint stage (additive export; the ABI stays 24).  Any of the six
+ * joint stages over the candidates [cand_base, cand_base + n_cand) of a run of
+ * n_cand_global candidates: a rank's share of a candidate-sharded joint
+ * suggest (tpe.suggest(..., joint_shard=(rank, world))).
+ *
+ * `stage` names the entry point whose `args` and record type the call takes
+ * (TPE_JOINT_STAGE_*).  args->n_cand is the LOCAL count; local candidate i is
+ * global candidate g = cand_base + i.  The first Philox counter word of every
+ * draw is g (everything else about the draws as the stage documents it), and
+ * record.global_idx is g.  cand, l_out and g_out are local arrays indexed by
+ * i, and scratch (and the table workspace) are sized by the stage's own
+ * *_scratch_bytes / *_table_bytes at the local n_cand.  A candidate is a
+ * function of (seed, stream word, new id, g) alone and a record's order key of
+ * (score, g), so the records of the parts of a partition, combined in
+ * np.argmax order (NaN first, the larger l - g, the lower global_idx; an empty
+ * record, global_idx < 0, never wins), are the bytes of the unsharded run.
+ * The six stage entry points are this call with shard {0, n_cand}.
+ *
+ * Returns TPE_E_ARG before any launch (no device needed) for null args or
+ * shard, a stage outside [0, 5], cand_base < 0, cand_base + n_cand >
+ * n_cand_global, n_cand_global >= 2^31 (the counter word and the index
+ * arithmetic are 32-bit), TPE_JOINT_INJECT with cand_base != 0 (injected rows
+ * have no global index), and for everything the stage's own entry point
+ * rejects.  Advances the resident-level epoch as the stage runs do.
+ * ---------------------------------------------------------------------- */
+#define TPE_JOINT_STAGE_RUN 0   /* args: tpe_joint_args,       records: tpe_joint_record      */
+#define TPE_JOINT_STAGE_WIDE 1  /*       tpe_joint_wide_args,           tpe_joint_wide_record */
+#define TPE_JOINT_STAGE_MIXED 2 /*       tpe_joint_mixed_args,          tpe_joint_record      */
+#define TPE_JOINT_STAGE_QUANT 3 /*       tpe_joint_quant_args                                 */
+#define TPE_JOINT_STAGE_SEG 4   /*       tpe_joint_seg_args                                   */
+#define TPE_JOINT_STAGE_MSEG 5  /*       tpe_joint_mseg_args                                  */
+typedef struct tpe_joint_shard {
+  int64_t cand_base, n_cand_global;
+} tpe_joint_shard;
+int tpe_joint_run_shard(int32_t stage, const void* args, const tpe_joint_shard* shard, void* records, float* cand,
+                        double* l_out, double* g_out, void* scratch, uint64_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Host phase clock of tpe_suggest_tree (tools/native_split.py).  While
  * enabled, a call records the steady-clock microseconds since its entry at
  * each phase below (a tree of several level runs: the last run's phases);
