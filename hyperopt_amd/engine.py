@@ -24,6 +24,7 @@ import os
 import numpy as np
 
 from . import _native as N
+from . import joint_pack as JP
 from . import parzen
 
 try:
@@ -36,6 +37,8 @@ try:                                    # (the native trampoline of tpe_suggest_
     from ._hostaddr import call_tree as _CALL_TREE
 except ImportError:                     # pragma: no cover
     _CALL_TREE = None
+# the torch dtype of a row of joint_pack.ROWS
+_TORCH_OF = {np.float32: torch.float32, np.float64: torch.float64} if torch is not None else {}
 
 # target number of above-mixture work items per launch (>= 8 per CU on 256 CUs)
 TARGET_WORK = 2048
@@ -976,7 +979,7 @@ class Engine(object):
         return d_top, d_ntop, d_stats
 
     def run_joint(self, below, above, low, high, ids, n_cand, seed, inject=None, return_cand=False, want_lg=False,
-                  report_k=0, shard=None):
+                  report_k=0, shard=None, stream_word=None):
         """One joint TPE stage (tpe_joint_run, include/tpe_hip.h "Joint
         (multivariate) TPE stage"): ``below`` / ``above`` = (w [K], mu [K, D],
         sigma [K, D]) float64 mixtures (joint.side_mixture), ``low`` / ``high``
@@ -1001,60 +1004,96 @@ class Engine(object):
         joint.combine_records over the parts of a partition gives the unsharded
         records.  ``n_cand`` may then be 0 (a rank whose range is empty): empty
         records (joint.empty_records) and no native call.  ``report_k`` > 0 or
-        ``inject`` with a non-zero cand_base raise ValueError."""
+        ``inject`` with a non-zero cand_base raise ValueError.
+        ``stream_word`` (every solo run_joint* method): the Philox stream word
+        (None: N.JOINT_STREAM; a branch group's joint.branch_stream_word, to
+        compare with run_joint_segments)."""
         return self._joint_continuous(False, below, above, low, high, ids, n_cand, seed, inject, return_cand, want_lg,
-                                      report_k=report_k, shard=shard)
+                                      stream_word, report_k, shard)
 
     def run_joint_wide(self, below, above, low, high, ids, n_cand, seed, inject=None, return_cand=False,
-                       want_lg=False, report_k=0, shard=None):
+                       want_lg=False, report_k=0, shard=None, stream_word=None):
         """``run_joint`` for up to N.JOINT_WIDE_MAX_DIMS dimensions
         (tpe_joint_wide_run, include/tpe_hip.h "Wide joint stage"): the same
         arguments, model, Philox streams and return shapes; the records are
         N.JOINT_WIDE_RECORD_DTYPE."""
         return self._joint_continuous(True, below, above, low, high, ids, n_cand, seed, inject, return_cand, want_lg,
-                                      report_k=report_k, shard=shard)
+                                      stream_word, report_k, shard)
 
     def _joint_continuous(self, wide, below, above, low, high, ids, n_cand, seed, inject, return_cand, want_lg,
                           stream_word=None, report_k=0, shard=None):
-        """``stream_word``: the Philox stream word (None: N.JOINT_STREAM; a branch
-        group's joint.branch_stream_word, to compare with run_joint_segments)."""
-        from . import joint as J
-        low, high = np.asarray(low, dtype=np.float64), np.asarray(high, dtype=np.float64)
-        D = len(low)
-        ids, n_ids, C = self._joint_sizes(D, ids, n_cand, N.JOINT_WIDE_MAX_DIMS if wide else N.JOINT_MAX_DIMS, shard)
+        """``run_joint`` (``wide``: ``run_joint_wide``) with the arguments in
+        the order this entry has always had; callers that reach past the two
+        public methods keep working."""
+        return self._joint_solo('wide' if wide else 'run', below, above, low, high, (), (), ids, n_cand, seed, inject,
+                                return_cand, want_lg, report_k, stream_word, shard)
+
+    # the solo stages by joint_pack entry: the args struct and the native function
+    _JOINT_SOLO = {'run': (N.JointArgs, 'tpe_joint_run'), 'wide': (N.JointWideArgs, 'tpe_joint_wide_run'),
+                   'mixed': (N.JointMixedArgs, 'tpe_joint_mixed_run'),
+                   'quant': (N.JointQuantArgs, 'tpe_joint_quant_run')}
+
+    def _joint_solo(self, entry, below, above, low, high, cats, quants, ids, n_cand, seed, inject, return_cand,
+                    want_lg, report_k, stream_word, shard, return_table=False):
+        """What the four solo stages share: the group's rows (joint_pack.group_rows,
+        which also checks the group; an empty part of a sharded stage is checked
+        too), one upload per row, the args struct filled from the same rows
+        record, the call and its results.  The library derives the f32 bounds
+        from the float64 ``low`` / ``high`` in the struct; a quantised label's
+        lattice ends follow the continuous bounds there."""
+        r = JP.group_rows(below, above, low, high, cats, quants, entry=entry)
+        Dc, Dk, Dq = r['Dc'], r['Dk'], r['Dq']
+        D, wide = Dc + Dk + Dq, entry == 'wide'
+        ids, n_ids, C = self._joint_sizes(D, ids, n_cand, shard)
         shard = self._joint_shard(shard, C, report_k, inject)
-        for side in (below, above):
-            if side[1].shape != (len(side[0]), D) or side[2].shape != side[1].shape:
-                raise ValueError('joint stage: mixture shapes do not match %d dimensions' % D)
         if C == 0:
+            if return_table:
+                raise ValueError('joint stage: return_table needs at least one candidate')
             return self._joint_empty(n_ids, D, return_cand, want_lg, wide)
         up = self._joint_up
-        a = N.JointWideArgs() if wide else N.JointArgs()
-        a.n_dims, a.n_cand, a.n_ids, a.flags = D, C, n_ids, 0
-        a.k_below, a.k_above = len(below[0]), len(above[0])
+        struct, fn = self._JOINT_SOLO[entry]
+        a = struct()
+        a.n_dims, a.n_cand, a.n_ids, a.flags = Dc, C, n_ids, 0
+        a.k_below, a.k_above = r['k_below'], r['k_above']
+        a.below_base, a.above_base = r['below_base'], r['above_base']
         a.stream_word = N.JOINT_STREAM if stream_word is None else int(stream_word)
         a.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        for name, side in (('below', below), ('above', above)):
-            mu, aa, c, base = J.density_rows(side[0], side[1], side[2], low, high)
-            setattr(a, name + '_mu', up(name + '_mu', mu, torch.float32))
-            setattr(a, name + '_a', up(name + '_a', aa, torch.float32))
-            setattr(a, name + '_c', up(name + '_c', c, torch.float32))
-            setattr(a, name + '_base', base)
-        cum, rows = J.sampler_rows(below[0], below[1], below[2], low, high)
-        a.samp_cum, a.samp = up('cum', cum, torch.float64), up('samp', rows, torch.float32)
+        for key, field, buf, dtype, part in JP.group_rows_present(r):
+            # tpe_joint_quant_run takes null pointers for the rows of an absent continuous part
+            if not (entry == 'quant' and part == 'cont' and Dc == 0):
+                setattr(a, field, up(buf, r[key], _TORCH_OF[dtype]))
         a.ids = up('ids', ids, torch.int64)
-        self._joint_inject(a, inject, C, D)
-        for d in range(D):
-            a.low[d], a.high[d] = low[d], high[d]
-        return self._joint_call('tpe_joint_wide_run' if wide else 'tpe_joint_run', a, n_ids, C, D, return_cand,
-                                want_lg, wide=wide, report_k=report_k, shard=shard)
+        if inject is not None:
+            a.flags |= N.JOINT_INJECT
+            a.inject = up('inject', JP.inject_rows(inject, C, D), torch.float32)
+        for d in range(Dc):
+            a.low[d], a.high[d] = r['low'][d], r['high'][d]
+        if Dk:
+            a.n_cat = Dk
+            for d in range(Dk):
+                a.cat_upper[d], a.cat_off[d] = r['cat_upper'][d], r['cat_off'][d]
+        if Dq:
+            a.n_quant, a.n_edges = Dq, len(r['quant_edges'])
+            for d in range(Dq):
+                a.low[Dc + d], a.high[Dc + d] = r['qlow'][d], r['qhigh'][d]
+                a.quant_v[d], a.quant_edge_off[d] = r['quant_v'][d], r['quant_edge_off'][d]
+            total = r['n_lattice']
+            nb = ctypes.c_uint64(0)
+            N.check(self.lib.tpe_joint_quant_table_bytes(a.k_below, a.k_above, total, ctypes.byref(nb)), self.lib,
+                    'tpe_joint_quant_table_bytes')
+            d_tab = self._buf('joint_qtable', (nb.value + 3) // 4, torch.float32)
+            a.quant_table, a.quant_table_bytes = d_tab.data_ptr(), d_tab.numel() * 4
+        out = self._joint_call(fn, a, n_ids, C, D, return_cand, want_lg, wide=wide, report_k=report_k, shard=shard)
+        if not return_table:
+            return out
+        tab = d_tab[:(a.k_below + a.k_above) * total].cpu().numpy()
+        tb = tab[:total * a.k_below].reshape(total, a.k_below).T.copy()
+        ta = tab[total * a.k_below:].reshape(total, a.k_above).T.copy()
+        return (out if isinstance(out, tuple) else (out,)) + (tb, ta)
 
-    # what run_joint and run_joint_mixed share: the size checks, the uploads, the call and its results
-    def _joint_sizes(self, D, ids, n_cand, max_dims=N.JOINT_MAX_DIMS, shard=None):
+    def _joint_sizes(self, D, ids, n_cand, shard=None):
         ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
         n_ids, C = len(ids), int(n_cand)
-        if not 1 <= D <= max_dims:
-            raise ValueError('joint stage: %d dimensions, at most %d' % (D, max_dims))
         if C < (1 if shard is None else 0) or C >= 2 ** 31 or n_ids < 1:   # (an empty part of a sharded stage: C = 0)
             raise ValueError('joint stage: n_cand / ids out of range')
         if n_ids * C * max(D, 2) >= 2 ** 31:
@@ -1115,15 +1154,6 @@ class Engine(object):
         t = self._buf('joint_' + name, arr.size, dtype)
         t[:arr.size].copy_(torch.from_numpy(np.ascontiguousarray(arr).reshape(-1)))
         return t.data_ptr()
-
-    def _joint_inject(self, a, inject, C, D):
-        if inject is None:
-            return
-        inj = np.ascontiguousarray(inject, dtype=np.float32)
-        if inj.shape != (C, D):
-            raise ValueError('joint stage: inject must be [n_cand, %d]' % D)
-        a.flags |= N.JOINT_INJECT
-        a.inject = self._joint_up('inject', inj, torch.float32)
 
     def _joint_call(self, fn, a, n_ids, C, D, return_cand, want_lg, wide=False, report_k=0, shard=None):
         """Scratch and result buffers, the native call ``fn`` and the records
@@ -1235,90 +1265,35 @@ class Engine(object):
         are those of the solo run of its group's kind; D_group counts the
         continuous, discrete and quantised coordinates, in that order.  With
         continuous groups only nothing changes: tpe_joint_seg_run, the same blob."""
-        from . import joint as J
-        if any(self._seg_parts(m)[4] or self._seg_parts(m)[5] for m in models):
-            return self._run_joint_msegments(models, stream_words, prob_seg, prob_id, n_cand, seed, inject,
-                                             return_cand, want_lg, report_k, shard)
-        S, C = len(models), int(n_cand)
+        # the choice of stage: continuous groups only keep tpe_joint_seg_run and its smaller descriptors
+        mixed = any(JP.seg_parts(m)[4] or JP.seg_parts(m)[5] for m in models)
+        C = int(n_cand)
         report_k = self._report_k(report_k)
         shard = self._joint_shard(shard, C, report_k, inject)
-        dev_cand, dev_lg = return_cand or report_k > 0, want_lg or report_k > 0
-        prob_seg = np.ascontiguousarray(prob_seg, dtype=np.int32).reshape(-1)
-        prob_id = np.ascontiguousarray(prob_id, dtype=np.int64).reshape(-1)
-        P = len(prob_seg)
-        if S < 1 or len(stream_words) != S:
-            raise ValueError('joint stage: one stream word per group, at least one group')
-        if P < 1 or len(prob_id) != P or C < (1 if shard is None else 0) or C >= 2 ** 31:
-            raise ValueError('joint stage: n_cand / problems out of range')
-        if prob_seg.min() < 0 or prob_seg.max() >= S:
-            raise ValueError('joint stage: a problem names a group outside [0, %d)' % S)
+        b = JP.segment_blob(models, stream_words, prob_seg, prob_id, C, inject,
+                            N.JOINT_MSEG_DTYPE if mixed else N.JOINT_SEG_DTYPE, empty_ok=shard is not None)
+        P = len(b.prob_seg)
         if C == 0:                                   # an empty part of a sharded stage
-            widths = [sum(len(x) for x in self._seg_parts(models[s])[3:]) for s in prob_seg]
-            return self._joint_empty(P, 0, return_cand, want_lg, widths=widths)
-        if inject is not None and len(inject) != S:
-            raise ValueError('joint stage: inject must hold one entry per group')
-        segs = np.zeros(S, dtype=N.JOINT_SEG_DTYPE)
-        f32, f64 = [], []
-        n32 = n64 = 0
-
-        def put32(arr):
-            nonlocal n32
-            arr = np.ascontiguousarray(arr, dtype=np.float32).reshape(-1)
-            f32.append(arr)
-            n32 += arr.size
-            return n32 - arr.size
-        dims = np.empty(S, dtype=np.int64)
-        for s, m in enumerate(models):
-            below, above, low, high = (m.below, m.above, m.low, m.high) if hasattr(m, 'below') else m
-            low, high = np.asarray(low, dtype=np.float64), np.asarray(high, dtype=np.float64)
-            D = dims[s] = len(low)
-            if not 1 <= D <= N.JOINT_MAX_DIMS:
-                raise ValueError('joint stage: %d dimensions, at most %d' % (D, N.JOINT_MAX_DIMS))
-            g = segs[s]
-            g['n_dims'], g['k_below'], g['k_above'] = D, len(below[0]), len(above[0])
-            g['stream_word'] = int(stream_words[s])
-            for name, side in (('below', below), ('above', above)):
-                if side[1].shape != (len(side[0]), D) or side[2].shape != side[1].shape:
-                    raise ValueError('joint stage: mixture shapes do not match %d dimensions' % D)
-                mu, aa, c, base = J.density_rows(side[0], side[1], side[2], low, high)
-                g[name + '_mu'], g[name + '_a'], g[name + '_c'] = put32(mu), put32(aa), put32(c)
-                g[name + '_base'] = base
-            cum, rows = J.sampler_rows(below[0], below[1], below[2], low, high)
-            g['samp'] = put32(rows)
-            g['samp_cum'] = n64
-            f64.append(cum)
-            n64 += cum.size
-            g['inject'] = -1
-            if inject is not None and inject[s] is not None:
-                inj = np.ascontiguousarray(inject[s], dtype=np.float32)
-                if inj.shape != (C, D):
-                    raise ValueError('joint stage: inject must be [n_cand, %d]' % D)
-                g['inject'] = put32(inj)
-            g['lo'], g['hi'] = np.float32(-np.inf), np.float32(np.inf)
-            g['lo'][:D], g['hi'][:D] = J.f32_bounds(low, high)
-        if inject is not None and any(inject[s] is None for s in np.unique(prob_seg)):
-            raise ValueError('joint stage: inject lacks the candidates of a group that has a problem')
-        pd = dims[prob_seg]
-        cand_off = np.concatenate([[0], np.cumsum(C * pd)]).astype(np.int64)
-        if P * C >= 2 ** 31 or cand_off[-1] >= 2 ** 31:
-            raise ValueError('joint stage: %d problems x %d candidates do not fit one run' % (P, C))
-
-        # one blob: 8-byte items first (descriptors, the f64 pool, ids, offsets), then the 4-byte ones
-        parts = [segs.view(np.uint8), np.concatenate(f64).view(np.uint8), prob_id.view(np.uint8),
-                 cand_off[:P].view(np.uint8), np.concatenate(f32).view(np.uint8), prob_seg.view(np.uint8)]
-        offs = np.concatenate([[0], np.cumsum([len(x) for x in parts])])
-        blob = np.concatenate(parts)
-        d_blob = self._buf('joint_seg_blob', len(blob), torch.uint8)
-        d_blob[:len(blob)].copy_(torch.from_numpy(blob))
-        base = d_blob.data_ptr()
-        a = N.JointSegArgs()
-        a.n_segs, a.n_probs, a.n_cand, a.flags = S, P, C, N.JOINT_INJECT if inject is not None else 0
+            return self._joint_empty(P, 0, return_cand, want_lg, widths=b.widths)
+        d_blob = self._buf('joint_seg_blob', len(b.blob), torch.uint8)
+        d_blob[:len(b.blob)].copy_(torch.from_numpy(b.blob))
+        a = N.JointMSegArgs() if mixed else N.JointSegArgs()
+        a.n_segs, a.n_probs, a.n_cand, a.flags = len(models), P, C, N.JOINT_INJECT if inject is not None else 0
         a.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        a.segs, a.host_segs = base + int(offs[0]), segs.ctypes.data
-        a.pool_f64, a.prob_id, a.cand_off = base + int(offs[1]), base + int(offs[2]), base + int(offs[3])
-        a.pool_f32, a.prob_seg, a.host_prob_seg = base + int(offs[4]), base + int(offs[5]), prob_seg.ctypes.data
-        a.pool_f32_len, a.pool_f64_len = n32, n64
-        return self._joint_seg_call('tpe_joint_seg', a, P, C, cand_off, pd, return_cand, want_lg, report_k, shard)
+        for name, off in zip(JP.SECTIONS, b.offs):
+            setattr(a, name, d_blob.data_ptr() + int(off))
+        a.host_segs, a.host_prob_seg = b.segs.ctypes.data, b.prob_seg.ctypes.data
+        a.pool_f32_len, a.pool_f64_len = b.n32, b.n64
+        if mixed:
+            nb = ctypes.c_uint64(0)
+            N.check(self.lib.tpe_joint_mseg_table_bytes(b.segs.ctypes.data, len(models), ctypes.byref(nb)), self.lib,
+                    'tpe_joint_mseg_table_bytes')
+            assert nb.value == 4 * b.n_table, (nb.value, b.n_table)
+            if b.n_table:
+                d_tab = self._buf('joint_mseg_table', b.n_table, torch.float32)
+                a.quant_table, a.quant_table_bytes = d_tab.data_ptr(), d_tab.numel() * 4
+        return self._joint_seg_call('tpe_joint_mseg' if mixed else 'tpe_joint_seg', a, P, C, b.cand_off, b.widths,
+                                    return_cand, want_lg, report_k, shard)
 
     def _joint_seg_call(self, fn, a, P, C, cand_off, pd, return_cand, want_lg, report_k, shard=None):
         """What the two segmented stages share: scratch and the result block, the
@@ -1363,211 +1338,6 @@ class Engine(object):
             res.extend(self._joint_report_host(rep, P, report_k, pd))
         return tuple(res)
 
-    @staticmethod
-    def _seg_parts(m):
-        """(below, above, low, high, cats, quants) of one group of
-        run_joint_segments: a model object or a tuple of 4, 5 or 6 entries;
-        below / above = (w, mu, sigma)."""
-        if hasattr(m, 'below'):
-            cats = m.cats() if hasattr(m, 'drows') else []
-            quants = m.quants() if hasattr(m, 'qrows') else []
-            return m.below[:3], m.above[:3], m.low, m.high, cats, quants
-        m = tuple(m)
-        return m[0][:3], m[1][:3], m[2], m[3], list(m[4]) if len(m) > 4 else [], list(m[5]) if len(m) > 5 else []
-
-    def _mseg_rows(self, below, above, low, high, cats, quants):
-        """The device rows of one group with discrete or quantised labels, as
-        run_joint_mixed / run_joint_quant make them (the same functions of
-        joint.py on the same arguments: the same bytes): a dict of arrays, the
-        per-side ones under 'below_..' / 'above_..'."""
-        from . import joint as J
-        low, high = np.asarray(low, dtype=np.float64).reshape(-1), np.asarray(high, dtype=np.float64).reshape(-1)
-        Dc, Dk, Dq = len(low), len(cats), len(quants)
-        if Dq > N.JOINT_MAX_QUANT:
-            raise ValueError('joint stage: %d quantised dimensions, at most %d' % (Dq, N.JOINT_MAX_QUANT))
-        if Dc > N.JOINT_MSEG_MAX_CONT or Dk > N.JOINT_MSEG_MAX_CAT:
-            raise ValueError('joint stage: a segment with discrete or quantised dimensions holds at most %d continuous '
-                             'and %d discrete ones, not %d and %d' % (N.JOINT_MSEG_MAX_CONT, N.JOINT_MSEG_MAX_CAT, Dc, Dk))
-        edges = [np.ascontiguousarray(q[4], dtype=np.float64).reshape(-1) for q in quants]
-        for e in edges:
-            if not 2 <= len(e) - 1 <= N.JOINT_MAX_LATTICE:
-                raise ValueError('joint stage: %d lattice values, outside [2, %d]' % (len(e) - 1, N.JOINT_MAX_LATTICE))
-            if not (np.isfinite(e).all() and (np.diff(e) > 0).all()):
-                raise ValueError('joint stage: the lattice edges must be finite and strictly increasing')
-        if sum(len(e) - 1 for e in edges) > N.JOINT_MAX_LATTICE_TOTAL:
-            raise ValueError('joint stage: %d lattice values in the group, at most %d'
-                             % (sum(len(e) - 1 for e in edges), N.JOINT_MAX_LATTICE_TOTAL))
-        ps = [np.asarray(c[2], dtype=np.float64).reshape(-1) for c in cats]
-        for p in ps:
-            if not 2 <= len(p) <= N.JOINT_MAX_CATS:
-                raise ValueError('joint stage: %d categories, outside [2, %d]' % (len(p), N.JOINT_MAX_CATS))
-            if not (p > 0).all():
-                raise ValueError('joint stage: a prior probability of 0')
-        if sum(len(p) for p in ps) > N.JOINT_MAX_CAT_TOTAL:
-            raise ValueError('joint stage: %d categories in the group, at most %d'
-                             % (sum(len(p) for p in ps), N.JOINT_MAX_CAT_TOTAL))
-        s_side = [np.array([float(c[3 + i]) for c in cats]) for i in (0, 1)]
-        if not all((s > 0).all() and np.isfinite(s).all() for s in s_side):
-            raise ValueError('joint stage: the smoothing masses must be positive')
-        r = dict(Dc=Dc, Dk=Dk, Dq=Dq, low=low, high=high, ps=ps, edges=edges)
-        sides = []
-        for i, (name, side) in enumerate((('below', below), ('above', above))):
-            w = np.asarray(side[0], dtype=np.float64)
-            mu = np.asarray(side[1], dtype=np.float64).reshape(len(w), -1)
-            sigma = np.asarray(side[2], dtype=np.float64).reshape(len(w), -1)
-            if mu.shape != (len(w), Dc) or sigma.shape != mu.shape:
-                raise ValueError('joint stage: mixture shapes do not match %d dimensions' % Dc)
-            cols = [np.asarray(c[i], dtype=np.int64).reshape(-1) for c in cats]
-            qmu = [np.asarray(q[2 * i], dtype=np.float64).reshape(-1) for q in quants]
-            qsig = [np.asarray(q[2 * i + 1], dtype=np.float64).reshape(-1) for q in quants]
-            if any(len(col) != len(w) for col in cols + qmu + qsig):
-                raise ValueError('joint stage: one category / (mu, sigma) per component and dimension')
-            for d, col in enumerate(cols):
-                if col.min() < -1 or col.max() >= len(ps[d]):
-                    raise ValueError('joint stage: a component category outside [-1, %d)' % len(ps[d]))
-            xc = np.stack(cols, axis=1) if cols else np.zeros((len(w), 0), dtype=np.int64)
-            if Dk:
-                mu32, aa, c, base, cat32, miss, bonus = J.mixed_density_rows(w, mu, sigma, low, high, xc, ps, s_side[i])
-                r[name + '_cat'], r[name + '_miss'], r[name + '_bonus'] = cat32, miss, bonus
-            else:
-                mu32, aa, c, base = J.density_rows(w, mu, sigma, low, high)
-            r[name + '_mu'], r[name + '_a'], r[name + '_c'], r[name + '_base'] = mu32, aa, c, base
-            if Dq:
-                qsig = np.stack(qsig, axis=1)
-                if not ((qsig > 0).all() and np.isfinite(qsig).all()):
-                    raise ValueError('joint stage: the quantised bandwidths must be positive')
-                r[name + '_qmu'], r[name + '_qsigma'] = np.stack(qmu, axis=1), qsig
-            sides.append((w, mu, sigma))
-        w, mu, sigma = sides[0]
-        if Dk:
-            r['cum'], r['samp'], r['below_h'], r['cat_cum'] = J.mixed_sampler_rows(w, mu, sigma, low, high, ps, s_side[0])
-        else:
-            r['cum'], r['samp'] = J.sampler_rows(w, mu, sigma, low, high)
-        if Dq:
-            qlow, qhigh = np.array([e[0] for e in edges]), np.array([e[-1] for e in edges])
-            r['quant_samp'] = J.sampler_rows(w, r['below_qmu'], r['below_qsigma'], qlow, qhigh)[1]
-            r['qlo'], r['qhi'] = J.f32_bounds(qlow, qhigh)
-        return r
-
-    def _run_joint_msegments(self, models, stream_words, prob_seg, prob_id, n_cand, seed, inject, return_cand,
-                             want_lg, report_k, shard=None):
-        """run_joint_segments through tpe_joint_mseg_run: every group, whatever
-        its kind, packed into the two pools behind one array of tpe_joint_mseg."""
-        from . import joint as J
-        S, C = len(models), int(n_cand)
-        report_k = self._report_k(report_k)
-        shard = self._joint_shard(shard, C, report_k, inject)
-        prob_seg = np.ascontiguousarray(prob_seg, dtype=np.int32).reshape(-1)
-        prob_id = np.ascontiguousarray(prob_id, dtype=np.int64).reshape(-1)
-        P = len(prob_seg)
-        if S < 1 or len(stream_words) != S:
-            raise ValueError('joint stage: one stream word per group, at least one group')
-        if P < 1 or len(prob_id) != P or C < (1 if shard is None else 0) or C >= 2 ** 31:
-            raise ValueError('joint stage: n_cand / problems out of range')
-        if prob_seg.min() < 0 or prob_seg.max() >= S:
-            raise ValueError('joint stage: a problem names a group outside [0, %d)' % S)
-        if C == 0:                                   # an empty part of a sharded stage
-            widths = [sum(len(x) for x in self._seg_parts(models[s])[3:]) for s in prob_seg]
-            return self._joint_empty(P, 0, return_cand, want_lg, widths=widths)
-        if inject is not None and len(inject) != S:
-            raise ValueError('joint stage: inject must hold one entry per group')
-        segs = np.zeros(S, dtype=N.JOINT_MSEG_DTYPE)
-        pools = {4: [], 8: []}
-        fill = {4: 0, 8: 0}
-
-        def put(arr, dtype):
-            arr = np.ascontiguousarray(arr, dtype=dtype).reshape(-1)
-            size = arr.dtype.itemsize
-            pools[size].append(arr)
-            fill[size] += arr.size
-            return fill[size] - arr.size
-        dims = np.empty(S, dtype=np.int64)
-        n_table = 0
-        for s, m in enumerate(models):
-            below, above, low, high, cats, quants = self._seg_parts(m)
-            g = segs[s]
-            g['stream_word'] = int(stream_words[s])
-            g['lo'], g['hi'] = np.float32(-np.inf), np.float32(np.inf)
-            g['qlo'], g['qhi'] = np.float32(-np.inf), np.float32(np.inf)
-            if not cats and not quants:                  # a continuous group: run_joint_segments' rows
-                low, high = np.asarray(low, dtype=np.float64), np.asarray(high, dtype=np.float64)
-                Dc, Dk, Dq = len(low), 0, 0
-                if not 1 <= Dc <= N.JOINT_MAX_DIMS:
-                    raise ValueError('joint stage: %d dimensions, at most %d' % (Dc, N.JOINT_MAX_DIMS))
-                r = dict(low=low, high=high)
-                for name, side in (('below', below), ('above', above)):
-                    if side[1].shape != (len(side[0]), Dc) or side[2].shape != side[1].shape:
-                        raise ValueError('joint stage: mixture shapes do not match %d dimensions' % Dc)
-                    r[name + '_mu'], r[name + '_a'], r[name + '_c'], r[name + '_base'] = J.density_rows(
-                        side[0], side[1], side[2], low, high)
-                r['cum'], r['samp'] = J.sampler_rows(below[0], below[1], below[2], low, high)
-            else:
-                r = self._mseg_rows(below, above, low, high, cats, quants)
-                Dc, Dk, Dq = r['Dc'], r['Dk'], r['Dq']
-            D = dims[s] = Dc + Dk + Dq
-            g['n_dims'], g['n_cat'], g['n_quant'] = Dc, Dk, Dq
-            g['k_below'], g['k_above'] = len(r['below_c']), len(r['above_c'])
-            for name in ('below', 'above'):
-                for f in ('_mu', '_a', '_c'):
-                    g[name + f] = put(r[name + f], np.float32)
-                g[name + '_base'] = r[name + '_base']
-                if Dk:
-                    for f in ('_cat', '_miss', '_bonus'):
-                        g[name + f] = put(r[name + f], np.float32)
-                if Dq:
-                    g[name + '_qmu'], g[name + '_qsigma'] = put(r[name + '_qmu'], np.float64), put(r[name + '_qsigma'],
-                                                                                                   np.float64)
-            g['samp'], g['samp_cum'] = put(r['samp'], np.float32), put(r['cum'], np.float64)
-            g['lo'][:Dc], g['hi'][:Dc] = J.f32_bounds(r['low'], r['high'])
-            if Dk:
-                g['below_h'], g['cat_cum'] = put(r['below_h'], np.float64), put(r['cat_cum'], np.float64)
-                ups = [len(p) for p in r['ps']]
-                g['cat_upper'][:Dk], g['cat_off'][:Dk] = ups, np.cumsum([0] + ups[:-1])
-            if Dq:
-                vs = [len(e) - 1 for e in r['edges']]
-                g['quant_v'][:Dq], g['quant_edge_off'][:Dq] = vs, np.cumsum([0] + [v + 1 for v in vs[:-1]])
-                g['quant_edges'], g['n_edges'] = put(np.concatenate(r['edges']), np.float64), sum(vs) + Dq
-                g['quant_samp'] = put(r['quant_samp'], np.float32)
-                g['qlo'][:Dq], g['qhi'][:Dq] = r['qlo'], r['qhi']
-                g['table'] = n_table
-                n_table += (int(g['k_below']) + int(g['k_above'])) * sum(vs)
-            g['inject'] = -1
-            if inject is not None and inject[s] is not None:
-                inj = np.ascontiguousarray(inject[s], dtype=np.float32)
-                if inj.shape != (C, D):
-                    raise ValueError('joint stage: inject must be [n_cand, %d]' % D)
-                g['inject'] = put(inj, np.float32)
-        if inject is not None and any(inject[s] is None for s in np.unique(prob_seg)):
-            raise ValueError('joint stage: inject lacks the candidates of a group that has a problem')
-        pd = dims[prob_seg]
-        cand_off = np.concatenate([[0], np.cumsum(C * pd)]).astype(np.int64)
-        if P * C >= 2 ** 31 or cand_off[-1] >= 2 ** 31:
-            raise ValueError('joint stage: %d problems x %d candidates do not fit one run' % (P, C))
-
-        # one blob: 8-byte items first (descriptors, the f64 pool, ids, offsets), then the 4-byte ones
-        parts = [segs.view(np.uint8), np.concatenate(pools[8]).view(np.uint8), prob_id.view(np.uint8),
-                 cand_off[:P].view(np.uint8), np.concatenate(pools[4]).view(np.uint8), prob_seg.view(np.uint8)]
-        offs = np.concatenate([[0], np.cumsum([len(x) for x in parts])])
-        blob = np.concatenate(parts)
-        d_blob = self._buf('joint_seg_blob', len(blob), torch.uint8)
-        d_blob[:len(blob)].copy_(torch.from_numpy(blob))
-        base = d_blob.data_ptr()
-        a = N.JointMSegArgs()
-        a.n_segs, a.n_probs, a.n_cand, a.flags = S, P, C, N.JOINT_INJECT if inject is not None else 0
-        a.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        a.segs, a.host_segs = base + int(offs[0]), segs.ctypes.data
-        a.pool_f64, a.prob_id, a.cand_off = base + int(offs[1]), base + int(offs[2]), base + int(offs[3])
-        a.pool_f32, a.prob_seg, a.host_prob_seg = base + int(offs[4]), base + int(offs[5]), prob_seg.ctypes.data
-        a.pool_f32_len, a.pool_f64_len = fill[4], fill[8]
-        nb = ctypes.c_uint64(0)
-        N.check(self.lib.tpe_joint_mseg_table_bytes(segs.ctypes.data, S, ctypes.byref(nb)), self.lib,
-                'tpe_joint_mseg_table_bytes')
-        assert nb.value == 4 * n_table, (nb.value, n_table)
-        if n_table:
-            d_tab = self._buf('joint_mseg_table', n_table, torch.float32)
-            a.quant_table, a.quant_table_bytes = d_tab.data_ptr(), d_tab.numel() * 4
-        return self._joint_seg_call('tpe_joint_mseg', a, P, C, cand_off, pd, return_cand, want_lg, report_k, shard)
-
     def run_joint_mixed(self, below, above, low, high, cats, ids, n_cand, seed, inject=None, return_cand=False,
                         want_lg=False, report_k=0, stream_word=None, shard=None):
         """One joint stage over a mixed group (tpe_joint_mixed_run,
@@ -1580,73 +1350,8 @@ class Engine(object):
         ``inject`` [C, Dc + Dk], candidates f32 [n_ids, C, Dc + Dk].
         ``stream_word``: the Philox stream word (None: N.JOINT_STREAM; a branch
         group's joint.branch_stream_word, to compare with run_joint_segments)."""
-        from . import joint as J
-        low, high = np.asarray(low, dtype=np.float64).reshape(-1), np.asarray(high, dtype=np.float64).reshape(-1)
-        Dc, Dk = len(low), len(cats)
-        D = Dc + Dk
-        if Dk == 0:
-            raise ValueError('joint stage: no discrete dimension, use run_joint')
-        ids, n_ids, C = self._joint_sizes(D, ids, n_cand, shard=shard)
-        shard = self._joint_shard(shard, C, report_k, inject)
-        if C == 0:
-            return self._joint_empty(n_ids, D, return_cand, want_lg)
-        sides = []
-        for i, side in enumerate((below, above)):
-            w = np.asarray(side[0], dtype=np.float64)
-            mu = np.asarray(side[1], dtype=np.float64).reshape(len(w), -1)
-            sigma = np.asarray(side[2], dtype=np.float64).reshape(len(w), -1)
-            if mu.shape != (len(w), Dc) or sigma.shape != mu.shape:
-                raise ValueError('joint stage: mixture shapes do not match %d dimensions' % Dc)
-            cols = [np.asarray(c[i], dtype=np.int64).reshape(-1) for c in cats]
-            if any(len(col) != len(w) for col in cols):
-                raise ValueError('joint stage: one category per component and discrete dimension')
-            sides.append((w, mu, sigma, np.stack(cols, axis=1)))
-        ps = [np.asarray(c[2], dtype=np.float64).reshape(-1) for c in cats]
-        total = 0
-        for d, p in enumerate(ps):
-            U = len(p)
-            if not 2 <= U <= N.JOINT_MAX_CATS:
-                raise ValueError('joint stage: %d categories, outside [2, %d]' % (U, N.JOINT_MAX_CATS))
-            if not (p > 0).all():
-                raise ValueError('joint stage: a prior probability of 0')
-            for w, mu, sigma, xc in sides:
-                if xc[:, d].min() < -1 or xc[:, d].max() >= U:
-                    raise ValueError('joint stage: a component category outside [-1, %d)' % U)
-            total += U
-        if total > N.JOINT_MAX_CAT_TOTAL:
-            raise ValueError('joint stage: %d categories in the group, at most %d' % (total, N.JOINT_MAX_CAT_TOTAL))
-        s_side = [np.array([float(c[3 + i]) for c in cats]) for i in (0, 1)]
-        if not all((s > 0).all() and np.isfinite(s).all() for s in s_side):
-            raise ValueError('joint stage: the smoothing masses must be positive')
-        up = self._joint_up
-        a = N.JointMixedArgs()
-        a.n_dims, a.n_cat, a.n_cand, a.n_ids, a.flags = Dc, Dk, C, n_ids, 0
-        a.k_below, a.k_above = len(sides[0][0]), len(sides[1][0])
-        a.stream_word = N.JOINT_STREAM if stream_word is None else int(stream_word)
-        a.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        for i, name in enumerate(('below', 'above')):
-            w, mu, sigma, xc = sides[i]
-            mu32, aa, c, base, cat32, miss, bonus = J.mixed_density_rows(w, mu, sigma, low, high, xc, ps, s_side[i])
-            setattr(a, name + '_mu', up(name + '_mu', mu32, torch.float32))
-            setattr(a, name + '_a', up(name + '_a', aa, torch.float32))
-            setattr(a, name + '_c', up(name + '_c', c, torch.float32))
-            setattr(a, name + '_base', base)
-            setattr(a, name + '_cat', up(name + '_cat', cat32, torch.float32))
-            setattr(a, name + '_miss', up(name + '_miss', miss, torch.float32))
-            setattr(a, name + '_bonus', up(name + '_bonus', bonus, torch.float32))
-        cum, rows, h, cat_cum = J.mixed_sampler_rows(sides[0][0], sides[0][1], sides[0][2], low, high, ps, s_side[0])
-        a.samp_cum, a.samp = up('cum', cum, torch.float64), up('samp', rows, torch.float32)
-        a.below_h, a.cat_cum = up('cat_h', h, torch.float64), up('cat_cum', cat_cum, torch.float64)
-        a.ids = up('ids', ids, torch.int64)
-        self._joint_inject(a, inject, C, D)
-        off = 0
-        for d in range(Dc):
-            a.low[d], a.high[d] = low[d], high[d]
-        for d, p in enumerate(ps):
-            a.cat_upper[d], a.cat_off[d] = len(p), off
-            off += len(p)
-        return self._joint_call('tpe_joint_mixed_run', a, n_ids, C, D, return_cand, want_lg, report_k=report_k,
-                                shard=shard)
+        return self._joint_solo('mixed', below, above, low, high, cats, (), ids, n_cand, seed, inject, return_cand,
+                                want_lg, report_k, stream_word, shard)
 
     def run_joint_quant(self, below, above, low, high, cats, quants, ids, n_cand, seed, inject=None, return_cand=False,
                         want_lg=False, return_table=False, report_k=0, stream_word=None, shard=None):
@@ -1662,128 +1367,8 @@ class Engine(object):
         Dc + Dk + Dq].  ``return_table`` (debug): also the two sides' tables
         log2 P as the device built them, f32 [K, sum V] each.  ``stream_word``: as
         in ``run_joint_mixed``."""
-        from . import joint as J
-        low, high = np.asarray(low, dtype=np.float64).reshape(-1), np.asarray(high, dtype=np.float64).reshape(-1)
-        Dc, Dk, Dq = len(low), len(cats), len(quants)
-        D = Dc + Dk + Dq
-        if Dq == 0:
-            raise ValueError('joint stage: no quantised dimension, use run_joint_mixed / run_joint')
-        if Dq > N.JOINT_MAX_QUANT:
-            raise ValueError('joint stage: %d quantised dimensions, at most %d' % (Dq, N.JOINT_MAX_QUANT))
-        if Dc > N.JOINT_QUANT_MAX_CONT or Dk > N.JOINT_QUANT_MAX_DISC:
-            raise ValueError('joint stage: beside a quantised dimension at most %d continuous and %d discrete ones, '
-                             'not %d and %d' % (N.JOINT_QUANT_MAX_CONT, N.JOINT_QUANT_MAX_DISC, Dc, Dk))
-        ids, n_ids, C = self._joint_sizes(D, ids, n_cand, shard=shard)
-        shard = self._joint_shard(shard, C, report_k, inject)
-        if C == 0:
-            if return_table:
-                raise ValueError('joint stage: return_table needs at least one candidate')
-            return self._joint_empty(n_ids, D, return_cand, want_lg)
-        edges = [np.ascontiguousarray(q[4], dtype=np.float64).reshape(-1) for q in quants]
-        total = 0
-        for e in edges:
-            V = len(e) - 1
-            if not 2 <= V <= N.JOINT_MAX_LATTICE:
-                raise ValueError('joint stage: %d lattice values, outside [2, %d]' % (V, N.JOINT_MAX_LATTICE))
-            if not (np.isfinite(e).all() and (np.diff(e) > 0).all()):
-                raise ValueError('joint stage: the lattice edges must be finite and strictly increasing')
-            total += V
-        if total > N.JOINT_MAX_LATTICE_TOTAL:
-            raise ValueError('joint stage: %d lattice values in the group, at most %d'
-                             % (total, N.JOINT_MAX_LATTICE_TOTAL))
-        sides = []
-        for i, side in enumerate((below, above)):
-            w = np.asarray(side[0], dtype=np.float64)
-            mu = np.asarray(side[1], dtype=np.float64).reshape(len(w), -1)
-            sigma = np.asarray(side[2], dtype=np.float64).reshape(len(w), -1)
-            if mu.shape != (len(w), Dc) or sigma.shape != mu.shape:
-                raise ValueError('joint stage: mixture shapes do not match %d dimensions' % Dc)
-            cols = [np.asarray(c[i], dtype=np.int64).reshape(-1) for c in cats]
-            qmu = [np.asarray(q[2 * i], dtype=np.float64).reshape(-1) for q in quants]
-            qsig = [np.asarray(q[2 * i + 1], dtype=np.float64).reshape(-1) for q in quants]
-            if any(len(col) != len(w) for col in cols + qmu + qsig):
-                raise ValueError('joint stage: one category / (mu, sigma) per component and dimension')
-            qsig = np.stack(qsig, axis=1)
-            if not ((qsig > 0).all() and np.isfinite(qsig).all()):
-                raise ValueError('joint stage: the quantised bandwidths must be positive')
-            xc = np.stack(cols, axis=1) if cols else np.zeros((len(w), 0), dtype=np.int64)
-            sides.append((w, mu, sigma, xc, np.stack(qmu, axis=1), qsig))
-        ps = [np.asarray(c[2], dtype=np.float64).reshape(-1) for c in cats]
-        cat_total = 0
-        for d, p in enumerate(ps):
-            U = len(p)
-            if not 2 <= U <= N.JOINT_MAX_CATS:
-                raise ValueError('joint stage: %d categories, outside [2, %d]' % (U, N.JOINT_MAX_CATS))
-            if not (p > 0).all():
-                raise ValueError('joint stage: a prior probability of 0')
-            for side in sides:
-                if side[3][:, d].min() < -1 or side[3][:, d].max() >= U:
-                    raise ValueError('joint stage: a component category outside [-1, %d)' % U)
-            cat_total += U
-        s_side = [np.array([float(c[3 + i]) for c in cats]) for i in (0, 1)]
-        if not all((s > 0).all() and np.isfinite(s).all() for s in s_side):
-            raise ValueError('joint stage: the smoothing masses must be positive')
-        up = self._joint_up
-        a = N.JointQuantArgs()
-        a.n_dims, a.n_cat, a.n_quant, a.n_cand, a.n_ids, a.flags = Dc, Dk, Dq, C, n_ids, 0
-        a.k_below, a.k_above = len(sides[0][0]), len(sides[1][0])
-        a.stream_word = N.JOINT_STREAM if stream_word is None else int(stream_word)
-        a.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        for i, name in enumerate(('below', 'above')):
-            w, mu, sigma, xc, qmu, qsig = sides[i]
-            if Dk:
-                mu32, aa, c, base, cat32, miss, bonus = J.mixed_density_rows(w, mu, sigma, low, high, xc, ps, s_side[i])
-                setattr(a, name + '_cat', up(name + '_cat', cat32, torch.float32))
-                setattr(a, name + '_miss', up(name + '_miss', miss, torch.float32))
-                setattr(a, name + '_bonus', up(name + '_bonus', bonus, torch.float32))
-            else:
-                mu32, aa, c, base = J.density_rows(w, mu, sigma, low, high)
-            if Dc:
-                setattr(a, name + '_mu', up(name + '_mu', mu32, torch.float32))
-                setattr(a, name + '_a', up(name + '_a', aa, torch.float32))
-            setattr(a, name + '_c', up(name + '_c', c, torch.float32))
-            setattr(a, name + '_base', base)
-            setattr(a, name + '_qmu', up(name + '_qmu', qmu, torch.float64))
-            setattr(a, name + '_qsigma', up(name + '_qsigma', qsig, torch.float64))
-        w, mu, sigma, xc, qmu, qsig = sides[0]
-        if Dk:
-            cum, rows, h, cat_cum = J.mixed_sampler_rows(w, mu, sigma, low, high, ps, s_side[0])
-            a.below_h, a.cat_cum = up('cat_h', h, torch.float64), up('cat_cum', cat_cum, torch.float64)
-        else:
-            cum, rows = J.sampler_rows(w, mu, sigma, low, high)
-        a.samp_cum = up('cum', cum, torch.float64)
-        if Dc:
-            a.samp = up('samp', rows, torch.float32)
-        qlow, qhigh = np.array([e[0] for e in edges]), np.array([e[-1] for e in edges])
-        a.quant_samp = up('qsamp', J.sampler_rows(w, qmu, qsig, qlow, qhigh)[1], torch.float32)
-        all_edges = np.concatenate(edges)
-        a.quant_edges, a.n_edges = up('qedges', all_edges, torch.float64), len(all_edges)
-        a.ids = up('ids', ids, torch.int64)
-        self._joint_inject(a, inject, C, D)
-        off = 0
-        for d in range(Dc):
-            a.low[d], a.high[d] = low[d], high[d]
-        for d, p in enumerate(ps):
-            a.cat_upper[d], a.cat_off[d] = len(p), off
-            off += len(p)
-        off = 0
-        for d, e in enumerate(edges):
-            a.low[Dc + d], a.high[Dc + d] = e[0], e[-1]
-            a.quant_v[d], a.quant_edge_off[d] = len(e) - 1, off
-            off += len(e)
-        nb = ctypes.c_uint64(0)
-        N.check(self.lib.tpe_joint_quant_table_bytes(a.k_below, a.k_above, total, ctypes.byref(nb)), self.lib,
-                'tpe_joint_quant_table_bytes')
-        d_tab = self._buf('joint_qtable', (nb.value + 3) // 4, torch.float32)
-        a.quant_table, a.quant_table_bytes = d_tab.data_ptr(), d_tab.numel() * 4
-        out = self._joint_call('tpe_joint_quant_run', a, n_ids, C, D, return_cand, want_lg, report_k=report_k,
-                               shard=shard)
-        if not return_table:
-            return out
-        tab = d_tab[:(a.k_below + a.k_above) * total].cpu().numpy()
-        tb = tab[:total * a.k_below].reshape(total, a.k_below).T.copy()
-        ta = tab[total * a.k_below:].reshape(total, a.k_above).T.copy()
-        return (out if isinstance(out, tuple) else (out,)) + (tb, ta)
+        return self._joint_solo('quant', below, above, low, high, cats, quants, ids, n_cand, seed, inject, return_cand,
+                                want_lg, report_k, stream_word, shard, return_table)
 
     def device_tables(self):
         """(problems, comp32) of the last ``run`` as the device holds them after

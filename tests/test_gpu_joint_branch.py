@@ -45,8 +45,7 @@ PROBLEMS = [(9, 2), (5, 0), (40, 3), (9, 1), (12, 2), (1000003, 0), (7, 3)]
 def _single(engine, model, word, new_id, inject=None):
     """tpe_joint_run over one segment alone with its stream word."""
     below, above, low, high = model
-    return engine._joint_continuous(False, below, above, low, high, [new_id], C, SEED, inject, True, True,
-                                    stream_word=word)
+    return engine.run_joint(below, above, low, high, [new_id], C, SEED, inject, True, True, stream_word=word)
 
 
 @pytest.fixture(scope='module')
@@ -285,8 +284,8 @@ def _check_batch(domain, trials, ids, Cn, seed):
             assert root[j][k] == plain[j][k], (j, k)
         # the joined pair: the winner of run_joint over the branch's observers with the group's stream word
         below, above, low, high = models[c]
-        rec = get_engine()._joint_continuous(False, below, above, low, high, [new_id], Cn, seed, None, False, False,
-                                             stream_word=words[c])
+        rec = get_engine().run_joint(below, above, low, high, [new_id], Cn, seed, None, False, False,
+                                     stream_word=words[c])
         z = rec['z'][0, :2]
         want = np.exp(z) if c == 0 else z
         for d, k in enumerate(branch[c]):

@@ -55,8 +55,8 @@ class Seg(object):
             return engine.run_joint_quant(*self.model, [new_id], C, SEED, inject=inject, stream_word=word, **kw)
         if self.kind == 'mixed':
             return engine.run_joint_mixed(*self.model, [new_id], C, SEED, inject=inject, stream_word=word, **kw)
-        return engine._joint_continuous(False, *self.model, [new_id], C, SEED, inject, kw['return_cand'],
-                                        kw['want_lg'], stream_word=word)
+        return engine.run_joint(*self.model, [new_id], C, SEED, inject, kw['return_cand'], kw['want_lg'],
+                                stream_word=word)
 
     def ref(self, cand):
         """float64 (l, g) of kernel rows ``cand`` [C, D]."""
@@ -148,14 +148,23 @@ def test_twice_the_same_bytes_any_order_and_records_alone(engine, seg_run):
 
 
 def test_all_continuous_list_is_the_segmented_stage_of_today(engine, monkeypatch):
-    """Continuous models only: tpe_joint_seg_run, never the new entry."""
+    """Continuous models only: the native function reached is
+    tpe_joint_seg_run, never tpe_joint_mseg_run or its table size query."""
     cases = [R.seeded_case(2, 40, 202)[:4], R.seeded_case(5, 300, 205)[:4]]
     words = [0xFFFFFFFE - 1, 0xFFFFFFFE - 4]
     probs, ids = [1, 0, 1], [9, 9, 12]
-    want = [engine._joint_continuous(False, *cases[s], [i], C, SEED, None, True, True, stream_word=words[s])
+    want = [engine.run_joint(*cases[s], [i], C, SEED, None, True, True, stream_word=words[s])
             for s, i in zip(probs, ids)]
-    monkeypatch.setattr(engine, '_run_joint_msegments', lambda *a, **k: pytest.fail('the mixed entry was taken'))
+    reached, native, lib = [], engine._joint_native, engine.lib
+    monkeypatch.setattr(engine, '_joint_native', lambda fn, *a: (reached.append(fn), native(fn, *a))[1])
+
+    class Lib(object):                                # the library, its mixed segmented entry points barred
+        def __getattr__(self, name):
+            assert not name.startswith('tpe_joint_mseg'), name
+            return getattr(lib, name)
+    monkeypatch.setattr(engine, 'lib', Lib())
     rec, cand, l, g = engine.run_joint_segments(cases, words, probs, ids, C, SEED, return_cand=True, want_lg=True)
+    assert reached == ['tpe_joint_seg_run']
     for p, w in enumerate(want):
         assert rec[p:p + 1].tobytes() == w[0].tobytes() and cand[p].tobytes() == w[1][0].tobytes()
         assert l[p].tobytes() == w[2][0].tobytes() and g[p].tobytes() == w[3][0].tobytes()

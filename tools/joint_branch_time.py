@@ -75,8 +75,7 @@ def measure(name, eng, models, words, prob_seg, prob_id, C, args):
         for s, ids in groups:
             b, a, lo, hi = models[s]
             if word:
-                out.append(eng._joint_continuous(False, b, a, lo, hi, ids, C, SEED, None, False, False,
-                                                 stream_word=words[s]))
+                out.append(eng.run_joint(b, a, lo, hi, ids, C, SEED, None, False, False, stream_word=words[s]))
             else:
                 out.append(eng.run_joint(b, a, lo, hi, ids, C, SEED))
         return out

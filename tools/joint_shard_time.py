@@ -119,7 +119,7 @@ def main():
         return main_exchange(args)
 
     import torch
-    from hyperopt_amd import _native as N, dist as D, history as H, joint as J
+    from hyperopt_amd import _native as N, dist as D, history as H, joint as J, joint_pack as JP
     from hyperopt_amd.engine import get_engine
 
     domain, hist = make_history(args.history)
@@ -141,12 +141,9 @@ def main():
         t, model = wall(lambda: J.fit_model(rows, hist, H.split_below(hist, 0.25), 1.0))
         fit_ms.append(t)
 
-        def pack():
-            out = []
-            for side in (model.below, model.above):
-                out.extend(J.density_rows(side[0], side[1], side[2], model.low, model.high)[:3])
-            out.extend(J.sampler_rows(model.below[0], model.below[1], model.below[2], model.low, model.high))
-            return out
+        def pack():                                  # what run_joint does before its uploads
+            r = JP.group_rows(model.below, model.above, model.low, model.high, entry='run')
+            return [r[row[0]] for row in JP.group_rows_present(r)]
         t, packed = wall(pack)
         pack_ms.append(t)
         t, _ = wall(lambda: [eng._joint_up('time_%d' % i, a, torch.float64 if a.dtype == np.float64 else torch.float32)
