@@ -47,7 +47,10 @@
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <string.h>
+
+#include <type_traits>
 
 #include "../../include/tpe_hip.h"
 #include "tpe_device_rng.h"
@@ -769,63 +772,6 @@ void k_joint_mseg_mixed_chunk(const MSegK p) {
   mixed_chunk_body<CP, KP>(io, chunk * TPE_JOINT_CHUNK, rows, cl, slot);
 }
 
-int64_t n_chunks_of(int32_t n_cand) { return ((int64_t)n_cand + TPE_JOINT_CHUNK - 1) / TPE_JOINT_CHUNK; }
-
-// tpe_joint_profile: start / stop events of the two launches (profiling only)
-struct {
-  int on, valid;
-  hipEvent_t ev[4];
-} g_prof = {0, 0, {nullptr, nullptr, nullptr, nullptr}};
-
-// tpe_joint_seg_run's / tpe_joint_mseg_run's launches before the merge: the order
-// kernel, the table kernel and one chunk launch per kernel class present
-// (g_prof.valid == 2: sum these for last_ms[0])
-uint64_t seg_order_bytes(int32_t n_probs) { return ((uint64_t)n_probs * sizeof(int32_t) + 7) & ~(uint64_t)7; }
-constexpr int kSegLaunches = 2 + kMClasses;
-struct {
-  int n;
-  hipEvent_t ev[2 * kSegLaunches];
-} g_sprof = {0, {}};
-
-template <int DP, bool MIXED = false>
-void launch_seg(const SegK& k, unsigned blocks, hipStream_t stream, hipEvent_t* ev) {
-  if (ev)
-    hipExtLaunchKernelGGL((k_joint_seg_chunk<DP, MIXED>), dim3(blocks), dim3(kThreads), 0u, stream, ev[0], ev[1], 0u,
-                          k);
-  else
-    hipLaunchKernelGGL((k_joint_seg_chunk<DP, MIXED>), dim3(blocks), dim3(kThreads), 0, stream, k);
-}
-
-template <int DP>
-void launch_chunk(const JointK& k, unsigned blocks, hipStream_t stream, bool timed) {
-  if (timed)
-    hipExtLaunchKernelGGL(k_joint_chunk<DP>, dim3(blocks), dim3(kThreads), 0u, stream, g_prof.ev[0], g_prof.ev[1], 0u,
-                          k);
-  else
-    hipLaunchKernelGGL(k_joint_chunk<DP>, dim3(blocks), dim3(kThreads), 0, stream, k);
-}
-
-template <int CP, int KP>
-void launch_mixed(const MixedK& k, unsigned blocks, hipStream_t stream, bool timed) {
-  if (timed)
-    hipExtLaunchKernelGGL((k_joint_mixed_chunk<CP, KP>), dim3(blocks), dim3(kThreads), 0u, stream, g_prof.ev[0],
-                          g_prof.ev[1], 0u, k);
-  else
-    hipLaunchKernelGGL((k_joint_mixed_chunk<CP, KP>), dim3(blocks), dim3(kThreads), 0, stream, k);
-}
-
-// padded counts: CP in {0, 2, 4, 8, 16}, KP in {1, 2, 4, 8, 16}; 16 continuous
-// slots mean at least 9 continuous labels, so at most 7 discrete ones: 24
-// instantiations in all
-template <int CP>
-void launch_mixed_k(const MixedK& k, unsigned blocks, hipStream_t stream, bool timed) {
-  const int Dk = k.Dk;
-  if (Dk == 1) launch_mixed<CP, 1>(k, blocks, stream, timed);
-  else if (Dk == 2) launch_mixed<CP, 2>(k, blocks, stream, timed);
-  else if (Dk <= 4) launch_mixed<CP, 4>(k, blocks, stream, timed);
-  else if (Dk <= 8) launch_mixed<CP, 8>(k, blocks, stream, timed);
-  else if constexpr (CP < 16) launch_mixed<CP, 16>(k, blocks, stream, timed);
-}
 
 // -------------------------------------------------------- quantised groups
 // Dc continuous and Dk discrete coordinates (as above) followed by Dq
@@ -1302,101 +1248,6 @@ void k_joint_mseg_quant_chunk(const MSegK p) {
   quant_chunk_body<CP, KP, QP>(io, chunk * TPE_JOINT_CHUNK, rows, cl, qt, slot);
 }
 
-// start / stop events around the two table launches (profiling only)
-struct {
-  int valid;
-  hipEvent_t ev[2];
-} g_qprof = {0, {nullptr, nullptr}};
-
-template <int CP, int KP, int QP>
-void launch_quant(const QuantK& k, unsigned blocks, unsigned lds, hipStream_t stream, bool timed) {
-  if (timed)
-    hipExtLaunchKernelGGL((k_joint_quant_chunk<CP, KP, QP>), dim3(blocks), dim3(kThreads), lds, stream, g_prof.ev[0],
-                          g_prof.ev[1], 0u, k);
-  else
-    hipLaunchKernelGGL((k_joint_quant_chunk<CP, KP, QP>), dim3(blocks), dim3(kThreads), lds, stream, k);
-}
-
-// padded counts: CP in {0, 2, 4, 8}, KP in {0, 1, 2, 4}, QP in {1, 2, 4}: 48 instantiations
-template <int CP, int KP>
-void launch_quant_q(const QuantK& k, unsigned blocks, unsigned lds, hipStream_t stream, bool timed) {
-  if (k.Dq == 1) launch_quant<CP, KP, 1>(k, blocks, lds, stream, timed);
-  else if (k.Dq == 2) launch_quant<CP, KP, 2>(k, blocks, lds, stream, timed);
-  else launch_quant<CP, KP, 4>(k, blocks, lds, stream, timed);
-}
-template <int CP>
-void launch_quant_k(const QuantK& k, unsigned blocks, unsigned lds, hipStream_t stream, bool timed) {
-  const int Dk = k.m.Dk;
-  if (Dk == 0) launch_quant_q<CP, 0>(k, blocks, lds, stream, timed);
-  else if (Dk == 1) launch_quant_q<CP, 1>(k, blocks, lds, stream, timed);
-  else if (Dk == 2) launch_quant_q<CP, 2>(k, blocks, lds, stream, timed);
-  else launch_quant_q<CP, 4>(k, blocks, lds, stream, timed);
-}
-
-// the segmented launches of the mixed and the quantised kernels, by class index
-template <int CP, int KP>
-void launch_mseg_mixed(const MSegK& k, unsigned blocks, hipStream_t stream, hipEvent_t* ev) {
-  if (ev)
-    hipExtLaunchKernelGGL((k_joint_mseg_mixed_chunk<CP, KP>), dim3(blocks), dim3(kThreads), 0u, stream, ev[0], ev[1],
-                          0u, k);
-  else
-    hipLaunchKernelGGL((k_joint_mseg_mixed_chunk<CP, KP>), dim3(blocks), dim3(kThreads), 0, stream, k);
-}
-template <int CP>
-void launch_mseg_mixed_k(int kp, const MSegK& k, unsigned blocks, hipStream_t stream, hipEvent_t* ev) {
-  if (kp == 0) launch_mseg_mixed<CP, 1>(k, blocks, stream, ev);
-  else if (kp == 1) launch_mseg_mixed<CP, 2>(k, blocks, stream, ev);
-  else launch_mseg_mixed<CP, 4>(k, blocks, stream, ev);
-}
-template <int CP, int KP, int QP>
-void launch_mseg_quant(const MSegK& k, unsigned blocks, unsigned lds, hipStream_t stream, hipEvent_t* ev) {
-  if (ev)
-    hipExtLaunchKernelGGL((k_joint_mseg_quant_chunk<CP, KP, QP>), dim3(blocks), dim3(kThreads), lds, stream, ev[0],
-                          ev[1], 0u, k);
-  else
-    hipLaunchKernelGGL((k_joint_mseg_quant_chunk<CP, KP, QP>), dim3(blocks), dim3(kThreads), lds, stream, k);
-}
-template <int CP, int KP>
-void launch_mseg_quant_q(int qp, const MSegK& k, unsigned blocks, unsigned lds, hipStream_t stream, hipEvent_t* ev) {
-  if (qp == 0) launch_mseg_quant<CP, KP, 1>(k, blocks, lds, stream, ev);
-  else if (qp == 1) launch_mseg_quant<CP, KP, 2>(k, blocks, lds, stream, ev);
-  else launch_mseg_quant<CP, KP, 4>(k, blocks, lds, stream, ev);
-}
-template <int CP>
-void launch_mseg_quant_k(int kp, int qp, const MSegK& k, unsigned blocks, unsigned lds, hipStream_t stream,
-                         hipEvent_t* ev) {
-  if (kp == 0) launch_mseg_quant_q<CP, 0>(qp, k, blocks, lds, stream, ev);
-  else if (kp == 1) launch_mseg_quant_q<CP, 1>(qp, k, blocks, lds, stream, ev);
-  else if (kp == 2) launch_mseg_quant_q<CP, 2>(qp, k, blocks, lds, stream, ev);
-  else launch_mseg_quant_q<CP, 4>(qp, k, blocks, lds, stream, ev);
-}
-// one chunk launch of kernel class c (mseg_class) over `blocks` workgroups
-void launch_mseg_class(int c, const MSegK& k, unsigned blocks, unsigned lds, hipStream_t s, hipEvent_t* ev) {
-  if (c < 8) {
-    switch (c) {
-      case 0: launch_seg<1, true>(k.s, blocks, s, ev); break;
-      case 1: launch_seg<2, true>(k.s, blocks, s, ev); break;
-      case 2: launch_seg<3, true>(k.s, blocks, s, ev); break;
-      case 3: launch_seg<4, true>(k.s, blocks, s, ev); break;
-      case 4: launch_seg<6, true>(k.s, blocks, s, ev); break;
-      case 5: launch_seg<8, true>(k.s, blocks, s, ev); break;
-      case 6: launch_seg<12, true>(k.s, blocks, s, ev); break;
-      default: launch_seg<16, true>(k.s, blocks, s, ev); break;
-    }
-  } else if (c < 20) {
-    const int cp = (c - 8) / 3, kp = (c - 8) % 3;
-    if (cp == 0) launch_mseg_mixed_k<0>(kp, k, blocks, s, ev);
-    else if (cp == 1) launch_mseg_mixed_k<2>(kp, k, blocks, s, ev);
-    else if (cp == 2) launch_mseg_mixed_k<4>(kp, k, blocks, s, ev);
-    else launch_mseg_mixed_k<8>(kp, k, blocks, s, ev);
-  } else {
-    const int cp = (c - 20) / 12, kp = (c - 20) / 3 % 4, qp = (c - 20) % 3;
-    if (cp == 0) launch_mseg_quant_k<0>(kp, qp, k, blocks, lds, s, ev);
-    else if (cp == 1) launch_mseg_quant_k<2>(kp, qp, k, blocks, lds, s, ev);
-    else if (cp == 2) launch_mseg_quant_k<4>(kp, qp, k, blocks, lds, s, ev);
-    else launch_mseg_quant_k<8>(kp, qp, k, blocks, lds, s, ev);
-  }
-}
 
 // -------------------------------------------------------------- wide groups
 // 17 to TPE_JOINT_WIDE_MAX_DIMS continuous coordinates (include/tpe_hip.h "Wide
@@ -1633,23 +1484,176 @@ __global__ __launch_bounds__(64) void k_joint_wide_merge(const tpe_joint_wide_re
   }
 }
 
-// start / stop events of the sampling kernel (profiling only)
+// ------------------------------------------------------------- host driver
+// Everything from here on runs on the host: the six stages' argument checks,
+// the kernel-argument fills and the launches.  What the stages share exists
+// once (the launch and its profiling events, the padded-width dispatchers, the
+// solo stages' head checks and JointK fill, the category and lattice checks,
+// the segmented stages' skeleton, every scratch size); a joint_*_run_at below
+// checks what is particular to its stage, fills what is particular and picks
+// the kernel.
+
+// "<entry>: <pre><what><post>" as the call's error; pre / post carry the
+// segmented stages' "a segment's " / " in a segment"
+constexpr const char* kSegs = "a segment's ";
+constexpr const char* kInSeg = " in a segment";
+int fail(const char* entry, const char* what, const char* pre = "", const char* post = "") {
+  char msg[256];
+  snprintf(msg, sizeof msg, "%s: %s%s%s", entry, pre, what, post);
+  return tpe_internal_fail(TPE_E_ARG, msg);
+}
+int hip_fail(hipError_t e) { return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e)); }
+
+// ---- profiling (tpe_joint_profile and its companions; off: no events at all)
+struct Ev {
+  hipEvent_t start = nullptr, stop = nullptr;
+};
+// tpe_joint_profile: start / stop events of the chunk launch and the merge
+struct {
+  int on, valid;
+  hipEvent_t ev[4];
+} g_prof = {0, 0, {}};
+// tpe_joint_seg_run's / tpe_joint_mseg_run's launches before the merge: the order
+// kernel, the table kernel and one chunk launch per kernel class present
+// (g_prof.valid == 2: sum these for last_ms[0])
+constexpr int kSegLaunches = 2 + kMClasses;
+struct {
+  int n;
+  hipEvent_t ev[2 * kSegLaunches];
+} g_sprof = {0, {}};
+// start / stop events around the two table launches of tpe_joint_quant_run
 struct {
   int valid;
   hipEvent_t ev[2];
-} g_wprof = {0, {nullptr, nullptr}};
+} g_qprof = {0, {}};
+// start / stop events of the wide stage's sampling kernel
+struct {
+  int valid;
+  hipEvent_t ev[2];
+} g_wprof = {0, {}};
 
-template <int DP>
-void launch_wide(const WideK& k, unsigned blocks, hipStream_t stream, bool timed) {
-  if (timed)
-    hipExtLaunchKernelGGL((k_joint_wide_chunk<DP, wide_r(DP)>), dim3(blocks), dim3(kThreads), 0u, stream, g_prof.ev[0],
-                          g_prof.ev[1], 0u, k);
-  else
-    hipLaunchKernelGGL((k_joint_wide_chunk<DP, wide_r(DP)>), dim3(blocks), dim3(kThreads), 0, stream, k);
+// the events of ev[0 .. n) that do not exist yet
+int ensure_events(hipEvent_t* ev, int n) {
+  for (int i = 0; i < n; ++i) {
+    if (ev[i]) continue;
+    const hipError_t e = hipEventCreate(&ev[i]);
+    if (e != hipSuccess) return hip_fail(e);
+  }
+  return TPE_OK;
 }
 
+// the device time between two recorded events (it WAITS for the second)
+int elapsed_ms(hipEvent_t start, hipEvent_t stop, double* out) {
+  float ms = 0.f;
+  hipError_t e = hipEventSynchronize(stop);
+  if (e == hipSuccess) e = hipEventElapsedTime(&ms, start, stop);
+  if (e != hipSuccess) return hip_fail(e);
+  *out = (double)ms;
+  return TPE_OK;
+}
+
+// One launch of 256-thread (merge: 64-thread) workgroups: the event launch when a
+// start or a stop event is given (profiling), else the plain one.
+template <typename K, typename... Args>
+void launch(K kernel, dim3 grid, unsigned block, unsigned lds, hipStream_t s, hipEvent_t start, hipEvent_t stop,
+            const Args&... args) {
+  if (start || stop) hipExtLaunchKernelGGL(kernel, grid, dim3(block), lds, s, start, stop, 0u, args...);
+  else hipLaunchKernelGGL(kernel, grid, dim3(block), lds, s, args...);
+}
+
+// a solo stage's chunk launch under profiling
+Ev chunk_marks(bool timed) { return timed ? Ev{g_prof.ev[0], g_prof.ev[1]} : Ev{}; }
+// the next launch of a segmented stage under profiling: n counts them
+Ev seg_marks(bool timed, int& n) {
+  if (!timed) return Ev{};
+  const Ev e{g_sprof.ev[2 * n], g_sprof.ev[2 * n + 1]};
+  ++n;
+  return e;
+}
+
+// What every run ends with: the merge over n_probs problems (k_joint_merge, or
+// k_joint_wide_merge on the wide record), under profiling what
+// tpe_joint_profile reads (valid: 1 a solo stage, 2 a segmented one with
+// n_timed launches before the merge), and the launches' error.
+template <typename Rec>
+int finish(void (*merge)(const Rec*, int, Rec*), const Rec* chunk_rec, int n_chunks, Rec* records, int n_probs,
+           hipStream_t s, bool timed, int valid, int n_timed = 0) {
+  launch(merge, dim3((unsigned)n_probs), 64u, 0u, s, timed ? g_prof.ev[2] : nullptr, timed ? g_prof.ev[3] : nullptr,
+         chunk_rec, n_chunks, records);
+  if (timed) {
+    g_sprof.n = n_timed;
+    g_prof.valid = valid;
+  }
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? hip_fail(e) : TPE_OK;
+}
+
+// ---- the padded widths: one dispatcher per axis, f(std::integral_constant<int, P>)
+template <int N>
+using Int = std::integral_constant<int, N>;
+// the first P of the list that n fits (the last one if none does)
+template <int P, int... Rest, typename F>
+void pad_to(int n, F&& f) {
+  if constexpr (sizeof...(Rest) == 0) f(Int<P>());
+  else if (n <= P) f(Int<P>());
+  else pad_to<Rest...>(n, f);
+}
+// the continuous width of class c (dp_class, which the order kernel sorts by)
+template <typename F>
+void for_dp(int c, F&& f) {
+  switch (c) {
+    case 0: f(Int<1>()); break;
+    case 1: f(Int<2>()); break;
+    case 2: f(Int<3>()); break;
+    case 3: f(Int<4>()); break;
+    case 4: f(Int<6>()); break;
+    case 5: f(Int<8>()); break;
+    case 6: f(Int<12>()); break;
+    default: f(Int<16>()); break;
+  }
+}
+// padded counts of a group with discrete labels: CP in {0, 2, 4, 8, 16}, KP in
+// {1, 2, 4, 8, 16}; 16 continuous slots mean at least 9 continuous labels, so at
+// most 7 discrete ones: 24 instantiations in all.  Beside a quantised label and
+// in a segment (TOP 8 / 4): CP in {0, 2, 4, 8}, KP in {0, 1, 2, 4} (without a
+// quantised label from 1), QP in {1, 2, 4}: 48 instantiations
+template <int TOP, typename F>
+void for_cp(int Dc, F&& f) {
+  if constexpr (TOP == 16) pad_to<0, 2, 4, 8, 16>(Dc, f);
+  else pad_to<0, 2, 4, 8>(Dc, f);
+}
+template <int LOW, int TOP, typename F>
+void for_kp(int Dk, F&& f) {
+  if constexpr (LOW == 0) pad_to<0, 1, 2, 4>(Dk, f);
+  else if constexpr (TOP == 4) pad_to<1, 2, 4>(Dk, f);
+  else if constexpr (TOP == 8) pad_to<1, 2, 4, 8>(Dk, f);
+  else pad_to<1, 2, 4, 8, 16>(Dk, f);
+}
+template <typename F>
+void for_qp(int Dq, F&& f) { pad_to<1, 2, 4>(Dq, f); }
+// the counts that cp_index and mseg_class's discrete and quantised indices stand for
+constexpr int kCpOf[4] = {0, 2, 4, 8}, kKpOf[4] = {0, 1, 2, 4}, kQpOf[3] = {1, 2, 4};
+
+// ---- sizes: each once, for the *_bytes exports and the runs' checks
+int64_t n_chunks_of(int32_t n_cand) { return ((int64_t)n_cand + TPE_JOINT_CHUNK - 1) / TPE_JOINT_CHUNK; }
+uint64_t joint_scratch_need(int32_t n_ids, int32_t n_cand) {
+  return (uint64_t)n_ids * (uint64_t)n_chunks_of(n_cand) * sizeof(tpe_joint_record);
+}
+uint64_t seg_order_bytes(int32_t n_probs) { return ((uint64_t)n_probs * sizeof(int32_t) + 7) & ~(uint64_t)7; }
+uint64_t seg_scratch_need(int32_t n_probs, int32_t n_cand) {
+  return seg_order_bytes(n_probs) + joint_scratch_need(n_probs, n_cand);
+}
+uint64_t quant_table_floats(int64_t k_below, int64_t k_above, int64_t total) {
+  return ((uint64_t)k_below + (uint64_t)k_above) * (uint64_t)total;
+}
 // padded width of a wide group: DP in {20, 24, 32, 48, 64}
-int wide_dp(int D) { return D <= 20 ? 20 : D <= 24 ? 24 : D <= 32 ? 32 : D <= 48 ? 48 : 64; }
+template <typename F>
+void for_wide_dp(int D, F&& f) { pad_to<20, 24, 32, 48, 64>(D, f); }
+int wide_dp(int D) {
+  int dp = 0;
+  for_wide_dp(D, [&](auto p) { dp = decltype(p)::value; });
+  return dp;
+}
 int64_t wide_blocks_of(int32_t n_cand) { return ((int64_t)n_cand + kThreads - 1) / kThreads; }
 int64_t wide_chunks_of(int32_t n_cand, int D) {
   const int64_t per = (int64_t)kThreads * wide_r(wide_dp(D));
@@ -1658,74 +1662,68 @@ int64_t wide_chunks_of(int32_t n_cand, int D) {
 uint64_t wide_record_bytes(int32_t n_ids, int32_t n_cand, int D) {
   return (uint64_t)n_ids * (uint64_t)wide_chunks_of(n_cand, D) * sizeof(tpe_joint_wide_record);
 }
-uint64_t wide_zbuf_bytes(int32_t n_ids, int32_t n_cand, int D) {
-  return (uint64_t)n_ids * (uint64_t)wide_blocks_of(n_cand) * kThreads * (uint64_t)D * sizeof(float);
+uint64_t wide_scratch_need(int32_t n_ids, int32_t n_cand, int D) {
+  return wide_record_bytes(n_ids, n_cand, D) +
+         (uint64_t)n_ids * (uint64_t)wide_blocks_of(n_cand) * kThreads * (uint64_t)D * sizeof(float);
 }
-
-}  // namespace
-
-extern "C" {
-
-int tpe_joint_profile(int32_t enable, double* last_ms) {
-  if (last_ms) {
-    if (!g_prof.valid) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_profile: no profiled tpe_joint_run to read");
-    for (int i = g_prof.valid == 2 ? 1 : 0; i < 2; ++i) {
-      float ms = 0.f;
-      hipError_t e = hipEventSynchronize(g_prof.ev[2 * i + 1]);
-      if (e == hipSuccess) e = hipEventElapsedTime(&ms, g_prof.ev[2 * i], g_prof.ev[2 * i + 1]);
-      if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
-      last_ms[i] = (double)ms;
-    }
-    if (g_prof.valid == 2) {               // tpe_joint_seg_run: its launches before the merge, summed
-      last_ms[0] = 0.0;
-      for (int i = 0; i < g_sprof.n; ++i) {
-        float ms = 0.f;
-        hipError_t e = hipEventSynchronize(g_sprof.ev[2 * i + 1]);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, g_sprof.ev[2 * i], g_sprof.ev[2 * i + 1]);
-        if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
-        last_ms[0] += (double)ms;
-      }
-    }
-  }
-  if (enable && !g_prof.ev[0])
-    for (int i = 0; i < 4; ++i) {
-      const hipError_t e = hipEventCreate(&g_prof.ev[i]);
-      if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
-    }
-  g_prof.on = enable ? 1 : 0;
-  g_prof.valid = 0;
+int size_out(const char* entry, bool ok, uint64_t value, uint64_t* bytes) {
+  if (!bytes || !ok) return fail(entry, "bad arguments");
+  *bytes = value;
   return TPE_OK;
 }
 
-int tpe_joint_scratch_bytes(int32_t n_ids, int32_t n_cand, uint64_t* bytes) {
-  if (!bytes || n_ids < 1 || n_cand < 1) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_scratch_bytes: bad arguments");
-  *bytes = (uint64_t)n_ids * (uint64_t)n_chunks_of(n_cand) * sizeof(tpe_joint_record);
-  return TPE_OK;
-}
+// ---- what the solo stages share
+// tpe_joint_args, tpe_joint_wide_args and tpe_joint_mixed_args (with it
+// tpe_joint_quant_args, which begins with it) have the same fields at the same
+// offsets up to `low`: the head checks and the JointK fill are templates over them
+static_assert(offsetof(tpe_joint_wide_args, low) == offsetof(tpe_joint_args, low) &&
+                  offsetof(tpe_joint_mixed_args, low) == offsetof(tpe_joint_args, low) &&
+                  offsetof(tpe_joint_mixed_args, n_cat) == offsetof(tpe_joint_args, reserved),
+              "the solo stages' shared head");
+// a mixed group without a discrete label IS a tpe_joint_args (n_cat = 0 reads as reserved)
+static_assert(sizeof(tpe_joint_args) == offsetof(tpe_joint_mixed_args, cat_upper) &&
+                  offsetof(tpe_joint_mixed_args, high) == offsetof(tpe_joint_args, high),
+              "tpe_joint_mixed_args starts with tpe_joint_args");
+// ... and a quantised group without a quantised label a tpe_joint_mixed_args
+static_assert(offsetof(tpe_joint_quant_args, n_quant) == sizeof(tpe_joint_mixed_args) &&
+                  offsetof(tpe_joint_quant_args, cat_cum) == offsetof(tpe_joint_mixed_args, cat_cum),
+              "tpe_joint_quant_args starts with tpe_joint_mixed_args");
 
-// tpe_joint_run with local candidate i as global candidate cand_base + i (tpe_joint_run_shard)
-static int joint_run_at(const tpe_joint_args* a, tpe_joint_record* records, float* cand, double* l_out,
-                        double* g_out, void* scratch, uint64_t scratch_bytes, void* stream, uint32_t cand_base) {
-  tpe_internal_epoch_bump();
-  if (!a) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run: null args");
-  if (a->n_dims < 1 || a->n_dims > TPE_JOINT_MAX_DIMS)
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run: n_dims outside [1, TPE_JOINT_MAX_DIMS]");
-  if (a->n_cand < 1) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run: n_cand < 1");
-  if (a->n_ids < 1) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run: n_ids < 1");
-  if (a->k_below < 1 || a->k_above < 1) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run: k_below < 1 or k_above < 1");
-  if (!a->below_mu || !a->below_a || !a->below_c || !a->above_mu || !a->above_a || !a->above_c)
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run: null density rows");
+// The checks after the stage's own ones on its dimensions; Dc: the continuous
+// coordinates (0: the group has none, and their rows may be null).
+template <typename A, typename Rec>
+int check_solo_head(const char* entry, const A* a, const Rec* records, int Dc) {
+  if (a->n_cand < 1) return fail(entry, "n_cand < 1");
+  if (a->n_ids < 1) return fail(entry, "n_ids < 1");
+  if (a->k_below < 1 || a->k_above < 1) return fail(entry, "k_below < 1 or k_above < 1");
+  if (!a->below_c || !a->above_c || (Dc > 0 && (!a->below_mu || !a->below_a || !a->above_mu || !a->above_a)))
+    return fail(entry, "null density rows");
   const bool inject = (a->flags & TPE_JOINT_INJECT) != 0;
-  if (inject && !a->inject) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run: TPE_JOINT_INJECT without candidates");
-  if (!inject && (!a->samp_cum || !a->samp)) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run: null sampler rows");
-  if (!a->ids || !records) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run: null ids / records");
-  const int64_t n_chunks = n_chunks_of(a->n_cand), blocks = n_chunks * a->n_ids;
-  if (blocks > INT32_MAX) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run: too many candidates");
-  const uint64_t need = (uint64_t)blocks * sizeof(tpe_joint_record);
-  if (!scratch || scratch_bytes < need) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run: scratch too small");
+  if (inject && !a->inject) return fail(entry, "TPE_JOINT_INJECT without candidates");
+  if (!inject && (!a->samp_cum || (Dc > 0 && !a->samp))) return fail(entry, "null sampler rows");
+  if (!a->ids || !records) return fail(entry, "null ids / records");
+  return TPE_OK;
+}
+// every stage's last checks: the launch grid, then the scratch
+int check_scratch(const char* entry, int64_t blocks, uint64_t need, const void* scratch, uint64_t scratch_bytes) {
+  if (blocks > INT32_MAX) return fail(entry, "too many candidates");
+  if (!scratch || scratch_bytes < need) return fail(entry, "scratch too small");
+  return TPE_OK;
+}
 
-  JointK k;
-  k.D = a->n_dims; k.C = a->n_cand; k.n_chunks = (int)n_chunks; k.inject = inject ? 1 : 0;
+// f32 bounds: smallest float >= low, largest float < high
+void f32_bounds(double L, double H, float& lo, float& hi) {
+  lo = -INFINITY; hi = INFINITY;
+  if (L > -INFINITY) { lo = (float)L; if ((double)lo < L) lo = nextafterf(lo, INFINITY); }
+  if (H < INFINITY) { hi = (float)H; while ((double)hi >= H) hi = nextafterf(hi, -INFINITY); }
+}
+
+// the kernels' view of a solo stage's head, Dc continuous coordinates
+template <typename A>
+void fill_joint(JointK& k, const A* a, int Dc, uint32_t cand_base, float* cand, double* l_out, double* g_out,
+                void* scratch) {
+  k.D = Dc; k.C = a->n_cand; k.n_chunks = (int)n_chunks_of(a->n_cand);
+  k.inject = (a->flags & TPE_JOINT_INJECT) ? 1 : 0;
   k.kb = a->k_below; k.ka = a->k_above;
   k.key0 = (uint32_t)a->seed; k.key1 = (uint32_t)(a->seed >> 32); k.stream_word = a->stream_word;
   k.cand_base = cand_base;
@@ -1734,408 +1732,104 @@ static int joint_run_at(const tpe_joint_args* a, tpe_joint_record* records, floa
   k.bbase = a->below_base; k.abase = a->above_base;
   k.cum = a->samp_cum; k.samp = a->samp; k.ids = a->ids; k.inj = a->inject;
   for (int d = 0; d < TPE_JOINT_MAX_DIMS; ++d) {
-    // f32 bounds: smallest float >= low, largest float < high
-    float lo = -INFINITY, hi = INFINITY;
-    if (d < a->n_dims) {
-      const double L = a->low[d], H = a->high[d];
-      if (L > -INFINITY) { lo = (float)L; if ((double)lo < L) lo = nextafterf(lo, INFINITY); }
-      if (H < INFINITY) { hi = (float)H; while ((double)hi >= H) hi = nextafterf(hi, -INFINITY); }
-    }
-    k.lo[d] = lo; k.hi[d] = hi;
+    k.lo[d] = -INFINITY; k.hi[d] = INFINITY;
+    if (d < Dc) f32_bounds(a->low[d], a->high[d], k.lo[d], k.hi[d]);
   }
   k.cand = cand; k.l_out = l_out; k.g_out = g_out;
   k.chunk_rec = (tpe_joint_record*)scratch;
+}
+// ... and of its discrete labels (tpe_joint_mixed_args / tpe_joint_quant_args)
+template <typename A>
+void fill_mixed(MixedK& m, const A* a) {
+  m.Dk = a->n_cat;
+  for (int d = 0; d < TPE_JOINT_MAX_DIMS; ++d) {
+    m.U[d] = d < m.Dk ? a->cat_upper[d] : 1;
+    m.off[d] = d < m.Dk ? a->cat_off[d] : 0;
+  }
+  m.bcat = a->below_cat; m.acat = a->above_cat;
+  m.bmiss = a->below_miss; m.bbonus = a->below_bonus; m.amiss = a->above_miss; m.abonus = a->above_bonus;
+  m.bh = a->below_h; m.ccum = a->cat_cum;
+}
+template <typename A>
+bool cat_tables_null(const A* a) {
+  return !a->below_cat || !a->above_cat || !a->below_miss || !a->below_bonus || !a->above_miss || !a->above_bonus ||
+         !a->below_h || !a->cat_cum;
+}
 
+// ---- category and lattice checks: the total, or -1 with the call's error set
+// n discrete labels' category counts and their offsets in the flat tables
+int64_t check_cats(const char* entry, const char* where, const int32_t* upper, const int32_t* off, int n) {
+  int64_t total = 0;
+  for (int d = 0; d < n; ++d) {
+    if (upper[d] < 2 || upper[d] > TPE_JOINT_MAX_CATS)
+      return fail(entry, "categories of a label outside [2, TPE_JOINT_MAX_CATS]"), -1;
+    total += upper[d];
+  }
+  if (total > TPE_JOINT_MAX_CAT_TOTAL) return fail(entry, "more than TPE_JOINT_MAX_CAT_TOTAL categories", "", where), -1;
+  for (int d = 0; d < n; ++d)
+    if (off[d] < 0 || off[d] > total - upper[d]) return fail(entry, "cat_off outside the tables"), -1;
+  return total;
+}
+// n quantised labels' lattice sizes and, with edge_off (null: the sizes alone, as
+// the table size needs them), their edges' places in an edge array of n_edges
+int64_t check_lattice(const char* entry, const char* where, const int32_t* v, const int32_t* edge_off, int n,
+                      int64_t n_edges) {
+  int64_t total = 0;
+  for (int d = 0; d < n; ++d) {
+    if (v[d] < 2 || v[d] > TPE_JOINT_MAX_LATTICE)
+      return fail(entry, "lattice values of a label outside [2, TPE_JOINT_MAX_LATTICE]"), -1;
+    total += v[d];
+  }
+  if (!edge_off) return total;
+  if (total > TPE_JOINT_MAX_LATTICE_TOTAL)
+    return fail(entry, "more than TPE_JOINT_MAX_LATTICE_TOTAL lattice values", "", where), -1;
+  for (int d = 0; d < n; ++d)
+    if (edge_off[d] < 0 || (int64_t)edge_off[d] + v[d] + 1 > n_edges)
+      return fail(entry, "quant_edge_off outside the edge array"), -1;
+  return total;
+}
+// the dynamic LDS of a quantised chunk launch: the table tile of `total` lattice values
+unsigned quant_lds(int total) { return (unsigned)((total + 1) * (quant_tile(total) + 4) * sizeof(float)); }
+
+// ---- the solo stages; local candidate i is global candidate cand_base + i (tpe_joint_run_shard)
+int joint_run_at(const tpe_joint_args* a, tpe_joint_record* records, float* cand, double* l_out, double* g_out,
+                 void* scratch, uint64_t scratch_bytes, void* stream, uint32_t cand_base) {
+  constexpr const char* E = "tpe_joint_run";
+  tpe_internal_epoch_bump();
+  if (!a) return fail(E, "null args");
+  if (a->n_dims < 1 || a->n_dims > TPE_JOINT_MAX_DIMS) return fail(E, "n_dims outside [1, TPE_JOINT_MAX_DIMS]");
+  if (int rc = check_solo_head(E, a, records, a->n_dims)) return rc;
+  const int64_t blocks = n_chunks_of(a->n_cand) * a->n_ids;
+  if (int rc = check_scratch(E, blocks, joint_scratch_need(a->n_ids, a->n_cand), scratch, scratch_bytes)) return rc;
+
+  JointK k;
+  fill_joint(k, a, a->n_dims, cand_base, cand, l_out, g_out, scratch);
   const bool timed = g_prof.on != 0;
   hipStream_t s = (hipStream_t)stream;
-  const unsigned nb = (unsigned)blocks;
-  const int D = a->n_dims;
-  if (D == 1) launch_chunk<1>(k, nb, s, timed);
-  else if (D == 2) launch_chunk<2>(k, nb, s, timed);
-  else if (D == 3) launch_chunk<3>(k, nb, s, timed);
-  else if (D == 4) launch_chunk<4>(k, nb, s, timed);
-  else if (D <= 6) launch_chunk<6>(k, nb, s, timed);
-  else if (D <= 8) launch_chunk<8>(k, nb, s, timed);
-  else if (D <= 12) launch_chunk<12>(k, nb, s, timed);
-  else launch_chunk<16>(k, nb, s, timed);
-  if (timed) {
-    hipExtLaunchKernelGGL(k_joint_merge, dim3((unsigned)a->n_ids), dim3(64), 0u, s, g_prof.ev[2], g_prof.ev[3], 0u,
-                          (const tpe_joint_record*)scratch, (int)n_chunks, records);
-    g_prof.valid = 1;
-  } else {
-    hipLaunchKernelGGL(k_joint_merge, dim3((unsigned)a->n_ids), dim3(64), 0, s, (const tpe_joint_record*)scratch,
-                       (int)n_chunks, records);
-  }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
-  return TPE_OK;
+  const Ev ev = chunk_marks(timed);
+  for_dp(dp_class(a->n_dims), [&](auto dp) {
+    launch(k_joint_chunk<decltype(dp)::value>, dim3((unsigned)blocks), kThreads, 0u, s, ev.start, ev.stop, k);
+  });
+  return finish(k_joint_merge, (const tpe_joint_record*)scratch, k.n_chunks, records, a->n_ids, s, timed, 1);
 }
 
-int tpe_joint_seg_scratch_bytes(int32_t n_probs, int32_t n_cand, uint64_t* bytes) {
-  if (!bytes || n_probs < 1 || n_cand < 1)
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_scratch_bytes: bad arguments");
-  *bytes = seg_order_bytes(n_probs) + (uint64_t)n_probs * (uint64_t)n_chunks_of(n_cand) * sizeof(tpe_joint_record);
-  return TPE_OK;
-}
-
-// tpe_joint_seg_run with local candidate i as global candidate cand_base + i (tpe_joint_run_shard)
-static int joint_seg_run_at(const tpe_joint_seg_args* a, tpe_joint_record* records, float* cand, double* l_out,
-                            double* g_out, void* scratch, uint64_t scratch_bytes, void* stream, uint32_t cand_base) {
+int joint_wide_run_at(const tpe_joint_wide_args* a, tpe_joint_wide_record* records, float* cand, double* l_out,
+                      double* g_out, void* scratch, uint64_t scratch_bytes, void* stream, uint32_t cand_base) {
+  constexpr const char* E = "tpe_joint_wide_run";
   tpe_internal_epoch_bump();
-  if (!a) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: null args");
-  if (a->n_segs < 1) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: n_segs < 1");
-  if (a->n_probs < 1) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: n_probs < 1");
-  if (a->n_cand < 1) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: n_cand < 1");
-  if (!a->segs || !a->host_segs) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: null segs / host_segs");
-  const bool inject = (a->flags & TPE_JOINT_INJECT) != 0;
-  if (!a->pool_f32 || (!inject && !a->pool_f64)) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: null pool");
-  if (!a->prob_seg || !a->host_prob_seg || !a->prob_id)
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: null prob_seg / host_prob_seg / prob_id");
-  if (!records) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: null records");
-  if (cand && !a->cand_off) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: cand without cand_off");
-  // rows [off, off + n) inside a pool of len elements
-  auto inside = [](int64_t off, int64_t n, int64_t len) { return off >= 0 && n <= len && off <= len - n; };
-  for (int s = 0; s < a->n_segs; ++s) {
-    const tpe_joint_seg& g = a->host_segs[s];
-    if (g.n_dims < 1 || g.n_dims > TPE_JOINT_MAX_DIMS)
-      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: a segment's n_dims outside [1, TPE_JOINT_MAX_DIMS]");
-    if (g.k_below < 1 || g.k_above < 1)
-      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: a segment's k_below < 1 or k_above < 1");
-    const int64_t D = g.n_dims, kb = g.k_below, ka = g.k_above, L = a->pool_f32_len;
-    bool ok = inside(g.below_mu, kb * D, L) && inside(g.below_a, kb * D, L) && inside(g.below_c, kb, L) &&
-              inside(g.above_mu, ka * D, L) && inside(g.above_a, ka * D, L) && inside(g.above_c, ka, L);
-    if (!inject) ok = ok && inside(g.samp, kb * D * 5, L) && inside(g.samp_cum, kb, a->pool_f64_len);
-    if (inject && g.inject >= 0) ok = ok && inside(g.inject, (int64_t)a->n_cand * D, L);
-    if (!ok) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: a segment's rows leave its pool");
-  }
-  int64_t per_class[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (int p = 0; p < a->n_probs; ++p) {
-    const int s = a->host_prob_seg[p];
-    if (s < 0 || s >= a->n_segs) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: prob_seg outside [0, n_segs)");
-    if (inject && a->host_segs[s].inject < 0)
-      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: TPE_JOINT_INJECT without candidates");
-    ++per_class[dp_class(a->host_segs[s].n_dims)];
-  }
-  const int64_t n_chunks = n_chunks_of(a->n_cand), blocks = n_chunks * a->n_probs;
-  if (blocks > INT32_MAX || (int64_t)a->n_segs * 8 > INT32_MAX)
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: too many candidates");
-  const uint64_t need = seg_order_bytes(a->n_probs) + (uint64_t)blocks * sizeof(tpe_joint_record);
-  if (!scratch || scratch_bytes < need) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_seg_run: scratch too small");
-
-  SegK k;
-  k.C = a->n_cand; k.n_chunks = (int)n_chunks; k.inject = inject ? 1 : 0; k.first = 0;
-  k.n_probs = a->n_probs; k.n_segs = a->n_segs;
-  k.key0 = (uint32_t)a->seed; k.key1 = (uint32_t)(a->seed >> 32); k.cand_base = cand_base;
-  k.segs = a->segs; k.pool = a->pool_f32; k.pool64 = a->pool_f64;
-  k.prob_seg = a->prob_seg; k.prob_id = a->prob_id; k.cand_off = a->cand_off;
-  k.order = (int32_t*)scratch;
-  k.cand = cand; k.l_out = l_out; k.g_out = g_out;
-  k.chunk_rec = (tpe_joint_record*)((char*)scratch + seg_order_bytes(a->n_probs));
-
-  const bool timed = g_prof.on != 0;
-  hipStream_t s = (hipStream_t)stream;
-  if (timed && !g_sprof.ev[2 * kSegLaunches - 1])
-    for (int i = 0; i < 2 * kSegLaunches; ++i) {
-      if (g_sprof.ev[i]) continue;
-      const hipError_t e = hipEventCreate(&g_sprof.ev[i]);
-      if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
-    }
-  int n_timed = 0;
-  const unsigned ob = (unsigned)((a->n_probs + kThreads - 1) / kThreads);
-  if (timed) {
-    hipExtLaunchKernelGGL(k_joint_seg_order<false>, dim3(ob), dim3(kThreads), 0u, s, g_sprof.ev[0], g_sprof.ev[1], 0u, k);
-    n_timed = 1;
-  } else {
-    hipLaunchKernelGGL(k_joint_seg_order<false>, dim3(ob), dim3(kThreads), 0, s, k);
-  }
-  int64_t first = 0;
-  for (int c = 0; c < 8; ++c) {
-    if (!per_class[c]) continue;
-    k.first = (int)first;
-    const unsigned nb = (unsigned)(per_class[c] * n_chunks);
-    hipEvent_t* ev = timed ? g_sprof.ev + 2 * n_timed++ : nullptr;
-    switch (c) {
-      case 0: launch_seg<1>(k, nb, s, ev); break;
-      case 1: launch_seg<2>(k, nb, s, ev); break;
-      case 2: launch_seg<3>(k, nb, s, ev); break;
-      case 3: launch_seg<4>(k, nb, s, ev); break;
-      case 4: launch_seg<6>(k, nb, s, ev); break;
-      case 5: launch_seg<8>(k, nb, s, ev); break;
-      case 6: launch_seg<12>(k, nb, s, ev); break;
-      default: launch_seg<16>(k, nb, s, ev); break;
-    }
-    first += per_class[c];
-  }
-  if (timed) {
-    hipExtLaunchKernelGGL(k_joint_merge, dim3((unsigned)a->n_probs), dim3(64), 0u, s, g_prof.ev[2], g_prof.ev[3], 0u,
-                          (const tpe_joint_record*)k.chunk_rec, (int)n_chunks, records);
-    g_sprof.n = n_timed;
-    g_prof.valid = 2;
-  } else {
-    hipLaunchKernelGGL(k_joint_merge, dim3((unsigned)a->n_probs), dim3(64), 0, s,
-                       (const tpe_joint_record*)k.chunk_rec, (int)n_chunks, records);
-  }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
-  return TPE_OK;
-}
-
-int tpe_joint_mseg_scratch_bytes(int32_t n_probs, int32_t n_cand, uint64_t* bytes) {
-  if (!bytes || n_probs < 1 || n_cand < 1)
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_scratch_bytes: bad arguments");
-  *bytes = seg_order_bytes(n_probs) + (uint64_t)n_probs * (uint64_t)n_chunks_of(n_cand) * sizeof(tpe_joint_record);
-  return TPE_OK;
-}
-
-int tpe_joint_mseg_table_bytes(const tpe_joint_mseg* host_segs, int32_t n_segs, uint64_t* bytes) {
-  if (!bytes || !host_segs || n_segs < 1)
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_table_bytes: bad arguments");
-  uint64_t n = 0;
-  for (int s = 0; s < n_segs; ++s) {
-    const tpe_joint_mseg& g = host_segs[s];
-    if (g.n_quant < 0 || g.n_quant > TPE_JOINT_MAX_QUANT || g.k_below < 1 || g.k_above < 1)
-      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_table_bytes: a segment's n_quant, k_below or k_above out of range");
-    uint64_t total = 0;
-    for (int d = 0; d < g.n_quant; ++d) {
-      if (g.quant_v[d] < 2 || g.quant_v[d] > TPE_JOINT_MAX_LATTICE)
-        return tpe_internal_fail(TPE_E_ARG,
-                                 "tpe_joint_mseg_table_bytes: lattice values of a label outside [2, TPE_JOINT_MAX_LATTICE]");
-      total += (uint64_t)g.quant_v[d];
-    }
-    n += ((uint64_t)g.k_below + (uint64_t)g.k_above) * total;
-  }
-  *bytes = n * sizeof(float);
-  return TPE_OK;
-}
-
-// tpe_joint_mseg_run with local candidate i as global candidate cand_base + i (tpe_joint_run_shard)
-static int joint_mseg_run_at(const tpe_joint_mseg_args* a, tpe_joint_record* records, float* cand, double* l_out,
-                             double* g_out, void* scratch, uint64_t scratch_bytes, void* stream, uint32_t cand_base) {
-  tpe_internal_epoch_bump();
-  static_assert(offsetof(tpe_joint_mseg, hi) == offsetof(tpe_joint_seg, hi) &&
-                    offsetof(tpe_joint_mseg, n_cat) == sizeof(tpe_joint_seg),
-                "tpe_joint_mseg starts with tpe_joint_seg");
-  static_assert(offsetof(tpe_joint_mseg_args, cand_off) == offsetof(tpe_joint_seg_args, cand_off), "the shared fields");
-  if (!a) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: null args");
-  if (a->n_segs < 1) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: n_segs < 1");
-  if (a->n_segs > 32767) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: more than 32767 segments");
-  if (a->n_probs < 1) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: n_probs < 1");
-  if (a->n_cand < 1) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: n_cand < 1");
-  if (!a->segs || !a->host_segs) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: null segs / host_segs");
-  const bool inject = (a->flags & TPE_JOINT_INJECT) != 0;
-  if (!a->pool_f32 || (!inject && !a->pool_f64)) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: null pool");
-  if (!a->prob_seg || !a->host_prob_seg || !a->prob_id)
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: null prob_seg / host_prob_seg / prob_id");
-  if (!records) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: null records");
-  if (cand && !a->cand_off) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: cand without cand_off");
-  // rows [off, off + n) inside a pool of len elements
-  auto inside = [](int64_t off, int64_t n, int64_t len) { return off >= 0 && n <= len && off <= len - n; };
-  const int64_t L = a->pool_f32_len, L64 = a->pool_f64_len, LT = (int64_t)(a->quant_table_bytes / sizeof(float));
-  int max_kblocks = 0;
-  bool any_quant = false;
-  for (int s = 0; s < a->n_segs; ++s) {
-    const tpe_joint_mseg& g = a->host_segs[s];
-    if (g.n_cat < 0 || g.n_cat > TPE_JOINT_MAX_DIMS)
-      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: a segment's n_cat outside [0, TPE_JOINT_MAX_DIMS]");
-    if (g.n_quant < 0 || g.n_quant > TPE_JOINT_MAX_QUANT)
-      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: a segment's n_quant outside [0, TPE_JOINT_MAX_QUANT]");
-    const int64_t Dc = g.n_dims, Dk = g.n_cat, Dq = g.n_quant, D = Dc + Dk + Dq, kb = g.k_below, ka = g.k_above;
-    if (Dk + Dq == 0) {
-      if (Dc < 1 || Dc > TPE_JOINT_MAX_DIMS)
-        return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: a segment's n_dims outside [1, TPE_JOINT_MAX_DIMS]");
-    } else {
-      if (Dc < 0) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: a segment's n_dims < 0");
-      if (Dc > TPE_JOINT_MSEG_MAX_CONT || Dk > TPE_JOINT_MSEG_MAX_CAT)
-        return tpe_internal_fail(TPE_E_ARG,
-                                 "tpe_joint_mseg_run: n_dims > 8 or n_cat > 4 in a segment with a discrete or quantised label");
-    }
-    if (kb < 1 || ka < 1)
-      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: a segment's k_below < 1 or k_above < 1");
-    int64_t cat_total = 0, total = 0;
-    for (int d = 0; d < Dk; ++d) {
-      if (g.cat_upper[d] < 2 || g.cat_upper[d] > TPE_JOINT_MAX_CATS)
-        return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: categories of a label outside [2, TPE_JOINT_MAX_CATS]");
-      cat_total += g.cat_upper[d];
-    }
-    if (cat_total > TPE_JOINT_MAX_CAT_TOTAL)
-      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: more than TPE_JOINT_MAX_CAT_TOTAL categories in a segment");
-    for (int d = 0; d < Dk; ++d)
-      if (g.cat_off[d] < 0 || g.cat_off[d] > cat_total - g.cat_upper[d])
-        return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: cat_off outside the tables");
-    for (int d = 0; d < Dq; ++d) {
-      if (g.quant_v[d] < 2 || g.quant_v[d] > TPE_JOINT_MAX_LATTICE)
-        return tpe_internal_fail(TPE_E_ARG,
-                                 "tpe_joint_mseg_run: lattice values of a label outside [2, TPE_JOINT_MAX_LATTICE]");
-      total += g.quant_v[d];
-    }
-    if (total > TPE_JOINT_MAX_LATTICE_TOTAL)
-      return tpe_internal_fail(TPE_E_ARG,
-                               "tpe_joint_mseg_run: more than TPE_JOINT_MAX_LATTICE_TOTAL lattice values in a segment");
-    for (int d = 0; d < Dq; ++d)
-      if (g.quant_edge_off[d] < 0 || (int64_t)g.quant_edge_off[d] + g.quant_v[d] + 1 > (int64_t)g.n_edges)
-        return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: quant_edge_off outside the edge array");
-    if (Dq > 0 && !a->pool_f64)
-      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: null pool_f64 with a quantised segment");
-    if (Dq > 0 && !a->quant_table)
-      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: null table workspace with a quantised segment");
-    bool ok = inside(g.below_c, kb, L) && inside(g.above_c, ka, L);
-    if (Dc > 0)
-      ok = ok && inside(g.below_mu, kb * Dc, L) && inside(g.below_a, kb * Dc, L) && inside(g.above_mu, ka * Dc, L) &&
-           inside(g.above_a, ka * Dc, L);
-    if (!inject) ok = ok && inside(g.samp_cum, kb, L64) && (Dc == 0 || inside(g.samp, kb * Dc * 5, L));
-    if (inject && g.inject >= 0) ok = ok && inside(g.inject, (int64_t)a->n_cand * D, L);
-    if (Dk > 0) {
-      ok = ok && inside(g.below_cat, kb * Dk, L) && inside(g.above_cat, ka * Dk, L) &&
-           inside(g.below_miss, cat_total, L) && inside(g.below_bonus, cat_total, L) &&
-           inside(g.above_miss, cat_total, L) && inside(g.above_bonus, cat_total, L);
-      if (!inject) ok = ok && inside(g.below_h, Dk, L64) && inside(g.cat_cum, cat_total, L64);
-    }
-    if (Dq > 0) {
-      ok = ok && inside(g.quant_edges, g.n_edges, L64) && inside(g.below_qmu, kb * Dq, L64) &&
-           inside(g.below_qsigma, kb * Dq, L64) && inside(g.above_qmu, ka * Dq, L64) &&
-           inside(g.above_qsigma, ka * Dq, L64);
-      if (!inject) ok = ok && inside(g.quant_samp, kb * Dq * 5, L);
-    }
-    if (!ok) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: a segment's rows leave its pool");
-    if (Dq > 0) {
-      if (!inside(g.table, (kb + ka) * total, LT))
-        return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: a segment's table leaves the table workspace");
-      any_quant = true;
-      const int64_t km = kb > ka ? kb : ka;
-      max_kblocks = (int)((km + kThreads - 1) / kThreads) > max_kblocks ? (int)((km + kThreads - 1) / kThreads) : max_kblocks;
-    }
-  }
-  int64_t per_class[kMClasses];
-  unsigned lds_class[kMClasses];
-  for (int c = 0; c < kMClasses; ++c) { per_class[c] = 0; lds_class[c] = 0u; }
-  for (int p = 0; p < a->n_probs; ++p) {
-    const int s = a->host_prob_seg[p];
-    if (s < 0 || s >= a->n_segs) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: prob_seg outside [0, n_segs)");
-    const tpe_joint_mseg& g = a->host_segs[s];
-    if (inject && g.inject < 0)
-      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: TPE_JOINT_INJECT without candidates");
-    const int c = mseg_class(g.n_dims, g.n_cat, g.n_quant);
-    ++per_class[c];
-    if (g.n_quant > 0) {                     // the segment's own tile (the solo run's rule); the launch takes the largest
-      int total = 0;
-      for (int d = 0; d < g.n_quant; ++d) total += g.quant_v[d];
-      const unsigned lds = (unsigned)((total + 1) * (quant_tile(total) + 4) * sizeof(float));
-      if (lds > lds_class[c]) lds_class[c] = lds;
-    }
-  }
-  const int64_t n_chunks = n_chunks_of(a->n_cand), blocks = n_chunks * a->n_probs;
-  if (blocks > INT32_MAX || (int64_t)a->n_segs * kMClasses > INT32_MAX)
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: too many candidates");
-  const uint64_t need = seg_order_bytes(a->n_probs) + (uint64_t)blocks * sizeof(tpe_joint_record);
-  if (!scratch || scratch_bytes < need) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mseg_run: scratch too small");
-
-  MSegK mk;
-  SegK& k = mk.s;
-  k.C = a->n_cand; k.n_chunks = (int)n_chunks; k.inject = inject ? 1 : 0; k.first = 0;
-  k.n_probs = a->n_probs; k.n_segs = a->n_segs;
-  k.key0 = (uint32_t)a->seed; k.key1 = (uint32_t)(a->seed >> 32); k.cand_base = cand_base;
-  k.segs = reinterpret_cast<const tpe_joint_seg*>(a->segs); k.pool = a->pool_f32; k.pool64 = a->pool_f64;
-  k.prob_seg = a->prob_seg; k.prob_id = a->prob_id; k.cand_off = a->cand_off;
-  k.order = (int32_t*)scratch;
-  k.cand = cand; k.l_out = l_out; k.g_out = g_out;
-  k.chunk_rec = (tpe_joint_record*)((char*)scratch + seg_order_bytes(a->n_probs));
-  mk.table = a->quant_table;
-
-  const bool timed = g_prof.on != 0;
-  hipStream_t s = (hipStream_t)stream;
-  if (timed && !g_sprof.ev[2 * kSegLaunches - 1])
-    for (int i = 0; i < 2 * kSegLaunches; ++i) {
-      if (g_sprof.ev[i]) continue;
-      const hipError_t e = hipEventCreate(&g_sprof.ev[i]);
-      if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
-    }
-  int n_timed = 0;
-  const unsigned ob = (unsigned)((a->n_probs + kThreads - 1) / kThreads);
-  if (timed) {
-    hipExtLaunchKernelGGL(k_joint_seg_order<true>, dim3(ob), dim3(kThreads), 0u, s, g_sprof.ev[0], g_sprof.ev[1], 0u, k);
-    n_timed = 1;
-  } else {
-    hipLaunchKernelGGL(k_joint_seg_order<true>, dim3(ob), dim3(kThreads), 0, s, k);
-  }
-  if (any_quant) {
-    const dim3 grid((unsigned)max_kblocks, (unsigned)TPE_JOINT_MAX_QUANT, (unsigned)(2 * a->n_segs));
-    if (timed) {
-      hipExtLaunchKernelGGL(k_joint_mseg_qtable, grid, dim3(kThreads), 0u, s, g_sprof.ev[2 * n_timed],
-                            g_sprof.ev[2 * n_timed + 1], 0u, mk);
-      ++n_timed;
-    } else {
-      hipLaunchKernelGGL(k_joint_mseg_qtable, grid, dim3(kThreads), 0, s, mk);
-    }
-  }
-  int64_t first = 0;
-  for (int c = 0; c < kMClasses; ++c) {
-    if (!per_class[c]) continue;
-    k.first = (int)first;
-    hipEvent_t* ev = timed ? g_sprof.ev + 2 * n_timed++ : nullptr;
-    launch_mseg_class(c, mk, (unsigned)(per_class[c] * n_chunks), lds_class[c], s, ev);
-    first += per_class[c];
-  }
-  if (timed) {
-    hipExtLaunchKernelGGL(k_joint_merge, dim3((unsigned)a->n_probs), dim3(64), 0u, s, g_prof.ev[2], g_prof.ev[3], 0u,
-                          (const tpe_joint_record*)k.chunk_rec, (int)n_chunks, records);
-    g_sprof.n = n_timed;
-    g_prof.valid = 2;
-  } else {
-    hipLaunchKernelGGL(k_joint_merge, dim3((unsigned)a->n_probs), dim3(64), 0, s,
-                       (const tpe_joint_record*)k.chunk_rec, (int)n_chunks, records);
-  }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
-  return TPE_OK;
-}
-
-int tpe_joint_wide_scratch_bytes(int32_t n_ids, int32_t n_cand, int32_t n_dims, uint64_t* bytes) {
-  if (!bytes || n_ids < 1 || n_cand < 1 || n_dims < 1 || n_dims > TPE_JOINT_WIDE_MAX_DIMS)
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_wide_scratch_bytes: bad arguments");
-  *bytes = wide_record_bytes(n_ids, n_cand, n_dims) + wide_zbuf_bytes(n_ids, n_cand, n_dims);
-  return TPE_OK;
-}
-
-int tpe_joint_wide_profile(double* sample_ms) {
-  if (!sample_ms || !g_wprof.valid)
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_wide_profile: no profiled sampling tpe_joint_wide_run to read");
-  float ms = 0.f;
-  hipError_t e = hipEventSynchronize(g_wprof.ev[1]);
-  if (e == hipSuccess) e = hipEventElapsedTime(&ms, g_wprof.ev[0], g_wprof.ev[1]);
-  if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
-  *sample_ms = (double)ms;
-  return TPE_OK;
-}
-
-// tpe_joint_wide_run with local candidate i as global candidate cand_base + i (tpe_joint_run_shard)
-static int joint_wide_run_at(const tpe_joint_wide_args* a, tpe_joint_wide_record* records, float* cand, double* l_out,
-                             double* g_out, void* scratch, uint64_t scratch_bytes, void* stream, uint32_t cand_base) {
-  tpe_internal_epoch_bump();
-  if (!a) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_wide_run: null args");
+  if (!a) return fail(E, "null args");
   if (a->n_dims < 1 || a->n_dims > TPE_JOINT_WIDE_MAX_DIMS)
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_wide_run: n_dims outside [1, TPE_JOINT_WIDE_MAX_DIMS]");
-  if (a->n_cand < 1) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_wide_run: n_cand < 1");
-  if (a->n_ids < 1) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_wide_run: n_ids < 1");
-  if (a->k_below < 1 || a->k_above < 1)
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_wide_run: k_below < 1 or k_above < 1");
-  if (!a->below_mu || !a->below_a || !a->below_c || !a->above_mu || !a->above_a || !a->above_c)
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_wide_run: null density rows");
-  const bool inject = (a->flags & TPE_JOINT_INJECT) != 0;
-  if (inject && !a->inject)
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_wide_run: TPE_JOINT_INJECT without candidates");
-  if (!inject && (!a->samp_cum || !a->samp)) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_wide_run: null sampler rows");
-  if (!a->ids || !records) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_wide_run: null ids / records");
+    return fail(E, "n_dims outside [1, TPE_JOINT_WIDE_MAX_DIMS]");
+  if (int rc = check_solo_head(E, a, records, a->n_dims)) return rc;
   const int D = a->n_dims;
+  const bool inject = (a->flags & TPE_JOINT_INJECT) != 0;
   const int64_t n_chunks = wide_chunks_of(a->n_cand, D), blocks = n_chunks * a->n_ids;
   const int64_t nblk = wide_blocks_of(a->n_cand), sblocks = nblk * a->n_ids;
-  if (sblocks > INT32_MAX) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_wide_run: too many candidates");
-  const uint64_t rec_bytes = wide_record_bytes(a->n_ids, a->n_cand, D);
-  const uint64_t need = rec_bytes + wide_zbuf_bytes(a->n_ids, a->n_cand, D);
-  if (!scratch || scratch_bytes < need) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_wide_run: scratch too small");
+  if (int rc = check_scratch(E, sblocks, wide_scratch_need(a->n_ids, a->n_cand, D), scratch, scratch_bytes)) return rc;
 
   const bool timed = g_prof.on != 0;
   hipStream_t s = (hipStream_t)stream;
-  float* zbuf = (float*)((char*)scratch + rec_bytes);
+  float* zbuf = (float*)((char*)scratch + wide_record_bytes(a->n_ids, a->n_cand, D));
   g_wprof.valid = 0;
   if (!inject) {
     WideSampK sk;
@@ -2144,27 +1838,14 @@ static int joint_wide_run_at(const tpe_joint_wide_args* a, tpe_joint_wide_record
     sk.cand_base = cand_base;
     sk.cum = a->samp_cum; sk.samp = a->samp; sk.ids = a->ids; sk.zbuf = zbuf;
     for (int d = 0; d < TPE_JOINT_WIDE_MAX_DIMS; ++d) {
-      // f32 bounds: smallest float >= low, largest float < high (as tpe_joint_run)
-      float lo = -INFINITY, hi = INFINITY;
-      if (d < D) {
-        const double L = a->low[d], H = a->high[d];
-        if (L > -INFINITY) { lo = (float)L; if ((double)lo < L) lo = nextafterf(lo, INFINITY); }
-        if (H < INFINITY) { hi = (float)H; while ((double)hi >= H) hi = nextafterf(hi, -INFINITY); }
-      }
-      sk.lo[d] = lo; sk.hi[d] = hi;
+      sk.lo[d] = -INFINITY; sk.hi[d] = INFINITY;
+      if (d < D) f32_bounds(a->low[d], a->high[d], sk.lo[d], sk.hi[d]);
     }
-    if (timed) {
-      if (!g_wprof.ev[0])
-        for (int i = 0; i < 2; ++i) {
-          const hipError_t e = hipEventCreate(&g_wprof.ev[i]);
-          if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
-        }
-      hipExtLaunchKernelGGL(k_joint_wide_sample, dim3((unsigned)sblocks), dim3(kThreads), 0u, s, g_wprof.ev[0],
-                            g_wprof.ev[1], 0u, sk);
-      g_wprof.valid = 1;
-    } else {
-      hipLaunchKernelGGL(k_joint_wide_sample, dim3((unsigned)sblocks), dim3(kThreads), 0, s, sk);
-    }
+    if (timed)
+      if (int rc = ensure_events(g_wprof.ev, 2)) return rc;
+    launch(k_joint_wide_sample, dim3((unsigned)sblocks), kThreads, 0u, s, timed ? g_wprof.ev[0] : nullptr,
+           timed ? g_wprof.ev[1] : nullptr, sk);
+    g_wprof.valid = timed ? 1 : 0;
   }
 
   WideK k;
@@ -2176,250 +1857,87 @@ static int joint_wide_run_at(const tpe_joint_wide_args* a, tpe_joint_wide_record
   k.zsrc = inject ? a->inject : zbuf;
   k.cand = cand; k.l_out = l_out; k.g_out = g_out;
   k.chunk_rec = (tpe_joint_wide_record*)scratch;
-
-  const unsigned nb = (unsigned)blocks;
-  switch (wide_dp(D)) {
-    case 20: launch_wide<20>(k, nb, s, timed); break;
-    case 24: launch_wide<24>(k, nb, s, timed); break;
-    case 32: launch_wide<32>(k, nb, s, timed); break;
-    case 48: launch_wide<48>(k, nb, s, timed); break;
-    default: launch_wide<64>(k, nb, s, timed); break;
-  }
-  if (timed) {
-    hipExtLaunchKernelGGL(k_joint_wide_merge, dim3((unsigned)a->n_ids), dim3(64), 0u, s, g_prof.ev[2], g_prof.ev[3],
-                          0u, (const tpe_joint_wide_record*)scratch, (int)n_chunks, records);
-    g_prof.valid = 1;
-  } else {
-    hipLaunchKernelGGL(k_joint_wide_merge, dim3((unsigned)a->n_ids), dim3(64), 0, s,
-                       (const tpe_joint_wide_record*)scratch, (int)n_chunks, records);
-  }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
-  return TPE_OK;
+  const Ev ev = chunk_marks(timed);
+  for_wide_dp(D, [&](auto dp) {
+    constexpr int DP = decltype(dp)::value;
+    launch(k_joint_wide_chunk<DP, wide_r(DP)>, dim3((unsigned)blocks), kThreads, 0u, s, ev.start, ev.stop, k);
+  });
+  return finish(k_joint_wide_merge, (const tpe_joint_wide_record*)scratch, (int)n_chunks, records, a->n_ids, s, timed, 1);
 }
 
-// tpe_joint_mixed_run with local candidate i as global candidate cand_base + i (tpe_joint_run_shard)
-static int joint_mixed_run_at(const tpe_joint_mixed_args* a, tpe_joint_record* records, float* cand, double* l_out,
-                              double* g_out, void* scratch, uint64_t scratch_bytes, void* stream, uint32_t cand_base) {
+int joint_mixed_run_at(const tpe_joint_mixed_args* a, tpe_joint_record* records, float* cand, double* l_out,
+                       double* g_out, void* scratch, uint64_t scratch_bytes, void* stream, uint32_t cand_base) {
+  constexpr const char* E = "tpe_joint_mixed_run";
   tpe_internal_epoch_bump();
-  if (!a) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: null args");
-  if (a->n_cat < 0) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: n_cat < 0");
+  if (!a) return fail(E, "null args");
+  if (a->n_cat < 0) return fail(E, "n_cat < 0");
   if (a->n_dims < 0 || a->n_dims > TPE_JOINT_MAX_DIMS || a->n_dims + a->n_cat < 1 ||
       a->n_dims + a->n_cat > TPE_JOINT_MAX_DIMS)
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: n_dims + n_cat outside [1, TPE_JOINT_MAX_DIMS]");
+    return fail(E, "n_dims + n_cat outside [1, TPE_JOINT_MAX_DIMS]");
   if (a->n_cat == 0) {                      // no discrete label: the continuous stage, the same bytes
     tpe_joint_args c;
-    c.n_dims = a->n_dims; c.n_cand = a->n_cand; c.n_ids = a->n_ids; c.flags = a->flags;
-    c.k_below = a->k_below; c.k_above = a->k_above; c.stream_word = a->stream_word; c.reserved = 0;
-    c.seed = a->seed;
-    c.below_mu = a->below_mu; c.below_a = a->below_a; c.below_c = a->below_c;
-    c.above_mu = a->above_mu; c.above_a = a->above_a; c.above_c = a->above_c;
-    c.below_base = a->below_base; c.above_base = a->above_base;
-    c.samp_cum = a->samp_cum; c.samp = a->samp; c.ids = a->ids; c.inject = a->inject;
-    for (int d = 0; d < TPE_JOINT_MAX_DIMS; ++d) { c.low[d] = a->low[d]; c.high[d] = a->high[d]; }
+    memcpy(&c, a, sizeof c);
     return joint_run_at(&c, records, cand, l_out, g_out, scratch, scratch_bytes, stream, cand_base);
   }
   const int Dc = a->n_dims, Dk = a->n_cat;
-  if (a->n_cand < 1) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: n_cand < 1");
-  if (a->n_ids < 1) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: n_ids < 1");
-  if (a->k_below < 1 || a->k_above < 1)
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: k_below < 1 or k_above < 1");
-  if (!a->below_c || !a->above_c || (Dc > 0 && (!a->below_mu || !a->below_a || !a->above_mu || !a->above_a)))
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: null density rows");
-  const bool inject = (a->flags & TPE_JOINT_INJECT) != 0;
-  if (inject && !a->inject)
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: TPE_JOINT_INJECT without candidates");
-  if (!inject && (!a->samp_cum || (Dc > 0 && !a->samp)))
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: null sampler rows");
-  if (!a->ids || !records) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: null ids / records");
-  if (!a->below_cat || !a->above_cat || !a->below_miss || !a->below_bonus || !a->above_miss || !a->above_bonus ||
-      !a->below_h || !a->cat_cum)
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: null category tables");
-  int total = 0;
-  for (int d = 0; d < Dk; ++d) {
-    if (a->cat_upper[d] < 2 || a->cat_upper[d] > TPE_JOINT_MAX_CATS)
-      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: categories of a label outside [2, TPE_JOINT_MAX_CATS]");
-    total += a->cat_upper[d];
-  }
-  if (total > TPE_JOINT_MAX_CAT_TOTAL)
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: more than TPE_JOINT_MAX_CAT_TOTAL categories");
-  for (int d = 0; d < Dk; ++d)
-    if (a->cat_off[d] < 0 || a->cat_off[d] > total - a->cat_upper[d])
-      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: cat_off outside the tables");
-  const int64_t n_chunks = n_chunks_of(a->n_cand), blocks = n_chunks * a->n_ids;
-  if (blocks > INT32_MAX) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: too many candidates");
-  const uint64_t need = (uint64_t)blocks * sizeof(tpe_joint_record);
-  if (!scratch || scratch_bytes < need) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_mixed_run: scratch too small");
+  if (int rc = check_solo_head(E, a, records, Dc)) return rc;
+  if (cat_tables_null(a)) return fail(E, "null category tables");
+  if (check_cats(E, "", a->cat_upper, a->cat_off, Dk) < 0) return TPE_E_ARG;
+  const int64_t blocks = n_chunks_of(a->n_cand) * a->n_ids;
+  if (int rc = check_scratch(E, blocks, joint_scratch_need(a->n_ids, a->n_cand), scratch, scratch_bytes)) return rc;
 
   MixedK m;
-  JointK& k = m.j;
-  k.D = Dc; k.C = a->n_cand; k.n_chunks = (int)n_chunks; k.inject = inject ? 1 : 0;
-  k.kb = a->k_below; k.ka = a->k_above;
-  k.key0 = (uint32_t)a->seed; k.key1 = (uint32_t)(a->seed >> 32); k.stream_word = a->stream_word;
-  k.cand_base = cand_base;
-  k.bmu = a->below_mu; k.ba = a->below_a; k.bc = a->below_c;
-  k.amu = a->above_mu; k.aa = a->above_a; k.ac = a->above_c;
-  k.bbase = a->below_base; k.abase = a->above_base;
-  k.cum = a->samp_cum; k.samp = a->samp; k.ids = a->ids; k.inj = a->inject;
-  for (int d = 0; d < TPE_JOINT_MAX_DIMS; ++d) {
-    // f32 bounds: smallest float >= low, largest float < high (as tpe_joint_run)
-    float lo = -INFINITY, hi = INFINITY;
-    if (d < Dc) {
-      const double L = a->low[d], H = a->high[d];
-      if (L > -INFINITY) { lo = (float)L; if ((double)lo < L) lo = nextafterf(lo, INFINITY); }
-      if (H < INFINITY) { hi = (float)H; while ((double)hi >= H) hi = nextafterf(hi, -INFINITY); }
-    }
-    k.lo[d] = lo; k.hi[d] = hi;
-    m.U[d] = d < Dk ? a->cat_upper[d] : 1;
-    m.off[d] = d < Dk ? a->cat_off[d] : 0;
-  }
-  k.cand = cand; k.l_out = l_out; k.g_out = g_out;
-  k.chunk_rec = (tpe_joint_record*)scratch;
-  m.Dk = Dk;
-  m.bcat = a->below_cat; m.acat = a->above_cat;
-  m.bmiss = a->below_miss; m.bbonus = a->below_bonus; m.amiss = a->above_miss; m.abonus = a->above_bonus;
-  m.bh = a->below_h; m.ccum = a->cat_cum;
-
+  fill_joint(m.j, a, Dc, cand_base, cand, l_out, g_out, scratch);
+  fill_mixed(m, a);
   const bool timed = g_prof.on != 0;
   hipStream_t s = (hipStream_t)stream;
-  const unsigned nb = (unsigned)blocks;
-  if (Dc == 0) launch_mixed_k<0>(m, nb, s, timed);
-  else if (Dc <= 2) launch_mixed_k<2>(m, nb, s, timed);
-  else if (Dc <= 4) launch_mixed_k<4>(m, nb, s, timed);
-  else if (Dc <= 8) launch_mixed_k<8>(m, nb, s, timed);
-  else launch_mixed_k<16>(m, nb, s, timed);
-  if (timed) {
-    hipExtLaunchKernelGGL(k_joint_merge, dim3((unsigned)a->n_ids), dim3(64), 0u, s, g_prof.ev[2], g_prof.ev[3], 0u,
-                          (const tpe_joint_record*)scratch, (int)n_chunks, records);
-    g_prof.valid = 1;
-  } else {
-    hipLaunchKernelGGL(k_joint_merge, dim3((unsigned)a->n_ids), dim3(64), 0, s, (const tpe_joint_record*)scratch,
-                       (int)n_chunks, records);
-  }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
-  return TPE_OK;
+  const Ev ev = chunk_marks(timed);
+  for_cp<16>(Dc, [&](auto cp) {
+    constexpr int CP = decltype(cp)::value;
+    for_kp<1, (CP < 16 ? 16 : 8)>(Dk, [&](auto kp) {       // (no <16, 16>: see for_cp)
+      launch(k_joint_mixed_chunk<CP, decltype(kp)::value>, dim3((unsigned)blocks), kThreads, 0u, s, ev.start, ev.stop, m);
+    });
+  });
+  return finish(k_joint_merge, (const tpe_joint_record*)scratch, m.j.n_chunks, records, a->n_ids, s, timed, 1);
 }
 
-int tpe_joint_quant_table_bytes(int32_t k_below, int32_t k_above, int32_t total_bins, uint64_t* bytes) {
-  if (!bytes || k_below < 1 || k_above < 1 || total_bins < 1)
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_table_bytes: bad arguments");
-  *bytes = ((uint64_t)k_below + (uint64_t)k_above) * (uint64_t)total_bins * sizeof(float);
-  return TPE_OK;
-}
-
-int tpe_joint_quant_profile(double* table_ms) {
-  if (!table_ms || !g_qprof.valid)
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_profile: no profiled tpe_joint_quant_run to read");
-  float ms = 0.f;
-  hipError_t e = hipEventSynchronize(g_qprof.ev[1]);
-  if (e == hipSuccess) e = hipEventElapsedTime(&ms, g_qprof.ev[0], g_qprof.ev[1]);
-  if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
-  *table_ms = (double)ms;
-  return TPE_OK;
-}
-
-// tpe_joint_quant_run with local candidate i as global candidate cand_base + i (tpe_joint_run_shard)
-static int joint_quant_run_at(const tpe_joint_quant_args* a, tpe_joint_record* records, float* cand, double* l_out,
-                              double* g_out, void* scratch, uint64_t scratch_bytes, void* stream, uint32_t cand_base) {
+int joint_quant_run_at(const tpe_joint_quant_args* a, tpe_joint_record* records, float* cand, double* l_out,
+                       double* g_out, void* scratch, uint64_t scratch_bytes, void* stream, uint32_t cand_base) {
+  constexpr const char* E = "tpe_joint_quant_run";
   tpe_internal_epoch_bump();
-  static_assert(offsetof(tpe_joint_quant_args, n_quant) == sizeof(tpe_joint_mixed_args), "the shared fields");
-  static_assert(offsetof(tpe_joint_quant_args, cat_cum) == offsetof(tpe_joint_mixed_args, cat_cum), "the shared fields");
-  if (!a) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: null args");
-  if (a->n_quant < 0 || a->n_quant > TPE_JOINT_MAX_QUANT)
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: n_quant outside [0, TPE_JOINT_MAX_QUANT]");
+  if (!a) return fail(E, "null args");
+  if (a->n_quant < 0 || a->n_quant > TPE_JOINT_MAX_QUANT) return fail(E, "n_quant outside [0, TPE_JOINT_MAX_QUANT]");
   if (a->n_quant == 0) {                    // no quantised label: the mixed stage, the same bytes
     tpe_joint_mixed_args m;
     memcpy(&m, a, sizeof m);
     return joint_mixed_run_at(&m, records, cand, l_out, g_out, scratch, scratch_bytes, stream, cand_base);
   }
   const int Dc = a->n_dims, Dk = a->n_cat, Dq = a->n_quant;
-  if (Dk < 0) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: n_cat < 0");
+  if (Dk < 0) return fail(E, "n_cat < 0");
   if (Dc < 0 || Dc > TPE_JOINT_MAX_DIMS || Dk > TPE_JOINT_MAX_DIMS || Dc + Dk + Dq > TPE_JOINT_MAX_DIMS)
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: n_dims + n_cat + n_quant outside [1, TPE_JOINT_MAX_DIMS]");
-  if (Dc > 8 || Dk > 4)
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: n_dims > 8 or n_cat > 4 beside a quantised label");
-  if (a->n_cand < 1) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: n_cand < 1");
-  if (a->n_ids < 1) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: n_ids < 1");
-  if (a->k_below < 1 || a->k_above < 1)
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: k_below < 1 or k_above < 1");
-  if (!a->below_c || !a->above_c || (Dc > 0 && (!a->below_mu || !a->below_a || !a->above_mu || !a->above_a)))
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: null density rows");
-  const bool inject = (a->flags & TPE_JOINT_INJECT) != 0;
-  if (inject && !a->inject)
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: TPE_JOINT_INJECT without candidates");
-  if (!inject && (!a->samp_cum || (Dc > 0 && !a->samp)))
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: null sampler rows");
-  if (!a->ids || !records) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: null ids / records");
-  int cat_total = 0;
+    return fail(E, "n_dims + n_cat + n_quant outside [1, TPE_JOINT_MAX_DIMS]");
+  if (Dc > 8 || Dk > 4) return fail(E, "n_dims > 8 or n_cat > 4 beside a quantised label");
+  if (int rc = check_solo_head(E, a, records, Dc)) return rc;
   if (Dk > 0) {
-    if (!a->below_cat || !a->above_cat || !a->below_miss || !a->below_bonus || !a->above_miss || !a->above_bonus ||
-        !a->below_h || !a->cat_cum)
-      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: null category tables");
-    for (int d = 0; d < Dk; ++d) {
-      if (a->cat_upper[d] < 2 || a->cat_upper[d] > TPE_JOINT_MAX_CATS)
-        return tpe_internal_fail(TPE_E_ARG,
-                                 "tpe_joint_quant_run: categories of a label outside [2, TPE_JOINT_MAX_CATS]");
-      cat_total += a->cat_upper[d];
-    }
-    for (int d = 0; d < Dk; ++d)
-      if (a->cat_off[d] < 0 || a->cat_off[d] > cat_total - a->cat_upper[d])
-        return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: cat_off outside the tables");
+    if (cat_tables_null(a)) return fail(E, "null category tables");
+    if (check_cats(E, "", a->cat_upper, a->cat_off, Dk) < 0) return TPE_E_ARG;
   }
-  int total = 0;
-  for (int d = 0; d < Dq; ++d) {
-    if (a->quant_v[d] < 2 || a->quant_v[d] > TPE_JOINT_MAX_LATTICE)
-      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: lattice values of a label outside [2, TPE_JOINT_MAX_LATTICE]");
-    total += a->quant_v[d];
-  }
-  if (total > TPE_JOINT_MAX_LATTICE_TOTAL)
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: more than TPE_JOINT_MAX_LATTICE_TOTAL lattice values");
-  for (int d = 0; d < Dq; ++d)
-    if (a->quant_edge_off[d] < 0 || (int64_t)a->quant_edge_off[d] + a->quant_v[d] + 1 > (int64_t)a->n_edges)
-      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: quant_edge_off outside the edge array");
+  const int64_t total = check_lattice(E, "", a->quant_v, a->quant_edge_off, Dq, a->n_edges);
+  if (total < 0) return TPE_E_ARG;
   if (!a->quant_edges || !a->below_qmu || !a->below_qsigma || !a->above_qmu || !a->above_qsigma || !a->quant_samp ||
       !a->quant_table)
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: null quantised rows or table");
-  const uint64_t tneed = ((uint64_t)a->k_below + (uint64_t)a->k_above) * (uint64_t)total * sizeof(float);
-  if (a->quant_table_bytes < tneed) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: table workspace too small");
-  const int64_t n_chunks = n_chunks_of(a->n_cand), blocks = n_chunks * a->n_ids;
-  if (blocks > INT32_MAX) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: too many candidates");
-  const uint64_t need = (uint64_t)blocks * sizeof(tpe_joint_record);
-  if (!scratch || scratch_bytes < need) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_quant_run: scratch too small");
+    return fail(E, "null quantised rows or table");
+  if (a->quant_table_bytes < quant_table_floats(a->k_below, a->k_above, total) * sizeof(float))
+    return fail(E, "table workspace too small");
+  const int64_t blocks = n_chunks_of(a->n_cand) * a->n_ids;
+  if (int rc = check_scratch(E, blocks, joint_scratch_need(a->n_ids, a->n_cand), scratch, scratch_bytes)) return rc;
 
   QuantK qk;
-  MixedK& m = qk.m;
-  JointK& k = m.j;
-  k.D = Dc; k.C = a->n_cand; k.n_chunks = (int)n_chunks; k.inject = inject ? 1 : 0;
-  k.kb = a->k_below; k.ka = a->k_above;
-  k.key0 = (uint32_t)a->seed; k.key1 = (uint32_t)(a->seed >> 32); k.stream_word = a->stream_word;
-  k.cand_base = cand_base;
-  k.bmu = a->below_mu; k.ba = a->below_a; k.bc = a->below_c;
-  k.amu = a->above_mu; k.aa = a->above_a; k.ac = a->above_c;
-  k.bbase = a->below_base; k.abase = a->above_base;
-  k.cum = a->samp_cum; k.samp = a->samp; k.ids = a->ids; k.inj = a->inject;
-  // f32 bounds: smallest float >= low, largest float < high (as tpe_joint_run)
-  auto f32_bounds = [](double L, double H, float& lo, float& hi) {
-    lo = -INFINITY; hi = INFINITY;
-    if (L > -INFINITY) { lo = (float)L; if ((double)lo < L) lo = nextafterf(lo, INFINITY); }
-    if (H < INFINITY) { hi = (float)H; while ((double)hi >= H) hi = nextafterf(hi, -INFINITY); }
-  };
-  for (int d = 0; d < TPE_JOINT_MAX_DIMS; ++d) {
-    k.lo[d] = -INFINITY; k.hi[d] = INFINITY;
-    if (d < Dc) f32_bounds(a->low[d], a->high[d], k.lo[d], k.hi[d]);
-    m.U[d] = d < Dk ? a->cat_upper[d] : 1;
-    m.off[d] = d < Dk ? a->cat_off[d] : 0;
-  }
-  k.cand = cand; k.l_out = l_out; k.g_out = g_out;
-  k.chunk_rec = (tpe_joint_record*)scratch;
-  m.Dk = Dk;
-  m.bcat = a->below_cat; m.acat = a->above_cat;
-  m.bmiss = a->below_miss; m.bbonus = a->below_bonus; m.amiss = a->above_miss; m.abonus = a->above_bonus;
-  m.bh = a->below_h; m.ccum = a->cat_cum;
-  qk.Dq = Dq; qk.total = total;
+  fill_joint(qk.m.j, a, Dc, cand_base, cand, l_out, g_out, scratch);
+  fill_mixed(qk.m, a);
+  qk.Dq = Dq; qk.total = (int)total;
   qk.edges = a->quant_edges; qk.qsamp = a->quant_samp;
-  qk.bT = a->quant_table; qk.aT = a->quant_table + (int64_t)total * a->k_below;
-
+  qk.bT = a->quant_table; qk.aT = a->quant_table + total * a->k_below;
   // a quantised dimension's bounds (its outer edges): low / high [Dc + d]
   QTabK tb, ta;
   int voff = 0;
@@ -2434,46 +1952,306 @@ static int joint_quant_run_at(const tpe_joint_quant_args* a, tpe_joint_record* r
       voff += a->quant_v[d];
     }
   }
-  qk.tile = quant_tile(total); qk.stride = qk.tile + 4;
-  const unsigned lds = (unsigned)((total + 1) * qk.stride * sizeof(float));
+  qk.tile = quant_tile((int)total); qk.stride = qk.tile + 4;
 
   const bool timed = g_prof.on != 0;
   hipStream_t s = (hipStream_t)stream;
-  if (timed && !g_qprof.ev[0])
-    for (int i = 0; i < 2; ++i) {
-      const hipError_t e = hipEventCreate(&g_qprof.ev[i]);
-      if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
-    }
+  if (timed)
+    if (int rc = ensure_events(g_qprof.ev, 2)) return rc;
   tb.K = a->k_below; tb.Dq = Dq; tb.mu = a->below_qmu; tb.sigma = a->below_qsigma; tb.edges = a->quant_edges;
   tb.T = a->quant_table;
   ta = tb;
-  ta.K = a->k_above; ta.mu = a->above_qmu; ta.sigma = a->above_qsigma; ta.T = a->quant_table + (int64_t)total * a->k_below;
+  ta.K = a->k_above; ta.mu = a->above_qmu; ta.sigma = a->above_qsigma; ta.T = a->quant_table + total * a->k_below;
   const dim3 gb((unsigned)((a->k_below + kThreads - 1) / kThreads), (unsigned)Dq);
   const dim3 ga((unsigned)((a->k_above + kThreads - 1) / kThreads), (unsigned)Dq);
-  if (timed) {
-    hipExtLaunchKernelGGL(k_joint_qtable, gb, dim3(kThreads), 0u, s, g_qprof.ev[0], nullptr, 0u, tb);
-    hipExtLaunchKernelGGL(k_joint_qtable, ga, dim3(kThreads), 0u, s, nullptr, g_qprof.ev[1], 0u, ta);
-    g_qprof.valid = 1;
-  } else {
-    hipLaunchKernelGGL(k_joint_qtable, gb, dim3(kThreads), 0, s, tb);
-    hipLaunchKernelGGL(k_joint_qtable, ga, dim3(kThreads), 0, s, ta);
-  }
+  launch(k_joint_qtable, gb, kThreads, 0u, s, timed ? g_qprof.ev[0] : nullptr, nullptr, tb);
+  launch(k_joint_qtable, ga, kThreads, 0u, s, nullptr, timed ? g_qprof.ev[1] : nullptr, ta);
+  if (timed) g_qprof.valid = 1;
 
-  const unsigned nb = (unsigned)blocks;
-  if (Dc == 0) launch_quant_k<0>(qk, nb, lds, s, timed);
-  else if (Dc <= 2) launch_quant_k<2>(qk, nb, lds, s, timed);
-  else if (Dc <= 4) launch_quant_k<4>(qk, nb, lds, s, timed);
-  else launch_quant_k<8>(qk, nb, lds, s, timed);
-  if (timed) {
-    hipExtLaunchKernelGGL(k_joint_merge, dim3((unsigned)a->n_ids), dim3(64), 0u, s, g_prof.ev[2], g_prof.ev[3], 0u,
-                          (const tpe_joint_record*)scratch, (int)n_chunks, records);
-    g_prof.valid = 1;
+  const Ev ev = chunk_marks(timed);
+  for_cp<8>(Dc, [&](auto cp) {
+    for_kp<0, 4>(Dk, [&](auto kp) {
+      for_qp(Dq, [&](auto qp) {
+        launch(k_joint_quant_chunk<decltype(cp)::value, decltype(kp)::value, decltype(qp)::value>,
+               dim3((unsigned)blocks), kThreads, quant_lds((int)total), s, ev.start, ev.stop, qk);
+      });
+    });
+  });
+  return finish(k_joint_merge, (const tpe_joint_record*)scratch, qk.m.j.n_chunks, records, a->n_ids, s, timed, 1);
+}
+
+// ---- the segmented stages: one skeleton (joint_seg_run_at); a stage supplies its
+// per-segment check, its class function and its class launcher as overloads on
+// its descriptor, tpe_joint_seg or tpe_joint_mseg
+static_assert(offsetof(tpe_joint_mseg, hi) == offsetof(tpe_joint_seg, hi) &&
+                  offsetof(tpe_joint_mseg, n_cat) == sizeof(tpe_joint_seg),
+              "tpe_joint_mseg starts with tpe_joint_seg");
+static_assert(offsetof(tpe_joint_mseg_args, cand_off) == offsetof(tpe_joint_seg_args, cand_off), "the shared fields");
+
+// rows [off, off + n) inside a pool of len elements
+bool inside(int64_t off, int64_t n, int64_t len) { return off >= 0 && n <= len && off <= len - n; }
+
+// what the checks leave for the launches: the problems per kernel class and, for
+// the mixed stage, the table launch's grid and the classes' dynamic LDS
+struct SegPlan {
+  int64_t per_class[kMClasses] = {};
+  unsigned lds[kMClasses] = {};
+  int max_kblocks = 0;
+  bool any_quant = false;
+};
+constexpr int n_classes_of(const tpe_joint_seg*) { return 8; }
+constexpr int n_classes_of(const tpe_joint_mseg*) { return kMClasses; }
+
+int check_segment(const char* entry, const tpe_joint_seg_args* a, const tpe_joint_seg& g, bool inject, SegPlan&) {
+  if (g.n_dims < 1 || g.n_dims > TPE_JOINT_MAX_DIMS) return fail(entry, "n_dims outside [1, TPE_JOINT_MAX_DIMS]", kSegs);
+  if (g.k_below < 1 || g.k_above < 1) return fail(entry, "k_below < 1 or k_above < 1", kSegs);
+  const int64_t D = g.n_dims, kb = g.k_below, ka = g.k_above, L = a->pool_f32_len;
+  bool ok = inside(g.below_mu, kb * D, L) && inside(g.below_a, kb * D, L) && inside(g.below_c, kb, L) &&
+            inside(g.above_mu, ka * D, L) && inside(g.above_a, ka * D, L) && inside(g.above_c, ka, L);
+  if (!inject) ok = ok && inside(g.samp, kb * D * 5, L) && inside(g.samp_cum, kb, a->pool_f64_len);
+  if (inject && g.inject >= 0) ok = ok && inside(g.inject, (int64_t)a->n_cand * D, L);
+  if (!ok) return fail(entry, "rows leave its pool", kSegs);
+  return TPE_OK;
+}
+
+int check_segment(const char* entry, const tpe_joint_mseg_args* a, const tpe_joint_mseg& g, bool inject, SegPlan& plan) {
+  const int64_t L = a->pool_f32_len, L64 = a->pool_f64_len, LT = (int64_t)(a->quant_table_bytes / sizeof(float));
+  if (g.n_cat < 0 || g.n_cat > TPE_JOINT_MAX_DIMS) return fail(entry, "n_cat outside [0, TPE_JOINT_MAX_DIMS]", kSegs);
+  if (g.n_quant < 0 || g.n_quant > TPE_JOINT_MAX_QUANT)
+    return fail(entry, "n_quant outside [0, TPE_JOINT_MAX_QUANT]", kSegs);
+  const int64_t Dc = g.n_dims, Dk = g.n_cat, Dq = g.n_quant, D = Dc + Dk + Dq, kb = g.k_below, ka = g.k_above;
+  if (Dk + Dq == 0) {
+    if (Dc < 1 || Dc > TPE_JOINT_MAX_DIMS) return fail(entry, "n_dims outside [1, TPE_JOINT_MAX_DIMS]", kSegs);
   } else {
-    hipLaunchKernelGGL(k_joint_merge, dim3((unsigned)a->n_ids), dim3(64), 0, s, (const tpe_joint_record*)scratch,
-                       (int)n_chunks, records);
+    if (Dc < 0) return fail(entry, "n_dims < 0", kSegs);
+    if (Dc > TPE_JOINT_MSEG_MAX_CONT || Dk > TPE_JOINT_MSEG_MAX_CAT)
+      return fail(entry, "n_dims > 8 or n_cat > 4 in a segment with a discrete or quantised label");
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
+  if (kb < 1 || ka < 1) return fail(entry, "k_below < 1 or k_above < 1", kSegs);
+  const int64_t cat_total = check_cats(entry, kInSeg, g.cat_upper, g.cat_off, (int)Dk);
+  if (cat_total < 0) return TPE_E_ARG;
+  const int64_t total = check_lattice(entry, kInSeg, g.quant_v, g.quant_edge_off, (int)Dq, g.n_edges);
+  if (total < 0) return TPE_E_ARG;
+  if (Dq > 0 && !a->pool_f64) return fail(entry, "null pool_f64 with a quantised segment");
+  if (Dq > 0 && !a->quant_table) return fail(entry, "null table workspace with a quantised segment");
+  bool ok = inside(g.below_c, kb, L) && inside(g.above_c, ka, L);
+  if (Dc > 0)
+    ok = ok && inside(g.below_mu, kb * Dc, L) && inside(g.below_a, kb * Dc, L) && inside(g.above_mu, ka * Dc, L) &&
+         inside(g.above_a, ka * Dc, L);
+  if (!inject) ok = ok && inside(g.samp_cum, kb, L64) && (Dc == 0 || inside(g.samp, kb * Dc * 5, L));
+  if (inject && g.inject >= 0) ok = ok && inside(g.inject, (int64_t)a->n_cand * D, L);
+  if (Dk > 0) {
+    ok = ok && inside(g.below_cat, kb * Dk, L) && inside(g.above_cat, ka * Dk, L) &&
+         inside(g.below_miss, cat_total, L) && inside(g.below_bonus, cat_total, L) &&
+         inside(g.above_miss, cat_total, L) && inside(g.above_bonus, cat_total, L);
+    if (!inject) ok = ok && inside(g.below_h, Dk, L64) && inside(g.cat_cum, cat_total, L64);
+  }
+  if (Dq > 0) {
+    ok = ok && inside(g.quant_edges, g.n_edges, L64) && inside(g.below_qmu, kb * Dq, L64) &&
+         inside(g.below_qsigma, kb * Dq, L64) && inside(g.above_qmu, ka * Dq, L64) &&
+         inside(g.above_qsigma, ka * Dq, L64);
+    if (!inject) ok = ok && inside(g.quant_samp, kb * Dq * 5, L);
+  }
+  if (!ok) return fail(entry, "rows leave its pool", kSegs);
+  if (Dq > 0) {
+    if (!inside(g.table, (int64_t)quant_table_floats(kb, ka, total), LT))
+      return fail(entry, "table leaves the table workspace", kSegs);
+    plan.any_quant = true;
+    const int kblocks = (int)(((kb > ka ? kb : ka) + kThreads - 1) / kThreads);
+    if (kblocks > plan.max_kblocks) plan.max_kblocks = kblocks;
+  }
+  return TPE_OK;
+}
+
+// the kernel class of a segment that has a problem
+int segment_class(const tpe_joint_seg& g, SegPlan&) { return dp_class(g.n_dims); }
+int segment_class(const tpe_joint_mseg& g, SegPlan& plan) {
+  const int c = mseg_class(g.n_dims, g.n_cat, g.n_quant);
+  if (g.n_quant > 0) {                     // the segment's own tile (the solo run's rule); the launch takes the largest
+    int total = 0;
+    for (int d = 0; d < g.n_quant; ++d) total += g.quant_v[d];
+    if (quant_lds(total) > plan.lds[c]) plan.lds[c] = quant_lds(total);
+  }
+  return c;
+}
+
+// one chunk launch of kernel class c over `blocks` workgroups
+void launch_class(const tpe_joint_seg*, int c, const MSegK& k, unsigned blocks, unsigned, hipStream_t s, Ev ev) {
+  for_dp(c, [&](auto dp) {
+    launch(k_joint_seg_chunk<decltype(dp)::value, false>, dim3(blocks), kThreads, 0u, s, ev.start, ev.stop, k.s);
+  });
+}
+void launch_class(const tpe_joint_mseg*, int c, const MSegK& k, unsigned blocks, unsigned lds, hipStream_t s, Ev ev) {
+  if (c < 8) {
+    for_dp(c, [&](auto dp) {
+      launch(k_joint_seg_chunk<decltype(dp)::value, true>, dim3(blocks), kThreads, 0u, s, ev.start, ev.stop, k.s);
+    });
+  } else if (c < 20) {                      // (mseg_class's numbering)
+    for_cp<8>(kCpOf[(c - 8) / 3], [&](auto cp) {
+      for_kp<1, 4>(kKpOf[(c - 8) % 3 + 1], [&](auto kp) {
+        launch(k_joint_mseg_mixed_chunk<decltype(cp)::value, decltype(kp)::value>, dim3(blocks), kThreads, 0u, s,
+               ev.start, ev.stop, k);
+      });
+    });
+  } else {
+    for_cp<8>(kCpOf[(c - 20) / 12], [&](auto cp) {
+      for_kp<0, 4>(kKpOf[(c - 20) / 3 % 4], [&](auto kp) {
+        for_qp(kQpOf[(c - 20) % 3], [&](auto qp) {
+          launch(k_joint_mseg_quant_chunk<decltype(cp)::value, decltype(kp)::value, decltype(qp)::value>, dim3(blocks),
+                 kThreads, lds, s, ev.start, ev.stop, k);
+        });
+      });
+    });
+  }
+}
+
+template <typename A>
+int joint_seg_run_at(const char* E, const A* a, tpe_joint_record* records, float* cand, double* l_out, double* g_out,
+                     void* scratch, uint64_t scratch_bytes, void* stream, uint32_t cand_base) {
+  using Seg = std::remove_cv_t<std::remove_pointer_t<decltype(A::host_segs)>>;
+  constexpr bool MIXED = std::is_same<Seg, tpe_joint_mseg>::value;
+  constexpr int n_classes = n_classes_of((const Seg*)nullptr);
+  tpe_internal_epoch_bump();
+  if (!a) return fail(E, "null args");
+  if (a->n_segs < 1) return fail(E, "n_segs < 1");
+  if (MIXED && a->n_segs > 32767) return fail(E, "more than 32767 segments");
+  if (a->n_probs < 1) return fail(E, "n_probs < 1");
+  if (a->n_cand < 1) return fail(E, "n_cand < 1");
+  if (!a->segs || !a->host_segs) return fail(E, "null segs / host_segs");
+  const bool inject = (a->flags & TPE_JOINT_INJECT) != 0;
+  if (!a->pool_f32 || (!inject && !a->pool_f64)) return fail(E, "null pool");
+  if (!a->prob_seg || !a->host_prob_seg || !a->prob_id) return fail(E, "null prob_seg / host_prob_seg / prob_id");
+  if (!records) return fail(E, "null records");
+  if (cand && !a->cand_off) return fail(E, "cand without cand_off");
+  SegPlan plan;
+  for (int s = 0; s < a->n_segs; ++s)
+    if (int rc = check_segment(E, a, a->host_segs[s], inject, plan)) return rc;
+  for (int p = 0; p < a->n_probs; ++p) {
+    const int s = a->host_prob_seg[p];
+    if (s < 0 || s >= a->n_segs) return fail(E, "prob_seg outside [0, n_segs)");
+    if (inject && a->host_segs[s].inject < 0) return fail(E, "TPE_JOINT_INJECT without candidates");
+    ++plan.per_class[segment_class(a->host_segs[s], plan)];
+  }
+  const int64_t n_chunks = n_chunks_of(a->n_cand);
+  if ((int64_t)a->n_segs * n_classes > INT32_MAX) return fail(E, "too many candidates");
+  if (int rc = check_scratch(E, n_chunks * a->n_probs, seg_scratch_need(a->n_probs, a->n_cand), scratch, scratch_bytes))
+    return rc;
+
+  MSegK mk;                                 // (the continuous stage's kernels take mk.s alone)
+  SegK& k = mk.s;
+  k.C = a->n_cand; k.n_chunks = (int)n_chunks; k.inject = inject ? 1 : 0; k.first = 0;
+  k.n_probs = a->n_probs; k.n_segs = a->n_segs;
+  k.key0 = (uint32_t)a->seed; k.key1 = (uint32_t)(a->seed >> 32); k.cand_base = cand_base;
+  k.segs = reinterpret_cast<const tpe_joint_seg*>(a->segs); k.pool = a->pool_f32; k.pool64 = a->pool_f64;
+  k.prob_seg = a->prob_seg; k.prob_id = a->prob_id; k.cand_off = a->cand_off;
+  k.order = (int32_t*)scratch;
+  k.cand = cand; k.l_out = l_out; k.g_out = g_out;
+  k.chunk_rec = (tpe_joint_record*)((char*)scratch + seg_order_bytes(a->n_probs));
+  mk.table = nullptr;
+
+  const bool timed = g_prof.on != 0;
+  hipStream_t s = (hipStream_t)stream;
+  if (timed)
+    if (int rc = ensure_events(g_sprof.ev, 2 * kSegLaunches)) return rc;
+  int n_timed = 0;
+  Ev ev = seg_marks(timed, n_timed);
+  launch(k_joint_seg_order<MIXED>, dim3((unsigned)((a->n_probs + kThreads - 1) / kThreads)), kThreads, 0u, s, ev.start,
+         ev.stop, k);
+  if constexpr (MIXED) {
+    mk.table = a->quant_table;
+    if (plan.any_quant) {
+      ev = seg_marks(timed, n_timed);
+      launch(k_joint_mseg_qtable, dim3((unsigned)plan.max_kblocks, (unsigned)TPE_JOINT_MAX_QUANT, (unsigned)(2 * a->n_segs)),
+             kThreads, 0u, s, ev.start, ev.stop, mk);
+    }
+  }
+  int64_t first = 0;
+  for (int c = 0; c < n_classes; ++c) {
+    if (!plan.per_class[c]) continue;
+    k.first = (int)first;
+    launch_class((const Seg*)nullptr, c, mk, (unsigned)(plan.per_class[c] * n_chunks), plan.lds[c], s,
+                 seg_marks(timed, n_timed));
+    first += plan.per_class[c];
+  }
+  return finish(k_joint_merge, (const tpe_joint_record*)k.chunk_rec, (int)n_chunks, records, a->n_probs, s, timed, 2,
+                n_timed);
+}
+
+}  // namespace
+
+extern "C" {
+
+int tpe_joint_profile(int32_t enable, double* last_ms) {
+  if (last_ms) {
+    if (!g_prof.valid) return fail("tpe_joint_profile", "no profiled tpe_joint_run to read");
+    for (int i = g_prof.valid == 2 ? 1 : 0; i < 2; ++i)
+      if (int rc = elapsed_ms(g_prof.ev[2 * i], g_prof.ev[2 * i + 1], &last_ms[i])) return rc;
+    if (g_prof.valid == 2) {               // a segmented run: its launches before the merge, summed
+      last_ms[0] = 0.0;
+      for (int i = 0; i < g_sprof.n; ++i) {
+        double ms = 0.0;
+        if (int rc = elapsed_ms(g_sprof.ev[2 * i], g_sprof.ev[2 * i + 1], &ms)) return rc;
+        last_ms[0] += ms;
+      }
+    }
+  }
+  if (enable)
+    if (int rc = ensure_events(g_prof.ev, 4)) return rc;
+  g_prof.on = enable ? 1 : 0;
+  g_prof.valid = 0;
+  return TPE_OK;
+}
+
+int tpe_joint_quant_profile(double* table_ms) {
+  if (!table_ms || !g_qprof.valid) return fail("tpe_joint_quant_profile", "no profiled tpe_joint_quant_run to read");
+  return elapsed_ms(g_qprof.ev[0], g_qprof.ev[1], table_ms);
+}
+
+int tpe_joint_wide_profile(double* sample_ms) {
+  if (!sample_ms || !g_wprof.valid)
+    return fail("tpe_joint_wide_profile", "no profiled sampling tpe_joint_wide_run to read");
+  return elapsed_ms(g_wprof.ev[0], g_wprof.ev[1], sample_ms);
+}
+
+int tpe_joint_scratch_bytes(int32_t n_ids, int32_t n_cand, uint64_t* bytes) {
+  const bool ok = n_ids >= 1 && n_cand >= 1;
+  return size_out("tpe_joint_scratch_bytes", ok, ok ? joint_scratch_need(n_ids, n_cand) : 0, bytes);
+}
+
+int tpe_joint_seg_scratch_bytes(int32_t n_probs, int32_t n_cand, uint64_t* bytes) {
+  const bool ok = n_probs >= 1 && n_cand >= 1;
+  return size_out("tpe_joint_seg_scratch_bytes", ok, ok ? seg_scratch_need(n_probs, n_cand) : 0, bytes);
+}
+
+int tpe_joint_mseg_scratch_bytes(int32_t n_probs, int32_t n_cand, uint64_t* bytes) {
+  const bool ok = n_probs >= 1 && n_cand >= 1;
+  return size_out("tpe_joint_mseg_scratch_bytes", ok, ok ? seg_scratch_need(n_probs, n_cand) : 0, bytes);
+}
+
+int tpe_joint_wide_scratch_bytes(int32_t n_ids, int32_t n_cand, int32_t n_dims, uint64_t* bytes) {
+  const bool ok = n_ids >= 1 && n_cand >= 1 && n_dims >= 1 && n_dims <= TPE_JOINT_WIDE_MAX_DIMS;
+  return size_out("tpe_joint_wide_scratch_bytes", ok, ok ? wide_scratch_need(n_ids, n_cand, n_dims) : 0, bytes);
+}
+
+int tpe_joint_quant_table_bytes(int32_t k_below, int32_t k_above, int32_t total_bins, uint64_t* bytes) {
+  const bool ok = k_below >= 1 && k_above >= 1 && total_bins >= 1;
+  return size_out("tpe_joint_quant_table_bytes", ok, quant_table_floats(k_below, k_above, total_bins) * sizeof(float),
+                  bytes);
+}
+
+int tpe_joint_mseg_table_bytes(const tpe_joint_mseg* host_segs, int32_t n_segs, uint64_t* bytes) {
+  constexpr const char* E = "tpe_joint_mseg_table_bytes";
+  if (!bytes || !host_segs || n_segs < 1) return fail(E, "bad arguments");
+  uint64_t n = 0;
+  for (int s = 0; s < n_segs; ++s) {
+    const tpe_joint_mseg& g = host_segs[s];
+    if (g.n_quant < 0 || g.n_quant > TPE_JOINT_MAX_QUANT || g.k_below < 1 || g.k_above < 1)
+      return fail(E, "n_quant, k_below or k_above out of range", kSegs);
+    const int64_t total = check_lattice(E, "", g.quant_v, nullptr, g.n_quant, 0);
+    if (total < 0) return TPE_E_ARG;
+    n += quant_table_floats(g.k_below, g.k_above, total);
+  }
+  *bytes = n * sizeof(float);
   return TPE_OK;
 }
 
@@ -2484,12 +2262,12 @@ int tpe_joint_run(const tpe_joint_args* a, tpe_joint_record* records, float* can
 
 int tpe_joint_seg_run(const tpe_joint_seg_args* a, tpe_joint_record* records, float* cand, double* l_out,
                       double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
-  return joint_seg_run_at(a, records, cand, l_out, g_out, scratch, scratch_bytes, stream, 0u);
+  return joint_seg_run_at("tpe_joint_seg_run", a, records, cand, l_out, g_out, scratch, scratch_bytes, stream, 0u);
 }
 
 int tpe_joint_mseg_run(const tpe_joint_mseg_args* a, tpe_joint_record* records, float* cand, double* l_out,
                        double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
-  return joint_mseg_run_at(a, records, cand, l_out, g_out, scratch, scratch_bytes, stream, 0u);
+  return joint_seg_run_at("tpe_joint_mseg_run", a, records, cand, l_out, g_out, scratch, scratch_bytes, stream, 0u);
 }
 
 int tpe_joint_wide_run(const tpe_joint_wide_args* a, tpe_joint_wide_record* records, float* cand, double* l_out,
@@ -2509,51 +2287,33 @@ int tpe_joint_quant_run(const tpe_joint_quant_args* a, tpe_joint_record* records
 
 int tpe_joint_run_shard(int32_t stage, const void* args, const tpe_joint_shard* shard, void* records, float* cand,
                         double* l_out, double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
+  constexpr const char* E = "tpe_joint_run_shard";
   tpe_internal_epoch_bump();
-  if (!args) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run_shard: null args");
-  if (!shard) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run_shard: null shard");
-  // every stage's args begin with int32 fields that hold n_cand and flags; read them by the stage's own type
-  int64_t n_cand = 0;
-  uint32_t flags = 0;
-#define TPE_SHARD_HEAD(T) { n_cand = ((const T*)args)->n_cand; flags = (uint32_t)((const T*)args)->flags; } break
+  if (!args) return fail(E, "null args");
+  if (!shard) return fail(E, "null shard");
+  // every stage's args hold n_cand and flags, read here by the stage's own type; then the stage itself runs
+  auto go = [&](auto* a, auto* rec, auto run_at) -> int {
+    const int64_t n_cand = a->n_cand;
+    if (shard->cand_base < 0) return fail(E, "cand_base < 0");
+    // the Philox counter word and the kernels' index arithmetic are 32-bit
+    if (shard->n_cand_global >= ((int64_t)1 << 31)) return fail(E, "n_cand_global >= 2^31");
+    if (n_cand > shard->n_cand_global || shard->cand_base > shard->n_cand_global - n_cand)
+      return fail(E, "cand_base + n_cand > n_cand_global");
+    if (((uint32_t)a->flags & TPE_JOINT_INJECT) && shard->cand_base != 0)
+      return fail(E, "TPE_JOINT_INJECT with cand_base != 0");
+    return run_at(a, rec, cand, l_out, g_out, scratch, scratch_bytes, stream, (uint32_t)shard->cand_base);
+  };
+  auto seg_at = [](auto* a, auto... rest) { return joint_seg_run_at("tpe_joint_seg_run", a, rest...); };
+  auto mseg_at = [](auto* a, auto... rest) { return joint_seg_run_at("tpe_joint_mseg_run", a, rest...); };
   switch (stage) {
-    case TPE_JOINT_STAGE_RUN: TPE_SHARD_HEAD(tpe_joint_args);
-    case TPE_JOINT_STAGE_WIDE: TPE_SHARD_HEAD(tpe_joint_wide_args);
-    case TPE_JOINT_STAGE_MIXED: TPE_SHARD_HEAD(tpe_joint_mixed_args);
-    case TPE_JOINT_STAGE_QUANT: TPE_SHARD_HEAD(tpe_joint_quant_args);
-    case TPE_JOINT_STAGE_SEG: TPE_SHARD_HEAD(tpe_joint_seg_args);
-    case TPE_JOINT_STAGE_MSEG: TPE_SHARD_HEAD(tpe_joint_mseg_args);
-    default: return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run_shard: stage outside [0, 5]");
-  }
-#undef TPE_SHARD_HEAD
-  if (shard->cand_base < 0) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run_shard: cand_base < 0");
-  // the Philox counter word and the kernels' index arithmetic are 32-bit
-  if (shard->n_cand_global >= ((int64_t)1 << 31))
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run_shard: n_cand_global >= 2^31");
-  if (n_cand > shard->n_cand_global || shard->cand_base > shard->n_cand_global - n_cand)
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run_shard: cand_base + n_cand > n_cand_global");
-  if ((flags & TPE_JOINT_INJECT) && shard->cand_base != 0)
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_run_shard: TPE_JOINT_INJECT with cand_base != 0");
-  const uint32_t base = (uint32_t)shard->cand_base;
-  switch (stage) {
-    case TPE_JOINT_STAGE_RUN:
-      return joint_run_at((const tpe_joint_args*)args, (tpe_joint_record*)records, cand, l_out, g_out, scratch,
-                          scratch_bytes, stream, base);
+    case TPE_JOINT_STAGE_RUN: return go((const tpe_joint_args*)args, (tpe_joint_record*)records, joint_run_at);
     case TPE_JOINT_STAGE_WIDE:
-      return joint_wide_run_at((const tpe_joint_wide_args*)args, (tpe_joint_wide_record*)records, cand, l_out, g_out,
-                               scratch, scratch_bytes, stream, base);
-    case TPE_JOINT_STAGE_MIXED:
-      return joint_mixed_run_at((const tpe_joint_mixed_args*)args, (tpe_joint_record*)records, cand, l_out, g_out,
-                                scratch, scratch_bytes, stream, base);
-    case TPE_JOINT_STAGE_QUANT:
-      return joint_quant_run_at((const tpe_joint_quant_args*)args, (tpe_joint_record*)records, cand, l_out, g_out,
-                                scratch, scratch_bytes, stream, base);
-    case TPE_JOINT_STAGE_SEG:
-      return joint_seg_run_at((const tpe_joint_seg_args*)args, (tpe_joint_record*)records, cand, l_out, g_out, scratch,
-                              scratch_bytes, stream, base);
-    default:
-      return joint_mseg_run_at((const tpe_joint_mseg_args*)args, (tpe_joint_record*)records, cand, l_out, g_out,
-                               scratch, scratch_bytes, stream, base);
+      return go((const tpe_joint_wide_args*)args, (tpe_joint_wide_record*)records, joint_wide_run_at);
+    case TPE_JOINT_STAGE_MIXED: return go((const tpe_joint_mixed_args*)args, (tpe_joint_record*)records, joint_mixed_run_at);
+    case TPE_JOINT_STAGE_QUANT: return go((const tpe_joint_quant_args*)args, (tpe_joint_record*)records, joint_quant_run_at);
+    case TPE_JOINT_STAGE_SEG: return go((const tpe_joint_seg_args*)args, (tpe_joint_record*)records, seg_at);
+    case TPE_JOINT_STAGE_MSEG: return go((const tpe_joint_mseg_args*)args, (tpe_joint_record*)records, mseg_at);
+    default: return fail(E, "stage outside [0, 5]");
   }
 }
 

@@ -1,5 +1,5 @@
 """Host time of the joint stages' packing, without a device.
-Usage: python tools/joint_pack_time.py [--calls 200] [--label TEXT] [--out FILE]
+Usage: python tools/joint_pack_time.py [--calls 200] [--label TEXT] [--out FILE] [--device]
 
 The engine of tests/joint_pack_capture.py (CPU tensors, a native library that
 answers 0) runs three calls over and over; what is timed is everything
@@ -9,6 +9,9 @@ uploads (here: copies), the args struct.
   quantised   run_joint_quant, 2 continuous + 1 discrete + 2 quantised (V = 50, 7)
   segmented   run_joint_segments over workload (c) of
               tools/joint_branch_mixed_time.py at its --small sizes
+--device: the same three calls on cuda:0 through the real library (TPE_HIP_LIB
+picks an A/B build), so that the native driver's checks, fills and launches are
+in the time too; a call ends when its records are on the host.
 One JSON line (per workload the median, the quartiles, min and max in ms) goes
 to stdout and, with --out, is appended there."""
 import argparse
@@ -28,6 +31,7 @@ def main():
     ap.add_argument('--calls', type=int, default=200)
     ap.add_argument('--label', default='')
     ap.add_argument('--out', default=None)
+    ap.add_argument('--device', action='store_true')
     args = ap.parse_args()
     from tests import joint_pack_capture as K
     from tools.joint_branch_mixed_time import SEED, make_group
@@ -38,18 +42,23 @@ def main():
     work = dict(continuous=lambda e: e.run_joint(*cont, K.IDS, K.C, K.SEED),
                 quantised=lambda e: e.run_joint_quant(*quant, K.IDS, K.C, K.SEED),
                 segmented=lambda e: e.run_joint_segments(models, words, prob_seg, prob_id, 4096, SEED))
-    line = dict(tool='joint_pack_time', label=args.label, calls=args.calls, ms={})
+    line = dict(tool='joint_pack_time', label=args.label, calls=args.calls, device=args.device, ms={})
+    if args.device:
+        import torch
+        from hyperopt_amd.engine import get_engine
+        dev_eng = get_engine(torch.device('cuda', 0))
     for name, fn in work.items():
-        eng, _ = K.stub_engine()
+        eng = dev_eng if args.device else K.stub_engine()[0]
+        clear = (lambda: None) if args.device else eng.lib.calls.clear
         for _ in range(10):
             fn(eng)
-        eng.lib.calls.clear()
+        clear()
         ms = []
         for _ in range(args.calls):
             t0 = time.perf_counter()
             fn(eng)
             ms.append((time.perf_counter() - t0) * 1e3)
-            eng.lib.calls.clear()
+            clear()
         q1, med, q3 = np.percentile(ms, [25, 50, 75])
         line['ms'][name] = dict(median=float(med), q1=float(q1), q3=float(q3), min=float(min(ms)), max=float(max(ms)))
     text = json.dumps(line)
