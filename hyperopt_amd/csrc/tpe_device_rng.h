@@ -40,9 +40,11 @@ __device__ __forceinline__ double u01w(uint32_t a) { return ((double)a + 0.5) * 
 // Phi^-1(pr) in f32 = -sqrt2 erfinv(1 - 2 pr), erfinv by Giles' single-precision
 // approximation ("Approximating the erfinv function", GPU Computing Gems 2010)
 // with its log argument (1 - x)(1 + x) = 4 pr (1 - pr) formed from pr itself (no
-// cancellation in the tails).  Relative error <= 3e-7 over the f32 uniforms
-// (checked against scipy.special.ndtri); one v_log_f32, the tail branch adds a
-// sqrt.  Every f32 draw inverts through this one function.
+// cancellation in the tails), and a third branch below the f32 uniforms (pr <
+// 2.8e-8, see there).  Relative error <= 3e-7 for every normal f32 pr in
+// [1e-38, 1 - 2^-24] (checked against scipy.special.ndtri; tests/draw_ref.py
+// brackets every device draw by this bound); one v_log_f32, the tail branches
+// add a sqrt.  Every f32 draw inverts through this one function.
 __device__ __forceinline__ float ndtri_f32(float pr) {
   const float x = 1.f - 2.f * pr;
   float w = -__logf(4.f * pr * (1.f - pr));
@@ -54,6 +56,24 @@ __device__ __forceinline__ float ndtri_f32(float pr) {
     q = __builtin_fmaf(q, w, -4.39150654e-06f); q = __builtin_fmaf(q, w, 0.00021858087f);
     q = __builtin_fmaf(q, w, -0.00125372503f); q = __builtin_fmaf(q, w, -0.00417768164f);
     q = __builtin_fmaf(q, w, 0.246640727f); q = __builtin_fmaf(q, w, 1.50140941f);
+  } else if (w >= 16.f) {
+    // pr < 2.8e-8: below every f32 uniform, past the range Giles' tail
+    // polynomial was fitted on (it is 4e-4 off at pr = 1e-10 and 3e-2 at
+    // 1e-14), but reached by pr = fa + u (fb - fa) of a truncated component
+    // whose visible mass fb - fa is small.  q(s), s = sqrt(w), by a degree-9
+    // least-squares fit on s in [3.95, 9.28] (pr from 4e-8 down to 1e-38)
+    // against scipy.special.ndtri: 1.7e-7 in f32 arithmetic.  Below 1.2e-38 (pr
+    // subnormal: fa rounded to 0 in f32 and fb - fa tiny) pr itself has lost
+    // bits and the error grows to about 2e-6 of z; pr = 0 (a visible mass
+    // under 1e-38: not drawn in practice) gives an infinite z of no meaning,
+    // which only the callers' clip to the bounds catches.
+    w = __builtin_sqrtf(w) - 6.5f;
+    q = -4.196834879621747e-09f;
+    q = __builtin_fmaf(q, w, 2.784403108080369e-08f); q = __builtin_fmaf(q, w, -9.715248694419643e-08f);
+    q = __builtin_fmaf(q, w, 5.151761115484987e-07f); q = __builtin_fmaf(q, w, -2.931430344688124e-06f);
+    q = __builtin_fmaf(q, w, 1.1722268027369864e-05f); q = __builtin_fmaf(q, w, -1.0785219274112023e-05f);
+    q = __builtin_fmaf(q, w, -0.0005107762990519404f); q = __builtin_fmaf(q, w, 1.009109377861023f);
+    q = __builtin_fmaf(q, w, 6.364593505859375f);
   } else {
     w = __builtin_sqrtf(w) - 3.f;
     q = -0.000200214257f;

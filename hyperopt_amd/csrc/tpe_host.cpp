@@ -712,8 +712,9 @@ void fill_label(const PackLevel& lv, int32_t li) {
     double acc = 0;
     std::vector<double> cum((size_t)k);
     for (int64_t i = 0; i < k; ++i) { acc += L.below_w[i]; cum[i] = acc; }
+    const double tot = np_sum(L.below_w, k);           // (np.cumsum(p) / np.sum(p): the sum pairwise)
     for (int64_t i = 0; i < k; ++i) {
-      const double row[8] = {i == k - 1 ? 1.0 : cum[i] / acc, 0, 0, 0, 0, 0, 0, 0};
+      const double row[8] = {i == k - 1 ? 1.0 : cum[i] / tot, 0, 0, 0, 0, 0, 0, 0};
       memcpy(srow + 8 * i, row, sizeof(row));
     }
     p.samp_len = (int32_t)k;
@@ -749,7 +750,7 @@ void fill_label(const PackLevel& lv, int32_t li) {
       any = any || sel[i] > 0;
     }
     if (!any) for (int64_t i = 0; i < k; ++i) sel[i] = L.below_w[i];
-    for (int64_t i = 0; i < k; ++i) tot += sel[i];
+    tot = np_sum(sel.data(), k);                       // (np.cumsum(sel) / np.sum(sel): the sum pairwise)
     double acc = 0;
     for (int64_t i = 0; i < k; ++i) {
       acc += sel[i];

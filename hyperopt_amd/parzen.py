@@ -15,7 +15,7 @@ References (gsmafra/hyperopt, /root/reference):
 import math
 
 import numpy as np
-from scipy.special import erf, erfc
+from scipy.special import erf
 
 from . import _native as N
 
@@ -363,6 +363,17 @@ def quant_table(w, mu, sigma, post):
     return mu, np.maximum(np.sqrt(2) * sigma, EPS), w, base
 
 
+_erfc_each = np.frompyfunc(math.erfc, 1, 1)
+
+
+def _erfc_libm(x):
+    """erfc by the C library's function (math.erfc), elementwise: the one the
+    native packer calls, so both packers' sampler rows are the same bytes.
+    scipy.special.erfc differs from it in the last bits, by up to 371 ulps of fa
+    in the far tail (1e-300 .. 1e-7)."""
+    return _erfc_each(np.asarray(x, dtype=np.float64)).astype(np.float64)
+
+
 def sampler_table(post):
     """Below-mixture sampler rows {cum, mu, sigma, fa, fb, flip}.
 
@@ -371,7 +382,8 @@ def sampler_table(post):
     draws are exactly: component k with probability ∝ w_k * mass_k, then a
     normal truncated to [low, high) — which the device samples by inversion,
     p = fa + u (fb - fa), z = Phi^-1(p).  When the standardised interval lies
-    right of 0 it is mirrored (flip) so fa, fb keep relative precision."""
+    right of 0 it is mirrored (flip) so fa, fb keep relative precision.
+    fa, fb = 0.5 erfc(-bound / sqrt 2) with the C library's erfc (math.erfc)."""
     if post.family == N.FAM_CATEGORICAL:
         p = np.asarray(post.below[0], dtype=float)
         rows = np.zeros((len(p), 8))
@@ -392,8 +404,8 @@ def sampler_table(post):
     flip = za > 0
     a = np.where(flip, -zb, za)
     b = np.where(flip, -za, zb)
-    fa = 0.5 * erfc(-a / np.sqrt(2))
-    fb = 0.5 * erfc(-b / np.sqrt(2))
+    fa = 0.5 * _erfc_libm(-a / np.sqrt(2))
+    fb = 0.5 * _erfc_libm(-b / np.sqrt(2))
     mass = np.maximum(fb - fa, 0.0)
     sel = np.asarray(w, dtype=float) * (mass if (post.low is not None or post.high is not None) else 1.0)
     if not np.any(sel > 0):          # every component outside the bounds

@@ -106,15 +106,20 @@ def test_lpdf_unit_vectors(golden, engine):
 def test_philox_sampler_distribution(engine):
     """Device draws follow the below mixture: bounds, quantisation, and the
     exact mixture CDF (Kolmogorov distance), incl. truncation (the rejection
-    loop of tpe.py:82-87 is sampled by inversion)."""
+    loop of tpe.py:82-87 is sampled by inversion); quantised labels against the
+    exact mass of each lattice value.  All ten families."""
     from hyperopt_amd import parzen
     from hyperopt_amd.engine import LevelProblem
     from scipy.special import erf
+    from tests.draw_cases import lattice_masses
     rs = np.random.RandomState(3)
     C = 1 << 18
     for dist, args in (('uniform', dict(low=-2.0, high=3.0)), ('normal', dict(mu=0.5, sigma=2.0)),
                        ('loguniform', dict(low=-4.0, high=1.0)), ('quniform', dict(low=0.0, high=10.0, q=0.5)),
-                       ('randint', dict(upper=5)), ('categorical', dict(p=[0.1, 0.5, 0.4], upper=3))):
+                       ('randint', dict(upper=5)), ('categorical', dict(p=[0.1, 0.5, 0.4], upper=3)),
+                       ('lognormal', dict(mu=0.0, sigma=1.0)), ('qnormal', dict(mu=2.0, sigma=4.0, q=0.5)),
+                       ('qloguniform', dict(low=0.0, high=5.0, q=2.0)),
+                       ('qlognormal', dict(mu=1.0, sigma=0.7, q=0.25))):
         if dist in ('randint', 'categorical'):
             below = rs.randint(0, args['upper'], 9)
             above = rs.randint(0, args['upper'], 50)
@@ -122,7 +127,7 @@ def test_philox_sampler_distribution(engine):
             lo, hi = (args['low'], args['high']) if 'low' in args else (-3.0, 4.0)
             below = rs.uniform(lo, hi, 9)
             above = rs.uniform(lo, hi, 50)
-            if dist == 'loguniform':
+            if dist in ('loguniform', 'lognormal', 'qloguniform', 'qlognormal'):
                 below, above = np.exp(below), np.exp(above)
         post = parzen.fit_posterior(dist, args, below, above, 1.0)
         for precision in ('fp32', 'fp64'):
@@ -141,6 +146,15 @@ def test_philox_sampler_distribution(engine):
                     assert t.min() >= post.low and t.max() < post.high, dist
             if post.q is not None:
                 np.testing.assert_allclose(np.round(x / post.q) * post.q, x, rtol=0, atol=0)
+                # the law: each lattice value's frequency within 5 binomial standard
+                # deviations (+ 1 / C) of the exact mass of the coordinates rounded to it
+                pts, cnt = np.unique(x, return_counts=True)
+                m = lattice_masses(dict(q=post.q, family=post.family, low=post.low, high=post.high,
+                                        below=post.below), pts)
+                assert abs(m.sum() - 1.0) < 1e-3, (dist, precision, float(m.sum()))
+                tol_q = 5 * np.sqrt(m * (1 - m) / C) + 1.0 / C
+                assert np.all(np.abs(cnt / C - m) <= tol_q), (dist, precision,
+                                                              float(np.max(np.abs(cnt / C - m) / tol_q)))
                 continue
             t = np.sort(np.log(x) if post.family == 1 else x)
             grid = t[:: C // 512]
