@@ -87,7 +87,8 @@ JOINT_MAX_LATTICE_TOTAL = 512  # TPE_JOINT_MAX_LATTICE_TOTAL: lattice values of 
 JOINT_QFLOOR = -4096.0         # TPE_JOINT_QFLOOR: the smallest stored log2 P_kd(i)
 JOINT_QUANT_MAX_CONT = 8       # continuous / discrete labels beside a quantised one
 JOINT_QUANT_MAX_DISC = 4
-JOINT_WIDE_MAX_DIMS = 64       # TPE_JOINT_WIDE_MAX_DIMS: labels of a wide joint group (continuous only)
+JOINT_WIDE_MAX_DIMS = 64       # TPE_JOINT_WIDE_MAX_DIMS: labels of a wide joint group
+JOINT_WIDE_MAX_CAT = 8         # TPE_JOINT_WIDE_MAX_CAT: discrete labels among them (tpe_joint_wide_mixed_run)
 JOINT_WIDE_RECORD_DTYPE = np.dtype([('global_idx', '<i8'), ('l', '<f8'), ('g', '<f8'),
                                     ('z', '<f8', (JOINT_WIDE_MAX_DIMS,))])
 assert JOINT_WIDE_RECORD_DTYPE.itemsize == 536
@@ -173,6 +174,15 @@ class JointMixedArgs(ctypes.Structure):
         ('above_miss', ctypes.c_void_p), ('above_bonus', ctypes.c_void_p),
         ('below_h', ctypes.c_void_p), ('cat_cum', ctypes.c_void_p),
     ]
+
+
+class JointWideMixedArgs(ctypes.Structure):
+    """tpe_joint_wide_mixed_args: one tpe_joint_wide_mixed_run (tpe_joint_wide_args' fields, then up to
+    JOINT_WIDE_MAX_CAT discrete labels and the mixed stage's tables)."""
+    _fields_ = JointWideArgs._fields_ + [
+        ('n_cat', ctypes.c_int32),
+        ('cat_upper', ctypes.c_int32 * JOINT_WIDE_MAX_CAT), ('cat_off', ctypes.c_int32 * JOINT_WIDE_MAX_CAT),
+    ] + JointMixedArgs._fields_[-8:]
 
 
 class JointQuantArgs(ctypes.Structure):
@@ -434,6 +444,7 @@ EXPORTS = ('tpe_abi_version', 'tpe_last_error', 'tpe_device_count', 'tpe_tile_si
            'tpe_report_profile', 'tpe_joint_scratch_bytes', 'tpe_joint_run', 'tpe_joint_profile',
            'tpe_joint_mixed_run', 'tpe_joint_quant_table_bytes', 'tpe_joint_quant_run', 'tpe_joint_quant_profile',
            'tpe_joint_wide_scratch_bytes', 'tpe_joint_wide_run', 'tpe_joint_wide_profile',
+           'tpe_joint_wide_mixed_scratch_bytes', 'tpe_joint_wide_mixed_run',
            'tpe_joint_seg_scratch_bytes', 'tpe_joint_seg_run', 'tpe_joint_mseg_scratch_bytes',
            'tpe_joint_mseg_table_bytes', 'tpe_joint_mseg_run', 'tpe_joint_report_scratch_bytes',
            'tpe_joint_report', 'tpe_joint_report_profile', 'tpe_joint_run_shard')
@@ -567,6 +578,10 @@ def load(path=LIB_PATH):
     lib.tpe_joint_wide_run.restype = ctypes.c_int
     lib.tpe_joint_wide_profile.argtypes = [P]
     lib.tpe_joint_wide_profile.restype = ctypes.c_int
+    lib.tpe_joint_wide_mixed_scratch_bytes.argtypes = [I32, I32, I32, I32, ctypes.POINTER(ctypes.c_uint64)]
+    lib.tpe_joint_wide_mixed_scratch_bytes.restype = ctypes.c_int
+    lib.tpe_joint_wide_mixed_run.argtypes = [ctypes.POINTER(JointWideMixedArgs), P, P, P, P, P, ctypes.c_uint64, P]
+    lib.tpe_joint_wide_mixed_run.restype = ctypes.c_int
     lib.tpe_joint_seg_scratch_bytes.argtypes = [I32, I32, ctypes.POINTER(ctypes.c_uint64)]
     lib.tpe_joint_seg_scratch_bytes.restype = ctypes.c_int
     lib.tpe_joint_seg_run.argtypes = [ctypes.POINTER(JointSegArgs), P, P, P, P, P, ctypes.c_uint64, P]

@@ -35,6 +35,8 @@
 // k_joint_wide_sample / k_joint_wide_chunk / k_joint_wide_merge  the continuous
 //                stage for 17 to 64 coordinates ("wide groups" below): the
 //                candidates are drawn by a kernel of their own into scratch.
+// k_joint_wide_mixed_sample / k_joint_wide_mixed_chunk  the wide stage for a
+//                group that also holds up to 8 discrete labels.
 // tpe_joint_run_shard  any of the six stages over the candidates [cand_base,
 //                cand_base + n_cand) of a larger run: the views carry cand_base (a
 //                kernel argument: scalar registers), added to the local index
@@ -1484,8 +1486,297 @@ __global__ __launch_bounds__(64) void k_joint_wide_merge(const tpe_joint_wide_re
   }
 }
 
+// ------------------------------------------ discrete labels in wide groups
+// Dc continuous coordinates followed by Dk <= TPE_JOINT_WIDE_MAX_CAT discrete
+// ones, Dc + Dk <= TPE_JOINT_WIDE_MAX_DIMS (include/tpe_hip.h "Wide mixed joint
+// stage"): the model and the draws of the mixed stage, the data movement of the
+// wide one.
+// k_joint_wide_mixed_sample  k_joint_wide_sample, then the Dk categories as
+//                k_joint_mixed_chunk's sampler draws them (word 1 + j serves
+//                kernel coordinate j); a block of zbuf is [Dc + Dk][256].
+// k_joint_wide_mixed_chunk<DP, KP, R>  k_joint_wide_chunk with KP category slots
+//                a candidate: the component tile also holds cat[KP], a discrete
+//                slot costs one compare, one select and one add per (candidate,
+//                component), and sum_d miss_d(v_d) is added in f64 at the end.
+// k_joint_wide_merge serves it unchanged.
+constexpr int kWK = TPE_JOINT_WIDE_MAX_CAT;
+
+struct WideMixedSampK {
+  WideSampK s;                      // s.D = Dc; a block of zbuf is [Dc + Dk][256]
+  int Dk;
+  int U[kWK], off[kWK];
+  const float* bcat;
+  const double* bh;
+  const double* ccum;
+};
+
+struct WideMixedK {
+  WideK w;                          // w.D = Dc; zsrc / cand rows are [Dc + Dk]
+  int Dk;
+  int U[kWK], off[kWK];
+  const float *bcat, *acat;
+  const float *bmiss, *bbonus, *amiss, *abonus;
+};
+
+__global__ __launch_bounds__(kThreads) void k_joint_wide_mixed_sample(const WideMixedSampK p) {
+  __shared__ float blo[kWD], bhi[kWD];          // (kernel-argument arrays: constant indices only)
+  __shared__ int cU[kWK], coff[kWK];
+  const int t = threadIdx.x, Dc = p.s.D, Dk = p.Dk, D = Dc + Dk;
+  if (t == 0) {
+#pragma unroll
+    for (int f = 0; f < kWD; ++f) { blo[f] = p.s.lo[f]; bhi[f] = p.s.hi[f]; }
+#pragma unroll
+    for (int f = 0; f < kWK; ++f) { cU[f] = p.U[f]; coff[f] = p.off[f]; }
+  }
+  __syncthreads();
+  const int id = blockIdx.x / p.s.nblk, blk = blockIdx.x % p.s.nblk;
+  const int i = blk * kThreads + t;
+  if (i >= p.s.C) return;
+  float* out = p.s.zbuf + (int64_t)blockIdx.x * kThreads * D + t;
+  const uint32_t c3 = (uint32_t)p.s.ids[id], gi = p.s.cand_base + (uint32_t)i;   // gi < 2^31 (i < C)
+  U4 w = philox4x32_10(gi, 0u, p.s.stream_word, c3, p.s.key0, p.s.key1);
+  const double us = u01w(w.x);
+  int lo = 0, hi = p.s.kb - 1;             // first k with us < cum[k]
+  while (lo < hi) { const int mid = (lo + hi) >> 1; if (us < p.s.cum[mid]) hi = mid; else lo = mid + 1; }
+  const int comp = lo;
+  const float* srow = p.s.samp + (int64_t)comp * Dc * 5;
+  // word 1 + j serves kernel coordinate j; a continuous one is k_joint_wide_sample's draw
+#pragma unroll 1
+  for (int d = 0; d < Dc; ++d) {
+    const int wi = d + 1;
+    if ((wi & 3) == 0) w = philox4x32_10(gi, (uint32_t)(wi >> 2), p.s.stream_word, c3, p.s.key0, p.s.key1);
+    const uint32_t word = (wi & 3) == 0 ? w.x : (wi & 3) == 1 ? w.y : (wi & 3) == 2 ? w.z : w.w;
+    const float* sr = srow + d * 5;
+    const float pr = sr[2] + u01f(word) * (sr[3] - sr[2]);
+    float zz = ndtri_f32(pr);
+    if (sr[4] != 0.f) zz = -zz;
+    float x = sr[0] + sr[1] * zz;
+    if (!(x == x)) x = sr[0];
+    out[(int64_t)d * kThreads] = fminf(fmaxf(x, blo[d]), bhi[d]);      // low <= z < high
+  }
+  // ... a discrete one k_joint_mixed_chunk's: the category index as an f32
+#pragma unroll 1
+  for (int d = 0; d < Dk; ++d) {
+    const int wi = Dc + d + 1;
+    if ((wi & 3) == 0) w = philox4x32_10(gi, (uint32_t)(wi >> 2), p.s.stream_word, c3, p.s.key0, p.s.key1);
+    const uint32_t word = (wi & 3) == 0 ? w.x : (wi & 3) == 1 ? w.y : (wi & 3) == 2 ? w.z : w.w;
+    const double u = u01w(word);
+    float x = p.bcat[(int64_t)comp * Dk + d];             // the component's category, -1: the prior row
+    const double h = x >= 0.f ? p.bh[d] : 0.0;
+    if (!(u < h)) {
+      const double u2 = (u - h) / (1.0 - h);
+      const double* cum = p.ccum + coff[d];
+      int a = 0, b = cU[d] - 1;                           // first category with u2 < cum[v]
+      while (a < b) { const int mid = (a + b) >> 1; if (u2 < cum[mid]) b = mid; else a = mid + 1; }
+      x = (float)a;
+    }
+    out[(int64_t)(Dc + d) * kThreads] = x;
+  }
+}
+
+// score_side_wide with KP discrete slots (score_side_mixed's discrete part): the
+// tile holds a component's categories beside its rows, read as 16-byte
+// broadcasts where KP allows; out gets + sum_d miss_d(v_d) in f64.
+template <int DP, int KP, int R>
+__device__ __forceinline__ void score_side_wide_mixed(const float* __restrict__ mu, const float* __restrict__ a,
+                                                      const float* __restrict__ c, const float* __restrict__ cat,
+                                                      const float* __restrict__ miss, const float* __restrict__ bonus,
+                                                      int K, int Dc, int Dk, const int (&U)[KP], const int (&off)[KP],
+                                                      const float (&z)[R][DP], const float (&v)[R][KP],
+                                                      float* __restrict__ rows, float* __restrict__ cats,
+                                                      float* __restrict__ cl, double (&out)[R]) {
+  constexpr int TK = wide_tile(DP);
+  float m[R], s[R], nb[R][KP];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    m[r] = -3.0e38f;
+    s[r] = 0.f;
+#pragma unroll
+    for (int d = 0; d < KP; ++d) nb[r][d] = d < Dk ? -bonus[off[d] + cat_index(v[r][d], U[d])] : 0.f;
+  }
+  for (int k0 = 0; k0 < K; k0 += TK) {
+    const int nk = min(TK, K - k0);
+    __syncthreads();                       // the previous tile (or side) is read
+    for (int e = threadIdx.x; e < nk * DP; e += kThreads) {
+      const int kk = e / DP, d = e % DP;
+      const bool in = d < Dc;              // padded dimensions: a = 0 adds nothing
+      const int64_t src = (int64_t)(k0 + kk) * Dc + d;
+      rows[kk * 2 * DP + d] = in ? mu[src] : 0.f;
+      rows[kk * 2 * DP + DP + d] = in ? a[src] : 0.f;
+    }
+    for (int e = threadIdx.x; e < nk * KP; e += kThreads) {
+      const int kk = e / KP, d = e % KP;   // padded slots: category -1 never matches
+      cats[e] = d < Dk ? cat[(int64_t)(k0 + kk) * Dk + d] : -1.f;
+    }
+    for (int e = threadIdx.x; e < nk; e += kThreads) cl[e] = c[k0 + e];
+    __syncthreads();
+    for (int kk = 0; kk < nk; ++kk) {
+      const float4* row = reinterpret_cast<const float4*>(rows + kk * 2 * DP);
+      float acc[R];
+#pragma unroll
+      for (int r = 0; r < R; ++r) acc[r] = 0.f;
+#pragma unroll
+      for (int q = 0; q < DP / 4; ++q) {
+        const float4 rm = row[q], ra = row[DP / 4 + q];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          float u = (z[r][4 * q] - rm.x) * ra.x;
+          acc[r] = __builtin_fmaf(u, u, acc[r]);
+          u = (z[r][4 * q + 1] - rm.y) * ra.y;
+          acc[r] = __builtin_fmaf(u, u, acc[r]);
+          u = (z[r][4 * q + 2] - rm.z) * ra.z;
+          acc[r] = __builtin_fmaf(u, u, acc[r]);
+          u = (z[r][4 * q + 3] - rm.w) * ra.w;
+          acc[r] = __builtin_fmaf(u, u, acc[r]);
+        }
+      }
+      float rc[KP];
+      if constexpr (KP % 4 == 0) {
+        const float4* cr = reinterpret_cast<const float4*>(cats + kk * KP);
+#pragma unroll
+        for (int q = 0; q < KP / 4; ++q) {
+          const float4 x = cr[q];
+          rc[4 * q] = x.x; rc[4 * q + 1] = x.y; rc[4 * q + 2] = x.z; rc[4 * q + 3] = x.w;
+        }
+      } else if constexpr (KP == 2) {
+        const float2 x = *reinterpret_cast<const float2*>(cats + kk * 2);
+        rc[0] = x.x; rc[1] = x.y;
+      } else {
+        rc[0] = cats[kk];
+      }
+      const float ck = cl[kk];
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+#pragma unroll
+        for (int d = 0; d < KP; ++d) acc[r] += v[r][d] == rc[d] ? nb[r][d] : 0.f;
+        const float t = ck - acc[r];
+        const float dl = t - m[r];
+        const float e2 = __builtin_amdgcn_exp2f(-__builtin_fabsf(dl));
+        s[r] = dl > 0.f ? __builtin_fmaf(s[r], e2, 1.f) : s[r] + e2;
+        m[r] = fmaxf(m[r], t);
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    double M = 0.0;
+#pragma unroll
+    for (int d = 0; d < KP; ++d)
+      if (d < Dk) M += (double)miss[off[d] + cat_index(v[r][d], U[d])];
+    out[r] = (double)m[r] + log2((double)s[r]) + M;
+  }
+}
+
+template <int DP, int KP, int R>
+__global__ __launch_bounds__(kThreads) void k_joint_wide_mixed_chunk(const WideMixedK p) {
+  static_assert(DP % 4 == 0 && DP <= kWD && KP <= kWK, "rows are read as float4; the argument arrays");
+  constexpr int TK = wide_tile(DP);
+  // at most 128 * (64 + 8) * 4 B = 36 KiB of tile: four workgroups fit a CU's 160 KiB
+  __shared__ __attribute__((aligned(16))) float rows[TK * 2 * DP];
+  __shared__ __attribute__((aligned(16))) float cats[TK * KP];
+  __shared__ float cl[TK];
+  __shared__ Pick slot[kThreads / 64];
+  const int t = threadIdx.x, Dc = p.w.D, Dk = p.Dk, D = Dc + Dk;
+  const int id = blockIdx.x / p.w.n_chunks, chunk = blockIdx.x % p.w.n_chunks;
+  const int first = chunk * (R * kThreads);
+  int U[KP], off[KP];                      // (kernel-argument arrays: constant indices only)
+#pragma unroll
+  for (int d = 0; d < KP; ++d) { U[d] = p.U[d]; off[d] = p.off[d]; }
+
+  float z[R][DP], v[R][KP];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+#pragma unroll
+    for (int d = 0; d < DP; ++d) z[r][d] = 0.f;
+#pragma unroll
+    for (int d = 0; d < KP; ++d) v[r][d] = 0.f;
+    const int i = first + r * kThreads + t;
+    if (i >= p.w.C) continue;
+    if (p.w.inject) {
+      const float* src = p.w.zsrc + (int64_t)i * D;
+#pragma unroll
+      for (int d = 0; d < DP; ++d)
+        if (d < Dc) z[r][d] = src[d];
+#pragma unroll
+      for (int d = 0; d < KP; ++d)
+        if (d < Dk) v[r][d] = src[Dc + d];
+    } else {
+      // block chunk * R + r of this id (i < C: the block exists)
+      const float* src = p.w.zsrc + ((int64_t)id * p.w.nblk + chunk * R + r) * kThreads * D + t;
+#pragma unroll
+      for (int d = 0; d < DP; ++d)
+        if (d < Dc) z[r][d] = src[(int64_t)d * kThreads];
+#pragma unroll
+      for (int d = 0; d < KP; ++d)
+        if (d < Dk) v[r][d] = src[(int64_t)(Dc + d) * kThreads];
+    }
+  }
+
+  double l2[R], g2[R];
+  score_side_wide_mixed<DP, KP, R>(p.w.bmu, p.w.ba, p.w.bc, p.bcat, p.bmiss, p.bbonus, p.w.kb, Dc, Dk, U, off, z, v,
+                                   rows, cats, cl, l2);
+  score_side_wide_mixed<DP, KP, R>(p.w.amu, p.w.aa, p.w.ac, p.acat, p.amiss, p.abonus, p.w.ka, Dc, Dk, U, off, z, v,
+                                   rows, cats, cl, g2);
+
+  Pick best{0, 0};
+  double lv[R], gv[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int i = first + r * kThreads + t;
+    lv[r] = l2[r] * kLn2 + p.w.bbase;
+    gv[r] = g2[r] * kLn2 + p.w.abase;
+    if (i >= p.w.C) continue;
+    const int64_t o = (int64_t)id * p.w.C + i;
+    if (p.w.l_out) p.w.l_out[o] = lv[r];
+    if (p.w.g_out) p.w.g_out[o] = gv[r];
+    if (p.w.cand) {
+#pragma unroll
+      for (int d = 0; d < DP; ++d)
+        if (d < Dc) p.w.cand[o * D + d] = z[r][d];
+#pragma unroll
+      for (int d = 0; d < KP; ++d)
+        if (d < Dk) p.w.cand[o * D + Dc + d] = v[r][d];
+    }
+    const uint64_t key = score_key(lv[r] - gv[r]);
+    if (key > best.key) best = Pick{key, (int64_t)i};   // ascending index: strict > keeps the first of a tie
+  }
+  Pick w = wave_best(best);
+  if ((t & 63) == 0) slot[t >> 6] = w;
+  __syncthreads();
+  w = slot[0];
+#pragma unroll
+  for (int q = 1; q < kThreads / 64; ++q)
+    if (beats(slot[q], w)) w = slot[q];
+
+  tpe_joint_wide_record* rec = p.w.chunk_rec + blockIdx.x;
+  if (w.key == 0) {
+    if (t == 0) rec->global_idx = -1;
+    return;
+  }
+  const int woff = (int)(w.idx - first);
+  if (t != woff % kThreads) return;
+  const int wr = woff / kThreads;
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    if (r != wr) continue;
+    rec->global_idx = w.idx + (int64_t)p.w.cand_base;
+    rec->l = lv[r];
+    rec->g = gv[r];
+    // kernel coordinate order: the Dc continuous entries, the categories, then zeros
+#pragma unroll
+    for (int d = 0; d < kWD; ++d)
+      if (d >= D) rec->z[d] = 0.0;
+#pragma unroll
+    for (int d = 0; d < DP; ++d)
+      if (d < Dc) rec->z[d] = (double)z[r][d];
+#pragma unroll
+    for (int d = 0; d < KP; ++d)
+      if (d < Dk) rec->z[Dc + d] = (double)v[r][d];
+  }
+}
+
 // ------------------------------------------------------------- host driver
-// Everything from here on runs on the host: the six stages' argument checks,
+// Everything from here on runs on the host: the stages' argument checks,
 // the kernel-argument fills and the launches.  What the stages share exists
 // once (the launch and its profiling events, the padded-width dispatchers, the
 // solo stages' head checks and JointK fill, the category and lattice checks,
@@ -1662,10 +1953,16 @@ int64_t wide_chunks_of(int32_t n_cand, int D) {
 uint64_t wide_record_bytes(int32_t n_ids, int32_t n_cand, int D) {
   return (uint64_t)n_ids * (uint64_t)wide_chunks_of(n_cand, D) * sizeof(tpe_joint_wide_record);
 }
-uint64_t wide_scratch_need(int32_t n_ids, int32_t n_cand, int D) {
+// (Dk: the discrete coordinates of a wide mixed run beside its D continuous ones;
+// the chunk size follows the continuous width, and R is 2 below 20 coordinates too)
+uint64_t wide_scratch_need(int32_t n_ids, int32_t n_cand, int D, int Dk = 0) {
   return wide_record_bytes(n_ids, n_cand, D) +
-         (uint64_t)n_ids * (uint64_t)wide_blocks_of(n_cand) * kThreads * (uint64_t)D * sizeof(float);
+         (uint64_t)n_ids * (uint64_t)wide_blocks_of(n_cand) * kThreads * (uint64_t)(D + Dk) * sizeof(float);
 }
+// padded continuous width of a wide group with discrete labels: narrow groups too
+template <typename F>
+void for_wide_mixed_dp(int Dc, F&& f) { pad_to<12, 16, 20, 24, 32, 48, 64>(Dc, f); }
+static_assert(wide_r(12) == wide_r(20) && wide_r(16) == wide_r(20), "wide_chunks_of serves the narrow widths");
 int size_out(const char* entry, bool ok, uint64_t value, uint64_t* bytes) {
   if (!bytes || !ok) return fail(entry, "bad arguments");
   *bytes = value;
@@ -1673,9 +1970,10 @@ int size_out(const char* entry, bool ok, uint64_t value, uint64_t* bytes) {
 }
 
 // ---- what the solo stages share
-// tpe_joint_args, tpe_joint_wide_args and tpe_joint_mixed_args (with it
-// tpe_joint_quant_args, which begins with it) have the same fields at the same
-// offsets up to `low`: the head checks and the JointK fill are templates over them
+// tpe_joint_args, tpe_joint_wide_args (with it tpe_joint_wide_mixed_args, which
+// begins with it) and tpe_joint_mixed_args (with it tpe_joint_quant_args, which
+// begins with it) have the same fields at the same offsets up to `low`: the
+// head checks and the JointK fill are templates over them
 static_assert(offsetof(tpe_joint_wide_args, low) == offsetof(tpe_joint_args, low) &&
                   offsetof(tpe_joint_mixed_args, low) == offsetof(tpe_joint_args, low) &&
                   offsetof(tpe_joint_mixed_args, n_cat) == offsetof(tpe_joint_args, reserved),
@@ -1688,6 +1986,12 @@ static_assert(sizeof(tpe_joint_args) == offsetof(tpe_joint_mixed_args, cat_upper
 static_assert(offsetof(tpe_joint_quant_args, n_quant) == sizeof(tpe_joint_mixed_args) &&
                   offsetof(tpe_joint_quant_args, cat_cum) == offsetof(tpe_joint_mixed_args, cat_cum),
               "tpe_joint_quant_args starts with tpe_joint_mixed_args");
+
+// ... and a wide group without a discrete label a tpe_joint_wide_args
+static_assert(offsetof(tpe_joint_wide_mixed_args, n_cat) == sizeof(tpe_joint_wide_args) &&
+                  offsetof(tpe_joint_wide_mixed_args, low) == offsetof(tpe_joint_wide_args, low) &&
+                  offsetof(tpe_joint_wide_mixed_args, high) == offsetof(tpe_joint_wide_args, high),
+              "tpe_joint_wide_mixed_args starts with tpe_joint_wide_args");
 
 // The checks after the stage's own ones on its dimensions; Dc: the continuous
 // coordinates (0: the group has none, and their rows may be null).
@@ -1813,6 +2117,43 @@ int joint_run_at(const tpe_joint_args* a, tpe_joint_record* records, float* cand
   return finish(k_joint_merge, (const tpe_joint_record*)scratch, k.n_chunks, records, a->n_ids, s, timed, 1);
 }
 
+// What the two wide stages share: the sampling kernel's arguments of a group of
+// D continuous coordinates (the bounds staged as f32), its launch under
+// profiling, the scoring kernel's arguments.
+template <typename A>
+void fill_wide_samp(WideSampK& sk, const A* a, int D, int64_t nblk, uint32_t cand_base, float* zbuf) {
+  sk.D = D; sk.C = a->n_cand; sk.nblk = (int)nblk; sk.kb = a->k_below;
+  sk.key0 = (uint32_t)a->seed; sk.key1 = (uint32_t)(a->seed >> 32); sk.stream_word = a->stream_word;
+  sk.cand_base = cand_base;
+  sk.cum = a->samp_cum; sk.samp = a->samp; sk.ids = a->ids; sk.zbuf = zbuf;
+  for (int d = 0; d < TPE_JOINT_WIDE_MAX_DIMS; ++d) {
+    sk.lo[d] = -INFINITY; sk.hi[d] = INFINITY;
+    if (d < D) f32_bounds(a->low[d], a->high[d], sk.lo[d], sk.hi[d]);
+  }
+}
+template <typename K, typename SK>
+int launch_wide_samp(K kernel, int64_t sblocks, hipStream_t s, bool timed, const SK& sk) {
+  if (timed)
+    if (int rc = ensure_events(g_wprof.ev, 2)) return rc;
+  launch(kernel, dim3((unsigned)sblocks), kThreads, 0u, s, timed ? g_wprof.ev[0] : nullptr,
+         timed ? g_wprof.ev[1] : nullptr, sk);
+  g_wprof.valid = timed ? 1 : 0;
+  return TPE_OK;
+}
+template <typename A>
+void fill_wide(WideK& k, const A* a, int D, int64_t n_chunks, int64_t nblk, uint32_t cand_base, const float* zbuf,
+               float* cand, double* l_out, double* g_out, void* scratch) {
+  const bool inject = (a->flags & TPE_JOINT_INJECT) != 0;
+  k.D = D; k.C = a->n_cand; k.n_chunks = (int)n_chunks; k.nblk = (int)nblk; k.inject = inject ? 1 : 0;
+  k.kb = a->k_below; k.ka = a->k_above; k.cand_base = cand_base;
+  k.bmu = a->below_mu; k.ba = a->below_a; k.bc = a->below_c;
+  k.amu = a->above_mu; k.aa = a->above_a; k.ac = a->above_c;
+  k.bbase = a->below_base; k.abase = a->above_base;
+  k.zsrc = inject ? a->inject : zbuf;
+  k.cand = cand; k.l_out = l_out; k.g_out = g_out;
+  k.chunk_rec = (tpe_joint_wide_record*)scratch;
+}
+
 int joint_wide_run_at(const tpe_joint_wide_args* a, tpe_joint_wide_record* records, float* cand, double* l_out,
                       double* g_out, void* scratch, uint64_t scratch_bytes, void* stream, uint32_t cand_base) {
   constexpr const char* E = "tpe_joint_wide_run";
@@ -1833,34 +2174,76 @@ int joint_wide_run_at(const tpe_joint_wide_args* a, tpe_joint_wide_record* recor
   g_wprof.valid = 0;
   if (!inject) {
     WideSampK sk;
-    sk.D = D; sk.C = a->n_cand; sk.nblk = (int)nblk; sk.kb = a->k_below;
-    sk.key0 = (uint32_t)a->seed; sk.key1 = (uint32_t)(a->seed >> 32); sk.stream_word = a->stream_word;
-    sk.cand_base = cand_base;
-    sk.cum = a->samp_cum; sk.samp = a->samp; sk.ids = a->ids; sk.zbuf = zbuf;
-    for (int d = 0; d < TPE_JOINT_WIDE_MAX_DIMS; ++d) {
-      sk.lo[d] = -INFINITY; sk.hi[d] = INFINITY;
-      if (d < D) f32_bounds(a->low[d], a->high[d], sk.lo[d], sk.hi[d]);
-    }
-    if (timed)
-      if (int rc = ensure_events(g_wprof.ev, 2)) return rc;
-    launch(k_joint_wide_sample, dim3((unsigned)sblocks), kThreads, 0u, s, timed ? g_wprof.ev[0] : nullptr,
-           timed ? g_wprof.ev[1] : nullptr, sk);
-    g_wprof.valid = timed ? 1 : 0;
+    fill_wide_samp(sk, a, D, nblk, cand_base, zbuf);
+    if (int rc = launch_wide_samp(k_joint_wide_sample, sblocks, s, timed, sk)) return rc;
   }
 
   WideK k;
-  k.D = D; k.C = a->n_cand; k.n_chunks = (int)n_chunks; k.nblk = (int)nblk; k.inject = inject ? 1 : 0;
-  k.kb = a->k_below; k.ka = a->k_above; k.cand_base = cand_base;
-  k.bmu = a->below_mu; k.ba = a->below_a; k.bc = a->below_c;
-  k.amu = a->above_mu; k.aa = a->above_a; k.ac = a->above_c;
-  k.bbase = a->below_base; k.abase = a->above_base;
-  k.zsrc = inject ? a->inject : zbuf;
-  k.cand = cand; k.l_out = l_out; k.g_out = g_out;
-  k.chunk_rec = (tpe_joint_wide_record*)scratch;
+  fill_wide(k, a, D, n_chunks, nblk, cand_base, zbuf, cand, l_out, g_out, scratch);
   const Ev ev = chunk_marks(timed);
   for_wide_dp(D, [&](auto dp) {
     constexpr int DP = decltype(dp)::value;
     launch(k_joint_wide_chunk<DP, wide_r(DP)>, dim3((unsigned)blocks), kThreads, 0u, s, ev.start, ev.stop, k);
+  });
+  return finish(k_joint_wide_merge, (const tpe_joint_wide_record*)scratch, (int)n_chunks, records, a->n_ids, s, timed, 1);
+}
+
+// (cand_base: the kernels carry it as the wide stage's do; tpe_joint_run_shard does not take this stage yet)
+int joint_wide_mixed_run_at(const tpe_joint_wide_mixed_args* a, tpe_joint_wide_record* records, float* cand,
+                            double* l_out, double* g_out, void* scratch, uint64_t scratch_bytes, void* stream,
+                            uint32_t cand_base) {
+  constexpr const char* E = "tpe_joint_wide_mixed_run";
+  tpe_internal_epoch_bump();
+  if (!a) return fail(E, "null args");
+  if (a->n_cat < 0 || a->n_cat > TPE_JOINT_WIDE_MAX_CAT) return fail(E, "n_cat outside [0, TPE_JOINT_WIDE_MAX_CAT]");
+  if (a->n_cat == 0) {                      // no discrete label: the wide stage, the same bytes
+    tpe_joint_wide_args c;
+    memcpy(&c, a, sizeof c);
+    return joint_wide_run_at(&c, records, cand, l_out, g_out, scratch, scratch_bytes, stream, cand_base);
+  }
+  if (a->n_dims < 1 || a->n_dims + a->n_cat > TPE_JOINT_WIDE_MAX_DIMS)
+    return fail(E, "n_dims < 1 or n_dims + n_cat outside [1, TPE_JOINT_WIDE_MAX_DIMS]");
+  const int Dc = a->n_dims, Dk = a->n_cat;
+  if (int rc = check_solo_head(E, a, records, Dc)) return rc;
+  if (cat_tables_null(a)) return fail(E, "null category tables");
+  if (check_cats(E, "", a->cat_upper, a->cat_off, Dk) < 0) return TPE_E_ARG;
+  const bool inject = (a->flags & TPE_JOINT_INJECT) != 0;
+  const int64_t n_chunks = wide_chunks_of(a->n_cand, Dc), blocks = n_chunks * a->n_ids;
+  const int64_t nblk = wide_blocks_of(a->n_cand), sblocks = nblk * a->n_ids;
+  if (int rc = check_scratch(E, sblocks, wide_scratch_need(a->n_ids, a->n_cand, Dc, Dk), scratch, scratch_bytes))
+    return rc;
+
+  const bool timed = g_prof.on != 0;
+  hipStream_t s = (hipStream_t)stream;
+  float* zbuf = (float*)((char*)scratch + wide_record_bytes(a->n_ids, a->n_cand, Dc));
+  int U[TPE_JOINT_WIDE_MAX_CAT], off[TPE_JOINT_WIDE_MAX_CAT];
+  for (int d = 0; d < TPE_JOINT_WIDE_MAX_CAT; ++d) {
+    U[d] = d < Dk ? a->cat_upper[d] : 1;
+    off[d] = d < Dk ? a->cat_off[d] : 0;
+  }
+  g_wprof.valid = 0;
+  if (!inject) {
+    WideMixedSampK sk;
+    fill_wide_samp(sk.s, a, Dc, nblk, cand_base, zbuf);
+    sk.Dk = Dk;
+    memcpy(sk.U, U, sizeof U); memcpy(sk.off, off, sizeof off);
+    sk.bcat = a->below_cat; sk.bh = a->below_h; sk.ccum = a->cat_cum;
+    if (int rc = launch_wide_samp(k_joint_wide_mixed_sample, sblocks, s, timed, sk)) return rc;
+  }
+
+  WideMixedK k;
+  fill_wide(k.w, a, Dc, n_chunks, nblk, cand_base, zbuf, cand, l_out, g_out, scratch);
+  k.Dk = Dk;
+  memcpy(k.U, U, sizeof U); memcpy(k.off, off, sizeof off);
+  k.bcat = a->below_cat; k.acat = a->above_cat;
+  k.bmiss = a->below_miss; k.bbonus = a->below_bonus; k.amiss = a->above_miss; k.abonus = a->above_bonus;
+  const Ev ev = chunk_marks(timed);
+  for_wide_mixed_dp(Dc, [&](auto dp) {
+    constexpr int DP = decltype(dp)::value;
+    for_kp<1, 8>(Dk, [&](auto kp) {
+      launch(k_joint_wide_mixed_chunk<DP, decltype(kp)::value, wide_r(DP)>, dim3((unsigned)blocks), kThreads, 0u, s,
+             ev.start, ev.stop, k);
+    });
   });
   return finish(k_joint_wide_merge, (const tpe_joint_wide_record*)scratch, (int)n_chunks, records, a->n_ids, s, timed, 1);
 }
@@ -2233,6 +2616,13 @@ int tpe_joint_wide_scratch_bytes(int32_t n_ids, int32_t n_cand, int32_t n_dims, 
   return size_out("tpe_joint_wide_scratch_bytes", ok, ok ? wide_scratch_need(n_ids, n_cand, n_dims) : 0, bytes);
 }
 
+int tpe_joint_wide_mixed_scratch_bytes(int32_t n_ids, int32_t n_cand, int32_t n_dims, int32_t n_cat, uint64_t* bytes) {
+  const bool ok = n_ids >= 1 && n_cand >= 1 && n_dims >= 1 && n_cat >= 0 && n_cat <= TPE_JOINT_WIDE_MAX_CAT &&
+                  n_dims + n_cat <= TPE_JOINT_WIDE_MAX_DIMS;
+  return size_out("tpe_joint_wide_mixed_scratch_bytes", ok, ok ? wide_scratch_need(n_ids, n_cand, n_dims, n_cat) : 0,
+                  bytes);
+}
+
 int tpe_joint_quant_table_bytes(int32_t k_below, int32_t k_above, int32_t total_bins, uint64_t* bytes) {
   const bool ok = k_below >= 1 && k_above >= 1 && total_bins >= 1;
   return size_out("tpe_joint_quant_table_bytes", ok, quant_table_floats(k_below, k_above, total_bins) * sizeof(float),
@@ -2273,6 +2663,11 @@ int tpe_joint_mseg_run(const tpe_joint_mseg_args* a, tpe_joint_record* records, 
 int tpe_joint_wide_run(const tpe_joint_wide_args* a, tpe_joint_wide_record* records, float* cand, double* l_out,
                        double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
   return joint_wide_run_at(a, records, cand, l_out, g_out, scratch, scratch_bytes, stream, 0u);
+}
+
+int tpe_joint_wide_mixed_run(const tpe_joint_wide_mixed_args* a, tpe_joint_wide_record* records, float* cand,
+                             double* l_out, double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
+  return joint_wide_mixed_run_at(a, records, cand, l_out, g_out, scratch, scratch_bytes, stream, 0u);
 }
 
 int tpe_joint_mixed_run(const tpe_joint_mixed_args* a, tpe_joint_record* records, float* cand, double* l_out,

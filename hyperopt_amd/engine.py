@@ -1031,11 +1031,12 @@ class Engine(object):
     # the solo stages by joint_pack entry: the args struct and the native function
     _JOINT_SOLO = {'run': (N.JointArgs, 'tpe_joint_run'), 'wide': (N.JointWideArgs, 'tpe_joint_wide_run'),
                    'mixed': (N.JointMixedArgs, 'tpe_joint_mixed_run'),
+                   'wide_mixed': (N.JointWideMixedArgs, 'tpe_joint_wide_mixed_run'),
                    'quant': (N.JointQuantArgs, 'tpe_joint_quant_run')}
 
     def _joint_solo(self, entry, below, above, low, high, cats, quants, ids, n_cand, seed, inject, return_cand,
                     want_lg, report_k, stream_word, shard, return_table=False):
-        """What the four solo stages share: the group's rows (joint_pack.group_rows,
+        """What the five solo stages share: the group's rows (joint_pack.group_rows,
         which also checks the group; an empty part of a sharded stage is checked
         too), one upload per row, the args struct filled from the same rows
         record, the call and its results.  The library derives the f32 bounds
@@ -1043,7 +1044,7 @@ class Engine(object):
         lattice ends follow the continuous bounds there."""
         r = JP.group_rows(below, above, low, high, cats, quants, entry=entry)
         Dc, Dk, Dq = r['Dc'], r['Dk'], r['Dq']
-        D, wide = Dc + Dk + Dq, entry == 'wide'
+        D, wide = Dc + Dk + Dq, entry in ('wide', 'wide_mixed')
         ids, n_ids, C = self._joint_sizes(D, ids, n_cand, shard)
         shard = self._joint_shard(shard, C, report_k, inject)
         if C == 0:
@@ -1083,7 +1084,8 @@ class Engine(object):
                     'tpe_joint_quant_table_bytes')
             d_tab = self._buf('joint_qtable', (nb.value + 3) // 4, torch.float32)
             a.quant_table, a.quant_table_bytes = d_tab.data_ptr(), d_tab.numel() * 4
-        out = self._joint_call(fn, a, n_ids, C, D, return_cand, want_lg, wide=wide, report_k=report_k, shard=shard)
+        out = self._joint_call(fn, a, n_ids, C, D, return_cand, want_lg, wide=wide, report_k=report_k, shard=shard,
+                               n_cat=Dk if wide else 0)
         if not return_table:
             return out
         tab = d_tab[:(a.k_below + a.k_above) * total].cpu().numpy()
@@ -1155,17 +1157,21 @@ class Engine(object):
         t[:arr.size].copy_(torch.from_numpy(np.ascontiguousarray(arr).reshape(-1)))
         return t.data_ptr()
 
-    def _joint_call(self, fn, a, n_ids, C, D, return_cand, want_lg, wide=False, report_k=0, shard=None):
+    def _joint_call(self, fn, a, n_ids, C, D, return_cand, want_lg, wide=False, report_k=0, shard=None, n_cat=0):
         """Scratch and result buffers, the native call ``fn`` and the records
         (and candidates [n_ids, C, D], l, g [n_ids, C]) on the host.  ``wide``:
-        the wide stage's scratch size and record.  ``report_k``: the stage
+        the wide stage's scratch size and record (``n_cat`` > 0: the wide mixed
+        stage's, ``n_cat`` of the D coordinates discrete).  ``report_k``: the stage
         writes all three device buffers and the joint report follows.
         ``shard`` (N.JointShard): the call goes through tpe_joint_run_shard."""
         report_k = self._report_k(report_k)
         dev_cand, dev_lg = return_cand or report_k > 0, want_lg or report_k > 0
         nb = ctypes.c_uint64(0)
         rec_dtype = N.JOINT_WIDE_RECORD_DTYPE if wide else N.JOINT_RECORD_DTYPE
-        if wide:
+        if wide and n_cat:
+            N.check(self.lib.tpe_joint_wide_mixed_scratch_bytes(n_ids, C, D - n_cat, n_cat, ctypes.byref(nb)), self.lib,
+                    'tpe_joint_wide_mixed_scratch_bytes')
+        elif wide:
             N.check(self.lib.tpe_joint_wide_scratch_bytes(n_ids, C, D, ctypes.byref(nb)), self.lib,
                     'tpe_joint_wide_scratch_bytes')
         else:
@@ -1352,6 +1358,20 @@ class Engine(object):
         group's joint.branch_stream_word, to compare with run_joint_segments)."""
         return self._joint_solo('mixed', below, above, low, high, cats, (), ids, n_cand, seed, inject, return_cand,
                                 want_lg, report_k, stream_word, shard)
+
+    def run_joint_wide_mixed(self, below, above, low, high, cats, ids, n_cand, seed, inject=None, return_cand=False,
+                             want_lg=False, report_k=0, stream_word=None):
+        """``run_joint_mixed`` for a group of up to N.JOINT_WIDE_MAX_DIMS
+        coordinates of which 1 to N.JOINT_WIDE_MAX_CAT are discrete and at least
+        one is continuous (tpe_joint_wide_mixed_run, include/tpe_hip.h "Wide
+        mixed joint stage"): the same arguments, model, kernel coordinate order,
+        Philox streams and return shapes; the records are
+        N.JOINT_WIDE_RECORD_DTYPE.  The continuous coordinates are those of
+        ``run_joint_wide`` over the continuous part, and a group of at most
+        N.JOINT_MAX_DIMS coordinates draws ``run_joint_mixed``'s candidates.  The
+        stage is not sharded: there is no ``shard`` argument."""
+        return self._joint_solo('wide_mixed', below, above, low, high, cats, (), ids, n_cand, seed, inject,
+                                return_cand, want_lg, report_k, stream_word, None)
 
     def run_joint_quant(self, below, above, low, high, cats, quants, ids, n_cand, seed, inject=None, return_cand=False,
                         want_lg=False, return_table=False, report_k=0, stream_word=None, shard=None):

@@ -10,6 +10,7 @@ The dimension limits by entry point (``_check_dims``):
   'run'      run_joint             1 <= D <= JOINT_MAX_DIMS, continuous only
   'wide'     run_joint_wide        1 <= D <= JOINT_WIDE_MAX_DIMS, continuous only
   'mixed'    run_joint_mixed       Dk >= 1, Dc + Dk <= JOINT_MAX_DIMS
+  'wide_mixed' run_joint_wide_mixed  1 <= Dk <= JOINT_WIDE_MAX_CAT, Dq = 0, 1 <= Dc + Dk <= JOINT_WIDE_MAX_DIMS
   'quant'    run_joint_quant       Dq >= 1, Dc <= JOINT_QUANT_MAX_CONT, Dk <= JOINT_QUANT_MAX_DISC
   'segment'  run_joint_segments    a continuous group 1 <= Dc <= JOINT_MAX_DIMS; one with discrete or
                                    quantised parts Dc <= JOINT_MSEG_MAX_CONT, Dk <= JOINT_MSEG_MAX_CAT
@@ -77,6 +78,12 @@ def _check_dims(entry, Dc, Dk, Dq):
             raise ValueError('joint stage: a segment with discrete or quantised dimensions holds at most %d continuous '
                              'and %d discrete ones, not %d and %d'
                              % (N.JOINT_MSEG_MAX_CONT, N.JOINT_MSEG_MAX_CAT, Dc, Dk))
+    elif entry == 'wide_mixed':
+        if Dq or not 1 <= Dk <= N.JOINT_WIDE_MAX_CAT:
+            raise ValueError('joint stage: a wide group with discrete dimensions holds 1 to %d of them and no '
+                             'quantised one, not %d and %d' % (N.JOINT_WIDE_MAX_CAT, Dk, Dq))
+        if not 1 <= Dc + Dk <= N.JOINT_WIDE_MAX_DIMS:
+            raise ValueError('joint stage: %d dimensions, at most %d' % (Dc + Dk, N.JOINT_WIDE_MAX_DIMS))
     else:
         top = N.JOINT_WIDE_MAX_DIMS if entry == 'wide' else N.JOINT_MAX_DIMS
         if not 1 <= Dc + Dk <= top:

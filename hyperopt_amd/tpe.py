@@ -38,7 +38,8 @@ Extensions over the reference (keyword-only, defaults keep its behaviour):
     ``joint_discrete=True`` lets the group also hold unconditional randint /
     categorical labels that gate no other label, ``joint_quantized=True``
     unconditional quniform / qloguniform labels of 2 to 256 lattice values,
-    ``joint_wide=True`` 17 to 64 continuous labels instead of at most 16.
+    ``joint_wide=True`` 17 to 64 continuous labels instead of at most 16,
+    ``joint_wide_mixed=True`` (with both) 1 to 8 discrete labels among them.
     ``joint_branches=True`` also joins the continuous labels of every
     conditional branch, one group per (gate, option), each id under the model
     of the branch it takes (DESIGN.md "Branch groups");
@@ -842,17 +843,18 @@ def suggest(new_ids, domain, trials, seed,
             linear_forgetting=_default_linear_forgetting,
             sampler='philox', precision='fp32', device=None, shard=None, shard_ids=None, shard_labels=None,
             shard_grid=None, joint=False, joint_discrete=False, joint_quantized=False, joint_wide=False,
-            joint_branches=False, joint_branches_mixed=False, joint_shard=None):
+            joint_branches=False, joint_branches_mixed=False, joint_shard=None, joint_wide_mixed=False):
     new_ids = list(new_ids)
     if not new_ids:
         return []
     if joint_shard is not None:                  # (argument errors first, as below; nothing on the default path)
-        _joint_shard_pair(joint_shard, joint)
+        _joint_shard_pair(joint_shard, joint, joint_wide_mixed)
     if ((joint is not False and joint is not None) or joint_discrete or joint_quantized or joint_wide or joint_branches
-            or joint_branches_mixed):
+            or joint_branches_mixed or joint_wide_mixed):
         # (argument errors first: no device use, no startup draw)
         _joint_plan(domain.table, joint, sampler, precision, (shard, shard_ids, shard_labels, shard_grid),
-                    joint_discrete, joint_quantized, joint_wide, joint_branches, joint_branches_mixed)
+                    joint_discrete, joint_quantized, _wide_mode(joint_wide, joint_wide_mixed), joint_branches,
+                    joint_branches_mixed)
     t0 = time.time()
     hist = _history.extract(domain, trials)
     if logger.isEnabledFor(logging.INFO):
@@ -869,7 +871,7 @@ def suggest(new_ids, domain, trials, seed,
                               shard_labels=shard_labels, shard_grid=shard_grid, joint=joint,
                               joint_discrete=joint_discrete, joint_quantized=joint_quantized, joint_wide=joint_wide,
                               joint_branches=joint_branches, joint_branches_mixed=joint_branches_mixed,
-                              joint_shard=joint_shard)
+                              joint_shard=joint_shard, joint_wide_mixed=joint_wide_mixed)
     logger.info('tpe.suggest took %f seconds', time.time() - t0)
     return rand.docs_from_choices(new_ids, domain, trials, choices)
 
@@ -911,7 +913,7 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
                     sampler='philox', precision='fp32', device=None, shard=None, columns=False,
                     shard_ids=None, shard_labels=None, shard_grid=None, joint=False, joint_discrete=False,
                     joint_quantized=False, joint_wide=False, joint_branches=False, joint_branches_mixed=False,
-                    joint_shard=None):
+                    joint_shard=None, joint_wide_mixed=False):
     """The suggest core on a structure-of-arrays history (``history.History``):
     per new id a {label: value or None} dict.  ``suggest`` wraps it with the
     Trials document layout; columnar callers (and bench.py's large configs)
@@ -957,6 +959,19 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
     groups"), whose candidates continue the same Philox streams.  A group of at
     most 16 labels takes exactly the path without the keyword, byte for byte.
     64 bounds the set of kernel instantiations; it is not a measured limit.
+
+    ``joint_wide_mixed=True`` (with ``joint``, ``joint_wide`` and
+    ``joint_discrete``): a group of 17 to 64 labels may hold 1 to
+    TPE_JOINT_WIDE_MAX_CAT = 8 discrete labels (those ``joint_discrete``
+    admits, at most 1024 categories in all) beside its continuous ones; it is
+    scored by the wide mixed stage (DESIGN.md "Discrete labels in wide groups"):
+    the mixed model, kernel coordinates continuous first, then discrete, the
+    continuous coordinates drawn as the wide stage draws them.  A group of at
+    most 16 labels, and a wide one without a discrete label, take exactly the
+    path without the keyword, byte for byte.  A quantised label, more than 8
+    discrete labels or more than 64 labels in such a group raise ValueError; 8
+    bounds the set of kernel instantiations, it is not a measured limit.  It
+    does not combine with ``joint_shard``.
 
     ``joint_branches=True`` (with ``joint``): conditional labels are joined
     too, one group per branch (DESIGN.md "Branch groups").  A branch group is
@@ -1009,13 +1024,14 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
     if sampler not in ('philox', 'replay'):
         raise ValueError("sampler must be 'philox' or 'replay'")
     if joint_shard is not None:
-        joint_shard = _joint_shard_pair(joint_shard, joint)
+        joint_shard = _joint_shard_pair(joint_shard, joint, joint_wide_mixed)
     group, branch_groups = None, []
     if ((joint is not False and joint is not None) or joint_discrete or joint_quantized or joint_wide or joint_branches
-            or joint_branches_mixed):
+            or joint_branches_mixed or joint_wide_mixed):
         group, branch_groups = _joint_plan(table, joint, sampler, precision,
                                            (shard, shard_ids, shard_labels, shard_grid), joint_discrete,
-                                           joint_quantized, joint_wide, joint_branches, joint_branches_mixed)
+                                           joint_quantized, _wide_mode(joint_wide, joint_wide_mixed),
+                                           joint_branches, joint_branches_mixed)
     if sum(a is not None for a in (shard, shard_ids, shard_labels, shard_grid)) > 1:
         raise ValueError('shard, shard_ids, shard_labels and shard_grid are exclusive: one shard axis per suggest')
     if (shard_ids is not None or shard_labels is not None or shard_grid is not None) and sampler == 'replay':
@@ -1034,16 +1050,19 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
 
 TPE_JOINT_MAX_DIMS = N.JOINT_MAX_DIMS
 TPE_JOINT_WIDE_MAX_DIMS = N.JOINT_WIDE_MAX_DIMS
+TPE_JOINT_WIDE_MAX_CAT = N.JOINT_WIDE_MAX_CAT
 
 
-def _joint_shard_pair(joint_shard, joint):
+def _joint_shard_pair(joint_shard, joint, wide_mixed=False):
     """(rank, world) of a ``joint_shard`` argument as ints, or None; ValueError
-    without ``joint`` and for anything but a pair of ints with 0 <= rank <
-    world.  Touches no device."""
+    without ``joint``, with ``joint_wide_mixed`` and for anything but a pair of
+    ints with 0 <= rank < world.  Touches no device."""
     if joint_shard is None:
         return None
     if joint is False or joint is None:
         raise ValueError('joint_shard needs joint=True or joint=[labels]: it only shards the joint stages')
+    if wide_mixed:
+        raise ValueError('joint_wide_mixed=True does not combine with joint_shard: the wide mixed stage is not sharded')
     ok = isinstance(joint_shard, (tuple, list)) and len(joint_shard) == 2 and \
         all(isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) for v in joint_shard)
     if not ok or not 0 <= joint_shard[0] < joint_shard[1]:
@@ -1102,10 +1121,26 @@ class _JointParts(object):
         return _joint.combine_records(stacked)
 
 
+WIDE_MIXED = 'mixed'
+
+
+def _wide_mode(joint_wide, joint_wide_mixed):
+    """The ``wide`` argument of _joint_plan and what it calls: ``joint_wide``
+    as given, or WIDE_MIXED where ``joint_wide_mixed`` also admits discrete
+    labels to the wide groups; ValueError for that keyword without
+    ``joint_wide``."""
+    if not joint_wide_mixed:
+        return joint_wide
+    if not joint_wide:
+        raise ValueError('joint_wide_mixed=True needs joint_wide=True: it only widens the wide groups')
+    return WIDE_MIXED
+
+
 def _joint_group(table, joint, sampler, precision, shards, discrete=False, quantized=False, wide=False):
     """The ParamRows a ``joint`` argument joins, in table order (``discrete`` /
     ``quantized``: the eligible discrete / quantised labels among them;
-    ``wide``: more than TPE_JOINT_MAX_DIMS continuous labels allowed);
+    ``wide``: more than TPE_JOINT_MAX_DIMS continuous labels allowed, as
+    WIDE_MIXED up to TPE_JOINT_WIDE_MAX_CAT discrete ones among them);
     ValueError for every combination the joint stage does not take.  Touches no
     device."""
     _joint_restrictions(joint, sampler, precision, shards, discrete, quantized, wide)
@@ -1117,8 +1152,12 @@ def _joint_group(table, joint, sampler, precision, shards, discrete=False, quant
 
 def _joint_restrictions(joint, sampler, precision, shards, discrete=False, quantized=False, wide=False,
                         branches=False, branch_mixed=False):
-    """ValueError for a keyword without ``joint`` and for the sampler, precision
-    and shard arguments the joint stage does not combine with."""
+    """ValueError for a keyword without ``joint`` (or without the keywords it
+    widens) and for the sampler, precision and shard arguments the joint stage
+    does not combine with."""
+    if wide == WIDE_MIXED and not discrete:
+        raise ValueError('joint_wide_mixed=True needs joint_discrete=True: it only admits the discrete labels that '
+                         'keyword joins to the wide groups')
     if branch_mixed and not branches:
         raise ValueError('joint_branches_mixed=True needs joint_branches=True: it only widens the branch groups')
     if branches and (joint is False or joint is None):
@@ -1169,7 +1208,8 @@ def _joint_rows(table, joint, discrete=False, quantized=False):
 
 def _joint_limits(rows, wide=False):
     """``rows`` (at least 2), or ValueError where the group exceeds what one
-    joint stage takes."""
+    joint stage takes (``wide`` = WIDE_MIXED: a wide group may hold 1 to
+    TPE_JOINT_WIDE_MAX_CAT discrete labels)."""
     if len(rows) > TPE_JOINT_MAX_DIMS:
         if not wide:
             raise ValueError('joint joins at most TPE_JOINT_MAX_DIMS = %d labels, not %d: pass the labels to join as '
@@ -1179,6 +1219,21 @@ def _joint_limits(rows, wide=False):
                              'pass the labels to join as joint=[...]' % (TPE_JOINT_WIDE_MAX_DIMS, len(rows)))
         n_disc = sum(1 for r in rows if r.categorical)
         n_quant = sum(1 for r in rows if r.dist in _joint.QUANT_DISTS)
+        if wide == WIDE_MIXED:
+            head = 'joint with joint_wide_mixed=True: a group of more than TPE_JOINT_MAX_DIMS = %d labels joins ' \
+                % TPE_JOINT_MAX_DIMS
+            tail = ' among its %d: pass the labels to join as joint=[...]' % len(rows)
+            n_cats = sum(int(r.args['upper']) for r in rows if r.categorical)
+            if n_quant:
+                raise ValueError('%sno quantised label, not %d quantised and %d discrete ones%s'
+                                 % (head, n_quant, n_disc, tail))
+            if n_disc > TPE_JOINT_WIDE_MAX_CAT:
+                raise ValueError('%sat most TPE_JOINT_WIDE_MAX_CAT = %d discrete labels, not %d%s'
+                                 % (head, TPE_JOINT_WIDE_MAX_CAT, n_disc, tail))
+            if n_cats > N.JOINT_MAX_CAT_TOTAL:
+                raise ValueError('%sdiscrete labels of at most TPE_JOINT_MAX_CAT_TOTAL = %d categories in all, not %d%s'
+                                 % (head, N.JOINT_MAX_CAT_TOTAL, n_cats, tail))
+            return rows
         if n_disc or n_quant:
             raise ValueError('joint with joint_wide=True: a group of more than TPE_JOINT_MAX_DIMS = %d labels joins '
                              'continuous labels only, not %d discrete and %d quantised ones among its %d: pass the '
@@ -1296,6 +1351,7 @@ def _joint_plan(table, joint, sampler, precision, shards, discrete=False, quanti
     first label.  ``branch_mixed``: ``discrete`` / ``quantized`` also admit
     conditional discrete / quantised labels with exactly one parent to the
     group of their condition (_branch_mixed_reason, _branch_mixed_limit).
+    ``wide`` (_wide_mode) widens the root group only (_joint_limits).
     ValueError as _joint_group; touches no device."""
     if not branches:
         if branch_mixed:
@@ -1368,8 +1424,10 @@ def _run_root_group(engine, group, hist, ids, seed, prior_weight, n_EI_candidate
         group = [r for r in group if not r.categorical] + drows
         model = _joint.fit_mixed_model(group[:len(group) - len(drows)], drows, hist,
                                        _history.split_below(hist, gamma), prior_weight, DEFAULT_LF)
-        out = engine.run_joint_mixed(model.below[:3], model.above[:3], model.low, model.high, model.cats(), ids,
-                                     int(n_EI_candidates), seed, **kw)
+        # more than TPE_JOINT_MAX_DIMS labels (joint_wide_mixed=True let them through): the wide mixed stage
+        run = engine.run_joint_wide_mixed if len(group) > TPE_JOINT_MAX_DIMS else engine.run_joint_mixed
+        out = run(model.below[:3], model.above[:3], model.low, model.high, model.cats(), ids, int(n_EI_candidates),
+                  seed, **kw)
     else:
         model = _joint.fit_model(group, hist, _history.split_below(hist, gamma), prior_weight, DEFAULT_LF)
         # more than TPE_JOINT_MAX_DIMS labels (joint_wide=True let them through): the wide stage
@@ -1776,14 +1834,16 @@ def _joint_group_report(rows, condition, model, top, z, n_top, stats):
 def joint_candidate_report_columns(table, hist, new_id, seed, k=8, joint=True, joint_discrete=False,
                                    joint_quantized=False, joint_wide=False, joint_branches=False,
                                    prior_weight=_default_prior_weight, n_EI_candidates=_default_n_EI_candidates,
-                                   gamma=_default_gamma, device=None, joint_branches_mixed=False):
+                                   gamma=_default_gamma, device=None, joint_branches_mixed=False,
+                                   joint_wide_mixed=False):
     """``joint_candidate_report`` on a structure-of-arrays history (as
     ``candidate_report_columns`` is to ``candidate_report``)."""
     k = _report_check_k(k)
     if joint is False or joint is None:
         raise ValueError('joint_candidate_report needs joint=True or joint=[labels]')
     group, branch_groups = _joint_plan(table, joint, 'philox', 'fp32', (None, None, None, None), joint_discrete,
-                                       joint_quantized, joint_wide, joint_branches, joint_branches_mixed)
+                                       joint_quantized, _wide_mode(joint_wide, joint_wide_mixed), joint_branches,
+                                       joint_branches_mixed)
     if len(hist) == 0:
         raise ValueError('joint_candidate_report needs a history: no completed trial to fit the models from')
     C = int(n_EI_candidates)
@@ -1818,7 +1878,7 @@ def joint_candidate_report_columns(table, hist, new_id, seed, k=8, joint=True, j
 def joint_candidate_report(new_id, domain, trials, seed, k=8, joint=True, joint_discrete=False, joint_quantized=False,
                            joint_wide=False, joint_branches=False, prior_weight=_default_prior_weight,
                            n_EI_candidates=_default_n_EI_candidates, gamma=_default_gamma, device=None,
-                           joint_branches_mixed=False):
+                           joint_branches_mixed=False, joint_wide_mixed=False):
     """The candidate pools behind the joint stages of a ``suggest([new_id],
     domain, trials, seed, joint=..., n_EI_candidates=...)`` with the same joint
     keywords: per joint group the ``k`` best distinct candidate vectors with
@@ -1833,13 +1893,14 @@ def joint_candidate_report(new_id, domain, trials, seed, k=8, joint=True, joint_
     k = _report_check_k(k)
     if joint is not False and joint is not None:
         _joint_plan(domain.table, joint, 'philox', 'fp32', (None, None, None, None), joint_discrete, joint_quantized,
-                    joint_wide, joint_branches, joint_branches_mixed)   # (argument errors before the history is read)
+                    _wide_mode(joint_wide, joint_wide_mixed), joint_branches,
+                    joint_branches_mixed)                    # (argument errors before the history is read)
     hist = _history.extract(domain, trials)
     return joint_candidate_report_columns(domain.table, hist, new_id, seed, k=k, joint=joint,
                                           joint_discrete=joint_discrete, joint_quantized=joint_quantized,
                                           joint_wide=joint_wide, joint_branches=joint_branches,
                                           joint_branches_mixed=joint_branches_mixed, prior_weight=prior_weight, n_EI_candidates=n_EI_candidates, gamma=gamma,
-                                          device=device)
+                                          device=device, joint_wide_mixed=joint_wide_mixed)
 
 
 def suggest_replay(new_ids, domain, trials, seed, **kw):

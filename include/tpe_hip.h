@@ -1220,8 +1220,9 @@ int tpe_joint_wide_run(const tpe_joint_wide_args* args, tpe_joint_wide_record* r
                        double* g_out, void* scratch, uint64_t scratch_bytes, void* stream);
 
 /* Profiling only: while tpe_joint_profile is enabled a sampling
- * tpe_joint_wide_run also times k_joint_wide_sample; this reads that time (ms)
- * of the last such run (it WAITS for it). */
+ * tpe_joint_wide_run (tpe_joint_wide_mixed_run) also times k_joint_wide_sample
+ * (k_joint_wide_mixed_sample); this reads that time (ms) of the last such run
+ * (it WAITS for it). */
 int tpe_joint_wide_profile(double* sample_ms);
 
 /* ------------------------------------------------------------------------
@@ -1293,6 +1294,93 @@ typedef struct tpe_joint_mixed_args {
 /* as tpe_joint_run; cand: device f32 [n_ids * n_cand * (n_dims + n_cat)] */
 int tpe_joint_mixed_run(const tpe_joint_mixed_args* args, tpe_joint_record* records, float* cand, double* l_out,
                         double* g_out, void* scratch, uint64_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Wide mixed joint stage (tpe_joint.hip; additive to ABI 24): a group of n_dims
+ * >= 1 continuous labels and 1 <= n_cat <= TPE_JOINT_WIDE_MAX_CAT discrete ones,
+ * n_dims + n_cat <= TPE_JOINT_WIDE_MAX_DIMS.  Nothing is defined anew:
+ *   model        that of the mixed joint stage above at a larger width: the
+ *                weights, mu, sigma and smoothing masses of a side, P_kd(v) with
+ *                s_d = prior_weight * U_d / (n + 1), in the device form miss_d /
+ *                bonus_d; the prior row carries category -1.  Every table and
+ *                row of tpe_joint_mixed_args means the same here.
+ *   coordinates  the n_dims continuous labels, then the n_cat discrete ones; a
+ *                category travels as its index (f32 in `cand` / `inject` / the
+ *                component rows, double in tpe_joint_wide_record.z).
+ *   streams      word 0 of block 0 picks the component; word 1 + j serves kernel
+ *                coordinate j, that is word (1 + j) & 3 of block (1 + j) >> 2
+ *                (stream_word and the new id as in tpe_joint_run).  A continuous
+ *                coordinate is drawn as tpe_joint_wide_run draws it, a discrete
+ *                one as tpe_joint_mixed_run does: u = u01w(word) in f64, h =
+ *                below_h[d] (0 for a component of category -1), u < h takes the
+ *                component's category, else the first category with (u - h) /
+ *                (1 - h) < cat_cum[cat_off[d] + v].
+ * So the continuous coordinates of a run equal those of a tpe_joint_wide_run
+ * over the continuous part alone (same seed, stream_word and ids), and a run at
+ * n_dims + n_cat <= TPE_JOINT_MAX_DIMS draws the candidates of
+ * tpe_joint_mixed_run, both bit for bit.
+ *
+ * Three launches: k_joint_wide_mixed_sample (skipped under TPE_JOINT_INJECT)
+ * draws one candidate a thread into `scratch`, laid out [256-candidate block]
+ * [j][256] over all n_dims + n_cat coordinates; k_joint_wide_mixed_chunk<DP, KP,
+ * R> (DP the padded n_dims in {12, 16, 20, 24, 32, 48, 64}, KP the padded n_cat
+ * in {1, 2, 4, 8}, R = 2 candidates a lane for DP <= 32 and 1 above) scores a
+ * chunk of 256 R candidates, both sides streaming through LDS in component
+ * tiles of mu[DP], a[DP], cat[KP] and c (under 37 KiB a workgroup); a
+ * discrete slot costs one compare, one select and one add per (candidate,
+ * component), and sum_d miss_d(v_d) is added in f64 after the sum over the
+ * components.  k_joint_wide_merge picks the winner.  No atomics: the same call
+ * twice gives the same bytes.  TPE_JOINT_WIDE_MAX_CAT bounds the set of kernel
+ * instantiations (7 x 4); it is a condition, not a measurement.
+ *
+ * tpe_joint_wide_mixed_args starts with the fields of tpe_joint_wide_args at
+ * the same offsets (low / high beyond n_dims are not read).  n_cat = 0 is
+ * tpe_joint_wide_run on those fields.  Narrow groups are accepted so that the
+ * stage can be compared with tpe_joint_mixed_run.  Returns TPE_E_ARG before any
+ * launch (no device needed), checked in this order, for: null args; n_cat
+ * outside [0, TPE_JOINT_WIDE_MAX_CAT]; n_dims < 1 or n_dims + n_cat >
+ * TPE_JOINT_WIDE_MAX_DIMS; everything tpe_joint_wide_run checks on the shared
+ * fields; a null table; a U_d outside [2, TPE_JOINT_MAX_CATS]; more than
+ * TPE_JOINT_MAX_CAT_TOTAL categories; a cat_off that leaves [0, total - U_d];
+ * scratch smaller than tpe_joint_wide_mixed_scratch_bytes.  As in
+ * tpe_joint_mixed_run an injected category outside its table is the caller's
+ * error.  tpe_joint_run_shard does not take this stage (the kernels' argument
+ * structs carry cand_base, always 0 here).  Advances the resident-level epoch
+ * as the other stage runs do; tpe_joint_profile and tpe_joint_wide_profile (the
+ * sampling kernel) serve it as they serve tpe_joint_wide_run.
+ * ---------------------------------------------------------------------- */
+#define TPE_JOINT_WIDE_MAX_CAT 8        /* discrete labels of a wide group */
+typedef struct tpe_joint_wide_mixed_args {
+  int32_t n_dims, n_cand, n_ids, flags;   /* as tpe_joint_wide_args; n_dims: the continuous labels */
+  int32_t k_below, k_above;
+  uint32_t stream_word;
+  int32_t reserved;
+  uint64_t seed;
+  const float *below_mu, *below_a, *below_c;
+  const float *above_mu, *above_a, *above_c;
+  double below_base, above_base;
+  const double* samp_cum;
+  const float* samp;
+  const int64_t* ids;
+  const float* inject;                    /* device [n_cand * (n_dims + n_cat)] */
+  double low[TPE_JOINT_WIDE_MAX_DIMS], high[TPE_JOINT_WIDE_MAX_DIMS];
+  int32_t n_cat;                          /* the discrete labels */
+  int32_t cat_upper[TPE_JOINT_WIDE_MAX_CAT];  /* U_d */
+  int32_t cat_off[TPE_JOINT_WIDE_MAX_CAT];    /* start of dimension d in the flat tables */
+  const float *below_cat, *above_cat;     /* device [K * n_cat] */
+  const float *below_miss, *below_bonus;  /* device [total] */
+  const float *above_miss, *above_bonus;
+  const double* below_h;                  /* device [n_cat] */
+  const double* cat_cum;                  /* device [total] */
+} tpe_joint_wide_mixed_args;
+
+/* the chunk records and the candidate block of one tpe_joint_wide_mixed_run
+ * (n_cat = 0: tpe_joint_wide_scratch_bytes) */
+int tpe_joint_wide_mixed_scratch_bytes(int32_t n_ids, int32_t n_cand, int32_t n_dims, int32_t n_cat, uint64_t* bytes);
+
+/* as tpe_joint_wide_run; cand: device f32 [n_ids * n_cand * (n_dims + n_cat)] */
+int tpe_joint_wide_mixed_run(const tpe_joint_wide_mixed_args* args, tpe_joint_wide_record* records, float* cand,
+                             double* l_out, double* g_out, void* scratch, uint64_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
  * Quantised joint stage (tpe_joint.hip; additive to ABI 24): a group that also

@@ -1,6 +1,6 @@
 """Time the joint TPE stage against the host route.
 Usage: python tools/joint_time.py [--pairs 3] [--warmup 1] [--cand 1048576] [--history 10000]
-                                  [--host-cand N] [--out FILE] [--mixed | --quant | --wide]
+                                  [--host-cand N] [--out FILE] [--mixed | --quant | --wide | --wide-mixed]
 
 Workload: a flat space of 4 continuous labels (uniform, loguniform, normal,
 uniform), a seeded 10,000-trial history whose loss has an x0 * x1 term, one
@@ -56,7 +56,21 @@ second of the chunk kernel and their ratio to the yardstick's; the worst l / g
 error of the first --host-cand (default 1024) sampled vectors at D = 64 as a
 fraction of the lpdf tolerance; and the host route at D = 20: joint.lpdf_numpy on
 both sides of those --host-cand vectors, measured and scaled linearly to C.
---out defaults to profiles/joint_wide_time.jsonl."""
+--out defaults to profiles/joint_wide_time.jsonl.
+
+--wide-mixed: the wide mixed stage (DESIGN.md "Discrete labels in wide groups").
+Flat spaces of Dc labels of hp.uniform(-5, 5) and Dk labels of hp.choice of 4,
+the same history size.  Per round, alternating in one process: Engine.run_joint_wide
+at D = 20 and Engine.run_joint_wide_mixed at 18 + 2; run_joint_wide at D = 32 and
+run_joint_wide_mixed at 28 + 4 (the yardsticks: k_joint_wide_chunk at the same
+number of coordinates); Engine.run_joint_mixed and run_joint_wide_mixed on one
+8 + 4 group (the yardstick: k_joint_mixed_chunk<8, 4>).  Each chunk kernel by its
+own events, the sampling kernels by theirs.  The line carries per run the
+medians and ranges, the chunk kernel's time per (candidate x component x
+coordinate) evaluation and its ratio to the yardstick's, and for the new stage
+the worst l / g error of the first --host-cand (default 1024) sampled vectors as
+a fraction of the lpdf tolerance.  --out defaults to
+profiles/joint_wide_mixed_time.jsonl."""
 import argparse
 import ctypes
 import json
@@ -390,6 +404,136 @@ def main_wide(args):
     return 0
 
 
+def make_flat_mixed_history(n, Dc, Dk):
+    """make_flat_history's Dc continuous labels with Dk labels of hp.choice of 4;
+    the loss also couples x00 with the first choice."""
+    from hyperopt_amd import base, history as H, hp
+    labels = ['x%02d' % i for i in range(Dc)]
+    clabels = ['c%02d' % i for i in range(Dk)]
+    space = {k: hp.uniform(k, -5, 5) for k in labels}
+    space.update({k: hp.choice(k, [0, 1, 2, 3]) for k in clabels})
+    domain = base.Domain(lambda d: 0.0, space)
+    rs = np.random.RandomState(SEED + 100 * Dc + Dk)
+    X = rs.uniform(-5, 5, (n, Dc))
+    XC = rs.randint(4, size=(n, Dk)).astype(np.int64)
+    loss = ((X - np.linspace(-2, 2, Dc)[None, :]) ** 2).sum(axis=1) + X[:, 0] * X[:, 1] \
+        + (X[:, 0] - (2.0 * XC[:, 0] - 3.0)) ** 2 + 0.1 * XC[:, 1:].sum(axis=1) + 0.01 * rs.standard_normal(n)
+    tids = np.arange(n, dtype=np.int64)
+    obs = {k: (tids, X[:, i]) for i, k in enumerate(labels)}
+    obs.update({k: (tids, XC[:, i]) for i, k in enumerate(clabels)})
+    return domain, H.History(tids, loss, obs)
+
+
+def main_wide_mixed(args):
+    import torch
+    from hyperopt_amd import _native as N, history as H, joint as J
+    from hyperopt_amd.engine import get_engine
+
+    eng = get_engine(None, 'fp32')
+    lib = eng.lib
+    C = args.cand
+    ids = np.array([args.history], dtype=np.int64)
+    wide, mixed = {}, {}
+    for D in (20, 32):
+        domain, hist = make_flat_history(args.history, D)
+        wide[D] = J.fit_model(list(domain.table.rows), hist, H.split_below(hist, 0.25), 1.0)
+    for Dc, Dk in ((18, 2), (28, 4), (8, 4)):
+        domain, hist = make_flat_mixed_history(args.history, Dc, Dk)
+        t = domain.table
+        crows = [r for r in t.rows if J.eligible(r)]
+        drows = [r for r in t.rows if J.eligible_discrete(r, t)]
+        assert (len(crows), len(drows)) == (Dc, Dk)
+        mixed[Dc, Dk] = J.fit_mixed_model(crows, drows, hist, H.split_below(hist, 0.25), 1.0)
+
+    def run_wide(D, **kw):
+        m = wide[D]
+        return eng.run_joint_wide(m.below, m.above, m.low, m.high, ids, C, SEED, **kw)
+
+    def run_mixed(key, narrow=False, **kw):
+        m = mixed[key]
+        fn = eng.run_joint_mixed if narrow else eng.run_joint_wide_mixed
+        return fn(m.below[:3], m.above[:3], m.low, m.high, m.cats(), ids, C, SEED, **kw)
+
+    # (name, the call, whether a sampling kernel of its own runs, coordinates, the model, the kernel, its yardstick)
+    routes = [
+        ('wide20', lambda **kw: run_wide(20, **kw), True, 20, wide[20], 'k_joint_wide_chunk<20, 2>', None),
+        ('wide_mixed_18_2', lambda **kw: run_mixed((18, 2), **kw), True, 20, mixed[18, 2],
+         'k_joint_wide_mixed_chunk<20, 2, 2>', 'wide20'),
+        ('wide32', lambda **kw: run_wide(32, **kw), True, 32, wide[32], 'k_joint_wide_chunk<32, 2>', None),
+        ('wide_mixed_28_4', lambda **kw: run_mixed((28, 4), **kw), True, 32, mixed[28, 4],
+         'k_joint_wide_mixed_chunk<32, 4, 2>', 'wide32'),
+        ('mixed_8_4', lambda **kw: run_mixed((8, 4), narrow=True, **kw), False, 12, mixed[8, 4],
+         'k_joint_mixed_chunk<8, 4>', None),
+        ('wide_mixed_8_4', lambda **kw: run_mixed((8, 4), **kw), True, 12, mixed[8, 4],
+         'k_joint_wide_mixed_chunk<12, 4, 2>', 'mixed_8_4'),
+    ]
+
+    def kernel_ms(fn, sampled):
+        ms2, sms = (ctypes.c_double * 2)(), ctypes.c_double(0.0)
+        torch.cuda.synchronize()
+        N.check(lib.tpe_joint_profile(1, None), lib, 'tpe_joint_profile')
+        fn()
+        if sampled:
+            N.check(lib.tpe_joint_wide_profile(ctypes.byref(sms)), lib, 'tpe_joint_wide_profile')
+        N.check(lib.tpe_joint_profile(0, ms2), lib, 'tpe_joint_profile')
+        return ms2[0], ms2[1], sms.value
+
+    for _ in range(args.warmup):
+        for r in routes:
+            r[1]()
+    ms = dict((r[0], []) for r in routes)
+    for i in range(args.pairs):
+        for r in routes:
+            ms[r[0]].append(kernel_ms(r[1], r[2]))
+        print('round %d: %s' % (i, ', '.join('%s %.3f ms' % (r[0], ms[r[0]][-1][0]) for r in routes)), file=sys.stderr,
+              flush=True)
+
+    # (untimed) l and g of the first --host-cand sampled vectors of the new stage against the float64 model
+    n_host = min(C, args.host_cand or 1024)
+    err = {}
+    for r in routes:
+        if not r[0].startswith('wide_mixed'):
+            continue
+        m = r[4]
+        Dc = len(m.rows)
+        _, cand, dl, dg = r[1](return_cand=True, want_lg=True)
+        z, v = cand[0, :n_host, :Dc].astype(np.float64), cand[0, :n_host, Dc:].astype(np.int64)
+        e = 0.0
+        for side, s, dev in ((m.below, m.s_below, dl), (m.above, m.s_above, dg)):
+            ref = J.mixed_lpdf_numpy(z, v, side[0], side[1], side[2], m.low, m.high, side[3], m.ps, s)
+            e = max(e, float(np.max(np.abs(dev[0, :n_host] - ref) / np.maximum(1.0, np.abs(ref)))) / 1e-5)
+        err[r[0]] = e
+
+    def stat(name, j=0):
+        x = [q[j] for q in ms[name]]
+        return dict(median=float(np.median(x)), min=min(x), max=max(x), all=x)
+
+    def per_eval_ps(r):
+        """picoseconds of chunk-kernel time per (candidate x component x coordinate) evaluation"""
+        m = r[4]
+        return stat(r[0])['median'] * 1e9 / (float(C) * (len(m.below[0]) + len(m.above[0])) * r[3])
+    by_name = dict((r[0], r) for r in routes)
+    runs = {}
+    for r in routes:
+        m = r[4]
+        yard = by_name.get(r[6])
+        runs[r[0]] = dict(kernel=r[5], coordinates=r[3], n_cat=len(getattr(m, 'drows', ())),
+                          k_below=len(m.below[0]), k_above=len(m.above[0]), chunk_ms=stat(r[0]),
+                          merge_ms=stat(r[0], 1)['median'], sample_ms=stat(r[0], 2) if r[2] else None,
+                          ps_per_eval=per_eval_ps(r), yardstick=r[6],
+                          ratio_to_yardstick=per_eval_ps(r) / per_eval_ps(yard) if yard else None,
+                          lpdf_err_over_tol=err.get(r[0]))
+    line = dict(tool='joint_time --wide-mixed', history=args.history, n_cand=C, rounds=args.pairs, runs=runs,
+                host_cand=n_host, gpu=torch.cuda.get_device_name(0))
+    text = json.dumps(line)
+    print(text)
+    out = args.out or os.path.join(ROOT, 'profiles', 'joint_wide_mixed_time.jsonl')
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, 'a') as f:
+        f.write(text + '\n')
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--pairs', type=int, default=3)
@@ -400,6 +544,7 @@ def main():
     ap.add_argument('--mixed', action='store_true')
     ap.add_argument('--quant', action='store_true')
     ap.add_argument('--wide', action='store_true')
+    ap.add_argument('--wide-mixed', action='store_true')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     if args.mixed:
@@ -408,6 +553,8 @@ def main():
         return main_quant(args)
     if args.wide:
         return main_wide(args)
+    if args.wide_mixed:
+        return main_wide_mixed(args)
     args.out = args.out or os.path.join(ROOT, 'profiles', 'joint_time.jsonl')
 
     import torch
