@@ -299,6 +299,23 @@ class JointReportArgs(ctypes.Structure):
     ]
 
 
+JOINT_LIAR_TILE = 32   # TPE_JOINT_LIAR_TILE
+JOINT_PICK_DTYPE = np.dtype([('idx', '<i8'), ('l', '<f8'), ('g', '<f8')])
+assert JOINT_PICK_DTYPE.itemsize == 24
+
+
+class JointLiarArgs(ctypes.Structure):
+    """tpe_joint_liar_args: one tpe_joint_liar."""
+    _fields_ = [
+        ('n_dims', ctypes.c_int32), ('n_cand', ctypes.c_int32), ('n_ids', ctypes.c_int32), ('n_given', ctypes.c_int32),
+        ('k_above', ctypes.c_int32), ('n_trials', ctypes.c_int32),
+        ('w_sum', ctypes.c_double),
+        ('cand', ctypes.c_void_p), ('l_out', ctypes.c_void_p), ('g_out', ctypes.c_void_p),
+        ('above_mu', ctypes.c_void_p), ('given', ctypes.c_void_p),
+        ('psig', ctypes.c_double * 64), ('low', ctypes.c_double * 64), ('high', ctypes.c_double * 64),
+    ]
+
+
 class LabelIn(ctypes.Structure):
     _fields_ = [
         ('family', ctypes.c_int32), ('flags', ctypes.c_int32), ('upper', ctypes.c_int32),
@@ -447,7 +464,8 @@ EXPORTS = ('tpe_abi_version', 'tpe_last_error', 'tpe_device_count', 'tpe_tile_si
            'tpe_joint_wide_mixed_scratch_bytes', 'tpe_joint_wide_mixed_run',
            'tpe_joint_seg_scratch_bytes', 'tpe_joint_seg_run', 'tpe_joint_mseg_scratch_bytes',
            'tpe_joint_mseg_table_bytes', 'tpe_joint_mseg_run', 'tpe_joint_report_scratch_bytes',
-           'tpe_joint_report', 'tpe_joint_report_profile', 'tpe_joint_run_shard')
+           'tpe_joint_report', 'tpe_joint_report_profile', 'tpe_joint_run_shard', 'tpe_joint_liar_scratch_bytes',
+           'tpe_joint_liar')
 
 # host phases of tpe_suggest_tree (tpe_host_phases order)
 PHASES = ('prefit', 'pack', 'launched', 'synced', 'level', 'return', 'recs')
@@ -600,6 +618,10 @@ def load(path=LIB_PATH):
     lib.tpe_joint_report.restype = ctypes.c_int
     lib.tpe_joint_report_profile.argtypes = [I32, P]
     lib.tpe_joint_report_profile.restype = ctypes.c_int
+    lib.tpe_joint_liar_scratch_bytes.argtypes = [I32, I32, I32, I32, ctypes.POINTER(ctypes.c_uint64)]
+    lib.tpe_joint_liar_scratch_bytes.restype = ctypes.c_int
+    lib.tpe_joint_liar.argtypes = [ctypes.POINTER(JointLiarArgs), P, P, P, P, ctypes.c_uint64, P]
+    lib.tpe_joint_liar.restype = ctypes.c_int
     lib.tpe_joint_profile.argtypes = [I32, P]
     lib.tpe_joint_profile.restype = ctypes.c_int
     lib.tpe_level_profile.argtypes = [ctypes.c_int32]

@@ -979,7 +979,7 @@ class Engine(object):
         return d_top, d_ntop, d_stats
 
     def run_joint(self, below, above, low, high, ids, n_cand, seed, inject=None, return_cand=False, want_lg=False,
-                  report_k=0, shard=None, stream_word=None):
+                  report_k=0, shard=None, stream_word=None, liar=False, given=None, return_sigma=False):
         """One joint TPE stage (tpe_joint_run, include/tpe_hip.h "Joint
         (multivariate) TPE stage"): ``below`` / ``above`` = (w [K], mu [K, D],
         sigma [K, D]) float64 mixtures (joint.side_mixture), ``low`` / ``high``
@@ -1007,26 +1007,61 @@ class Engine(object):
         ``inject`` with a non-zero cand_base raise ValueError.
         ``stream_word`` (every solo run_joint* method): the Philox stream word
         (None: N.JOINT_STREAM; a branch group's joint.branch_stream_word, to
-        compare with run_joint_segments)."""
+        compare with run_joint_segments).
+        ``liar`` (run_joint and run_joint_wide; DESIGN.md "Batch-aware joint
+        suggests", the model in joint.py): the ids pick greedily in the order
+        given.  The stage keeps its three buffers on the device and
+        tpe_joint_liar follows on the same stream; record j then holds pick j's
+        index, l, g_j (the above density extended by the ``given`` vectors
+        [G, D] and the picks before it, each counted as one more bad trial) and
+        z.  ``want_lg`` still returns the base l and g.  True takes the above
+        side's un-normalised weight sum W as 1 / w[-1] (the newest trial weighs
+        1; a side without trials: 1), a float is W itself
+        (joint.side_weight_sum).  ``return_sigma``: also, last, the liars'
+        bandwidths float64 [G + n_ids, D].  ``liar`` with ``shard`` or
+        ``report_k`` > 0, and ``given`` or ``return_sigma`` without ``liar``,
+        raise ValueError."""
         return self._joint_continuous(False, below, above, low, high, ids, n_cand, seed, inject, return_cand, want_lg,
-                                      stream_word, report_k, shard)
+                                      stream_word, report_k, shard, self._liar(liar, given, return_sigma, report_k,
+                                                                               shard))
 
     def run_joint_wide(self, below, above, low, high, ids, n_cand, seed, inject=None, return_cand=False,
-                       want_lg=False, report_k=0, shard=None, stream_word=None):
+                       want_lg=False, report_k=0, shard=None, stream_word=None, liar=False, given=None,
+                       return_sigma=False):
         """``run_joint`` for up to N.JOINT_WIDE_MAX_DIMS dimensions
         (tpe_joint_wide_run, include/tpe_hip.h "Wide joint stage"): the same
         arguments, model, Philox streams and return shapes; the records are
         N.JOINT_WIDE_RECORD_DTYPE."""
         return self._joint_continuous(True, below, above, low, high, ids, n_cand, seed, inject, return_cand, want_lg,
-                                      stream_word, report_k, shard)
+                                      stream_word, report_k, shard, self._liar(liar, given, return_sigma, report_k,
+                                                                               shard))
+
+    @staticmethod
+    def _liar(liar, given, return_sigma, report_k, shard):
+        """The ``liar`` / ``given`` / ``return_sigma`` arguments of run_joint as
+        one dict (None: no liar stage); their ValueErrors.  Touches no device."""
+        if liar is False or liar is None:
+            if given is not None or return_sigma:
+                raise ValueError('joint stage: given and return_sigma need liar')
+            return None
+        if shard is not None:
+            raise ValueError('joint stage: liar does not combine with shard')
+        if int(report_k) > 0:
+            raise ValueError('joint stage: liar does not combine with report_k')
+        W = None
+        if not isinstance(liar, (bool, np.bool_)):
+            W = float(liar)
+            if not (W > 0 and np.isfinite(W)):
+                raise ValueError('joint stage: liar must be True or the positive weight sum W: %r' % (liar,))
+        return {'W': W, 'given': given, 'sigma': bool(return_sigma)}
 
     def _joint_continuous(self, wide, below, above, low, high, ids, n_cand, seed, inject, return_cand, want_lg,
-                          stream_word=None, report_k=0, shard=None):
+                          stream_word=None, report_k=0, shard=None, liar=None):
         """``run_joint`` (``wide``: ``run_joint_wide``) with the arguments in
         the order this entry has always had; callers that reach past the two
         public methods keep working."""
         return self._joint_solo('wide' if wide else 'run', below, above, low, high, (), (), ids, n_cand, seed, inject,
-                                return_cand, want_lg, report_k, stream_word, shard)
+                                return_cand, want_lg, report_k, stream_word, shard, liar=liar)
 
     # the solo stages by joint_pack entry: the args struct and the native function
     _JOINT_SOLO = {'run': (N.JointArgs, 'tpe_joint_run'), 'wide': (N.JointWideArgs, 'tpe_joint_wide_run'),
@@ -1035,7 +1070,7 @@ class Engine(object):
                    'quant': (N.JointQuantArgs, 'tpe_joint_quant_run')}
 
     def _joint_solo(self, entry, below, above, low, high, cats, quants, ids, n_cand, seed, inject, return_cand,
-                    want_lg, report_k, stream_word, shard, return_table=False):
+                    want_lg, report_k, stream_word, shard, return_table=False, liar=None):
         """What the five solo stages share: the group's rows (joint_pack.group_rows,
         which also checks the group; an empty part of a sharded stage is checked
         too), one upload per row, the args struct filled from the same rows
@@ -1047,6 +1082,8 @@ class Engine(object):
         D, wide = Dc + Dk + Dq, entry in ('wide', 'wide_mixed')
         ids, n_ids, C = self._joint_sizes(D, ids, n_cand, shard)
         shard = self._joint_shard(shard, C, report_k, inject)
+        if liar is not None:
+            liar = self._liar_model(liar, entry, above, r, D)
         if C == 0:
             if return_table:
                 raise ValueError('joint stage: return_table needs at least one candidate')
@@ -1085,13 +1122,30 @@ class Engine(object):
             d_tab = self._buf('joint_qtable', (nb.value + 3) // 4, torch.float32)
             a.quant_table, a.quant_table_bytes = d_tab.data_ptr(), d_tab.numel() * 4
         out = self._joint_call(fn, a, n_ids, C, D, return_cand, want_lg, wide=wide, report_k=report_k, shard=shard,
-                               n_cat=Dk if wide else 0)
+                               n_cat=Dk if wide else 0, liar=liar)
         if not return_table:
             return out
         tab = d_tab[:(a.k_below + a.k_above) * total].cpu().numpy()
         tb = tab[:total * a.k_below].reshape(total, a.k_below).T.copy()
         ta = tab[total * a.k_below:].reshape(total, a.k_above).T.copy()
         return (out if isinstance(out, tuple) else (out,)) + (tb, ta)
+
+    @staticmethod
+    def _liar_model(liar, entry, above, r, D):
+        """``liar`` (Engine._liar) completed from the group: W, the prior sigmas,
+        the bounds and the given vectors as f32 [G, D]."""
+        if entry not in ('run', 'wide'):
+            raise ValueError('joint stage: liar needs a group of continuous labels')
+        w, sigma = np.asarray(above[0], dtype=np.float64), np.asarray(above[2], dtype=np.float64).reshape(-1, D)
+        W = liar['W']
+        if W is None:
+            W = 1.0 / float(w[-1]) if len(w) > 1 else 1.0
+        given = np.zeros((0, D), dtype=np.float32)
+        if liar['given'] is not None:
+            given = np.ascontiguousarray(liar['given'], dtype=np.float32)
+            if given.ndim != 2 or given.shape[1] != D:
+                raise ValueError('joint stage: given must be [G, %d]: %r' % (D, given.shape))
+        return {'W': W, 'given': given, 'sigma': liar['sigma'], 'psig': sigma[0], 'low': r['low'], 'high': r['high']}
 
     def _joint_sizes(self, D, ids, n_cand, shard=None):
         ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
@@ -1157,15 +1211,19 @@ class Engine(object):
         t[:arr.size].copy_(torch.from_numpy(np.ascontiguousarray(arr).reshape(-1)))
         return t.data_ptr()
 
-    def _joint_call(self, fn, a, n_ids, C, D, return_cand, want_lg, wide=False, report_k=0, shard=None, n_cat=0):
+    def _joint_call(self, fn, a, n_ids, C, D, return_cand, want_lg, wide=False, report_k=0, shard=None, n_cat=0,
+                    liar=None):
         """Scratch and result buffers, the native call ``fn`` and the records
         (and candidates [n_ids, C, D], l, g [n_ids, C]) on the host.  ``wide``:
         the wide stage's scratch size and record (``n_cat`` > 0: the wide mixed
         stage's, ``n_cat`` of the D coordinates discrete).  ``report_k``: the stage
         writes all three device buffers and the joint report follows.
-        ``shard`` (N.JointShard): the call goes through tpe_joint_run_shard."""
+        ``shard`` (N.JointShard): the call goes through tpe_joint_run_shard.
+        ``liar`` (Engine._liar_model): the stage writes all three device buffers,
+        tpe_joint_liar follows, and the records hold its picks."""
         report_k = self._report_k(report_k)
-        dev_cand, dev_lg = return_cand or report_k > 0, want_lg or report_k > 0
+        keep = report_k > 0 or liar is not None
+        dev_cand, dev_lg = return_cand or keep, want_lg or keep
         nb = ctypes.c_uint64(0)
         rec_dtype = N.JOINT_WIDE_RECORD_DTYPE if wide else N.JOINT_RECORD_DTYPE
         if wide and n_cat:
@@ -1188,8 +1246,15 @@ class Engine(object):
         if report_k:
             rep = self._joint_report(d_cand.data_ptr(), d_l.data_ptr(), d_g.data_ptr(), n_ids, C, report_k, stream,
                                      width=D)
+        if liar is not None:
+            lr = self._joint_liar(a, liar, d_cand.data_ptr(), d_l.data_ptr(), d_g.data_ptr(), n_ids, C, D, stream)
         rec = d_rec[:n_ids * rec_dtype.itemsize // 8].cpu().numpy().view(rec_dtype).copy()
-        if not (return_cand or want_lg or report_k):
+        if liar is not None:
+            d_picks, d_z, d_sig, G = lr
+            picks = d_picks[:n_ids * 3].cpu().numpy().view(N.JOINT_PICK_DTYPE)
+            rec['global_idx'], rec['l'], rec['g'] = picks['idx'], picks['l'], picks['g']
+            rec['z'][:, :D] = d_z[:n_ids * D].cpu().numpy().reshape(n_ids, D)
+        if not (return_cand or want_lg or report_k or (liar is not None and liar['sigma'])):
             return rec
         out = [rec]
         if return_cand:
@@ -1199,7 +1264,35 @@ class Engine(object):
             out.append(d_g[:n_ids * C].cpu().numpy().reshape(n_ids, C).copy())
         if report_k:
             out.extend(self._joint_report_host(rep, n_ids, report_k, D))
+        if liar is not None and liar['sigma']:
+            out.append(d_sig[:(G + n_ids) * D].cpu().numpy().reshape(G + n_ids, D).copy())
         return tuple(out)
+
+    def _joint_liar(self, a, liar, cand, l, g, n_ids, C, D, stream):
+        """Enqueue tpe_joint_liar over the device buffers the continuous joint
+        stage ``a`` just wrote; returns the device tensors (picks, pick_z,
+        liar_sigma) and the number of given liars."""
+        given = liar['given']
+        G = len(given)
+        la = N.JointLiarArgs()
+        la.n_dims, la.n_cand, la.n_ids, la.n_given = D, C, n_ids, G
+        la.k_above, la.n_trials, la.w_sum = a.k_above, a.k_above - 1, liar['W']
+        la.cand, la.l_out, la.g_out, la.above_mu = cand, l, g, a.above_mu
+        if G:
+            la.given = self._joint_up('liar_given', given, torch.float32)
+        for d in range(D):
+            la.psig[d], la.low[d], la.high[d] = liar['psig'][d], liar['low'][d], liar['high'][d]
+        nb = ctypes.c_uint64(0)
+        N.check(self.lib.tpe_joint_liar_scratch_bytes(n_ids, C, D, G, ctypes.byref(nb)), self.lib,
+                'tpe_joint_liar_scratch_bytes')
+        d_scr = self._buf('joint_liar_scratch', (nb.value + 7) // 8, torch.float64)
+        d_picks = self._buf('joint_liar_picks', n_ids * 3, torch.float64)
+        d_z = self._buf('joint_liar_z', n_ids * D, torch.float32)
+        d_sig = self._buf('joint_liar_sigma', (G + n_ids) * D, torch.float64)
+        N.check(self.lib.tpe_joint_liar(ctypes.byref(la), d_picks.data_ptr(), d_z.data_ptr(), d_sig.data_ptr(),
+                                        d_scr.data_ptr(), d_scr.numel() * 8, ctypes.c_void_p(stream)), self.lib,
+                'tpe_joint_liar')
+        return d_picks, d_z, d_sig, G
 
     @staticmethod
     def _report_k(report_k):

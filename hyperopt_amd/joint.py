@@ -656,3 +656,55 @@ def combine_records(stacked):
         better = (better | out_empty) & ~new_empty
         out[better] = new[better]
     return out
+
+
+# ------------------------------------------------- batch-aware joint suggests
+# The ids of one batched call pick greedily (include/tpe_hip.h "Batch-aware
+# joint suggests", DESIGN.md "Batch-aware joint suggests"; continuous groups
+# only).  The above side is side_mixture's: n trial rows and the prior row,
+# un-normalised weights w~ (prior_weight, then the linear-forgetting ramp or 1),
+# W their sum.  Id j (step j, the order given) is scored under the above
+# mixture extended by J = G + j "liars": the G given vectors, then the picks of
+# the ids before it.  Liar i (its ordinal among all liars):
+#   weight  1 un-normalised (the newest trial), so the weights are (w~, 1, .., 1) / (W + J)
+#   mean    z, the f32 coordinates of the pick or given vector
+#   sigma_d the adaptive-Parzen neighbour rule over P_d = the side's K f32 mu
+#           values of dimension d and the z_d of the liars before it: with L =
+#           max{p <= z_d} and U = min{p > z_d}, max(z_d - L, U - z_d) (a missing
+#           side dropped), clipped to [psig_d / min(100, m + 2), psig_d], m = n +
+#           i + 1; float64 on f32 values.
+#   log g_j(z) = logaddexp(log g(z), logsumexp_i log k_i(z) - log W) - log1p(J / W)
+#   log k_i(z) = -sum_d [log(sigma_id sqrt(2 pi) mass_id) + ((z_d - mu_id) / sigma_id)^2 / 2]
+# l is unchanged, score_j = l - g_j, the winner in np.argmax order.  Deviation
+# from B sequential asks: the existing components are not refitted (their
+# bandwidths, the below / above split and the forgetting ramp stay).
+def side_weight_sum(n, prior_weight=1.0, lf=DEFAULT_LF):
+    """W: the sum of the un-normalised weights side_mixture gives n trials."""
+    w = linear_forgetting_weights(n, lf) if (lf and lf < n) else np.ones(n)
+    return float(prior_weight) + float(np.sum(w))
+
+
+def liar_sigmas(points, z, psig, m):
+    """sigma [D] of a liar at the f32 vector ``z``: ``points`` [P, D] f32 the
+    side's mu rows followed by the earlier liars, m = n + i + 1."""
+    pts = np.asarray(points, dtype=np.float32).astype(np.float64)
+    z = np.asarray(z, dtype=np.float32).astype(np.float64)
+    psig = np.asarray(psig, dtype=np.float64)
+    out = np.empty(len(z))
+    for d in range(len(z)):
+        col = pts[:, d]
+        le, gt = col[col <= z[d]], col[col > z[d]]
+        gaps = ([z[d] - le.max()] if len(le) else []) + ([gt.min() - z[d]] if len(gt) else [])
+        out[d] = max(gaps) if gaps else 0.0
+    return np.minimum(np.maximum(out, psig / min(100.0, m + 2.0)), psig)
+
+
+def liar_log_g(z, log_g, liar_mu, liar_sigma, W, low, high):
+    """log g_J at ``z`` [C, D] from the base ``log_g`` [C] and J liars (mu,
+    sigma [J, D]); J = 0: log_g."""
+    J = len(liar_mu)
+    if J == 0:
+        return np.array(log_g, dtype=np.float64)
+    lk = lpdf_numpy(z, np.ones(J), np.asarray(liar_mu, dtype=np.float64), np.asarray(liar_sigma, dtype=np.float64),
+                    low, high)
+    return np.logaddexp(log_g, lk - math.log(W)) - math.log1p(J / W)

@@ -843,18 +843,23 @@ def suggest(new_ids, domain, trials, seed,
             linear_forgetting=_default_linear_forgetting,
             sampler='philox', precision='fp32', device=None, shard=None, shard_ids=None, shard_labels=None,
             shard_grid=None, joint=False, joint_discrete=False, joint_quantized=False, joint_wide=False,
-            joint_branches=False, joint_branches_mixed=False, joint_shard=None, joint_wide_mixed=False):
+            joint_branches=False, joint_branches_mixed=False, joint_shard=None, joint_wide_mixed=False,
+            joint_liar=False):
     new_ids = list(new_ids)
     if not new_ids:
         return []
     if joint_shard is not None:                  # (argument errors first, as below; nothing on the default path)
         _joint_shard_pair(joint_shard, joint, joint_wide_mixed)
+    if joint_liar:
+        _joint_liar_check(joint, joint_shard)
     if ((joint is not False and joint is not None) or joint_discrete or joint_quantized or joint_wide or joint_branches
             or joint_branches_mixed or joint_wide_mixed):
         # (argument errors first: no device use, no startup draw)
-        _joint_plan(domain.table, joint, sampler, precision, (shard, shard_ids, shard_labels, shard_grid),
-                    joint_discrete, joint_quantized, _wide_mode(joint_wide, joint_wide_mixed), joint_branches,
-                    joint_branches_mixed)
+        plan = _joint_plan(domain.table, joint, sampler, precision, (shard, shard_ids, shard_labels, shard_grid),
+                           joint_discrete, joint_quantized, _wide_mode(joint_wide, joint_wide_mixed), joint_branches,
+                           joint_branches_mixed)
+        if joint_liar:
+            _joint_liar_check(joint, joint_shard, plan)
     t0 = time.time()
     hist = _history.extract(domain, trials)
     if logger.isEnabledFor(logging.INFO):
@@ -871,7 +876,7 @@ def suggest(new_ids, domain, trials, seed,
                               shard_labels=shard_labels, shard_grid=shard_grid, joint=joint,
                               joint_discrete=joint_discrete, joint_quantized=joint_quantized, joint_wide=joint_wide,
                               joint_branches=joint_branches, joint_branches_mixed=joint_branches_mixed,
-                              joint_shard=joint_shard, joint_wide_mixed=joint_wide_mixed)
+                              joint_shard=joint_shard, joint_wide_mixed=joint_wide_mixed, joint_liar=joint_liar)
     logger.info('tpe.suggest took %f seconds', time.time() - t0)
     return rand.docs_from_choices(new_ids, domain, trials, choices)
 
@@ -913,7 +918,7 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
                     sampler='philox', precision='fp32', device=None, shard=None, columns=False,
                     shard_ids=None, shard_labels=None, shard_grid=None, joint=False, joint_discrete=False,
                     joint_quantized=False, joint_wide=False, joint_branches=False, joint_branches_mixed=False,
-                    joint_shard=None, joint_wide_mixed=False):
+                    joint_shard=None, joint_wide_mixed=False, joint_liar=False):
     """The suggest core on a structure-of-arrays history (``history.History``):
     per new id a {label: value or None} dict.  ``suggest`` wraps it with the
     Trials document layout; columnar callers (and bench.py's large configs)
@@ -1020,11 +1025,25 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
     winner records (joint.combine_records).  Every rank returns the whole
     result, byte for byte that of the same call without the keyword.
     n_EI_candidates < 2^31.  It does not combine with the four ``shard*``
-    arguments, and joint_candidate_report does not take it."""
+    arguments, and joint_candidate_report does not take it.
+
+    ``joint_liar=True`` (with ``joint``; the root group continuous, at most 16
+    labels or, with ``joint_wide``, 17 to 64): the ids of one call pick the
+    group's vector greedily, in the order given (DESIGN.md "Batch-aware joint
+    suggests").  Id 0 picks as without the keyword; its vector then counts as
+    one more bad trial of the above mixture (a "liar"), id 1 picks under that,
+    and so on, on the device.  Without it every id of a batch finds the same
+    mode.  Only the group's values change: every other label, and with one id
+    the whole result, is the same bytes as without the keyword.  A root group
+    with a discrete or quantised label, any branch group, ``joint_shard`` and
+    the keyword without ``joint`` raise ValueError; joint_candidate_report does
+    not take it."""
     if sampler not in ('philox', 'replay'):
         raise ValueError("sampler must be 'philox' or 'replay'")
     if joint_shard is not None:
         joint_shard = _joint_shard_pair(joint_shard, joint, joint_wide_mixed)
+    if joint_liar:
+        _joint_liar_check(joint, joint_shard)
     group, branch_groups = None, []
     if ((joint is not False and joint is not None) or joint_discrete or joint_quantized or joint_wide or joint_branches
             or joint_branches_mixed or joint_wide_mixed):
@@ -1032,6 +1051,8 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
                                            (shard, shard_ids, shard_labels, shard_grid), joint_discrete,
                                            joint_quantized, _wide_mode(joint_wide, joint_wide_mixed),
                                            joint_branches, joint_branches_mixed)
+        if joint_liar:
+            _joint_liar_check(joint, joint_shard, (group, branch_groups))
     if sum(a is not None for a in (shard, shard_ids, shard_labels, shard_grid)) > 1:
         raise ValueError('shard, shard_ids, shard_labels and shard_grid are exclusive: one shard axis per suggest')
     if (shard_ids is not None or shard_labels is not None or shard_grid is not None) and sampler == 'replay':
@@ -1043,7 +1064,7 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
                                 columns, shard_ids, shard_labels, shard_grid)
     if group is not None or branch_groups:
         return _suggest_joint(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, device, columns, group,
-                              branch_groups, joint_shard)
+                              branch_groups, joint_shard, bool(joint_liar))
     return _suggest_local(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, sampler, precision,
                           device, shard, columns)
 
@@ -1051,6 +1072,26 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
 TPE_JOINT_MAX_DIMS = N.JOINT_MAX_DIMS
 TPE_JOINT_WIDE_MAX_DIMS = N.JOINT_WIDE_MAX_DIMS
 TPE_JOINT_WIDE_MAX_CAT = N.JOINT_WIDE_MAX_CAT
+
+
+def _joint_liar_check(joint, joint_shard, plan=None):
+    """ValueError where ``joint_liar=True`` does not apply: without ``joint``,
+    with ``joint_shard``, and (``plan`` = _joint_plan's result) for a root group
+    that is missing or holds a discrete or quantised label and for any branch
+    group.  Touches no device."""
+    if joint is False or joint is None:
+        raise ValueError('joint_liar needs joint=True or joint=[labels]: it only changes how the joint stage picks')
+    if joint_shard is not None:
+        raise ValueError('joint_liar=True does not combine with joint_shard')
+    if plan is None:
+        return
+    group, branch_groups = plan
+    if branch_groups:
+        raise ValueError('joint_liar=True does not combine with branch groups (joint_branches)')
+    other = [r.label for r in (group or ()) if r.dist not in _joint.JOINT_DISTS]
+    if group is None or other:
+        raise ValueError('joint_liar=True needs a root group of continuous labels only: %s'
+                         % ('there is no root group' if group is None else '%r is discrete or quantised' % other[0]))
 
 
 def _joint_shard_pair(joint_shard, joint, wide_mixed=False):
@@ -1432,12 +1473,14 @@ def _run_root_group(engine, group, hist, ids, seed, prior_weight, n_EI_candidate
         model = _joint.fit_model(group, hist, _history.split_below(hist, gamma), prior_weight, DEFAULT_LF)
         # more than TPE_JOINT_MAX_DIMS labels (joint_wide=True let them through): the wide stage
         run = engine.run_joint_wide if len(group) > TPE_JOINT_MAX_DIMS else engine.run_joint
+        if kw.pop('liar', False):                # (joint_liar: W of the above side as side_mixture weighs it)
+            kw['liar'] = _joint.side_weight_sum(len(model.above[0]) - 1, prior_weight, DEFAULT_LF)
         out = run(model.below, model.above, model.low, model.high, ids, int(n_EI_candidates), seed, **kw)
     return group, model, out
 
 
 def _suggest_joint(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, device, columns, group,
-                   branch_groups=(), joint_shard=None):
+                   branch_groups=(), joint_shard=None, joint_liar=False):
     """The univariate suggest of every label (the joined labels' univariate
     winners are discarded: each costs one problem of the level's batch, and the
     other labels' values are then the same bytes as without ``joint``), then
@@ -1447,7 +1490,8 @@ def _suggest_joint(table, hist, new_ids, seed, prior_weight, n_EI_candidates, ga
     its columns for those ids only (a joined label gates nothing, so the
     routing is the univariate pass's).  ``joint_shard``: the two joint stages
     run over this rank's candidate range and exchange their records
-    (_JointParts); the univariate pass is replicated."""
+    (_JointParts); the univariate pass is replicated.  ``joint_liar``: the
+    root group's ids pick greedily (Engine.run_joint's ``liar``)."""
     cc = _suggest_local(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, 'philox', 'fp32', device,
                         None, True)
     if len(cc) == 0:
@@ -1468,7 +1512,8 @@ def _suggest_joint(table, hist, new_ids, seed, prior_weight, n_EI_candidates, ga
                             else N.JOINT_RECORD_DTYPE)
         group, model = got[0], got[1]
     elif group is not None:
-        group, model, rec = _run_root_group(engine, group, hist, ids, seed, prior_weight, n_EI_candidates, gamma)
+        group, model, rec = _run_root_group(engine, group, hist, ids, seed, prior_weight, n_EI_candidates, gamma,
+                                            **({'liar': True} if joint_liar else {}))
     if group is not None:
         if (rec['global_idx'] < 0).any():
             raise RuntimeError('no joint candidate selected')

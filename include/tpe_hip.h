@@ -1728,6 +1728,73 @@ int tpe_joint_run_shard(int32_t stage, const void* args, const tpe_joint_shard* 
                         double* l_out, double* g_out, void* scratch, uint64_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Batch-aware joint suggests (tpe_joint_liar.hip; additive exports, the ABI
+ * stays 24).  A follow-up stage of tpe_joint_run / tpe_joint_wide_run, enqueued
+ * after the stage that wrote cand, l_out and g_out (as tpe_joint_report is):
+ * the ids pick greedily, in the order given.  Id 0 picks as the stage itself
+ * does; its vector then joins the above mixture as one more component, a
+ * "liar" (a point not yet evaluated, counted as bad), id 1 picks under that
+ * mixture, and so on.  n_given vectors may be liars before step 0; i is a
+ * liar's ordinal among all liars, the given ones first.
+ *
+ * The above side has n = n_trials trial rows and the prior row (k_above rows of
+ * above_mu, the f32 rows as uploaded), un-normalised weights w~ with W = w_sum
+ * their sum.  Liar i has un-normalised weight 1 and mean mu = z, the f32
+ * coordinates of the pick (or given vector).  Its bandwidth in dimension d is
+ * the adaptive-Parzen neighbour rule over P_d = the k_above values
+ * above_mu[., d] and the z_d of the liars before it: L = max{p in P_d: p <=
+ * z_d}, U = min{p in P_d: p > z_d}, sigma = max(z_d - L, U - z_d) (a missing
+ * side is dropped; none: 0), clipped to [psig_d / min(100, m + 2), psig_d] with
+ * m = n + i + 1: float64 arithmetic on f32 values, so liar_sigma is the same
+ * bits on every IEEE machine.  The existing components keep their bandwidths.
+ *
+ * With J = n_given + j liars, step j scores
+ *   log g_j(z) = logaddexp(log g(z), logsumexp_i log k_i(z) - log W) - log1p(J / W)
+ *   log k_i(z) = - sum_d [ log(sigma_id sqrt(2 pi) mass_id) + ((z_d - mu_id) / sigma_id)^2 / 2 ]
+ * (mass: of the normal truncated to [low_d, high_d), 1 where unbounded), the
+ * liar term in float64; score_j = l - g_j, l and g read from l_out / g_out of
+ * id j; winner in np.argmax order (NaN first, ties to the lower index).  With
+ * J = 0, g_0 = g: pick 0 is the stage's own record.
+ *
+ * Outputs: picks[j] = {candidate index, l, g_j}; pick_z[j * n_dims ..] the
+ * winner's row, copied bit for bit; liar_sigma[i * n_dims ..] for every liar
+ * (the last pick's too).  2 launches a step (a one-workgroup pick kernel, a
+ * chunk kernel over TPE_JOINT_CHUNK candidates a workgroup; liar rows stream
+ * through LDS in tiles of TPE_JOINT_LIAR_TILE), ordered by the stream alone.
+ * No atomics: the same call twice gives the same bytes.
+ *
+ * tpe_joint_liar_scratch_bytes = (n_given + n_ids) (2 n_dims + 1) 8 +
+ * ceil(n_cand / TPE_JOINT_CHUNK) 24.  tpe_joint_liar returns TPE_E_ARG before
+ * any launch (no device needed) for null args, buffers or outputs, n_dims
+ * outside [1, TPE_JOINT_WIDE_MAX_DIMS], n_ids, n_cand or k_above < 1, n_given
+ * or n_trials < 0, n_given > 0 without `given`, w_sum not positive and finite,
+ * a psig that is not positive, or scratch smaller than that.
+ * ---------------------------------------------------------------------- */
+#define TPE_JOINT_LIAR_TILE 32
+typedef struct tpe_joint_pick {
+  int64_t idx;                 /* the winner's candidate index in its id's pool */
+  double l, g;                 /* g: log g_j at the winner */
+} tpe_joint_pick;
+typedef struct tpe_joint_liar_args {
+  int32_t n_dims, n_cand, n_ids, n_given;
+  int32_t k_above, n_trials;
+  double w_sum;
+  const float* cand;           /* device [n_ids * n_cand * n_dims] */
+  const double *l_out, *g_out; /* device [n_ids * n_cand] */
+  const float* above_mu;       /* device [k_above * n_dims] */
+  const float* given;          /* device [n_given * n_dims]; NULL with n_given == 0 */
+  double psig[TPE_JOINT_WIDE_MAX_DIMS];                                    /* the prior sigmas */
+  double low[TPE_JOINT_WIDE_MAX_DIMS], high[TPE_JOINT_WIDE_MAX_DIMS];      /* -inf / +inf: unbounded */
+} tpe_joint_liar_args;
+
+int tpe_joint_liar_scratch_bytes(int32_t n_ids, int32_t n_cand, int32_t n_dims, int32_t n_given, uint64_t* bytes);
+
+/* picks: device [n_ids]; pick_z: device f32 [n_ids * n_dims]; liar_sigma:
+ * device f64 [(n_given + n_ids) * n_dims]; enqueued on `stream` */
+int tpe_joint_liar(const tpe_joint_liar_args* args, tpe_joint_pick* picks, float* pick_z, double* liar_sigma,
+                   void* scratch, uint64_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Host phase clock of tpe_suggest_tree (tools/native_split.py).  While
  * enabled, a call records the steady-clock microseconds since its entry at
  * each phase below (a tree of several level runs: the last run's phases);

@@ -1,6 +1,6 @@
 """Time the joint TPE stage against the host route.
 Usage: python tools/joint_time.py [--pairs 3] [--warmup 1] [--cand 1048576] [--history 10000]
-                                  [--host-cand N] [--out FILE] [--mixed | --quant | --wide | --wide-mixed]
+                                  [--host-cand N] [--out FILE] [--mixed | --quant | --wide | --wide-mixed | --liar]
 
 Workload: a flat space of 4 continuous labels (uniform, loguniform, normal,
 uniform), a seeded 10,000-trial history whose loss has an x0 * x1 term, one
@@ -70,7 +70,19 @@ medians and ranges, the chunk kernel's time per (candidate x component x
 coordinate) evaluation and its ratio to the yardstick's, and for the new stage
 the worst l / g error of the first --host-cand (default 1024) sampled vectors as
 a fraction of the lpdf tolerance.  --out defaults to
-profiles/joint_wide_mixed_time.jsonl."""
+profiles/joint_wide_mixed_time.jsonl.
+
+--liar: batch-aware joint suggests (DESIGN.md "Batch-aware joint suggests").  The
+4-label workload above with --batch (default 64) new ids in one call; per round,
+alternating in one process, Engine.run_joint without the keyword (the stage as
+it was) and with liar=W, each timed from a synchronised device to its records
+on the host (wall clock).  The line carries both medians and ranges, their
+difference (what the keyword costs: the three per-candidate buffers the stage
+now writes, and the 2 B + 1 launches of tpe_joint_liar), that difference per
+step, and how far apart the B picks of either call lie: the median distance of a
+pick to its nearest other pick, each coordinate in units of its prior sigma (every id
+draws its own candidates, so the picks of the plain call differ in their bytes but sit
+on one mode).  --out defaults to profiles/joint_liar_time.jsonl."""
 import argparse
 import ctypes
 import json
@@ -534,6 +546,65 @@ def main_wide_mixed(args):
     return 0
 
 
+def main_liar(args):
+    import torch
+    from hyperopt_amd import history as H, joint as J
+    from hyperopt_amd.engine import get_engine
+    from hyperopt_amd.parzen import DEFAULT_LF
+
+    domain, hist = make_history(args.history)
+    rows = [r for r in domain.table.rows if J.eligible(r)]
+    model = J.fit_model(rows, hist, H.split_below(hist, 0.25), 1.0)
+    eng = get_engine(None, 'fp32')
+    C, D, B = args.cand, len(rows), args.batch
+    Kb, Ka = len(model.below[0]), len(model.above[0])
+    W = J.side_weight_sum(Ka - 1, 1.0, DEFAULT_LF)
+    ids = np.arange(args.history, args.history + B, dtype=np.int64)
+
+    def run(liar):
+        return eng.run_joint(model.below, model.above, model.low, model.high, ids, C, SEED, liar=liar)
+
+    def timed(fn, *a):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn(*a)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, out
+
+    for _ in range(args.warmup):
+        run(False)
+        run(W)
+    wall = {'plain': [], 'liar': []}
+    for i in range(args.pairs):
+        w, plain = timed(run, False)
+        wall['plain'].append(w)
+        w, liar = timed(run, W)
+        wall['liar'].append(w)
+        print('pair %d: plain %.2f ms, liar %.2f ms' % (i, wall['plain'][-1], w), file=sys.stderr, flush=True)
+    assert liar[:1].tobytes() == plain[:1].tobytes()
+    med = lambda x: float(np.median(x))   # noqa: E731
+
+    def spread(rec):
+        z = rec['z'][:, :D] / np.asarray(model.above[2])[0][None, :]
+        d = np.sqrt(((z[:, None, :] - z[None, :, :]) ** 2).sum(axis=2))
+        np.fill_diagonal(d, np.inf)
+        return float(np.median(d.min(axis=1)))
+    extra = med(wall['liar']) - med(wall['plain'])
+    line = dict(tool='joint_time --liar', labels=[r.label for r in rows], history=args.history, n_cand=C, n_dims=D,
+                k_below=Kb, k_above=Ka, batch=B, pairs=args.pairs, w_sum=W,
+                plain_ms=dict(wall_median=med(wall['plain']), wall_min=min(wall['plain']), wall_max=max(wall['plain'])),
+                liar_ms=dict(wall_median=med(wall['liar']), wall_min=min(wall['liar']), wall_max=max(wall['liar'])),
+                liar_minus_plain_ms=extra, per_step_ms=extra / B, ratio=med(wall['liar']) / med(wall['plain']),
+                nearest_pick_median=dict(plain=spread(plain), liar=spread(liar)), gpu=torch.cuda.get_device_name(0))
+    text = json.dumps(line)
+    print(text)
+    out = args.out or os.path.join(ROOT, 'profiles', 'joint_liar_time.jsonl')
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, 'a') as f:
+        f.write(text + '\n')
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--pairs', type=int, default=3)
@@ -545,6 +616,8 @@ def main():
     ap.add_argument('--quant', action='store_true')
     ap.add_argument('--wide', action='store_true')
     ap.add_argument('--wide-mixed', action='store_true')
+    ap.add_argument('--liar', action='store_true')
+    ap.add_argument('--batch', type=int, default=64)
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     if args.mixed:
@@ -555,6 +628,8 @@ def main():
         return main_wide(args)
     if args.wide_mixed:
         return main_wide_mixed(args)
+    if args.liar:
+        return main_liar(args)
     args.out = args.out or os.path.join(ROOT, 'profiles', 'joint_time.jsonl')
 
     import torch
