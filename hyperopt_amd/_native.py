@@ -316,6 +316,19 @@ class JointLiarArgs(ctypes.Structure):
     ]
 
 
+class JointLiarMixedArgs(ctypes.Structure):
+    """tpe_joint_liar_mixed_args: one tpe_joint_liar_mixed (tpe_joint_liar_args' fields, then the discrete and
+    quantised labels')."""
+    _fields_ = JointLiarArgs._fields_ + [
+        ('n_cat', ctypes.c_int32), ('n_quant', ctypes.c_int32),
+        ('cat_upper', ctypes.c_int32 * JOINT_MAX_DIMS), ('cat_off', ctypes.c_int32 * JOINT_MAX_DIMS),
+        ('cat_miss', ctypes.c_void_p), ('cat_bonus', ctypes.c_void_p),
+        ('quant_v', ctypes.c_int32 * JOINT_MAX_QUANT), ('quant_edge_off', ctypes.c_int32 * JOINT_MAX_QUANT),
+        ('n_edges', ctypes.c_int32), ('reserved', ctypes.c_int32),
+        ('quant_edges', ctypes.c_void_p), ('quant_centre', ctypes.c_void_p), ('above_qmu', ctypes.c_void_p),
+    ]
+
+
 class LabelIn(ctypes.Structure):
     _fields_ = [
         ('family', ctypes.c_int32), ('flags', ctypes.c_int32), ('upper', ctypes.c_int32),
@@ -465,7 +478,7 @@ EXPORTS = ('tpe_abi_version', 'tpe_last_error', 'tpe_device_count', 'tpe_tile_si
            'tpe_joint_seg_scratch_bytes', 'tpe_joint_seg_run', 'tpe_joint_mseg_scratch_bytes',
            'tpe_joint_mseg_table_bytes', 'tpe_joint_mseg_run', 'tpe_joint_report_scratch_bytes',
            'tpe_joint_report', 'tpe_joint_report_profile', 'tpe_joint_run_shard', 'tpe_joint_liar_scratch_bytes',
-           'tpe_joint_liar')
+           'tpe_joint_liar', 'tpe_joint_liar_mixed_scratch_bytes', 'tpe_joint_liar_mixed')
 
 # host phases of tpe_suggest_tree (tpe_host_phases order)
 PHASES = ('prefit', 'pack', 'launched', 'synced', 'level', 'return', 'recs')
@@ -622,6 +635,10 @@ def load(path=LIB_PATH):
     lib.tpe_joint_liar_scratch_bytes.restype = ctypes.c_int
     lib.tpe_joint_liar.argtypes = [ctypes.POINTER(JointLiarArgs), P, P, P, P, ctypes.c_uint64, P]
     lib.tpe_joint_liar.restype = ctypes.c_int
+    lib.tpe_joint_liar_mixed_scratch_bytes.argtypes = [I32] * 7 + [ctypes.POINTER(ctypes.c_uint64)]
+    lib.tpe_joint_liar_mixed_scratch_bytes.restype = ctypes.c_int
+    lib.tpe_joint_liar_mixed.argtypes = [ctypes.POINTER(JointLiarMixedArgs), P, P, P, P, ctypes.c_uint64, P]
+    lib.tpe_joint_liar_mixed.restype = ctypes.c_int
     lib.tpe_joint_profile.argtypes = [I32, P]
     lib.tpe_joint_profile.restype = ctypes.c_int
     lib.tpe_level_profile.argtypes = [ctypes.c_int32]

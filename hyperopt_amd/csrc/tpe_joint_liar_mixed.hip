@@ -1,0 +1,514 @@
+// MI355X (gfx950) batch-aware joint suggests over discrete and quantised
+// labels: the greedy "liar" stage that runs after a mixed, wide mixed or
+// quantised joint stage (include/tpe_hip.h, "Batch-aware picks over discrete and
+// quantised labels").  A candidate row is [z (f32) | category index | lattice
+// index]; a liar is a component of un-normalised weight 1 whose continuous part
+// is tpe_joint_liar's, whose discrete factor is that of a trial component of the
+// above side and whose quantised factor is the binned normal at the picked
+// lattice value's fit coordinate.  Nothing on the default suggest path, and
+// nothing tpe_joint_liar runs, goes through this file.
+//
+// k_liar_mixed_pick   one 256-thread workgroup per step: merges the previous
+//                     step's chunk records in index order, copies the winner's
+//                     row, then fits the new liar: the f32 neighbour sweep of
+//                     the continuous dimensions (as k_liar_pick), a float64
+//                     sweep over above_qmu and the earlier centres for the
+//                     quantised ones, the category copy for the discrete ones;
+//                     then the liar's bin tables T_i[d][v] = log Q_i(v), one
+//                     thread per lattice value, the V_d + 1 tails once through
+//                     LDS.  Row: {mu[Dc], sqrt(1/2) / sigma[Dc], c, cat[Dk],
+//                     centre[Dq]} in float64.  Step 0 adds the given liars.
+// k_liar_mixed_chunk  one 256-thread workgroup per chunk of TPE_JOINT_CHUNK
+//                     candidates of ONE id: the liar rows stream through LDS in
+//                     tiles of TPE_JOINT_LIAR_TILE; per (candidate, liar) the
+//                     continuous loop of k_liar_chunk, one compare-select-add per
+//                     discrete dimension and one table read (through L1 / L2, at
+//                     the candidate's own lattice index) per quantised one.
+//                     sum_d miss_d(v_d) depends on the candidate alone and is
+//                     added after the sum over the liars.  All in float64.
+// The steps are ordered by the stream alone: no workgroup waits on another, no
+// atomics, every reduction has a fixed shape, so the output bytes are a
+// function of the input bytes.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/tpe_hip.h"
+
+extern "C" int tpe_internal_fail(int code, const char* what);   // tpe_kernels.hip (hidden)
+extern "C" void tpe_internal_epoch_bump(void);                    // tpe_kernels.hip (hidden): the device epoch
+
+namespace {
+
+constexpr int kThreads = 256;                       // 4 waves of 64
+constexpr int kR = TPE_JOINT_CHUNK / kThreads;      // candidates per lane
+constexpr int kTile = TPE_JOINT_LIAR_TILE;          // liars per LDS tile
+constexpr int kQ = 4;                               // liars a lane accumulates at once
+constexpr int kMaxD = TPE_JOINT_WIDE_MAX_DIMS;
+constexpr int kMaxK = TPE_JOINT_MAX_DIMS;           // discrete dimensions
+constexpr int kMaxQ = TPE_JOINT_MAX_QUANT;
+constexpr int kMaxV = TPE_JOINT_MAX_LATTICE;
+constexpr int kMaxRow = 2 * kMaxD + 1;              // doubles of a liar row: 2 Dc + 1 + Dk + Dq, with Dc + Dk + Dq <= 64
+constexpr double kSqrtHalf = 0.70710678118654752440;
+constexpr double kTailMax = 26.5;                   // joint.QUANT_TAIL_MAX
+static_assert(kR * kThreads == TPE_JOINT_CHUNK && kTile % kQ == 0, "chunk and tile shapes");
+static_assert(sizeof(tpe_joint_pick) == 24, "layout");
+static_assert(offsetof(tpe_joint_liar_mixed_args, n_cat) == sizeof(tpe_joint_liar_args), "the shared prefix");
+static_assert(kMaxV <= kThreads, "one thread per lattice value");
+
+struct LiarMK {
+  int Dc, Dk, Dq, D, LS, C, n_chunks, K, G, n, totV;
+  const float* cand;
+  const double *l_out, *g_out;
+  const float* amu;
+  const double* aqmu;
+  const float* given;
+  const double *miss, *bonus;   // [sum U_d], natural log
+  const double *edges, *centre; // [n_edges], [sum V_d]
+  double* rows;                 // scratch [(G + n_ids) * LS]
+  double* tabs;                 // scratch [(G + n_ids) * totV]: log Q_i(v)
+  tpe_joint_pick* chunk_rec;    // scratch [n_chunks]: the records of the step that ran last
+  tpe_joint_pick* picks;
+  float* pick_z;
+  double* liar_sigma;
+  int cat_upper[kMaxK], cat_off[kMaxK];
+  int qv[kMaxQ], qeoff[kMaxQ], qtoff[kMaxQ];
+  double psig[kMaxD], low[kMaxD], high[kMaxD];   // [Dc + d]: quantised dimension d (psig only)
+};
+
+// np.argmax order of a score as one unsigned key (as tpe_joint.hip)
+__device__ __forceinline__ uint64_t score_key(double s) {
+  if (s != s) return ~0ull;
+  const uint64_t b = (uint64_t)__double_as_longlong(s + 0.0);
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+struct Pick {
+  uint64_t key;
+  int64_t idx;
+};
+__device__ __forceinline__ bool beats(const Pick& a, const Pick& b) {
+  return a.key > b.key || (a.key == b.key && a.key != 0 && a.idx < b.idx);
+}
+// the block's best competitor, the same in every thread
+__device__ __forceinline__ Pick block_best(Pick p, Pick* slot) {
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) {
+    Pick o;
+    o.key = (uint64_t)__shfl_xor((unsigned long long)p.key, m, 64);
+    o.idx = (int64_t)__shfl_xor((long long)p.idx, m, 64);
+    if (beats(o, p)) p = o;
+  }
+  if ((threadIdx.x & 63) == 0) slot[threadIdx.x >> 6] = p;
+  __syncthreads();
+  Pick w = slot[0];
+#pragma unroll
+  for (int i = 1; i < kThreads / 64; ++i)
+    if (beats(slot[i], w)) w = slot[i];
+  __syncthreads();
+  return w;
+}
+
+__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
+
+// the neighbour rule's end: the larger gap (a missing side dropped, none: 0), clipped
+__device__ __forceinline__ double neighbour_sigma(double z, double L, double U, bool hasL, bool hasU, double ps, int n,
+                                                  int i) {
+  double s = 0.0;
+  if (hasL) s = z - L;
+  if (hasU) s = hasL ? fmax(s, U - z) : U - z;
+  const double m = (double)n + (double)i + 1.0;
+  return fmin(fmax(s, ps / fmin(100.0, m + 2.0)), ps);
+}
+
+// joint.quant_bin_masses' three-way rule on the two smaller tails
+__device__ __forceinline__ double bin_mass(double ta, double sa, double tb, double sb) {
+  return tb <= 0.0 ? sb - sa : (ta >= 0.0 ? sa - sb : 1.0 - sa - sb);
+}
+
+struct PickLds {
+  float sL[kThreads], sU[kThreads];
+  double dL[kThreads], dU[kThreads];
+  double sterm[kMaxD];
+  double qc[kMaxQ], qs[kMaxQ];
+  double st[kMaxV + 1], ss[kMaxV + 1];
+  Pick slot[kThreads / 64];
+};
+
+// Liar `i` (ordinal among all liars) at the f32 row src[D] (nullptr: a row of
+// zeros): bandwidths, liar_sigma, the row and the bin tables.  zcopy: where the
+// row is also copied to, bit for bit.
+__device__ __forceinline__ void add_liar(const LiarMK& p, int i, const float* __restrict__ src,
+                                         float* __restrict__ zcopy, PickLds& s) {
+  const int t = threadIdx.x, Dc = p.Dc, Dk = p.Dk, Dq = p.Dq, LS = p.LS, DS = Dc + Dq;
+  double* row = p.rows + (int64_t)i * LS;
+  if (zcopy && t < p.D) zcopy[t] = src ? src[t] : 0.f;
+  if (Dc > 0) {                                 // as k_liar_pick: thread t serves dimension t % Dc
+    const int S = (kThreads / Dc) * Dc, d = t % Dc;
+    const float zd = src ? src[d] : 0.f;
+    float L = -INFINITY, U = INFINITY;          // -inf / +inf: no neighbour on that side
+    if (t < S) {
+      const int64_t total = (int64_t)p.K * Dc;
+      for (int64_t e = t; e < total; e += S) {
+        const float x = p.amu[e];
+        if (x <= zd) L = fmaxf(L, x);
+        else if (x > zd) U = fminf(U, x);
+      }
+      for (int q = t / Dc; q < i; q += S / Dc) {
+        const float x = (float)p.rows[(int64_t)q * LS + d];   // an earlier liar's f32 coordinate
+        if (x <= zd) L = fmaxf(L, x);
+        else if (x > zd) U = fminf(U, x);
+      }
+    }
+    s.sL[t] = L;
+    s.sU[t] = U;
+    __syncthreads();
+    if (t < Dc) {
+      for (int u = t + Dc; u < S; u += Dc) { L = fmaxf(L, s.sL[u]); U = fminf(U, s.sU[u]); }
+      const double z = (double)zd;
+      const double sg = neighbour_sigma(z, (double)L, (double)U, L != -INFINITY, U != INFINITY, p.psig[d], p.n, i);
+      p.liar_sigma[(int64_t)i * DS + d] = sg;
+      row[d] = z;
+      row[Dc + d] = kSqrtHalf / sg;
+      // the mass of the normal truncated to the label's bounds (joint._std_bounds)
+      const double za = (p.low[d] - z) / sg, zb = (p.high[d] - z) / sg;
+      const bool flip = za > 0.0;
+      const double a = flip ? -zb : za, b = flip ? -za : zb;
+      const double fa = 0.5 * erfc(-a * kSqrtHalf), fb = 0.5 * erfc(-b * kSqrtHalf);
+      s.sterm[d] = log(sg * 2.50662827463100050242 * (fb - fa));
+    }
+  }
+  if (t < Dk) {                                 // a discrete dimension: the category, no bandwidth
+    const int v = src ? (int)src[Dc + t] : 0;
+    int U = 2;
+#pragma unroll
+    for (int dd = 0; dd < kMaxK; ++dd)          // (static indices into the kernel arguments: no private copy)
+      if (dd == t) U = p.cat_upper[dd];
+    row[2 * Dc + 1 + t] = (double)clampi(v, U - 1);
+  }
+  if (Dq > 0) {                                 // thread t serves quantised dimension t % Dq, in float64
+    const int S = (kThreads / Dq) * Dq, d = t % Dq;
+    int V = 2, toff = 0;
+#pragma unroll
+    for (int dd = 0; dd < kMaxQ; ++dd)
+      if (dd == d) { V = p.qv[dd]; toff = p.qtoff[dd]; }
+    const int v = clampi(src ? (int)src[Dc + Dk + d] : 0, V - 1);
+    const double c = p.centre[toff + v];
+    double L = -INFINITY, U = INFINITY;
+    if (t < S) {
+      const int64_t total = (int64_t)p.K * Dq;
+      for (int64_t e = t; e < total; e += S) {
+        const double x = p.aqmu[e];
+        if (x <= c) L = fmax(L, x);
+        else if (x > c) U = fmin(U, x);
+      }
+      for (int q = t / Dq; q < i; q += S / Dq) {
+        const double x = p.rows[(int64_t)q * LS + 2 * Dc + 1 + Dk + d];   // an earlier liar's centre
+        if (x <= c) L = fmax(L, x);
+        else if (x > c) U = fmin(U, x);
+      }
+    }
+    s.dL[t] = L;
+    s.dU[t] = U;
+    __syncthreads();
+    if (t < Dq) {
+      for (int u = t + Dq; u < S; u += Dq) { L = fmax(L, s.dL[u]); U = fmin(U, s.dU[u]); }
+      const double sg = neighbour_sigma(c, L, U, L != -INFINITY, U != INFINITY, p.psig[Dc + d], p.n, i);
+      p.liar_sigma[(int64_t)i * DS + Dc + d] = sg;
+      row[2 * Dc + 1 + Dk + d] = c;
+      s.qc[d] = c;
+      s.qs[d] = sg;
+    }
+    __syncthreads();
+    for (int dd = 0; dd < Dq; ++dd) {           // T_i[dd][v] = log Q_i(v): the V + 1 tails once, then the differences
+      const int V = p.qv[dd];
+      const double* __restrict__ e = p.edges + p.qeoff[dd];
+      const double cc = s.qc[dd], sc = kSqrtHalf / s.qs[dd];
+      for (int u = t; u <= V; u += kThreads) {
+        const double tt = (e[u] - cc) * sc;
+        s.st[u] = tt;
+        s.ss[u] = fabs(tt) > kTailMax ? 0.0 : 0.5 * erfc(fabs(tt));
+      }
+      __syncthreads();
+      if (t < V) {
+        const double diff = bin_mass(s.st[t], s.ss[t], s.st[t + 1], s.ss[t + 1]);
+        const double mass = bin_mass(s.st[0], s.ss[0], s.st[V], s.ss[V]);
+        p.tabs[(int64_t)i * p.totV + p.qtoff[dd] + t] = diff > 0.0 ? log(diff / mass) : -INFINITY;
+      }
+      __syncthreads();                          // st / ss are read: the next dimension may overwrite them
+    }
+  }
+  __syncthreads();
+  if (t == 0) {
+    double c = 0.0;
+    for (int u = 0; u < Dc; ++u) c += s.sterm[u];
+    row[2 * Dc] = -c;
+  }
+  __syncthreads();                              // the row is written: the next liar of this launch may scan it
+}
+
+// step: 0 adds the given liars; j >= 1 merges step j - 1's chunk records into
+// picks[j - 1], copies its row and adds it as liar G + j - 1
+__global__ __launch_bounds__(kThreads) void k_liar_mixed_pick(const LiarMK p, int step) {
+  __shared__ PickLds s;
+  const int t = threadIdx.x;
+  if (step == 0) {
+    for (int i = 0; i < p.G; ++i) add_liar(p, i, p.given + (int64_t)i * p.D, nullptr, s);
+    return;
+  }
+  const int j = step - 1;
+  Pick best{0, 0};
+  for (int c = t; c < p.n_chunks; c += kThreads) {
+    const tpe_joint_pick r = p.chunk_rec[c];
+    if (r.idx < 0) continue;
+    const Pick x{score_key(r.l - r.g), r.idx};
+    if (beats(x, best)) best = x;            // (chunk order = candidate index order)
+  }
+  const Pick w = block_best(best, s.slot);
+  const bool none = w.key == 0;
+  if (t == 0) p.picks[j] = none ? tpe_joint_pick{-1, 0.0, 0.0} : p.chunk_rec[w.idx / TPE_JOINT_CHUNK];
+  add_liar(p, p.G + j, none ? nullptr : p.cand + ((int64_t)j * p.C + w.idx) * p.D, p.pick_z + (int64_t)j * p.D, s);
+}
+
+// id j's candidates under the above mixture extended by J = G + j liars
+__global__ __launch_bounds__(kThreads) void k_liar_mixed_chunk(const LiarMK p, int j, double log_w, double log_norm) {
+  __shared__ double tile[kTile * kMaxRow];
+  __shared__ Pick slot[kThreads / 64];
+  const int t = threadIdx.x, Dc = p.Dc, Dk = p.Dk, Dq = p.Dq, D = p.D, LS = p.LS, J = p.G + j;
+  const int first = blockIdx.x * TPE_JOINT_CHUNK;
+  const int64_t o = (int64_t)j * p.C;
+
+  double m[kR], s[kR];
+#pragma unroll
+  for (int r = 0; r < kR; ++r) { m[r] = -1.0e300; s[r] = 0.0; }   // a finite floor: all terms -inf leave s = 0, no NaN
+  for (int q0 = 0; q0 < J; q0 += kTile) {
+    const int nq = min(kTile, J - q0), nq4 = (nq + kQ - 1) / kQ * kQ;
+    __syncthreads();                         // the previous tile is read
+    for (int e = t; e < nq4 * LS; e += kThreads) {
+      const int q = e / LS, f = e % LS;      // a padded liar: h = 0, c = -inf, category -1 adds nothing
+      tile[e] = q < nq ? p.rows[(int64_t)(q0 + q) * LS + f] : (f == 2 * Dc ? -INFINITY : (f > 2 * Dc ? -1.0 : 0.0));
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < kR; ++r) {
+      const int i = first + r * kThreads + t;
+      if (i >= p.C) continue;
+      const float* __restrict__ zr = p.cand + (o + i) * D;
+      for (int qq = 0; qq < nq4; qq += kQ) {
+        const double* __restrict__ row = tile + qq * LS;
+        double acc[kQ], tt[kQ];
+#pragma unroll
+        for (int u = 0; u < kQ; ++u) acc[u] = 0.0;
+        for (int d = 0; d < Dc; ++d) {
+          const double zd = (double)zr[d];
+#pragma unroll
+          for (int u = 0; u < kQ; ++u) {
+            const double x = (zd - row[u * LS + d]) * row[u * LS + Dc + d];
+            acc[u] = fma(x, x, acc[u]);
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < kQ; ++u) tt[u] = row[u * LS + 2 * Dc] - acc[u];
+        for (int d = 0; d < Dk; ++d) {       // one compare, one select, one add per (candidate, liar)
+          const double vc = (double)zr[Dc + d];
+          const double b = p.bonus[p.cat_off[d] + clampi((int)vc, p.cat_upper[d] - 1)];
+#pragma unroll
+          for (int u = 0; u < kQ; ++u) tt[u] += row[u * LS + 2 * Dc + 1 + d] == vc ? b : 0.0;
+        }
+        for (int d = 0; d < Dq; ++d) {       // one table read at the candidate's own lattice index
+          const int v = p.qtoff[d] + clampi((int)zr[Dc + Dk + d], p.qv[d] - 1);
+#pragma unroll
+          for (int u = 0; u < kQ; ++u)       // (a padded liar reads the last real one's table: its c is -inf)
+            tt[u] += p.tabs[(int64_t)min(q0 + qq + u, J - 1) * p.totV + v];
+        }
+#pragma unroll
+        for (int u = 0; u < kQ; ++u) {
+          const double dl = tt[u] - m[r];
+          const double e2 = exp(-fabs(dl));
+          s[r] = dl > 0.0 ? fma(s[r], e2, 1.0) : s[r] + e2;
+          m[r] = fmax(m[r], tt[u]);
+        }
+      }
+    }
+  }
+
+  Pick best{0, 0};
+  double lv[kR], gv[kR];
+#pragma unroll
+  for (int r = 0; r < kR; ++r) {
+    const int i = first + r * kThreads + t;
+    lv[r] = gv[r] = 0.0;
+    if (i >= p.C) continue;
+    lv[r] = p.l_out[o + i];
+    double g = p.g_out[o + i];
+    if (J > 0 && g == g) {                   // logaddexp(g, lse - log W) - log1p(J / W)
+      const float* __restrict__ zr = p.cand + (o + i) * D;
+      double miss = 0.0;                     // sum_d miss_d(v_d): the candidate's alone
+      for (int d = 0; d < Dk; ++d) miss += p.miss[p.cat_off[d] + clampi((int)zr[Dc + d], p.cat_upper[d] - 1)];
+      const double x = m[r] + log(s[r]) + miss - log_w;
+      const double hi = fmax(g, x), lo = fmin(g, x);
+      g = (hi == -INFINITY ? hi : hi + log1p(exp(lo - hi))) - log_norm;
+    }
+    gv[r] = g;
+    const uint64_t key = score_key(lv[r] - g);
+    if (key > best.key) best = Pick{key, (int64_t)i};   // ascending index: strict > keeps the first of a tie
+  }
+  const Pick w = block_best(best, slot);
+  tpe_joint_pick* rec = p.chunk_rec + blockIdx.x;
+  if (w.key == 0) {
+    if (t == 0) *rec = tpe_joint_pick{-1, 0.0, 0.0};
+    return;
+  }
+  const int off = (int)(w.idx - first);
+  if (t != off % kThreads) return;
+#pragma unroll
+  for (int r = 0; r < kR; ++r)
+    if (r == off / kThreads) *rec = tpe_joint_pick{w.idx, lv[r], gv[r]};
+}
+
+struct Sizes {
+  uint64_t rows_bytes, tabs_bytes, bytes;
+};
+
+// the scratch of one call, or false where the sizes are out of range
+bool liar_mixed_scratch(int32_t n_ids, int32_t n_cand, int32_t n_dims, int32_t n_cat, int32_t n_quant,
+                        int32_t n_lattice, int32_t n_given, Sizes* z) {
+  if (n_ids < 1 || n_cand < 1 || n_dims < 0 || n_cat < 0 || n_quant < 0 || n_given < 0 || n_lattice < 0) return false;
+  if (n_cat > kMaxK || n_quant > kMaxQ || n_lattice > TPE_JOINT_MAX_LATTICE_TOTAL) return false;
+  const int D = n_dims + n_cat + n_quant;
+  if (D < 1 || D > kMaxD || (n_quant == 0) != (n_lattice == 0)) return false;
+  const uint64_t chunks = ((uint64_t)n_cand + TPE_JOINT_CHUNK - 1) / TPE_JOINT_CHUNK;
+  const uint64_t liars = (uint64_t)n_ids + (uint64_t)n_given;
+  z->rows_bytes = liars * (2 * (uint64_t)n_dims + 1 + (uint64_t)n_cat + (uint64_t)n_quant) * sizeof(double);
+  z->tabs_bytes = liars * (uint64_t)n_lattice * sizeof(double);
+  z->bytes = z->rows_bytes + z->tabs_bytes + chunks * sizeof(tpe_joint_pick);
+  return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tpe_joint_liar_mixed_scratch_bytes(int32_t n_ids, int32_t n_cand, int32_t n_dims, int32_t n_cat, int32_t n_quant,
+                                       int32_t n_lattice, int32_t n_given, uint64_t* bytes) {
+  Sizes z;
+  if (!bytes || !liar_mixed_scratch(n_ids, n_cand, n_dims, n_cat, n_quant, n_lattice, n_given, &z))
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar_mixed_scratch_bytes: bad arguments");
+  *bytes = z.bytes;
+  return TPE_OK;
+}
+
+int tpe_joint_liar_mixed(const tpe_joint_liar_mixed_args* a, tpe_joint_pick* picks, float* pick_z, double* liar_sigma,
+                         void* scratch, uint64_t scratch_bytes, void* stream) {
+  if (!a) {
+    tpe_internal_epoch_bump();
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar_mixed: null args");
+  }
+  // a continuous group: tpe_joint_liar over the shared prefix, its checks and its bytes
+  if (a->n_cat == 0 && a->n_quant == 0)
+    return tpe_joint_liar((const tpe_joint_liar_args*)a, picks, pick_z, liar_sigma, scratch, scratch_bytes, stream);
+  tpe_internal_epoch_bump();
+  const int Dc = a->n_dims, Dk = a->n_cat, Dq = a->n_quant;
+  if (Dc < 0 || Dk < 0 || Dq < 0)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar_mixed: n_dims / n_cat / n_quant < 0");
+  if (Dk > kMaxK || Dq > kMaxQ)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar_mixed: n_cat above TPE_JOINT_MAX_DIMS or n_quant above "
+                                        "TPE_JOINT_MAX_QUANT");
+  const int D = Dc + Dk + Dq;
+  if (D < 1 || D > kMaxD)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar_mixed: row width outside [1, TPE_JOINT_WIDE_MAX_DIMS]");
+  if (Dq > 0 && (Dc > 8 || Dk > 4))
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar_mixed: beside a quantised label n_dims <= 8 and n_cat <= 4");
+  if (a->n_ids < 1 || a->n_cand < 1 || a->k_above < 1)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar_mixed: n_ids / n_cand / k_above < 1");
+  if (a->n_given < 0 || a->n_trials < 0)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar_mixed: n_given / n_trials < 0");
+  if (!(a->w_sum > 0.0) || !(a->w_sum < INFINITY))
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar_mixed: w_sum must be positive and finite");
+  if (!a->cand || !a->l_out || !a->g_out || (Dc > 0 && !a->above_mu))
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar_mixed: null cand / l_out / g_out / above_mu");
+  if (a->n_given > 0 && !a->given)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar_mixed: n_given > 0 without given");
+  if (!picks || !pick_z || !liar_sigma) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar_mixed: null outputs");
+  for (int d = 0; d < Dc; ++d)
+    if (!(a->psig[d] > 0.0))
+      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar_mixed: a prior sigma that is not positive");
+  for (int d = 0; d < Dq; ++d)
+    if (!(a->psig[Dc + d] > 0.0))
+      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar_mixed: a prior sigma that is not positive");
+  int64_t cat_total = 0, lat_total = 0;
+  if (Dk > 0) {
+    if (!a->cat_miss || !a->cat_bonus) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar_mixed: null category table");
+    for (int d = 0; d < Dk; ++d) {
+      if (a->cat_upper[d] < 2 || a->cat_upper[d] > TPE_JOINT_MAX_CATS)
+        return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar_mixed: a U_d outside [2, TPE_JOINT_MAX_CATS]");
+      cat_total += a->cat_upper[d];
+    }
+    if (cat_total > TPE_JOINT_MAX_CAT_TOTAL)
+      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar_mixed: more than TPE_JOINT_MAX_CAT_TOTAL categories");
+    for (int d = 0; d < Dk; ++d)
+      if (a->cat_off[d] < 0 || a->cat_off[d] > cat_total - a->cat_upper[d])
+        return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar_mixed: a cat_off that leaves the table");
+  }
+  if (Dq > 0) {
+    if (!a->quant_edges || !a->quant_centre || !a->above_qmu)
+      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar_mixed: null quant_edges / quant_centre / above_qmu");
+    for (int d = 0; d < Dq; ++d) {
+      if (a->quant_v[d] < 2 || a->quant_v[d] > kMaxV)
+        return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar_mixed: a V_d outside [2, TPE_JOINT_MAX_LATTICE]");
+      lat_total += a->quant_v[d];
+    }
+    if (lat_total > TPE_JOINT_MAX_LATTICE_TOTAL)
+      return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar_mixed: more than TPE_JOINT_MAX_LATTICE_TOTAL lattice values");
+    for (int d = 0; d < Dq; ++d)
+      if (a->quant_edge_off[d] < 0 || a->quant_edge_off[d] > a->n_edges - a->quant_v[d] - 1)
+        return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar_mixed: a quant_edge_off that leaves quant_edges");
+  }
+  Sizes z;
+  if (!liar_mixed_scratch(a->n_ids, a->n_cand, Dc, Dk, Dq, (int32_t)lat_total, a->n_given, &z))
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar_mixed: sizes out of range");
+  if (!scratch || scratch_bytes < z.bytes)
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar_mixed: scratch too small");
+
+  LiarMK k;
+  k.Dc = Dc; k.Dk = Dk; k.Dq = Dq; k.D = D; k.LS = 2 * Dc + 1 + Dk + Dq;
+  k.C = a->n_cand; k.K = a->k_above; k.G = a->n_given; k.n = a->n_trials; k.totV = (int)lat_total;
+  k.n_chunks = (int)(((int64_t)a->n_cand + TPE_JOINT_CHUNK - 1) / TPE_JOINT_CHUNK);
+  k.cand = a->cand; k.l_out = a->l_out; k.g_out = a->g_out; k.amu = a->above_mu; k.aqmu = a->above_qmu;
+  k.given = a->given; k.miss = a->cat_miss; k.bonus = a->cat_bonus; k.edges = a->quant_edges;
+  k.centre = a->quant_centre;
+  k.rows = (double*)scratch;
+  k.tabs = (double*)((char*)scratch + z.rows_bytes);
+  k.chunk_rec = (tpe_joint_pick*)((char*)scratch + z.rows_bytes + z.tabs_bytes);
+  k.picks = picks; k.pick_z = pick_z; k.liar_sigma = liar_sigma;
+  for (int d = 0; d < kMaxK; ++d) {
+    k.cat_upper[d] = d < Dk ? a->cat_upper[d] : 2;
+    k.cat_off[d] = d < Dk ? a->cat_off[d] : 0;
+  }
+  int toff = 0;
+  for (int d = 0; d < kMaxQ; ++d) {
+    k.qv[d] = d < Dq ? a->quant_v[d] : 2;
+    k.qeoff[d] = d < Dq ? a->quant_edge_off[d] : 0;
+    k.qtoff[d] = d < Dq ? toff : 0;
+    if (d < Dq) toff += a->quant_v[d];
+  }
+  for (int d = 0; d < kMaxD; ++d) {
+    const bool cont = d < Dc, in = cont || d < Dc + Dq;
+    k.psig[d] = in ? a->psig[d] : 1.0;
+    k.low[d] = cont ? a->low[d] : -INFINITY;
+    k.high[d] = cont ? a->high[d] : INFINITY;
+  }
+  const hipStream_t s = (hipStream_t)stream;
+  const double log_w = log(a->w_sum);
+  if (k.G > 0) hipLaunchKernelGGL(k_liar_mixed_pick, dim3(1), dim3(kThreads), 0, s, k, 0);
+  for (int j = 0; j < a->n_ids; ++j) {
+    hipLaunchKernelGGL(k_liar_mixed_chunk, dim3((unsigned)k.n_chunks), dim3(kThreads), 0, s, k, j, log_w,
+                       log1p((double)(k.G + j) / a->w_sum));
+    hipLaunchKernelGGL(k_liar_mixed_pick, dim3(1), dim3(kThreads), 0, s, k, j + 1);
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
+  return TPE_OK;
+}
+
+}  // extern "C"

@@ -1083,7 +1083,8 @@ class Engine(object):
         ids, n_ids, C = self._joint_sizes(D, ids, n_cand, shard)
         shard = self._joint_shard(shard, C, report_k, inject)
         if liar is not None:
-            liar = self._liar_model(liar, entry, above, r, D)
+            liar = (self._liar_mixed_model(liar, above, r, cats, quants) if liar.get('mixed')
+                    else self._liar_model(liar, entry, above, r, D))
         if C == 0:
             if return_table:
                 raise ValueError('joint stage: return_table needs at least one candidate')
@@ -1146,6 +1147,85 @@ class Engine(object):
             if given.ndim != 2 or given.shape[1] != D:
                 raise ValueError('joint stage: given must be [G, %d]: %r' % (D, given.shape))
         return {'W': W, 'given': given, 'sigma': liar['sigma'], 'psig': sigma[0], 'low': r['low'], 'high': r['high']}
+
+    def run_joint_liar_mixed(self, below, above, low, high, cats, quants, ids, n_cand, seed, liar=True, given=None,
+                             return_sigma=False, centres=None, inject=None, return_cand=False, want_lg=False,
+                             report_k=0, shard=None, stream_word=None):
+        """A batch-aware joint stage over a group with discrete and / or
+        quantised labels (DESIGN.md "Batch-aware picks over discrete and
+        quantised labels"): the stage ``run_joint_quant`` (``quants`` not
+        empty), ``run_joint_wide_mixed`` (more than N.JOINT_MAX_DIMS
+        coordinates) or ``run_joint_mixed`` would run over the same group, its
+        three buffers kept on the device, then tpe_joint_liar_mixed on the same
+        stream.  ``below`` .. ``cats``, ``ids`` .. ``seed``, ``inject``,
+        ``return_cand``, ``want_lg`` and ``stream_word`` are those methods';
+        ``quants`` as run_joint_quant (() without quantised labels).  ``liar``,
+        ``given`` and ``return_sigma`` mean what they mean on ``run_joint``:
+        ``given`` is [G, D] in kernel coordinates (continuous, categories,
+        lattice indices), the categories and lattice indices integral values in
+        range, else ValueError; the bandwidths come back as float64 [G + n_ids,
+        Dc + Dq], the continuous dimensions, then the quantised ones.
+        ``centres``: per quantised dimension the float64 [V] fit coordinates of
+        its lattice values (QuantModel.centres()), required with quantised
+        labels.  ``shard`` and ``report_k`` > 0 raise as on ``run_joint``.  The
+        three stage methods themselves keep their signatures (tests pin them):
+        the liar keywords live here."""
+        lm = self._liar(liar, given, return_sigma, report_k, shard)
+        if lm is None:
+            raise ValueError('joint stage: run_joint_liar_mixed needs liar (True or the weight sum W)')
+        lm['mixed'], lm['centres'] = True, centres
+        D = len(np.asarray(low).reshape(-1)) + len(cats) + len(quants)
+        entry = 'quant' if len(quants) else ('wide_mixed' if D > N.JOINT_MAX_DIMS else 'mixed')
+        return self._joint_solo(entry, below, above, low, high, cats, quants, ids, n_cand, seed, inject, return_cand,
+                                want_lg, 0, stream_word, None, liar=lm)
+
+    @staticmethod
+    def _liar_mixed_model(liar, above, r, cats, quants):
+        """``liar`` (run_joint_liar_mixed) completed from a group with discrete or
+        quantised labels (joint.py "Batch-aware picks over discrete and quantised
+        labels"): W, the prior sigmas of the continuous and the quantised
+        dimensions, the bounds, the float64 liar tables of the discrete
+        dimensions from the above side's smoothing masses, the centre table, and
+        the given rows as f32 [G, D] (categories and lattice indices integral
+        and in range, else ValueError)."""
+        from . import joint as J
+        Dc, Dk, Dq = r['Dc'], r['Dk'], r['Dq']
+        D = Dc + Dk + Dq
+        w = np.asarray(above[0], dtype=np.float64)
+        sigma = np.asarray(above[2], dtype=np.float64).reshape(len(w), Dc)
+        W = liar['W']
+        if W is None:
+            W = 1.0 / float(w[-1]) if len(w) > 1 else 1.0
+        ups, vs = list(r.get('cat_upper', ())), list(r.get('quant_v', ()))
+        tabs = [J.liar_cat_tables(c[2], c[4]) for c in cats]
+        centre = np.zeros(0)
+        if Dq:
+            cs = liar.get('centres')
+            if cs is None or len(cs) != Dq:
+                raise ValueError('joint stage: liar with quantised labels needs centres, one array per quantised '
+                                 'dimension (joint.quant_centres)')
+            cs = [np.ascontiguousarray(c, dtype=np.float64).reshape(-1) for c in cs]
+            if any(len(c) != V or not np.isfinite(c).all() for c, V in zip(cs, vs)):
+                raise ValueError('joint stage: centres must hold one finite value per lattice value')
+            centre = np.concatenate(cs)
+        elif liar.get('centres'):
+            raise ValueError('joint stage: centres without a quantised dimension')
+        given = np.zeros((0, D), dtype=np.float32)
+        if liar['given'] is not None:
+            g64 = np.asarray(liar['given'], dtype=np.float64)
+            if g64.ndim != 2 or g64.shape[1] != D:
+                raise ValueError('joint stage: given must be [G, %d]: %r' % (D, g64.shape))
+            for d, top in enumerate(ups + vs):
+                col = g64[:, Dc + d]
+                if not ((col == np.rint(col)) & (col >= 0) & (col < top)).all():
+                    raise ValueError('joint stage: given holds a %s that is not an integer in [0, %d)'
+                                     % ('category' if d < Dk else 'lattice index', top))
+            given = np.ascontiguousarray(g64, dtype=np.float32)
+        psig = np.concatenate([sigma[0], np.asarray(r['above_qsigma'], dtype=np.float64)[0] if Dq else np.zeros(0)])
+        return {'mixed': True, 'W': W, 'given': given, 'sigma': liar['sigma'], 'psig': psig, 'low': r['low'],
+                'high': r['high'], 'n_sigma': Dc + Dq,
+                'miss': np.concatenate([t[0] for t in tabs]) if tabs else np.zeros(0),
+                'bonus': np.concatenate([t[1] for t in tabs]) if tabs else np.zeros(0), 'centre': centre}
 
     def _joint_sizes(self, D, ids, n_cand, shard=None):
         ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
@@ -1247,7 +1327,8 @@ class Engine(object):
             rep = self._joint_report(d_cand.data_ptr(), d_l.data_ptr(), d_g.data_ptr(), n_ids, C, report_k, stream,
                                      width=D)
         if liar is not None:
-            lr = self._joint_liar(a, liar, d_cand.data_ptr(), d_l.data_ptr(), d_g.data_ptr(), n_ids, C, D, stream)
+            enq = self._joint_liar_mixed if liar.get('mixed') else self._joint_liar
+            lr = enq(a, liar, d_cand.data_ptr(), d_l.data_ptr(), d_g.data_ptr(), n_ids, C, D, stream)
         rec = d_rec[:n_ids * rec_dtype.itemsize // 8].cpu().numpy().view(rec_dtype).copy()
         if liar is not None:
             d_picks, d_z, d_sig, G = lr
@@ -1265,7 +1346,8 @@ class Engine(object):
         if report_k:
             out.extend(self._joint_report_host(rep, n_ids, report_k, D))
         if liar is not None and liar['sigma']:
-            out.append(d_sig[:(G + n_ids) * D].cpu().numpy().reshape(G + n_ids, D).copy())
+            ns = liar.get('n_sigma', D)
+            out.append(d_sig[:(G + n_ids) * ns].cpu().numpy().reshape(G + n_ids, ns).copy())
         return tuple(out)
 
     def _joint_liar(self, a, liar, cand, l, g, n_ids, C, D, stream):
@@ -1292,6 +1374,49 @@ class Engine(object):
         N.check(self.lib.tpe_joint_liar(ctypes.byref(la), d_picks.data_ptr(), d_z.data_ptr(), d_sig.data_ptr(),
                                         d_scr.data_ptr(), d_scr.numel() * 8, ctypes.c_void_p(stream)), self.lib,
                 'tpe_joint_liar')
+        return d_picks, d_z, d_sig, G
+
+    def _joint_liar_mixed(self, a, liar, cand, l, g, n_ids, C, D, stream):
+        """Enqueue tpe_joint_liar_mixed over the device buffers the mixed, wide
+        mixed or quantised stage ``a`` just wrote (the lattice edges and the
+        above side's rows are the stage's own uploads); returns as _joint_liar."""
+        given = liar['given']
+        G, Dc, Dk, Dq = len(given), a.n_dims, a.n_cat, getattr(a, 'n_quant', 0)
+        la = N.JointLiarMixedArgs()
+        la.n_dims, la.n_cand, la.n_ids, la.n_given = Dc, C, n_ids, G
+        la.k_above, la.n_trials, la.w_sum = a.k_above, a.k_above - 1, liar['W']
+        la.cand, la.l_out, la.g_out = cand, l, g
+        if Dc:
+            la.above_mu = a.above_mu
+        if G:
+            la.given = self._joint_up('liar_given', given, torch.float32)
+        for d in range(Dc):
+            la.psig[d], la.low[d], la.high[d] = liar['psig'][d], liar['low'][d], liar['high'][d]
+        la.n_cat, la.n_quant = Dk, Dq
+        if Dk:
+            for d in range(Dk):
+                la.cat_upper[d], la.cat_off[d] = a.cat_upper[d], a.cat_off[d]
+            la.cat_miss = self._joint_up('liar_miss', liar['miss'], torch.float64)
+            la.cat_bonus = self._joint_up('liar_bonus', liar['bonus'], torch.float64)
+        n_lattice = 0
+        if Dq:
+            for d in range(Dq):
+                la.psig[Dc + d], la.low[Dc + d], la.high[Dc + d] = liar['psig'][Dc + d], a.low[Dc + d], a.high[Dc + d]
+                la.quant_v[d], la.quant_edge_off[d] = a.quant_v[d], a.quant_edge_off[d]
+                n_lattice += a.quant_v[d]
+            la.n_edges, la.quant_edges, la.above_qmu = a.n_edges, a.quant_edges, a.above_qmu
+            la.quant_centre = self._joint_up('liar_centre', liar['centre'], torch.float64)
+        nb = ctypes.c_uint64(0)
+        N.check(self.lib.tpe_joint_liar_mixed_scratch_bytes(n_ids, C, Dc, Dk, Dq, n_lattice, G, ctypes.byref(nb)),
+                self.lib, 'tpe_joint_liar_mixed_scratch_bytes')
+        ns = Dc + Dq
+        d_scr = self._buf('joint_liar_scratch', (nb.value + 7) // 8, torch.float64)
+        d_picks = self._buf('joint_liar_picks', n_ids * 3, torch.float64)
+        d_z = self._buf('joint_liar_z', n_ids * D, torch.float32)
+        d_sig = self._buf('joint_liar_sigma', max(1, (G + n_ids) * ns), torch.float64)
+        N.check(self.lib.tpe_joint_liar_mixed(ctypes.byref(la), d_picks.data_ptr(), d_z.data_ptr(), d_sig.data_ptr(),
+                                              d_scr.data_ptr(), d_scr.numel() * 8, ctypes.c_void_p(stream)), self.lib,
+                'tpe_joint_liar_mixed')
         return d_picks, d_z, d_sig, G
 
     @staticmethod

@@ -566,6 +566,11 @@ class QuantModel(object):
         return [(self.below[4][:, d], self.below[5][:, d], self.above[4][:, d], self.above[5][:, d], lat[3])
                 for d, lat in enumerate(self.lattices)]
 
+    def centres(self):
+        """The ``centres`` argument of Engine.run_joint_quant with ``liar``:
+        per quantised label the fit coordinates of its lattice values."""
+        return [quant_centres(r.dist, r.args) for r in self.qrows]
+
     def values(self, z):
         """Label values of kernel coordinates z [.., Dc + Dk + Dq]: exp for the
         log families, (m_lo + i) q for a lattice index i."""
@@ -660,8 +665,9 @@ def combine_records(stacked):
 
 # ------------------------------------------------- batch-aware joint suggests
 # The ids of one batched call pick greedily (include/tpe_hip.h "Batch-aware
-# joint suggests", DESIGN.md "Batch-aware joint suggests"; continuous groups
-# only).  The above side is side_mixture's: n trial rows and the prior row,
+# joint suggests", DESIGN.md "Batch-aware joint suggests"; continuous groups:
+# the block after this one takes discrete and quantised labels).  The above
+# side is side_mixture's: n trial rows and the prior row,
 # un-normalised weights w~ (prior_weight, then the linear-forgetting ramp or 1),
 # W their sum.  Id j (step j, the order given) is scored under the above
 # mixture extended by J = G + j "liars": the G given vectors, then the picks of
@@ -707,4 +713,100 @@ def liar_log_g(z, log_g, liar_mu, liar_sigma, W, low, high):
         return np.array(log_g, dtype=np.float64)
     lk = lpdf_numpy(z, np.ones(J), np.asarray(liar_mu, dtype=np.float64), np.asarray(liar_sigma, dtype=np.float64),
                     low, high)
+    return np.logaddexp(log_g, lk - math.log(W)) - math.log1p(J / W)
+
+
+# ------------------------- batch-aware picks over discrete and quantised labels
+# The liar model above for a root group that also holds discrete and / or
+# quantised labels (include/tpe_hip.h and DESIGN.md "Batch-aware picks over
+# discrete and quantised labels").  A row is [z (f32) | category index | lattice
+# index] in kernel order; steps, ordering, W and m = n + i + 1 are unchanged, as
+# are the below side, l and the existing components (their smoothing masses
+# included).  Liar i from a row r, un-normalised weight 1:
+#   continuous d   the rule above, over above_mu[:, d] (f32) and the earlier liars
+#   discrete d     the category x = r[Dc + d] and the factor of a trial component
+#                  of the above side as the stage holds it, P(v) = (1[v = x] +
+#                  s_d p_d(v)) / (1 + s_d) with s_d = s_above[d] unchanged (one
+#                  more trial would make it prior_weight U / (n + 2)); float64
+#                  tables from discrete_tables; no bandwidth
+#   quantised d    centre: the fit coordinate of the picked lattice value,
+#                  fit_coord(dist, args, (m_lo + i) q), what a trial that observed
+#                  it gets as qmu (quant_centres, one table per call).  Bandwidth:
+#                  the neighbour rule over the K values above_qmu[:, d] (float64,
+#                  the prior row included) and the earlier liars' centres,
+#                  clipped to [psig_d / min(100, m + 2), psig_d], psig_d =
+#                  above_qsigma[0, d].  Factor: quant_P(centre, sigma, edges_d),
+#                  not floored: a far bin's log is -inf.
+#   log k_i(z, v, q) = the continuous term + sum_d log P_id(v_d) + sum_d log Q_id(q_d)
+# and log g_j as above; where every liar's term is -inf, g_j = log g - log1p(J / W).
+LN2 = math.log(2.0)
+
+
+def quant_centres(dist, args):
+    """float64 [V]: the fit coordinate of every lattice value of a joinable
+    quantised label, (m_lo + i) q through parzen.fit_coord."""
+    m_lo, V, q = lattice_size(dist, args)
+    return np.ascontiguousarray(fit_coord(dist, args, (m_lo + np.arange(V)) * q), dtype=np.float64)
+
+
+def liar_cat_tables(p, s):
+    """float64 (miss [U], bonus [U]) of a liar's discrete factor in natural
+    logarithms: log P(v) = miss[v] + bonus[v] 1[v = x]; discrete_tables' values."""
+    miss, bonus, _ = discrete_tables(p, s)
+    return miss * LN2, bonus * LN2
+
+
+def liar_quant_sigmas(points, c, psig, m):
+    """sigma [Dq] of a liar's quantised dimensions at the centres ``c``:
+    ``points`` [P, Dq] float64 the side's qmu rows followed by the earlier
+    liars' centres, m = n + i + 1.  Float64 subtractions, one division, max /
+    min: bit for bit what the device computes."""
+    c = np.asarray(c, dtype=np.float64).reshape(-1)
+    pts = np.asarray(points, dtype=np.float64)
+    pts = pts.reshape(len(pts), len(c))
+    psig = np.asarray(psig, dtype=np.float64)
+    out = np.empty(len(c))
+    for d in range(len(c)):
+        col = pts[:, d]
+        le, gt = col[col <= c[d]], col[col > c[d]]
+        gaps = ([c[d] - le.max()] if len(le) else []) + ([gt.min() - c[d]] if len(gt) else [])
+        out[d] = max(gaps) if gaps else 0.0
+    return np.minimum(np.maximum(out, psig / min(100.0, m + 2.0)), psig)
+
+
+def liar_mixed_log_g(z, v, qi, log_g, liars, W, low, high, cat_tabs=(), edges=()):
+    """log g_J at continuous ``z`` [C, Dc], categories ``v`` [C, Dk] and lattice
+    indices ``qi`` [C, Dq] from the base ``log_g`` [C]: ``liars`` = (mu [J, Dc],
+    sigma [J, Dc], cat [J, Dk], centre [J, Dq], qsigma [J, Dq]), ``cat_tabs`` one
+    liar_cat_tables per discrete dimension, ``edges`` one array per quantised
+    one.  J = 0: log_g."""
+    mu, sigma, cat, qc, qs = liars
+    J = len(cat)
+    if J == 0:
+        return np.array(log_g, dtype=np.float64)
+    C = len(log_g)
+    mu, sigma = np.asarray(mu, dtype=np.float64).reshape(J, -1), np.asarray(sigma, dtype=np.float64).reshape(J, -1)
+    Dc = mu.shape[1]
+    z = np.asarray(z, dtype=np.float64).reshape(C, Dc)
+    v = np.asarray(v, dtype=np.int64).reshape(C, len(cat_tabs))
+    qi = np.asarray(qi, dtype=np.int64).reshape(C, len(edges))
+    cat = np.asarray(cat, dtype=np.int64).reshape(J, len(cat_tabs))
+    t = np.zeros((C, J))
+    if Dc:
+        fa, fb, _ = _std_bounds(mu, sigma, np.asarray(low, dtype=np.float64)[None, :],
+                                np.asarray(high, dtype=np.float64)[None, :])
+        t -= np.sum(np.log(sigma * np.sqrt(2 * np.pi)) + np.log(fb - fa), axis=1)[None, :]
+        for d in range(Dc):
+            t -= 0.5 * ((z[:, d, None] - mu[None, :, d]) / sigma[None, :, d]) ** 2
+    for d, (miss, bonus) in enumerate(cat_tabs):
+        t += miss[v[:, d]][:, None] + np.where(v[:, d, None] == cat[None, :, d], bonus[v[:, d]][:, None], 0.0)
+    for d, e in enumerate(edges):
+        with np.errstate(divide='ignore'):
+            logQ = np.log(quant_P(np.asarray(qc, dtype=np.float64).reshape(J, -1)[:, d],
+                                  np.asarray(qs, dtype=np.float64).reshape(J, -1)[:, d], e))
+        t += logQ[:, qi[:, d]].T
+    m = t.max(axis=1)
+    m = np.where(np.isfinite(m), m, 0.0)                 # every term -inf: the sum is 0, its log -inf, no NaN
+    with np.errstate(divide='ignore'):
+        lk = m + np.log(np.exp(t - m[:, None]).sum(axis=1))
     return np.logaddexp(log_g, lk - math.log(W)) - math.log1p(J / W)

@@ -850,16 +850,17 @@ def suggest(new_ids, domain, trials, seed,
         return []
     if joint_shard is not None:                  # (argument errors first, as below; nothing on the default path)
         _joint_shard_pair(joint_shard, joint, joint_wide_mixed)
-    if joint_liar:
-        _joint_liar_check(joint, joint_shard)
+    liar_mode = _joint_liar_mode(joint_liar)
+    if liar_mode:
+        _joint_liar_check(joint, joint_shard, mode=liar_mode)
     if ((joint is not False and joint is not None) or joint_discrete or joint_quantized or joint_wide or joint_branches
             or joint_branches_mixed or joint_wide_mixed):
         # (argument errors first: no device use, no startup draw)
         plan = _joint_plan(domain.table, joint, sampler, precision, (shard, shard_ids, shard_labels, shard_grid),
                            joint_discrete, joint_quantized, _wide_mode(joint_wide, joint_wide_mixed), joint_branches,
                            joint_branches_mixed)
-        if joint_liar:
-            _joint_liar_check(joint, joint_shard, plan)
+        if liar_mode:
+            _joint_liar_check(joint, joint_shard, plan, liar_mode)
     t0 = time.time()
     hist = _history.extract(domain, trials)
     if logger.isEnabledFor(logging.INFO):
@@ -1037,13 +1038,24 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
     the whole result, is the same bytes as without the keyword.  A root group
     with a discrete or quantised label, any branch group, ``joint_shard`` and
     the keyword without ``joint`` raise ValueError; joint_candidate_report does
-    not take it."""
+    not take it.
+
+    ``joint_liar='mixed'``: everything True does, and the root group may also
+    hold discrete labels (``joint_discrete``), quantised labels
+    (``joint_quantized``) or be a wide group with discrete labels
+    (``joint_wide_mixed``): DESIGN.md "Batch-aware picks over discrete and
+    quantised labels".  A picked category counts as one more trial component of
+    the above side with that category, a picked lattice value as a binned
+    normal at its fit coordinate.  On a continuous root group it is True byte
+    for byte.  Branch groups, ``joint_shard`` and the keyword without ``joint``
+    raise as under True; any other value raises ValueError."""
     if sampler not in ('philox', 'replay'):
         raise ValueError("sampler must be 'philox' or 'replay'")
     if joint_shard is not None:
         joint_shard = _joint_shard_pair(joint_shard, joint, joint_wide_mixed)
-    if joint_liar:
-        _joint_liar_check(joint, joint_shard)
+    liar_mode = _joint_liar_mode(joint_liar)
+    if liar_mode:
+        _joint_liar_check(joint, joint_shard, mode=liar_mode)
     group, branch_groups = None, []
     if ((joint is not False and joint is not None) or joint_discrete or joint_quantized or joint_wide or joint_branches
             or joint_branches_mixed or joint_wide_mixed):
@@ -1051,8 +1063,8 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
                                            (shard, shard_ids, shard_labels, shard_grid), joint_discrete,
                                            joint_quantized, _wide_mode(joint_wide, joint_wide_mixed),
                                            joint_branches, joint_branches_mixed)
-        if joint_liar:
-            _joint_liar_check(joint, joint_shard, (group, branch_groups))
+        if liar_mode:
+            _joint_liar_check(joint, joint_shard, (group, branch_groups), liar_mode)
     if sum(a is not None for a in (shard, shard_ids, shard_labels, shard_grid)) > 1:
         raise ValueError('shard, shard_ids, shard_labels and shard_grid are exclusive: one shard axis per suggest')
     if (shard_ids is not None or shard_labels is not None or shard_grid is not None) and sampler == 'replay':
@@ -1064,7 +1076,7 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
                                 columns, shard_ids, shard_labels, shard_grid)
     if group is not None or branch_groups:
         return _suggest_joint(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, device, columns, group,
-                              branch_groups, joint_shard, bool(joint_liar))
+                              branch_groups, joint_shard, bool(liar_mode))
     return _suggest_local(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, sampler, precision,
                           device, shard, columns)
 
@@ -1074,20 +1086,36 @@ TPE_JOINT_WIDE_MAX_DIMS = N.JOINT_WIDE_MAX_DIMS
 TPE_JOINT_WIDE_MAX_CAT = N.JOINT_WIDE_MAX_CAT
 
 
-def _joint_liar_check(joint, joint_shard, plan=None):
-    """ValueError where ``joint_liar=True`` does not apply: without ``joint``,
-    with ``joint_shard``, and (``plan`` = _joint_plan's result) for a root group
-    that is missing or holds a discrete or quantised label and for any branch
-    group.  Touches no device."""
+def _joint_liar_mode(joint_liar):
+    """``joint_liar`` as None (off: False or None), True or 'mixed'; ValueError
+    for anything else (another string, a number)."""
+    if joint_liar is None or (isinstance(joint_liar, (bool, np.bool_)) and not joint_liar):
+        return None
+    if isinstance(joint_liar, (bool, np.bool_)):
+        return True
+    if isinstance(joint_liar, str) and joint_liar == 'mixed':
+        return 'mixed'
+    raise ValueError("joint_liar must be True or 'mixed' (or False): %r" % (joint_liar,))
+
+
+def _joint_liar_check(joint, joint_shard, plan=None, mode=True):
+    """ValueError where ``joint_liar`` (``mode``: True or 'mixed') does not
+    apply: without ``joint``, with ``joint_shard``, and (``plan`` = _joint_plan's
+    result) for a root group that is missing or, under True, holds a discrete or
+    quantised label, and for any branch group.  Touches no device."""
     if joint is False or joint is None:
         raise ValueError('joint_liar needs joint=True or joint=[labels]: it only changes how the joint stage picks')
     if joint_shard is not None:
-        raise ValueError('joint_liar=True does not combine with joint_shard')
+        raise ValueError('joint_liar=%r does not combine with joint_shard' % (mode,))
     if plan is None:
         return
     group, branch_groups = plan
     if branch_groups:
-        raise ValueError('joint_liar=True does not combine with branch groups (joint_branches)')
+        raise ValueError('joint_liar=%r does not combine with branch groups (joint_branches)' % (mode,))
+    if mode == 'mixed':
+        if group is None:
+            raise ValueError("joint_liar='mixed' needs a root group: there is none")
+        return
     other = [r.label for r in (group or ()) if r.dist not in _joint.JOINT_DISTS]
     if group is None or other:
         raise ValueError('joint_liar=True needs a root group of continuous labels only: %s'
@@ -1459,16 +1487,27 @@ def _run_root_group(engine, group, hist, ids, seed, prior_weight, n_EI_candidate
         group = crows + drows + qrows
         model = _joint.fit_quant_model(crows, drows, qrows, hist, _history.split_below(hist, gamma), prior_weight,
                                        DEFAULT_LF)
-        out = engine.run_joint_quant(model.below[:3], model.above[:3], model.low, model.high, model.cats(),
-                                     model.quants(), ids, int(n_EI_candidates), seed, **kw)
+        if kw.pop('liar', False):                # (joint_liar='mixed': W as below, the lattice values' fit coordinates)
+            out = engine.run_joint_liar_mixed(
+                model.below[:3], model.above[:3], model.low, model.high, model.cats(), model.quants(), ids,
+                int(n_EI_candidates), seed, centres=model.centres(),
+                liar=_joint.side_weight_sum(len(model.above[0]) - 1, prior_weight, DEFAULT_LF), **kw)
+        else:
+            out = engine.run_joint_quant(model.below[:3], model.above[:3], model.low, model.high, model.cats(),
+                                         model.quants(), ids, int(n_EI_candidates), seed, **kw)
     elif drows:                                  # kernel coordinates: the continuous labels, then the discrete ones
         group = [r for r in group if not r.categorical] + drows
         model = _joint.fit_mixed_model(group[:len(group) - len(drows)], drows, hist,
                                        _history.split_below(hist, gamma), prior_weight, DEFAULT_LF)
         # more than TPE_JOINT_MAX_DIMS labels (joint_wide_mixed=True let them through): the wide mixed stage
         run = engine.run_joint_wide_mixed if len(group) > TPE_JOINT_MAX_DIMS else engine.run_joint_mixed
-        out = run(model.below[:3], model.above[:3], model.low, model.high, model.cats(), ids, int(n_EI_candidates),
-                  seed, **kw)
+        if kw.pop('liar', False):                # (the stage `run` names, then tpe_joint_liar_mixed)
+            out = engine.run_joint_liar_mixed(
+                model.below[:3], model.above[:3], model.low, model.high, model.cats(), (), ids, int(n_EI_candidates),
+                seed, liar=_joint.side_weight_sum(len(model.above[0]) - 1, prior_weight, DEFAULT_LF), **kw)
+        else:
+            out = run(model.below[:3], model.above[:3], model.low, model.high, model.cats(), ids,
+                      int(n_EI_candidates), seed, **kw)
     else:
         model = _joint.fit_model(group, hist, _history.split_below(hist, gamma), prior_weight, DEFAULT_LF)
         # more than TPE_JOINT_MAX_DIMS labels (joint_wide=True let them through): the wide stage

@@ -1795,6 +1795,110 @@ int tpe_joint_liar(const tpe_joint_liar_args* args, tpe_joint_pick* picks, float
                    void* scratch, uint64_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Batch-aware picks over discrete and quantised labels
+ * (tpe_joint_liar_mixed.hip; additive exports, the ABI stays 24).  The liar
+ * stage above for a group that also holds n_cat discrete and / or n_quant
+ * quantised labels: a follow-up of tpe_joint_mixed_run, tpe_joint_wide_mixed_run
+ * or tpe_joint_quant_run, enqueued after the stage that wrote cand, l_out and
+ * g_out.  A row (of `cand`, `given`, pick_z) is [z (f32, n_dims) | category
+ * index (n_cat) | lattice index (n_quant)], D = n_dims + n_cat + n_quant wide.
+ * Steps, ordering, W, m = n + i + 1, the score, the winner order and the
+ * outputs are tpe_joint_liar's; the existing components are not refitted, their
+ * smoothing masses included.  Liar i at a row r:
+ *   continuous d < n_dims   tpe_joint_liar's rule over above_mu[., d] (f32) and
+ *                           the earlier liars' coordinates.
+ *   discrete d              the category x = r[n_dims + d] and the factor of a
+ *                           trial component of the above side as the stage holds
+ *                           it, P(v) = (1[v = x] + s_d p_d(v)) / (1 + s_d), from
+ *                           the f64 tables cat_miss[cat_off[d] + v] = ln(s_d
+ *                           p_d(v) / (1 + s_d)) and cat_bonus[..] = ln(1 + 1 /
+ *                           (s_d p_d(v))) (natural logarithms); no bandwidth.
+ *   quantised d             centre c = quant_centre[t_d + v], v = r[n_dims +
+ *                           n_cat + d], t_d = sum of V_e over e < d: the fit
+ *                           coordinate of the picked lattice value, a host table
+ *                           the device only indexes.  Bandwidth: the neighbour
+ *                           rule over the k_above values above_qmu[., d] (f64,
+ *                           the prior row included) and the centres of the liars
+ *                           before it, L = max{p <= c}, U = min{p > c}, sigma =
+ *                           max(c - L, U - c) (a missing side dropped; none: 0),
+ *                           clipped to [psig / min(100, m + 2), psig] with psig
+ *                           = psig[n_dims + d]: f64 subtractions, one division,
+ *                           max / min, so the same bits on every IEEE machine.
+ *                           Factor Q_i(v): the normal (c, sigma) on the bin
+ *                           [e_v, e_v+1) over its mass on [e_0, e_V), by the
+ *                           quantised stage's rule (differences between the two
+ *                           smaller tails, a tail beyond 26.5 exactly 0), in f64
+ *                           and NOT floored: a far bin's log is -inf and the
+ *                           liar adds exactly 0 there.
+ *   log k_i(z, v, q) = tpe_joint_liar's continuous term + sum_d ln P_id(v_d) +
+ *                      sum_d ln Q_id(q_d)
+ *   log g_j = logaddexp(log g, logsumexp_i log k_i - log W) - log1p(J / W);
+ * where every liar's term is -inf, g_j = log g - log1p(J / W), no NaN.
+ *
+ * Outputs: picks[j] as tpe_joint_liar; pick_z[j * D ..] the winner's row, bit
+ * for bit; liar_sigma[i * (n_dims + n_quant) ..]: the continuous dimensions,
+ * then the quantised ones, for every liar (the last pick's too).  2 launches a
+ * step: k_liar_mixed_pick (one workgroup: merge, row copy, the two neighbour
+ * sweeps, then the liar's tables T_i[d][v] = ln Q_i(v), one thread per lattice
+ * value, the V_d + 1 tails once through LDS) and k_liar_mixed_chunk
+ * (TPE_JOINT_CHUNK candidates a workgroup, four a lane; liar rows {mu, sqrt(1/2)
+ * / sigma, c, category, centre} through LDS in tiles of TPE_JOINT_LIAR_TILE;
+ * per (candidate, liar) one compare-select-add per discrete dimension and one
+ * table read through L1 / L2 at the candidate's own lattice index per quantised
+ * one; sum_d miss_d(v_d) after the sum over the liars).  Ordered by the stream
+ * alone, no atomics: the same call twice gives the same bytes.  As in the base
+ * stages a category or lattice index outside its table is the caller's error;
+ * the device only keeps its table indices in range.
+ *
+ * tpe_joint_liar_mixed_scratch_bytes = (n_given + n_ids) (2 n_dims + 1 + n_cat
+ * + n_quant + n_lattice) 8 + ceil(n_cand / TPE_JOINT_CHUNK) 24, n_lattice = sum_d
+ * V_d; TPE_E_ARG for counts out of range.  tpe_joint_liar_mixed_args starts with
+ * the fields of tpe_joint_liar_args at the same offsets (n_dims: the continuous
+ * labels; low / high [n_dims + d] are not read).  With n_cat = n_quant = 0 the
+ * call IS tpe_joint_liar on that prefix: its checks, its bytes.  Otherwise
+ * tpe_joint_liar_mixed returns TPE_E_ARG before any launch (no device needed)
+ * for: null args, buffers or outputs (above_mu may be NULL with n_dims = 0); a
+ * negative count; n_cat > TPE_JOINT_MAX_DIMS, n_quant > TPE_JOINT_MAX_QUANT; D
+ * outside [1, TPE_JOINT_WIDE_MAX_DIMS]; n_dims > 8 or n_cat > 4 while n_quant >
+ * 0; n_ids, n_cand or k_above < 1; n_given > 0 without `given`; w_sum not
+ * positive and finite; a psig (continuous or quantised) that is not positive; a
+ * null table while its count is > 0; a U_d outside [2, TPE_JOINT_MAX_CATS], more
+ * than TPE_JOINT_MAX_CAT_TOTAL categories, a cat_off that leaves [0, total -
+ * U_d]; a V_d outside [2, TPE_JOINT_MAX_LATTICE], more than
+ * TPE_JOINT_MAX_LATTICE_TOTAL lattice values, a quant_edge_off that leaves [0,
+ * n_edges - V_d - 1]; scratch smaller than the formula.
+ * ---------------------------------------------------------------------- */
+typedef struct tpe_joint_liar_mixed_args {
+  int32_t n_dims, n_cand, n_ids, n_given;  /* as tpe_joint_liar_args ...; n_dims: the continuous labels */
+  int32_t k_above, n_trials;
+  double w_sum;
+  const float* cand;           /* device [n_ids * n_cand * D] */
+  const double *l_out, *g_out; /* device [n_ids * n_cand] */
+  const float* above_mu;       /* device [k_above * n_dims] */
+  const float* given;          /* device [n_given * D]; NULL with n_given == 0 */
+  double psig[TPE_JOINT_WIDE_MAX_DIMS];      /* [d] continuous, [n_dims + d] quantised dimension d */
+  double low[TPE_JOINT_WIDE_MAX_DIMS], high[TPE_JOINT_WIDE_MAX_DIMS];   /* ... up to here; the continuous bounds */
+  int32_t n_cat, n_quant;
+  int32_t cat_upper[TPE_JOINT_MAX_DIMS];   /* U_d */
+  int32_t cat_off[TPE_JOINT_MAX_DIMS];     /* start of dimension d in cat_miss / cat_bonus */
+  const double *cat_miss, *cat_bonus;      /* device f64 [sum_d U_d], natural logarithms, the above side's s_d */
+  int32_t quant_v[TPE_JOINT_MAX_QUANT];         /* V_d */
+  int32_t quant_edge_off[TPE_JOINT_MAX_QUANT];  /* e_0 of dimension d in quant_edges */
+  int32_t n_edges, reserved;
+  const double* quant_edges;   /* device f64 [n_edges], as tpe_joint_quant_args */
+  const double* quant_centre;  /* device f64 [sum_d V_d], dimensions in order */
+  const double* above_qmu;     /* device f64 [k_above * n_quant], as tpe_joint_quant_args */
+} tpe_joint_liar_mixed_args;
+
+int tpe_joint_liar_mixed_scratch_bytes(int32_t n_ids, int32_t n_cand, int32_t n_dims, int32_t n_cat, int32_t n_quant,
+                                       int32_t n_lattice, int32_t n_given, uint64_t* bytes);
+
+/* picks: device [n_ids]; pick_z: device f32 [n_ids * D]; liar_sigma: device f64
+ * [(n_given + n_ids) * (n_dims + n_quant)]; enqueued on `stream` */
+int tpe_joint_liar_mixed(const tpe_joint_liar_mixed_args* args, tpe_joint_pick* picks, float* pick_z,
+                         double* liar_sigma, void* scratch, uint64_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Host phase clock of tpe_suggest_tree (tools/native_split.py).  While
  * enabled, a call records the steady-clock microseconds since its entry at
  * each phase below (a tree of several level runs: the last run's phases);

@@ -1,6 +1,7 @@
 """Time the joint TPE stage against the host route.
 Usage: python tools/joint_time.py [--pairs 3] [--warmup 1] [--cand 1048576] [--history 10000]
-                                  [--host-cand N] [--out FILE] [--mixed | --quant | --wide | --wide-mixed | --liar]
+                                  [--host-cand N] [--out FILE] [--mixed | --quant | --wide | --wide-mixed | --liar |
+                                   --liar-mixed]
 
 Workload: a flat space of 4 continuous labels (uniform, loguniform, normal,
 uniform), a seeded 10,000-trial history whose loss has an x0 * x1 term, one
@@ -82,7 +83,15 @@ now writes, and the 2 B + 1 launches of tpe_joint_liar), that difference per
 step, and how far apart the B picks of either call lie: the median distance of a
 pick to its nearest other pick, each coordinate in units of its prior sigma (every id
 draws its own candidates, so the picks of the plain call differ in their bytes but sit
-on one mode).  --out defaults to profiles/joint_liar_time.jsonl."""
+on one mode).  --out defaults to profiles/joint_liar_time.jsonl.
+
+--liar-mixed: batch-aware picks over discrete and quantised labels.
+The shape of --liar on a group of the 4 continuous labels, one hp.choice of 3 and
+one hp.quniform of 32 values: Engine.run_joint_quant (the stage as it was) and
+Engine.run_joint_liar_mixed with liar=W, alternating, wall clock from a synchronised
+device to the records on the host.  The nearest-pick distance counts a
+continuous or quantised coordinate in units of its prior sigma and a differing
+category as 1.  --out defaults to profiles/joint_liar_mixed_time.jsonl."""
 import argparse
 import ctypes
 import json
@@ -605,6 +614,91 @@ def main_liar(args):
     return 0
 
 
+def make_liar_mixed_history(n):
+    from hyperopt_amd import base, history as H, hp
+    space = {'x0': hp.uniform('x0', -5, 5), 'x1': hp.loguniform('x1', -3, 2), 'x2': hp.normal('x2', 0, 2),
+             'x3': hp.uniform('x3', 0, 1), 'c4': hp.choice('c4', [0, 1, 2]), 'q5': hp.quniform('q5', 1, 32, 1)}
+    domain = base.Domain(lambda d: 0.0, space)
+    rs = np.random.RandomState(SEED)
+    cols = {'x0': rs.uniform(-5, 5, n), 'x1': np.exp(rs.uniform(-3, 2, n)), 'x2': rs.normal(0, 2, n),
+            'x3': rs.uniform(0, 1, n), 'c4': rs.randint(3, size=n), 'q5': np.rint(rs.uniform(1, 32, n))}
+    loss = (cols['x0'] * cols['x1'] - 2.0) ** 2 + 0.1 * cols['x2'] ** 2 + (cols['x3'] - 0.3) ** 2 \
+        + 0.2 * (cols['c4'] != 1) + 1e-3 * (cols['q5'] - 12.0) ** 2 + 0.01 * rs.standard_normal(n)
+    tids = np.arange(n, dtype=np.int64)
+    return domain, H.History(tids, loss, {k: (tids, v) for k, v in cols.items()})
+
+
+def main_liar_mixed(args):
+    import torch
+    from hyperopt_amd import history as H, joint as J
+    from hyperopt_amd.engine import get_engine
+    from hyperopt_amd.parzen import DEFAULT_LF
+
+    domain, hist = make_liar_mixed_history(args.history)
+    rows = [r for r in domain.table.rows if J.eligible(r)]
+    drows = [r for r in domain.table.rows if J.eligible_discrete(r, domain.table)]
+    qrows = [r for r in domain.table.rows if J.eligible_quant(r, domain.table)]
+    model = J.fit_quant_model(rows, drows, qrows, hist, H.split_below(hist, 0.25), 1.0)
+    eng = get_engine(None, 'fp32')
+    C, B = args.cand, args.batch
+    Dc, Dk, Dq = len(rows), len(drows), len(qrows)
+    Kb, Ka = len(model.below[0]), len(model.above[0])
+    W = J.side_weight_sum(Ka - 1, 1.0, DEFAULT_LF)
+    ids = np.arange(args.history, args.history + B, dtype=np.int64)
+    cats, quants, centres = model.cats(), model.quants(), model.centres()
+
+    def run(liar):
+        head = (model.below[:3], model.above[:3], model.low, model.high, cats, quants, ids, C, SEED)
+        return eng.run_joint_liar_mixed(*head, liar=W, centres=centres) if liar else eng.run_joint_quant(*head)
+
+    def timed(fn, *a):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn(*a)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, out
+
+    for _ in range(args.warmup):
+        run(False)
+        run(True)
+    wall = {'plain': [], 'liar': []}
+    for i in range(args.pairs):
+        w, plain = timed(run, False)
+        wall['plain'].append(w)
+        w, liar = timed(run, True)
+        wall['liar'].append(w)
+        print('pair %d: plain %.2f ms, liar %.2f ms' % (i, wall['plain'][-1], w), file=sys.stderr, flush=True)
+    assert liar[:1].tobytes() == plain[:1].tobytes()
+    med = lambda x: float(np.median(x))   # noqa: E731
+
+    def spread(rec):
+        z = rec['z'][:, :Dc] / np.asarray(model.above[2])[0][None, :]
+        q = np.stack([centres[d][rec['z'][:, Dc + Dk + d].astype(np.int64)] / model.above[5][0, d] for d in range(Dq)],
+                     axis=1)
+        z = np.hstack([z, q])
+        d2 = ((z[:, None, :] - z[None, :, :]) ** 2).sum(axis=2)
+        v = rec['z'][:, Dc:Dc + Dk]
+        d2 = d2 + (v[:, None, :] != v[None, :, :]).sum(axis=2)
+        d = np.sqrt(d2)
+        np.fill_diagonal(d, np.inf)
+        return float(np.median(d.min(axis=1)))
+    extra = med(wall['liar']) - med(wall['plain'])
+    line = dict(tool='joint_time --liar-mixed', labels=[r.label for r in rows + drows + qrows], history=args.history,
+                n_cand=C, n_dims=Dc, n_cat=Dk, n_quant=Dq, lattice=[lat[1] for lat in model.lattices],
+                k_below=Kb, k_above=Ka, batch=B, pairs=args.pairs, w_sum=W,
+                plain_ms=dict(wall_median=med(wall['plain']), wall_min=min(wall['plain']), wall_max=max(wall['plain'])),
+                liar_ms=dict(wall_median=med(wall['liar']), wall_min=min(wall['liar']), wall_max=max(wall['liar'])),
+                liar_minus_plain_ms=extra, per_step_ms=extra / B, ratio=med(wall['liar']) / med(wall['plain']),
+                nearest_pick_median=dict(plain=spread(plain), liar=spread(liar)), gpu=torch.cuda.get_device_name(0))
+    text = json.dumps(line)
+    print(text)
+    out = args.out or os.path.join(ROOT, 'profiles', 'joint_liar_mixed_time.jsonl')
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, 'a') as f:
+        f.write(text + '\n')
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--pairs', type=int, default=3)
@@ -617,6 +711,7 @@ def main():
     ap.add_argument('--wide', action='store_true')
     ap.add_argument('--wide-mixed', action='store_true')
     ap.add_argument('--liar', action='store_true')
+    ap.add_argument('--liar-mixed', action='store_true')
     ap.add_argument('--batch', type=int, default=64)
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
@@ -630,6 +725,8 @@ def main():
         return main_wide_mixed(args)
     if args.liar:
         return main_liar(args)
+    if args.liar_mixed:
+        return main_liar_mixed(args)
     args.out = args.out or os.path.join(ROOT, 'profiles', 'joint_time.jsonl')
 
     import torch
