@@ -11,7 +11,6 @@ POOL_SRC = os.path.join(HERE, 'csrc', 'tpe_pool.cpp')
 REPORT_SRC = os.path.join(HERE, 'csrc', 'tpe_report.hip')
 JOINT_SRC = os.path.join(HERE, 'csrc', 'tpe_joint.hip')
 LIAR_SRC = os.path.join(HERE, 'csrc', 'tpe_joint_liar.hip')
-LIAR_MIXED_SRC = os.path.join(HERE, 'csrc', 'tpe_joint_liar_mixed.hip')
 RNG_HDR = os.path.join(HERE, 'csrc', 'tpe_device_rng.h')
 OUT = os.path.join(HERE, 'libtpe_hip.so')
 ARCH = os.environ.get('TPE_OFFLOAD_ARCH', 'gfx950')
@@ -25,7 +24,7 @@ def build(force=False, verbose=False, out=OUT, defines=()):
     semantics), link both into hyperopt_amd/libtpe_hip.so (or `out`, with extra
     -D `defines` on the kernels: A/B variants for tools/)."""
     OUT = out
-    deps = [SRC, HOST_SRC, SUGGEST_SRC, POOL_SRC, REPORT_SRC, JOINT_SRC, LIAR_SRC, LIAR_MIXED_SRC, RNG_HDR, os.path.join(HERE, 'csrc', 'tpe_pool.h'), os.path.join(HERE, 'csrc', 'sort_net.h'),
+    deps = [SRC, HOST_SRC, SUGGEST_SRC, POOL_SRC, REPORT_SRC, JOINT_SRC, LIAR_SRC, RNG_HDR, os.path.join(HERE, 'csrc', 'tpe_pool.h'), os.path.join(HERE, 'csrc', 'sort_net.h'),
             os.path.join(HERE, 'csrc', 'tpe_keystore.h'),
             os.path.join(HERE, '..', 'include', 'tpe_hip.h'), os.path.abspath(__file__)]
     if out == os.path.join(HERE, 'libtpe_hip.so'):
@@ -43,7 +42,6 @@ def build(force=False, verbose=False, out=OUT, defines=()):
     report_o = os.path.join(HERE, 'csrc', 'tpe_report.o')
     joint_o = os.path.join(HERE, 'csrc', 'tpe_joint.o')
     liar_o = os.path.join(HERE, 'csrc', 'tpe_joint_liar.o')
-    liar_mixed_o = os.path.join(HERE, 'csrc', 'tpe_joint_liar_mixed.o')
     hdr = [os.path.join(HERE, '..', 'include', 'tpe_hip.h'), os.path.join(HERE, 'csrc', 'tpe_pool.h'),
            os.path.join(HERE, 'csrc', 'sort_net.h'), os.path.join(HERE, 'csrc', 'tpe_keystore.h')]
     host_flags = [gxx, '-O3', '-march=' + HOST_MARCH, '-std=c++17', '-fPIC', '-Wall']
@@ -63,14 +61,11 @@ def build(force=False, verbose=False, out=OUT, defines=()):
                                                '-Wno-unused-command-line-argument', '-c', JOINT_SRC, '-o', joint_o]),
         (liar_o, [LIAR_SRC] + hdr, [hipcc, '-O3', '--offload-arch=' + ARCH, '-std=c++17', '-fPIC', '-Wall',
                                     '-Wno-unused-command-line-argument', '-c', LIAR_SRC, '-o', liar_o]),
-        (liar_mixed_o, [LIAR_MIXED_SRC] + hdr, [hipcc, '-O3', '--offload-arch=' + ARCH, '-std=c++17', '-fPIC', '-Wall',
-                                                '-Wno-unused-command-line-argument', '-c', LIAR_MIXED_SRC, '-o',
-                                                liar_mixed_o]),
     ]
     cmds = [c for o, srcs, c in objs
             if force or not os.path.exists(o) or any(os.path.getmtime(s) > os.path.getmtime(o) for s in srcs)]
     cmds.append([hipcc, '-shared', '-fPIC', '--offload-arch=' + ARCH, '-Wno-unused-command-line-argument', '-o', tmp,
-                 dev_o, report_o, joint_o, liar_o, liar_mixed_o, host_o, suggest_o, pool_o, '-pthread'])
+                 dev_o, report_o, joint_o, liar_o, host_o, suggest_o, pool_o, '-pthread'])
     for cmd in cmds:
         if verbose:
             print(' '.join(cmd))

@@ -1,15 +1,29 @@
 // MI355X (gfx950) batch-aware joint suggests: the greedy "liar" stage that runs
-// after a continuous joint stage (include/tpe_hip.h, "Batch-aware joint
-// suggests").  Id j picks under the above mixture extended by the vectors the
-// ids before it picked (and the given ones), each a component of un-normalised
-// weight 1.  Nothing on the default suggest path runs through this file.
+// after a joint stage (include/tpe_hip.h, "Batch-aware joint suggests" and
+// "Batch-aware picks over discrete and quantised labels").  Id j picks under the
+// above mixture extended by the vectors the ids before it picked (and the given
+// ones), each a component of un-normalised weight 1.  Nothing on the default
+// suggest path runs through this file.
+//
+// Every kernel exists in two instantiations of one template.  <false> serves a
+// group of continuous labels (tpe_joint_liar); <true> a group that also holds
+// discrete and / or quantised labels (tpe_joint_liar_mixed): a candidate row is
+// then [z (f32) | category index | lattice index], a liar's discrete factor is
+// that of a trial component of the above side and its quantised factor the
+// binned normal at the picked lattice value's fit coordinate.  What only <true>
+// needs sits under `if constexpr (kMixed)` and in LiarMK / PickLds<true>: the
+// continuous instantiation holds none of it, in registers, LDS or arguments.
 //
 // k_liar_pick   one 256-thread workgroup per step: merges the previous step's
 //               chunk records in index order, copies the winner's row, then
 //               fits the new liar's bandwidths (the adaptive-Parzen neighbour
 //               rule over the K_above f32 mu values and the earlier liars of
 //               each dimension, float64 on f32 values: exact) and writes its
-//               float64 row {mu[D], sqrt(1/2) / sigma[D], c}.  Step 0 adds the
+//               float64 row {mu[Dc], sqrt(1/2) / sigma[Dc], c}.  <true>: the
+//               row goes on with {cat[Dk], centre[Dq]}: the category copy, a
+//               float64 sweep over above_qmu and the earlier centres, then the
+//               liar's bin tables T_i[d][v] = log Q_i(v), one thread per lattice
+//               value, the V_d + 1 tails once through LDS.  Step 0 adds the
 //               given liars one after the other.
 // k_liar_chunk  one 256-thread workgroup per chunk of TPE_JOINT_CHUNK
 //               consecutive candidates of ONE id: the liar rows stream through
@@ -17,13 +31,22 @@
 //               sum_d ((z_d - mu_d) / (sigma_d sqrt 2))^2 of four liars at a
 //               time in float64 (subtract, then scale), keeps a running
 //               maximum, finishes against the stored g and writes the chunk
-//               winner through the butterfly on (score key, index).
+//               winner through the butterfly on (score key, index).  <true>:
+//               per (candidate, liar) also one compare-select-add per discrete
+//               dimension and one table read (through L1 / L2, at the
+//               candidate's own lattice index) per quantised one; sum_d
+//               miss_d(v_d) depends on the candidate alone and is added after
+//               the sum over the liars.
 // The steps are ordered by the stream alone: no workgroup waits on another, no
 // atomics, every reduction has a fixed shape, so the output bytes are a
 // function of the input bytes.
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <stddef.h>
 #include <stdint.h>
+#include <stdio.h>
+
+#include <type_traits>
 
 #include "../../include/tpe_hip.h"
 
@@ -37,23 +60,53 @@ constexpr int kR = TPE_JOINT_CHUNK / kThreads;      // candidates per lane
 constexpr int kTile = TPE_JOINT_LIAR_TILE;          // liars per LDS tile
 constexpr int kQ = 4;                               // liars a lane accumulates at once
 constexpr int kMaxD = TPE_JOINT_WIDE_MAX_DIMS;
-constexpr int kMaxRow = 2 * kMaxD + 1;              // doubles of a liar row: mu[D], h[D], c
+constexpr int kMaxK = TPE_JOINT_MAX_DIMS;           // discrete dimensions
+constexpr int kMaxQ = TPE_JOINT_MAX_QUANT;
+constexpr int kMaxV = TPE_JOINT_MAX_LATTICE;
+constexpr int kMaxRow = 2 * kMaxD + 1;              // doubles of a liar row: 2 Dc + 1 + Dk + Dq, with Dc + Dk + Dq <= 64
+constexpr double kSqrtHalf = 0.70710678118654752440;
+constexpr double kTailMax = 26.5;                   // joint.QUANT_TAIL_MAX
 static_assert(kR * kThreads == TPE_JOINT_CHUNK && kTile % kQ == 0, "chunk and tile shapes");
 static_assert(sizeof(tpe_joint_pick) == 24, "layout");
+static_assert(offsetof(tpe_joint_liar_mixed_args, n_cat) == sizeof(tpe_joint_liar_args), "the shared prefix");
+static_assert(kMaxV <= kThreads, "one thread per lattice value");
 
-struct LiarK {
-  int D, C, n_chunks, K, G, n;
+struct LiarK {                  // what both instantiations take
+  int D, C, n_chunks, K, G, n;  // D: the width of a candidate row
   const float* cand;
   const double *l_out, *g_out;
   const float* amu;
   const float* given;
-  double* rows;                 // scratch [(G + n_ids) * (2 D + 1)]
+  double* rows;                 // scratch [(G + n_ids) * LS]
   tpe_joint_pick* chunk_rec;    // scratch [n_chunks]: the records of the step that ran last
   tpe_joint_pick* picks;
   float* pick_z;
   double* liar_sigma;
-  double psig[kMaxD], low[kMaxD], high[kMaxD];
+  double psig[kMaxD], low[kMaxD], high[kMaxD];   // [Dc + d]: quantised dimension d (psig only)
 };
+struct LiarMK : LiarK {         // <true> alone
+  int Dc, Dk, Dq, LS, totV;
+  const double* aqmu;
+  const double *miss, *bonus;   // [sum U_d], natural log
+  const double *edges, *centre; // [n_edges], [sum V_d]
+  double* tabs;                 // scratch [(G + n_ids) * totV]: log Q_i(v)
+  int cat_upper[kMaxK], cat_off[kMaxK];
+  int qv[kMaxQ], qeoff[kMaxQ], qtoff[kMaxQ];
+};
+template <bool kMixed>
+using Params = std::conditional_t<kMixed, LiarMK, LiarK>;
+
+// the continuous dimensions and the doubles of a liar row
+template <bool kMixed>
+__device__ __forceinline__ int cont_dims(const Params<kMixed>& p) {
+  if constexpr (kMixed) return p.Dc;
+  else return p.D;
+}
+template <bool kMixed>
+__device__ __forceinline__ int row_len(const Params<kMixed>& p) {
+  if constexpr (kMixed) return p.LS;
+  else return 2 * p.D + 1;
+}
 
 // np.argmax order of a score as one unsigned key (as tpe_joint.hip)
 __device__ __forceinline__ uint64_t score_key(double s) {
@@ -87,72 +140,165 @@ __device__ __forceinline__ Pick block_best(Pick p, Pick* slot) {
   return w;
 }
 
-// Liar `i` (ordinal among all liars) at the f32 vector zsrc[D]: bandwidths,
-// liar_sigma and the row.  S = the largest multiple of D up to 256 threads scan:
-// thread t serves dimension t % D and the points t / D, t / D + S / D, ..., so a
-// sweep reads S consecutive floats.  zcopy: where the vector is also copied to.
-__device__ __forceinline__ void add_liar(const LiarK& p, int i, const float* __restrict__ zsrc,
-                                         float* __restrict__ zcopy, float* sL, float* sU, double* sterm) {
-  const int t = threadIdx.x, D = p.D, S = (kThreads / D) * D, LS = 2 * D + 1;
-  const int d = t % D;
-  const float zd = zsrc ? zsrc[d] : 0.f;
-  float L = -INFINITY, U = INFINITY;          // -inf / +inf: no neighbour on that side
-  if (t < S) {
-    const int64_t total = (int64_t)p.K * D;
-    for (int64_t e = t; e < total; e += S) {
-      const float x = p.amu[e];
-      if (x <= zd) L = fmaxf(L, x);
-      else if (x > zd) U = fminf(U, x);
+__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
+
+// the neighbour rule's end: the larger gap (a missing side dropped, none: 0), clipped
+__device__ __forceinline__ double neighbour_sigma(double z, double L, double U, bool hasL, bool hasU, double ps, int n,
+                                                  int i) {
+  double s = 0.0;
+  if (hasL) s = z - L;
+  if (hasU) s = hasL ? fmax(s, U - z) : U - z;
+  const double m = (double)n + (double)i + 1.0;
+  return fmin(fmax(s, ps / fmin(100.0, m + 2.0)), ps);
+}
+
+// joint.quant_bin_masses' three-way rule on the two smaller tails
+__device__ __forceinline__ double bin_mass(double ta, double sa, double tb, double sb) {
+  return tb <= 0.0 ? sb - sa : (ta >= 0.0 ? sa - sb : 1.0 - sa - sb);
+}
+
+struct PickLdsCont {
+  float sL[kThreads], sU[kThreads];
+  double sterm[kMaxD];
+  Pick slot[kThreads / 64];
+};
+struct PickLdsMixed : PickLdsCont {
+  double dL[kThreads], dU[kThreads];
+  double qc[kMaxQ], qs[kMaxQ];
+  double st[kMaxV + 1], ss[kMaxV + 1];
+};
+template <bool kMixed>
+using PickLds = std::conditional_t<kMixed, PickLdsMixed, PickLdsCont>;
+
+// Liar `i` (ordinal among all liars) at the f32 row src[D] (nullptr: a row of
+// zeros): bandwidths, liar_sigma, the row and (<true>) the bin tables.  S = the
+// largest multiple of Dc up to 256 threads scan: thread t serves dimension
+// t % Dc and the points t / Dc, t / Dc + S / Dc, ..., so a sweep reads S
+// consecutive floats.  zcopy: where the row is also copied to, bit for bit.
+template <bool kMixed>
+__device__ __forceinline__ void add_liar(const Params<kMixed>& p, int i, const float* __restrict__ src,
+                                         float* __restrict__ zcopy, PickLds<kMixed>& s) {
+  const int t = threadIdx.x, Dc = cont_dims<kMixed>(p), LS = row_len<kMixed>(p);
+  int DS = Dc;                                  // the width of a liar_sigma row
+  if constexpr (kMixed) DS += p.Dq;
+  if (zcopy && t < p.D) zcopy[t] = src ? src[t] : 0.f;
+  if (!kMixed || Dc > 0) {
+    const int S = (kThreads / Dc) * Dc, d = t % Dc;
+    const float zd = src ? src[d] : 0.f;
+    float L = -INFINITY, U = INFINITY;          // -inf / +inf: no neighbour on that side
+    if (t < S) {
+      const int64_t total = (int64_t)p.K * Dc;
+      for (int64_t e = t; e < total; e += S) {
+        const float x = p.amu[e];
+        if (x <= zd) L = fmaxf(L, x);
+        else if (x > zd) U = fminf(U, x);
+      }
+      for (int q = t / Dc; q < i; q += S / Dc) {
+        const float x = (float)p.rows[(int64_t)q * LS + d];   // an earlier liar's f32 coordinate
+        if (x <= zd) L = fmaxf(L, x);
+        else if (x > zd) U = fminf(U, x);
+      }
     }
-    for (int q = t / D; q < i; q += S / D) {
-      const float x = (float)p.rows[(int64_t)q * LS + d];   // an earlier liar's f32 coordinate
-      if (x <= zd) L = fmaxf(L, x);
-      else if (x > zd) U = fminf(U, x);
+    s.sL[t] = L;
+    s.sU[t] = U;
+    __syncthreads();
+    if (t < Dc) {
+      for (int u = t + Dc; u < S; u += Dc) { L = fmaxf(L, s.sL[u]); U = fminf(U, s.sU[u]); }
+      const double z = (double)zd;
+      const double sg = neighbour_sigma(z, (double)L, (double)U, L != -INFINITY, U != INFINITY, p.psig[d], p.n, i);
+      p.liar_sigma[(int64_t)i * DS + d] = sg;
+      double* row = p.rows + (int64_t)i * LS;   // (formed here: held across the sweep it costs <false> 12 VGPRs)
+      row[d] = z;
+      row[Dc + d] = kSqrtHalf / sg;
+      // the mass of the normal truncated to the label's bounds (joint._std_bounds)
+      const double za = (p.low[d] - z) / sg, zb = (p.high[d] - z) / sg;
+      const bool flip = za > 0.0;
+      const double a = flip ? -zb : za, b = flip ? -za : zb;
+      const double fa = 0.5 * erfc(-a * kSqrtHalf), fb = 0.5 * erfc(-b * kSqrtHalf);
+      s.sterm[d] = log(sg * 2.50662827463100050242 * (fb - fa));
     }
   }
-  sL[t] = L;
-  sU[t] = U;
-  __syncthreads();
-  if (t < D) {
-    for (int u = t + D; u < S; u += D) { L = fmaxf(L, sL[u]); U = fminf(U, sU[u]); }
-    const double z = (double)zd;
-    const bool hasL = L != -INFINITY, hasU = U != INFINITY;
-    double s = 0.0;
-    if (hasL) s = z - (double)L;
-    if (hasU) s = hasL ? fmax(s, (double)U - z) : (double)U - z;
-    const double ps = p.psig[d];
-    const double m = (double)p.n + (double)i + 1.0;
-    s = fmin(fmax(s, ps / fmin(100.0, m + 2.0)), ps);
-    p.liar_sigma[(int64_t)i * D + d] = s;
+  if constexpr (kMixed) {
+    const int Dk = p.Dk, Dq = p.Dq;
     double* row = p.rows + (int64_t)i * LS;
-    row[d] = z;
-    row[D + d] = 0.70710678118654752440 / s;
-    // the mass of the normal truncated to the label's bounds (joint._std_bounds)
-    const double za = (p.low[d] - z) / s, zb = (p.high[d] - z) / s;
-    const bool flip = za > 0.0;
-    const double a = flip ? -zb : za, b = flip ? -za : zb;
-    const double fa = 0.5 * erfc(-a * 0.70710678118654752440), fb = 0.5 * erfc(-b * 0.70710678118654752440);
-    sterm[d] = log(s * 2.50662827463100050242 * (fb - fa));
-    if (zcopy) zcopy[d] = zd;
+    if (t < Dk) {                               // a discrete dimension: the category, no bandwidth
+      const int v = src ? (int)src[Dc + t] : 0;
+      int U = 2;
+#pragma unroll
+      for (int dd = 0; dd < kMaxK; ++dd)        // (static indices into the kernel arguments: no private copy)
+        if (dd == t) U = p.cat_upper[dd];
+      row[2 * Dc + 1 + t] = (double)clampi(v, U - 1);
+    }
+    if (Dq > 0) {                               // thread t serves quantised dimension t % Dq, in float64
+      const int S = (kThreads / Dq) * Dq, d = t % Dq;
+      int V = 2, toff = 0;
+#pragma unroll
+      for (int dd = 0; dd < kMaxQ; ++dd)
+        if (dd == d) { V = p.qv[dd]; toff = p.qtoff[dd]; }
+      const int v = clampi(src ? (int)src[Dc + Dk + d] : 0, V - 1);
+      const double c = p.centre[toff + v];
+      double L = -INFINITY, U = INFINITY;
+      if (t < S) {
+        const int64_t total = (int64_t)p.K * Dq;
+        for (int64_t e = t; e < total; e += S) {
+          const double x = p.aqmu[e];
+          if (x <= c) L = fmax(L, x);
+          else if (x > c) U = fmin(U, x);
+        }
+        for (int q = t / Dq; q < i; q += S / Dq) {
+          const double x = p.rows[(int64_t)q * LS + 2 * Dc + 1 + Dk + d];   // an earlier liar's centre
+          if (x <= c) L = fmax(L, x);
+          else if (x > c) U = fmin(U, x);
+        }
+      }
+      s.dL[t] = L;
+      s.dU[t] = U;
+      __syncthreads();
+      if (t < Dq) {
+        for (int u = t + Dq; u < S; u += Dq) { L = fmax(L, s.dL[u]); U = fmin(U, s.dU[u]); }
+        const double sg = neighbour_sigma(c, L, U, L != -INFINITY, U != INFINITY, p.psig[Dc + d], p.n, i);
+        p.liar_sigma[(int64_t)i * DS + Dc + d] = sg;
+        row[2 * Dc + 1 + Dk + d] = c;
+        s.qc[d] = c;
+        s.qs[d] = sg;
+      }
+      __syncthreads();
+      for (int dd = 0; dd < Dq; ++dd) {         // T_i[dd][v] = log Q_i(v): the V + 1 tails once, then the differences
+        const int V = p.qv[dd];
+        const double* __restrict__ e = p.edges + p.qeoff[dd];
+        const double cc = s.qc[dd], sc = kSqrtHalf / s.qs[dd];
+        for (int u = t; u <= V; u += kThreads) {
+          const double tt = (e[u] - cc) * sc;
+          s.st[u] = tt;
+          s.ss[u] = fabs(tt) > kTailMax ? 0.0 : 0.5 * erfc(fabs(tt));
+        }
+        __syncthreads();
+        if (t < V) {
+          const double diff = bin_mass(s.st[t], s.ss[t], s.st[t + 1], s.ss[t + 1]);
+          const double mass = bin_mass(s.st[0], s.ss[0], s.st[V], s.ss[V]);
+          p.tabs[(int64_t)i * p.totV + p.qtoff[dd] + t] = diff > 0.0 ? log(diff / mass) : -INFINITY;
+        }
+        __syncthreads();                        // st / ss are read: the next dimension may overwrite them
+      }
+    }
   }
   __syncthreads();
   if (t == 0) {
     double c = 0.0;
-    for (int u = 0; u < D; ++u) c += sterm[u];
-    p.rows[(int64_t)i * LS + 2 * D] = -c;
+    for (int u = 0; u < Dc; ++u) c += s.sterm[u];
+    p.rows[(int64_t)i * LS + 2 * Dc] = -c;
   }
-  __syncthreads();                            // the row is written: the next liar of this launch may scan it
+  __syncthreads();                              // the row is written: the next liar of this launch may scan it
 }
 
 // step: 0 adds the given liars; j >= 1 merges step j - 1's chunk records into
 // picks[j - 1], copies its row and adds it as liar G + j - 1
-__global__ __launch_bounds__(kThreads) void k_liar_pick(const LiarK p, int step) {
-  __shared__ float sL[kThreads], sU[kThreads];
-  __shared__ double sterm[kMaxD];
-  __shared__ Pick slot[kThreads / 64];
-  const int t = threadIdx.x, D = p.D;
+template <bool kMixed>
+__global__ __launch_bounds__(kThreads) void k_liar_pick(const Params<kMixed> p, int step) {
+  __shared__ PickLds<kMixed> s;
+  const int t = threadIdx.x;
   if (step == 0) {
-    for (int i = 0; i < p.G; ++i) add_liar(p, i, p.given + (int64_t)i * D, nullptr, sL, sU, sterm);
+    for (int i = 0; i < p.G; ++i) add_liar<kMixed>(p, i, p.given + (int64_t)i * p.D, nullptr, s);
     return;
   }
   const int j = step - 1;
@@ -163,30 +309,35 @@ __global__ __launch_bounds__(kThreads) void k_liar_pick(const LiarK p, int step)
     const Pick x{score_key(r.l - r.g), r.idx};
     if (beats(x, best)) best = x;            // (chunk order = candidate index order)
   }
-  const Pick w = block_best(best, slot);
+  const Pick w = block_best(best, s.slot);
   const bool none = w.key == 0;
   if (t == 0) p.picks[j] = none ? tpe_joint_pick{-1, 0.0, 0.0} : p.chunk_rec[w.idx / TPE_JOINT_CHUNK];
-  add_liar(p, p.G + j, none ? nullptr : p.cand + ((int64_t)j * p.C + w.idx) * D, p.pick_z + (int64_t)j * D, sL, sU,
-           sterm);
+  add_liar<kMixed>(p, p.G + j, none ? nullptr : p.cand + ((int64_t)j * p.C + w.idx) * p.D,
+                   p.pick_z + (int64_t)j * p.D, s);
 }
 
 // id j's candidates under the above mixture extended by J = G + j liars
-__global__ __launch_bounds__(kThreads) void k_liar_chunk(const LiarK p, int j, double log_w, double log_norm) {
+template <bool kMixed>
+__global__ __launch_bounds__(kThreads) void k_liar_chunk(const Params<kMixed> p, int j, double log_w,
+                                                         double log_norm) {
   __shared__ double tile[kTile * kMaxRow];
   __shared__ Pick slot[kThreads / 64];
-  const int t = threadIdx.x, D = p.D, LS = 2 * D + 1, J = p.G + j;
+  const int t = threadIdx.x, D = p.D, Dc = cont_dims<kMixed>(p), LS = row_len<kMixed>(p), J = p.G + j;
   const int first = blockIdx.x * TPE_JOINT_CHUNK;
   const int64_t o = (int64_t)j * p.C;
 
   double m[kR], s[kR];
 #pragma unroll
-  for (int r = 0; r < kR; ++r) { m[r] = -1.0e300; s[r] = 0.0; }
+  for (int r = 0; r < kR; ++r) { m[r] = -1.0e300; s[r] = 0.0; }   // a finite floor: all terms -inf leave s = 0, no NaN
   for (int q0 = 0; q0 < J; q0 += kTile) {
     const int nq = min(kTile, J - q0), nq4 = (nq + kQ - 1) / kQ * kQ;
     __syncthreads();                         // the previous tile is read
     for (int e = t; e < nq4 * LS; e += kThreads) {
-      const int q = e / LS, f = e % LS;      // a padded liar: h = 0, c = -inf adds nothing
-      tile[e] = q < nq ? p.rows[(int64_t)(q0 + q) * LS + f] : (f == 2 * D ? -INFINITY : 0.0);
+      const int q = e / LS, f = e % LS;      // a padded liar: h = 0, c = -inf, category -1 adds nothing
+      double pad = f == 2 * Dc ? -INFINITY : 0.0;
+      if constexpr (kMixed)
+        if (f > 2 * Dc) pad = -1.0;
+      tile[e] = q < nq ? p.rows[(int64_t)(q0 + q) * LS + f] : pad;
     }
     __syncthreads();
 #pragma unroll
@@ -196,24 +347,39 @@ __global__ __launch_bounds__(kThreads) void k_liar_chunk(const LiarK p, int j, d
       const float* __restrict__ zr = p.cand + (o + i) * D;
       for (int qq = 0; qq < nq4; qq += kQ) {
         const double* __restrict__ row = tile + qq * LS;
-        double acc[kQ];
+        double acc[kQ], tt[kQ];
 #pragma unroll
         for (int u = 0; u < kQ; ++u) acc[u] = 0.0;
-        for (int d = 0; d < D; ++d) {
+        for (int d = 0; d < Dc; ++d) {
           const double zd = (double)zr[d];
 #pragma unroll
           for (int u = 0; u < kQ; ++u) {
-            const double x = (zd - row[u * LS + d]) * row[u * LS + D + d];
+            const double x = (zd - row[u * LS + d]) * row[u * LS + Dc + d];
             acc[u] = fma(x, x, acc[u]);
           }
         }
 #pragma unroll
+        for (int u = 0; u < kQ; ++u) tt[u] = row[u * LS + 2 * Dc] - acc[u];
+        if constexpr (kMixed) {
+          for (int d = 0; d < p.Dk; ++d) {   // one compare, one select, one add per (candidate, liar)
+            const double vc = (double)zr[Dc + d];
+            const double b = p.bonus[p.cat_off[d] + clampi((int)vc, p.cat_upper[d] - 1)];
+#pragma unroll
+            for (int u = 0; u < kQ; ++u) tt[u] += row[u * LS + 2 * Dc + 1 + d] == vc ? b : 0.0;
+          }
+          for (int d = 0; d < p.Dq; ++d) {   // one table read at the candidate's own lattice index
+            const int v = p.qtoff[d] + clampi((int)zr[Dc + p.Dk + d], p.qv[d] - 1);
+#pragma unroll
+            for (int u = 0; u < kQ; ++u)     // (a padded liar reads the last real one's table: its c is -inf)
+              tt[u] += p.tabs[(int64_t)min(q0 + qq + u, J - 1) * p.totV + v];
+          }
+        }
+#pragma unroll
         for (int u = 0; u < kQ; ++u) {
-          const double tt = row[u * LS + 2 * D] - acc[u];
-          const double dl = tt - m[r];
+          const double dl = tt[u] - m[r];
           const double e2 = exp(-fabs(dl));
           s[r] = dl > 0.0 ? fma(s[r], e2, 1.0) : s[r] + e2;
-          m[r] = fmax(m[r], tt);
+          m[r] = fmax(m[r], tt[u]);
         }
       }
     }
@@ -229,7 +395,16 @@ __global__ __launch_bounds__(kThreads) void k_liar_chunk(const LiarK p, int j, d
     lv[r] = p.l_out[o + i];
     double g = p.g_out[o + i];
     if (J > 0 && g == g) {                   // logaddexp(g, lse - log W) - log1p(J / W)
-      const double x = m[r] + log(s[r]) - log_w;
+      double x;
+      if constexpr (kMixed) {
+        const float* __restrict__ zr = p.cand + (o + i) * D;
+        double miss = 0.0;                   // sum_d miss_d(v_d): the candidate's alone
+        for (int d = 0; d < p.Dk; ++d)
+          miss += p.miss[p.cat_off[d] + clampi((int)zr[Dc + d], p.cat_upper[d] - 1)];
+        x = m[r] + log(s[r]) + miss - log_w;
+      } else {
+        x = m[r] + log(s[r]) - log_w;
+      }
       const double hi = fmax(g, x), lo = fmin(g, x);
       g = (hi == -INFINITY ? hi : hi + log1p(exp(lo - hi))) - log_norm;
     }
@@ -250,13 +425,88 @@ __global__ __launch_bounds__(kThreads) void k_liar_chunk(const LiarK p, int j, d
     if (r == off / kThreads) *rec = tpe_joint_pick{w.idx, lv[r], gv[r]};
 }
 
-// the scratch of one call in bytes, or false where the sizes are out of range
-bool liar_scratch(int32_t n_ids, int32_t n_cand, int32_t n_dims, int32_t n_given, uint64_t* rows_bytes, uint64_t* bytes) {
-  if (n_ids < 1 || n_cand < 1 || n_dims < 1 || n_dims > kMaxD || n_given < 0) return false;
+struct Sizes {
+  uint64_t rows_bytes, tabs_bytes, bytes;
+};
+
+// the scratch of one call, or false where the sizes are out of range
+bool liar_scratch(int32_t n_ids, int32_t n_cand, int32_t n_dims, int32_t n_cat, int32_t n_quant, int32_t n_lattice,
+                  int32_t n_given, Sizes* z) {
+  if (n_ids < 1 || n_cand < 1 || n_dims < 0 || n_cat < 0 || n_quant < 0 || n_given < 0 || n_lattice < 0) return false;
+  if (n_cat > kMaxK || n_quant > kMaxQ || n_lattice > TPE_JOINT_MAX_LATTICE_TOTAL) return false;
+  const int D = n_dims + n_cat + n_quant;
+  if (D < 1 || D > kMaxD || (n_quant == 0) != (n_lattice == 0)) return false;
   const uint64_t chunks = ((uint64_t)n_cand + TPE_JOINT_CHUNK - 1) / TPE_JOINT_CHUNK;
-  *rows_bytes = ((uint64_t)n_ids + (uint64_t)n_given) * (2 * (uint64_t)n_dims + 1) * sizeof(double);
-  *bytes = *rows_bytes + chunks * sizeof(tpe_joint_pick);
+  const uint64_t liars = (uint64_t)n_ids + (uint64_t)n_given;
+  z->rows_bytes = liars * (2 * (uint64_t)n_dims + 1 + (uint64_t)n_cat + (uint64_t)n_quant) * sizeof(double);
+  z->tabs_bytes = liars * (uint64_t)n_lattice * sizeof(double);
+  z->bytes = z->rows_bytes + z->tabs_bytes + chunks * sizeof(tpe_joint_pick);
   return true;
+}
+
+// TPE_E_ARG with the message "<who>: <what>"
+int bad(const char* who, const char* what) {
+  char msg[192];
+  snprintf(msg, sizeof(msg), "%s: %s", who, what);
+  return tpe_internal_fail(TPE_E_ARG, msg);
+}
+
+// The checks of the prefix both args structs share, in the entry `who`'s words;
+// x: the whole struct of tpe_joint_liar_mixed (nullptr: tpe_joint_liar, n_dims
+// alone is the row).
+int check_args(const char* who, const tpe_joint_liar_args* a, const tpe_joint_liar_mixed_args* x,
+               const tpe_joint_pick* picks, const float* pick_z, const double* liar_sigma) {
+  const int Dc = a->n_dims, Dk = x ? x->n_cat : 0, Dq = x ? x->n_quant : 0;
+  if (!x) {
+    if (Dc < 1 || Dc > kMaxD) return bad(who, "n_dims outside [1, TPE_JOINT_WIDE_MAX_DIMS]");
+  } else {
+    if (Dc < 0 || Dk < 0 || Dq < 0) return bad(who, "n_dims / n_cat / n_quant < 0");
+    if (Dk > kMaxK || Dq > kMaxQ)
+      return bad(who, "n_cat above TPE_JOINT_MAX_DIMS or n_quant above TPE_JOINT_MAX_QUANT");
+    if (Dc + Dk + Dq < 1 || Dc + Dk + Dq > kMaxD) return bad(who, "row width outside [1, TPE_JOINT_WIDE_MAX_DIMS]");
+    if (Dq > 0 && (Dc > 8 || Dk > 4)) return bad(who, "beside a quantised label n_dims <= 8 and n_cat <= 4");
+  }
+  if (a->n_ids < 1 || a->n_cand < 1 || a->k_above < 1) return bad(who, "n_ids / n_cand / k_above < 1");
+  if (a->n_given < 0 || a->n_trials < 0) return bad(who, "n_given / n_trials < 0");
+  if (!(a->w_sum > 0.0) || !(a->w_sum < INFINITY)) return bad(who, "w_sum must be positive and finite");
+  if (!a->cand || !a->l_out || !a->g_out || (Dc > 0 && !a->above_mu))
+    return bad(who, "null cand / l_out / g_out / above_mu");
+  if (a->n_given > 0 && !a->given) return bad(who, "n_given > 0 without given");
+  if (!picks || !pick_z || !liar_sigma) return bad(who, "null outputs");
+  for (int d = 0; d < Dc + Dq; ++d)             // the continuous dimensions, then the quantised ones
+    if (!(a->psig[d] > 0.0)) return bad(who, "a prior sigma that is not positive");
+  return TPE_OK;
+}
+
+// The shared fields of `k` from the checked prefix (the instantiation's own are
+// the caller's), then the launches: the given liars, then a chunk and a pick
+// launch per id.  D: the row width; Dq: the quantised dimensions.
+template <bool kMixed>
+int run(Params<kMixed>& k, const tpe_joint_liar_args* a, int D, int Dq, tpe_joint_pick* picks, float* pick_z,
+        double* liar_sigma, void* scratch, const Sizes& z, void* stream) {
+  k.D = D; k.C = a->n_cand; k.K = a->k_above; k.G = a->n_given; k.n = a->n_trials;
+  k.n_chunks = (int)(((int64_t)a->n_cand + TPE_JOINT_CHUNK - 1) / TPE_JOINT_CHUNK);
+  k.cand = a->cand; k.l_out = a->l_out; k.g_out = a->g_out; k.amu = a->above_mu; k.given = a->given;
+  k.rows = (double*)scratch;
+  k.chunk_rec = (tpe_joint_pick*)((char*)scratch + z.rows_bytes + z.tabs_bytes);
+  k.picks = picks; k.pick_z = pick_z; k.liar_sigma = liar_sigma;
+  for (int d = 0; d < kMaxD; ++d) {
+    const bool cont = d < a->n_dims, in = cont || d < a->n_dims + Dq;
+    k.psig[d] = in ? a->psig[d] : 1.0;
+    k.low[d] = cont ? a->low[d] : -INFINITY;
+    k.high[d] = cont ? a->high[d] : INFINITY;
+  }
+  const hipStream_t s = (hipStream_t)stream;
+  const double log_w = log(a->w_sum);
+  if (k.G > 0) hipLaunchKernelGGL(k_liar_pick<kMixed>, dim3(1), dim3(kThreads), 0, s, k, 0);
+  for (int j = 0; j < a->n_ids; ++j) {
+    hipLaunchKernelGGL(k_liar_chunk<kMixed>, dim3((unsigned)k.n_chunks), dim3(kThreads), 0, s, k, j, log_w,
+                       log1p((double)(k.G + j) / a->w_sum));
+    hipLaunchKernelGGL(k_liar_pick<kMixed>, dim3(1), dim3(kThreads), 0, s, k, j + 1);
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
+  return TPE_OK;
 }
 
 }  // namespace
@@ -264,57 +514,97 @@ bool liar_scratch(int32_t n_ids, int32_t n_cand, int32_t n_dims, int32_t n_given
 extern "C" {
 
 int tpe_joint_liar_scratch_bytes(int32_t n_ids, int32_t n_cand, int32_t n_dims, int32_t n_given, uint64_t* bytes) {
-  uint64_t rows_bytes = 0;
-  if (!bytes || !liar_scratch(n_ids, n_cand, n_dims, n_given, &rows_bytes, bytes))
+  Sizes z;
+  if (!bytes || n_dims < 1 || !liar_scratch(n_ids, n_cand, n_dims, 0, 0, 0, n_given, &z))
     return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar_scratch_bytes: bad arguments");
+  *bytes = z.bytes;
+  return TPE_OK;
+}
+
+int tpe_joint_liar_mixed_scratch_bytes(int32_t n_ids, int32_t n_cand, int32_t n_dims, int32_t n_cat, int32_t n_quant,
+                                       int32_t n_lattice, int32_t n_given, uint64_t* bytes) {
+  Sizes z;
+  if (!bytes || !liar_scratch(n_ids, n_cand, n_dims, n_cat, n_quant, n_lattice, n_given, &z))
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar_mixed_scratch_bytes: bad arguments");
+  *bytes = z.bytes;
   return TPE_OK;
 }
 
 int tpe_joint_liar(const tpe_joint_liar_args* a, tpe_joint_pick* picks, float* pick_z, double* liar_sigma,
                    void* scratch, uint64_t scratch_bytes, void* stream) {
+  const char* who = "tpe_joint_liar";
   tpe_internal_epoch_bump();
-  if (!a) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar: null args");
-  if (a->n_dims < 1 || a->n_dims > kMaxD)
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar: n_dims outside [1, TPE_JOINT_WIDE_MAX_DIMS]");
-  if (a->n_ids < 1 || a->n_cand < 1 || a->k_above < 1)
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar: n_ids / n_cand / k_above < 1");
-  if (a->n_given < 0 || a->n_trials < 0) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar: n_given / n_trials < 0");
-  if (!(a->w_sum > 0.0) || !(a->w_sum < INFINITY))
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar: w_sum must be positive and finite");
-  if (!a->cand || !a->l_out || !a->g_out || !a->above_mu)
-    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar: null cand / l_out / g_out / above_mu");
-  if (a->n_given > 0 && !a->given) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar: n_given > 0 without given");
-  if (!picks || !pick_z || !liar_sigma) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar: null outputs");
-  for (int d = 0; d < a->n_dims; ++d)
-    if (!(a->psig[d] > 0.0)) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar: a prior sigma that is not positive");
-  uint64_t rows_bytes = 0, need = 0;
-  liar_scratch(a->n_ids, a->n_cand, a->n_dims, a->n_given, &rows_bytes, &need);
-  if (!scratch || scratch_bytes < need) return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar: scratch too small");
-
+  if (!a) return bad(who, "null args");
+  if (const int rc = check_args(who, a, nullptr, picks, pick_z, liar_sigma)) return rc;
+  Sizes z;
+  liar_scratch(a->n_ids, a->n_cand, a->n_dims, 0, 0, 0, a->n_given, &z);
+  if (!scratch || scratch_bytes < z.bytes) return bad(who, "scratch too small");
   LiarK k;
-  k.D = a->n_dims; k.C = a->n_cand; k.K = a->k_above; k.G = a->n_given; k.n = a->n_trials;
-  k.n_chunks = (int)(((int64_t)a->n_cand + TPE_JOINT_CHUNK - 1) / TPE_JOINT_CHUNK);
-  k.cand = a->cand; k.l_out = a->l_out; k.g_out = a->g_out; k.amu = a->above_mu; k.given = a->given;
-  k.rows = (double*)scratch;
-  k.chunk_rec = (tpe_joint_pick*)((char*)scratch + rows_bytes);
-  k.picks = picks; k.pick_z = pick_z; k.liar_sigma = liar_sigma;
-  for (int d = 0; d < kMaxD; ++d) {
-    const bool in = d < a->n_dims;
-    k.psig[d] = in ? a->psig[d] : 1.0;
-    k.low[d] = in ? a->low[d] : -INFINITY;
-    k.high[d] = in ? a->high[d] : INFINITY;
+  return run<false>(k, a, a->n_dims, 0, picks, pick_z, liar_sigma, scratch, z, stream);
+}
+
+int tpe_joint_liar_mixed(const tpe_joint_liar_mixed_args* a, tpe_joint_pick* picks, float* pick_z, double* liar_sigma,
+                         void* scratch, uint64_t scratch_bytes, void* stream) {
+  const char* who = "tpe_joint_liar_mixed";
+  const tpe_joint_liar_args* pre = (const tpe_joint_liar_args*)a;   // (the shared prefix)
+  if (!a) {
+    tpe_internal_epoch_bump();
+    return bad(who, "null args");
   }
-  const hipStream_t s = (hipStream_t)stream;
-  const double log_w = log(a->w_sum);
-  if (k.G > 0) hipLaunchKernelGGL(k_liar_pick, dim3(1), dim3(kThreads), 0, s, k, 0);
-  for (int j = 0; j < a->n_ids; ++j) {
-    hipLaunchKernelGGL(k_liar_chunk, dim3((unsigned)k.n_chunks), dim3(kThreads), 0, s, k, j, log_w,
-                       log1p((double)(k.G + j) / a->w_sum));
-    hipLaunchKernelGGL(k_liar_pick, dim3(1), dim3(kThreads), 0, s, k, j + 1);
+  // a continuous group: tpe_joint_liar over the shared prefix, its checks and its bytes
+  if (a->n_cat == 0 && a->n_quant == 0)
+    return tpe_joint_liar(pre, picks, pick_z, liar_sigma, scratch, scratch_bytes, stream);
+  tpe_internal_epoch_bump();
+  if (const int rc = check_args(who, pre, a, picks, pick_z, liar_sigma)) return rc;
+  const int Dc = a->n_dims, Dk = a->n_cat, Dq = a->n_quant;
+  int64_t cat_total = 0, lat_total = 0;
+  if (Dk > 0) {
+    if (!a->cat_miss || !a->cat_bonus) return bad(who, "null category table");
+    for (int d = 0; d < Dk; ++d) {
+      if (a->cat_upper[d] < 2 || a->cat_upper[d] > TPE_JOINT_MAX_CATS)
+        return bad(who, "a U_d outside [2, TPE_JOINT_MAX_CATS]");
+      cat_total += a->cat_upper[d];
+    }
+    if (cat_total > TPE_JOINT_MAX_CAT_TOTAL) return bad(who, "more than TPE_JOINT_MAX_CAT_TOTAL categories");
+    for (int d = 0; d < Dk; ++d)
+      if (a->cat_off[d] < 0 || a->cat_off[d] > cat_total - a->cat_upper[d])
+        return bad(who, "a cat_off that leaves the table");
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
-  return TPE_OK;
+  if (Dq > 0) {
+    if (!a->quant_edges || !a->quant_centre || !a->above_qmu)
+      return bad(who, "null quant_edges / quant_centre / above_qmu");
+    for (int d = 0; d < Dq; ++d) {
+      if (a->quant_v[d] < 2 || a->quant_v[d] > kMaxV) return bad(who, "a V_d outside [2, TPE_JOINT_MAX_LATTICE]");
+      lat_total += a->quant_v[d];
+    }
+    if (lat_total > TPE_JOINT_MAX_LATTICE_TOTAL)
+      return bad(who, "more than TPE_JOINT_MAX_LATTICE_TOTAL lattice values");
+    for (int d = 0; d < Dq; ++d)
+      if (a->quant_edge_off[d] < 0 || a->quant_edge_off[d] > a->n_edges - a->quant_v[d] - 1)
+        return bad(who, "a quant_edge_off that leaves quant_edges");
+  }
+  Sizes z;
+  if (!liar_scratch(a->n_ids, a->n_cand, Dc, Dk, Dq, (int32_t)lat_total, a->n_given, &z))
+    return bad(who, "sizes out of range");
+  if (!scratch || scratch_bytes < z.bytes) return bad(who, "scratch too small");
+
+  LiarMK k;
+  k.Dc = Dc; k.Dk = Dk; k.Dq = Dq; k.LS = 2 * Dc + 1 + Dk + Dq; k.totV = (int)lat_total;
+  k.aqmu = a->above_qmu; k.miss = a->cat_miss; k.bonus = a->cat_bonus; k.edges = a->quant_edges;
+  k.centre = a->quant_centre;
+  k.tabs = (double*)((char*)scratch + z.rows_bytes);
+  for (int d = 0; d < kMaxK; ++d) {
+    k.cat_upper[d] = d < Dk ? a->cat_upper[d] : 2;
+    k.cat_off[d] = d < Dk ? a->cat_off[d] : 0;
+  }
+  int toff = 0;
+  for (int d = 0; d < kMaxQ; ++d) {
+    k.qv[d] = d < Dq ? a->quant_v[d] : 2;
+    k.qeoff[d] = d < Dq ? a->quant_edge_off[d] : 0;
+    k.qtoff[d] = d < Dq ? toff : 0;
+    if (d < Dq) toff += a->quant_v[d];
+  }
+  return run<true>(k, pre, Dc + Dk + Dq, Dq, picks, pick_z, liar_sigma, scratch, z, stream);
 }
 
 }  // extern "C"

@@ -1327,8 +1327,7 @@ class Engine(object):
             rep = self._joint_report(d_cand.data_ptr(), d_l.data_ptr(), d_g.data_ptr(), n_ids, C, report_k, stream,
                                      width=D)
         if liar is not None:
-            enq = self._joint_liar_mixed if liar.get('mixed') else self._joint_liar
-            lr = enq(a, liar, d_cand.data_ptr(), d_l.data_ptr(), d_g.data_ptr(), n_ids, C, D, stream)
+            lr = self._joint_liar(a, liar, d_cand.data_ptr(), d_l.data_ptr(), d_g.data_ptr(), n_ids, C, D, stream)
         rec = d_rec[:n_ids * rec_dtype.itemsize // 8].cpu().numpy().view(rec_dtype).copy()
         if liar is not None:
             d_picks, d_z, d_sig, G = lr
@@ -1351,37 +1350,13 @@ class Engine(object):
         return tuple(out)
 
     def _joint_liar(self, a, liar, cand, l, g, n_ids, C, D, stream):
-        """Enqueue tpe_joint_liar over the device buffers the continuous joint
-        stage ``a`` just wrote; returns the device tensors (picks, pick_z,
+        """Enqueue tpe_joint_liar_mixed (a continuous group: the library runs
+        tpe_joint_liar on the shared prefix) over the device buffers the joint
+        stage ``a`` just wrote (the lattice edges and the above side's rows are
+        the stage's own uploads); returns the device tensors (picks, pick_z,
         liar_sigma) and the number of given liars."""
         given = liar['given']
-        G = len(given)
-        la = N.JointLiarArgs()
-        la.n_dims, la.n_cand, la.n_ids, la.n_given = D, C, n_ids, G
-        la.k_above, la.n_trials, la.w_sum = a.k_above, a.k_above - 1, liar['W']
-        la.cand, la.l_out, la.g_out, la.above_mu = cand, l, g, a.above_mu
-        if G:
-            la.given = self._joint_up('liar_given', given, torch.float32)
-        for d in range(D):
-            la.psig[d], la.low[d], la.high[d] = liar['psig'][d], liar['low'][d], liar['high'][d]
-        nb = ctypes.c_uint64(0)
-        N.check(self.lib.tpe_joint_liar_scratch_bytes(n_ids, C, D, G, ctypes.byref(nb)), self.lib,
-                'tpe_joint_liar_scratch_bytes')
-        d_scr = self._buf('joint_liar_scratch', (nb.value + 7) // 8, torch.float64)
-        d_picks = self._buf('joint_liar_picks', n_ids * 3, torch.float64)
-        d_z = self._buf('joint_liar_z', n_ids * D, torch.float32)
-        d_sig = self._buf('joint_liar_sigma', (G + n_ids) * D, torch.float64)
-        N.check(self.lib.tpe_joint_liar(ctypes.byref(la), d_picks.data_ptr(), d_z.data_ptr(), d_sig.data_ptr(),
-                                        d_scr.data_ptr(), d_scr.numel() * 8, ctypes.c_void_p(stream)), self.lib,
-                'tpe_joint_liar')
-        return d_picks, d_z, d_sig, G
-
-    def _joint_liar_mixed(self, a, liar, cand, l, g, n_ids, C, D, stream):
-        """Enqueue tpe_joint_liar_mixed over the device buffers the mixed, wide
-        mixed or quantised stage ``a`` just wrote (the lattice edges and the
-        above side's rows are the stage's own uploads); returns as _joint_liar."""
-        given = liar['given']
-        G, Dc, Dk, Dq = len(given), a.n_dims, a.n_cat, getattr(a, 'n_quant', 0)
+        G, Dc, Dk, Dq = len(given), a.n_dims, getattr(a, 'n_cat', 0), getattr(a, 'n_quant', 0)
         la = N.JointLiarMixedArgs()
         la.n_dims, la.n_cand, la.n_ids, la.n_given = Dc, C, n_ids, G
         la.k_above, la.n_trials, la.w_sum = a.k_above, a.k_above - 1, liar['W']

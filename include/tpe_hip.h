@@ -1728,8 +1728,9 @@ int tpe_joint_run_shard(int32_t stage, const void* args, const tpe_joint_shard* 
                         double* l_out, double* g_out, void* scratch, uint64_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
- * Batch-aware joint suggests (tpe_joint_liar.hip; additive exports, the ABI
- * stays 24).  A follow-up stage of tpe_joint_run / tpe_joint_wide_run, enqueued
+ * Batch-aware joint suggests (tpe_joint_liar.hip, which also holds the stage
+ * for discrete and quantised labels below; additive exports, the ABI stays
+ * 24).  A follow-up stage of tpe_joint_run / tpe_joint_wide_run, enqueued
  * after the stage that wrote cand, l_out and g_out (as tpe_joint_report is):
  * the ids pick greedily, in the order given.  Id 0 picks as the stage itself
  * does; its vector then joins the above mixture as one more component, a
@@ -1758,9 +1759,10 @@ int tpe_joint_run_shard(int32_t stage, const void* args, const tpe_joint_shard* 
  *
  * Outputs: picks[j] = {candidate index, l, g_j}; pick_z[j * n_dims ..] the
  * winner's row, copied bit for bit; liar_sigma[i * n_dims ..] for every liar
- * (the last pick's too).  2 launches a step (a one-workgroup pick kernel, a
- * chunk kernel over TPE_JOINT_CHUNK candidates a workgroup; liar rows stream
- * through LDS in tiles of TPE_JOINT_LIAR_TILE), ordered by the stream alone.
+ * (the last pick's too).  2 launches a step (k_liar_pick<false>, one workgroup,
+ * and k_liar_chunk<false>, TPE_JOINT_CHUNK candidates a workgroup; liar rows
+ * stream through LDS in tiles of TPE_JOINT_LIAR_TILE), ordered by the stream
+ * alone.
  * No atomics: the same call twice gives the same bytes.
  *
  * tpe_joint_liar_scratch_bytes = (n_given + n_ids) (2 n_dims + 1) 8 +
@@ -1796,7 +1798,8 @@ int tpe_joint_liar(const tpe_joint_liar_args* args, tpe_joint_pick* picks, float
 
 /* ------------------------------------------------------------------------
  * Batch-aware picks over discrete and quantised labels
- * (tpe_joint_liar_mixed.hip; additive exports, the ABI stays 24).  The liar
+ * (tpe_joint_liar.hip, the <true> instantiations of its two kernel templates;
+ * additive exports, the ABI stays 24).  The liar
  * stage above for a group that also holds n_cat discrete and / or n_quant
  * quantised labels: a follow-up of tpe_joint_mixed_run, tpe_joint_wide_mixed_run
  * or tpe_joint_quant_run, enqueued after the stage that wrote cand, l_out and
@@ -1838,9 +1841,9 @@ int tpe_joint_liar(const tpe_joint_liar_args* args, tpe_joint_pick* picks, float
  * Outputs: picks[j] as tpe_joint_liar; pick_z[j * D ..] the winner's row, bit
  * for bit; liar_sigma[i * (n_dims + n_quant) ..]: the continuous dimensions,
  * then the quantised ones, for every liar (the last pick's too).  2 launches a
- * step: k_liar_mixed_pick (one workgroup: merge, row copy, the two neighbour
+ * step: k_liar_pick<true> (one workgroup: merge, row copy, the two neighbour
  * sweeps, then the liar's tables T_i[d][v] = ln Q_i(v), one thread per lattice
- * value, the V_d + 1 tails once through LDS) and k_liar_mixed_chunk
+ * value, the V_d + 1 tails once through LDS) and k_liar_chunk<true>
  * (TPE_JOINT_CHUNK candidates a workgroup, four a lane; liar rows {mu, sqrt(1/2)
  * / sigma, c, category, centre} through LDS in tiles of TPE_JOINT_LIAR_TILE;
  * per (candidate, liar) one compare-select-add per discrete dimension and one
