@@ -329,6 +329,42 @@ class JointLiarMixedArgs(ctypes.Structure):
     ]
 
 
+class JointLiarSeg(ctypes.Structure):
+    """tpe_joint_liar_seg_desc: the device descriptor of one group of a tpe_joint_liar_seg."""
+    _fields_ = [
+        ('n_dims', ctypes.c_int32), ('k_above', ctypes.c_int32), ('n_trials', ctypes.c_int32),
+        ('chain_len', ctypes.c_int32), ('chain_first', ctypes.c_int32), ('reserved', ctypes.c_int32),
+        ('w_sum', ctypes.c_double), ('log_w', ctypes.c_double),
+        ('above_mu', ctypes.c_int64), ('row_off', ctypes.c_int64), ('sigma_off', ctypes.c_int64),
+        ('psig', ctypes.c_double * JOINT_MAX_DIMS), ('low', ctypes.c_double * JOINT_MAX_DIMS),
+        ('high', ctypes.c_double * JOINT_MAX_DIMS),
+    ]
+
+
+# numpy mirror of tpe_joint_liar_seg_desc (an array of them is uploaded in one transfer)
+JOINT_LIAR_SEG_DTYPE = np.dtype([
+    ('n_dims', '<i4'), ('k_above', '<i4'), ('n_trials', '<i4'), ('chain_len', '<i4'), ('chain_first', '<i4'),
+    ('reserved', '<i4'), ('w_sum', '<f8'), ('log_w', '<f8'), ('above_mu', '<i8'), ('row_off', '<i8'),
+    ('sigma_off', '<i8'), ('psig', '<f8', (JOINT_MAX_DIMS,)), ('low', '<f8', (JOINT_MAX_DIMS,)),
+    ('high', '<f8', (JOINT_MAX_DIMS,))])
+assert JOINT_LIAR_SEG_DTYPE.itemsize == ctypes.sizeof(JointLiarSeg) == 448
+
+
+class JointLiarSegArgs(ctypes.Structure):
+    """tpe_joint_liar_seg_args: one tpe_joint_liar_seg."""
+    _fields_ = [
+        ('n_segs', ctypes.c_int32), ('n_probs', ctypes.c_int32), ('n_cand', ctypes.c_int32),
+        ('reserved', ctypes.c_int32),
+        ('segs', ctypes.c_void_p), ('host_segs', ctypes.c_void_p),
+        ('order', ctypes.c_void_p), ('host_order', ctypes.c_void_p),
+        ('chain', ctypes.c_void_p), ('host_chain', ctypes.c_void_p),
+        ('log_norm', ctypes.c_void_p), ('host_log_norm', ctypes.c_void_p),
+        ('host_prob_seg', ctypes.c_void_p),
+        ('cand', ctypes.c_void_p), ('cand_off', ctypes.c_void_p), ('l_out', ctypes.c_void_p),
+        ('g_out', ctypes.c_void_p), ('pool_f32', ctypes.c_void_p), ('pool_f32_len', ctypes.c_int64),
+    ]
+
+
 class LabelIn(ctypes.Structure):
     _fields_ = [
         ('family', ctypes.c_int32), ('flags', ctypes.c_int32), ('upper', ctypes.c_int32),
@@ -478,7 +514,8 @@ EXPORTS = ('tpe_abi_version', 'tpe_last_error', 'tpe_device_count', 'tpe_tile_si
            'tpe_joint_seg_scratch_bytes', 'tpe_joint_seg_run', 'tpe_joint_mseg_scratch_bytes',
            'tpe_joint_mseg_table_bytes', 'tpe_joint_mseg_run', 'tpe_joint_report_scratch_bytes',
            'tpe_joint_report', 'tpe_joint_report_profile', 'tpe_joint_run_shard', 'tpe_joint_liar_scratch_bytes',
-           'tpe_joint_liar', 'tpe_joint_liar_mixed_scratch_bytes', 'tpe_joint_liar_mixed')
+           'tpe_joint_liar', 'tpe_joint_liar_mixed_scratch_bytes', 'tpe_joint_liar_mixed',
+           'tpe_joint_liar_seg_scratch_bytes', 'tpe_joint_liar_seg')
 
 # host phases of tpe_suggest_tree (tpe_host_phases order)
 PHASES = ('prefit', 'pack', 'launched', 'synced', 'level', 'return', 'recs')
@@ -639,6 +676,10 @@ def load(path=LIB_PATH):
     lib.tpe_joint_liar_mixed_scratch_bytes.restype = ctypes.c_int
     lib.tpe_joint_liar_mixed.argtypes = [ctypes.POINTER(JointLiarMixedArgs), P, P, P, P, ctypes.c_uint64, P]
     lib.tpe_joint_liar_mixed.restype = ctypes.c_int
+    lib.tpe_joint_liar_seg_scratch_bytes.argtypes = [P, I32, I32, ctypes.POINTER(ctypes.c_uint64)]
+    lib.tpe_joint_liar_seg_scratch_bytes.restype = ctypes.c_int
+    lib.tpe_joint_liar_seg.argtypes = [ctypes.POINTER(JointLiarSegArgs), P, P, P, P, ctypes.c_uint64, P]
+    lib.tpe_joint_liar_seg.restype = ctypes.c_int
     lib.tpe_joint_profile.argtypes = [I32, P]
     lib.tpe_joint_profile.restype = ctypes.c_int
     lib.tpe_level_profile.argtypes = [ctypes.c_int32]

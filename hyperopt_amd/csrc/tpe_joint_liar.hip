@@ -37,6 +37,14 @@
 //               candidate's own lattice index) per quantised one; sum_d
 //               miss_d(v_d) depends on the candidate alone and is added after
 //               the sum over the liars.
+// The bodies of the two kernels are device functions (pick_step, chunk_step,
+// add_liar) over a view of ONE group, so that the segmented stage
+// (tpe_joint_liar_seg, "Batch-aware picks in branch groups": one greedy chain per
+// group of a tpe_joint_seg_run) runs the same code:
+// k_liar_seg_chunk  round r, grid (chunks) x (groups with more than r problems):
+//               the workgroup reads its group's descriptor from device memory
+//               and runs chunk_step<false> over problem chain[first + r].
+// k_liar_seg_pick   round r, one workgroup per such group: pick_step<false>.
 // The steps are ordered by the stream alone: no workgroup waits on another, no
 // atomics, every reduction has a fixed shape, so the output bytes are a
 // function of the input bytes.
@@ -47,6 +55,7 @@
 #include <stdio.h>
 
 #include <type_traits>
+#include <vector>
 
 #include "../../include/tpe_hip.h"
 
@@ -96,14 +105,27 @@ struct LiarMK : LiarK {         // <true> alone
 template <bool kMixed>
 using Params = std::conditional_t<kMixed, LiarMK, LiarK>;
 
+// What the two bodies below (pick_step, chunk_step) read of ONE group, for the
+// segmented kernels: LiarK's fields of the same names, built in registers from
+// the group's device descriptor (psig / low / high point into it).  The solo
+// kernels hand the bodies their kernel argument itself; View is either.
+struct SegView {
+  int D, C, K, n;
+  const float* amu;
+  const double *l_out, *g_out;
+  double* rows;                 // the group's rows in scratch [chain_len * (2 D + 1)]
+  double* liar_sigma;           // the group's rows of liar_sigma [chain_len * D]
+  const double *psig, *low, *high;
+};
+
 // the continuous dimensions and the doubles of a liar row
-template <bool kMixed>
-__device__ __forceinline__ int cont_dims(const Params<kMixed>& p) {
+template <bool kMixed, class View>
+__device__ __forceinline__ int cont_dims(const View& p) {
   if constexpr (kMixed) return p.Dc;
   else return p.D;
 }
-template <bool kMixed>
-__device__ __forceinline__ int row_len(const Params<kMixed>& p) {
+template <bool kMixed, class View>
+__device__ __forceinline__ int row_len(const View& p) {
   if constexpr (kMixed) return p.LS;
   else return 2 * p.D + 1;
 }
@@ -175,8 +197,8 @@ using PickLds = std::conditional_t<kMixed, PickLdsMixed, PickLdsCont>;
 // largest multiple of Dc up to 256 threads scan: thread t serves dimension
 // t % Dc and the points t / Dc, t / Dc + S / Dc, ..., so a sweep reads S
 // consecutive floats.  zcopy: where the row is also copied to, bit for bit.
-template <bool kMixed>
-__device__ __forceinline__ void add_liar(const Params<kMixed>& p, int i, const float* __restrict__ src,
+template <bool kMixed, class View>
+__device__ __forceinline__ void add_liar(const View& p, int i, const float* __restrict__ src,
                                          float* __restrict__ zcopy, PickLds<kMixed>& s) {
   const int t = threadIdx.x, Dc = cont_dims<kMixed>(p), LS = row_len<kMixed>(p);
   int DS = Dc;                                  // the width of a liar_sigma row
@@ -291,40 +313,50 @@ __device__ __forceinline__ void add_liar(const Params<kMixed>& p, int i, const f
   __syncthreads();                              // the row is written: the next liar of this launch may scan it
 }
 
-// step: 0 adds the given liars; j >= 1 merges step j - 1's chunk records into
-// picks[j - 1], copies its row and adds it as liar G + j - 1
-template <bool kMixed>
-__global__ __launch_bounds__(kThreads) void k_liar_pick(const Params<kMixed> p, int step) {
-  __shared__ PickLds<kMixed> s;
+// One pick: merges the n_chunks records at `chunk_rec` (one problem's, in chunk
+// order) into *pick, copies the winner's row (row zo + idx of `cand`) to zcopy
+// and adds it as liar i of the group `p`.
+template <bool kMixed, class View>
+__device__ __forceinline__ void pick_step(const View& p, const tpe_joint_pick* chunk_rec, int n_chunks,
+                                          tpe_joint_pick* pick, const float* cand, int64_t zo, int i, float* zcopy,
+                                          PickLds<kMixed>& s) {
   const int t = threadIdx.x;
-  if (step == 0) {
-    for (int i = 0; i < p.G; ++i) add_liar<kMixed>(p, i, p.given + (int64_t)i * p.D, nullptr, s);
-    return;
-  }
-  const int j = step - 1;
   Pick best{0, 0};
-  for (int c = t; c < p.n_chunks; c += kThreads) {
-    const tpe_joint_pick r = p.chunk_rec[c];
+  for (int c = t; c < n_chunks; c += kThreads) {
+    const tpe_joint_pick r = chunk_rec[c];
     if (r.idx < 0) continue;
     const Pick x{score_key(r.l - r.g), r.idx};
     if (beats(x, best)) best = x;            // (chunk order = candidate index order)
   }
   const Pick w = block_best(best, s.slot);
   const bool none = w.key == 0;
-  if (t == 0) p.picks[j] = none ? tpe_joint_pick{-1, 0.0, 0.0} : p.chunk_rec[w.idx / TPE_JOINT_CHUNK];
-  add_liar<kMixed>(p, p.G + j, none ? nullptr : p.cand + ((int64_t)j * p.C + w.idx) * p.D,
-                   p.pick_z + (int64_t)j * p.D, s);
+  if (t == 0) *pick = none ? tpe_joint_pick{-1, 0.0, 0.0} : chunk_rec[w.idx / TPE_JOINT_CHUNK];
+  add_liar<kMixed>(p, i, none ? nullptr : cand + (zo + w.idx) * p.D, zcopy, s);
 }
 
-// id j's candidates under the above mixture extended by J = G + j liars
+// step: 0 adds the given liars; j >= 1 merges step j - 1's chunk records into
+// picks[j - 1], copies its row and adds it as liar G + j - 1
 template <bool kMixed>
-__global__ __launch_bounds__(kThreads) void k_liar_chunk(const Params<kMixed> p, int j, double log_w,
-                                                         double log_norm) {
-  __shared__ double tile[kTile * kMaxRow];
-  __shared__ Pick slot[kThreads / 64];
-  const int t = threadIdx.x, D = p.D, Dc = cont_dims<kMixed>(p), LS = row_len<kMixed>(p), J = p.G + j;
+__global__ __launch_bounds__(kThreads) void k_liar_pick(const Params<kMixed> p, int step) {
+  __shared__ PickLds<kMixed> s;
+  if (step == 0) {
+    for (int i = 0; i < p.G; ++i) add_liar<kMixed>(p, i, p.given + (int64_t)i * p.D, nullptr, s);
+    return;
+  }
+  const int j = step - 1;
+  pick_step<kMixed>(p, p.chunk_rec, p.n_chunks, p.picks + j, p.cand, (int64_t)j * p.C, p.G + j,
+                    p.pick_z + (int64_t)j * p.D, s);
+}
+
+// One chunk of one problem under the above mixture of the group `p` extended by
+// its first J liars: candidate i is row zo + i of `cand`, its l and g are at
+// o + i; the chunk's winner goes to *rec.  tile: LDS [kTile * row length].
+template <bool kMixed, class View>
+__device__ __forceinline__ void chunk_step(const View& p, int J, const float* cand, int64_t zo, int64_t o,
+                                           tpe_joint_pick* rec, double log_w, double log_norm, double* tile,
+                                           Pick* slot) {
+  const int t = threadIdx.x, D = p.D, Dc = cont_dims<kMixed>(p), LS = row_len<kMixed>(p);
   const int first = blockIdx.x * TPE_JOINT_CHUNK;
-  const int64_t o = (int64_t)j * p.C;
 
   double m[kR], s[kR];
 #pragma unroll
@@ -344,7 +376,7 @@ __global__ __launch_bounds__(kThreads) void k_liar_chunk(const Params<kMixed> p,
     for (int r = 0; r < kR; ++r) {
       const int i = first + r * kThreads + t;
       if (i >= p.C) continue;
-      const float* __restrict__ zr = p.cand + (o + i) * D;
+      const float* __restrict__ zr = cand + (zo + i) * D;
       for (int qq = 0; qq < nq4; qq += kQ) {
         const double* __restrict__ row = tile + qq * LS;
         double acc[kQ], tt[kQ];
@@ -397,7 +429,7 @@ __global__ __launch_bounds__(kThreads) void k_liar_chunk(const Params<kMixed> p,
     if (J > 0 && g == g) {                   // logaddexp(g, lse - log W) - log1p(J / W)
       double x;
       if constexpr (kMixed) {
-        const float* __restrict__ zr = p.cand + (o + i) * D;
+        const float* __restrict__ zr = cand + (zo + i) * D;
         double miss = 0.0;                   // sum_d miss_d(v_d): the candidate's alone
         for (int d = 0; d < p.Dk; ++d)
           miss += p.miss[p.cat_off[d] + clampi((int)zr[Dc + d], p.cat_upper[d] - 1)];
@@ -413,7 +445,6 @@ __global__ __launch_bounds__(kThreads) void k_liar_chunk(const Params<kMixed> p,
     if (key > best.key) best = Pick{key, (int64_t)i};   // ascending index: strict > keeps the first of a tie
   }
   const Pick w = block_best(best, slot);
-  tpe_joint_pick* rec = p.chunk_rec + blockIdx.x;
   if (w.key == 0) {
     if (t == 0) *rec = tpe_joint_pick{-1, 0.0, 0.0};
     return;
@@ -425,9 +456,94 @@ __global__ __launch_bounds__(kThreads) void k_liar_chunk(const Params<kMixed> p,
     if (r == off / kThreads) *rec = tpe_joint_pick{w.idx, lv[r], gv[r]};
 }
 
+// id j's candidates under the above mixture extended by J = G + j liars
+template <bool kMixed>
+__global__ __launch_bounds__(kThreads) void k_liar_chunk(const Params<kMixed> p, int j, double log_w,
+                                                         double log_norm) {
+  __shared__ double tile[kTile * kMaxRow];
+  __shared__ Pick slot[kThreads / 64];
+  const int64_t o = (int64_t)j * p.C;
+  chunk_step<kMixed>(p, p.G + j, p.cand, o, o, p.chunk_rec + blockIdx.x, log_w, log_norm, tile, slot);
+}
+
+// ---- the segmented stage (tpe_joint_liar_seg): one greedy chain per group ----
+constexpr int kSegRow = 2 * TPE_JOINT_MAX_DIMS + 1;   // doubles of a liar row of a segment
+
+struct SegK {                   // the kernel argument of both segmented kernels
+  int C, n_chunks;
+  const tpe_joint_liar_seg_desc* segs;   // [n_segs], read on the device: not a kernel argument of n_segs descriptors
+  const int32_t* order;             // rank -> group, chain length descending
+  const int32_t* chain;             // slot -> problem
+  const double* log_norm;           // [slot]
+  const float* cand;
+  const int64_t* cand_off;
+  const double *l_out, *g_out;
+  const float* pool;
+  double* rows;                     // scratch
+  tpe_joint_pick* chunk_rec;        // scratch [n_active * n_chunks], by rank
+  tpe_joint_pick* picks;
+  float* pick_z;
+  double* liar_sigma;
+};
+
+__device__ __forceinline__ SegView seg_view(const SegK& k, const tpe_joint_liar_seg_desc& g) {
+  SegView v;
+  v.D = g.n_dims; v.C = k.C; v.K = g.k_above; v.n = g.n_trials;
+  v.amu = k.pool + g.above_mu;
+  v.l_out = k.l_out; v.g_out = k.g_out;
+  v.rows = k.rows + g.row_off;
+  v.liar_sigma = k.liar_sigma + g.sigma_off;
+  v.psig = g.psig; v.low = g.low; v.high = g.high;
+  return v;
+}
+
+// round r, group of rank blockIdx.y (chain length > r): one chunk of problem
+// chain[first + r] under its group's r liars
+__global__ __launch_bounds__(kThreads) void k_liar_seg_chunk(const SegK k, int r) {
+  __shared__ double tile[kTile * kSegRow];
+  __shared__ Pick slot[kThreads / 64];
+  const int rank = blockIdx.y;
+  const tpe_joint_liar_seg_desc& g = k.segs[k.order[rank]];
+  const int sl = g.chain_first + r, prob = k.chain[sl];
+  const SegView v = seg_view(k, g);
+  chunk_step<false>(v, r, k.cand + k.cand_off[prob], 0, (int64_t)prob * k.C,
+                    k.chunk_rec + (int64_t)rank * k.n_chunks + blockIdx.x, g.log_w, k.log_norm[sl], tile, slot);
+}
+
+// round r, group of rank blockIdx.x: the merge of that problem's records, the
+// row copy, and the pick as liar r of its group
+__global__ __launch_bounds__(kThreads) void k_liar_seg_pick(const SegK k, int r) {
+  __shared__ PickLds<false> s;
+  const int rank = blockIdx.x;
+  const tpe_joint_liar_seg_desc& g = k.segs[k.order[rank]];
+  const int prob = k.chain[g.chain_first + r];
+  const SegView v = seg_view(k, g);
+  pick_step<false>(v, k.chunk_rec + (int64_t)rank * k.n_chunks, k.n_chunks, k.picks + prob,
+                   k.cand + k.cand_off[prob], 0, r, k.pick_z + (int64_t)prob * TPE_JOINT_MAX_DIMS, s);
+}
+
 struct Sizes {
   uint64_t rows_bytes, tabs_bytes, bytes;
 };
+
+// the scratch of one tpe_joint_liar_seg from the host descriptors, or false
+// where a count is out of range; n_active: the groups with a problem
+bool liar_seg_scratch(const tpe_joint_liar_seg_desc* segs, int32_t n_segs, int32_t n_cand, Sizes* z, int* n_active) {
+  if (!segs || n_segs < 1 || n_cand < 1) return false;
+  uint64_t row_doubles = 0;
+  int active = 0;
+  for (int s = 0; s < n_segs; ++s) {
+    if (segs[s].n_dims < 1 || segs[s].n_dims > TPE_JOINT_MAX_DIMS || segs[s].chain_len < 0) return false;
+    row_doubles += (uint64_t)segs[s].chain_len * (2 * (uint64_t)segs[s].n_dims + 1);
+    active += segs[s].chain_len > 0;
+  }
+  const uint64_t chunks = ((uint64_t)n_cand + TPE_JOINT_CHUNK - 1) / TPE_JOINT_CHUNK;
+  z->rows_bytes = row_doubles * sizeof(double);
+  z->tabs_bytes = 0;
+  z->bytes = z->rows_bytes + (uint64_t)active * chunks * sizeof(tpe_joint_pick);
+  if (n_active) *n_active = active;
+  return true;
+}
 
 // the scratch of one call, or false where the sizes are out of range
 bool liar_scratch(int32_t n_ids, int32_t n_cand, int32_t n_dims, int32_t n_cat, int32_t n_quant, int32_t n_lattice,
@@ -605,6 +721,101 @@ int tpe_joint_liar_mixed(const tpe_joint_liar_mixed_args* a, tpe_joint_pick* pic
     if (d < Dq) toff += a->quant_v[d];
   }
   return run<true>(k, pre, Dc + Dk + Dq, Dq, picks, pick_z, liar_sigma, scratch, z, stream);
+}
+
+int tpe_joint_liar_seg_scratch_bytes(const tpe_joint_liar_seg_desc* host_segs, int32_t n_segs, int32_t n_cand,
+                                     uint64_t* bytes) {
+  Sizes z;
+  if (!bytes || !liar_seg_scratch(host_segs, n_segs, n_cand, &z, nullptr))
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar_seg_scratch_bytes: bad arguments");
+  *bytes = z.bytes;
+  return TPE_OK;
+}
+
+int tpe_joint_liar_seg(const tpe_joint_liar_seg_args* a, tpe_joint_pick* picks, float* pick_z, double* liar_sigma,
+                       void* scratch, uint64_t scratch_bytes, void* stream) {
+  const char* who = "tpe_joint_liar_seg";
+  tpe_internal_epoch_bump();
+  if (!a) return bad(who, "null args");
+  if (a->n_segs < 1 || a->n_probs < 1 || a->n_cand < 1) return bad(who, "n_segs / n_probs / n_cand < 1");
+  if (!a->segs || !a->host_segs || !a->order || !a->host_order || !a->chain || !a->host_chain || !a->log_norm ||
+      !a->host_log_norm || !a->host_prob_seg)
+    return bad(who, "null segs / order / chain / log_norm / host_prob_seg");
+  if (!a->cand || !a->cand_off || !a->l_out || !a->g_out || !a->pool_f32)
+    return bad(who, "null cand / cand_off / l_out / g_out / pool_f32");
+  if (!picks || !pick_z || !liar_sigma) return bad(who, "null outputs");
+  const int S = a->n_segs, P = a->n_probs;
+  const tpe_joint_liar_seg_desc* hs = a->host_segs;
+  for (int s = 0; s < S; ++s) {
+    const tpe_joint_liar_seg_desc& g = hs[s];
+    if (g.n_dims < 1 || g.n_dims > TPE_JOINT_MAX_DIMS) return bad(who, "n_dims outside [1, TPE_JOINT_MAX_DIMS]");
+    if (g.k_above < 1) return bad(who, "k_above < 1");
+    if (g.n_trials < 0) return bad(who, "n_trials < 0");
+    if (!(g.w_sum > 0.0) || !(g.w_sum < INFINITY)) return bad(who, "w_sum must be positive and finite");
+    for (int d = 0; d < g.n_dims; ++d)
+      if (!(g.psig[d] > 0.0)) return bad(who, "a prior sigma that is not positive");
+    if (g.above_mu < 0 || g.above_mu > a->pool_f32_len - (int64_t)g.k_above * g.n_dims)
+      return bad(who, "an above_mu range that leaves pool_f32");
+    // tpe_joint_liar takes log W from the host's log: the device's differs in the last bits
+    if (g.log_w != log(g.w_sum)) return bad(who, "a log_w that is not the host's log(w_sum)");
+  }
+  // the chains: host_prob_seg alone fixes every count, the order, the slots and the offsets
+  const char* part = "a chain table that is not the partition of the problems host_prob_seg gives";
+  for (int p = 0; p < P; ++p)
+    if (a->host_prob_seg[p] < 0 || a->host_prob_seg[p] >= S) return bad(who, "a host_prob_seg entry outside [0, n_segs)");
+  int64_t slot = 0, row = 0, sig = 0;
+  int n_active = 0, longest = 0;
+  for (int rank = 0; rank < S; ++rank) {
+    const int s = a->host_order[rank];
+    if (s < 0 || s >= S) return bad(who, part);
+    const tpe_joint_liar_seg_desc& g = hs[s];
+    if (g.chain_len < 0 || g.chain_len > P - slot || g.chain_first != slot) return bad(who, part);
+    if (rank > 0) {                               // chain length descending, ties by group index: a permutation
+      const int q = a->host_order[rank - 1];
+      if (hs[q].chain_len < g.chain_len || (hs[q].chain_len == g.chain_len && q >= s)) return bad(who, part);
+    }
+    if (g.row_off != row || g.sigma_off != sig) return bad(who, "a row_off / sigma_off that is not the running sum");
+    slot += g.chain_len;
+    row += (int64_t)g.chain_len * (2 * g.n_dims + 1);
+    sig += (int64_t)g.chain_len * g.n_dims;
+    n_active += g.chain_len > 0;
+    if (g.chain_len > longest) longest = g.chain_len;
+  }
+  if (slot != P) return bad(who, part);
+  {                                               // slot first_s + j holds the (j + 1)-th problem of group s
+    std::vector<int> next((size_t)S, 0);          // (the lengths sum to P, so full chains hit every slot once)
+    for (int p = 0; p < P; ++p) {
+      const tpe_joint_liar_seg_desc& g = hs[a->host_prob_seg[p]];
+      const int j = next[(size_t)a->host_prob_seg[p]]++;
+      if (j >= g.chain_len || a->host_chain[g.chain_first + j] != p) return bad(who, part);
+      if (a->host_log_norm[g.chain_first + j] != log1p((double)j / g.w_sum))
+        return bad(who, "a log_norm that is not the host's log1p(j / w_sum)");
+    }
+    for (int s = 0; s < S; ++s)
+      if (next[(size_t)s] != hs[s].chain_len) return bad(who, part);
+  }
+  Sizes z;
+  if (n_active > 65535 || !liar_seg_scratch(hs, S, a->n_cand, &z, nullptr)) return bad(who, "sizes out of range");
+  if (!scratch || scratch_bytes < z.bytes) return bad(who, "scratch too small");
+
+  SegK k;
+  k.C = a->n_cand;
+  k.n_chunks = (int)(((int64_t)a->n_cand + TPE_JOINT_CHUNK - 1) / TPE_JOINT_CHUNK);
+  k.segs = a->segs; k.order = a->order; k.chain = a->chain; k.log_norm = a->log_norm;
+  k.cand = a->cand; k.cand_off = a->cand_off; k.l_out = a->l_out; k.g_out = a->g_out; k.pool = a->pool_f32;
+  k.rows = (double*)scratch;
+  k.chunk_rec = (tpe_joint_pick*)((char*)scratch + z.rows_bytes);
+  k.picks = picks; k.pick_z = pick_z; k.liar_sigma = liar_sigma;
+  const hipStream_t st = (hipStream_t)stream;
+  int active = n_active;                          // the groups of chain length > r: a prefix of the order
+  for (int r = 0; r < longest; ++r) {
+    while (hs[a->host_order[active - 1]].chain_len <= r) --active;
+    hipLaunchKernelGGL(k_liar_seg_chunk, dim3((unsigned)k.n_chunks, (unsigned)active), dim3(kThreads), 0, st, k, r);
+    hipLaunchKernelGGL(k_liar_seg_pick, dim3((unsigned)active), dim3(kThreads), 0, st, k, r);
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
+  return TPE_OK;
 }
 
 }  // extern "C"

@@ -1474,15 +1474,7 @@ class Engine(object):
         P = len(b.prob_seg)
         if C == 0:                                   # an empty part of a sharded stage
             return self._joint_empty(P, 0, return_cand, want_lg, widths=b.widths)
-        d_blob = self._buf('joint_seg_blob', len(b.blob), torch.uint8)
-        d_blob[:len(b.blob)].copy_(torch.from_numpy(b.blob))
-        a = N.JointMSegArgs() if mixed else N.JointSegArgs()
-        a.n_segs, a.n_probs, a.n_cand, a.flags = len(models), P, C, N.JOINT_INJECT if inject is not None else 0
-        a.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        for name, off in zip(JP.SECTIONS, b.offs):
-            setattr(a, name, d_blob.data_ptr() + int(off))
-        a.host_segs, a.host_prob_seg = b.segs.ctypes.data, b.prob_seg.ctypes.data
-        a.pool_f32_len, a.pool_f64_len = b.n32, b.n64
+        a = self._joint_seg_args(N.JointMSegArgs if mixed else N.JointSegArgs, b, len(models), C, seed, inject)
         if mixed:
             nb = ctypes.c_uint64(0)
             N.check(self.lib.tpe_joint_mseg_table_bytes(b.segs.ctypes.data, len(models), ctypes.byref(nb)), self.lib,
@@ -1493,6 +1485,20 @@ class Engine(object):
                 a.quant_table, a.quant_table_bytes = d_tab.data_ptr(), d_tab.numel() * 4
         return self._joint_seg_call('tpe_joint_mseg' if mixed else 'tpe_joint_seg', a, P, C, b.cand_off, b.widths,
                                     return_cand, want_lg, report_k, shard)
+
+    def _joint_seg_args(self, struct, b, n_segs, C, seed, inject):
+        """Upload the blob ``b`` (joint_pack.segment_blob) and fill the args
+        ``struct`` of a segmented stage from it."""
+        d_blob = self._buf('joint_seg_blob', len(b.blob), torch.uint8)
+        d_blob[:len(b.blob)].copy_(torch.from_numpy(b.blob))
+        a = struct()
+        a.n_segs, a.n_probs, a.n_cand, a.flags = n_segs, len(b.prob_seg), C, N.JOINT_INJECT if inject is not None else 0
+        a.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        for name, off in zip(JP.SECTIONS, b.offs):
+            setattr(a, name, d_blob.data_ptr() + int(off))
+        a.host_segs, a.host_prob_seg = b.segs.ctypes.data, b.prob_seg.ctypes.data
+        a.pool_f32_len, a.pool_f64_len = b.n32, b.n64
+        return a
 
     def _joint_seg_call(self, fn, a, P, C, cand_off, pd, return_cand, want_lg, report_k, shard=None):
         """What the two segmented stages share: scratch and the result block, the
@@ -1535,6 +1541,90 @@ class Engine(object):
             res.append(host[rec_w + lg_w:rec_w + 2 * lg_w].reshape(P, C).copy())
         if report_k:
             res.extend(self._joint_report_host(rep, P, report_k, pd))
+        return tuple(res)
+
+    def run_joint_segments_liar(self, models, stream_words, prob_seg, prob_id, n_cand, seed, liar=True, inject=None,
+                                return_cand=False, want_lg=False, return_sigma=False):
+        """``run_joint_segments`` over continuous groups, batch-aware inside every
+        group (tpe_joint_liar_seg, include/tpe_hip.h "Batch-aware picks in
+        branch groups"; DESIGN.md of the same name): the problems of group s, in
+        the order given, pick greedily as the ids of ``run_joint(..., liar=W_s)``
+        do; groups do not see each other.  The segmented stage keeps its three
+        buffers on the device, the liar stage follows on the same stream, and
+        one transfer brings the results back.  Record p (N.JOINT_RECORD_DTYPE,
+        the caller's problem order) holds its pick's index, l, g_j and row.
+        The picks, rows and bandwidths of group s are byte for byte those of
+        ``run_joint`` over that group with its stream word, ids = its problems'
+        ids, ``liar=W_s`` and ``return_sigma=True``.
+
+        ``liar``: True (W_s = 1 / w[-1] of each group's above side, as
+        ``run_joint``) or one positive finite W_s per group.  ``return_cand`` /
+        ``want_lg``: as ``run_joint_segments``, the base stage's bytes.
+        ``return_sigma``: also, last, a list of float64 [L_s, D_s] per group in
+        the caller's group order (a group without a problem: [0, D_s]).  A group
+        with a discrete or quantised label raises ValueError."""
+        for s, m in enumerate(models):
+            parts = JP.seg_parts(m)
+            if parts[4] or parts[5]:
+                raise ValueError('joint stage: the segmented liar stage takes groups of continuous labels only: group '
+                                 '%d holds a discrete or quantised label' % s)
+        W = JP.liar_weight_sums(liar, models)
+        C = int(n_cand)
+        b = JP.segment_blob(models, stream_words, prob_seg, prob_id, C, inject, N.JOINT_SEG_DTYPE)
+        lb = JP.liar_segment_blob(models, b.segs, W, b.prob_seg)
+        P, S = len(b.prob_seg), len(models)
+        a = self._joint_seg_args(N.JointSegArgs, b, S, C, seed, inject)
+        d_lblob = self._buf('joint_liar_seg_blob', len(lb.blob), torch.uint8)
+        d_lblob[:len(lb.blob)].copy_(torch.from_numpy(lb.blob))
+        la = N.JointLiarSegArgs()
+        la.n_segs, la.n_probs, la.n_cand = S, P, C
+        for name, off in zip(JP.LIAR_SECTIONS, lb.offs):
+            setattr(la, name, d_lblob.data_ptr() + int(off))
+        la.host_segs, la.host_order, la.host_chain = lb.segs.ctypes.data, lb.order.ctypes.data, lb.chain.ctypes.data
+        la.host_log_norm, la.host_prob_seg = lb.log_norm.ctypes.data, b.prob_seg.ctypes.data
+        la.cand_off, la.pool_f32, la.pool_f32_len = a.cand_off, a.pool_f32, b.n32
+        nb, lnb = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        N.check(self.lib.tpe_joint_seg_scratch_bytes(P, C, ctypes.byref(nb)), self.lib, 'tpe_joint_seg_scratch_bytes')
+        N.check(self.lib.tpe_joint_liar_seg_scratch_bytes(lb.segs.ctypes.data, S, C, ctypes.byref(lnb)), self.lib,
+                'tpe_joint_liar_seg_scratch_bytes')
+        d_scr = self._buf('joint_scratch', (nb.value + 7) // 8, torch.float64)
+        d_lscr = self._buf('joint_liar_scratch', (lnb.value + 7) // 8, torch.float64)
+        # one result block of 8-byte words: picks, pick rows (f32 pairs), bandwidths; then what only the device
+        # or a caller of return_cand / want_lg reads: records, l, g, candidates (f32 pairs)
+        MD = N.JOINT_MAX_DIMS
+        pk_w, z_w, sg_w = 3 * P, P * MD // 2, max(1, lb.n_sigma)
+        head = pk_w + z_w + sg_w
+        rec_w, lg_w, cand_w = P * N.JOINT_RECORD_DTYPE.itemsize // 8, P * C, (int(b.cand_off[-1]) + 1) // 2
+        d_out = self._buf('joint_seg_liar_out', head + rec_w + 2 * lg_w + cand_w, torch.float64)
+        out = d_out.data_ptr()
+        o_l, o_g, o_cand = out + 8 * (head + rec_w), out + 8 * (head + rec_w + lg_w), out + 8 * (head + rec_w + 2 * lg_w)
+        la.cand, la.l_out, la.g_out = o_cand, o_l, o_g
+        stream = self._stream()
+        N.check(self.lib.tpe_joint_seg_run(ctypes.byref(a), out + 8 * head, o_cand, o_l, o_g, d_scr.data_ptr(),
+                                           d_scr.numel() * 8, ctypes.c_void_p(stream)), self.lib, 'tpe_joint_seg_run')
+        N.check(self.lib.tpe_joint_liar_seg(ctypes.byref(la), out, out + 8 * pk_w, out + 8 * (pk_w + z_w),
+                                            d_lscr.data_ptr(), d_lscr.numel() * 8, ctypes.c_void_p(stream)), self.lib,
+                'tpe_joint_liar_seg')
+        host = d_out[:head + ((rec_w + 2 * lg_w + cand_w) if (return_cand or want_lg) else 0)].cpu().numpy()
+        picks = host[:pk_w].view(N.JOINT_PICK_DTYPE)
+        z = host[pk_w:pk_w + z_w].view(np.float32).reshape(P, MD)
+        rec = np.zeros(P, dtype=N.JOINT_RECORD_DTYPE)
+        rec['global_idx'], rec['l'], rec['g'] = picks['idx'], picks['l'], picks['g']
+        for p in range(P):
+            rec['z'][p, :int(b.widths[p])] = z[p, :int(b.widths[p])]
+        if not (return_cand or want_lg or return_sigma):
+            return rec
+        res = [rec]
+        if return_cand:
+            flat = host[head + rec_w + 2 * lg_w:].view(np.float32)
+            res.append([flat[b.cand_off[p]:b.cand_off[p + 1]].reshape(C, int(b.widths[p])).copy() for p in range(P)])
+        if want_lg:
+            res.append(host[head + rec_w:head + rec_w + lg_w].reshape(P, C).copy())
+            res.append(host[head + rec_w + lg_w:head + rec_w + 2 * lg_w].reshape(P, C).copy())
+        if return_sigma:
+            sig = host[pk_w + z_w:head]
+            res.append([sig[int(g['sigma_off']):int(g['sigma_off']) + int(g['chain_len']) * int(g['n_dims'])]
+                        .reshape(int(g['chain_len']), int(g['n_dims'])).copy() for g in lb.segs])
         return tuple(res)
 
     def run_joint_mixed(self, below, above, low, high, cats, ids, n_cand, seed, inject=None, return_cand=False,

@@ -259,3 +259,96 @@ def segment_blob(models, stream_words, prob_seg, prob_id, n_cand, inject, seg_dt
              cand_off[:P].view(np.uint8), np.concatenate(pools[4]).view(np.uint8), prob_seg.view(np.uint8)]
     offs = np.concatenate([[0], np.cumsum([len(x) for x in parts])])
     return SegmentBlob(np.concatenate(parts), offs, segs, prob_seg, cand_off, widths, fill[4], fill[8], n_table)
+
+
+# What liar_chains returns.  order [S]: rank -> group, chain length descending,
+# ties by group index; first [S]: BY GROUP, its first slot; chain [P]: slot ->
+# problem, group after group in that order, a group's problems in the caller's
+# order; active [longest chain]: the groups with more than r problems, which
+# are order[:active[r]].
+LiarChains = collections.namedtuple('LiarChains', 'order first chain active')
+
+
+def liar_chains(prob_seg, n_segs):
+    """The greedy chains of a segmented liar stage (include/tpe_hip.h
+    "Batch-aware picks in branch groups"): the chain of group s is its problems
+    in the caller's order.  Pure numpy; a group without a problem is legal."""
+    prob_seg = np.ascontiguousarray(prob_seg, dtype=np.int32).reshape(-1)
+    S = int(n_segs)
+    if S < 1 or len(prob_seg) < 1:
+        raise ValueError('joint stage: at least one group and one problem')
+    if prob_seg.min() < 0 or prob_seg.max() >= S:
+        raise ValueError('joint stage: a problem names a group outside [0, %d)' % S)
+    lens = np.bincount(prob_seg, minlength=S)
+    order = np.argsort(-lens, kind='stable').astype(np.int32)
+    first = np.zeros(S, dtype=np.int32)
+    first[order] = np.concatenate([[0], np.cumsum(lens[order])[:-1]])
+    rank = np.empty(S, dtype=np.int64)
+    rank[order] = np.arange(S)
+    chain = np.argsort(rank[prob_seg], kind='stable').astype(np.int32)
+    active = np.array([(lens > r).sum() for r in range(int(lens.max()))], dtype=np.int32)
+    return LiarChains(order, first, chain, active)
+
+
+# What liar_segment_blob returns.  blob: the one upload; offs: where its
+# sections start, in the order LIAR_SECTIONS; segs / order / chain / log_norm:
+# the host copies the library checks (segs['sigma_off'][s]: where group s's
+# [L_s, D_s] rows start in liar_sigma); n_sigma: the doubles of liar_sigma.
+LiarSegmentBlob = collections.namedtuple('LiarSegmentBlob', 'blob offs segs order chain log_norm n_sigma')
+LIAR_SECTIONS = ('segs', 'log_norm', 'order', 'chain')
+
+
+def liar_weight_sums(liar, models):
+    """The un-normalised weight sum W_s of every group's above side: ``liar``
+    True takes 1 / w[-1] (the newest trial weighs 1; a side without trials: 1),
+    as Engine.run_joint does; a sequence gives one positive finite W_s per
+    group.  ValueError for anything else."""
+    S = len(models)
+    if isinstance(liar, (bool, np.bool_)):
+        if not liar:
+            raise ValueError('joint stage: liar must be True or one positive weight sum W per group')
+        out = []
+        for m in models:
+            w = np.asarray(seg_parts(m)[1][0], dtype=np.float64)
+            out.append(1.0 / float(w[-1]) if len(w) > 1 else 1.0)
+        return out
+    try:
+        out = [float(x) for x in liar]
+    except TypeError:
+        raise ValueError('joint stage: liar must be True or one positive weight sum W per group: %r' % (liar,))
+    if len(out) != S or not all(x > 0 and np.isfinite(x) for x in out):
+        raise ValueError('joint stage: liar must be True or one positive weight sum W per group: %r' % (liar,))
+    return out
+
+
+def liar_segment_blob(models, segs, weight_sums, prob_seg):
+    """The upload of a segmented liar stage after a segmented stage over the
+    same ``models`` and ``prob_seg``: per group its descriptor
+    (N.JOINT_LIAR_SEG_DTYPE; ``segs``: that stage's descriptors, whose above_mu
+    offsets it shares), the chains (liar_chains) and log1p(j / W_s) by slot.
+    log W_s and log1p come from the C library (math), as tpe_joint_liar takes
+    them; the library rejects any other bits."""
+    import math
+    S = len(models)
+    ch = liar_chains(prob_seg, S)
+    out = np.zeros(S, dtype=N.JOINT_LIAR_SEG_DTYPE)
+    lens = np.bincount(np.asarray(prob_seg, dtype=np.int64), minlength=S)
+    log_norm = np.zeros(len(ch.chain), dtype=np.float64)
+    row = sig = 0
+    for s in ch.order:
+        above, low, high = seg_parts(models[s])[1:4]
+        D, g, W = int(segs[s]['n_dims']), out[s], float(weight_sums[s])
+        g['n_dims'], g['k_above'], g['n_trials'] = D, segs[s]['k_above'], segs[s]['k_above'] - 1
+        g['chain_len'], g['chain_first'] = lens[s], ch.first[s]
+        g['w_sum'], g['log_w'], g['above_mu'] = W, math.log(W), segs[s]['above_mu']
+        g['row_off'], g['sigma_off'] = row, sig
+        g['psig'], g['low'], g['high'] = 1.0, -np.inf, np.inf
+        g['psig'][:D] = np.asarray(above[2], dtype=np.float64).reshape(-1, D)[0]
+        g['low'][:D], g['high'][:D] = np.asarray(low, dtype=np.float64), np.asarray(high, dtype=np.float64)
+        for j in range(int(lens[s])):
+            log_norm[ch.first[s] + j] = math.log1p(j / W)
+        row += int(lens[s]) * (2 * D + 1)
+        sig += int(lens[s]) * D
+    parts = [out.view(np.uint8), log_norm.view(np.uint8), ch.order.view(np.uint8), ch.chain.view(np.uint8)]
+    offs = np.concatenate([[0], np.cumsum([len(x) for x in parts])])
+    return LiarSegmentBlob(np.concatenate(parts), offs, out, ch.order, ch.chain, log_norm, sig)

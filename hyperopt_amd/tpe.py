@@ -852,7 +852,7 @@ def suggest(new_ids, domain, trials, seed,
         _joint_shard_pair(joint_shard, joint, joint_wide_mixed)
     liar_mode = _joint_liar_mode(joint_liar)
     if liar_mode:
-        _joint_liar_check(joint, joint_shard, mode=liar_mode)
+        _joint_liar_check(joint, joint_shard, mode=liar_mode, joint_branches=joint_branches)
     if ((joint is not False and joint is not None) or joint_discrete or joint_quantized or joint_wide or joint_branches
             or joint_branches_mixed or joint_wide_mixed):
         # (argument errors first: no device use, no startup draw)
@@ -860,7 +860,7 @@ def suggest(new_ids, domain, trials, seed,
                            joint_discrete, joint_quantized, _wide_mode(joint_wide, joint_wide_mixed), joint_branches,
                            joint_branches_mixed)
         if liar_mode:
-            _joint_liar_check(joint, joint_shard, plan, liar_mode)
+            _joint_liar_check(joint, joint_shard, plan, liar_mode, joint_branches)
     t0 = time.time()
     hist = _history.extract(domain, trials)
     if logger.isEnabledFor(logging.INFO):
@@ -1048,14 +1048,28 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
     the above side with that category, a picked lattice value as a binned
     normal at its fit coordinate.  On a continuous root group it is True byte
     for byte.  Branch groups, ``joint_shard`` and the keyword without ``joint``
-    raise as under True; any other value raises ValueError."""
+    raise as under True; any other value raises ValueError.
+
+    ``joint_liar='branches'`` (with ``joint_branches``): everything 'mixed'
+    does on the root group, which need not exist, and every branch group is
+    batch-aware too (DESIGN.md "Batch-aware picks in branch groups"): the ids
+    that take one branch pick that group's vector greedily, in the order given,
+    one chain per branch, all chains in one segmented device stage
+    (Engine.run_joint_segments_liar).  Only the branch-group values of ids that
+    share their branch with an earlier id change: every other label, a call
+    with one id and a call whose ids all take different branches are the same
+    bytes as without the keyword; without any branch group in the space it is
+    'mixed' byte for byte.  A branch group with a discrete or quantised label
+    (``joint_branches_mixed``), ``joint_shard``, and the value without
+    ``joint`` or without ``joint_branches`` raise ValueError.  Univariate
+    labels, the gates included, stay as they are."""
     if sampler not in ('philox', 'replay'):
         raise ValueError("sampler must be 'philox' or 'replay'")
     if joint_shard is not None:
         joint_shard = _joint_shard_pair(joint_shard, joint, joint_wide_mixed)
     liar_mode = _joint_liar_mode(joint_liar)
     if liar_mode:
-        _joint_liar_check(joint, joint_shard, mode=liar_mode)
+        _joint_liar_check(joint, joint_shard, mode=liar_mode, joint_branches=joint_branches)
     group, branch_groups = None, []
     if ((joint is not False and joint is not None) or joint_discrete or joint_quantized or joint_wide or joint_branches
             or joint_branches_mixed or joint_wide_mixed):
@@ -1064,7 +1078,7 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
                                            joint_quantized, _wide_mode(joint_wide, joint_wide_mixed),
                                            joint_branches, joint_branches_mixed)
         if liar_mode:
-            _joint_liar_check(joint, joint_shard, (group, branch_groups), liar_mode)
+            _joint_liar_check(joint, joint_shard, (group, branch_groups), liar_mode, joint_branches)
     if sum(a is not None for a in (shard, shard_ids, shard_labels, shard_grid)) > 1:
         raise ValueError('shard, shard_ids, shard_labels and shard_grid are exclusive: one shard axis per suggest')
     if (shard_ids is not None or shard_labels is not None or shard_grid is not None) and sampler == 'replay':
@@ -1076,7 +1090,7 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
                                 columns, shard_ids, shard_labels, shard_grid)
     if group is not None or branch_groups:
         return _suggest_joint(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, device, columns, group,
-                              branch_groups, joint_shard, bool(liar_mode))
+                              branch_groups, joint_shard, liar_mode or False)
     return _suggest_local(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, sampler, precision,
                           device, shard, columns)
 
@@ -1087,29 +1101,44 @@ TPE_JOINT_WIDE_MAX_CAT = N.JOINT_WIDE_MAX_CAT
 
 
 def _joint_liar_mode(joint_liar):
-    """``joint_liar`` as None (off: False or None), True or 'mixed'; ValueError
-    for anything else (another string, a number)."""
+    """``joint_liar`` as None (off: False or None), True, 'mixed' or 'branches';
+    ValueError for anything else (another string, a number)."""
     if joint_liar is None or (isinstance(joint_liar, (bool, np.bool_)) and not joint_liar):
         return None
     if isinstance(joint_liar, (bool, np.bool_)):
         return True
-    if isinstance(joint_liar, str) and joint_liar == 'mixed':
-        return 'mixed'
-    raise ValueError("joint_liar must be True or 'mixed' (or False): %r" % (joint_liar,))
+    if isinstance(joint_liar, str) and joint_liar in ('mixed', 'branches'):
+        return joint_liar
+    raise ValueError("joint_liar must be True or 'mixed', or 'branches' with joint_branches (or False): %r"
+                     % (joint_liar,))
 
 
-def _joint_liar_check(joint, joint_shard, plan=None, mode=True):
-    """ValueError where ``joint_liar`` (``mode``: True or 'mixed') does not
-    apply: without ``joint``, with ``joint_shard``, and (``plan`` = _joint_plan's
-    result) for a root group that is missing or, under True, holds a discrete or
-    quantised label, and for any branch group.  Touches no device."""
+def _joint_liar_check(joint, joint_shard, plan=None, mode=True, joint_branches=False):
+    """ValueError where ``joint_liar`` (``mode``: True, 'mixed' or 'branches')
+    does not apply: without ``joint``, with ``joint_shard``, 'branches' without
+    ``joint_branches``, and (``plan`` = _joint_plan's result) for a root group
+    that is missing or, under True, holds a discrete or quantised label, and for
+    any branch group; under 'branches' for a branch group that holds a discrete
+    or quantised label, and without any branch group what 'mixed' raises.
+    Touches no device."""
     if joint is False or joint is None:
         raise ValueError('joint_liar needs joint=True or joint=[labels]: it only changes how the joint stage picks')
     if joint_shard is not None:
         raise ValueError('joint_liar=%r does not combine with joint_shard' % (mode,))
+    if mode == 'branches' and not joint_branches:
+        raise ValueError("joint_liar='branches' needs joint_branches=True: the keyword that makes branch groups")
     if plan is None:
         return
     group, branch_groups = plan
+    if mode == 'branches' and branch_groups:
+        for rows in branch_groups:
+            other = [r.label for r in rows if r.dist not in _joint.JOINT_DISTS]
+            if other:
+                raise ValueError("joint_liar='branches' needs branch groups of continuous labels only "
+                                 '(joint_branches_mixed): %r is discrete or quantised' % other[0])
+        return
+    if mode == 'branches':                       # no branch group in the space: 'mixed'
+        mode = 'mixed'
     if branch_groups:
         raise ValueError('joint_liar=%r does not combine with branch groups (joint_branches)' % (mode,))
     if mode == 'mixed':
@@ -1529,8 +1558,10 @@ def _suggest_joint(table, hist, new_ids, seed, prior_weight, n_EI_candidates, ga
     its columns for those ids only (a joined label gates nothing, so the
     routing is the univariate pass's).  ``joint_shard``: the two joint stages
     run over this rank's candidate range and exchange their records
-    (_JointParts); the univariate pass is replicated.  ``joint_liar``: the
-    root group's ids pick greedily (Engine.run_joint's ``liar``)."""
+    (_JointParts); the univariate pass is replicated.  ``joint_liar`` (False,
+    True, 'mixed' or 'branches'): the root group's ids pick greedily
+    (Engine.run_joint's ``liar``); 'branches': so do the ids of every branch
+    group (Engine.run_joint_segments_liar)."""
     cc = _suggest_local(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, 'philox', 'fp32', device,
                         None, True)
     if len(cc) == 0:
@@ -1562,7 +1593,7 @@ def _suggest_joint(table, hist, new_ids, seed, prior_weight, n_EI_candidates, ga
             active[:, r.index] = True
     if branch_groups:
         _suggest_branches(engine, hist, ids, seed, prior_weight, n_EI_candidates, gamma, branch_groups,
-                          np.asarray(cc.active, dtype=bool), values, parts)
+                          np.asarray(cc.active, dtype=bool), values, parts, joint_liar == 'branches')
     cc = ChoiceColumns(table.labels, values, active)
     return cc if columns else cc.dicts(table)
 
@@ -1581,12 +1612,15 @@ def _fit_branch_model(rows, hist, below_tids, prior_weight):
 
 
 def _suggest_branches(engine, hist, ids, seed, prior_weight, n_EI_candidates, gamma, branch_groups, taken, values,
-                      parts=None):
+                      parts=None, liar=False):
     """The segmented joint stage of a suggest: one problem per (new id, branch
     group whose labels are active for it in ``taken`` [n_ids x n_labels]), all
     in one Engine.run_joint_segments call; the winners overwrite ``values``.
     ``parts`` (_JointParts): the call covers this rank's candidates, and the
-    records of all ranks are combined."""
+    records of all ranks are combined.  ``liar`` (joint_liar='branches'): the ids
+    that take one branch pick its vector greedily, in the order given
+    (Engine.run_joint_segments_liar, W of every group's above side as
+    side_mixture weighs it)."""
     below_tids = _history.split_below(hist, gamma)
     models, words, prob_seg, prob_id, where = [], [], [], [], []
     for rows in branch_groups:
@@ -1605,7 +1639,11 @@ def _suggest_branches(engine, hist, ids, seed, prior_weight, n_EI_candidates, ga
         words.append(_joint.branch_stream_word(rows))
     if not models:
         return
-    if parts is None:
+    if liar:
+        assert parts is None, 'joint_liar does not combine with joint_shard'
+        W = [_joint.side_weight_sum(len(m.above[0]) - 1, prior_weight, DEFAULT_LF) for m in models]
+        rec = engine.run_joint_segments_liar(models, words, prob_seg, prob_id, int(n_EI_candidates), seed, liar=W)
+    elif parts is None:
         rec = engine.run_joint_segments(models, words, prob_seg, prob_id, int(n_EI_candidates), seed)
     else:
         rec = parts.records(lambda: engine.run_joint_segments(models, words, prob_seg, prob_id, parts.n_cand, seed,

@@ -1902,6 +1902,103 @@ int tpe_joint_liar_mixed(const tpe_joint_liar_mixed_args* args, tpe_joint_pick* 
                          double* liar_sigma, void* scratch, uint64_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Batch-aware picks in branch groups (tpe_joint_liar.hip, k_liar_seg_chunk and
+ * k_liar_seg_pick; additive exports, the ABI stays 24).  The liar stage for
+ * the problems of a tpe_joint_seg_run: a follow-up enqueued on the same stream
+ * over the cand / cand_off, l_out / g_out and pool_f32 that call just used.
+ * Problem p = (prob_id[p], group prob_seg[p]).  The chain of group s is its
+ * problems in the caller's order, step j its (j + 1)-th problem; chains of
+ * different groups do not see each other, and there are no given liars.  Inside
+ * a chain the model is tpe_joint_liar's with n_given = 0: liar weight 1, mean
+ * the picked f32 row, the neighbour rule over the group's own above_mu rows
+ * (pool_f32 + above_mu, k_above rows of n_dims) and the chain's earlier picks
+ * with m = n_trials + j + 1, and log g_j = logaddexp(log g, lse - log W_s) -
+ * log1p(j / W_s), W_s = w_sum.
+ *
+ * Defining property: picks, pick_z rows and liar_sigma rows of group s are byte
+ * for byte those of a tpe_joint_liar with n_ids = chain_len over that group's
+ * problems' cand, l_out and g_out in chain order, its above_mu, k_above,
+ * n_trials, w_sum, psig, low, high and n_given = 0.  A chain of one problem is
+ * tpe_joint_seg_run's record of that problem.  The device code is
+ * tpe_joint_liar's: the bodies of k_liar_chunk<false> and k_liar_pick<false>
+ * are device functions over a view of one group, which the segmented kernels
+ * build from the group's descriptor in device memory.
+ *
+ * The caller orders the groups by chain length, longest first, ties by group
+ * index (`order`: rank -> group), so the groups still active in round r are a
+ * prefix.  `chain` lists the problems chain by chain in that order: group s
+ * holds the slots [chain_first, chain_first + chain_len).  row_off / sigma_off
+ * are the running sums, in the same order, of chain_len (2 n_dims + 1) and
+ * chain_len n_dims: where the group's rows start in scratch and in liar_sigma,
+ * in doubles.  log_w = log(w_sum) and log_norm[chain_first + j] = log1p(j /
+ * w_sum) are the HOST C library's values, as tpe_joint_liar computes them (the
+ * device's log differs in the last bits, and the bytes are the contract).
+ *
+ * Launches, all on `stream`, ordered by the stream alone: round r = 0 ..
+ * (longest chain) - 1 runs k_liar_seg_chunk on a grid of (chunks of
+ * TPE_JOINT_CHUNK candidates) x (groups with chain_len > r), then
+ * k_liar_seg_pick with one 256-thread workgroup per such group: 2 x (longest
+ * chain) launches.  No workgroup waits on another, no atomics, plain vector
+ * stores, fixed reduction shapes: the same call twice gives the same bytes.
+ *
+ * tpe_joint_liar_seg_scratch_bytes = sum_s chain_len_s (2 n_dims_s + 1) 8 +
+ * n_active ceil(n_cand / TPE_JOINT_CHUNK) 24, n_active the groups with
+ * chain_len > 0; it reads n_dims and chain_len of host_segs and returns
+ * TPE_E_ARG for null pointers, n_segs or n_cand < 1, an n_dims outside [1,
+ * TPE_JOINT_MAX_DIMS] or a chain_len < 0.  tpe_joint_liar_seg returns TPE_E_ARG
+ * before any launch (no device needed) for: null args, arrays or outputs;
+ * n_segs, n_probs or n_cand < 1; a descriptor with n_dims outside [1,
+ * TPE_JOINT_MAX_DIMS], k_above < 1, n_trials < 0, a w_sum that is not positive
+ * and finite, a psig that is not positive, an above_mu range that leaves
+ * pool_f32 (pool_f32_len elements) or a log_w that is not log(w_sum); a
+ * host_prob_seg entry outside [0, n_segs); an order, chain_len, chain_first or
+ * chain table that is not the partition of [0, n_probs) host_prob_seg gives; a
+ * row_off or sigma_off that is not the running sum; a log_norm entry that is
+ * not log1p(j / w_sum); more than 65535 groups with a problem; scratch smaller
+ * than the formula.  The checks read the host copies; the kernels read the
+ * device arrays, which must hold the same bytes.  cand_off is read on the
+ * device alone, as by tpe_joint_seg_run.  A group without a problem is legal.
+ * ---------------------------------------------------------------------- */
+typedef struct tpe_joint_liar_seg_desc {
+  int32_t n_dims, k_above, n_trials;
+  int32_t chain_len;           /* L_s: the problems of this group */
+  int32_t chain_first;         /* its first slot in `chain` */
+  int32_t reserved;
+  double w_sum, log_w;         /* W_s, log(W_s) by the host's C library */
+  int64_t above_mu;            /* element offset in pool_f32, as tpe_joint_seg.above_mu */
+  int64_t row_off, sigma_off;  /* doubles: the group's liar rows in scratch, its rows of liar_sigma */
+  double psig[TPE_JOINT_MAX_DIMS];                                /* the prior sigmas */
+  double low[TPE_JOINT_MAX_DIMS], high[TPE_JOINT_MAX_DIMS];       /* -inf / +inf: unbounded */
+} tpe_joint_liar_seg_desc;
+typedef struct tpe_joint_liar_seg_args {
+  int32_t n_segs, n_probs, n_cand, reserved;
+  const tpe_joint_liar_seg_desc* segs;        /* device [n_segs], group index order */
+  const tpe_joint_liar_seg_desc* host_segs;   /* host   [n_segs], the same bytes */
+  const int32_t* order;                  /* device [n_segs]: rank -> group */
+  const int32_t* host_order;
+  const int32_t* chain;                  /* device [n_probs]: slot -> problem */
+  const int32_t* host_chain;
+  const double* log_norm;                /* device [n_probs]: by slot */
+  const double* host_log_norm;
+  const int32_t* host_prob_seg;          /* host   [n_probs], as tpe_joint_seg_args */
+  const float* cand;                     /* device, what tpe_joint_seg_run wrote */
+  const int64_t* cand_off;               /* device [n_probs] */
+  const double *l_out, *g_out;           /* device [n_probs * n_cand] */
+  const float* pool_f32;                 /* device */
+  int64_t pool_f32_len;                  /* elements */
+} tpe_joint_liar_seg_args;
+
+int tpe_joint_liar_seg_scratch_bytes(const tpe_joint_liar_seg_desc* host_segs, int32_t n_segs, int32_t n_cand,
+                                     uint64_t* bytes);
+
+/* picks: device [n_probs], by problem; pick_z: device f32 [n_probs *
+ * TPE_JOINT_MAX_DIMS], problem p's row at p * TPE_JOINT_MAX_DIMS (n_dims
+ * floats written); liar_sigma: device f64 [sum_s chain_len_s n_dims_s], group
+ * s's [chain_len, n_dims] rows at sigma_off; enqueued on `stream` */
+int tpe_joint_liar_seg(const tpe_joint_liar_seg_args* args, tpe_joint_pick* picks, float* pick_z,
+                       double* liar_sigma, void* scratch, uint64_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Host phase clock of tpe_suggest_tree (tools/native_split.py).  While
  * enabled, a call records the steady-clock microseconds since its entry at
  * each phase below (a tree of several level runs: the last run's phases);

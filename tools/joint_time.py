@@ -1,7 +1,7 @@
 """Time the joint TPE stage against the host route.
 Usage: python tools/joint_time.py [--pairs 3] [--warmup 1] [--cand 1048576] [--history 10000]
                                   [--host-cand N] [--out FILE] [--mixed | --quant | --wide | --wide-mixed | --liar |
-                                   --liar-mixed]
+                                   --liar-mixed | --liar-branches]
 
 Workload: a flat space of 4 continuous labels (uniform, loguniform, normal,
 uniform), a seeded 10,000-trial history whose loss has an x0 * x1 term, one
@@ -91,7 +91,20 @@ one hp.quniform of 32 values: Engine.run_joint_quant (the stage as it was) and
 Engine.run_joint_liar_mixed with liar=W, alternating, wall clock from a synchronised
 device to the records on the host.  The nearest-pick distance counts a
 continuous or quantised coordinate in units of its prior sigma and a differing
-category as 1.  --out defaults to profiles/joint_liar_mixed_time.jsonl."""
+category as 1.  --out defaults to profiles/joint_liar_mixed_time.jsonl.
+
+--liar-branches: batch-aware picks in branch groups.  4 groups of the
+4 continuous labels above, each fitted on its own quarter of --history trials,
+--batch (default 64) new ids dealt round-robin over the groups, every group with
+its own stream word.  Per round, alternating in one process, wall clock from a
+synchronised device to the records on the host: (a) Engine.run_joint_segments
+(no liar stage), (b) Engine.run_joint_segments_liar (one segmented liar stage:
+2 launches a round of ALL chains), (c) one Engine.run_joint(liar=W_s) per group
+(the only way without the segmented stage: 2 launches a step of EVERY chain, one
+group after another).  (b) and (c) must agree byte for byte.  The line carries
+the three medians and ranges, (b) - (a) per step of the longest chain, and the
+median nearest-pick distance inside a branch (prior sigmas) with and without the
+stage.  --out defaults to profiles/joint_liar_seg_time.jsonl."""
 import argparse
 import ctypes
 import json
@@ -108,12 +121,12 @@ VALU_PEAK = 1228.8e9          # wave-instructions per second
 SEED = 20240607
 
 
-def make_history(n):
+def make_history(n, seed=SEED):
     from hyperopt_amd import base, history as H, hp
     space = {'x0': hp.uniform('x0', -5, 5), 'x1': hp.loguniform('x1', -3, 2), 'x2': hp.normal('x2', 0, 2),
              'x3': hp.uniform('x3', 0, 1)}
     domain = base.Domain(lambda d: 0.0, space)
-    rs = np.random.RandomState(SEED)
+    rs = np.random.RandomState(seed)
     cols = {'x0': rs.uniform(-5, 5, n), 'x1': np.exp(rs.uniform(-3, 2, n)), 'x2': rs.normal(0, 2, n),
             'x3': rs.uniform(0, 1, n)}
     loss = (cols['x0'] * cols['x1'] - 2.0) ** 2 + 0.1 * cols['x2'] ** 2 + (cols['x3'] - 0.3) ** 2 \
@@ -699,6 +712,87 @@ def main_liar_mixed(args):
     return 0
 
 
+def main_liar_branches(args):
+    import torch
+    from hyperopt_amd import history as H, joint as J
+    from hyperopt_amd.engine import get_engine
+    from hyperopt_amd.parzen import DEFAULT_LF
+
+    S = 4
+    models = []
+    for s in range(S):
+        domain, hist = make_history(args.history // S, SEED + s)
+        rows = [r for r in domain.table.rows if J.eligible(r)]
+        models.append(J.fit_model(rows, hist, H.split_below(hist, 0.25), 1.0))
+    eng = get_engine(None, 'fp32')
+    C, D, B = args.cand, len(rows), args.batch
+    W = [J.side_weight_sum(len(m.above[0]) - 1, 1.0, DEFAULT_LF) for m in models]
+    words = [0x51000 + s for s in range(S)]
+    prob_seg = (np.arange(B) % S).astype(np.int32)
+    prob_id = np.arange(args.history, args.history + B, dtype=np.int64)
+    chains = [np.flatnonzero(prob_seg == s) for s in range(S)]
+
+    def seg():
+        return eng.run_joint_segments(models, words, prob_seg, prob_id, C, SEED)
+
+    def seg_liar():
+        return eng.run_joint_segments_liar(models, words, prob_seg, prob_id, C, SEED, liar=W)
+
+    def solo_liars():
+        return [eng.run_joint(m.below, m.above, m.low, m.high, prob_id[ps], C, SEED, liar=w, stream_word=word)
+                for m, w, word, ps in zip(models, W, words, chains)]
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, out
+
+    runs = (('seg', seg), ('seg_liar', seg_liar), ('solo_liars', solo_liars))
+    for _ in range(args.warmup):
+        for _, fn in runs:
+            fn()
+    wall, out = dict((k, []) for k, _ in runs), {}
+    for i in range(args.pairs):
+        for k, fn in runs:
+            w, out[k] = timed(fn)
+            wall[k].append(w)
+        print('round %d: %s' % (i, ', '.join('%s %.2f ms' % (k, wall[k][-1]) for k, _ in runs)), file=sys.stderr,
+              flush=True)
+    for ps, solo in zip(chains, out['solo_liars']):        # the defining property, on the timed runs
+        for f in ('global_idx', 'l', 'g', 'z'):
+            assert out['seg_liar'][f][ps].tobytes() == solo[f].tobytes(), f
+    med = lambda x: float(np.median(x))   # noqa: E731
+
+    def spread(rec):
+        per = []
+        for m, ps in zip(models, chains):
+            z = rec['z'][ps][:, :D] / np.asarray(m.above[2])[0][None, :]
+            d = np.sqrt(((z[:, None, :] - z[None, :, :]) ** 2).sum(axis=2))
+            np.fill_diagonal(d, np.inf)
+            per.append(float(np.median(d.min(axis=1))))
+        return float(np.median(per))
+    stat = lambda k: dict(wall_median=med(wall[k]), wall_min=min(wall[k]), wall_max=max(wall[k]))   # noqa: E731
+    longest = max(len(ps) for ps in chains)
+    extra = med(wall['seg_liar']) - med(wall['seg'])
+    line = dict(tool='joint_time --liar-branches', groups=S, n_dims=D, history=args.history, n_cand=C, batch=B,
+                chain=longest, pairs=args.pairs, k_above=[len(m.above[0]) for m in models], w_sum=W,
+                launches=dict(seg_liar=2 * longest, solo_liars=2 * B),
+                seg_ms=stat('seg'), seg_liar_ms=stat('seg_liar'), solo_liars_ms=stat('solo_liars'),
+                seg_liar_minus_seg_ms=extra, per_round_ms=extra / longest, per_pick_ms=extra / B,
+                seg_liar_over_solo_liars=med(wall['seg_liar']) / med(wall['solo_liars']),
+                nearest_pick_median=dict(seg=spread(out['seg']), seg_liar=spread(out['seg_liar'])),
+                gpu=torch.cuda.get_device_name(0))
+    text = json.dumps(line)
+    print(text)
+    path = args.out or os.path.join(ROOT, 'profiles', 'joint_liar_seg_time.jsonl')
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, 'a') as f:
+        f.write(text + '\n')
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--pairs', type=int, default=3)
@@ -712,6 +806,7 @@ def main():
     ap.add_argument('--wide-mixed', action='store_true')
     ap.add_argument('--liar', action='store_true')
     ap.add_argument('--liar-mixed', action='store_true')
+    ap.add_argument('--liar-branches', action='store_true')
     ap.add_argument('--batch', type=int, default=64)
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
@@ -727,6 +822,8 @@ def main():
         return main_liar(args)
     if args.liar_mixed:
         return main_liar_mixed(args)
+    if args.liar_branches:
+        return main_liar_branches(args)
     args.out = args.out or os.path.join(ROOT, 'profiles', 'joint_time.jsonl')
 
     import torch
