@@ -506,7 +506,7 @@ EXPORTS = ('tpe_abi_version', 'tpe_last_error', 'tpe_device_count', 'tpe_tile_si
            'tpe_replay_mixture', 'tpe_replay_categorical', 'tpe_level_profile', 'tpe_level_profile_read',
            'tpe_suggest_tree', 'tpe_comm_unique_id', 'tpe_comm_init', 'tpe_comm_destroy', 'tpe_combine_results',
            'tpe_host_threads', 'tpe_host_phases', 'tpe_exchange_allgather', 'tpe_debug_fast_lg',
-           'tpe_collectives_issued', 'tpe_level_resident', 'tpe_scatter_f64', 'tpe_move_ranges', 'tpe_report_scratch_bytes', 'tpe_report',
+           'tpe_collectives_issued', 'tpe_level_resident', 'tpe_level_resident_fused', 'tpe_scatter_f64', 'tpe_move_ranges', 'tpe_report_scratch_bytes', 'tpe_report',
            'tpe_report_profile', 'tpe_joint_scratch_bytes', 'tpe_joint_run', 'tpe_joint_profile',
            'tpe_joint_mixed_run', 'tpe_joint_quant_table_bytes', 'tpe_joint_quant_run', 'tpe_joint_quant_profile',
            'tpe_joint_wide_scratch_bytes', 'tpe_joint_wide_run', 'tpe_joint_wide_profile',
@@ -616,6 +616,8 @@ def load(path=LIB_PATH):
     lib.tpe_debug_fast_lg.restype = ctypes.c_int
     lib.tpe_level_resident.argtypes = [I32, ctypes.POINTER(I64)]
     lib.tpe_level_resident.restype = ctypes.c_int
+    lib.tpe_level_resident_fused.argtypes = [ctypes.POINTER(I64)]
+    lib.tpe_level_resident_fused.restype = ctypes.c_int
     lib.tpe_collectives_issued.argtypes = [ctypes.POINTER(I64)]
     lib.tpe_collectives_issued.restype = ctypes.c_int
     lib.tpe_scatter_f64.argtypes = [P, I64, P, P]
@@ -727,3 +729,13 @@ def level_resident(mode=-1, lib=None):
     st = (ctypes.c_int64 * 4)()
     on = lib.tpe_level_resident(int(mode), st)
     return bool(on), dict(zip(('hits', 'misses', 'fit_reuses', 'drops'), (int(v) for v in st)))
+
+
+def level_resident_fused(lib=None):
+    """tpe_level_resident_fused: {fused, fallbacks} — the hits that ran the
+    argument-keyed sample kernel alone, and those of them whose host selection
+    did not settle (the patch kernel behind it)."""
+    lib = lib or load()
+    st = (ctypes.c_int64 * 2)()
+    check(lib.tpe_level_resident_fused(st), lib, 'tpe_level_resident_fused')
+    return {'fused': int(st[0]), 'fallbacks': int(st[1])}

@@ -12,6 +12,7 @@ REPORT_SRC = os.path.join(HERE, 'csrc', 'tpe_report.hip')
 JOINT_SRC = os.path.join(HERE, 'csrc', 'tpe_joint.hip')
 LIAR_SRC = os.path.join(HERE, 'csrc', 'tpe_joint_liar.hip')
 RNG_HDR = os.path.join(HERE, 'csrc', 'tpe_device_rng.h')
+LAZY_HDR = os.path.join(HERE, 'csrc', 'tpe_lazy_host.h')
 OUT = os.path.join(HERE, 'libtpe_hip.so')
 ARCH = os.environ.get('TPE_OFFLOAD_ARCH', 'gfx950')
 # host ISA baseline of the runtime (any x86-64 host); the vectorised pack loops
@@ -24,7 +25,7 @@ def build(force=False, verbose=False, out=OUT, defines=()):
     semantics), link both into hyperopt_amd/libtpe_hip.so (or `out`, with extra
     -D `defines` on the kernels: A/B variants for tools/)."""
     OUT = out
-    deps = [SRC, HOST_SRC, SUGGEST_SRC, POOL_SRC, REPORT_SRC, JOINT_SRC, LIAR_SRC, RNG_HDR, os.path.join(HERE, 'csrc', 'tpe_pool.h'), os.path.join(HERE, 'csrc', 'sort_net.h'),
+    deps = [SRC, HOST_SRC, SUGGEST_SRC, POOL_SRC, REPORT_SRC, JOINT_SRC, LIAR_SRC, RNG_HDR, LAZY_HDR, os.path.join(HERE, 'csrc', 'tpe_pool.h'), os.path.join(HERE, 'csrc', 'sort_net.h'),
             os.path.join(HERE, 'csrc', 'tpe_keystore.h'),
             os.path.join(HERE, '..', 'include', 'tpe_hip.h'), os.path.abspath(__file__)]
     if out == os.path.join(HERE, 'libtpe_hip.so'):
@@ -52,7 +53,7 @@ def build(force=False, verbose=False, out=OUT, defines=()):
         (host_o, [HOST_SRC] + hdr, host_flags + numpy_fp + ['-c', HOST_SRC, '-o', host_o]),
         (suggest_o, [SUGGEST_SRC] + hdr, host_flags + numpy_fp + ['-c', SUGGEST_SRC, '-o', suggest_o]),
         (pool_o, [POOL_SRC] + hdr, host_flags + ['-pthread', '-c', POOL_SRC, '-o', pool_o]),
-        (dev_o, [SRC, RNG_HDR] + hdr, [hipcc, '-O3', '--offload-arch=' + ARCH, '-std=c++17', '-fPIC', '-Wall',
+        (dev_o, [SRC, RNG_HDR, LAZY_HDR] + hdr, [hipcc, '-O3', '--offload-arch=' + ARCH, '-std=c++17', '-fPIC', '-Wall',
                               '-Wno-unused-command-line-argument'] + ['-D' + d for d in defines] +
          ['-c', SRC, '-o', dev_o]),
         (report_o, [REPORT_SRC] + hdr, [hipcc, '-O3', '--offload-arch=' + ARCH, '-std=c++17', '-fPIC', '-Wall',

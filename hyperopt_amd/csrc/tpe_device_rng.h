@@ -1,19 +1,30 @@
 // Device helpers shared by the sampling kernels (tpe_kernels.hip, tpe_joint.hip):
 // the Philox-4x32-10 block function, the open-interval uniforms made from its
 // words, and the f32 inverse normal CDF every f32 draw inverts through.
-// Include after <hip/hip_runtime.h>, outside any namespace.
+// Include after <hip/hip_runtime.h>, outside any namespace.  The Philox block
+// and u01d are integer and IEEE f64 code that the host runs too (a resident
+// level's fused hit selects its lazy categoricals there, tpe_lazy_host.h): a
+// plain C++ compiler sees only those two.
 #ifndef TPE_DEVICE_RNG_H
 #define TPE_DEVICE_RNG_H
 
 #include <stdint.h>
 
+#ifdef __HIPCC__
+#define TPE_HD __host__ __device__ __forceinline__
+#define TPE_UNROLL _Pragma("unroll")
+#else
+#define TPE_HD inline
+#define TPE_UNROLL
+#endif
+
 // ---------------------------------------------------------------- Philox
 struct U4 { uint32_t x, y, z, w; };
 
-__device__ __forceinline__ U4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                            uint32_t k0, uint32_t k1) {
+TPE_HD U4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
+                        uint32_t k0, uint32_t k1) {
   const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
+  TPE_UNROLL
   for (int r = 0; r < 10; ++r) {
     // one 32x32 -> 64-bit product per multiplier (v_mad_u64_u32) instead of a
     // mul_hi / mul_lo pair
@@ -28,12 +39,14 @@ __device__ __forceinline__ U4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c
 }
 
 // open-interval uniforms
-// 23-bit float uniform in [2^-24, 1 - 2^-24]: (k + 0.5) is exact, so never 0 or 1
-__device__ __forceinline__ float u01f(uint32_t r) { return ((float)(r >> 9) + 0.5f) * 1.1920928955078125e-07f; }
-__device__ __forceinline__ double u01d(uint32_t a, uint32_t b) {
+// (u01d: IEEE f64 operations only, the same value on the host and on the device)
+TPE_HD double u01d(uint32_t a, uint32_t b) {
   const uint64_t m = ((uint64_t)a << 21) ^ (uint64_t)(b >> 11);   // 53 bits
   return ((double)m + 0.5) * 1.1102230246251565e-16;
 }
+#ifdef __HIPCC__
+// 23-bit float uniform in [2^-24, 1 - 2^-24]: (k + 0.5) is exact, so never 0 or 1
+__device__ __forceinline__ float u01f(uint32_t r) { return ((float)(r >> 9) + 0.5f) * 1.1920928955078125e-07f; }
 // 32-bit uniform as a double in (0, 1) (exact)
 __device__ __forceinline__ double u01w(uint32_t a) { return ((double)a + 0.5) * 2.3283064365386963e-10; }
 
@@ -84,5 +97,6 @@ __device__ __forceinline__ float ndtri_f32(float pr) {
   }
   return -1.41421356237309505f * (q * x);
 }
+#endif  // __HIPCC__
 
 #endif  // TPE_DEVICE_RNG_H

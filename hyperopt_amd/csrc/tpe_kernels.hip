@@ -45,6 +45,7 @@
 
 #include "../../include/tpe_hip.h"
 #include "tpe_device_rng.h"
+#include "tpe_lazy_host.h"
 
 extern "C" void tpe_internal_phase(int i);   // tpe_suggest.cpp: host phase clock (hidden)
 extern "C" uint64_t tpe_internal_pack_switches(void);   // tpe_host.cpp: the packer's per-call switches (hidden)
@@ -338,16 +339,21 @@ __device__ __forceinline__ int tile_pos(int cand_start, int j) {
 // selection uniform and 23 bits of inversion; f64 draws and categories take one
 // block per candidate (53-bit selection, 53-bit inversion).
 struct DrawU { double us; float uf; double ud; uint32_t ws; };   // ws: us's 32-bit word (f32 draws)
-__device__ __forceinline__ DrawU draw_uniforms(const tpe_problem& p, int64_t i, int precision) {
+// (the per-call words given apart from the row: k_sample_fast's argument-keyed launch)
+__device__ __forceinline__ DrawU draw_uniforms(const tpe_problem& p, int64_t i, int precision, uint32_t ctr3,
+                                               uint32_t key0, uint32_t key1) {
   const uint64_t g = (uint64_t)p.cand_base + (uint64_t)i;
   if (precision == TPE_PREC_F32 && p.family != TPE_FAM_CATEGORICAL) {
     const uint64_t blk = g >> 1;
-    const U4 r = philox4x32_10((uint32_t)blk, (uint32_t)(blk >> 32), p.ctr2, p.ctr3, p.key0, p.key1);
+    const U4 r = philox4x32_10((uint32_t)blk, (uint32_t)(blk >> 32), p.ctr2, ctr3, key0, key1);
     const bool odd = g & 1;
     return DrawU{u01w(odd ? r.z : r.x), u01f(odd ? r.w : r.y), 0.0, odd ? r.z : r.x};
   }
-  const U4 r = philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), p.ctr2, p.ctr3, p.key0, p.key1);
+  const U4 r = philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), p.ctr2, ctr3, key0, key1);
   return DrawU{u01d(r.x, r.y), u01f(r.z), u01d(r.z, r.w), 0u};
+}
+__device__ __forceinline__ DrawU draw_uniforms(const tpe_problem& p, int64_t i, int precision) {
+  return draw_uniforms(p, i, precision, p.ctr3, p.key0, p.key1);
 }
 
 // f32 truncation bounds of a problem: smallest float >= low, largest float < high
@@ -1591,6 +1597,14 @@ __global__ __launch_bounds__(kTabThreads) void k_sample_tab(const tpe_problem* _
 // as better() on the f64 scores, so the winner is k_sample_tab's), and the run
 // record carries the f64 l, g and score.  LG (debug builds of the stage,
 // tpe_debug_fast_lg): every candidate's {value, l, g, label} written besides.
+// Argument-keyed (AK: a resident level's fused hit, level_run_impl): the
+// per-call words of every problem — the Philox key and ctr3 — are the kernel
+// arguments a_key0 / a_key1 / a_ctr3 (scalar registers from the launch on), and
+// the rows' own, an older call's, are never read.  The choice is made by the
+// instantiation, not by a flag in the kernel: the kernel is at its register
+// budget (NP = 2: 80 VGPRs and 105 SGPRs), and a run-time selection of the three
+// words spilled scalar registers into vector lanes and those into scratch.
+// Without AK the arguments are unused and the kernel is the row-keyed one.
 constexpr int kFastThreads = 512;
 constexpr int kFastSamp = 64;                  // sampler rows (below components) in LDS
 constexpr int kFastWgsPerCu = 3;
@@ -1626,12 +1640,13 @@ __device__ void lattice_ranks(const double2* __restrict__ rows, int n, int* __re
 // NP = 2: 80 VGPRs, six waves a SIMD (three workgroups a CU: batched levels);
 // NP = 4: two candidate pairs in flight per lane for levels of at most two
 // workgroups a CU (config 3's 2^21 candidates), four waves a SIMD
-template <int NP, bool LG>
+template <int NP, bool LG, bool AK>
 __global__ __launch_bounds__(kFastThreads) __attribute__((amdgpu_waves_per_eu(NP == 2 ? 6 : 4)))
 void k_sample_fast(const tpe_problem* __restrict__ P, const tpe_tile* __restrict__ tiles,
                    const int32_t* __restrict__ list, int n_list, int per_wg, const double* __restrict__ samp,
                    const float4* __restrict__ comp32, const float4* __restrict__ tab,
-                   tpe_result* __restrict__ run_best, int tpp, double* __restrict__ lg_out) {
+                   tpe_result* __restrict__ run_best, int tpp, double* __restrict__ lg_out, uint32_t a_key0,
+                   uint32_t a_key1, uint32_t a_ctr3) {
   constexpr int kFastUnit = 64 * NP;
   static_assert(NP % 2 == 0 && kTile % kFastUnit == 0, "fast units: Philox pairs tiling the tiles");
   extern __shared__ float4 fast_tab[];                       // the label's table (tab_fast - 1 units at most)
@@ -1741,18 +1756,26 @@ void k_sample_fast(const tpe_problem* __restrict__ P, const tpe_tile* __restrict
       float uf[NP], tj[NP];
       if (have) {
         const uint64_t g0 = (uint64_t)p.cand_base + (uint64_t)first;
+        // AK: the arguments' words as values of this unit (opaque to the compiler:
+        // the ten round keys are made from them here, in three scalar registers'
+        // reach, instead of being kept in twenty over the whole kernel)
+        uint32_t r_key0 = a_key0, r_key1 = a_key1, r_ctr3 = a_ctr3;
+        if (AK) asm volatile("" : "+s"(r_key0), "+s"(r_key1), "+s"(r_ctr3));
         if ((g0 & 1) == 0) {
 #pragma unroll
           for (int j = 0; j < NP; j += 2) {
             const uint64_t blk = (g0 + (uint64_t)j) >> 1;
-            const U4 r = philox4x32_10((uint32_t)blk, (uint32_t)(blk >> 32), p.ctr2, p.ctr3, p.key0, p.key1);
+            // (the per-call words: the run's copy of the launch's arguments, else the row's)
+            const U4 r = philox4x32_10((uint32_t)blk, (uint32_t)(blk >> 32), p.ctr2, AK ? r_ctr3 : p.ctr3,
+                                       AK ? r_key0 : p.key0, AK ? r_key1 : p.key1);
             ws[j] = r.x; uf[j] = u01f(r.y);
             ws[j + 1] = r.z; uf[j + 1] = u01f(r.w);
           }
         } else {
 #pragma unroll
           for (int j = 0; j < NP; ++j) {
-            const DrawU d = draw_uniforms(p, first + j, TPE_PREC_F32);
+            const DrawU d = AK ? draw_uniforms(p, first + j, TPE_PREC_F32, r_ctr3, r_key0, r_key1)
+                               : draw_uniforms(p, first + j, TPE_PREC_F32);
             ws[j] = d.ws; uf[j] = d.uf;
           }
         }
@@ -5069,13 +5092,7 @@ bool fast2_disabled() {
 }
 
 // np.argmax order of (score, index) on the host: better() of the kernels
-bool host_better(double s, int64_t i, double bs, int64_t bi) {
-  if (bi < 0) return i >= 0;
-  if (i < 0) return false;
-  const bool n = s != s, bn = bs != bs;
-  if (n || bn) return n && (!bn || i < bi);
-  return s > bs || (s == bs && i < bi);
-}
+bool host_better(double s, int64_t i, double bs, int64_t bi) { return tpe_lazy_better(s, i, bs, bi); }
 
 }  // namespace
 
@@ -5233,14 +5250,27 @@ int tpe_debug_fast_lg(void* dev, int64_t n_records) {
   return TPE_OK;
 }
 
+// a resident level's fused hit (level_run_impl): the per-call words every
+// problem of the level shares, passed to k_sample_fast as launch arguments
+// (null: the kernel reads each row's own)
+struct FastKey { uint32_t key0, key1, ctr3; };
+static thread_local const FastKey* g_fast_key = nullptr;
+
 extern "C++" {
-// k_sample_fast<NP, LG> over the level's tabulated tiles
+// k_sample_fast<NP, LG, AK> over the level's tabulated tiles
+template <int NP, bool LG, bool AK>
+void launch_fast_k(const tpe_batch* b, int wgs, size_t lds, hipStream_t s, int n_tab, int per, tpe_result* run_best,
+                   double* lg, const FastKey& k) {
+  TPE_LAUNCH_TIMED((k_sample_fast<NP, LG, AK>), dim3(wgs), dim3(kFastThreads), lds, s, b->problems, b->tiles,
+                   b->tab_tiles, n_tab, per, b->samp, (const float4*)b->comp32, (const float4*)b->tab, run_best,
+                   b->tiles_per_problem, lg, k.key0, k.key1, k.ctr3);
+}
 template <int NP, bool LG>
 void launch_fast(const tpe_batch* b, int wgs, size_t lds, hipStream_t s, int n_tab, int per, tpe_result* run_best,
                  double* lg) {
-  TPE_LAUNCH_TIMED((k_sample_fast<NP, LG>), dim3(wgs), dim3(kFastThreads), lds, s, b->problems, b->tiles,
-                   b->tab_tiles, n_tab, per, b->samp, (const float4*)b->comp32, (const float4*)b->tab, run_best,
-                   b->tiles_per_problem, lg);
+  const FastKey* fk = g_fast_key;
+  if (fk) launch_fast_k<NP, LG, true>(b, wgs, lds, s, n_tab, per, run_best, lg, *fk);
+  else launch_fast_k<NP, LG, false>(b, wgs, lds, s, n_tab, per, run_best, lg, FastKey{0u, 0u, 0u});
 }
 }
 
@@ -5444,6 +5474,7 @@ static thread_local const ResidentPatch* g_patch = nullptr;
 // the per-call patch of the problem rows (the tables are the previous run's)
 static int level_tables(const tpe_batch* b, void* stream) {
   const ResidentPatch* h = g_patch;
+  if (g_fast_key) return TPE_OK;        // (a fused hit: nothing before the argument-keyed sample stage)
   if (!h) return tpe_tables(b, stream);
   TPE_LAUNCH(k_resident_patch, dim3(b->n_problems), dim3(kTabTblThreads), 0, (hipStream_t)stream, h->host_rows,
              h->dev_rows, h->lazy, b->samp, (const double4*)b->comp64, b->result);
@@ -6063,6 +6094,35 @@ int tpe_level_resident(int32_t mode, int64_t* stats) {
   return tpe_internal_resident_on();
 }
 
+// fused hits, and those of them whose host selection did not settle (k_resident_patch behind the sample stage)
+static std::atomic<int64_t> g_resident_fused[2];
+enum { RES_FUSED = 0, RES_FUSED_FALLBACK = 1 };
+
+int tpe_level_resident_fused(int64_t* stats) {
+  if (!stats) return fail(TPE_E_ARG, "tpe_level_resident_fused: null stats");
+  for (int i = 0; i < 2; ++i) stats[i] = g_resident_fused[i].load(std::memory_order_relaxed);
+  return TPE_OK;
+}
+
+// Draws the host scans at most for the lazy categoricals of one fused hit, all
+// of them together (tpe_lazy_host_select); a problem the rest of them does not
+// settle is selected by the device (k_resident_patch behind the sample stage).
+// The scan runs while the host would only wait for k_sample_fast, about 15 us on
+// the headline level: tools/ubench/lazy_scan_ubench measured 21.9 ns a draw at
+// K = 3 and 58.2 ns at K = 64 on the build host, so 256 draws take 5.6 us of the
+// headline's labels (K <= 4) and 14.9 us at the largest K.  A label whose best
+// category has mass m settles within about 5 / m draws.
+constexpr int64_t kLazyHostBudget = 256;
+
+// TPE_LAZY_HOST_BUDGET=n: the budget of this call (A/B, tests; 0: every fused
+// hit falls back, large: none does); read per call, part of the resident key
+static int64_t lazy_host_budget() {
+  const char* e = getenv("TPE_LAZY_HOST_BUDGET");
+  if (!e || !e[0]) return kLazyHostBudget;
+  const long long v = atoll(e);
+  return v < 0 ? 0 : (int64_t)v;
+}
+
 // the calling thread's resident level: what its device blob, tables and pinned
 // staging buffer hold, and the exact key of the run that wrote them
 struct ResidentRec {
@@ -6083,12 +6143,13 @@ static void resident_key(const tpe_label_in* labels, int32_t n_labels, const uin
   int dev = -1;
   if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = -1; }
   constexpr size_t ws_words = (sizeof(tpe_level_ws) + 7) / 8;
-  key.assign(8 + ws_words + 3 * (size_t)n_labels, 0);
+  key.assign(9 + ws_words + 3 * (size_t)n_labels, 0);
   key[0] = (uint64_t)n_labels; key[1] = (uint64_t)(int64_t)n_cand; key[2] = (uint64_t)cand_base;
   key[3] = (uint64_t)n_cand_global; key[4] = (uint64_t)(int64_t)precision; key[5] = (uint64_t)(int64_t)flags;
   key[6] = (uint64_t)(int64_t)dev; key[7] = (exchange ? 1 : 0) ^ (tpe_internal_pack_switches() << 1);
-  memcpy(key.data() + 8, ws, sizeof(tpe_level_ws));   // every pointer and capacity, pinned_dev included
-  uint64_t* k = key.data() + 8 + ws_words;
+  key[8] = (uint64_t)lazy_host_budget();
+  memcpy(key.data() + 9, ws, sizeof(tpe_level_ws));   // every pointer and capacity, pinned_dev included
+  uint64_t* k = key.data() + 9 + ws_words;
   for (int32_t i = 0; i < n_labels; ++i) {
     k[3 * i] = (uint64_t)(int64_t)labels[i].label_ix;
     k[3 * i + 1] = gens[i];
@@ -6100,9 +6161,36 @@ struct EpochQuiet {
   EpochQuiet() { ++g_epoch_quiet; }
   ~EpochQuiet() { --g_epoch_quiet; }
 };
-struct PatchScope {                    // (g_patch set for the hit's launches only)
-  ~PatchScope() { g_patch = nullptr; }
+struct PatchScope {                    // (g_patch / g_fast_key set for the hit's launches only)
+  ~PatchScope() { g_patch = nullptr; g_fast_key = nullptr; }
 };
+
+// Whether a resident level's hit may take the fused path: the batch launches
+// nothing but k_sample_fast after the table stage — early selection at f32
+// with the small-workgroup kernel, no generic sample tiles, no ordered draws,
+// sort, above or finalize work, no device fit, nothing left for the select
+// stage — and every problem is tabulated or a lazy categorical (which the host
+// selects: `lazy` gets their rows)
+static bool fused_hit_ok(const tpe_batch& b, const tpe_pack_info& info, const tpe_problem* rows, int64_t P,
+                         std::vector<int32_t>& lazy) {
+  lazy.clear();
+  if (!(b.early_select && b.tab_fast >= 2 && b.precision == TPE_PREC_F32 && lazy_ok(&b) && b.run_best &&
+        b.n_late == 0 && b.n_fit == 0 && info.n_fit == 0 && b.samp_tiles && b.n_samp_eager == 0 &&
+        b.n_tab_tiles > 0 && !ordered_draws(&b) && (b.sort_count == 0 || b.sort_end_bit == 0) &&
+        b.n_work_cont + b.n_work_qgauss + b.n_work_qlog == 0 && b.fin_tiles && !(b.flags & TPE_BATCH_NO_FUSE) &&
+        b.n_fin_tiles == 0))
+    return false;
+  for (int64_t r = 0; r < P; ++r) {
+    const tpe_problem& q = rows[r];
+    if (q.tab_mode != TPE_TAB_NONE) continue;
+    if (!((q.flags & TPE_F_CAT_LAZY) && q.family == TPE_FAM_CATEGORICAL && q.samp_len >= 1 && q.samp_len <= 64))
+      return false;
+    lazy.push_back((int32_t)r);
+  }
+  return true;
+}
+static thread_local std::vector<int32_t> g_fused_lazy;
+static thread_local std::vector<tpe_result> g_fused_res;
 
 static int level_run_impl(const tpe_label_in* labels, int32_t n_labels, int32_t n_cand, uint64_t seed,
                           int64_t cand_base, int64_t n_cand_global, int32_t precision, int32_t flags,
@@ -6145,12 +6233,16 @@ static int level_run_impl(const tpe_label_in* labels, int32_t n_labels, int32_t 
     tpe_problem* crow = rec.hp.data();
     const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
     int64_t r = 0;
+    bool one_id = true;                                 // every row the same ctr3 (one id across the labels)
+    uint32_t id0 = 0;
     for (int32_t li = 0; li < n_labels; ++li)           // (the packer's row order: step_prob)
       for (int64_t j = 0; j < labels[li].n_ids; ++j, ++r) {
         const uint32_t c3 = (uint32_t)labels[li].ids[j];
         hrow[r].key0 = crow[r].key0 = k0;
         hrow[r].key1 = crow[r].key1 = k1;
         hrow[r].ctr3 = crow[r].ctr3 = c3;
+        if (r == 0) id0 = c3;
+        one_id = one_id && c3 == id0;
       }
     tpe_internal_phase(TPE_PHASE_PACK);
     x.hp = crow;
@@ -6162,7 +6254,21 @@ static int level_run_impl(const tpe_label_in* labels, int32_t n_labels, int32_t 
     const bool tab_lazy = b.early_select && !(b.n_tab_jobs == 0 || (b.tab_blocks == 0 && b.fgt_max_cells == 0));
     const ResidentPatch pt{(const unsigned long long*)(x.dbase + info.off_problems),
                            (unsigned long long*)(x.dev + info.off_problems), tab_lazy && lazy_ok(&b) ? 1 : 0};
-    g_patch = &pt;
+    // The fused hit: one id, and nothing to launch but k_sample_fast.  The
+    // three per-call words are that launch's arguments and the lazy
+    // categoricals are selected on the host (below): no k_resident_patch.  The
+    // device rows then keep an OLDER call's words.  Nothing may read them: the
+    // argument-keyed kernel does not, the next hit on the patch path rewrites
+    // every row before its stages run, and every other entry that could read
+    // the rows bumps the epoch, which kills this record (the next run is a miss
+    // and uploads the rows afresh).
+    // (A run under the stage profiler takes the patch path: the profile's table
+    // slot is that kernel's on a hit.)
+    std::vector<int32_t>& lazy_rows = g_fused_lazy;
+    const bool fused = !g_prof.on && one_id && r == P && P > 0 && pt.lazy && fused_hit_ok(b, info, crow, P, lazy_rows);
+    const FastKey fk{k0, k1, id0};
+    if (fused) g_fast_key = &fk;
+    else g_patch = &pt;
     if (g_prof.on) {
       g_prof.valid = 0;
       if ((rc = check_batch(&b)) || (rc = run_batch_profiled(&b, stream))) { rec.live = false; return rc; }
@@ -6171,12 +6277,47 @@ static int level_run_impl(const tpe_label_in* labels, int32_t n_labels, int32_t 
       return rc;
     }
     g_patch = nullptr;
+    g_fast_key = nullptr;
     tpe_result* rh = (tpe_result*)(x.host + x.res_off);
     tpe_internal_phase(TPE_PHASE_LAUNCHED);
+    // the fused hit's lazy categoricals, while the host would only wait for the
+    // sample kernel: scanned from the staging buffer's sampler rows and {l, g}
+    // rows (the packed level's, untouched by a hit).  One that does not settle
+    // within the budget: k_resident_patch behind the sample kernel (stream
+    // order: that kernel never read the rows' words) selects every lazy row on
+    // the device, and the unsettled ones keep the device's result.
+    std::vector<tpe_result>& lres = g_fused_res;
+    bool fell_back = false;
+    if (fused) {
+      int64_t budget = lazy_host_budget();              // (what is left of it: the level's, not a problem's)
+      const double* hsamp = (const double*)(x.host + info.off_samp);
+      const double* hc64 = (const double*)(x.host + info.off_comp64);
+      lres.resize(lazy_rows.size());
+      for (size_t k = 0; k < lazy_rows.size(); ++k) {
+        const tpe_problem& q = crow[lazy_rows[k]];
+        lres[k].idx = -2;                                 // (not settled)
+        const int64_t d = tpe_lazy_host_select(q.key0, q.key1, q.ctr2, q.ctr3, q.cand_base, q.n_cand, q.samp_len,
+                                               hsamp + 8 * (int64_t)q.samp_off, 8, hc64 + 4 * (int64_t)q.below_off,
+                                               hc64 + 4 * (int64_t)q.above_off, 4, budget, &lres[k]);
+        if (d < 0) { fell_back = true; budget = 0; }
+        else budget -= d;
+      }
+      if (fell_back) {
+        TPE_LAUNCH(k_resident_patch, dim3(b.n_problems), dim3(kTabTblThreads), 0, x.s, pt.host_rows, pt.dev_rows, 1,
+                   b.samp, (const double4*)b.comp64, b.result);
+        if ((rc = hip_check("k_resident_patch"))) { rec.live = false; return rc; }
+      }
+    }
     if (lg->after_launch) lg->after_launch(lg->ctx);
     const hipError_t e = hipStreamSynchronize(x.s);
     if (e != hipSuccess) { rec.live = false; return fail(TPE_E_HIP, hipGetErrorString(e)); }
     tpe_internal_phase(TPE_PHASE_SYNCED);
+    if (fused) {
+      for (size_t k = 0; k < lazy_rows.size(); ++k)
+        if (lres[k].idx != -2) rh[lazy_rows[k]] = lres[k];
+      g_resident_fused[RES_FUSED].fetch_add(1, std::memory_order_relaxed);
+      if (fell_back) g_resident_fused[RES_FUSED_FALLBACK].fetch_add(1, std::memory_order_relaxed);
+    }
     if (!(b.early_select && level_reduce_runs(x, b, rh, out))) memcpy(out, rh, (size_t)P * sizeof(tpe_result));
     tpe_internal_phase(TPE_PHASE_LEVEL);
     g_resident_stats[RES_HITS].fetch_add(1, std::memory_order_relaxed);

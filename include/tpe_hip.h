@@ -2029,7 +2029,11 @@ int tpe_host_phases(int32_t enable, double* last, int32_t n);
  * process-wide device epoch).  A level run with the same record skips the
  * pack, the upload and the table stage: one small kernel patches key0 / key1 /
  * ctr3 of the device problem rows and selects the lazy categoricals, then the
- * stages run as ever.  Every exported entry that enqueues device work or packs
+ * stages run as ever.  A hit with one id across its labels whose stages are the
+ * fast sample kernel alone is fused: that kernel takes the three words as launch
+ * arguments, the host selects the lazy categoricals while it runs, and the
+ * patch kernel is not launched (unless a host selection does not settle within
+ * its draw budget: then it runs behind the sample kernel).  Every exported entry that enqueues device work or packs
  * into caller memory advances the epoch, so nothing else can have written
  * under a record that is still alive.  tpe_level_run itself is never resident;
  * levels with device fits, expanded levels, TPE_BATCH_WRITE_CAND levels and
@@ -2042,6 +2046,13 @@ int tpe_host_phases(int32_t enable, double* last, int32_t n);
  * variable TPE_RESIDENT_LEVEL=0 (read once) keeps it off whatever the mode.
  * ---------------------------------------------------------------------- */
 int tpe_level_resident(int32_t mode, int64_t* stats);
+
+/* stats[2] gets {fused hits, fused hits that fell back to the patch kernel}
+ * since load (both are also counted among tpe_level_resident's hits).  The
+ * environment variable TPE_LAZY_HOST_BUDGET (read per call, part of the
+ * record's key) sets the draws the host scans per lazy categorical: 0 makes
+ * every fused hit fall back. */
+int tpe_level_resident_fused(int64_t* stats);
 
 #ifdef __cplusplus
 }
