@@ -365,6 +365,40 @@ class JointLiarSegArgs(ctypes.Structure):
     ]
 
 
+class JointLiarMSeg(ctypes.Structure):
+    """tpe_joint_liar_mseg_desc: the device descriptor of one group of a tpe_joint_liar_mseg (JointLiarSeg's fields
+    first)."""
+    _fields_ = JointLiarSeg._fields_ + [
+        ('n_cat', ctypes.c_int32), ('n_quant', ctypes.c_int32),
+        ('cat_upper', ctypes.c_int32 * JOINT_MSEG_MAX_CAT), ('cat_off', ctypes.c_int32 * JOINT_MSEG_MAX_CAT),
+        ('quant_v', ctypes.c_int32 * JOINT_MAX_QUANT), ('quant_edge_off', ctypes.c_int32 * JOINT_MAX_QUANT),
+        ('quant_tab_off', ctypes.c_int32 * JOINT_MAX_QUANT),
+        ('n_edges', ctypes.c_int32), ('n_lattice', ctypes.c_int32),
+        ('above_qmu', ctypes.c_int64), ('quant_edges', ctypes.c_int64),
+        ('cat_miss', ctypes.c_int64), ('cat_bonus', ctypes.c_int64), ('quant_centre', ctypes.c_int64),
+        ('tab_off', ctypes.c_int64),
+    ]
+
+
+# numpy mirror of tpe_joint_liar_mseg_desc
+JOINT_LIAR_MSEG_DTYPE = np.dtype(JOINT_LIAR_SEG_DTYPE.descr + [
+    ('n_cat', '<i4'), ('n_quant', '<i4'),
+    ('cat_upper', '<i4', (JOINT_MSEG_MAX_CAT,)), ('cat_off', '<i4', (JOINT_MSEG_MAX_CAT,)),
+    ('quant_v', '<i4', (JOINT_MAX_QUANT,)), ('quant_edge_off', '<i4', (JOINT_MAX_QUANT,)),
+    ('quant_tab_off', '<i4', (JOINT_MAX_QUANT,)), ('n_edges', '<i4'), ('n_lattice', '<i4'),
+    ('above_qmu', '<i8'), ('quant_edges', '<i8'), ('cat_miss', '<i8'), ('cat_bonus', '<i8'), ('quant_centre', '<i8'),
+    ('tab_off', '<i8')])
+assert JOINT_LIAR_MSEG_DTYPE.itemsize == ctypes.sizeof(JointLiarMSeg) == 592
+
+
+class JointLiarMSegArgs(ctypes.Structure):
+    """tpe_joint_liar_mseg_args: one tpe_joint_liar_mseg (tpe_joint_liar_seg_args' fields, then the f64 pools)."""
+    _fields_ = JointLiarSegArgs._fields_ + [
+        ('pool_f64', ctypes.c_void_p), ('pool_f64_len', ctypes.c_int64),
+        ('liar_pool', ctypes.c_void_p), ('liar_pool_len', ctypes.c_int64),
+    ]
+
+
 class LabelIn(ctypes.Structure):
     _fields_ = [
         ('family', ctypes.c_int32), ('flags', ctypes.c_int32), ('upper', ctypes.c_int32),
@@ -515,7 +549,8 @@ EXPORTS = ('tpe_abi_version', 'tpe_last_error', 'tpe_device_count', 'tpe_tile_si
            'tpe_joint_mseg_table_bytes', 'tpe_joint_mseg_run', 'tpe_joint_report_scratch_bytes',
            'tpe_joint_report', 'tpe_joint_report_profile', 'tpe_joint_run_shard', 'tpe_joint_liar_scratch_bytes',
            'tpe_joint_liar', 'tpe_joint_liar_mixed_scratch_bytes', 'tpe_joint_liar_mixed',
-           'tpe_joint_liar_seg_scratch_bytes', 'tpe_joint_liar_seg')
+           'tpe_joint_liar_seg_scratch_bytes', 'tpe_joint_liar_seg', 'tpe_joint_liar_mseg_scratch_bytes',
+           'tpe_joint_liar_mseg')
 
 # host phases of tpe_suggest_tree (tpe_host_phases order)
 PHASES = ('prefit', 'pack', 'launched', 'synced', 'level', 'return', 'recs')
@@ -682,6 +717,10 @@ def load(path=LIB_PATH):
     lib.tpe_joint_liar_seg_scratch_bytes.restype = ctypes.c_int
     lib.tpe_joint_liar_seg.argtypes = [ctypes.POINTER(JointLiarSegArgs), P, P, P, P, ctypes.c_uint64, P]
     lib.tpe_joint_liar_seg.restype = ctypes.c_int
+    lib.tpe_joint_liar_mseg_scratch_bytes.argtypes = [P, I32, I32, ctypes.POINTER(ctypes.c_uint64)]
+    lib.tpe_joint_liar_mseg_scratch_bytes.restype = ctypes.c_int
+    lib.tpe_joint_liar_mseg.argtypes = [ctypes.POINTER(JointLiarMSegArgs), P, P, P, P, ctypes.c_uint64, P]
+    lib.tpe_joint_liar_mseg.restype = ctypes.c_int
     lib.tpe_joint_profile.argtypes = [I32, P]
     lib.tpe_joint_profile.restype = ctypes.c_int
     lib.tpe_level_profile.argtypes = [ctypes.c_int32]

@@ -45,6 +45,11 @@
 //               the workgroup reads its group's descriptor from device memory
 //               and runs chunk_step<false> over problem chain[first + r].
 // k_liar_seg_pick   round r, one workgroup per such group: pick_step<false>.
+// k_liar_mseg_chunk / k_liar_mseg_pick   the same rounds after a tpe_joint_mseg_run
+//               (tpe_joint_liar_mseg, "Batch-aware picks in mixed branch
+//               groups"): the <true> bodies over SegMView, whose per-dimension
+//               arrays point into the group's descriptor; a continuous group
+//               is their case Dk = Dq = 0.
 // The steps are ordered by the stream alone: no workgroup waits on another, no
 // atomics, every reduction has a fixed shape, so the output bytes are a
 // function of the input bytes.
@@ -117,6 +122,25 @@ struct SegView {
   double* liar_sigma;           // the group's rows of liar_sigma [chain_len * D]
   const double *psig, *low, *high;
 };
+// The same for a group of a tpe_joint_mseg_run: LiarMK's fields too.  The
+// per-dimension arrays are pointers into the device descriptor, so a lane may
+// index them (through a pointer that costs no private copy).
+struct SegMView {
+  int D, C, K, n;
+  int Dc, Dk, Dq, LS, totV;
+  const float* amu;
+  const double *l_out, *g_out;
+  double* rows;                 // [chain_len * LS]
+  double* liar_sigma;           // [chain_len * (Dc + Dq)]
+  double* tabs;                 // [chain_len * totV]
+  const double *psig, *low, *high;
+  const double* aqmu;
+  const double *miss, *bonus, *edges, *centre;
+  const int32_t *cat_upper, *cat_off, *qv, *qeoff, *qtoff;
+};
+// whether View's per-dimension arrays are pointers (SegMView) or kernel arguments (LiarMK)
+template <class View>
+constexpr bool kDimsByPointer = std::is_pointer_v<decltype(View::cat_upper)>;
 
 // the continuous dimensions and the doubles of a liar row
 template <bool kMixed, class View>
@@ -246,17 +270,26 @@ __device__ __forceinline__ void add_liar(const View& p, int i, const float* __re
     if (t < Dk) {                               // a discrete dimension: the category, no bandwidth
       const int v = src ? (int)src[Dc + t] : 0;
       int U = 2;
+      if constexpr (kDimsByPointer<View>) {
+        U = p.cat_upper[t];
+      } else {
 #pragma unroll
-      for (int dd = 0; dd < kMaxK; ++dd)        // (static indices into the kernel arguments: no private copy)
-        if (dd == t) U = p.cat_upper[dd];
+        for (int dd = 0; dd < kMaxK; ++dd)      // (static indices into the kernel arguments: no private copy)
+          if (dd == t) U = p.cat_upper[dd];
+      }
       row[2 * Dc + 1 + t] = (double)clampi(v, U - 1);
     }
     if (Dq > 0) {                               // thread t serves quantised dimension t % Dq, in float64
       const int S = (kThreads / Dq) * Dq, d = t % Dq;
       int V = 2, toff = 0;
+      if constexpr (kDimsByPointer<View>) {
+        V = p.qv[d];
+        toff = p.qtoff[d];
+      } else {
 #pragma unroll
-      for (int dd = 0; dd < kMaxQ; ++dd)
-        if (dd == d) { V = p.qv[dd]; toff = p.qtoff[dd]; }
+        for (int dd = 0; dd < kMaxQ; ++dd)
+          if (dd == d) { V = p.qv[dd]; toff = p.qtoff[dd]; }
+      }
       const int v = clampi(src ? (int)src[Dc + Dk + d] : 0, V - 1);
       const double c = p.centre[toff + v];
       double L = -INFINITY, U = INFINITY;
@@ -522,9 +555,105 @@ __global__ __launch_bounds__(kThreads) void k_liar_seg_pick(const SegK k, int r)
                    k.cand + k.cand_off[prob], 0, r, k.pick_z + (int64_t)prob * TPE_JOINT_MAX_DIMS, s);
 }
 
+// ---- the mixed segmented stage (tpe_joint_liar_mseg): groups of a tpe_joint_mseg_run ----
+static_assert(2 * TPE_JOINT_MSEG_MAX_CONT + 1 + TPE_JOINT_MSEG_MAX_CAT + TPE_JOINT_MAX_QUANT <= kSegRow,
+              "a mixed segment's liar row fits the continuous segments' tile");
+static_assert(offsetof(tpe_joint_liar_mseg_desc, n_cat) == sizeof(tpe_joint_liar_seg_desc), "the shared prefix");
+static_assert(offsetof(tpe_joint_liar_mseg_args, pool_f64) == sizeof(tpe_joint_liar_seg_args), "the shared prefix");
+
+struct SegMK {                  // the kernel argument of both mixed segmented kernels: SegK's fields, then the f64 pools
+  int C, n_chunks;
+  const tpe_joint_liar_mseg_desc* segs;
+  const int32_t* order;
+  const int32_t* chain;
+  const double* log_norm;
+  const float* cand;
+  const int64_t* cand_off;
+  const double *l_out, *g_out;
+  const float* pool;
+  const double* pool64;             // the mseg stage's pool_f64: above_qmu, quant_edges
+  const double* lpool;              // the liar pool: category tables, centres
+  double* rows;                     // scratch
+  double* tabs;                     // scratch, behind the rows
+  tpe_joint_pick* chunk_rec;        // scratch [n_active * n_chunks], by rank
+  tpe_joint_pick* picks;
+  float* pick_z;
+  double* liar_sigma;
+};
+
+__device__ __forceinline__ SegMView seg_mview(const SegMK& k, const tpe_joint_liar_mseg_desc& g) {
+  SegMView v;
+  v.Dc = g.n_dims; v.Dk = g.n_cat; v.Dq = g.n_quant;
+  v.D = v.Dc + v.Dk + v.Dq; v.LS = 2 * v.Dc + 1 + v.Dk + v.Dq; v.totV = g.n_lattice;
+  v.C = k.C; v.K = g.k_above; v.n = g.n_trials;
+  v.amu = k.pool + g.above_mu;
+  v.l_out = k.l_out; v.g_out = k.g_out;
+  v.rows = k.rows + g.row_off;
+  v.liar_sigma = k.liar_sigma + g.sigma_off;
+  v.tabs = k.tabs + g.tab_off;
+  v.psig = g.psig; v.low = g.low; v.high = g.high;
+  v.aqmu = k.pool64 + g.above_qmu; v.edges = k.pool64 + g.quant_edges;
+  v.miss = k.lpool + g.cat_miss; v.bonus = k.lpool + g.cat_bonus; v.centre = k.lpool + g.quant_centre;
+  v.cat_upper = g.cat_upper; v.cat_off = g.cat_off;
+  v.qv = g.quant_v; v.qeoff = g.quant_edge_off; v.qtoff = g.quant_tab_off;
+  return v;
+}
+
+// k_liar_seg_chunk's round over the groups of a tpe_joint_mseg_run
+__global__ __launch_bounds__(kThreads) void k_liar_mseg_chunk(const SegMK k, int r) {
+  __shared__ double tile[kTile * kSegRow];
+  __shared__ Pick slot[kThreads / 64];
+  const int rank = blockIdx.y;
+  const tpe_joint_liar_mseg_desc& g = k.segs[k.order[rank]];
+  const int sl = g.chain_first + r, prob = k.chain[sl];
+  const SegMView v = seg_mview(k, g);
+  chunk_step<true>(v, r, k.cand + k.cand_off[prob], 0, (int64_t)prob * k.C,
+                   k.chunk_rec + (int64_t)rank * k.n_chunks + blockIdx.x, g.log_w, k.log_norm[sl], tile, slot);
+}
+
+// k_liar_seg_pick's round over the groups of a tpe_joint_mseg_run
+__global__ __launch_bounds__(kThreads) void k_liar_mseg_pick(const SegMK k, int r) {
+  __shared__ PickLds<true> s;
+  const int rank = blockIdx.x;
+  const tpe_joint_liar_mseg_desc& g = k.segs[k.order[rank]];
+  const int prob = k.chain[g.chain_first + r];
+  const SegMView v = seg_mview(k, g);
+  pick_step<true>(v, k.chunk_rec + (int64_t)rank * k.n_chunks, k.n_chunks, k.picks + prob,
+                  k.cand + k.cand_off[prob], 0, r, k.pick_z + (int64_t)prob * TPE_JOINT_MAX_DIMS, s);
+}
+
 struct Sizes {
   uint64_t rows_bytes, tabs_bytes, bytes;
 };
+
+// whether the counts of one group of a tpe_joint_liar_mseg are inside the limits
+bool mseg_counts_ok(const tpe_joint_liar_mseg_desc& g) {
+  if (g.n_dims < 0 || g.n_cat < 0 || g.n_quant < 0 || g.n_lattice < 0 || g.chain_len < 0) return false;
+  if (g.n_cat == 0 && g.n_quant == 0) return g.n_dims >= 1 && g.n_dims <= TPE_JOINT_MAX_DIMS && g.n_lattice == 0;
+  return g.n_dims <= TPE_JOINT_MSEG_MAX_CONT && g.n_cat <= TPE_JOINT_MSEG_MAX_CAT && g.n_quant <= kMaxQ &&
+         g.n_lattice <= TPE_JOINT_MAX_LATTICE_TOTAL && (g.n_quant == 0) == (g.n_lattice == 0);
+}
+
+// the scratch of one tpe_joint_liar_mseg from the host descriptors, or false
+// where a count is out of range; n_active: the groups with a problem
+bool liar_mseg_scratch(const tpe_joint_liar_mseg_desc* segs, int32_t n_segs, int32_t n_cand, Sizes* z, int* n_active) {
+  if (!segs || n_segs < 1 || n_cand < 1) return false;
+  uint64_t row_doubles = 0, tab_doubles = 0;
+  int active = 0;
+  for (int s = 0; s < n_segs; ++s) {
+    const tpe_joint_liar_mseg_desc& g = segs[s];
+    if (!mseg_counts_ok(g)) return false;
+    row_doubles += (uint64_t)g.chain_len * (2 * (uint64_t)g.n_dims + 1 + (uint64_t)g.n_cat + (uint64_t)g.n_quant);
+    tab_doubles += (uint64_t)g.chain_len * (uint64_t)g.n_lattice;
+    active += g.chain_len > 0;
+  }
+  const uint64_t chunks = ((uint64_t)n_cand + TPE_JOINT_CHUNK - 1) / TPE_JOINT_CHUNK;
+  z->rows_bytes = row_doubles * sizeof(double);
+  z->tabs_bytes = tab_doubles * sizeof(double);
+  z->bytes = z->rows_bytes + z->tabs_bytes + (uint64_t)active * chunks * sizeof(tpe_joint_pick);
+  if (n_active) *n_active = active;
+  return true;
+}
 
 // the scratch of one tpe_joint_liar_seg from the host descriptors, or false
 // where a count is out of range; n_active: the groups with a problem
@@ -812,6 +941,142 @@ int tpe_joint_liar_seg(const tpe_joint_liar_seg_args* a, tpe_joint_pick* picks, 
     while (hs[a->host_order[active - 1]].chain_len <= r) --active;
     hipLaunchKernelGGL(k_liar_seg_chunk, dim3((unsigned)k.n_chunks, (unsigned)active), dim3(kThreads), 0, st, k, r);
     hipLaunchKernelGGL(k_liar_seg_pick, dim3((unsigned)active), dim3(kThreads), 0, st, k, r);
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));
+  return TPE_OK;
+}
+
+int tpe_joint_liar_mseg_scratch_bytes(const tpe_joint_liar_mseg_desc* host_segs, int32_t n_segs, int32_t n_cand,
+                                      uint64_t* bytes) {
+  Sizes z;
+  if (!bytes || !liar_mseg_scratch(host_segs, n_segs, n_cand, &z, nullptr))
+    return tpe_internal_fail(TPE_E_ARG, "tpe_joint_liar_mseg_scratch_bytes: bad arguments");
+  *bytes = z.bytes;
+  return TPE_OK;
+}
+
+int tpe_joint_liar_mseg(const tpe_joint_liar_mseg_args* a, tpe_joint_pick* picks, float* pick_z, double* liar_sigma,
+                        void* scratch, uint64_t scratch_bytes, void* stream) {
+  const char* who = "tpe_joint_liar_mseg";
+  tpe_internal_epoch_bump();
+  if (!a) return bad(who, "null args");
+  if (a->n_segs < 1 || a->n_probs < 1 || a->n_cand < 1) return bad(who, "n_segs / n_probs / n_cand < 1");
+  if (!a->segs || !a->host_segs || !a->order || !a->host_order || !a->chain || !a->host_chain || !a->log_norm ||
+      !a->host_log_norm || !a->host_prob_seg)
+    return bad(who, "null segs / order / chain / log_norm / host_prob_seg");
+  if (!a->cand || !a->cand_off || !a->l_out || !a->g_out || !a->pool_f32)
+    return bad(who, "null cand / cand_off / l_out / g_out / pool_f32");
+  if (!picks || !pick_z || !liar_sigma) return bad(who, "null outputs");
+  const int S = a->n_segs, P = a->n_probs;
+  const tpe_joint_liar_mseg_desc* hs = a->host_segs;
+  const int64_t n64 = a->pool_f64 ? a->pool_f64_len : 0, nl = a->liar_pool ? a->liar_pool_len : 0;
+  for (int s = 0; s < S; ++s) {
+    const tpe_joint_liar_mseg_desc& g = hs[s];
+    const int Dc = g.n_dims, Dk = g.n_cat, Dq = g.n_quant;
+    if (Dc < 0 || Dk < 0 || Dq < 0) return bad(who, "n_dims / n_cat / n_quant < 0");
+    if (Dk == 0 && Dq == 0) {
+      if (Dc < 1 || Dc > TPE_JOINT_MAX_DIMS) return bad(who, "n_dims outside [1, TPE_JOINT_MAX_DIMS]");
+    } else if (Dc > TPE_JOINT_MSEG_MAX_CONT || Dk > TPE_JOINT_MSEG_MAX_CAT || Dq > kMaxQ) {
+      return bad(who, "n_dims above TPE_JOINT_MSEG_MAX_CONT, n_cat above TPE_JOINT_MSEG_MAX_CAT or n_quant above "
+                      "TPE_JOINT_MAX_QUANT");
+    }
+    if (g.k_above < 1) return bad(who, "k_above < 1");
+    if (g.n_trials < 0) return bad(who, "n_trials < 0");
+    if (!(g.w_sum > 0.0) || !(g.w_sum < INFINITY)) return bad(who, "w_sum must be positive and finite");
+    for (int d = 0; d < Dc + Dq; ++d)             // the continuous dimensions, then the quantised ones
+      if (!(g.psig[d] > 0.0)) return bad(who, "a prior sigma that is not positive");
+    if (g.above_mu < 0 || g.above_mu > a->pool_f32_len - (int64_t)g.k_above * Dc)
+      return bad(who, "an above_mu range that leaves pool_f32");
+    if (g.log_w != log(g.w_sum)) return bad(who, "a log_w that is not the host's log(w_sum)");
+    int64_t cat_total = 0, lat_total = 0;
+    for (int d = 0; d < Dk; ++d) {
+      if (g.cat_upper[d] < 2 || g.cat_upper[d] > TPE_JOINT_MAX_CATS)
+        return bad(who, "a U_d outside [2, TPE_JOINT_MAX_CATS]");
+      cat_total += g.cat_upper[d];
+    }
+    static_assert(TPE_JOINT_MSEG_MAX_CAT * TPE_JOINT_MAX_CATS <= TPE_JOINT_MAX_CAT_TOTAL, "no total to check");
+    for (int d = 0; d < Dk; ++d)
+      if (g.cat_off[d] < 0 || g.cat_off[d] > cat_total - g.cat_upper[d])
+        return bad(who, "a cat_off that leaves the table");
+    if (Dk > 0 && (g.cat_miss < 0 || g.cat_miss > nl - cat_total || g.cat_bonus < 0 || g.cat_bonus > nl - cat_total))
+      return bad(who, "a cat_miss / cat_bonus range that leaves liar_pool");
+    for (int d = 0; d < Dq; ++d) {
+      if (g.quant_v[d] < 2 || g.quant_v[d] > kMaxV) return bad(who, "a V_d outside [2, TPE_JOINT_MAX_LATTICE]");
+      if (g.quant_tab_off[d] != lat_total) return bad(who, "a quant_tab_off that is not the running sum of V_d");
+      lat_total += g.quant_v[d];
+    }
+    if (lat_total > TPE_JOINT_MAX_LATTICE_TOTAL)
+      return bad(who, "more than TPE_JOINT_MAX_LATTICE_TOTAL lattice values");
+    if (g.n_lattice != lat_total) return bad(who, "an n_lattice that is not the sum of V_d");
+    if (Dq > 0) {
+      for (int d = 0; d < Dq; ++d)
+        if (g.quant_edge_off[d] < 0 || g.quant_edge_off[d] > g.n_edges - g.quant_v[d] - 1)
+          return bad(who, "a quant_edge_off that leaves quant_edges");
+      if (g.quant_edges < 0 || g.quant_edges > n64 - g.n_edges || g.above_qmu < 0 ||
+          g.above_qmu > n64 - (int64_t)g.k_above * Dq)
+        return bad(who, "a quant_edges / above_qmu range that leaves pool_f64");
+      if (g.quant_centre < 0 || g.quant_centre > nl - lat_total)
+        return bad(who, "a quant_centre range that leaves liar_pool");
+    }
+  }
+  // the chains: host_prob_seg alone fixes every count, the order, the slots and the offsets
+  const char* part = "a chain table that is not the partition of the problems host_prob_seg gives";
+  for (int p = 0; p < P; ++p)
+    if (a->host_prob_seg[p] < 0 || a->host_prob_seg[p] >= S) return bad(who, "a host_prob_seg entry outside [0, n_segs)");
+  int64_t slot = 0, row = 0, tab = 0, sig = 0;
+  int n_active = 0, longest = 0;
+  for (int rank = 0; rank < S; ++rank) {
+    const int s = a->host_order[rank];
+    if (s < 0 || s >= S) return bad(who, part);
+    const tpe_joint_liar_mseg_desc& g = hs[s];
+    if (g.chain_len < 0 || g.chain_len > P - slot || g.chain_first != slot) return bad(who, part);
+    if (rank > 0) {                               // chain length descending, ties by group index: a permutation
+      const int q = a->host_order[rank - 1];
+      if (hs[q].chain_len < g.chain_len || (hs[q].chain_len == g.chain_len && q >= s)) return bad(who, part);
+    }
+    if (g.row_off != row || g.tab_off != tab || g.sigma_off != sig)
+      return bad(who, "a row_off / tab_off / sigma_off that is not the running sum");
+    slot += g.chain_len;
+    row += (int64_t)g.chain_len * (2 * g.n_dims + 1 + g.n_cat + g.n_quant);
+    tab += (int64_t)g.chain_len * g.n_lattice;
+    sig += (int64_t)g.chain_len * (g.n_dims + g.n_quant);
+    n_active += g.chain_len > 0;
+    if (g.chain_len > longest) longest = g.chain_len;
+  }
+  if (slot != P) return bad(who, part);
+  {                                               // slot first_s + j holds the (j + 1)-th problem of group s
+    std::vector<int> next((size_t)S, 0);
+    for (int p = 0; p < P; ++p) {
+      const tpe_joint_liar_mseg_desc& g = hs[a->host_prob_seg[p]];
+      const int j = next[(size_t)a->host_prob_seg[p]]++;
+      if (j >= g.chain_len || a->host_chain[g.chain_first + j] != p) return bad(who, part);
+      if (a->host_log_norm[g.chain_first + j] != log1p((double)j / g.w_sum))
+        return bad(who, "a log_norm that is not the host's log1p(j / w_sum)");
+    }
+    for (int s = 0; s < S; ++s)
+      if (next[(size_t)s] != hs[s].chain_len) return bad(who, part);
+  }
+  Sizes z;
+  if (n_active > 65535 || !liar_mseg_scratch(hs, S, a->n_cand, &z, nullptr)) return bad(who, "sizes out of range");
+  if (!scratch || scratch_bytes < z.bytes) return bad(who, "scratch too small");
+
+  SegMK k;
+  k.C = a->n_cand;
+  k.n_chunks = (int)(((int64_t)a->n_cand + TPE_JOINT_CHUNK - 1) / TPE_JOINT_CHUNK);
+  k.segs = a->segs; k.order = a->order; k.chain = a->chain; k.log_norm = a->log_norm;
+  k.cand = a->cand; k.cand_off = a->cand_off; k.l_out = a->l_out; k.g_out = a->g_out; k.pool = a->pool_f32;
+  k.pool64 = a->pool_f64; k.lpool = a->liar_pool;
+  k.rows = (double*)scratch;
+  k.tabs = (double*)((char*)scratch + z.rows_bytes);
+  k.chunk_rec = (tpe_joint_pick*)((char*)scratch + z.rows_bytes + z.tabs_bytes);
+  k.picks = picks; k.pick_z = pick_z; k.liar_sigma = liar_sigma;
+  const hipStream_t st = (hipStream_t)stream;
+  int active = n_active;                          // the groups of chain length > r: a prefix of the order
+  for (int r = 0; r < longest; ++r) {
+    while (hs[a->host_order[active - 1]].chain_len <= r) --active;
+    hipLaunchKernelGGL(k_liar_mseg_chunk, dim3((unsigned)k.n_chunks, (unsigned)active), dim3(kThreads), 0, st, k, r);
+    hipLaunchKernelGGL(k_liar_mseg_pick, dim3((unsigned)active), dim3(kThreads), 0, st, k, r);
   }
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return tpe_internal_fail(TPE_E_HIP, hipGetErrorString(e));

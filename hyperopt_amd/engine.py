@@ -1583,10 +1583,19 @@ class Engine(object):
         la.host_segs, la.host_order, la.host_chain = lb.segs.ctypes.data, lb.order.ctypes.data, lb.chain.ctypes.data
         la.host_log_norm, la.host_prob_seg = lb.log_norm.ctypes.data, b.prob_seg.ctypes.data
         la.cand_off, la.pool_f32, la.pool_f32_len = a.cand_off, a.pool_f32, b.n32
+        return self._joint_seg_liar_call('seg', a, la, b, lb, C, return_cand, want_lg, return_sigma)
+
+    def _joint_seg_liar_call(self, fn, a, la, b, lb, C, return_cand, want_lg, return_sigma):
+        """What the two segmented liar stages share: scratch, the result block,
+        the stage ``fn``_run (``a``) with its three buffers kept, the liar
+        stage tpe_joint_liar_``fn``'s suffix (``la``) on the same stream, one
+        transfer, and the results on the host.  ``b`` / ``lb``: the two blobs."""
+        stage, liar = 'tpe_joint_' + fn, 'tpe_joint_liar_' + fn
+        P, S = len(b.prob_seg), len(lb.segs)
         nb, lnb = ctypes.c_uint64(0), ctypes.c_uint64(0)
-        N.check(self.lib.tpe_joint_seg_scratch_bytes(P, C, ctypes.byref(nb)), self.lib, 'tpe_joint_seg_scratch_bytes')
-        N.check(self.lib.tpe_joint_liar_seg_scratch_bytes(lb.segs.ctypes.data, S, C, ctypes.byref(lnb)), self.lib,
-                'tpe_joint_liar_seg_scratch_bytes')
+        N.check(getattr(self.lib, stage + '_scratch_bytes')(P, C, ctypes.byref(nb)), self.lib, stage + '_scratch_bytes')
+        N.check(getattr(self.lib, liar + '_scratch_bytes')(lb.segs.ctypes.data, S, C, ctypes.byref(lnb)), self.lib,
+                liar + '_scratch_bytes')
         d_scr = self._buf('joint_scratch', (nb.value + 7) // 8, torch.float64)
         d_lscr = self._buf('joint_liar_scratch', (lnb.value + 7) // 8, torch.float64)
         # one result block of 8-byte words: picks, pick rows (f32 pairs), bandwidths; then what only the device
@@ -1600,11 +1609,10 @@ class Engine(object):
         o_l, o_g, o_cand = out + 8 * (head + rec_w), out + 8 * (head + rec_w + lg_w), out + 8 * (head + rec_w + 2 * lg_w)
         la.cand, la.l_out, la.g_out = o_cand, o_l, o_g
         stream = self._stream()
-        N.check(self.lib.tpe_joint_seg_run(ctypes.byref(a), out + 8 * head, o_cand, o_l, o_g, d_scr.data_ptr(),
-                                           d_scr.numel() * 8, ctypes.c_void_p(stream)), self.lib, 'tpe_joint_seg_run')
-        N.check(self.lib.tpe_joint_liar_seg(ctypes.byref(la), out, out + 8 * pk_w, out + 8 * (pk_w + z_w),
-                                            d_lscr.data_ptr(), d_lscr.numel() * 8, ctypes.c_void_p(stream)), self.lib,
-                'tpe_joint_liar_seg')
+        N.check(getattr(self.lib, stage + '_run')(ctypes.byref(a), out + 8 * head, o_cand, o_l, o_g, d_scr.data_ptr(),
+                                                  d_scr.numel() * 8, ctypes.c_void_p(stream)), self.lib, stage + '_run')
+        N.check(getattr(self.lib, liar)(ctypes.byref(la), out, out + 8 * pk_w, out + 8 * (pk_w + z_w),
+                                        d_lscr.data_ptr(), d_lscr.numel() * 8, ctypes.c_void_p(stream)), self.lib, liar)
         host = d_out[:head + ((rec_w + 2 * lg_w + cand_w) if (return_cand or want_lg) else 0)].cpu().numpy()
         picks = host[:pk_w].view(N.JOINT_PICK_DTYPE)
         z = host[pk_w:pk_w + z_w].view(np.float32).reshape(P, MD)
@@ -1621,11 +1629,65 @@ class Engine(object):
         if want_lg:
             res.append(host[head + rec_w:head + rec_w + lg_w].reshape(P, C).copy())
             res.append(host[head + rec_w + lg_w:head + rec_w + 2 * lg_w].reshape(P, C).copy())
-        if return_sigma:
+        if return_sigma:                                 # a row: the continuous dimensions, then the quantised ones
             sig = host[pk_w + z_w:head]
-            res.append([sig[int(g['sigma_off']):int(g['sigma_off']) + int(g['chain_len']) * int(g['n_dims'])]
-                        .reshape(int(g['chain_len']), int(g['n_dims'])).copy() for g in lb.segs])
+            quant = 'n_quant' in lb.segs.dtype.names
+            rows = []
+            for g in lb.segs:
+                L, w = int(g['chain_len']), int(g['n_dims']) + (int(g['n_quant']) if quant else 0)
+                rows.append(sig[int(g['sigma_off']):int(g['sigma_off']) + L * w].reshape(L, w).copy())
+            res.append(rows)
         return tuple(res)
+
+    def run_joint_msegments_liar(self, models, stream_words, prob_seg, prob_id, n_cand, seed, liar=True, centres=None,
+                                 inject=None, return_cand=False, want_lg=False, return_sigma=False):
+        """``run_joint_segments_liar`` where a group may also hold discrete or
+        quantised labels (tpe_joint_mseg_run, then tpe_joint_liar_mseg on the
+        same stream, include/tpe_hip.h "Batch-aware picks in mixed branch
+        groups"; DESIGN.md of the same name).  ``models`` as
+        ``run_joint_segments`` takes them.  The picks, rows and bandwidths of
+        group s are byte for byte those of ``run_joint_liar_mixed`` (a
+        continuous group: ``run_joint``) over that group with its stream word,
+        ids = its problems' ids, ``liar=W_s``, its centres and
+        ``return_sigma=True``.
+
+        ``centres``: per group None or one float64 [V_d] array per quantised
+        dimension (QuantModel.centres()); a group with a quantised label needs
+        them.  ``return_sigma`` rows are [L_s, Dc_s + Dq_s]: the continuous
+        dimensions, then the quantised ones.  The other arguments and the
+        return shapes are ``run_joint_segments_liar``'s; with no discrete or
+        quantised group among ``models`` the call IS that method."""
+        if not any(JP.seg_parts(m)[4] or JP.seg_parts(m)[5] for m in models):
+            if centres is not None and any(c for c in centres):
+                raise ValueError('joint stage: centres without a quantised dimension')
+            return self.run_joint_segments_liar(models, stream_words, prob_seg, prob_id, n_cand, seed, liar=liar,
+                                                inject=inject, return_cand=return_cand, want_lg=want_lg,
+                                                return_sigma=return_sigma)
+        W = JP.liar_weight_sums(liar, models)
+        C = int(n_cand)
+        b = JP.segment_blob(models, stream_words, prob_seg, prob_id, C, inject, N.JOINT_MSEG_DTYPE)
+        lb = JP.liar_msegment_blob(models, b.segs, W, b.prob_seg, centres)
+        P, S = len(b.prob_seg), len(models)
+        a = self._joint_seg_args(N.JointMSegArgs, b, S, C, seed, inject)
+        nb = ctypes.c_uint64(0)
+        N.check(self.lib.tpe_joint_mseg_table_bytes(b.segs.ctypes.data, S, ctypes.byref(nb)), self.lib,
+                'tpe_joint_mseg_table_bytes')
+        assert nb.value == 4 * b.n_table, (nb.value, b.n_table)
+        if b.n_table:
+            d_tab = self._buf('joint_mseg_table', b.n_table, torch.float32)
+            a.quant_table, a.quant_table_bytes = d_tab.data_ptr(), d_tab.numel() * 4
+        d_lblob = self._buf('joint_liar_seg_blob', len(lb.blob), torch.uint8)
+        d_lblob[:len(lb.blob)].copy_(torch.from_numpy(lb.blob))
+        la = N.JointLiarMSegArgs()
+        la.n_segs, la.n_probs, la.n_cand = S, P, C
+        for name, off in zip(JP.LIAR_MSECTIONS, lb.offs):
+            setattr(la, name, d_lblob.data_ptr() + int(off))
+        la.liar_pool_len = lb.n_pool
+        la.host_segs, la.host_order, la.host_chain = lb.segs.ctypes.data, lb.order.ctypes.data, lb.chain.ctypes.data
+        la.host_log_norm, la.host_prob_seg = lb.log_norm.ctypes.data, b.prob_seg.ctypes.data
+        la.cand_off, la.pool_f32, la.pool_f32_len = a.cand_off, a.pool_f32, b.n32
+        la.pool_f64, la.pool_f64_len = a.pool_f64, b.n64
+        return self._joint_seg_liar_call('mseg', a, la, b, lb, C, return_cand, want_lg, return_sigma)
 
     def run_joint_mixed(self, below, above, low, high, cats, ids, n_cand, seed, inject=None, return_cand=False,
                         want_lg=False, report_k=0, stream_word=None, shard=None):

@@ -352,3 +352,84 @@ def liar_segment_blob(models, segs, weight_sums, prob_seg):
     parts = [out.view(np.uint8), log_norm.view(np.uint8), ch.order.view(np.uint8), ch.chain.view(np.uint8)]
     offs = np.concatenate([[0], np.cumsum([len(x) for x in parts])])
     return LiarSegmentBlob(np.concatenate(parts), offs, out, ch.order, ch.chain, log_norm, sig)
+
+
+# What liar_msegment_blob returns: LiarSegmentBlob's fields (segs:
+# N.JOINT_LIAR_MSEG_DTYPE; sections in the order LIAR_MSECTIONS) and n_pool, the
+# doubles of the liar pool.
+LiarMSegmentBlob = collections.namedtuple('LiarMSegmentBlob', 'blob offs segs order chain log_norm n_sigma n_pool')
+LIAR_MSECTIONS = ('segs', 'log_norm', 'liar_pool', 'order', 'chain')
+
+
+def liar_msegment_blob(models, segs, weight_sums, prob_seg, centres=None):
+    """liar_segment_blob for the groups of a mixed segmented stage
+    (include/tpe_hip.h "Batch-aware picks in mixed branch groups"): ``segs`` are
+    that stage's descriptors (N.JOINT_MSEG_DTYPE), whose above_mu, above_qmu and
+    quant_edges offsets and per-dimension sizes the liar descriptors
+    (N.JOINT_LIAR_MSEG_DTYPE) share.  The float64 liar pool, uploaded in the
+    same blob, holds per group the natural-log category tables of the above side
+    (joint.liar_cat_tables: miss, then bonus) and the centres.  ``centres``: per
+    group None or one float64 [V_d] array per quantised dimension
+    (QuantModel.centres()); a group with a quantised label needs them."""
+    import math
+    S = len(models)
+    if centres is None:
+        centres = [None] * S
+    if len(centres) != S:
+        raise ValueError('joint stage: centres must hold one entry per group')
+    ch = liar_chains(prob_seg, S)
+    out = np.zeros(S, dtype=N.JOINT_LIAR_MSEG_DTYPE)
+    lens = np.bincount(np.asarray(prob_seg, dtype=np.int64), minlength=S)
+    log_norm = np.zeros(len(ch.chain), dtype=np.float64)
+    pool, fill = [], 0
+    row = tab = sig = 0
+    for s in ch.order:
+        above, low, high, cats, quants = seg_parts(models[s])[1:6]
+        g, m, W, L = out[s], segs[s], float(weight_sums[s]), int(lens[s])
+        Dc, Dk, Dq = int(m['n_dims']), int(m['n_cat']), int(m['n_quant'])
+        g['n_dims'], g['n_cat'], g['n_quant'] = Dc, Dk, Dq
+        g['k_above'], g['n_trials'] = m['k_above'], m['k_above'] - 1
+        g['chain_len'], g['chain_first'] = L, ch.first[s]
+        g['w_sum'], g['log_w'], g['above_mu'] = W, math.log(W), m['above_mu']
+        g['psig'], g['low'], g['high'] = 1.0, -np.inf, np.inf
+        if Dc:
+            g['psig'][:Dc] = np.asarray(above[2], dtype=np.float64).reshape(-1, Dc)[0]
+            g['low'][:Dc], g['high'][:Dc] = np.asarray(low, dtype=np.float64), np.asarray(high, dtype=np.float64)
+        vs =[int(v) for v in m['quant_v'][:Dq]]
+        if Dk:
+            g['cat_upper'], g['cat_off'] = m['cat_upper'], m['cat_off']
+            tabs = [J.liar_cat_tables(c[2], c[4]) for c in cats]
+            for field, i in (('cat_miss', 0), ('cat_bonus', 1)):
+                g[field] = fill
+                pool.extend(np.asarray(t[i], dtype=np.float64).reshape(-1) for t in tabs)
+                fill += int(sum(m['cat_upper'][:Dk]))
+        if Dq:
+            cs = centres[s]
+            if cs is None or len(cs) != Dq:
+                raise ValueError('joint stage: liar with quantised labels needs centres, one array per quantised '
+                                 'dimension (joint.quant_centres): group %d' % s)
+            cs = [np.ascontiguousarray(c, dtype=np.float64).reshape(-1) for c in cs]
+            if any(len(c) != V or not np.isfinite(c).all() for c, V in zip(cs, vs)):
+                raise ValueError('joint stage: centres must hold one finite value per lattice value')
+            g['psig'][Dc:Dc + Dq] = [float(np.asarray(q[3], dtype=np.float64).reshape(-1)[0]) for q in quants]
+            g['quant_v'], g['quant_edge_off'], g['n_edges'] = m['quant_v'], m['quant_edge_off'], m['n_edges']
+            g['quant_tab_off'][:Dq] = np.cumsum([0] + vs[:-1])
+            g['n_lattice'] = sum(vs)
+            g['above_qmu'], g['quant_edges'] = m['above_qmu'], m['quant_edges']
+            g['quant_centre'] = fill
+            pool.extend(cs)
+            fill += sum(vs)
+        elif centres[s]:
+            raise ValueError('joint stage: centres without a quantised dimension: group %d' % s)
+        g['row_off'], g['tab_off'], g['sigma_off'] = row, tab, sig
+        for j in range(L):
+            log_norm[ch.first[s] + j] = math.log1p(j / W)
+        row += L * (2 * Dc + 1 + Dk + Dq)
+        tab += L * sum(vs)
+        sig += L * (Dc + Dq)
+    lpool = np.concatenate(pool) if pool else np.zeros(0)
+    assert len(lpool) == fill
+    parts = [out.view(np.uint8), log_norm.view(np.uint8), lpool.view(np.uint8), ch.order.view(np.uint8),
+             ch.chain.view(np.uint8)]
+    offs = np.concatenate([[0], np.cumsum([len(x) for x in parts])])
+    return LiarMSegmentBlob(np.concatenate(parts), offs, out, ch.order, ch.chain, log_norm, sig, fill)

@@ -1062,7 +1062,18 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
     'mixed' byte for byte.  A branch group with a discrete or quantised label
     (``joint_branches_mixed``), ``joint_shard``, and the value without
     ``joint`` or without ``joint_branches`` raise ValueError.  Univariate
-    labels, the gates included, stay as they are."""
+    labels, the gates included, stay as they are.
+
+    ``joint_liar='branches_mixed'`` (with ``joint_branches``): everything
+    'branches' does, and a branch group may also hold discrete or quantised
+    labels (``joint_branches_mixed``; DESIGN.md "Batch-aware picks in mixed
+    branch groups"): one chain per branch, all chains in one segmented device
+    stage (Engine.run_joint_msegments_liar), a picked category or lattice value
+    counting as under 'mixed'.  On a space whose branch groups are all
+    continuous, or without a branch group, it is 'branches' byte for byte; one
+    id, or ids that all take different branches, are the same bytes as without
+    the keyword.  ``joint_shard`` and the value without ``joint`` or without
+    ``joint_branches`` raise ValueError."""
     if sampler not in ('philox', 'replay'):
         raise ValueError("sampler must be 'philox' or 'replay'")
     if joint_shard is not None:
@@ -1101,35 +1112,38 @@ TPE_JOINT_WIDE_MAX_CAT = N.JOINT_WIDE_MAX_CAT
 
 
 def _joint_liar_mode(joint_liar):
-    """``joint_liar`` as None (off: False or None), True, 'mixed' or 'branches';
-    ValueError for anything else (another string, a number)."""
+    """``joint_liar`` as None (off: False or None), True, 'mixed', 'branches' or
+    'branches_mixed'; ValueError for anything else (another string, a number)."""
     if joint_liar is None or (isinstance(joint_liar, (bool, np.bool_)) and not joint_liar):
         return None
     if isinstance(joint_liar, (bool, np.bool_)):
         return True
-    if isinstance(joint_liar, str) and joint_liar in ('mixed', 'branches'):
+    if isinstance(joint_liar, str) and joint_liar in ('mixed', 'branches', 'branches_mixed'):
         return joint_liar
-    raise ValueError("joint_liar must be True or 'mixed', or 'branches' with joint_branches (or False): %r"
-                     % (joint_liar,))
+    raise ValueError("joint_liar must be True or 'mixed', or 'branches' with joint_branches or 'branches_mixed' with "
+                     'joint_branches (or False): %r' % (joint_liar,))
 
 
 def _joint_liar_check(joint, joint_shard, plan=None, mode=True, joint_branches=False):
-    """ValueError where ``joint_liar`` (``mode``: True, 'mixed' or 'branches')
-    does not apply: without ``joint``, with ``joint_shard``, 'branches' without
-    ``joint_branches``, and (``plan`` = _joint_plan's result) for a root group
-    that is missing or, under True, holds a discrete or quantised label, and for
-    any branch group; under 'branches' for a branch group that holds a discrete
-    or quantised label, and without any branch group what 'mixed' raises.
-    Touches no device."""
+    """ValueError where ``joint_liar`` (``mode``: True, 'mixed', 'branches' or
+    'branches_mixed') does not apply: without ``joint``, with ``joint_shard``,
+    'branches' / 'branches_mixed' without ``joint_branches``, and (``plan`` =
+    _joint_plan's result) for a root group that is missing or, under True,
+    holds a discrete or quantised label, and for any branch group; under
+    'branches' for a branch group that holds a discrete or quantised label
+    ('branches_mixed' admits it), and under both without any branch group what
+    'mixed' raises.  Touches no device."""
     if joint is False or joint is None:
         raise ValueError('joint_liar needs joint=True or joint=[labels]: it only changes how the joint stage picks')
     if joint_shard is not None:
         raise ValueError('joint_liar=%r does not combine with joint_shard' % (mode,))
-    if mode == 'branches' and not joint_branches:
-        raise ValueError("joint_liar='branches' needs joint_branches=True: the keyword that makes branch groups")
+    if mode in ('branches', 'branches_mixed') and not joint_branches:
+        raise ValueError('joint_liar=%r needs joint_branches=True: the keyword that makes branch groups' % (mode,))
     if plan is None:
         return
     group, branch_groups = plan
+    if mode == 'branches_mixed' and branch_groups:   # every kind of branch group
+        return
     if mode == 'branches' and branch_groups:
         for rows in branch_groups:
             other = [r.label for r in rows if r.dist not in _joint.JOINT_DISTS]
@@ -1137,7 +1151,7 @@ def _joint_liar_check(joint, joint_shard, plan=None, mode=True, joint_branches=F
                 raise ValueError("joint_liar='branches' needs branch groups of continuous labels only "
                                  '(joint_branches_mixed): %r is discrete or quantised' % other[0])
         return
-    if mode == 'branches':                       # no branch group in the space: 'mixed'
+    if mode in ('branches', 'branches_mixed'):   # no branch group in the space: 'mixed'
         mode = 'mixed'
     if branch_groups:
         raise ValueError('joint_liar=%r does not combine with branch groups (joint_branches)' % (mode,))
@@ -1559,9 +1573,10 @@ def _suggest_joint(table, hist, new_ids, seed, prior_weight, n_EI_candidates, ga
     routing is the univariate pass's).  ``joint_shard``: the two joint stages
     run over this rank's candidate range and exchange their records
     (_JointParts); the univariate pass is replicated.  ``joint_liar`` (False,
-    True, 'mixed' or 'branches'): the root group's ids pick greedily
-    (Engine.run_joint's ``liar``); 'branches': so do the ids of every branch
-    group (Engine.run_joint_segments_liar)."""
+    True, 'mixed', 'branches' or 'branches_mixed'): the root group's ids pick
+    greedily (Engine.run_joint's ``liar``); 'branches' / 'branches_mixed': so do
+    the ids of every branch group (Engine.run_joint_segments_liar /
+    run_joint_msegments_liar)."""
     cc = _suggest_local(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, 'philox', 'fp32', device,
                         None, True)
     if len(cc) == 0:
@@ -1593,7 +1608,8 @@ def _suggest_joint(table, hist, new_ids, seed, prior_weight, n_EI_candidates, ga
             active[:, r.index] = True
     if branch_groups:
         _suggest_branches(engine, hist, ids, seed, prior_weight, n_EI_candidates, gamma, branch_groups,
-                          np.asarray(cc.active, dtype=bool), values, parts, joint_liar == 'branches')
+                          np.asarray(cc.active, dtype=bool), values, parts,
+                          joint_liar if joint_liar in ('branches', 'branches_mixed') else False)
     cc = ChoiceColumns(table.labels, values, active)
     return cc if columns else cc.dicts(table)
 
@@ -1620,7 +1636,9 @@ def _suggest_branches(engine, hist, ids, seed, prior_weight, n_EI_candidates, ga
     records of all ranks are combined.  ``liar`` (joint_liar='branches'): the ids
     that take one branch pick its vector greedily, in the order given
     (Engine.run_joint_segments_liar, W of every group's above side as
-    side_mixture weighs it)."""
+    side_mixture weighs it); 'branches_mixed': the same over groups that may
+    hold discrete or quantised labels (Engine.run_joint_msegments_liar, with
+    each model's centres())."""
     below_tids = _history.split_below(hist, gamma)
     models, words, prob_seg, prob_id, where = [], [], [], [], []
     for rows in branch_groups:
@@ -1642,7 +1660,12 @@ def _suggest_branches(engine, hist, ids, seed, prior_weight, n_EI_candidates, ga
     if liar:
         assert parts is None, 'joint_liar does not combine with joint_shard'
         W = [_joint.side_weight_sum(len(m.above[0]) - 1, prior_weight, DEFAULT_LF) for m in models]
-        rec = engine.run_joint_segments_liar(models, words, prob_seg, prob_id, int(n_EI_candidates), seed, liar=W)
+        if liar == 'branches_mixed':
+            rec = engine.run_joint_msegments_liar(
+                models, words, prob_seg, prob_id, int(n_EI_candidates), seed, liar=W,
+                centres=[m.centres() if hasattr(m, 'centres') else None for m in models])
+        else:
+            rec = engine.run_joint_segments_liar(models, words, prob_seg, prob_id, int(n_EI_candidates), seed, liar=W)
     elif parts is None:
         rec = engine.run_joint_segments(models, words, prob_seg, prob_id, int(n_EI_candidates), seed)
     else:

@@ -1999,6 +1999,119 @@ int tpe_joint_liar_seg(const tpe_joint_liar_seg_args* args, tpe_joint_pick* pick
                        double* liar_sigma, void* scratch, uint64_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Batch-aware picks in mixed branch groups (tpe_joint_liar.hip,
+ * k_liar_mseg_chunk and k_liar_mseg_pick; additive exports, the ABI stays 24).
+ * tpe_joint_liar_seg for the problems of a tpe_joint_mseg_run: a group may also
+ * hold n_cat discrete and n_quant quantised labels.  Problems, chains, order,
+ * slots, log_w and log_norm are tpe_joint_liar_seg's; there are no given liars.
+ * Inside a chain the model is the solo stage of the group's kind with n_given =
+ * 0: tpe_joint_liar_mixed's for a group with n_cat + n_quant > 0, tpe_joint_liar's
+ * for a continuous one.  No new math.
+ *
+ * Defining property: picks, pick_z rows and liar_sigma rows of group s are byte
+ * for byte those of a tpe_joint_liar_mixed (n_cat = n_quant = 0: tpe_joint_liar)
+ * with n_ids = chain_len over that group's problems' cand, l_out and g_out in
+ * chain order, its above_mu, above_qmu, tables, k_above, n_trials, w_sum, psig,
+ * low, high and n_given = 0.  A chain of one problem is tpe_joint_mseg_run's
+ * record of that problem.  The device code is tpe_joint_liar_mixed's: the bodies
+ * of k_liar_chunk<true> and k_liar_pick<true> over a second view of one group,
+ * built in registers from the group's descriptor in device memory, its
+ * per-dimension arrays pointers into that descriptor.  A continuous group runs
+ * the same bodies with n_cat = n_quant = 0, which gives k_liar_seg_*'s bytes.
+ *
+ * Descriptor: the fields of tpe_joint_liar_seg_desc at the same offsets (n_dims
+ * counts the continuous labels; psig[n_dims + d] is quantised dimension d's),
+ * then the group's discrete and quantised parts.  above_qmu [k_above * n_quant]
+ * and quant_edges [n_edges] are ELEMENT offsets into the pool_f64 of the
+ * tpe_joint_mseg_run before (the same values as in its tpe_joint_mseg).  cat_miss
+ * / cat_bonus [sum U_d] (natural logarithms, as tpe_joint_liar_mixed_args) and
+ * quant_centre [sum V_d] are element offsets into liar_pool, a device f64 array
+ * of this call (liar_pool_len elements).  quant_tab_off[d] = sum of V_e over e <
+ * d; n_lattice = sum V_d.  row_off, tab_off and sigma_off are the running sums,
+ * in `order`, of chain_len (2 n_dims + 1 + n_cat + n_quant), chain_len n_lattice
+ * and chain_len (n_dims + n_quant): the group's liar rows and liar bin tables
+ * (ln Q_i(v), read through L1 / L2 as in the solo stage) in scratch, and its rows
+ * of liar_sigma.
+ *
+ * Launches: tpe_joint_liar_seg's rounds with k_liar_mseg_chunk and
+ * k_liar_mseg_pick: 2 x (longest chain) launches, ordered by the stream alone, no
+ * atomics, plain vector stores, fixed reduction shapes: the same call twice
+ * gives the same bytes.
+ *
+ * tpe_joint_liar_mseg_scratch_bytes = sum_s chain_len_s (2 n_dims + 1 + n_cat +
+ * n_quant + n_lattice)_s 8 + n_active ceil(n_cand / TPE_JOINT_CHUNK) 24; it reads
+ * n_dims, n_cat, n_quant, n_lattice and chain_len of host_segs and returns
+ * TPE_E_ARG for null pointers, n_segs or n_cand < 1, a negative count, counts
+ * outside the limits below or a chain_len < 0.  tpe_joint_liar_mseg returns
+ * TPE_E_ARG before any launch (no device needed), from the host copies, for
+ * everything tpe_joint_liar_seg checks (a continuous group: n_dims in [1,
+ * TPE_JOINT_MAX_DIMS]) and per group with n_cat + n_quant > 0: a negative count,
+ * n_dims > TPE_JOINT_MSEG_MAX_CONT, n_cat > TPE_JOINT_MSEG_MAX_CAT, n_quant >
+ * TPE_JOINT_MAX_QUANT; a psig (continuous or quantised) that is not positive; a
+ * U_d outside [2, TPE_JOINT_MAX_CATS] (four of them cannot exceed
+ * TPE_JOINT_MAX_CAT_TOTAL), a cat_off that leaves [0, total - U_d], a cat_miss /
+ * cat_bonus range that leaves liar_pool; a V_d outside [2, TPE_JOINT_MAX_LATTICE], more than
+ * TPE_JOINT_MAX_LATTICE_TOTAL lattice values, an n_lattice that is not sum V_d, a
+ * quant_tab_off that is not the running sum of V_d, a quant_edge_off that leaves
+ * [0, n_edges - V_d - 1], a quant_edges / above_qmu range that leaves pool_f64
+ * (or a null pool_f64), a quant_centre range that leaves liar_pool; a null
+ * liar_pool where a group needs it; a row_off, tab_off or sigma_off that is not
+ * the running sum.
+ * ---------------------------------------------------------------------- */
+typedef struct tpe_joint_liar_mseg_desc {
+  int32_t n_dims, k_above, n_trials;       /* as tpe_joint_liar_seg_desc ...; n_dims: the continuous labels */
+  int32_t chain_len;
+  int32_t chain_first;
+  int32_t reserved;
+  double w_sum, log_w;
+  int64_t above_mu;
+  int64_t row_off, sigma_off;
+  double psig[TPE_JOINT_MAX_DIMS];         /* [d] continuous, [n_dims + d] quantised dimension d */
+  double low[TPE_JOINT_MAX_DIMS], high[TPE_JOINT_MAX_DIMS];   /* ... up to here; the continuous bounds */
+  int32_t n_cat, n_quant;
+  int32_t cat_upper[TPE_JOINT_MSEG_MAX_CAT], cat_off[TPE_JOINT_MSEG_MAX_CAT];   /* as tpe_joint_mseg */
+  int32_t quant_v[TPE_JOINT_MAX_QUANT], quant_edge_off[TPE_JOINT_MAX_QUANT];
+  int32_t quant_tab_off[TPE_JOINT_MAX_QUANT];   /* start of dimension d in a liar's table and in quant_centre */
+  int32_t n_edges, n_lattice;              /* elements of quant_edges; sum_d V_d */
+  int64_t above_qmu, quant_edges;          /* element offsets in pool_f64, as tpe_joint_mseg */
+  int64_t cat_miss, cat_bonus;             /* element offsets in liar_pool [sum U_d] */
+  int64_t quant_centre;                    /* element offset in liar_pool [n_lattice] */
+  int64_t tab_off;                         /* doubles: the group's liar tables in scratch [chain_len * n_lattice] */
+} tpe_joint_liar_mseg_desc;
+typedef struct tpe_joint_liar_mseg_args {
+  int32_t n_segs, n_probs, n_cand, reserved;   /* as tpe_joint_liar_seg_args ... */
+  const tpe_joint_liar_mseg_desc* segs;        /* device [n_segs], group index order */
+  const tpe_joint_liar_mseg_desc* host_segs;   /* host   [n_segs], the same bytes */
+  const int32_t* order;
+  const int32_t* host_order;
+  const int32_t* chain;
+  const int32_t* host_chain;
+  const double* log_norm;
+  const double* host_log_norm;
+  const int32_t* host_prob_seg;
+  const float* cand;                     /* device, what tpe_joint_mseg_run wrote */
+  const int64_t* cand_off;
+  const double *l_out, *g_out;
+  const float* pool_f32;
+  int64_t pool_f32_len;                  /* ... up to here */
+  const double* pool_f64;                /* device, tpe_joint_mseg_args.pool_f64 (may be NULL without a quantised group) */
+  int64_t pool_f64_len;                  /* elements */
+  const double* liar_pool;               /* device f64 (may be NULL with continuous groups only) */
+  int64_t liar_pool_len;                 /* elements */
+} tpe_joint_liar_mseg_args;
+
+int tpe_joint_liar_mseg_scratch_bytes(const tpe_joint_liar_mseg_desc* host_segs, int32_t n_segs, int32_t n_cand,
+                                      uint64_t* bytes);
+
+/* picks: device [n_probs], by problem; pick_z: device f32 [n_probs *
+ * TPE_JOINT_MAX_DIMS], problem p's row at p * TPE_JOINT_MAX_DIMS (n_dims + n_cat
+ * + n_quant floats written); liar_sigma: device f64 [sum_s chain_len_s (n_dims +
+ * n_quant)_s], group s's [chain_len, n_dims + n_quant] rows at sigma_off;
+ * enqueued on `stream` */
+int tpe_joint_liar_mseg(const tpe_joint_liar_mseg_args* args, tpe_joint_pick* picks, float* pick_z,
+                        double* liar_sigma, void* scratch, uint64_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Host phase clock of tpe_suggest_tree (tools/native_split.py).  While
  * enabled, a call records the steady-clock microseconds since its entry at
  * each phase below (a tree of several level runs: the last run's phases);

@@ -1,7 +1,7 @@
 """Time the joint TPE stage against the host route.
 Usage: python tools/joint_time.py [--pairs 3] [--warmup 1] [--cand 1048576] [--history 10000]
                                   [--host-cand N] [--out FILE] [--mixed | --quant | --wide | --wide-mixed | --liar |
-                                   --liar-mixed | --liar-branches]
+                                   --liar-mixed | --liar-branches | --liar-branches-mixed]
 
 Workload: a flat space of 4 continuous labels (uniform, loguniform, normal,
 uniform), a seeded 10,000-trial history whose loss has an x0 * x1 term, one
@@ -104,7 +104,15 @@ synchronised device to the records on the host: (a) Engine.run_joint_segments
 group after another).  (b) and (c) must agree byte for byte.  The line carries
 the three medians and ranges, (b) - (a) per step of the longest chain, and the
 median nearest-pick distance inside a branch (prior sigmas) with and without the
-stage.  --out defaults to profiles/joint_liar_seg_time.jsonl."""
+stage.  --out defaults to profiles/joint_liar_seg_time.jsonl.
+
+--liar-branches-mixed: batch-aware picks in mixed branch groups.  The
+shape of --liar-branches on 4 groups of 2 continuous labels, one hp.choice of 3 and
+one hp.quniform of 32 values: (a) Engine.run_joint_segments, (b)
+Engine.run_joint_msegments_liar, (c) one Engine.run_joint_liar_mixed(liar=W_s) per
+group; (b) and (c) must agree byte for byte.  The nearest-pick distance is
+--liar-mixed's, inside a branch.  --out defaults to
+profiles/joint_liar_mseg_time.jsonl."""
 import argparse
 import ctypes
 import json
@@ -793,6 +801,111 @@ def main_liar_branches(args):
     return 0
 
 
+def make_branch_mixed_history(n, seed):
+    from hyperopt_amd import base, history as H, hp
+    space = {'x0': hp.uniform('x0', -5, 5), 'x1': hp.loguniform('x1', -3, 2), 'c2': hp.choice('c2', [0, 1, 2]),
+             'q3': hp.quniform('q3', 1, 32, 1)}
+    domain = base.Domain(lambda d: 0.0, space)
+    rs = np.random.RandomState(seed)
+    cols = {'x0': rs.uniform(-5, 5, n), 'x1': np.exp(rs.uniform(-3, 2, n)), 'c2': rs.randint(3, size=n),
+            'q3': np.rint(rs.uniform(1, 32, n))}
+    loss = (cols['x0'] * cols['x1'] - 2.0) ** 2 + 0.2 * (cols['c2'] != 1) + 1e-3 * (cols['q3'] - 12.0) ** 2 \
+        + 0.01 * rs.standard_normal(n)
+    tids = np.arange(n, dtype=np.int64)
+    return domain, H.History(tids, loss, {k: (tids, v) for k, v in cols.items()})
+
+
+def main_liar_branches_mixed(args):
+    import torch
+    from hyperopt_amd import history as H, joint as J
+    from hyperopt_amd.engine import get_engine
+    from hyperopt_amd.parzen import DEFAULT_LF
+
+    S = 4
+    models = []
+    for s in range(S):
+        domain, hist = make_branch_mixed_history(args.history // S, SEED + s)
+        rows = [r for r in domain.table.rows if J.eligible(r)]
+        drows = [r for r in domain.table.rows if J.eligible_discrete(r, domain.table)]
+        qrows = [r for r in domain.table.rows if J.eligible_quant(r, domain.table)]
+        models.append(J.fit_quant_model(rows, drows, qrows, hist, H.split_below(hist, 0.25), 1.0))
+    eng = get_engine(None, 'fp32')
+    C, B = args.cand, args.batch
+    Dc, Dk, Dq = len(rows), len(drows), len(qrows)
+    W = [J.side_weight_sum(len(m.above[0]) - 1, 1.0, DEFAULT_LF) for m in models]
+    words = [0x52000 + s for s in range(S)]
+    centres = [m.centres() for m in models]
+    prob_seg = (np.arange(B) % S).astype(np.int32)
+    prob_id = np.arange(args.history, args.history + B, dtype=np.int64)
+    chains = [np.flatnonzero(prob_seg == s) for s in range(S)]
+
+    def seg():
+        return eng.run_joint_segments(models, words, prob_seg, prob_id, C, SEED)
+
+    def seg_liar():
+        return eng.run_joint_msegments_liar(models, words, prob_seg, prob_id, C, SEED, liar=W, centres=centres)
+
+    def solo_liars():
+        return [eng.run_joint_liar_mixed(m.below[:3], m.above[:3], m.low, m.high, m.cats(), m.quants(), prob_id[ps], C,
+                                         SEED, liar=w, stream_word=word, centres=cs)
+                for m, w, word, cs, ps in zip(models, W, words, centres, chains)]
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, out
+
+    runs = (('seg', seg), ('seg_liar', seg_liar), ('solo_liars', solo_liars))
+    for _ in range(args.warmup):
+        for _, fn in runs:
+            fn()
+    wall, out = dict((k, []) for k, _ in runs), {}
+    for i in range(args.pairs):
+        for k, fn in runs:
+            w, out[k] = timed(fn)
+            wall[k].append(w)
+        print('round %d: %s' % (i, ', '.join('%s %.2f ms' % (k, wall[k][-1]) for k, _ in runs)), file=sys.stderr,
+              flush=True)
+    for ps, solo in zip(chains, out['solo_liars']):        # the defining property, on the timed runs
+        for f in ('global_idx', 'l', 'g', 'z'):
+            assert out['seg_liar'][f][ps].tobytes() == solo[f].tobytes(), f
+    med = lambda x: float(np.median(x))   # noqa: E731
+
+    def spread(rec):                                       # main_liar_mixed's distance, inside every branch
+        per = []
+        for m, cs, ps in zip(models, centres, chains):
+            r = rec['z'][ps]
+            z = r[:, :Dc] / np.asarray(m.above[2])[0][None, :]
+            q = np.stack([cs[d][r[:, Dc + Dk + d].astype(np.int64)] / m.above[5][0, d] for d in range(Dq)], axis=1)
+            z = np.hstack([z, q])
+            v = r[:, Dc:Dc + Dk]
+            d = np.sqrt(((z[:, None, :] - z[None, :, :]) ** 2).sum(axis=2) + (v[:, None, :] != v[None, :, :]).sum(axis=2))
+            np.fill_diagonal(d, np.inf)
+            per.append(float(np.median(d.min(axis=1))))
+        return float(np.median(per))
+    stat = lambda k: dict(wall_median=med(wall[k]), wall_min=min(wall[k]), wall_max=max(wall[k]))   # noqa: E731
+    longest = max(len(ps) for ps in chains)
+    extra = med(wall['seg_liar']) - med(wall['seg'])
+    line = dict(tool='joint_time --liar-branches-mixed', groups=S, n_dims=Dc, n_cat=Dk, n_quant=Dq,
+                lattice=[lat[1] for lat in models[0].lattices], history=args.history, n_cand=C, batch=B,
+                chain=longest, pairs=args.pairs, k_above=[len(m.above[0]) for m in models], w_sum=W,
+                launches=dict(seg_liar=2 * longest, solo_liars=2 * B),
+                seg_ms=stat('seg'), seg_liar_ms=stat('seg_liar'), solo_liars_ms=stat('solo_liars'),
+                seg_liar_minus_seg_ms=extra, per_round_ms=extra / longest, per_pick_ms=extra / B,
+                seg_liar_over_solo_liars=med(wall['seg_liar']) / med(wall['solo_liars']),
+                nearest_pick_median=dict(seg=spread(out['seg']), seg_liar=spread(out['seg_liar'])),
+                gpu=torch.cuda.get_device_name(0))
+    text = json.dumps(line)
+    print(text)
+    path = args.out or os.path.join(ROOT, 'profiles', 'joint_liar_mseg_time.jsonl')
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, 'a') as f:
+        f.write(text + '\n')
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--pairs', type=int, default=3)
@@ -807,6 +920,7 @@ def main():
     ap.add_argument('--liar', action='store_true')
     ap.add_argument('--liar-mixed', action='store_true')
     ap.add_argument('--liar-branches', action='store_true')
+    ap.add_argument('--liar-branches-mixed', action='store_true')
     ap.add_argument('--batch', type=int, default=64)
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
@@ -824,7 +938,9 @@ def main():
         return main_liar_mixed(args)
     if args.liar_branches:
         return main_liar_branches(args)
-    args.out = args.out or os.path.join(ROOT, 'profiles', 'joint_time.jsonl')
+    if args.liar_branches_mixed:
+        return main_liar_branches_mixed(args)
+    args.out =args.out or os.path.join(ROOT, 'profiles', 'joint_time.jsonl')
 
     import torch
     from hyperopt_amd import _native as N, history as H, joint as J
