@@ -197,6 +197,12 @@ class JointQuantArgs(ctypes.Structure):
     ]
 
 
+class JointWideQuantArgs(ctypes.Structure):
+    """tpe_joint_wide_quant_args: one tpe_joint_wide_quant_run (tpe_joint_wide_mixed_args' fields, then the
+    quantised labels' of tpe_joint_quant_args)."""
+    _fields_ = JointWideMixedArgs._fields_ + JointQuantArgs._fields_[len(JointMixedArgs._fields_):]
+
+
 class JointSeg(ctypes.Structure):
     """tpe_joint_seg: the device descriptor of one group of a tpe_joint_seg_run."""
     _fields_ = [
@@ -545,6 +551,7 @@ EXPORTS = ('tpe_abi_version', 'tpe_last_error', 'tpe_device_count', 'tpe_tile_si
            'tpe_joint_mixed_run', 'tpe_joint_quant_table_bytes', 'tpe_joint_quant_run', 'tpe_joint_quant_profile',
            'tpe_joint_wide_scratch_bytes', 'tpe_joint_wide_run', 'tpe_joint_wide_profile',
            'tpe_joint_wide_mixed_scratch_bytes', 'tpe_joint_wide_mixed_run',
+           'tpe_joint_wide_quant_scratch_bytes', 'tpe_joint_wide_quant_run', 'tpe_joint_wide_quant_profile',
            'tpe_joint_seg_scratch_bytes', 'tpe_joint_seg_run', 'tpe_joint_mseg_scratch_bytes',
            'tpe_joint_mseg_table_bytes', 'tpe_joint_mseg_run', 'tpe_joint_report_scratch_bytes',
            'tpe_joint_report', 'tpe_joint_report_profile', 'tpe_joint_run_shard', 'tpe_joint_liar_scratch_bytes',
@@ -687,6 +694,12 @@ def load(path=LIB_PATH):
     lib.tpe_joint_wide_mixed_scratch_bytes.restype = ctypes.c_int
     lib.tpe_joint_wide_mixed_run.argtypes = [ctypes.POINTER(JointWideMixedArgs), P, P, P, P, P, ctypes.c_uint64, P]
     lib.tpe_joint_wide_mixed_run.restype = ctypes.c_int
+    lib.tpe_joint_wide_quant_scratch_bytes.argtypes = [I32, I32, I32, I32, I32, ctypes.POINTER(ctypes.c_uint64)]
+    lib.tpe_joint_wide_quant_scratch_bytes.restype = ctypes.c_int
+    lib.tpe_joint_wide_quant_run.argtypes = [ctypes.POINTER(JointWideQuantArgs), P, P, P, P, P, ctypes.c_uint64, P]
+    lib.tpe_joint_wide_quant_run.restype = ctypes.c_int
+    lib.tpe_joint_wide_quant_profile.argtypes = [P]
+    lib.tpe_joint_wide_quant_profile.restype = ctypes.c_int
     lib.tpe_joint_seg_scratch_bytes.argtypes = [I32, I32, ctypes.POINTER(ctypes.c_uint64)]
     lib.tpe_joint_seg_scratch_bytes.restype = ctypes.c_int
     lib.tpe_joint_seg_run.argtypes = [ctypes.POINTER(JointSegArgs), P, P, P, P, P, ctypes.c_uint64, P]

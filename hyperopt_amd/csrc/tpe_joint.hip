@@ -37,6 +37,9 @@
 //                candidates are drawn by a kernel of their own into scratch.
 // k_joint_wide_mixed_sample / k_joint_wide_mixed_chunk  the wide stage for a
 //                group that also holds up to 8 discrete labels.
+// k_joint_wide_quant_sample / k_joint_wide_quant_chunk  the wide stage for a
+//                group that also holds up to 4 quantised labels: k_joint_qtable's
+//                tables stream through LDS beside the rows, in one common tile.
 // tpe_joint_run_shard  any of the six stages over the candidates [cand_base,
 //                cand_base + n_cand) of a larger run: the views carry cand_base (a
 //                kernel argument: scalar registers), added to the local index
@@ -1775,6 +1778,394 @@ __global__ __launch_bounds__(kThreads) void k_joint_wide_mixed_chunk(const WideM
   }
 }
 
+// ----------------------------------------- quantised labels in wide groups
+// Dc >= 1 continuous coordinates, Dk <= TPE_JOINT_WIDE_MAX_CAT discrete ones (0
+// allowed) and 1 <= Dq <= TPE_JOINT_MAX_QUANT quantised ones, Dc + Dk + Dq <=
+// TPE_JOINT_WIDE_MAX_DIMS (include/tpe_hip.h "Wide quantised joint stage"): the
+// model, the tables (k_joint_qtable) and the draws of the quantised stage, the
+// data movement of the wide mixed one.
+// k_joint_wide_quant_sample  k_joint_wide_mixed_sample, then the Dq lattice
+//                indices as k_joint_quant_chunk's sampler draws them (word 1 + j
+//                serves kernel coordinate j); a block of zbuf is
+//                [Dc + Dk + Dq][256].
+// k_joint_wide_quant_chunk<DP, KP, QP, R>  k_joint_wide_mixed_chunk with QP lattice
+//                slots a candidate.  The side's table streams through a dynamic
+//                LDS tile beside the rows, laid out [lattice value][component] as
+//                in k_joint_quant_chunk (stride tile + 4: 16 lanes with 16
+//                consecutive values read 16 different bank quads); rows and table
+//                share ONE tile length, the longest that keeps the table tile
+//                inside kWQTileBytes (and at most wide_tile(DP)).  Components are
+//                taken four at a time (one 16-byte table read per candidate and
+//                quantised slot); the tile's tail is padded with c = -3e38.
+// k_joint_wide_merge serves it unchanged.
+// rows (<= 32 KiB) + cats (<= 4 KiB) + c + the table tile stay under 64 KiB: no
+// launch attribute is needed, and two workgroups fit a CU's 160 KiB.
+constexpr int kWQTileBytes = 26 * 1024;
+
+// the common tile length of a group with `total` lattice values: a multiple of 8
+// components, at most tk; 8 at the least ((512 + 1) * 12 * 4 B = 24 KiB fits)
+__host__ __device__ __forceinline__ int wide_quant_tile(int total, int tk) {
+  int tile = 8;
+  for (int t = tk; t >= 8; t -= 8)
+    if ((int64_t)(total + 1) * (t + 4) * (int64_t)sizeof(float) <= kWQTileBytes) { tile = t; break; }
+  return tile;
+}
+static_assert((int64_t)(TPE_JOINT_MAX_LATTICE_TOTAL + 1) * 12 * sizeof(float) <= kWQTileBytes, "the shortest tile fits");
+
+struct WideQuantSampK {
+  WideMixedSampK m;                 // m.s.D = Dc, m.Dk = Dk; a block of zbuf is [Dc + Dk + Dq][256]
+  int Dq;
+  int V[TPE_JOINT_MAX_QUANT], eoff[TPE_JOINT_MAX_QUANT];
+  float qlo[TPE_JOINT_MAX_QUANT], qhi[TPE_JOINT_MAX_QUANT];
+  const double* edges;
+  const float* qsamp;
+};
+
+struct WideQuantK {
+  WideMixedK m;                     // m.w.D = Dc, m.Dk = Dk; zsrc / cand rows are [Dc + Dk + Dq]
+  int Dq, tile, stride, total;      // components per tile, floats per lattice value in the tile, sum V_d
+  int V[TPE_JOINT_MAX_QUANT], voff[TPE_JOINT_MAX_QUANT];
+  const float *bT, *aT;             // [total][K] of a side
+};
+
+__global__ __launch_bounds__(kThreads) void k_joint_wide_quant_sample(const WideQuantSampK p) {
+  __shared__ float blo[kWD], bhi[kWD];          // (kernel-argument arrays: constant indices only)
+  __shared__ int cU[kWK], coff[kWK];
+  __shared__ int qV[TPE_JOINT_MAX_QUANT], qeoff[TPE_JOINT_MAX_QUANT];
+  __shared__ float qlo[TPE_JOINT_MAX_QUANT], qhi[TPE_JOINT_MAX_QUANT];
+  const WideSampK& s = p.m.s;
+  const int t = threadIdx.x, Dc = s.D, Dk = p.m.Dk, Dq = p.Dq, D = Dc + Dk + Dq;
+  if (t == 0) {
+#pragma unroll
+    for (int f = 0; f < kWD; ++f) { blo[f] = s.lo[f]; bhi[f] = s.hi[f]; }
+#pragma unroll
+    for (int f = 0; f < kWK; ++f) { cU[f] = p.m.U[f]; coff[f] = p.m.off[f]; }
+#pragma unroll
+    for (int f = 0; f < TPE_JOINT_MAX_QUANT; ++f) {
+      qV[f] = p.V[f]; qeoff[f] = p.eoff[f];
+      qlo[f] = p.qlo[f]; qhi[f] = p.qhi[f];
+    }
+  }
+  __syncthreads();
+  const int id = blockIdx.x / s.nblk, blk = blockIdx.x % s.nblk;
+  const int i = blk * kThreads + t;
+  if (i >= s.C) return;
+  float* out = s.zbuf + (int64_t)blockIdx.x * kThreads * D + t;
+  const uint32_t c3 = (uint32_t)s.ids[id], gi = s.cand_base + (uint32_t)i;   // gi < 2^31 (i < C)
+  U4 w = philox4x32_10(gi, 0u, s.stream_word, c3, s.key0, s.key1);
+  const double us = u01w(w.x);
+  int lo = 0, hi = s.kb - 1;               // first k with us < cum[k]
+  while (lo < hi) { const int mid = (lo + hi) >> 1; if (us < s.cum[mid]) hi = mid; else lo = mid + 1; }
+  const int comp = lo;
+  const float* srow = s.samp + (int64_t)comp * Dc * 5;
+  // word 1 + j serves kernel coordinate j; a continuous one is k_joint_wide_sample's draw
+#pragma unroll 1
+  for (int d = 0; d < Dc; ++d) {
+    const int wi = d + 1;
+    if ((wi & 3) == 0) w = philox4x32_10(gi, (uint32_t)(wi >> 2), s.stream_word, c3, s.key0, s.key1);
+    const uint32_t word = (wi & 3) == 0 ? w.x : (wi & 3) == 1 ? w.y : (wi & 3) == 2 ? w.z : w.w;
+    const float* sr = srow + d * 5;
+    const float pr = sr[2] + u01f(word) * (sr[3] - sr[2]);
+    float zz = ndtri_f32(pr);
+    if (sr[4] != 0.f) zz = -zz;
+    float x = sr[0] + sr[1] * zz;
+    if (!(x == x)) x = sr[0];
+    out[(int64_t)d * kThreads] = fminf(fmaxf(x, blo[d]), bhi[d]);      // low <= z < high
+  }
+  // ... a discrete one k_joint_wide_mixed_sample's: the category index as an f32
+#pragma unroll 1
+  for (int d = 0; d < Dk; ++d) {
+    const int wi = Dc + d + 1;
+    if ((wi & 3) == 0) w = philox4x32_10(gi, (uint32_t)(wi >> 2), s.stream_word, c3, s.key0, s.key1);
+    const uint32_t word = (wi & 3) == 0 ? w.x : (wi & 3) == 1 ? w.y : (wi & 3) == 2 ? w.z : w.w;
+    const double u = u01w(word);
+    float x = p.m.bcat[(int64_t)comp * Dk + d];           // the component's category, -1: the prior row
+    const double h = x >= 0.f ? p.m.bh[d] : 0.0;
+    if (!(u < h)) {
+      const double u2 = (u - h) / (1.0 - h);
+      const double* cum = p.m.ccum + coff[d];
+      int a = 0, b = cU[d] - 1;                           // first category with u2 < cum[v]
+      while (a < b) { const int mid = (a + b) >> 1; if (u2 < cum[mid]) b = mid; else a = mid + 1; }
+      x = (float)a;
+    }
+    out[(int64_t)(Dc + d) * kThreads] = x;
+  }
+  // ... a quantised one k_joint_quant_chunk's: the continuous draw through the
+  // dimension's sampler row, binned; the lattice index as an f32
+#pragma unroll 1
+  for (int d = 0; d < Dq; ++d) {
+    const int wi = Dc + Dk + d + 1;
+    if ((wi & 3) == 0) w = philox4x32_10(gi, (uint32_t)(wi >> 2), s.stream_word, c3, s.key0, s.key1);
+    const uint32_t word = (wi & 3) == 0 ? w.x : (wi & 3) == 1 ? w.y : (wi & 3) == 2 ? w.z : w.w;
+    const float* sr = p.qsamp + ((int64_t)comp * Dq + d) * 5;
+    const float pr = sr[2] + u01f(word) * (sr[3] - sr[2]);
+    float zz = ndtri_f32(pr);
+    if (sr[4] != 0.f) zz = -zz;
+    float x = sr[0] + sr[1] * zz;
+    if (!(x == x)) x = sr[0];
+    x = fminf(fmaxf(x, qlo[d]), qhi[d]);                  // low <= z < high
+    const double* e = p.edges + qeoff[d] + 1;             // the interior edges e_1 .. e_{V-1}
+    const double zd = (double)x;
+    int a = 0, b = qV[d] - 1;                             // how many of them are <= z
+    while (a < b) { const int mid = (a + b) >> 1; if (e[mid] <= zd) a = mid + 1; else b = mid; }
+    out[(int64_t)(Dc + Dk + d) * kThreads] = (float)a;
+  }
+}
+
+// score_side_wide_mixed with QP quantised slots (score_side_quant's table part);
+// KP = 0: no discrete slot.  qo: a candidate's table row offsets in floats.
+template <int DP, int KP, int QP, int R>
+__device__ __forceinline__ void score_side_wide_quant(const float* __restrict__ mu, const float* __restrict__ a,
+                                                      const float* __restrict__ c, const float* __restrict__ cat,
+                                                      const float* __restrict__ miss, const float* __restrict__ bonus,
+                                                      const float* __restrict__ T, int K, int Dc, int Dk, int tile,
+                                                      int stride, int total, const int (&U)[KP > 0 ? KP : 1],
+                                                      const int (&off)[KP > 0 ? KP : 1], const float (&z)[R][DP],
+                                                      const float (&v)[R][KP > 0 ? KP : 1], const int (&qo)[R][QP],
+                                                      float* __restrict__ rows, float* __restrict__ cats,
+                                                      float* __restrict__ cl, float* __restrict__ qt,
+                                                      double (&out)[R]) {
+  constexpr int KPa = KP > 0 ? KP : 1;
+  float m[R], s[R], nb[R][KPa];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    m[r] = -3.0e38f;
+    s[r] = 0.f;
+#pragma unroll
+    for (int d = 0; d < KP; ++d) nb[r][d] = d < Dk ? -bonus[off[d] + cat_index(v[r][d], U[d])] : 0.f;
+  }
+  for (int k0 = 0; k0 < K; k0 += tile) {
+    const int nk = min(tile, K - k0), nk4 = (nk + 3) & ~3;
+    __syncthreads();                       // the previous tile (or side) is read
+    for (int e = threadIdx.x; e < nk4 * DP; e += kThreads) {
+      const int kk = e / DP, d = e % DP;
+      const bool in = d < Dc && kk < nk;   // padded dimensions and components: a = 0 adds nothing
+      const int64_t src = (int64_t)(k0 + kk) * Dc + d;
+      rows[kk * 2 * DP + d] = in ? mu[src] : 0.f;
+      rows[kk * 2 * DP + DP + d] = in ? a[src] : 0.f;
+    }
+    if constexpr (KP > 0)
+      for (int e = threadIdx.x; e < nk4 * KP; e += kThreads) {
+        const int kk = e / KP, d = e % KP;   // padded slots: category -1 never matches
+        cats[e] = (d < Dk && kk < nk) ? cat[(int64_t)(k0 + kk) * Dk + d] : -1.f;
+      }
+    for (int e = threadIdx.x; e < nk4; e += kThreads) cl[e] = e < nk ? c[k0 + e] : -3.0e38f;
+    for (int e = threadIdx.x; e < total * tile; e += kThreads) {
+      const int b = e / tile, kk = e - b * tile;           // a run over k of one lattice value: coalesced
+      if (kk < nk4) qt[b * stride + kk] = kk < nk ? T[(int64_t)b * K + k0 + kk] : 0.f;
+    }
+    __syncthreads();
+    for (int k4 = 0; k4 < nk4; k4 += 4) {
+      float tq[R][QP][4];
+#pragma unroll
+      for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int d = 0; d < QP; ++d) {
+          const float4 x = *reinterpret_cast<const float4*>(qt + qo[r][d] + k4);
+          tq[r][d][0] = x.x; tq[r][d][1] = x.y; tq[r][d][2] = x.z; tq[r][d][3] = x.w;
+        }
+      // (R = 1, the widths above 32: the four components are a loop, not four copies,
+      // which would hold their 4 x 2 DP row values at once and leave one wave a SIMD)
+#pragma unroll(R == 1 ? 1 : 4)
+      for (int j = 0; j < 4; ++j) {
+        const int kk = k4 + j;
+        const float4* row = reinterpret_cast<const float4*>(rows + kk * 2 * DP);
+        float acc[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc[r] = 0.f;
+#pragma unroll
+        for (int q = 0; q < DP / 4; ++q) {
+          const float4 rm = row[q], ra = row[DP / 4 + q];
+#pragma unroll
+          for (int r = 0; r < R; ++r) {
+            float u = (z[r][4 * q] - rm.x) * ra.x;
+            acc[r] = __builtin_fmaf(u, u, acc[r]);
+            u = (z[r][4 * q + 1] - rm.y) * ra.y;
+            acc[r] = __builtin_fmaf(u, u, acc[r]);
+            u = (z[r][4 * q + 2] - rm.z) * ra.z;
+            acc[r] = __builtin_fmaf(u, u, acc[r]);
+            u = (z[r][4 * q + 3] - rm.w) * ra.w;
+            acc[r] = __builtin_fmaf(u, u, acc[r]);
+          }
+        }
+        float rc[KPa];
+        if constexpr (KP > 0 && KP % 4 == 0) {
+          const float4* cr = reinterpret_cast<const float4*>(cats + kk * KP);
+#pragma unroll
+          for (int q = 0; q < KP / 4; ++q) {
+            const float4 x = cr[q];
+            rc[4 * q] = x.x; rc[4 * q + 1] = x.y; rc[4 * q + 2] = x.z; rc[4 * q + 3] = x.w;
+          }
+        } else if constexpr (KP == 2) {
+          const float2 x = *reinterpret_cast<const float2*>(cats + kk * 2);
+          rc[0] = x.x; rc[1] = x.y;
+        } else if constexpr (KP == 1) {
+          rc[0] = cats[kk];
+        }
+        const float ck = cl[kk];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+#pragma unroll
+          for (int d = 0; d < KP; ++d) acc[r] += v[r][d] == rc[d] ? nb[r][d] : 0.f;
+#pragma unroll
+          for (int d = 0; d < QP; ++d)   // (selects, not an indexed read: tq stays in registers in the looped form)
+            acc[r] -= j == 0 ? tq[r][d][0] : j == 1 ? tq[r][d][1] : j == 2 ? tq[r][d][2] : tq[r][d][3];
+          const float t = ck - acc[r];
+          const float dl = t - m[r];
+          const float e2 = __builtin_amdgcn_exp2f(-__builtin_fabsf(dl));
+          s[r] = dl > 0.f ? __builtin_fmaf(s[r], e2, 1.f) : s[r] + e2;
+          m[r] = fmaxf(m[r], t);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    double M = 0.0;
+#pragma unroll
+    for (int d = 0; d < KP; ++d)
+      if (d < Dk) M += (double)miss[off[d] + cat_index(v[r][d], U[d])];
+    out[r] = (double)m[r] + log2((double)s[r]) + M;
+  }
+}
+
+template <int DP, int KP, int QP, int R>
+__global__ __launch_bounds__(kThreads) void k_joint_wide_quant_chunk(const WideQuantK p) {
+  static_assert(DP % 4 == 0 && DP <= kWD && KP <= kWK && QP <= TPE_JOINT_MAX_QUANT,
+                "rows are read as float4; the argument arrays");
+  constexpr int TK = wide_tile(DP), KPa = KP > 0 ? KP : 1;
+  __shared__ __attribute__((aligned(16))) float rows[TK * 2 * DP];
+  __shared__ __attribute__((aligned(16))) float cats[TK * KPa];
+  __shared__ float cl[TK];
+  __shared__ Pick slot[kThreads / 64];
+  extern __shared__ __attribute__((aligned(16))) float qt[];     // [(total + 1) * stride]
+  static_assert(sizeof(float) * (TK * 2 * DP + TK * KPa + TK) + sizeof(Pick) * (kThreads / 64) + kWQTileBytes <=
+                    64 * 1024, "static and dynamic LDS of a workgroup stay under 64 KiB");
+  const WideK& w0 = p.m.w;
+  const int t = threadIdx.x, Dc = w0.D, Dk = p.m.Dk, Dq = p.Dq, D = Dc + Dk + Dq;
+  const int id = blockIdx.x / w0.n_chunks, chunk = blockIdx.x % w0.n_chunks;
+  const int first = chunk * (R * kThreads);
+  int U[KPa], off[KPa];                    // (kernel-argument arrays: constant indices only)
+  U[0] = 1; off[0] = 0;
+#pragma unroll
+  for (int d = 0; d < KP; ++d) { U[d] = p.m.U[d]; off[d] = p.m.off[d]; }
+
+  for (int e = t; e < p.stride; e += kThreads) qt[p.total * p.stride + e] = 0.f;   // the padded slots' row
+
+  float z[R][DP], v[R][KPa], x[R][QP];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+#pragma unroll
+    for (int d = 0; d < DP; ++d) z[r][d] = 0.f;
+#pragma unroll
+    for (int d = 0; d < KPa; ++d) v[r][d] = 0.f;
+#pragma unroll
+    for (int d = 0; d < QP; ++d) x[r][d] = 0.f;
+    const int i = first + r * kThreads + t;
+    if (i >= w0.C) continue;
+    if (w0.inject) {
+      const float* src = w0.zsrc + (int64_t)i * D;
+#pragma unroll
+      for (int d = 0; d < DP; ++d)
+        if (d < Dc) z[r][d] = src[d];
+#pragma unroll
+      for (int d = 0; d < KP; ++d)
+        if (d < Dk) v[r][d] = src[Dc + d];
+#pragma unroll
+      for (int d = 0; d < QP; ++d)
+        if (d < Dq) x[r][d] = src[Dc + Dk + d];
+    } else {
+      // block chunk * R + r of this id (i < C: the block exists)
+      const float* src = w0.zsrc + ((int64_t)id * w0.nblk + chunk * R + r) * kThreads * D + t;
+#pragma unroll
+      for (int d = 0; d < DP; ++d)
+        if (d < Dc) z[r][d] = src[(int64_t)d * kThreads];
+#pragma unroll
+      for (int d = 0; d < KP; ++d)
+        if (d < Dk) v[r][d] = src[(int64_t)(Dc + d) * kThreads];
+#pragma unroll
+      for (int d = 0; d < QP; ++d)
+        if (d < Dq) x[r][d] = src[(int64_t)(Dc + Dk + d) * kThreads];
+    }
+  }
+
+  // the lattice value's row in the tile (kept inside the table); a padded slot reads the zero row
+  int qo[R][QP];
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+#pragma unroll
+    for (int d = 0; d < QP; ++d)
+      qo[r][d] = (d < Dq ? p.voff[d] + cat_index(x[r][d], p.V[d]) : p.total) * p.stride;
+
+  double l2[R], g2[R];
+  score_side_wide_quant<DP, KP, QP, R>(w0.bmu, w0.ba, w0.bc, p.m.bcat, p.m.bmiss, p.m.bbonus, p.bT, w0.kb, Dc, Dk,
+                                       p.tile, p.stride, p.total, U, off, z, v, qo, rows, cats, cl, qt, l2);
+  score_side_wide_quant<DP, KP, QP, R>(w0.amu, w0.aa, w0.ac, p.m.acat, p.m.amiss, p.m.abonus, p.aT, w0.ka, Dc, Dk,
+                                       p.tile, p.stride, p.total, U, off, z, v, qo, rows, cats, cl, qt, g2);
+
+  Pick best{0, 0};
+  double lv[R], gv[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int i = first + r * kThreads + t;
+    lv[r] = l2[r] * kLn2 + w0.bbase;
+    gv[r] = g2[r] * kLn2 + w0.abase;
+    if (i >= w0.C) continue;
+    const int64_t o = (int64_t)id * w0.C + i;
+    if (w0.l_out) w0.l_out[o] = lv[r];
+    if (w0.g_out) w0.g_out[o] = gv[r];
+    if (w0.cand) {
+#pragma unroll
+      for (int d = 0; d < DP; ++d)
+        if (d < Dc) w0.cand[o * D + d] = z[r][d];
+#pragma unroll
+      for (int d = 0; d < KP; ++d)
+        if (d < Dk) w0.cand[o * D + Dc + d] = v[r][d];
+#pragma unroll
+      for (int d = 0; d < QP; ++d)
+        if (d < Dq) w0.cand[o * D + Dc + Dk + d] = x[r][d];
+    }
+    const uint64_t key = score_key(lv[r] - gv[r]);
+    if (key > best.key) best = Pick{key, (int64_t)i};   // ascending index: strict > keeps the first of a tie
+  }
+  Pick w = wave_best(best);
+  if ((t & 63) == 0) slot[t >> 6] = w;
+  __syncthreads();
+  w = slot[0];
+#pragma unroll
+  for (int q = 1; q < kThreads / 64; ++q)
+    if (beats(slot[q], w)) w = slot[q];
+
+  tpe_joint_wide_record* rec = w0.chunk_rec + blockIdx.x;
+  if (w.key == 0) {
+    if (t == 0) rec->global_idx = -1;
+    return;
+  }
+  const int woff = (int)(w.idx - first);
+  if (t != woff % kThreads) return;
+  const int wr = woff / kThreads;
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    if (r != wr) continue;
+    rec->global_idx = w.idx + (int64_t)w0.cand_base;
+    rec->l = lv[r];
+    rec->g = gv[r];
+    // kernel coordinate order: continuous, categories, lattice indices, then zeros
+#pragma unroll
+    for (int d = 0; d < kWD; ++d)
+      if (d >= D) rec->z[d] = 0.0;
+#pragma unroll
+    for (int d = 0; d < DP; ++d)
+      if (d < Dc) rec->z[d] = (double)z[r][d];
+#pragma unroll
+    for (int d = 0; d < KP; ++d)
+      if (d < Dk) rec->z[Dc + d] = (double)v[r][d];
+#pragma unroll
+    for (int d = 0; d < QP; ++d)
+      if (d < Dq) rec->z[Dc + Dk + d] = (double)x[r][d];
+  }
+}
+
 // ------------------------------------------------------------- host driver
 // Everything from here on runs on the host: the stages' argument checks,
 // the kernel-argument fills and the launches.  What the stages share exists
@@ -2248,6 +2639,135 @@ int joint_wide_mixed_run_at(const tpe_joint_wide_mixed_args* a, tpe_joint_wide_r
   return finish(k_joint_wide_merge, (const tpe_joint_wide_record*)scratch, (int)n_chunks, records, a->n_ids, s, timed, 1);
 }
 
+// ... and a wide quantised group without a quantised label a tpe_joint_wide_mixed_args
+static_assert(offsetof(tpe_joint_wide_quant_args, n_quant) == sizeof(tpe_joint_wide_mixed_args) &&
+                  offsetof(tpe_joint_wide_quant_args, n_cat) == offsetof(tpe_joint_wide_mixed_args, n_cat) &&
+                  offsetof(tpe_joint_wide_quant_args, cat_cum) == offsetof(tpe_joint_wide_mixed_args, cat_cum),
+              "tpe_joint_wide_quant_args starts with tpe_joint_wide_mixed_args");
+
+// padded widths of a wide group with quantised labels: DP in {16, 24, 32, 48, 64}
+// (of for_wide_mixed_dp's set), KP in {0, 2, 8}, QP in {1, 2, 4}: 45 instantiations
+template <typename F>
+void for_wide_quant_dp(int Dc, F&& f) { pad_to<16, 24, 32, 48, 64>(Dc, f); }
+template <typename F>
+void for_wide_quant_kp(int Dk, F&& f) { pad_to<0, 2, 8>(Dk, f); }
+int wide_quant_dp(int Dc) {
+  int dp = 0;
+  for_wide_quant_dp(Dc, [&](auto p) { dp = decltype(p)::value; });
+  return dp;
+}
+static_assert(wide_r(16) == wide_r(20) && wide_r(24) == wide_r(20), "wide_chunks_of serves these widths");
+// the scratch of a wide quantised run: the chunk records (their count follows the
+// continuous width), then the candidate block over all Dc + Dk + Dq coordinates
+uint64_t wide_quant_scratch_need(int32_t n_ids, int32_t n_cand, int Dc, int Dk, int Dq) {
+  return wide_scratch_need(n_ids, n_cand, Dc, Dk + Dq);
+}
+// ... and its limits on the counts alone (tpe_joint_wide_quant_scratch_bytes, the run)
+bool wide_quant_counts_ok(int Dc, int Dk, int Dq) {
+  return Dc >= 1 && Dk >= 0 && Dk <= TPE_JOINT_WIDE_MAX_CAT && Dq >= 1 && Dq <= TPE_JOINT_MAX_QUANT &&
+         Dc <= TPE_JOINT_WIDE_MAX_DIMS && Dc + Dk + Dq <= TPE_JOINT_WIDE_MAX_DIMS;
+}
+
+// (cand_base: as the wide mixed stage; tpe_joint_run_shard does not take this stage)
+int joint_wide_quant_run_at(const tpe_joint_wide_quant_args* a, tpe_joint_wide_record* records, float* cand,
+                            double* l_out, double* g_out, void* scratch, uint64_t scratch_bytes, void* stream,
+                            uint32_t cand_base) {
+  constexpr const char* E = "tpe_joint_wide_quant_run";
+  tpe_internal_epoch_bump();
+  if (!a) return fail(E, "null args");
+  if (a->n_quant < 1 || a->n_quant > TPE_JOINT_MAX_QUANT) return fail(E, "n_quant outside [1, TPE_JOINT_MAX_QUANT]");
+  if (a->n_cat < 0 || a->n_cat > TPE_JOINT_WIDE_MAX_CAT) return fail(E, "n_cat outside [0, TPE_JOINT_WIDE_MAX_CAT]");
+  if (!wide_quant_counts_ok(a->n_dims, a->n_cat, a->n_quant))
+    return fail(E, "n_dims < 1 or n_dims + n_cat + n_quant outside [2, TPE_JOINT_WIDE_MAX_DIMS]");
+  const int Dc = a->n_dims, Dk = a->n_cat, Dq = a->n_quant;
+  if (int rc = check_solo_head(E, a, records, Dc)) return rc;
+  if (Dk > 0) {
+    if (cat_tables_null(a)) return fail(E, "null category tables");
+    if (check_cats(E, "", a->cat_upper, a->cat_off, Dk) < 0) return TPE_E_ARG;
+  }
+  const int64_t total = check_lattice(E, "", a->quant_v, a->quant_edge_off, Dq, a->n_edges);
+  if (total < 0) return TPE_E_ARG;
+  if (!a->quant_edges || !a->below_qmu || !a->below_qsigma || !a->above_qmu || !a->above_qsigma || !a->quant_samp ||
+      !a->quant_table)
+    return fail(E, "null quantised rows or table");
+  if (a->quant_table_bytes < quant_table_floats(a->k_below, a->k_above, total) * sizeof(float))
+    return fail(E, "table workspace too small");
+  const bool inject = (a->flags & TPE_JOINT_INJECT) != 0;
+  const int64_t n_chunks = wide_chunks_of(a->n_cand, Dc), blocks = n_chunks * a->n_ids;
+  const int64_t nblk = wide_blocks_of(a->n_cand), sblocks = nblk * a->n_ids;
+  if (int rc = check_scratch(E, sblocks, wide_quant_scratch_need(a->n_ids, a->n_cand, Dc, Dk, Dq), scratch,
+                             scratch_bytes))
+    return rc;
+
+  const bool timed = g_prof.on != 0;
+  hipStream_t s = (hipStream_t)stream;
+  float* zbuf = (float*)((char*)scratch + wide_record_bytes(a->n_ids, a->n_cand, Dc));
+  int U[TPE_JOINT_WIDE_MAX_CAT], off[TPE_JOINT_WIDE_MAX_CAT];
+  for (int d = 0; d < TPE_JOINT_WIDE_MAX_CAT; ++d) {
+    U[d] = d < Dk ? a->cat_upper[d] : 1;
+    off[d] = d < Dk ? a->cat_off[d] : 0;
+  }
+
+  // the two sides' tables: tpe_joint_quant_run's launches
+  WideQuantSampK sk;
+  WideQuantK k;
+  QTabK tb, ta;
+  int voff = 0;
+  for (int d = 0; d < TPE_JOINT_MAX_QUANT; ++d) {
+    const bool in = d < Dq;
+    k.V[d] = sk.V[d] = tb.V[d] = in ? a->quant_v[d] : 2;
+    k.voff[d] = tb.voff[d] = in ? voff : 0;
+    sk.eoff[d] = tb.eoff[d] = in ? a->quant_edge_off[d] : 0;
+    sk.qlo[d] = -INFINITY; sk.qhi[d] = INFINITY;
+    if (in) {                                // a quantised dimension's bounds (its outer edges): low / high [Dc + d]
+      f32_bounds(a->low[Dc + d], a->high[Dc + d], sk.qlo[d], sk.qhi[d]);
+      voff += a->quant_v[d];
+    }
+  }
+  if (timed)
+    if (int rc = ensure_events(g_qprof.ev, 2)) return rc;
+  tb.K = a->k_below; tb.Dq = Dq; tb.mu = a->below_qmu; tb.sigma = a->below_qsigma; tb.edges = a->quant_edges;
+  tb.T = a->quant_table;
+  ta = tb;
+  ta.K = a->k_above; ta.mu = a->above_qmu; ta.sigma = a->above_qsigma; ta.T = a->quant_table + total * a->k_below;
+  const dim3 gb((unsigned)((a->k_below + kThreads - 1) / kThreads), (unsigned)Dq);
+  const dim3 ga((unsigned)((a->k_above + kThreads - 1) / kThreads), (unsigned)Dq);
+  launch(k_joint_qtable, gb, kThreads, 0u, s, timed ? g_qprof.ev[0] : nullptr, nullptr, tb);
+  launch(k_joint_qtable, ga, kThreads, 0u, s, nullptr, timed ? g_qprof.ev[1] : nullptr, ta);
+  if (timed) g_qprof.valid = 1;
+
+  g_wprof.valid = 0;
+  if (!inject) {
+    fill_wide_samp(sk.m.s, a, Dc, nblk, cand_base, zbuf);
+    sk.m.Dk = Dk;
+    memcpy(sk.m.U, U, sizeof U); memcpy(sk.m.off, off, sizeof off);
+    sk.m.bcat = a->below_cat; sk.m.bh = a->below_h; sk.m.ccum = a->cat_cum;
+    sk.Dq = Dq; sk.edges = a->quant_edges; sk.qsamp = a->quant_samp;
+    if (int rc = launch_wide_samp(k_joint_wide_quant_sample, sblocks, s, timed, sk)) return rc;
+  }
+
+  fill_wide(k.m.w, a, Dc, n_chunks, nblk, cand_base, zbuf, cand, l_out, g_out, scratch);
+  k.m.Dk = Dk;
+  memcpy(k.m.U, U, sizeof U); memcpy(k.m.off, off, sizeof off);
+  k.m.bcat = a->below_cat; k.m.acat = a->above_cat;
+  k.m.bmiss = a->below_miss; k.m.bbonus = a->below_bonus; k.m.amiss = a->above_miss; k.m.abonus = a->above_bonus;
+  k.Dq = Dq; k.total = (int)total;
+  k.tile = wide_quant_tile((int)total, wide_tile(wide_quant_dp(Dc))); k.stride = k.tile + 4;
+  k.bT = a->quant_table; k.aT = a->quant_table + total * a->k_below;
+  const unsigned lds = (unsigned)((total + 1) * k.stride * sizeof(float));
+  const Ev ev = chunk_marks(timed);
+  for_wide_quant_dp(Dc, [&](auto dp) {
+    constexpr int DP = decltype(dp)::value;
+    for_wide_quant_kp(Dk, [&](auto kp) {
+      for_qp(Dq, [&](auto qp) {
+        launch(k_joint_wide_quant_chunk<DP, decltype(kp)::value, decltype(qp)::value, wide_r(DP)>,
+               dim3((unsigned)blocks), kThreads, lds, s, ev.start, ev.stop, k);
+      });
+    });
+  });
+  return finish(k_joint_wide_merge, (const tpe_joint_wide_record*)scratch, (int)n_chunks, records, a->n_ids, s, timed, 1);
+}
+
 int joint_mixed_run_at(const tpe_joint_mixed_args* a, tpe_joint_record* records, float* cand, double* l_out,
                        double* g_out, void* scratch, uint64_t scratch_bytes, void* stream, uint32_t cand_base) {
   constexpr const char* E = "tpe_joint_mixed_run";
@@ -2623,6 +3143,13 @@ int tpe_joint_wide_mixed_scratch_bytes(int32_t n_ids, int32_t n_cand, int32_t n_
                   bytes);
 }
 
+int tpe_joint_wide_quant_scratch_bytes(int32_t n_ids, int32_t n_cand, int32_t n_dims, int32_t n_cat, int32_t n_quant,
+                                       uint64_t* bytes) {
+  const bool ok = n_ids >= 1 && n_cand >= 1 && wide_quant_counts_ok(n_dims, n_cat, n_quant);
+  return size_out("tpe_joint_wide_quant_scratch_bytes", ok,
+                  ok ? wide_quant_scratch_need(n_ids, n_cand, n_dims, n_cat, n_quant) : 0, bytes);
+}
+
 int tpe_joint_quant_table_bytes(int32_t k_below, int32_t k_above, int32_t total_bins, uint64_t* bytes) {
   const bool ok = k_below >= 1 && k_above >= 1 && total_bins >= 1;
   return size_out("tpe_joint_quant_table_bytes", ok, quant_table_floats(k_below, k_above, total_bins) * sizeof(float),
@@ -2668,6 +3195,17 @@ int tpe_joint_wide_run(const tpe_joint_wide_args* a, tpe_joint_wide_record* reco
 int tpe_joint_wide_mixed_run(const tpe_joint_wide_mixed_args* a, tpe_joint_wide_record* records, float* cand,
                              double* l_out, double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
   return joint_wide_mixed_run_at(a, records, cand, l_out, g_out, scratch, scratch_bytes, stream, 0u);
+}
+
+int tpe_joint_wide_quant_run(const tpe_joint_wide_quant_args* a, tpe_joint_wide_record* records, float* cand,
+                             double* l_out, double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
+  return joint_wide_quant_run_at(a, records, cand, l_out, g_out, scratch, scratch_bytes, stream, 0u);
+}
+
+int tpe_joint_wide_quant_profile(double* sample_ms) {
+  if (!sample_ms || !g_wprof.valid)
+    return fail("tpe_joint_wide_quant_profile", "no profiled sampling tpe_joint_wide_quant_run to read");
+  return elapsed_ms(g_wprof.ev[0], g_wprof.ev[1], sample_ms);
 }
 
 int tpe_joint_mixed_run(const tpe_joint_mixed_args* a, tpe_joint_record* records, float* cand, double* l_out,

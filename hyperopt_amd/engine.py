@@ -1067,11 +1067,12 @@ class Engine(object):
     _JOINT_SOLO = {'run': (N.JointArgs, 'tpe_joint_run'), 'wide': (N.JointWideArgs, 'tpe_joint_wide_run'),
                    'mixed': (N.JointMixedArgs, 'tpe_joint_mixed_run'),
                    'wide_mixed': (N.JointWideMixedArgs, 'tpe_joint_wide_mixed_run'),
-                   'quant': (N.JointQuantArgs, 'tpe_joint_quant_run')}
+                   'quant': (N.JointQuantArgs, 'tpe_joint_quant_run'),
+                   'wide_quant': (N.JointWideQuantArgs, 'tpe_joint_wide_quant_run')}
 
     def _joint_solo(self, entry, below, above, low, high, cats, quants, ids, n_cand, seed, inject, return_cand,
                     want_lg, report_k, stream_word, shard, return_table=False, liar=None):
-        """What the five solo stages share: the group's rows (joint_pack.group_rows,
+        """What the six solo stages share: the group's rows (joint_pack.group_rows,
         which also checks the group; an empty part of a sharded stage is checked
         too), one upload per row, the args struct filled from the same rows
         record, the call and its results.  The library derives the f32 bounds
@@ -1079,7 +1080,7 @@ class Engine(object):
         lattice ends follow the continuous bounds there."""
         r = JP.group_rows(below, above, low, high, cats, quants, entry=entry)
         Dc, Dk, Dq = r['Dc'], r['Dk'], r['Dq']
-        D, wide = Dc + Dk + Dq, entry in ('wide', 'wide_mixed')
+        D, wide = Dc + Dk + Dq, entry in ('wide', 'wide_mixed', 'wide_quant')
         ids, n_ids, C = self._joint_sizes(D, ids, n_cand, shard)
         shard = self._joint_shard(shard, C, report_k, inject)
         if liar is not None:
@@ -1123,7 +1124,7 @@ class Engine(object):
             d_tab = self._buf('joint_qtable', (nb.value + 3) // 4, torch.float32)
             a.quant_table, a.quant_table_bytes = d_tab.data_ptr(), d_tab.numel() * 4
         out = self._joint_call(fn, a, n_ids, C, D, return_cand, want_lg, wide=wide, report_k=report_k, shard=shard,
-                               n_cat=Dk if wide else 0, liar=liar)
+                               n_cat=Dk if wide else 0, liar=liar, n_quant=Dq if wide else 0)
         if not return_table:
             return out
         tab = d_tab[:(a.k_below + a.k_above) * total].cpu().numpy()
@@ -1292,11 +1293,12 @@ class Engine(object):
         return t.data_ptr()
 
     def _joint_call(self, fn, a, n_ids, C, D, return_cand, want_lg, wide=False, report_k=0, shard=None, n_cat=0,
-                    liar=None):
+                    liar=None, n_quant=0):
         """Scratch and result buffers, the native call ``fn`` and the records
         (and candidates [n_ids, C, D], l, g [n_ids, C]) on the host.  ``wide``:
         the wide stage's scratch size and record (``n_cat`` > 0: the wide mixed
-        stage's, ``n_cat`` of the D coordinates discrete).  ``report_k``: the stage
+        stage's, ``n_cat`` of the D coordinates discrete; ``n_quant`` > 0: the
+        wide quantised stage's, ``n_quant`` of them quantised).  ``report_k``: the stage
         writes all three device buffers and the joint report follows.
         ``shard`` (N.JointShard): the call goes through tpe_joint_run_shard.
         ``liar`` (Engine._liar_model): the stage writes all three device buffers,
@@ -1306,7 +1308,11 @@ class Engine(object):
         dev_cand, dev_lg = return_cand or keep, want_lg or keep
         nb = ctypes.c_uint64(0)
         rec_dtype = N.JOINT_WIDE_RECORD_DTYPE if wide else N.JOINT_RECORD_DTYPE
-        if wide and n_cat:
+        if wide and n_quant:
+            N.check(self.lib.tpe_joint_wide_quant_scratch_bytes(n_ids, C, D - n_cat - n_quant, n_cat, n_quant,
+                                                                ctypes.byref(nb)), self.lib,
+                    'tpe_joint_wide_quant_scratch_bytes')
+        elif wide and n_cat:
             N.check(self.lib.tpe_joint_wide_mixed_scratch_bytes(n_ids, C, D - n_cat, n_cat, ctypes.byref(nb)), self.lib,
                     'tpe_joint_wide_mixed_scratch_bytes')
         elif wide:
@@ -1734,6 +1740,23 @@ class Engine(object):
         in ``run_joint_mixed``."""
         return self._joint_solo('quant', below, above, low, high, cats, quants, ids, n_cand, seed, inject, return_cand,
                                 want_lg, report_k, stream_word, shard, return_table)
+
+    def run_joint_wide_quant(self, below, above, low, high, cats, quants, ids, n_cand, seed, inject=None,
+                             return_cand=False, want_lg=False, return_table=False, report_k=0, stream_word=None):
+        """``run_joint_quant`` for a group of up to N.JOINT_WIDE_MAX_DIMS
+        coordinates: at least one continuous label, 0 to N.JOINT_WIDE_MAX_CAT
+        discrete ones and 1 to N.JOINT_MAX_QUANT quantised ones
+        (tpe_joint_wide_quant_run, include/tpe_hip.h "Wide quantised joint
+        stage"): the same arguments, model, tables, kernel coordinate order,
+        Philox streams and return shapes; the records are
+        N.JOINT_WIDE_RECORD_DTYPE.  The continuous and discrete coordinates are
+        those of ``run_joint_wide_mixed`` (``run_joint_wide`` without discrete
+        labels) over the group without its quantised labels, and a group that
+        ``run_joint_quant`` also takes draws that method's candidates.  The
+        stage is neither sharded nor batch-aware: there is no ``shard`` and no
+        ``liar`` argument."""
+        return self._joint_solo('wide_quant', below, above, low, high, cats, quants, ids, n_cand, seed, inject,
+                                return_cand, want_lg, report_k, stream_word, None, return_table)
 
     def device_tables(self):
         """(problems, comp32) of the last ``run`` as the device holds them after

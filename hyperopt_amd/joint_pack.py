@@ -12,6 +12,7 @@ The dimension limits by entry point (``_check_dims``):
   'mixed'    run_joint_mixed       Dk >= 1, Dc + Dk <= JOINT_MAX_DIMS
   'wide_mixed' run_joint_wide_mixed  1 <= Dk <= JOINT_WIDE_MAX_CAT, Dq = 0, 1 <= Dc + Dk <= JOINT_WIDE_MAX_DIMS
   'quant'    run_joint_quant       Dq >= 1, Dc <= JOINT_QUANT_MAX_CONT, Dk <= JOINT_QUANT_MAX_DISC
+  'wide_quant' run_joint_wide_quant  Dq >= 1, Dc >= 1, Dk <= JOINT_WIDE_MAX_CAT, 2 <= Dc + Dk + Dq <= JOINT_WIDE_MAX_DIMS
   'segment'  run_joint_segments    a continuous group 1 <= Dc <= JOINT_MAX_DIMS; one with discrete or
                                    quantised parts Dc <= JOINT_MSEG_MAX_CONT, Dk <= JOINT_MSEG_MAX_CAT
 and Dq <= JOINT_MAX_QUANT everywhere.
@@ -78,6 +79,16 @@ def _check_dims(entry, Dc, Dk, Dq):
             raise ValueError('joint stage: a segment with discrete or quantised dimensions holds at most %d continuous '
                              'and %d discrete ones, not %d and %d'
                              % (N.JOINT_MSEG_MAX_CONT, N.JOINT_MSEG_MAX_CAT, Dc, Dk))
+    elif entry == 'wide_quant':
+        if Dq == 0:
+            raise ValueError('joint stage: no quantised dimension, use run_joint_wide_mixed / run_joint_wide')
+        if Dc < 1:
+            raise ValueError('joint stage: a wide group with quantised dimensions needs at least 1 continuous one')
+        if Dk > N.JOINT_WIDE_MAX_CAT:
+            raise ValueError('joint stage: a wide group with quantised dimensions holds at most %d discrete ones, '
+                             'not %d' % (N.JOINT_WIDE_MAX_CAT, Dk))
+        if Dc + Dk + Dq > N.JOINT_WIDE_MAX_DIMS:
+            raise ValueError('joint stage: %d dimensions, at most %d' % (Dc + Dk + Dq, N.JOINT_WIDE_MAX_DIMS))
     elif entry == 'wide_mixed':
         if Dq or not 1 <= Dk <= N.JOINT_WIDE_MAX_CAT:
             raise ValueError('joint stage: a wide group with discrete dimensions holds 1 to %d of them and no '

@@ -39,7 +39,9 @@ Extensions over the reference (keyword-only, defaults keep its behaviour):
     categorical labels that gate no other label, ``joint_quantized=True``
     unconditional quniform / qloguniform labels of 2 to 256 lattice values,
     ``joint_wide=True`` 17 to 64 continuous labels instead of at most 16,
-    ``joint_wide_mixed=True`` (with both) 1 to 8 discrete labels among them.
+    ``joint_wide_mixed=True`` (with both) 1 to 8 discrete labels among them,
+    ``joint_wide_quantized=True`` (with joint_wide and joint_quantized) 1 to
+    4 quantised labels beside more than 8 continuous or 4 discrete ones.
     ``joint_branches=True`` also joins the continuous labels of every
     conditional branch, one group per (gate, option), each id under the model
     of the branch it takes (DESIGN.md "Branch groups");
@@ -844,23 +846,25 @@ def suggest(new_ids, domain, trials, seed,
             sampler='philox', precision='fp32', device=None, shard=None, shard_ids=None, shard_labels=None,
             shard_grid=None, joint=False, joint_discrete=False, joint_quantized=False, joint_wide=False,
             joint_branches=False, joint_branches_mixed=False, joint_shard=None, joint_wide_mixed=False,
-            joint_liar=False):
+            joint_wide_quantized=False, joint_liar=False):
     new_ids = list(new_ids)
     if not new_ids:
         return []
     if joint_shard is not None:                  # (argument errors first, as below; nothing on the default path)
-        _joint_shard_pair(joint_shard, joint, joint_wide_mixed)
+        _joint_shard_pair(joint_shard, joint, joint_wide_mixed, joint_wide_quantized)
     liar_mode = _joint_liar_mode(joint_liar)
     if liar_mode:
         _joint_liar_check(joint, joint_shard, mode=liar_mode, joint_branches=joint_branches)
     if ((joint is not False and joint is not None) or joint_discrete or joint_quantized or joint_wide or joint_branches
-            or joint_branches_mixed or joint_wide_mixed):
+            or joint_branches_mixed or joint_wide_mixed or joint_wide_quantized):
         # (argument errors first: no device use, no startup draw)
         plan = _joint_plan(domain.table, joint, sampler, precision, (shard, shard_ids, shard_labels, shard_grid),
-                           joint_discrete, joint_quantized, _wide_mode(joint_wide, joint_wide_mixed), joint_branches,
+                           joint_discrete, joint_quantized,
+                           _wide_mode(joint_wide, joint_wide_mixed, joint_wide_quantized), joint_branches,
                            joint_branches_mixed)
         if liar_mode:
             _joint_liar_check(joint, joint_shard, plan, liar_mode, joint_branches)
+            _wide_quant_liar_check(plan[0], liar_mode)
     t0 = time.time()
     hist = _history.extract(domain, trials)
     if logger.isEnabledFor(logging.INFO):
@@ -877,7 +881,8 @@ def suggest(new_ids, domain, trials, seed,
                               shard_labels=shard_labels, shard_grid=shard_grid, joint=joint,
                               joint_discrete=joint_discrete, joint_quantized=joint_quantized, joint_wide=joint_wide,
                               joint_branches=joint_branches, joint_branches_mixed=joint_branches_mixed,
-                              joint_shard=joint_shard, joint_wide_mixed=joint_wide_mixed, joint_liar=joint_liar)
+                              joint_shard=joint_shard, joint_wide_mixed=joint_wide_mixed,
+                              joint_wide_quantized=joint_wide_quantized, joint_liar=joint_liar)
     logger.info('tpe.suggest took %f seconds', time.time() - t0)
     return rand.docs_from_choices(new_ids, domain, trials, choices)
 
@@ -919,7 +924,7 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
                     sampler='philox', precision='fp32', device=None, shard=None, columns=False,
                     shard_ids=None, shard_labels=None, shard_grid=None, joint=False, joint_discrete=False,
                     joint_quantized=False, joint_wide=False, joint_branches=False, joint_branches_mixed=False,
-                    joint_shard=None, joint_wide_mixed=False, joint_liar=False):
+                    joint_shard=None, joint_wide_mixed=False, joint_wide_quantized=False, joint_liar=False):
     """The suggest core on a structure-of-arrays history (``history.History``):
     per new id a {label: value or None} dict.  ``suggest`` wraps it with the
     Trials document layout; columnar callers (and bench.py's large configs)
@@ -978,6 +983,21 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
     discrete labels or more than 64 labels in such a group raise ValueError; 8
     bounds the set of kernel instantiations, it is not a measured limit.  It
     does not combine with ``joint_shard``.
+
+    ``joint_wide_quantized=True`` (with ``joint``, ``joint_wide`` and
+    ``joint_quantized``): a root group with 1 to 4 quantised labels that the
+    quantised stage does not take (more than 16 labels, more than 8 continuous
+    or more than 4 discrete ones) is scored by the wide quantised stage
+    (DESIGN.md "Quantised labels in wide groups"): 2 to 64 labels in all, at
+    least 1 continuous, at most 512 lattice values, 0 to 8 discrete labels
+    (those ``joint_discrete`` admits; ``joint_wide_mixed`` is not needed for
+    them) of at most 1024 categories in all; more raises ValueError.  The
+    model is the quantised stage's, the kernel coordinates continuous, discrete,
+    then quantised, and the continuous and discrete coordinates are drawn as
+    the wide mixed stage draws them.  A group the quantised stage takes and a
+    group without a quantised label take exactly the path without the keyword,
+    byte for byte.  It does not combine with ``joint_shard``, nor with any
+    ``joint_liar`` value where the root group takes the new stage.
 
     ``joint_branches=True`` (with ``joint``): conditional labels are joined
     too, one group per branch (DESIGN.md "Branch groups").  A branch group is
@@ -1077,19 +1097,21 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
     if sampler not in ('philox', 'replay'):
         raise ValueError("sampler must be 'philox' or 'replay'")
     if joint_shard is not None:
-        joint_shard = _joint_shard_pair(joint_shard, joint, joint_wide_mixed)
+        joint_shard = _joint_shard_pair(joint_shard, joint, joint_wide_mixed, joint_wide_quantized)
     liar_mode = _joint_liar_mode(joint_liar)
     if liar_mode:
         _joint_liar_check(joint, joint_shard, mode=liar_mode, joint_branches=joint_branches)
     group, branch_groups = None, []
     if ((joint is not False and joint is not None) or joint_discrete or joint_quantized or joint_wide or joint_branches
-            or joint_branches_mixed or joint_wide_mixed):
+            or joint_branches_mixed or joint_wide_mixed or joint_wide_quantized):
         group, branch_groups = _joint_plan(table, joint, sampler, precision,
                                            (shard, shard_ids, shard_labels, shard_grid), joint_discrete,
-                                           joint_quantized, _wide_mode(joint_wide, joint_wide_mixed),
+                                           joint_quantized,
+                                           _wide_mode(joint_wide, joint_wide_mixed, joint_wide_quantized),
                                            joint_branches, joint_branches_mixed)
         if liar_mode:
             _joint_liar_check(joint, joint_shard, (group, branch_groups), liar_mode, joint_branches)
+            _wide_quant_liar_check(group, liar_mode)
     if sum(a is not None for a in (shard, shard_ids, shard_labels, shard_grid)) > 1:
         raise ValueError('shard, shard_ids, shard_labels and shard_grid are exclusive: one shard axis per suggest')
     if (shard_ids is not None or shard_labels is not None or shard_grid is not None) and sampler == 'replay':
@@ -1165,9 +1187,9 @@ def _joint_liar_check(joint, joint_shard, plan=None, mode=True, joint_branches=F
                          % ('there is no root group' if group is None else '%r is discrete or quantised' % other[0]))
 
 
-def _joint_shard_pair(joint_shard, joint, wide_mixed=False):
+def _joint_shard_pair(joint_shard, joint, wide_mixed=False, wide_quant=False):
     """(rank, world) of a ``joint_shard`` argument as ints, or None; ValueError
-    without ``joint``, with ``joint_wide_mixed`` and for anything but a pair of
+    without ``joint``, with ``joint_wide_mixed`` / ``joint_wide_quantized`` and for anything but a pair of
     ints with 0 <= rank < world.  Touches no device."""
     if joint_shard is None:
         return None
@@ -1175,6 +1197,9 @@ def _joint_shard_pair(joint_shard, joint, wide_mixed=False):
         raise ValueError('joint_shard needs joint=True or joint=[labels]: it only shards the joint stages')
     if wide_mixed:
         raise ValueError('joint_wide_mixed=True does not combine with joint_shard: the wide mixed stage is not sharded')
+    if wide_quant:
+        raise ValueError('joint_wide_quantized=True does not combine with joint_shard: the wide quantised stage is '
+                         'not sharded')
     ok = isinstance(joint_shard, (tuple, list)) and len(joint_shard) == 2 and \
         all(isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) for v in joint_shard)
     if not ok or not 0 <= joint_shard[0] < joint_shard[1]:
@@ -1234,18 +1259,37 @@ class _JointParts(object):
 
 
 WIDE_MIXED = 'mixed'
+WIDE_QUANT = 'quant'                  # joint_wide_quantized
+WIDE_QUANT_MIXED = 'quant_mixed'      # ... together with joint_wide_mixed
+_WIDE_QUANT_MODES = (WIDE_QUANT, WIDE_QUANT_MIXED)
 
 
-def _wide_mode(joint_wide, joint_wide_mixed):
+def _is_wide_quant(wide):
+    return isinstance(wide, str) and wide in _WIDE_QUANT_MODES
+
+
+def _wide_base(wide):
+    """``wide`` (_wide_mode) without ``joint_wide_quantized``: what governs a
+    group that the wide quantised stage does not take."""
+    if _is_wide_quant(wide):
+        return WIDE_MIXED if wide == WIDE_QUANT_MIXED else True
+    return wide
+
+
+def _wide_mode(joint_wide, joint_wide_mixed, joint_wide_quantized=False):
     """The ``wide`` argument of _joint_plan and what it calls: ``joint_wide``
     as given, or WIDE_MIXED where ``joint_wide_mixed`` also admits discrete
-    labels to the wide groups; ValueError for that keyword without
-    ``joint_wide``."""
+    labels to the wide groups, or WIDE_QUANT (with ``joint_wide_mixed``:
+    WIDE_QUANT_MIXED) where ``joint_wide_quantized`` admits quantised labels
+    beyond the quantised stage's limits; ValueError for one of those keywords
+    without ``joint_wide``."""
+    if joint_wide_quantized and not joint_wide:
+        raise ValueError('joint_wide_quantized=True needs joint_wide=True: it only widens the wide groups')
     if not joint_wide_mixed:
-        return joint_wide
+        return WIDE_QUANT if joint_wide_quantized else joint_wide
     if not joint_wide:
         raise ValueError('joint_wide_mixed=True needs joint_wide=True: it only widens the wide groups')
-    return WIDE_MIXED
+    return WIDE_QUANT_MIXED if joint_wide_quantized else WIDE_MIXED
 
 
 def _joint_group(table, joint, sampler, precision, shards, discrete=False, quantized=False, wide=False):
@@ -1267,7 +1311,14 @@ def _joint_restrictions(joint, sampler, precision, shards, discrete=False, quant
     """ValueError for a keyword without ``joint`` (or without the keywords it
     widens) and for the sampler, precision and shard arguments the joint stage
     does not combine with."""
-    if wide == WIDE_MIXED and not discrete:
+    if _is_wide_quant(wide):
+        if joint is False or joint is None:
+            raise ValueError('joint_wide_quantized=True needs joint=True or joint=[labels]: it only widens what joint '
+                             'joins')
+        if not quantized:
+            raise ValueError('joint_wide_quantized=True needs joint_quantized=True: it only admits the quantised '
+                             'labels that keyword joins to the wide groups')
+    if _wide_base(wide) == WIDE_MIXED and not discrete:
         raise ValueError('joint_wide_mixed=True needs joint_discrete=True: it only admits the discrete labels that '
                          'keyword joins to the wide groups')
     if branch_mixed and not branches:
@@ -1321,7 +1372,14 @@ def _joint_rows(table, joint, discrete=False, quantized=False):
 def _joint_limits(rows, wide=False):
     """``rows`` (at least 2), or ValueError where the group exceeds what one
     joint stage takes (``wide`` = WIDE_MIXED: a wide group may hold 1 to
-    TPE_JOINT_WIDE_MAX_CAT discrete labels)."""
+    TPE_JOINT_WIDE_MAX_CAT discrete labels; WIDE_QUANT / WIDE_QUANT_MIXED: a
+    group with a quantised label that the quantised stage does not take is held
+    to the wide quantised stage's limits, every other group to those without
+    ``joint_wide_quantized``)."""
+    if _is_wide_quant(wide):
+        if _takes_wide_quant(rows):
+            return _wide_quant_limits(rows)
+        wide = _wide_base(wide)
     if len(rows) > TPE_JOINT_MAX_DIMS:
         if not wide:
             raise ValueError('joint joins at most TPE_JOINT_MAX_DIMS = %d labels, not %d: pass the labels to join as '
@@ -1374,6 +1432,58 @@ def _joint_limits(rows, wide=False):
             raise ValueError('joint joins at most %d discrete labels beside a quantised one, not %d%s'
                              % (N.JOINT_QUANT_MAX_DISC, n_disc, tail))
     return rows
+
+
+def _takes_wide_quant(rows):
+    """Whether a root group holds a quantised label and does not fit the
+    quantised stage (more than TPE_JOINT_MAX_DIMS labels, more than 8
+    continuous or more than 4 discrete ones): under ``joint_wide_quantized``
+    the wide quantised stage takes it."""
+    n_quant = sum(1 for r in rows if r.dist in _joint.QUANT_DISTS)
+    if not n_quant:
+        return False
+    n_disc = sum(1 for r in rows if r.categorical)
+    return (len(rows) > TPE_JOINT_MAX_DIMS or len(rows) - n_quant - n_disc > N.JOINT_QUANT_MAX_CONT
+            or n_disc > N.JOINT_QUANT_MAX_DISC)
+
+
+def _wide_quant_limits(rows):
+    """``rows`` of a group the wide quantised stage takes, or ValueError where
+    it exceeds that stage's limits (they bound the set of compiled kernels)."""
+    n_disc = sum(1 for r in rows if r.categorical)
+    qrows = [r for r in rows if r.dist in _joint.QUANT_DISTS]
+    n_cont = len(rows) - len(qrows) - n_disc
+    n_cats = sum(int(r.args['upper']) for r in rows if r.categorical)
+    n_lat = sum(_joint.lattice_size(r.dist, r.args)[1] for r in qrows)
+    head = 'joint with joint_wide_quantized=True: a group with quantised labels beyond the quantised stage joins '
+    tail = ' among its %d: pass the labels to join as joint=[...]' % len(rows)
+    if len(rows) > TPE_JOINT_WIDE_MAX_DIMS:
+        raise ValueError('%sat most TPE_JOINT_WIDE_MAX_DIMS = %d labels, not %d%s'
+                         % (head, TPE_JOINT_WIDE_MAX_DIMS, len(rows), tail))
+    if n_cont < 1:
+        raise ValueError('%sat least 1 continuous label, not %d%s' % (head, n_cont, tail))
+    if len(qrows) > N.JOINT_MAX_QUANT:
+        raise ValueError('%sat most TPE_JOINT_MAX_QUANT = %d quantised labels, not %d%s'
+                         % (head, N.JOINT_MAX_QUANT, len(qrows), tail))
+    if n_lat > N.JOINT_MAX_LATTICE_TOTAL:
+        raise ValueError('%squantised labels of at most TPE_JOINT_MAX_LATTICE_TOTAL = %d lattice values in all, not '
+                         '%d%s' % (head, N.JOINT_MAX_LATTICE_TOTAL, n_lat, tail))
+    if n_disc > TPE_JOINT_WIDE_MAX_CAT:
+        raise ValueError('%sat most TPE_JOINT_WIDE_MAX_CAT = %d discrete labels, not %d%s'
+                         % (head, TPE_JOINT_WIDE_MAX_CAT, n_disc, tail))
+    if n_cats > N.JOINT_MAX_CAT_TOTAL:
+        raise ValueError('%sdiscrete labels of at most TPE_JOINT_MAX_CAT_TOTAL = %d categories in all, not %d%s'
+                         % (head, N.JOINT_MAX_CAT_TOTAL, n_cats, tail))
+    return rows
+
+
+def _wide_quant_liar_check(group, mode):
+    """ValueError where ``joint_liar`` meets a root group that takes the wide
+    quantised stage: tpe_joint_liar_mixed does not take such a group."""
+    if group is not None and _takes_wide_quant(group):
+        raise ValueError('joint_liar=%r does not combine with a root group that takes the wide quantised stage '
+                         '(joint_wide_quantized): more than 8 continuous or 4 discrete labels beside a quantised one'
+                         % (mode,))
 
 
 def _joint_kernel_order(group):
@@ -1463,7 +1573,7 @@ def _joint_plan(table, joint, sampler, precision, shards, discrete=False, quanti
     first label.  ``branch_mixed``: ``discrete`` / ``quantized`` also admit
     conditional discrete / quantised labels with exactly one parent to the
     group of their condition (_branch_mixed_reason, _branch_mixed_limit).
-    ``wide`` (_wide_mode) widens the root group only (_joint_limits).
+    ``wide`` (_wide_mode, WIDE_QUANT among its values) widens the root group only (_joint_limits).
     ValueError as _joint_group; touches no device."""
     if not branches:
         if branch_mixed:
@@ -1531,13 +1641,16 @@ def _run_root_group(engine, group, hist, ids, seed, prior_weight, n_EI_candidate
         model = _joint.fit_quant_model(crows, drows, qrows, hist, _history.split_below(hist, gamma), prior_weight,
                                        DEFAULT_LF)
         if kw.pop('liar', False):                # (joint_liar='mixed': W as below, the lattice values' fit coordinates)
+            _wide_quant_liar_check(group, 'mixed')
             out = engine.run_joint_liar_mixed(
                 model.below[:3], model.above[:3], model.low, model.high, model.cats(), model.quants(), ids,
                 int(n_EI_candidates), seed, centres=model.centres(),
                 liar=_joint.side_weight_sum(len(model.above[0]) - 1, prior_weight, DEFAULT_LF), **kw)
         else:
-            out = engine.run_joint_quant(model.below[:3], model.above[:3], model.low, model.high, model.cats(),
-                                         model.quants(), ids, int(n_EI_candidates), seed, **kw)
+            # beyond the quantised stage's limits (joint_wide_quantized=True let the group through): the wide one
+            run = engine.run_joint_wide_quant if _takes_wide_quant(group) else engine.run_joint_quant
+            out = run(model.below[:3], model.above[:3], model.low, model.high, model.cats(), model.quants(), ids,
+                      int(n_EI_candidates), seed, **kw)
     elif drows:                                  # kernel coordinates: the continuous labels, then the discrete ones
         group = [r for r in group if not r.categorical] + drows
         model = _joint.fit_mixed_model(group[:len(group) - len(drows)], drows, hist,
@@ -1980,14 +2093,15 @@ def joint_candidate_report_columns(table, hist, new_id, seed, k=8, joint=True, j
                                    joint_quantized=False, joint_wide=False, joint_branches=False,
                                    prior_weight=_default_prior_weight, n_EI_candidates=_default_n_EI_candidates,
                                    gamma=_default_gamma, device=None, joint_branches_mixed=False,
-                                   joint_wide_mixed=False):
+                                   joint_wide_mixed=False, joint_wide_quantized=False):
     """``joint_candidate_report`` on a structure-of-arrays history (as
     ``candidate_report_columns`` is to ``candidate_report``)."""
     k = _report_check_k(k)
     if joint is False or joint is None:
         raise ValueError('joint_candidate_report needs joint=True or joint=[labels]')
     group, branch_groups = _joint_plan(table, joint, 'philox', 'fp32', (None, None, None, None), joint_discrete,
-                                       joint_quantized, _wide_mode(joint_wide, joint_wide_mixed), joint_branches,
+                                       joint_quantized,
+                                       _wide_mode(joint_wide, joint_wide_mixed, joint_wide_quantized), joint_branches,
                                        joint_branches_mixed)
     if len(hist) == 0:
         raise ValueError('joint_candidate_report needs a history: no completed trial to fit the models from')
@@ -2023,7 +2137,7 @@ def joint_candidate_report_columns(table, hist, new_id, seed, k=8, joint=True, j
 def joint_candidate_report(new_id, domain, trials, seed, k=8, joint=True, joint_discrete=False, joint_quantized=False,
                            joint_wide=False, joint_branches=False, prior_weight=_default_prior_weight,
                            n_EI_candidates=_default_n_EI_candidates, gamma=_default_gamma, device=None,
-                           joint_branches_mixed=False, joint_wide_mixed=False):
+                           joint_branches_mixed=False, joint_wide_mixed=False, joint_wide_quantized=False):
     """The candidate pools behind the joint stages of a ``suggest([new_id],
     domain, trials, seed, joint=..., n_EI_candidates=...)`` with the same joint
     keywords: per joint group the ``k`` best distinct candidate vectors with
@@ -2038,14 +2152,15 @@ def joint_candidate_report(new_id, domain, trials, seed, k=8, joint=True, joint_
     k = _report_check_k(k)
     if joint is not False and joint is not None:
         _joint_plan(domain.table, joint, 'philox', 'fp32', (None, None, None, None), joint_discrete, joint_quantized,
-                    _wide_mode(joint_wide, joint_wide_mixed), joint_branches,
+                    _wide_mode(joint_wide, joint_wide_mixed, joint_wide_quantized), joint_branches,
                     joint_branches_mixed)                    # (argument errors before the history is read)
     hist = _history.extract(domain, trials)
     return joint_candidate_report_columns(domain.table, hist, new_id, seed, k=k, joint=joint,
                                           joint_discrete=joint_discrete, joint_quantized=joint_quantized,
                                           joint_wide=joint_wide, joint_branches=joint_branches,
                                           joint_branches_mixed=joint_branches_mixed, prior_weight=prior_weight, n_EI_candidates=n_EI_candidates, gamma=gamma,
-                                          device=device, joint_wide_mixed=joint_wide_mixed)
+                                          device=device, joint_wide_mixed=joint_wide_mixed,
+                                          joint_wide_quantized=joint_wide_quantized)
 
 
 def suggest_replay(new_ids, domain, trials, seed, **kw):

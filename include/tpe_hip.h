@@ -1497,6 +1497,107 @@ int tpe_joint_quant_run(const tpe_joint_quant_args* args, tpe_joint_record* reco
 int tpe_joint_quant_profile(double* table_ms);
 
 /* ------------------------------------------------------------------------
+ * Wide quantised joint stage (tpe_joint.hip; additive to ABI 24): a group of
+ * n_dims >= 1 continuous labels, 0 <= n_cat <= TPE_JOINT_WIDE_MAX_CAT discrete
+ * ones and 1 <= n_quant <= TPE_JOINT_MAX_QUANT quantised ones, n_dims + n_cat +
+ * n_quant <= TPE_JOINT_WIDE_MAX_DIMS.  Nothing is defined anew:
+ *   model        that of the quantised joint stage above at a larger width: the
+ *                lattice edges, P_kd(i), the table T[d][i][k] = log2 P_kd(i)
+ *                built by the same k_joint_qtable launches into a workspace of
+ *                tpe_joint_quant_table_bytes, the floor TPE_JOINT_QFLOOR; the
+ *                discrete part that of the wide mixed stage.
+ *   coordinates  the n_dims continuous labels, the n_cat discrete ones, then the
+ *                n_quant quantised ones; a category and a lattice index travel
+ *                as f32 in `cand` / `inject` and as double in
+ *                tpe_joint_wide_record.z.  low / high [n_dims + d] are the outer
+ *                edges of quantised dimension d, as in tpe_joint_quant_args.
+ *   streams      word 0 of block 0 picks the component; word 1 + j serves kernel
+ *                coordinate j, that is word (1 + j) & 3 of block (1 + j) >> 2.  A
+ *                continuous coordinate is drawn as tpe_joint_wide_run draws it,
+ *                a discrete one as tpe_joint_wide_mixed_run does, a quantised
+ *                one as tpe_joint_quant_run does (the continuous draw through
+ *                quant_samp, clipped in f32, then the number of interior edges
+ *                <= (double) z by binary search).
+ * So the continuous and discrete coordinates of a run equal those of a
+ * tpe_joint_wide_mixed_run (n_cat = 0: tpe_joint_wide_run) over the group
+ * without its quantised labels, and a run at a shape tpe_joint_quant_run also
+ * takes draws that run's candidates, both bit for bit.
+ *
+ * Launches: k_joint_qtable once per side; k_joint_wide_quant_sample (skipped
+ * under TPE_JOINT_INJECT) draws one candidate a thread into `scratch`, laid out
+ * [256-candidate block][j][256] over all coordinates;
+ * k_joint_wide_quant_chunk<DP, KP, QP, R> (DP the padded n_dims in {16, 24, 32,
+ * 48, 64}, KP the padded n_cat in {0, 2, 8}, QP the padded n_quant in {1, 2, 4},
+ * R = 2 candidates a lane for DP <= 32 and 1 above) scores a chunk of 256 R
+ * candidates: rows, categories and the table stream through LDS in component
+ * tiles of ONE length, the longest multiple of 8 (at most the wide stage's
+ * tile) whose table tile [sum V + 1][tile + 4] f32 stays within 26 KiB, so that
+ * a workgroup's LDS stays under 64 KiB; per (candidate, component, quantised
+ * slot) one table read at the candidate's own lattice index and one add.
+ * k_joint_wide_merge picks the winner.  No atomics: the same call twice gives
+ * the same bytes.
+ *
+ * tpe_joint_wide_quant_args starts with the fields of tpe_joint_wide_mixed_args
+ * at the same offsets; the quantised fields of tpe_joint_quant_args follow.
+ * Returns TPE_E_ARG before any launch (no device needed) for: null args;
+ * n_quant outside [1, TPE_JOINT_MAX_QUANT]; n_cat outside [0,
+ * TPE_JOINT_WIDE_MAX_CAT]; n_dims < 1 or n_dims + n_cat + n_quant >
+ * TPE_JOINT_WIDE_MAX_DIMS; everything tpe_joint_wide_run checks on the shared
+ * fields; with n_cat > 0 everything tpe_joint_wide_mixed_run checks on the
+ * category tables; everything tpe_joint_quant_run checks on the lattices, the
+ * quantised rows and the table workspace; scratch smaller than
+ * tpe_joint_wide_quant_scratch_bytes.  tpe_joint_run_shard does not take this
+ * stage.  Advances the resident-level epoch as the other stage runs do;
+ * tpe_joint_profile (scoring kernel, merge), tpe_joint_quant_profile (the table
+ * launches) and tpe_joint_wide_quant_profile (the sampling kernel) serve it.
+ * ---------------------------------------------------------------------- */
+typedef struct tpe_joint_wide_quant_args {
+  int32_t n_dims, n_cand, n_ids, flags;   /* as tpe_joint_wide_mixed_args ... */
+  int32_t k_below, k_above;
+  uint32_t stream_word;
+  int32_t reserved;
+  uint64_t seed;
+  const float *below_mu, *below_a, *below_c;
+  const float *above_mu, *above_a, *above_c;
+  double below_base, above_base;
+  const double* samp_cum;
+  const float* samp;
+  const int64_t* ids;
+  const float* inject;                    /* device [n_cand * (n_dims + n_cat + n_quant)] */
+  double low[TPE_JOINT_WIDE_MAX_DIMS], high[TPE_JOINT_WIDE_MAX_DIMS];
+  int32_t n_cat;                          /* 0 allowed: the category tables may be NULL then */
+  int32_t cat_upper[TPE_JOINT_WIDE_MAX_CAT];
+  int32_t cat_off[TPE_JOINT_WIDE_MAX_CAT];
+  const float *below_cat, *above_cat;
+  const float *below_miss, *below_bonus;
+  const float *above_miss, *above_bonus;
+  const double* below_h;
+  const double* cat_cum;                  /* ... up to here */
+  int32_t n_quant;                        /* as tpe_joint_quant_args from here on */
+  int32_t n_edges;
+  int32_t quant_v[TPE_JOINT_MAX_QUANT];
+  int32_t quant_edge_off[TPE_JOINT_MAX_QUANT];
+  const double* quant_edges;
+  const double *below_qmu, *below_qsigma;
+  const double *above_qmu, *above_qsigma;
+  const float* quant_samp;
+  float* quant_table;
+  uint64_t quant_table_bytes;
+} tpe_joint_wide_quant_args;
+
+/* the chunk records and the candidate block of one tpe_joint_wide_quant_run */
+int tpe_joint_wide_quant_scratch_bytes(int32_t n_ids, int32_t n_cand, int32_t n_dims, int32_t n_cat, int32_t n_quant,
+                                       uint64_t* bytes);
+
+/* as tpe_joint_wide_run; cand: device f32 [n_ids * n_cand * (n_dims + n_cat + n_quant)] */
+int tpe_joint_wide_quant_run(const tpe_joint_wide_quant_args* args, tpe_joint_wide_record* records, float* cand,
+                             double* l_out, double* g_out, void* scratch, uint64_t scratch_bytes, void* stream);
+
+/* Profiling only: the sampling kernel's time (ms) of the last profiled sampling
+ * tpe_joint_wide_quant_run (it WAITS for it). */
+int tpe_joint_wide_quant_profile(double* sample_ms);
+
+/* ------------------------------------------------------------------------
  * Segmented joint stage (tpe_joint.hip; additive to ABI 24): one call scores the
  * (new id, group) problems of MANY continuous groups, each group ("segment")
  * with its own model, dimension count and Philox stream word.  It serves joint

@@ -1,6 +1,6 @@
 """Time the joint TPE stage against the host route.
 Usage: python tools/joint_time.py [--pairs 3] [--warmup 1] [--cand 1048576] [--history 10000]
-                                  [--host-cand N] [--out FILE] [--mixed | --quant | --wide | --wide-mixed | --liar |
+                                  [--host-cand N] [--out FILE] [--mixed | --quant | --wide | --wide-mixed | --wide-quant | --liar |
                                    --liar-mixed | --liar-branches | --liar-branches-mixed]
 
 Workload: a flat space of 4 continuous labels (uniform, loguniform, normal,
@@ -72,6 +72,23 @@ coordinate) evaluation and its ratio to the yardstick's, and for the new stage
 the worst l / g error of the first --host-cand (default 1024) sampled vectors as
 a fraction of the lpdf tolerance.  --out defaults to
 profiles/joint_wide_mixed_time.jsonl.
+
+--wide-quant: the wide quantised stage (DESIGN.md "Quantised labels in wide
+groups").  Flat spaces of Dc labels of hp.uniform(-5, 5), Dk labels of hp.choice
+of 4 and Dq labels of hp.quniform (32 values the first, 8 the second), the same
+history size.  Per round, alternating in one process: Engine.run_joint_wide_mixed
+at 18 + 2 and Engine.run_joint_wide_quant at 17 + 2 + 1; run_joint_wide_mixed at
+28 + 4 and run_joint_wide_quant at 26 + 4 + 2 (the yardsticks:
+k_joint_wide_mixed_chunk at the same number of coordinates);
+Engine.run_joint_quant and run_joint_wide_quant on one 8 + 4 + 2 group (the
+yardstick: k_joint_quant_chunk<8, 4, 2>); and run_joint_wide_quant at 17 + 2 + 2
+with two lattices of 256 values (512 in all: the shortest tile).  Each chunk
+kernel by its own events, the sampling and table kernels by theirs.  The line
+carries per run the medians and ranges, the chunk kernel's time per (candidate x
+component x coordinate) evaluation and its ratio to the yardstick's, and for the
+new stage the worst l / g error of the first --host-cand (default 1024) sampled
+vectors as a fraction of the lpdf tolerance.  --out defaults to
+profiles/joint_wide_quant_time.jsonl.
 
 --liar: batch-aware joint suggests (DESIGN.md "Batch-aware joint suggests").  The
 4-label workload above with --batch (default 64) new ids in one call; per round,
@@ -576,6 +593,155 @@ def main_wide_mixed(args):
     return 0
 
 
+def make_flat_quant_history(n, Dc, Dk, Vs):
+    """make_flat_mixed_history's labels with one hp.quniform(0, V - 1, 1) per entry
+    of ``Vs``; the loss also couples x00 with the first quantised label."""
+    from hyperopt_amd import base, history as H, hp
+    labels = ['x%02d' % i for i in range(Dc)]
+    clabels = ['c%02d' % i for i in range(Dk)]
+    qlabels = ['q%02d' % i for i in range(len(Vs))]
+    space = {k: hp.uniform(k, -5, 5) for k in labels}
+    space.update({k: hp.choice(k, [0, 1, 2, 3]) for k in clabels})
+    space.update({k: hp.quniform(k, 0, V - 1, 1) for k, V in zip(qlabels, Vs)})
+    domain = base.Domain(lambda d: 0.0, space)
+    rs = np.random.RandomState(SEED + 10000 * len(Vs) + 100 * Dc + Dk)
+    X = rs.uniform(-5, 5, (n, Dc))
+    XC = rs.randint(4, size=(n, Dk)).astype(np.int64)
+    XQ = np.stack([np.rint(rs.uniform(0, V - 1, n)) for V in Vs], axis=1)
+    loss = ((X - np.linspace(-2, 2, Dc)[None, :]) ** 2).sum(axis=1) + X[:, 0] * X[:, 1] \
+        + (X[:, 0] - (10.0 * XQ[:, 0] / (Vs[0] - 1) - 5.0)) ** 2 + 0.1 * XC.sum(axis=1) \
+        + 0.01 * rs.standard_normal(n)
+    tids = np.arange(n, dtype=np.int64)
+    obs = {k: (tids, X[:, i]) for i, k in enumerate(labels)}
+    obs.update({k: (tids, XC[:, i]) for i, k in enumerate(clabels)})
+    obs.update({k: (tids, XQ[:, i]) for i, k in enumerate(qlabels)})
+    return domain, H.History(tids, loss, obs)
+
+
+def main_wide_quant(args):
+    import torch
+    from hyperopt_amd import _native as N, history as H, joint as J
+    from hyperopt_amd.engine import get_engine
+
+    eng = get_engine(None, 'fp32')
+    lib = eng.lib
+    C = args.cand
+    ids = np.array([args.history], dtype=np.int64)
+    mixed, quant = {}, {}
+    for Dc, Dk in ((18, 2), (28, 4)):
+        domain, hist = make_flat_mixed_history(args.history, Dc, Dk)
+        t = domain.table
+        crows = [r for r in t.rows if J.eligible(r)]
+        drows = [r for r in t.rows if J.eligible_discrete(r, t)]
+        mixed[Dc, Dk] = J.fit_mixed_model(crows, drows, hist, H.split_below(hist, 0.25), 1.0)
+    for Dc, Dk, Vs in ((17, 2, (32,)), (26, 4, (32, 8)), (8, 4, (32, 8)), (17, 2, (256, 256))):
+        domain, hist = make_flat_quant_history(args.history, Dc, Dk, Vs)
+        t = domain.table
+        crows = [r for r in t.rows if J.eligible(r)]
+        drows = [r for r in t.rows if J.eligible_discrete(r, t)]
+        qrows = [r for r in t.rows if J.eligible_quant(r, t)]
+        assert (len(crows), len(drows), len(qrows)) == (Dc, Dk, len(Vs))
+        quant[Dc, Dk, Vs] = J.fit_quant_model(crows, drows, qrows, hist, H.split_below(hist, 0.25), 1.0)
+
+    def run_mixed(key, **kw):
+        m = mixed[key]
+        return eng.run_joint_wide_mixed(m.below[:3], m.above[:3], m.low, m.high, m.cats(), ids, C, SEED, **kw)
+
+    def run_quant(key, narrow=False, **kw):
+        m = quant[key]
+        fn = eng.run_joint_quant if narrow else eng.run_joint_wide_quant
+        return fn(m.below[:3], m.above[:3], m.low, m.high, m.cats(), m.quants(), ids, C, SEED, **kw)
+
+    # (name, the call, sampling kernel of its own, table kernels, coordinates, the model, the kernel, its yardstick)
+    routes = [
+        ('wide_mixed_18_2', lambda **kw: run_mixed((18, 2), **kw), True, False, 20, mixed[18, 2],
+         'k_joint_wide_mixed_chunk<20, 2, 2>', None),
+        ('wide_quant_17_2_1', lambda **kw: run_quant((17, 2, (32,)), **kw), True, True, 20, quant[17, 2, (32,)],
+         'k_joint_wide_quant_chunk<24, 2, 1, 2>', 'wide_mixed_18_2'),
+        ('wide_mixed_28_4', lambda **kw: run_mixed((28, 4), **kw), True, False, 32, mixed[28, 4],
+         'k_joint_wide_mixed_chunk<32, 4, 2>', None),
+        ('wide_quant_26_4_2', lambda **kw: run_quant((26, 4, (32, 8)), **kw), True, True, 32, quant[26, 4, (32, 8)],
+         'k_joint_wide_quant_chunk<32, 8, 2, 2>', 'wide_mixed_28_4'),
+        ('quant_8_4_2', lambda **kw: run_quant((8, 4, (32, 8)), narrow=True, **kw), False, True, 14,
+         quant[8, 4, (32, 8)], 'k_joint_quant_chunk<8, 4, 2>', None),
+        ('wide_quant_8_4_2', lambda **kw: run_quant((8, 4, (32, 8)), **kw), True, True, 14, quant[8, 4, (32, 8)],
+         'k_joint_wide_quant_chunk<16, 8, 2, 2>', 'quant_8_4_2'),
+        ('wide_quant_17_2_2_v512', lambda **kw: run_quant((17, 2, (256, 256)), **kw), True, True, 21,
+         quant[17, 2, (256, 256)], 'k_joint_wide_quant_chunk<24, 2, 2, 2>', 'wide_mixed_18_2'),
+    ]
+
+    def kernel_ms(r):
+        ms2, sms, tms = (ctypes.c_double * 2)(), ctypes.c_double(0.0), ctypes.c_double(0.0)
+        torch.cuda.synchronize()
+        N.check(lib.tpe_joint_profile(1, None), lib, 'tpe_joint_profile')
+        r[1]()
+        if r[2]:
+            prof = 'tpe_joint_wide_quant_profile' if r[0].startswith('wide_quant') else 'tpe_joint_wide_profile'
+            N.check(getattr(lib, prof)(ctypes.byref(sms)), lib, prof)
+        if r[3]:
+            N.check(lib.tpe_joint_quant_profile(ctypes.byref(tms)), lib, 'tpe_joint_quant_profile')
+        N.check(lib.tpe_joint_profile(0, ms2), lib, 'tpe_joint_profile')
+        return ms2[0], ms2[1], sms.value, tms.value
+
+    for _ in range(args.warmup):
+        for r in routes:
+            r[1]()
+    ms = dict((r[0], []) for r in routes)
+    for i in range(args.pairs):
+        for r in routes:
+            ms[r[0]].append(kernel_ms(r))
+        print('round %d: %s' % (i, ', '.join('%s %.3f ms' % (r[0], ms[r[0]][-1][0]) for r in routes)), file=sys.stderr,
+              flush=True)
+
+    # (untimed) l and g of the first --host-cand sampled vectors of the new stage against the float64 model
+    n_host = min(C, args.host_cand or 1024)
+    err = {}
+    for r in routes:
+        if not r[0].startswith('wide_quant'):
+            continue
+        m = r[5]
+        Dc, Dk = len(m.rows), len(m.drows)
+        _, cand, dl, dg = r[1](return_cand=True, want_lg=True)
+        z, v = cand[0, :n_host, :Dc].astype(np.float64), cand[0, :n_host, Dc:Dc + Dk].astype(np.int64)
+        qi = cand[0, :n_host, Dc + Dk:].astype(np.int64)
+        e = 0.0
+        for side, s, dev in ((m.below, m.s_below, dl), (m.above, m.s_above, dg)):
+            qs = [(side[4][:, d], side[5][:, d], lat[3]) for d, lat in enumerate(m.lattices)]
+            ref = J.quant_lpdf_numpy(z, v, qi, side[0], side[1], side[2], m.low, m.high, side[3], m.ps, s, qs)
+            e = max(e, float(np.max(np.abs(dev[0, :n_host] - ref) / np.maximum(1.0, np.abs(ref)))) / 1e-5)
+        err[r[0]] = e
+
+    def stat(name, j=0):
+        x = [q[j] for q in ms[name]]
+        return dict(median=float(np.median(x)), min=min(x), max=max(x), all=x)
+
+    def per_eval_ps(r):
+        """picoseconds of chunk-kernel time per (candidate x component x coordinate) evaluation"""
+        m = r[5]
+        return stat(r[0])['median'] * 1e9 / (float(C) * (len(m.below[0]) + len(m.above[0])) * r[4])
+    by_name = dict((r[0], r) for r in routes)
+    runs = {}
+    for r in routes:
+        m = r[5]
+        yard = by_name.get(r[7])
+        runs[r[0]] = dict(kernel=r[6], coordinates=r[4], n_cat=len(m.drows), n_quant=len(getattr(m, 'qrows', ())),
+                          lattice_values=[lat[1] for lat in getattr(m, 'lattices', ())],
+                          k_below=len(m.below[0]), k_above=len(m.above[0]), chunk_ms=stat(r[0]),
+                          merge_ms=stat(r[0], 1)['median'], sample_ms=stat(r[0], 2) if r[2] else None,
+                          table_ms=stat(r[0], 3) if r[3] else None, ps_per_eval=per_eval_ps(r), yardstick=r[7],
+                          ratio_to_yardstick=per_eval_ps(r) / per_eval_ps(yard) if yard else None,
+                          lpdf_err_over_tol=err.get(r[0]))
+    line = dict(tool='joint_time --wide-quant', history=args.history, n_cand=C, rounds=args.pairs, runs=runs,
+                host_cand=n_host, gpu=torch.cuda.get_device_name(0))
+    text = json.dumps(line)
+    print(text)
+    out = args.out or os.path.join(ROOT, 'profiles', 'joint_wide_quant_time.jsonl')
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, 'a') as f:
+        f.write(text + '\n')
+    return 0
+
+
 def main_liar(args):
     import torch
     from hyperopt_amd import history as H, joint as J
@@ -917,6 +1083,7 @@ def main():
     ap.add_argument('--quant', action='store_true')
     ap.add_argument('--wide', action='store_true')
     ap.add_argument('--wide-mixed', action='store_true')
+    ap.add_argument('--wide-quant', action='store_true')
     ap.add_argument('--liar', action='store_true')
     ap.add_argument('--liar-mixed', action='store_true')
     ap.add_argument('--liar-branches', action='store_true')
@@ -932,6 +1099,8 @@ def main():
         return main_wide(args)
     if args.wide_mixed:
         return main_wide_mixed(args)
+    if args.wide_quant:
+        return main_wide_quant(args)
     if args.liar:
         return main_liar(args)
     if args.liar_mixed:
