@@ -1255,40 +1255,136 @@ void k_joint_mseg_quant_chunk(const MSegK p) {
 
 
 // -------------------------------------------------------------- wide groups
-// 17 to TPE_JOINT_WIDE_MAX_DIMS continuous coordinates (include/tpe_hip.h "Wide
-// joint stage").  A lane cannot hold 4 x 64 coordinates, and 64 inlined copies
-// of the sampler cannot be unrolled, so the work is split:
-// k_joint_wide_sample  one thread per (id, candidate): k_joint_chunk's draw, word
-//                for word, in a loop over d that is not unrolled.  Block b of an
-//                id (256 consecutive candidates) writes zbuf[(id * nblk + b)]
-//                [d][256]: thread t stores at d * 256 + t, a coalesced store.
+// 17 to TPE_JOINT_WIDE_MAX_DIMS coordinates (include/tpe_hip.h "Wide joint
+// stage", "Wide mixed joint stage", "Wide quantised joint stage"): Dc continuous
+// ones, then Dk <= TPE_JOINT_WIDE_MAX_CAT discrete and Dq <= TPE_JOINT_MAX_QUANT
+// quantised ones -- the models, tables (k_joint_qtable) and draws of the narrow
+// stages.  A lane cannot hold 4 x 64 coordinates, and 64 inlined copies of the
+// sampler cannot be unrolled, so the work is split:
+// k_joint_wide_sample / _mixed_sample / _quant_sample  one thread per (id,
+//                candidate): k_joint_chunk's / k_joint_mixed_chunk's /
+//                k_joint_quant_chunk's draw, word for word (word 1 + j serves
+//                kernel coordinate j), in loops that are not unrolled.  Block b
+//                of an id (256 consecutive candidates) writes zbuf[(id * nblk +
+//                b)][D][256], D = Dc + Dk + Dq: thread t stores at d * 256 + t, a
+//                coalesced store.  A category and a lattice index are f32.
 // k_joint_wide_chunk<DP, R>  one workgroup per (id, chunk of 256 R candidates):
 //                loads R candidates' z[DP] per lane from zbuf (coalesced) or
 //                from `inject`, every index a compile-time constant, and scores
 //                them as k_joint_chunk does.  A tile row is read four dimensions
 //                at a time (16-byte broadcast reads of mu and a).
-// k_joint_wide_merge  k_joint_merge on the wide record.
+// k_joint_wide_mixed_chunk<DP, KP, R>  the same with KP category slots a
+//                candidate: the component tile also holds cat[KP], a discrete
+//                slot costs one compare, one select and one add per (candidate,
+//                component), and sum_d miss_d(v_d) is added in f64 at the end.
+// k_joint_wide_quant_chunk<DP, KP, QP, R>  the same with QP lattice slots a
+//                candidate (KP = 0: no discrete slot).  The side's table streams
+//                through a dynamic LDS tile beside the rows, laid out [lattice
+//                value][component] as in k_joint_quant_chunk (stride tile + 4: 16
+//                lanes with 16 consecutive values read 16 different bank quads);
+//                rows and table share ONE tile length, the longest that keeps the
+//                table tile inside kWQTileBytes (and at most wide_tile(DP)).
+//                Components are taken four at a time (one 16-byte table read per
+//                candidate and quantised slot); the tile's tail is padded with
+//                c = -3e38.
+// k_joint_wide_merge  k_joint_merge on the wide record; it serves all three.
+// The kernels are their arguments, their LDS and calls into the parts below;
+// each part exists once.  A count of 0 slots (KP, QP) means "none": arrays of a
+// slot kind then have one unused entry (slots()).
 constexpr int kWD = TPE_JOINT_WIDE_MAX_DIMS;
+constexpr int kWK = TPE_JOINT_WIDE_MAX_CAT;
+constexpr int kWQ = TPE_JOINT_MAX_QUANT;
 static_assert(sizeof(tpe_joint_wide_record) == 24 + 8 * kWD, "layout");
 
 // components per LDS tile: at most 32 KiB of rows, so four workgroups fit a CU's 160 KiB
 constexpr int wide_tile(int DP) { return DP <= 32 ? 128 : ((4096 / DP) & ~7); }
 constexpr int wide_r(int DP) { return DP <= 32 ? 2 : 1; }
+constexpr int slots(int P) { return P > 0 ? P : 1; }
 
-struct WideK {
-  int D, C, n_chunks, nblk, inject;
-  int kb, ka;
-  uint32_t cand_base;               // as JointK: the record index only (the draws are k_joint_wide_sample's)
-  const float *bmu, *ba, *bc, *amu, *aa, *ac;
-  double bbase, abase;
-  const float* zsrc;                // inject: [C][D]; else zbuf [n_ids * nblk][D][256]
-  float* cand;
-  double *l_out, *g_out;
-  tpe_joint_wide_record* chunk_rec; // scratch [n_ids * n_chunks]
+// rows (<= 32 KiB) + cats (<= 4 KiB) + c + the quantised stage's table tile stay
+// under 64 KiB: no launch attribute is needed, and two workgroups fit a CU's 160 KiB.
+constexpr int kWQTileBytes = 26 * 1024;
+
+// the common tile length of a group with `total` lattice values: a multiple of 8
+// components, at most tk; 8 at the least ((512 + 1) * 12 * 4 B = 24 KiB fits)
+__host__ __device__ __forceinline__ int wide_quant_tile(int total, int tk) {
+  int tile = 8;
+  for (int t = tk; t >= 8; t -= 8)
+    if ((int64_t)(total + 1) * (t + 4) * (int64_t)sizeof(float) <= kWQTileBytes) { tile = t; break; }
+  return tile;
+}
+static_assert((int64_t)(TPE_JOINT_MAX_LATTICE_TOTAL + 1) * 12 * sizeof(float) <= kWQTileBytes, "the shortest tile fits");
+
+// the workgroup's best of every lane's pick: the waves' winners meet in slot[4]
+__device__ __forceinline__ Pick block_best(Pick best, Pick* __restrict__ slot) {
+  const int t = threadIdx.x;
+  Pick w = wave_best(best);
+  if ((t & 63) == 0) slot[t >> 6] = w;
+  __syncthreads();
+  w = slot[0];
+#pragma unroll
+  for (int q = 1; q < kThreads / 64; ++q)
+    if (beats(slot[q], w)) w = slot[q];
+  return w;
+}
+
+// ---- the steps the wide samplers and scoring loops are made of (the narrow
+// stages above carry the same steps written out: their code generation is pinned)
+// One candidate's Philox stream: block b of it holds the words 4 b .. 4 b + 3.
+struct Stream {
+  uint32_t gi, stream_word, c3, key0, key1;   // gi: the candidate's global index; c3: the new id's low word
 };
+__device__ __forceinline__ U4 stream_block(const Stream& q, uint32_t b) {
+  return philox4x32_10(q.gi, b, q.stream_word, q.c3, q.key0, q.key1);
+}
+// Word 0 picks the candidate's component of the below mixture: w becomes block
+// 0 of the stream, the result is the first k with us < cum[k].
+__device__ __forceinline__ int draw_component(const Stream& q, U4& w, const double* cum, int kb) {
+  w = stream_block(q, 0u);
+  const double us = u01w(w.x);
+  int lo = 0, hi = kb - 1;
+  while (lo < hi) { const int mid = (lo + hi) >> 1; if (us < cum[mid]) hi = mid; else lo = mid + 1; }
+  return lo;
+}
+// Word 1 + j serves kernel coordinate j (w: the block drawn last; the
+// coordinates are visited in ascending order).
+__device__ __forceinline__ uint32_t coord_word(const Stream& q, U4& w, int j) {
+  const int wi = j + 1;
+  if ((wi & 3) == 0) w = stream_block(q, (uint32_t)(wi >> 2));
+  return (wi & 3) == 0 ? w.x : (wi & 3) == 1 ? w.y : (wi & 3) == 2 ? w.z : w.w;
+}
+// One continuous coordinate from its 5-float sampler row (mu, sigma, the two
+// ends of the truncated uniform, the tail's sign), kept in [lo, hi]: low <= z < high.
+__device__ __forceinline__ float draw_continuous(const float* sr, uint32_t word, float lo, float hi) {
+  const float pr = sr[2] + u01f(word) * (sr[3] - sr[2]);
+  float zz = ndtri_f32(pr);
+  if (sr[4] != 0.f) zz = -zz;
+  float x = sr[0] + sr[1] * zz;
+  if (!(x == x)) x = sr[0];
+  return fminf(fmaxf(x, lo), hi);
+}
+// The lattice index of a drawn quantised coordinate: how many of the interior
+// edges e_1 .. e_{V-1} (e points at e_1) are <= z.
+__device__ __forceinline__ int lattice_index(const double* e, int V, float z) {
+  const double zd = (double)z;
+  int a = 0, b = V - 1;
+  while (a < b) { const int mid = (a + b) >> 1; if (e[mid] <= zd) a = mid + 1; else b = mid; }
+  return a;
+}
+// One component's term t joins the running sum: s accumulates 2^(term - m) with
+// m the running maximum of the terms (one v_exp_f32).
+__device__ __forceinline__ void lse_step(float t, float& m, float& s) {
+  const float dl = t - m;
+  const float e2 = __builtin_amdgcn_exp2f(-__builtin_fabsf(dl));
+  s = dl > 0.f ? __builtin_fmaf(s, e2, 1.f) : s + e2;
+  m = fmaxf(m, t);
+}
+// ... and log2 of the sum when the side is through
+__device__ __forceinline__ double lse_log2(float m, float s) { return (double)m + log2((double)s); }
 
+// The kernels' arguments: a stage's struct begins with the one of the stage it extends.
 struct WideSampK {
-  int D, C, nblk, kb;
+  int D, C, nblk, kb;               // D = Dc; a block of zbuf is [Dc + Dk + Dq][256]
   uint32_t key0, key1, stream_word;
   uint32_t cand_base;               // as JointK: the Philox word
   const double* cum;
@@ -1297,131 +1393,407 @@ struct WideSampK {
   float* zbuf;
   float lo[kWD], hi[kWD];
 };
+struct WideMixedSampK : WideSampK {
+  int Dk;
+  int U[kWK], off[kWK];
+  const float* bcat;
+  const double* bh;
+  const double* ccum;
+};
+struct WideQuantSampK : WideMixedSampK {
+  int Dq;
+  int V[kWQ], eoff[kWQ];
+  float qlo[kWQ], qhi[kWQ];
+  const double* edges;
+  const float* qsamp;
+};
 
-__global__ __launch_bounds__(kThreads) void k_joint_wide_sample(const WideSampK p) {
-  __shared__ float blo[kWD], bhi[kWD];          // (kernel-argument arrays: constant indices only)
-  const int t = threadIdx.x, D = p.D;
-  if (t == 0) {
+struct WideK {
+  int D, C, n_chunks, nblk, inject; // D = Dc; zsrc / cand rows are [Dc + Dk + Dq]
+  int kb, ka;
+  uint32_t cand_base;               // as JointK: the record index only (the draws are the sampling kernel's)
+  const float *bmu, *ba, *bc, *amu, *aa, *ac;
+  double bbase, abase;
+  const float* zsrc;                // inject: [C][D]; else zbuf [n_ids * nblk][D][256]
+  float* cand;
+  double *l_out, *g_out;
+  tpe_joint_wide_record* chunk_rec; // scratch [n_ids * n_chunks]
+};
+struct WideMixedK : WideK {
+  int Dk;
+  int U[kWK], off[kWK];
+  const float *bcat, *acat;
+  const float *bmiss, *bbonus, *amiss, *abonus;
+};
+struct WideQuantK : WideMixedK {
+  int Dq, tile, stride, total;      // components per tile, floats per lattice value in the tile, sum V_d
+  int V[kWQ], voff[kWQ];
+  const float *bT, *aT;             // [total][K] of a side
+};
+
+// ---- the samplers' parts.  Arguments that a loop indexes at run time are
+// staged in LDS by thread 0 (kernel-argument arrays: constant indices only).
+template <typename T, int N>
+__device__ __forceinline__ void stage(T (&lds)[N], const T (&arg)[N]) {
 #pragma unroll
-    for (int f = 0; f < kWD; ++f) { blo[f] = p.lo[f]; bhi[f] = p.hi[f]; }
-  }
-  __syncthreads();
+  for (int f = 0; f < N; ++f) lds[f] = arg[f];
+}
+
+// a sampler thread's candidate: its stream, its component, its column of zbuf
+struct WideDraw {
+  Stream st;
+  U4 w;
+  int comp;
+  float* out;                       // coordinate j goes to out[j * 256]
+};
+// false: the thread is past the last candidate.  D: all the group's coordinates.
+__device__ __forceinline__ bool wide_sample_head(const WideSampK& p, int D, WideDraw& c) {
+  const int t = threadIdx.x;
   const int id = blockIdx.x / p.nblk, blk = blockIdx.x % p.nblk;
   const int i = blk * kThreads + t;
-  if (i >= p.C) return;
-  float* out = p.zbuf + (int64_t)blockIdx.x * kThreads * D + t;
-  const uint32_t c3 = (uint32_t)p.ids[id], gi = p.cand_base + (uint32_t)i;   // gi < 2^31 (i < C)
-  U4 w = philox4x32_10(gi, 0u, p.stream_word, c3, p.key0, p.key1);
-  const double us = u01w(w.x);
-  int lo = 0, hi = p.kb - 1;               // first k with us < cum[k]
-  while (lo < hi) { const int mid = (lo + hi) >> 1; if (us < p.cum[mid]) hi = mid; else lo = mid + 1; }
-  const float* srow = p.samp + (int64_t)lo * D * 5;
-  // word 1 + d serves dimension d: k_joint_chunk's draw, operation for operation
+  if (i >= p.C) return false;
+  c.out = p.zbuf + (int64_t)blockIdx.x * kThreads * D + t;
+  c.st = Stream{p.cand_base + (uint32_t)i, p.stream_word, (uint32_t)p.ids[id], p.key0, p.key1};   // gi < 2^31 (i < C)
+  c.comp = draw_component(c.st, c.w, p.cum, p.kb);
+  return true;
+}
+// the Dc continuous coordinates: k_joint_chunk's draw, operation for operation
+__device__ __forceinline__ void wide_sample_continuous(const WideSampK& p, WideDraw& c, const float* blo,
+                                                       const float* bhi) {
+  const int Dc = p.D;
+  const float* srow = p.samp + (int64_t)c.comp * Dc * 5;
 #pragma unroll 1
-  for (int d = 0; d < D; ++d) {
-    const int wi = d + 1;
-    if ((wi & 3) == 0) w = philox4x32_10(gi, (uint32_t)(wi >> 2), p.stream_word, c3, p.key0, p.key1);
-    const uint32_t word = (wi & 3) == 0 ? w.x : (wi & 3) == 1 ? w.y : (wi & 3) == 2 ? w.z : w.w;
-    const float* sr = srow + d * 5;
-    const float pr = sr[2] + u01f(word) * (sr[3] - sr[2]);
-    float zz = ndtri_f32(pr);
-    if (sr[4] != 0.f) zz = -zz;
-    float x = sr[0] + sr[1] * zz;
-    if (!(x == x)) x = sr[0];
-    out[(int64_t)d * kThreads] = fminf(fmaxf(x, blo[d]), bhi[d]);      // low <= z < high
+  for (int d = 0; d < Dc; ++d) {
+    const uint32_t word = coord_word(c.st, c.w, d);
+    c.out[(int64_t)d * kThreads] = draw_continuous(srow + d * 5, word, blo[d], bhi[d]);
+  }
+}
+// the Dk categories as k_joint_mixed_chunk's sampler draws them: the category index as an f32
+__device__ __forceinline__ void wide_sample_categories(const WideMixedSampK& p, WideDraw& c, const int* cU,
+                                                       const int* coff) {
+  const int Dc = p.D, Dk = p.Dk;
+#pragma unroll 1
+  for (int d = 0; d < Dk; ++d) {
+    const double u = u01w(coord_word(c.st, c.w, Dc + d));
+    float x = p.bcat[(int64_t)c.comp * Dk + d];           // the component's category, -1: the prior row
+    const double h = x >= 0.f ? p.bh[d] : 0.0;
+    if (!(u < h)) {
+      const double u2 = (u - h) / (1.0 - h);
+      const double* cum = p.ccum + coff[d];
+      int a = 0, b = cU[d] - 1;                           // first category with u2 < cum[v]
+      while (a < b) { const int mid = (a + b) >> 1; if (u2 < cum[mid]) b = mid; else a = mid + 1; }
+      x = (float)a;
+    }
+    c.out[(int64_t)(Dc + d) * kThreads] = x;
+  }
+}
+// the Dq lattice indices as k_joint_quant_chunk's sampler draws them: the continuous
+// draw through the dimension's sampler row, binned; the lattice index as an f32
+__device__ __forceinline__ void wide_sample_lattice(const WideQuantSampK& p, WideDraw& c, const int* qV,
+                                                    const int* qeoff, const float* qlo, const float* qhi) {
+  const int Dq = p.Dq, first = p.D + p.Dk;
+#pragma unroll 1
+  for (int d = 0; d < Dq; ++d) {
+    const uint32_t word = coord_word(c.st, c.w, first + d);
+    const float x = draw_continuous(p.qsamp + ((int64_t)c.comp * Dq + d) * 5, word, qlo[d], qhi[d]);
+    c.out[(int64_t)(first + d) * kThreads] = (float)lattice_index(p.edges + qeoff[d] + 1, qV[d], x);
   }
 }
 
-// score_side for R candidates a lane; a row is read four dimensions at a time
-template <int DP, int R>
-__device__ __forceinline__ void score_side_wide(const float* __restrict__ mu, const float* __restrict__ a,
-                                                const float* __restrict__ c, int K, int D, const float (&z)[R][DP],
-                                                float* __restrict__ rows, float* __restrict__ cl, double (&out)[R]) {
-  constexpr int TK = wide_tile(DP);
-  float m[R], s[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) { m[r] = -3.0e38f; s[r] = 0.f; }
-  for (int k0 = 0; k0 < K; k0 += TK) {
-    const int nk = min(TK, K - k0);
-    __syncthreads();                       // the previous tile (or side) is read
-    for (int e = threadIdx.x; e < nk * DP; e += kThreads) {
-      const int kk = e / DP, d = e % DP;
-      const bool in = d < D;               // padded dimensions: a = 0 adds nothing
-      const int64_t src = (int64_t)(k0 + kk) * D + d;
-      rows[kk * 2 * DP + d] = in ? mu[src] : 0.f;
-      rows[kk * 2 * DP + DP + d] = in ? a[src] : 0.f;
-    }
-    for (int e = threadIdx.x; e < nk; e += kThreads) cl[e] = c[k0 + e];
-    __syncthreads();
-    for (int kk = 0; kk < nk; ++kk) {
-      const float4* row = reinterpret_cast<const float4*>(rows + kk * 2 * DP);
-      float acc[R];
-#pragma unroll
-      for (int r = 0; r < R; ++r) acc[r] = 0.f;
-#pragma unroll
-      for (int q = 0; q < DP / 4; ++q) {
-        const float4 rm = row[q], ra = row[DP / 4 + q];
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-          float u = (z[r][4 * q] - rm.x) * ra.x;
-          acc[r] = __builtin_fmaf(u, u, acc[r]);
-          u = (z[r][4 * q + 1] - rm.y) * ra.y;
-          acc[r] = __builtin_fmaf(u, u, acc[r]);
-          u = (z[r][4 * q + 2] - rm.z) * ra.z;
-          acc[r] = __builtin_fmaf(u, u, acc[r]);
-          u = (z[r][4 * q + 3] - rm.w) * ra.w;
-          acc[r] = __builtin_fmaf(u, u, acc[r]);
-        }
-      }
-      const float ck = cl[kk];
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        const float t = ck - acc[r];
-        const float dl = t - m[r];
-        const float e2 = __builtin_amdgcn_exp2f(-__builtin_fabsf(dl));
-        s[r] = dl > 0.f ? __builtin_fmaf(s[r], e2, 1.f) : s[r] + e2;
-        m[r] = fmaxf(m[r], t);
-      }
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < R; ++r) out[r] = (double)m[r] + log2((double)s[r]);
+__global__ __launch_bounds__(kThreads) void k_joint_wide_sample(const WideSampK p) {
+  __shared__ float blo[kWD], bhi[kWD];
+  if (threadIdx.x == 0) { stage(blo, p.lo); stage(bhi, p.hi); }
+  __syncthreads();
+  WideDraw c;
+  if (!wide_sample_head(p, p.D, c)) return;
+  wide_sample_continuous(p, c, blo, bhi);
 }
 
-template <int DP, int R>
-__global__ __launch_bounds__(kThreads) void k_joint_wide_chunk(const WideK p) {
-  static_assert(DP % 4 == 0 && DP <= kWD, "rows are read as float4");
-  constexpr int TK = wide_tile(DP);
-  __shared__ __attribute__((aligned(16))) float rows[TK * 2 * DP];
-  __shared__ float cl[TK];
-  __shared__ Pick slot[kThreads / 64];
-  const int t = threadIdx.x, D = p.D;
+__global__ __launch_bounds__(kThreads) void k_joint_wide_mixed_sample(const WideMixedSampK p) {
+  __shared__ float blo[kWD], bhi[kWD];
+  __shared__ int cU[kWK], coff[kWK];
+  if (threadIdx.x == 0) {
+    stage(blo, p.lo); stage(bhi, p.hi);
+    stage(cU, p.U); stage(coff, p.off);
+  }
+  __syncthreads();
+  WideDraw c;
+  if (!wide_sample_head(p, p.D + p.Dk, c)) return;
+  wide_sample_continuous(p, c, blo, bhi);
+  wide_sample_categories(p, c, cU, coff);
+}
+
+__global__ __launch_bounds__(kThreads) void k_joint_wide_quant_sample(const WideQuantSampK p) {
+  __shared__ float blo[kWD], bhi[kWD];
+  __shared__ int cU[kWK], coff[kWK];
+  __shared__ int qV[kWQ], qeoff[kWQ];
+  __shared__ float qlo[kWQ], qhi[kWQ];
+  if (threadIdx.x == 0) {
+    stage(blo, p.lo); stage(bhi, p.hi);
+    stage(cU, p.U); stage(coff, p.off);
+    stage(qV, p.V); stage(qeoff, p.eoff); stage(qlo, p.qlo); stage(qhi, p.qhi);
+  }
+  __syncthreads();
+  WideDraw c;
+  if (!wide_sample_head(p, p.D + p.Dk + p.Dq, c)) return;
+  wide_sample_continuous(p, c, blo, bhi);
+  wide_sample_categories(p, c, cU, coff);
+  wide_sample_lattice(p, c, qV, qeoff, qlo, qhi);
+}
+
+// ---- the scoring kernels' parts
+// A lane's R candidates: continuous coordinates, categories, lattice indices.
+template <int DP, int KP, int QP, int R>
+struct WideCand {
+  float z[R][DP], v[R][slots(KP)], x[R][slots(QP)];
+};
+
+// Zero, then the candidates first + r * 256 + t of this workgroup's id from
+// `inject` rows or from zbuf; every register index is a compile-time constant.
+template <int DP, int KP, int QP, int R>
+__device__ __forceinline__ void wide_load(const WideK& p, int Dk, int Dq, WideCand<DP, KP, QP, R>& c) {
+  const int t = threadIdx.x, Dc = p.D, D = Dc + Dk + Dq;
   const int id = blockIdx.x / p.n_chunks, chunk = blockIdx.x % p.n_chunks;
   const int first = chunk * (R * kThreads);
-
-  float z[R][DP];
 #pragma unroll
   for (int r = 0; r < R; ++r) {
 #pragma unroll
-    for (int d = 0; d < DP; ++d) z[r][d] = 0.f;
+    for (int d = 0; d < DP; ++d) c.z[r][d] = 0.f;
+#pragma unroll
+    for (int d = 0; d < slots(KP); ++d) c.v[r][d] = 0.f;
+#pragma unroll
+    for (int d = 0; d < slots(QP); ++d) c.x[r][d] = 0.f;
     const int i = first + r * kThreads + t;
     if (i >= p.C) continue;
     if (p.inject) {
+      const float* src = p.zsrc + (int64_t)i * D;
 #pragma unroll
       for (int d = 0; d < DP; ++d)
-        if (d < D) z[r][d] = p.zsrc[(int64_t)i * D + d];
+        if (d < Dc) c.z[r][d] = src[d];
+#pragma unroll
+      for (int d = 0; d < KP; ++d)
+        if (d < Dk) c.v[r][d] = src[Dc + d];
+#pragma unroll
+      for (int d = 0; d < QP; ++d)
+        if (d < Dq) c.x[r][d] = src[Dc + Dk + d];
     } else {
       // block chunk * R + r of this id (i < C: the block exists)
       const float* src = p.zsrc + ((int64_t)id * p.nblk + chunk * R + r) * kThreads * D + t;
 #pragma unroll
       for (int d = 0; d < DP; ++d)
-        if (d < D) z[r][d] = src[(int64_t)d * kThreads];
+        if (d < Dc) c.z[r][d] = src[(int64_t)d * kThreads];
+#pragma unroll
+      for (int d = 0; d < KP; ++d)
+        if (d < Dk) c.v[r][d] = src[(int64_t)(Dc + d) * kThreads];
+#pragma unroll
+      for (int d = 0; d < QP; ++d)
+        if (d < Dq) c.x[r][d] = src[(int64_t)(Dc + Dk + d) * kThreads];
     }
   }
+}
 
-  double l2[R], g2[R];
-  score_side_wide<DP, R>(p.bmu, p.ba, p.bc, p.kb, D, z, rows, cl, l2);
-  score_side_wide<DP, R>(p.amu, p.aa, p.ac, p.ka, D, z, rows, cl, g2);
+// The components [k0, k0 + nk) of a side into the tile: rows, cats (KP > 0) and
+// cl.  PAD4 (the quantised stage, which takes components four at a time): the
+// tile is filled up to a multiple of 4 with components that add nothing.
+template <int DP, int KP, bool PAD4>
+__device__ __forceinline__ void wide_fill_tile(const float* __restrict__ mu, const float* __restrict__ a,
+                                               const float* __restrict__ c, const float* __restrict__ cat, int k0,
+                                               int nk, int Dc, int Dk, float* __restrict__ rows,
+                                               float* __restrict__ cats, float* __restrict__ cl) {
+  const int nkp = PAD4 ? (nk + 3) & ~3 : nk;
+  for (int e = threadIdx.x; e < nkp * DP; e += kThreads) {
+    const int kk = e / DP, d = e % DP;
+    const bool in = d < Dc && (!PAD4 || kk < nk);   // padded dimensions (and components): a = 0 adds nothing
+    const int64_t src = (int64_t)(k0 + kk) * Dc + d;
+    rows[kk * 2 * DP + d] = in ? mu[src] : 0.f;
+    rows[kk * 2 * DP + DP + d] = in ? a[src] : 0.f;
+  }
+  if constexpr (KP > 0)
+    for (int e = threadIdx.x; e < nkp * KP; e += kThreads) {
+      const int kk = e / KP, d = e % KP;     // padded slots: category -1 never matches
+      cats[e] = (d < Dk && (!PAD4 || kk < nk)) ? cat[(int64_t)(k0 + kk) * Dk + d] : -1.f;
+    }
+  for (int e = threadIdx.x; e < nkp; e += kThreads) cl[e] = (!PAD4 || e < nk) ? c[k0 + e] : -3.0e38f;
+}
+
+// acc[r] = sum_d ((z_d - mu_d) a_d)^2 of tile row kk, read four dimensions at a
+// time: every lane reads the same 16 bytes, a broadcast
+template <int DP, int R>
+__device__ __forceinline__ void wide_row_product(const float* __restrict__ rows, int kk, const float (&z)[R][DP],
+                                                 float (&acc)[R]) {
+  const float4* row = reinterpret_cast<const float4*>(rows + kk * 2 * DP);
+#pragma unroll
+  for (int r = 0; r < R; ++r) acc[r] = 0.f;
+#pragma unroll
+  for (int q = 0; q < DP / 4; ++q) {
+    const float4 rm = row[q], ra = row[DP / 4 + q];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      float u = (z[r][4 * q] - rm.x) * ra.x;
+      acc[r] = __builtin_fmaf(u, u, acc[r]);
+      u = (z[r][4 * q + 1] - rm.y) * ra.y;
+      acc[r] = __builtin_fmaf(u, u, acc[r]);
+      u = (z[r][4 * q + 2] - rm.z) * ra.z;
+      acc[r] = __builtin_fmaf(u, u, acc[r]);
+      u = (z[r][4 * q + 3] - rm.w) * ra.w;
+      acc[r] = __builtin_fmaf(u, u, acc[r]);
+    }
+  }
+}
+
+// The category terms (score_side_mixed's discrete part): component kk's categories,
+// as 16-byte broadcasts where KP allows.
+template <int KP>
+__device__ __forceinline__ void wide_cat_row(const float* __restrict__ cats, int kk, float (&rc)[slots(KP)]) {
+  if constexpr (KP > 0 && KP % 4 == 0) {
+    const float4* cr = reinterpret_cast<const float4*>(cats + kk * KP);
+#pragma unroll
+    for (int q = 0; q < KP / 4; ++q) {
+      const float4 x = cr[q];
+      rc[4 * q] = x.x; rc[4 * q + 1] = x.y; rc[4 * q + 2] = x.z; rc[4 * q + 3] = x.w;
+    }
+  } else if constexpr (KP == 2) {
+    const float2 x = *reinterpret_cast<const float2*>(cats + kk * 2);
+    rc[0] = x.x; rc[1] = x.y;
+  } else if constexpr (KP == 1) {
+    rc[0] = cats[kk];
+  }
+}
+// (nb = -bonus_d(v_d), read once per candidate, the compare-add and the f64 sum of
+// miss_d(v_d) are a short loop each in the two score sides: as functions they
+// cost four quantised instantiations a wave of occupancy.)
+
+// score_side for R candidates a lane and KP category slots (0: none; cat, miss,
+// bonus and cats are not read): log2 of one side's mixture, + sum_d miss_d(v_d).
+template <int DP, int KP, int R>
+__device__ __forceinline__ void score_side_wide(const float* __restrict__ mu, const float* __restrict__ a,
+                                                const float* __restrict__ c, const float* __restrict__ cat,
+                                                const float* __restrict__ miss, const float* __restrict__ bonus,
+                                                int K, int Dc, int Dk, const int (&U)[slots(KP)],
+                                                const int (&off)[slots(KP)], const float (&z)[R][DP],
+                                                const float (&v)[R][slots(KP)], float* __restrict__ rows,
+                                                float* __restrict__ cats, float* __restrict__ cl, double (&out)[R]) {
+  constexpr int TK = wide_tile(DP);
+  float m[R], s[R], nb[R][slots(KP)];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    m[r] = -3.0e38f;
+    s[r] = 0.f;
+#pragma unroll
+    for (int d = 0; d < KP; ++d) nb[r][d] = d < Dk ? -bonus[off[d] + cat_index(v[r][d], U[d])] : 0.f;
+  }
+  for (int k0 = 0; k0 < K; k0 += TK) {
+    const int nk = min(TK, K - k0);
+    __syncthreads();                       // the previous tile (or side) is read
+    wide_fill_tile<DP, KP, false>(mu, a, c, cat, k0, nk, Dc, Dk, rows, cats, cl);
+    __syncthreads();
+    for (int kk = 0; kk < nk; ++kk) {
+      float acc[R], rc[slots(KP)];
+      wide_row_product<DP, R>(rows, kk, z, acc);
+      wide_cat_row<KP>(cats, kk, rc);
+      const float ck = cl[kk];
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+#pragma unroll
+        for (int d = 0; d < KP; ++d) acc[r] += v[r][d] == rc[d] ? nb[r][d] : 0.f;   // one compare, one select, one add
+        lse_step(ck - acc[r], m[r], s[r]);
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    out[r] = lse_log2(m[r], s[r]);
+    if constexpr (KP > 0) {
+      double M = 0.0;
+#pragma unroll
+      for (int d = 0; d < KP; ++d)
+        if (d < Dk) M += (double)miss[off[d] + cat_index(v[r][d], U[d])];
+      out[r] += M;
+    }
+  }
+}
+
+// score_side_wide with QP quantised slots (score_side_quant's table part).  qo: a
+// candidate's table row offsets in floats.  Its own component loop: four at a
+// time, the table tile in dynamic LDS.
+template <int DP, int KP, int QP, int R>
+__device__ __forceinline__ void score_side_wide_quant(const float* __restrict__ mu, const float* __restrict__ a,
+                                                      const float* __restrict__ c, const float* __restrict__ cat,
+                                                      const float* __restrict__ miss, const float* __restrict__ bonus,
+                                                      const float* __restrict__ T, int K, int Dc, int Dk, int tile,
+                                                      int stride, int total, const int (&U)[slots(KP)],
+                                                      const int (&off)[slots(KP)], const float (&z)[R][DP],
+                                                      const float (&v)[R][slots(KP)], const int (&qo)[R][QP],
+                                                      float* __restrict__ rows, float* __restrict__ cats,
+                                                      float* __restrict__ cl, float* __restrict__ qt,
+                                                      double (&out)[R]) {
+  float m[R], s[R], nb[R][slots(KP)];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    m[r] = -3.0e38f;
+    s[r] = 0.f;
+#pragma unroll
+    for (int d = 0; d < KP; ++d) nb[r][d] = d < Dk ? -bonus[off[d] + cat_index(v[r][d], U[d])] : 0.f;
+  }
+  for (int k0 = 0; k0 < K; k0 += tile) {
+    const int nk = min(tile, K - k0), nk4 = (nk + 3) & ~3;
+    __syncthreads();                       // the previous tile (or side) is read
+    wide_fill_tile<DP, KP, true>(mu, a, c, cat, k0, nk, Dc, Dk, rows, cats, cl);
+    for (int e = threadIdx.x; e < total * tile; e += kThreads) {
+      const int b = e / tile, kk = e - b * tile;           // a run over k of one lattice value: coalesced
+      if (kk < nk4) qt[b * stride + kk] = kk < nk ? T[(int64_t)b * K + k0 + kk] : 0.f;
+    }
+    __syncthreads();
+    for (int k4 = 0; k4 < nk4; k4 += 4) {
+      float tq[R][QP][4];
+#pragma unroll
+      for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int d = 0; d < QP; ++d) {
+          const float4 x = *reinterpret_cast<const float4*>(qt + qo[r][d] + k4);
+          tq[r][d][0] = x.x; tq[r][d][1] = x.y; tq[r][d][2] = x.z; tq[r][d][3] = x.w;
+        }
+      // (R = 1, the widths above 32: the four components are a loop, not four copies,
+      // which would hold their 4 x 2 DP row values at once and leave one wave a SIMD)
+#pragma unroll(R == 1 ? 1 : 4)
+      for (int j = 0; j < 4; ++j) {
+        const int kk = k4 + j;
+        float acc[R], rc[slots(KP)];
+        wide_row_product<DP, R>(rows, kk, z, acc);
+        wide_cat_row<KP>(cats, kk, rc);
+        const float ck = cl[kk];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+#pragma unroll
+          for (int d = 0; d < KP; ++d) acc[r] += v[r][d] == rc[d] ? nb[r][d] : 0.f;
+#pragma unroll
+          for (int d = 0; d < QP; ++d)   // (selects, not an indexed read: tq stays in registers in the looped form)
+            acc[r] -= j == 0 ? tq[r][d][0] : j == 1 ? tq[r][d][1] : j == 2 ? tq[r][d][2] : tq[r][d][3];
+          lse_step(ck - acc[r], m[r], s[r]);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    double M = 0.0;
+#pragma unroll
+    for (int d = 0; d < KP; ++d)
+      if (d < Dk) M += (double)miss[off[d] + cat_index(v[r][d], U[d])];
+    out[r] = lse_log2(m[r], s[r]) + M;
+  }
+}
+
+// What every scoring kernel ends with: l and g of the lane's candidates, the
+// optional outputs, the chunk's winner (the first of a tie) and its record.  The
+// coordinate order in cand and in the record's z: continuous, categories,
+// lattice indices, then zeros.
+template <int DP, int KP, int QP, int R>
+__device__ __forceinline__ void wide_finish(const WideK& p, int Dk, int Dq, const WideCand<DP, KP, QP, R>& c,
+                                            const double (&l2)[R], const double (&g2)[R], Pick* __restrict__ slot) {
+  const int t = threadIdx.x, Dc = p.D, D = Dc + Dk + Dq;
+  const int id = blockIdx.x / p.n_chunks, chunk = blockIdx.x % p.n_chunks;
+  const int first = chunk * (R * kThreads);
 
   Pick best{0, 0};
   double lv[R], gv[R];
@@ -1434,10 +1806,148 @@ __global__ __launch_bounds__(kThreads) void k_joint_wide_chunk(const WideK p) {
     const int64_t o = (int64_t)id * p.C + i;
     if (p.l_out) p.l_out[o] = lv[r];
     if (p.g_out) p.g_out[o] = gv[r];
-    if (p.cand)
+    if (p.cand) {
 #pragma unroll
       for (int d = 0; d < DP; ++d)
-        if (d < D) p.cand[o * D + d] = z[r][d];
+        if (d < Dc) p.cand[o * D + d] = c.z[r][d];
+#pragma unroll
+      for (int d = 0; d < KP; ++d)
+        if (d < Dk) p.cand[o * D + Dc + d] = c.v[r][d];
+#pragma unroll
+      for (int d = 0; d < QP; ++d)
+        if (d < Dq) p.cand[o * D + Dc + Dk + d] = c.x[r][d];
+    }
+    const uint64_t key = score_key(lv[r] - gv[r]);
+    if (key > best.key) best = Pick{key, (int64_t)i};   // ascending index: strict > keeps the first of a tie
+  }
+  const Pick w = block_best(best, slot);
+
+  tpe_joint_wide_record* rec = p.chunk_rec + blockIdx.x;
+  if (w.key == 0) {
+    if (t == 0) rec->global_idx = -1;
+    return;
+  }
+  const int woff = (int)(w.idx - first);
+  if (t != woff % kThreads) return;
+  const int wr = woff / kThreads;
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    if (r != wr) continue;
+    rec->global_idx = w.idx + (int64_t)p.cand_base;
+    rec->l = lv[r];
+    rec->g = gv[r];
+    if constexpr (KP == 0 && QP == 0) {     // continuous alone: the padded slots hold zeros, no compare against D
+#pragma unroll
+      for (int d = 0; d < kWD; ++d) rec->z[d] = d < DP ? (double)c.z[r][d < DP ? d : 0] : 0.0;
+    } else {
+#pragma unroll
+      for (int d = 0; d < kWD; ++d)
+        if (d >= D) rec->z[d] = 0.0;
+#pragma unroll
+      for (int d = 0; d < DP; ++d)
+        if (d < Dc) rec->z[d] = (double)c.z[r][d];
+#pragma unroll
+      for (int d = 0; d < KP; ++d)
+        if (d < Dk) rec->z[Dc + d] = (double)c.v[r][d];
+#pragma unroll
+      for (int d = 0; d < QP; ++d)
+        if (d < Dq) rec->z[Dc + Dk + d] = (double)c.x[r][d];
+    }
+  }
+}
+
+template <int DP, int R>
+__global__ __launch_bounds__(kThreads) void k_joint_wide_chunk(const WideK p) {
+  static_assert(DP % 4 == 0 && DP <= kWD, "rows are read as float4");
+  constexpr int TK = wide_tile(DP);
+  __shared__ __attribute__((aligned(16))) float rows[TK * 2 * DP];
+  __shared__ float cl[TK];
+  __shared__ Pick slot[kThreads / 64];
+  const int none[1] = {0};
+
+  WideCand<DP, 0, 0, R> c;
+  wide_load(p, 0, 0, c);
+  double l2[R], g2[R];
+  score_side_wide<DP, 0, R>(p.bmu, p.ba, p.bc, nullptr, nullptr, nullptr, p.kb, p.D, 0, none, none, c.z, c.v, rows,
+                            nullptr, cl, l2);
+  score_side_wide<DP, 0, R>(p.amu, p.aa, p.ac, nullptr, nullptr, nullptr, p.ka, p.D, 0, none, none, c.z, c.v, rows,
+                            nullptr, cl, g2);
+  wide_finish(p, 0, 0, c, l2, g2, slot);
+}
+
+// (This kernel carries wide_load and wide_finish written out, KP slots and no
+// lattice slot: through the shared functions <20, 2, 2> needs 130 VGPRs for 124
+// and drops from 4 waves a SIMD to 3.  A change to either part is made here too.)
+template <int DP, int KP, int R>
+__global__ __launch_bounds__(kThreads) void k_joint_wide_mixed_chunk(const WideMixedK p) {
+  static_assert(DP % 4 == 0 && DP <= kWD && KP <= kWK, "rows are read as float4; the argument arrays");
+  constexpr int TK = wide_tile(DP);
+  // at most 128 * (64 + 8) * 4 B = 36 KiB of tile: four workgroups fit a CU's 160 KiB
+  __shared__ __attribute__((aligned(16))) float rows[TK * 2 * DP];
+  __shared__ __attribute__((aligned(16))) float cats[TK * KP];
+  __shared__ float cl[TK];
+  __shared__ Pick slot[kThreads / 64];
+  const int t = threadIdx.x, Dc = p.D, Dk = p.Dk, D = Dc + Dk;
+  const int id = blockIdx.x / p.n_chunks, chunk = blockIdx.x % p.n_chunks;
+  const int first = chunk * (R * kThreads);
+  int U[KP], off[KP];                      // (kernel-argument arrays: constant indices only)
+#pragma unroll
+  for (int d = 0; d < KP; ++d) { U[d] = p.U[d]; off[d] = p.off[d]; }
+
+  float z[R][DP], v[R][KP];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+#pragma unroll
+    for (int d = 0; d < DP; ++d) z[r][d] = 0.f;
+#pragma unroll
+    for (int d = 0; d < KP; ++d) v[r][d] = 0.f;
+    const int i = first + r * kThreads + t;
+    if (i >= p.C) continue;
+    if (p.inject) {
+      const float* src = p.zsrc + (int64_t)i * D;
+#pragma unroll
+      for (int d = 0; d < DP; ++d)
+        if (d < Dc) z[r][d] = src[d];
+#pragma unroll
+      for (int d = 0; d < KP; ++d)
+        if (d < Dk) v[r][d] = src[Dc + d];
+    } else {
+      // block chunk * R + r of this id (i < C: the block exists)
+      const float* src = p.zsrc + ((int64_t)id * p.nblk + chunk * R + r) * kThreads * D + t;
+#pragma unroll
+      for (int d = 0; d < DP; ++d)
+        if (d < Dc) z[r][d] = src[(int64_t)d * kThreads];
+#pragma unroll
+      for (int d = 0; d < KP; ++d)
+        if (d < Dk) v[r][d] = src[(int64_t)(Dc + d) * kThreads];
+    }
+  }
+
+  double l2[R], g2[R];
+  score_side_wide<DP, KP, R>(p.bmu, p.ba, p.bc, p.bcat, p.bmiss, p.bbonus, p.kb, Dc, Dk, U, off, z, v, rows, cats, cl,
+                             l2);
+  score_side_wide<DP, KP, R>(p.amu, p.aa, p.ac, p.acat, p.amiss, p.abonus, p.ka, Dc, Dk, U, off, z, v, rows, cats, cl,
+                             g2);
+
+  Pick best{0, 0};
+  double lv[R], gv[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int i = first + r * kThreads + t;
+    lv[r] = l2[r] * kLn2 + p.bbase;
+    gv[r] = g2[r] * kLn2 + p.abase;
+    if (i >= p.C) continue;
+    const int64_t o = (int64_t)id * p.C + i;
+    if (p.l_out) p.l_out[o] = lv[r];
+    if (p.g_out) p.g_out[o] = gv[r];
+    if (p.cand) {
+#pragma unroll
+      for (int d = 0; d < DP; ++d)
+        if (d < Dc) p.cand[o * D + d] = z[r][d];
+#pragma unroll
+      for (int d = 0; d < KP; ++d)
+        if (d < Dk) p.cand[o * D + Dc + d] = v[r][d];
+    }
     const uint64_t key = score_key(lv[r] - gv[r]);
     if (key > best.key) best = Pick{key, (int64_t)i};   // ascending index: strict > keeps the first of a tie
   }
@@ -1454,18 +1964,63 @@ __global__ __launch_bounds__(kThreads) void k_joint_wide_chunk(const WideK p) {
     if (t == 0) rec->global_idx = -1;
     return;
   }
-  const int off = (int)(w.idx - first);
-  if (t != off % kThreads) return;
-  const int wr = off / kThreads;
+  const int woff = (int)(w.idx - first);
+  if (t != woff % kThreads) return;
+  const int wr = woff / kThreads;
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     if (r != wr) continue;
     rec->global_idx = w.idx + (int64_t)p.cand_base;
     rec->l = lv[r];
     rec->g = gv[r];
+    // kernel coordinate order: the Dc continuous entries, the categories, then zeros
 #pragma unroll
-    for (int d = 0; d < kWD; ++d) rec->z[d] = d < DP ? (double)z[r][d < DP ? d : 0] : 0.0;
+    for (int d = 0; d < kWD; ++d)
+      if (d >= D) rec->z[d] = 0.0;
+#pragma unroll
+    for (int d = 0; d < DP; ++d)
+      if (d < Dc) rec->z[d] = (double)z[r][d];
+#pragma unroll
+    for (int d = 0; d < KP; ++d)
+      if (d < Dk) rec->z[Dc + d] = (double)v[r][d];
   }
+}
+
+template <int DP, int KP, int QP, int R>
+__global__ __launch_bounds__(kThreads) void k_joint_wide_quant_chunk(const WideQuantK p) {
+  static_assert(DP % 4 == 0 && DP <= kWD && KP <= kWK && QP >= 1 && QP <= kWQ,
+                "rows are read as float4; the argument arrays");
+  constexpr int TK = wide_tile(DP);
+  __shared__ __attribute__((aligned(16))) float rows[TK * 2 * DP];
+  __shared__ __attribute__((aligned(16))) float cats[TK * slots(KP)];
+  __shared__ float cl[TK];
+  __shared__ Pick slot[kThreads / 64];
+  extern __shared__ __attribute__((aligned(16))) float qt[];     // [(total + 1) * stride]
+  static_assert(sizeof(float) * (TK * 2 * DP + TK * slots(KP) + TK) + sizeof(Pick) * (kThreads / 64) + kWQTileBytes <=
+                    64 * 1024, "static and dynamic LDS of a workgroup stay under 64 KiB");
+  int U[slots(KP)], off[slots(KP)];        // (kernel-argument arrays: constant indices only)
+  U[0] = 1; off[0] = 0;
+#pragma unroll
+  for (int d = 0; d < KP; ++d) { U[d] = p.U[d]; off[d] = p.off[d]; }
+
+  for (int e = threadIdx.x; e < p.stride; e += kThreads) qt[p.total * p.stride + e] = 0.f;   // the padded slots' row
+
+  WideCand<DP, KP, QP, R> c;
+  wide_load(p, p.Dk, p.Dq, c);
+  // the lattice value's row in the tile (kept inside the table); a padded slot reads the zero row
+  int qo[R][QP];
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+#pragma unroll
+    for (int d = 0; d < QP; ++d)
+      qo[r][d] = (d < p.Dq ? p.voff[d] + cat_index(c.x[r][d], p.V[d]) : p.total) * p.stride;
+
+  double l2[R], g2[R];
+  score_side_wide_quant<DP, KP, QP, R>(p.bmu, p.ba, p.bc, p.bcat, p.bmiss, p.bbonus, p.bT, p.kb, p.D, p.Dk, p.tile,
+                                       p.stride, p.total, U, off, c.z, c.v, qo, rows, cats, cl, qt, l2);
+  score_side_wide_quant<DP, KP, QP, R>(p.amu, p.aa, p.ac, p.acat, p.amiss, p.abonus, p.aT, p.ka, p.D, p.Dk, p.tile,
+                                       p.stride, p.total, U, off, c.z, c.v, qo, rows, cats, cl, qt, g2);
+  wide_finish(p, p.Dk, p.Dq, c, l2, g2, slot);
 }
 
 __global__ __launch_bounds__(64) void k_joint_wide_merge(const tpe_joint_wide_record* __restrict__ chunk_rec,
@@ -1486,683 +2041,6 @@ __global__ __launch_bounds__(64) void k_joint_wide_merge(const tpe_joint_wide_re
     for (int d = 0; d < kWD; ++d) out->z[d] = 0.0;
   } else {
     *out = rec[w.idx];
-  }
-}
-
-// ------------------------------------------ discrete labels in wide groups
-// Dc continuous coordinates followed by Dk <= TPE_JOINT_WIDE_MAX_CAT discrete
-// ones, Dc + Dk <= TPE_JOINT_WIDE_MAX_DIMS (include/tpe_hip.h "Wide mixed joint
-// stage"): the model and the draws of the mixed stage, the data movement of the
-// wide one.
-// k_joint_wide_mixed_sample  k_joint_wide_sample, then the Dk categories as
-//                k_joint_mixed_chunk's sampler draws them (word 1 + j serves
-//                kernel coordinate j); a block of zbuf is [Dc + Dk][256].
-// k_joint_wide_mixed_chunk<DP, KP, R>  k_joint_wide_chunk with KP category slots
-//                a candidate: the component tile also holds cat[KP], a discrete
-//                slot costs one compare, one select and one add per (candidate,
-//                component), and sum_d miss_d(v_d) is added in f64 at the end.
-// k_joint_wide_merge serves it unchanged.
-constexpr int kWK = TPE_JOINT_WIDE_MAX_CAT;
-
-struct WideMixedSampK {
-  WideSampK s;                      // s.D = Dc; a block of zbuf is [Dc + Dk][256]
-  int Dk;
-  int U[kWK], off[kWK];
-  const float* bcat;
-  const double* bh;
-  const double* ccum;
-};
-
-struct WideMixedK {
-  WideK w;                          // w.D = Dc; zsrc / cand rows are [Dc + Dk]
-  int Dk;
-  int U[kWK], off[kWK];
-  const float *bcat, *acat;
-  const float *bmiss, *bbonus, *amiss, *abonus;
-};
-
-__global__ __launch_bounds__(kThreads) void k_joint_wide_mixed_sample(const WideMixedSampK p) {
-  __shared__ float blo[kWD], bhi[kWD];          // (kernel-argument arrays: constant indices only)
-  __shared__ int cU[kWK], coff[kWK];
-  const int t = threadIdx.x, Dc = p.s.D, Dk = p.Dk, D = Dc + Dk;
-  if (t == 0) {
-#pragma unroll
-    for (int f = 0; f < kWD; ++f) { blo[f] = p.s.lo[f]; bhi[f] = p.s.hi[f]; }
-#pragma unroll
-    for (int f = 0; f < kWK; ++f) { cU[f] = p.U[f]; coff[f] = p.off[f]; }
-  }
-  __syncthreads();
-  const int id = blockIdx.x / p.s.nblk, blk = blockIdx.x % p.s.nblk;
-  const int i = blk * kThreads + t;
-  if (i >= p.s.C) return;
-  float* out = p.s.zbuf + (int64_t)blockIdx.x * kThreads * D + t;
-  const uint32_t c3 = (uint32_t)p.s.ids[id], gi = p.s.cand_base + (uint32_t)i;   // gi < 2^31 (i < C)
-  U4 w = philox4x32_10(gi, 0u, p.s.stream_word, c3, p.s.key0, p.s.key1);
-  const double us = u01w(w.x);
-  int lo = 0, hi = p.s.kb - 1;             // first k with us < cum[k]
-  while (lo < hi) { const int mid = (lo + hi) >> 1; if (us < p.s.cum[mid]) hi = mid; else lo = mid + 1; }
-  const int comp = lo;
-  const float* srow = p.s.samp + (int64_t)comp * Dc * 5;
-  // word 1 + j serves kernel coordinate j; a continuous one is k_joint_wide_sample's draw
-#pragma unroll 1
-  for (int d = 0; d < Dc; ++d) {
-    const int wi = d + 1;
-    if ((wi & 3) == 0) w = philox4x32_10(gi, (uint32_t)(wi >> 2), p.s.stream_word, c3, p.s.key0, p.s.key1);
-    const uint32_t word = (wi & 3) == 0 ? w.x : (wi & 3) == 1 ? w.y : (wi & 3) == 2 ? w.z : w.w;
-    const float* sr = srow + d * 5;
-    const float pr = sr[2] + u01f(word) * (sr[3] - sr[2]);
-    float zz = ndtri_f32(pr);
-    if (sr[4] != 0.f) zz = -zz;
-    float x = sr[0] + sr[1] * zz;
-    if (!(x == x)) x = sr[0];
-    out[(int64_t)d * kThreads] = fminf(fmaxf(x, blo[d]), bhi[d]);      // low <= z < high
-  }
-  // ... a discrete one k_joint_mixed_chunk's: the category index as an f32
-#pragma unroll 1
-  for (int d = 0; d < Dk; ++d) {
-    const int wi = Dc + d + 1;
-    if ((wi & 3) == 0) w = philox4x32_10(gi, (uint32_t)(wi >> 2), p.s.stream_word, c3, p.s.key0, p.s.key1);
-    const uint32_t word = (wi & 3) == 0 ? w.x : (wi & 3) == 1 ? w.y : (wi & 3) == 2 ? w.z : w.w;
-    const double u = u01w(word);
-    float x = p.bcat[(int64_t)comp * Dk + d];             // the component's category, -1: the prior row
-    const double h = x >= 0.f ? p.bh[d] : 0.0;
-    if (!(u < h)) {
-      const double u2 = (u - h) / (1.0 - h);
-      const double* cum = p.ccum + coff[d];
-      int a = 0, b = cU[d] - 1;                           // first category with u2 < cum[v]
-      while (a < b) { const int mid = (a + b) >> 1; if (u2 < cum[mid]) b = mid; else a = mid + 1; }
-      x = (float)a;
-    }
-    out[(int64_t)(Dc + d) * kThreads] = x;
-  }
-}
-
-// score_side_wide with KP discrete slots (score_side_mixed's discrete part): the
-// tile holds a component's categories beside its rows, read as 16-byte
-// broadcasts where KP allows; out gets + sum_d miss_d(v_d) in f64.
-template <int DP, int KP, int R>
-__device__ __forceinline__ void score_side_wide_mixed(const float* __restrict__ mu, const float* __restrict__ a,
-                                                      const float* __restrict__ c, const float* __restrict__ cat,
-                                                      const float* __restrict__ miss, const float* __restrict__ bonus,
-                                                      int K, int Dc, int Dk, const int (&U)[KP], const int (&off)[KP],
-                                                      const float (&z)[R][DP], const float (&v)[R][KP],
-                                                      float* __restrict__ rows, float* __restrict__ cats,
-                                                      float* __restrict__ cl, double (&out)[R]) {
-  constexpr int TK = wide_tile(DP);
-  float m[R], s[R], nb[R][KP];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    m[r] = -3.0e38f;
-    s[r] = 0.f;
-#pragma unroll
-    for (int d = 0; d < KP; ++d) nb[r][d] = d < Dk ? -bonus[off[d] + cat_index(v[r][d], U[d])] : 0.f;
-  }
-  for (int k0 = 0; k0 < K; k0 += TK) {
-    const int nk = min(TK, K - k0);
-    __syncthreads();                       // the previous tile (or side) is read
-    for (int e = threadIdx.x; e < nk * DP; e += kThreads) {
-      const int kk = e / DP, d = e % DP;
-      const bool in = d < Dc;              // padded dimensions: a = 0 adds nothing
-      const int64_t src = (int64_t)(k0 + kk) * Dc + d;
-      rows[kk * 2 * DP + d] = in ? mu[src] : 0.f;
-      rows[kk * 2 * DP + DP + d] = in ? a[src] : 0.f;
-    }
-    for (int e = threadIdx.x; e < nk * KP; e += kThreads) {
-      const int kk = e / KP, d = e % KP;   // padded slots: category -1 never matches
-      cats[e] = d < Dk ? cat[(int64_t)(k0 + kk) * Dk + d] : -1.f;
-    }
-    for (int e = threadIdx.x; e < nk; e += kThreads) cl[e] = c[k0 + e];
-    __syncthreads();
-    for (int kk = 0; kk < nk; ++kk) {
-      const float4* row = reinterpret_cast<const float4*>(rows + kk * 2 * DP);
-      float acc[R];
-#pragma unroll
-      for (int r = 0; r < R; ++r) acc[r] = 0.f;
-#pragma unroll
-      for (int q = 0; q < DP / 4; ++q) {
-        const float4 rm = row[q], ra = row[DP / 4 + q];
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-          float u = (z[r][4 * q] - rm.x) * ra.x;
-          acc[r] = __builtin_fmaf(u, u, acc[r]);
-          u = (z[r][4 * q + 1] - rm.y) * ra.y;
-          acc[r] = __builtin_fmaf(u, u, acc[r]);
-          u = (z[r][4 * q + 2] - rm.z) * ra.z;
-          acc[r] = __builtin_fmaf(u, u, acc[r]);
-          u = (z[r][4 * q + 3] - rm.w) * ra.w;
-          acc[r] = __builtin_fmaf(u, u, acc[r]);
-        }
-      }
-      float rc[KP];
-      if constexpr (KP % 4 == 0) {
-        const float4* cr = reinterpret_cast<const float4*>(cats + kk * KP);
-#pragma unroll
-        for (int q = 0; q < KP / 4; ++q) {
-          const float4 x = cr[q];
-          rc[4 * q] = x.x; rc[4 * q + 1] = x.y; rc[4 * q + 2] = x.z; rc[4 * q + 3] = x.w;
-        }
-      } else if constexpr (KP == 2) {
-        const float2 x = *reinterpret_cast<const float2*>(cats + kk * 2);
-        rc[0] = x.x; rc[1] = x.y;
-      } else {
-        rc[0] = cats[kk];
-      }
-      const float ck = cl[kk];
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-#pragma unroll
-        for (int d = 0; d < KP; ++d) acc[r] += v[r][d] == rc[d] ? nb[r][d] : 0.f;
-        const float t = ck - acc[r];
-        const float dl = t - m[r];
-        const float e2 = __builtin_amdgcn_exp2f(-__builtin_fabsf(dl));
-        s[r] = dl > 0.f ? __builtin_fmaf(s[r], e2, 1.f) : s[r] + e2;
-        m[r] = fmaxf(m[r], t);
-      }
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    double M = 0.0;
-#pragma unroll
-    for (int d = 0; d < KP; ++d)
-      if (d < Dk) M += (double)miss[off[d] + cat_index(v[r][d], U[d])];
-    out[r] = (double)m[r] + log2((double)s[r]) + M;
-  }
-}
-
-template <int DP, int KP, int R>
-__global__ __launch_bounds__(kThreads) void k_joint_wide_mixed_chunk(const WideMixedK p) {
-  static_assert(DP % 4 == 0 && DP <= kWD && KP <= kWK, "rows are read as float4; the argument arrays");
-  constexpr int TK = wide_tile(DP);
-  // at most 128 * (64 + 8) * 4 B = 36 KiB of tile: four workgroups fit a CU's 160 KiB
-  __shared__ __attribute__((aligned(16))) float rows[TK * 2 * DP];
-  __shared__ __attribute__((aligned(16))) float cats[TK * KP];
-  __shared__ float cl[TK];
-  __shared__ Pick slot[kThreads / 64];
-  const int t = threadIdx.x, Dc = p.w.D, Dk = p.Dk, D = Dc + Dk;
-  const int id = blockIdx.x / p.w.n_chunks, chunk = blockIdx.x % p.w.n_chunks;
-  const int first = chunk * (R * kThreads);
-  int U[KP], off[KP];                      // (kernel-argument arrays: constant indices only)
-#pragma unroll
-  for (int d = 0; d < KP; ++d) { U[d] = p.U[d]; off[d] = p.off[d]; }
-
-  float z[R][DP], v[R][KP];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-#pragma unroll
-    for (int d = 0; d < DP; ++d) z[r][d] = 0.f;
-#pragma unroll
-    for (int d = 0; d < KP; ++d) v[r][d] = 0.f;
-    const int i = first + r * kThreads + t;
-    if (i >= p.w.C) continue;
-    if (p.w.inject) {
-      const float* src = p.w.zsrc + (int64_t)i * D;
-#pragma unroll
-      for (int d = 0; d < DP; ++d)
-        if (d < Dc) z[r][d] = src[d];
-#pragma unroll
-      for (int d = 0; d < KP; ++d)
-        if (d < Dk) v[r][d] = src[Dc + d];
-    } else {
-      // block chunk * R + r of this id (i < C: the block exists)
-      const float* src = p.w.zsrc + ((int64_t)id * p.w.nblk + chunk * R + r) * kThreads * D + t;
-#pragma unroll
-      for (int d = 0; d < DP; ++d)
-        if (d < Dc) z[r][d] = src[(int64_t)d * kThreads];
-#pragma unroll
-      for (int d = 0; d < KP; ++d)
-        if (d < Dk) v[r][d] = src[(int64_t)(Dc + d) * kThreads];
-    }
-  }
-
-  double l2[R], g2[R];
-  score_side_wide_mixed<DP, KP, R>(p.w.bmu, p.w.ba, p.w.bc, p.bcat, p.bmiss, p.bbonus, p.w.kb, Dc, Dk, U, off, z, v,
-                                   rows, cats, cl, l2);
-  score_side_wide_mixed<DP, KP, R>(p.w.amu, p.w.aa, p.w.ac, p.acat, p.amiss, p.abonus, p.w.ka, Dc, Dk, U, off, z, v,
-                                   rows, cats, cl, g2);
-
-  Pick best{0, 0};
-  double lv[R], gv[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    const int i = first + r * kThreads + t;
-    lv[r] = l2[r] * kLn2 + p.w.bbase;
-    gv[r] = g2[r] * kLn2 + p.w.abase;
-    if (i >= p.w.C) continue;
-    const int64_t o = (int64_t)id * p.w.C + i;
-    if (p.w.l_out) p.w.l_out[o] = lv[r];
-    if (p.w.g_out) p.w.g_out[o] = gv[r];
-    if (p.w.cand) {
-#pragma unroll
-      for (int d = 0; d < DP; ++d)
-        if (d < Dc) p.w.cand[o * D + d] = z[r][d];
-#pragma unroll
-      for (int d = 0; d < KP; ++d)
-        if (d < Dk) p.w.cand[o * D + Dc + d] = v[r][d];
-    }
-    const uint64_t key = score_key(lv[r] - gv[r]);
-    if (key > best.key) best = Pick{key, (int64_t)i};   // ascending index: strict > keeps the first of a tie
-  }
-  Pick w = wave_best(best);
-  if ((t & 63) == 0) slot[t >> 6] = w;
-  __syncthreads();
-  w = slot[0];
-#pragma unroll
-  for (int q = 1; q < kThreads / 64; ++q)
-    if (beats(slot[q], w)) w = slot[q];
-
-  tpe_joint_wide_record* rec = p.w.chunk_rec + blockIdx.x;
-  if (w.key == 0) {
-    if (t == 0) rec->global_idx = -1;
-    return;
-  }
-  const int woff = (int)(w.idx - first);
-  if (t != woff % kThreads) return;
-  const int wr = woff / kThreads;
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    if (r != wr) continue;
-    rec->global_idx = w.idx + (int64_t)p.w.cand_base;
-    rec->l = lv[r];
-    rec->g = gv[r];
-    // kernel coordinate order: the Dc continuous entries, the categories, then zeros
-#pragma unroll
-    for (int d = 0; d < kWD; ++d)
-      if (d >= D) rec->z[d] = 0.0;
-#pragma unroll
-    for (int d = 0; d < DP; ++d)
-      if (d < Dc) rec->z[d] = (double)z[r][d];
-#pragma unroll
-    for (int d = 0; d < KP; ++d)
-      if (d < Dk) rec->z[Dc + d] = (double)v[r][d];
-  }
-}
-
-// ----------------------------------------- quantised labels in wide groups
-// Dc >= 1 continuous coordinates, Dk <= TPE_JOINT_WIDE_MAX_CAT discrete ones (0
-// allowed) and 1 <= Dq <= TPE_JOINT_MAX_QUANT quantised ones, Dc + Dk + Dq <=
-// TPE_JOINT_WIDE_MAX_DIMS (include/tpe_hip.h "Wide quantised joint stage"): the
-// model, the tables (k_joint_qtable) and the draws of the quantised stage, the
-// data movement of the wide mixed one.
-// k_joint_wide_quant_sample  k_joint_wide_mixed_sample, then the Dq lattice
-//                indices as k_joint_quant_chunk's sampler draws them (word 1 + j
-//                serves kernel coordinate j); a block of zbuf is
-//                [Dc + Dk + Dq][256].
-// k_joint_wide_quant_chunk<DP, KP, QP, R>  k_joint_wide_mixed_chunk with QP lattice
-//                slots a candidate.  The side's table streams through a dynamic
-//                LDS tile beside the rows, laid out [lattice value][component] as
-//                in k_joint_quant_chunk (stride tile + 4: 16 lanes with 16
-//                consecutive values read 16 different bank quads); rows and table
-//                share ONE tile length, the longest that keeps the table tile
-//                inside kWQTileBytes (and at most wide_tile(DP)).  Components are
-//                taken four at a time (one 16-byte table read per candidate and
-//                quantised slot); the tile's tail is padded with c = -3e38.
-// k_joint_wide_merge serves it unchanged.
-// rows (<= 32 KiB) + cats (<= 4 KiB) + c + the table tile stay under 64 KiB: no
-// launch attribute is needed, and two workgroups fit a CU's 160 KiB.
-constexpr int kWQTileBytes = 26 * 1024;
-
-// the common tile length of a group with `total` lattice values: a multiple of 8
-// components, at most tk; 8 at the least ((512 + 1) * 12 * 4 B = 24 KiB fits)
-__host__ __device__ __forceinline__ int wide_quant_tile(int total, int tk) {
-  int tile = 8;
-  for (int t = tk; t >= 8; t -= 8)
-    if ((int64_t)(total + 1) * (t + 4) * (int64_t)sizeof(float) <= kWQTileBytes) { tile = t; break; }
-  return tile;
-}
-static_assert((int64_t)(TPE_JOINT_MAX_LATTICE_TOTAL + 1) * 12 * sizeof(float) <= kWQTileBytes, "the shortest tile fits");
-
-struct WideQuantSampK {
-  WideMixedSampK m;                 // m.s.D = Dc, m.Dk = Dk; a block of zbuf is [Dc + Dk + Dq][256]
-  int Dq;
-  int V[TPE_JOINT_MAX_QUANT], eoff[TPE_JOINT_MAX_QUANT];
-  float qlo[TPE_JOINT_MAX_QUANT], qhi[TPE_JOINT_MAX_QUANT];
-  const double* edges;
-  const float* qsamp;
-};
-
-struct WideQuantK {
-  WideMixedK m;                     // m.w.D = Dc, m.Dk = Dk; zsrc / cand rows are [Dc + Dk + Dq]
-  int Dq, tile, stride, total;      // components per tile, floats per lattice value in the tile, sum V_d
-  int V[TPE_JOINT_MAX_QUANT], voff[TPE_JOINT_MAX_QUANT];
-  const float *bT, *aT;             // [total][K] of a side
-};
-
-__global__ __launch_bounds__(kThreads) void k_joint_wide_quant_sample(const WideQuantSampK p) {
-  __shared__ float blo[kWD], bhi[kWD];          // (kernel-argument arrays: constant indices only)
-  __shared__ int cU[kWK], coff[kWK];
-  __shared__ int qV[TPE_JOINT_MAX_QUANT], qeoff[TPE_JOINT_MAX_QUANT];
-  __shared__ float qlo[TPE_JOINT_MAX_QUANT], qhi[TPE_JOINT_MAX_QUANT];
-  const WideSampK& s = p.m.s;
-  const int t = threadIdx.x, Dc = s.D, Dk = p.m.Dk, Dq = p.Dq, D = Dc + Dk + Dq;
-  if (t == 0) {
-#pragma unroll
-    for (int f = 0; f < kWD; ++f) { blo[f] = s.lo[f]; bhi[f] = s.hi[f]; }
-#pragma unroll
-    for (int f = 0; f < kWK; ++f) { cU[f] = p.m.U[f]; coff[f] = p.m.off[f]; }
-#pragma unroll
-    for (int f = 0; f < TPE_JOINT_MAX_QUANT; ++f) {
-      qV[f] = p.V[f]; qeoff[f] = p.eoff[f];
-      qlo[f] = p.qlo[f]; qhi[f] = p.qhi[f];
-    }
-  }
-  __syncthreads();
-  const int id = blockIdx.x / s.nblk, blk = blockIdx.x % s.nblk;
-  const int i = blk * kThreads + t;
-  if (i >= s.C) return;
-  float* out = s.zbuf + (int64_t)blockIdx.x * kThreads * D + t;
-  const uint32_t c3 = (uint32_t)s.ids[id], gi = s.cand_base + (uint32_t)i;   // gi < 2^31 (i < C)
-  U4 w = philox4x32_10(gi, 0u, s.stream_word, c3, s.key0, s.key1);
-  const double us = u01w(w.x);
-  int lo = 0, hi = s.kb - 1;               // first k with us < cum[k]
-  while (lo < hi) { const int mid = (lo + hi) >> 1; if (us < s.cum[mid]) hi = mid; else lo = mid + 1; }
-  const int comp = lo;
-  const float* srow = s.samp + (int64_t)comp * Dc * 5;
-  // word 1 + j serves kernel coordinate j; a continuous one is k_joint_wide_sample's draw
-#pragma unroll 1
-  for (int d = 0; d < Dc; ++d) {
-    const int wi = d + 1;
-    if ((wi & 3) == 0) w = philox4x32_10(gi, (uint32_t)(wi >> 2), s.stream_word, c3, s.key0, s.key1);
-    const uint32_t word = (wi & 3) == 0 ? w.x : (wi & 3) == 1 ? w.y : (wi & 3) == 2 ? w.z : w.w;
-    const float* sr = srow + d * 5;
-    const float pr = sr[2] + u01f(word) * (sr[3] - sr[2]);
-    float zz = ndtri_f32(pr);
-    if (sr[4] != 0.f) zz = -zz;
-    float x = sr[0] + sr[1] * zz;
-    if (!(x == x)) x = sr[0];
-    out[(int64_t)d * kThreads] = fminf(fmaxf(x, blo[d]), bhi[d]);      // low <= z < high
-  }
-  // ... a discrete one k_joint_wide_mixed_sample's: the category index as an f32
-#pragma unroll 1
-  for (int d = 0; d < Dk; ++d) {
-    const int wi = Dc + d + 1;
-    if ((wi & 3) == 0) w = philox4x32_10(gi, (uint32_t)(wi >> 2), s.stream_word, c3, s.key0, s.key1);
-    const uint32_t word = (wi & 3) == 0 ? w.x : (wi & 3) == 1 ? w.y : (wi & 3) == 2 ? w.z : w.w;
-    const double u = u01w(word);
-    float x = p.m.bcat[(int64_t)comp * Dk + d];           // the component's category, -1: the prior row
-    const double h = x >= 0.f ? p.m.bh[d] : 0.0;
-    if (!(u < h)) {
-      const double u2 = (u - h) / (1.0 - h);
-      const double* cum = p.m.ccum + coff[d];
-      int a = 0, b = cU[d] - 1;                           // first category with u2 < cum[v]
-      while (a < b) { const int mid = (a + b) >> 1; if (u2 < cum[mid]) b = mid; else a = mid + 1; }
-      x = (float)a;
-    }
-    out[(int64_t)(Dc + d) * kThreads] = x;
-  }
-  // ... a quantised one k_joint_quant_chunk's: the continuous draw through the
-  // dimension's sampler row, binned; the lattice index as an f32
-#pragma unroll 1
-  for (int d = 0; d < Dq; ++d) {
-    const int wi = Dc + Dk + d + 1;
-    if ((wi & 3) == 0) w = philox4x32_10(gi, (uint32_t)(wi >> 2), s.stream_word, c3, s.key0, s.key1);
-    const uint32_t word = (wi & 3) == 0 ? w.x : (wi & 3) == 1 ? w.y : (wi & 3) == 2 ? w.z : w.w;
-    const float* sr = p.qsamp + ((int64_t)comp * Dq + d) * 5;
-    const float pr = sr[2] + u01f(word) * (sr[3] - sr[2]);
-    float zz = ndtri_f32(pr);
-    if (sr[4] != 0.f) zz = -zz;
-    float x = sr[0] + sr[1] * zz;
-    if (!(x == x)) x = sr[0];
-    x = fminf(fmaxf(x, qlo[d]), qhi[d]);                  // low <= z < high
-    const double* e = p.edges + qeoff[d] + 1;             // the interior edges e_1 .. e_{V-1}
-    const double zd = (double)x;
-    int a = 0, b = qV[d] - 1;                             // how many of them are <= z
-    while (a < b) { const int mid = (a + b) >> 1; if (e[mid] <= zd) a = mid + 1; else b = mid; }
-    out[(int64_t)(Dc + Dk + d) * kThreads] = (float)a;
-  }
-}
-
-// score_side_wide_mixed with QP quantised slots (score_side_quant's table part);
-// KP = 0: no discrete slot.  qo: a candidate's table row offsets in floats.
-template <int DP, int KP, int QP, int R>
-__device__ __forceinline__ void score_side_wide_quant(const float* __restrict__ mu, const float* __restrict__ a,
-                                                      const float* __restrict__ c, const float* __restrict__ cat,
-                                                      const float* __restrict__ miss, const float* __restrict__ bonus,
-                                                      const float* __restrict__ T, int K, int Dc, int Dk, int tile,
-                                                      int stride, int total, const int (&U)[KP > 0 ? KP : 1],
-                                                      const int (&off)[KP > 0 ? KP : 1], const float (&z)[R][DP],
-                                                      const float (&v)[R][KP > 0 ? KP : 1], const int (&qo)[R][QP],
-                                                      float* __restrict__ rows, float* __restrict__ cats,
-                                                      float* __restrict__ cl, float* __restrict__ qt,
-                                                      double (&out)[R]) {
-  constexpr int KPa = KP > 0 ? KP : 1;
-  float m[R], s[R], nb[R][KPa];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    m[r] = -3.0e38f;
-    s[r] = 0.f;
-#pragma unroll
-    for (int d = 0; d < KP; ++d) nb[r][d] = d < Dk ? -bonus[off[d] + cat_index(v[r][d], U[d])] : 0.f;
-  }
-  for (int k0 = 0; k0 < K; k0 += tile) {
-    const int nk = min(tile, K - k0), nk4 = (nk + 3) & ~3;
-    __syncthreads();                       // the previous tile (or side) is read
-    for (int e = threadIdx.x; e < nk4 * DP; e += kThreads) {
-      const int kk = e / DP, d = e % DP;
-      const bool in = d < Dc && kk < nk;   // padded dimensions and components: a = 0 adds nothing
-      const int64_t src = (int64_t)(k0 + kk) * Dc + d;
-      rows[kk * 2 * DP + d] = in ? mu[src] : 0.f;
-      rows[kk * 2 * DP + DP + d] = in ? a[src] : 0.f;
-    }
-    if constexpr (KP > 0)
-      for (int e = threadIdx.x; e < nk4 * KP; e += kThreads) {
-        const int kk = e / KP, d = e % KP;   // padded slots: category -1 never matches
-        cats[e] = (d < Dk && kk < nk) ? cat[(int64_t)(k0 + kk) * Dk + d] : -1.f;
-      }
-    for (int e = threadIdx.x; e < nk4; e += kThreads) cl[e] = e < nk ? c[k0 + e] : -3.0e38f;
-    for (int e = threadIdx.x; e < total * tile; e += kThreads) {
-      const int b = e / tile, kk = e - b * tile;           // a run over k of one lattice value: coalesced
-      if (kk < nk4) qt[b * stride + kk] = kk < nk ? T[(int64_t)b * K + k0 + kk] : 0.f;
-    }
-    __syncthreads();
-    for (int k4 = 0; k4 < nk4; k4 += 4) {
-      float tq[R][QP][4];
-#pragma unroll
-      for (int r = 0; r < R; ++r)
-#pragma unroll
-        for (int d = 0; d < QP; ++d) {
-          const float4 x = *reinterpret_cast<const float4*>(qt + qo[r][d] + k4);
-          tq[r][d][0] = x.x; tq[r][d][1] = x.y; tq[r][d][2] = x.z; tq[r][d][3] = x.w;
-        }
-      // (R = 1, the widths above 32: the four components are a loop, not four copies,
-      // which would hold their 4 x 2 DP row values at once and leave one wave a SIMD)
-#pragma unroll(R == 1 ? 1 : 4)
-      for (int j = 0; j < 4; ++j) {
-        const int kk = k4 + j;
-        const float4* row = reinterpret_cast<const float4*>(rows + kk * 2 * DP);
-        float acc[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) acc[r] = 0.f;
-#pragma unroll
-        for (int q = 0; q < DP / 4; ++q) {
-          const float4 rm = row[q], ra = row[DP / 4 + q];
-#pragma unroll
-          for (int r = 0; r < R; ++r) {
-            float u = (z[r][4 * q] - rm.x) * ra.x;
-            acc[r] = __builtin_fmaf(u, u, acc[r]);
-            u = (z[r][4 * q + 1] - rm.y) * ra.y;
-            acc[r] = __builtin_fmaf(u, u, acc[r]);
-            u = (z[r][4 * q + 2] - rm.z) * ra.z;
-            acc[r] = __builtin_fmaf(u, u, acc[r]);
-            u = (z[r][4 * q + 3] - rm.w) * ra.w;
-            acc[r] = __builtin_fmaf(u, u, acc[r]);
-          }
-        }
-        float rc[KPa];
-        if constexpr (KP > 0 && KP % 4 == 0) {
-          const float4* cr = reinterpret_cast<const float4*>(cats + kk * KP);
-#pragma unroll
-          for (int q = 0; q < KP / 4; ++q) {
-            const float4 x = cr[q];
-            rc[4 * q] = x.x; rc[4 * q + 1] = x.y; rc[4 * q + 2] = x.z; rc[4 * q + 3] = x.w;
-          }
-        } else if constexpr (KP == 2) {
-          const float2 x = *reinterpret_cast<const float2*>(cats + kk * 2);
-          rc[0] = x.x; rc[1] = x.y;
-        } else if constexpr (KP == 1) {
-          rc[0] = cats[kk];
-        }
-        const float ck = cl[kk];
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-#pragma unroll
-          for (int d = 0; d < KP; ++d) acc[r] += v[r][d] == rc[d] ? nb[r][d] : 0.f;
-#pragma unroll
-          for (int d = 0; d < QP; ++d)   // (selects, not an indexed read: tq stays in registers in the looped form)
-            acc[r] -= j == 0 ? tq[r][d][0] : j == 1 ? tq[r][d][1] : j == 2 ? tq[r][d][2] : tq[r][d][3];
-          const float t = ck - acc[r];
-          const float dl = t - m[r];
-          const float e2 = __builtin_amdgcn_exp2f(-__builtin_fabsf(dl));
-          s[r] = dl > 0.f ? __builtin_fmaf(s[r], e2, 1.f) : s[r] + e2;
-          m[r] = fmaxf(m[r], t);
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    double M = 0.0;
-#pragma unroll
-    for (int d = 0; d < KP; ++d)
-      if (d < Dk) M += (double)miss[off[d] + cat_index(v[r][d], U[d])];
-    out[r] = (double)m[r] + log2((double)s[r]) + M;
-  }
-}
-
-template <int DP, int KP, int QP, int R>
-__global__ __launch_bounds__(kThreads) void k_joint_wide_quant_chunk(const WideQuantK p) {
-  static_assert(DP % 4 == 0 && DP <= kWD && KP <= kWK && QP <= TPE_JOINT_MAX_QUANT,
-                "rows are read as float4; the argument arrays");
-  constexpr int TK = wide_tile(DP), KPa = KP > 0 ? KP : 1;
-  __shared__ __attribute__((aligned(16))) float rows[TK * 2 * DP];
-  __shared__ __attribute__((aligned(16))) float cats[TK * KPa];
-  __shared__ float cl[TK];
-  __shared__ Pick slot[kThreads / 64];
-  extern __shared__ __attribute__((aligned(16))) float qt[];     // [(total + 1) * stride]
-  static_assert(sizeof(float) * (TK * 2 * DP + TK * KPa + TK) + sizeof(Pick) * (kThreads / 64) + kWQTileBytes <=
-                    64 * 1024, "static and dynamic LDS of a workgroup stay under 64 KiB");
-  const WideK& w0 = p.m.w;
-  const int t = threadIdx.x, Dc = w0.D, Dk = p.m.Dk, Dq = p.Dq, D = Dc + Dk + Dq;
-  const int id = blockIdx.x / w0.n_chunks, chunk = blockIdx.x % w0.n_chunks;
-  const int first = chunk * (R * kThreads);
-  int U[KPa], off[KPa];                    // (kernel-argument arrays: constant indices only)
-  U[0] = 1; off[0] = 0;
-#pragma unroll
-  for (int d = 0; d < KP; ++d) { U[d] = p.m.U[d]; off[d] = p.m.off[d]; }
-
-  for (int e = t; e < p.stride; e += kThreads) qt[p.total * p.stride + e] = 0.f;   // the padded slots' row
-
-  float z[R][DP], v[R][KPa], x[R][QP];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-#pragma unroll
-    for (int d = 0; d < DP; ++d) z[r][d] = 0.f;
-#pragma unroll
-    for (int d = 0; d < KPa; ++d) v[r][d] = 0.f;
-#pragma unroll
-    for (int d = 0; d < QP; ++d) x[r][d] = 0.f;
-    const int i = first + r * kThreads + t;
-    if (i >= w0.C) continue;
-    if (w0.inject) {
-      const float* src = w0.zsrc + (int64_t)i * D;
-#pragma unroll
-      for (int d = 0; d < DP; ++d)
-        if (d < Dc) z[r][d] = src[d];
-#pragma unroll
-      for (int d = 0; d < KP; ++d)
-        if (d < Dk) v[r][d] = src[Dc + d];
-#pragma unroll
-      for (int d = 0; d < QP; ++d)
-        if (d < Dq) x[r][d] = src[Dc + Dk + d];
-    } else {
-      // block chunk * R + r of this id (i < C: the block exists)
-      const float* src = w0.zsrc + ((int64_t)id * w0.nblk + chunk * R + r) * kThreads * D + t;
-#pragma unroll
-      for (int d = 0; d < DP; ++d)
-        if (d < Dc) z[r][d] = src[(int64_t)d * kThreads];
-#pragma unroll
-      for (int d = 0; d < KP; ++d)
-        if (d < Dk) v[r][d] = src[(int64_t)(Dc + d) * kThreads];
-#pragma unroll
-      for (int d = 0; d < QP; ++d)
-        if (d < Dq) x[r][d] = src[(int64_t)(Dc + Dk + d) * kThreads];
-    }
-  }
-
-  // the lattice value's row in the tile (kept inside the table); a padded slot reads the zero row
-  int qo[R][QP];
-#pragma unroll
-  for (int r = 0; r < R; ++r)
-#pragma unroll
-    for (int d = 0; d < QP; ++d)
-      qo[r][d] = (d < Dq ? p.voff[d] + cat_index(x[r][d], p.V[d]) : p.total) * p.stride;
-
-  double l2[R], g2[R];
-  score_side_wide_quant<DP, KP, QP, R>(w0.bmu, w0.ba, w0.bc, p.m.bcat, p.m.bmiss, p.m.bbonus, p.bT, w0.kb, Dc, Dk,
-                                       p.tile, p.stride, p.total, U, off, z, v, qo, rows, cats, cl, qt, l2);
-  score_side_wide_quant<DP, KP, QP, R>(w0.amu, w0.aa, w0.ac, p.m.acat, p.m.amiss, p.m.abonus, p.aT, w0.ka, Dc, Dk,
-                                       p.tile, p.stride, p.total, U, off, z, v, qo, rows, cats, cl, qt, g2);
-
-  Pick best{0, 0};
-  double lv[R], gv[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    const int i = first + r * kThreads + t;
-    lv[r] = l2[r] * kLn2 + w0.bbase;
-    gv[r] = g2[r] * kLn2 + w0.abase;
-    if (i >= w0.C) continue;
-    const int64_t o = (int64_t)id * w0.C + i;
-    if (w0.l_out) w0.l_out[o] = lv[r];
-    if (w0.g_out) w0.g_out[o] = gv[r];
-    if (w0.cand) {
-#pragma unroll
-      for (int d = 0; d < DP; ++d)
-        if (d < Dc) w0.cand[o * D + d] = z[r][d];
-#pragma unroll
-      for (int d = 0; d < KP; ++d)
-        if (d < Dk) w0.cand[o * D + Dc + d] = v[r][d];
-#pragma unroll
-      for (int d = 0; d < QP; ++d)
-        if (d < Dq) w0.cand[o * D + Dc + Dk + d] = x[r][d];
-    }
-    const uint64_t key = score_key(lv[r] - gv[r]);
-    if (key > best.key) best = Pick{key, (int64_t)i};   // ascending index: strict > keeps the first of a tie
-  }
-  Pick w = wave_best(best);
-  if ((t & 63) == 0) slot[t >> 6] = w;
-  __syncthreads();
-  w = slot[0];
-#pragma unroll
-  for (int q = 1; q < kThreads / 64; ++q)
-    if (beats(slot[q], w)) w = slot[q];
-
-  tpe_joint_wide_record* rec = w0.chunk_rec + blockIdx.x;
-  if (w.key == 0) {
-    if (t == 0) rec->global_idx = -1;
-    return;
-  }
-  const int woff = (int)(w.idx - first);
-  if (t != woff % kThreads) return;
-  const int wr = woff / kThreads;
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    if (r != wr) continue;
-    rec->global_idx = w.idx + (int64_t)w0.cand_base;
-    rec->l = lv[r];
-    rec->g = gv[r];
-    // kernel coordinate order: continuous, categories, lattice indices, then zeros
-#pragma unroll
-    for (int d = 0; d < kWD; ++d)
-      if (d >= D) rec->z[d] = 0.0;
-#pragma unroll
-    for (int d = 0; d < DP; ++d)
-      if (d < Dc) rec->z[d] = (double)z[r][d];
-#pragma unroll
-    for (int d = 0; d < KP; ++d)
-      if (d < Dk) rec->z[Dc + d] = (double)v[r][d];
-#pragma unroll
-    for (int d = 0; d < QP; ++d)
-      if (d < Dq) rec->z[Dc + Dk + d] = (double)x[r][d];
   }
 }
 
@@ -2433,17 +2311,29 @@ void fill_joint(JointK& k, const A* a, int Dc, uint32_t cand_base, float* cand, 
   k.cand = cand; k.l_out = l_out; k.g_out = g_out;
   k.chunk_rec = (tpe_joint_record*)scratch;
 }
-// ... and of its discrete labels (tpe_joint_mixed_args / tpe_joint_quant_args)
-template <typename A>
-void fill_mixed(MixedK& m, const A* a) {
-  m.Dk = a->n_cat;
-  for (int d = 0; d < TPE_JOINT_MAX_DIMS; ++d) {
-    m.U[d] = d < m.Dk ? a->cat_upper[d] : 1;
-    m.off[d] = d < m.Dk ? a->cat_off[d] : 0;
+// ... and of its discrete labels, for every stage that has them.  K: MixedK, a
+// wide sampling kernel's or a wide scoring kernel's arguments; the padded slots
+// hold one category at offset 0.
+template <typename K, typename A>
+void fill_cat_slots(K& k, const A* a) {
+  constexpr int N = (int)(sizeof k.U / sizeof k.U[0]);
+  k.Dk = a->n_cat;
+  for (int d = 0; d < N; ++d) {
+    k.U[d] = d < k.Dk ? a->cat_upper[d] : 1;
+    k.off[d] = d < k.Dk ? a->cat_off[d] : 0;
   }
-  m.bcat = a->below_cat; m.acat = a->above_cat;
-  m.bmiss = a->below_miss; m.bbonus = a->below_bonus; m.amiss = a->above_miss; m.abonus = a->above_bonus;
-  m.bh = a->below_h; m.ccum = a->cat_cum;
+  k.bcat = a->below_cat;
+}
+// what the sampler reads of them ...
+template <typename K, typename A>
+void fill_cat_draw(K& k, const A* a) {
+  k.bh = a->below_h; k.ccum = a->cat_cum;
+}
+// ... and what the scoring loop reads
+template <typename K, typename A>
+void fill_cat_score(K& k, const A* a) {
+  k.acat = a->above_cat;
+  k.bmiss = a->below_miss; k.bbonus = a->below_bonus; k.amiss = a->above_miss; k.abonus = a->above_bonus;
 }
 template <typename A>
 bool cat_tables_null(const A* a) {
@@ -2486,6 +2376,57 @@ int64_t check_lattice(const char* entry, const char* where, const int32_t* v, co
 // the dynamic LDS of a quantised chunk launch: the table tile of `total` lattice values
 unsigned quant_lds(int total) { return (unsigned)((total + 1) * (quant_tile(total) + 4) * sizeof(float)); }
 
+// ---- what the two stages with quantised labels share (tpe_joint_quant_args,
+// tpe_joint_wide_quant_args): the checks on the labels, their rows and the table
+// workspace (the lattice total, or -1 with the call's error set) ...
+template <typename A>
+int64_t check_quant(const char* entry, const A* a) {
+  const int64_t total = check_lattice(entry, "", a->quant_v, a->quant_edge_off, a->n_quant, a->n_edges);
+  if (total < 0) return -1;
+  if (!a->quant_edges || !a->below_qmu || !a->below_qsigma || !a->above_qmu || !a->above_qsigma || !a->quant_samp ||
+      !a->quant_table)
+    return fail(entry, "null quantised rows or table"), -1;
+  if (a->quant_table_bytes < quant_table_floats(a->k_below, a->k_above, total) * sizeof(float))
+    return fail(entry, "table workspace too small"), -1;
+  return total;
+}
+// ... the labels' padded slots: sizes, table and edge offsets (in tb) and f32
+// bounds (a quantised dimension's outer edges: low / high [Dc + d]) ...
+template <typename A>
+void fill_quant_slots(QTabK& tb, float (&qlo)[TPE_JOINT_MAX_QUANT], float (&qhi)[TPE_JOINT_MAX_QUANT], const A* a) {
+  const int Dc = a->n_dims, Dq = a->n_quant;
+  int voff = 0;
+  for (int d = 0; d < TPE_JOINT_MAX_QUANT; ++d) {
+    const bool in = d < Dq;
+    tb.V[d] = in ? a->quant_v[d] : 2;
+    tb.voff[d] = in ? voff : 0;
+    tb.eoff[d] = in ? a->quant_edge_off[d] : 0;
+    qlo[d] = -INFINITY; qhi[d] = INFINITY;
+    if (in) {
+      f32_bounds(a->low[Dc + d], a->high[Dc + d], qlo[d], qhi[d]);
+      voff += a->quant_v[d];
+    }
+  }
+}
+// ... and the two sides' table launches (tb: fill_quant_slots'), under profiling
+// between the events that tpe_joint_quant_profile reads
+template <typename A>
+int launch_qtables(QTabK& tb, const A* a, int64_t total, hipStream_t s, bool timed) {
+  if (timed)
+    if (int rc = ensure_events(g_qprof.ev, 2)) return rc;
+  const int Dq = a->n_quant;
+  tb.K = a->k_below; tb.Dq = Dq; tb.mu = a->below_qmu; tb.sigma = a->below_qsigma; tb.edges = a->quant_edges;
+  tb.T = a->quant_table;
+  QTabK ta = tb;
+  ta.K = a->k_above; ta.mu = a->above_qmu; ta.sigma = a->above_qsigma; ta.T = a->quant_table + total * a->k_below;
+  const dim3 gb((unsigned)((a->k_below + kThreads - 1) / kThreads), (unsigned)Dq);
+  const dim3 ga((unsigned)((a->k_above + kThreads - 1) / kThreads), (unsigned)Dq);
+  launch(k_joint_qtable, gb, kThreads, 0u, s, timed ? g_qprof.ev[0] : nullptr, nullptr, tb);
+  launch(k_joint_qtable, ga, kThreads, 0u, s, nullptr, timed ? g_qprof.ev[1] : nullptr, ta);
+  if (timed) g_qprof.valid = 1;
+  return TPE_OK;
+}
+
 // ---- the solo stages; local candidate i is global candidate cand_base + i (tpe_joint_run_shard)
 int joint_run_at(const tpe_joint_args* a, tpe_joint_record* records, float* cand, double* l_out, double* g_out,
                  void* scratch, uint64_t scratch_bytes, void* stream, uint32_t cand_base) {
@@ -2508,9 +2449,10 @@ int joint_run_at(const tpe_joint_args* a, tpe_joint_record* records, float* cand
   return finish(k_joint_merge, (const tpe_joint_record*)scratch, k.n_chunks, records, a->n_ids, s, timed, 1);
 }
 
-// What the two wide stages share: the sampling kernel's arguments of a group of
-// D continuous coordinates (the bounds staged as f32), its launch under
-// profiling, the scoring kernel's arguments.
+// ---- the wide stages: one skeleton (joint_wide_stage); a stage supplies its
+// checks, the extra fields of its sampling and scoring arguments and its kernels.
+// The sampling kernel's arguments of a group of D continuous coordinates (the
+// bounds staged as f32), its launch under profiling, the scoring kernel's arguments.
 template <typename A>
 void fill_wide_samp(WideSampK& sk, const A* a, int D, int64_t nblk, uint32_t cand_base, float* zbuf) {
   sk.D = D; sk.C = a->n_cand; sk.nblk = (int)nblk; sk.kb = a->k_below;
@@ -2545,6 +2487,37 @@ void fill_wide(WideK& k, const A* a, int D, int64_t n_chunks, int64_t nblk, uint
   k.chunk_rec = (tpe_joint_wide_record*)scratch;
 }
 
+// What follows a wide stage's own checks.  Dx: the group's discrete and
+// quantised coordinates beside its a->n_dims continuous ones.  sk / k: the
+// stage's sampling / scoring arguments with its own fields filled; the shared
+// ones are filled here.  tables(s, timed): the stage's launches before the
+// sampling kernel (the quantised stage's tables); chunk(blocks, s, ev): its
+// scoring launch at its padded widths.
+template <typename A, typename SK, typename K, typename SampKernel, typename Tables, typename Chunk>
+int joint_wide_stage(const char* E, const A* a, int Dx, SK& sk, K& k, SampKernel samp_kernel, Tables tables,
+                     Chunk chunk, tpe_joint_wide_record* records, float* cand, double* l_out, double* g_out,
+                     void* scratch, uint64_t scratch_bytes, void* stream, uint32_t cand_base) {
+  const int D = a->n_dims;
+  const bool inject = (a->flags & TPE_JOINT_INJECT) != 0;
+  const int64_t n_chunks = wide_chunks_of(a->n_cand, D), blocks = n_chunks * a->n_ids;
+  const int64_t nblk = wide_blocks_of(a->n_cand), sblocks = nblk * a->n_ids;
+  if (int rc = check_scratch(E, sblocks, wide_scratch_need(a->n_ids, a->n_cand, D, Dx), scratch, scratch_bytes)) return rc;
+
+  const bool timed = g_prof.on != 0;
+  hipStream_t s = (hipStream_t)stream;
+  float* zbuf = (float*)((char*)scratch + wide_record_bytes(a->n_ids, a->n_cand, D));
+  if (int rc = tables(s, timed)) return rc;
+  g_wprof.valid = 0;
+  if (!inject) {
+    fill_wide_samp(sk, a, D, nblk, cand_base, zbuf);
+    if (int rc = launch_wide_samp(samp_kernel, sblocks, s, timed, sk)) return rc;
+  }
+  fill_wide(k, a, D, n_chunks, nblk, cand_base, zbuf, cand, l_out, g_out, scratch);
+  chunk((unsigned)blocks, s, chunk_marks(timed));
+  return finish(k_joint_wide_merge, (const tpe_joint_wide_record*)scratch, (int)n_chunks, records, a->n_ids, s, timed, 1);
+}
+constexpr auto kNoTables = [](hipStream_t, bool) { return (int)TPE_OK; };
+
 int joint_wide_run_at(const tpe_joint_wide_args* a, tpe_joint_wide_record* records, float* cand, double* l_out,
                       double* g_out, void* scratch, uint64_t scratch_bytes, void* stream, uint32_t cand_base) {
   constexpr const char* E = "tpe_joint_wide_run";
@@ -2553,30 +2526,17 @@ int joint_wide_run_at(const tpe_joint_wide_args* a, tpe_joint_wide_record* recor
   if (a->n_dims < 1 || a->n_dims > TPE_JOINT_WIDE_MAX_DIMS)
     return fail(E, "n_dims outside [1, TPE_JOINT_WIDE_MAX_DIMS]");
   if (int rc = check_solo_head(E, a, records, a->n_dims)) return rc;
-  const int D = a->n_dims;
-  const bool inject = (a->flags & TPE_JOINT_INJECT) != 0;
-  const int64_t n_chunks = wide_chunks_of(a->n_cand, D), blocks = n_chunks * a->n_ids;
-  const int64_t nblk = wide_blocks_of(a->n_cand), sblocks = nblk * a->n_ids;
-  if (int rc = check_scratch(E, sblocks, wide_scratch_need(a->n_ids, a->n_cand, D), scratch, scratch_bytes)) return rc;
 
-  const bool timed = g_prof.on != 0;
-  hipStream_t s = (hipStream_t)stream;
-  float* zbuf = (float*)((char*)scratch + wide_record_bytes(a->n_ids, a->n_cand, D));
-  g_wprof.valid = 0;
-  if (!inject) {
-    WideSampK sk;
-    fill_wide_samp(sk, a, D, nblk, cand_base, zbuf);
-    if (int rc = launch_wide_samp(k_joint_wide_sample, sblocks, s, timed, sk)) return rc;
-  }
-
+  WideSampK sk;
   WideK k;
-  fill_wide(k, a, D, n_chunks, nblk, cand_base, zbuf, cand, l_out, g_out, scratch);
-  const Ev ev = chunk_marks(timed);
-  for_wide_dp(D, [&](auto dp) {
-    constexpr int DP = decltype(dp)::value;
-    launch(k_joint_wide_chunk<DP, wide_r(DP)>, dim3((unsigned)blocks), kThreads, 0u, s, ev.start, ev.stop, k);
-  });
-  return finish(k_joint_wide_merge, (const tpe_joint_wide_record*)scratch, (int)n_chunks, records, a->n_ids, s, timed, 1);
+  auto chunk = [&](unsigned blocks, hipStream_t s, Ev ev) {
+    for_wide_dp(a->n_dims, [&](auto dp) {
+      constexpr int DP = decltype(dp)::value;
+      launch(k_joint_wide_chunk<DP, wide_r(DP)>, dim3(blocks), kThreads, 0u, s, ev.start, ev.stop, k);
+    });
+  };
+  return joint_wide_stage(E, a, 0, sk, k, k_joint_wide_sample, kNoTables, chunk, records, cand, l_out, g_out, scratch,
+                          scratch_bytes, stream, cand_base);
 }
 
 // (cand_base: the kernels carry it as the wide stage's do; tpe_joint_run_shard does not take this stage yet)
@@ -2598,45 +2558,22 @@ int joint_wide_mixed_run_at(const tpe_joint_wide_mixed_args* a, tpe_joint_wide_r
   if (int rc = check_solo_head(E, a, records, Dc)) return rc;
   if (cat_tables_null(a)) return fail(E, "null category tables");
   if (check_cats(E, "", a->cat_upper, a->cat_off, Dk) < 0) return TPE_E_ARG;
-  const bool inject = (a->flags & TPE_JOINT_INJECT) != 0;
-  const int64_t n_chunks = wide_chunks_of(a->n_cand, Dc), blocks = n_chunks * a->n_ids;
-  const int64_t nblk = wide_blocks_of(a->n_cand), sblocks = nblk * a->n_ids;
-  if (int rc = check_scratch(E, sblocks, wide_scratch_need(a->n_ids, a->n_cand, Dc, Dk), scratch, scratch_bytes))
-    return rc;
 
-  const bool timed = g_prof.on != 0;
-  hipStream_t s = (hipStream_t)stream;
-  float* zbuf = (float*)((char*)scratch + wide_record_bytes(a->n_ids, a->n_cand, Dc));
-  int U[TPE_JOINT_WIDE_MAX_CAT], off[TPE_JOINT_WIDE_MAX_CAT];
-  for (int d = 0; d < TPE_JOINT_WIDE_MAX_CAT; ++d) {
-    U[d] = d < Dk ? a->cat_upper[d] : 1;
-    off[d] = d < Dk ? a->cat_off[d] : 0;
-  }
-  g_wprof.valid = 0;
-  if (!inject) {
-    WideMixedSampK sk;
-    fill_wide_samp(sk.s, a, Dc, nblk, cand_base, zbuf);
-    sk.Dk = Dk;
-    memcpy(sk.U, U, sizeof U); memcpy(sk.off, off, sizeof off);
-    sk.bcat = a->below_cat; sk.bh = a->below_h; sk.ccum = a->cat_cum;
-    if (int rc = launch_wide_samp(k_joint_wide_mixed_sample, sblocks, s, timed, sk)) return rc;
-  }
-
+  WideMixedSampK sk;
   WideMixedK k;
-  fill_wide(k.w, a, Dc, n_chunks, nblk, cand_base, zbuf, cand, l_out, g_out, scratch);
-  k.Dk = Dk;
-  memcpy(k.U, U, sizeof U); memcpy(k.off, off, sizeof off);
-  k.bcat = a->below_cat; k.acat = a->above_cat;
-  k.bmiss = a->below_miss; k.bbonus = a->below_bonus; k.amiss = a->above_miss; k.abonus = a->above_bonus;
-  const Ev ev = chunk_marks(timed);
-  for_wide_mixed_dp(Dc, [&](auto dp) {
-    constexpr int DP = decltype(dp)::value;
-    for_kp<1, 8>(Dk, [&](auto kp) {
-      launch(k_joint_wide_mixed_chunk<DP, decltype(kp)::value, wide_r(DP)>, dim3((unsigned)blocks), kThreads, 0u, s,
-             ev.start, ev.stop, k);
+  fill_cat_slots(sk, a); fill_cat_draw(sk, a);
+  fill_cat_slots(k, a); fill_cat_score(k, a);
+  auto chunk = [&](unsigned blocks, hipStream_t s, Ev ev) {
+    for_wide_mixed_dp(Dc, [&](auto dp) {
+      constexpr int DP = decltype(dp)::value;
+      for_kp<1, 8>(Dk, [&](auto kp) {
+        launch(k_joint_wide_mixed_chunk<DP, decltype(kp)::value, wide_r(DP)>, dim3(blocks), kThreads, 0u, s, ev.start,
+               ev.stop, k);
+      });
     });
-  });
-  return finish(k_joint_wide_merge, (const tpe_joint_wide_record*)scratch, (int)n_chunks, records, a->n_ids, s, timed, 1);
+  };
+  return joint_wide_stage(E, a, Dk, sk, k, k_joint_wide_mixed_sample, kNoTables, chunk, records, cand, l_out, g_out,
+                          scratch, scratch_bytes, stream, cand_base);
 }
 
 // ... and a wide quantised group without a quantised label a tpe_joint_wide_mixed_args
@@ -2685,87 +2622,36 @@ int joint_wide_quant_run_at(const tpe_joint_wide_quant_args* a, tpe_joint_wide_r
     if (cat_tables_null(a)) return fail(E, "null category tables");
     if (check_cats(E, "", a->cat_upper, a->cat_off, Dk) < 0) return TPE_E_ARG;
   }
-  const int64_t total = check_lattice(E, "", a->quant_v, a->quant_edge_off, Dq, a->n_edges);
+  const int64_t total = check_quant(E, a);
   if (total < 0) return TPE_E_ARG;
-  if (!a->quant_edges || !a->below_qmu || !a->below_qsigma || !a->above_qmu || !a->above_qsigma || !a->quant_samp ||
-      !a->quant_table)
-    return fail(E, "null quantised rows or table");
-  if (a->quant_table_bytes < quant_table_floats(a->k_below, a->k_above, total) * sizeof(float))
-    return fail(E, "table workspace too small");
-  const bool inject = (a->flags & TPE_JOINT_INJECT) != 0;
-  const int64_t n_chunks = wide_chunks_of(a->n_cand, Dc), blocks = n_chunks * a->n_ids;
-  const int64_t nblk = wide_blocks_of(a->n_cand), sblocks = nblk * a->n_ids;
-  if (int rc = check_scratch(E, sblocks, wide_quant_scratch_need(a->n_ids, a->n_cand, Dc, Dk, Dq), scratch,
-                             scratch_bytes))
-    return rc;
 
-  const bool timed = g_prof.on != 0;
-  hipStream_t s = (hipStream_t)stream;
-  float* zbuf = (float*)((char*)scratch + wide_record_bytes(a->n_ids, a->n_cand, Dc));
-  int U[TPE_JOINT_WIDE_MAX_CAT], off[TPE_JOINT_WIDE_MAX_CAT];
-  for (int d = 0; d < TPE_JOINT_WIDE_MAX_CAT; ++d) {
-    U[d] = d < Dk ? a->cat_upper[d] : 1;
-    off[d] = d < Dk ? a->cat_off[d] : 0;
-  }
-
-  // the two sides' tables: tpe_joint_quant_run's launches
   WideQuantSampK sk;
   WideQuantK k;
-  QTabK tb, ta;
-  int voff = 0;
-  for (int d = 0; d < TPE_JOINT_MAX_QUANT; ++d) {
-    const bool in = d < Dq;
-    k.V[d] = sk.V[d] = tb.V[d] = in ? a->quant_v[d] : 2;
-    k.voff[d] = tb.voff[d] = in ? voff : 0;
-    sk.eoff[d] = tb.eoff[d] = in ? a->quant_edge_off[d] : 0;
-    sk.qlo[d] = -INFINITY; sk.qhi[d] = INFINITY;
-    if (in) {                                // a quantised dimension's bounds (its outer edges): low / high [Dc + d]
-      f32_bounds(a->low[Dc + d], a->high[Dc + d], sk.qlo[d], sk.qhi[d]);
-      voff += a->quant_v[d];
-    }
-  }
-  if (timed)
-    if (int rc = ensure_events(g_qprof.ev, 2)) return rc;
-  tb.K = a->k_below; tb.Dq = Dq; tb.mu = a->below_qmu; tb.sigma = a->below_qsigma; tb.edges = a->quant_edges;
-  tb.T = a->quant_table;
-  ta = tb;
-  ta.K = a->k_above; ta.mu = a->above_qmu; ta.sigma = a->above_qsigma; ta.T = a->quant_table + total * a->k_below;
-  const dim3 gb((unsigned)((a->k_below + kThreads - 1) / kThreads), (unsigned)Dq);
-  const dim3 ga((unsigned)((a->k_above + kThreads - 1) / kThreads), (unsigned)Dq);
-  launch(k_joint_qtable, gb, kThreads, 0u, s, timed ? g_qprof.ev[0] : nullptr, nullptr, tb);
-  launch(k_joint_qtable, ga, kThreads, 0u, s, nullptr, timed ? g_qprof.ev[1] : nullptr, ta);
-  if (timed) g_qprof.valid = 1;
-
-  g_wprof.valid = 0;
-  if (!inject) {
-    fill_wide_samp(sk.m.s, a, Dc, nblk, cand_base, zbuf);
-    sk.m.Dk = Dk;
-    memcpy(sk.m.U, U, sizeof U); memcpy(sk.m.off, off, sizeof off);
-    sk.m.bcat = a->below_cat; sk.m.bh = a->below_h; sk.m.ccum = a->cat_cum;
-    sk.Dq = Dq; sk.edges = a->quant_edges; sk.qsamp = a->quant_samp;
-    if (int rc = launch_wide_samp(k_joint_wide_quant_sample, sblocks, s, timed, sk)) return rc;
-  }
-
-  fill_wide(k.m.w, a, Dc, n_chunks, nblk, cand_base, zbuf, cand, l_out, g_out, scratch);
-  k.m.Dk = Dk;
-  memcpy(k.m.U, U, sizeof U); memcpy(k.m.off, off, sizeof off);
-  k.m.bcat = a->below_cat; k.m.acat = a->above_cat;
-  k.m.bmiss = a->below_miss; k.m.bbonus = a->below_bonus; k.m.amiss = a->above_miss; k.m.abonus = a->above_bonus;
+  QTabK tb;
+  fill_cat_slots(sk, a); fill_cat_draw(sk, a);
+  fill_cat_slots(k, a); fill_cat_score(k, a);
+  fill_quant_slots(tb, sk.qlo, sk.qhi, a);
+  memcpy(sk.V, tb.V, sizeof tb.V); memcpy(sk.eoff, tb.eoff, sizeof tb.eoff);
+  memcpy(k.V, tb.V, sizeof tb.V); memcpy(k.voff, tb.voff, sizeof tb.voff);
+  sk.Dq = Dq; sk.edges = a->quant_edges; sk.qsamp = a->quant_samp;
   k.Dq = Dq; k.total = (int)total;
   k.tile = wide_quant_tile((int)total, wide_tile(wide_quant_dp(Dc))); k.stride = k.tile + 4;
   k.bT = a->quant_table; k.aT = a->quant_table + total * a->k_below;
   const unsigned lds = (unsigned)((total + 1) * k.stride * sizeof(float));
-  const Ev ev = chunk_marks(timed);
-  for_wide_quant_dp(Dc, [&](auto dp) {
-    constexpr int DP = decltype(dp)::value;
-    for_wide_quant_kp(Dk, [&](auto kp) {
-      for_qp(Dq, [&](auto qp) {
-        launch(k_joint_wide_quant_chunk<DP, decltype(kp)::value, decltype(qp)::value, wide_r(DP)>,
-               dim3((unsigned)blocks), kThreads, lds, s, ev.start, ev.stop, k);
+  auto tables = [&](hipStream_t s, bool timed) { return launch_qtables(tb, a, total, s, timed); };
+  auto chunk = [&](unsigned blocks, hipStream_t s, Ev ev) {
+    for_wide_quant_dp(Dc, [&](auto dp) {
+      constexpr int DP = decltype(dp)::value;
+      for_wide_quant_kp(Dk, [&](auto kp) {
+        for_qp(Dq, [&](auto qp) {
+          launch(k_joint_wide_quant_chunk<DP, decltype(kp)::value, decltype(qp)::value, wide_r(DP)>, dim3(blocks),
+                 kThreads, lds, s, ev.start, ev.stop, k);
+        });
       });
     });
-  });
-  return finish(k_joint_wide_merge, (const tpe_joint_wide_record*)scratch, (int)n_chunks, records, a->n_ids, s, timed, 1);
+  };
+  return joint_wide_stage(E, a, Dk + Dq, sk, k, k_joint_wide_quant_sample, tables, chunk, records, cand, l_out, g_out,
+                          scratch, scratch_bytes, stream, cand_base);
 }
 
 int joint_mixed_run_at(const tpe_joint_mixed_args* a, tpe_joint_record* records, float* cand, double* l_out,
@@ -2791,7 +2677,7 @@ int joint_mixed_run_at(const tpe_joint_mixed_args* a, tpe_joint_record* records,
 
   MixedK m;
   fill_joint(m.j, a, Dc, cand_base, cand, l_out, g_out, scratch);
-  fill_mixed(m, a);
+  fill_cat_slots(m, a); fill_cat_draw(m, a); fill_cat_score(m, a);
   const bool timed = g_prof.on != 0;
   hipStream_t s = (hipStream_t)stream;
   const Ev ev = chunk_marks(timed);
@@ -2825,51 +2711,25 @@ int joint_quant_run_at(const tpe_joint_quant_args* a, tpe_joint_record* records,
     if (cat_tables_null(a)) return fail(E, "null category tables");
     if (check_cats(E, "", a->cat_upper, a->cat_off, Dk) < 0) return TPE_E_ARG;
   }
-  const int64_t total = check_lattice(E, "", a->quant_v, a->quant_edge_off, Dq, a->n_edges);
+  const int64_t total = check_quant(E, a);
   if (total < 0) return TPE_E_ARG;
-  if (!a->quant_edges || !a->below_qmu || !a->below_qsigma || !a->above_qmu || !a->above_qsigma || !a->quant_samp ||
-      !a->quant_table)
-    return fail(E, "null quantised rows or table");
-  if (a->quant_table_bytes < quant_table_floats(a->k_below, a->k_above, total) * sizeof(float))
-    return fail(E, "table workspace too small");
   const int64_t blocks = n_chunks_of(a->n_cand) * a->n_ids;
   if (int rc = check_scratch(E, blocks, joint_scratch_need(a->n_ids, a->n_cand), scratch, scratch_bytes)) return rc;
 
   QuantK qk;
   fill_joint(qk.m.j, a, Dc, cand_base, cand, l_out, g_out, scratch);
-  fill_mixed(qk.m, a);
+  fill_cat_slots(qk.m, a); fill_cat_draw(qk.m, a); fill_cat_score(qk.m, a);
   qk.Dq = Dq; qk.total = (int)total;
   qk.edges = a->quant_edges; qk.qsamp = a->quant_samp;
   qk.bT = a->quant_table; qk.aT = a->quant_table + total * a->k_below;
-  // a quantised dimension's bounds (its outer edges): low / high [Dc + d]
-  QTabK tb, ta;
-  int voff = 0;
-  for (int d = 0; d < TPE_JOINT_MAX_QUANT; ++d) {
-    const bool in = d < Dq;
-    qk.V[d] = tb.V[d] = in ? a->quant_v[d] : 2;
-    qk.voff[d] = tb.voff[d] = in ? voff : 0;
-    qk.eoff[d] = tb.eoff[d] = in ? a->quant_edge_off[d] : 0;
-    qk.qlo[d] = -INFINITY; qk.qhi[d] = INFINITY;
-    if (in) {
-      f32_bounds(a->low[Dc + d], a->high[Dc + d], qk.qlo[d], qk.qhi[d]);
-      voff += a->quant_v[d];
-    }
-  }
+  QTabK tb;
+  fill_quant_slots(tb, qk.qlo, qk.qhi, a);
+  memcpy(qk.V, tb.V, sizeof tb.V); memcpy(qk.voff, tb.voff, sizeof tb.voff); memcpy(qk.eoff, tb.eoff, sizeof tb.eoff);
   qk.tile = quant_tile((int)total); qk.stride = qk.tile + 4;
 
   const bool timed = g_prof.on != 0;
   hipStream_t s = (hipStream_t)stream;
-  if (timed)
-    if (int rc = ensure_events(g_qprof.ev, 2)) return rc;
-  tb.K = a->k_below; tb.Dq = Dq; tb.mu = a->below_qmu; tb.sigma = a->below_qsigma; tb.edges = a->quant_edges;
-  tb.T = a->quant_table;
-  ta = tb;
-  ta.K = a->k_above; ta.mu = a->above_qmu; ta.sigma = a->above_qsigma; ta.T = a->quant_table + total * a->k_below;
-  const dim3 gb((unsigned)((a->k_below + kThreads - 1) / kThreads), (unsigned)Dq);
-  const dim3 ga((unsigned)((a->k_above + kThreads - 1) / kThreads), (unsigned)Dq);
-  launch(k_joint_qtable, gb, kThreads, 0u, s, timed ? g_qprof.ev[0] : nullptr, nullptr, tb);
-  launch(k_joint_qtable, ga, kThreads, 0u, s, nullptr, timed ? g_qprof.ev[1] : nullptr, ta);
-  if (timed) g_qprof.valid = 1;
+  if (int rc = launch_qtables(tb, a, total, s, timed)) return rc;
 
   const Ev ev = chunk_marks(timed);
   for_cp<8>(Dc, [&](auto cp) {
