@@ -240,6 +240,24 @@ class JointSegArgs(ctypes.Structure):
     ]
 
 
+class JointWideSeg(ctypes.Structure):
+    """tpe_joint_wide_seg: the device descriptor of one group of a tpe_joint_wide_seg_run (tpe_joint_seg with
+    JOINT_WIDE_MAX_DIMS bounds)."""
+    _fields_ = JointSeg._fields_[:-2] + [
+        ('lo', ctypes.c_float * JOINT_WIDE_MAX_DIMS), ('hi', ctypes.c_float * JOINT_WIDE_MAX_DIMS)]
+
+
+# numpy mirror of tpe_joint_wide_seg
+JOINT_WIDE_SEG_DTYPE = np.dtype(JOINT_SEG_DTYPE.descr[:-2] + [
+    ('lo', '<f4', (JOINT_WIDE_MAX_DIMS,)), ('hi', '<f4', (JOINT_WIDE_MAX_DIMS,))])
+assert JOINT_WIDE_SEG_DTYPE.itemsize == ctypes.sizeof(JointWideSeg) == 616
+
+
+class JointWideSegArgs(ctypes.Structure):
+    """tpe_joint_wide_seg_args: one tpe_joint_wide_seg_run (tpe_joint_seg_args' fields)."""
+    _fields_ = list(JointSegArgs._fields_)
+
+
 JOINT_MSEG_MAX_CONT = 8        # TPE_JOINT_MSEG_MAX_CONT: continuous coordinates beside a discrete / quantised one
 JOINT_MSEG_MAX_CAT = 4         # TPE_JOINT_MSEG_MAX_CAT: discrete coordinates of a segment
 
@@ -553,7 +571,8 @@ EXPORTS = ('tpe_abi_version', 'tpe_last_error', 'tpe_device_count', 'tpe_tile_si
            'tpe_joint_wide_mixed_scratch_bytes', 'tpe_joint_wide_mixed_run',
            'tpe_joint_wide_quant_scratch_bytes', 'tpe_joint_wide_quant_run', 'tpe_joint_wide_quant_profile',
            'tpe_joint_seg_scratch_bytes', 'tpe_joint_seg_run', 'tpe_joint_mseg_scratch_bytes',
-           'tpe_joint_mseg_table_bytes', 'tpe_joint_mseg_run', 'tpe_joint_report_scratch_bytes',
+           'tpe_joint_mseg_table_bytes', 'tpe_joint_mseg_run', 'tpe_joint_wide_seg_scratch_bytes',
+           'tpe_joint_wide_seg_run', 'tpe_joint_report_scratch_bytes',
            'tpe_joint_report', 'tpe_joint_report_profile', 'tpe_joint_run_shard', 'tpe_joint_liar_scratch_bytes',
            'tpe_joint_liar', 'tpe_joint_liar_mixed_scratch_bytes', 'tpe_joint_liar_mixed',
            'tpe_joint_liar_seg_scratch_bytes', 'tpe_joint_liar_seg', 'tpe_joint_liar_mseg_scratch_bytes',
@@ -704,6 +723,10 @@ def load(path=LIB_PATH):
     lib.tpe_joint_seg_scratch_bytes.restype = ctypes.c_int
     lib.tpe_joint_seg_run.argtypes = [ctypes.POINTER(JointSegArgs), P, P, P, P, P, ctypes.c_uint64, P]
     lib.tpe_joint_seg_run.restype = ctypes.c_int
+    lib.tpe_joint_wide_seg_scratch_bytes.argtypes = [I32, I32, ctypes.POINTER(ctypes.c_uint64)]
+    lib.tpe_joint_wide_seg_scratch_bytes.restype = ctypes.c_int
+    lib.tpe_joint_wide_seg_run.argtypes = [ctypes.POINTER(JointWideSegArgs), P, P, P, P, P, ctypes.c_uint64, P]
+    lib.tpe_joint_wide_seg_run.restype = ctypes.c_int
     lib.tpe_joint_mseg_scratch_bytes.argtypes = [I32, I32, ctypes.POINTER(ctypes.c_uint64)]
     lib.tpe_joint_mseg_scratch_bytes.restype = ctypes.c_int
     lib.tpe_joint_mseg_table_bytes.argtypes = [P, I32, ctypes.POINTER(ctypes.c_uint64)]

@@ -40,6 +40,12 @@
 // k_joint_wide_quant_sample / k_joint_wide_quant_chunk  the wide stage for a
 //                group that also holds up to 4 quantised labels: k_joint_qtable's
 //                tables stream through LDS beside the rows, in one common tile.
+// k_joint_wide_seg_sample / k_joint_wide_seg_chunk  the wide continuous stage
+//                over the (id, group) problems of many groups at once ("wide
+//                segmented stage" below): a workgroup builds the solo kernels'
+//                argument view of its problem from the group's descriptor and
+//                runs their parts; k_joint_seg_order (over the wide classes)
+//                and k_joint_wide_merge serve it.
 // tpe_joint_run_shard  any of the six stages over the candidates [cand_base,
 //                cand_base + n_cand) of a larger run: the views carry cand_base (a
 //                kernel argument: scalar registers), added to the local index
@@ -363,8 +369,9 @@ __device__ __forceinline__ int seg_class(const SegK& p, int s) {
 // order[rank of p] = p, the rank by (kernel class, group, problem index): one
 // thread a problem counts the problems before it.  No atomics; P^2 / 256 reads a
 // workgroup from arrays that sit in L2.
-template <bool MIXED>
-__global__ __launch_bounds__(kThreads) void k_joint_seg_order(const SegK p) {
+// (K: SegK, or the wide segmented stage's WideSegK with its own seg_class)
+template <bool MIXED, typename K>
+__global__ __launch_bounds__(kThreads) void k_joint_seg_order(const K p) {
   const int me = blockIdx.x * kThreads + threadIdx.x;
   if (me >= p.n_probs) return;
   const int sme = p.prob_seg[me];
@@ -1446,6 +1453,23 @@ struct WideDraw {
   int comp;
   float* out;                       // coordinate j goes to out[j * 256]
 };
+// Which of a scoring launch's problems a workgroup serves.  id indexes the
+// view's zsrc blocks, cand and l_out / g_out; chunk is the chunk of that id; slot
+// is the workgroup's place in chunk_rec.  The solo kernels: id * n_chunks + chunk
+// = slot = blockIdx.x.
+struct WideAt {
+  int id, chunk;
+  int64_t slot;
+};
+__device__ __forceinline__ WideAt wide_at(int per_id) {
+  return WideAt{(int)(blockIdx.x / per_id), (int)(blockIdx.x % per_id), (int64_t)blockIdx.x};
+}
+
+// candidate i of the view's id `id`: its stream and its component
+__device__ __forceinline__ void wide_sample_stream(const WideSampK& p, int i, int id, WideDraw& c) {
+  c.st = Stream{p.cand_base + (uint32_t)i, p.stream_word, (uint32_t)p.ids[id], p.key0, p.key1};   // gi < 2^31 (i < C)
+  c.comp = draw_component(c.st, c.w, p.cum, p.kb);
+}
 // false: the thread is past the last candidate.  D: all the group's coordinates.
 __device__ __forceinline__ bool wide_sample_head(const WideSampK& p, int D, WideDraw& c) {
   const int t = threadIdx.x;
@@ -1453,8 +1477,7 @@ __device__ __forceinline__ bool wide_sample_head(const WideSampK& p, int D, Wide
   const int i = blk * kThreads + t;
   if (i >= p.C) return false;
   c.out = p.zbuf + (int64_t)blockIdx.x * kThreads * D + t;
-  c.st = Stream{p.cand_base + (uint32_t)i, p.stream_word, (uint32_t)p.ids[id], p.key0, p.key1};   // gi < 2^31 (i < C)
-  c.comp = draw_component(c.st, c.w, p.cum, p.kb);
+  wide_sample_stream(p, i, id, c);
   return true;
 }
 // the Dc continuous coordinates: k_joint_chunk's draw, operation for operation
@@ -1551,9 +1574,10 @@ struct WideCand {
 // Zero, then the candidates first + r * 256 + t of this workgroup's id from
 // `inject` rows or from zbuf; every register index is a compile-time constant.
 template <int DP, int KP, int QP, int R>
-__device__ __forceinline__ void wide_load(const WideK& p, int Dk, int Dq, WideCand<DP, KP, QP, R>& c) {
+__device__ __forceinline__ void wide_load(const WideK& p, const WideAt& at, int Dk, int Dq,
+                                          WideCand<DP, KP, QP, R>& c) {
   const int t = threadIdx.x, Dc = p.D, D = Dc + Dk + Dq;
-  const int id = blockIdx.x / p.n_chunks, chunk = blockIdx.x % p.n_chunks;
+  const int id = at.id, chunk = at.chunk;
   const int first = chunk * (R * kThreads);
 #pragma unroll
   for (int r = 0; r < R; ++r) {
@@ -1789,10 +1813,11 @@ __device__ __forceinline__ void score_side_wide_quant(const float* __restrict__ 
 // coordinate order in cand and in the record's z: continuous, categories,
 // lattice indices, then zeros.
 template <int DP, int KP, int QP, int R>
-__device__ __forceinline__ void wide_finish(const WideK& p, int Dk, int Dq, const WideCand<DP, KP, QP, R>& c,
-                                            const double (&l2)[R], const double (&g2)[R], Pick* __restrict__ slot) {
+__device__ __forceinline__ void wide_finish(const WideK& p, const WideAt& at, int Dk, int Dq,
+                                            const WideCand<DP, KP, QP, R>& c, const double (&l2)[R],
+                                            const double (&g2)[R], Pick* __restrict__ slot) {
   const int t = threadIdx.x, Dc = p.D, D = Dc + Dk + Dq;
-  const int id = blockIdx.x / p.n_chunks, chunk = blockIdx.x % p.n_chunks;
+  const int id = at.id, chunk = at.chunk;
   const int first = chunk * (R * kThreads);
 
   Pick best{0, 0};
@@ -1822,7 +1847,7 @@ __device__ __forceinline__ void wide_finish(const WideK& p, int Dk, int Dq, cons
   }
   const Pick w = block_best(best, slot);
 
-  tpe_joint_wide_record* rec = p.chunk_rec + blockIdx.x;
+  tpe_joint_wide_record* rec = p.chunk_rec + at.slot;
   if (w.key == 0) {
     if (t == 0) rec->global_idx = -1;
     return;
@@ -1866,13 +1891,13 @@ __global__ __launch_bounds__(kThreads) void k_joint_wide_chunk(const WideK p) {
   const int none[1] = {0};
 
   WideCand<DP, 0, 0, R> c;
-  wide_load(p, 0, 0, c);
+  wide_load(p, wide_at(p.n_chunks), 0, 0, c);
   double l2[R], g2[R];
   score_side_wide<DP, 0, R>(p.bmu, p.ba, p.bc, nullptr, nullptr, nullptr, p.kb, p.D, 0, none, none, c.z, c.v, rows,
                             nullptr, cl, l2);
   score_side_wide<DP, 0, R>(p.amu, p.aa, p.ac, nullptr, nullptr, nullptr, p.ka, p.D, 0, none, none, c.z, c.v, rows,
                             nullptr, cl, g2);
-  wide_finish(p, 0, 0, c, l2, g2, slot);
+  wide_finish(p, wide_at(p.n_chunks), 0, 0, c, l2, g2, slot);
 }
 
 // (This kernel carries wide_load and wide_finish written out, KP slots and no
@@ -2006,7 +2031,7 @@ __global__ __launch_bounds__(kThreads) void k_joint_wide_quant_chunk(const WideQ
   for (int e = threadIdx.x; e < p.stride; e += kThreads) qt[p.total * p.stride + e] = 0.f;   // the padded slots' row
 
   WideCand<DP, KP, QP, R> c;
-  wide_load(p, p.Dk, p.Dq, c);
+  wide_load(p, wide_at(p.n_chunks), p.Dk, p.Dq, c);
   // the lattice value's row in the tile (kept inside the table); a padded slot reads the zero row
   int qo[R][QP];
 #pragma unroll
@@ -2020,7 +2045,7 @@ __global__ __launch_bounds__(kThreads) void k_joint_wide_quant_chunk(const WideQ
                                        p.stride, p.total, U, off, c.z, c.v, qo, rows, cats, cl, qt, l2);
   score_side_wide_quant<DP, KP, QP, R>(p.amu, p.aa, p.ac, p.acat, p.amiss, p.abonus, p.aT, p.ka, p.D, p.Dk, p.tile,
                                        p.stride, p.total, U, off, c.z, c.v, qo, rows, cats, cl, qt, g2);
-  wide_finish(p, p.Dk, p.Dq, c, l2, g2, slot);
+  wide_finish(p, wide_at(p.n_chunks), p.Dk, p.Dq, c, l2, g2, slot);
 }
 
 __global__ __launch_bounds__(64) void k_joint_wide_merge(const tpe_joint_wide_record* __restrict__ chunk_rec,
@@ -2042,6 +2067,98 @@ __global__ __launch_bounds__(64) void k_joint_wide_merge(const tpe_joint_wide_re
   } else {
     *out = rec[w.idx];
   }
+}
+
+// ---------------------------------------------------- wide segmented stage
+// The wide stage over the (id, group) problems of MANY groups at once
+// (include/tpe_hip.h "Wide segmented joint stage"): a workgroup reads its
+// problem's descriptor, builds the solo kernels' argument view of that problem
+// alone (one id, its pointers set to the problem's rows and outputs) and runs
+// the solo kernels' parts, so a problem's bytes are those of a solo launch over
+// its group.
+struct WideSegK {
+  int C, n_chunks, inject, first;   // n_chunks, first: this launch's class (as SegK::first)
+  int n_probs, n_segs, nblk;        // nblk: 256-candidate blocks a problem = chunk_rec's stride
+  uint32_t key0, key1;
+  uint32_t cand_base;
+  const tpe_joint_wide_seg* segs;
+  const float* pool;
+  const double* pool64;
+  const int32_t* prob_seg;
+  const int64_t* prob_id;
+  const int64_t* cand_off;
+  int32_t* order;                   // scratch [n_probs]: the problems by (DP class, group, index)
+  float* cand;
+  double *l_out, *g_out;
+  tpe_joint_wide_record* chunk_rec; // scratch [n_probs * nblk], problem-major
+  float* zbuf;                      // scratch [n_probs] slabs of nblk * 256 * kWD floats; a slab is [nblk][D][256]
+};
+__host__ __device__ __forceinline__ int wide_class(int D) { return D <= 20 ? 0 : D <= 24 ? 1 : D <= 32 ? 2 : D <= 48 ? 3 : 4; }
+template <bool MIXED>
+__device__ __forceinline__ int seg_class(const WideSegK& p, int s) { return wide_class(p.segs[s].n_dims); }
+__device__ __forceinline__ float* wide_seg_slab(const WideSegK& p, int prob) {
+  return p.zbuf + (int64_t)prob * p.nblk * (kThreads * kWD);
+}
+
+// one workgroup per (problem, 256-candidate block), in the caller's problem order
+__global__ __launch_bounds__(kThreads) void k_joint_wide_seg_sample(const WideSegK p) {
+  __shared__ float blo[kWD], bhi[kWD];
+  const int prob = blockIdx.x / p.nblk, blk = blockIdx.x % p.nblk;
+  const tpe_joint_wide_seg* __restrict__ sg = p.segs + uni(p.prob_seg[prob]);
+  if (threadIdx.x < kWD) { blo[threadIdx.x] = sg->lo[threadIdx.x]; bhi[threadIdx.x] = sg->hi[threadIdx.x]; }
+  __syncthreads();
+
+  WideSampK q;                      // (q.lo / q.hi: the parts read the LDS copies)
+  q.D = uni(sg->n_dims); q.C = p.C; q.nblk = p.nblk; q.kb = uni(sg->k_below);
+  q.key0 = p.key0; q.key1 = p.key1; q.stream_word = (uint32_t)uni((int)sg->stream_word);
+  q.cand_base = p.cand_base;
+  q.cum = p.pool64 + uni(sg->samp_cum); q.samp = p.pool + uni(sg->samp);
+  q.ids = p.prob_id; q.zbuf = wide_seg_slab(p, prob);
+  const int i = blk * kThreads + threadIdx.x;
+  if (i >= p.C) return;
+  WideDraw c;                       // wide_sample_head over this problem: block blk of its slab, its id
+  c.out = q.zbuf + (int64_t)blk * kThreads * q.D + threadIdx.x;
+  wide_sample_stream(q, i, prob, c);
+  wide_sample_continuous(q, c, blo, bhi);
+}
+
+// one workgroup per (problem of the launch's DP class, chunk of 256 R candidates)
+template <int DP, int R>
+__global__ __launch_bounds__(kThreads) void k_joint_wide_seg_chunk(const WideSegK p) {
+  static_assert(DP % 4 == 0 && DP <= kWD, "rows are read as float4");
+  constexpr int TK = wide_tile(DP);
+  __shared__ __attribute__((aligned(16))) float rows[TK * 2 * DP];
+  __shared__ float cl[TK];
+  __shared__ Pick slot[kThreads / 64];
+  const int none[1] = {0};
+  const int chunk = blockIdx.x % p.n_chunks;
+  // the problem and its group: the same for every lane, kept in scalar registers
+  const int prob = uni(p.order[p.first + blockIdx.x / p.n_chunks]);
+  const tpe_joint_wide_seg* __restrict__ sg = p.segs + uni(p.prob_seg[prob]);
+
+  WideK k;
+  k.D = uni(sg->n_dims); k.C = p.C; k.n_chunks = p.n_chunks; k.nblk = p.nblk; k.inject = p.inject;
+  k.kb = uni(sg->k_below); k.ka = uni(sg->k_above); k.cand_base = p.cand_base;
+  k.bmu = p.pool + uni(sg->below_mu); k.ba = p.pool + uni(sg->below_a); k.bc = p.pool + uni(sg->below_c);
+  k.amu = p.pool + uni(sg->above_mu); k.aa = p.pool + uni(sg->above_a); k.ac = p.pool + uni(sg->above_c);
+  k.bbase = unid(sg->below_base); k.abase = unid(sg->above_base);
+  k.zsrc = p.inject ? p.pool + uni(sg->inject) : wide_seg_slab(p, prob);
+  k.cand = p.cand ? p.cand + uni(p.cand_off[prob]) : nullptr;
+  k.l_out = p.l_out ? p.l_out + (int64_t)prob * p.C : nullptr;
+  k.g_out = p.g_out ? p.g_out + (int64_t)prob * p.C : nullptr;
+  k.chunk_rec = p.chunk_rec + (int64_t)prob * p.nblk;
+  const WideAt at{0, chunk, (int64_t)chunk};
+  // R = 2: the class has n_chunks <= nblk <= 2 n_chunks records a problem; the merge reads nblk
+  if (R > 1 && threadIdx.x == 0 && p.n_chunks + chunk < p.nblk) k.chunk_rec[p.n_chunks + chunk].global_idx = -1;
+
+  WideCand<DP, 0, 0, R> c;
+  wide_load(k, at, 0, 0, c);
+  double l2[R], g2[R];
+  score_side_wide<DP, 0, R>(k.bmu, k.ba, k.bc, nullptr, nullptr, nullptr, k.kb, k.D, 0, none, none, c.z, c.v, rows,
+                            nullptr, cl, l2);
+  score_side_wide<DP, 0, R>(k.amu, k.aa, k.ac, nullptr, nullptr, nullptr, k.ka, k.D, 0, none, none, c.z, c.v, rows,
+                            nullptr, cl, g2);
+  wide_finish(k, at, 0, 0, c, l2, g2, slot);
 }
 
 // ------------------------------------------------------------- host driver
@@ -2227,6 +2344,15 @@ uint64_t wide_record_bytes(int32_t n_ids, int32_t n_cand, int D) {
 uint64_t wide_scratch_need(int32_t n_ids, int32_t n_cand, int D, int Dk = 0) {
   return wide_record_bytes(n_ids, n_cand, D) +
          (uint64_t)n_ids * (uint64_t)wide_blocks_of(n_cand) * kThreads * (uint64_t)(D + Dk) * sizeof(float);
+}
+// the wide segmented stage: the order, nblk chunk records a problem (the count at
+// R = 1), then a slab of nblk blocks of kWD coordinates a problem
+uint64_t wide_seg_record_bytes(int32_t n_probs, int32_t n_cand) {
+  return (uint64_t)n_probs * (uint64_t)wide_blocks_of(n_cand) * sizeof(tpe_joint_wide_record);
+}
+uint64_t wide_seg_scratch_need(int32_t n_probs, int32_t n_cand) {
+  return seg_order_bytes(n_probs) + wide_seg_record_bytes(n_probs, n_cand) +
+         (uint64_t)n_probs * (uint64_t)wide_blocks_of(n_cand) * kThreads * kWD * sizeof(float);
 }
 // padded continuous width of a wide group with discrete labels: narrow groups too
 template <typename F>
@@ -2764,9 +2890,12 @@ struct SegPlan {
 };
 constexpr int n_classes_of(const tpe_joint_seg*) { return 8; }
 constexpr int n_classes_of(const tpe_joint_mseg*) { return kMClasses; }
+constexpr int n_classes_of(const tpe_joint_wide_seg*) { return 5; }
 
-int check_segment(const char* entry, const tpe_joint_seg_args* a, const tpe_joint_seg& g, bool inject, SegPlan&) {
-  if (g.n_dims < 1 || g.n_dims > TPE_JOINT_MAX_DIMS) return fail(entry, "n_dims outside [1, TPE_JOINT_MAX_DIMS]", kSegs);
+// a continuous segment, narrow or wide: its counts and its rows' places
+template <typename A, typename Seg>
+int check_cont_segment(const char* entry, const A* a, const Seg& g, bool inject, int max_dims, const char* range) {
+  if (g.n_dims < 1 || g.n_dims > max_dims) return fail(entry, range, kSegs);
   if (g.k_below < 1 || g.k_above < 1) return fail(entry, "k_below < 1 or k_above < 1", kSegs);
   const int64_t D = g.n_dims, kb = g.k_below, ka = g.k_above, L = a->pool_f32_len;
   bool ok = inside(g.below_mu, kb * D, L) && inside(g.below_a, kb * D, L) && inside(g.below_c, kb, L) &&
@@ -2775,6 +2904,13 @@ int check_segment(const char* entry, const tpe_joint_seg_args* a, const tpe_join
   if (inject && g.inject >= 0) ok = ok && inside(g.inject, (int64_t)a->n_cand * D, L);
   if (!ok) return fail(entry, "rows leave its pool", kSegs);
   return TPE_OK;
+}
+int check_segment(const char* entry, const tpe_joint_seg_args* a, const tpe_joint_seg& g, bool inject, SegPlan&) {
+  return check_cont_segment(entry, a, g, inject, TPE_JOINT_MAX_DIMS, "n_dims outside [1, TPE_JOINT_MAX_DIMS]");
+}
+int check_segment(const char* entry, const tpe_joint_wide_seg_args* a, const tpe_joint_wide_seg& g, bool inject,
+                  SegPlan&) {
+  return check_cont_segment(entry, a, g, inject, TPE_JOINT_WIDE_MAX_DIMS, "n_dims outside [1, TPE_JOINT_WIDE_MAX_DIMS]");
 }
 
 int check_segment(const char* entry, const tpe_joint_mseg_args* a, const tpe_joint_mseg& g, bool inject, SegPlan& plan) {
@@ -2828,6 +2964,7 @@ int check_segment(const char* entry, const tpe_joint_mseg_args* a, const tpe_joi
 
 // the kernel class of a segment that has a problem
 int segment_class(const tpe_joint_seg& g, SegPlan&) { return dp_class(g.n_dims); }
+int segment_class(const tpe_joint_wide_seg& g, SegPlan&) { return wide_class(g.n_dims); }
 int segment_class(const tpe_joint_mseg& g, SegPlan& plan) {
   const int c = mseg_class(g.n_dims, g.n_cat, g.n_quant);
   if (g.n_quant > 0) {                     // the segment's own tile (the solo run's rule); the launch takes the largest
@@ -2868,11 +3005,31 @@ void launch_class(const tpe_joint_mseg*, int c, const MSegK& k, unsigned blocks,
   }
 }
 
-template <typename A>
-int joint_seg_run_at(const char* E, const A* a, tpe_joint_record* records, float* cand, double* l_out, double* g_out,
+constexpr int kWideDpOf[5] = {20, 24, 32, 48, 64};   // (wide_class's numbering)
+void launch_class(const tpe_joint_wide_seg*, int c, const WideSegK& k, unsigned blocks, unsigned, hipStream_t s, Ev ev) {
+  for_wide_dp(kWideDpOf[c], [&](auto dp) {
+    constexpr int DP = decltype(dp)::value;
+    launch(k_joint_wide_seg_chunk<DP, wide_r(DP)>, dim3(blocks), kThreads, 0u, s, ev.start, ev.stop, k);
+  });
+}
+
+// the merge kernel of a stage's record
+auto merge_of(const tpe_joint_record*) { return &k_joint_merge; }
+auto merge_of(const tpe_joint_wide_record*) { return &k_joint_wide_merge; }
+
+// the stages' kernel arguments: SegK (inside MSegK, whose table the mixed stage
+// adds) or WideSegK, which names the shared fields alike
+SegK& seg_view(MSegK& mk) { return mk.s; }
+WideSegK& seg_view(WideSegK& k) { return k; }
+
+template <typename A, typename Rec>
+int joint_seg_run_at(const char* E, const A* a, Rec* records, float* cand, double* l_out, double* g_out,
                      void* scratch, uint64_t scratch_bytes, void* stream, uint32_t cand_base) {
   using Seg = std::remove_cv_t<std::remove_pointer_t<decltype(A::host_segs)>>;
   constexpr bool MIXED = std::is_same<Seg, tpe_joint_mseg>::value;
+  constexpr bool WIDE = std::is_same<Seg, tpe_joint_wide_seg>::value;
+  static_assert(std::is_same<Rec, std::conditional_t<WIDE, tpe_joint_wide_record, tpe_joint_record>>::value,
+                "the stage's record");
   constexpr int n_classes = n_classes_of((const Seg*)nullptr);
   tpe_internal_epoch_bump();
   if (!a) return fail(E, "null args");
@@ -2895,22 +3052,28 @@ int joint_seg_run_at(const char* E, const A* a, tpe_joint_record* records, float
     if (inject && a->host_segs[s].inject < 0) return fail(E, "TPE_JOINT_INJECT without candidates");
     ++plan.per_class[segment_class(a->host_segs[s], plan)];
   }
-  const int64_t n_chunks = n_chunks_of(a->n_cand);
+  // the chunk records a problem: the wide stage's count at R = 1, its sampler's grid a problem too
+  const int64_t n_chunks = WIDE ? wide_blocks_of(a->n_cand) : n_chunks_of(a->n_cand);
   if ((int64_t)a->n_segs * n_classes > INT32_MAX) return fail(E, "too many candidates");
-  if (int rc = check_scratch(E, n_chunks * a->n_probs, seg_scratch_need(a->n_probs, a->n_cand), scratch, scratch_bytes))
-    return rc;
+  const uint64_t need = WIDE ? wide_seg_scratch_need(a->n_probs, a->n_cand) : seg_scratch_need(a->n_probs, a->n_cand);
+  if (int rc = check_scratch(E, n_chunks * a->n_probs, need, scratch, scratch_bytes)) return rc;
 
-  MSegK mk;                                 // (the continuous stage's kernels take mk.s alone)
-  SegK& k = mk.s;
+  std::conditional_t<WIDE, WideSegK, MSegK> mk;   // (the continuous stage's kernels take mk.s alone)
+  auto& k = seg_view(mk);
   k.C = a->n_cand; k.n_chunks = (int)n_chunks; k.inject = inject ? 1 : 0; k.first = 0;
   k.n_probs = a->n_probs; k.n_segs = a->n_segs;
   k.key0 = (uint32_t)a->seed; k.key1 = (uint32_t)(a->seed >> 32); k.cand_base = cand_base;
-  k.segs = reinterpret_cast<const tpe_joint_seg*>(a->segs); k.pool = a->pool_f32; k.pool64 = a->pool_f64;
+  k.segs = reinterpret_cast<decltype(k.segs)>(a->segs); k.pool = a->pool_f32; k.pool64 = a->pool_f64;
   k.prob_seg = a->prob_seg; k.prob_id = a->prob_id; k.cand_off = a->cand_off;
   k.order = (int32_t*)scratch;
   k.cand = cand; k.l_out = l_out; k.g_out = g_out;
-  k.chunk_rec = (tpe_joint_record*)((char*)scratch + seg_order_bytes(a->n_probs));
-  mk.table = nullptr;
+  k.chunk_rec = (Rec*)((char*)scratch + seg_order_bytes(a->n_probs));
+  if constexpr (WIDE) {
+    k.nblk = (int)n_chunks;
+    k.zbuf = (float*)((char*)k.chunk_rec + wide_seg_record_bytes(a->n_probs, a->n_cand));
+  } else {
+    mk.table = nullptr;
+  }
 
   const bool timed = g_prof.on != 0;
   hipStream_t s = (hipStream_t)stream;
@@ -2918,8 +3081,8 @@ int joint_seg_run_at(const char* E, const A* a, tpe_joint_record* records, float
     if (int rc = ensure_events(g_sprof.ev, 2 * kSegLaunches)) return rc;
   int n_timed = 0;
   Ev ev = seg_marks(timed, n_timed);
-  launch(k_joint_seg_order<MIXED>, dim3((unsigned)((a->n_probs + kThreads - 1) / kThreads)), kThreads, 0u, s, ev.start,
-         ev.stop, k);
+  launch(k_joint_seg_order<MIXED, std::remove_reference_t<decltype(k)>>,
+         dim3((unsigned)((a->n_probs + kThreads - 1) / kThreads)), kThreads, 0u, s, ev.start, ev.stop, k);
   if constexpr (MIXED) {
     mk.table = a->quant_table;
     if (plan.any_quant) {
@@ -2928,16 +3091,22 @@ int joint_seg_run_at(const char* E, const A* a, tpe_joint_record* records, float
              kThreads, 0u, s, ev.start, ev.stop, mk);
     }
   }
+  if constexpr (WIDE) {                     // the sampler's time is tpe_joint_wide_profile's, as in the solo wide stage
+    g_wprof.valid = 0;
+    if (!inject)
+      if (int rc = launch_wide_samp(k_joint_wide_seg_sample, n_chunks * a->n_probs, s, timed, k)) return rc;
+  }
   int64_t first = 0;
   for (int c = 0; c < n_classes; ++c) {
     if (!plan.per_class[c]) continue;
     k.first = (int)first;
-    launch_class((const Seg*)nullptr, c, mk, (unsigned)(plan.per_class[c] * n_chunks), plan.lds[c], s,
+    int64_t class_chunks = n_chunks;
+    if constexpr (WIDE) k.n_chunks = (int)(class_chunks = wide_chunks_of(a->n_cand, kWideDpOf[c]));
+    launch_class((const Seg*)nullptr, c, mk, (unsigned)(plan.per_class[c] * class_chunks), plan.lds[c], s,
                  seg_marks(timed, n_timed));
     first += plan.per_class[c];
   }
-  return finish(k_joint_merge, (const tpe_joint_record*)k.chunk_rec, (int)n_chunks, records, a->n_probs, s, timed, 2,
-                n_timed);
+  return finish(merge_of(records), (const Rec*)k.chunk_rec, (int)n_chunks, records, a->n_probs, s, timed, 2, n_timed);
 }
 
 }  // namespace
@@ -2989,6 +3158,11 @@ int tpe_joint_seg_scratch_bytes(int32_t n_probs, int32_t n_cand, uint64_t* bytes
 int tpe_joint_mseg_scratch_bytes(int32_t n_probs, int32_t n_cand, uint64_t* bytes) {
   const bool ok = n_probs >= 1 && n_cand >= 1;
   return size_out("tpe_joint_mseg_scratch_bytes", ok, ok ? seg_scratch_need(n_probs, n_cand) : 0, bytes);
+}
+
+int tpe_joint_wide_seg_scratch_bytes(int32_t n_probs, int32_t n_cand, uint64_t* bytes) {
+  const bool ok = n_probs >= 1 && n_cand >= 1;
+  return size_out("tpe_joint_wide_seg_scratch_bytes", ok, ok ? wide_seg_scratch_need(n_probs, n_cand) : 0, bytes);
 }
 
 int tpe_joint_wide_scratch_bytes(int32_t n_ids, int32_t n_cand, int32_t n_dims, uint64_t* bytes) {
@@ -3045,6 +3219,11 @@ int tpe_joint_seg_run(const tpe_joint_seg_args* a, tpe_joint_record* records, fl
 int tpe_joint_mseg_run(const tpe_joint_mseg_args* a, tpe_joint_record* records, float* cand, double* l_out,
                        double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
   return joint_seg_run_at("tpe_joint_mseg_run", a, records, cand, l_out, g_out, scratch, scratch_bytes, stream, 0u);
+}
+
+int tpe_joint_wide_seg_run(const tpe_joint_wide_seg_args* a, tpe_joint_wide_record* records, float* cand,
+                           double* l_out, double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
+  return joint_seg_run_at("tpe_joint_wide_seg_run", a, records, cand, l_out, g_out, scratch, scratch_bytes, stream, 0u);
 }
 
 int tpe_joint_wide_run(const tpe_joint_wide_args* a, tpe_joint_wide_record* records, float* cand, double* l_out,

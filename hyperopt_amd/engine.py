@@ -1492,6 +1492,24 @@ class Engine(object):
         return self._joint_seg_call('tpe_joint_mseg' if mixed else 'tpe_joint_seg', a, P, C, b.cand_off, b.widths,
                                     return_cand, want_lg, report_k, shard)
 
+    def run_joint_wide_segments(self, models, stream_words, prob_seg, prob_id, n_cand, seed, inject=None,
+                                return_cand=False, want_lg=False, report_k=0):
+        """``run_joint_segments`` for continuous groups of up to
+        N.JOINT_WIDE_MAX_DIMS dimensions (tpe_joint_wide_seg_run,
+        include/tpe_hip.h "Wide segmented joint stage"): the same arguments, one
+        upload, one call and one download.  Problem p's results are byte for
+        byte those of ``run_joint_wide`` over its group with that stream word
+        and ids = [prob_id[p]].  Returns the records [P]
+        (N.JOINT_WIDE_RECORD_DTYPE); with ``return_cand`` also a list of P
+        arrays f32 [C, D_group]; with ``want_lg`` also l, g float64 [P, C]; with
+        ``report_k`` also the joint report, as ``run_joint_segments``."""
+        C = int(n_cand)
+        report_k = self._report_k(report_k)
+        b = JP.segment_blob(models, stream_words, prob_seg, prob_id, C, inject, N.JOINT_WIDE_SEG_DTYPE)
+        a = self._joint_seg_args(N.JointWideSegArgs, b, len(models), C, seed, inject)
+        return self._joint_seg_call('tpe_joint_wide_seg', a, len(b.prob_seg), C, b.cand_off, b.widths, return_cand,
+                                    want_lg, report_k, rec_dtype=N.JOINT_WIDE_RECORD_DTYPE)
+
     def _joint_seg_args(self, struct, b, n_segs, C, seed, inject):
         """Upload the blob ``b`` (joint_pack.segment_blob) and fill the args
         ``struct`` of a segmented stage from it."""
@@ -1506,15 +1524,16 @@ class Engine(object):
         a.pool_f32_len, a.pool_f64_len = b.n32, b.n64
         return a
 
-    def _joint_seg_call(self, fn, a, P, C, cand_off, pd, return_cand, want_lg, report_k, shard=None):
-        """What the two segmented stages share: scratch and the result block, the
+    def _joint_seg_call(self, fn, a, P, C, cand_off, pd, return_cand, want_lg, report_k, shard=None,
+                        rec_dtype=N.JOINT_RECORD_DTYPE):
+        """What the segmented stages share: scratch and the result block, the
         native call ``fn``_run, the report, and one transfer of the results."""
         dev_cand, dev_lg = return_cand or report_k > 0, want_lg or report_k > 0
         nb = ctypes.c_uint64(0)
         N.check(getattr(self.lib, fn + '_scratch_bytes')(P, C, ctypes.byref(nb)), self.lib, fn + '_scratch_bytes')
         d_scr = self._buf('joint_scratch', (nb.value + 7) // 8, torch.float64)
         # one result block of 8-byte words: records, l, g, then the candidates (f32 pairs)
-        rec_w = P * N.JOINT_RECORD_DTYPE.itemsize // 8
+        rec_w = P * rec_dtype.itemsize // 8
         lg_w = P * C if dev_lg else 0
         cand_w = (int(cand_off[-1]) + 1) // 2 if dev_cand else 0
         d_out = self._buf('joint_seg_out', rec_w + 2 * lg_w + cand_w, torch.float64)
@@ -1535,7 +1554,7 @@ class Engine(object):
             host[:hi] = d_out[:hi].cpu().numpy()
             if return_cand:
                 host[rec_w + 2 * lg_w:] = d_out[rec_w + 2 * lg_w:rec_w + 2 * lg_w + cand_w].cpu().numpy()
-        rec = host[:rec_w].view(N.JOINT_RECORD_DTYPE).copy()
+        rec = host[:rec_w].view(rec_dtype).copy()
         if not (return_cand or want_lg or report_k):
             return rec
         res = [rec]

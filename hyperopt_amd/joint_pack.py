@@ -15,6 +15,7 @@ The dimension limits by entry point (``_check_dims``):
   'wide_quant' run_joint_wide_quant  Dq >= 1, Dc >= 1, Dk <= JOINT_WIDE_MAX_CAT, 2 <= Dc + Dk + Dq <= JOINT_WIDE_MAX_DIMS
   'segment'  run_joint_segments    a continuous group 1 <= Dc <= JOINT_MAX_DIMS; one with discrete or
                                    quantised parts Dc <= JOINT_MSEG_MAX_CONT, Dk <= JOINT_MSEG_MAX_CAT
+  'wide_segment' run_joint_wide_segments  1 <= Dc <= JOINT_WIDE_MAX_DIMS, continuous only
 and Dq <= JOINT_MAX_QUANT everywhere.
 """
 import collections
@@ -95,8 +96,11 @@ def _check_dims(entry, Dc, Dk, Dq):
                              'quantised one, not %d and %d' % (N.JOINT_WIDE_MAX_CAT, Dk, Dq))
         if not 1 <= Dc + Dk <= N.JOINT_WIDE_MAX_DIMS:
             raise ValueError('joint stage: %d dimensions, at most %d' % (Dc + Dk, N.JOINT_WIDE_MAX_DIMS))
+    elif entry == 'wide_segment' and (Dk or Dq):
+        raise ValueError('joint stage: a wide segment holds continuous dimensions only, not %d discrete and %d '
+                         'quantised ones' % (Dk, Dq))
     else:
-        top = N.JOINT_WIDE_MAX_DIMS if entry == 'wide' else N.JOINT_MAX_DIMS
+        top = N.JOINT_WIDE_MAX_DIMS if entry in ('wide', 'wide_segment') else N.JOINT_MAX_DIMS
         if not 1 <= Dc + Dk <= top:
             raise ValueError('joint stage: %d dimensions, at most %d' % (Dc + Dk, top))
 
@@ -200,7 +204,8 @@ SECTIONS = ('segs', 'pool_f64', 'prob_id', 'cand_off', 'pool_f32', 'prob_seg')
 def segment_blob(models, stream_words, prob_seg, prob_id, n_cand, inject, seg_dtype, empty_ok=False):
     """The upload of a segmented stage (Engine.run_joint_segments' arguments):
     per group its descriptor (``seg_dtype``: N.JOINT_SEG_DTYPE, continuous
-    groups only, or N.JOINT_MSEG_DTYPE) and its group_rows in the two pools,
+    groups only, N.JOINT_WIDE_SEG_DTYPE, continuous groups of up to
+    JOINT_WIDE_MAX_DIMS labels, or N.JOINT_MSEG_DTYPE) and its group_rows in the two pools,
     in the order of ROWS with the group's inject rows last; a continuous group
     is the case Dk = Dq = 0.  The descriptors carry the f32 bounds
     (joint.f32_bounds), padded with -+inf.  ``empty_ok``: n_cand = 0 is allowed
@@ -222,6 +227,7 @@ def segment_blob(models, stream_words, prob_seg, prob_id, n_cand, inject, seg_dt
     if inject is not None and len(inject) != S:
         raise ValueError('joint stage: inject must hold one entry per group')
     mixed = 'n_cat' in seg_dtype.names
+    entry = 'wide_segment' if seg_dtype['lo'].shape == (N.JOINT_WIDE_MAX_DIMS,) else 'segment'
     segs = np.zeros(S, dtype=seg_dtype)
     pools = {4: [], 8: []}
     fill = {4: 0, 8: 0}
@@ -235,7 +241,7 @@ def segment_blob(models, stream_words, prob_seg, prob_id, n_cand, inject, seg_dt
     dims = np.empty(S, dtype=np.int64)
     n_table = 0
     for s, group in enumerate(groups):
-        r = group_rows(*group)
+        r = group_rows(*group, entry=entry)
         Dc, Dk, Dq = r['Dc'], r['Dk'], r['Dq']
         D = dims[s] = Dc + Dk + Dq
         g = segs[s]

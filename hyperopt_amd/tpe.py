@@ -46,7 +46,8 @@ Extensions over the reference (keyword-only, defaults keep its behaviour):
     conditional branch, one group per (gate, option), each id under the model
     of the branch it takes (DESIGN.md "Branch groups");
     ``joint_branches_mixed=True`` lets joint_discrete / joint_quantized widen
-    those branch groups too.
+    those branch groups too, ``joint_branches_wide=True`` lets joint_wide
+    widen them to 17 to 64 continuous labels.
 
 ``linear_forgetting`` is accepted and, as in the reference, not used: the
 forgetting window is fixed at DEFAULT_LF=25 (tpe.py:27-29).
@@ -845,8 +846,8 @@ def suggest(new_ids, domain, trials, seed,
             linear_forgetting=_default_linear_forgetting,
             sampler='philox', precision='fp32', device=None, shard=None, shard_ids=None, shard_labels=None,
             shard_grid=None, joint=False, joint_discrete=False, joint_quantized=False, joint_wide=False,
-            joint_branches=False, joint_branches_mixed=False, joint_shard=None, joint_wide_mixed=False,
-            joint_wide_quantized=False, joint_liar=False):
+            joint_branches=False, joint_branches_mixed=False, joint_branches_wide=False, joint_shard=None,
+            joint_wide_mixed=False, joint_wide_quantized=False, joint_liar=False):
     new_ids = list(new_ids)
     if not new_ids:
         return []
@@ -856,12 +857,13 @@ def suggest(new_ids, domain, trials, seed,
     if liar_mode:
         _joint_liar_check(joint, joint_shard, mode=liar_mode, joint_branches=joint_branches)
     if ((joint is not False and joint is not None) or joint_discrete or joint_quantized or joint_wide or joint_branches
-            or joint_branches_mixed or joint_wide_mixed or joint_wide_quantized):
+            or joint_branches_mixed or joint_branches_wide or joint_wide_mixed or joint_wide_quantized):
         # (argument errors first: no device use, no startup draw)
         plan = _joint_plan(domain.table, joint, sampler, precision, (shard, shard_ids, shard_labels, shard_grid),
                            joint_discrete, joint_quantized,
-                           _wide_mode(joint_wide, joint_wide_mixed, joint_wide_quantized), joint_branches,
-                           joint_branches_mixed)
+                           _wide_mode(joint_wide, joint_wide_mixed, joint_wide_quantized),
+                           _branch_mode(joint_branches, joint_branches_wide, joint_wide), joint_branches_mixed)
+        _branch_wide_check(plan, joint_shard, liar_mode)
         if liar_mode:
             _joint_liar_check(joint, joint_shard, plan, liar_mode, joint_branches)
             _wide_quant_liar_check(plan[0], liar_mode)
@@ -881,7 +883,8 @@ def suggest(new_ids, domain, trials, seed,
                               shard_labels=shard_labels, shard_grid=shard_grid, joint=joint,
                               joint_discrete=joint_discrete, joint_quantized=joint_quantized, joint_wide=joint_wide,
                               joint_branches=joint_branches, joint_branches_mixed=joint_branches_mixed,
-                              joint_shard=joint_shard, joint_wide_mixed=joint_wide_mixed,
+                              joint_branches_wide=joint_branches_wide, joint_shard=joint_shard,
+                              joint_wide_mixed=joint_wide_mixed,
                               joint_wide_quantized=joint_wide_quantized, joint_liar=joint_liar)
     logger.info('tpe.suggest took %f seconds', time.time() - t0)
     return rand.docs_from_choices(new_ids, domain, trials, choices)
@@ -924,7 +927,8 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
                     sampler='philox', precision='fp32', device=None, shard=None, columns=False,
                     shard_ids=None, shard_labels=None, shard_grid=None, joint=False, joint_discrete=False,
                     joint_quantized=False, joint_wide=False, joint_branches=False, joint_branches_mixed=False,
-                    joint_shard=None, joint_wide_mixed=False, joint_wide_quantized=False, joint_liar=False):
+                    joint_branches_wide=False, joint_shard=None, joint_wide_mixed=False, joint_wide_quantized=False,
+                    joint_liar=False):
     """The suggest core on a structure-of-arrays history (``history.History``):
     per new id a {label: value or None} dict.  ``suggest`` wraps it with the
     Trials document layout; columnar callers (and bench.py's large configs)
@@ -1037,6 +1041,21 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
     quantised value is a multiple of q.  Without the keyword every plan and
     every output byte is what ``joint_branches`` alone gives.
 
+    ``joint_branches_wide=True`` (with ``joint_branches`` and ``joint_wide``):
+    ``joint_wide`` widens the branch groups too (DESIGN.md "Wide branch
+    groups"): a branch group of continuous labels only may hold 2 to 64 labels
+    (more raises ValueError).  The grouping, the model (fitted on the trials
+    that took the branch), the ids a group applies to and its stream word are
+    those of ``joint_branches``.  Groups of at most 16 labels and every group
+    with a discrete or quantised label keep their plan, their stage and their
+    bytes; the groups of 17 to 64 labels of a suggest are scored by one call of
+    the wide segmented stage (Engine.run_joint_wide_segments), each (id, group)
+    problem byte for byte as Engine.run_joint_wide scores it alone.  A branch
+    group of more than 16 labels with a discrete or quantised one,
+    ``joint_shard`` and ``joint_liar='branches'`` / ``'branches_mixed'`` on a
+    plan that holds a wide branch group raise ValueError.  Without the keyword
+    17 labels under a gate raise as before.
+
     ``joint_shard=(rank, world)`` (with ``joint`` and any of the keywords
     above): the candidates of every joint stage are split over the ranks of the
     default process group (DESIGN.md "Sharded joint stage").  The univariate
@@ -1103,12 +1122,14 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
         _joint_liar_check(joint, joint_shard, mode=liar_mode, joint_branches=joint_branches)
     group, branch_groups = None, []
     if ((joint is not False and joint is not None) or joint_discrete or joint_quantized or joint_wide or joint_branches
-            or joint_branches_mixed or joint_wide_mixed or joint_wide_quantized):
+            or joint_branches_mixed or joint_branches_wide or joint_wide_mixed or joint_wide_quantized):
         group, branch_groups = _joint_plan(table, joint, sampler, precision,
                                            (shard, shard_ids, shard_labels, shard_grid), joint_discrete,
                                            joint_quantized,
                                            _wide_mode(joint_wide, joint_wide_mixed, joint_wide_quantized),
-                                           joint_branches, joint_branches_mixed)
+                                           _branch_mode(joint_branches, joint_branches_wide, joint_wide),
+                                           joint_branches_mixed)
+        _branch_wide_check((group, branch_groups), joint_shard, liar_mode)
         if liar_mode:
             _joint_liar_check(joint, joint_shard, (group, branch_groups), liar_mode, joint_branches)
             _wide_quant_liar_check(group, liar_mode)
@@ -1290,6 +1311,57 @@ def _wide_mode(joint_wide, joint_wide_mixed, joint_wide_quantized=False):
     if not joint_wide:
         raise ValueError('joint_wide_mixed=True needs joint_wide=True: it only widens the wide groups')
     return WIDE_QUANT_MIXED if joint_wide_quantized else WIDE_MIXED
+
+
+BRANCH_WIDE = 'wide'                  # joint_branches_wide: the ``branches`` argument of _joint_plan
+
+
+def _branch_mode(joint_branches, joint_branches_wide, joint_wide):
+    """The ``branches`` argument of _joint_plan: ``joint_branches`` as given, or
+    BRANCH_WIDE where ``joint_branches_wide`` lets ``joint_wide`` widen the
+    branch groups too; ValueError for that keyword without one of the two."""
+    if not joint_branches_wide:
+        return joint_branches
+    if not joint_branches:
+        raise ValueError('joint_branches_wide=True needs joint_branches=True: it only widens the branch groups')
+    if not joint_wide:
+        raise ValueError('joint_branches_wide=True needs joint_wide=True: it lets that keyword widen the branch groups')
+    return BRANCH_WIDE
+
+
+def _is_wide_branch(rows):
+    """A branch group that the wide segmented stage takes (it is continuous: _branch_limit)."""
+    return len(rows) > TPE_JOINT_MAX_DIMS
+
+
+def _branch_wide_check(plan, joint_shard, liar_mode):
+    """ValueError where a plan that holds a wide branch group (joint_branches_wide)
+    meets ``joint_shard`` or a ``joint_liar`` for branch groups: the wide
+    segmented stage has neither.  Touches no device."""
+    wide = [rows for rows in plan[1] if _is_wide_branch(rows)]
+    if not wide:
+        return
+    key = _branch_condition(wide[0][0])
+    where = 'the branch group under option %d of gate %r has %d labels' % (key[1], key[0], len(wide[0]))
+    if joint_shard is not None:
+        raise ValueError('joint_branches_wide=True does not combine with joint_shard: %s, and the wide segmented stage '
+                         'is not sharded' % where)
+    if liar_mode in ('branches', 'branches_mixed'):
+        raise ValueError('joint_liar=%r does not combine with joint_branches_wide=True: %s, and the batch-aware picks '
+                         'take branch groups of at most TPE_JOINT_MAX_DIMS = %d labels'
+                         % (liar_mode, where, TPE_JOINT_MAX_DIMS))
+
+
+def _branch_stages(engine, groups):
+    """[(Engine call, indices into ``groups``)] of the segmented stages that
+    serve the branch groups ``groups`` (each in kernel coordinate order): the
+    groups of at most TPE_JOINT_MAX_DIMS labels and the mixed ones through
+    Engine.run_joint_segments, the wide ones through
+    Engine.run_joint_wide_segments; a part without groups is left out."""
+    narrow = [i for i, rows in enumerate(groups) if not _is_wide_branch(rows)]
+    wide = [i for i, rows in enumerate(groups) if _is_wide_branch(rows)]
+    return ([(engine.run_joint_segments, narrow)] if narrow else []) + \
+        ([(engine.run_joint_wide_segments, wide)] if wide else [])
 
 
 def _joint_group(table, joint, sampler, precision, shards, discrete=False, quantized=False, wide=False):
@@ -1526,14 +1598,20 @@ def _branch_mixed_reason(row, table, discrete, quantized):
     return why
 
 
-def _branch_mixed_limit(key, rows):
+def _branch_mixed_limit(key, rows, wide=False):
     """``rows`` of the branch group under ``key``, or ValueError where it
     exceeds what the segmented stage takes: a group with a discrete or
     quantised label is bound by the quantised stage's limits (they bound the
-    set of compiled kernels), a continuous one by _branch_limit."""
+    set of compiled kernels), a continuous one by _branch_limit.  ``wide``
+    (joint_branches_wide) widens the continuous groups only."""
     crows, drows, qrows = _joint_kernel_order(rows)
     if not drows and not qrows:
-        return _branch_limit(key, rows)
+        return _branch_limit(key, rows, wide)
+    if wide and len(rows) > TPE_JOINT_MAX_DIMS:
+        raise ValueError('joint with joint_branches_wide=True: the branch group under option %d of gate %r has %d '
+                         'labels, more than TPE_JOINT_MAX_DIMS = %d, and %r is discrete or quantised: a wide branch '
+                         'group holds continuous labels only: pass the labels to join as joint=[...]'
+                         % (key[1], key[0], len(rows), TPE_JOINT_MAX_DIMS, (drows + qrows)[0].label))
     head = 'joint with joint_branches_mixed=True: the branch group under option %d of gate %r has ' % (key[1], key[0])
     tail = ': pass the labels to join as joint=[...]'
     n_cats = sum(int(r.args['upper']) for r in drows)
@@ -1555,8 +1633,12 @@ def _branch_mixed_limit(key, rows):
     return rows
 
 
-def _branch_limit(key, rows):
-    if len(rows) > TPE_JOINT_MAX_DIMS:
+def _branch_limit(key, rows, wide=False):
+    if wide and len(rows) > TPE_JOINT_WIDE_MAX_DIMS:
+        raise ValueError('joint with joint_branches_wide=True: the branch group under option %d of gate %r has %d '
+                         'labels, more than TPE_JOINT_WIDE_MAX_DIMS = %d: pass the labels to join as joint=[...]'
+                         % (key[1], key[0], len(rows), TPE_JOINT_WIDE_MAX_DIMS))
+    if not wide and len(rows) > TPE_JOINT_MAX_DIMS:
         raise ValueError('joint with joint_branches=True: the branch group under option %d of gate %r has %d labels, '
                          'more than TPE_JOINT_MAX_DIMS = %d: pass the labels to join as joint=[...]'
                          % (key[1], key[0], len(rows), TPE_JOINT_MAX_DIMS))
@@ -1573,7 +1655,9 @@ def _joint_plan(table, joint, sampler, precision, shards, discrete=False, quanti
     first label.  ``branch_mixed``: ``discrete`` / ``quantized`` also admit
     conditional discrete / quantised labels with exactly one parent to the
     group of their condition (_branch_mixed_reason, _branch_mixed_limit).
-    ``wide`` (_wide_mode, WIDE_QUANT among its values) widens the root group only (_joint_limits).
+    ``wide`` (_wide_mode, WIDE_QUANT among its values) widens the root group only (_joint_limits),
+    unless ``branches`` is BRANCH_WIDE (_branch_mode): then a branch group of continuous
+    labels holds up to TPE_JOINT_WIDE_MAX_DIMS of them.
     ValueError as _joint_group; touches no device."""
     if not branches:
         if branch_mixed:
@@ -1581,7 +1665,10 @@ def _joint_plan(table, joint, sampler, precision, shards, discrete=False, quanti
         return _joint_group(table, joint, sampler, precision, shards, discrete, quantized, wide), []
     _joint_restrictions(joint, sampler, precision, shards, discrete, quantized, wide, True, branch_mixed)
     parts = {}
-    limit = _branch_mixed_limit if branch_mixed else _branch_limit
+    branch_wide = isinstance(branches, str) and branches == BRANCH_WIDE
+
+    def limit(key, rows):
+        return (_branch_mixed_limit if branch_mixed else _branch_limit)(key, rows, branch_wide)
 
     def conditional(r):
         return any(p is not None for p in r.parents)
@@ -1779,8 +1866,21 @@ def _suggest_branches(engine, hist, ids, seed, prior_weight, n_EI_candidates, ga
                 centres=[m.centres() if hasattr(m, 'centres') else None for m in models])
         else:
             rec = engine.run_joint_segments_liar(models, words, prob_seg, prob_id, int(n_EI_candidates), seed, liar=W)
-    elif parts is None:
+    elif parts is None and not any(_is_wide_branch(w[0]) for w in where):
         rec = engine.run_joint_segments(models, words, prob_seg, prob_id, int(n_EI_candidates), seed)
+    elif parts is None:
+        # joint_branches_wide: the wide groups' problems in one call of their own, the others' in the call above
+        rec = np.zeros(len(prob_seg), dtype=N.JOINT_WIDE_RECORD_DTYPE)
+        seg = np.asarray(prob_seg)
+        for run, sel in _branch_stages(engine, [w[0] for w in where]):
+            local = np.full(len(models), -1)
+            local[sel] = np.arange(len(sel))
+            at = np.flatnonzero(local[seg] >= 0)
+            got = run([models[i] for i in sel], [words[i] for i in sel], local[seg[at]],
+                      np.asarray(prob_id, dtype=np.int64)[at], int(n_EI_candidates), seed)
+            for f in ('global_idx', 'l', 'g'):
+                rec[f][at] = got[f]
+            rec['z'][at, :got['z'].shape[1]] = got['z']
     else:
         rec = parts.records(lambda: engine.run_joint_segments(models, words, prob_seg, prob_id, parts.n_cand, seed,
                                                               shard=parts.shard), len(prob_seg), N.JOINT_RECORD_DTYPE)
@@ -2093,7 +2193,7 @@ def joint_candidate_report_columns(table, hist, new_id, seed, k=8, joint=True, j
                                    joint_quantized=False, joint_wide=False, joint_branches=False,
                                    prior_weight=_default_prior_weight, n_EI_candidates=_default_n_EI_candidates,
                                    gamma=_default_gamma, device=None, joint_branches_mixed=False,
-                                   joint_wide_mixed=False, joint_wide_quantized=False):
+                                   joint_branches_wide=False, joint_wide_mixed=False, joint_wide_quantized=False):
     """``joint_candidate_report`` on a structure-of-arrays history (as
     ``candidate_report_columns`` is to ``candidate_report``)."""
     k = _report_check_k(k)
@@ -2101,7 +2201,8 @@ def joint_candidate_report_columns(table, hist, new_id, seed, k=8, joint=True, j
         raise ValueError('joint_candidate_report needs joint=True or joint=[labels]')
     group, branch_groups = _joint_plan(table, joint, 'philox', 'fp32', (None, None, None, None), joint_discrete,
                                        joint_quantized,
-                                       _wide_mode(joint_wide, joint_wide_mixed, joint_wide_quantized), joint_branches,
+                                       _wide_mode(joint_wide, joint_wide_mixed, joint_wide_quantized),
+                                       _branch_mode(joint_branches, joint_branches_wide, joint_wide),
                                        joint_branches_mixed)
     if len(hist) == 0:
         raise ValueError('joint_candidate_report needs a history: no completed trial to fit the models from')
@@ -2125,19 +2226,23 @@ def joint_candidate_report_columns(table, hist, new_id, seed, k=8, joint=True, j
             fits = [_fit_branch_model(rows, hist, below_tids, prior_weight) for rows in branch_groups[lo:lo + per_run]]
             part, models = [f[0] for f in fits], [f[1] for f in fits]
             words = [_joint.branch_stream_word(rows) for rows in part]
-            out = engine.run_joint_segments(models, words, np.arange(len(part)), np.repeat(ids, len(part)), C, seed,
-                                            report_k=k)
-            top, z, nt, st = out[-4:]
-            for p, (rows, model) in enumerate(zip(part, models)):
-                groups.append(_joint_group_report(rows, _branch_condition(rows[0]), model, top[p], z[p], nt[p],
-                                                  st[p]))
+            done = {}
+            for run, sel in _branch_stages(engine, part):   # the wide groups through their own stage
+                out = run([models[i] for i in sel], [words[i] for i in sel], np.arange(len(sel)),
+                          np.repeat(ids, len(sel)), C, seed, report_k=k)
+                top, z, nt, st = out[-4:]
+                for p, i in enumerate(sel):
+                    done[i] = _joint_group_report(part[i], _branch_condition(part[i][0]), models[i], top[p], z[p],
+                                                  nt[p], st[p])
+            groups.extend(done[i] for i in range(len(part)))
     return JointCandidateReport(groups)
 
 
 def joint_candidate_report(new_id, domain, trials, seed, k=8, joint=True, joint_discrete=False, joint_quantized=False,
                            joint_wide=False, joint_branches=False, prior_weight=_default_prior_weight,
                            n_EI_candidates=_default_n_EI_candidates, gamma=_default_gamma, device=None,
-                           joint_branches_mixed=False, joint_wide_mixed=False, joint_wide_quantized=False):
+                           joint_branches_mixed=False, joint_branches_wide=False, joint_wide_mixed=False,
+                           joint_wide_quantized=False):
     """The candidate pools behind the joint stages of a ``suggest([new_id],
     domain, trials, seed, joint=..., n_EI_candidates=...)`` with the same joint
     keywords: per joint group the ``k`` best distinct candidate vectors with
@@ -2152,13 +2257,16 @@ def joint_candidate_report(new_id, domain, trials, seed, k=8, joint=True, joint_
     k = _report_check_k(k)
     if joint is not False and joint is not None:
         _joint_plan(domain.table, joint, 'philox', 'fp32', (None, None, None, None), joint_discrete, joint_quantized,
-                    _wide_mode(joint_wide, joint_wide_mixed, joint_wide_quantized), joint_branches,
+                    _wide_mode(joint_wide, joint_wide_mixed, joint_wide_quantized),
+                    _branch_mode(joint_branches, joint_branches_wide, joint_wide),
                     joint_branches_mixed)                    # (argument errors before the history is read)
     hist = _history.extract(domain, trials)
     return joint_candidate_report_columns(domain.table, hist, new_id, seed, k=k, joint=joint,
                                           joint_discrete=joint_discrete, joint_quantized=joint_quantized,
                                           joint_wide=joint_wide, joint_branches=joint_branches,
-                                          joint_branches_mixed=joint_branches_mixed, prior_weight=prior_weight, n_EI_candidates=n_EI_candidates, gamma=gamma,
+                                          joint_branches_mixed=joint_branches_mixed,
+                                          joint_branches_wide=joint_branches_wide, prior_weight=prior_weight,
+                                          n_EI_candidates=n_EI_candidates, gamma=gamma,
                                           device=device, joint_wide_mixed=joint_wide_mixed,
                                           joint_wide_quantized=joint_wide_quantized)
 

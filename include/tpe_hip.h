@@ -1155,8 +1155,9 @@ int tpe_joint_run(const tpe_joint_args* args, tpe_joint_record* records, float* 
 
 /* Profiling only (tools/joint_time.py), as tpe_report_profile: last_ms gets the
  * device times {chunk kernel, merge kernel} of the last profiled tpe_joint_run,
- * tpe_joint_mixed_run, tpe_joint_quant_run, tpe_joint_wide_run or
- * tpe_joint_seg_run (whose first entry sums its launches before the merge). */
+ * tpe_joint_mixed_run, tpe_joint_quant_run, tpe_joint_wide_run,
+ * tpe_joint_seg_run or tpe_joint_wide_seg_run (a segmented run's first entry
+ * sums its launches before the merge; the wide one's without its sampler). */
 int tpe_joint_profile(int32_t enable, double* last_ms);
 
 /* ------------------------------------------------------------------------
@@ -1675,6 +1676,76 @@ int tpe_joint_seg_scratch_bytes(int32_t n_probs, int32_t n_cand, uint64_t* bytes
  * `stream` */
 int tpe_joint_seg_run(const tpe_joint_seg_args* args, tpe_joint_record* records, float* cand, double* l_out,
                       double* g_out, void* scratch, uint64_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Wide segmented joint stage (tpe_joint.hip; additive to ABI 24): the segmented
+ * stage for continuous groups of up to TPE_JOINT_WIDE_MAX_DIMS labels (DESIGN.md
+ * "Wide branch groups").  tpe_joint_wide_seg is tpe_joint_seg with 64 f32 bounds
+ * and n_dims in [1, TPE_JOINT_WIDE_MAX_DIMS]; the pools, the problems and the
+ * args are tpe_joint_seg_args'; the records are tpe_joint_wide_record.
+ *
+ * Defining property: the record, the cand rows, l_out and g_out of problem p =
+ * (prob_id[p], segment prob_seg[p]) are byte for byte those of a
+ * tpe_joint_wide_run over that segment's rows with its stream_word, ids =
+ * [prob_id[p]] and the same seed, n_cand and flags, with and without
+ * TPE_JOINT_INJECT; the order of the problems does not matter.  The device code
+ * is tpe_joint_wide_run's: the kernels below read their problem's descriptor
+ * into scalar registers, build the solo kernels' argument view from it and run
+ * the solo kernels' parts (the sampler steps, wide_load, score_side_wide,
+ * wide_finish).  Launches, all on `stream` with no sync between them:
+ * k_joint_seg_order over the wide classes (ranks the problems by DP class 20,
+ * 24, 32, 48, 64, then segment, then index); k_joint_wide_seg_sample (skipped
+ * under TPE_JOINT_INJECT; one workgroup per problem and block of 256 candidates,
+ * the block's [d][256] floats written to the problem's slab of `scratch`; a
+ * slab is [blocks][n_dims][256] and slabs are TPE_JOINT_WIDE_MAX_DIMS wide
+ * apart); one k_joint_wide_seg_chunk<DP, R> launch per DP class present (one
+ * workgroup per problem of the class and chunk of 256 R candidates, R = 2 for DP
+ * <= 32 and 1 above); k_joint_wide_merge over all problems.  The chunk records
+ * of a problem are ceil(n_cand / 256) apart, the count at R = 1; an R = 2
+ * workgroup marks the slot behind its class's count as empty (global_idx = -1),
+ * so the merge reads one stride.  Plain vector stores, no atomics: the same
+ * call twice gives the same bytes.
+ *
+ * tpe_joint_wide_seg_run returns TPE_E_ARG before any launch (no device needed)
+ * for everything tpe_joint_seg_run checks, with n_dims outside [1,
+ * TPE_JOINT_WIDE_MAX_DIMS] in place of its range and scratch smaller than
+ * tpe_joint_wide_seg_scratch_bytes(n_probs, n_cand).  A segment with no problem
+ * is legal.  tpe_joint_profile covers this stage as it covers tpe_joint_seg_run
+ * (the order kernel and the chunk launches, summed; the merge), and
+ * tpe_joint_wide_profile reads its sampling kernel's time.
+ * ---------------------------------------------------------------------- */
+typedef struct tpe_joint_wide_seg {
+  int32_t n_dims, k_below, k_above;       /* as tpe_joint_seg ... */
+  uint32_t stream_word;
+  double below_base, above_base;
+  int64_t below_mu, below_a, below_c;
+  int64_t above_mu, above_a, above_c;
+  int64_t samp;
+  int64_t inject;
+  int64_t samp_cum;
+  float lo[TPE_JOINT_WIDE_MAX_DIMS], hi[TPE_JOINT_WIDE_MAX_DIMS];   /* ... with 64 bounds */
+} tpe_joint_wide_seg;
+typedef struct tpe_joint_wide_seg_args {
+  int32_t n_segs, n_probs, n_cand, flags;   /* as tpe_joint_seg_args */
+  uint64_t seed;
+  const tpe_joint_wide_seg* segs;
+  const tpe_joint_wide_seg* host_segs;
+  const float* pool_f32;
+  const double* pool_f64;
+  int64_t pool_f32_len, pool_f64_len;
+  const int32_t* prob_seg;
+  const int32_t* host_prob_seg;
+  const int64_t* prob_id;
+  const int64_t* cand_off;
+} tpe_joint_wide_seg_args;
+
+/* the problem order, the chunk records and the candidate slabs of one
+ * tpe_joint_wide_seg_run (sized for 64 coordinates a problem) */
+int tpe_joint_wide_seg_scratch_bytes(int32_t n_probs, int32_t n_cand, uint64_t* bytes);
+
+/* as tpe_joint_seg_run, with tpe_joint_wide_record records */
+int tpe_joint_wide_seg_run(const tpe_joint_wide_seg_args* args, tpe_joint_wide_record* records, float* cand,
+                           double* l_out, double* g_out, void* scratch, uint64_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
  * Mixed segmented joint stage (tpe_joint.hip; additive to ABI 24): the
