@@ -149,6 +149,11 @@ class JointArgs(ctypes.Structure):
     ]
 
 
+class JointF64Args(ctypes.Structure):
+    """tpe_joint_f64_args: one tpe_joint_f64_run (tpe_joint_args with float64 density rows, then the centres)."""
+    _fields_ = JointArgs._fields_ + [('centre', ctypes.c_double * JOINT_MAX_DIMS)]
+
+
 class JointWideArgs(ctypes.Structure):
     """tpe_joint_wide_args: one tpe_joint_wide_run (tpe_joint_args with 64 bounds)."""
     _fields_ = JointArgs._fields_[:-2] + [
@@ -566,6 +571,7 @@ EXPORTS = ('tpe_abi_version', 'tpe_last_error', 'tpe_device_count', 'tpe_tile_si
            'tpe_host_threads', 'tpe_host_phases', 'tpe_exchange_allgather', 'tpe_debug_fast_lg',
            'tpe_collectives_issued', 'tpe_level_resident', 'tpe_level_resident_fused', 'tpe_scatter_f64', 'tpe_move_ranges', 'tpe_report_scratch_bytes', 'tpe_report',
            'tpe_report_profile', 'tpe_joint_scratch_bytes', 'tpe_joint_run', 'tpe_joint_profile',
+           'tpe_joint_f64_scratch_bytes', 'tpe_joint_f64_run',
            'tpe_joint_mixed_run', 'tpe_joint_quant_table_bytes', 'tpe_joint_quant_run', 'tpe_joint_quant_profile',
            'tpe_joint_wide_scratch_bytes', 'tpe_joint_wide_run', 'tpe_joint_wide_profile',
            'tpe_joint_wide_mixed_scratch_bytes', 'tpe_joint_wide_mixed_run',
@@ -695,6 +701,10 @@ def load(path=LIB_PATH):
     lib.tpe_joint_scratch_bytes.restype = ctypes.c_int
     lib.tpe_joint_run.argtypes = [ctypes.POINTER(JointArgs), P, P, P, P, P, ctypes.c_uint64, P]
     lib.tpe_joint_run.restype = ctypes.c_int
+    lib.tpe_joint_f64_scratch_bytes.argtypes = [I32, I32, ctypes.POINTER(ctypes.c_uint64)]
+    lib.tpe_joint_f64_scratch_bytes.restype = ctypes.c_int
+    lib.tpe_joint_f64_run.argtypes = [ctypes.POINTER(JointF64Args), P, P, P, P, P, ctypes.c_uint64, P]
+    lib.tpe_joint_f64_run.restype = ctypes.c_int
     lib.tpe_joint_mixed_run.argtypes = [ctypes.POINTER(JointMixedArgs), P, P, P, P, P, ctypes.c_uint64, P]
     lib.tpe_joint_mixed_run.restype = ctypes.c_int
     lib.tpe_joint_quant_table_bytes.argtypes = [I32, I32, I32, ctypes.POINTER(ctypes.c_uint64)]

@@ -188,6 +188,44 @@ struct ChunkIO {
   tpe_joint_record* rec;            // this workgroup's chunk record
 };
 
+// Candidate i of one problem into z: zeros past the last candidate, the injected
+// row, or the draw of include/tpe_hip.h (one component, then D truncated-normal
+// inversions, clipped to the f32 bounds blo / bhi of the DP padded dimensions).
+template <int DP>
+__device__ __forceinline__ void load_candidate(const ChunkIO& p, const float (&blo)[DP], const float (&bhi)[DP], int i,
+                                               float (&z)[DP]) {
+  const int D = p.D;
+#pragma unroll
+  for (int d = 0; d < DP; ++d) z[d] = 0.f;
+  if (i >= p.C) return;
+  if (p.inject) {
+#pragma unroll
+    for (int d = 0; d < DP; ++d)
+      if (d < D) z[d] = p.inj[(int64_t)i * D + d];
+    return;
+  }
+  const uint32_t c3 = p.c3, gi = p.base + (uint32_t)i;   // gi < 2^31: i < C and base + C <= n_cand_global
+  U4 w = philox4x32_10(gi, 0u, p.stream_word, c3, p.key0, p.key1);
+  const double us = u01w(w.x);
+  int lo = 0, hi = p.kb - 1;             // first k with us < cum[k]
+  while (lo < hi) { const int mid = (lo + hi) >> 1; if (us < p.cum[mid]) hi = mid; else lo = mid + 1; }
+  const float* srow = p.samp + (int64_t)lo * D * 5;
+#pragma unroll
+  for (int d = 0; d < DP; ++d) {
+    if (d >= D) continue;
+    const int wi = d + 1;
+    if ((wi & 3) == 0) w = philox4x32_10(gi, (uint32_t)(wi >> 2), p.stream_word, c3, p.key0, p.key1);
+    const uint32_t word = (wi & 3) == 0 ? w.x : (wi & 3) == 1 ? w.y : (wi & 3) == 2 ? w.z : w.w;
+    const float* sr = srow + d * 5;
+    const float pr = sr[2] + u01f(word) * (sr[3] - sr[2]);
+    float zz = ndtri_f32(pr);
+    if (sr[4] != 0.f) zz = -zz;
+    float x = sr[0] + sr[1] * zz;
+    if (!(x == x)) x = sr[0];
+    z[d] = fminf(fmaxf(x, blo[d]), bhi[d]);        // low <= z < high
+  }
+}
+
 // The chunk of candidates [first, first + TPE_JOINT_CHUNK) of one problem: draw
 // (or load) kR candidates a lane, score both sides, write the optional outputs
 // and the chunk winner.  blo / bhi: the f32 bounds of the DP padded dimensions.
@@ -199,38 +237,7 @@ __device__ __forceinline__ void joint_chunk_body(const ChunkIO& p, const float (
 
   float z[kR][DP];
 #pragma unroll
-  for (int r = 0; r < kR; ++r) {
-#pragma unroll
-    for (int d = 0; d < DP; ++d) z[r][d] = 0.f;
-    const int i = first + r * kThreads + t;
-    if (i >= p.C) continue;
-    if (p.inject) {
-#pragma unroll
-      for (int d = 0; d < DP; ++d)
-        if (d < D) z[r][d] = p.inj[(int64_t)i * D + d];
-      continue;
-    }
-    const uint32_t c3 = p.c3, gi = p.base + (uint32_t)i;   // gi < 2^31: i < C and base + C <= n_cand_global
-    U4 w = philox4x32_10(gi, 0u, p.stream_word, c3, p.key0, p.key1);
-    const double us = u01w(w.x);
-    int lo = 0, hi = p.kb - 1;             // first k with us < cum[k]
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (us < p.cum[mid]) hi = mid; else lo = mid + 1; }
-    const float* srow = p.samp + (int64_t)lo * D * 5;
-#pragma unroll
-    for (int d = 0; d < DP; ++d) {
-      if (d >= D) continue;
-      const int wi = d + 1;
-      if ((wi & 3) == 0) w = philox4x32_10(gi, (uint32_t)(wi >> 2), p.stream_word, c3, p.key0, p.key1);
-      const uint32_t word = (wi & 3) == 0 ? w.x : (wi & 3) == 1 ? w.y : (wi & 3) == 2 ? w.z : w.w;
-      const float* sr = srow + d * 5;
-      const float pr = sr[2] + u01f(word) * (sr[3] - sr[2]);
-      float zz = ndtri_f32(pr);
-      if (sr[4] != 0.f) zz = -zz;
-      float x = sr[0] + sr[1] * zz;
-      if (!(x == x)) x = sr[0];
-      z[r][d] = fminf(fmaxf(x, blo[d]), bhi[d]);        // low <= z < high
-    }
-  }
+  for (int r = 0; r < kR; ++r) load_candidate<DP>(p, blo, bhi, first + r * kThreads + t, z[r]);
 
   double l2[kR], g2[kR];
   score_side<DP>(p.bmu, p.ba, p.bc, p.kb, D, z, rows, cl, l2);
@@ -2161,6 +2168,231 @@ __global__ __launch_bounds__(kThreads) void k_joint_wide_seg_chunk(const WideSeg
   wide_finish(k, at, 0, 0, c, l2, g2, slot);
 }
 
+// ------------------------------------------------------------ float64 stage
+// k_joint_chunk's model, candidates and chunk records with the scoring in f64
+// (include/tpe_hip.h "Float64 joint stage").  With z' = z - centre and mu' = mu -
+// centre the exponent sum_d (a_kd (z_d - mu_kd))^2 - c_k is the dot product of
+//   phi   = [z'_1^2 .. z'_DP^2, z'_1 .. z'_DP, 1]                      (a candidate)
+//   psi_k = [a_k1^2 .., -2 a_k1^2 mu'_k1 .., sum_d a_kd^2 mu'_kd^2 - c_k]  (a component)
+// of 2 DP + 1 entries, padded with zeros to NI steps of 4: one
+// v_mfma_f64_16x16x4_f64 a step gives 16 candidates x 16 components.  Operand
+// layout of that instruction: lane (i = lane & 15, k = lane >> 4) holds A[i][k]
+// and B[k][i]; its four results are D[4 v + (lane >> 4)][lane & 15], v = 0 .. 3.
+//
+// A pass serves one candidate a lane (the kR passes of a chunk run one after the
+// other): a wave's 64 candidates are 4 row blocks, whose phi a lane keeps in
+// registers over both sides (4 NI doubles).  A tile of kTileK components is
+// staged as psi in the B operand's layout, tile[(cb NI + s) 64 + lane], so a
+// wave's read of one step is 512 consecutive bytes and serves its 4 row blocks.
+// Each lane carries running (max, sum 2^(term - max)) pairs for its 4 x 4 results
+// over the components of its column; a 16 x 16 block none of whose terms lies
+// within kF64Skip binades of its pair's maximum adds less than 2^-100 a term and
+// is dropped by a wave vote before any exponential is evaluated.  The 16 column
+// lanes of a row are combined once a side.
+constexpr double kF64Skip = 100.0;
+constexpr double kF64Lowest = -1.7976931348623157e308;
+constexpr int f64_steps(int DP) { return (2 * DP + 1 + 3) / 4; }
+typedef double F64x4 __attribute__((ext_vector_type(4)));
+
+struct JointF64K {
+  JointK j;                         // the draws, the outputs and the chunk records (its f32 density rows: null)
+  const double *bmu, *ba, *bc, *amu, *aa, *ac;
+  double centre[TPE_JOINT_MAX_DIMS];
+};
+
+// 2^x for x <= 0 (NaN stays NaN; below -1100: 0): x = n + f with |f| <= 1/2,
+// e^(f ln 2) as its Taylor polynomial of degree 13 (remainder below 4e-18), then
+// the exponent.  17 f64 operations; relative error below 4e-16.
+__device__ __forceinline__ double exp2_nonpos(double x) {
+  x = x < -1100.0 ? -1100.0 : x;
+  const double n = __builtin_rint(x);
+  const double y = (x - n) * kLn2;
+  double p = 1.0 / 6227020800.0;
+  p = __builtin_fma(p, y, 1.0 / 479001600.0);
+  p = __builtin_fma(p, y, 1.0 / 39916800.0);
+  p = __builtin_fma(p, y, 1.0 / 3628800.0);
+  p = __builtin_fma(p, y, 1.0 / 362880.0);
+  p = __builtin_fma(p, y, 1.0 / 40320.0);
+  p = __builtin_fma(p, y, 1.0 / 5040.0);
+  p = __builtin_fma(p, y, 1.0 / 720.0);
+  p = __builtin_fma(p, y, 1.0 / 120.0);
+  p = __builtin_fma(p, y, 1.0 / 24.0);
+  p = __builtin_fma(p, y, 1.0 / 6.0);
+  p = __builtin_fma(p, y, 0.5);
+  p = __builtin_fma(p, y, 1.0);
+  p = __builtin_fma(p, y, 1.0);
+  return __builtin_amdgcn_ldexp(p, (int)n);
+}
+
+// log2 of one side's mixture at this pass's candidate of every lane (phi: the
+// wave's 4 row blocks in the A layout); the result comes back through `res`.
+template <int DP>
+__device__ __forceinline__ double score_side_f64(const double* __restrict__ mu, const double* __restrict__ a,
+                                                 const double* __restrict__ c, int K, int D,
+                                                 const double (&phi)[4][f64_steps(DP)], double* __restrict__ tile,
+                                                 const double* __restrict__ cs, double* __restrict__ res) {
+  constexpr int NI = f64_steps(DP);
+  const int t = threadIdx.x, lane = t & 63;
+  double m[4][4], s[4][4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+#pragma unroll
+    for (int v = 0; v < 4; ++v) { m[q][v] = kF64Lowest; s[q][v] = 0.0; }   // (any finite first term exceeds it)
+  for (int k0 = 0; k0 < K; k0 += kTileK) {
+    const int nk = min(kTileK, K - k0), ncb = (nk + 15) >> 4;
+    __syncthreads();                       // the previous tile (or the candidates' staging) is read
+    for (int e = t; e < ncb * NI * 64; e += kThreads) {
+      const int col = e & 15, inner = 4 * ((e >> 6) % NI) + ((e >> 4) & 3), kk = ((e >> 6) / NI) * 16 + col;
+      double v = 0.0;
+      if (kk >= nk) {                      // past the side's last component: a term of -inf
+        if (inner == 2 * DP) v = INFINITY;
+      } else if (inner < 2 * DP) {
+        const int d = inner < DP ? inner : inner - DP;
+        if (d < D) {
+          const int64_t src = (int64_t)(k0 + kk) * D + d;
+          const double ad = a[src];
+          v = inner < DP ? ad * ad : -2.0 * ad * (ad * (mu[src] - cs[d]));
+        }
+      } else if (inner == 2 * DP) {
+        const int64_t src = (int64_t)(k0 + kk) * D;
+        for (int d = 0; d < D; ++d) {
+          const double u = a[src + d] * (mu[src + d] - cs[d]);
+          v = __builtin_fma(u, u, v);
+        }
+        v -= c[k0 + kk];
+      }
+      tile[e] = v;
+    }
+    __syncthreads();
+    for (int cb = 0; cb < ncb; ++cb) {
+      const double* bt = tile + cb * NI * 64 + lane;
+      double b[NI];
+#pragma unroll
+      for (int i = 0; i < NI; ++i) b[i] = bt[i * 64];
+      F64x4 acc[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc[q] = F64x4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int i = 0; i < NI; ++i)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(phi[q][i], b[i], acc[q], 0, 0, 0);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        bool live = false;                 // (a NaN term is live, and stays in the sum)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) live |= !(-acc[q][v] <= m[q][v] - kF64Skip);
+        if (__builtin_amdgcn_ballot_w64(live) == 0) continue;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          const double term = -acc[q][v], dl = term - m[q][v];
+          const double e2 = exp2_nonpos(-__builtin_fabs(dl));
+          s[q][v] = dl > 0.0 ? __builtin_fma(s[q][v], e2, 1.0) : s[q][v] + e2;
+          m[q][v] = fmax(m[q][v], term);
+        }
+      }
+    }
+  }
+  // a row's 16 column lanes (lane & 15) hold its partial pairs
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+#pragma unroll
+      for (int mask = 1; mask < 16; mask <<= 1) {
+        const double mo = __shfl_xor(m[q][v], mask, 64), so = __shfl_xor(s[q][v], mask, 64);
+        const double top = fmax(m[q][v], mo);
+        s[q][v] = s[q][v] * exp2_nonpos(m[q][v] - top) + so * exp2_nonpos(mo - top);
+        m[q][v] = top;
+      }
+      if ((lane & 15) == 0) res[(t & ~63) + 16 * q + 4 * v + (lane >> 4)] = m[q][v] + log2(s[q][v]);
+    }
+  __syncthreads();
+  return res[t];
+}
+
+template <int DP>
+__global__ __launch_bounds__(kThreads) void k_joint_f64_chunk(const JointF64K p) {
+  constexpr int NI = f64_steps(DP);
+  __shared__ __attribute__((aligned(16))) double tile[(kTileK / 16) * NI * 64];
+  __shared__ double res[kThreads];
+  __shared__ double cs[DP];
+  __shared__ Pick slot[kThreads / 64];
+  static_assert(sizeof(float) * kThreads * DP <= sizeof tile, "a pass's candidates are staged in the tile");
+  float* zbuf = reinterpret_cast<float*>(tile);
+  const int t = threadIdx.x, lane = t & 63, first = (int)(blockIdx.x % p.j.n_chunks) * TPE_JOINT_CHUNK;
+
+  ChunkIO q;
+  solo_chunk_io(q, p.j, p.j.D);
+  const int D = q.D;
+  float blo[DP], bhi[DP];                  // (kernel-argument arrays: constant indices only)
+#pragma unroll
+  for (int d = 0; d < DP; ++d) {
+    blo[d] = p.j.lo[d]; bhi[d] = p.j.hi[d];
+    if (t == d) cs[d] = p.centre[d];
+  }
+
+  Pick best{0, 0};
+  double bl = 0.0, bg = 0.0;
+  float bz[DP];
+#pragma unroll
+  for (int d = 0; d < DP; ++d) bz[d] = 0.f;
+#pragma unroll 1
+  for (int r = 0; r < kR; ++r) {
+    const int i = first + r * kThreads + t;
+    float z[DP];
+    load_candidate<DP>(q, blo, bhi, i, z);
+    __syncthreads();                       // the previous pass's last tile is read
+#pragma unroll
+    for (int d = 0; d < DP; ++d) zbuf[t * DP + d] = z[d];
+    __syncthreads();
+    double phi[4][NI];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const float* zr = zbuf + ((t & ~63) + 16 * b + (lane & 15)) * DP;
+#pragma unroll
+      for (int s = 0; s < NI; ++s) {
+        const int e = 4 * s + (lane >> 4), d = min(e < DP ? e : e - DP, DP - 1);
+        const double zp = (double)zr[d] - cs[d];
+        phi[b][s] = e < DP ? zp * zp : e < 2 * DP ? zp : e == 2 * DP ? 1.0 : 0.0;
+      }
+    }
+    const double l2 = score_side_f64<DP>(p.bmu, p.ba, p.bc, q.kb, D, phi, tile, cs, res);
+    const double g2 = score_side_f64<DP>(p.amu, p.aa, p.ac, q.ka, D, phi, tile, cs, res);
+    const double lv = l2 * kLn2 + q.bbase, gv = g2 * kLn2 + q.abase;
+    if (i >= q.C) continue;
+    if (q.l_out) q.l_out[i] = lv;
+    if (q.g_out) q.g_out[i] = gv;
+    if (q.cand)
+#pragma unroll
+      for (int d = 0; d < DP; ++d)
+        if (d < D) q.cand[(int64_t)i * D + d] = z[d];
+    const uint64_t key = score_key(lv - gv);
+    if (key > best.key) {                  // ascending index: strict > keeps the first of a tie
+      best = Pick{key, (int64_t)i};
+      bl = lv; bg = gv;
+#pragma unroll
+      for (int d = 0; d < DP; ++d) bz[d] = z[d];
+    }
+  }
+  Pick w = wave_best(best);
+  if (lane == 0) slot[t >> 6] = w;
+  __syncthreads();
+  w = slot[0];
+#pragma unroll
+  for (int k = 1; k < kThreads / 64; ++k)
+    if (beats(slot[k], w)) w = slot[k];
+  if (w.key == 0) {
+    if (t == 0) q.rec->global_idx = -1;
+    return;
+  }
+  if (best.key != w.key || best.idx != w.idx) return;
+  q.rec->global_idx = w.idx + (int64_t)q.base;
+  q.rec->l = bl;
+  q.rec->g = bg;
+#pragma unroll
+  for (int d = 0; d < TPE_JOINT_MAX_DIMS; ++d) q.rec->z[d] = d < DP ? (double)bz[d < DP ? d : 0] : 0.0;
+}
+
 // ------------------------------------------------------------- host driver
 // Everything from here on runs on the host: the stages' argument checks,
 // the kernel-argument fills and the launches.  What the stages share exists
@@ -2426,8 +2658,12 @@ void fill_joint(JointK& k, const A* a, int Dc, uint32_t cand_base, float* cand, 
   k.kb = a->k_below; k.ka = a->k_above;
   k.key0 = (uint32_t)a->seed; k.key1 = (uint32_t)(a->seed >> 32); k.stream_word = a->stream_word;
   k.cand_base = cand_base;
-  k.bmu = a->below_mu; k.ba = a->below_a; k.bc = a->below_c;
-  k.amu = a->above_mu; k.aa = a->above_a; k.ac = a->above_c;
+  if constexpr (std::is_same<decltype(a->below_mu), const float*>::value) {
+    k.bmu = a->below_mu; k.ba = a->below_a; k.bc = a->below_c;
+    k.amu = a->above_mu; k.aa = a->above_a; k.ac = a->above_c;
+  } else {                                 // (the float64 stage: its rows travel beside this view)
+    k.bmu = k.ba = k.bc = k.amu = k.aa = k.ac = nullptr;
+  }
   k.bbase = a->below_base; k.abase = a->above_base;
   k.cum = a->samp_cum; k.samp = a->samp; k.ids = a->ids; k.inj = a->inject;
   for (int d = 0; d < TPE_JOINT_MAX_DIMS; ++d) {
@@ -2573,6 +2809,37 @@ int joint_run_at(const tpe_joint_args* a, tpe_joint_record* records, float* cand
     launch(k_joint_chunk<decltype(dp)::value>, dim3((unsigned)blocks), kThreads, 0u, s, ev.start, ev.stop, k);
   });
   return finish(k_joint_merge, (const tpe_joint_record*)scratch, k.n_chunks, records, a->n_ids, s, timed, 1);
+}
+
+// the float64 stage: tpe_joint_run's head (the two structs share every field name
+// up to `high`), chunk records and merge; its own rows, centres and kernel
+static_assert(offsetof(tpe_joint_f64_args, low) == offsetof(tpe_joint_args, low) &&
+                  offsetof(tpe_joint_f64_args, centre) == sizeof(tpe_joint_args),
+              "tpe_joint_f64_args is tpe_joint_args with f64 rows, then the centres");
+int joint_f64_run(const tpe_joint_f64_args* a, tpe_joint_record* records, float* cand, double* l_out, double* g_out,
+                  void* scratch, uint64_t scratch_bytes, void* stream) {
+  constexpr const char* E = "tpe_joint_f64_run";
+  tpe_internal_epoch_bump();
+  if (!a) return fail(E, "null args");
+  if (a->n_dims < 1 || a->n_dims > TPE_JOINT_MAX_DIMS) return fail(E, "n_dims outside [1, TPE_JOINT_MAX_DIMS]");
+  if (int rc = check_solo_head(E, a, records, a->n_dims)) return rc;
+  const int64_t blocks = n_chunks_of(a->n_cand) * a->n_ids;
+  if (int rc = check_scratch(E, blocks, joint_scratch_need(a->n_ids, a->n_cand), scratch, scratch_bytes)) return rc;
+  for (int d = 0; d < a->n_dims; ++d)
+    if (!isfinite(a->centre[d])) return fail(E, "centre not finite");
+
+  JointF64K k;
+  fill_joint(k.j, a, a->n_dims, 0u, cand, l_out, g_out, scratch);
+  k.bmu = a->below_mu; k.ba = a->below_a; k.bc = a->below_c;
+  k.amu = a->above_mu; k.aa = a->above_a; k.ac = a->above_c;
+  for (int d = 0; d < TPE_JOINT_MAX_DIMS; ++d) k.centre[d] = d < a->n_dims ? a->centre[d] : 0.0;
+  const bool timed = g_prof.on != 0;
+  hipStream_t s = (hipStream_t)stream;
+  const Ev ev = chunk_marks(timed);
+  for_dp(dp_class(a->n_dims), [&](auto dp) {
+    launch(k_joint_f64_chunk<decltype(dp)::value>, dim3((unsigned)blocks), kThreads, 0u, s, ev.start, ev.stop, k);
+  });
+  return finish(k_joint_merge, (const tpe_joint_record*)scratch, k.j.n_chunks, records, a->n_ids, s, timed, 1);
 }
 
 // ---- the wide stages: one skeleton (joint_wide_stage); a stage supplies its
@@ -3209,6 +3476,16 @@ int tpe_joint_mseg_table_bytes(const tpe_joint_mseg* host_segs, int32_t n_segs, 
 int tpe_joint_run(const tpe_joint_args* a, tpe_joint_record* records, float* cand, double* l_out,
                   double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
   return joint_run_at(a, records, cand, l_out, g_out, scratch, scratch_bytes, stream, 0u);
+}
+
+int tpe_joint_f64_scratch_bytes(int32_t n_ids, int32_t n_cand, uint64_t* bytes) {
+  const bool ok = n_ids >= 1 && n_cand >= 1;
+  return size_out("tpe_joint_f64_scratch_bytes", ok, ok ? joint_scratch_need(n_ids, n_cand) : 0, bytes);
+}
+
+int tpe_joint_f64_run(const tpe_joint_f64_args* a, tpe_joint_record* records, float* cand, double* l_out,
+                      double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
+  return joint_f64_run(a, records, cand, l_out, g_out, scratch, scratch_bytes, stream);
 }
 
 int tpe_joint_seg_run(const tpe_joint_seg_args* a, tpe_joint_record* records, float* cand, double* l_out,

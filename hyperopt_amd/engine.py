@@ -979,7 +979,8 @@ class Engine(object):
         return d_top, d_ntop, d_stats
 
     def run_joint(self, below, above, low, high, ids, n_cand, seed, inject=None, return_cand=False, want_lg=False,
-                  report_k=0, shard=None, stream_word=None, liar=False, given=None, return_sigma=False):
+                  report_k=0, shard=None, stream_word=None, liar=False, given=None, return_sigma=False,
+                  precision='fp32'):
         """One joint TPE stage (tpe_joint_run, include/tpe_hip.h "Joint
         (multivariate) TPE stage"): ``below`` / ``above`` = (w [K], mu [K, D],
         sigma [K, D]) float64 mixtures (joint.side_mixture), ``low`` / ``high``
@@ -1020,7 +1021,23 @@ class Engine(object):
         (joint.side_weight_sum).  ``return_sigma``: also, last, the liars'
         bandwidths float64 [G + n_ids, D].  ``liar`` with ``shard`` or
         ``report_k`` > 0, and ``given`` or ``return_sigma`` without ``liar``,
-        raise ValueError."""
+        raise ValueError.
+        ``precision`` 'fp64' (run_joint only; DESIGN.md "Float64 joint stage"):
+        tpe_joint_f64_run scores the same candidates, bit for bit those of the
+        'fp32' call, in float64 from the unrounded rows; ``inject``,
+        ``return_cand``, ``want_lg`` and ``stream_word`` work as they do
+        without it, ``report_k`` > 0, ``shard`` and ``liar`` raise ValueError."""
+        if precision not in ('fp32', 'fp64'):
+            raise ValueError("joint stage: precision must be 'fp32' or 'fp64': %r" % (precision,))
+        if precision == 'fp64':
+            for name, on in (('report_k', int(report_k) > 0), ('shard', shard is not None),
+                             ('liar', not (liar is False or liar is None))):
+                if on:
+                    raise ValueError("joint stage: precision='fp64' does not combine with %s: it is an fp32 stage"
+                                     % name)
+            self._liar(liar, given, return_sigma, report_k, shard)
+            return self._joint_solo('f64', below, above, low, high, (), (), ids, n_cand, seed, inject, return_cand,
+                                    want_lg, 0, stream_word, None)
         return self._joint_continuous(False, below, above, low, high, ids, n_cand, seed, inject, return_cand, want_lg,
                                       stream_word, report_k, shard, self._liar(liar, given, return_sigma, report_k,
                                                                                shard))
@@ -1064,7 +1081,8 @@ class Engine(object):
                                 return_cand, want_lg, report_k, stream_word, shard, liar=liar)
 
     # the solo stages by joint_pack entry: the args struct and the native function
-    _JOINT_SOLO = {'run': (N.JointArgs, 'tpe_joint_run'), 'wide': (N.JointWideArgs, 'tpe_joint_wide_run'),
+    _JOINT_SOLO = {'run': (N.JointArgs, 'tpe_joint_run'), 'f64': (N.JointF64Args, 'tpe_joint_f64_run'),
+                   'wide': (N.JointWideArgs, 'tpe_joint_wide_run'),
                    'mixed': (N.JointMixedArgs, 'tpe_joint_mixed_run'),
                    'wide_mixed': (N.JointWideMixedArgs, 'tpe_joint_wide_mixed_run'),
                    'quant': (N.JointQuantArgs, 'tpe_joint_quant_run'),
@@ -1108,6 +1126,9 @@ class Engine(object):
             a.inject = up('inject', JP.inject_rows(inject, C, D), torch.float32)
         for d in range(Dc):
             a.low[d], a.high[d] = r['low'][d], r['high'][d]
+        if entry == 'f64':
+            for d in range(Dc):
+                a.centre[d] = r['centre'][d]
         if Dk:
             a.n_cat = Dk
             for d in range(Dk):
@@ -1318,6 +1339,9 @@ class Engine(object):
         elif wide:
             N.check(self.lib.tpe_joint_wide_scratch_bytes(n_ids, C, D, ctypes.byref(nb)), self.lib,
                     'tpe_joint_wide_scratch_bytes')
+        elif fn == 'tpe_joint_f64_run':
+            N.check(self.lib.tpe_joint_f64_scratch_bytes(n_ids, C, ctypes.byref(nb)), self.lib,
+                    'tpe_joint_f64_scratch_bytes')
         else:
             N.check(self.lib.tpe_joint_scratch_bytes(n_ids, C, ctypes.byref(nb)), self.lib, 'tpe_joint_scratch_bytes')
         d_scr = self._buf('joint_scratch', (nb.value + 7) // 8, torch.float64)

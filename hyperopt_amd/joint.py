@@ -81,16 +81,32 @@ def _std_bounds(mu, sigma, low, high):
     return 0.5 * erfc(-a / np.sqrt(2)), 0.5 * erfc(-b / np.sqrt(2)), flip
 
 
-def density_rows(w, mu, sigma, low, high):
-    """f32 (mu [K, D], a [K, D], c [K]) and the float64 base of one side."""
+def density_rows_f64(w, mu, sigma, low, high):
+    """float64 (mu [K, D], a [K, D], c [K]) and the base of one side: what
+    tpe_joint_f64_run takes, and density_rows before its rounding."""
     fa, fb, _ = _std_bounds(mu, sigma, np.asarray(low)[None, :], np.asarray(high)[None, :])
     with np.errstate(divide='ignore'):
         logc = np.log(w) - np.sum(np.log(sigma * np.sqrt(2 * np.pi)) + np.log(fb - fa), axis=1)
     c = logc * LOG2E
     fin = np.isfinite(c)
     shift = float(np.max(c[fin])) if fin.any() else 0.0
-    return (np.ascontiguousarray(mu, dtype=np.float32), np.ascontiguousarray(A_SCALE / sigma, dtype=np.float32),
-            np.ascontiguousarray(c - shift, dtype=np.float32), shift * math.log(2.0))
+    return (np.ascontiguousarray(mu, dtype=np.float64), np.ascontiguousarray(A_SCALE / sigma, dtype=np.float64),
+            np.ascontiguousarray(c - shift, dtype=np.float64), shift * math.log(2.0))
+
+
+def density_rows(w, mu, sigma, low, high):
+    """f32 (mu [K, D], a [K, D], c [K]) and the float64 base of one side."""
+    mu, a, c, base = density_rows_f64(w, mu, sigma, low, high)
+    return mu.astype(np.float32), a.astype(np.float32), c.astype(np.float32), base
+
+
+def expansion_centres(low, high, prior_mu):
+    """The float64 stage's centre per dimension: the midpoint of the bounds
+    where both are finite, else the label's prior mean."""
+    low, high = np.asarray(low, dtype=np.float64), np.asarray(high, dtype=np.float64)
+    both = np.isfinite(low) & np.isfinite(high)
+    with np.errstate(invalid='ignore'):
+        return np.where(both, 0.5 * low + 0.5 * high, np.asarray(prior_mu, dtype=np.float64))
 
 
 def sampler_rows(w, mu, sigma, low, high):

@@ -8,6 +8,7 @@ and make the native call.
 
 The dimension limits by entry point (``_check_dims``):
   'run'      run_joint             1 <= D <= JOINT_MAX_DIMS, continuous only
+  'f64'      run_joint(precision='fp64')  as 'run'; the density rows stay float64, and the group gets its centres
   'wide'     run_joint_wide        1 <= D <= JOINT_WIDE_MAX_DIMS, continuous only
   'mixed'    run_joint_mixed       Dk >= 1, Dc + Dk <= JOINT_MAX_DIMS
   'wide_mixed' run_joint_wide_mixed  1 <= Dk <= JOINT_WIDE_MAX_CAT, Dq = 0, 1 <= Dc + Dk <= JOINT_WIDE_MAX_DIMS
@@ -47,9 +48,15 @@ _PRESENT = {(cat, quant): tuple(row for row in ROWS if row[4] in (None, 'cont') 
             for cat in (False, True) for quant in (False, True)}
 
 
+# the float64 stage's rows (entry 'f64'): the density rows as float64, in buffers of their own
+_F64_ROWS = tuple((key, field, buf + '64', np.float64, part) if key.split('_')[-1] in ('mu', 'a', 'c')
+                  else (key, field, buf, dt, part) for key, field, buf, dt, part in _PRESENT[False, False])
+assert sum(row[3] is np.float64 for row in _F64_ROWS) == 7      # the six density rows and the sampler's cum
+
+
 def group_rows_present(r):
     """ROWS without the parts the group ``r`` (group_rows) does not have."""
-    return _PRESENT[r['Dk'] > 0, r['Dq'] > 0]
+    return _F64_ROWS if r.get('f64') else _PRESENT[r['Dk'] > 0, r['Dq'] > 0]
 
 
 def seg_parts(m):
@@ -117,6 +124,9 @@ def group_rows(below, above, low, high, cats=(), quants=(), entry='segment'):
     low, high = np.asarray(low, dtype=np.float64).reshape(-1), np.asarray(high, dtype=np.float64).reshape(-1)
     Dc, Dk, Dq = len(low), len(cats), len(quants)
     _check_dims(entry, Dc, Dk, Dq)
+    if entry == 'f64' and (Dk or Dq):
+        raise ValueError('joint stage: the float64 stage holds continuous dimensions only, not %d discrete and %d '
+                         'quantised ones' % (Dk, Dq))
     edges = [np.ascontiguousarray(q[4], dtype=np.float64).reshape(-1) for q in quants]
     vs = [len(e) - 1 for e in edges]
     for e in edges:
@@ -157,6 +167,10 @@ def group_rows(below, above, low, high, cats=(), quants=(), entry='segment'):
         if Dk:
             (r[name + '_mu'], r[name + '_a'], r[name + '_c'], r[name + '_base'], r[name + '_cat'], r[name + '_miss'],
              r[name + '_bonus']) = J.mixed_density_rows(w, mu, sigma, low, high, np.stack(cols, axis=1), ps, s_side[i])
+        elif entry == 'f64':                         # the same rows before their rounding, and the centres
+            r[name + '_mu'], r[name + '_a'], r[name + '_c'], r[name + '_base'] = J.density_rows_f64(w, mu, sigma, low,
+                                                                                                    high)
+            r['f64'], r['centre'] = True, J.expansion_centres(low, high, mu[0])
         else:
             r[name + '_mu'], r[name + '_a'], r[name + '_c'], r[name + '_base'] = J.density_rows(w, mu, sigma, low, high)
         if Dq:

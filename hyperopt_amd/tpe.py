@@ -847,7 +847,7 @@ def suggest(new_ids, domain, trials, seed,
             sampler='philox', precision='fp32', device=None, shard=None, shard_ids=None, shard_labels=None,
             shard_grid=None, joint=False, joint_discrete=False, joint_quantized=False, joint_wide=False,
             joint_branches=False, joint_branches_mixed=False, joint_branches_wide=False, joint_shard=None,
-            joint_wide_mixed=False, joint_wide_quantized=False, joint_liar=False):
+            joint_precision='fp32', joint_wide_mixed=False, joint_wide_quantized=False, joint_liar=False):
     new_ids = list(new_ids)
     if not new_ids:
         return []
@@ -856,6 +856,7 @@ def suggest(new_ids, domain, trials, seed,
     liar_mode = _joint_liar_mode(joint_liar)
     if liar_mode:
         _joint_liar_check(joint, joint_shard, mode=liar_mode, joint_branches=joint_branches)
+    fp64 = _joint_precision_check(joint_precision, joint, joint_shard, liar_mode)
     if ((joint is not False and joint is not None) or joint_discrete or joint_quantized or joint_wide or joint_branches
             or joint_branches_mixed or joint_branches_wide or joint_wide_mixed or joint_wide_quantized):
         # (argument errors first: no device use, no startup draw)
@@ -867,6 +868,8 @@ def suggest(new_ids, domain, trials, seed,
         if liar_mode:
             _joint_liar_check(joint, joint_shard, plan, liar_mode, joint_branches)
             _wide_quant_liar_check(plan[0], liar_mode)
+        if fp64:
+            _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, plan)
     t0 = time.time()
     hist = _history.extract(domain, trials)
     if logger.isEnabledFor(logging.INFO):
@@ -885,7 +888,8 @@ def suggest(new_ids, domain, trials, seed,
                               joint_branches=joint_branches, joint_branches_mixed=joint_branches_mixed,
                               joint_branches_wide=joint_branches_wide, joint_shard=joint_shard,
                               joint_wide_mixed=joint_wide_mixed,
-                              joint_wide_quantized=joint_wide_quantized, joint_liar=joint_liar)
+                              joint_wide_quantized=joint_wide_quantized, joint_liar=joint_liar,
+                              joint_precision=joint_precision)
     logger.info('tpe.suggest took %f seconds', time.time() - t0)
     return rand.docs_from_choices(new_ids, domain, trials, choices)
 
@@ -927,8 +931,8 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
                     sampler='philox', precision='fp32', device=None, shard=None, columns=False,
                     shard_ids=None, shard_labels=None, shard_grid=None, joint=False, joint_discrete=False,
                     joint_quantized=False, joint_wide=False, joint_branches=False, joint_branches_mixed=False,
-                    joint_branches_wide=False, joint_shard=None, joint_wide_mixed=False, joint_wide_quantized=False,
-                    joint_liar=False):
+                    joint_branches_wide=False, joint_shard=None, joint_precision='fp32', joint_wide_mixed=False,
+                    joint_wide_quantized=False, joint_liar=False):
     """The suggest core on a structure-of-arrays history (``history.History``):
     per new id a {label: value or None} dict.  ``suggest`` wraps it with the
     Trials document layout; columnar callers (and bench.py's large configs)
@@ -1112,7 +1116,18 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
     continuous, or without a branch group, it is 'branches' byte for byte; one
     id, or ids that all take different branches, are the same bytes as without
     the keyword.  ``joint_shard`` and the value without ``joint`` or without
-    ``joint_branches`` raise ValueError."""
+    ``joint_branches`` raise ValueError.
+
+    ``joint_precision='fp64'`` (with ``joint``; the root group 2 to 16
+    continuous labels): the root group's stage scores in float64 (DESIGN.md
+    "Float64 joint stage").  Its candidates are the fp32 stage's bit for bit, so
+    the winner is the float64 arg-max over the same pool; every other label is
+    the same bytes as without the keyword.  The default 'fp32' is the path
+    above byte for byte.  Without ``joint``, with a root group that holds a
+    discrete or quantised label or more than 16 labels, with any branch group,
+    with ``joint_shard`` or ``joint_liar``, and for any other value it raises
+    ValueError; joint_candidate_report does not take it.  (``precision='fp64'``,
+    the univariate parity mode, still does not combine with ``joint``.)"""
     if sampler not in ('philox', 'replay'):
         raise ValueError("sampler must be 'philox' or 'replay'")
     if joint_shard is not None:
@@ -1120,6 +1135,7 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
     liar_mode = _joint_liar_mode(joint_liar)
     if liar_mode:
         _joint_liar_check(joint, joint_shard, mode=liar_mode, joint_branches=joint_branches)
+    fp64 = _joint_precision_check(joint_precision, joint, joint_shard, liar_mode)
     group, branch_groups = None, []
     if ((joint is not False and joint is not None) or joint_discrete or joint_quantized or joint_wide or joint_branches
             or joint_branches_mixed or joint_branches_wide or joint_wide_mixed or joint_wide_quantized):
@@ -1133,6 +1149,8 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
         if liar_mode:
             _joint_liar_check(joint, joint_shard, (group, branch_groups), liar_mode, joint_branches)
             _wide_quant_liar_check(group, liar_mode)
+        if fp64:
+            _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, (group, branch_groups))
     if sum(a is not None for a in (shard, shard_ids, shard_labels, shard_grid)) > 1:
         raise ValueError('shard, shard_ids, shard_labels and shard_grid are exclusive: one shard axis per suggest')
     if (shard_ids is not None or shard_labels is not None or shard_grid is not None) and sampler == 'replay':
@@ -1144,7 +1162,7 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
                                 columns, shard_ids, shard_labels, shard_grid)
     if group is not None or branch_groups:
         return _suggest_joint(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, device, columns, group,
-                              branch_groups, joint_shard, liar_mode or False)
+                              branch_groups, joint_shard, liar_mode or False, fp64)
     return _suggest_local(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, sampler, precision,
                           device, shard, columns)
 
@@ -1165,6 +1183,44 @@ def _joint_liar_mode(joint_liar):
         return joint_liar
     raise ValueError("joint_liar must be True or 'mixed', or 'branches' with joint_branches or 'branches_mixed' with "
                      'joint_branches (or False): %r' % (joint_liar,))
+
+
+def _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, plan=None):
+    """Whether ``joint_precision`` asks for the float64 stage; ValueError for a
+    value other than 'fp32' / 'fp64' and where 'fp64' does not apply: without
+    ``joint``, with ``joint_shard`` or ``joint_liar``, and (``plan`` =
+    _joint_plan's result) without a root group, for a root group that holds a
+    discrete or quantised label or more than TPE_JOINT_MAX_DIMS labels, and for
+    any branch group.  Touches no device."""
+    if joint_precision not in ('fp32', 'fp64'):
+        raise ValueError("joint_precision must be 'fp32' or 'fp64': %r" % (joint_precision,))
+    if joint_precision == 'fp32':
+        return False
+    if joint is False or joint is None:
+        raise ValueError("joint_precision='fp64' needs joint=True or joint=[labels]: it only changes how the joint "
+                         'stage scores')
+    if joint_shard is not None:
+        raise ValueError("joint_precision='fp64' does not combine with joint_shard: the sharded joint stage scores in "
+                         'fp32 only')
+    if liar_mode:
+        raise ValueError("joint_precision='fp64' does not combine with joint_liar: the batch-aware liar stage scores "
+                         'in fp32 only')
+    if plan is None:
+        return True
+    group, branch_groups = plan
+    if branch_groups:
+        raise ValueError("joint_precision='fp64' does not combine with branch groups (joint_branches): the segmented "
+                         'joint stage scores in fp32 only')
+    if group is None:
+        raise ValueError("joint_precision='fp64' needs a root group: there is none")
+    other = [r.label for r in group if r.dist not in _joint.JOINT_DISTS]
+    if other:
+        raise ValueError("joint_precision='fp64' needs a root group of continuous labels only: %r is discrete or "
+                         'quantised, and the mixed and quantised joint stages score in fp32 only' % other[0])
+    if len(group) > TPE_JOINT_MAX_DIMS:
+        raise ValueError("joint_precision='fp64' takes a root group of at most %d labels, not %d: the wide joint stage "
+                         'scores in fp32 only' % (TPE_JOINT_MAX_DIMS, len(group)))
+    return True
 
 
 def _joint_liar_check(joint, joint_shard, plan=None, mode=True, joint_branches=False):
@@ -1762,7 +1818,7 @@ def _run_root_group(engine, group, hist, ids, seed, prior_weight, n_EI_candidate
 
 
 def _suggest_joint(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, device, columns, group,
-                   branch_groups=(), joint_shard=None, joint_liar=False):
+                   branch_groups=(), joint_shard=None, joint_liar=False, fp64=False):
     """The univariate suggest of every label (the joined labels' univariate
     winners are discarded: each costs one problem of the level's batch, and the
     other labels' values are then the same bytes as without ``joint``), then
@@ -1776,7 +1832,8 @@ def _suggest_joint(table, hist, new_ids, seed, prior_weight, n_EI_candidates, ga
     True, 'mixed', 'branches' or 'branches_mixed'): the root group's ids pick
     greedily (Engine.run_joint's ``liar``); 'branches' / 'branches_mixed': so do
     the ids of every branch group (Engine.run_joint_segments_liar /
-    run_joint_msegments_liar)."""
+    run_joint_msegments_liar).  ``fp64`` (joint_precision='fp64'): the root
+    group's stage is Engine.run_joint(precision='fp64')."""
     cc = _suggest_local(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, 'philox', 'fp32', device,
                         None, True)
     if len(cc) == 0:
@@ -1798,7 +1855,8 @@ def _suggest_joint(table, hist, new_ids, seed, prior_weight, n_EI_candidates, ga
         group, model = got[0], got[1]
     elif group is not None:
         group, model, rec = _run_root_group(engine, group, hist, ids, seed, prior_weight, n_EI_candidates, gamma,
-                                            **({'liar': True} if joint_liar else {}))
+                                            **({'liar': True} if joint_liar else
+                                               {'precision': 'fp64'} if fp64 else {}))
     if group is not None:
         if (rec['global_idx'] < 0).any():
             raise RuntimeError('no joint candidate selected')

@@ -1161,6 +1161,60 @@ int tpe_joint_run(const tpe_joint_args* args, tpe_joint_record* records, float* 
 int tpe_joint_profile(int32_t enable, double* last_ms);
 
 /* ------------------------------------------------------------------------
+ * Float64 joint stage (tpe_joint.hip; additive to ABI 24): tpe_joint_run with
+ * the scoring in f64.  The model, the sampler rows, the Philox streams, the
+ * score, the winner's order, tpe_joint_record, the chunk records and their
+ * merge are tpe_joint_run's, and a candidate is the same f32 vector bit for bit:
+ * the same seed, ids and stream word give both stages the same pool, and their
+ * l and g differ by the f32 stage's rounding alone.
+ *
+ * Density rows of a side, K components, all f64, device (the values that
+ * tpe_joint_args holds rounded to f32):
+ *   mu[K * D], a[K * D] = sqrt(log2(e) / 2) / sigma_kd, c[K] in log2 units
+ *   shifted so that max_k c_k = 0; below_base / above_base as there.
+ * centre[d]: a finite point near the label's values, the midpoint of the bounds
+ * where both are finite, else the prior mean.  The kernel expands the exponent
+ * around it,
+ *   sum_d (a_kd (z_d - mu_kd))^2 - c_k  =  phi(z) . psi_k,
+ *   phi = [z'^2 .., z' .., 1], psi_k = [a^2 .., -2 a^2 mu' .., sum_d a^2 mu'^2 - c_k],
+ *   z' = z - centre, mu' = mu - centre (subtracted in f64),
+ * and evaluates it with v_mfma_f64_16x16x4_f64 (16 candidates x 16 components a
+ * step).  The expansion loses about (sum_d a^2 (z'^2 + mu'^2)) 2^-52 log2 units:
+ * with |z'|, |mu'| <= range / 2 and sigma >= range / 100, below 1e-11 at D = 16.
+ * The sum over k carries a running maximum as in tpe_joint_run; a 16 x 16 block
+ * whose terms all lie more than 100 binades below the running maxima is
+ * dropped before its exponentials (each term adds less than 2^-100 of the sum).
+ * No atomics: the same call twice gives the same bytes.
+ *
+ * tpe_joint_f64_run returns TPE_E_ARG before any launch (no device needed) for
+ * everything tpe_joint_run does, for a centre that is not finite, and for
+ * scratch smaller than tpe_joint_f64_scratch_bytes(n_ids, n_cand).
+ * tpe_joint_profile serves this stage too.
+ * ---------------------------------------------------------------------- */
+typedef struct tpe_joint_f64_args {
+  int32_t n_dims, n_cand, n_ids, flags;   /* as tpe_joint_args ... */
+  int32_t k_below, k_above;
+  uint32_t stream_word;
+  int32_t reserved;
+  uint64_t seed;
+  const double *below_mu, *below_a, *below_c;   /* ... but f64 */
+  const double *above_mu, *above_a, *above_c;
+  double below_base, above_base;
+  const double* samp_cum;
+  const float* samp;
+  const int64_t* ids;
+  const float* inject;
+  double low[TPE_JOINT_MAX_DIMS], high[TPE_JOINT_MAX_DIMS];
+  double centre[TPE_JOINT_MAX_DIMS];      /* entries from n_dims on: ignored */
+} tpe_joint_f64_args;
+
+int tpe_joint_f64_scratch_bytes(int32_t n_ids, int32_t n_cand, uint64_t* bytes);
+
+/* records, cand, l_out, g_out, scratch and stream as tpe_joint_run */
+int tpe_joint_f64_run(const tpe_joint_f64_args* args, tpe_joint_record* records, float* cand, double* l_out,
+                      double* g_out, void* scratch, uint64_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Wide joint stage (tpe_joint.hip; additive to ABI 24): the stage above for a
  * group of up to TPE_JOINT_WIDE_MAX_DIMS continuous labels.  The model, the
  * density and sampler rows, the score and the winner's order are those of

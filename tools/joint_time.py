@@ -129,7 +129,17 @@ one hp.quniform of 32 values: (a) Engine.run_joint_segments, (b)
 Engine.run_joint_msegments_liar, (c) one Engine.run_joint_liar_mixed(liar=W_s) per
 group; (b) and (c) must agree byte for byte.  The nearest-pick distance is
 --liar-mixed's, inside a branch.  --out defaults to
-profiles/joint_liar_mseg_time.jsonl."""
+profiles/joint_liar_mseg_time.jsonl.
+
+--fp64: the float64 joint stage (DESIGN.md "Float64 joint stage") against the
+fp32 one on the shape above (4 labels, --history trials, --cand candidates, one
+id): Engine.run_joint and Engine.run_joint(precision='fp64') alternate in one
+process, wall clock from a synchronised device to the record on the host, each
+call also timed by the chunk kernel's own events (tpe_joint_profile).  Untimed,
+both stages return l and g of the whole shared pool: the line carries the worst
+|l32 - l64| and |g32 - g64| in units of the fp32 tolerance 1e-5 max(1, |ref|)
+with the float64 stage as ref, and how many ids' winners differ.  --out
+defaults to profiles/joint_fp64_time.jsonl."""
 import argparse
 import ctypes
 import json
@@ -801,6 +811,65 @@ def main_liar(args):
     return 0
 
 
+def main_fp64(args):
+    import torch
+    from hyperopt_amd import _native as N, history as H, joint as J
+    from hyperopt_amd.engine import get_engine
+
+    domain, hist = make_history(args.history)
+    rows = [r for r in domain.table.rows if J.eligible(r)]
+    model = J.fit_model(rows, hist, H.split_below(hist, 0.25), 1.0)
+    eng = get_engine(None, 'fp32')
+    lib = eng.lib
+    C, D = args.cand, len(rows)
+    Kb, Ka = len(model.below[0]), len(model.above[0])
+    ids = np.array([args.history], dtype=np.int64)
+
+    def run(precision, **kw):
+        return eng.run_joint(model.below, model.above, model.low, model.high, ids, C, SEED, precision=precision, **kw)
+
+    for _ in range(args.warmup):
+        run('fp32')
+        run('fp64')
+    wall, kern = {'fp32': [], 'fp64': []}, {'fp32': [], 'fp64': []}
+    ms2 = (ctypes.c_double * 2)()
+    for i in range(args.pairs):
+        for prec in ('fp32', 'fp64'):
+            N.check(lib.tpe_joint_profile(1, None), lib, 'tpe_joint_profile')
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            run(prec)
+            torch.cuda.synchronize()
+            wall[prec].append((time.perf_counter() - t0) * 1e3)
+            N.check(lib.tpe_joint_profile(0, ms2), lib, 'tpe_joint_profile')
+            kern[prec].append(ms2[0])
+        print('pair %d: fp32 %.2f ms, fp64 %.2f ms' % (i, wall['fp32'][-1], wall['fp64'][-1]), file=sys.stderr,
+              flush=True)
+    r32, c32, l32, g32 = run('fp32', return_cand=True, want_lg=True)
+    r64, c64, l64, g64 = run('fp64', return_cand=True, want_lg=True)
+    assert c32.tobytes() == c64.tobytes()
+    err = lambda a, ref: float(np.max(np.abs(a - ref) / np.maximum(1.0, np.abs(ref)))) / 1e-5   # noqa: E731
+    med = lambda x: float(np.median(x))   # noqa: E731
+    ms = lambda w, k: dict(wall_median=med(w), wall_min=min(w), wall_max=max(w), chunk_kernel_median=med(k),  # noqa: E731
+                           chunk_kernel_min=min(k), chunk_kernel_max=max(k))
+    evals = float(C) * (Kb + Ka) * D
+    k32, k64 = med(kern['fp32']), med(kern['fp64'])
+    line = dict(tool='joint_time --fp64', labels=[r.label for r in rows], history=args.history, n_cand=C, n_dims=D,
+                k_below=Kb, k_above=Ka, pairs=args.pairs, fp32_ms=ms(wall['fp32'], kern['fp32']),
+                fp64_ms=ms(wall['fp64'], kern['fp64']), wall_ratio=med(wall['fp64']) / med(wall['fp32']),
+                kernel_ratio=k64 / k32, fp32_evals_per_s=evals / (k32 * 1e-3), fp64_evals_per_s=evals / (k64 * 1e-3),
+                l_err_over_fp32_tol=err(l32, l64), g_err_over_fp32_tol=err(g32, g64),
+                winners_differ=int((r32['global_idx'] != r64['global_idx']).sum()), n_ids=len(ids),
+                gpu=torch.cuda.get_device_name(0))
+    text = json.dumps(line)
+    print(text)
+    out = args.out or os.path.join(ROOT, 'profiles', 'joint_fp64_time.jsonl')
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, 'a') as f:
+        f.write(text + '\n')
+    return 0
+
+
 def make_liar_mixed_history(n):
     from hyperopt_amd import base, history as H, hp
     space = {'x0': hp.uniform('x0', -5, 5), 'x1': hp.loguniform('x1', -3, 2), 'x2': hp.normal('x2', 0, 2),
@@ -1088,6 +1157,7 @@ def main():
     ap.add_argument('--liar-mixed', action='store_true')
     ap.add_argument('--liar-branches', action='store_true')
     ap.add_argument('--liar-branches-mixed', action='store_true')
+    ap.add_argument('--fp64', action='store_true')
     ap.add_argument('--batch', type=int, default=64)
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
@@ -1101,6 +1171,8 @@ def main():
         return main_wide_mixed(args)
     if args.wide_quant:
         return main_wide_quant(args)
+    if args.fp64:
+        return main_fp64(args)
     if args.liar:
         return main_liar(args)
     if args.liar_mixed:
