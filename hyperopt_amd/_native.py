@@ -161,6 +161,12 @@ class JointWideArgs(ctypes.Structure):
     ]
 
 
+class JointWideF64Args(ctypes.Structure):
+    """tpe_joint_wide_f64_args: one tpe_joint_wide_f64_run (tpe_joint_wide_args with float64 density rows, then the
+    centres)."""
+    _fields_ = JointWideArgs._fields_ + [('centre', ctypes.c_double * JOINT_WIDE_MAX_DIMS)]
+
+
 class JointMixedArgs(ctypes.Structure):
     """tpe_joint_mixed_args: one tpe_joint_mixed_run (n_dims continuous, n_cat discrete labels)."""
     _fields_ = [
@@ -574,6 +580,7 @@ EXPORTS = ('tpe_abi_version', 'tpe_last_error', 'tpe_device_count', 'tpe_tile_si
            'tpe_joint_f64_scratch_bytes', 'tpe_joint_f64_run',
            'tpe_joint_mixed_run', 'tpe_joint_quant_table_bytes', 'tpe_joint_quant_run', 'tpe_joint_quant_profile',
            'tpe_joint_wide_scratch_bytes', 'tpe_joint_wide_run', 'tpe_joint_wide_profile',
+           'tpe_joint_wide_f64_scratch_bytes', 'tpe_joint_wide_f64_run', 'tpe_joint_wide_f64_profile',
            'tpe_joint_wide_mixed_scratch_bytes', 'tpe_joint_wide_mixed_run',
            'tpe_joint_wide_quant_scratch_bytes', 'tpe_joint_wide_quant_run', 'tpe_joint_wide_quant_profile',
            'tpe_joint_seg_scratch_bytes', 'tpe_joint_seg_run', 'tpe_joint_mseg_scratch_bytes',
@@ -719,6 +726,12 @@ def load(path=LIB_PATH):
     lib.tpe_joint_wide_run.restype = ctypes.c_int
     lib.tpe_joint_wide_profile.argtypes = [P]
     lib.tpe_joint_wide_profile.restype = ctypes.c_int
+    lib.tpe_joint_wide_f64_scratch_bytes.argtypes = [I32, I32, I32, I32, I32, ctypes.POINTER(ctypes.c_uint64)]
+    lib.tpe_joint_wide_f64_scratch_bytes.restype = ctypes.c_int
+    lib.tpe_joint_wide_f64_run.argtypes = [ctypes.POINTER(JointWideF64Args), P, P, P, P, P, ctypes.c_uint64, P]
+    lib.tpe_joint_wide_f64_run.restype = ctypes.c_int
+    lib.tpe_joint_wide_f64_profile.argtypes = [P]
+    lib.tpe_joint_wide_f64_profile.restype = ctypes.c_int
     lib.tpe_joint_wide_mixed_scratch_bytes.argtypes = [I32, I32, I32, I32, ctypes.POINTER(ctypes.c_uint64)]
     lib.tpe_joint_wide_mixed_scratch_bytes.restype = ctypes.c_int
     lib.tpe_joint_wide_mixed_run.argtypes = [ctypes.POINTER(JointWideMixedArgs), P, P, P, P, P, ctypes.c_uint64, P]

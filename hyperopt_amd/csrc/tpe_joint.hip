@@ -2393,6 +2393,237 @@ __global__ __launch_bounds__(kThreads) void k_joint_f64_chunk(const JointF64K p)
   for (int d = 0; d < TPE_JOINT_MAX_DIMS; ++d) q.rec->z[d] = d < DP ? (double)bz[d < DP ? d : 0] : 0.0;
 }
 
+// ------------------------------------------------------- wide float64 stage
+// The float64 stage for a wide group (include/tpe_hip.h "Wide float64 joint
+// stage"): k_joint_wide_sample's candidates in zbuf (or `inject`), the wide
+// stage's chunks, chunk records and merge, and the scoring above at DP in {20, 24,
+// 32, 48, 64}, where phi has up to 129 entries.  Two things differ from
+// k_joint_f64_chunk.
+//
+// phi is not kept.  DP is a multiple of 4, so step s of the inner dimension holds,
+// in lane group k = lane >> 4, the entry of ONE dimension d = 4 (s mod DP/4) + k:
+// z'_d^2 for s < DP/4, z'_d for DP/4 <= s < DP/2, and the constant in step DP/2.
+// A lane therefore needs only the dimensions d = k (mod 4) of its 4 row blocks'
+// candidates: DP f32 registers in all (DP/4 a row block), read straight from zbuf
+// (16 consecutive floats a lane group and dimension).  z' = (double)z - centre and
+// z'^2 are formed beside the two MFMAs that take them.
+//
+// psi is made once a call by k_joint_wide_f64_psi, both sides in one launch, and
+// written in the B operand's layout psi[(cb NI + s) 64 + lane], column block cb of
+// 16 components (a side's blocks one after the other; components past the side's
+// end carry +inf in the constant entry, dimensions past D zeros).  A scoring
+// workgroup stages wide_f64_cbs(DP) column blocks a tile by 16-byte copies.
+constexpr int kWF64TileBytes = 56 * 1024;   // + res, cs and slot: under the 64 KiB of a static allocation
+constexpr int wide_f64_cbs(int DP) {
+  const int n = kWF64TileBytes / (f64_steps(DP) * 512);
+  return n < kTileK / 16 ? n : kTileK / 16;
+}
+constexpr int kWF64Tile = 16 * wide_f64_cbs(20);   // the largest component tile (DP = 20 and 24)
+static_assert(wide_f64_cbs(64) == 3 && wide_f64_cbs(48) == 4 && wide_f64_cbs(32) == 6 && wide_f64_cbs(24) == 8 &&
+                  kWF64Tile == 128,
+              "DESIGN.md \"Wide float64 joint stage\" names these tiles");
+
+struct WideF64PsiK {
+  int D, DP, kb, ka;
+  const double *bmu, *ba, *bc, *amu, *aa, *ac;
+  double* psi;                      // [ceil(kb / 16) + ceil(ka / 16)][NI][64]
+  double centre[kWD];
+};
+struct WideF64K {
+  WideK w;                          // the wide stage's view (its f32 density rows: null)
+  const double *bpsi, *apsi;
+  double centre[kWD];
+};
+
+// one workgroup a column block; the entries are score_side_f64's tile fill
+__global__ __launch_bounds__(kThreads) void k_joint_wide_f64_psi(const WideF64PsiK p) {
+  __shared__ double cs[kWD];
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int d = 0; d < kWD; ++d)            // (kernel-argument arrays: constant indices only)
+    if (t == d) cs[d] = p.centre[d];
+  __syncthreads();
+  const int nbb = (p.kb + 15) >> 4;
+  const bool below = (int)blockIdx.x < nbb;
+  const int cb = below ? (int)blockIdx.x : (int)blockIdx.x - nbb, K = below ? p.kb : p.ka;
+  const double* __restrict__ mu = below ? p.bmu : p.amu;
+  const double* __restrict__ a = below ? p.ba : p.aa;
+  const double* __restrict__ c = below ? p.bc : p.ac;
+  const int D = p.D, DP = p.DP, NI = DP / 2 + 1;
+  double* __restrict__ out = p.psi + (int64_t)blockIdx.x * NI * 64;
+  for (int e = t; e < NI * 64; e += kThreads) {
+    const int inner = 4 * (e >> 6) + ((e >> 4) & 3), kk = cb * 16 + (e & 15);
+    double v = 0.0;
+    if (kk >= K) {                         // past the side's last component: a term of -inf
+      if (inner == 2 * DP) v = INFINITY;
+    } else if (inner < 2 * DP) {
+      const int d = inner < DP ? inner : inner - DP;
+      if (d < D) {
+        const int64_t src = (int64_t)kk * D + d;
+        const double ad = a[src];
+        v = inner < DP ? ad * ad : -2.0 * ad * (ad * (mu[src] - cs[d]));
+      }
+    } else if (inner == 2 * DP) {
+      const int64_t src = (int64_t)kk * D;
+      for (int d = 0; d < D; ++d) {
+        const double u = a[src + d] * (mu[src + d] - cs[d]);
+        v = __builtin_fma(u, u, v);
+      }
+      v -= c[kk];
+    }
+    out[e] = v;
+  }
+}
+
+// where candidate ci of the workgroup's id lies: coordinate d at at[d * step]
+struct WideZ {
+  const float* at;
+  int step;
+};
+__device__ __forceinline__ WideZ wide_z_of(const WideK& w, int id, int ci) {
+  if (w.inject) return WideZ{w.zsrc + (int64_t)ci * w.D, 1};
+  return WideZ{w.zsrc + ((int64_t)id * w.nblk + ci / kThreads) * kThreads * w.D + ci % kThreads, kThreads};
+}
+
+// log2 of one side's mixture at this pass's candidate of every lane, as
+// score_side_f64; z: the lane's dimensions of its wave's 4 row blocks
+template <int DP>
+__device__ __forceinline__ double score_side_wide_f64(const double* __restrict__ psi, int K,
+                                                      const float (&z)[4][DP / 4], double* __restrict__ tile,
+                                                      const double* __restrict__ cs, double* __restrict__ res) {
+  constexpr int NI = f64_steps(DP), Q = DP / 4, CB = wide_f64_cbs(DP);
+  const int t = threadIdx.x, lane = t & 63, k = lane >> 4;
+  const double one = k == 0 ? 1.0 : 0.0;
+  double m[4][4], s[4][4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+#pragma unroll
+    for (int v = 0; v < 4; ++v) { m[q][v] = kF64Lowest; s[q][v] = 0.0; }   // (any finite first term exceeds it)
+  const int ncbs = (K + 15) >> 4;
+  for (int c0 = 0; c0 < ncbs; c0 += CB) {
+    const int ncb = min(CB, ncbs - c0);
+    __syncthreads();                       // the previous tile is read
+    {
+      const double2* __restrict__ src = reinterpret_cast<const double2*>(psi + (int64_t)c0 * NI * 64);
+      double2* __restrict__ dst = reinterpret_cast<double2*>(tile);
+      for (int e = t; e < ncb * NI * 32; e += kThreads) dst[e] = src[e];
+    }
+    __syncthreads();
+    for (int cb = 0; cb < ncb; ++cb) {
+      const double* bt = tile + cb * NI * 64 + lane;
+      F64x4 acc[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc[q] = F64x4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int j = 0; j < Q; ++j) {
+        const double cj = cs[4 * j + k], b2 = bt[j * 64], b1 = bt[(Q + j) * 64];
+        double zp[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          zp[q] = (double)z[q][j] - cj;
+          acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(zp[q] * zp[q], b2, acc[q], 0, 0, 0);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(zp[q], b1, acc[q], 0, 0, 0);
+      }
+      const double b0 = bt[2 * Q * 64];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(one, b0, acc[q], 0, 0, 0);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        bool live = false;                 // (a NaN term is live, and stays in the sum)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) live |= !(-acc[q][v] <= m[q][v] - kF64Skip);
+        if (__builtin_amdgcn_ballot_w64(live) == 0) continue;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          const double term = -acc[q][v], dl = term - m[q][v];
+          const double e2 = exp2_nonpos(-__builtin_fabs(dl));
+          s[q][v] = dl > 0.0 ? __builtin_fma(s[q][v], e2, 1.0) : s[q][v] + e2;
+          m[q][v] = fmax(m[q][v], term);
+        }
+      }
+    }
+  }
+  // a row's 16 column lanes (lane & 15) hold its partial pairs
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+#pragma unroll
+      for (int mask = 1; mask < 16; mask <<= 1) {
+        const double mo = __shfl_xor(m[q][v], mask, 64), so = __shfl_xor(s[q][v], mask, 64);
+        const double top = fmax(m[q][v], mo);
+        s[q][v] = s[q][v] * exp2_nonpos(m[q][v] - top) + so * exp2_nonpos(mo - top);
+        m[q][v] = top;
+      }
+      if ((lane & 15) == 0) res[(t & ~63) + 16 * q + 4 * v + (lane >> 4)] = m[q][v] + log2(s[q][v]);
+    }
+  __syncthreads();
+  return res[t];
+}
+
+template <int DP>
+__global__ __launch_bounds__(kThreads) void k_joint_wide_f64_chunk(const WideF64K p) {
+  constexpr int NI = f64_steps(DP), Q = DP / 4, R = wide_r(DP);
+  static_assert(DP % 4 == 0 && DP <= kWD && NI == DP / 2 + 1, "a step holds one dimension a lane group");
+  __shared__ __attribute__((aligned(16))) double tile[wide_f64_cbs(DP) * NI * 64];
+  __shared__ double res[kThreads];
+  __shared__ double cs[DP];
+  __shared__ Pick slot[kThreads / 64];
+  const WideK& w = p.w;
+  const int t = threadIdx.x, lane = t & 63, k = lane >> 4, D = w.D;
+  const WideAt at = wide_at(w.n_chunks);
+  const int first = at.chunk * (R * kThreads);
+#pragma unroll
+  for (int d = 0; d < DP; ++d)             // (read after the first tile's barrier)
+    if (t == d) cs[d] = p.centre[d];
+
+  Pick best{0, 0};
+  double bl = 0.0, bg = 0.0;
+#pragma unroll 1
+  for (int r = 0; r < R; ++r) {
+    float z[4][Q];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int ci = first + r * kThreads + (t & ~63) + 16 * q + (lane & 15);
+      const WideZ zs = wide_z_of(w, at.id, ci);
+#pragma unroll
+      for (int j = 0; j < Q; ++j)          // (past C: no block of zbuf, or one the sampler left unwritten)
+        z[q][j] = (ci < w.C && 4 * j + k < D) ? zs.at[(int64_t)(4 * j + k) * zs.step] : 0.f;
+    }
+    const double l2 = score_side_wide_f64<DP>(p.bpsi, w.kb, z, tile, cs, res);
+    const double g2 = score_side_wide_f64<DP>(p.apsi, w.ka, z, tile, cs, res);
+    const double lv = l2 * kLn2 + w.bbase, gv = g2 * kLn2 + w.abase;
+    const int i = first + r * kThreads + t;
+    if (i >= w.C) continue;
+    const int64_t o = (int64_t)at.id * w.C + i;
+    if (w.l_out) w.l_out[o] = lv;
+    if (w.g_out) w.g_out[o] = gv;
+    if (w.cand) {
+      const WideZ zs = wide_z_of(w, at.id, i);
+      for (int d = 0; d < D; ++d) w.cand[o * D + d] = zs.at[(int64_t)d * zs.step];
+    }
+    const uint64_t key = score_key(lv - gv);
+    if (key > best.key) {                  // ascending index: strict > keeps the first of a tie
+      best = Pick{key, (int64_t)i};
+      bl = lv; bg = gv;
+    }
+  }
+  const Pick win = block_best(best, slot);
+  tpe_joint_wide_record* rec = w.chunk_rec + at.slot;
+  if (win.key == 0) {
+    if (t == 0) rec->global_idx = -1;
+    return;
+  }
+  if (best.key != win.key || best.idx != win.idx) return;
+  rec->global_idx = win.idx + (int64_t)w.cand_base;
+  rec->l = bl;
+  rec->g = bg;
+  const WideZ zs = wide_z_of(w, at.id, (int)win.idx);
+  for (int d = 0; d < kWD; ++d) rec->z[d] = d < D ? (double)zs.at[(int64_t)d * zs.step] : 0.0;
+}
+
 // ------------------------------------------------------------- host driver
 // Everything from here on runs on the host: the stages' argument checks,
 // the kernel-argument fills and the launches.  What the stages share exists
@@ -2872,8 +3103,12 @@ void fill_wide(WideK& k, const A* a, int D, int64_t n_chunks, int64_t nblk, uint
   const bool inject = (a->flags & TPE_JOINT_INJECT) != 0;
   k.D = D; k.C = a->n_cand; k.n_chunks = (int)n_chunks; k.nblk = (int)nblk; k.inject = inject ? 1 : 0;
   k.kb = a->k_below; k.ka = a->k_above; k.cand_base = cand_base;
-  k.bmu = a->below_mu; k.ba = a->below_a; k.bc = a->below_c;
-  k.amu = a->above_mu; k.aa = a->above_a; k.ac = a->above_c;
+  if constexpr (std::is_same<decltype(a->below_mu), const float*>::value) {
+    k.bmu = a->below_mu; k.ba = a->below_a; k.bc = a->below_c;
+    k.amu = a->above_mu; k.aa = a->above_a; k.ac = a->above_c;
+  } else {                                 // (the wide float64 stage: its rows go through k_joint_wide_f64_psi)
+    k.bmu = k.ba = k.bc = k.amu = k.aa = k.ac = nullptr;
+  }
   k.bbase = a->below_base; k.abase = a->above_base;
   k.zsrc = inject ? a->inject : zbuf;
   k.cand = cand; k.l_out = l_out; k.g_out = g_out;
@@ -2885,16 +3120,18 @@ void fill_wide(WideK& k, const A* a, int D, int64_t n_chunks, int64_t nblk, uint
 // stage's sampling / scoring arguments with its own fields filled; the shared
 // ones are filled here.  tables(s, timed): the stage's launches before the
 // sampling kernel (the quantised stage's tables); chunk(blocks, s, ev): its
-// scoring launch at its padded widths.
+// scoring launch at its padded widths.  more: the bytes the stage keeps in the
+// scratch behind the records and the candidate block.
 template <typename A, typename SK, typename K, typename SampKernel, typename Tables, typename Chunk>
 int joint_wide_stage(const char* E, const A* a, int Dx, SK& sk, K& k, SampKernel samp_kernel, Tables tables,
                      Chunk chunk, tpe_joint_wide_record* records, float* cand, double* l_out, double* g_out,
-                     void* scratch, uint64_t scratch_bytes, void* stream, uint32_t cand_base) {
+                     void* scratch, uint64_t scratch_bytes, void* stream, uint32_t cand_base, uint64_t more = 0) {
   const int D = a->n_dims;
   const bool inject = (a->flags & TPE_JOINT_INJECT) != 0;
   const int64_t n_chunks = wide_chunks_of(a->n_cand, D), blocks = n_chunks * a->n_ids;
   const int64_t nblk = wide_blocks_of(a->n_cand), sblocks = nblk * a->n_ids;
-  if (int rc = check_scratch(E, sblocks, wide_scratch_need(a->n_ids, a->n_cand, D, Dx), scratch, scratch_bytes)) return rc;
+  if (int rc = check_scratch(E, sblocks, wide_scratch_need(a->n_ids, a->n_cand, D, Dx) + more, scratch, scratch_bytes))
+    return rc;
 
   const bool timed = g_prof.on != 0;
   hipStream_t s = (hipStream_t)stream;
@@ -2930,6 +3167,67 @@ int joint_wide_run_at(const tpe_joint_wide_args* a, tpe_joint_wide_record* recor
   };
   return joint_wide_stage(E, a, 0, sk, k, k_joint_wide_sample, kNoTables, chunk, records, cand, l_out, g_out, scratch,
                           scratch_bytes, stream, cand_base);
+}
+
+// the wide float64 stage: tpe_joint_wide_run's head, sampler, chunk records and
+// merge; its own rows and centres, the psi launch before the sampler, its kernel.
+// The scratch: the wide stage's, filled up to a multiple of 16 bytes, then psi.
+static_assert(offsetof(tpe_joint_wide_f64_args, low) == offsetof(tpe_joint_wide_args, low) &&
+                  offsetof(tpe_joint_wide_f64_args, high) == offsetof(tpe_joint_wide_args, high) &&
+                  offsetof(tpe_joint_wide_f64_args, centre) == sizeof(tpe_joint_wide_args),
+              "tpe_joint_wide_f64_args is tpe_joint_wide_args with f64 rows, then the centres");
+uint64_t wide_f64_psi_off(int32_t n_ids, int32_t n_cand, int D) {
+  return (wide_scratch_need(n_ids, n_cand, D) + 15) & ~(uint64_t)15;
+}
+uint64_t wide_f64_psi_bytes(int D, int32_t k_below, int32_t k_above) {
+  const uint64_t cbs = ((uint64_t)k_below + 15) / 16 + ((uint64_t)k_above + 15) / 16;
+  return cbs * (uint64_t)f64_steps(wide_dp(D)) * 64 * sizeof(double);
+}
+uint64_t wide_f64_scratch_need(int32_t n_ids, int32_t n_cand, int D, int32_t k_below, int32_t k_above) {
+  return wide_f64_psi_off(n_ids, n_cand, D) + wide_f64_psi_bytes(D, k_below, k_above);
+}
+
+int joint_wide_f64_run(const tpe_joint_wide_f64_args* a, tpe_joint_wide_record* records, float* cand, double* l_out,
+                       double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
+  constexpr const char* E = "tpe_joint_wide_f64_run";
+  tpe_internal_epoch_bump();
+  if (!a) return fail(E, "null args");
+  if (a->n_dims < 1 || a->n_dims > TPE_JOINT_WIDE_MAX_DIMS)
+    return fail(E, "n_dims outside [1, TPE_JOINT_WIDE_MAX_DIMS]");
+  if (int rc = check_solo_head(E, a, records, a->n_dims)) return rc;
+  for (int d = 0; d < a->n_dims; ++d)
+    if (!isfinite(a->centre[d])) return fail(E, "centre not finite");
+  if ((uintptr_t)scratch & 15) return fail(E, "scratch not 16-byte aligned");
+
+  const int D = a->n_dims;
+  const uint64_t psi_off = wide_f64_psi_off(a->n_ids, a->n_cand, D);
+  const int64_t nbb = ((int64_t)a->k_below + 15) / 16, nba = ((int64_t)a->k_above + 15) / 16;
+  WideSampK sk;
+  WideF64K k;
+  WideF64PsiK pk;
+  pk.D = D; pk.DP = wide_dp(D); pk.kb = a->k_below; pk.ka = a->k_above;
+  pk.bmu = a->below_mu; pk.ba = a->below_a; pk.bc = a->below_c;
+  pk.amu = a->above_mu; pk.aa = a->above_a; pk.ac = a->above_c;
+  pk.psi = (double*)((char*)scratch + psi_off);
+  for (int d = 0; d < kWD; ++d) pk.centre[d] = k.centre[d] = d < D ? a->centre[d] : 0.0;
+  k.bpsi = pk.psi; k.apsi = pk.psi + nbb * f64_steps(pk.DP) * 64;
+  // under profiling between the events that tpe_joint_wide_f64_profile reads
+  auto tables = [&](hipStream_t s, bool timed) {
+    if (timed)
+      if (int rc = ensure_events(g_qprof.ev, 2)) return rc;
+    launch(k_joint_wide_f64_psi, dim3((unsigned)(nbb + nba)), kThreads, 0u, s, timed ? g_qprof.ev[0] : nullptr,
+           timed ? g_qprof.ev[1] : nullptr, pk);
+    if (timed) g_qprof.valid = 1;
+    return (int)TPE_OK;
+  };
+  auto chunk = [&](unsigned blocks, hipStream_t s, Ev ev) {
+    for_wide_dp(D, [&](auto dp) {
+      launch(k_joint_wide_f64_chunk<decltype(dp)::value>, dim3(blocks), kThreads, 0u, s, ev.start, ev.stop, k);
+    });
+  };
+  return joint_wide_stage(E, a, 0, sk, k.w, k_joint_wide_sample, tables, chunk, records, cand, l_out, g_out, scratch,
+                          scratch_bytes, stream, 0u, wide_f64_scratch_need(a->n_ids, a->n_cand, D, a->k_below, a->k_above) -
+                                                         wide_scratch_need(a->n_ids, a->n_cand, D));
 }
 
 // (cand_base: the kernels carry it as the wide stage's do; tpe_joint_run_shard does not take this stage yet)
@@ -3486,6 +3784,25 @@ int tpe_joint_f64_scratch_bytes(int32_t n_ids, int32_t n_cand, uint64_t* bytes) 
 int tpe_joint_f64_run(const tpe_joint_f64_args* a, tpe_joint_record* records, float* cand, double* l_out,
                       double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
   return joint_f64_run(a, records, cand, l_out, g_out, scratch, scratch_bytes, stream);
+}
+
+int tpe_joint_wide_f64_scratch_bytes(int32_t n_ids, int32_t n_cand, int32_t n_dims, int32_t k_below, int32_t k_above,
+                                     uint64_t* bytes) {
+  const bool ok = n_ids >= 1 && n_cand >= 1 && n_dims >= 1 && n_dims <= TPE_JOINT_WIDE_MAX_DIMS && k_below >= 1 &&
+                  k_above >= 1;
+  return size_out("tpe_joint_wide_f64_scratch_bytes", ok,
+                  ok ? wide_f64_scratch_need(n_ids, n_cand, n_dims, k_below, k_above) : 0, bytes);
+}
+
+int tpe_joint_wide_f64_run(const tpe_joint_wide_f64_args* a, tpe_joint_wide_record* records, float* cand,
+                           double* l_out, double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
+  return joint_wide_f64_run(a, records, cand, l_out, g_out, scratch, scratch_bytes, stream);
+}
+
+int tpe_joint_wide_f64_profile(double* psi_ms) {
+  if (!psi_ms || !g_qprof.valid)
+    return fail("tpe_joint_wide_f64_profile", "no profiled tpe_joint_wide_f64_run to read");
+  return elapsed_ms(g_qprof.ev[0], g_qprof.ev[1], psi_ms);
 }
 
 int tpe_joint_seg_run(const tpe_joint_seg_args* a, tpe_joint_record* records, float* cand, double* l_out,

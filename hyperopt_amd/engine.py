@@ -1027,28 +1027,41 @@ class Engine(object):
         'fp32' call, in float64 from the unrounded rows; ``inject``,
         ``return_cand``, ``want_lg`` and ``stream_word`` work as they do
         without it, ``report_k`` > 0, ``shard`` and ``liar`` raise ValueError."""
-        if precision not in ('fp32', 'fp64'):
-            raise ValueError("joint stage: precision must be 'fp32' or 'fp64': %r" % (precision,))
-        if precision == 'fp64':
-            for name, on in (('report_k', int(report_k) > 0), ('shard', shard is not None),
-                             ('liar', not (liar is False or liar is None))):
-                if on:
-                    raise ValueError("joint stage: precision='fp64' does not combine with %s: it is an fp32 stage"
-                                     % name)
-            self._liar(liar, given, return_sigma, report_k, shard)
+        if self._joint_fp64(precision, report_k, shard, liar, given, return_sigma):
             return self._joint_solo('f64', below, above, low, high, (), (), ids, n_cand, seed, inject, return_cand,
                                     want_lg, 0, stream_word, None)
         return self._joint_continuous(False, below, above, low, high, ids, n_cand, seed, inject, return_cand, want_lg,
                                       stream_word, report_k, shard, self._liar(liar, given, return_sigma, report_k,
                                                                                shard))
 
+    def _joint_fp64(self, precision, report_k, shard, liar, given, return_sigma):
+        """Whether ``precision`` asks for a float64 stage (run_joint,
+        run_joint_wide); ValueError for another value and for what those stages
+        do not take.  Touches no device."""
+        if precision not in ('fp32', 'fp64'):
+            raise ValueError("joint stage: precision must be 'fp32' or 'fp64': %r" % (precision,))
+        if precision == 'fp32':
+            return False
+        for name, on in (('report_k', int(report_k) > 0), ('shard', shard is not None),
+                         ('liar', not (liar is False or liar is None))):
+            if on:
+                raise ValueError("joint stage: precision='fp64' does not combine with %s: it is an fp32 stage" % name)
+        self._liar(liar, given, return_sigma, report_k, shard)
+        return True
+
     def run_joint_wide(self, below, above, low, high, ids, n_cand, seed, inject=None, return_cand=False,
                        want_lg=False, report_k=0, shard=None, stream_word=None, liar=False, given=None,
-                       return_sigma=False):
+                       return_sigma=False, precision='fp32'):
         """``run_joint`` for up to N.JOINT_WIDE_MAX_DIMS dimensions
         (tpe_joint_wide_run, include/tpe_hip.h "Wide joint stage"): the same
         arguments, model, Philox streams and return shapes; the records are
-        N.JOINT_WIDE_RECORD_DTYPE."""
+        N.JOINT_WIDE_RECORD_DTYPE.  ``precision`` 'fp64' (DESIGN.md "Wide
+        float64 joint stage"): tpe_joint_wide_f64_run scores the 'fp32' call's
+        candidates, bit for bit, in float64 from the unrounded rows; what
+        ``run_joint`` takes and refuses with it holds here."""
+        if self._joint_fp64(precision, report_k, shard, liar, given, return_sigma):
+            return self._joint_solo('wide_f64', below, above, low, high, (), (), ids, n_cand, seed, inject,
+                                    return_cand, want_lg, 0, stream_word, None)
         return self._joint_continuous(True, below, above, low, high, ids, n_cand, seed, inject, return_cand, want_lg,
                                       stream_word, report_k, shard, self._liar(liar, given, return_sigma, report_k,
                                                                                shard))
@@ -1083,6 +1096,7 @@ class Engine(object):
     # the solo stages by joint_pack entry: the args struct and the native function
     _JOINT_SOLO = {'run': (N.JointArgs, 'tpe_joint_run'), 'f64': (N.JointF64Args, 'tpe_joint_f64_run'),
                    'wide': (N.JointWideArgs, 'tpe_joint_wide_run'),
+                   'wide_f64': (N.JointWideF64Args, 'tpe_joint_wide_f64_run'),
                    'mixed': (N.JointMixedArgs, 'tpe_joint_mixed_run'),
                    'wide_mixed': (N.JointWideMixedArgs, 'tpe_joint_wide_mixed_run'),
                    'quant': (N.JointQuantArgs, 'tpe_joint_quant_run'),
@@ -1098,7 +1112,7 @@ class Engine(object):
         lattice ends follow the continuous bounds there."""
         r = JP.group_rows(below, above, low, high, cats, quants, entry=entry)
         Dc, Dk, Dq = r['Dc'], r['Dk'], r['Dq']
-        D, wide = Dc + Dk + Dq, entry in ('wide', 'wide_mixed', 'wide_quant')
+        D, wide = Dc + Dk + Dq, entry in ('wide', 'wide_f64', 'wide_mixed', 'wide_quant')
         ids, n_ids, C = self._joint_sizes(D, ids, n_cand, shard)
         shard = self._joint_shard(shard, C, report_k, inject)
         if liar is not None:
@@ -1126,7 +1140,7 @@ class Engine(object):
             a.inject = up('inject', JP.inject_rows(inject, C, D), torch.float32)
         for d in range(Dc):
             a.low[d], a.high[d] = r['low'][d], r['high'][d]
-        if entry == 'f64':
+        if entry in ('f64', 'wide_f64'):
             for d in range(Dc):
                 a.centre[d] = r['centre'][d]
         if Dk:
@@ -1329,7 +1343,10 @@ class Engine(object):
         dev_cand, dev_lg = return_cand or keep, want_lg or keep
         nb = ctypes.c_uint64(0)
         rec_dtype = N.JOINT_WIDE_RECORD_DTYPE if wide else N.JOINT_RECORD_DTYPE
-        if wide and n_quant:
+        if fn == 'tpe_joint_wide_f64_run':
+            N.check(self.lib.tpe_joint_wide_f64_scratch_bytes(n_ids, C, D, a.k_below, a.k_above, ctypes.byref(nb)),
+                    self.lib, 'tpe_joint_wide_f64_scratch_bytes')
+        elif wide and n_quant:
             N.check(self.lib.tpe_joint_wide_quant_scratch_bytes(n_ids, C, D - n_cat - n_quant, n_cat, n_quant,
                                                                 ctypes.byref(nb)), self.lib,
                     'tpe_joint_wide_quant_scratch_bytes')

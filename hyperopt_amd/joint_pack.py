@@ -10,6 +10,7 @@ The dimension limits by entry point (``_check_dims``):
   'run'      run_joint             1 <= D <= JOINT_MAX_DIMS, continuous only
   'f64'      run_joint(precision='fp64')  as 'run'; the density rows stay float64, and the group gets its centres
   'wide'     run_joint_wide        1 <= D <= JOINT_WIDE_MAX_DIMS, continuous only
+  'wide_f64' run_joint_wide(precision='fp64')  as 'wide'; float64 density rows and the centres, as 'f64'
   'mixed'    run_joint_mixed       Dk >= 1, Dc + Dk <= JOINT_MAX_DIMS
   'wide_mixed' run_joint_wide_mixed  1 <= Dk <= JOINT_WIDE_MAX_CAT, Dq = 0, 1 <= Dc + Dk <= JOINT_WIDE_MAX_DIMS
   'quant'    run_joint_quant       Dq >= 1, Dc <= JOINT_QUANT_MAX_CONT, Dk <= JOINT_QUANT_MAX_DISC
@@ -107,7 +108,7 @@ def _check_dims(entry, Dc, Dk, Dq):
         raise ValueError('joint stage: a wide segment holds continuous dimensions only, not %d discrete and %d '
                          'quantised ones' % (Dk, Dq))
     else:
-        top = N.JOINT_WIDE_MAX_DIMS if entry in ('wide', 'wide_segment') else N.JOINT_MAX_DIMS
+        top = N.JOINT_WIDE_MAX_DIMS if entry in ('wide', 'wide_f64', 'wide_segment') else N.JOINT_MAX_DIMS
         if not 1 <= Dc + Dk <= top:
             raise ValueError('joint stage: %d dimensions, at most %d' % (Dc + Dk, top))
 
@@ -124,7 +125,8 @@ def group_rows(below, above, low, high, cats=(), quants=(), entry='segment'):
     low, high = np.asarray(low, dtype=np.float64).reshape(-1), np.asarray(high, dtype=np.float64).reshape(-1)
     Dc, Dk, Dq = len(low), len(cats), len(quants)
     _check_dims(entry, Dc, Dk, Dq)
-    if entry == 'f64' and (Dk or Dq):
+    f64 = entry in ('f64', 'wide_f64')
+    if f64 and (Dk or Dq):
         raise ValueError('joint stage: the float64 stage holds continuous dimensions only, not %d discrete and %d '
                          'quantised ones' % (Dk, Dq))
     edges = [np.ascontiguousarray(q[4], dtype=np.float64).reshape(-1) for q in quants]
@@ -167,7 +169,7 @@ def group_rows(below, above, low, high, cats=(), quants=(), entry='segment'):
         if Dk:
             (r[name + '_mu'], r[name + '_a'], r[name + '_c'], r[name + '_base'], r[name + '_cat'], r[name + '_miss'],
              r[name + '_bonus']) = J.mixed_density_rows(w, mu, sigma, low, high, np.stack(cols, axis=1), ps, s_side[i])
-        elif entry == 'f64':                         # the same rows before their rounding, and the centres
+        elif f64:                                    # the same rows before their rounding, and the centres
             r[name + '_mu'], r[name + '_a'], r[name + '_c'], r[name + '_base'] = J.density_rows_f64(w, mu, sigma, low,
                                                                                                     high)
             r['f64'], r['centre'] = True, J.expansion_centres(low, high, mu[0])

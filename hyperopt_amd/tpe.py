@@ -847,7 +847,8 @@ def suggest(new_ids, domain, trials, seed,
             sampler='philox', precision='fp32', device=None, shard=None, shard_ids=None, shard_labels=None,
             shard_grid=None, joint=False, joint_discrete=False, joint_quantized=False, joint_wide=False,
             joint_branches=False, joint_branches_mixed=False, joint_branches_wide=False, joint_shard=None,
-            joint_precision='fp32', joint_wide_mixed=False, joint_wide_quantized=False, joint_liar=False):
+            joint_precision='fp32', joint_precision_wide=False, joint_wide_mixed=False, joint_wide_quantized=False,
+            joint_liar=False):
     new_ids = list(new_ids)
     if not new_ids:
         return []
@@ -856,7 +857,8 @@ def suggest(new_ids, domain, trials, seed,
     liar_mode = _joint_liar_mode(joint_liar)
     if liar_mode:
         _joint_liar_check(joint, joint_shard, mode=liar_mode, joint_branches=joint_branches)
-    fp64 = _joint_precision_check(joint_precision, joint, joint_shard, liar_mode)
+    fp64 = _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, None, joint_precision_wide,
+                                  joint_wide)
     if ((joint is not False and joint is not None) or joint_discrete or joint_quantized or joint_wide or joint_branches
             or joint_branches_mixed or joint_branches_wide or joint_wide_mixed or joint_wide_quantized):
         # (argument errors first: no device use, no startup draw)
@@ -869,7 +871,8 @@ def suggest(new_ids, domain, trials, seed,
             _joint_liar_check(joint, joint_shard, plan, liar_mode, joint_branches)
             _wide_quant_liar_check(plan[0], liar_mode)
         if fp64:
-            _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, plan)
+            _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, plan, joint_precision_wide,
+                                   joint_wide)
     t0 = time.time()
     hist = _history.extract(domain, trials)
     if logger.isEnabledFor(logging.INFO):
@@ -889,7 +892,7 @@ def suggest(new_ids, domain, trials, seed,
                               joint_branches_wide=joint_branches_wide, joint_shard=joint_shard,
                               joint_wide_mixed=joint_wide_mixed,
                               joint_wide_quantized=joint_wide_quantized, joint_liar=joint_liar,
-                              joint_precision=joint_precision)
+                              joint_precision=joint_precision, joint_precision_wide=joint_precision_wide)
     logger.info('tpe.suggest took %f seconds', time.time() - t0)
     return rand.docs_from_choices(new_ids, domain, trials, choices)
 
@@ -931,8 +934,8 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
                     sampler='philox', precision='fp32', device=None, shard=None, columns=False,
                     shard_ids=None, shard_labels=None, shard_grid=None, joint=False, joint_discrete=False,
                     joint_quantized=False, joint_wide=False, joint_branches=False, joint_branches_mixed=False,
-                    joint_branches_wide=False, joint_shard=None, joint_precision='fp32', joint_wide_mixed=False,
-                    joint_wide_quantized=False, joint_liar=False):
+                    joint_branches_wide=False, joint_shard=None, joint_precision='fp32', joint_precision_wide=False,
+                    joint_wide_mixed=False, joint_wide_quantized=False, joint_liar=False):
     """The suggest core on a structure-of-arrays history (``history.History``):
     per new id a {label: value or None} dict.  ``suggest`` wraps it with the
     Trials document layout; columnar callers (and bench.py's large configs)
@@ -1127,7 +1130,17 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
     discrete or quantised label or more than 16 labels, with any branch group,
     with ``joint_shard`` or ``joint_liar``, and for any other value it raises
     ValueError; joint_candidate_report does not take it.  (``precision='fp64'``,
-    the univariate parity mode, still does not combine with ``joint``.)"""
+    the univariate parity mode, still does not combine with ``joint``.)
+
+    ``joint_precision_wide=True`` (with ``joint_precision='fp64'`` and
+    ``joint_wide=True``): a root group of 17 to 64 continuous labels is scored
+    in float64 too (DESIGN.md "Wide float64 joint stage",
+    Engine.run_joint_wide(precision='fp64')), over the fp32 wide stage's pool
+    bit for bit; a root group of at most 16 labels takes the stage above with
+    the same bytes.  Without either of the two keywords, with a discrete or
+    quantised label in the group, more than 64 labels, any branch group,
+    ``joint_shard`` or ``joint_liar`` it raises ValueError;
+    joint_candidate_report does not take it."""
     if sampler not in ('philox', 'replay'):
         raise ValueError("sampler must be 'philox' or 'replay'")
     if joint_shard is not None:
@@ -1135,7 +1148,8 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
     liar_mode = _joint_liar_mode(joint_liar)
     if liar_mode:
         _joint_liar_check(joint, joint_shard, mode=liar_mode, joint_branches=joint_branches)
-    fp64 = _joint_precision_check(joint_precision, joint, joint_shard, liar_mode)
+    fp64 = _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, None, joint_precision_wide,
+                                  joint_wide)
     group, branch_groups = None, []
     if ((joint is not False and joint is not None) or joint_discrete or joint_quantized or joint_wide or joint_branches
             or joint_branches_mixed or joint_branches_wide or joint_wide_mixed or joint_wide_quantized):
@@ -1150,7 +1164,8 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
             _joint_liar_check(joint, joint_shard, (group, branch_groups), liar_mode, joint_branches)
             _wide_quant_liar_check(group, liar_mode)
         if fp64:
-            _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, (group, branch_groups))
+            _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, (group, branch_groups),
+                                   joint_precision_wide, joint_wide)
     if sum(a is not None for a in (shard, shard_ids, shard_labels, shard_grid)) > 1:
         raise ValueError('shard, shard_ids, shard_labels and shard_grid are exclusive: one shard axis per suggest')
     if (shard_ids is not None or shard_labels is not None or shard_grid is not None) and sampler == 'replay':
@@ -1185,17 +1200,25 @@ def _joint_liar_mode(joint_liar):
                      'joint_branches (or False): %r' % (joint_liar,))
 
 
-def _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, plan=None):
+def _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, plan=None, wide_f64=False, joint_wide=False):
     """Whether ``joint_precision`` asks for the float64 stage; ValueError for a
     value other than 'fp32' / 'fp64' and where 'fp64' does not apply: without
     ``joint``, with ``joint_shard`` or ``joint_liar``, and (``plan`` =
     _joint_plan's result) without a root group, for a root group that holds a
-    discrete or quantised label or more than TPE_JOINT_MAX_DIMS labels, and for
-    any branch group.  Touches no device."""
+    discrete or quantised label or more than TPE_JOINT_MAX_DIMS labels
+    (``wide_f64``, the joint_precision_wide keyword: TPE_JOINT_WIDE_MAX_DIMS),
+    and for any branch group; for ``wide_f64`` without 'fp64' or without
+    ``joint_wide``.  Touches no device."""
     if joint_precision not in ('fp32', 'fp64'):
         raise ValueError("joint_precision must be 'fp32' or 'fp64': %r" % (joint_precision,))
+    if wide_f64 and joint_precision != 'fp64':
+        raise ValueError("joint_precision_wide=True needs joint_precision='fp64': it only widens the groups that "
+                         'keyword scores in float64')
     if joint_precision == 'fp32':
         return False
+    if wide_f64 and not joint_wide:
+        raise ValueError('joint_precision_wide=True needs joint_wide=True: it only scores the wide groups that keyword '
+                         'joins in float64')
     if joint is False or joint is None:
         raise ValueError("joint_precision='fp64' needs joint=True or joint=[labels]: it only changes how the joint "
                          'stage scores')
@@ -1217,9 +1240,12 @@ def _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, plan=
     if other:
         raise ValueError("joint_precision='fp64' needs a root group of continuous labels only: %r is discrete or "
                          'quantised, and the mixed and quantised joint stages score in fp32 only' % other[0])
-    if len(group) > TPE_JOINT_MAX_DIMS:
+    if len(group) > TPE_JOINT_MAX_DIMS and not wide_f64:
         raise ValueError("joint_precision='fp64' takes a root group of at most %d labels, not %d: the wide joint stage "
                          'scores in fp32 only' % (TPE_JOINT_MAX_DIMS, len(group)))
+    if len(group) > TPE_JOINT_WIDE_MAX_DIMS:
+        raise ValueError("joint_precision='fp64' with joint_precision_wide=True takes a root group of at most %d "
+                         'labels, not %d' % (TPE_JOINT_WIDE_MAX_DIMS, len(group)))
     return True
 
 

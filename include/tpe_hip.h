@@ -1281,6 +1281,62 @@ int tpe_joint_wide_run(const tpe_joint_wide_args* args, tpe_joint_wide_record* r
 int tpe_joint_wide_profile(double* sample_ms);
 
 /* ------------------------------------------------------------------------
+ * Wide float64 joint stage (tpe_joint.hip; additive to ABI 24):
+ * tpe_joint_wide_run with the scoring in f64, as tpe_joint_f64_run is to
+ * tpe_joint_run.  The sampler, its Philox streams, the candidate block, the
+ * chunks, tpe_joint_wide_record, the chunk records and their merge are
+ * tpe_joint_wide_run's, so the same seed, ids and stream word give both stages
+ * the same f32 pool bit for bit.  The density rows, the centres, the expanded
+ * form phi . psi_k, the running (max, sum) pairs, the skipped 16 x 16 blocks and
+ * the score are tpe_joint_f64_run's.
+ *
+ * Three launches and the merge: k_joint_wide_f64_psi writes psi_k of both sides
+ * once into `scratch`, in the layout the matrix instruction's B operand is read
+ * in; k_joint_wide_sample (skipped under TPE_JOINT_INJECT);
+ * k_joint_wide_f64_chunk<DP> (DP in {20, 24, 32, 48, 64}) stages tiles of psi in
+ * LDS by plain copies and forms phi from the f32 candidates beside the matrix
+ * instructions.  No atomics: the same call twice gives the same bytes.
+ *
+ * scratch (16-byte aligned):
+ *   tpe_joint_wide_scratch_bytes(n_ids, n_cand, n_dims) rounded up to 16, then
+ *   (ceil(k_below / 16) + ceil(k_above / 16)) * (DP / 2 + 1) * 512 bytes of psi,
+ *   DP the padded width of n_dims.
+ *
+ * tpe_joint_wide_f64_run returns TPE_E_ARG before any launch (no device needed)
+ * for everything tpe_joint_wide_run does, for a centre that is not finite, for a
+ * scratch that is not 16-byte aligned or smaller than
+ * tpe_joint_wide_f64_scratch_bytes(n_ids, n_cand, n_dims, k_below, k_above).
+ * tpe_joint_profile and tpe_joint_wide_profile serve this stage too;
+ * tpe_joint_wide_f64_profile reads the psi kernel's time (ms) of the last
+ * profiled run (it WAITS for it).
+ * ---------------------------------------------------------------------- */
+typedef struct tpe_joint_wide_f64_args {
+  int32_t n_dims, n_cand, n_ids, flags;   /* as tpe_joint_wide_args ... */
+  int32_t k_below, k_above;
+  uint32_t stream_word;
+  int32_t reserved;
+  uint64_t seed;
+  const double *below_mu, *below_a, *below_c;   /* ... but f64, as tpe_joint_f64_args */
+  const double *above_mu, *above_a, *above_c;
+  double below_base, above_base;
+  const double* samp_cum;
+  const float* samp;
+  const int64_t* ids;
+  const float* inject;
+  double low[TPE_JOINT_WIDE_MAX_DIMS], high[TPE_JOINT_WIDE_MAX_DIMS];
+  double centre[TPE_JOINT_WIDE_MAX_DIMS];   /* entries from n_dims on: ignored */
+} tpe_joint_wide_f64_args;
+
+int tpe_joint_wide_f64_scratch_bytes(int32_t n_ids, int32_t n_cand, int32_t n_dims, int32_t k_below, int32_t k_above,
+                                     uint64_t* bytes);
+
+/* records, cand, l_out, g_out, scratch and stream as tpe_joint_wide_run */
+int tpe_joint_wide_f64_run(const tpe_joint_wide_f64_args* args, tpe_joint_wide_record* records, float* cand,
+                           double* l_out, double* g_out, void* scratch, uint64_t scratch_bytes, void* stream);
+
+int tpe_joint_wide_f64_profile(double* psi_ms);
+
+/* ------------------------------------------------------------------------
  * Mixed joint stage (tpe_joint.hip; additive to ABI 24): a group of n_dims
  * continuous labels (0 allowed) and n_cat discrete ones (randint /
  * categorical), 1 <= n_dims + n_cat <= TPE_JOINT_MAX_DIMS.  Kernel coordinate

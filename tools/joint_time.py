@@ -139,7 +139,18 @@ call also timed by the chunk kernel's own events (tpe_joint_profile).  Untimed,
 both stages return l and g of the whole shared pool: the line carries the worst
 |l32 - l64| and |g32 - g64| in units of the fp32 tolerance 1e-5 max(1, |ref|)
 with the float64 stage as ref, and how many ids' winners differ.  --out
-defaults to profiles/joint_fp64_time.jsonl."""
+defaults to profiles/joint_fp64_time.jsonl.
+
+--wide --fp64: the wide float64 stage (DESIGN.md "Wide float64 joint stage").
+--wide's flat spaces at D = 16, 20 and 64; per pair, alternating in one process,
+the fp32 and the float64 stage at each D (D = 16: Engine.run_joint, the narrow
+float64 stage as the yardstick), the chunk kernels by their own events, the
+sampling and the psi kernel by theirs.  The line carries per run the medians and
+ranges, the evaluations per second, the ratio to the fp32 kernel at the same D
+and to the narrow float64 stage's rate; and, untimed, the worst |l32 - l64| and
+|g32 - g64| over the whole shared pool in units of the fp32 tolerance at D = 20
+and 64, on the flat space and on one whose trials are clustered so that every
+bandwidth is psig / 100.  --out defaults to profiles/joint_wide_fp64_time.jsonl."""
 import argparse
 import ctypes
 import json
@@ -373,14 +384,18 @@ def main_quant(args):
     return 0
 
 
-def make_flat_history(n, D):
+def make_flat_history(n, D, clustered=False):
     """D labels of hp.uniform(-5, 5) (bench.py config 4's space at D = 20), a
-    seeded history whose loss is a shifted bowl with one product term."""
+    seeded history whose loss is a shifted bowl with one product term.
+    ``clustered``: every trial within 1e-3 prior sigmas of one point, so every
+    bandwidth is clipped to psig / 100."""
     from hyperopt_amd import base, history as H, hp
     labels = ['x%02d' % i for i in range(D)]
     domain = base.Domain(lambda d: 0.0, {k: hp.uniform(k, -5, 5) for k in labels})
     rs = np.random.RandomState(SEED + D)
     X = rs.uniform(-5, 5, (n, D))
+    if clustered:
+        X = 1.5 + 1e-2 * rs.uniform(0, 1, (n, D))
     loss = ((X - np.linspace(-2, 2, D)[None, :]) ** 2).sum(axis=1) + X[:, 0] * X[:, 1] + 0.01 * rs.standard_normal(n)
     tids = np.arange(n, dtype=np.int64)
     return domain, H.History(tids, loss, {k: (tids, X[:, i]) for i, k in enumerate(labels)})
@@ -467,6 +482,89 @@ def main_wide(args):
     text = json.dumps(line)
     print(text)
     out = args.out or os.path.join(ROOT, 'profiles', 'joint_wide_time.jsonl')
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, 'a') as f:
+        f.write(text + '\n')
+    return 0
+
+
+def main_wide_fp64(args):
+    import torch
+    from hyperopt_amd import _native as N, history as H, joint as J
+    from hyperopt_amd.engine import get_engine
+
+    eng = get_engine(None, 'fp32')
+    lib = eng.lib
+    C = args.cand
+    ids = np.array([args.history], dtype=np.int64)
+    models = {}
+    for D, clustered in ((16, False), (20, False), (64, False), (20, True), (64, True)):
+        domain, hist = make_flat_history(args.history, D, clustered)
+        models[D, clustered] = J.fit_model(list(domain.table.rows), hist, H.split_below(hist, 0.25), 1.0)
+
+    def run(D, precision, clustered=False, **kw):
+        m = models[D, clustered]
+        fn = eng.run_joint if D <= N.JOINT_MAX_DIMS else eng.run_joint_wide
+        return fn(m.below, m.above, m.low, m.high, ids, C, SEED, precision=precision, **kw)
+
+    def kernel_ms(D, precision):
+        ms2, sms, pms = (ctypes.c_double * 2)(), ctypes.c_double(0.0), ctypes.c_double(0.0)
+        torch.cuda.synchronize()
+        N.check(lib.tpe_joint_profile(1, None), lib, 'tpe_joint_profile')
+        run(D, precision)
+        if D > N.JOINT_MAX_DIMS:
+            N.check(lib.tpe_joint_wide_profile(ctypes.byref(sms)), lib, 'tpe_joint_wide_profile')
+            if precision == 'fp64':
+                N.check(lib.tpe_joint_wide_f64_profile(ctypes.byref(pms)), lib, 'tpe_joint_wide_f64_profile')
+        N.check(lib.tpe_joint_profile(0, ms2), lib, 'tpe_joint_profile')
+        return ms2[0], ms2[1], sms.value, pms.value
+
+    routes = [(D, p) for D in (16, 20, 64) for p in ('fp32', 'fp64')]
+    for _ in range(args.warmup):
+        for r in routes:
+            run(*r)
+    ms = dict((r, []) for r in routes)
+    for i in range(args.pairs):
+        for r in routes:
+            ms[r].append(kernel_ms(*r))
+        print('pair %d: %s' % (i, ', '.join('D=%d %s %.3f ms' % (r + (ms[r][-1][0],)) for r in routes)),
+              file=sys.stderr, flush=True)
+
+    # (untimed) both stages' l and g over the whole shared pool, the float64 stage as the reference
+    def err(a, ref):
+        return float(np.max(np.abs(a - ref) / np.maximum(1.0, np.abs(ref)))) / 1e-5
+    dist = {}
+    for D in (20, 64):
+        for clustered in (False, True):
+            r32, c32, l32, g32 = run(D, 'fp32', clustered, return_cand=True, want_lg=True)
+            r64, c64, l64, g64 = run(D, 'fp64', clustered, return_cand=True, want_lg=True)
+            assert c32.tobytes() == c64.tobytes()
+            dist['D%d_%s' % (D, 'clustered' if clustered else 'flat')] = dict(
+                l_err_over_fp32_tol=err(l32, l64), g_err_over_fp32_tol=err(g32, g64),
+                winners_differ=int((r32['global_idx'] != r64['global_idx']).sum()))
+
+    def stat(r, j=0):
+        x = [q[j] for q in ms[r]]
+        return dict(median=float(np.median(x)), min=min(x), max=max(x), all=x)
+
+    def rate(r):
+        m = models[r[0], False]
+        k = stat(r)['median']
+        return float(C) * (len(m.below[0]) + len(m.above[0])) * r[0] / (k * 1e-3) if k > 0 else None
+    runs = {}
+    for r in routes:
+        D, prec = r
+        m, wide = models[D, False], D > N.JOINT_MAX_DIMS
+        runs['D%d_%s' % r] = dict(
+            n_dims=D, k_below=len(m.below[0]), k_above=len(m.above[0]), chunk_ms=stat(r), merge_ms=stat(r, 1)['median'],
+            sample_ms=stat(r, 2) if wide else None, psi_ms=stat(r, 3) if wide and prec == 'fp64' else None,
+            evals_per_s=rate(r), ratio_to_fp32_kernel=stat(r)['median'] / stat((D, 'fp32'))['median'],
+            evals_per_s_over_narrow_fp64_D16=rate(r) / rate((16, 'fp64')))
+    line = dict(tool='joint_time --wide --fp64', history=args.history, n_cand=C, pairs=args.pairs, runs=runs,
+                fp32_to_fp64_distance=dist, gpu=torch.cuda.get_device_name(0))
+    text = json.dumps(line)
+    print(text)
+    out = args.out or os.path.join(ROOT, 'profiles', 'joint_wide_fp64_time.jsonl')
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, 'a') as f:
         f.write(text + '\n')
@@ -1165,6 +1263,8 @@ def main():
         return main_mixed(args)
     if args.quant:
         return main_quant(args)
+    if args.wide and args.fp64:
+        return main_wide_fp64(args)
     if args.wide:
         return main_wide(args)
     if args.wide_mixed:
