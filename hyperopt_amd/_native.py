@@ -575,6 +575,7 @@ EXPORTS = ('tpe_abi_version', 'tpe_last_error', 'tpe_device_count', 'tpe_tile_si
            'tpe_replay_mixture', 'tpe_replay_categorical', 'tpe_level_profile', 'tpe_level_profile_read',
            'tpe_suggest_tree', 'tpe_comm_unique_id', 'tpe_comm_init', 'tpe_comm_destroy', 'tpe_combine_results',
            'tpe_host_threads', 'tpe_host_phases', 'tpe_exchange_allgather', 'tpe_debug_fast_lg',
+           'tpe_debug_fast_image', 'tpe_debug_fast_runs',
            'tpe_collectives_issued', 'tpe_level_resident', 'tpe_level_resident_fused', 'tpe_scatter_f64', 'tpe_move_ranges', 'tpe_report_scratch_bytes', 'tpe_report',
            'tpe_report_profile', 'tpe_joint_scratch_bytes', 'tpe_joint_run', 'tpe_joint_profile',
            'tpe_joint_f64_scratch_bytes', 'tpe_joint_f64_run',
@@ -688,6 +689,10 @@ def load(path=LIB_PATH):
     lib.tpe_host_phases.restype = ctypes.c_int
     lib.tpe_debug_fast_lg.argtypes = [P, I64]
     lib.tpe_debug_fast_lg.restype = ctypes.c_int
+    lib.tpe_debug_fast_image.argtypes = [I32, P, I64]
+    lib.tpe_debug_fast_image.restype = ctypes.c_int
+    lib.tpe_debug_fast_runs.argtypes = [I32, I32, I32, P, I64, ctypes.POINTER(I32)]
+    lib.tpe_debug_fast_runs.restype = ctypes.c_int
     lib.tpe_level_resident.argtypes = [I32, ctypes.POINTER(I64)]
     lib.tpe_level_resident.restype = ctypes.c_int
     lib.tpe_level_resident_fused.argtypes = [ctypes.POINTER(I64)]

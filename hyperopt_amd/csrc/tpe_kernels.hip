@@ -340,7 +340,9 @@ __device__ __forceinline__ int tile_pos(int cand_start, int j) {
 // block per candidate (53-bit selection, 53-bit inversion).
 struct DrawU { double us; float uf; double ud; uint32_t ws; };   // ws: us's 32-bit word (f32 draws)
 // (the per-call words given apart from the row: k_sample_fast's argument-keyed launch)
-__device__ __forceinline__ DrawU draw_uniforms(const tpe_problem& p, int64_t i, int precision, uint32_t ctr3,
+// (Row: tpe_problem, or the fused hit's image header)
+template <class Row>
+__device__ __forceinline__ DrawU draw_uniforms(const Row& p, int64_t i, int precision, uint32_t ctr3,
                                                uint32_t key0, uint32_t key1) {
   const uint64_t g = (uint64_t)p.cand_base + (uint64_t)i;
   if (precision == TPE_PREC_F32 && p.family != TPE_FAM_CATEGORICAL) {
@@ -1605,6 +1607,9 @@ __global__ __launch_bounds__(kTabThreads) void k_sample_tab(const tpe_problem* _
 // budget (NP = 2: 80 VGPRs and 105 SGPRs), and a run-time selection of the three
 // words spilled scalar registers into vector lanes and those into scratch.
 // Without AK the arguments are unused and the kernel is the row-keyed one.
+// The AK kernel also starts each run from the record's prepared image
+// (k_fast_prep, above) and a run descriptor instead of the problem row, the
+// tile list and the f64 sampler rows, and writes run r's record at index r.
 constexpr int kFastThreads = 512;
 constexpr int kFastSamp = 64;                  // sampler rows (below components) in LDS
 constexpr int kFastWgsPerCu = 3;
@@ -1637,6 +1642,110 @@ __device__ void lattice_ranks(const double2* __restrict__ rows, int n, int* __re
   }
 }
 
+// guide entry b of a selection CDF of `len` rows (cum: the rows' cumulative masses)
+__device__ __forceinline__ GuideEnt fast_guide_entry(const double* __restrict__ cum, int len, int b) {
+  const double v = (double)b / (double)kGuide;
+  int a = 0, e2 = len - 1;
+  while (a < e2) { const int m = (a + e2) >> 1; if (v < cum[m]) e2 = m; else a = m + 1; }
+  GuideEnt e;
+  e.k0 = a;
+  e.never = 0u;
+  e.t0 = guide_thresh(a < len - 1 ? cum[a] : INFINITY, e.never, 1u);
+  e.t1 = guide_thresh(a + 1 < len - 1 ? cum[a + 1] : INFINITY, e.never, 2u);
+  return e;
+}
+
+// ---- the fused hit's prepared image (k_fast_prep -> k_sample_fast<NP, false, true>) ----
+// What a sample-stage workgroup derives from a tabulated problem before its
+// first candidate is a function of the resident level alone.  The miss that
+// makes a level resident writes it once per problem, as 16-byte units: a header
+// (the row's scalars the kernel reads, with the same names, and the f32 values
+// it derives from them), the selection CDF, the f32 sampler rows, the guide and
+// a lattice's score ranks.  The argument-keyed kernel reads the header through
+// scalar loads and brings the rest to LDS by LDS-DMA beside the table rows.
+struct FastHdr {
+  int64_t cand_base, cand_off, lat_lo;
+  double q, below_base, above_base;
+  int32_t family, n_cand, samp_len, tab_mode;
+  uint32_t ctr2;
+  int32_t below_off, below_len, above_off;
+  int32_t above_len, wide_off, wide_len, pad0;
+  int32_t tab_off[1], tab_n[1];
+  float tab_lo[1], tab_inv[1];
+  float lo_f, hi_f, w0, ih0;
+};
+static_assert(sizeof(FastHdr) == 128, "image header: 8 units");
+// the sampler part of the image as the kernel's LDS holds it
+struct FastSampLds {
+  double cum[kFastSamp];
+  float4 row[kFastSamp];
+  GuideEnt guide[kGuide];
+};
+constexpr int kFastHdrUnits = (int)sizeof(FastHdr) / 16;
+constexpr int kFastSampUnits = (int)sizeof(FastSampLds) / 16;
+constexpr int kFastRankUnits = (kFastLatMax + 3) / 4;
+constexpr int kFastImgUnits = kFastHdrUnits + kFastSampUnits + kFastRankUnits;   // one problem's image
+static_assert(kFastSampUnits <= kFastThreads, "the sampler part: one LDS-DMA round");
+// a run of the argument-keyed kernel: n_tiles consecutive tiles of problem pid
+// from candidate `start` (n_tiles == 0: the workgroup has no further run); the
+// image, the table and the rank units, so that every load of the run's set-up
+// follows from this one
+struct FastDesc {
+  int32_t pid, start, n_tiles, img_off;
+  int32_t tab_off, tab_units, rank_units, pad0;
+};
+static_assert(sizeof(FastDesc) == 32, "run descriptor: one scalar load");
+
+// the f32 sampler row of f64 sampler row sr (k_sample_fast's staging)
+__device__ __forceinline__ float4 fast_samp_row(const double* __restrict__ sr) {
+  const float sg = (float)sr[2];
+  return make_float4((float)sr[1], sr[5] != 0.0 ? -sg : sg, (float)sr[3], (float)sr[4]);
+}
+
+// one workgroup per problem row (untabulated rows: nothing): problem r's image at unit r * kFastImgUnits
+__global__ __launch_bounds__(kFastThreads)
+void k_fast_prep(const tpe_problem* __restrict__ P, const double* __restrict__ samp, const float4* __restrict__ tab,
+                 uint4* __restrict__ img) {
+  const tpe_problem& p = P[blockIdx.x];
+  if (p.tab_mode == TPE_TAB_NONE) return;                    // (workgroup-uniform)
+  uint4* im = img + (int64_t)blockIdx.x * kFastImgUnits;
+  __shared__ double cum_lds[kFastSamp];
+  const int len = min(p.samp_len, kFastSamp);
+  if (threadIdx.x == 0) {
+    FastHdr h;
+    h.cand_base = p.cand_base; h.cand_off = p.cand_off; h.lat_lo = p.lat_lo;
+    h.q = p.q; h.below_base = p.below_base; h.above_base = p.above_base;
+    h.family = p.family; h.n_cand = p.n_cand; h.samp_len = p.samp_len; h.tab_mode = p.tab_mode;
+    h.ctr2 = p.ctr2;
+    h.below_off = p.below_off; h.below_len = p.below_len; h.above_off = p.above_off;
+    h.above_len = p.above_len; h.wide_off = p.wide_off; h.wide_len = p.wide_len; h.pad0 = 0;
+    h.tab_off[0] = p.tab_off[0]; h.tab_n[0] = p.tab_n[0];
+    h.tab_lo[0] = p.tab_lo[0]; h.tab_inv[0] = p.tab_inv[0];
+    f32_bounds(p, h.lo_f, h.hi_f);
+    h.w0 = 1.f / h.tab_inv[0];
+    h.ih0 = 1.f / (0.5f * h.w0);
+    *reinterpret_cast<FastHdr*>(im) = h;
+  }
+  FastSampLds* sl = reinterpret_cast<FastSampLds*>(im + kFastHdrUnits);
+  if ((int)threadIdx.x < kFastSamp) {
+    double c = 0.0;
+    float4 row = make_float4(0.f, 0.f, 0.f, 0.f);
+    if ((int)threadIdx.x < len) {
+      const double* sr = samp + 8 * (int64_t)p.samp_off + 8 * (int)threadIdx.x;
+      c = sr[0];
+      row = fast_samp_row(sr);
+    }
+    cum_lds[threadIdx.x] = c;
+    sl->cum[threadIdx.x] = c;
+    sl->row[threadIdx.x] = row;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < kGuide) sl->guide[threadIdx.x] = fast_guide_entry(cum_lds, len, (int)threadIdx.x);
+  if (p.tab_mode == TPE_TAB_LATTICE && p.tab_n[0] <= kFastLatMax)
+    lattice_ranks(reinterpret_cast<const double2*>(tab + p.tab_off[0]), p.tab_n[0],
+                  reinterpret_cast<int*>(im + kFastHdrUnits + kFastSampUnits));
+}
+
 // NP = 2: 80 VGPRs, six waves a SIMD (three workgroups a CU: batched levels);
 // NP = 4: two candidate pairs in flight per lane for levels of at most two
 // workgroups a CU (config 3's 2^21 candidates), four waves a SIMD
@@ -1646,13 +1755,18 @@ void k_sample_fast(const tpe_problem* __restrict__ P, const tpe_tile* __restrict
                    const int32_t* __restrict__ list, int n_list, int per_wg, const double* __restrict__ samp,
                    const float4* __restrict__ comp32, const float4* __restrict__ tab,
                    tpe_result* __restrict__ run_best, int tpp, double* __restrict__ lg_out, uint32_t a_key0,
-                   uint32_t a_key1, uint32_t a_ctr3) {
+                   uint32_t a_key1, uint32_t a_ctr3, const uint4* __restrict__ img,
+                   const FastDesc* __restrict__ desc) {
   constexpr int kFastUnit = 64 * NP;
   static_assert(NP % 2 == 0 && kTile % kFastUnit == 0, "fast units: Philox pairs tiling the tiles");
+  static_assert(!(AK && LG), "the argument-keyed kernel has no debug build");
   extern __shared__ float4 fast_tab[];                       // the label's table (tab_fast - 1 units at most)
-  __shared__ double cum_lds[kFastSamp];
-  __shared__ float4 row_lds[kFastSamp];
-  __shared__ GuideEnt guide[kGuide];
+  __shared__ FastSampLds samp_lds;
+  double* const cum_lds = samp_lds.cum;
+  float4* const row_lds = samp_lds.row;
+  GuideEnt* const guide = samp_lds.guide;
+  // (AK: the run's row is its image header)
+  using Row = typename std::conditional<AK, FastHdr, tpe_problem>::type;
   constexpr int kW = kFastThreads / 64;
   struct RunRec { int64_t cand_base, lat_lo; double bb, ab, q; int tile, logc, lat, tab_off; };
   __shared__ RunRec s_run[kTabMaxTilesPerWg];
@@ -1668,31 +1782,78 @@ void k_sample_fast(const tpe_problem* __restrict__ P, const tpe_tile* __restrict
   // lattice) as the bits of flb and fla, draw ft
   float fd = 0.f, flb = 0.f, fla = 0.f, ft = 0.f;
   int fi = -1;
-  if ((int)threadIdx.x < kTabMaxTilesPerWg) s_unit[threadIdx.x] = 0;
-  const int n_my = min(per_wg, n_list - (int)blockIdx.x * per_wg);
-  if ((int)threadIdx.x < n_my) {
-    const int li = (int)blockIdx.x * per_wg + (int)threadIdx.x;
-    const int tile = list ? list[li] : li;
-    s_tile[threadIdx.x] = tile;
-    if (tpp > 0) {
-      const int r = tile / tpp;
-      s_prob[threadIdx.x] = r; s_start[threadIdx.x] = (tile - r * tpp) * kTile;
-    } else {
-      const tpe_tile tl = tiles[tile];
-      s_prob[threadIdx.x] = tl.problem; s_start[threadIdx.x] = tl.cand_start;
+  // AK: per_wg run descriptors a workgroup (its runs first), record r that of descriptor r
+  const int n_my = AK ? per_wg : min(per_wg, n_list - (int)blockIdx.x * per_wg);
+  if constexpr (!AK) {
+    if ((int)threadIdx.x < kTabMaxTilesPerWg) s_unit[threadIdx.x] = 0;
+    if ((int)threadIdx.x < n_my) {
+      const int li = (int)blockIdx.x * per_wg + (int)threadIdx.x;
+      const int tile = list ? list[li] : li;
+      s_tile[threadIdx.x] = tile;
+      if (tpp > 0) {
+        const int r = tile / tpp;
+        s_prob[threadIdx.x] = r; s_start[threadIdx.x] = (tile - r * tpp) * kTile;
+      } else {
+        const tpe_tile tl = tiles[tile];
+        s_prob[threadIdx.x] = tl.problem; s_start[threadIdx.x] = tl.cand_start;
+      }
     }
+    __syncthreads();
   }
-  __syncthreads();
   for (int gi = 0; gi < n_my;) {
-    const int tile = __builtin_amdgcn_readfirstlane(s_tile[gi]), pid = __builtin_amdgcn_readfirstlane(s_prob[gi]);
-    int gk = gi;                                             // the run: tiles gi .. gk, one problem
-    while (gk + 1 < n_my && __builtin_amdgcn_readfirstlane(s_prob[gk + 1]) == pid) ++gk;
-    const tpe_problem& p = P[pid];
+    int tile, gk = gi, ntl, start0;                          // the run: tiles gi .. gk, one problem
+    const void* row;
+    FastDesc dsc{};
+    if constexpr (AK) {
+      dsc = desc[(int)blockIdx.x * per_wg + gi];            // (a scalar load: the address is uniform)
+      if (dsc.n_tiles == 0) break;
+      tile = (int)blockIdx.x * per_wg + gi;
+      ntl = dsc.n_tiles;
+      start0 = dsc.start;
+      row = img + dsc.img_off;
+    } else {
+      tile = __builtin_amdgcn_readfirstlane(s_tile[gi]);
+      const int pid = __builtin_amdgcn_readfirstlane(s_prob[gi]);
+      while (gk + 1 < n_my && __builtin_amdgcn_readfirstlane(s_prob[gk + 1]) == pid) ++gk;
+      ntl = gk - gi + 1;
+      start0 = __builtin_amdgcn_readfirstlane(s_start[gi]);
+      row = &P[pid];
+    }
+    const Row& p = *static_cast<const Row*>(row);
     const bool lat = p.tab_mode == TPE_TAB_LATTICE;         // (run-uniform)
     const int n0 = p.tab_n[0];
     bool staged = false;
     double scum = 0.0;
     float4 srow = make_float4(0.f, 0.f, 0.f, 0.f);
+    const int wv = (int)(threadIdx.x >> 6);
+    if constexpr (AK) {
+      // the prepared image's sampler part, the table rows and a lattice's ranks
+      // (behind its rows and thresholds) by LDS-DMA: every address from the
+      // descriptor, one wait and one barrier before the first candidate
+      if (dsc.img_off != st_samp) {
+        st_samp = dsc.img_off;
+        if (n_def > 0) __syncthreads();                      // LDS free for the next label's rows
+        if ((int)threadIdx.x < kFastSampUnits)
+          __builtin_amdgcn_global_load_lds((const void*)(img + (int64_t)dsc.img_off + kFastHdrUnits + (int)threadIdx.x),
+                                           (__attribute__((address_space(3))) void*)(reinterpret_cast<float4*>(&samp_lds) + 64 * wv),
+                                           16, 0, 0);
+        for (int u = 0; u * kFastThreads < dsc.tab_units; ++u) {
+          const int q = u * kFastThreads + (int)threadIdx.x;
+          if (q < dsc.tab_units)
+            __builtin_amdgcn_global_load_lds((const void*)(tab + (int64_t)dsc.tab_off + q),
+                                             (__attribute__((address_space(3))) void*)(fast_tab + u * kFastThreads + 64 * wv),
+                                             16, 0, 0);
+        }
+        for (int u = 0; u * kFastThreads < dsc.rank_units; ++u) {
+          const int q = u * kFastThreads + (int)threadIdx.x;
+          if (q < dsc.rank_units)
+            __builtin_amdgcn_global_load_lds((const void*)(img + (int64_t)dsc.img_off + kFastHdrUnits + kFastSampUnits + q),
+                                             (__attribute__((address_space(3))) void*)(fast_tab + dsc.tab_units + u * kFastThreads + 64 * wv),
+                                             16, 0, 0);
+        }
+        staged = true;
+      }
+    } else {
     const bool same = p.samp_off == st_samp && p.samp_len == st_len && p.tab_off[0] == st_t0 && n0 == st_n0;
     if (!same) {
       st_samp = p.samp_off; st_len = p.samp_len; st_t0 = p.tab_off[0]; st_n0 = n0;
@@ -1700,15 +1861,13 @@ void k_sample_fast(const tpe_problem* __restrict__ P, const tpe_tile* __restrict
       if ((int)threadIdx.x < p.samp_len) {
         const double* sr = samp + 8 * (int64_t)p.samp_off + 8 * (int)threadIdx.x;
         scum = sr[0];
-        const float sg = (float)sr[2];
-        srow = make_float4((float)sr[1], sr[5] != 0.0 ? -sg : sg, (float)sr[3], (float)sr[4]);
+        srow = fast_samp_row(sr);
       }
       // the table rows (cells: 3 units a row; lattice: one {l, g} unit a value) by
       // LDS-DMA, every round's loads issued before the one wait; the last round's
       // lanes past the rows issue nothing (an LDS-DMA lane writes its slot
       // whatever its address: the dynamic LDS holds exactly the rows)
       const int nu = lat ? n0 + lat_thresh_units(n0) : TPE_TAB_ROW_UNITS * n0;
-      const int wv = (int)(threadIdx.x >> 6);
       for (int u = 0; u * kFastThreads < nu; ++u) {
         const int q = u * kFastThreads + (int)threadIdx.x;
         if (q < nu)
@@ -1718,25 +1877,32 @@ void k_sample_fast(const tpe_problem* __restrict__ P, const tpe_tile* __restrict
       }
       staged = true;
     }
+    }
     if (threadIdx.x == 0) {
       const bool lgf = p.family == TPE_FAM_LOGGAUSS || p.family == TPE_FAM_QLOGGAUSS;
       s_run[n_def] = RunRec{(int64_t)p.cand_base, p.lat_lo, p.below_base, p.above_base, p.q, tile, lgf ? 1 : 0,
                             lat ? 1 : 0, p.tab_off[0]};
     }
-    const int nunits = (gk - gi + 1) * (kTile / kFastUnit);
-    float lo_f, hi_f;
-    f32_bounds(p, lo_f, hi_f);
+    const int nunits = ntl * (kTile / kFastUnit);
+    float lo_f, hi_f, w0, ih0;
     const float lo0 = p.tab_lo[0], inv0 = p.tab_inv[0];
-    const float w0 = 1.f / inv0, ih0 = 1.f / (0.5f * w0);
+    if constexpr (AK) {
+      lo_f = p.lo_f; hi_f = p.hi_f; w0 = p.w0; ih0 = p.ih0;
+    } else {
+      f32_bounds(p, lo_f, hi_f);
+      w0 = 1.f / inv0; ih0 = 1.f / (0.5f * w0);
+    }
     const double2* __restrict__ lrow = reinterpret_cast<const double2*>(fast_tab);
     const float* __restrict__ lthr = reinterpret_cast<const float*>(fast_tab + n0);
     const int* __restrict__ lrank = reinterpret_cast<const int*>(fast_tab + n0 + lat_thresh_units(n0));
-    // a run whose tiles are one candidate range (the packer's order): wave w takes
-    // units w, w + kW, ... with no LDS traffic for the hand-out or the addresses
-    const int start0 = __builtin_amdgcn_readfirstlane(s_start[gi]);
-    const int ntl = gk - gi + 1;
-    const int tl = min(lane, ntl - 1);
-    const bool contig = __ballot(s_start[gi + tl] != start0 + tl * kTile) == 0ull;
+    // a run whose tiles are one candidate range (the packer's order; AK: every
+    // run): wave w takes units w, w + kW, ... with no LDS traffic for the
+    // hand-out or the addresses
+    bool contig = true;
+    if constexpr (!AK) {
+      const int tl = min(lane, ntl - 1);
+      contig = __ballot(s_start[gi + tl] != start0 + tl * kTile) == 0ull;
+    }
     const int wave0 = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     bool first_unit = true;
     for (int k = 0;; ++k) {
@@ -1760,44 +1926,35 @@ void k_sample_fast(const tpe_problem* __restrict__ P, const tpe_tile* __restrict
         // the ten round keys are made from them here, in three scalar registers'
         // reach, instead of being kept in twenty over the whole kernel)
         uint32_t r_key0 = a_key0, r_key1 = a_key1, r_ctr3 = a_ctr3;
-        if (AK) asm volatile("" : "+s"(r_key0), "+s"(r_key1), "+s"(r_ctr3));
+        if constexpr (AK) asm volatile("" : "+s"(r_key0), "+s"(r_key1), "+s"(r_ctr3));
+        else { r_key0 = p.key0; r_key1 = p.key1; r_ctr3 = p.ctr3; }
         if ((g0 & 1) == 0) {
 #pragma unroll
           for (int j = 0; j < NP; j += 2) {
             const uint64_t blk = (g0 + (uint64_t)j) >> 1;
             // (the per-call words: the run's copy of the launch's arguments, else the row's)
-            const U4 r = philox4x32_10((uint32_t)blk, (uint32_t)(blk >> 32), p.ctr2, AK ? r_ctr3 : p.ctr3,
-                                       AK ? r_key0 : p.key0, AK ? r_key1 : p.key1);
+            const U4 r = philox4x32_10((uint32_t)blk, (uint32_t)(blk >> 32), p.ctr2, r_ctr3, r_key0, r_key1);
             ws[j] = r.x; uf[j] = u01f(r.y);
             ws[j + 1] = r.z; uf[j + 1] = u01f(r.w);
           }
         } else {
 #pragma unroll
           for (int j = 0; j < NP; ++j) {
-            const DrawU d = AK ? draw_uniforms(p, first + j, TPE_PREC_F32, r_ctr3, r_key0, r_key1)
-                               : draw_uniforms(p, first + j, TPE_PREC_F32);
+            const DrawU d = draw_uniforms(p, first + j, TPE_PREC_F32, r_ctr3, r_key0, r_key1);
             ws[j] = d.ws; uf[j] = d.uf;
           }
         }
       }
       if (first_unit && staged) {
-        if ((int)threadIdx.x < p.samp_len) { cum_lds[threadIdx.x] = scum; row_lds[threadIdx.x] = srow; }
-        __syncthreads();
-        if (threadIdx.x < kGuide) {                  // first k with cum_k > b / kGuide, its two steps
-          const double v = (double)threadIdx.x / (double)kGuide;
-          const int len = p.samp_len;
-          int a = 0, b = len - 1;
-          while (a < b) { const int m = (a + b) >> 1; if (v < cum_lds[m]) b = m; else a = m + 1; }
-          GuideEnt e;
-          e.k0 = a;
-          e.never = 0u;
-          e.t0 = guide_thresh(a < len - 1 ? cum_lds[a] : INFINITY, e.never, 1u);
-          e.t1 = guide_thresh(a + 1 < len - 1 ? cum_lds[a + 1] : INFINITY, e.never, 2u);
-          guide[threadIdx.x] = e;
+        if constexpr (!AK) {
+          if ((int)threadIdx.x < p.samp_len) { cum_lds[threadIdx.x] = scum; row_lds[threadIdx.x] = srow; }
+          __syncthreads();
+          // first k with cum_k > b / kGuide, its two steps
+          if (threadIdx.x < kGuide) guide[threadIdx.x] = fast_guide_entry(cum_lds, p.samp_len, (int)threadIdx.x);
         }
         __builtin_amdgcn_s_waitcnt(0);               // (the LDS-DMA loads: vmcnt)
         __syncthreads();
-        if (lat) {                                   // the values' score ranks after the rows
+        if (!AK && lat) {                            // the values' score ranks after the rows
           lattice_ranks(lrow, n0, const_cast<int*>(lrank));
           __syncthreads();
         }
@@ -5253,7 +5410,9 @@ int tpe_debug_fast_lg(void* dev, int64_t n_records) {
 // a resident level's fused hit (level_run_impl): the per-call words every
 // problem of the level shares, passed to k_sample_fast as launch arguments
 // (null: the kernel reads each row's own)
-struct FastKey { uint32_t key0, key1, ctr3; };
+// with them the record's prepared images and run descriptors (`runs` descriptors
+// a workgroup: k_sample_fast's per_wg)
+struct FastKey { uint32_t key0, key1, ctr3; const uint4* img; const FastDesc* desc; int runs; };
 static thread_local const FastKey* g_fast_key = nullptr;
 
 extern "C++" {
@@ -5262,15 +5421,17 @@ template <int NP, bool LG, bool AK>
 void launch_fast_k(const tpe_batch* b, int wgs, size_t lds, hipStream_t s, int n_tab, int per, tpe_result* run_best,
                    double* lg, const FastKey& k) {
   TPE_LAUNCH_TIMED((k_sample_fast<NP, LG, AK>), dim3(wgs), dim3(kFastThreads), lds, s, b->problems, b->tiles,
-                   b->tab_tiles, n_tab, per, b->samp, (const float4*)b->comp32, (const float4*)b->tab, run_best,
-                   b->tiles_per_problem, lg, k.key0, k.key1, k.ctr3);
+                   b->tab_tiles, n_tab, AK ? k.runs : per, b->samp, (const float4*)b->comp32, (const float4*)b->tab,
+                   run_best, b->tiles_per_problem, lg, k.key0, k.key1, k.ctr3, k.img, k.desc);
 }
 template <int NP, bool LG>
 void launch_fast(const tpe_batch* b, int wgs, size_t lds, hipStream_t s, int n_tab, int per, tpe_result* run_best,
                  double* lg) {
   const FastKey* fk = g_fast_key;
-  if (fk) launch_fast_k<NP, LG, true>(b, wgs, lds, s, n_tab, per, run_best, lg, *fk);
-  else launch_fast_k<NP, LG, false>(b, wgs, lds, s, n_tab, per, run_best, lg, FastKey{0u, 0u, 0u});
+  if constexpr (!LG) {                                // (the fused hit is never a debug run: level_run_impl)
+    if (fk) { launch_fast_k<NP, false, true>(b, wgs, lds, s, n_tab, per, run_best, lg, *fk); return; }
+  }
+  launch_fast_k<NP, LG, false>(b, wgs, lds, s, n_tab, per, run_best, lg, FastKey{0u, 0u, 0u, nullptr, nullptr, 0});
 }
 }
 
@@ -6131,9 +6292,29 @@ struct ResidentRec {
   std::vector<uint64_t> key;
   tpe_pack_info info;
   std::vector<tpe_problem> hp;         // the host-written problem rows (the hit's early selection and reduction)
+  // what a fused hit needs besides (written by the miss, fast_image_build): the
+  // verdict of fused_hit_ok and its lazy rows, the prepared images (problem r's
+  // at unit r * kFastImgUnits) and the run descriptors, `runs` a workgroup —
+  // library-owned buffers that only grow (desc_host: pinned, the upload's source
+  // and the dense run reduction's list)
+  bool fused_ok = false;
+  std::vector<int32_t> lazy_rows;
+  int dev = -1;
+  uint4* img = nullptr;
+  int64_t img_units = 0;
+  FastDesc *desc_dev = nullptr, *desc_host = nullptr;
+  int64_t desc_cap = 0;
+  int n_desc = 0, runs = 0;
 };
 static thread_local ResidentRec g_res;
 static thread_local std::vector<uint64_t> g_res_key;
+
+// TPE_FAST_IMAGE=0: no prepared images, so no fused hit (A/B, tests); read per
+// call, part of the resident key
+static bool fast_image_on() {
+  const char* e = getenv("TPE_FAST_IMAGE");
+  return !(e && e[0] == '0');
+}
 
 // the level key: everything but the labels' content (their generations stand
 // for it) that the packed level, its tables or the launches depend on
@@ -6143,13 +6324,13 @@ static void resident_key(const tpe_label_in* labels, int32_t n_labels, const uin
   int dev = -1;
   if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = -1; }
   constexpr size_t ws_words = (sizeof(tpe_level_ws) + 7) / 8;
-  key.assign(9 + ws_words + 3 * (size_t)n_labels, 0);
+  key.assign(10 + ws_words + 3 * (size_t)n_labels, 0);
   key[0] = (uint64_t)n_labels; key[1] = (uint64_t)(int64_t)n_cand; key[2] = (uint64_t)cand_base;
   key[3] = (uint64_t)n_cand_global; key[4] = (uint64_t)(int64_t)precision; key[5] = (uint64_t)(int64_t)flags;
   key[6] = (uint64_t)(int64_t)dev; key[7] = (exchange ? 1 : 0) ^ (tpe_internal_pack_switches() << 1);
-  key[8] = (uint64_t)lazy_host_budget();
-  memcpy(key.data() + 9, ws, sizeof(tpe_level_ws));   // every pointer and capacity, pinned_dev included
-  uint64_t* k = key.data() + 9 + ws_words;
+  key[8] = (uint64_t)lazy_host_budget(); key[9] = fast_image_on() ? 1 : 0;
+  memcpy(key.data() + 10, ws, sizeof(tpe_level_ws));   // every pointer and capacity, pinned_dev included
+  uint64_t* k = key.data() + 10 + ws_words;
   for (int32_t i = 0; i < n_labels; ++i) {
     k[3 * i] = (uint64_t)(int64_t)labels[i].label_ix;
     k[3 * i + 1] = gens[i];
@@ -6189,8 +6370,147 @@ static bool fused_hit_ok(const tpe_batch& b, const tpe_pack_info& info, const tp
   }
   return true;
 }
-static thread_local std::vector<int32_t> g_fused_lazy;
 static thread_local std::vector<tpe_result> g_fused_res;
+
+// The run descriptors of a level's sample stage, `*runs` a workgroup (a
+// workgroup's runs first, n_tiles == 0 after them), from the partition
+// k_sample_fast makes itself: workgroup w takes list entries [w per, (w + 1) per),
+// consecutive tiles of one problem that continue one candidate range are a
+// run.  tile_at(i, pid, start): list entry i's problem and first candidate.
+extern "C++" {
+template <class TileAt>
+static void fast_run_descs(int n_tab, int per, const tpe_problem* hp, TileAt tile_at, std::vector<FastDesc>& out,
+                           int* runs) {
+  const int wgs = (n_tab + per - 1) / per;
+  static thread_local std::vector<FastDesc> flat;
+  static thread_local std::vector<int> first;
+  flat.clear();
+  first.assign(wgs + 1, 0);
+  int most = 1;
+  for (int w = 0; w < wgs; ++w) {
+    first[w] = (int)flat.size();
+    for (int i = w * per; i < std::min(n_tab, (w + 1) * per); ++i) {
+      int pid = 0, start = 0;
+      tile_at(i, pid, start);
+      if ((int)flat.size() > first[w] && flat.back().pid == pid && flat.back().start + flat.back().n_tiles * kTile == start) {
+        ++flat.back().n_tiles;
+        continue;
+      }
+      const tpe_problem& q = hp[pid];
+      const bool lat = q.tab_mode == TPE_TAB_LATTICE;
+      const int n0 = q.tab_n[0];
+      flat.push_back(FastDesc{pid, start, 1, pid * kFastImgUnits, q.tab_off[0],
+                              lat ? n0 + lat_thresh_units(n0) : TPE_TAB_ROW_UNITS * n0, lat ? (n0 + 3) / 4 : 0, 0});
+    }
+    most = std::max(most, (int)flat.size() - first[w]);
+  }
+  first[wgs] = (int)flat.size();
+  out.assign((size_t)wgs * most, FastDesc{0, 0, 0, 0, 0, 0, 0, 0});
+  for (int w = 0; w < wgs; ++w) std::copy(flat.begin() + first[w], flat.begin() + first[w + 1], out.begin() + (size_t)w * most);
+  *runs = most;
+}
+}
+static thread_local std::vector<FastDesc> g_fast_descs;
+
+// The miss that makes `rec` live: whether its hits may be fused, and if so the
+// images (k_fast_prep behind the level's stages, on its stream) and the run
+// descriptors.  Any failure leaves the level unfused: its hits take the patch path.
+static void fast_image_build(ResidentRec& rec, const LevelRun& x, const tpe_batch& b) {
+  rec.fused_ok = false;
+  const tpe_pack_info& info = x.info;
+  const int64_t P = x.P;
+  if (!fast_image_on() || !x.hp || !fused_hit_ok(b, info, x.hp, P, rec.lazy_rows)) return;
+  const int n_tab = (int)info.n_tab_tiles, per = tab_tiles_per_wg(n_tab, tab_wgs_per_cu(&b));
+  const int32_t* list = b.tab_tiles ? (const int32_t*)(x.host + info.off_tab_tiles) : nullptr;
+  const tpe_tile* tl = (const tpe_tile*)(x.host + info.off_tiles);
+  const int tpp = b.tiles_per_problem;
+  std::vector<FastDesc>& descs = g_fast_descs;
+  int runs = 0;
+  fast_run_descs(n_tab, per, x.hp, [&](int i, int& pid, int& start) {
+    const int t = list ? list[i] : i;
+    if (tpp > 0) { pid = t / tpp; start = (t - pid * tpp) * kTile; }
+    else { pid = tl[t].problem; start = tl[t].cand_start; }
+  }, descs, &runs);
+  // (what the kernel's LDS-DMA rounds and its run arrays rest on)
+  if (runs > kTabMaxTilesPerWg || (int64_t)descs.size() > info.n_tiles) return;
+  for (const FastDesc& d : descs)
+    if (d.n_tiles && (d.pid < 0 || d.pid >= P || x.hp[d.pid].tab_mode == TPE_TAB_NONE || x.hp[d.pid].samp_len > kFastSamp ||
+                      d.tab_units + d.rank_units > b.tab_fast - 1 || d.rank_units > kFastRankUnits))
+      return;
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return; }
+  auto drop = [&] {
+    if (rec.img) (void)hipFree(rec.img);
+    if (rec.desc_dev) (void)hipFree(rec.desc_dev);
+    if (rec.desc_host) (void)hipHostFree(rec.desc_host);
+    rec.img = nullptr; rec.desc_dev = rec.desc_host = nullptr; rec.img_units = rec.desc_cap = 0;
+    (void)hipGetLastError();
+  };
+  if (dev != rec.dev) { drop(); rec.dev = dev; }
+  const int64_t units = P * (int64_t)kFastImgUnits, nd = (int64_t)descs.size();
+  if (units > rec.img_units) {
+    if (rec.img) (void)hipFree(rec.img);
+    rec.img = nullptr; rec.img_units = 0;
+    // (cleared on the level's stream, ahead of k_fast_prep: the rank slots' tails
+    // and the untabulated rows' images are never written, and tpe_debug_fast_image reads them)
+    if (hipMalloc((void**)&rec.img, (size_t)units * 16) != hipSuccess ||
+        hipMemsetAsync(rec.img, 0, (size_t)units * 16, x.s) != hipSuccess) { drop(); return; }
+    rec.img_units = units;
+  }
+  if (nd > rec.desc_cap) {
+    if (rec.desc_dev) (void)hipFree(rec.desc_dev);
+    if (rec.desc_host) (void)hipHostFree(rec.desc_host);
+    rec.desc_dev = rec.desc_host = nullptr; rec.desc_cap = 0;
+    if (hipMalloc((void**)&rec.desc_dev, (size_t)nd * sizeof(FastDesc)) != hipSuccess ||
+        hipHostMalloc((void**)&rec.desc_host, (size_t)nd * sizeof(FastDesc), hipHostMallocDefault) != hipSuccess) {
+      drop();
+      return;
+    }
+    rec.desc_cap = nd;
+  }
+  memcpy(rec.desc_host, descs.data(), (size_t)nd * sizeof(FastDesc));
+  if (hipMemcpyAsync(rec.desc_dev, rec.desc_host, (size_t)nd * sizeof(FastDesc), hipMemcpyHostToDevice, x.s) != hipSuccess) {
+    (void)hipGetLastError();
+    return;
+  }
+  TPE_LAUNCH(k_fast_prep, dim3((unsigned)P), dim3(kFastThreads), 0, x.s, b.problems, b.samp, (const float4*)b.tab, rec.img);
+  if (hipGetLastError() != hipSuccess) return;
+  rec.n_desc = (int)nd;
+  rec.runs = runs;
+  rec.fused_ok = true;
+}
+
+int tpe_debug_fast_image(int32_t problem, void* out, int64_t bytes) {
+  const ResidentRec& rec = g_res;
+  const int64_t need = (int64_t)kFastImgUnits * 16;
+  if (!out || bytes < need) return fail(TPE_E_ARG, "tpe_debug_fast_image: null or short buffer");
+  if (!(rec.live && rec.epoch == tpe_pool::epoch() && rec.fused_ok && problem >= 0 && problem < (int32_t)rec.hp.size() &&
+        rec.hp[problem].tab_mode != TPE_TAB_NONE))
+    return fail(TPE_E_ARG, "tpe_debug_fast_image: no live image of this problem");
+  const hipError_t e = hipMemcpy(out, rec.img + (int64_t)problem * kFastImgUnits, (size_t)need, hipMemcpyDeviceToHost);
+  epoch_bump();
+  if (e != hipSuccess) return fail(TPE_E_HIP, hipGetErrorString(e));
+  return TPE_OK;
+}
+
+int tpe_debug_fast_runs(int32_t n_problems, int32_t tiles_per_problem, int32_t per, int32_t* out, int64_t cap,
+                        int32_t* runs) {
+  if (n_problems < 1 || tiles_per_problem < 1 || per < 1 || per > kTabMaxTilesPerWg || !out || !runs)
+    return fail(TPE_E_ARG, "tpe_debug_fast_runs: bad arguments");
+  std::vector<tpe_problem> hp((size_t)n_problems);
+  memset(hp.data(), 0, hp.size() * sizeof(tpe_problem));
+  for (int32_t r = 0; r < n_problems; ++r) { hp[r].tab_mode = TPE_TAB_CELLS; hp[r].tab_n[0] = 1; }
+  std::vector<FastDesc> descs;
+  int most = 0;
+  fast_run_descs(n_problems * tiles_per_problem, per, hp.data(), [&](int i, int& pid, int& start) {
+    pid = i / tiles_per_problem;
+    start = (i - pid * tiles_per_problem) * kTile;
+  }, descs, &most);
+  if ((int64_t)descs.size() > cap) return fail(TPE_E_SPACE, "tpe_debug_fast_runs: short buffer");
+  memcpy(out, descs.data(), descs.size() * sizeof(FastDesc));
+  *runs = most;
+  return (int)descs.size();
+}
 
 static int level_run_impl(const tpe_label_in* labels, int32_t n_labels, int32_t n_cand, uint64_t seed,
                           int64_t cand_base, int64_t n_cand_global, int32_t precision, int32_t flags,
@@ -6264,9 +6584,11 @@ static int level_run_impl(const tpe_label_in* labels, int32_t n_labels, int32_t 
     // and uploads the rows afresh).
     // (A run under the stage profiler takes the patch path: the profile's table
     // slot is that kernel's on a hit.)
-    std::vector<int32_t>& lazy_rows = g_fused_lazy;
-    const bool fused = !g_prof.on && one_id && r == P && P > 0 && pt.lazy && fused_hit_ok(b, info, crow, P, lazy_rows);
-    const FastKey fk{k0, k1, id0};
+    // (fused_hit_ok's verdict and the lazy rows are functions of the key: the
+    // record's, made by the miss with the images the kernel starts from)
+    const std::vector<int32_t>& lazy_rows = rec.lazy_rows;
+    const bool fused = !g_prof.on && one_id && r == P && P > 0 && pt.lazy && rec.fused_ok && !g_fast_lg.dev;
+    const FastKey fk{k0, k1, id0, rec.img, rec.desc_dev, rec.runs};
     if (fused) g_fast_key = &fk;
     else g_patch = &pt;
     if (g_prof.on) {
@@ -6318,7 +6640,21 @@ static int level_run_impl(const tpe_label_in* labels, int32_t n_labels, int32_t 
       g_resident_fused[RES_FUSED].fetch_add(1, std::memory_order_relaxed);
       if (fell_back) g_resident_fused[RES_FUSED_FALLBACK].fetch_add(1, std::memory_order_relaxed);
     }
-    if (!(b.early_select && level_reduce_runs(x, b, rh, out))) memcpy(out, rh, (size_t)P * sizeof(tpe_result));
+    if (fused) {
+      // the argument-keyed kernel's records: run r's at index r of the run area
+      const tpe_result* rb = (const tpe_result*)(x.host + x.rb_off);
+      for (int64_t q = 0; q < P; ++q)
+        if (crow[q].tab_mode != TPE_TAB_NONE) rh[q] = tpe_result{0, 0, 0, 0, -1, -1};
+      for (int k = 0; k < rec.n_desc; ++k) {
+        if (rec.desc_host[k].n_tiles == 0) continue;
+        const tpe_result& c = rb[k];
+        tpe_result& w = rh[rec.desc_host[k].pid];
+        if (host_better(c.score, c.idx, w.score, w.idx)) w = c;
+      }
+      memcpy(out, rh, (size_t)P * sizeof(tpe_result));
+    } else if (!(b.early_select && level_reduce_runs(x, b, rh, out))) {
+      memcpy(out, rh, (size_t)P * sizeof(tpe_result));
+    }
     tpe_internal_phase(TPE_PHASE_LEVEL);
     g_resident_stats[RES_HITS].fetch_add(1, std::memory_order_relaxed);
     return g_prof.on ? profile_collect(b, info, x.hp, nullptr, n_cand) : TPE_OK;
@@ -6377,7 +6713,10 @@ static int level_run_impl(const tpe_label_in* labels, int32_t n_labels, int32_t 
                            : hipMemcpyAsync(rh, ws->result, (size_t)P * sizeof(tpe_result), hipMemcpyDeviceToHost, x.s);
     tpe_internal_phase(TPE_PHASE_LAUNCHED);
     // (while the device works: the record's copy of the rows, the caller's key copies)
-    if (keep && e == hipSuccess) rec.hp.assign(x.hp, x.hp + P);
+    if (keep && e == hipSuccess) {
+      rec.hp.assign(x.hp, x.hp + P);
+      fast_image_build(rec, x, b);
+    }
     if (lg && lg->after_launch) lg->after_launch(lg->ctx);
     if (e == hipSuccess) e = hipStreamSynchronize(x.s);
     if (e != hipSuccess) return fail(TPE_E_HIP, hipGetErrorString(e));

@@ -934,6 +934,22 @@ int tpe_level_profile(int32_t enable);
  * the run records are unchanged).  NULL: the production kernel.  Process-wide. */
 int tpe_debug_fast_lg(void* dev, int64_t n_records);
 
+/* Debug (tests): the prepared image of problem row `problem` of the calling
+ * thread's live resident level (the fused hit's: DESIGN.md section 3 "Two hit
+ * paths"), copied to `out`: 616 units of 16 bytes — a 128-byte header, 64 f64
+ * cumulative masses, 64 f32x4 sampler rows, 256 guide entries {t0, t1, k0,
+ * never}, 1024 int32 lattice ranks.  Advances the epoch (the record dies).
+ * TPE_E_ARG: short buffer, or no live fused level / untabulated problem. */
+int tpe_debug_fast_image(int32_t problem, void* out, int64_t bytes);
+
+/* Debug (tests; host only): the fused hit's run descriptors of a level of
+ * n_problems tabulated problems of tiles_per_problem tiles each at `per` tiles a
+ * sample-stage workgroup: 8 int32 a descriptor {problem, first candidate, tiles,
+ * image unit, table unit, table units, rank units, 0}, *runs of them a
+ * workgroup (tiles == 0: unused).  Returns their number (<= cap), or an error. */
+int tpe_debug_fast_runs(int32_t n_problems, int32_t tiles_per_problem, int32_t per, int32_t* out, int64_t cap,
+                        int32_t* runs);
+
 /* the last profiled tpe_level_run: min(n, TPE_N_STAGES) records in stage
  * order; TPE_E_ARG if no run completed since the profiler was enabled */
 int tpe_level_profile_read(tpe_stage_prof* out, int32_t n);
