@@ -251,6 +251,33 @@ class JointSegArgs(ctypes.Structure):
     ]
 
 
+class JointSegF64(ctypes.Structure):
+    """tpe_joint_seg_f64: the device descriptor of one group of a tpe_joint_seg_f64_run (tpe_joint_seg's fields first;
+    its six f32 density-row offsets are not read)."""
+    _fields_ = JointSeg._fields_ + [(side + f + '64', ctypes.c_int64) for side in ('below', 'above')
+                                    for f in ('_mu', '_a', '_c')] + [
+        ('centre', ctypes.c_double * JOINT_MAX_DIMS), ('psi', ctypes.c_int64)]
+
+
+# numpy mirror of tpe_joint_seg_f64
+JOINT_SEG_F64_DTYPE = np.dtype(JOINT_SEG_DTYPE.descr + [(side + f + '64', '<i8') for side in ('below', 'above')
+                                                        for f in ('_mu', '_a', '_c')] + [
+    ('centre', '<f8', (JOINT_MAX_DIMS,)), ('psi', '<i8')])
+assert JOINT_SEG_F64_DTYPE.itemsize == ctypes.sizeof(JointSegF64) == 416
+
+
+class JointSegF64Args(ctypes.Structure):
+    """tpe_joint_seg_f64_args: one tpe_joint_seg_f64_run (tpe_joint_seg_args' fields)."""
+    _fields_ = list(JointSegArgs._fields_)
+
+
+def f64_steps(n_dims):
+    """NI of the float64 stages: the steps of 4 that hold the 2 DP + 1 entries of psi, DP the padded width of a
+    group of ``n_dims`` labels (1, 2, 3, 4, 6, 8, 12, 16)."""
+    dp = next(p for p in (1, 2, 3, 4, 6, 8, 12, 16) if n_dims <= p)
+    return (2 * dp + 1 + 3) // 4
+
+
 class JointWideSeg(ctypes.Structure):
     """tpe_joint_wide_seg: the device descriptor of one group of a tpe_joint_wide_seg_run (tpe_joint_seg with
     JOINT_WIDE_MAX_DIMS bounds)."""
@@ -584,7 +611,8 @@ EXPORTS = ('tpe_abi_version', 'tpe_last_error', 'tpe_device_count', 'tpe_tile_si
            'tpe_joint_wide_f64_scratch_bytes', 'tpe_joint_wide_f64_run', 'tpe_joint_wide_f64_profile',
            'tpe_joint_wide_mixed_scratch_bytes', 'tpe_joint_wide_mixed_run',
            'tpe_joint_wide_quant_scratch_bytes', 'tpe_joint_wide_quant_run', 'tpe_joint_wide_quant_profile',
-           'tpe_joint_seg_scratch_bytes', 'tpe_joint_seg_run', 'tpe_joint_mseg_scratch_bytes',
+           'tpe_joint_seg_scratch_bytes', 'tpe_joint_seg_run', 'tpe_joint_seg_f64_scratch_bytes',
+           'tpe_joint_seg_f64_run', 'tpe_joint_seg_f64_profile', 'tpe_joint_mseg_scratch_bytes',
            'tpe_joint_mseg_table_bytes', 'tpe_joint_mseg_run', 'tpe_joint_wide_seg_scratch_bytes',
            'tpe_joint_wide_seg_run', 'tpe_joint_report_scratch_bytes',
            'tpe_joint_report', 'tpe_joint_report_profile', 'tpe_joint_run_shard', 'tpe_joint_liar_scratch_bytes',
@@ -751,6 +779,12 @@ def load(path=LIB_PATH):
     lib.tpe_joint_seg_scratch_bytes.restype = ctypes.c_int
     lib.tpe_joint_seg_run.argtypes = [ctypes.POINTER(JointSegArgs), P, P, P, P, P, ctypes.c_uint64, P]
     lib.tpe_joint_seg_run.restype = ctypes.c_int
+    lib.tpe_joint_seg_f64_scratch_bytes.argtypes = [P, I32, I32, I32, ctypes.POINTER(ctypes.c_uint64)]
+    lib.tpe_joint_seg_f64_scratch_bytes.restype = ctypes.c_int
+    lib.tpe_joint_seg_f64_run.argtypes = [ctypes.POINTER(JointSegF64Args), P, P, P, P, P, ctypes.c_uint64, P]
+    lib.tpe_joint_seg_f64_run.restype = ctypes.c_int
+    lib.tpe_joint_seg_f64_profile.argtypes = [P]
+    lib.tpe_joint_seg_f64_profile.restype = ctypes.c_int
     lib.tpe_joint_wide_seg_scratch_bytes.argtypes = [I32, I32, ctypes.POINTER(ctypes.c_uint64)]
     lib.tpe_joint_wide_seg_scratch_bytes.restype = ctypes.c_int
     lib.tpe_joint_wide_seg_run.argtypes = [ctypes.POINTER(JointWideSegArgs), P, P, P, P, P, ctypes.c_uint64, P]

@@ -61,7 +61,9 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
 #include <type_traits>
+#include <vector>
 
 #include "../../include/tpe_hip.h"
 #include "tpe_device_rng.h"
@@ -2224,6 +2226,35 @@ __device__ __forceinline__ double exp2_nonpos(double x) {
   return __builtin_amdgcn_ldexp(p, (int)n);
 }
 
+// Entry `inner` of psi_k for component k of a side (mu / a [K][D], c [K]; cs: the
+// centres): a^2 for inner < DP, -2 a^2 mu' up to 2 DP, the constant at 2 DP, and
+// zero in the padding and for the dimensions past D.  `past`: k lies past the
+// side's last component, which gives +inf in the constant entry: a term of -inf.
+// The one place an entry is formed: the solo stage's tile build and
+// k_joint_seg_f64_psi call it.
+__device__ __forceinline__ double psi_entry(const double* mu, const double* a, const double* c, bool past, int D,
+                                            int DP, int k, int inner, const double* cs) {
+  double v = 0.0;
+  if (past) {                              // a term of -inf
+    if (inner == 2 * DP) v = INFINITY;
+  } else if (inner < 2 * DP) {
+    const int d = inner < DP ? inner : inner - DP;
+    if (d < D) {
+      const int64_t src = (int64_t)k * D + d;
+      const double ad = a[src];
+      v = inner < DP ? ad * ad : -2.0 * ad * (ad * (mu[src] - cs[d]));
+    }
+  } else if (inner == 2 * DP) {
+    const int64_t src = (int64_t)k * D;
+    for (int d = 0; d < D; ++d) {
+      const double u = a[src + d] * (mu[src + d] - cs[d]);
+      v = __builtin_fma(u, u, v);
+    }
+    v -= c[k];
+  }
+  return v;
+}
+
 // log2 of one side's mixture at this pass's candidate of every lane (phi: the
 // wave's 4 row blocks in the A layout); the result comes back through `res`.
 template <int DP>
@@ -2243,25 +2274,7 @@ __device__ __forceinline__ double score_side_f64(const double* __restrict__ mu, 
     __syncthreads();                       // the previous tile (or the candidates' staging) is read
     for (int e = t; e < ncb * NI * 64; e += kThreads) {
       const int col = e & 15, inner = 4 * ((e >> 6) % NI) + ((e >> 4) & 3), kk = ((e >> 6) / NI) * 16 + col;
-      double v = 0.0;
-      if (kk >= nk) {                      // past the side's last component: a term of -inf
-        if (inner == 2 * DP) v = INFINITY;
-      } else if (inner < 2 * DP) {
-        const int d = inner < DP ? inner : inner - DP;
-        if (d < D) {
-          const int64_t src = (int64_t)(k0 + kk) * D + d;
-          const double ad = a[src];
-          v = inner < DP ? ad * ad : -2.0 * ad * (ad * (mu[src] - cs[d]));
-        }
-      } else if (inner == 2 * DP) {
-        const int64_t src = (int64_t)(k0 + kk) * D;
-        for (int d = 0; d < D; ++d) {
-          const double u = a[src + d] * (mu[src + d] - cs[d]);
-          v = __builtin_fma(u, u, v);
-        }
-        v -= c[k0 + kk];
-      }
-      tile[e] = v;
+      tile[e] = psi_entry(mu, a, c, kk >= nk, D, DP, k0 + kk, inner, cs);
     }
     __syncthreads();
     for (int cb = 0; cb < ncb; ++cb) {
@@ -2624,6 +2637,230 @@ __global__ __launch_bounds__(kThreads) void k_joint_wide_f64_chunk(const WideF64
   for (int d = 0; d < kWD; ++d) rec->z[d] = d < D ? (double)zs.at[(int64_t)d * zs.step] : 0.0;
 }
 
+// -------------------------------------------------- segmented float64 stage
+// The float64 stage over the (id, group) problems of MANY groups (include/
+// tpe_hip.h "Float64 segmented joint stage").  Every id that takes one branch
+// shares that branch's model, so psi is not rebuilt per workgroup, pass and tile
+// as in k_joint_f64_chunk: k_joint_seg_f64_psi writes every segment's psi once a
+// call into the call's scratch, in the B operand's layout, and the scoring
+// workgroups copy their tiles from there (the order kernel puts the problems of
+// one segment side by side, so the copies hit in L2).  The entries come from
+// psi_entry and the tiles end where the solo stage's do, so a lane's sequence
+// of (max, sum) updates, and with it every output byte, is the solo stage's.
+struct SegF64K {
+  int C, n_chunks, inject, first;   // as SegK
+  int n_probs, n_segs;
+  uint32_t key0, key1;
+  const tpe_joint_seg_f64* segs;
+  const float* pool;
+  const double* pool64;
+  const int32_t* prob_seg;
+  const int64_t* prob_id;
+  const int64_t* cand_off;
+  int32_t* order;
+  float* cand;
+  double *l_out, *g_out;
+  tpe_joint_record* chunk_rec;
+  double* psi;                      // scratch: the f64 area that tpe_joint_seg_f64.psi counts in
+};
+template <bool MIXED>
+__device__ __forceinline__ int seg_class(const SegF64K& p, int s) { return dp_class(p.segs[s].n_dims); }
+// the padded width of a group of D dimensions (for_dp's list)
+__host__ __device__ __forceinline__ int dp_width(int D) { return D <= 4 ? D : D <= 6 ? 6 : D <= 8 ? 8 : D <= 12 ? 12 : 16; }
+
+// One workgroup per (column block of 16 components, segment): blockIdx.x counts
+// the below side's blocks, then the above side's; a segment with fewer blocks
+// than the grid is wide leaves the rest idle.
+__global__ __launch_bounds__(kThreads) void k_joint_seg_f64_psi(const SegF64K p) {
+  __shared__ double cs[TPE_JOINT_MAX_DIMS];
+  const tpe_joint_seg_f64* __restrict__ sg = p.segs + blockIdx.y;
+  const int t = threadIdx.x, D = uni(sg->n_dims), kb = uni(sg->k_below), ka = uni(sg->k_above);
+  const int nbb = (kb + 15) >> 4, nba = (ka + 15) >> 4;
+  if ((int)blockIdx.x >= nbb + nba) return;
+  if (t < TPE_JOINT_MAX_DIMS) cs[t] = t < D ? sg->centre[t] : 0.0;
+  __syncthreads();
+  const bool below = (int)blockIdx.x < nbb;
+  const int cb = below ? (int)blockIdx.x : (int)blockIdx.x - nbb, K = below ? kb : ka;
+  const double* __restrict__ mu = p.pool64 + uni(below ? sg->below_mu64 : sg->above_mu64);
+  const double* __restrict__ a = p.pool64 + uni(below ? sg->below_a64 : sg->above_a64);
+  const double* __restrict__ c = p.pool64 + uni(below ? sg->below_c64 : sg->above_c64);
+  const int DP = dp_width(D), NI = f64_steps(DP);
+  double* __restrict__ out = p.psi + uni(sg->psi) + (int64_t)blockIdx.x * NI * 64;
+  for (int e = t; e < NI * 64; e += kThreads) {
+    const int k = cb * 16 + (e & 15);
+    out[e] = psi_entry(mu, a, c, k >= K, D, DP, k, 4 * (e >> 6) + ((e >> 4) & 3), cs);
+  }
+}
+
+// score_side_f64 with every tile copied from the side's psi (kTileK components a
+// tile: the solo stage's boundaries), 16 bytes a lane and step
+template <int DP>
+__device__ __forceinline__ double score_side_seg_f64(const double* __restrict__ psi, int K,
+                                                     const double (&phi)[4][f64_steps(DP)], double* __restrict__ tile,
+                                                     double* __restrict__ res) {
+  constexpr int NI = f64_steps(DP);
+  const int t = threadIdx.x, lane = t & 63;
+  double m[4][4], s[4][4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+#pragma unroll
+    for (int v = 0; v < 4; ++v) { m[q][v] = kF64Lowest; s[q][v] = 0.0; }   // (any finite first term exceeds it)
+  for (int k0 = 0; k0 < K; k0 += kTileK) {
+    const int nk = min(kTileK, K - k0), ncb = (nk + 15) >> 4;
+    __syncthreads();                       // the previous tile (or the candidates' staging) is read
+    {
+      const double2* __restrict__ src = reinterpret_cast<const double2*>(psi + (int64_t)(k0 >> 4) * NI * 64);
+      double2* __restrict__ dst = reinterpret_cast<double2*>(tile);
+      for (int e = t; e < ncb * NI * 32; e += kThreads) dst[e] = src[e];
+    }
+    __syncthreads();
+    for (int cb = 0; cb < ncb; ++cb) {
+      const double* bt = tile + cb * NI * 64 + lane;
+      double b[NI];
+#pragma unroll
+      for (int i = 0; i < NI; ++i) b[i] = bt[i * 64];
+      F64x4 acc[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc[q] = F64x4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int i = 0; i < NI; ++i)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(phi[q][i], b[i], acc[q], 0, 0, 0);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        bool live = false;                 // (a NaN term is live, and stays in the sum)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) live |= !(-acc[q][v] <= m[q][v] - kF64Skip);
+        if (__builtin_amdgcn_ballot_w64(live) == 0) continue;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          const double term = -acc[q][v], dl = term - m[q][v];
+          const double e2 = exp2_nonpos(-__builtin_fabs(dl));
+          s[q][v] = dl > 0.0 ? __builtin_fma(s[q][v], e2, 1.0) : s[q][v] + e2;
+          m[q][v] = fmax(m[q][v], term);
+        }
+      }
+    }
+  }
+  // a row's 16 column lanes (lane & 15) hold its partial pairs
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+#pragma unroll
+      for (int mask = 1; mask < 16; mask <<= 1) {
+        const double mo = __shfl_xor(m[q][v], mask, 64), so = __shfl_xor(s[q][v], mask, 64);
+        const double top = fmax(m[q][v], mo);
+        s[q][v] = s[q][v] * exp2_nonpos(m[q][v] - top) + so * exp2_nonpos(mo - top);
+        m[q][v] = top;
+      }
+      if ((lane & 15) == 0) res[(t & ~63) + 16 * q + 4 * v + (lane >> 4)] = m[q][v] + log2(s[q][v]);
+    }
+  __syncthreads();
+  return res[t];
+}
+
+// one workgroup per (problem of the launch's DP class, chunk), in k_joint_seg_order's order
+template <int DP>
+__global__ __launch_bounds__(kThreads) void k_joint_seg_f64_chunk(const SegF64K p) {
+  constexpr int NI = f64_steps(DP);
+  __shared__ __attribute__((aligned(16))) double tile[(kTileK / 16) * NI * 64];
+  __shared__ double res[kThreads];
+  __shared__ double cs[DP];
+  __shared__ Pick slot[kThreads / 64];
+  static_assert(sizeof(float) * kThreads * DP <= sizeof tile, "a pass's candidates are staged in the tile");
+  float* zbuf = reinterpret_cast<float*>(tile);
+  const int t = threadIdx.x, lane = t & 63, chunk = blockIdx.x % p.n_chunks, first = chunk * TPE_JOINT_CHUNK;
+  // the problem and its group: the same for every lane, kept in scalar registers
+  const int prob = uni(p.order[p.first + blockIdx.x / p.n_chunks]);
+  const tpe_joint_seg_f64* __restrict__ sg = p.segs + uni(p.prob_seg[prob]);
+
+  ChunkIO q;
+  q.D = uni(sg->n_dims); q.C = p.C; q.inject = p.inject;
+  q.kb = uni(sg->k_below); q.ka = uni(sg->k_above);
+  q.key0 = p.key0; q.key1 = p.key1; q.stream_word = (uint32_t)uni((int)sg->stream_word);
+  q.c3 = (uint32_t)uni((int)(uint32_t)p.prob_id[prob]);
+  q.base = 0u;
+  q.bmu = q.ba = q.bc = q.amu = q.aa = q.ac = nullptr;   // (the f32 density rows: this stage has none)
+  q.bbase = unid(sg->below_base); q.abase = unid(sg->above_base);
+  q.cum = p.inject ? nullptr : p.pool64 + uni(sg->samp_cum);
+  q.samp = p.inject ? nullptr : p.pool + uni(sg->samp);
+  q.inj = p.inject ? p.pool + uni(sg->inject) : nullptr;
+  q.cand = p.cand ? p.cand + uni(p.cand_off[prob]) : nullptr;
+  q.l_out = p.l_out ? p.l_out + (int64_t)prob * p.C : nullptr;
+  q.g_out = p.g_out ? p.g_out + (int64_t)prob * p.C : nullptr;
+  q.rec = p.chunk_rec + (int64_t)prob * p.n_chunks + chunk;
+  const int D = q.D;
+  float blo[DP], bhi[DP];
+#pragma unroll
+  for (int d = 0; d < DP; ++d) { blo[d] = unif(sg->lo[d]); bhi[d] = unif(sg->hi[d]); }
+  if (t < DP) cs[t] = t < q.D ? sg->centre[t] : 0.0;   // (read after the candidates' barrier; vector loads: no SGPRs)
+  // the below side's column blocks, then the above side's
+  const double* __restrict__ bpsi = p.psi + uni(sg->psi);
+  const double* __restrict__ apsi = bpsi + (int64_t)((q.kb + 15) >> 4) * NI * 64;
+  // from here on k_joint_f64_chunk's passes and finish
+  Pick best{0, 0};
+  double bl = 0.0, bg = 0.0;
+  float bz[DP];
+#pragma unroll
+  for (int d = 0; d < DP; ++d) bz[d] = 0.f;
+#pragma unroll 1
+  for (int r = 0; r < kR; ++r) {
+    const int i = first + r * kThreads + t;
+    float z[DP];
+    load_candidate<DP>(q, blo, bhi, i, z);
+    __syncthreads();                       // the previous pass's last tile is read
+#pragma unroll
+    for (int d = 0; d < DP; ++d) zbuf[t * DP + d] = z[d];
+    __syncthreads();
+    double phi[4][NI];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const float* zr = zbuf + ((t & ~63) + 16 * b + (lane & 15)) * DP;
+#pragma unroll
+      for (int s = 0; s < NI; ++s) {
+        const int e = 4 * s + (lane >> 4), d = min(e < DP ? e : e - DP, DP - 1);
+        const double zp = (double)zr[d] - cs[d];
+        phi[b][s] = e < DP ? zp * zp : e < 2 * DP ? zp : e == 2 * DP ? 1.0 : 0.0;
+      }
+    }
+    const double l2 = score_side_seg_f64<DP>(bpsi, q.kb, phi, tile, res);
+    const double g2 = score_side_seg_f64<DP>(apsi, q.ka, phi, tile, res);
+    const double lv = l2 * kLn2 + q.bbase, gv = g2 * kLn2 + q.abase;
+    if (i >= q.C) continue;
+    if (q.l_out) q.l_out[i] = lv;
+    if (q.g_out) q.g_out[i] = gv;
+    if (q.cand)
+#pragma unroll
+      for (int d = 0; d < DP; ++d)
+        if (d < D) q.cand[(int64_t)i * D + d] = z[d];
+    const uint64_t key = score_key(lv - gv);
+    if (key > best.key) {                  // ascending index: strict > keeps the first of a tie
+      best = Pick{key, (int64_t)i};
+      bl = lv; bg = gv;
+#pragma unroll
+      for (int d = 0; d < DP; ++d) bz[d] = z[d];
+    }
+  }
+  Pick w = wave_best(best);
+  if (lane == 0) slot[t >> 6] = w;
+  __syncthreads();
+  w = slot[0];
+#pragma unroll
+  for (int k = 1; k < kThreads / 64; ++k)
+    if (beats(slot[k], w)) w = slot[k];
+  if (w.key == 0) {
+    if (t == 0) q.rec->global_idx = -1;
+    return;
+  }
+  if (best.key != w.key || best.idx != w.idx) return;
+  q.rec->global_idx = w.idx + (int64_t)q.base;
+  q.rec->l = bl;
+  q.rec->g = bg;
+#pragma unroll
+  for (int d = 0; d < TPE_JOINT_MAX_DIMS; ++d) q.rec->z[d] = d < DP ? (double)bz[d < DP ? d : 0] : 0.0;
+}
+
 // ------------------------------------------------------------- host driver
 // Everything from here on runs on the host: the stages' argument checks,
 // the kernel-argument fills and the launches.  What the stages share exists
@@ -2782,6 +3019,20 @@ uint64_t joint_scratch_need(int32_t n_ids, int32_t n_cand) {
 uint64_t seg_order_bytes(int32_t n_probs) { return ((uint64_t)n_probs * sizeof(int32_t) + 7) & ~(uint64_t)7; }
 uint64_t seg_scratch_need(int32_t n_probs, int32_t n_cand) {
   return seg_order_bytes(n_probs) + joint_scratch_need(n_probs, n_cand);
+}
+// the float64 segmented stage: the above up to a multiple of 16 bytes, then every segment's psi
+uint64_t seg_f64_psi_off(int32_t n_probs, int32_t n_cand) { return (seg_scratch_need(n_probs, n_cand) + 15) & ~(uint64_t)15; }
+uint64_t seg_f64_psi_doubles(const tpe_joint_seg_f64& g) {   // (counts in range: check_segment)
+  const uint64_t cbs = (uint64_t)((g.k_below + 15) / 16) + (uint64_t)((g.k_above + 15) / 16);
+  return cbs * (uint64_t)f64_steps(dp_width(g.n_dims)) * 64;
+}
+bool seg_f64_counts_ok(const tpe_joint_seg_f64& g) {
+  return g.n_dims >= 1 && g.n_dims <= TPE_JOINT_MAX_DIMS && g.k_below >= 1 && g.k_above >= 1;
+}
+uint64_t seg_f64_scratch_need(const tpe_joint_seg_f64* host_segs, int32_t n_segs, int32_t n_probs, int32_t n_cand) {
+  uint64_t n = 0;
+  for (int s = 0; s < n_segs; ++s) n += seg_f64_counts_ok(host_segs[s]) ? seg_f64_psi_doubles(host_segs[s]) : 0;
+  return seg_f64_psi_off(n_probs, n_cand) + n * sizeof(double);
 }
 uint64_t quant_table_floats(int64_t k_below, int64_t k_above, int64_t total) {
   return ((uint64_t)k_below + (uint64_t)k_above) * (uint64_t)total;
@@ -3436,11 +3687,15 @@ int joint_quant_run_at(const tpe_joint_quant_args* a, tpe_joint_record* records,
 
 // ---- the segmented stages: one skeleton (joint_seg_run_at); a stage supplies its
 // per-segment check, its class function and its class launcher as overloads on
-// its descriptor, tpe_joint_seg or tpe_joint_mseg
+// its descriptor, tpe_joint_seg, tpe_joint_wide_seg, tpe_joint_mseg or tpe_joint_seg_f64
 static_assert(offsetof(tpe_joint_mseg, hi) == offsetof(tpe_joint_seg, hi) &&
                   offsetof(tpe_joint_mseg, n_cat) == sizeof(tpe_joint_seg),
               "tpe_joint_mseg starts with tpe_joint_seg");
 static_assert(offsetof(tpe_joint_mseg_args, cand_off) == offsetof(tpe_joint_seg_args, cand_off), "the shared fields");
+static_assert(offsetof(tpe_joint_seg_f64, hi) == offsetof(tpe_joint_seg, hi) &&
+                  offsetof(tpe_joint_seg_f64, below_mu64) == sizeof(tpe_joint_seg) &&
+                  sizeof(tpe_joint_seg_f64_args) == sizeof(tpe_joint_seg_args),
+              "tpe_joint_seg_f64 starts with tpe_joint_seg; the args are tpe_joint_seg_args'");
 
 // rows [off, off + n) inside a pool of len elements
 bool inside(int64_t off, int64_t n, int64_t len) { return off >= 0 && n <= len && off <= len - n; }
@@ -3456,6 +3711,7 @@ struct SegPlan {
 constexpr int n_classes_of(const tpe_joint_seg*) { return 8; }
 constexpr int n_classes_of(const tpe_joint_mseg*) { return kMClasses; }
 constexpr int n_classes_of(const tpe_joint_wide_seg*) { return 5; }
+constexpr int n_classes_of(const tpe_joint_seg_f64*) { return 8; }
 
 // a continuous segment, narrow or wide: its counts and its rows' places
 template <typename A, typename Seg>
@@ -3476,6 +3732,38 @@ int check_segment(const char* entry, const tpe_joint_seg_args* a, const tpe_join
 int check_segment(const char* entry, const tpe_joint_wide_seg_args* a, const tpe_joint_wide_seg& g, bool inject,
                   SegPlan&) {
   return check_cont_segment(entry, a, g, inject, TPE_JOINT_WIDE_MAX_DIMS, "n_dims outside [1, TPE_JOINT_WIDE_MAX_DIMS]");
+}
+// the float64 stage: its density rows lie in pool_f64; the psi ranges are checked after the scratch size
+int check_segment(const char* entry, const tpe_joint_seg_f64_args* a, const tpe_joint_seg_f64& g, bool inject,
+                  SegPlan& plan) {
+  if (g.n_dims < 1 || g.n_dims > TPE_JOINT_MAX_DIMS) return fail(entry, "n_dims outside [1, TPE_JOINT_MAX_DIMS]", kSegs);
+  if (g.k_below < 1 || g.k_above < 1) return fail(entry, "k_below < 1 or k_above < 1", kSegs);
+  const int64_t D = g.n_dims, kb = g.k_below, ka = g.k_above, L = a->pool_f32_len, L64 = a->pool_f64_len;
+  bool ok = inside(g.below_mu64, kb * D, L64) && inside(g.below_a64, kb * D, L64) && inside(g.below_c64, kb, L64) &&
+            inside(g.above_mu64, ka * D, L64) && inside(g.above_a64, ka * D, L64) && inside(g.above_c64, ka, L64);
+  if (!inject) ok = ok && inside(g.samp, kb * D * 5, L) && inside(g.samp_cum, kb, L64);
+  if (inject && g.inject >= 0) ok = ok && inside(g.inject, (int64_t)a->n_cand * D, L);
+  if (!ok) return fail(entry, "rows leave its pool", kSegs);
+  for (int d = 0; d < g.n_dims; ++d)
+    if (!isfinite(g.centre[d])) return fail(entry, "centre not finite", kSegs);
+  const int blocks = (int)((kb + 15) / 16 + (ka + 15) / 16);   // the psi launch's width: the widest segment
+  if (blocks > plan.max_kblocks) plan.max_kblocks = blocks;
+  return TPE_OK;
+}
+// every psi range inside the f64 area of `doubles` elements, and no two of them overlapping
+int check_psi_ranges(const char* entry, const tpe_joint_seg_f64* g, int n_segs, uint64_t doubles) {
+  std::vector<int> by(n_segs);
+  for (int s = 0; s < n_segs; ++s) {
+    const uint64_t n = seg_f64_psi_doubles(g[s]);
+    if (g[s].psi < 0 || n > doubles || (uint64_t)g[s].psi > doubles - n)
+      return fail(entry, "psi range leaves scratch", kSegs);
+    by[s] = s;
+  }
+  std::sort(by.begin(), by.end(), [&](int x, int y) { return g[x].psi < g[y].psi; });
+  for (int i = 1; i < n_segs; ++i)         // (ranges are not empty: by start, each must end before the next)
+    if (g[by[i - 1]].psi + (int64_t)seg_f64_psi_doubles(g[by[i - 1]]) > g[by[i]].psi)
+      return fail(entry, "psi range overlaps another segment's", kSegs);
+  return TPE_OK;
 }
 
 int check_segment(const char* entry, const tpe_joint_mseg_args* a, const tpe_joint_mseg& g, bool inject, SegPlan& plan) {
@@ -3530,6 +3818,7 @@ int check_segment(const char* entry, const tpe_joint_mseg_args* a, const tpe_joi
 // the kernel class of a segment that has a problem
 int segment_class(const tpe_joint_seg& g, SegPlan&) { return dp_class(g.n_dims); }
 int segment_class(const tpe_joint_wide_seg& g, SegPlan&) { return wide_class(g.n_dims); }
+int segment_class(const tpe_joint_seg_f64& g, SegPlan&) { return dp_class(g.n_dims); }
 int segment_class(const tpe_joint_mseg& g, SegPlan& plan) {
   const int c = mseg_class(g.n_dims, g.n_cat, g.n_quant);
   if (g.n_quant > 0) {                     // the segment's own tile (the solo run's rule); the launch takes the largest
@@ -3577,15 +3866,26 @@ void launch_class(const tpe_joint_wide_seg*, int c, const WideSegK& k, unsigned 
     launch(k_joint_wide_seg_chunk<DP, wide_r(DP)>, dim3(blocks), kThreads, 0u, s, ev.start, ev.stop, k);
   });
 }
+void launch_class(const tpe_joint_seg_f64*, int c, const SegF64K& k, unsigned blocks, unsigned, hipStream_t s, Ev ev) {
+  for_dp(c, [&](auto dp) {
+    launch(k_joint_seg_f64_chunk<decltype(dp)::value>, dim3(blocks), kThreads, 0u, s, ev.start, ev.stop, k);
+  });
+}
 
 // the merge kernel of a stage's record
 auto merge_of(const tpe_joint_record*) { return &k_joint_merge; }
 auto merge_of(const tpe_joint_wide_record*) { return &k_joint_wide_merge; }
 
 // the stages' kernel arguments: SegK (inside MSegK, whose table the mixed stage
-// adds) or WideSegK, which names the shared fields alike
+// adds), or WideSegK / SegF64K, which name the shared fields alike
 SegK& seg_view(MSegK& mk) { return mk.s; }
 WideSegK& seg_view(WideSegK& k) { return k; }
+SegF64K& seg_view(SegF64K& k) { return k; }
+template <typename Seg>
+using SegKernelArgs = std::conditional_t<std::is_same<Seg, tpe_joint_wide_seg>::value, WideSegK,
+                                         std::conditional_t<std::is_same<Seg, tpe_joint_seg_f64>::value, SegF64K, MSegK>>;
+// the launch of the float64 stage's psi kernel among a profiled run's launches (-1: none)
+int g_psi_mark = -1;
 
 template <typename A, typename Rec>
 int joint_seg_run_at(const char* E, const A* a, Rec* records, float* cand, double* l_out, double* g_out,
@@ -3593,6 +3893,7 @@ int joint_seg_run_at(const char* E, const A* a, Rec* records, float* cand, doubl
   using Seg = std::remove_cv_t<std::remove_pointer_t<decltype(A::host_segs)>>;
   constexpr bool MIXED = std::is_same<Seg, tpe_joint_mseg>::value;
   constexpr bool WIDE = std::is_same<Seg, tpe_joint_wide_seg>::value;
+  constexpr bool F64 = std::is_same<Seg, tpe_joint_seg_f64>::value;
   static_assert(std::is_same<Rec, std::conditional_t<WIDE, tpe_joint_wide_record, tpe_joint_record>>::value,
                 "the stage's record");
   constexpr int n_classes = n_classes_of((const Seg*)nullptr);
@@ -3600,10 +3901,12 @@ int joint_seg_run_at(const char* E, const A* a, Rec* records, float* cand, doubl
   if (!a) return fail(E, "null args");
   if (a->n_segs < 1) return fail(E, "n_segs < 1");
   if (MIXED && a->n_segs > 32767) return fail(E, "more than 32767 segments");
+  if (F64 && a->n_segs > 65535) return fail(E, "more than 65535 segments");   // (the psi launch's grid)
   if (a->n_probs < 1) return fail(E, "n_probs < 1");
   if (a->n_cand < 1) return fail(E, "n_cand < 1");
   if (!a->segs || !a->host_segs) return fail(E, "null segs / host_segs");
   const bool inject = (a->flags & TPE_JOINT_INJECT) != 0;
+  if (F64 && !a->pool_f64) return fail(E, "null pool_f64");   // (under inject too: the density rows live there)
   if (!a->pool_f32 || (!inject && !a->pool_f64)) return fail(E, "null pool");
   if (!a->prob_seg || !a->host_prob_seg || !a->prob_id) return fail(E, "null prob_seg / host_prob_seg / prob_id");
   if (!records) return fail(E, "null records");
@@ -3620,14 +3923,20 @@ int joint_seg_run_at(const char* E, const A* a, Rec* records, float* cand, doubl
   // the chunk records a problem: the wide stage's count at R = 1, its sampler's grid a problem too
   const int64_t n_chunks = WIDE ? wide_blocks_of(a->n_cand) : n_chunks_of(a->n_cand);
   if ((int64_t)a->n_segs * n_classes > INT32_MAX) return fail(E, "too many candidates");
-  const uint64_t need = WIDE ? wide_seg_scratch_need(a->n_probs, a->n_cand) : seg_scratch_need(a->n_probs, a->n_cand);
+  uint64_t need = WIDE ? wide_seg_scratch_need(a->n_probs, a->n_cand) : seg_scratch_need(a->n_probs, a->n_cand);
+  if constexpr (F64) need = seg_f64_scratch_need(a->host_segs, a->n_segs, a->n_probs, a->n_cand);
   if (int rc = check_scratch(E, n_chunks * a->n_probs, need, scratch, scratch_bytes)) return rc;
+  if constexpr (F64) {
+    const uint64_t doubles = (scratch_bytes - seg_f64_psi_off(a->n_probs, a->n_cand)) / sizeof(double);
+    if (int rc = check_psi_ranges(E, a->host_segs, a->n_segs, doubles)) return rc;
+  }
 
-  std::conditional_t<WIDE, WideSegK, MSegK> mk;   // (the continuous stage's kernels take mk.s alone)
+  SegKernelArgs<Seg> mk;                    // (the continuous stage's kernels take mk.s alone)
   auto& k = seg_view(mk);
   k.C = a->n_cand; k.n_chunks = (int)n_chunks; k.inject = inject ? 1 : 0; k.first = 0;
   k.n_probs = a->n_probs; k.n_segs = a->n_segs;
-  k.key0 = (uint32_t)a->seed; k.key1 = (uint32_t)(a->seed >> 32); k.cand_base = cand_base;
+  k.key0 = (uint32_t)a->seed; k.key1 = (uint32_t)(a->seed >> 32);
+  if constexpr (!F64) k.cand_base = cand_base;   // (the float64 stage is not sharded: its base is 0)
   k.segs = reinterpret_cast<decltype(k.segs)>(a->segs); k.pool = a->pool_f32; k.pool64 = a->pool_f64;
   k.prob_seg = a->prob_seg; k.prob_id = a->prob_id; k.cand_off = a->cand_off;
   k.order = (int32_t*)scratch;
@@ -3636,6 +3945,8 @@ int joint_seg_run_at(const char* E, const A* a, Rec* records, float* cand, doubl
   if constexpr (WIDE) {
     k.nblk = (int)n_chunks;
     k.zbuf = (float*)((char*)k.chunk_rec + wide_seg_record_bytes(a->n_probs, a->n_cand));
+  } else if constexpr (F64) {
+    k.psi = (double*)((char*)scratch + seg_f64_psi_off(a->n_probs, a->n_cand));
   } else {
     mk.table = nullptr;
   }
@@ -3645,6 +3956,7 @@ int joint_seg_run_at(const char* E, const A* a, Rec* records, float* cand, doubl
   if (timed)
     if (int rc = ensure_events(g_sprof.ev, 2 * kSegLaunches)) return rc;
   int n_timed = 0;
+  g_psi_mark = -1;
   Ev ev = seg_marks(timed, n_timed);
   launch(k_joint_seg_order<MIXED, std::remove_reference_t<decltype(k)>>,
          dim3((unsigned)((a->n_probs + kThreads - 1) / kThreads)), kThreads, 0u, s, ev.start, ev.stop, k);
@@ -3655,6 +3967,12 @@ int joint_seg_run_at(const char* E, const A* a, Rec* records, float* cand, doubl
       launch(k_joint_mseg_qtable, dim3((unsigned)plan.max_kblocks, (unsigned)TPE_JOINT_MAX_QUANT, (unsigned)(2 * a->n_segs)),
              kThreads, 0u, s, ev.start, ev.stop, mk);
     }
+  }
+  if constexpr (F64) {                      // psi of every segment, once a call (the table launch's slot)
+    if (timed) g_psi_mark = n_timed;
+    ev = seg_marks(timed, n_timed);
+    launch(k_joint_seg_f64_psi, dim3((unsigned)plan.max_kblocks, (unsigned)a->n_segs), kThreads, 0u, s, ev.start,
+           ev.stop, k);
   }
   if constexpr (WIDE) {                     // the sampler's time is tpe_joint_wide_profile's, as in the solo wide stage
     g_wprof.valid = 0;
@@ -3808,6 +4126,25 @@ int tpe_joint_wide_f64_profile(double* psi_ms) {
 int tpe_joint_seg_run(const tpe_joint_seg_args* a, tpe_joint_record* records, float* cand, double* l_out,
                       double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
   return joint_seg_run_at("tpe_joint_seg_run", a, records, cand, l_out, g_out, scratch, scratch_bytes, stream, 0u);
+}
+
+int tpe_joint_seg_f64_scratch_bytes(const tpe_joint_seg_f64* host_segs, int32_t n_segs, int32_t n_probs,
+                                    int32_t n_cand, uint64_t* bytes) {
+  bool ok = host_segs && n_segs >= 1 && n_probs >= 1 && n_cand >= 1;
+  for (int s = 0; ok && s < n_segs; ++s) ok = seg_f64_counts_ok(host_segs[s]);
+  return size_out("tpe_joint_seg_f64_scratch_bytes", ok,
+                  ok ? seg_f64_scratch_need(host_segs, n_segs, n_probs, n_cand) : 0, bytes);
+}
+
+int tpe_joint_seg_f64_run(const tpe_joint_seg_f64_args* a, tpe_joint_record* records, float* cand, double* l_out,
+                          double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
+  return joint_seg_run_at("tpe_joint_seg_f64_run", a, records, cand, l_out, g_out, scratch, scratch_bytes, stream, 0u);
+}
+
+int tpe_joint_seg_f64_profile(double* psi_ms) {
+  if (!psi_ms || g_prof.valid != 2 || g_psi_mark < 0 || g_psi_mark >= g_sprof.n)
+    return fail("tpe_joint_seg_f64_profile", "no profiled tpe_joint_seg_f64_run to read");
+  return elapsed_ms(g_sprof.ev[2 * g_psi_mark], g_sprof.ev[2 * g_psi_mark + 1], psi_ms);
 }
 
 int tpe_joint_mseg_run(const tpe_joint_mseg_args* a, tpe_joint_record* records, float* cand, double* l_out,

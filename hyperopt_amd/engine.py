@@ -1486,7 +1486,7 @@ class Engine(object):
                 d_stats[:P * 8].cpu().numpy().view(N.SCORE_STATS_DTYPE).copy())
 
     def run_joint_segments(self, models, stream_words, prob_seg, prob_id, n_cand, seed, inject=None,
-                           return_cand=False, want_lg=False, report_k=0, shard=None):
+                           return_cand=False, want_lg=False, report_k=0, shard=None, precision='fp32'):
         """One segmented joint stage (tpe_joint_seg_run, include/tpe_hip.h
         "Segmented joint stage"): problem p scores new id ``prob_id[p]`` under
         group ``prob_seg[p]``.  ``models``: per group a joint.JointModel or a
@@ -1510,7 +1510,26 @@ class Engine(object):
         still one upload, one call and one download, and problem p's results
         are those of the solo run of its group's kind; D_group counts the
         continuous, discrete and quantised coordinates, in that order.  With
-        continuous groups only nothing changes: tpe_joint_seg_run, the same blob."""
+        continuous groups only nothing changes: tpe_joint_seg_run, the same blob.
+
+        ``precision`` 'fp64' (DESIGN.md "Float64 branch groups"):
+        tpe_joint_seg_f64_run scores the 'fp32' call's candidates, bit for bit,
+        in float64 from the unrounded rows; psi of a group is built once a call
+        and shared by all its problems.  Problem p's results are byte for byte
+        those of ``run_joint(precision='fp64')`` over its group with that stream
+        word and ids = [prob_id[p]].  Still one upload, one call and one
+        download.  ``report_k`` > 0, ``shard`` and a group with discrete or
+        quantised dimensions raise ValueError."""
+        if self._joint_fp64(precision, report_k, shard, False, None, False):
+            for m in models:
+                if JP.seg_parts(m)[4] or JP.seg_parts(m)[5]:
+                    raise ValueError("joint stage: precision='fp64' does not combine with a group that has discrete or "
+                                     'quantised dimensions: the mixed segmented stage is an fp32 stage')
+            C = int(n_cand)
+            b = JP.segment_blob(models, stream_words, prob_seg, prob_id, C, inject, N.JOINT_SEG_F64_DTYPE)
+            a = self._joint_seg_args(N.JointSegF64Args, b, len(models), C, seed, inject)
+            return self._joint_seg_call('tpe_joint_seg_f64', a, len(b.prob_seg), C, b.cand_off, b.widths, return_cand,
+                                        want_lg, 0, host_segs=b.segs)
         # the choice of stage: continuous groups only keep tpe_joint_seg_run and its smaller descriptors
         mixed = any(JP.seg_parts(m)[4] or JP.seg_parts(m)[5] for m in models)
         C = int(n_cand)
@@ -1566,12 +1585,16 @@ class Engine(object):
         return a
 
     def _joint_seg_call(self, fn, a, P, C, cand_off, pd, return_cand, want_lg, report_k, shard=None,
-                        rec_dtype=N.JOINT_RECORD_DTYPE):
+                        rec_dtype=N.JOINT_RECORD_DTYPE, host_segs=None):
         """What the segmented stages share: scratch and the result block, the
-        native call ``fn``_run, the report, and one transfer of the results."""
+        native call ``fn``_run, the report, and one transfer of the results.
+        ``host_segs``: the descriptors, for a stage whose scratch depends on
+        them (the float64 one: its psi)."""
         dev_cand, dev_lg = return_cand or report_k > 0, want_lg or report_k > 0
         nb = ctypes.c_uint64(0)
-        N.check(getattr(self.lib, fn + '_scratch_bytes')(P, C, ctypes.byref(nb)), self.lib, fn + '_scratch_bytes')
+        sized = () if host_segs is None else (host_segs.ctypes.data, len(host_segs))
+        N.check(getattr(self.lib, fn + '_scratch_bytes')(*(sized + (P, C, ctypes.byref(nb)))), self.lib,
+                fn + '_scratch_bytes')
         d_scr = self._buf('joint_scratch', (nb.value + 7) // 8, torch.float64)
         # one result block of 8-byte words: records, l, g, then the candidates (f32 pairs)
         rec_w = P * rec_dtype.itemsize // 8

@@ -18,6 +18,7 @@ The dimension limits by entry point (``_check_dims``):
   'segment'  run_joint_segments    a continuous group 1 <= Dc <= JOINT_MAX_DIMS; one with discrete or
                                    quantised parts Dc <= JOINT_MSEG_MAX_CONT, Dk <= JOINT_MSEG_MAX_CAT
   'wide_segment' run_joint_wide_segments  1 <= Dc <= JOINT_WIDE_MAX_DIMS, continuous only
+  (run_joint_segments(precision='fp64') packs every group by 'f64')
 and Dq <= JOINT_MAX_QUANT everywhere.
 """
 import collections
@@ -221,7 +222,11 @@ def segment_blob(models, stream_words, prob_seg, prob_id, n_cand, inject, seg_dt
     """The upload of a segmented stage (Engine.run_joint_segments' arguments):
     per group its descriptor (``seg_dtype``: N.JOINT_SEG_DTYPE, continuous
     groups only, N.JOINT_WIDE_SEG_DTYPE, continuous groups of up to
-    JOINT_WIDE_MAX_DIMS labels, or N.JOINT_MSEG_DTYPE) and its group_rows in the two pools,
+    JOINT_WIDE_MAX_DIMS labels, N.JOINT_MSEG_DTYPE, or N.JOINT_SEG_F64_DTYPE, the
+    float64 stage: a group's rows are group_rows(entry='f64'), its float64
+    density rows in pool_f64 under the descriptor's *64 fields, and the
+    descriptor also carries the centres and where the group's psi starts in
+    the stage's scratch, the ranges laid end to end) and its group_rows in the two pools,
     in the order of ROWS with the group's inject rows last; a continuous group
     is the case Dk = Dq = 0.  The descriptors carry the f32 bounds
     (joint.f32_bounds), padded with -+inf.  ``empty_ok``: n_cand = 0 is allowed
@@ -242,8 +247,8 @@ def segment_blob(models, stream_words, prob_seg, prob_id, n_cand, inject, seg_dt
         return SegmentBlob(None, None, None, prob_seg, None, widths, 0, 0, 0)
     if inject is not None and len(inject) != S:
         raise ValueError('joint stage: inject must hold one entry per group')
-    mixed = 'n_cat' in seg_dtype.names
-    entry = 'wide_segment' if seg_dtype['lo'].shape == (N.JOINT_WIDE_MAX_DIMS,) else 'segment'
+    mixed, f64 = 'n_cat' in seg_dtype.names, 'psi' in seg_dtype.names
+    entry = 'f64' if f64 else 'wide_segment' if seg_dtype['lo'].shape == (N.JOINT_WIDE_MAX_DIMS,) else 'segment'
     segs = np.zeros(S, dtype=seg_dtype)
     pools = {4: [], 8: []}
     fill = {4: 0, 8: 0}
@@ -255,7 +260,7 @@ def segment_blob(models, stream_words, prob_seg, prob_id, n_cand, inject, seg_dt
         fill[size] += arr.size
         return fill[size] - arr.size
     dims = np.empty(S, dtype=np.int64)
-    n_table = 0
+    n_table = n_psi = 0
     for s, group in enumerate(groups):
         r = group_rows(*group, entry=entry)
         Dc, Dk, Dq = r['Dc'], r['Dk'], r['Dq']
@@ -264,10 +269,13 @@ def segment_blob(models, stream_words, prob_seg, prob_id, n_cand, inject, seg_dt
         g['n_dims'], g['k_below'], g['k_above'] = Dc, r['k_below'], r['k_above']
         g['stream_word'] = int(stream_words[s])
         g['below_base'], g['above_base'] = r['below_base'], r['above_base']
-        for key, field, _, dtype, _ in group_rows_present(r):
-            g[field] = put(r[key], dtype)
+        for key, field, buf, dtype, _ in group_rows_present(r):
+            g[field + '64' if buf.endswith('64') else field] = put(r[key], dtype)
         g['lo'], g['hi'] = np.float32(-np.inf), np.float32(np.inf)
         g['lo'][:Dc], g['hi'][:Dc] = J.f32_bounds(r['low'], r['high'])
+        if f64:                                      # psi: both sides' column blocks of 16 components, NI * 64 doubles each
+            g['centre'][:Dc], g['psi'] = r['centre'], n_psi
+            n_psi += ((r['k_below'] + 15) // 16 + (r['k_above'] + 15) // 16) * N.f64_steps(Dc) * 64
         if mixed:
             g['n_cat'], g['n_quant'] = Dk, Dq
             g['qlo'], g['qhi'] = np.float32(-np.inf), np.float32(np.inf)

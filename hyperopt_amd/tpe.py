@@ -847,8 +847,8 @@ def suggest(new_ids, domain, trials, seed,
             sampler='philox', precision='fp32', device=None, shard=None, shard_ids=None, shard_labels=None,
             shard_grid=None, joint=False, joint_discrete=False, joint_quantized=False, joint_wide=False,
             joint_branches=False, joint_branches_mixed=False, joint_branches_wide=False, joint_shard=None,
-            joint_precision='fp32', joint_precision_wide=False, joint_wide_mixed=False, joint_wide_quantized=False,
-            joint_liar=False):
+            joint_precision='fp32', joint_precision_wide=False, joint_precision_branches=False,
+            joint_wide_mixed=False, joint_wide_quantized=False, joint_liar=False):
     new_ids = list(new_ids)
     if not new_ids:
         return []
@@ -858,7 +858,7 @@ def suggest(new_ids, domain, trials, seed,
     if liar_mode:
         _joint_liar_check(joint, joint_shard, mode=liar_mode, joint_branches=joint_branches)
     fp64 = _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, None, joint_precision_wide,
-                                  joint_wide)
+                                  joint_wide, joint_precision_branches, joint_branches)
     if ((joint is not False and joint is not None) or joint_discrete or joint_quantized or joint_wide or joint_branches
             or joint_branches_mixed or joint_branches_wide or joint_wide_mixed or joint_wide_quantized):
         # (argument errors first: no device use, no startup draw)
@@ -872,7 +872,7 @@ def suggest(new_ids, domain, trials, seed,
             _wide_quant_liar_check(plan[0], liar_mode)
         if fp64:
             _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, plan, joint_precision_wide,
-                                   joint_wide)
+                                   joint_wide, joint_precision_branches, joint_branches)
     t0 = time.time()
     hist = _history.extract(domain, trials)
     if logger.isEnabledFor(logging.INFO):
@@ -892,7 +892,8 @@ def suggest(new_ids, domain, trials, seed,
                               joint_branches_wide=joint_branches_wide, joint_shard=joint_shard,
                               joint_wide_mixed=joint_wide_mixed,
                               joint_wide_quantized=joint_wide_quantized, joint_liar=joint_liar,
-                              joint_precision=joint_precision, joint_precision_wide=joint_precision_wide)
+                              joint_precision=joint_precision, joint_precision_wide=joint_precision_wide,
+                              joint_precision_branches=joint_precision_branches)
     logger.info('tpe.suggest took %f seconds', time.time() - t0)
     return rand.docs_from_choices(new_ids, domain, trials, choices)
 
@@ -935,7 +936,8 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
                     shard_ids=None, shard_labels=None, shard_grid=None, joint=False, joint_discrete=False,
                     joint_quantized=False, joint_wide=False, joint_branches=False, joint_branches_mixed=False,
                     joint_branches_wide=False, joint_shard=None, joint_precision='fp32', joint_precision_wide=False,
-                    joint_wide_mixed=False, joint_wide_quantized=False, joint_liar=False):
+                    joint_precision_branches=False, joint_wide_mixed=False, joint_wide_quantized=False,
+                    joint_liar=False):
     """The suggest core on a structure-of-arrays history (``history.History``):
     per new id a {label: value or None} dict.  ``suggest`` wraps it with the
     Trials document layout; columnar callers (and bench.py's large configs)
@@ -1127,8 +1129,9 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
     the winner is the float64 arg-max over the same pool; every other label is
     the same bytes as without the keyword.  The default 'fp32' is the path
     above byte for byte.  Without ``joint``, with a root group that holds a
-    discrete or quantised label or more than 16 labels, with any branch group,
-    with ``joint_shard`` or ``joint_liar``, and for any other value it raises
+    discrete or quantised label or more than 16 labels, with any branch group
+    (unless ``joint_precision_branches``, below), with ``joint_shard`` or
+    ``joint_liar``, and for any other value it raises
     ValueError; joint_candidate_report does not take it.  (``precision='fp64'``,
     the univariate parity mode, still does not combine with ``joint``.)
 
@@ -1140,7 +1143,23 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
     the same bytes.  Without either of the two keywords, with a discrete or
     quantised label in the group, more than 64 labels, any branch group,
     ``joint_shard`` or ``joint_liar`` it raises ValueError;
-    joint_candidate_report does not take it."""
+    joint_candidate_report does not take it.
+
+    ``joint_precision_branches=True`` (with ``joint_precision='fp64'`` and
+    ``joint_branches=True``): every branch group of 2 to 16 continuous labels
+    is scored in float64 too (DESIGN.md "Float64 branch groups"): all (id,
+    group) problems of the suggest go through one
+    Engine.run_joint_segments(precision='fp64') call, over the fp32 segmented
+    stage's pool bit for bit (the same stream words), so a branch group's pick
+    is the float64 arg-max over the pool the call without the keyword sees.  A
+    root group, if there is one, goes where ``joint_precision='fp64'`` sends it
+    (the wide float64 stage with ``joint_precision_wide``); none is needed.
+    Gates, univariate labels and every label outside a group keep the bytes of
+    the call without ``joint_precision``.  Without either of the two keywords,
+    with a branch group that holds a discrete or quantised label
+    (``joint_branches_mixed``) or more than 16 labels
+    (``joint_branches_wide``), with ``joint_shard`` or ``joint_liar`` it raises
+    ValueError; joint_candidate_report does not take it."""
     if sampler not in ('philox', 'replay'):
         raise ValueError("sampler must be 'philox' or 'replay'")
     if joint_shard is not None:
@@ -1149,7 +1168,7 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
     if liar_mode:
         _joint_liar_check(joint, joint_shard, mode=liar_mode, joint_branches=joint_branches)
     fp64 = _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, None, joint_precision_wide,
-                                  joint_wide)
+                                  joint_wide, joint_precision_branches, joint_branches)
     group, branch_groups = None, []
     if ((joint is not False and joint is not None) or joint_discrete or joint_quantized or joint_wide or joint_branches
             or joint_branches_mixed or joint_branches_wide or joint_wide_mixed or joint_wide_quantized):
@@ -1165,7 +1184,7 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
             _wide_quant_liar_check(group, liar_mode)
         if fp64:
             _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, (group, branch_groups),
-                                   joint_precision_wide, joint_wide)
+                                   joint_precision_wide, joint_wide, joint_precision_branches, joint_branches)
     if sum(a is not None for a in (shard, shard_ids, shard_labels, shard_grid)) > 1:
         raise ValueError('shard, shard_ids, shard_labels and shard_grid are exclusive: one shard axis per suggest')
     if (shard_ids is not None or shard_labels is not None or shard_grid is not None) and sampler == 'replay':
@@ -1177,7 +1196,7 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
                                 columns, shard_ids, shard_labels, shard_grid)
     if group is not None or branch_groups:
         return _suggest_joint(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, device, columns, group,
-                              branch_groups, joint_shard, liar_mode or False, fp64)
+                              branch_groups, joint_shard, liar_mode or False, fp64)   # (fp64: every group it holds)
     return _suggest_local(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, sampler, precision,
                           device, shard, columns)
 
@@ -1200,7 +1219,8 @@ def _joint_liar_mode(joint_liar):
                      'joint_branches (or False): %r' % (joint_liar,))
 
 
-def _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, plan=None, wide_f64=False, joint_wide=False):
+def _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, plan=None, wide_f64=False, joint_wide=False,
+                           branches_f64=False, joint_branches=False):
     """Whether ``joint_precision`` asks for the float64 stage; ValueError for a
     value other than 'fp32' / 'fp64' and where 'fp64' does not apply: without
     ``joint``, with ``joint_shard`` or ``joint_liar``, and (``plan`` =
@@ -1208,9 +1228,16 @@ def _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, plan=
     discrete or quantised label or more than TPE_JOINT_MAX_DIMS labels
     (``wide_f64``, the joint_precision_wide keyword: TPE_JOINT_WIDE_MAX_DIMS),
     and for any branch group; for ``wide_f64`` without 'fp64' or without
-    ``joint_wide``.  Touches no device."""
+    ``joint_wide``.  ``branches_f64`` (the joint_precision_branches keyword)
+    lets continuous branch groups of at most TPE_JOINT_MAX_DIMS labels through,
+    with or without a root group; without 'fp64' or ``joint_branches``, and for
+    a branch group with a discrete or quantised label or more labels, it
+    raises.  Touches no device."""
     if joint_precision not in ('fp32', 'fp64'):
         raise ValueError("joint_precision must be 'fp32' or 'fp64': %r" % (joint_precision,))
+    if branches_f64 and joint_precision != 'fp64':
+        raise ValueError("joint_precision_branches=True needs joint_precision='fp64': it only names the branch groups "
+                         'that keyword scores in float64; without it the segmented joint stage scores in fp32')
     if wide_f64 and joint_precision != 'fp64':
         raise ValueError("joint_precision_wide=True needs joint_precision='fp64': it only widens the groups that "
                          'keyword scores in float64')
@@ -1222,6 +1249,9 @@ def _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, plan=
     if joint is False or joint is None:
         raise ValueError("joint_precision='fp64' needs joint=True or joint=[labels]: it only changes how the joint "
                          'stage scores')
+    if branches_f64 and not joint_branches:
+        raise ValueError('joint_precision_branches=True needs joint_branches=True: it only scores the branch groups '
+                         'that keyword makes in float64')
     if joint_shard is not None:
         raise ValueError("joint_precision='fp64' does not combine with joint_shard: the sharded joint stage scores in "
                          'fp32 only')
@@ -1231,9 +1261,21 @@ def _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, plan=
     if plan is None:
         return True
     group, branch_groups = plan
-    if branch_groups:
+    if branch_groups and not branches_f64:
         raise ValueError("joint_precision='fp64' does not combine with branch groups (joint_branches): the segmented "
                          'joint stage scores in fp32 only')
+    for rows in branch_groups:
+        other = [r.label for r in rows if r.dist not in _joint.JOINT_DISTS]
+        if other:
+            raise ValueError('joint_precision_branches=True needs branch groups of continuous labels only: %r is '
+                             'discrete or quantised (joint_branches_mixed), and the mixed segmented joint stage scores '
+                             'in fp32 only' % other[0])
+        if len(rows) > TPE_JOINT_MAX_DIMS:
+            raise ValueError('joint_precision_branches=True takes branch groups of at most %d labels, not %d '
+                             '(joint_branches_wide): the wide segmented joint stage scores in fp32 only'
+                             % (TPE_JOINT_MAX_DIMS, len(rows)))
+    if group is None and branch_groups:
+        return True
     if group is None:
         raise ValueError("joint_precision='fp64' needs a root group: there is none")
     other = [r.label for r in group if r.dist not in _joint.JOINT_DISTS]
@@ -1859,7 +1901,9 @@ def _suggest_joint(table, hist, new_ids, seed, prior_weight, n_EI_candidates, ga
     greedily (Engine.run_joint's ``liar``); 'branches' / 'branches_mixed': so do
     the ids of every branch group (Engine.run_joint_segments_liar /
     run_joint_msegments_liar).  ``fp64`` (joint_precision='fp64'): the root
-    group's stage is Engine.run_joint(precision='fp64')."""
+    group's stage is Engine.run_joint(precision='fp64'), and the branch groups'
+    (there are some only with joint_precision_branches)
+    Engine.run_joint_segments(precision='fp64')."""
     cc = _suggest_local(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, 'philox', 'fp32', device,
                         None, True)
     if len(cc) == 0:
@@ -1893,7 +1937,7 @@ def _suggest_joint(table, hist, new_ids, seed, prior_weight, n_EI_candidates, ga
     if branch_groups:
         _suggest_branches(engine, hist, ids, seed, prior_weight, n_EI_candidates, gamma, branch_groups,
                           np.asarray(cc.active, dtype=bool), values, parts,
-                          joint_liar if joint_liar in ('branches', 'branches_mixed') else False)
+                          joint_liar if joint_liar in ('branches', 'branches_mixed') else False, fp64)
     cc = ChoiceColumns(table.labels, values, active)
     return cc if columns else cc.dicts(table)
 
@@ -1912,7 +1956,7 @@ def _fit_branch_model(rows, hist, below_tids, prior_weight):
 
 
 def _suggest_branches(engine, hist, ids, seed, prior_weight, n_EI_candidates, gamma, branch_groups, taken, values,
-                      parts=None, liar=False):
+                      parts=None, liar=False, fp64=False):
     """The segmented joint stage of a suggest: one problem per (new id, branch
     group whose labels are active for it in ``taken`` [n_ids x n_labels]), all
     in one Engine.run_joint_segments call; the winners overwrite ``values``.
@@ -1922,7 +1966,9 @@ def _suggest_branches(engine, hist, ids, seed, prior_weight, n_EI_candidates, ga
     (Engine.run_joint_segments_liar, W of every group's above side as
     side_mixture weighs it); 'branches_mixed': the same over groups that may
     hold discrete or quantised labels (Engine.run_joint_msegments_liar, with
-    each model's centres())."""
+    each model's centres()).  ``fp64`` (joint_precision_branches): the one call
+    is Engine.run_joint_segments(precision='fp64'), over the same stream words
+    and so the same candidates."""
     below_tids = _history.split_below(hist, gamma)
     models, words, prob_seg, prob_id, where = [], [], [], [], []
     for rows in branch_groups:
@@ -1950,6 +1996,8 @@ def _suggest_branches(engine, hist, ids, seed, prior_weight, n_EI_candidates, ga
                 centres=[m.centres() if hasattr(m, 'centres') else None for m in models])
         else:
             rec = engine.run_joint_segments_liar(models, words, prob_seg, prob_id, int(n_EI_candidates), seed, liar=W)
+    elif fp64:
+        rec = engine.run_joint_segments(models, words, prob_seg, prob_id, int(n_EI_candidates), seed, precision='fp64')
     elif parts is None and not any(_is_wide_branch(w[0]) for w in where):
         rec = engine.run_joint_segments(models, words, prob_seg, prob_id, int(n_EI_candidates), seed)
     elif parts is None:

@@ -1804,6 +1804,98 @@ int tpe_joint_seg_run(const tpe_joint_seg_args* args, tpe_joint_record* records,
                       double* g_out, void* scratch, uint64_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Float64 segmented joint stage (tpe_joint.hip; additive to ABI 24): the
+ * segmented stage above with the scoring of the float64 joint stage (DESIGN.md
+ * "Float64 branch groups").  A segment's rows are those of tpe_joint_f64_args:
+ *   pool_f64   every group's f64 mu / a / c rows of both sides (the *64 fields
+ *              are their ELEMENT offsets) and its samp_cum[k_below]
+ *   pool_f32   every group's sampler rows samp[k_below * n_dims * 5] and, under
+ *              TPE_JOINT_INJECT, its candidates
+ *   centre     as tpe_joint_f64_args.centre (entries from n_dims on: ignored)
+ * tpe_joint_seg_f64 starts with the fields of tpe_joint_seg at the same offsets;
+ * its six f32 row offsets are not read.
+ *
+ * psi lives in `scratch` and is built ONCE per segment and call: the ELEMENT
+ * offset `psi` says where the segment's range starts in the f64 area behind the
+ * order and the chunk records (that area starts at tpe_joint_seg_scratch_bytes
+ * filled up to a multiple of 16 bytes).  A range holds the below side's
+ * ceil(k_below / 16) column blocks of 16 components, then the above side's, each
+ * block NI * 64 doubles in the B operand's layout [(cb NI + s) 64 + lane] of
+ * v_mfma_f64_16x16x4_f64, NI = ceil((2 DP + 1) / 4), DP the padded width of
+ * n_dims (1, 2, 3, 4, 6, 8, 12, 16); entries: a^2, -2 a^2 mu', sum_d a^2 mu'^2 -
+ * c_k with mu' = mu - centre; components past a side's end carry +inf in the
+ * constant entry, dimensions past n_dims and the last step's padding zeros.
+ * Ranges must not overlap; tpe_joint_seg_f64_scratch_bytes sizes the ranges of
+ * all segments laid end to end in descriptor order.
+ *
+ * Defining property: the record, the cand rows, l_out and g_out of problem p =
+ * (prob_id[p], segment prob_seg[p]) are byte for byte those of a
+ * tpe_joint_f64_run over that segment's rows and centres with its stream_word,
+ * ids = [prob_id[p]] and the same seed, n_cand and flags; the candidates are
+ * those of tpe_joint_seg_run.  The order of the problems does not matter.
+ * Launches, all on `stream` with no sync between them: k_joint_seg_order,
+ * k_joint_seg_f64_psi (one workgroup per segment, side and column block; an
+ * entry is formed by the device function the solo stage's tile build calls), one
+ * k_joint_seg_f64_chunk<DP> launch per DP class present (one 256-thread
+ * workgroup per problem and chunk of TPE_JOINT_CHUNK candidates, in the order
+ * kernel's order, so consecutive workgroups read one segment's psi; a tile of at
+ * most 128 components is copied from psi into LDS, nothing is recomputed, and
+ * the passes, the vote, the exponentials, the combine and the finish are the
+ * solo stage's), k_joint_merge.  Plain vector stores, no atomics: the same call
+ * twice gives the same bytes.
+ *
+ * tpe_joint_seg_f64_run returns TPE_E_ARG before any launch (no device needed)
+ * for everything tpe_joint_seg_run checks (rows: the f64 ones in pool_f64), a
+ * null pool_f64 (also under TPE_JOINT_INJECT: the density rows live there), a
+ * centre that is not finite, more than 65535 segments, scratch smaller than
+ * tpe_joint_seg_f64_scratch_bytes says, and a psi range that leaves scratch or
+ * overlaps another segment's.  tpe_joint_profile covers this stage as it covers
+ * tpe_joint_seg_run; tpe_joint_seg_f64_profile reads the psi kernel's time of
+ * the last profiled run.
+ * ---------------------------------------------------------------------- */
+typedef struct tpe_joint_seg_f64 {
+  int32_t n_dims, k_below, k_above;       /* as tpe_joint_seg ... */
+  uint32_t stream_word;
+  double below_base, above_base;
+  int64_t below_mu, below_a, below_c;     /* (the f32 density rows: not read) */
+  int64_t above_mu, above_a, above_c;
+  int64_t samp;
+  int64_t inject;
+  int64_t samp_cum;
+  float lo[TPE_JOINT_MAX_DIMS], hi[TPE_JOINT_MAX_DIMS];   /* ... up to here */
+  int64_t below_mu64, below_a64, below_c64;   /* element offsets in pool_f64 */
+  int64_t above_mu64, above_a64, above_c64;
+  double centre[TPE_JOINT_MAX_DIMS];
+  int64_t psi;                            /* element offset in the f64 area of scratch */
+} tpe_joint_seg_f64;
+typedef struct tpe_joint_seg_f64_args {
+  int32_t n_segs, n_probs, n_cand, flags;   /* as tpe_joint_seg_args */
+  uint64_t seed;
+  const tpe_joint_seg_f64* segs;
+  const tpe_joint_seg_f64* host_segs;
+  const float* pool_f32;
+  const double* pool_f64;
+  int64_t pool_f32_len, pool_f64_len;
+  const int32_t* prob_seg;
+  const int32_t* host_prob_seg;
+  const int64_t* prob_id;
+  const int64_t* cand_off;
+} tpe_joint_seg_f64_args;
+
+/* tpe_joint_seg_scratch_bytes(n_probs, n_cand) filled up to a multiple of 16
+ * bytes, then per host descriptor (ceil(k_below / 16) + ceil(k_above / 16)) * NI
+ * * 512 bytes of psi */
+int tpe_joint_seg_f64_scratch_bytes(const tpe_joint_seg_f64* host_segs, int32_t n_segs, int32_t n_probs,
+                                    int32_t n_cand, uint64_t* bytes);
+
+/* records, cand, l_out, g_out, scratch and stream as tpe_joint_seg_run */
+int tpe_joint_seg_f64_run(const tpe_joint_seg_f64_args* args, tpe_joint_record* records, float* cand, double* l_out,
+                          double* g_out, void* scratch, uint64_t scratch_bytes, void* stream);
+
+/* the psi kernel's device time of the last profiled tpe_joint_seg_f64_run */
+int tpe_joint_seg_f64_profile(double* psi_ms);
+
+/* ------------------------------------------------------------------------
  * Wide segmented joint stage (tpe_joint.hip; additive to ABI 24): the segmented
  * stage for continuous groups of up to TPE_JOINT_WIDE_MAX_DIMS labels (DESIGN.md
  * "Wide branch groups").  tpe_joint_wide_seg is tpe_joint_seg with 64 f32 bounds

@@ -1,5 +1,5 @@
 """Time the segmented joint stage against one tpe_joint_run per branch group.
-Usage: python tools/joint_branch_time.py [--pairs 7] [--warmup 2] [--out FILE] [--small] [--wide]
+Usage: python tools/joint_branch_time.py [--pairs 7] [--warmup 2] [--out FILE] [--small] [--wide | --fp64]
 
 Two workloads (DESIGN.md "Branch groups"), each with two routes to the same
 winners, alternating in one process, each timed from a synchronised device to
@@ -36,7 +36,21 @@ branch groups"), appended to profiles/joint_branch_wide_time.jsonl:
       k_joint_wide_seg_chunk<32, 2> against k_joint_wide_chunk<32, 2>.
 Here the chunk figure holds the scoring launches (with the order kernel for the
 segmented route) and the sampling kernels are reported beside it
-(tpe_joint_wide_profile)."""
+(tpe_joint_wide_profile).
+
+--fp64: the float64 segmented stage (DESIGN.md "Float64 branch groups"),
+appended to profiles/joint_branch_fp64_time.jsonl.  Workloads (a) and (b) above
+and (c), as (b) at D = 16; three routes alternating in one process:
+  seg64      one Engine.run_joint_segments(precision='fp64') call
+  group64    one Engine.run_joint(precision='fp64', stream_word=...) per group
+  seg32      one Engine.run_joint_segments call
+Wall clock from a synchronised device, then the kernels by their own events
+(tpe_joint_profile; the psi kernel: tpe_joint_seg_f64_profile).  seg64's records
+must be group64's bytes.  A difference of two medians is `shown` only if it
+exceeds three times the larger of the two ranges.  Each
+line also holds the worst distance of seg32's l and g from seg64's over the
+shared pool, as a fraction of 1e-5 max(1, |ref|); a last line does that for a
+clustered branch (every bandwidth psig / 100)."""
 import argparse
 import ctypes
 import json
@@ -82,6 +96,18 @@ def make_wide_group(D, n, seed):
     priors = [(0.0, 10.0) if e else (0.0, 2.0) for e in even]
     low, high = np.where(even, -5.0, -np.inf), np.where(even, 5.0, np.inf)
     return J.side_mixture(X[m], priors), J.side_mixture(X[~m], priors), low, high
+
+
+def make_clustered_group(n, seed):
+    """make_group's space with every trial within 1e-3 prior sigmas of one point."""
+    from hyperopt_amd import joint as J
+    rs = np.random.RandomState(seed)
+    priors = [(0.0, 10.0), (-0.5, 5.0), (0.0, 2.0), (0.5, 1.0)]
+    X = np.array([m + 0.03 * sg for m, sg in priors])[None, :] + 1e-3 * np.array([sg for _, sg in priors])[None, :] \
+        * rs.uniform(0, 1, (n, 4))
+    nb = min(int(np.ceil(0.25 * np.sqrt(n))), 25)
+    low, high = np.array([-5.0, -3.0, -np.inf, 0.0]), np.array([5.0, 2.0, np.inf, 1.0])
+    return J.side_mixture(X[:nb], priors), J.side_mixture(X[nb:], priors), low, high
 
 
 def stats(x):
@@ -199,6 +225,94 @@ def measure(name, eng, models, words, prob_seg, prob_id, C, args):
         f.write(text + '\n')
 
 
+def shown(x, y):
+    """Whether the medians of x and y differ by more than three times the larger range."""
+    return bool(abs(np.median(x) - np.median(y)) > 3 * max(np.ptp(x), np.ptp(y)))
+
+
+def measure_fp64(name, eng, models, words, prob_seg, prob_id, C, args, time_it=True):
+    import torch
+    from hyperopt_amd import _native as N
+    lib = eng.lib
+    prob_seg, prob_id = np.asarray(prob_seg), np.asarray(prob_id, dtype=np.int64)
+    groups = [(s, prob_id[prob_seg == s]) for s in range(len(models))]
+
+    def seg(precision, **kw):
+        return eng.run_joint_segments(models, words, prob_seg, prob_id, C, SEED, precision=precision, **kw)
+
+    def group64():
+        return [eng.run_joint(*models[s], ids, C, SEED, stream_word=words[s], precision='fp64') for s, ids in groups]
+    routes = dict(seg64=lambda: seg('fp64'), group64=group64, seg32=lambda: seg('fp32'))
+
+    def events(route):
+        """{launches before the merge, merge, psi kernel} of one profiled run of the route, in ms."""
+        ms2, psi, tot = (ctypes.c_double * 2)(), ctypes.c_double(0.0), [0.0, 0.0, 0.0]
+        torch.cuda.synchronize()
+        N.check(lib.tpe_joint_profile(1, None), lib, 'tpe_joint_profile')
+        for s, ids in (groups if route == 'group64' else [(None, None)]):   # (the per-group route: read after every call)
+            if route == 'group64':
+                eng.run_joint(*models[s], ids, C, SEED, stream_word=words[s], precision='fp64')
+            else:
+                routes[route]()
+            if route == 'seg64':
+                N.check(lib.tpe_joint_seg_f64_profile(ctypes.byref(psi)), lib, 'tpe_joint_seg_f64_profile')
+            N.check(lib.tpe_joint_profile(1, ms2), lib, 'tpe_joint_profile')
+            tot = [tot[0] + ms2[0], tot[1] + ms2[1], psi.value]
+        N.check(lib.tpe_joint_profile(0, None), lib, 'tpe_joint_profile')
+        return tot
+
+    line = dict(tool='joint_branch_time --fp64', workload=name, n_groups=len(models), n_problems=int(len(prob_seg)),
+                n_dims=len(models[0][2]), n_cand=C, k_below=[len(m[0][0]) for m in models],
+                k_above=[len(m[1][0]) for m in models], pairs=args.pairs, warmup=args.warmup)
+    # the fp32 stage's distance from the float64 stage over the shared pool, in units of the fp32 tolerance
+    r64, r32 = seg('fp64', return_cand=True, want_lg=True), seg('fp32', return_cand=True, want_lg=True)
+    assert all(x.tobytes() == y.tobytes() for x, y in zip(r64[1], r32[1])), 'the pools differ'
+    line['fp32_distance'] = dict((k, float(np.max(np.abs(r32[i] - r64[i]) / (1e-5 * np.maximum(1.0, np.abs(r64[i]))))))
+                                 for k, i in (('l', 2), ('g', 3)))
+    line['same_winners'] = bool((r64[0]['global_idx'] == r32[0]['global_idx']).all())
+    if time_it:
+        for _ in range(args.warmup):
+            for fn in routes.values():
+                fn()
+        rec, ref = routes['seg64'](), routes['group64']()
+        for s, ids in groups:
+            assert rec[prob_seg == s].tobytes() == ref[s].tobytes(), 'group %d: records differ' % s
+        wall, kern = dict((k, []) for k in routes), dict((k, []) for k in routes)
+        for i in range(args.pairs):
+            for k, fn in routes.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()                                 # (returns with the records on the host)
+                wall[k].append((time.perf_counter() - t0) * 1e3)
+        for i in range(args.pairs):
+            for k in routes:
+                kern[k].append(events(k))
+        evals = float(sum(len(ids) * C * (len(models[s][0][0]) + len(models[s][1][0])) * len(models[s][2])
+                          for s, ids in groups))
+        pre = dict((k, [e[0] for e in kern[k]]) for k in routes)
+        # seg64's launches before the merge without the psi kernel: what compares with k_joint_f64_chunk
+        chunk64 = [e[0] - e[2] for e in kern['seg64']]
+        line.update(records_equal=True,
+                    wall_ms=dict((k, stats(v)) for k, v in wall.items()),
+                    kernel_ms=dict([(k + '_before_merge', stats(v)) for k, v in pre.items()] +
+                                   [('seg64_psi', stats([e[2] for e in kern['seg64']])),
+                                    ('seg64_without_psi', stats(chunk64))]),
+                    evals_per_s=dict(seg64=evals / (np.median(pre['seg64']) * 1e-3),
+                                     group64=evals / (np.median(pre['group64']) * 1e-3),
+                                     seg32=evals / (np.median(pre['seg32']) * 1e-3)),
+                    shown=dict(wall_seg64_vs_group64=shown(wall['seg64'], wall['group64']),
+                               kernels_seg64_vs_group64=shown(pre['seg64'], pre['group64']),
+                               wall_seg64_vs_seg32=shown(wall['seg64'], wall['seg32']),
+                               kernels_seg64_vs_seg32=shown(pre['seg64'], pre['seg32'])))
+    line['gpu'] = torch.cuda.get_device_name(0)
+    text = json.dumps(line)
+    print(text)
+    out = args.out or os.path.join(ROOT, 'profiles', 'joint_branch_fp64_time.jsonl')
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, 'a') as f:
+        f.write(text + '\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--pairs', type=int, default=7)
@@ -206,6 +320,7 @@ def main():
     ap.add_argument('--out', default=None)
     ap.add_argument('--small', action='store_true')
     ap.add_argument('--wide', action='store_true')
+    ap.add_argument('--fp64', action='store_true')
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -226,6 +341,14 @@ def main():
     words = [0xFFFFFFFE - 5 * s for s in range(8)]
     prob_id = np.arange(n_a, n_a + 64, dtype=np.int64)
     prob_seg = np.arange(64) % 8                 # (every id its own branch: the groups interleave)
+    if args.fp64:
+        measure_fp64('a: 64 ids over 8 groups', eng, models, words, prob_seg, prob_id, 4096, args)
+        measure_fp64('b: 1 id, 1 group', eng, [make_group(n_b, SEED)], [0xFFFFFFFE], [0], [n_b], c_b, args)
+        measure_fp64('c: 1 id, 1 group, D = 16', eng, [make_wide_group(16, n_b, SEED)], [0xFFFFFFFE], [0], [n_b], c_b,
+                     args)
+        measure_fp64('clustered branch: 1 id, 1 group', eng, [make_clustered_group(n_a, SEED)], [0xFFFFFFFE], [0], [n_a],
+                     c_b, args, time_it=False)
+        return 0
     measure('a: 64 ids over 8 groups', eng, models, words, prob_seg, prob_id, 4096, args)
     measure('b: 1 id, 1 group', eng, [make_group(n_b, SEED)], [0xFFFFFFFE], [0], [n_b], c_b, args)
     return 0
