@@ -208,6 +208,19 @@ class JointQuantArgs(ctypes.Structure):
     ]
 
 
+class JointMqF64Args(ctypes.Structure):
+    """tpe_joint_mq_f64_args: one tpe_joint_mq_f64_run (tpe_joint_quant_args' fields, then the float64 density rows,
+    the centres, the float64 category tables and the float64 table workspace)."""
+    _fields_ = JointQuantArgs._fields_ + [
+        ('below_mu64', ctypes.c_void_p), ('below_a64', ctypes.c_void_p), ('below_c64', ctypes.c_void_p),
+        ('above_mu64', ctypes.c_void_p), ('above_a64', ctypes.c_void_p), ('above_c64', ctypes.c_void_p),
+        ('centre', ctypes.c_double * JOINT_MAX_DIMS),
+        ('below_miss64', ctypes.c_void_p), ('below_bonus64', ctypes.c_void_p),
+        ('above_miss64', ctypes.c_void_p), ('above_bonus64', ctypes.c_void_p),
+        ('quant_table64', ctypes.c_void_p), ('quant_table64_bytes', ctypes.c_uint64),
+    ]
+
+
 class JointWideQuantArgs(ctypes.Structure):
     """tpe_joint_wide_quant_args: one tpe_joint_wide_quant_run (tpe_joint_wide_mixed_args' fields, then the
     quantised labels' of tpe_joint_quant_args)."""
@@ -607,6 +620,8 @@ EXPORTS = ('tpe_abi_version', 'tpe_last_error', 'tpe_device_count', 'tpe_tile_si
            'tpe_report_profile', 'tpe_joint_scratch_bytes', 'tpe_joint_run', 'tpe_joint_profile',
            'tpe_joint_f64_scratch_bytes', 'tpe_joint_f64_run',
            'tpe_joint_mixed_run', 'tpe_joint_quant_table_bytes', 'tpe_joint_quant_run', 'tpe_joint_quant_profile',
+           'tpe_joint_mq_f64_scratch_bytes', 'tpe_joint_mq_f64_table_bytes', 'tpe_joint_mq_f64_run',
+           'tpe_joint_mq_f64_profile',
            'tpe_joint_wide_scratch_bytes', 'tpe_joint_wide_run', 'tpe_joint_wide_profile',
            'tpe_joint_wide_f64_scratch_bytes', 'tpe_joint_wide_f64_run', 'tpe_joint_wide_f64_profile',
            'tpe_joint_wide_mixed_scratch_bytes', 'tpe_joint_wide_mixed_run',
@@ -753,6 +768,14 @@ def load(path=LIB_PATH):
     lib.tpe_joint_quant_run.restype = ctypes.c_int
     lib.tpe_joint_quant_profile.argtypes = [P]
     lib.tpe_joint_quant_profile.restype = ctypes.c_int
+    lib.tpe_joint_mq_f64_scratch_bytes.argtypes = [I32, I32, ctypes.POINTER(ctypes.c_uint64)]
+    lib.tpe_joint_mq_f64_scratch_bytes.restype = ctypes.c_int
+    lib.tpe_joint_mq_f64_table_bytes.argtypes = [I32, I32, I32, ctypes.POINTER(ctypes.c_uint64)]
+    lib.tpe_joint_mq_f64_table_bytes.restype = ctypes.c_int
+    lib.tpe_joint_mq_f64_run.argtypes = [ctypes.POINTER(JointMqF64Args), P, P, P, P, P, ctypes.c_uint64, P]
+    lib.tpe_joint_mq_f64_run.restype = ctypes.c_int
+    lib.tpe_joint_mq_f64_profile.argtypes = [P]
+    lib.tpe_joint_mq_f64_profile.restype = ctypes.c_int
     lib.tpe_joint_wide_scratch_bytes.argtypes = [I32, I32, I32, ctypes.POINTER(ctypes.c_uint64)]
     lib.tpe_joint_wide_scratch_bytes.restype = ctypes.c_int
     lib.tpe_joint_wide_run.argtypes = [ctypes.POINTER(JointWideArgs), P, P, P, P, P, ctypes.c_uint64, P]

@@ -834,9 +834,10 @@ __device__ __forceinline__ double bin_mass(double ta, double sa, double tb, doub
 
 // One (component, dimension) column of a side's table: walk the V + 1 edges e of
 // the dimension once, one erfc per edge (the smaller tail), shared by the two
-// bins that meet there; out[i * K] = log2 P(i), floored at TPE_JOINT_QFLOOR.
+// bins that meet there; out[i * K] = log2 P(i), as f32 floored at TPE_JOINT_QFLOOR.
+template <typename T>
 __device__ __forceinline__ void qtable_column(double m, double s, const double* __restrict__ e, int V,
-                                              float* __restrict__ out, int K) {
+                                              T* __restrict__ out, int64_t K) {
   const double r = 0.70710678118654752440 / s;
   const double t0 = (e[0] - m) * r, tv = (e[V] - m) * r;
   const double s0 = small_tail(fabs(t0)), sv = small_tail(fabs(tv));
@@ -846,8 +847,9 @@ __device__ __forceinline__ void qtable_column(double m, double s, const double* 
     const double tb = i + 1 < V ? (e[i + 1] - m) * r : tv;
     const double sb = i + 1 < V ? small_tail(fabs(tb)) : sv;
     double v = log2(bin_mass(ta, sa, tb, sb)) - lmass;
-    if (!(v >= kQFloor)) v = kQFloor;       // -inf (a far bin's mass is 0) and NaN included
-    out[(int64_t)i * K] = (float)v;
+    if constexpr (std::is_same<T, float>::value)
+      if (!(v >= kQFloor)) v = kQFloor;     // -inf (a far bin's mass is 0) and NaN included
+    out[i * K] = (T)v;                      // (T = double, the float64 mixed stage: unrounded, a zero mass -inf)
     ta = tb; sa = sb;
   }
 }
@@ -2406,6 +2408,298 @@ __global__ __launch_bounds__(kThreads) void k_joint_f64_chunk(const JointF64K p)
   for (int d = 0; d < TPE_JOINT_MAX_DIMS; ++d) q.rec->z[d] = d < DP ? (double)bz[d < DP ? d : 0] : 0.0;
 }
 
+// ------------------------------------------------------ float64 mixed stage
+// k_joint_f64_chunk for a group that also holds discrete and quantised labels
+// (include/tpe_hip.h "Float64 mixed joint stage").  The pass, phi, the psi tile,
+// the pairs, the vote and the finish are that kernel's; what differs:
+//
+// Candidates.  A pass's 256 candidates are drawn by the wide samplers' parts
+// (wide_sample_continuous / _categories / _lattice: k_joint_quant_chunk's draw,
+// word for word) into zs[coordinate][thread] in LDS, or copied there from
+// `inject`; the per-label sizes that those loops index at run time are staged in
+// LDS.  A lane reads phi's entries and, after the MFMA chain, the categories and
+// lattice indices of its 16 results' candidates from zs: a lane group of 16
+// lanes reads one address (a broadcast), the four groups four addresses.
+//
+// Between the MFMA chain and the vote a lane adds, to each of its 4 x 4 results
+// (candidate 16 q + 4 v + (lane >> 4) of the wave, component cb 16 + (lane & 15)),
+//   bonus_d(v_d) where v_d equals the component's category (the side's f64 bonus
+//   table in LDS; the component's categories in LDS as [slot][component] f32),
+//   T_q[i_q][k] from the side's f64 table in device memory, laid out [lattice
+//   value][component] with the component stride a multiple of 16: the 16 lanes of
+//   a group read one aligned 128-byte run, the four groups four runs.  (At sum V =
+//   512 a 16-component f64 tile alone would fill the 64 KiB, so the table is
+//   read where it lies; it is the L2's to keep.)
+// in run-time loops over the discrete and quantised slots (no register array is
+// indexed by them).  A table entry of -inf makes the term -inf: it fails the vote
+// (-inf <= m - skip for every finite m), and in a live block exp2_nonpos gives 0
+// and fmax keeps m; m starts at the lowest finite double, so -inf - -inf never
+// arises.  No continuous label: the class DP = 1 with phi = [0, 0, 1, 0] (the
+// constant-only phi: one MFMA step that delivers -c_k).
+constexpr int kMqSlots = TPE_JOINT_MAX_DIMS;
+constexpr int mq_tile(int DP) { return DP > 8 ? 64 : 128; }   // components per psi tile
+__host__ __device__ __forceinline__ int64_t mq_stride(int K) { return ((int64_t)K + 15) & ~(int64_t)15; }
+
+struct MqF64K {
+  WideQuantSampK s;                 // the draws: s.D = Dc, s.Dk, s.Dq (its U / off: unused, see below)
+  int n_chunks, inject, ka, ncat;   // ncat: sum U_d
+  int U[kMqSlots], off[kMqSlots], voff[kWQ];
+  const float* inj;
+  const double *bmu, *ba, *bc, *amu, *aa, *ac;
+  const float* acat;                // (the below side's: s.bcat)
+  const double *bmiss, *bbonus, *amiss, *abonus;
+  const double *bT, *aT;            // [sum V][mq_stride(K)] of a side
+  double bbase, abase;
+  double centre[TPE_JOINT_MAX_DIMS];
+  float* cand;
+  double *l_out, *g_out;
+  tpe_joint_record* chunk_rec;
+};
+
+// one side of the model as the scoring loop reads it
+struct MqSide {
+  const double *mu, *a, *c;
+  const float* cat;
+  const double *miss, *bonus, *T;
+  int K;
+};
+// the per-label sizes, staged in LDS
+struct MqDims {
+  int cU[kMqSlots], coff[kMqSlots];
+  int qV[kWQ], qeoff[kWQ], qvoff[kWQ];
+  float qlo[kWQ], qhi[kWQ];
+  float blo[TPE_JOINT_MAX_DIMS], bhi[TPE_JOINT_MAX_DIMS];
+};
+
+// The f64 table of one side: k_joint_qtable's walk, stored unrounded and
+// unfloored (an exactly-zero mass: -inf) with the component stride Ks; the
+// columns [K, Ks) hold zeros (their components' terms are -inf through psi).
+struct QTab64K {
+  int K, Dq;
+  int64_t Ks;
+  int V[TPE_JOINT_MAX_QUANT], voff[TPE_JOINT_MAX_QUANT], eoff[TPE_JOINT_MAX_QUANT];
+  const double *mu, *sigma, *edges;
+  double* T;
+};
+__global__ __launch_bounds__(kThreads) void k_joint_qtable_f64(const QTab64K p) {
+  const int k = blockIdx.x * kThreads + threadIdx.x, d = blockIdx.y;
+  if (k >= p.Ks) return;
+  int V = 2, voff = 0, eoff = 0;            // (kernel-argument arrays: constant indices only)
+#pragma unroll
+  for (int f = 0; f < TPE_JOINT_MAX_QUANT; ++f)
+    if (f == d) { V = p.V[f]; voff = p.voff[f]; eoff = p.eoff[f]; }
+  double* out = p.T + (int64_t)voff * p.Ks + k;
+  if (k >= p.K) {
+    for (int i = 0; i < V; ++i) out[(int64_t)i * p.Ks] = 0.0;
+    return;
+  }
+  qtable_column(p.mu[(int64_t)k * p.Dq + d], p.sigma[(int64_t)k * p.Dq + d], p.edges + eoff, V, out, p.Ks);
+}
+
+// score_side_f64 with the discrete and quantised terms.  zs: the pass's
+// candidates [coordinate][thread]; ccat: the tile's categories [slot][TK]; bon:
+// the side's bonus table.
+template <int DP>
+__device__ __forceinline__ double score_side_mq_f64(const MqSide& sd, int Dc, int Dk, int Dq, int ncat,
+                                                    const double (&phi)[4][f64_steps(DP)],
+                                                    double* __restrict__ tile, float* __restrict__ ccat,
+                                                    double* __restrict__ bon, const float* __restrict__ zs,
+                                                    const MqDims& dm, const double* __restrict__ cs,
+                                                    double* __restrict__ res) {
+  constexpr int NI = f64_steps(DP), TK = mq_tile(DP);
+  const int t = threadIdx.x, lane = t & 63, K = sd.K;
+  const int64_t Ks = mq_stride(K);
+  const float* zw = zs + (t & ~63) + (lane >> 4);          // result (q, v): zw[coordinate * 256 + 16 q + 4 v]
+  double m[4][4], s[4][4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+#pragma unroll
+    for (int v = 0; v < 4; ++v) { m[q][v] = kF64Lowest; s[q][v] = 0.0; }   // (any finite first term exceeds it)
+  for (int e = t; e < ncat; e += kThreads) bon[e] = sd.bonus[e];           // (the side before ended on a barrier)
+  for (int k0 = 0; k0 < K; k0 += TK) {
+    const int nk = min(TK, K - k0), ncb = (nk + 15) >> 4;
+    __syncthreads();                       // the previous tile (or the candidates' staging) is read
+    for (int e = t; e < ncb * NI * 64; e += kThreads) {
+      const int col = e & 15, inner = 4 * ((e >> 6) % NI) + ((e >> 4) & 3), kk = ((e >> 6) / NI) * 16 + col;
+      tile[e] = psi_entry(sd.mu, sd.a, sd.c, kk >= nk, Dc, DP, k0 + kk, inner, cs);
+    }
+    for (int e = t; e < Dk * TK; e += kThreads) {
+      const int d = e / TK, kk = e - d * TK;               // past the side's end: -1 never matches
+      ccat[e] = kk < nk ? sd.cat[(int64_t)(k0 + kk) * Dk + d] : -1.f;
+    }
+    __syncthreads();
+    for (int cb = 0; cb < ncb; ++cb) {
+      const double* bt = tile + cb * NI * 64 + lane;
+      double b[NI];
+#pragma unroll
+      for (int i = 0; i < NI; ++i) b[i] = bt[i * 64];
+      F64x4 acc[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc[q] = F64x4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int i = 0; i < NI; ++i)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(phi[q][i], b[i], acc[q], 0, 0, 0);
+      const int kk = cb * 16 + (lane & 15);
+#pragma unroll 1
+      for (int d = 0; d < Dk; ++d) {
+        const float xk = ccat[d * TK + kk];
+        const float* zr = zw + (Dc + d) * kThreads;
+        const double* bd = bon + dm.coff[d];
+        const int U = dm.cU[d];
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+          for (int v = 0; v < 4; ++v) {
+            const float vc = zr[16 * q + 4 * v];
+            if (vc == xk) acc[q][v] -= bd[cat_index(vc, U)];
+          }
+      }
+#pragma unroll 1
+      for (int d = 0; d < Dq; ++d) {
+        const float* zr = zw + (Dc + Dk + d) * kThreads;
+        const double* Tr = sd.T + (int64_t)dm.qvoff[d] * Ks + k0 + kk;   // k0 + kk < Ks: the stride is a multiple of 16
+        const int V = dm.qV[d];
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+          for (int v = 0; v < 4; ++v) acc[q][v] -= Tr[(int64_t)cat_index(zr[16 * q + 4 * v], V) * Ks];
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        bool live = false;                 // (a NaN term is live, and stays in the sum; a -inf term is not)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) live |= !(-acc[q][v] <= m[q][v] - kF64Skip);
+        if (__builtin_amdgcn_ballot_w64(live) == 0) continue;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          const double term = -acc[q][v], dl = term - m[q][v];
+          const double e2 = exp2_nonpos(-__builtin_fabs(dl));
+          s[q][v] = dl > 0.0 ? __builtin_fma(s[q][v], e2, 1.0) : s[q][v] + e2;
+          m[q][v] = fmax(m[q][v], term);
+        }
+      }
+    }
+  }
+  // a row's 16 column lanes (lane & 15) hold its partial pairs
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+#pragma unroll
+      for (int mask = 1; mask < 16; mask <<= 1) {
+        const double mo = __shfl_xor(m[q][v], mask, 64), so = __shfl_xor(s[q][v], mask, 64);
+        const double top = fmax(m[q][v], mo);
+        s[q][v] = s[q][v] * exp2_nonpos(m[q][v] - top) + so * exp2_nonpos(mo - top);
+        m[q][v] = top;
+      }
+      if ((lane & 15) == 0) res[(t & ~63) + 16 * q + 4 * v + (lane >> 4)] = m[q][v] + log2(s[q][v]);
+    }
+  __syncthreads();
+  double out = res[t];                     // + the candidate's sum_d miss_d(v_d), after the sum over k
+#pragma unroll 1
+  for (int d = 0; d < Dk; ++d) out += sd.miss[dm.coff[d] + cat_index(zs[(Dc + d) * kThreads + t], dm.cU[d])];
+  return out;
+}
+
+template <int DP>
+__global__ __launch_bounds__(kThreads) void k_joint_mq_f64_chunk(const MqF64K p) {
+  constexpr int NI = f64_steps(DP), TK = mq_tile(DP), MD = TPE_JOINT_MAX_DIMS;
+  __shared__ __attribute__((aligned(16))) double tile[(TK / 16) * NI * 64];
+  __shared__ double bon[TPE_JOINT_MAX_CAT_TOTAL];
+  __shared__ double res[kThreads];
+  __shared__ double cs[DP];
+  __shared__ float zs[MD * kThreads];
+  __shared__ float ccat[kMqSlots * TK];
+  __shared__ MqDims dm;
+  __shared__ Pick slot[kThreads / 64];
+  const int t = threadIdx.x, lane = t & 63;
+  const int id = blockIdx.x / p.n_chunks, first = (int)(blockIdx.x % p.n_chunks) * TPE_JOINT_CHUNK;
+  const int Dc = p.s.D, Dk = p.s.Dk, Dq = p.s.Dq, D = Dc + Dk + Dq, C = p.s.C;
+
+  if (t == 0) {                            // (kernel-argument arrays: constant indices only)
+    stage(dm.cU, p.U); stage(dm.coff, p.off);
+    stage(dm.qV, p.s.V); stage(dm.qeoff, p.s.eoff); stage(dm.qvoff, p.voff);
+    stage(dm.qlo, p.s.qlo); stage(dm.qhi, p.s.qhi);
+#pragma unroll
+    for (int d = 0; d < MD; ++d) { dm.blo[d] = p.s.lo[d]; dm.bhi[d] = p.s.hi[d]; }
+#pragma unroll
+    for (int d = 0; d < DP; ++d) cs[d] = d < MD ? p.centre[d < MD ? d : 0] : 0.0;
+  }
+  const MqSide below{p.bmu, p.ba, p.bc, p.s.bcat, p.bmiss, p.bbonus, p.bT, p.s.kb};
+  const MqSide above{p.amu, p.aa, p.ac, p.acat, p.amiss, p.abonus, p.aT, p.ka};
+  const int64_t o = (int64_t)id * C;
+  tpe_joint_record* rec = p.chunk_rec + blockIdx.x;
+
+  Pick best{0, 0};
+  double bl = 0.0, bg = 0.0;
+  float bz[MD];
+#pragma unroll
+  for (int d = 0; d < MD; ++d) bz[d] = 0.f;
+#pragma unroll 1
+  for (int r = 0; r < kR; ++r) {
+    const int i = first + r * kThreads + t;
+    __syncthreads();                       // dm is staged; the previous pass has read zs
+    for (int d = 0; d < D; ++d) zs[d * kThreads + t] = 0.f;
+    if (i < C) {
+      if (p.inject) {
+        for (int d = 0; d < D; ++d) zs[d * kThreads + t] = p.inj[(int64_t)i * D + d];
+      } else {
+        WideDraw c;
+        c.out = zs + t;                    // coordinate j at out[j * 256]
+        wide_sample_stream(p.s, i, id, c);
+        wide_sample_continuous(p.s, c, dm.blo, dm.bhi);
+        wide_sample_categories(p.s, c, dm.cU, dm.coff);
+        wide_sample_lattice(p.s, c, dm.qV, dm.qeoff, dm.qlo, dm.qhi);
+      }
+    }
+    __syncthreads();
+    double phi[4][NI];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const float* zr = zs + (t & ~63) + 16 * b + (lane & 15);
+#pragma unroll
+      for (int s = 0; s < NI; ++s) {
+        const int e = 4 * s + (lane >> 4), d = min(e < DP ? e : e - DP, DP - 1);
+        const double zp = d < Dc ? (double)zr[d * kThreads] - cs[d] : 0.0;
+        phi[b][s] = e < DP ? zp * zp : e < 2 * DP ? zp : e == 2 * DP ? 1.0 : 0.0;
+      }
+    }
+    const double l2 = score_side_mq_f64<DP>(below, Dc, Dk, Dq, p.ncat, phi, tile, ccat, bon, zs, dm, cs, res);
+    const double g2 = score_side_mq_f64<DP>(above, Dc, Dk, Dq, p.ncat, phi, tile, ccat, bon, zs, dm, cs, res);
+    const double lv = l2 * kLn2 + p.bbase, gv = g2 * kLn2 + p.abase;
+    if (i >= C) continue;
+    if (p.l_out) p.l_out[o + i] = lv;
+    if (p.g_out) p.g_out[o + i] = gv;
+    if (p.cand)
+      for (int d = 0; d < D; ++d) p.cand[(o + i) * D + d] = zs[d * kThreads + t];
+    const uint64_t key = score_key(lv - gv);
+    if (key > best.key) {                  // ascending index: strict > keeps the first of a tie
+      best = Pick{key, (int64_t)i};
+      bl = lv; bg = gv;
+#pragma unroll
+      for (int d = 0; d < MD; ++d) bz[d] = d < D ? zs[d * kThreads + t] : 0.f;
+    }
+  }
+  Pick w = wave_best(best);
+  if (lane == 0) slot[t >> 6] = w;
+  __syncthreads();
+  w = slot[0];
+#pragma unroll
+  for (int k = 1; k < kThreads / 64; ++k)
+    if (beats(slot[k], w)) w = slot[k];
+  if (w.key == 0) {
+    if (t == 0) rec->global_idx = -1;
+    return;
+  }
+  if (best.key != w.key || best.idx != w.idx) return;
+  rec->global_idx = w.idx + (int64_t)p.s.cand_base;
+  rec->l = bl;
+  rec->g = bg;
+#pragma unroll
+  for (int d = 0; d < MD; ++d) rec->z[d] = (double)bz[d];   // kernel coordinate order, then zeros
+}
+
 // ------------------------------------------------------- wide float64 stage
 // The float64 stage for a wide group (include/tpe_hip.h "Wide float64 joint
 // stage"): k_joint_wide_sample's candidates in zbuf (or `inject`), the wide
@@ -3685,6 +3979,138 @@ int joint_quant_run_at(const tpe_joint_quant_args* a, tpe_joint_record* records,
   return finish(k_joint_merge, (const tpe_joint_record*)scratch, qk.m.j.n_chunks, records, a->n_ids, s, timed, 1);
 }
 
+// the float64 mixed stage: tpe_joint_quant_run's head, labels, chunk records and
+// merge; its own f64 rows, centres, category tables, table workspace and kernels
+static_assert(offsetof(tpe_joint_mq_f64_args, quant_table_bytes) == offsetof(tpe_joint_quant_args, quant_table_bytes) &&
+                  offsetof(tpe_joint_mq_f64_args, below_mu64) == sizeof(tpe_joint_quant_args) &&
+                  offsetof(tpe_joint_mq_f64_args, cat_cum) == offsetof(tpe_joint_quant_args, cat_cum),
+              "tpe_joint_mq_f64_args starts with tpe_joint_quant_args");
+static_assert(offsetof(tpe_joint_mq_f64_args, seed) == offsetof(tpe_joint_f64_args, seed) &&
+                  offsetof(tpe_joint_mq_f64_args, below_base) == offsetof(tpe_joint_f64_args, below_base) &&
+                  offsetof(tpe_joint_mq_f64_args, low) == offsetof(tpe_joint_f64_args, low) &&
+                  offsetof(tpe_joint_mq_f64_args, high) == offsetof(tpe_joint_f64_args, high) &&
+                  offsetof(tpe_joint_f64_args, centre) ==
+                      offsetof(tpe_joint_f64_args, high) + sizeof(double[TPE_JOINT_MAX_DIMS]),
+              "the forward to tpe_joint_f64_run copies the head up to the centres");
+struct {
+  int valid;
+  hipEvent_t ev[2];
+} g_mqprof = {0, {}};
+uint64_t mq_f64_table_doubles(int64_t k_below, int64_t k_above, int64_t total) {
+  return (uint64_t)(mq_stride((int)k_below) + mq_stride((int)k_above)) * (uint64_t)total;
+}
+int joint_mq_f64_run(const tpe_joint_mq_f64_args* a, tpe_joint_record* records, float* cand, double* l_out,
+                     double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
+  constexpr const char* E = "tpe_joint_mq_f64_run";
+  tpe_internal_epoch_bump();
+  if (!a) return fail(E, "null args");
+  if (a->n_quant < 0 || a->n_quant > TPE_JOINT_MAX_QUANT) return fail(E, "n_quant outside [0, TPE_JOINT_MAX_QUANT]");
+  if (a->n_cat < 0) return fail(E, "n_cat < 0");
+  if (a->n_cat == 0 && a->n_quant == 0) {   // continuous labels alone: the float64 stage, the same bytes
+    tpe_joint_f64_args c;
+    memcpy(&c, a, offsetof(tpe_joint_f64_args, centre));
+    c.reserved = 0;
+    c.below_mu = a->below_mu64; c.below_a = a->below_a64; c.below_c = a->below_c64;
+    c.above_mu = a->above_mu64; c.above_a = a->above_a64; c.above_c = a->above_c64;
+    memcpy(c.centre, a->centre, sizeof c.centre);
+    return joint_f64_run(&c, records, cand, l_out, g_out, scratch, scratch_bytes, stream);
+  }
+  const int Dc = a->n_dims, Dk = a->n_cat, Dq = a->n_quant;
+  if (Dc < 0 || Dc > TPE_JOINT_MAX_DIMS || Dk > TPE_JOINT_MAX_DIMS || Dc + Dk + Dq > TPE_JOINT_MAX_DIMS)
+    return fail(E, "n_dims + n_cat + n_quant outside [1, TPE_JOINT_MAX_DIMS]");
+  if (Dq > 0 && (Dc > 8 || Dk > 4)) return fail(E, "n_dims > 8 or n_cat > 4 beside a quantised label");
+  if (a->n_cand < 1) return fail(E, "n_cand < 1");
+  if (a->n_ids < 1) return fail(E, "n_ids < 1");
+  if (a->k_below < 1 || a->k_above < 1) return fail(E, "k_below < 1 or k_above < 1");
+  if (!a->below_c64 || !a->above_c64 || (Dc > 0 && (!a->below_mu64 || !a->below_a64 || !a->above_mu64 || !a->above_a64)))
+    return fail(E, "null f64 density rows");
+  const bool inject = (a->flags & TPE_JOINT_INJECT) != 0;
+  if (inject && !a->inject) return fail(E, "TPE_JOINT_INJECT without candidates");
+  if (!inject && (!a->samp_cum || (Dc > 0 && !a->samp))) return fail(E, "null sampler rows");
+  if (!a->ids || !records) return fail(E, "null ids / records");
+  int64_t ncat = 0, total = 0;
+  if (Dk > 0) {
+    if (!a->below_cat || !a->above_cat || !a->below_h || !a->cat_cum) return fail(E, "null category tables");
+    if (!a->below_miss64 || !a->below_bonus64 || !a->above_miss64 || !a->above_bonus64)
+      return fail(E, "null f64 category tables");
+    if ((ncat = check_cats(E, "", a->cat_upper, a->cat_off, Dk)) < 0) return TPE_E_ARG;
+  }
+  if (Dq > 0) {
+    if ((total = check_lattice(E, "", a->quant_v, a->quant_edge_off, Dq, a->n_edges)) < 0) return TPE_E_ARG;
+    if (!a->quant_edges || !a->below_qmu || !a->below_qsigma || !a->above_qmu || !a->above_qsigma || !a->quant_samp)
+      return fail(E, "null quantised rows");
+    if (!a->quant_table64) return fail(E, "null f64 table");
+    if (a->quant_table64_bytes < mq_f64_table_doubles(a->k_below, a->k_above, total) * sizeof(double))
+      return fail(E, "table workspace too small");
+  }
+  for (int d = 0; d < Dc; ++d)
+    if (!isfinite(a->centre[d])) return fail(E, "centre not finite");
+  const int64_t blocks = n_chunks_of(a->n_cand) * a->n_ids;
+  if (int rc = check_scratch(E, blocks, joint_scratch_need(a->n_ids, a->n_cand), scratch, scratch_bytes)) return rc;
+
+  MqF64K k;
+  WideQuantSampK& sk = k.s;
+  fill_wide_samp(sk, a, Dc, 0, 0u, nullptr);
+  sk.Dk = Dk; sk.Dq = Dq;
+  for (int d = 0; d < kWK; ++d) { sk.U[d] = 1; sk.off[d] = 0; }   // (the kernel stages k.U / k.off: up to 16 slots)
+  sk.bcat = a->below_cat; sk.bh = a->below_h; sk.ccum = a->cat_cum;
+  sk.edges = a->quant_edges; sk.qsamp = a->quant_samp;
+  for (int d = 0; d < kMqSlots; ++d) {
+    k.U[d] = d < Dk ? a->cat_upper[d] : 1;
+    k.off[d] = d < Dk ? a->cat_off[d] : 0;
+  }
+  int voff = 0;
+  for (int d = 0; d < kWQ; ++d) {
+    const bool in = d < Dq;
+    sk.V[d] = in ? a->quant_v[d] : 2;
+    sk.eoff[d] = in ? a->quant_edge_off[d] : 0;
+    k.voff[d] = in ? voff : 0;
+    sk.qlo[d] = -INFINITY; sk.qhi[d] = INFINITY;
+    if (in) {
+      f32_bounds(a->low[Dc + d], a->high[Dc + d], sk.qlo[d], sk.qhi[d]);
+      voff += a->quant_v[d];
+    }
+  }
+  k.n_chunks = (int)n_chunks_of(a->n_cand); k.inject = inject ? 1 : 0; k.ka = a->k_above; k.ncat = (int)ncat;
+  k.inj = a->inject;
+  k.bmu = a->below_mu64; k.ba = a->below_a64; k.bc = a->below_c64;
+  k.amu = a->above_mu64; k.aa = a->above_a64; k.ac = a->above_c64;
+  k.acat = a->above_cat;
+  k.bmiss = a->below_miss64; k.bbonus = a->below_bonus64; k.amiss = a->above_miss64; k.abonus = a->above_bonus64;
+  k.bT = a->quant_table64;
+  k.aT = Dq > 0 ? a->quant_table64 + total * mq_stride(a->k_below) : nullptr;
+  k.bbase = a->below_base; k.abase = a->above_base;
+  for (int d = 0; d < TPE_JOINT_MAX_DIMS; ++d) k.centre[d] = d < Dc ? a->centre[d] : 0.0;
+  k.cand = cand; k.l_out = l_out; k.g_out = g_out;
+  k.chunk_rec = (tpe_joint_record*)scratch;
+
+  const bool timed = g_prof.on != 0;
+  hipStream_t s = (hipStream_t)stream;
+  g_mqprof.valid = 0;
+  if (Dq > 0) {                             // the two sides' tables, under profiling between g_mqprof's events
+    if (timed)
+      if (int rc = ensure_events(g_mqprof.ev, 2)) return rc;
+    QTab64K tb;
+    tb.Dq = Dq; tb.edges = a->quant_edges;
+    memcpy(tb.V, sk.V, sizeof tb.V); memcpy(tb.voff, k.voff, sizeof tb.voff); memcpy(tb.eoff, sk.eoff, sizeof tb.eoff);
+    tb.K = a->k_below; tb.Ks = mq_stride(a->k_below); tb.mu = a->below_qmu; tb.sigma = a->below_qsigma;
+    tb.T = a->quant_table64;
+    QTab64K ta = tb;
+    ta.K = a->k_above; ta.Ks = mq_stride(a->k_above); ta.mu = a->above_qmu; ta.sigma = a->above_qsigma;
+    ta.T = a->quant_table64 + total * tb.Ks;
+    launch(k_joint_qtable_f64, dim3((unsigned)((tb.Ks + kThreads - 1) / kThreads), (unsigned)Dq), kThreads, 0u, s,
+           timed ? g_mqprof.ev[0] : nullptr, nullptr, tb);
+    launch(k_joint_qtable_f64, dim3((unsigned)((ta.Ks + kThreads - 1) / kThreads), (unsigned)Dq), kThreads, 0u, s,
+           nullptr, timed ? g_mqprof.ev[1] : nullptr, ta);
+    if (timed) g_mqprof.valid = 1;
+  }
+  const Ev ev = chunk_marks(timed);
+  pad_to<1, 2, 4, 8, 16>(Dc, [&](auto dp) {   // 5 classes: the continuous width alone
+    launch(k_joint_mq_f64_chunk<decltype(dp)::value>, dim3((unsigned)blocks), kThreads, 0u, s, ev.start, ev.stop, k);
+  });
+  return finish(k_joint_merge, (const tpe_joint_record*)scratch, k.n_chunks, records, a->n_ids, s, timed, 1);
+}
+
 // ---- the segmented stages: one skeleton (joint_seg_run_at); a stage supplies its
 // per-segment check, its class function and its class launcher as overloads on
 // its descriptor, tpe_joint_seg, tpe_joint_wide_seg, tpe_joint_mseg or tpe_joint_seg_f64
@@ -4102,6 +4528,25 @@ int tpe_joint_f64_scratch_bytes(int32_t n_ids, int32_t n_cand, uint64_t* bytes) 
 int tpe_joint_f64_run(const tpe_joint_f64_args* a, tpe_joint_record* records, float* cand, double* l_out,
                       double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
   return joint_f64_run(a, records, cand, l_out, g_out, scratch, scratch_bytes, stream);
+}
+
+int tpe_joint_mq_f64_scratch_bytes(int32_t n_ids, int32_t n_cand, uint64_t* bytes) {
+  return size_out("tpe_joint_mq_f64_scratch_bytes", n_ids >= 1 && n_cand >= 1, joint_scratch_need(n_ids, n_cand), bytes);
+}
+
+int tpe_joint_mq_f64_table_bytes(int32_t k_below, int32_t k_above, int32_t total_bins, uint64_t* bytes) {
+  return size_out("tpe_joint_mq_f64_table_bytes", k_below >= 1 && k_above >= 1 && total_bins >= 1,
+                  mq_f64_table_doubles(k_below, k_above, total_bins) * sizeof(double), bytes);
+}
+
+int tpe_joint_mq_f64_run(const tpe_joint_mq_f64_args* a, tpe_joint_record* records, float* cand, double* l_out,
+                         double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
+  return joint_mq_f64_run(a, records, cand, l_out, g_out, scratch, scratch_bytes, stream);
+}
+
+int tpe_joint_mq_f64_profile(double* table_ms) {
+  if (!table_ms || !g_mqprof.valid) return fail("tpe_joint_mq_f64_profile", "no profiled tpe_joint_mq_f64_run to read");
+  return elapsed_ms(g_mqprof.ev[0], g_mqprof.ev[1], table_ms);
 }
 
 int tpe_joint_wide_f64_scratch_bytes(int32_t n_ids, int32_t n_cand, int32_t n_dims, int32_t k_below, int32_t k_above,

@@ -1100,6 +1100,7 @@ class Engine(object):
                    'mixed': (N.JointMixedArgs, 'tpe_joint_mixed_run'),
                    'wide_mixed': (N.JointWideMixedArgs, 'tpe_joint_wide_mixed_run'),
                    'quant': (N.JointQuantArgs, 'tpe_joint_quant_run'),
+                   'mq_f64': (N.JointMqF64Args, 'tpe_joint_mq_f64_run'),
                    'wide_quant': (N.JointWideQuantArgs, 'tpe_joint_wide_quant_run')}
 
     def _joint_solo(self, entry, below, above, low, high, cats, quants, ids, n_cand, seed, inject, return_cand,
@@ -1122,6 +1123,8 @@ class Engine(object):
             if return_table:
                 raise ValueError('joint stage: return_table needs at least one candidate')
             return self._joint_empty(n_ids, D, return_cand, want_lg, wide)
+        if return_table and not Dq:
+            raise ValueError('joint stage: return_table needs a quantised dimension')
         up = self._joint_up
         struct, fn = self._JOINT_SOLO[entry]
         a = struct()
@@ -1132,15 +1135,19 @@ class Engine(object):
         a.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         for key, field, buf, dtype, part in JP.group_rows_present(r):
             # tpe_joint_quant_run takes null pointers for the rows of an absent continuous part
-            if not (entry == 'quant' and part == 'cont' and Dc == 0):
-                setattr(a, field, up(buf, r[key], _TORCH_OF[dtype]))
+            if entry in ('quant', 'mq_f64') and part == 'cont' and Dc == 0:
+                continue
+            # tpe_joint_mq_f64_run does not read the f32 density rows and category tables: their pointers stay null
+            if entry == 'mq_f64' and key.split('_')[-1] in ('mu', 'a', 'c', 'miss', 'bonus'):
+                continue
+            setattr(a, field, up(buf, r[key], _TORCH_OF[dtype]))
         a.ids = up('ids', ids, torch.int64)
         if inject is not None:
             a.flags |= N.JOINT_INJECT
             a.inject = up('inject', JP.inject_rows(inject, C, D), torch.float32)
         for d in range(Dc):
             a.low[d], a.high[d] = r['low'][d], r['high'][d]
-        if entry in ('f64', 'wide_f64'):
+        if entry in ('f64', 'wide_f64', 'mq_f64'):
             for d in range(Dc):
                 a.centre[d] = r['centre'][d]
         if Dk:
@@ -1154,14 +1161,26 @@ class Engine(object):
                 a.quant_v[d], a.quant_edge_off[d] = r['quant_v'][d], r['quant_edge_off'][d]
             total = r['n_lattice']
             nb = ctypes.c_uint64(0)
-            N.check(self.lib.tpe_joint_quant_table_bytes(a.k_below, a.k_above, total, ctypes.byref(nb)), self.lib,
-                    'tpe_joint_quant_table_bytes')
-            d_tab = self._buf('joint_qtable', (nb.value + 3) // 4, torch.float32)
-            a.quant_table, a.quant_table_bytes = d_tab.data_ptr(), d_tab.numel() * 4
+            if entry == 'mq_f64':                    # the float64 tables, a side's component stride a multiple of 16
+                N.check(self.lib.tpe_joint_mq_f64_table_bytes(a.k_below, a.k_above, total, ctypes.byref(nb)), self.lib,
+                        'tpe_joint_mq_f64_table_bytes')
+                d_tab = self._buf('joint_qtable64', nb.value // 8, torch.float64)
+                a.quant_table64, a.quant_table64_bytes = d_tab.data_ptr(), d_tab.numel() * 8
+            else:
+                N.check(self.lib.tpe_joint_quant_table_bytes(a.k_below, a.k_above, total, ctypes.byref(nb)), self.lib,
+                        'tpe_joint_quant_table_bytes')
+                d_tab = self._buf('joint_qtable', (nb.value + 3) // 4, torch.float32)
+                a.quant_table, a.quant_table_bytes = d_tab.data_ptr(), d_tab.numel() * 4
         out = self._joint_call(fn, a, n_ids, C, D, return_cand, want_lg, wide=wide, report_k=report_k, shard=shard,
                                n_cat=Dk if wide else 0, liar=liar, n_quant=Dq if wide else 0)
         if not return_table:
             return out
+        if entry == 'mq_f64':
+            sb, sa = (a.k_below + 15) // 16 * 16, (a.k_above + 15) // 16 * 16
+            tab = d_tab[:(sb + sa) * total].cpu().numpy()
+            tb = tab[:total * sb].reshape(total, sb)[:, :a.k_below].T.copy()
+            ta = tab[total * sb:].reshape(total, sa)[:, :a.k_above].T.copy()
+            return (out if isinstance(out, tuple) else (out,)) + (tb, ta)
         tab = d_tab[:(a.k_below + a.k_above) * total].cpu().numpy()
         tb = tab[:total * a.k_below].reshape(total, a.k_below).T.copy()
         ta = tab[total * a.k_below:].reshape(total, a.k_above).T.copy()
@@ -1359,6 +1378,9 @@ class Engine(object):
         elif fn == 'tpe_joint_f64_run':
             N.check(self.lib.tpe_joint_f64_scratch_bytes(n_ids, C, ctypes.byref(nb)), self.lib,
                     'tpe_joint_f64_scratch_bytes')
+        elif fn == 'tpe_joint_mq_f64_run':
+            N.check(self.lib.tpe_joint_mq_f64_scratch_bytes(n_ids, C, ctypes.byref(nb)), self.lib,
+                    'tpe_joint_mq_f64_scratch_bytes')
         else:
             N.check(self.lib.tpe_joint_scratch_bytes(n_ids, C, ctypes.byref(nb)), self.lib, 'tpe_joint_scratch_bytes')
         d_scr = self._buf('joint_scratch', (nb.value + 7) // 8, torch.float64)
@@ -1779,7 +1801,7 @@ class Engine(object):
         return self._joint_seg_liar_call('mseg', a, la, b, lb, C, return_cand, want_lg, return_sigma)
 
     def run_joint_mixed(self, below, above, low, high, cats, ids, n_cand, seed, inject=None, return_cand=False,
-                        want_lg=False, report_k=0, stream_word=None, shard=None):
+                        want_lg=False, report_k=0, stream_word=None, shard=None, precision='fp32'):
         """One joint stage over a mixed group (tpe_joint_mixed_run,
         include/tpe_hip.h "Mixed joint stage"): ``below`` / ``above`` = (w [K],
         mu [K, Dc], sigma [K, Dc]) the continuous part as in ``run_joint`` (Dc
@@ -1789,7 +1811,15 @@ class Engine(object):
         coordinates: the Dc continuous ones, then the categories as indices;
         ``inject`` [C, Dc + Dk], candidates f32 [n_ids, C, Dc + Dk].
         ``stream_word``: the Philox stream word (None: N.JOINT_STREAM; a branch
-        group's joint.branch_stream_word, to compare with run_joint_segments)."""
+        group's joint.branch_stream_word, to compare with run_joint_segments).
+        ``precision`` 'fp64' (DESIGN.md "Float64 mixed joint stage"):
+        tpe_joint_mq_f64_run scores the 'fp32' call's candidates, bit for bit,
+        in float64 from the unrounded rows and category tables; ``inject``,
+        ``return_cand``, ``want_lg`` and ``stream_word`` work as without it,
+        ``report_k`` > 0 and ``shard`` raise ValueError."""
+        if self._joint_fp64(precision, report_k, shard, False, None, False):
+            return self._joint_solo('mq_f64', below, above, low, high, cats, (), ids, n_cand, seed, inject,
+                                    return_cand, want_lg, 0, stream_word, None)
         return self._joint_solo('mixed', below, above, low, high, cats, (), ids, n_cand, seed, inject, return_cand,
                                 want_lg, report_k, stream_word, shard)
 
@@ -1808,7 +1838,8 @@ class Engine(object):
                                 return_cand, want_lg, report_k, stream_word, None)
 
     def run_joint_quant(self, below, above, low, high, cats, quants, ids, n_cand, seed, inject=None, return_cand=False,
-                        want_lg=False, return_table=False, report_k=0, stream_word=None, shard=None):
+                        want_lg=False, return_table=False, report_k=0, stream_word=None, shard=None,
+                        precision='fp32'):
         """One joint stage over a group with quantised labels
         (tpe_joint_quant_run, include/tpe_hip.h "Quantised joint stage"):
         ``below`` / ``above``, ``low`` / ``high`` and ``cats`` the continuous and
@@ -1820,7 +1851,12 @@ class Engine(object):
         lattice indices; ``inject`` [C, Dc + Dk + Dq], candidates f32 [n_ids, C,
         Dc + Dk + Dq].  ``return_table`` (debug): also the two sides' tables
         log2 P as the device built them, f32 [K, sum V] each.  ``stream_word``: as
-        in ``run_joint_mixed``."""
+        in ``run_joint_mixed``.  ``precision`` 'fp64': as in ``run_joint_mixed``;
+        ``return_table`` then returns the float64 tables (no floor: -inf where
+        a bin's mass is exactly 0)."""
+        if self._joint_fp64(precision, report_k, shard, False, None, False):
+            return self._joint_solo('mq_f64', below, above, low, high, cats, quants, ids, n_cand, seed, inject,
+                                    return_cand, want_lg, 0, stream_word, None, return_table)
         return self._joint_solo('quant', below, above, low, high, cats, quants, ids, n_cand, seed, inject, return_cand,
                                 want_lg, report_k, stream_word, shard, return_table)
 

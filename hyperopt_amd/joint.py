@@ -286,10 +286,12 @@ def discrete_tables(p, s):
     return miss, bonus, corr
 
 
-def mixed_density_rows(w, mu, sigma, low, high, xc, ps, s):
-    """density_rows of a mixed side: f32 (mu [K, Dc], a [K, Dc], c [K]), the
-    float64 base, f32 cat [K, Dk] and the flat f32 (miss, bonus) [sum U_d].
-    c carries the prior rows' correction (category -1) before the shift."""
+def mixed_density_rows_f64(w, mu, sigma, low, high, xc, ps, s):
+    """mixed_density_rows before its rounding: float64 (mu [K, Dc], a [K, Dc],
+    c [K]), the base, f32 cat [K, Dk] and the flat float64 (miss, bonus)
+    [sum U_d]: what tpe_joint_mq_f64_run takes.  c carries the prior rows'
+    correction (category -1) before the shift.  No discrete dimension (``ps``
+    empty): density_rows_f64's values."""
     mu, sigma = np.asarray(mu, dtype=np.float64), np.asarray(sigma, dtype=np.float64)
     fa, fb, _ = _std_bounds(mu, sigma, np.asarray(low, dtype=np.float64)[None, :],
                             np.asarray(high, dtype=np.float64)[None, :])
@@ -304,10 +306,19 @@ def mixed_density_rows(w, mu, sigma, low, high, xc, ps, s):
         c = c + np.where(xc[:, d] < 0, corr, 0.0)
     fin = np.isfinite(c)
     shift = float(np.max(c[fin])) if fin.any() else 0.0
-    return (np.ascontiguousarray(mu, dtype=np.float32), np.ascontiguousarray(A_SCALE / sigma, dtype=np.float32),
-            np.ascontiguousarray(c - shift, dtype=np.float32), shift * math.log(2.0),
-            np.ascontiguousarray(xc, dtype=np.float32), np.concatenate(miss).astype(np.float32),
-            np.concatenate(bonus).astype(np.float32))
+    return (np.ascontiguousarray(mu, dtype=np.float64), np.ascontiguousarray(A_SCALE / sigma, dtype=np.float64),
+            np.ascontiguousarray(c - shift, dtype=np.float64), shift * math.log(2.0),
+            np.ascontiguousarray(xc, dtype=np.float32), np.concatenate(miss) if miss else np.zeros(0),
+            np.concatenate(bonus) if bonus else np.zeros(0))
+
+
+def mixed_density_rows(w, mu, sigma, low, high, xc, ps, s):
+    """density_rows of a mixed side: f32 (mu [K, Dc], a [K, Dc], c [K]), the
+    float64 base, f32 cat [K, Dk] and the flat f32 (miss, bonus) [sum U_d].
+    c carries the prior rows' correction (category -1) before the shift."""
+    mu, a, c, base, cat, miss, bonus = mixed_density_rows_f64(w, mu, sigma, low, high, xc, ps, s)
+    return (mu.astype(np.float32), a.astype(np.float32), c.astype(np.float32), base, cat, miss.astype(np.float32),
+            bonus.astype(np.float32))
 
 
 def mixed_sampler_rows(w, mu, sigma, low, high, ps, s):

@@ -14,6 +14,9 @@ The dimension limits by entry point (``_check_dims``):
   'mixed'    run_joint_mixed       Dk >= 1, Dc + Dk <= JOINT_MAX_DIMS
   'wide_mixed' run_joint_wide_mixed  1 <= Dk <= JOINT_WIDE_MAX_CAT, Dq = 0, 1 <= Dc + Dk <= JOINT_WIDE_MAX_DIMS
   'quant'    run_joint_quant       Dq >= 1, Dc <= JOINT_QUANT_MAX_CONT, Dk <= JOINT_QUANT_MAX_DISC
+  'mq_f64'   run_joint_mixed / run_joint_quant(precision='fp64')  Dk + Dq >= 1; as 'quant' with a quantised
+                                   dimension, else as 'mixed'; the group's f32 rows as those entries make them,
+                                   and beside them the float64 density rows, category tables and the centres
   'wide_quant' run_joint_wide_quant  Dq >= 1, Dc >= 1, Dk <= JOINT_WIDE_MAX_CAT, 2 <= Dc + Dk + Dq <= JOINT_WIDE_MAX_DIMS
   'segment'  run_joint_segments    a continuous group 1 <= Dc <= JOINT_MAX_DIMS; one with discrete or
                                    quantised parts Dc <= JOINT_MSEG_MAX_CONT, Dk <= JOINT_MSEG_MAX_CAT
@@ -56,8 +59,17 @@ _F64_ROWS = tuple((key, field, buf + '64', np.float64, part) if key.split('_')[-
 assert sum(row[3] is np.float64 for row in _F64_ROWS) == 7      # the six density rows and the sampler's cum
 
 
+# the float64 mixed stage's rows (entry 'mq_f64'): the group's rows as 'mixed' / 'quant' hand them over, then the
+# float64 density rows and category tables under the struct's *64 fields, in buffers of their own
+_MQ_F64_MORE = tuple((s + f + '64', s + f + '64', s + f + '64', np.float64, part) for s in SIDES for f, part in (
+    ('_mu', 'cont'), ('_a', 'cont'), ('_c', None), ('_miss', 'cat'), ('_bonus', 'cat')))
+
+
 def group_rows_present(r):
     """ROWS without the parts the group ``r`` (group_rows) does not have."""
+    if r.get('mq_f64'):
+        return _PRESENT[r['Dk'] > 0, r['Dq'] > 0] + tuple(row for row in _MQ_F64_MORE
+                                                          if row[4] != 'cat' or r['Dk'] > 0)
     return _F64_ROWS if r.get('f64') else _PRESENT[r['Dk'] > 0, r['Dq'] > 0]
 
 
@@ -74,6 +86,10 @@ def seg_parts(m):
 
 
 def _check_dims(entry, Dc, Dk, Dq):
+    if entry == 'mq_f64':
+        if Dk + Dq == 0:
+            raise ValueError('joint stage: no discrete or quantised dimension, use run_joint')
+        entry = 'quant' if Dq else 'mixed'
     if entry == 'mixed' and Dk == 0:
         raise ValueError('joint stage: no discrete dimension, use run_joint')
     if entry == 'quant' and Dq == 0:
@@ -167,7 +183,16 @@ def group_rows(below, above, low, high, cats=(), quants=(), entry='segment'):
         for col, U in zip(cols, ups):
             if col.min() < -1 or col.max() >= U:
                 raise ValueError('joint stage: a component category outside [-1, %d)' % U)
-        if Dk:
+        if entry == 'mq_f64':                        # the rows before their rounding, and the centres
+            xc = np.stack(cols, axis=1) if Dk else np.zeros((len(w), 0), dtype=np.int64)
+            (r[name + '_mu64'], r[name + '_a64'], r[name + '_c64'], base, cat, r[name + '_miss64'],
+             r[name + '_bonus64']) = J.mixed_density_rows_f64(w, mu, sigma, low, high, xc, ps, s_side[i])
+            r['mq_f64'], r['centre'] = True, J.expansion_centres(low, high, mu[0])
+        if Dk and entry == 'mq_f64':                 # the 'mixed' rows: the rounding of those (joint.mixed_density_rows)
+            for f in ('_mu', '_a', '_c', '_miss', '_bonus'):
+                r[name + f] = r[name + f + '64'].astype(np.float32)
+            r[name + '_base'], r[name + '_cat'] = base, cat
+        elif Dk:
             (r[name + '_mu'], r[name + '_a'], r[name + '_c'], r[name + '_base'], r[name + '_cat'], r[name + '_miss'],
              r[name + '_bonus']) = J.mixed_density_rows(w, mu, sigma, low, high, np.stack(cols, axis=1), ps, s_side[i])
         elif f64:                                    # the same rows before their rounding, and the centres

@@ -848,7 +848,7 @@ def suggest(new_ids, domain, trials, seed,
             shard_grid=None, joint=False, joint_discrete=False, joint_quantized=False, joint_wide=False,
             joint_branches=False, joint_branches_mixed=False, joint_branches_wide=False, joint_shard=None,
             joint_precision='fp32', joint_precision_wide=False, joint_precision_branches=False,
-            joint_wide_mixed=False, joint_wide_quantized=False, joint_liar=False):
+            joint_precision_mixed=False, joint_wide_mixed=False, joint_wide_quantized=False, joint_liar=False):
     new_ids = list(new_ids)
     if not new_ids:
         return []
@@ -858,7 +858,8 @@ def suggest(new_ids, domain, trials, seed,
     if liar_mode:
         _joint_liar_check(joint, joint_shard, mode=liar_mode, joint_branches=joint_branches)
     fp64 = _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, None, joint_precision_wide,
-                                  joint_wide, joint_precision_branches, joint_branches)
+                                  joint_wide, joint_precision_branches, joint_branches,
+                                  _mixed_f64(joint_precision_mixed, joint_discrete, joint_quantized))
     if ((joint is not False and joint is not None) or joint_discrete or joint_quantized or joint_wide or joint_branches
             or joint_branches_mixed or joint_branches_wide or joint_wide_mixed or joint_wide_quantized):
         # (argument errors first: no device use, no startup draw)
@@ -872,7 +873,8 @@ def suggest(new_ids, domain, trials, seed,
             _wide_quant_liar_check(plan[0], liar_mode)
         if fp64:
             _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, plan, joint_precision_wide,
-                                   joint_wide, joint_precision_branches, joint_branches)
+                                   joint_wide, joint_precision_branches, joint_branches,
+                                   _mixed_f64(joint_precision_mixed, joint_discrete, joint_quantized))
     t0 = time.time()
     hist = _history.extract(domain, trials)
     if logger.isEnabledFor(logging.INFO):
@@ -893,7 +895,8 @@ def suggest(new_ids, domain, trials, seed,
                               joint_wide_mixed=joint_wide_mixed,
                               joint_wide_quantized=joint_wide_quantized, joint_liar=joint_liar,
                               joint_precision=joint_precision, joint_precision_wide=joint_precision_wide,
-                              joint_precision_branches=joint_precision_branches)
+                              joint_precision_branches=joint_precision_branches,
+                              joint_precision_mixed=joint_precision_mixed)
     logger.info('tpe.suggest took %f seconds', time.time() - t0)
     return rand.docs_from_choices(new_ids, domain, trials, choices)
 
@@ -936,8 +939,8 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
                     shard_ids=None, shard_labels=None, shard_grid=None, joint=False, joint_discrete=False,
                     joint_quantized=False, joint_wide=False, joint_branches=False, joint_branches_mixed=False,
                     joint_branches_wide=False, joint_shard=None, joint_precision='fp32', joint_precision_wide=False,
-                    joint_precision_branches=False, joint_wide_mixed=False, joint_wide_quantized=False,
-                    joint_liar=False):
+                    joint_precision_branches=False, joint_precision_mixed=False, joint_wide_mixed=False,
+                    joint_wide_quantized=False, joint_liar=False):
     """The suggest core on a structure-of-arrays history (``history.History``):
     per new id a {label: value or None} dict.  ``suggest`` wraps it with the
     Trials document layout; columnar callers (and bench.py's large configs)
@@ -1159,7 +1162,22 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
     with a branch group that holds a discrete or quantised label
     (``joint_branches_mixed``) or more than 16 labels
     (``joint_branches_wide``), with ``joint_shard`` or ``joint_liar`` it raises
-    ValueError; joint_candidate_report does not take it."""
+    ValueError; joint_candidate_report does not take it.
+
+    ``joint_precision_mixed=True`` (with ``joint_precision='fp64'`` and
+    ``joint_discrete`` and/or ``joint_quantized``): a root group of at most 16
+    labels that holds discrete or quantised labels, which the mixed or the
+    quantised joint stage takes, is scored in float64 too (DESIGN.md "Float64
+    mixed joint stage", Engine.run_joint_mixed / run_joint_quant with
+    ``precision='fp64'``), over that fp32 stage's pool bit for bit (continuous
+    coordinates, category indices and lattice indices); the joined values come
+    back with the fp32 stages' types.  A root group of continuous labels goes
+    where ``joint_precision='fp64'`` sends it, and every other label is the same
+    bytes as without the keyword.  Without ``joint_precision='fp64'``, without
+    both of ``joint_discrete`` / ``joint_quantized``, for a wide group (more than
+    16 labels) or a branch group that holds a discrete or quantised label, with
+    ``joint_shard`` or ``joint_liar`` it raises ValueError;
+    joint_candidate_report does not take it."""
     if sampler not in ('philox', 'replay'):
         raise ValueError("sampler must be 'philox' or 'replay'")
     if joint_shard is not None:
@@ -1168,7 +1186,8 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
     if liar_mode:
         _joint_liar_check(joint, joint_shard, mode=liar_mode, joint_branches=joint_branches)
     fp64 = _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, None, joint_precision_wide,
-                                  joint_wide, joint_precision_branches, joint_branches)
+                                  joint_wide, joint_precision_branches, joint_branches,
+                                  _mixed_f64(joint_precision_mixed, joint_discrete, joint_quantized))
     group, branch_groups = None, []
     if ((joint is not False and joint is not None) or joint_discrete or joint_quantized or joint_wide or joint_branches
             or joint_branches_mixed or joint_branches_wide or joint_wide_mixed or joint_wide_quantized):
@@ -1184,7 +1203,8 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
             _wide_quant_liar_check(group, liar_mode)
         if fp64:
             _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, (group, branch_groups),
-                                   joint_precision_wide, joint_wide, joint_precision_branches, joint_branches)
+                                   joint_precision_wide, joint_wide, joint_precision_branches, joint_branches,
+                                   _mixed_f64(joint_precision_mixed, joint_discrete, joint_quantized))
     if sum(a is not None for a in (shard, shard_ids, shard_labels, shard_grid)) > 1:
         raise ValueError('shard, shard_ids, shard_labels and shard_grid are exclusive: one shard axis per suggest')
     if (shard_ids is not None or shard_labels is not None or shard_grid is not None) and sampler == 'replay':
@@ -1219,8 +1239,14 @@ def _joint_liar_mode(joint_liar):
                      'joint_branches (or False): %r' % (joint_liar,))
 
 
+def _mixed_f64(joint_precision_mixed, joint_discrete, joint_quantized):
+    """The joint_precision_mixed keyword for _joint_precision_check: None (off),
+    else whether one of joint_discrete / joint_quantized goes with it."""
+    return bool(joint_discrete or joint_quantized) if joint_precision_mixed else None
+
+
 def _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, plan=None, wide_f64=False, joint_wide=False,
-                           branches_f64=False, joint_branches=False):
+                           branches_f64=False, joint_branches=False, mixed_f64=None):
     """Whether ``joint_precision`` asks for the float64 stage; ValueError for a
     value other than 'fp32' / 'fp64' and where 'fp64' does not apply: without
     ``joint``, with ``joint_shard`` or ``joint_liar``, and (``plan`` =
@@ -1232,9 +1258,20 @@ def _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, plan=
     lets continuous branch groups of at most TPE_JOINT_MAX_DIMS labels through,
     with or without a root group; without 'fp64' or ``joint_branches``, and for
     a branch group with a discrete or quantised label or more labels, it
+    raises.  ``mixed_f64`` (_mixed_f64, the joint_precision_mixed keyword) lets
+    a root group of at most TPE_JOINT_MAX_DIMS labels with discrete or
+    quantised ones through; without 'fp64', without joint_discrete /
+    joint_quantized, and for a wide or a branch group with such a label it
     raises.  Touches no device."""
     if joint_precision not in ('fp32', 'fp64'):
         raise ValueError("joint_precision must be 'fp32' or 'fp64': %r" % (joint_precision,))
+    if mixed_f64 is not None and joint_precision != 'fp64':
+        raise ValueError("joint_precision_mixed=True needs joint_precision='fp64': it only names the mixed and "
+                         'quantised root groups that keyword scores in float64; without it the mixed and quantised '
+                         'joint stages score in fp32')
+    if mixed_f64 is False:
+        raise ValueError('joint_precision_mixed=True needs joint_discrete=True or joint_quantized=True: it only scores '
+                         'the groups those keywords join in float64; the float64 joint stage takes continuous labels')
     if branches_f64 and joint_precision != 'fp64':
         raise ValueError("joint_precision_branches=True needs joint_precision='fp64': it only names the branch groups "
                          'that keyword scores in float64; without it the segmented joint stage scores in fp32')
@@ -1261,6 +1298,23 @@ def _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, plan=
     if plan is None:
         return True
     group, branch_groups = plan
+    if mixed_f64:
+        for rows in branch_groups:
+            other = [r.label for r in rows if r.dist not in _joint.JOINT_DISTS]
+            if other:
+                raise ValueError('joint_precision_mixed=True does not reach branch groups: %r is discrete or quantised '
+                                 '(joint_branches_mixed), and the mixed segmented joint stage scores in fp32 only'
+                                 % other[0])
+        other = [r.label for r in group or () if r.dist not in _joint.JOINT_DISTS]
+        if other and _takes_wide_quant(group):       # (joint_wide_quantized let it through)
+            raise ValueError('joint_precision_mixed=True takes a root group within the quantised joint stage\'s limits '
+                             '(at most %d labels, %d continuous and %d discrete ones): the wide quantised joint stage '
+                             'scores in fp32 only' % (TPE_JOINT_MAX_DIMS, N.JOINT_QUANT_MAX_CONT,
+                                                      N.JOINT_QUANT_MAX_DISC))
+        if other and len(group) > TPE_JOINT_MAX_DIMS:
+            raise ValueError('joint_precision_mixed=True takes a root group of at most %d labels, not %d: %r is '
+                             'discrete or quantised, and the wide mixed and wide quantised joint stages score in fp32 '
+                             'only' % (TPE_JOINT_MAX_DIMS, len(group), other[0]))
     if branch_groups and not branches_f64:
         raise ValueError("joint_precision='fp64' does not combine with branch groups (joint_branches): the segmented "
                          'joint stage scores in fp32 only')
@@ -1279,6 +1333,8 @@ def _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, plan=
     if group is None:
         raise ValueError("joint_precision='fp64' needs a root group: there is none")
     other = [r.label for r in group if r.dist not in _joint.JOINT_DISTS]
+    if other and mixed_f64:
+        return True
     if other:
         raise ValueError("joint_precision='fp64' needs a root group of continuous labels only: %r is discrete or "
                          'quantised, and the mixed and quantised joint stages score in fp32 only' % other[0])

@@ -1624,6 +1624,111 @@ int tpe_joint_quant_run(const tpe_joint_quant_args* args, tpe_joint_record* reco
 int tpe_joint_quant_profile(double* table_ms);
 
 /* ------------------------------------------------------------------------
+ * Float64 mixed joint stage (tpe_joint.hip; additive to ABI 24):
+ * tpe_joint_mixed_run / tpe_joint_quant_run with the scoring in f64, as
+ * tpe_joint_f64_run is to tpe_joint_run.  The model, the sampler rows (samp,
+ * samp_cum, below_cat, below_h, cat_cum, quant_edges, quant_samp), the Philox
+ * streams, the kernel coordinate order, the score, the winner's order,
+ * tpe_joint_record, the chunk records and their merge are those stages', and a
+ * candidate is the same f32 vector bit for bit (continuous coordinates,
+ * category indices and lattice indices): the same seed, ids and stream word
+ * give the same pool.  The limits are theirs: n_dims + n_cat <=
+ * TPE_JOINT_MAX_DIMS without a quantised label; with one n_dims <= 8, n_cat <=
+ * 4, n_quant <= TPE_JOINT_MAX_QUANT.
+ *
+ * tpe_joint_mq_f64_args holds the fields of tpe_joint_quant_args at the same
+ * offsets; of these the f32 density rows (below_mu .. above_c), the f32
+ * miss / bonus tables and quant_table / quant_table_bytes are NOT read (they may
+ * be null).  Then, all f64, device:
+ *   below_mu64 .. above_c64   the density rows unrounded (mu[K * n_dims], a, c[K];
+ *                             c carries the prior rows' correction, shifted to
+ *                             max 0, as the mixed stage's c before its rounding)
+ *   centre[d]                 as tpe_joint_f64_args (the continuous labels)
+ *   below_miss64 .. above_bonus64   the mixed stage's tables unrounded [total]
+ *   quant_table64             caller-owned workspace of
+ *                             tpe_joint_mq_f64_table_bytes(k_below, k_above, sum V)
+ *                             bytes: the below side's [sum V][S_below], then the
+ *                             above side's [sum V][S_above], S = K rounded up to
+ *                             a multiple of 16 (the columns past K hold zeros).
+ * k_joint_qtable_f64 (one launch per side) stores log2 P_kd(i) as the f64 it
+ * evaluates: no TPE_JOINT_QFLOOR, an exactly-zero mass is -inf (the 37.5-sigma
+ * tail rule of the quantised stage holds).  A -inf entry makes the component's
+ * term -inf, which adds exactly 0 to the sum over k; the prior row's entries
+ * are finite, so every candidate keeps a finite sum.
+ *
+ * The continuous part is scored as in tpe_joint_f64_run (phi . psi_k on
+ * v_mfma_f64_16x16x4_f64, the running (max, sum) pairs, the vote at 100
+ * binades); before the vote every result gains sum_d [v_d = x_kd] bonus_d(v_d)
+ * and sum_q T_q[i_q][k], and the candidate's sum_d miss_d(v_d) is added after
+ * the sum over k.  n_dims = 0 is served (phi is the constant alone).  No
+ * atomics: the same call twice gives the same bytes.
+ *
+ * tpe_joint_mq_f64_run returns TPE_E_ARG before any launch (no device needed),
+ * in this order, for: null args; n_quant outside [0, TPE_JOINT_MAX_QUANT];
+ * n_cat < 0; (n_cat = 0 and n_quant = 0 forward to tpe_joint_f64_run on the
+ * shared fields, n_dims = 1 included: the same bytes); the coordinate counts
+ * outside the limits above; n_cand, n_ids, k_below, k_above < 1; a null f64
+ * density row; TPE_JOINT_INJECT without candidates; a null sampler row; null ids
+ * / records; a null category row or f64 category table, a U_d, total or cat_off
+ * out of range (as tpe_joint_mixed_run); a V_d, total or quant_edge_off out of
+ * range, a null quantised row (as tpe_joint_quant_run); a null f64 table; a
+ * table workspace smaller than tpe_joint_mq_f64_table_bytes says; a centre that
+ * is not finite; scratch smaller than tpe_joint_mq_f64_scratch_bytes(n_ids,
+ * n_cand).  tpe_joint_profile serves this stage; tpe_joint_mq_f64_profile reads
+ * the table launches' time of a profiled run.
+ * ---------------------------------------------------------------------- */
+typedef struct tpe_joint_mq_f64_args {
+  int32_t n_dims, n_cand, n_ids, flags;   /* as tpe_joint_quant_args ... */
+  int32_t k_below, k_above;
+  uint32_t stream_word;
+  int32_t n_cat;
+  uint64_t seed;
+  const float *below_mu, *below_a, *below_c;    /* (not read) */
+  const float *above_mu, *above_a, *above_c;    /* (not read) */
+  double below_base, above_base;
+  const double* samp_cum;
+  const float* samp;
+  const int64_t* ids;
+  const float* inject;
+  double low[TPE_JOINT_MAX_DIMS], high[TPE_JOINT_MAX_DIMS];
+  int32_t cat_upper[TPE_JOINT_MAX_DIMS];
+  int32_t cat_off[TPE_JOINT_MAX_DIMS];
+  const float *below_cat, *above_cat;
+  const float *below_miss, *below_bonus;        /* (not read) */
+  const float *above_miss, *above_bonus;        /* (not read) */
+  const double* below_h;
+  const double* cat_cum;
+  int32_t n_quant;
+  int32_t n_edges;
+  int32_t quant_v[TPE_JOINT_MAX_QUANT];
+  int32_t quant_edge_off[TPE_JOINT_MAX_QUANT];
+  const double* quant_edges;
+  const double *below_qmu, *below_qsigma;
+  const double *above_qmu, *above_qsigma;
+  const float* quant_samp;
+  float* quant_table;                           /* (not read) */
+  uint64_t quant_table_bytes;                   /* ... up to here */
+  const double *below_mu64, *below_a64, *below_c64;
+  const double *above_mu64, *above_a64, *above_c64;
+  double centre[TPE_JOINT_MAX_DIMS];      /* entries from n_dims on: ignored */
+  const double *below_miss64, *below_bonus64;   /* device [total] */
+  const double *above_miss64, *above_bonus64;
+  double* quant_table64;                  /* device workspace */
+  uint64_t quant_table64_bytes;
+} tpe_joint_mq_f64_args;
+
+int tpe_joint_mq_f64_scratch_bytes(int32_t n_ids, int32_t n_cand, uint64_t* bytes);
+int tpe_joint_mq_f64_table_bytes(int32_t k_below, int32_t k_above, int32_t total_bins, uint64_t* bytes);
+
+/* records, cand, l_out, g_out, scratch and stream as tpe_joint_quant_run */
+int tpe_joint_mq_f64_run(const tpe_joint_mq_f64_args* args, tpe_joint_record* records, float* cand, double* l_out,
+                         double* g_out, void* scratch, uint64_t scratch_bytes, void* stream);
+
+/* Profiling only: as tpe_joint_quant_profile, for the two k_joint_qtable_f64
+ * launches of the last profiled tpe_joint_mq_f64_run with a quantised label. */
+int tpe_joint_mq_f64_profile(double* table_ms);
+
+/* ------------------------------------------------------------------------
  * Wide quantised joint stage (tpe_joint.hip; additive to ABI 24): a group of
  * n_dims >= 1 continuous labels, 0 <= n_cat <= TPE_JOINT_WIDE_MAX_CAT discrete
  * ones and 1 <= n_quant <= TPE_JOINT_MAX_QUANT quantised ones, n_dims + n_cat +

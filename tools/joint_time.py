@@ -150,7 +150,22 @@ ranges, the evaluations per second, the ratio to the fp32 kernel at the same D
 and to the narrow float64 stage's rate; and, untimed, the worst |l32 - l64| and
 |g32 - g64| over the whole shared pool in units of the fp32 tolerance at D = 20
 and 64, on the flat space and on one whose trials are clustered so that every
-bandwidth is psig / 100.  --out defaults to profiles/joint_wide_fp64_time.jsonl."""
+bandwidth is psig / 100.  --out defaults to profiles/joint_wide_fp64_time.jsonl.
+
+--mixed --fp64 / --quant --fp64: the float64 mixed stage (DESIGN.md "Float64
+mixed joint stage") on --mixed's group (3 continuous labels + one hp.choice of
+4) or --quant's two (3 continuous + one hp.quniform of 32 and of 256 values).
+Per pair, alternating in one process: Engine.run_joint_mixed / run_joint_quant
+with precision 'fp32' then 'fp64' for each group, then Engine.run_joint(
+precision='fp64') over the three continuous labels alone (k_joint_f64_chunk<4>:
+what the categories and the lattice add is read off against it).  Each chunk
+kernel by its own events (tpe_joint_profile), the two table launches by theirs
+(tpe_joint_quant_profile, tpe_joint_mq_f64_profile).  The line carries per run
+the medians and ranges, the ratio to the fp32 kernel of the same group and to
+the continuous float64 kernel; and, untimed, per group the worst |l32 - l64| and
+|g32 - g64| over the whole shared pool in units of the fp32 tolerance, whether
+the winners differ, and how many candidates the float64 stage scores above the
+fp32 winner.  --out defaults to profiles/joint_mq_fp64_time.jsonl."""
 import argparse
 import ctypes
 import json
@@ -968,6 +983,106 @@ def main_fp64(args):
     return 0
 
 
+def main_mq_fp64(args):
+    import torch
+    from hyperopt_amd import _native as N, history as H, joint as J
+    from hyperopt_amd.engine import get_engine
+
+    eng = get_engine(None, 'fp32')
+    lib = eng.lib
+    C = args.cand
+    ids = np.array([args.history], dtype=np.int64)
+    groups = {}
+    if args.mixed:
+        domain, hist = make_mixed_history(args.history)
+        t = domain.table
+        crows = [r for r in t.rows if J.eligible(r)]
+        below = H.split_below(hist, 0.25)
+        groups['mixed4'] = J.fit_mixed_model(crows, [r for r in t.rows if J.eligible_discrete(r, t)], hist, below, 1.0)
+        cont3 = J.fit_model(crows, hist, below, 1.0)
+    else:
+        for V in (32, 256):
+            domain, hist = make_quant_history(args.history, V)
+            t = domain.table
+            crows = [r for r in t.rows if J.eligible(r)]
+            below = H.split_below(hist, 0.25)
+            groups['quant%d' % V] = J.fit_quant_model(crows, [], [t.by_label['q3']], hist, below, 1.0)
+        cont3 = J.fit_model(crows, hist, below, 1.0)
+
+    def run(name, precision, **kw):
+        if name == 'continuous3':
+            return eng.run_joint(cont3.below, cont3.above, cont3.low, cont3.high, ids, C, SEED, precision=precision, **kw)
+        m = groups[name]
+        if args.mixed:
+            return eng.run_joint_mixed(m.below[:3], m.above[:3], m.low, m.high, m.cats(), ids, C, SEED,
+                                       precision=precision, **kw)
+        return eng.run_joint_quant(m.below[:3], m.above[:3], m.low, m.high, [], m.quants(), ids, C, SEED,
+                                   precision=precision, **kw)
+
+    def kernel_ms(name, precision):
+        ms2, tms = (ctypes.c_double * 2)(), ctypes.c_double(0.0)
+        torch.cuda.synchronize()
+        N.check(lib.tpe_joint_profile(1, None), lib, 'tpe_joint_profile')
+        run(name, precision)
+        if name.startswith('quant'):                     # the two table launches, by their own events
+            prof = 'tpe_joint_mq_f64_profile' if precision == 'fp64' else 'tpe_joint_quant_profile'
+            N.check(getattr(lib, prof)(ctypes.byref(tms)), lib, prof)
+        N.check(lib.tpe_joint_profile(0, ms2), lib, 'tpe_joint_profile')
+        return ms2[0], ms2[1], tms.value
+
+    # a pair is the fp32 then the float64 stage of one group; the continuous part alone in float64 closes the round
+    routes = [(name, p) for name in groups for p in ('fp32', 'fp64')] + [('continuous3', 'fp64')]
+    for _ in range(args.warmup):
+        for r in routes:
+            run(*r)
+    ms = dict((r, []) for r in routes)
+    for i in range(args.pairs):
+        for r in routes:
+            ms[r].append(kernel_ms(*r))
+        print('pair %d: %s' % (i, ', '.join('%s %s %.3f ms' % (r + (ms[r][-1][0],)) for r in routes)), file=sys.stderr,
+              flush=True)
+
+    # (untimed) both stages' l and g over the whole shared pool, the float64 stage as the reference
+    def err(a, ref):
+        return float(np.max(np.abs(a - ref) / np.maximum(1.0, np.abs(ref)))) / 1e-5
+    dist = {}
+    for name in groups:
+        r32, c32, l32, g32 = run(name, 'fp32', return_cand=True, want_lg=True)
+        r64, c64, l64, g64 = run(name, 'fp64', return_cand=True, want_lg=True)
+        assert c32.tobytes() == c64.tobytes()
+        dist[name] = dict(l_err_over_fp32_tol=err(l32, l64), g_err_over_fp32_tol=err(g32, g64),
+                          winners_differ=int((r32['global_idx'] != r64['global_idx']).sum()),
+                          fp32_winner_score_rank_in_fp64=int(((l64 - g64)[0] > (l64 - g64)[0, r32['global_idx'][0]]).sum()))
+
+    def stat(r, j=0):
+        x = [q[j] for q in ms[r]]
+        return dict(median=float(np.median(x)), min=min(x), max=max(x), all=x)
+    yard = stat(('continuous3', 'fp64'))['median']
+    runs = {}
+    for r in routes:
+        name, prec = r
+        m = cont3 if name == 'continuous3' else groups[name]
+        quant = name.startswith('quant')
+        kernel = ('k_joint_f64_chunk<4>' if name == 'continuous3' else 'k_joint_mq_f64_chunk<4>' if prec == 'fp64'
+                  else 'k_joint_quant_chunk<4, 0, 1>' if quant else 'k_joint_mixed_chunk<4, 1>')
+        runs['%s_%s' % r] = dict(
+            kernel=kernel, k_below=len(m.below[0]), k_above=len(m.above[0]),
+            lattice_values=[lat[1] for lat in getattr(m, 'lattices', ())], chunk_ms=stat(r),
+            merge_ms=stat(r, 1)['median'], table_ms=stat(r, 2) if quant else None,
+            ratio_to_fp32_kernel=stat(r)['median'] / stat((name, 'fp32'))['median'] if name in groups else None,
+            ratio_to_continuous3_fp64=stat(r)['median'] / yard if yard > 0 else None)
+    which = '--mixed' if args.mixed else '--quant'
+    line = dict(tool='joint_time %s --fp64' % which, history=args.history, n_cand=C, pairs=args.pairs, runs=runs,
+                fp32_to_fp64_distance=dist, gpu=torch.cuda.get_device_name(0))
+    text = json.dumps(line)
+    print(text)
+    out = args.out or os.path.join(ROOT, 'profiles', 'joint_mq_fp64_time.jsonl')
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, 'a') as f:
+        f.write(text + '\n')
+    return 0
+
+
 def make_liar_mixed_history(n):
     from hyperopt_amd import base, history as H, hp
     space = {'x0': hp.uniform('x0', -5, 5), 'x1': hp.loguniform('x1', -3, 2), 'x2': hp.normal('x2', 0, 2),
@@ -1259,6 +1374,8 @@ def main():
     ap.add_argument('--batch', type=int, default=64)
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
+    if (args.mixed or args.quant) and args.fp64:
+        return main_mq_fp64(args)
     if args.mixed:
         return main_mixed(args)
     if args.quant:
