@@ -351,6 +351,40 @@ class JointMSegArgs(ctypes.Structure):
     _fields_ = JointSegArgs._fields_ + [('quant_table', ctypes.c_void_p), ('quant_table_bytes', ctypes.c_uint64)]
 
 
+class JointMSegF64(ctypes.Structure):
+    """tpe_joint_mseg_f64: the device descriptor of one group of a tpe_joint_mseg_f64_run (tpe_joint_mseg's fields
+    first; its f32 density-row, f32 table and `table` offsets are not read)."""
+    _fields_ = JointMSeg._fields_ + [(side + f + '64', ctypes.c_int64) for side in ('below', 'above')
+                                     for f in ('_mu', '_a', '_c')] + [
+        ('centre', ctypes.c_double * JOINT_MAX_DIMS),
+        ('below_miss64', ctypes.c_int64), ('below_bonus64', ctypes.c_int64),
+        ('above_miss64', ctypes.c_int64), ('above_bonus64', ctypes.c_int64),
+        ('psi', ctypes.c_int64), ('table64', ctypes.c_int64)]
+
+
+# numpy mirror of tpe_joint_mseg_f64
+JOINT_MSEG_F64_DTYPE = np.dtype(JOINT_MSEG_DTYPE.descr + [(side + f + '64', '<i8') for side in ('below', 'above')
+                                                          for f in ('_mu', '_a', '_c')] + [
+    ('centre', '<f8', (JOINT_MAX_DIMS,)), ('below_miss64', '<i8'), ('below_bonus64', '<i8'),
+    ('above_miss64', '<i8'), ('above_bonus64', '<i8'), ('psi', '<i8'), ('table64', '<i8')])
+assert JOINT_MSEG_F64_DTYPE.itemsize == ctypes.sizeof(JointMSegF64) == 688
+
+
+class JointMSegF64Args(ctypes.Structure):
+    """tpe_joint_mseg_f64_args: one tpe_joint_mseg_f64_run (tpe_joint_seg_args' fields, then the f64 table
+    workspace)."""
+    _fields_ = JointSegArgs._fields_ + [('quant_table64', ctypes.c_void_p), ('quant_table64_bytes', ctypes.c_uint64)]
+
+
+def mseg_f64_steps(n_dims, n_cat, n_quant):
+    """NI of a group of the float64 mixed segmented stage: ``f64_steps`` for a continuous group; with discrete or
+    quantised labels the padded width of its ``n_dims`` continuous ones is 1, 2, 4 or 8 (none: 1)."""
+    if n_cat + n_quant == 0:
+        return f64_steps(n_dims)
+    dp = next(p for p in (1, 2, 4, 8) if n_dims <= p)
+    return (2 * dp + 1 + 3) // 4
+
+
 # tpe_joint_run_shard (include/tpe_hip.h "Sharded joint stage"): the stage whose args and records a call takes
 JOINT_STAGE_RUN, JOINT_STAGE_WIDE, JOINT_STAGE_MIXED, JOINT_STAGE_QUANT, JOINT_STAGE_SEG, JOINT_STAGE_MSEG = range(6)
 # the stage of each stage entry point, by its name
@@ -628,7 +662,9 @@ EXPORTS = ('tpe_abi_version', 'tpe_last_error', 'tpe_device_count', 'tpe_tile_si
            'tpe_joint_wide_quant_scratch_bytes', 'tpe_joint_wide_quant_run', 'tpe_joint_wide_quant_profile',
            'tpe_joint_seg_scratch_bytes', 'tpe_joint_seg_run', 'tpe_joint_seg_f64_scratch_bytes',
            'tpe_joint_seg_f64_run', 'tpe_joint_seg_f64_profile', 'tpe_joint_mseg_scratch_bytes',
-           'tpe_joint_mseg_table_bytes', 'tpe_joint_mseg_run', 'tpe_joint_wide_seg_scratch_bytes',
+           'tpe_joint_mseg_table_bytes', 'tpe_joint_mseg_run', 'tpe_joint_mseg_f64_scratch_bytes',
+           'tpe_joint_mseg_f64_table_bytes', 'tpe_joint_mseg_f64_run', 'tpe_joint_mseg_f64_profile',
+           'tpe_joint_wide_seg_scratch_bytes',
            'tpe_joint_wide_seg_run', 'tpe_joint_report_scratch_bytes',
            'tpe_joint_report', 'tpe_joint_report_profile', 'tpe_joint_run_shard', 'tpe_joint_liar_scratch_bytes',
            'tpe_joint_liar', 'tpe_joint_liar_mixed_scratch_bytes', 'tpe_joint_liar_mixed',
@@ -818,6 +854,14 @@ def load(path=LIB_PATH):
     lib.tpe_joint_mseg_table_bytes.restype = ctypes.c_int
     lib.tpe_joint_mseg_run.argtypes = [ctypes.POINTER(JointMSegArgs), P, P, P, P, P, ctypes.c_uint64, P]
     lib.tpe_joint_mseg_run.restype = ctypes.c_int
+    lib.tpe_joint_mseg_f64_scratch_bytes.argtypes = [P, I32, I32, I32, ctypes.POINTER(ctypes.c_uint64)]
+    lib.tpe_joint_mseg_f64_scratch_bytes.restype = ctypes.c_int
+    lib.tpe_joint_mseg_f64_table_bytes.argtypes = [P, I32, ctypes.POINTER(ctypes.c_uint64)]
+    lib.tpe_joint_mseg_f64_table_bytes.restype = ctypes.c_int
+    lib.tpe_joint_mseg_f64_run.argtypes = [ctypes.POINTER(JointMSegF64Args), P, P, P, P, P, ctypes.c_uint64, P]
+    lib.tpe_joint_mseg_f64_run.restype = ctypes.c_int
+    lib.tpe_joint_mseg_f64_profile.argtypes = [P, P]
+    lib.tpe_joint_mseg_f64_profile.restype = ctypes.c_int
     lib.tpe_joint_run_shard.argtypes = [I32, P, ctypes.POINTER(JointShard), P, P, P, P, P, ctypes.c_uint64, P]
     lib.tpe_joint_run_shard.restype = ctypes.c_int
     lib.tpe_joint_report_scratch_bytes.argtypes = [I32, I32, I32, ctypes.POINTER(ctypes.c_uint64)]

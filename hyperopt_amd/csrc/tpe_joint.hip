@@ -3155,6 +3155,513 @@ __global__ __launch_bounds__(kThreads) void k_joint_seg_f64_chunk(const SegF64K 
   for (int d = 0; d < TPE_JOINT_MAX_DIMS; ++d) q.rec->z[d] = d < DP ? (double)bz[d < DP ? d : 0] : 0.0;
 }
 
+// -------------------------------------------- segmented float64 mixed stage
+// The float64 mixed stage over the (id, group) problems of MANY groups
+// (include/tpe_hip.h "Float64 mixed segmented joint stage"): the model and the
+// pass of k_joint_mq_f64_chunk in the segmented form of the stage above.  Per
+// call and segment psi (k_joint_mseg_f64_psi) and, for a quantised segment, the
+// two sides' f64 lattice tables (k_joint_mseg_f64_qtable) are built once; the
+// scoring workgroups copy psi tiles from L2 and read the table where it lies.
+//
+// What k_joint_mseg_f64_chunk does differently from the solo kernel between the
+// MFMA chain and the vote (the values subtracted, and their order, are the solo
+// kernel's, so a result's bytes are):
+//   component side  a tile's categories are staged as integer codes (category +
+//     2; past the side's end -1) beside the bonus a match subtracts,
+//     bonus_d(max(x_kd, 0)): a match fixes the candidate's category, so the
+//     bonus is the component's and no table lookup is left per result
+//   candidate side  each thread packs its candidate once a pass into three
+//     32-bit words in LDS: the 4 category slots as 16-bit codes (category + 2 of
+//     an integer category in [-1, 255], else 0: matches no component), the 4
+//     lattice slots as bytes (the clamped index); a lane loads the words of its
+//     16 results' candidates once a pass and keeps them in registers (48
+//     VGPRs), so the loops over the column blocks read no candidate from LDS.
+constexpr int kMsK = TPE_JOINT_MSEG_MAX_CAT, kMsQ = TPE_JOINT_MAX_QUANT, kMsC = TPE_JOINT_MSEG_MAX_CONT;
+constexpr int kMsD = kMsC + kMsK + kMsQ;    // coordinates of a mixed segment
+static_assert(kMsD == TPE_JOINT_MAX_DIMS, "a record's z holds them");
+static_assert(kMsK == 4 && kMsQ == 4 && TPE_JOINT_MAX_CATS <= 256 && TPE_JOINT_MAX_LATTICE <= 256,
+              "four 16-bit codes in two words, four bytes in one");
+static_assert(mq_tile(kMsC) == kTileK, "one tile length in both kinds of class");
+
+struct MSegF64K : SegF64K {         // segs: the tpe_joint_mseg_f64 array behind the pointer
+  double* table;                    // the f64 table workspace
+};
+__device__ __forceinline__ const tpe_joint_mseg_f64* mseg_f64_at(const SegF64K& p, int s) {
+  return reinterpret_cast<const tpe_joint_mseg_f64*>(p.segs) + s;
+}
+// The classes: the continuous DP classes (dp_class), then the mixed kernel's DP = 1, 2, 4, 8.
+constexpr int kMF64Classes = 8 + 4;
+__host__ __device__ __forceinline__ int mseg_f64_class(int Dc, int Dk, int Dq) {
+  if (Dk + Dq == 0) return dp_class(Dc);
+  return 8 + (Dc <= 1 ? 0 : Dc <= 2 ? 1 : Dc <= 4 ? 2 : 3);
+}
+// the padded width of a segment's psi
+__host__ __device__ __forceinline__ int mseg_f64_width(int Dc, int Dk, int Dq) {
+  if (Dk + Dq == 0) return dp_width(Dc);
+  return Dc <= 1 ? 1 : Dc <= 2 ? 2 : Dc <= 4 ? 4 : 8;
+}
+template <bool MIXED>
+__device__ __forceinline__ int seg_class(const MSegF64K& p, int s) {
+  const tpe_joint_mseg_f64* m = mseg_f64_at(p, s);
+  return mseg_f64_class(m->n_dims, m->n_cat, m->n_quant);
+}
+
+// k_joint_seg_f64_psi's work on this stage's descriptor (that kernel carries the same statements written out: its
+// code generation is pinned).  D counts the continuous coordinates, DP is the segment's class width.
+template <typename Seg>
+__device__ __forceinline__ void seg_f64_psi_block(const Seg* __restrict__ sg, const double* __restrict__ pool64,
+                                                  double* __restrict__ psi, int D, int DP, double* __restrict__ cs) {
+  const int t = threadIdx.x, kb = uni(sg->k_below), ka = uni(sg->k_above);
+  const int nbb = (kb + 15) >> 4, nba = (ka + 15) >> 4;
+  if ((int)blockIdx.x >= nbb + nba) return;
+  if (t < TPE_JOINT_MAX_DIMS) cs[t] = t < D ? sg->centre[t] : 0.0;
+  __syncthreads();
+  const bool below = (int)blockIdx.x < nbb;
+  const int cb = below ? (int)blockIdx.x : (int)blockIdx.x - nbb, K = below ? kb : ka;
+  const double* __restrict__ mu = pool64 + uni(below ? sg->below_mu64 : sg->above_mu64);
+  const double* __restrict__ a = pool64 + uni(below ? sg->below_a64 : sg->above_a64);
+  const double* __restrict__ c = pool64 + uni(below ? sg->below_c64 : sg->above_c64);
+  const int NI = f64_steps(DP);
+  double* __restrict__ out = psi + uni(sg->psi) + (int64_t)blockIdx.x * NI * 64;
+  for (int e = t; e < NI * 64; e += kThreads) {
+    const int k = cb * 16 + (e & 15);
+    out[e] = psi_entry(mu, a, c, k >= K, D, DP, k, 4 * (e >> 6) + ((e >> 4) & 3), cs);
+  }
+}
+
+// k_joint_seg_f64_chunk's work on a continuous segment of this stage (that kernel carries the same statements
+// written out: its code generation is pinned); tile: (kTileK / 16) * NI * 64 doubles.
+template <int DP, typename Seg>
+__device__ __forceinline__ void seg_f64_chunk_body(const SegF64K& p, const Seg* __restrict__ sg, int prob,
+                                                   double* __restrict__ tile, double* __restrict__ res,
+                                                   double* __restrict__ cs, Pick* __restrict__ slot) {
+  constexpr int NI = f64_steps(DP);
+  float* zbuf = reinterpret_cast<float*>(tile);
+  const int t = threadIdx.x, lane = t & 63, chunk = blockIdx.x % p.n_chunks, first = chunk * TPE_JOINT_CHUNK;
+
+  ChunkIO q;
+  q.D = uni(sg->n_dims); q.C = p.C; q.inject = p.inject;
+  q.kb = uni(sg->k_below); q.ka = uni(sg->k_above);
+  q.key0 = p.key0; q.key1 = p.key1; q.stream_word = (uint32_t)uni((int)sg->stream_word);
+  q.c3 = (uint32_t)uni((int)(uint32_t)p.prob_id[prob]);
+  q.base = 0u;
+  q.bmu = q.ba = q.bc = q.amu = q.aa = q.ac = nullptr;   // (the f32 density rows: this stage has none)
+  q.bbase = unid(sg->below_base); q.abase = unid(sg->above_base);
+  q.cum = p.inject ? nullptr : p.pool64 + uni(sg->samp_cum);
+  q.samp = p.inject ? nullptr : p.pool + uni(sg->samp);
+  q.inj = p.inject ? p.pool + uni(sg->inject) : nullptr;
+  q.cand = p.cand ? p.cand + uni(p.cand_off[prob]) : nullptr;
+  q.l_out = p.l_out ? p.l_out + (int64_t)prob * p.C : nullptr;
+  q.g_out = p.g_out ? p.g_out + (int64_t)prob * p.C : nullptr;
+  q.rec = p.chunk_rec + (int64_t)prob * p.n_chunks + chunk;
+  const int D = q.D;
+  float blo[DP], bhi[DP];
+#pragma unroll
+  for (int d = 0; d < DP; ++d) { blo[d] = unif(sg->lo[d]); bhi[d] = unif(sg->hi[d]); }
+  if (t < DP) cs[t] = t < q.D ? sg->centre[t] : 0.0;   // (read after the candidates' barrier; vector loads: no SGPRs)
+  // the below side's column blocks, then the above side's
+  const double* __restrict__ bpsi = p.psi + uni(sg->psi);
+  const double* __restrict__ apsi = bpsi + (int64_t)((q.kb + 15) >> 4) * NI * 64;
+  // from here on k_joint_f64_chunk's passes and finish
+  Pick best{0, 0};
+  double bl = 0.0, bg = 0.0;
+  float bz[DP];
+#pragma unroll
+  for (int d = 0; d < DP; ++d) bz[d] = 0.f;
+#pragma unroll 1
+  for (int r = 0; r < kR; ++r) {
+    const int i = first + r * kThreads + t;
+    float z[DP];
+    load_candidate<DP>(q, blo, bhi, i, z);
+    __syncthreads();                       // the previous pass's last tile is read
+#pragma unroll
+    for (int d = 0; d < DP; ++d) zbuf[t * DP + d] = z[d];
+    __syncthreads();
+    double phi[4][NI];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const float* zr = zbuf + ((t & ~63) + 16 * b + (lane & 15)) * DP;
+#pragma unroll
+      for (int s = 0; s < NI; ++s) {
+        const int e = 4 * s + (lane >> 4), d = min(e < DP ? e : e - DP, DP - 1);
+        const double zp = (double)zr[d] - cs[d];
+        phi[b][s] = e < DP ? zp * zp : e < 2 * DP ? zp : e == 2 * DP ? 1.0 : 0.0;
+      }
+    }
+    const double l2 = score_side_seg_f64<DP>(bpsi, q.kb, phi, tile, res);
+    const double g2 = score_side_seg_f64<DP>(apsi, q.ka, phi, tile, res);
+    const double lv = l2 * kLn2 + q.bbase, gv = g2 * kLn2 + q.abase;
+    if (i >= q.C) continue;
+    if (q.l_out) q.l_out[i] = lv;
+    if (q.g_out) q.g_out[i] = gv;
+    if (q.cand)
+#pragma unroll
+      for (int d = 0; d < DP; ++d)
+        if (d < D) q.cand[(int64_t)i * D + d] = z[d];
+    const uint64_t key = score_key(lv - gv);
+    if (key > best.key) {                  // ascending index: strict > keeps the first of a tie
+      best = Pick{key, (int64_t)i};
+      bl = lv; bg = gv;
+#pragma unroll
+      for (int d = 0; d < DP; ++d) bz[d] = z[d];
+    }
+  }
+  Pick w = wave_best(best);
+  if (lane == 0) slot[t >> 6] = w;
+  __syncthreads();
+  w = slot[0];
+#pragma unroll
+  for (int k = 1; k < kThreads / 64; ++k)
+    if (beats(slot[k], w)) w = slot[k];
+  if (w.key == 0) {
+    if (t == 0) q.rec->global_idx = -1;
+    return;
+  }
+  if (best.key != w.key || best.idx != w.idx) return;
+  q.rec->global_idx = w.idx + (int64_t)q.base;
+  q.rec->l = bl;
+  q.rec->g = bg;
+#pragma unroll
+  for (int d = 0; d < TPE_JOINT_MAX_DIMS; ++d) q.rec->z[d] = d < DP ? (double)bz[d < DP ? d : 0] : 0.0;
+}
+
+__global__ __launch_bounds__(kThreads) void k_joint_mseg_f64_psi(const MSegF64K p) {
+  __shared__ double cs[TPE_JOINT_MAX_DIMS];
+  const tpe_joint_mseg_f64* __restrict__ sg = mseg_f64_at(p, (int)blockIdx.y);
+  const int D = uni(sg->n_dims);
+  seg_f64_psi_block(sg, p.pool64, p.psi, D, mseg_f64_width(D, uni(sg->n_cat), uni(sg->n_quant)), cs);
+}
+
+// k_joint_qtable_f64 for every quantised segment and side of a call in one
+// launch: blockIdx.z = 2 * segment + side, blockIdx.y the quantised dimension,
+// thread k of blockIdx.x the column (the columns [K, S) hold zeros).
+__global__ __launch_bounds__(kThreads) void k_joint_mseg_f64_qtable(const MSegF64K p) {
+  const tpe_joint_mseg_f64* __restrict__ sg = mseg_f64_at(p, (int)(blockIdx.z >> 1));
+  const int side = blockIdx.z & 1, d = blockIdx.y, Dq = sg->n_quant;
+  const int kb = sg->k_below, K = side ? sg->k_above : kb;
+  const int64_t Ks = mq_stride(K);
+  const int k = blockIdx.x * kThreads + threadIdx.x;
+  if (d >= Dq || k >= Ks) return;
+  int voff = 0, total = 0;
+  for (int f = 0; f < Dq; ++f) {
+    if (f < d) voff += sg->quant_v[f];
+    total += sg->quant_v[f];
+  }
+  const int V = sg->quant_v[d];
+  double* out = p.table + sg->table64 + (side ? (int64_t)total * mq_stride(kb) : 0) + (int64_t)voff * Ks + k;
+  if (k >= K) {
+    for (int i = 0; i < V; ++i) out[(int64_t)i * Ks] = 0.0;
+    return;
+  }
+  const double* mu = p.pool64 + (side ? sg->above_qmu : sg->below_qmu);
+  const double* sigma = p.pool64 + (side ? sg->above_qsigma : sg->below_qsigma);
+  qtable_column(mu[(int64_t)k * Dq + d], sigma[(int64_t)k * Dq + d],
+                p.pool64 + sg->quant_edges + sg->quant_edge_off[d], V, out, Ks);
+}
+
+// one side of a mixed segment as the scoring loop reads it
+struct MsSide {
+  const double* psi;
+  const float* cat;
+  const double *miss, *bonus, *T;
+  int K;
+};
+// the per-label sizes, staged in LDS
+struct MsDims {
+  int cU[kMsK], coff[kMsK];
+  int qV[kMsQ], qeoff[kMsQ], qvoff[kMsQ];
+  float qlo[kMsQ], qhi[kMsQ];
+  float blo[kMsC], bhi[kMsC];
+};
+// A lane's 16 results' candidates as packed words, loaded once a pass: words 0
+// and 1 the category codes of slots 0 .. 3 (16 bits each, kept as one 64-bit
+// value), word 2 the lattice indices (a byte each).  A slot is reached by a
+// shift, so the loops over the slots index no register array.  zp: the pass's
+// words [word][thread], offset to the lane's first candidate (result (q, v): +
+// 16 q + 4 v).
+struct MsIdx {
+  uint64_t c[16];
+  uint32_t w[16];
+  __device__ __forceinline__ void load(const uint32_t* __restrict__ zp) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int at = 16 * (r >> 2) + 4 * (r & 3);
+      c[r] = (uint64_t)zp[at] | ((uint64_t)zp[kThreads + at] << 32);
+      w[r] = zp[2 * kThreads + at];
+    }
+  }
+  __device__ __forceinline__ int cat(int q, int v, int d) const { return (int)((c[4 * q + v] >> (16 * d)) & 0xffffu); }
+  __device__ __forceinline__ int lat(int q, int v, int d) const { return (int)((w[4 * q + v] >> (8 * d)) & 0xffu); }
+};
+// a candidate's category as its code: an integer in [-1, 255] + 2, anything else 0
+__device__ __forceinline__ uint32_t cat_code(float v) {
+  return (v >= -1.f && v <= 255.f && (float)(int)v == v) ? (uint32_t)((int)v + 2) : 0u;
+}
+
+// score_side_mq_f64 in the segmented form.  ccode / cbon: the tile's component
+// category codes and bonuses [slot][kTileK].
+template <int DP>
+__device__ __forceinline__ double score_side_mseg_f64(const MsSide& sd, int Dc, int Dk, int Dq,
+                                                      const double (&phi)[4][f64_steps(DP)], const MsIdx& ix,
+                                                      double* __restrict__ tile, int* __restrict__ ccode,
+                                                      double* __restrict__ cbon, const float* __restrict__ zs,
+                                                      const MsDims& dm, double* __restrict__ res) {
+  constexpr int NI = f64_steps(DP), TK = kTileK;
+  const int t = threadIdx.x, lane = t & 63, K = sd.K;
+  const int64_t Ks = mq_stride(K);
+  double m[4][4], s[4][4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+#pragma unroll
+    for (int v = 0; v < 4; ++v) { m[q][v] = kF64Lowest; s[q][v] = 0.0; }   // (any finite first term exceeds it)
+  for (int k0 = 0; k0 < K; k0 += TK) {
+    const int nk = min(TK, K - k0), ncb = (nk + 15) >> 4;
+    __syncthreads();                       // the previous tile (or the candidates' staging) is read
+    {
+      const double2* __restrict__ src = reinterpret_cast<const double2*>(sd.psi + (int64_t)(k0 >> 4) * NI * 64);
+      double2* __restrict__ dst = reinterpret_cast<double2*>(tile);
+      for (int e = t; e < ncb * NI * 32; e += kThreads) dst[e] = src[e];
+    }
+    for (int e = t; e < Dk * TK; e += kThreads) {
+      const int d = e / TK, kk = e - d * TK;
+      int code = -1;                       // past the side's end: matches no candidate
+      double bk = 0.0;
+      if (kk < nk) {
+        const int x = (int)sd.cat[(int64_t)(k0 + kk) * Dk + d];   // -1: the prior row
+        code = x + 2;
+        bk = sd.bonus[dm.coff[d] + min(max(x, 0), dm.cU[d] - 1)];
+      }
+      ccode[e] = code; cbon[e] = bk;
+    }
+    __syncthreads();
+    for (int cb = 0; cb < ncb; ++cb) {
+      const double* bt = tile + cb * NI * 64 + lane;
+      double b[NI];
+#pragma unroll
+      for (int i = 0; i < NI; ++i) b[i] = bt[i * 64];
+      F64x4 acc[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc[q] = F64x4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int i = 0; i < NI; ++i)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(phi[q][i], b[i], acc[q], 0, 0, 0);
+      const int kk = cb * 16 + (lane & 15);
+#pragma unroll 1
+      for (int d = 0; d < Dk; ++d) {
+        const int xc = ccode[d * TK + kk];
+        const double bk = cbon[d * TK + kk];
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+          for (int v = 0; v < 4; ++v)
+            if (ix.cat(q, v, d) == xc) acc[q][v] -= bk;
+      }
+#pragma unroll 1
+      for (int d = 0; d < Dq; ++d) {
+        const double* Tr = sd.T + (int64_t)dm.qvoff[d] * Ks + k0 + kk;   // k0 + kk < Ks: the stride is a multiple of 16
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+          for (int v = 0; v < 4; ++v) acc[q][v] -= Tr[(int64_t)ix.lat(q, v, d) * Ks];
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        bool live = false;                 // (a NaN term is live, and stays in the sum; a -inf term is not)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) live |= !(-acc[q][v] <= m[q][v] - kF64Skip);
+        if (__builtin_amdgcn_ballot_w64(live) == 0) continue;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          const double term = -acc[q][v], dl = term - m[q][v];
+          const double e2 = exp2_nonpos(-__builtin_fabs(dl));
+          s[q][v] = dl > 0.0 ? __builtin_fma(s[q][v], e2, 1.0) : s[q][v] + e2;
+          m[q][v] = fmax(m[q][v], term);
+        }
+      }
+    }
+  }
+  // a row's 16 column lanes (lane & 15) hold its partial pairs
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+#pragma unroll
+      for (int mask = 1; mask < 16; mask <<= 1) {
+        const double mo = __shfl_xor(m[q][v], mask, 64), so = __shfl_xor(s[q][v], mask, 64);
+        const double top = fmax(m[q][v], mo);
+        s[q][v] = s[q][v] * exp2_nonpos(m[q][v] - top) + so * exp2_nonpos(mo - top);
+        m[q][v] = top;
+      }
+      if ((lane & 15) == 0) res[(t & ~63) + 16 * q + 4 * v + (lane >> 4)] = m[q][v] + log2(s[q][v]);
+    }
+  __syncthreads();
+  double out = res[t];                     // + the candidate's sum_d miss_d(v_d), after the sum over k
+#pragma unroll 1
+  for (int d = 0; d < Dk; ++d) out += sd.miss[dm.coff[d] + cat_index(zs[(Dc + d) * kThreads + t], dm.cU[d])];
+  return out;
+}
+
+// one workgroup per (problem of the launch's mixed class, chunk), in k_joint_seg_order's order
+template <int DP>
+__global__ __launch_bounds__(kThreads) void k_joint_mseg_f64_chunk(const MSegF64K p) {
+  constexpr int NI = f64_steps(DP), TK = kTileK;
+  __shared__ __attribute__((aligned(16))) double tile[(TK / 16) * NI * 64];
+  __shared__ double cbon[kMsK * TK];
+  __shared__ double res[kThreads];
+  __shared__ double cs[DP];
+  __shared__ float zs[kMsD * kThreads];
+  __shared__ uint32_t zp[3 * kThreads];
+  __shared__ int ccode[kMsK * TK];
+  __shared__ MsDims dm;
+  __shared__ Pick slot[kThreads / 64];
+  const int t = threadIdx.x, lane = t & 63, chunk = blockIdx.x % p.n_chunks, first = chunk * TPE_JOINT_CHUNK;
+  // the problem and its group: the same for every lane, kept in scalar registers
+  const int prob = uni(p.order[p.first + blockIdx.x / p.n_chunks]);
+  const tpe_joint_mseg_f64* __restrict__ sg = mseg_f64_at(p, uni(p.prob_seg[prob]));
+  const int Dc = uni(sg->n_dims), Dk = uni(sg->n_cat), Dq = uni(sg->n_quant), D = Dc + Dk + Dq, C = p.C;
+  const int kb = uni(sg->k_below), ka = uni(sg->k_above);
+
+  if (t < kMsK) { dm.cU[t] = t < Dk ? sg->cat_upper[t] : 1; dm.coff[t] = t < Dk ? sg->cat_off[t] : 0; }
+  if (t < kMsQ) {
+    int voff = 0;
+    for (int f = 0; f < t && f < Dq; ++f) voff += sg->quant_v[f];
+    dm.qV[t] = t < Dq ? sg->quant_v[t] : 2; dm.qeoff[t] = t < Dq ? sg->quant_edge_off[t] : 0;
+    dm.qvoff[t] = t < Dq ? voff : 0;
+    dm.qlo[t] = sg->qlo[t]; dm.qhi[t] = sg->qhi[t];
+  }
+  if (t < kMsC) { dm.blo[t] = sg->lo[t]; dm.bhi[t] = sg->hi[t]; }
+  if (t < DP) cs[t] = t < Dc ? sg->centre[t] : 0.0;   // (all read after the first pass's barrier)
+
+  // the draws: the solo kernel's sampler view of this problem (id 0 of ids = prob_id + prob)
+  WideQuantSampK sp;
+  sp.D = Dc; sp.C = C; sp.nblk = 0; sp.kb = kb;
+  sp.key0 = p.key0; sp.key1 = p.key1; sp.stream_word = (uint32_t)uni((int)sg->stream_word);
+  sp.cand_base = 0u;
+  sp.cum = p.pool64 + uni(sg->samp_cum);
+  sp.samp = p.pool + uni(sg->samp);
+  sp.ids = p.prob_id + prob;
+  sp.zbuf = nullptr;
+  sp.Dk = Dk;
+  sp.bcat = p.pool + uni(sg->below_cat);
+  sp.bh = p.pool64 + uni(sg->below_h);
+  sp.ccum = p.pool64 + uni(sg->cat_cum);
+  sp.Dq = Dq;
+  sp.edges = p.pool64 + uni(sg->quant_edges);
+  sp.qsamp = p.pool + uni(sg->quant_samp);
+  const float* inj = p.inject ? p.pool + uni(sg->inject) : nullptr;
+
+  // the below side's column blocks, then the above side's; a side's table: [sum V][mq_stride(K)]
+  int total = 0;
+  for (int f = 0; f < Dq; ++f) total += uni(sg->quant_v[f]);
+  const double* bpsi = p.psi + uni(sg->psi);
+  const double* bT = p.table + uni(sg->table64);
+  const MsSide below{bpsi, sp.bcat, p.pool64 + uni(sg->below_miss64), p.pool64 + uni(sg->below_bonus64), bT, kb};
+  const MsSide above{bpsi + (int64_t)((kb + 15) >> 4) * NI * 64, p.pool + uni(sg->above_cat),
+                     p.pool64 + uni(sg->above_miss64), p.pool64 + uni(sg->above_bonus64),
+                     bT + (int64_t)total * mq_stride(kb), ka};
+  const double bbase = unid(sg->below_base), abase = unid(sg->above_base);
+  float* cand = p.cand ? p.cand + uni(p.cand_off[prob]) : nullptr;
+  double* l_out = p.l_out ? p.l_out + (int64_t)prob * C : nullptr;
+  double* g_out = p.g_out ? p.g_out + (int64_t)prob * C : nullptr;
+  tpe_joint_record* rec = p.chunk_rec + (int64_t)prob * p.n_chunks + chunk;
+  MsIdx ix;
+
+  Pick best{0, 0};
+  double bl = 0.0, bg = 0.0;
+  float bz[kMsD];
+#pragma unroll
+  for (int d = 0; d < kMsD; ++d) bz[d] = 0.f;
+#pragma unroll 1
+  for (int r = 0; r < kR; ++r) {
+    const int i = first + r * kThreads + t;
+    __syncthreads();                       // dm is staged; the previous pass has read zs and zp
+    for (int d = 0; d < D; ++d) zs[d * kThreads + t] = 0.f;
+    if (i < C) {
+      if (p.inject) {
+        for (int d = 0; d < D; ++d) zs[d * kThreads + t] = inj[(int64_t)i * D + d];
+      } else {
+        WideDraw c;
+        c.out = zs + t;                    // coordinate j at out[j * 256]
+        wide_sample_stream(sp, i, 0, c);
+        wide_sample_continuous(sp, c, dm.blo, dm.bhi);
+        wide_sample_categories(sp, c, dm.cU, dm.coff);
+        wide_sample_lattice(sp, c, dm.qV, dm.qeoff, dm.qlo, dm.qhi);
+      }
+    }
+    {                                      // this thread's candidate as its three words
+      uint32_t w0 = 0u, w1 = 0u, w2 = 0u;
+#pragma unroll
+      for (int d = 0; d < kMsK; ++d)
+        if (d < Dk) {
+          const uint32_t code = cat_code(zs[(Dc + d) * kThreads + t]) << (16 * (d & 1));
+          if (d < 2) w0 |= code; else w1 |= code;
+        }
+#pragma unroll
+      for (int d = 0; d < kMsQ; ++d)
+        if (d < Dq) w2 |= (uint32_t)cat_index(zs[(Dc + Dk + d) * kThreads + t], dm.qV[d]) << (8 * d);
+      zp[t] = w0; zp[kThreads + t] = w1; zp[2 * kThreads + t] = w2;
+    }
+    __syncthreads();
+    ix.load(zp + (t & ~63) + (lane >> 4));
+    double phi[4][NI];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const float* zr = zs + (t & ~63) + 16 * b + (lane & 15);
+#pragma unroll
+      for (int s = 0; s < NI; ++s) {
+        const int e = 4 * s + (lane >> 4), d = min(e < DP ? e : e - DP, DP - 1);
+        const double zv = d < Dc ? (double)zr[d * kThreads] - cs[d] : 0.0;
+        phi[b][s] = e < DP ? zv * zv : e < 2 * DP ? zv : e == 2 * DP ? 1.0 : 0.0;
+      }
+    }
+    const double l2 = score_side_mseg_f64<DP>(below, Dc, Dk, Dq, phi, ix, tile, ccode, cbon, zs, dm, res);
+    const double g2 = score_side_mseg_f64<DP>(above, Dc, Dk, Dq, phi, ix, tile, ccode, cbon, zs, dm, res);
+    const double lv = l2 * kLn2 + bbase, gv = g2 * kLn2 + abase;
+    if (i >= C) continue;
+    if (l_out) l_out[i] = lv;
+    if (g_out) g_out[i] = gv;
+    if (cand)
+      for (int d = 0; d < D; ++d) cand[(int64_t)i * D + d] = zs[d * kThreads + t];
+    const uint64_t key = score_key(lv - gv);
+    if (key > best.key) {                  // ascending index: strict > keeps the first of a tie
+      best = Pick{key, (int64_t)i};
+      bl = lv; bg = gv;
+#pragma unroll
+      for (int d = 0; d < kMsD; ++d) bz[d] = d < D ? zs[d * kThreads + t] : 0.f;
+    }
+  }
+  Pick w = wave_best(best);
+  if (lane == 0) slot[t >> 6] = w;
+  __syncthreads();
+  w = slot[0];
+#pragma unroll
+  for (int k = 1; k < kThreads / 64; ++k)
+    if (beats(slot[k], w)) w = slot[k];
+  if (w.key == 0) {
+    if (t == 0) rec->global_idx = -1;
+    return;
+  }
+  if (best.key != w.key || best.idx != w.idx) return;
+  rec->global_idx = w.idx;
+  rec->l = bl;
+  rec->g = bg;
+#pragma unroll
+  for (int d = 0; d < kMsD; ++d) rec->z[d] = (double)bz[d];   // kernel coordinate order, then zeros
+}
+
+// a continuous segment of the same call: k_joint_seg_f64_chunk's body on this stage's descriptor
+template <int DP>
+__global__ __launch_bounds__(kThreads) void k_joint_mseg_f64_cont_chunk(const MSegF64K p) {
+  constexpr int NI = f64_steps(DP);
+  __shared__ __attribute__((aligned(16))) double tile[(kTileK / 16) * NI * 64];
+  __shared__ double res[kThreads];
+  __shared__ double cs[DP];
+  __shared__ Pick slot[kThreads / 64];
+  const int prob = uni(p.order[p.first + blockIdx.x / p.n_chunks]);
+  seg_f64_chunk_body<DP>(p, mseg_f64_at(p, uni(p.prob_seg[prob])), prob, tile, res, cs, slot);
+}
+
 // ------------------------------------------------------------- host driver
 // Everything from here on runs on the host: the stages' argument checks,
 // the kernel-argument fills and the launches.  What the stages share exists
@@ -3327,6 +3834,27 @@ uint64_t seg_f64_scratch_need(const tpe_joint_seg_f64* host_segs, int32_t n_segs
   uint64_t n = 0;
   for (int s = 0; s < n_segs; ++s) n += seg_f64_counts_ok(host_segs[s]) ? seg_f64_psi_doubles(host_segs[s]) : 0;
   return seg_f64_psi_off(n_probs, n_cand) + n * sizeof(double);
+}
+// the float64 mixed segmented stage: the same area; a segment's psi by its class width, its table by its lattice total
+bool mseg_f64_counts_ok(const tpe_joint_mseg_f64& g) {
+  const bool mixed = g.n_cat > 0 || g.n_quant > 0;
+  return g.n_cat >= 0 && g.n_cat <= TPE_JOINT_MSEG_MAX_CAT && g.n_quant >= 0 && g.n_quant <= TPE_JOINT_MAX_QUANT &&
+         g.n_dims >= (mixed ? 0 : 1) && g.n_dims <= (mixed ? TPE_JOINT_MSEG_MAX_CONT : TPE_JOINT_MAX_DIMS) &&
+         g.k_below >= 1 && g.k_above >= 1;
+}
+uint64_t mseg_f64_psi_doubles(const tpe_joint_mseg_f64& g) {   // (counts in range)
+  const uint64_t cbs = (uint64_t)((g.k_below + 15) / 16) + (uint64_t)((g.k_above + 15) / 16);
+  return cbs * (uint64_t)f64_steps(mseg_f64_width(g.n_dims, g.n_cat, g.n_quant)) * 64;
+}
+uint64_t mseg_f64_scratch_need(const tpe_joint_mseg_f64* host_segs, int32_t n_segs, int32_t n_probs, int32_t n_cand) {
+  uint64_t n = 0;
+  for (int s = 0; s < n_segs; ++s) n += mseg_f64_counts_ok(host_segs[s]) ? mseg_f64_psi_doubles(host_segs[s]) : 0;
+  return seg_f64_psi_off(n_probs, n_cand) + n * sizeof(double);
+}
+uint64_t mseg_f64_table_doubles(const tpe_joint_mseg_f64& g) {   // (counts and lattice sizes in range)
+  int64_t total = 0;
+  for (int d = 0; d < g.n_quant; ++d) total += g.quant_v[d];
+  return (uint64_t)(mq_stride(g.k_below) + mq_stride(g.k_above)) * (uint64_t)total;
 }
 uint64_t quant_table_floats(int64_t k_below, int64_t k_above, int64_t total) {
   return ((uint64_t)k_below + (uint64_t)k_above) * (uint64_t)total;
@@ -4113,7 +4641,8 @@ int joint_mq_f64_run(const tpe_joint_mq_f64_args* a, tpe_joint_record* records, 
 
 // ---- the segmented stages: one skeleton (joint_seg_run_at); a stage supplies its
 // per-segment check, its class function and its class launcher as overloads on
-// its descriptor, tpe_joint_seg, tpe_joint_wide_seg, tpe_joint_mseg or tpe_joint_seg_f64
+// its descriptor, tpe_joint_seg, tpe_joint_wide_seg, tpe_joint_mseg, tpe_joint_seg_f64 or
+// tpe_joint_mseg_f64
 static_assert(offsetof(tpe_joint_mseg, hi) == offsetof(tpe_joint_seg, hi) &&
                   offsetof(tpe_joint_mseg, n_cat) == sizeof(tpe_joint_seg),
               "tpe_joint_mseg starts with tpe_joint_seg");
@@ -4122,6 +4651,15 @@ static_assert(offsetof(tpe_joint_seg_f64, hi) == offsetof(tpe_joint_seg, hi) &&
                   offsetof(tpe_joint_seg_f64, below_mu64) == sizeof(tpe_joint_seg) &&
                   sizeof(tpe_joint_seg_f64_args) == sizeof(tpe_joint_seg_args),
               "tpe_joint_seg_f64 starts with tpe_joint_seg; the args are tpe_joint_seg_args'");
+static_assert(offsetof(tpe_joint_mseg_f64, hi) == offsetof(tpe_joint_mseg, hi) &&
+                  offsetof(tpe_joint_mseg_f64, n_cat) == offsetof(tpe_joint_mseg, n_cat) &&
+                  offsetof(tpe_joint_mseg_f64, qhi) == offsetof(tpe_joint_mseg, qhi) &&
+                  offsetof(tpe_joint_mseg_f64, below_cat) == offsetof(tpe_joint_mseg, below_cat) &&
+                  offsetof(tpe_joint_mseg_f64, table) == offsetof(tpe_joint_mseg, table) &&
+                  offsetof(tpe_joint_mseg_f64, below_mu64) == sizeof(tpe_joint_mseg) &&
+                  offsetof(tpe_joint_mseg_f64_args, quant_table64) == offsetof(tpe_joint_mseg_args, quant_table) &&
+                  sizeof(tpe_joint_mseg_f64_args) == sizeof(tpe_joint_mseg_args),
+              "tpe_joint_mseg_f64 starts with tpe_joint_mseg; the args are laid out as tpe_joint_mseg_args");
 
 // rows [off, off + n) inside a pool of len elements
 bool inside(int64_t off, int64_t n, int64_t len) { return off >= 0 && n <= len && off <= len - n; }
@@ -4132,12 +4670,14 @@ struct SegPlan {
   int64_t per_class[kMClasses] = {};
   unsigned lds[kMClasses] = {};
   int max_kblocks = 0;
+  int max_tblocks = 0;                     // (the float64 mixed stage: max_kblocks is its psi launch's width)
   bool any_quant = false;
 };
 constexpr int n_classes_of(const tpe_joint_seg*) { return 8; }
 constexpr int n_classes_of(const tpe_joint_mseg*) { return kMClasses; }
 constexpr int n_classes_of(const tpe_joint_wide_seg*) { return 5; }
 constexpr int n_classes_of(const tpe_joint_seg_f64*) { return 8; }
+constexpr int n_classes_of(const tpe_joint_mseg_f64*) { return kMF64Classes; }
 
 // a continuous segment, narrow or wide: its counts and its rows' places
 template <typename A, typename Seg>
@@ -4176,20 +4716,38 @@ int check_segment(const char* entry, const tpe_joint_seg_f64_args* a, const tpe_
   if (blocks > plan.max_kblocks) plan.max_kblocks = blocks;
   return TPE_OK;
 }
+// every segment's range [off(s), off(s) + len(s)) inside an area of `doubles` elements, and no two of them
+// overlapping (an empty range, len = 0, is not looked at)
+template <typename Off, typename Len>
+int check_ranges(const char* entry, int n_segs, uint64_t doubles, Off off, Len len, const char* leaves,
+                 const char* overlaps) {
+  std::vector<int> by;
+  for (int s = 0; s < n_segs; ++s) {
+    const uint64_t n = len(s);
+    if (n == 0) continue;
+    if (off(s) < 0 || n > doubles || (uint64_t)off(s) > doubles - n) return fail(entry, leaves, kSegs);
+    by.push_back(s);
+  }
+  std::sort(by.begin(), by.end(), [&](int x, int y) { return off(x) < off(y); });
+  for (size_t i = 1; i < by.size(); ++i)   // (by start, each must end before the next)
+    if (off(by[i - 1]) + (int64_t)len(by[i - 1]) > off(by[i])) return fail(entry, overlaps, kSegs);
+  return TPE_OK;
+}
 // every psi range inside the f64 area of `doubles` elements, and no two of them overlapping
 int check_psi_ranges(const char* entry, const tpe_joint_seg_f64* g, int n_segs, uint64_t doubles) {
-  std::vector<int> by(n_segs);
-  for (int s = 0; s < n_segs; ++s) {
-    const uint64_t n = seg_f64_psi_doubles(g[s]);
-    if (g[s].psi < 0 || n > doubles || (uint64_t)g[s].psi > doubles - n)
-      return fail(entry, "psi range leaves scratch", kSegs);
-    by[s] = s;
-  }
-  std::sort(by.begin(), by.end(), [&](int x, int y) { return g[x].psi < g[y].psi; });
-  for (int i = 1; i < n_segs; ++i)         // (ranges are not empty: by start, each must end before the next)
-    if (g[by[i - 1]].psi + (int64_t)seg_f64_psi_doubles(g[by[i - 1]]) > g[by[i]].psi)
-      return fail(entry, "psi range overlaps another segment's", kSegs);
-  return TPE_OK;
+  return check_ranges(entry, n_segs, doubles, [&](int s) { return g[s].psi; },
+                      [&](int s) { return seg_f64_psi_doubles(g[s]); }, "psi range leaves scratch",
+                      "psi range overlaps another segment's");
+}
+int check_psi_ranges(const char* entry, const tpe_joint_mseg_f64* g, int n_segs, uint64_t doubles) {
+  return check_ranges(entry, n_segs, doubles, [&](int s) { return g[s].psi; },
+                      [&](int s) { return mseg_f64_psi_doubles(g[s]); }, "psi range leaves scratch",
+                      "psi range overlaps another segment's");
+}
+int check_table_ranges(const char* entry, const tpe_joint_mseg_f64* g, int n_segs, uint64_t doubles) {
+  return check_ranges(entry, n_segs, doubles, [&](int s) { return g[s].table64; },
+                      [&](int s) { return mseg_f64_table_doubles(g[s]); }, "table leaves the table workspace",
+                      "table overlaps another segment's");
 }
 
 int check_segment(const char* entry, const tpe_joint_mseg_args* a, const tpe_joint_mseg& g, bool inject, SegPlan& plan) {
@@ -4241,8 +4799,62 @@ int check_segment(const char* entry, const tpe_joint_mseg_args* a, const tpe_joi
   return TPE_OK;
 }
 
+// the float64 mixed stage: tpe_joint_mseg's counts and tables, the rows this stage reads (the f64 density rows and
+// category tables in pool_f64; not the f32 density rows, tables and table); psi and table ranges: after the sizes
+int check_segment(const char* entry, const tpe_joint_mseg_f64_args* a, const tpe_joint_mseg_f64& g, bool inject,
+                  SegPlan& plan) {
+  const int64_t L = a->pool_f32_len, L64 = a->pool_f64_len;
+  if (g.n_cat < 0 || g.n_cat > TPE_JOINT_MAX_DIMS) return fail(entry, "n_cat outside [0, TPE_JOINT_MAX_DIMS]", kSegs);
+  if (g.n_quant < 0 || g.n_quant > TPE_JOINT_MAX_QUANT)
+    return fail(entry, "n_quant outside [0, TPE_JOINT_MAX_QUANT]", kSegs);
+  const int64_t Dc = g.n_dims, Dk = g.n_cat, Dq = g.n_quant, D = Dc + Dk + Dq, kb = g.k_below, ka = g.k_above;
+  if (Dk + Dq == 0) {
+    if (Dc < 1 || Dc > TPE_JOINT_MAX_DIMS) return fail(entry, "n_dims outside [1, TPE_JOINT_MAX_DIMS]", kSegs);
+  } else {
+    if (Dc < 0) return fail(entry, "n_dims < 0", kSegs);
+    if (Dc > TPE_JOINT_MSEG_MAX_CONT || Dk > TPE_JOINT_MSEG_MAX_CAT)
+      return fail(entry, "n_dims > 8 or n_cat > 4 in a segment with a discrete or quantised label");
+  }
+  if (kb < 1 || ka < 1) return fail(entry, "k_below < 1 or k_above < 1", kSegs);
+  const int64_t cat_total = check_cats(entry, kInSeg, g.cat_upper, g.cat_off, (int)Dk);
+  if (cat_total < 0) return TPE_E_ARG;
+  const int64_t total = check_lattice(entry, kInSeg, g.quant_v, g.quant_edge_off, (int)Dq, g.n_edges);
+  if (total < 0) return TPE_E_ARG;
+  if (Dq > 0 && !a->quant_table64) return fail(entry, "null table workspace with a quantised segment");
+  bool ok = inside(g.below_c64, kb, L64) && inside(g.above_c64, ka, L64);
+  if (Dc > 0)
+    ok = ok && inside(g.below_mu64, kb * Dc, L64) && inside(g.below_a64, kb * Dc, L64) &&
+         inside(g.above_mu64, ka * Dc, L64) && inside(g.above_a64, ka * Dc, L64);
+  if (!inject) ok = ok && inside(g.samp_cum, kb, L64) && (Dc == 0 || inside(g.samp, kb * Dc * 5, L));
+  if (inject && g.inject >= 0) ok = ok && inside(g.inject, (int64_t)a->n_cand * D, L);
+  if (Dk > 0) {
+    ok = ok && inside(g.below_cat, kb * Dk, L) && inside(g.above_cat, ka * Dk, L) &&
+         inside(g.below_miss64, cat_total, L64) && inside(g.below_bonus64, cat_total, L64) &&
+         inside(g.above_miss64, cat_total, L64) && inside(g.above_bonus64, cat_total, L64);
+    if (!inject) ok = ok && inside(g.below_h, Dk, L64) && inside(g.cat_cum, cat_total, L64);
+  }
+  if (Dq > 0) {
+    ok = ok && inside(g.quant_edges, g.n_edges, L64) && inside(g.below_qmu, kb * Dq, L64) &&
+         inside(g.below_qsigma, kb * Dq, L64) && inside(g.above_qmu, ka * Dq, L64) &&
+         inside(g.above_qsigma, ka * Dq, L64);
+    if (!inject) ok = ok && inside(g.quant_samp, kb * Dq * 5, L);
+  }
+  if (!ok) return fail(entry, "rows leave its pool", kSegs);
+  for (int d = 0; d < Dc; ++d)
+    if (!isfinite(g.centre[d])) return fail(entry, "centre not finite", kSegs);
+  const int blocks = (int)((kb + 15) / 16 + (ka + 15) / 16);   // the psi launch's width: the widest segment
+  if (blocks > plan.max_kblocks) plan.max_kblocks = blocks;
+  if (Dq > 0) {
+    plan.any_quant = true;
+    const int tblocks = (int)((mq_stride((int)(kb > ka ? kb : ka)) + kThreads - 1) / kThreads);
+    if (tblocks > plan.max_tblocks) plan.max_tblocks = tblocks;
+  }
+  return TPE_OK;
+}
+
 // the kernel class of a segment that has a problem
 int segment_class(const tpe_joint_seg& g, SegPlan&) { return dp_class(g.n_dims); }
+int segment_class(const tpe_joint_mseg_f64& g, SegPlan&) { return mseg_f64_class(g.n_dims, g.n_cat, g.n_quant); }
 int segment_class(const tpe_joint_wide_seg& g, SegPlan&) { return wide_class(g.n_dims); }
 int segment_class(const tpe_joint_seg_f64& g, SegPlan&) { return dp_class(g.n_dims); }
 int segment_class(const tpe_joint_mseg& g, SegPlan& plan) {
@@ -4298,6 +4910,20 @@ void launch_class(const tpe_joint_seg_f64*, int c, const SegF64K& k, unsigned bl
   });
 }
 
+// (mseg_f64_class's numbering: the continuous classes run the continuous float64 body)
+constexpr int kMsDpOf[4] = {1, 2, 4, 8};
+void launch_class(const tpe_joint_mseg_f64*, int c, const MSegF64K& k, unsigned blocks, unsigned, hipStream_t s, Ev ev) {
+  if (c < 8) {
+    for_dp(c, [&](auto dp) {
+      launch(k_joint_mseg_f64_cont_chunk<decltype(dp)::value>, dim3(blocks), kThreads, 0u, s, ev.start, ev.stop, k);
+    });
+  } else {
+    pad_to<1, 2, 4, 8>(kMsDpOf[c - 8], [&](auto dp) {
+      launch(k_joint_mseg_f64_chunk<decltype(dp)::value>, dim3(blocks), kThreads, 0u, s, ev.start, ev.stop, k);
+    });
+  }
+}
+
 // the merge kernel of a stage's record
 auto merge_of(const tpe_joint_record*) { return &k_joint_merge; }
 auto merge_of(const tpe_joint_wide_record*) { return &k_joint_wide_merge; }
@@ -4307,11 +4933,16 @@ auto merge_of(const tpe_joint_wide_record*) { return &k_joint_wide_merge; }
 SegK& seg_view(MSegK& mk) { return mk.s; }
 WideSegK& seg_view(WideSegK& k) { return k; }
 SegF64K& seg_view(SegF64K& k) { return k; }
+MSegF64K& seg_view(MSegF64K& k) { return k; }
 template <typename Seg>
-using SegKernelArgs = std::conditional_t<std::is_same<Seg, tpe_joint_wide_seg>::value, WideSegK,
-                                         std::conditional_t<std::is_same<Seg, tpe_joint_seg_f64>::value, SegF64K, MSegK>>;
-// the launch of the float64 stage's psi kernel among a profiled run's launches (-1: none)
-int g_psi_mark = -1;
+using SegKernelArgs = std::conditional_t<
+    std::is_same<Seg, tpe_joint_wide_seg>::value, WideSegK,
+    std::conditional_t<std::is_same<Seg, tpe_joint_seg_f64>::value, SegF64K,
+                       std::conditional_t<std::is_same<Seg, tpe_joint_mseg_f64>::value, MSegF64K, MSegK>>>;
+// the launch of the float64 stages' psi kernel among a profiled run's launches (-1: none), and of the float64
+// mixed stage's table kernel (-1: none)
+int g_psi_mark = -1, g_tab_mark = -1;
+bool g_marks_mseg_f64 = false;             // the marks are a tpe_joint_mseg_f64_run's
 
 template <typename A, typename Rec>
 int joint_seg_run_at(const char* E, const A* a, Rec* records, float* cand, double* l_out, double* g_out,
@@ -4319,14 +4950,15 @@ int joint_seg_run_at(const char* E, const A* a, Rec* records, float* cand, doubl
   using Seg = std::remove_cv_t<std::remove_pointer_t<decltype(A::host_segs)>>;
   constexpr bool MIXED = std::is_same<Seg, tpe_joint_mseg>::value;
   constexpr bool WIDE = std::is_same<Seg, tpe_joint_wide_seg>::value;
-  constexpr bool F64 = std::is_same<Seg, tpe_joint_seg_f64>::value;
+  constexpr bool MF64 = std::is_same<Seg, tpe_joint_mseg_f64>::value;   // the float64 mixed stage
+  constexpr bool F64 = std::is_same<Seg, tpe_joint_seg_f64>::value || MF64;
   static_assert(std::is_same<Rec, std::conditional_t<WIDE, tpe_joint_wide_record, tpe_joint_record>>::value,
                 "the stage's record");
   constexpr int n_classes = n_classes_of((const Seg*)nullptr);
   tpe_internal_epoch_bump();
   if (!a) return fail(E, "null args");
   if (a->n_segs < 1) return fail(E, "n_segs < 1");
-  if (MIXED && a->n_segs > 32767) return fail(E, "more than 32767 segments");
+  if ((MIXED || MF64) && a->n_segs > 32767) return fail(E, "more than 32767 segments");   // (the table launch's grid)
   if (F64 && a->n_segs > 65535) return fail(E, "more than 65535 segments");   // (the psi launch's grid)
   if (a->n_probs < 1) return fail(E, "n_probs < 1");
   if (a->n_cand < 1) return fail(E, "n_cand < 1");
@@ -4350,12 +4982,15 @@ int joint_seg_run_at(const char* E, const A* a, Rec* records, float* cand, doubl
   const int64_t n_chunks = WIDE ? wide_blocks_of(a->n_cand) : n_chunks_of(a->n_cand);
   if ((int64_t)a->n_segs * n_classes > INT32_MAX) return fail(E, "too many candidates");
   uint64_t need = WIDE ? wide_seg_scratch_need(a->n_probs, a->n_cand) : seg_scratch_need(a->n_probs, a->n_cand);
-  if constexpr (F64) need = seg_f64_scratch_need(a->host_segs, a->n_segs, a->n_probs, a->n_cand);
+  if constexpr (MF64) need = mseg_f64_scratch_need(a->host_segs, a->n_segs, a->n_probs, a->n_cand);
+  else if constexpr (F64) need = seg_f64_scratch_need(a->host_segs, a->n_segs, a->n_probs, a->n_cand);
   if (int rc = check_scratch(E, n_chunks * a->n_probs, need, scratch, scratch_bytes)) return rc;
   if constexpr (F64) {
     const uint64_t doubles = (scratch_bytes - seg_f64_psi_off(a->n_probs, a->n_cand)) / sizeof(double);
     if (int rc = check_psi_ranges(E, a->host_segs, a->n_segs, doubles)) return rc;
   }
+  if constexpr (MF64)
+    if (int rc = check_table_ranges(E, a->host_segs, a->n_segs, a->quant_table64_bytes / sizeof(double))) return rc;
 
   SegKernelArgs<Seg> mk;                    // (the continuous stage's kernels take mk.s alone)
   auto& k = seg_view(mk);
@@ -4373,6 +5008,7 @@ int joint_seg_run_at(const char* E, const A* a, Rec* records, float* cand, doubl
     k.zbuf = (float*)((char*)k.chunk_rec + wide_seg_record_bytes(a->n_probs, a->n_cand));
   } else if constexpr (F64) {
     k.psi = (double*)((char*)scratch + seg_f64_psi_off(a->n_probs, a->n_cand));
+    if constexpr (MF64) k.table = a->quant_table64;
   } else {
     mk.table = nullptr;
   }
@@ -4382,7 +5018,8 @@ int joint_seg_run_at(const char* E, const A* a, Rec* records, float* cand, doubl
   if (timed)
     if (int rc = ensure_events(g_sprof.ev, 2 * kSegLaunches)) return rc;
   int n_timed = 0;
-  g_psi_mark = -1;
+  g_psi_mark = g_tab_mark = -1;
+  g_marks_mseg_f64 = MF64;
   Ev ev = seg_marks(timed, n_timed);
   launch(k_joint_seg_order<MIXED, std::remove_reference_t<decltype(k)>>,
          dim3((unsigned)((a->n_probs + kThreads - 1) / kThreads)), kThreads, 0u, s, ev.start, ev.stop, k);
@@ -4397,8 +5034,20 @@ int joint_seg_run_at(const char* E, const A* a, Rec* records, float* cand, doubl
   if constexpr (F64) {                      // psi of every segment, once a call (the table launch's slot)
     if (timed) g_psi_mark = n_timed;
     ev = seg_marks(timed, n_timed);
-    launch(k_joint_seg_f64_psi, dim3((unsigned)plan.max_kblocks, (unsigned)a->n_segs), kThreads, 0u, s, ev.start,
-           ev.stop, k);
+    if constexpr (MF64) {
+      launch(k_joint_mseg_f64_psi, dim3((unsigned)plan.max_kblocks, (unsigned)a->n_segs), kThreads, 0u, s, ev.start,
+             ev.stop, k);
+      if (plan.any_quant) {                 // the f64 tables of every quantised segment and side
+        if (timed) g_tab_mark = n_timed;
+        ev = seg_marks(timed, n_timed);
+        launch(k_joint_mseg_f64_qtable,
+               dim3((unsigned)plan.max_tblocks, (unsigned)TPE_JOINT_MAX_QUANT, (unsigned)(2 * a->n_segs)), kThreads, 0u,
+               s, ev.start, ev.stop, k);
+      }
+    } else {
+      launch(k_joint_seg_f64_psi, dim3((unsigned)plan.max_kblocks, (unsigned)a->n_segs), kThreads, 0u, s, ev.start,
+             ev.stop, k);
+    }
   }
   if constexpr (WIDE) {                     // the sampler's time is tpe_joint_wide_profile's, as in the solo wide stage
     g_wprof.valid = 0;
@@ -4595,6 +5244,43 @@ int tpe_joint_seg_f64_profile(double* psi_ms) {
 int tpe_joint_mseg_run(const tpe_joint_mseg_args* a, tpe_joint_record* records, float* cand, double* l_out,
                        double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
   return joint_seg_run_at("tpe_joint_mseg_run", a, records, cand, l_out, g_out, scratch, scratch_bytes, stream, 0u);
+}
+
+int tpe_joint_mseg_f64_scratch_bytes(const tpe_joint_mseg_f64* host_segs, int32_t n_segs, int32_t n_probs,
+                                     int32_t n_cand, uint64_t* bytes) {
+  bool ok = host_segs && n_segs >= 1 && n_probs >= 1 && n_cand >= 1;
+  for (int s = 0; ok && s < n_segs; ++s) ok = mseg_f64_counts_ok(host_segs[s]);
+  return size_out("tpe_joint_mseg_f64_scratch_bytes", ok,
+                  ok ? mseg_f64_scratch_need(host_segs, n_segs, n_probs, n_cand) : 0, bytes);
+}
+
+int tpe_joint_mseg_f64_table_bytes(const tpe_joint_mseg_f64* host_segs, int32_t n_segs, uint64_t* bytes) {
+  constexpr const char* E = "tpe_joint_mseg_f64_table_bytes";
+  if (!bytes || !host_segs || n_segs < 1) return fail(E, "bad arguments");
+  uint64_t n = 0;
+  for (int s = 0; s < n_segs; ++s) {
+    const tpe_joint_mseg_f64& g = host_segs[s];
+    if (g.n_quant < 0 || g.n_quant > TPE_JOINT_MAX_QUANT || g.k_below < 1 || g.k_above < 1)
+      return fail(E, "n_quant, k_below or k_above out of range", kSegs);
+    if (check_lattice(E, "", g.quant_v, nullptr, g.n_quant, 0) < 0) return TPE_E_ARG;
+    n += mseg_f64_table_doubles(g);
+  }
+  *bytes = n * sizeof(double);
+  return TPE_OK;
+}
+
+int tpe_joint_mseg_f64_run(const tpe_joint_mseg_f64_args* a, tpe_joint_record* records, float* cand, double* l_out,
+                           double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
+  return joint_seg_run_at("tpe_joint_mseg_f64_run", a, records, cand, l_out, g_out, scratch, scratch_bytes, stream, 0u);
+}
+
+int tpe_joint_mseg_f64_profile(double* psi_ms, double* table_ms) {
+  if (!psi_ms || !table_ms || !g_marks_mseg_f64 || g_prof.valid != 2 || g_psi_mark < 0 || g_psi_mark >= g_sprof.n || g_tab_mark >= g_sprof.n)
+    return fail("tpe_joint_mseg_f64_profile", "no profiled tpe_joint_mseg_f64_run to read");
+  *table_ms = 0.0;
+  if (g_tab_mark >= 0)
+    if (int rc = elapsed_ms(g_sprof.ev[2 * g_tab_mark], g_sprof.ev[2 * g_tab_mark + 1], table_ms)) return rc;
+  return elapsed_ms(g_sprof.ev[2 * g_psi_mark], g_sprof.ev[2 * g_psi_mark + 1], psi_ms);
 }
 
 int tpe_joint_wide_seg_run(const tpe_joint_wide_seg_args* a, tpe_joint_wide_record* records, float* cand,

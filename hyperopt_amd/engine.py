@@ -1574,6 +1574,34 @@ class Engine(object):
         return self._joint_seg_call('tpe_joint_mseg' if mixed else 'tpe_joint_seg', a, P, C, b.cand_off, b.widths,
                                     return_cand, want_lg, report_k, shard)
 
+    def run_joint_msegments_f64(self, models, stream_words, prob_seg, prob_id, n_cand, seed, inject=None,
+                                return_cand=False, want_lg=False):
+        """``run_joint_segments`` over groups that may hold discrete and
+        quantised labels, scored in float64 (tpe_joint_mseg_f64_run,
+        include/tpe_hip.h "Float64 mixed segmented joint stage"; DESIGN.md
+        "Float64 mixed branch groups").  ``models`` and the other arguments as
+        ``run_joint_segments`` takes them, within the mixed segmented stage's
+        limits; all groups, continuous ones included, go through one upload, one
+        call and one download.  The candidates are those of the fp32 call, bit
+        for bit; psi of a group and the float64 lattice tables of a quantised
+        one are built once a call.  Problem p's results are those of the solo
+        float64 run of its group's kind over its group with that stream word
+        and ids = [prob_id[p]]: ``run_joint_quant`` / ``run_joint_mixed`` /
+        ``run_joint`` with ``precision='fp64'``.  Returns as
+        ``run_joint_segments``; there is no report and no shard."""
+        C = int(n_cand)
+        b = JP.segment_blob(models, stream_words, prob_seg, prob_id, C, inject, N.JOINT_MSEG_F64_DTYPE)
+        a = self._joint_seg_args(N.JointMSegF64Args, b, len(models), C, seed, inject)
+        nb = ctypes.c_uint64(0)
+        N.check(self.lib.tpe_joint_mseg_f64_table_bytes(b.segs.ctypes.data, len(models), ctypes.byref(nb)), self.lib,
+                'tpe_joint_mseg_f64_table_bytes')
+        assert nb.value == 8 * b.n_table, (nb.value, b.n_table)
+        if b.n_table:
+            d_tab = self._buf('joint_mseg_table64', b.n_table, torch.float64)
+            a.quant_table64, a.quant_table64_bytes = d_tab.data_ptr(), d_tab.numel() * 8
+        return self._joint_seg_call('tpe_joint_mseg_f64', a, len(b.prob_seg), C, b.cand_off, b.widths, return_cand,
+                                    want_lg, 0, host_segs=b.segs)
+
     def run_joint_wide_segments(self, models, stream_words, prob_seg, prob_id, n_cand, seed, inject=None,
                                 return_cand=False, want_lg=False, report_k=0):
         """``run_joint_segments`` for continuous groups of up to

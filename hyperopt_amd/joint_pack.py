@@ -21,7 +21,8 @@ The dimension limits by entry point (``_check_dims``):
   'segment'  run_joint_segments    a continuous group 1 <= Dc <= JOINT_MAX_DIMS; one with discrete or
                                    quantised parts Dc <= JOINT_MSEG_MAX_CONT, Dk <= JOINT_MSEG_MAX_CAT
   'wide_segment' run_joint_wide_segments  1 <= Dc <= JOINT_WIDE_MAX_DIMS, continuous only
-  (run_joint_segments(precision='fp64') packs every group by 'f64')
+  (run_joint_segments(precision='fp64') packs every group by 'f64'; run_joint_msegments_f64 packs a group with
+   discrete or quantised parts by 'mq_f64' within 'segment''s limits, a continuous one by 'f64')
 and Dq <= JOINT_MAX_QUANT everywhere.
 """
 import collections
@@ -237,7 +238,7 @@ def inject_rows(inject, C, D):
 # SECTIONS; segs: the descriptors on the host; prob_seg: the int32 problem list
 # on the host; cand_off [P + 1]; widths [P]: D of every problem's group; n32 /
 # n64: the pools' element counts; n_table: the f32 elements of the quantised
-# tables.
+# tables (the float64 mixed stage: their f64 elements).
 SegmentBlob = collections.namedtuple('SegmentBlob', 'blob offs segs prob_seg cand_off widths n32 n64 n_table')
 # one blob: the 8-byte items first, then the 4-byte ones
 SECTIONS = ('segs', 'pool_f64', 'prob_id', 'cand_off', 'pool_f32', 'prob_seg')
@@ -247,11 +248,16 @@ def segment_blob(models, stream_words, prob_seg, prob_id, n_cand, inject, seg_dt
     """The upload of a segmented stage (Engine.run_joint_segments' arguments):
     per group its descriptor (``seg_dtype``: N.JOINT_SEG_DTYPE, continuous
     groups only, N.JOINT_WIDE_SEG_DTYPE, continuous groups of up to
-    JOINT_WIDE_MAX_DIMS labels, N.JOINT_MSEG_DTYPE, or N.JOINT_SEG_F64_DTYPE, the
+    JOINT_WIDE_MAX_DIMS labels, N.JOINT_MSEG_DTYPE, N.JOINT_SEG_F64_DTYPE, the
     float64 stage: a group's rows are group_rows(entry='f64'), its float64
     density rows in pool_f64 under the descriptor's *64 fields, and the
     descriptor also carries the centres and where the group's psi starts in
-    the stage's scratch, the ranges laid end to end) and its group_rows in the two pools,
+    the stage's scratch, the ranges laid end to end, or N.JOINT_MSEG_F64_DTYPE,
+    the float64 mixed stage: a group with discrete or quantised parts is
+    group_rows(entry='mq_f64'), a continuous one entry='f64', and beside psi
+    the descriptor says where a quantised group's float64 table starts in the
+    stage's table workspace, SegmentBlob.n_table then counting its doubles)
+    and its group_rows in the two pools,
     in the order of ROWS with the group's inject rows last; a continuous group
     is the case Dk = Dq = 0.  The descriptors carry the f32 bounds
     (joint.f32_bounds), padded with -+inf.  ``empty_ok``: n_cand = 0 is allowed
@@ -273,6 +279,7 @@ def segment_blob(models, stream_words, prob_seg, prob_id, n_cand, inject, seg_dt
     if inject is not None and len(inject) != S:
         raise ValueError('joint stage: inject must hold one entry per group')
     mixed, f64 = 'n_cat' in seg_dtype.names, 'psi' in seg_dtype.names
+    mf64 = mixed and f64
     entry = 'f64' if f64 else 'wide_segment' if seg_dtype['lo'].shape == (N.JOINT_WIDE_MAX_DIMS,) else 'segment'
     segs = np.zeros(S, dtype=seg_dtype)
     pools = {4: [], 8: []}
@@ -287,7 +294,11 @@ def segment_blob(models, stream_words, prob_seg, prob_id, n_cand, inject, seg_dt
     dims = np.empty(S, dtype=np.int64)
     n_table = n_psi = 0
     for s, group in enumerate(groups):
-        r = group_rows(*group, entry=entry)
+        if mf64 and (group[4] or group[5]):          # the solo float64 run's rows, within a mixed segment's limits
+            _check_dims('segment', len(np.reshape(group[2], -1)), len(group[4]), len(group[5]))
+            r = group_rows(*group, entry='mq_f64')
+        else:
+            r = group_rows(*group, entry=entry)
         Dc, Dk, Dq = r['Dc'], r['Dk'], r['Dq']
         D = dims[s] = Dc + Dk + Dq
         g = segs[s]
@@ -295,12 +306,12 @@ def segment_blob(models, stream_words, prob_seg, prob_id, n_cand, inject, seg_dt
         g['stream_word'] = int(stream_words[s])
         g['below_base'], g['above_base'] = r['below_base'], r['above_base']
         for key, field, buf, dtype, _ in group_rows_present(r):
-            g[field + '64' if buf.endswith('64') else field] = put(r[key], dtype)
+            g[field + '64' if buf.endswith('64') and not field.endswith('64') else field] = put(r[key], dtype)
         g['lo'], g['hi'] = np.float32(-np.inf), np.float32(np.inf)
         g['lo'][:Dc], g['hi'][:Dc] = J.f32_bounds(r['low'], r['high'])
         if f64:                                      # psi: both sides' column blocks of 16 components, NI * 64 doubles each
             g['centre'][:Dc], g['psi'] = r['centre'], n_psi
-            n_psi += ((r['k_below'] + 15) // 16 + (r['k_above'] + 15) // 16) * N.f64_steps(Dc) * 64
+            n_psi += ((r['k_below'] + 15) // 16 + (r['k_above'] + 15) // 16) * N.mseg_f64_steps(Dc, Dk, Dq) * 64
         if mixed:
             g['n_cat'], g['n_quant'] = Dk, Dq
             g['qlo'], g['qhi'] = np.float32(-np.inf), np.float32(np.inf)
@@ -310,8 +321,12 @@ def segment_blob(models, stream_words, prob_seg, prob_id, n_cand, inject, seg_dt
             g['quant_v'][:Dq], g['quant_edge_off'][:Dq] = r['quant_v'], r['quant_edge_off']
             g['n_edges'] = r['n_lattice'] + Dq
             g['qlo'][:Dq], g['qhi'][:Dq] = J.f32_bounds(r['qlow'], r['qhigh'])
-            g['table'] = n_table
-            n_table += (r['k_below'] + r['k_above']) * r['n_lattice']
+            if mf64:                                 # a side's component stride: K rounded up to a multiple of 16
+                g['table64'] = n_table
+                n_table += ((r['k_below'] + 15) // 16 + (r['k_above'] + 15) // 16) * 16 * r['n_lattice']
+            else:
+                g['table'] = n_table
+                n_table += (r['k_below'] + r['k_above']) * r['n_lattice']
         g['inject'] = -1
         if inject is not None and inject[s] is not None:
             g['inject'] = put(inject_rows(inject[s], C, D), np.float32)

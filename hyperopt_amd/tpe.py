@@ -848,7 +848,8 @@ def suggest(new_ids, domain, trials, seed,
             shard_grid=None, joint=False, joint_discrete=False, joint_quantized=False, joint_wide=False,
             joint_branches=False, joint_branches_mixed=False, joint_branches_wide=False, joint_shard=None,
             joint_precision='fp32', joint_precision_wide=False, joint_precision_branches=False,
-            joint_precision_mixed=False, joint_wide_mixed=False, joint_wide_quantized=False, joint_liar=False):
+            joint_precision_mixed=False, joint_precision_branches_mixed=False, joint_wide_mixed=False,
+            joint_wide_quantized=False, joint_liar=False):
     new_ids = list(new_ids)
     if not new_ids:
         return []
@@ -857,9 +858,11 @@ def suggest(new_ids, domain, trials, seed,
     liar_mode = _joint_liar_mode(joint_liar)
     if liar_mode:
         _joint_liar_check(joint, joint_shard, mode=liar_mode, joint_branches=joint_branches)
+    bm64 = _branches_mixed_f64(joint_precision_branches_mixed, joint_precision, joint_branches,
+                               joint_precision_branches, joint_branches_mixed, joint_discrete, joint_quantized)
     fp64 = _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, None, joint_precision_wide,
                                   joint_wide, joint_precision_branches, joint_branches,
-                                  _mixed_f64(joint_precision_mixed, joint_discrete, joint_quantized))
+                                  _mixed_f64(joint_precision_mixed, joint_discrete, joint_quantized), bm64)
     if ((joint is not False and joint is not None) or joint_discrete or joint_quantized or joint_wide or joint_branches
             or joint_branches_mixed or joint_branches_wide or joint_wide_mixed or joint_wide_quantized):
         # (argument errors first: no device use, no startup draw)
@@ -874,7 +877,7 @@ def suggest(new_ids, domain, trials, seed,
         if fp64:
             _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, plan, joint_precision_wide,
                                    joint_wide, joint_precision_branches, joint_branches,
-                                   _mixed_f64(joint_precision_mixed, joint_discrete, joint_quantized))
+                                   _mixed_f64(joint_precision_mixed, joint_discrete, joint_quantized), bm64)
     t0 = time.time()
     hist = _history.extract(domain, trials)
     if logger.isEnabledFor(logging.INFO):
@@ -896,7 +899,8 @@ def suggest(new_ids, domain, trials, seed,
                               joint_wide_quantized=joint_wide_quantized, joint_liar=joint_liar,
                               joint_precision=joint_precision, joint_precision_wide=joint_precision_wide,
                               joint_precision_branches=joint_precision_branches,
-                              joint_precision_mixed=joint_precision_mixed)
+                              joint_precision_mixed=joint_precision_mixed,
+                              joint_precision_branches_mixed=joint_precision_branches_mixed)
     logger.info('tpe.suggest took %f seconds', time.time() - t0)
     return rand.docs_from_choices(new_ids, domain, trials, choices)
 
@@ -939,8 +943,9 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
                     shard_ids=None, shard_labels=None, shard_grid=None, joint=False, joint_discrete=False,
                     joint_quantized=False, joint_wide=False, joint_branches=False, joint_branches_mixed=False,
                     joint_branches_wide=False, joint_shard=None, joint_precision='fp32', joint_precision_wide=False,
-                    joint_precision_branches=False, joint_precision_mixed=False, joint_wide_mixed=False,
-                    joint_wide_quantized=False, joint_liar=False):
+                    joint_precision_branches=False, joint_precision_mixed=False,
+                    joint_precision_branches_mixed=False, joint_wide_mixed=False, joint_wide_quantized=False,
+                    joint_liar=False):
     """The suggest core on a structure-of-arrays history (``history.History``):
     per new id a {label: value or None} dict.  ``suggest`` wraps it with the
     Trials document layout; columnar callers (and bench.py's large configs)
@@ -1177,7 +1182,21 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
     both of ``joint_discrete`` / ``joint_quantized``, for a wide group (more than
     16 labels) or a branch group that holds a discrete or quantised label, with
     ``joint_shard`` or ``joint_liar`` it raises ValueError;
-    joint_candidate_report does not take it."""
+    joint_candidate_report does not take it.
+
+    ``joint_precision_branches_mixed=True`` (with ``joint_precision='fp64'``,
+    ``joint_branches=True``, ``joint_precision_branches=True``,
+    ``joint_branches_mixed=True`` and ``joint_discrete`` and/or
+    ``joint_quantized``): a branch group that holds discrete or quantised
+    labels is scored in float64 too (DESIGN.md "Float64 mixed branch groups"),
+    within ``joint_branches_mixed``'s limits.  All branch groups of the suggest,
+    continuous ones included, go through one Engine.run_joint_msegments_f64
+    call over the fp32 mixed segmented stage's pool bit for bit; the joined
+    values come back with the fp32 stage's types.  The root group goes where
+    ``joint_precision_mixed`` / ``joint_precision_wide`` send it; none is
+    needed.  Without one of the keywords above it raises ValueError naming it,
+    as it does with ``joint_shard``, ``joint_liar`` or a branch group of more
+    than 16 labels; joint_candidate_report does not take it."""
     if sampler not in ('philox', 'replay'):
         raise ValueError("sampler must be 'philox' or 'replay'")
     if joint_shard is not None:
@@ -1185,9 +1204,11 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
     liar_mode = _joint_liar_mode(joint_liar)
     if liar_mode:
         _joint_liar_check(joint, joint_shard, mode=liar_mode, joint_branches=joint_branches)
+    bm64 = _branches_mixed_f64(joint_precision_branches_mixed, joint_precision, joint_branches,
+                               joint_precision_branches, joint_branches_mixed, joint_discrete, joint_quantized)
     fp64 = _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, None, joint_precision_wide,
                                   joint_wide, joint_precision_branches, joint_branches,
-                                  _mixed_f64(joint_precision_mixed, joint_discrete, joint_quantized))
+                                  _mixed_f64(joint_precision_mixed, joint_discrete, joint_quantized), bm64)
     group, branch_groups = None, []
     if ((joint is not False and joint is not None) or joint_discrete or joint_quantized or joint_wide or joint_branches
             or joint_branches_mixed or joint_branches_wide or joint_wide_mixed or joint_wide_quantized):
@@ -1204,7 +1225,7 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
         if fp64:
             _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, (group, branch_groups),
                                    joint_precision_wide, joint_wide, joint_precision_branches, joint_branches,
-                                   _mixed_f64(joint_precision_mixed, joint_discrete, joint_quantized))
+                                   _mixed_f64(joint_precision_mixed, joint_discrete, joint_quantized), bm64)
     if sum(a is not None for a in (shard, shard_ids, shard_labels, shard_grid)) > 1:
         raise ValueError('shard, shard_ids, shard_labels and shard_grid are exclusive: one shard axis per suggest')
     if (shard_ids is not None or shard_labels is not None or shard_grid is not None) and sampler == 'replay':
@@ -1216,7 +1237,8 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
                                 columns, shard_ids, shard_labels, shard_grid)
     if group is not None or branch_groups:
         return _suggest_joint(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, device, columns, group,
-                              branch_groups, joint_shard, liar_mode or False, fp64)   # (fp64: every group it holds)
+                              branch_groups, joint_shard, liar_mode or False,   # (fp64: every group it holds)
+                              'branches_mixed' if fp64 and bm64 else fp64)
     return _suggest_local(table, hist, new_ids, seed, prior_weight, n_EI_candidates, gamma, sampler, precision,
                           device, shard, columns)
 
@@ -1245,8 +1267,25 @@ def _mixed_f64(joint_precision_mixed, joint_discrete, joint_quantized):
     return bool(joint_discrete or joint_quantized) if joint_precision_mixed else None
 
 
+def _branches_mixed_f64(on, joint_precision, joint_branches, joint_precision_branches, joint_branches_mixed,
+                        joint_discrete, joint_quantized):
+    """The joint_precision_branches_mixed keyword for _joint_precision_check:
+    False (off), else True; ValueError naming the first keyword it needs and
+    does not find.  Touches no device."""
+    if not on:
+        return False
+    for name, given in (("joint_precision='fp64'", joint_precision == 'fp64'), ('joint_branches=True', joint_branches),
+                        ('joint_precision_branches=True', joint_precision_branches),
+                        ('joint_branches_mixed=True', joint_branches_mixed),
+                        ('joint_discrete=True or joint_quantized=True', joint_discrete or joint_quantized)):
+        if not given:
+            raise ValueError('joint_precision_branches_mixed=True needs %s: it only scores in float64 the branch groups '
+                             'with discrete or quantised labels that those keywords make' % name)
+    return True
+
+
 def _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, plan=None, wide_f64=False, joint_wide=False,
-                           branches_f64=False, joint_branches=False, mixed_f64=None):
+                           branches_f64=False, joint_branches=False, mixed_f64=None, branches_mixed_f64=False):
     """Whether ``joint_precision`` asks for the float64 stage; ValueError for a
     value other than 'fp32' / 'fp64' and where 'fp64' does not apply: without
     ``joint``, with ``joint_shard`` or ``joint_liar``, and (``plan`` =
@@ -1262,7 +1301,10 @@ def _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, plan=
     a root group of at most TPE_JOINT_MAX_DIMS labels with discrete or
     quantised ones through; without 'fp64', without joint_discrete /
     joint_quantized, and for a wide or a branch group with such a label it
-    raises.  Touches no device."""
+    raises.  ``branches_mixed_f64`` (_branches_mixed_f64, the
+    joint_precision_branches_mixed keyword) lets branch groups with discrete or
+    quantised labels through, whatever ``mixed_f64`` says about them.  Touches
+    no device."""
     if joint_precision not in ('fp32', 'fp64'):
         raise ValueError("joint_precision must be 'fp32' or 'fp64': %r" % (joint_precision,))
     if mixed_f64 is not None and joint_precision != 'fp64':
@@ -1299,7 +1341,7 @@ def _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, plan=
         return True
     group, branch_groups = plan
     if mixed_f64:
-        for rows in branch_groups:
+        for rows in () if branches_mixed_f64 else branch_groups:
             other = [r.label for r in rows if r.dist not in _joint.JOINT_DISTS]
             if other:
                 raise ValueError('joint_precision_mixed=True does not reach branch groups: %r is discrete or quantised '
@@ -1320,7 +1362,7 @@ def _joint_precision_check(joint_precision, joint, joint_shard, liar_mode, plan=
                          'joint stage scores in fp32 only')
     for rows in branch_groups:
         other = [r.label for r in rows if r.dist not in _joint.JOINT_DISTS]
-        if other:
+        if other and not branches_mixed_f64:
             raise ValueError('joint_precision_branches=True needs branch groups of continuous labels only: %r is '
                              'discrete or quantised (joint_branches_mixed), and the mixed segmented joint stage scores '
                              'in fp32 only' % other[0])
@@ -2024,7 +2066,8 @@ def _suggest_branches(engine, hist, ids, seed, prior_weight, n_EI_candidates, ga
     hold discrete or quantised labels (Engine.run_joint_msegments_liar, with
     each model's centres()).  ``fp64`` (joint_precision_branches): the one call
     is Engine.run_joint_segments(precision='fp64'), over the same stream words
-    and so the same candidates."""
+    and so the same candidates; 'branches_mixed'
+    (joint_precision_branches_mixed): Engine.run_joint_msegments_f64."""
     below_tids = _history.split_below(hist, gamma)
     models, words, prob_seg, prob_id, where = [], [], [], [], []
     for rows in branch_groups:
@@ -2052,6 +2095,8 @@ def _suggest_branches(engine, hist, ids, seed, prior_weight, n_EI_candidates, ga
                 centres=[m.centres() if hasattr(m, 'centres') else None for m in models])
         else:
             rec = engine.run_joint_segments_liar(models, words, prob_seg, prob_id, int(n_EI_candidates), seed, liar=W)
+    elif fp64 == 'branches_mixed':                   # (joint_precision_branches_mixed: all groups in the one call)
+        rec = engine.run_joint_msegments_f64(models, words, prob_seg, prob_id, int(n_EI_candidates), seed)
     elif fp64:
         rec = engine.run_joint_segments(models, words, prob_seg, prob_id, int(n_EI_candidates), seed, precision='fp64')
     elif parts is None and not any(_is_wide_branch(w[0]) for w in where):

@@ -2185,6 +2185,132 @@ int tpe_joint_mseg_run(const tpe_joint_mseg_args* args, tpe_joint_record* record
                        double* g_out, void* scratch, uint64_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Float64 mixed segmented joint stage (tpe_joint.hip; additive to ABI 24): the
+ * mixed segmented stage above with the scoring of the float64 mixed joint stage
+ * (DESIGN.md "Float64 mixed branch groups").  A segment with n_cat + n_quant > 0
+ * is a group of tpe_joint_mq_f64_args' kind, a segment with neither one of
+ * tpe_joint_f64_args' kind.  tpe_joint_mseg_f64 starts with the fields of
+ * tpe_joint_mseg at the same offsets; of these the six f32 density-row offsets,
+ * the four f32 miss / bonus offsets and `table` are NOT read.  Then, as ELEMENT
+ * offsets in pool_f64 unless said otherwise:
+ *   below_mu64 .. above_c64   the density rows unrounded (tpe_joint_mq_f64_args;
+ *                             a continuous segment: tpe_joint_f64_args')
+ *   centre                    as tpe_joint_f64_args.centre (the continuous
+ *                             coordinates; entries from n_dims on: ignored)
+ *   below_miss64 .. above_bonus64   the f64 category tables [sum U_d]
+ *   psi      the segment's range in the f64 area of `scratch` (that area starts
+ *            at tpe_joint_mseg_scratch_bytes filled up to a multiple of 16
+ *            bytes): the layout of tpe_joint_seg_f64.psi, with DP the padded
+ *            width of the segment's kernel class: 1, 2, 4, 8 for n_dims = 0 .. 8
+ *            continuous coordinates beside a discrete or quantised one (n_dims
+ *            = 0: the constant entry alone), tpe_joint_seg_f64's widths for a
+ *            continuous segment
+ *   table64  the segment's range in `quant_table64`, one caller-owned device
+ *            workspace of f64: the below side's [sum V][S_below], then the above
+ *            side's [sum V][S_above], S = K rounded up to a multiple of 16 (the
+ *            layout of tpe_joint_mq_f64_args.quant_table64)
+ * psi ranges and table ranges must not overlap one another;
+ * tpe_joint_mseg_f64_scratch_bytes / _table_bytes size the ranges of all
+ * segments laid end to end in descriptor order.  The component categories in
+ * below_cat / above_cat are integers in [-1, U_d) (-1: the prior row).
+ *
+ * Defining property: the record, the cand rows, l_out and g_out of problem p =
+ * (prob_id[p], segment prob_seg[p]) are byte for byte those of the solo
+ * float64 run over that segment's rows and centres with its stream_word, ids =
+ * [prob_id[p]] and the same seed, n_cand and flags:
+ * tpe_joint_mq_f64_run when n_cat + n_quant > 0, else tpe_joint_f64_run; the
+ * candidates are those of tpe_joint_mseg_run.  The order of the problems does
+ * not matter; the same call twice gives the same bytes (plain vector stores, no
+ * atomics).
+ *
+ * Launches, all on `stream` with no sync between them: k_joint_seg_order (ranks
+ * the problems by kernel class: the eight continuous DP classes, then the mixed
+ * classes DP = 1, 2, 4, 8; then segment, then index), k_joint_mseg_f64_psi (psi
+ * of every segment, once a call, entry by entry the solo stages' psi_entry),
+ * k_joint_mseg_f64_qtable (one launch: the f64 tables of every quantised segment
+ * and side, k_joint_qtable_f64's arithmetic: unfloored, an exactly-zero mass is
+ * -inf), one chunk launch per class present — a continuous class runs
+ * k_joint_seg_f64_chunk's body, a mixed one k_joint_mseg_f64_chunk<DP>: the pass
+ * of k_joint_mq_f64_chunk with its psi tiles copied from the segment's range, a
+ * tile's component categories staged as integer codes beside their f64 bonus,
+ * and a lane's 16 candidates' category codes and lattice indices packed into
+ * three 32-bit words a candidate and held in registers for the pass — and
+ * k_joint_merge over all problems.
+ *
+ * Limits: tpe_joint_mseg's.  tpe_joint_mseg_f64_run returns TPE_E_ARG before any
+ * launch (no device needed) for everything tpe_joint_mseg_run and
+ * tpe_joint_seg_f64_run check (rows: the ones this stage reads), a centre that
+ * is not finite, a null table workspace with a quantised segment, scratch
+ * smaller than tpe_joint_mseg_f64_scratch_bytes says, and a psi range or a table
+ * that leaves its area or overlaps another segment's.  tpe_joint_profile covers
+ * this stage as it covers tpe_joint_seg_run; tpe_joint_mseg_f64_profile reads
+ * the psi and the table kernel's time of the last profiled run (the table's: 0
+ * without a quantised segment).
+ * ---------------------------------------------------------------------- */
+typedef struct tpe_joint_mseg_f64 {
+  int32_t n_dims, k_below, k_above;       /* as tpe_joint_mseg ... */
+  uint32_t stream_word;
+  double below_base, above_base;
+  int64_t below_mu, below_a, below_c;     /* (the f32 density rows: not read) */
+  int64_t above_mu, above_a, above_c;
+  int64_t samp;
+  int64_t inject;
+  int64_t samp_cum;
+  float lo[TPE_JOINT_MAX_DIMS], hi[TPE_JOINT_MAX_DIMS];
+  int32_t n_cat, n_quant;
+  int32_t cat_upper[TPE_JOINT_MSEG_MAX_CAT], cat_off[TPE_JOINT_MSEG_MAX_CAT];
+  int32_t quant_v[TPE_JOINT_MAX_QUANT], quant_edge_off[TPE_JOINT_MAX_QUANT];
+  float qlo[TPE_JOINT_MAX_QUANT], qhi[TPE_JOINT_MAX_QUANT];
+  int32_t n_edges, reserved;
+  int64_t below_cat, above_cat;
+  int64_t below_miss, below_bonus, above_miss, above_bonus;   /* (the f32 tables: not read) */
+  int64_t quant_samp;
+  int64_t below_h, cat_cum;
+  int64_t quant_edges;
+  int64_t below_qmu, below_qsigma, above_qmu, above_qsigma;
+  int64_t table;                          /* (the f32 table: not read) ... up to here */
+  int64_t below_mu64, below_a64, below_c64;   /* element offsets in pool_f64 */
+  int64_t above_mu64, above_a64, above_c64;
+  double centre[TPE_JOINT_MAX_DIMS];
+  int64_t below_miss64, below_bonus64, above_miss64, above_bonus64;
+  int64_t psi;                            /* element offset in the f64 area of scratch */
+  int64_t table64;                        /* element offset in quant_table64 */
+} tpe_joint_mseg_f64;
+typedef struct tpe_joint_mseg_f64_args {
+  int32_t n_segs, n_probs, n_cand, flags;   /* as tpe_joint_mseg_args ... */
+  uint64_t seed;
+  const tpe_joint_mseg_f64* segs;
+  const tpe_joint_mseg_f64* host_segs;
+  const float* pool_f32;
+  const double* pool_f64;                   /* (needed under TPE_JOINT_INJECT too) */
+  int64_t pool_f32_len, pool_f64_len;
+  const int32_t* prob_seg;
+  const int32_t* host_prob_seg;
+  const int64_t* prob_id;
+  const int64_t* cand_off;                  /* ... up to here */
+  double* quant_table64;                    /* device workspace (may be NULL without a quantised segment) */
+  uint64_t quant_table64_bytes;
+} tpe_joint_mseg_f64_args;
+
+/* tpe_joint_mseg_scratch_bytes(n_probs, n_cand) filled up to a multiple of 16
+ * bytes, then per host descriptor (ceil(k_below / 16) + ceil(k_above / 16)) * NI
+ * * 512 bytes of psi, NI = ceil((2 DP + 1) / 4) */
+int tpe_joint_mseg_f64_scratch_bytes(const tpe_joint_mseg_f64* host_segs, int32_t n_segs, int32_t n_probs,
+                                     int32_t n_cand, uint64_t* bytes);
+
+/* the table workspace of the host descriptors: sum over the segments with
+ * n_quant > 0 of (S_below + S_above) * sum_d V_d doubles */
+int tpe_joint_mseg_f64_table_bytes(const tpe_joint_mseg_f64* host_segs, int32_t n_segs, uint64_t* bytes);
+
+/* records, cand, l_out, g_out, scratch and stream as tpe_joint_mseg_run */
+int tpe_joint_mseg_f64_run(const tpe_joint_mseg_f64_args* args, tpe_joint_record* records, float* cand,
+                           double* l_out, double* g_out, void* scratch, uint64_t scratch_bytes, void* stream);
+
+/* the psi kernel's and the table kernel's device time of the last profiled
+ * tpe_joint_mseg_f64_run */
+int tpe_joint_mseg_f64_profile(double* psi_ms, double* table_ms);
+
+/* ------------------------------------------------------------------------
  * Sharded joint stage (additive export; the ABI stays 24).  Any of the six
  * joint stages over the candidates [cand_base, cand_base + n_cand) of a run of
  * n_cand_global candidates: a rank's share of a candidate-sharded joint

@@ -1,5 +1,5 @@
 """Time the segmented joint stage against one tpe_joint_run per branch group.
-Usage: python tools/joint_branch_time.py [--pairs 7] [--warmup 2] [--out FILE] [--small] [--wide | --fp64]
+Usage: python tools/joint_branch_time.py [--pairs 7] [--warmup 2] [--out FILE] [--small] [--wide | --fp64 [--mixed]]
 
 Two workloads (DESIGN.md "Branch groups"), each with two routes to the same
 winners, alternating in one process, each timed from a synchronised device to
@@ -50,7 +50,20 @@ must be group64's bytes.  A difference of two medians is `shown` only if it
 exceeds three times the larger of the two ranges.  Each
 line also holds the worst distance of seg32's l and g from seg64's over the
 shared pool, as a fraction of 1e-5 max(1, |ref|); a last line does that for a
-clustered branch (every bandwidth psig / 100)."""
+clustered branch (every bandwidth psig / 100).
+
+--fp64 --mixed: the float64 mixed segmented stage (DESIGN.md "Float64 mixed
+branch groups"), appended to profiles/joint_branch_mq_fp64_time.jsonl, the same
+three routes over groups with discrete and quantised labels:
+  seg64      one Engine.run_joint_msegments_f64 call
+  group64    one Engine.run_joint_quant / run_joint_mixed(precision='fp64',
+             stream_word=...) per group
+  seg32      one Engine.run_joint_segments call (tpe_joint_mseg_run)
+Workloads: (a) 64 ids over 8 groups of 3 continuous labels + a choice of 4 + a
+quniform of 32, 2,000 trials a group, C = 4096; (b) 1 id, one group of a
+quniform of 50 x a choice of 2 (no continuous label), 10,000 trials, C = 2^20;
+(c) 1 id, one group of 3 continuous labels + a quniform of 256, 10,000 trials,
+C = 2^20.  The psi and the table kernel: tpe_joint_mseg_f64_profile."""
 import argparse
 import ctypes
 import json
@@ -108,6 +121,25 @@ def make_clustered_group(n, seed):
     nb = min(int(np.ceil(0.25 * np.sqrt(n))), 25)
     low, high = np.array([-5.0, -3.0, -np.inf, 0.0]), np.array([5.0, 2.0, np.inf, 1.0])
     return J.side_mixture(X[:nb], priors), J.side_mixture(X[nb:], priors), low, high
+
+
+def make_mixed_group(n, seed, Dc, us, Vs):
+    """make_group's first Dc coordinates, then a category of u values for every
+    u in us and a lattice of V values for every V in Vs, each trial's drawn at
+    random; a component's lattice bandwidth is V / 8 (the prior row: V):
+    (below, above, low, high, cats, quants) as Engine.run_joint_quant takes them."""
+    below, above, low, high = make_group(n, seed)
+    rs = np.random.RandomState(seed + 1)
+    sides = [(w, np.asarray(mu)[:, :Dc], np.asarray(sg)[:, :Dc]) for w, mu, sg in (below[:3], above[:3])]
+    kb, ka = len(below[0]), len(above[0])
+    cats = [(np.concatenate([[-1], rs.randint(0, u, kb - 1)]), np.concatenate([[-1], rs.randint(0, u, ka - 1)]),
+             np.full(u, 1.0 / u), 1.0, 1.0) for u in us]
+    quants = []
+    for V in Vs:
+        side = [x for K in (kb, ka) for x in (np.concatenate([[0.5 * (V - 1)], np.rint(rs.uniform(0, V - 1, K - 1))]),
+                                              np.concatenate([[float(V)], np.full(K - 1, V / 8.0)]))]
+        quants.append(tuple(side) + (np.arange(V + 1) - 0.5,))
+    return sides[0], sides[1], low[:Dc], high[:Dc], cats, quants
 
 
 def stats(x):
@@ -230,7 +262,7 @@ def shown(x, y):
     return bool(abs(np.median(x) - np.median(y)) > 3 * max(np.ptp(x), np.ptp(y)))
 
 
-def measure_fp64(name, eng, models, words, prob_seg, prob_id, C, args, time_it=True):
+def measure_fp64(name, eng, models, words, prob_seg, prob_id, C, args, time_it=True, mixed=False):
     import torch
     from hyperopt_amd import _native as N
     lib = eng.lib
@@ -238,31 +270,44 @@ def measure_fp64(name, eng, models, words, prob_seg, prob_id, C, args, time_it=T
     groups = [(s, prob_id[prob_seg == s]) for s in range(len(models))]
 
     def seg(precision, **kw):
+        if mixed and precision == 'fp64':
+            return eng.run_joint_msegments_f64(models, words, prob_seg, prob_id, C, SEED, **kw)
         return eng.run_joint_segments(models, words, prob_seg, prob_id, C, SEED, precision=precision, **kw)
 
+    def solo64(s, ids):
+        if not mixed:
+            return eng.run_joint(*models[s], ids, C, SEED, stream_word=words[s], precision='fp64')
+        b, a, lo, hi, cats, quants = models[s]
+        if quants:
+            return eng.run_joint_quant(b, a, lo, hi, cats, quants, ids, C, SEED, stream_word=words[s], precision='fp64')
+        return eng.run_joint_mixed(b, a, lo, hi, cats, ids, C, SEED, stream_word=words[s], precision='fp64')
+
     def group64():
-        return [eng.run_joint(*models[s], ids, C, SEED, stream_word=words[s], precision='fp64') for s, ids in groups]
+        return [solo64(s, ids) for s, ids in groups]
     routes = dict(seg64=lambda: seg('fp64'), group64=group64, seg32=lambda: seg('fp32'))
 
     def events(route):
-        """{launches before the merge, merge, psi kernel} of one profiled run of the route, in ms."""
-        ms2, psi, tot = (ctypes.c_double * 2)(), ctypes.c_double(0.0), [0.0, 0.0, 0.0]
+        """{launches before the merge, merge, psi kernel, mixed: table kernel} of one profiled run of the route, in ms."""
+        ms2, psi, tab, tot = (ctypes.c_double * 2)(), ctypes.c_double(0.0), ctypes.c_double(0.0), [0.0, 0.0, 0.0, 0.0]
         torch.cuda.synchronize()
         N.check(lib.tpe_joint_profile(1, None), lib, 'tpe_joint_profile')
         for s, ids in (groups if route == 'group64' else [(None, None)]):   # (the per-group route: read after every call)
             if route == 'group64':
-                eng.run_joint(*models[s], ids, C, SEED, stream_word=words[s], precision='fp64')
+                solo64(s, ids)
             else:
                 routes[route]()
-            if route == 'seg64':
+            if route == 'seg64' and mixed:
+                N.check(lib.tpe_joint_mseg_f64_profile(ctypes.byref(psi), ctypes.byref(tab)), lib,
+                        'tpe_joint_mseg_f64_profile')
+            elif route == 'seg64':
                 N.check(lib.tpe_joint_seg_f64_profile(ctypes.byref(psi)), lib, 'tpe_joint_seg_f64_profile')
             N.check(lib.tpe_joint_profile(1, ms2), lib, 'tpe_joint_profile')
-            tot = [tot[0] + ms2[0], tot[1] + ms2[1], psi.value]
+            tot = [tot[0] + ms2[0], tot[1] + ms2[1], psi.value, tab.value]
         N.check(lib.tpe_joint_profile(0, None), lib, 'tpe_joint_profile')
         return tot
 
-    line = dict(tool='joint_branch_time --fp64', workload=name, n_groups=len(models), n_problems=int(len(prob_seg)),
-                n_dims=len(models[0][2]), n_cand=C, k_below=[len(m[0][0]) for m in models],
+    line = dict(tool='joint_branch_time --fp64' + (' --mixed' if mixed else ''), workload=name, n_groups=len(models),
+                n_problems=int(len(prob_seg)), n_dims=len(models[0][2]), n_cand=C, k_below=[len(m[0][0]) for m in models],
                 k_above=[len(m[1][0]) for m in models], pairs=args.pairs, warmup=args.warmup)
     # the fp32 stage's distance from the float64 stage over the shared pool, in units of the fp32 tolerance
     r64, r32 = seg('fp64', return_cand=True, want_lg=True), seg('fp32', return_cand=True, want_lg=True)
@@ -287,8 +332,9 @@ def measure_fp64(name, eng, models, words, prob_seg, prob_id, C, args, time_it=T
         for i in range(args.pairs):
             for k in routes:
                 kern[k].append(events(k))
-        evals = float(sum(len(ids) * C * (len(models[s][0][0]) + len(models[s][1][0])) * len(models[s][2])
-                          for s, ids in groups))
+        # (mixed: a category or lattice slot counts as a dimension)
+        evals = float(sum(len(ids) * C * (len(models[s][0][0]) + len(models[s][1][0]))
+                          * (len(models[s][2]) + sum(len(x) for x in models[s][4:])) for s, ids in groups))
         pre = dict((k, [e[0] for e in kern[k]]) for k in routes)
         # seg64's launches before the merge without the psi kernel: what compares with k_joint_f64_chunk
         chunk64 = [e[0] - e[2] for e in kern['seg64']]
@@ -296,7 +342,8 @@ def measure_fp64(name, eng, models, words, prob_seg, prob_id, C, args, time_it=T
                     wall_ms=dict((k, stats(v)) for k, v in wall.items()),
                     kernel_ms=dict([(k + '_before_merge', stats(v)) for k, v in pre.items()] +
                                    [('seg64_psi', stats([e[2] for e in kern['seg64']])),
-                                    ('seg64_without_psi', stats(chunk64))]),
+                                    ('seg64_without_psi', stats(chunk64))] +
+                                   ([('seg64_table', stats([e[3] for e in kern['seg64']]))] if mixed else [])),
                     evals_per_s=dict(seg64=evals / (np.median(pre['seg64']) * 1e-3),
                                      group64=evals / (np.median(pre['group64']) * 1e-3),
                                      seg32=evals / (np.median(pre['seg32']) * 1e-3)),
@@ -307,7 +354,8 @@ def measure_fp64(name, eng, models, words, prob_seg, prob_id, C, args, time_it=T
     line['gpu'] = torch.cuda.get_device_name(0)
     text = json.dumps(line)
     print(text)
-    out = args.out or os.path.join(ROOT, 'profiles', 'joint_branch_fp64_time.jsonl')
+    out = args.out or os.path.join(ROOT, 'profiles', 'joint_branch_mq_fp64_time.jsonl' if mixed
+                                   else 'joint_branch_fp64_time.jsonl')
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, 'a') as f:
         f.write(text + '\n')
@@ -321,6 +369,7 @@ def main():
     ap.add_argument('--small', action='store_true')
     ap.add_argument('--wide', action='store_true')
     ap.add_argument('--fp64', action='store_true')
+    ap.add_argument('--mixed', action='store_true')
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -336,6 +385,19 @@ def main():
         prob_id = np.arange(n_a, n_a + 64, dtype=np.int64)
         measure('wide a: 64 ids over 4 groups', eng, models, words, np.arange(64) % 4, prob_id, 4096, args)
         measure('wide b: 1 id, 1 group', eng, [make_wide_group(32, n_b, SEED)], [0xFFFFFFFE], [0], [n_b], c_b, args)
+        return 0
+    if args.mixed and not args.fp64:
+        print('--mixed goes with --fp64', file=sys.stderr)
+        return 2
+    if args.mixed:
+        words = [0xFFFFFFFE - 5 * s for s in range(8)]
+        measure_fp64('mixed a: 64 ids over 8 groups of 3 + choice 4 + quniform 32', eng,
+                     [make_mixed_group(n_a, SEED + s, 3, (4,), (32,)) for s in range(8)], words, np.arange(64) % 8,
+                     np.arange(n_a, n_a + 64, dtype=np.int64), 4096, args, mixed=True)
+        measure_fp64('mixed b: 1 id, quniform 50 x choice 2', eng, [make_mixed_group(n_b, SEED, 0, (2,), (50,))],
+                     [0xFFFFFFFE], [0], [n_b], c_b, args, mixed=True)
+        measure_fp64('mixed c: 1 id, 3 + quniform 256', eng, [make_mixed_group(n_b, SEED, 3, (), (256,))], [0xFFFFFFFE],
+                     [0], [n_b], c_b, args, mixed=True)
         return 0
     models = [make_group(n_a, SEED + s) for s in range(8)]
     words = [0xFFFFFFFE - 5 * s for s in range(8)]
