@@ -84,6 +84,7 @@ JOINT_MAX_CAT_TOTAL = 1024     # TPE_JOINT_MAX_CAT_TOTAL: categories of a joint 
 JOINT_MAX_QUANT = 4            # TPE_JOINT_MAX_QUANT: quantised labels of a joint group
 JOINT_MAX_LATTICE = 256        # TPE_JOINT_MAX_LATTICE: lattice values of one joined quantised label
 JOINT_MAX_LATTICE_TOTAL = 512  # TPE_JOINT_MAX_LATTICE_TOTAL: lattice values of a joint group
+JOINT_MAX_LATTICE_LARGE = 65536  # TPE_JOINT_MAX_LATTICE_LARGE: lattice values of a label of tpe_joint_quant_large_run
 JOINT_QFLOOR = -4096.0         # TPE_JOINT_QFLOOR: the smallest stored log2 P_kd(i)
 JOINT_QUANT_MAX_CONT = 8       # continuous / discrete labels beside a quantised one
 JOINT_QUANT_MAX_DISC = 4
@@ -654,6 +655,7 @@ EXPORTS = ('tpe_abi_version', 'tpe_last_error', 'tpe_device_count', 'tpe_tile_si
            'tpe_report_profile', 'tpe_joint_scratch_bytes', 'tpe_joint_run', 'tpe_joint_profile',
            'tpe_joint_f64_scratch_bytes', 'tpe_joint_f64_run',
            'tpe_joint_mixed_run', 'tpe_joint_quant_table_bytes', 'tpe_joint_quant_run', 'tpe_joint_quant_profile',
+           'tpe_joint_quant_large_lds_bytes', 'tpe_joint_quant_large_run',
            'tpe_joint_mq_f64_scratch_bytes', 'tpe_joint_mq_f64_table_bytes', 'tpe_joint_mq_f64_run',
            'tpe_joint_mq_f64_profile',
            'tpe_joint_wide_scratch_bytes', 'tpe_joint_wide_run', 'tpe_joint_wide_profile',
@@ -804,6 +806,10 @@ def load(path=LIB_PATH):
     lib.tpe_joint_quant_run.restype = ctypes.c_int
     lib.tpe_joint_quant_profile.argtypes = [P]
     lib.tpe_joint_quant_profile.restype = ctypes.c_int
+    lib.tpe_joint_quant_large_lds_bytes.argtypes = [ctypes.POINTER(I32), I32, ctypes.POINTER(ctypes.c_uint64)]
+    lib.tpe_joint_quant_large_lds_bytes.restype = ctypes.c_int
+    lib.tpe_joint_quant_large_run.argtypes = [ctypes.POINTER(JointQuantArgs), P, P, P, P, P, ctypes.c_uint64, P]
+    lib.tpe_joint_quant_large_run.restype = ctypes.c_int
     lib.tpe_joint_mq_f64_scratch_bytes.argtypes = [I32, I32, ctypes.POINTER(ctypes.c_uint64)]
     lib.tpe_joint_mq_f64_scratch_bytes.restype = ctypes.c_int
     lib.tpe_joint_mq_f64_table_bytes.argtypes = [I32, I32, I32, ctypes.POINTER(ctypes.c_uint64)]

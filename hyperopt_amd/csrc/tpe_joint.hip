@@ -835,22 +835,43 @@ __device__ __forceinline__ double bin_mass(double ta, double sa, double tb, doub
 // One (component, dimension) column of a side's table: walk the V + 1 edges e of
 // the dimension once, one erfc per edge (the smaller tail), shared by the two
 // bins that meet there; out[i * K] = log2 P(i), as f32 floored at TPE_JOINT_QFLOOR.
+// What every table entry is made of (k_joint_qtable's full columns and the
+// chunk-local mini-table of k_joint_quant_large_chunk call these, so an entry is
+// the same bytes wherever it is evaluated): an edge e of a component (m, r =
+// 1 / (sigma sqrt 2)) as its standardised place and its smaller tail ...
+struct QEdge {
+  double t, s;
+};
+__device__ __forceinline__ QEdge q_edge(double e, double m, double r) {
+  const double t = (e - m) * r;
+  return QEdge{t, small_tail(fabs(t))};
+}
+// ... log2 of the mass between two edges a < b (the whole range [e_0, e_V): lmass) ...
+__device__ __forceinline__ double q_log2_mass(const QEdge& a, const QEdge& b) {
+  return log2(bin_mass(a.t, a.s, b.t, b.s));
+}
+// ... and the entry log2 P(i) of the bin between them: as f32 floored at
+// TPE_JOINT_QFLOOR, -inf (a far bin's mass is 0) and NaN included; T = double
+// (the float64 mixed stage): unrounded, a zero mass -inf.
+template <typename T>
+__device__ __forceinline__ T q_entry(const QEdge& a, const QEdge& b, double lmass) {
+  double v = q_log2_mass(a, b) - lmass;
+  if constexpr (std::is_same<T, float>::value)
+    if (!(v >= kQFloor)) v = kQFloor;
+  return (T)v;
+}
+
 template <typename T>
 __device__ __forceinline__ void qtable_column(double m, double s, const double* __restrict__ e, int V,
                                               T* __restrict__ out, int64_t K) {
   const double r = 0.70710678118654752440 / s;
-  const double t0 = (e[0] - m) * r, tv = (e[V] - m) * r;
-  const double s0 = small_tail(fabs(t0)), sv = small_tail(fabs(tv));
-  const double lmass = log2(bin_mass(t0, s0, tv, sv));
-  double ta = t0, sa = s0;
+  const QEdge e0 = q_edge(e[0], m, r), ev = q_edge(e[V], m, r);
+  const double lmass = q_log2_mass(e0, ev);
+  QEdge a = e0;
   for (int i = 0; i < V; ++i) {
-    const double tb = i + 1 < V ? (e[i + 1] - m) * r : tv;
-    const double sb = i + 1 < V ? small_tail(fabs(tb)) : sv;
-    double v = log2(bin_mass(ta, sa, tb, sb)) - lmass;
-    if constexpr (std::is_same<T, float>::value)
-      if (!(v >= kQFloor)) v = kQFloor;     // -inf (a far bin's mass is 0) and NaN included
-    out[i * K] = (T)v;                      // (T = double, the float64 mixed stage: unrounded, a zero mass -inf)
-    ta = tb; sa = sb;
+    const QEdge b = i + 1 < V ? q_edge(e[i + 1], m, r) : ev;
+    out[i * K] = q_entry<T>(a, b, lmass);
+    a = b;
   }
 }
 
@@ -900,6 +921,11 @@ struct QuantIO {
   const double* edges;
   const float* qsamp;
   const float *bT, *aT;             // [total][K] of a side
+  // k_joint_quant_large_chunk only (it has no bT / aT, and tile, stride and total are the chunk's own): per
+  // dimension the count and the first mini-table row of the chunk's distinct lattice indices, the indices
+  // themselves (LDS, ascending per dimension), and the floats of LDS the mini-table may take
+  int nd[QP], boff[QP], mt_floats;
+  const uint16_t* bins;
 };
 
 // the longest tile (a multiple of 8 components, at most kTileK) whose table of
@@ -919,14 +945,24 @@ __host__ __device__ __forceinline__ int quant_tile(int total) {
 // consecutive components of its own lattice value with one 16-byte read; qo is
 // that value's row offset in floats.  Components are taken four at a time: the
 // tile's tail is padded with c = -3e38 (such a term adds 2^-inf = 0).
-template <int CP, int KP, int QP>
+// LARGE (k_joint_quant_large_chunk): there is no table T; row b of the tile is
+// distinct lattice index p.bins[b] of the chunk, and the tile's entries are
+// evaluated here, per (row, tile component), in f64 from the side's qmu / qsigma
+// and the row's two edges: q_entry, the bytes k_joint_qtable would store there.
+// Lane kk of a run of nk4 lanes owns tile component kk and walks a contiguous
+// share of a dimension's rows (ascending lattice indices): where two rows are
+// neighbours on the lattice, the edge between them costs one erfc, not two; its
+// stores of one row are nk4 consecutive floats.
+template <int CP, int KP, int QP, bool LARGE = false>
 __device__ __forceinline__ void score_side_quant(const float* __restrict__ mu, const float* __restrict__ a,
                                                  const float* __restrict__ c, const float* __restrict__ cat,
                                                  const float* __restrict__ miss, const float* __restrict__ bonus,
                                                  const float* __restrict__ T, int K, const QuantIO<CP, KP, QP>& p,
                                                  const float (&z)[kR][CP + KP + QP], const int (&qo)[kR][QP],
                                                  float* __restrict__ rows, float* __restrict__ cl,
-                                                 float* __restrict__ qt, double (&out)[kR]) {
+                                                 float* __restrict__ qt, double (&out)[kR],
+                                                 const double* __restrict__ qmu = nullptr,
+                                                 const double* __restrict__ qsigma = nullptr) {
   constexpr int S = 2 * CP + KP, KPa = KP > 0 ? KP : 1;
   const int Dc = p.m.q.D, Dk = p.m.Dk, tile = p.tile, stride = p.stride;
   float m[kR], s[kR], nb[kR][KPa];
@@ -955,9 +991,36 @@ __device__ __forceinline__ void score_side_quant(const float* __restrict__ mu, c
         rows[kk * S + 2 * CP + d] = (d < Dk && kk < nk) ? cat[(int64_t)(k0 + kk) * Dk + d] : -1.f;
       }
     for (int e = threadIdx.x; e < nk4; e += kThreads) cl[e] = e < nk ? c[k0 + e] : -3.0e38f;
-    for (int e = threadIdx.x; e < p.total * tile; e += kThreads) {
-      const int b = e / tile, kk = e - b * tile;         // a run over k of one lattice value: coalesced
-      if (kk < nk4) qt[b * stride + kk] = kk < nk ? T[(int64_t)b * K + k0 + kk] : 0.f;
+    if constexpr (!LARGE) {
+      for (int e = threadIdx.x; e < p.total * tile; e += kThreads) {
+        const int b = e / tile, kk = e - b * tile;         // a run over k of one lattice value: coalesced
+        if (kk < nk4) qt[b * stride + kk] = kk < nk ? T[(int64_t)b * K + k0 + kk] : 0.f;
+      }
+    } else {
+      const int Dq = p.Dq, segs = kThreads / nk4, seg = (int)threadIdx.x / nk4, kk = (int)threadIdx.x - seg * nk4;
+#pragma unroll
+      for (int d = 0; d < QP; ++d) {
+        if (d >= Dq || seg >= segs) continue;
+        const int n = p.nd[d], per = (n + segs - 1) / segs, b0 = seg * per, b1 = min(n, b0 + per);
+        float* col = qt + (p.boff[d] + b0) * stride + kk;
+        if (kk >= nk) {                                    // the tile's padded tail
+          for (int b = b0; b < b1; ++b, col += stride) *col = 0.f;
+          continue;
+        }
+        const double* e = p.edges + p.eoff[d];
+        const int64_t src = (int64_t)(k0 + kk) * Dq + d;
+        const double m = qmu[src], r = 0.70710678118654752440 / qsigma[src];
+        const double lmass = q_log2_mass(q_edge(e[0], m, r), q_edge(e[p.V[d]], m, r));
+        int prev = -2;
+        QEdge hi{0.0, 0.0};
+        for (int b = b0; b < b1; ++b, col += stride) {
+          const int i = p.bins[p.boff[d] + b];             // < V_d: i + 1 is an edge
+          const QEdge lo = i == prev + 1 ? hi : q_edge(e[i], m, r);
+          hi = q_edge(e[i + 1], m, r);
+          *col = q_entry<float>(lo, hi, lmass);
+          prev = i;
+        }
+      }
     }
     __syncthreads();
     for (int k4 = 0; k4 < nk4; k4 += 4) {
@@ -1012,20 +1075,137 @@ __device__ __forceinline__ void score_side_quant(const float* __restrict__ mu, c
   }
 }
 
+// ---- large lattices (include/tpe_hip.h "Large lattices"): the chunk-local lattice
+// Whatever V_d is, the TPE_JOINT_CHUNK candidates of a chunk hold at most that
+// many distinct lattice indices of dimension d.  Per dimension the workgroup
+// sorts the keys (lattice index << 10 | candidate slot) in LDS, marks the first
+// key of every run of equal indices and scans the marks: run number = the
+// index's row in the chunk's mini-table.  Plain LDS stores, no atomics.
+constexpr int kQLTileBytes = 40 * 1024;     // the mini-table's share of the LDS, unless its shortest tile needs more
+static_assert(TPE_JOINT_CHUNK == kR * kThreads && TPE_JOINT_CHUNK == 1024 && TPE_JOINT_MAX_LATTICE_LARGE <= 65536,
+              "a key holds the lattice index above 10 bits of candidate slot; a row and an index fit 16 bits");
+// floats of LDS for the mini-table of a launch whose chunks hold at most nmax - 1
+// distinct lattice indices (nmax: with the padded slots' zero row): its shortest
+// tile, 4 components at stride 8, always fits
+__host__ __device__ __forceinline__ int quant_large_floats(int nmax) { return nmax * 8 > kQLTileBytes / 4 ? nmax * 8 : kQLTileBytes / 4; }
+// the scratch of the compaction lies where the mini-table is built afterwards
+static_assert(kQLTileBytes >= TPE_JOINT_CHUNK * 6 + 64, "keys, rows and the waves' counts");
+
+// bitonic sort of the chunk's keys, ascending: two compare-exchanges a thread and step
+__device__ __forceinline__ void sort_chunk_keys(uint32_t* __restrict__ keys) {
+  const int t = threadIdx.x;
+  for (int k = 2; k <= TPE_JOINT_CHUNK; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      __syncthreads();
+#pragma unroll
+      for (int h = 0; h < TPE_JOINT_CHUNK / 2 / kThreads; ++h) {
+        const int e = h * kThreads + t;
+        const int i = ((e & ~(j - 1)) << 1) | (e & (j - 1)), l = i | j;   // the pair (i, i + j), bit j of i clear
+        const uint32_t a = keys[i], b = keys[l];
+        if ((a > b) == ((i & k) == 0)) { keys[i] = b; keys[l] = a; }
+      }
+    }
+  __syncthreads();
+}
+
+// Fills p.nd / p.boff / p.bins / p.total and the chunk's own tile and stride, qo
+// (a candidate's row offset in the mini-table, the zero row for a padded slot
+// and a candidate beyond C) and the zero row itself.  qt: [p.mt_floats] floats,
+// then the distinct indices as uint16 (at most min(V_d, TPE_JOINT_CHUNK) a dimension).
+template <int CP, int KP, int QP>
+__device__ __forceinline__ void compact_chunk_lattice(QuantIO<CP, KP, QP>& p, int first,
+                                                      const float (&z)[kR][CP + KP + QP], int (&qo)[kR][QP],
+                                                      float* __restrict__ qt) {
+  const int t = threadIdx.x, C = p.m.q.C, Dq = p.Dq;
+  uint32_t* keys = reinterpret_cast<uint32_t*>(qt);                          // [TPE_JOINT_CHUNK]
+  uint16_t* crow = reinterpret_cast<uint16_t*>(keys + TPE_JOINT_CHUNK);      // [TPE_JOINT_CHUNK] by candidate slot
+  int* wtot = reinterpret_cast<int*>(crow + TPE_JOINT_CHUNK);                // [kThreads / 64]
+  uint16_t* bins = reinterpret_cast<uint16_t*>(qt + p.mt_floats);
+  int n_total = 0, row[kR][QP];
+#pragma unroll
+  for (int d = 0; d < QP; ++d) {
+    p.nd[d] = 0; p.boff[d] = n_total;
+#pragma unroll
+    for (int r = 0; r < kR; ++r) row[r][d] = -1;
+    if (d >= Dq) continue;
+    __syncthreads();                         // the previous dimension's rows are read
+#pragma unroll
+    for (int r = 0; r < kR; ++r) {
+      const int sl = r * kThreads + t;
+      keys[sl] = first + sl < C ? ((uint32_t)cat_index(z[r][CP + KP + d], p.V[d]) << 10) | (uint32_t)sl : ~0u;
+    }
+    sort_chunk_keys(keys);
+    // sorted places kR t .. kR t + kR - 1 are this thread's; a key of ~0 (beyond C) sorts last and counts nowhere
+    uint32_t kq[kR];
+    bool head[kR];
+    uint32_t before = t > 0 ? keys[kR * t - 1] >> 10 : ~0u;
+    int cnt = 0;
+#pragma unroll
+    for (int h = 0; h < kR; ++h) {
+      kq[h] = keys[kR * t + h];
+      head[h] = kq[h] != ~0u && (kq[h] >> 10) != before;
+      before = kq[h] >> 10;
+      cnt += head[h] ? 1 : 0;
+    }
+    int inc = cnt;                           // inclusive scan over the wave, then the waves before this one
+    for (int o = 1; o < 64; o <<= 1) {
+      const int v = __shfl_up(inc, o);
+      if ((t & 63) >= o) inc += v;
+    }
+    if ((t & 63) == 63) wtot[t >> 6] = inc;
+    __syncthreads();
+    int rank = inc - cnt, n = 0;
+#pragma unroll
+    for (int w = 0; w < kThreads / 64; ++w) {
+      const int v = wtot[w];
+      if (w < (t >> 6)) rank += v;
+      n += v;
+    }
+    // (a thread's first key may continue the run of the thread before: its row is rank - 1, which that thread made)
+#pragma unroll
+    for (int h = 0; h < kR; ++h) {
+      if (head[h]) bins[n_total + rank++] = (uint16_t)(kq[h] >> 10);
+      if (kq[h] != ~0u) crow[kq[h] & (TPE_JOINT_CHUNK - 1)] = (uint16_t)(rank - 1);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < kR; ++r)
+      if (first + r * kThreads + t < C) row[r][d] = n_total + crow[r * kThreads + t];
+    n = uni(n);
+    p.nd[d] = n;
+    n_total += n;
+  }
+  p.total = n_total; p.bins = bins;
+  p.tile = min(kTileK, (p.mt_floats / (n_total + 1) - 4) & ~3);    // >= 4: quant_large_floats
+  p.stride = p.tile + 4;
+  __syncthreads();                           // the last rows are read: the table takes the scratch's place
+  for (int e = t; e < p.stride; e += kThreads) qt[n_total * p.stride + e] = 0.f;   // the padded slots' row
+#pragma unroll
+  for (int r = 0; r < kR; ++r)
+#pragma unroll
+    for (int d = 0; d < QP; ++d) qo[r][d] = (row[r][d] >= 0 ? row[r][d] : n_total) * p.stride;
+}
+
 // mixed_chunk_body for a group with quantised labels: CP / KP / QP the padded
 // continuous / discrete / quantised counts (CP = 0, KP = 0 allowed).  z[r] holds
 // the continuous coordinates at [0, CP), the categories at [CP, CP + KP) and the
 // lattice indices at [CP + KP, CP + KP + QP).  qt: the dynamic LDS tile,
 // [(total + 1) * stride].
-template <int CP, int KP, int QP>
+// LARGE (k_joint_quant_large_chunk): qt is [p.mt_floats] floats, then the
+// chunk's distinct lattice indices; qmu: the two sides' f64 components.
+template <int CP, int KP, int QP, bool LARGE = false>
 __device__ __forceinline__ void quant_chunk_body(const QuantIO<CP, KP, QP>& p, int first, float* __restrict__ rows,
                                                  float* __restrict__ cl, float* __restrict__ qt,
-                                                 Pick* __restrict__ slot) {
+                                                 Pick* __restrict__ slot, const double* __restrict__ bqmu = nullptr,
+                                                 const double* __restrict__ bqsigma = nullptr,
+                                                 const double* __restrict__ aqmu = nullptr,
+                                                 const double* __restrict__ aqsigma = nullptr) {
   constexpr int ZP = CP + KP + QP;
   const ChunkIO& q = p.m.q;
   const int t = threadIdx.x, Dc = q.D, Dk = p.m.Dk, Dq = p.Dq, D = Dc + Dk + Dq;
 
-  for (int e = t; e < p.stride; e += kThreads) qt[p.total * p.stride + e] = 0.f;   // the padded slots' row
+  if constexpr (!LARGE)
+    for (int e = t; e < p.stride; e += kThreads) qt[p.total * p.stride + e] = 0.f;   // the padded slots' row
 
   float z[kR][ZP];
 #pragma unroll
@@ -1121,17 +1301,24 @@ __device__ __forceinline__ void quant_chunk_body(const QuantIO<CP, KP, QP>& p, i
 
   // the lattice value's row in the tile (kept inside the table); a padded slot reads the zero row
   int qo[kR][QP];
+  QuantIO<CP, KP, QP> pl;                    // (LARGE: p with the chunk's own lattice, tile and stride)
+  if constexpr (!LARGE) {
 #pragma unroll
-  for (int r = 0; r < kR; ++r)
+    for (int r = 0; r < kR; ++r)
 #pragma unroll
-    for (int d = 0; d < QP; ++d)
-      qo[r][d] = (d < Dq ? p.voff[d] + cat_index(z[r][CP + KP + d], p.V[d]) : p.total) * p.stride;
+      for (int d = 0; d < QP; ++d)
+        qo[r][d] = (d < Dq ? p.voff[d] + cat_index(z[r][CP + KP + d], p.V[d]) : p.total) * p.stride;
+  } else {
+    pl = p;
+    compact_chunk_lattice<CP, KP, QP>(pl, first, z, qo, qt);
+  }
+  const QuantIO<CP, KP, QP>& ps = LARGE ? pl : p;
 
   double l2[kR], g2[kR];
-  score_side_quant<CP, KP, QP>(q.bmu, q.ba, q.bc, p.m.bcat, p.m.bmiss, p.m.bbonus, p.bT, q.kb, p, z, qo, rows, cl, qt,
-                               l2);
-  score_side_quant<CP, KP, QP>(q.amu, q.aa, q.ac, p.m.acat, p.m.amiss, p.m.abonus, p.aT, q.ka, p, z, qo, rows, cl, qt,
-                               g2);
+  score_side_quant<CP, KP, QP, LARGE>(q.bmu, q.ba, q.bc, p.m.bcat, p.m.bmiss, p.m.bbonus, p.bT, q.kb, ps, z, qo, rows,
+                                      cl, qt, l2, bqmu, bqsigma);
+  score_side_quant<CP, KP, QP, LARGE>(q.amu, q.aa, q.ac, p.m.acat, p.m.amiss, p.m.abonus, p.aT, q.ka, ps, z, qo, rows,
+                                      cl, qt, g2, aqmu, aqsigma);
 
   Pick best{0, 0};
   double lv[kR], gv[kR];
@@ -1196,16 +1383,10 @@ __device__ __forceinline__ void quant_chunk_body(const QuantIO<CP, KP, QP>& p, i
   }
 }
 
+// QuantIO of workgroup blockIdx.x of a solo launch
 template <int CP, int KP, int QP>
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, (CP + KP + QP >= 12 ? 2 : 8))))
-void k_joint_quant_chunk(const QuantK p) {
-  constexpr int S = 2 * CP + KP;
-  __shared__ __attribute__((aligned(16))) float rows[kTileK * (S > 0 ? S : 1)];
-  __shared__ float cl[kTileK];
-  __shared__ Pick slot[kThreads / 64];
-  extern __shared__ __attribute__((aligned(16))) float qt[];     // [(total + 1) * stride]
+__device__ __forceinline__ void solo_quant_io(QuantIO<CP, KP, QP>& io, const QuantK& p) {
   const JointK& j = p.m.j;
-  QuantIO<CP, KP, QP> io;
   solo_chunk_io(io.m.q, j, j.D + p.m.Dk + p.Dq);
   io.m.Dk = p.m.Dk;
 #pragma unroll
@@ -1222,7 +1403,42 @@ void k_joint_quant_chunk(const QuantK p) {
     io.qlo[d] = p.qlo[d]; io.qhi[d] = p.qhi[d];
   }
   io.edges = p.edges; io.qsamp = p.qsamp; io.bT = p.bT; io.aT = p.aT;
-  quant_chunk_body<CP, KP, QP>(io, (int)(blockIdx.x % j.n_chunks) * TPE_JOINT_CHUNK, rows, cl, qt, slot);
+}
+
+template <int CP, int KP, int QP>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, (CP + KP + QP >= 12 ? 2 : 8))))
+void k_joint_quant_chunk(const QuantK p) {
+  constexpr int S = 2 * CP + KP;
+  __shared__ __attribute__((aligned(16))) float rows[kTileK * (S > 0 ? S : 1)];
+  __shared__ float cl[kTileK];
+  __shared__ Pick slot[kThreads / 64];
+  extern __shared__ __attribute__((aligned(16))) float qt[];     // [(total + 1) * stride]
+  QuantIO<CP, KP, QP> io;
+  solo_quant_io(io, p);
+  quant_chunk_body<CP, KP, QP>(io, (int)(blockIdx.x % p.m.j.n_chunks) * TPE_JOINT_CHUNK, rows, cl, qt, slot);
+}
+
+// k_joint_quant_chunk without the tables (include/tpe_hip.h "Large lattices"):
+// every quantised dimension goes through the chunk's own lattice and mini-table.
+struct QuantLargeK {
+  QuantK q;                         // (tile, stride, total, voff, bT, aT: unused)
+  const double *bqmu, *bqsigma, *aqmu, *aqsigma;   // f64 [K * Dq] of a side
+  int mt_floats;                    // quant_large_floats of the launch
+};
+
+template <int CP, int KP, int QP>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, (CP + KP + QP >= 12 ? 2 : 8))))
+void k_joint_quant_large_chunk(const QuantLargeK p) {
+  constexpr int S = 2 * CP + KP;
+  __shared__ __attribute__((aligned(16))) float rows[kTileK * (S > 0 ? S : 1)];
+  __shared__ float cl[kTileK];
+  __shared__ Pick slot[kThreads / 64];
+  extern __shared__ __attribute__((aligned(16))) float qt[];     // [mt_floats], then the distinct indices
+  QuantIO<CP, KP, QP> io;
+  solo_quant_io(io, p.q);
+  io.mt_floats = p.mt_floats;
+  quant_chunk_body<CP, KP, QP, true>(io, (int)(blockIdx.x % p.q.m.j.n_chunks) * TPE_JOINT_CHUNK, rows, cl, qt, slot,
+                                     p.bqmu, p.bqsigma, p.aqmu, p.aqsigma);
 }
 
 template <int CP, int KP, int QP>
@@ -4507,6 +4723,76 @@ int joint_quant_run_at(const tpe_joint_quant_args* a, tpe_joint_record* records,
   return finish(k_joint_merge, (const tpe_joint_record*)scratch, qk.m.j.n_chunks, records, a->n_ids, s, timed, 1);
 }
 
+// ---- large lattices: tpe_joint_quant_run's arguments, checks (the lattice sizes up
+// to TPE_JOINT_MAX_LATTICE_LARGE, no total, no table workspace) and launch
+// skeleton; no table launches, the chunk kernel makes its own mini-tables.
+// The rows a chunk's mini-table may need (the zero row included), or -1 with the call's error set
+int64_t check_lattice_large(const char* entry, const int32_t* v, const int32_t* edge_off, int n, int64_t n_edges) {
+  int64_t nmax = 1;
+  for (int d = 0; d < n; ++d) {
+    if (v[d] < 2 || v[d] > TPE_JOINT_MAX_LATTICE_LARGE)
+      return fail(entry, "lattice values of a label outside [2, TPE_JOINT_MAX_LATTICE_LARGE]"), -1;
+    if (edge_off && (edge_off[d] < 0 || (int64_t)edge_off[d] + v[d] + 1 > n_edges))
+      return fail(entry, "quant_edge_off outside the edge array"), -1;
+    nmax += v[d] < TPE_JOINT_CHUNK ? v[d] : TPE_JOINT_CHUNK;
+  }
+  return nmax;
+}
+// the dynamic LDS of the launch: the mini-table, then the distinct indices (uint16)
+uint64_t quant_large_lds(int64_t nmax) {
+  return (uint64_t)quant_large_floats((int)nmax) * sizeof(float) + (((uint64_t)nmax * sizeof(uint16_t) + 15) & ~(uint64_t)15);
+}
+
+int joint_quant_large_run(const tpe_joint_quant_args* a, tpe_joint_record* records, float* cand, double* l_out,
+                          double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
+  constexpr const char* E = "tpe_joint_quant_large_run";
+  tpe_internal_epoch_bump();
+  if (!a) return fail(E, "null args");
+  if (a->n_quant < 1 || a->n_quant > TPE_JOINT_MAX_QUANT) return fail(E, "n_quant outside [1, TPE_JOINT_MAX_QUANT]");
+  const int Dc = a->n_dims, Dk = a->n_cat, Dq = a->n_quant;
+  if (Dk < 0) return fail(E, "n_cat < 0");
+  if (Dc < 0 || Dc > TPE_JOINT_MAX_DIMS || Dk > TPE_JOINT_MAX_DIMS || Dc + Dk + Dq > TPE_JOINT_MAX_DIMS)
+    return fail(E, "n_dims + n_cat + n_quant outside [1, TPE_JOINT_MAX_DIMS]");
+  if (Dc > 8 || Dk > 4) return fail(E, "n_dims > 8 or n_cat > 4 beside a quantised label");
+  if (int rc = check_solo_head(E, a, records, Dc)) return rc;
+  if (Dk > 0) {
+    if (cat_tables_null(a)) return fail(E, "null category tables");
+    if (check_cats(E, "", a->cat_upper, a->cat_off, Dk) < 0) return TPE_E_ARG;
+  }
+  const int64_t nmax = check_lattice_large(E, a->quant_v, a->quant_edge_off, Dq, a->n_edges);
+  if (nmax < 0) return TPE_E_ARG;
+  if (!a->quant_edges || !a->below_qmu || !a->below_qsigma || !a->above_qmu || !a->above_qsigma || !a->quant_samp)
+    return fail(E, "null quantised rows");
+  const int64_t blocks = n_chunks_of(a->n_cand) * a->n_ids;
+  if (int rc = check_scratch(E, blocks, joint_scratch_need(a->n_ids, a->n_cand), scratch, scratch_bytes)) return rc;
+
+  QuantLargeK lk;
+  QuantK& qk = lk.q;
+  fill_joint(qk.m.j, a, Dc, 0u, cand, l_out, g_out, scratch);
+  fill_cat_slots(qk.m, a); fill_cat_draw(qk.m, a); fill_cat_score(qk.m, a);
+  qk.Dq = Dq; qk.total = qk.tile = qk.stride = 0;
+  qk.edges = a->quant_edges; qk.qsamp = a->quant_samp;
+  qk.bT = qk.aT = nullptr;
+  QTabK tb;
+  fill_quant_slots(tb, qk.qlo, qk.qhi, a);
+  memcpy(qk.V, tb.V, sizeof tb.V); memcpy(qk.voff, tb.voff, sizeof tb.voff); memcpy(qk.eoff, tb.eoff, sizeof tb.eoff);
+  lk.bqmu = a->below_qmu; lk.bqsigma = a->below_qsigma; lk.aqmu = a->above_qmu; lk.aqsigma = a->above_qsigma;
+  lk.mt_floats = quant_large_floats((int)nmax);
+
+  const bool timed = g_prof.on != 0;
+  hipStream_t s = (hipStream_t)stream;
+  const Ev ev = chunk_marks(timed);
+  for_cp<8>(Dc, [&](auto cp) {
+    for_kp<0, 4>(Dk, [&](auto kp) {
+      for_qp(Dq, [&](auto qp) {
+        launch(k_joint_quant_large_chunk<decltype(cp)::value, decltype(kp)::value, decltype(qp)::value>,
+               dim3((unsigned)blocks), kThreads, (unsigned)quant_large_lds(nmax), s, ev.start, ev.stop, lk);
+      });
+    });
+  });
+  return finish(k_joint_merge, (const tpe_joint_record*)scratch, qk.m.j.n_chunks, records, a->n_ids, s, timed, 1);
+}
+
 // the float64 mixed stage: tpe_joint_quant_run's head, labels, chunk records and
 // merge; its own f64 rows, centres, category tables, table workspace and kernels
 static_assert(offsetof(tpe_joint_mq_f64_args, quant_table_bytes) == offsetof(tpe_joint_quant_args, quant_table_bytes) &&
@@ -5317,6 +5603,20 @@ int tpe_joint_mixed_run(const tpe_joint_mixed_args* a, tpe_joint_record* records
 int tpe_joint_quant_run(const tpe_joint_quant_args* a, tpe_joint_record* records, float* cand, double* l_out,
                         double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
   return joint_quant_run_at(a, records, cand, l_out, g_out, scratch, scratch_bytes, stream, 0u);
+}
+
+int tpe_joint_quant_large_lds_bytes(const int32_t* quant_v, int32_t n_quant, uint64_t* bytes) {
+  constexpr const char* E = "tpe_joint_quant_large_lds_bytes";
+  if (!bytes || !quant_v || n_quant < 1 || n_quant > TPE_JOINT_MAX_QUANT) return fail(E, "bad arguments");
+  const int64_t nmax = check_lattice_large(E, quant_v, nullptr, n_quant, 0);
+  if (nmax < 0) return TPE_E_ARG;
+  *bytes = quant_large_lds(nmax);
+  return TPE_OK;
+}
+
+int tpe_joint_quant_large_run(const tpe_joint_quant_args* a, tpe_joint_record* records, float* cand, double* l_out,
+                              double* g_out, void* scratch, uint64_t scratch_bytes, void* stream) {
+  return joint_quant_large_run(a, records, cand, l_out, g_out, scratch, scratch_bytes, stream);
 }
 
 int tpe_joint_run_shard(int32_t stage, const void* args, const tpe_joint_shard* shard, void* records, float* cand,

@@ -1100,6 +1100,7 @@ class Engine(object):
                    'mixed': (N.JointMixedArgs, 'tpe_joint_mixed_run'),
                    'wide_mixed': (N.JointWideMixedArgs, 'tpe_joint_wide_mixed_run'),
                    'quant': (N.JointQuantArgs, 'tpe_joint_quant_run'),
+                   'quant_large': (N.JointQuantArgs, 'tpe_joint_quant_large_run'),
                    'mq_f64': (N.JointMqF64Args, 'tpe_joint_mq_f64_run'),
                    'wide_quant': (N.JointWideQuantArgs, 'tpe_joint_wide_quant_run')}
 
@@ -1135,7 +1136,7 @@ class Engine(object):
         a.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         for key, field, buf, dtype, part in JP.group_rows_present(r):
             # tpe_joint_quant_run takes null pointers for the rows of an absent continuous part
-            if entry in ('quant', 'mq_f64') and part == 'cont' and Dc == 0:
+            if entry in ('quant', 'quant_large', 'mq_f64') and part == 'cont' and Dc == 0:
                 continue
             # tpe_joint_mq_f64_run does not read the f32 density rows and category tables: their pointers stay null
             if entry == 'mq_f64' and key.split('_')[-1] in ('mu', 'a', 'c', 'miss', 'bonus'):
@@ -1166,6 +1167,8 @@ class Engine(object):
                         'tpe_joint_mq_f64_table_bytes')
                 d_tab = self._buf('joint_qtable64', nb.value // 8, torch.float64)
                 a.quant_table64, a.quant_table64_bytes = d_tab.data_ptr(), d_tab.numel() * 8
+            elif entry == 'quant_large':             # no table: the chunks build their own mini-tables
+                pass
             else:
                 N.check(self.lib.tpe_joint_quant_table_bytes(a.k_below, a.k_above, total, ctypes.byref(nb)), self.lib,
                         'tpe_joint_quant_table_bytes')
@@ -1887,6 +1890,20 @@ class Engine(object):
                                     return_cand, want_lg, 0, stream_word, None, return_table)
         return self._joint_solo('quant', below, above, low, high, cats, quants, ids, n_cand, seed, inject, return_cand,
                                 want_lg, report_k, stream_word, shard, return_table)
+
+    def run_joint_quant_large(self, below, above, low, high, cats, quants, ids, n_cand, seed, inject=None,
+                              return_cand=False, want_lg=False, stream_word=None):
+        """``run_joint_quant`` for quantised labels of up to
+        N.JOINT_MAX_LATTICE_LARGE lattice values (tpe_joint_quant_large_run,
+        include/tpe_hip.h "Large lattices"): the same arguments, model, kernel
+        coordinate order, Philox streams and return shapes, and for a group that
+        ``run_joint_quant`` also takes the same bytes.  No table is built (every
+        chunk evaluates the bins its own candidates hold), so there is no
+        ``return_table`` and the group's lattice total is not limited.  The
+        stage has no report, is neither sharded nor batch-aware and scores in
+        fp32: no ``report_k``, ``shard``, ``liar`` or ``precision`` argument."""
+        return self._joint_solo('quant_large', below, above, low, high, cats, quants, ids, n_cand, seed, inject,
+                                return_cand, want_lg, 0, stream_word, None)
 
     def run_joint_wide_quant(self, below, above, low, high, cats, quants, ids, n_cand, seed, inject=None,
                              return_cand=False, want_lg=False, return_table=False, report_k=0, stream_word=None):

@@ -474,9 +474,18 @@ def quant_lattice(dist, args):
     return m_lo, V, q, edges
 
 
-def quant_reason(row, table, conditional=False):
+def is_large_lattice(row):
+    """Whether ``row`` is a quniform / qloguniform label with more than
+    TPE_JOINT_MAX_LATTICE lattice values: one that only the large-lattice stage
+    joins (joint_quantized='large')."""
+    return (row.dist in QUANT_DISTS and float(row.args['q']) > 0 and float(row.args['high']) > float(row.args['low'])
+            and lattice_size(row.dist, row.args)[1] > N.JOINT_MAX_LATTICE)
+
+
+def quant_reason(row, table, conditional=False, large=False):
     """Why ``row`` cannot be joined as a quantised dimension, or None if it can
-    (``conditional``: as in discrete_reason)."""
+    (``conditional``: as in discrete_reason; ``large``, joint_quantized='large':
+    up to TPE_JOINT_MAX_LATTICE_LARGE lattice values)."""
     if not conditional and (not all(p is None for p in row.parents) or row.depth != 0):
         return 'conditional (%s)' % row.dist
     if row.dist in ('qnormal', 'qlognormal'):
@@ -491,16 +500,20 @@ def quant_reason(row, table, conditional=False):
     V = lattice_size(row.dist, row.args)[1]
     if V < 2:
         return '%d lattice value, fewer than 2: nothing to choose' % V
-    if V > N.JOINT_MAX_LATTICE:
+    if large and V > N.JOINT_MAX_LATTICE_LARGE:
+        return ('%d lattice values, more than TPE_JOINT_MAX_LATTICE_LARGE = %d: the large-lattice joint stage keeps a '
+                'lattice index in 16 bits; model the label as uniform / loguniform' % (V, N.JOINT_MAX_LATTICE_LARGE))
+    if V > N.JOINT_MAX_LATTICE and not large:
         return ('%d lattice values, more than TPE_JOINT_MAX_LATTICE = %d: such a label is close to continuous, model '
                 'it as uniform / loguniform' % (V, N.JOINT_MAX_LATTICE))
     return None
 
 
-def eligible_quant(row, table):
+def eligible_quant(row, table, large=False):
     """Whether a ParamRow can be joined as a quantised dimension: unconditional
-    quniform / qloguniform, q > 0, 2 to 256 lattice values."""
-    return quant_reason(row, table) is None
+    quniform / qloguniform, q > 0, 2 to 256 lattice values (``large``: to
+    TPE_JOINT_MAX_LATTICE_LARGE)."""
+    return quant_reason(row, table, large=large) is None
 
 
 def quant_bin_masses(mu, sigma, edges):

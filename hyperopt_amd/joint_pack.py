@@ -14,6 +14,8 @@ The dimension limits by entry point (``_check_dims``):
   'mixed'    run_joint_mixed       Dk >= 1, Dc + Dk <= JOINT_MAX_DIMS
   'wide_mixed' run_joint_wide_mixed  1 <= Dk <= JOINT_WIDE_MAX_CAT, Dq = 0, 1 <= Dc + Dk <= JOINT_WIDE_MAX_DIMS
   'quant'    run_joint_quant       Dq >= 1, Dc <= JOINT_QUANT_MAX_CONT, Dk <= JOINT_QUANT_MAX_DISC
+  'quant_large' run_joint_quant_large  as 'quant'; a label holds up to JOINT_MAX_LATTICE_LARGE lattice values, and
+                                   JOINT_MAX_LATTICE_TOTAL does not apply (no table is built)
   'mq_f64'   run_joint_mixed / run_joint_quant(precision='fp64')  Dk + Dq >= 1; as 'quant' with a quantised
                                    dimension, else as 'mixed'; the group's f32 rows as those entries make them,
                                    and beside them the float64 density rows, category tables and the centres
@@ -93,11 +95,11 @@ def _check_dims(entry, Dc, Dk, Dq):
         entry = 'quant' if Dq else 'mixed'
     if entry == 'mixed' and Dk == 0:
         raise ValueError('joint stage: no discrete dimension, use run_joint')
-    if entry == 'quant' and Dq == 0:
+    if entry in ('quant', 'quant_large') and Dq == 0:
         raise ValueError('joint stage: no quantised dimension, use run_joint_mixed / run_joint')
     if Dq > N.JOINT_MAX_QUANT:
         raise ValueError('joint stage: %d quantised dimensions, at most %d' % (Dq, N.JOINT_MAX_QUANT))
-    if entry == 'quant':
+    if entry in ('quant', 'quant_large'):
         if Dc > N.JOINT_QUANT_MAX_CONT or Dk > N.JOINT_QUANT_MAX_DISC:
             raise ValueError('joint stage: beside a quantised dimension at most %d continuous and %d discrete ones, '
                              'not %d and %d' % (N.JOINT_QUANT_MAX_CONT, N.JOINT_QUANT_MAX_DISC, Dc, Dk))
@@ -149,12 +151,14 @@ def group_rows(below, above, low, high, cats=(), quants=(), entry='segment'):
                          'quantised ones' % (Dk, Dq))
     edges = [np.ascontiguousarray(q[4], dtype=np.float64).reshape(-1) for q in quants]
     vs = [len(e) - 1 for e in edges]
+    # (the large stage builds no table: a label's lattice is bounded by the sort key, the group's total is not)
+    top = N.JOINT_MAX_LATTICE_LARGE if entry == 'quant_large' else N.JOINT_MAX_LATTICE
     for e in edges:
-        if not 2 <= len(e) - 1 <= N.JOINT_MAX_LATTICE:
-            raise ValueError('joint stage: %d lattice values, outside [2, %d]' % (len(e) - 1, N.JOINT_MAX_LATTICE))
+        if not 2 <= len(e) - 1 <= top:
+            raise ValueError('joint stage: %d lattice values, outside [2, %d]' % (len(e) - 1, top))
         if not (np.isfinite(e).all() and (np.diff(e) > 0).all()):
             raise ValueError('joint stage: the lattice edges must be finite and strictly increasing')
-    if sum(vs) > N.JOINT_MAX_LATTICE_TOTAL:
+    if entry != 'quant_large' and sum(vs) > N.JOINT_MAX_LATTICE_TOTAL:
         raise ValueError('joint stage: %d lattice values in the group, at most %d'
                          % (sum(vs), N.JOINT_MAX_LATTICE_TOTAL))
     ps = [np.asarray(c[2], dtype=np.float64).reshape(-1) for c in cats]

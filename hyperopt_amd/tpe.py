@@ -853,6 +853,7 @@ def suggest(new_ids, domain, trials, seed,
     new_ids = list(new_ids)
     if not new_ids:
         return []
+    _quantized_mode(joint_quantized)
     if joint_shard is not None:                  # (argument errors first, as below; nothing on the default path)
         _joint_shard_pair(joint_shard, joint, joint_wide_mixed, joint_wide_quantized)
     liar_mode = _joint_liar_mode(joint_liar)
@@ -870,6 +871,7 @@ def suggest(new_ids, domain, trials, seed,
                            joint_discrete, joint_quantized,
                            _wide_mode(joint_wide, joint_wide_mixed, joint_wide_quantized),
                            _branch_mode(joint_branches, joint_branches_wide, joint_wide), joint_branches_mixed)
+        _large_lattice_check(plan[0], joint_shard, liar_mode, fp64)
         _branch_wide_check(plan, joint_shard, liar_mode)
         if liar_mode:
             _joint_liar_check(joint, joint_shard, plan, liar_mode, joint_branches)
@@ -984,6 +986,18 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
     joint stage").  Their joined values are ``np.float64`` multiples of q.
     ``qnormal`` / ``qlognormal`` labels stay univariate.  A group that ends up
     with no quantised label is the stage without the keyword, byte for byte.
+
+    ``joint_quantized='large'``: everything ``True`` does, and the root group
+    may also hold unconditional ``quniform`` / ``qloguniform`` labels with 257
+    to TPE_JOINT_MAX_LATTICE_LARGE = 65,536 lattice values, the shape of an
+    integer hyperparameter (``hp.quniform('units', 16, 1024, 1)``); such a label
+    does not count towards the 512 (DESIGN.md "Large lattices",
+    Engine.run_joint_quant_large).  The model, the sampler and the returned
+    value are the same; a group without such a label takes the stage of
+    ``True`` and returns the same bytes.  A group with such a label raises
+    ValueError with ``joint_wide_quantized``, ``joint_liar``, ``joint_shard``
+    and ``joint_precision='fp64'``, in joint_candidate_report, and where
+    ``joint_branches_mixed`` would admit the label to a branch group.
 
     ``joint_wide=True`` (with ``joint``): a group may hold 17 to
     TPE_JOINT_WIDE_MAX_DIMS = 64 labels, all of them continuous (the labels
@@ -1199,6 +1213,7 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
     than 16 labels; joint_candidate_report does not take it."""
     if sampler not in ('philox', 'replay'):
         raise ValueError("sampler must be 'philox' or 'replay'")
+    _quantized_mode(joint_quantized)
     if joint_shard is not None:
         joint_shard = _joint_shard_pair(joint_shard, joint, joint_wide_mixed, joint_wide_quantized)
     liar_mode = _joint_liar_mode(joint_liar)
@@ -1218,6 +1233,7 @@ def suggest_choices(table, hist, new_ids, seed, prior_weight=_default_prior_weig
                                            _wide_mode(joint_wide, joint_wide_mixed, joint_wide_quantized),
                                            _branch_mode(joint_branches, joint_branches_wide, joint_wide),
                                            joint_branches_mixed)
+        _large_lattice_check(group, joint_shard, liar_mode, fp64)
         _branch_wide_check((group, branch_groups), joint_shard, liar_mode)
         if liar_mode:
             _joint_liar_check(joint, joint_shard, (group, branch_groups), liar_mode, joint_branches)
@@ -1536,6 +1552,51 @@ def _wide_mode(joint_wide, joint_wide_mixed, joint_wide_quantized=False):
 
 
 BRANCH_WIDE = 'wide'                  # joint_branches_wide: the ``branches`` argument of _joint_plan
+QUANT_LARGE = 'large'                 # joint_quantized='large': the ``quantized`` argument of _joint_plan
+
+
+def _quantized_mode(joint_quantized):
+    """``joint_quantized`` as given (False / None, True or QUANT_LARGE);
+    ValueError for any other string.  Touches no device."""
+    if isinstance(joint_quantized, str) and joint_quantized != QUANT_LARGE:
+        raise ValueError("joint_quantized must be True or 'large' (or False): %r; 'large' also joins quantised labels "
+                         'of %d to %d lattice values (the large-lattice joint stage)'
+                         % (joint_quantized, N.JOINT_MAX_LATTICE + 1, N.JOINT_MAX_LATTICE_LARGE))
+    return joint_quantized
+
+
+def _is_large(quantized):
+    return isinstance(quantized, str) and quantized == QUANT_LARGE
+
+
+def _large_rows(rows):
+    """The labels of a group that only the large-lattice stage joins
+    (joint_quantized='large' let them through)."""
+    return [r for r in rows or () if _joint.is_large_lattice(r)]
+
+
+def _large_lattice_error(row, keyword, stage):
+    return ValueError("joint_quantized='large' does not combine with %s: %r has %d lattice values, more than "
+                      'TPE_JOINT_MAX_LATTICE = %d, and %s does not take large lattices'
+                      % (keyword, row.label, _joint.lattice_size(row.dist, row.args)[1], N.JOINT_MAX_LATTICE, stage))
+
+
+def _large_lattice_check(group, joint_shard=None, liar_mode=None, fp64=False, report=False):
+    """ValueError where a root group with a large lattice (joint_quantized=
+    'large') meets ``joint_shard``, ``joint_liar``, joint_precision='fp64' or the
+    candidate report: the large-lattice stage has none of them.  Touches no
+    device."""
+    large = _large_rows(group)
+    if not large:
+        return
+    if joint_shard is not None:
+        raise _large_lattice_error(large[0], 'joint_shard', 'the sharded joint stage')
+    if liar_mode:
+        raise _large_lattice_error(large[0], 'joint_liar=%r' % (liar_mode,), 'the batch-aware liar stage')
+    if fp64:
+        raise _large_lattice_error(large[0], "joint_precision='fp64'", 'the float64 mixed joint stage')
+    if report:
+        raise _large_lattice_error(large[0], 'joint_candidate_report', 'the joint candidate report')
 
 
 def _branch_mode(joint_branches, joint_branches_wide, joint_wide):
@@ -1605,6 +1666,7 @@ def _joint_restrictions(joint, sampler, precision, shards, discrete=False, quant
     """ValueError for a keyword without ``joint`` (or without the keywords it
     widens) and for the sampler, precision and shard arguments the joint stage
     does not combine with."""
+    _quantized_mode(quantized)
     if _is_wide_quant(wide):
         if joint is False or joint is None:
             raise ValueError('joint_wide_quantized=True needs joint=True or joint=[labels]: it only widens what joint '
@@ -1638,7 +1700,7 @@ def _joint_rows(table, joint, discrete=False, quantized=False):
     table order; ValueError for a listed label that cannot be joined."""
     if joint is True:
         rows = [r for r in table.rows if _joint.eligible(r) or (discrete and _joint.eligible_discrete(r, table))
-                or (quantized and _joint.eligible_quant(r, table))]
+                or (quantized and _joint.eligible_quant(r, table, _is_large(quantized)))]
     else:
         if isinstance(joint, str):
             raise ValueError('joint must be True or a list of labels, not the string %r' % joint)
@@ -1648,9 +1710,10 @@ def _joint_rows(table, joint, discrete=False, quantized=False):
             if r is None:
                 raise ValueError('joint: %r is not a label of the space' % (label,))
             if quantized and r.dist.startswith('q'):
-                why = _joint.quant_reason(r, table)
+                why = _joint.quant_reason(r, table, large=_is_large(quantized))
                 if why is not None:
-                    raise ValueError('joint: label %r is not eligible with joint_quantized=True: %s' % (label, why))
+                    raise ValueError('joint: label %r is not eligible with joint_quantized=%s: %s'
+                                     % (label, "'large'" if _is_large(quantized) else 'True', why))
             elif discrete and not _joint.eligible(r):
                 why = _joint.discrete_reason(r, table)
                 if why is not None:
@@ -1669,7 +1732,12 @@ def _joint_limits(rows, wide=False):
     TPE_JOINT_WIDE_MAX_CAT discrete labels; WIDE_QUANT / WIDE_QUANT_MIXED: a
     group with a quantised label that the quantised stage does not take is held
     to the wide quantised stage's limits, every other group to those without
-    ``joint_wide_quantized``)."""
+    ``joint_wide_quantized``).  A label of more than TPE_JOINT_MAX_LATTICE lattice
+    values (joint_quantized='large') does not count towards
+    TPE_JOINT_MAX_LATTICE_TOTAL: it keeps no table."""
+    large = _large_rows(rows)
+    if large and _is_wide_quant(wide):
+        raise _large_lattice_error(large[0], 'joint_wide_quantized=True', 'the wide quantised joint stage')
     if _is_wide_quant(wide):
         if _takes_wide_quant(rows):
             return _wide_quant_limits(rows)
@@ -1711,7 +1779,7 @@ def _joint_limits(rows, wide=False):
     if qrows:
         n_disc = sum(1 for r in rows if r.categorical)
         n_cont = len(rows) - len(qrows) - n_disc
-        n_lat = sum(_joint.lattice_size(r.dist, r.args)[1] for r in qrows)
+        n_lat = sum(_joint.lattice_size(r.dist, r.args)[1] for r in qrows if r not in large)
         tail = ': pass the labels to join as joint=[...]'
         if len(qrows) > N.JOINT_MAX_QUANT:
             raise ValueError('joint joins at most TPE_JOINT_MAX_QUANT = %d quantised labels, not %d%s'
@@ -1809,6 +1877,9 @@ def _branch_mixed_reason(row, table, discrete, quantized):
     if _branch_key(row) is not None:
         return None
     if quantized and row.dist.startswith('q'):
+        if _is_large(quantized) and _joint.is_large_lattice(row) and \
+                _joint.quant_reason(row, table, conditional=True, large=True) is None:
+            raise _large_lattice_error(row, 'joint_branches_mixed=True', 'the mixed segmented joint stage')
         why = _joint.quant_reason(row, table, conditional=True)
     elif discrete and row.categorical:
         why = _joint.discrete_reason(row, table, conditional=True)
@@ -1958,6 +2029,8 @@ def _run_root_group(engine, group, hist, ids, seed, prior_weight, n_EI_candidate
         else:
             # beyond the quantised stage's limits (joint_wide_quantized=True let the group through): the wide one
             run = engine.run_joint_wide_quant if _takes_wide_quant(group) else engine.run_joint_quant
+            if _large_rows(qrows):               # (joint_quantized='large' let them through: no table, no keyword)
+                run = engine.run_joint_quant_large
             out = run(model.below[:3], model.above[:3], model.low, model.high, model.cats(), model.quants(), ids,
                       int(n_EI_candidates), seed, **kw)
     elif drows:                                  # kernel coordinates: the continuous labels, then the discrete ones
@@ -2437,6 +2510,7 @@ def joint_candidate_report_columns(table, hist, new_id, seed, k=8, joint=True, j
                                        _wide_mode(joint_wide, joint_wide_mixed, joint_wide_quantized),
                                        _branch_mode(joint_branches, joint_branches_wide, joint_wide),
                                        joint_branches_mixed)
+    _large_lattice_check(group, report=True)
     if len(hist) == 0:
         raise ValueError('joint_candidate_report needs a history: no completed trial to fit the models from')
     C = int(n_EI_candidates)
@@ -2489,10 +2563,11 @@ def joint_candidate_report(new_id, domain, trials, seed, k=8, joint=True, joint_
     [1, 64]."""
     k = _report_check_k(k)
     if joint is not False and joint is not None:
-        _joint_plan(domain.table, joint, 'philox', 'fp32', (None, None, None, None), joint_discrete, joint_quantized,
-                    _wide_mode(joint_wide, joint_wide_mixed, joint_wide_quantized),
-                    _branch_mode(joint_branches, joint_branches_wide, joint_wide),
-                    joint_branches_mixed)                    # (argument errors before the history is read)
+        plan = _joint_plan(domain.table, joint, 'philox', 'fp32', (None, None, None, None), joint_discrete,
+                           joint_quantized, _wide_mode(joint_wide, joint_wide_mixed, joint_wide_quantized),
+                           _branch_mode(joint_branches, joint_branches_wide, joint_wide),
+                           joint_branches_mixed)             # (argument errors before the history is read)
+        _large_lattice_check(plan[0], report=True)
     hist = _history.extract(domain, trials)
     return joint_candidate_report_columns(domain.table, hist, new_id, seed, k=k, joint=joint,
                                           joint_discrete=joint_discrete, joint_quantized=joint_quantized,

@@ -1624,6 +1624,57 @@ int tpe_joint_quant_run(const tpe_joint_quant_args* args, tpe_joint_record* reco
 int tpe_joint_quant_profile(double* table_ms);
 
 /* ------------------------------------------------------------------------
+ * Large lattices (tpe_joint.hip; additive to ABI 24): tpe_joint_quant_run for
+ * quantised labels of up to TPE_JOINT_MAX_LATTICE_LARGE lattice values.  The
+ * arguments are a tpe_joint_quant_args; the model, the kernel coordinate order,
+ * the sampler (the same Philox words, the same binary search over the f64
+ * edges), P_kd(i), the floor and the record are those of "Quantised joint
+ * stage".  quant_table and quant_table_bytes are not read: no table is built.
+ *
+ * A table over the whole lattice would be (K_below + K_above) * V floats and
+ * would pass through every workgroup's LDS.  Here a workgroup builds the lattice
+ * of its own chunk instead: the TPE_JOINT_CHUNK candidates of a chunk hold at
+ * most TPE_JOINT_CHUNK distinct lattice indices per dimension whatever V_d is.
+ * Per dimension it sorts the candidates' indices in LDS, numbers the runs of
+ * equal indices (sort, mark, scan: no atomics), and each candidate keeps the
+ * number of its run, a row of the chunk's mini-table.  While a tile of
+ * components is staged, the workgroup evaluates log2 P_kd(i) per (row, tile
+ * component) in f64 from qmu, qsigma and the row's two edges, with the device
+ * function k_joint_qtable stores its entries with, and keeps it as f32 in LDS
+ * laid out [row][component] (stride tile + 4, as the table tile).  The tile
+ * length is the chunk's own: the longest multiple of 4 components (at most 128)
+ * whose mini-table fits the launch's LDS.  Every quantised label of the group
+ * takes this path, one of at most TPE_JOINT_MAX_LATTICE values included, so
+ * TPE_JOINT_MAX_LATTICE_TOTAL does not apply.  A group that tpe_joint_quant_run
+ * also takes gets the same candidates, l, g and record, byte for byte: the
+ * entries are the same f32 values and the components are accumulated in the
+ * same order.
+ *
+ * The launch's dynamic LDS (tpe_joint_quant_large_lds_bytes) is 40 KiB for the
+ * mini-table, or 32 bytes a row where sum_d min(V_d, TPE_JOINT_CHUNK) + 1 rows
+ * at the shortest tile need more (two or more labels of 1,024 values and up:
+ * up to 128 KiB), and 2 bytes a row for the distinct indices.
+ *
+ * TPE_JOINT_MAX_LATTICE_LARGE is a condition, not a measurement: a lattice
+ * index is exact as f32 and fits 16 bits beside the candidate's slot in a sort
+ * key.  tpe_joint_quant_large_run returns TPE_E_ARG before any launch (no device
+ * needed) for everything tpe_joint_quant_run checks except the table workspace
+ * and the lattice total, with V_d outside [2, TPE_JOINT_MAX_LATTICE_LARGE] in
+ * place of its lattice check, and for n_quant = 0.  It is neither sharded nor
+ * batch-aware, and there is no float64 form.  tpe_joint_scratch_bytes and
+ * tpe_joint_profile (chunk kernel, merge) serve it; it launches no table
+ * kernel, so there is nothing for tpe_joint_quant_profile to read.
+ * ---------------------------------------------------------------------- */
+#define TPE_JOINT_MAX_LATTICE_LARGE 65536  /* lattice values per quantised label of tpe_joint_quant_large_run */
+
+/* the dynamic LDS of a tpe_joint_quant_large_run launch over n_quant labels of quant_v[d] lattice values */
+int tpe_joint_quant_large_lds_bytes(const int32_t* quant_v, int32_t n_quant, uint64_t* bytes);
+
+/* as tpe_joint_quant_run */
+int tpe_joint_quant_large_run(const tpe_joint_quant_args* args, tpe_joint_record* records, float* cand, double* l_out,
+                              double* g_out, void* scratch, uint64_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Float64 mixed joint stage (tpe_joint.hip; additive to ABI 24):
  * tpe_joint_mixed_run / tpe_joint_quant_run with the scoring in f64, as
  * tpe_joint_f64_run is to tpe_joint_run.  The model, the sampler rows (samp,

@@ -46,6 +46,16 @@ carries the medians and ranges, (a) / (b), (a) - (c), and the worst l / g error
 of the first --host-cand (default 4096) sampled vectors of (a) as a fraction of
 the lpdf tolerance; --out defaults to profiles/joint_quant_time.jsonl.
 
+--quant-large: the large-lattice stage (DESIGN.md "Large lattices").  Three
+continuous labels and one hp.quniform: per round the table stage at 256 values
+(Engine.run_joint_quant) and Engine.run_joint_quant_large on the same inputs,
+then the latter at 1,024, 4,096 and 65,536 values, alternating in one process,
+each chunk kernel by its own events (use --pairs 5).  The line carries the
+medians and ranges, per lattice the mean number of distinct lattice indices in
+a chunk of 1,024 of the run's own candidates, whether the two stages' bytes at
+256 values are equal, and the worst l / g error as above; --out defaults to
+profiles/joint_quant_large_time.jsonl.
+
 --wide: the wide stage (DESIGN.md "Wide groups").  Flat spaces of D labels of
 hp.uniform(-5, 5) with the same history size; per round one run of
 Engine.run_joint at D = 16 (k_joint_chunk<16>: the yardstick) and one of
@@ -292,12 +302,13 @@ def main_mixed(args):
     return 0
 
 
-def make_quant_history(n, V):
+def make_quant_history(n, V, choice=True):
     """make_mixed_history's continuous columns with a quniform(0, V - 1, 1) label
-    'q3' and a choice 'c3' of V options; the loss couples x0 with both."""
+    'q3' and a choice 'c3' of V options (``choice`` False: of 2, for the large
+    lattices); the loss couples x0 with both."""
     from hyperopt_amd import base, history as H, hp
     space = {'x0': hp.uniform('x0', -5, 5), 'x1': hp.loguniform('x1', -3, 2), 'x2': hp.normal('x2', 0, 2),
-             'q3': hp.quniform('q3', 0, V - 1, 1), 'c3': hp.choice('c3', list(range(V)))}
+             'q3': hp.quniform('q3', 0, V - 1, 1), 'c3': hp.choice('c3', list(range(V if choice else 2)))}
     domain = base.Domain(lambda d: 0.0, space)
     rs = np.random.RandomState(SEED)
     cols = {'x0': rs.uniform(-5, 5, n), 'x1': np.exp(rs.uniform(-3, 2, n)), 'x2': rs.normal(0, 2, n)}
@@ -393,6 +404,91 @@ def main_quant(args):
     text = json.dumps(line)
     print(text)
     out = args.out or os.path.join(ROOT, 'profiles', 'joint_quant_time.jsonl')
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, 'a') as f:
+        f.write(text + '\n')
+    return 0
+
+
+def main_quant_large(args):
+    """--quant-large: the large-lattice stage (Engine.run_joint_quant_large) at the
+    quantised section's shape, 3 continuous labels + one quniform: at 256 values
+    beside the table stage on the same inputs (the A/B), then at 1,024, 4,096 and
+    65,536 values.  Alternating rounds, kernels by their own events; per lattice
+    the mean number of distinct lattice indices in a chunk of the run's own
+    candidates, which is the row count of the chunk's mini-table."""
+    import torch
+    from hyperopt_amd import _native as N, history as H, joint as J
+    from hyperopt_amd.engine import get_engine
+
+    eng = get_engine(None, 'fp32')
+    lib = eng.lib
+    C = args.cand
+    ids = np.array([args.history], dtype=np.int64)
+    models = {}
+    for V in (256, 1024, 4096, 65536):
+        domain, hist = make_quant_history(args.history, V, choice=False)
+        t = domain.table
+        models[V] = J.fit_quant_model([r for r in t.rows if J.eligible(r)], [], [t.by_label['q3']], hist,
+                                      H.split_below(hist, 0.25), 1.0)
+
+    def run(V, large=True, **kw):
+        m = models[V]
+        fn = eng.run_joint_quant_large if large else eng.run_joint_quant
+        return fn(m.below[:3], m.above[:3], m.low, m.high, [], m.quants(), ids, C, SEED, **kw)
+
+    def kernel_ms(fn, table):
+        ms2, tms = (ctypes.c_double * 2)(), ctypes.c_double(0.0)
+        torch.cuda.synchronize()
+        N.check(lib.tpe_joint_profile(1, None), lib, 'tpe_joint_profile')
+        fn()
+        if table:
+            N.check(lib.tpe_joint_quant_profile(ctypes.byref(tms)), lib, 'tpe_joint_quant_profile')
+        N.check(lib.tpe_joint_profile(0, ms2), lib, 'tpe_joint_profile')
+        return ms2[0], ms2[1], tms.value
+
+    routes = [('table256', lambda: run(256, False), True)] + \
+        [('large%d' % V, (lambda V=V: run(V)), False) for V in sorted(models)]
+    for _ in range(args.warmup):
+        for _, fn, _ in routes:
+            fn()
+    ms = dict((name, []) for name, _, _ in routes)
+    for i in range(args.pairs):
+        for name, fn, table in routes:
+            ms[name].append(kernel_ms(fn, table))
+        print('round %d: %s' % (i, ', '.join('%s %.3f ms' % (name, ms[name][-1][0]) for name, _, _ in routes)),
+              file=sys.stderr, flush=True)
+    # (untimed) the two stages' bytes at 256 values; per lattice the distinct indices per chunk and l, g against
+    # the float64 model on the first --host-cand vectors
+    same = all(a.tobytes() == b.tobytes() for a, b in zip(run(256, False, return_cand=True, want_lg=True),
+                                                          run(256, return_cand=True, want_lg=True)))
+    n_host = min(C, args.host_cand or 4096)
+    distinct, err = {}, 0.0
+    for V, m in sorted(models.items()):
+        _, cand, dl, dg = run(V, return_cand=True, want_lg=True)
+        qi = cand[0, :, 3].astype(np.int64)
+        distinct[V] = float(np.mean([len(np.unique(qi[lo:lo + 1024])) for lo in range(0, C, 1024)]))
+        z, q = cand[0, :n_host, :3].astype(np.float64), qi[:n_host, None]
+        for side, dev in ((m.below, dl), (m.above, dg)):
+            ref = J.quant_lpdf_numpy(z, np.zeros((n_host, 0)), q, side[0], side[1], side[2], m.low, m.high, side[3],
+                                     [], [], [(side[4][:, 0], side[5][:, 0], m.lattices[0][3])])
+            err = max(err, float(np.max(np.abs(dev[0, :n_host] - ref) / np.maximum(1.0, np.abs(ref)))) / 1e-5)
+
+    def stat(name, j=0):
+        x = [r[j] for r in ms[name]]
+        return dict(median=float(np.median(x)), min=min(x), max=max(x), all=x)
+    m = models[256]
+    line = dict(tool='joint_time --quant-large', history=args.history, n_cand=C, rounds=args.pairs,
+                k_below=len(m.below[0]), k_above=len(m.above[0]),
+                table256=dict(kernel='k_joint_quant_chunk<4, 0, 1>', chunk_ms=stat('table256'),
+                              table_ms=stat('table256', 2)),
+                same_bytes_at_256=same, lpdf_err_over_tol=err, host_cand=n_host, gpu=torch.cuda.get_device_name(0))
+    for V in sorted(models):
+        line['large%d' % V] = dict(kernel='k_joint_quant_large_chunk<4, 0, 1>', chunk_ms=stat('large%d' % V),
+                                   mean_distinct_per_chunk=distinct[V])
+    text = json.dumps(line)
+    print(text)
+    out = args.out or os.path.join(ROOT, 'profiles', 'joint_quant_large_time.jsonl')
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, 'a') as f:
         f.write(text + '\n')
@@ -1363,6 +1459,7 @@ def main():
     ap.add_argument('--host-cand', type=int, default=None)
     ap.add_argument('--mixed', action='store_true')
     ap.add_argument('--quant', action='store_true')
+    ap.add_argument('--quant-large', action='store_true')
     ap.add_argument('--wide', action='store_true')
     ap.add_argument('--wide-mixed', action='store_true')
     ap.add_argument('--wide-quant', action='store_true')
@@ -1374,6 +1471,8 @@ def main():
     ap.add_argument('--batch', type=int, default=64)
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
+    if args.quant_large:
+        return main_quant_large(args)
     if (args.mixed or args.quant) and args.fp64:
         return main_mq_fp64(args)
     if args.mixed:
